@@ -12,7 +12,11 @@ with 8 GPUs is configs[2] (batch 64, data parallel).
 Multi-GPU: one process per GPU (torchrun), pages sharded by index, no data-path
 collective; a CPU gloo group only provides the barrier and the max-over-ranks time.
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the steps and prints the line
+(`roofline`, `cpu_baseline` and the host-prepare figure are null); `--full` adds the measurements that take
+runs of their own after the timed region: the decode rooflines (span / event / profile_decode generates), the
+dots tower's attention-timed page and the CPU baseline.  `--dump-outputs DIR` writes what the last timed step
+returned to its caller as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -118,6 +122,29 @@ def pmc_traffic(kernel_prefix, runs=None):
                     return v["priced_hbm_bytes_per_launch"], v.get("traffic_over_algorithmic")
                 return v.get("hbm_bytes_per_launch"), None
     return None, None
+
+
+DUMP_MAX_BYTES = 64 << 20  # --dump-outputs writes at most this much in all
+
+
+def dump_name(name, rank, world):
+    return name if world == 1 else f"{name}_rank{rank}"
+
+
+def dump_array(d, name, arr):
+    """--dump-outputs: one output of the last timed step as DIR/<name>.npy (float32 stays, anything else becomes
+    float64); an array over the budget is cut to a fixed seeded sample of its rows (sorted, so row order holds)."""
+    import numpy as np
+    a = np.asarray(arr)
+    a = np.ascontiguousarray(a if a.dtype == np.float32 else a.astype(np.float64))
+    if a.nbytes > DUMP_MAX_BYTES:
+        rows = a.reshape(a.shape[0], -1) if a.ndim > 1 else a.reshape(-1, 1)
+        keep = max(1, DUMP_MAX_BYTES // (rows.shape[1] * a.itemsize))
+        pick = np.sort(np.random.default_rng(0).choice(rows.shape[0], size=min(keep, rows.shape[0]), replace=False))
+        a = np.ascontiguousarray(rows[pick])
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, name + ".npy"), a)
+    log(f"[bench] --dump-outputs: {name}.npy {a.dtype} {list(a.shape)}")
 
 
 def cpu_model():
@@ -363,18 +390,15 @@ def run_dots(args, rank, world, local, dist):
     elapsed = time.perf_counter() - t0
     elapsed, _ = reduce_over_ranks(dist, elapsed, 0.0)
     value = args.steps * ppg * world / elapsed
+    if args.dump_outputs:  # the merged rows of the last timed page (what embed_device leaves in `out`)
+        rows = np.empty((groups, eng.hidden), np.float32)
+        check(L.dsocr_memcpy_d2h(rows.ctypes.data_as(C.c_void_p), out, rows.nbytes))
+        dump_array(args.dump_outputs, dump_name("embeddings", rank, world), rows)
     if rank != 0:
         return None
-    # one more page with its first 4 layers' attention timed alone (events around each launch)
-    eng.embed_device(pages[-1][0][0], pages[-1][0][1], out, time_attention_layers=4)
-    tm = eng.last_timings()
-    gemm_f, attn_f, other_f = dots_flops(cfg, N)
-    attn_layer_ms = tm["attention_ms"] / 4
-    attn_tf = (attn_f / cfg["num_hidden_layers"]) / (attn_layer_ms * 1e-3) / 1e12
-    planes = 2 if os.environ.get("DSOCR_DOTS_PV_PLANES") == "2" else 3
-    issue = (1 + planes) / 2.0
     page_ms = elapsed / (args.steps * ppg) * 1e3
-    return {
+    planes = 2 if os.environ.get("DSOCR_DOTS_PV_PLANES") == "2" else 3
+    res = {
         "metric": "pages/sec, dots.ocr bf16 vision tower, 2048px page (BASELINE configs[3])",
         "value": round(value, 4), "unit": "pages/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
         "ms_per_step": round(elapsed / args.steps * 1e3, 2), "higher_is_better": True, "scaling": "weak",
@@ -388,6 +412,20 @@ def run_dots(args, rank, world, local, dist):
                                f"{grid[1] * 14}x{grid[2] * 14}), grid {grid[1]}x{grid[2]}, "
                                f"{N} patch tokens, {groups} output rows", "pages_per_gpu": ppg,
                    "global_batch": ppg * world, "parallelism": f"dp{world}"},
+        "stage_ms": {"page_ms": round(page_ms, 2)},
+        "roofline": None,
+        "cpu_baseline": None,
+    }
+    if not args.full:
+        return res
+    # --full: one more page with its first 4 layers' attention timed alone (events around each launch)
+    eng.embed_device(pages[-1][0][0], pages[-1][0][1], out, time_attention_layers=4)
+    tm = eng.last_timings()
+    gemm_f, attn_f, other_f = dots_flops(cfg, N)
+    attn_layer_ms = tm["attention_ms"] / 4
+    attn_tf = (attn_f / cfg["num_hidden_layers"]) / (attn_layer_ms * 1e-3) / 1e12
+    issue = (1 + planes) / 2.0
+    res.update({
         "stage_ms": {"page_ms": round(page_ms, 2), "blocks_ms": round(tm["blocks_ms"], 2),
                      "patch_ms": round(tm["patch_ms"], 2), "merger_ms": round(tm["merger_ms"], 2)},
         # achieved = the reference's attention FLOPs (QK^T + P.V, f32 math) / the kernel's time; the kernel
@@ -404,8 +442,8 @@ def run_dots(args, rank, world, local, dist):
                      "flops_per_launch": attn_f / cfg["num_hidden_layers"],
                      "tower_tflops_total": round((gemm_f + attn_f + other_f) / 1e12, 2),
                      "tower_achieved_tflops": round((gemm_f + attn_f + other_f) / (page_ms * 1e-3) / 1e12, 2)},
-        "cpu_baseline": None,
-    }
+    })
+    return res
 
 
 def chain_roofline(chain, waves, d, B, P):
@@ -607,13 +645,21 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--pages-per-gpu", type=int, default=1)
     ap.add_argument("--max-new-tokens", type=int, default=512)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also take the measurements that need runs of their own: the decode "
+                         "rooflines, the dots tower's attention-timed page, the host-prepare figure and the CPU "
+                         "baseline (a plain run reports them as null)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step returned as DIR/<name>.npy (deepseek: tokens.npy, the "
+                         "generated ids [pages][max_new_tokens] as float64; dots2048: embeddings.npy, the merged "
+                         "rows of the last page as float32; with several ranks <name>_rank<r>.npy each)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-decode-steps", type=int, default=0, help="(unused: the C++ baseline times every decode step)")
     ap.add_argument("--roofline-iters", type=int, default=20)
     ap.add_argument("--no-chain-roofline", action="store_true",
                     help="skip the per-layer launch chain's roofline beside the persistent decode's (one page)")
     ap.add_argument("--trace-only", action="store_true",
-                    help="production-only run for a rocprofv3 kernel trace: the timed generates and nothing else "
+                    help="with --full: the timed generates and nothing else, for a rocprofv3 kernel trace "
                          "(no span / event / profile_decode generates, no CPU baseline); roofline is null")
     ap.add_argument("--workload", default="deepseek", choices=["deepseek", "dots2048"],
                     help="deepseek: configs[1]/[2] (default); dots2048: configs[3], the dots.ocr vision tower")
@@ -716,10 +762,11 @@ def main():
     params = DecodeParameters(max_new_tokens=args.max_new_tokens)
     batches = [make_batch(s) for s in range(args.warmup + args.steps)]
     gpu_prep_ms = prep_gpu_s[0] * 1e3 / max(1, len(batches) * ppg)
-    t = time.time()
-    if not args.text_pages:
+    prep_ms = None
+    if args.full and not args.text_pages:
+        t = time.time()
         Page(synthetic_page(0), vs)  # the host C++ path on the same page, for the report
-    prep_ms = (time.time() - t) * 1e3
+        prep_ms = (time.time() - t) * 1e3
     for s in range(args.warmup):
         eng.generate_batch(batches[s][1], params, ignore_eos=True)
 
@@ -732,6 +779,8 @@ def main():
         timings.append(eng.last_timings())
     barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:  # the ids the last timed generate_batch returned, one row per page of this rank
+        dump_array(args.dump_outputs, dump_name("tokens", rank, world), np.asarray(out, np.int64))
     iterative_s = sum(t["decode_iterative_ms"] for t in timings) / 1e3
     stage = {k: sum(t[k] for t in timings) / len(timings)
              for k in ("vision_compute_ms", "decode_prefill_ms", "decode_iterative_ms", "vision_flops", "prefill_flops")}
@@ -746,7 +795,7 @@ def main():
         log(f"[bench] timed: {value:.4f} pages/s, {tok_s:.1f} decode tok/s, stages "
             + ", ".join(f"{k} {stage[k]:.2f}" for k in ("vision_compute_ms", "decode_prefill_ms", "decode_iterative_ms")))
         roofline = None
-        if not args.trace_only:
+        if args.full and not args.trace_only:
             if eng.persist_info()["used"] and ppg == 1:  # the timed generates ran the persistent decode
                 roofline = persist_roofline(eng, batches[args.warmup][1], params, ppg, args)
                 if not args.no_chain_roofline:  # the per-layer launch chain's line, same page (DSOCR_PERSIST=0)
@@ -756,7 +805,8 @@ def main():
             else:
                 roofline = decode_roofline(eng, batches[args.warmup][1], params, ppg, args)
         cpu = None
-        if world == 1 and not (args.no_cpu_baseline or args.trace_only) and not snap and not args.text_pages:
+        if (args.full and world == 1 and not (args.no_cpu_baseline or args.trace_only) and not snap
+                and not args.text_pages):
             b = batches[args.warmup]
             try:
                 cpu = cpu_baseline(b[0], b[1][0][0], b[1][0][1], args.max_new_tokens, args.cpu_decode_steps)
@@ -803,7 +853,7 @@ def main():
                                             ("prefill", stage["prefill_flops"], stage["decode_prefill_ms"], 5))
                 if fl > 0 and ms > 0},
             "snapshot": snap,
-            "host_prepare_ms_per_page": round(prep_ms, 2),
+            "host_prepare_ms_per_page": None if prep_ms is None else round(prep_ms, 2),
             "gpu_prepare_ms_per_page": round(gpu_prep_ms, 2),
             "roofline": roofline,
             "cpu_baseline": cpu,

@@ -104,6 +104,68 @@ def test_two_rank_bench_process_run(gpu):
     assert abs(res["value"] - 2 / (res["ms_per_step"] / 1e3)) < 1e-3 * res["value"] + 1e-3
 
 
+def test_dump_array_formats_and_budget(tmp_path):
+    """bench.dump_array (--dump-outputs): ids become float64 exactly, float32 stays float32, and an array over
+    the budget is cut to the same seeded, ordered sample of its rows on every call."""
+    import numpy as np
+    ids = np.array([[129279, 0, 5], [7, 2**31 + 1, 9]], np.int64)
+    bench.dump_array(str(tmp_path / "a"), "tokens", ids)
+    got = np.load(tmp_path / "a" / "tokens.npy")
+    assert got.dtype == np.float64 and got.shape == (2, 3) and np.array_equal(got.astype(np.int64), ids)
+    rows = np.arange(64 * 8, dtype=np.float32).reshape(64, 8)
+    bench.dump_array(str(tmp_path / "a"), "whole", rows)
+    assert np.array_equal(np.load(tmp_path / "a" / "whole.npy"), rows)
+    budget, bench.DUMP_MAX_BYTES = bench.DUMP_MAX_BYTES, 10 * 8 * 4 + 5  # room for 10 rows
+    try:
+        bench.dump_array(str(tmp_path / "a"), "cut", rows)
+        bench.dump_array(str(tmp_path / "b"), "cut", rows)
+    finally:
+        bench.DUMP_MAX_BYTES = budget
+    cut = np.load(tmp_path / "a" / "cut.npy")
+    assert cut.dtype == np.float32 and cut.shape == (10, 8) and cut.nbytes <= 10 * 8 * 4 + 5
+    assert np.array_equal(cut, np.load(tmp_path / "b" / "cut.npy"))
+    first = (cut[:, 0] / 8).astype(int)
+    assert np.all(np.diff(first) > 0) and np.array_equal(cut, rows[first])
+    assert bench.dump_name("tokens", 0, 1) == "tokens" and bench.dump_name("tokens", 1, 2) == "tokens_rank1"
+
+
+@pytest.mark.gpu
+@pytest.mark.timeout(300)
+def test_plain_bench_line_and_dumped_outputs(gpu, tmp_path):
+    """A plain `bench.py --gpus 1 --steps N --warmup W` times exactly N steps and takes none of the --full
+    measurements (roofline, cpu_baseline, host prepare: null); --dump-outputs writes the ids the last timed step
+    returned, and they are what the engine generates for that step's page (page index warmup + steps - 1)."""
+    import json
+    import subprocess
+
+    import numpy as np
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+           "--max-new-tokens", "8", "--dump-outputs", str(tmp_path / "dump")]
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    out = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=280)
+    assert out.returncode == 0, out.stderr[-3000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, out.stdout[-2000:]
+    res = json.loads(lines[0])
+    assert res["steps"] == 2 and res["warmup"] == 1 and res["unit"] == "pages/s" and res["higher_is_better"] is True
+    assert res["ms_per_step"] > 0 and abs(res["value"] - 1e3 / res["ms_per_step"]) < 1e-3 * res["value"] + 1e-3
+    assert res["roofline"] is None and res["cpu_baseline"] is None and res["host_prepare_ms_per_page"] is None
+    assert "[cpu]" not in out.stderr
+    assert os.listdir(tmp_path / "dump") == ["tokens.npy"]
+    tokens = np.load(tmp_path / "dump" / "tokens.npy")
+    assert tokens.dtype == np.float64 and tokens.shape == (1, 8)
+
+    import dsocr
+    from dsocr import DecodeParameters, ModelLoadArgs, Page, VisionSettings, build_prompt_tokens, load_model
+    from dsocr.synth import BENCH_PROMPT, SyntheticTokenizer, synthetic_page
+    eng = load_model(ModelLoadArgs(config_path=dsocr.FULL_CONFIG, synthetic_seed=0, dtype="f16", device=0))
+    page = Page(synthetic_page(bench.page_indices(2, 1, 0, 1)[0]), VisionSettings(1024, 640, True), eng)
+    ids, mask = build_prompt_tokens(SyntheticTokenizer(eng.vocab), BENCH_PROMPT, [page.n_image_tokens])
+    want = eng.generate_batch([(ids, mask, page, None)], DecodeParameters(max_new_tokens=8), ignore_eos=True)
+    eng.close()
+    assert tokens.astype(np.int64).tolist() == want
+
+
 def test_span_roofline_prices_each_launch():
     """bench.span_roofline: every recorded launch priced from its own expert count (gate/up, down) or
     step (attention), achieved = sum(bytes) / sum(durations); empty slots ignored."""
