@@ -350,8 +350,7 @@ void DotsVision::embed_device(const float* d_patches, int gt, int gh, int gw, fl
     void* GU = swiglu_fused_ ? nullptr : ws("d_gu", (size_t)N * 2 * I * 2);
     void* HB = ws("d_h", (size_t)N * I * 2);
     void* PB = ws("d_pb", (size_t)N * patch_kp_ * 2);
-    hipEvent_t ev[4];
-    for (auto& e : ev) HIP_CHECK(hipEventCreate(&e));
+    HipEvent ev[4];
     HIP_CHECK(hipEventRecord(ev[0], st));
     // patch embed (DotsPatchEmbed::forward 256-261): pixels in the model dtype, conv as a GEMM, + bias, RMSNorm
     launch_dots_to_bf16(d_patches, N, patch_k_, patch_k_, PB, patch_kp_, st);
@@ -359,9 +358,7 @@ void DotsVision::embed_device(const float* d_patches, int gt, int gh, int gw, fl
     launch_dots_rmsnorm(X, 0, N, D, patch_norm_, (float)c_.eps, X, st);
     HIP_CHECK(hipEventRecord(ev[1], st));
     float attn_ms = 0.f;
-    hipEvent_t a0, a1;
-    HIP_CHECK(hipEventCreate(&a0));
-    HIP_CHECK(hipEventCreate(&a1));
+    HipEvent a0, a1;
     for (int l = 0; l < c_.layers; ++l) {
         const Block& b = blocks_[l];
         // DotsVisionBlock::forward (305-315) / VisionAttention::forward (364-431)
@@ -390,8 +387,10 @@ void DotsVision::embed_device(const float* d_patches, int gt, int gh, int gw, fl
         a.o = CTXb; a.o_rs = D; a.o_hs = hd; a.o_bf16 = 1;
         a.n_seq = gt; a.L = (int)per; a.heads = H; a.kv_heads = H; a.hd = hd; a.scale = scale;
         a.pv_planes = dots_pv_planes();
-        if (timed) prof_events() = ProfEvents{a0, a1};  // the launch's own dispatch timestamps
-        launch_attention_bf16(a, st);
+        {  // timed: the launch's own dispatch timestamps
+            ScopedSet timing(prof_events(), timed ? ProfEvents{a0, a1} : ProfEvents());
+            launch_attention_bf16(a, st);
+        }
         if (timed) {
             HIP_CHECK(hipEventSynchronize(a1));
             float ms = 0.f;
@@ -429,9 +428,6 @@ void DotsVision::embed_device(const float* d_patches, int gt, int gh, int gw, fl
     t_.tokens = N;
     t_.groups = groups;
     t_.total_ms = std::chrono::duration<double, std::milli>(clock::now() - t0).count();
-    for (auto& e : ev) (void)hipEventDestroy(e);
-    (void)hipEventDestroy(a0);
-    (void)hipEventDestroy(a1);
 }
 
 std::vector<float> DotsVision::embed(const DotsPatches& p) {

@@ -321,8 +321,7 @@ void Engine::prepare_page_device(const uint8_t* rgb, int w, int h, PagePixels& p
 Engine::~Engine() {
     if (stream_) (void)hipStreamSynchronize(stream_);
     if (vstream_) (void)hipStreamSynchronize(vstream_);
-    for (auto& e : span_ev_) (void)hipEventDestroy(e);
-    for (auto& e : vis_ev_)
+    for (auto& e : vis_ev_)  // (span_ev_ and persist_ev_ own their events)
         if (e) (void)hipEventDestroy(e);
     for (auto& kv : pinned_) (void)hipHostFree(kv.second.first);
     for (auto& kv : winmaps_) { (void)hipFree(kv.second.first); (void)hipFree(kv.second.second); }
@@ -853,6 +852,31 @@ float* Engine::vision_pass(const float* imgs, int n, int Spx, const std::string&
     return post;
 }
 
+// row kinds of launch_assemble_rows: token embedding, caller-supplied image row, vision row, the two markers
+enum RowKind : int { ROW_TOKEN = 0, ROW_HOST = 1, ROW_VISION = 2, ROW_NEWLINE = 3, ROW_SEPARATOR = 4 };
+
+// The <image> slots of a page in prompt order, as (kind, index into the page's [local | global] vision rows):
+// format_local_tokens (model/mod.rs:677-709) walks the tile grid row by row with a newline after each, then
+// format_global_tokens (656-675) the global view likewise, then the separator
+static std::vector<std::pair<int, long>> image_row_order(const PagePixels& pg) {
+    std::vector<std::pair<int, long>> seq;
+    const int ls = pg.tile / 64, gs = pg.gsize / 64;
+    const long n_local = pg.n_tiles > 0 ? (long)pg.n_tiles * ls * ls : 0;
+    for (int R = 0; n_local && R < pg.crop_h * ls; ++R) {
+        for (int Cc = 0; Cc < pg.crop_w * ls; ++Cc) {
+            const int crop = (R / ls) * pg.crop_w + (Cc / ls);
+            seq.push_back({ROW_VISION, ((long)crop * ls + R % ls) * ls + Cc % ls});
+        }
+        seq.push_back({ROW_NEWLINE, 0});
+    }
+    for (int R = 0; R < gs; ++R) {
+        for (int Cc = 0; Cc < gs; ++Cc) seq.push_back({ROW_VISION, n_local + (long)R * gs + Cc});
+        seq.push_back({ROW_NEWLINE, 0});
+    }
+    seq.push_back({ROW_SEPARATOR, 0});
+    return seq;
+}
+
 std::vector<std::vector<float>> Engine::image_embeddings(const std::vector<const PagePixels*>& pages) {
     std::vector<std::vector<float>> result;
     const int H = cfg_.proj_out;
@@ -877,21 +901,12 @@ std::vector<std::vector<float>> Engine::image_embeddings(const std::vector<const
         HIP_CHECK(hipMemcpy(nl.data(), newline_, H * 4, hipMemcpyDeviceToHost));
         HIP_CHECK(hipMemcpy(sp.data(), separator_, H * 4, hipMemcpyDeviceToHost));
         std::vector<float> rows;
-        auto push = [&](const float* r) { rows.insert(rows.end(), r, r + H); };
-        if (p->n_tiles > 0) {  // format_local_tokens (model/mod.rs:677-709)
-            for (int R = 0; R < p->crop_h * ls; ++R) {
-                for (int Cc = 0; Cc < p->crop_w * ls; ++Cc) {
-                    int crop = (R / ls) * p->crop_w + (Cc / ls);
-                    push(&lh[(((size_t)crop * ls + R % ls) * ls + Cc % ls) * H]);
-                }
-                push(nl.data());
-            }
+        const size_t n_local = lh.size() / H;
+        for (const auto& [kind, i] : image_row_order(*p)) {
+            const float* r = kind == ROW_NEWLINE ? nl.data() : kind == ROW_SEPARATOR ? sp.data()
+                             : (size_t)i < n_local ? &lh[i * H] : &gh[(i - n_local) * H];
+            rows.insert(rows.end(), r, r + H);
         }
-        for (int R = 0; R < gs; ++R) {  // format_global_tokens (656-675)
-            for (int Cc = 0; Cc < gs; ++Cc) push(&gh[((size_t)R * gs + Cc) * H]);
-            push(nl.data());
-        }
-        push(sp.data());
         result.push_back(std::move(rows));
     }
     return result;
@@ -1041,6 +1056,34 @@ MoeDecodeArgs Engine::moe_args(int l, int B, float* X) {
     return a;
 }
 
+// Decode attention arguments of layer l (shared by decode_step and profile_decode, which points q/k/v, the
+// position and the output at scratch rows): RoPE + K/V append + flash-decoding on the named workspaces
+DecAttn2Args Engine::attn_args(int l, int B, int Lmax) {
+    const LangConfig& L = cfg_.lang;
+    const int hd = L.head_dim, QKVN = layers_[l].qkv.N;
+    const long layer_kv = (long)B * page_stride_;
+    DecAttn2Args da;
+    da.qkv = wsf("s_qkv", (size_t)B * QKVN); da.ld = QKVN; da.kv_pos = wsi("s_kvpos", B); da.B = B;
+    da.heads = L.heads; da.kv_heads = L.kv_heads; da.hd = hd; da.rope_dim = L.rope_dim; da.use_mla = L.use_mla;
+    da.max_len = Lmax; da.cos = rope_cos_; da.sin = rope_sin_;
+    da.kc = kc_ + (long)l * layer_kv; da.vc = vc_ + (long)l * layer_kv;
+    da.page_stride = page_stride_; da.head_stride = head_stride_;
+    da.scale = (float)(1.0 / std::sqrt((double)hd));
+    da.part = wsf("s_part", dec_attn_workspace(B, L.heads, hd, Lmax) / 4 + 16);
+    da.o = wsf("s_ctx", (size_t)B * L.hidden); da.o_ld = L.hidden;
+    da.counters = wsi("s_attn_cnt", (size_t)B * L.heads);
+    da.err = wsi("s_err", 4);
+    return da;
+}
+
+// DSOCR_NO_GRAPH=1 (read per generate and per profile section): the decode step's kernels launched eagerly
+// instead of replayed from a hipGraph (rocprofv3 kernel tracing of graph replays is unreliable on this stack;
+// kernel durations are unchanged)
+static bool graphs_on() {
+    const char* e = getenv("DSOCR_NO_GRAPH");
+    return !(e && atoi(e) != 0);
+}
+
 bool Engine::persist_ok(int B, int Lmax) {
     // opt-in (DSOCR_PERSIST=1, read per generate): measured slower than the per-layer launch chain on MI355X
     // (43.5 vs 33.5 us per layer), kept as the A/B of the persistent-layer design
@@ -1138,7 +1181,6 @@ void Engine::decode_step(int B, int Lmax) {
     float* XN = wsf("s_xn", (size_t)B * H);
     int* kv_pos = wsi("s_kvpos", B);
     float* CTX = wsf("s_ctx", (size_t)B * H);
-    float* part = wsf("s_part", dec_attn_workspace(B, L.heads, hd, Lmax) / 4 + 16);
     if (L.heads % L.kv_heads) throw std::runtime_error("EINVAL: num_attention_heads must be a multiple of num_key_value_heads");
     int* err = wsi("s_err", 4);
     if (B == 1 && persist_active_ && !step_skip_ && !span_rec_) {
@@ -1150,18 +1192,12 @@ void Engine::decode_step(int B, int Lmax) {
         pa.scale = (float)(1.0 / std::sqrt((double)hd)); pa.eps = L.rms_eps;
         pa.softmax_scoring = L.scoring == "softmax"; pa.norm_topk = L.norm_topk; pa.scaling = L.routed_scaling;
         pa.g = persist_g_; pa.err = err;
-        if (persist_stamp_mode_ && !persist_ev_.empty() && persist_stamps_) {
-            pa.stamps = persist_stamps_;
-            pa.stamp_pos0 = persist_stamp_pos0_;
-            pa.stamp_cap = persist_stamp_cap_;
-            // the launch's own dispatch begin / end (hipExtLaunchKernelGGL events: what rocprofv3's kernel trace
-            // reports); the timed generate runs its steps eagerly (events on a dispatch packet cannot be captured)
-            prof_events() = ProfEvents{persist_ev_[0], persist_ev_[1]};
-            launch_dec_persist(pa, st);
-            prof_events() = ProfEvents();
-        } else {
-            launch_dec_persist(pa, st);
-        }
+        const bool stamp = persist_stamp_mode_ && !persist_ev_.empty() && persist_stamps_;
+        if (stamp) { pa.stamps = persist_stamps_; pa.stamp_pos0 = persist_stamp_pos0_; pa.stamp_cap = persist_stamp_cap_; }
+        // stamped: the launch's own dispatch begin / end (hipExtLaunchKernelGGL events: what rocprofv3's kernel trace
+        // reports); the timed generate runs its steps eagerly (events on a dispatch packet cannot be captured)
+        ScopedSet pe(prof_events(), stamp ? ProfEvents{persist_ev_[0], persist_ev_[1]} : ProfEvents());
+        launch_dec_persist(pa, st);
         return;
     }
     // launch spans (set_spans): HIP events on the stream around the launch (dispatch-level duration,
@@ -1171,7 +1207,7 @@ void Engine::decode_step(int B, int Lmax) {
             launch();
             return;
         }
-        hipEvent_t* ev = &span_ev_[((size_t)kind * L.layers + l) * 2];
+        const HipEvent* ev = &span_ev_[((size_t)kind * L.layers + l) * 2];
         const bool events = (span_mode_ & SPAN_EVENTS) != 0, waves = (span_mode_ & SPAN_WAVES) != 0;
         if (events) HIP_CHECK(hipEventRecord(ev[0], st));
         launch();
@@ -1185,17 +1221,8 @@ void Engine::decode_step(int B, int Lmax) {
         DecLayer& d = layers_[l];
         const int QKVN = d.qkv.N;
         float* QKV = wsf("s_qkv", (size_t)B * QKVN);
-        const long layer_kv = (long)B * page_stride_;
         // attention: [norm] qkv -> rope + append + flash-decoding -> o_proj + residual
-        DecAttn2Args da;
-        da.qkv = QKV; da.ld = QKVN; da.kv_pos = kv_pos; da.B = B; da.heads = L.heads; da.kv_heads = L.kv_heads;
-        da.hd = hd; da.rope_dim = L.rope_dim; da.use_mla = L.use_mla; da.max_len = Lmax;
-        da.cos = rope_cos_; da.sin = rope_sin_;
-        da.kc = kc_ + (long)l * layer_kv; da.vc = vc_ + (long)l * layer_kv;
-        da.page_stride = page_stride_; da.head_stride = head_stride_;
-        da.scale = (float)(1.0 / std::sqrt((double)hd)); da.part = part; da.o = CTX; da.o_ld = H;
-        da.counters = wsi("s_attn_cnt", (size_t)B * L.heads);
-        da.err = err;
+        DecAttn2Args da = attn_args(l, B, Lmax);
         da.kv_delay = att_kv_delay();
         da.span = chain_active_ ? chain_slots(l, SPAN_ATTN) : ((span_rec_ && (span_mode_ & SPAN_WAVES)) ? span_slots_ : nullptr);
         // q/k/v projection with the input RMSNorm fused; one page: RoPE in the projection's epilogue, so the
@@ -1448,34 +1475,81 @@ std::vector<uint32_t> rng_state_from_u64(uint64_t state) {
 }
 
 // ============================================================================ generate
+// One generate() call: what its phases hand to each other.  The events and the pinned buffer die with it.
+struct Engine::GenState {
+    GenState(const std::vector<GenRequest>& r, const GenParams& gp, TokenCb c, void* u)
+        : reqs(r), p(gp), cb(c), user(u), B((int)r.size()) {}
+    const std::vector<GenRequest>& reqs;
+    const GenParams& p;
+    TokenCb cb;
+    void* user;
+    const int B;
+    HipEvent ev[6];  // stream marks: vision [0, 1], prefill [2, 3], decode loop [4, 5]
+    std::vector<int> prompt_len;
+    int max_p = 0, Lmax = 0;
+    std::vector<const float*> gpost, lpost;              // per page: its global / local post rows (device)
+    std::vector<float> host_rows;                        // caller-supplied image rows of every page (ROW_HOST)
+    float* vis_rows = nullptr;                           // every page's [local | global] post rows, contiguous
+    std::vector<std::vector<std::pair<int, long>>> img;  // per page: (kind, index) of every <image> slot
+    std::vector<std::vector<int>> extra;                 // per page: the tokens a forward without cache appends
+    float *SX = nullptr, *LOGITS = nullptr;
+    std::vector<int> kvpos, kvlen;                       // first decode position / cache length of every page
+    int *d_kvpos = nullptr, *d_kvlen = nullptr, *d_done = nullptr, *d_outlen = nullptr, *d_out = nullptr, *d_tok = nullptr;
+    SampleArgs pen;
+    DecSampleArgs sa;
+    PinnedBuffer<int> pin;  // poll(): [done | output length | last token] x B
+    int streamed = 0;       // tokens the stream callback has seen
+    size_t steps = 0;
+};
+
 std::vector<std::vector<int64_t>> Engine::generate(const std::vector<GenRequest>& reqs, const GenParams& p, TokenCb cb,
                                                    void* user) {
-    using clock = std::chrono::steady_clock;
-    const LangConfig& L = cfg_.lang;
-    const int B = (int)reqs.size();
-    const int H = L.hidden;
     timings_ = Timings();
-    timings_.pages = B;
-    std::vector<std::vector<int64_t>> out(B);
-    if (B == 0) return out;
-    if (p.max_new == 0) return out;
-    ensure_small(std::max(B, 64));
+    timings_.pages = reqs.size();
+    if (reqs.empty() || p.max_new == 0) return std::vector<std::vector<int64_t>>(reqs.size());
+    ensure_small(std::max((int)reqs.size(), 64));
+    GenState g(reqs, p, cb, user);
+    // what a running generate sets for decode_step / decode_head is back to idle on every exit, a throw included
+    // (profile_decode runs unstamped; every later generate is stamped again while span_mode_ is set)
+    ScopedSet idle_chain(chain_active_, false);
+    ScopedSet idle_rec(span_rec_, nullptr);
+    ScopedSet idle_step(span_step_, nullptr);
+    ScopedSet idle_slots(span_slots_, nullptr);
+    ScopedSet idle_trace(trace_, nullptr);
     hipStream_t st = stream_;
-    hipEvent_t ev[6];
-    for (auto& e : ev) HIP_CHECK(hipEventCreate(&e));
-    auto t0 = clock::now();
-    HIP_CHECK(hipEventRecord(ev[0], st));
+    HIP_CHECK(hipEventRecord(g.ev[0], st));
     flops_acc_ = 0;
+    embed_pages(g);
+    HIP_CHECK(hipEventRecord(g.ev[1], st));
+    timings_.vision_flops = flops_acc_;
+    plan_image_rows(g);
+    reset_decode_state(g);
+    HIP_CHECK(hipEventRecord(g.ev[2], st));
+    flops_acc_ = 0;
+    forward_rows(g, g.prompt_len);
+    init_sampling(g);
+    HIP_CHECK(hipEventRecord(g.ev[3], st));
+    timings_.prefill_flops = flops_acc_;
+    g.pin = PinnedBuffer<int>(3 * g.B + 1);
+    if (cb && g.B == 1) {
+        poll(g);
+        if (g.pin[g.B] > 0) stream_tokens(g, g.pin[g.B]);
+    }
+    if (p.use_cache) decode_cached(g);
+    else decode_uncached(g);
+    return collect_outputs(g);
+}
 
-    // ---------------- 1. vision (compute_image_embeddings, batched over pages)
-    std::vector<int> prompt_len(B);
-    int max_p = 0;
-    long T = 0;
+// ---------------- 1. vision (compute_image_embeddings, batched over pages): g.gpost / g.lpost
+void Engine::embed_pages(GenState& g) {
+    const std::vector<GenRequest>& reqs = g.reqs;
+    const int B = g.B, H = cfg_.lang.hidden;
+    hipStream_t st = stream_;
+    g.prompt_len.resize(B);
     for (int b = 0; b < B; ++b) {
-        prompt_len[b] = (int)reqs[b].ids.size();
-        if (prompt_len[b] == 0) throw std::runtime_error("EINVAL: empty prompt");
-        max_p = std::max(max_p, prompt_len[b]);
-        T += prompt_len[b];
+        g.prompt_len[b] = (int)reqs[b].ids.size();
+        if (g.prompt_len[b] == 0) throw std::runtime_error("EINVAL: empty prompt");
+        g.max_p = std::max(g.max_p, g.prompt_len[b]);
     }
     // group pages by global/tile size
     std::map<int, std::vector<int>> gsz, tsz;
@@ -1484,15 +1558,13 @@ std::vector<std::vector<int64_t>> Engine::generate(const std::vector<GenRequest>
             gsz[reqs[b].page->gsize].push_back(b);
             if (reqs[b].page->n_tiles > 0) tsz[reqs[b].page->tile].push_back(b);
         }
-    // per page: device pointers of global post rows and local post rows
-    std::vector<const float*> gpost(B, nullptr), lpost(B, nullptr);
-    std::vector<float*> pass_outputs;
+    g.gpost.assign(B, nullptr);
+    g.lpost.assign(B, nullptr);
     int pass_id = 0;
     // pixels of one size group as one contiguous device batch: device-to-device gathers of
     // HBM-resident pages (dsocr_page_to_device / dsocr_prepare_page_device), host uploads otherwise
     auto gather = [&](const std::vector<int>& pages, bool tiles, size_t n_floats) -> float* {
-        const std::string name = "g_img" + std::to_string(pass_id);
-        float* d = wsf(name, n_floats);
+        float* d = wsf("g_img" + std::to_string(pass_id++), n_floats);
         size_t off = 0;
         bool host_copy = false;
         for (int b : pages) {
@@ -1500,14 +1572,14 @@ std::vector<std::vector<int64_t>> Engine::generate(const std::vector<GenRequest>
             const size_t nf = tiles ? (size_t)pg.n_tiles * 3 * pg.tile * pg.tile : (size_t)3 * pg.gsize * pg.gsize;
             const float* dev = tiles ? pg.tiles_dev : pg.global_dev;
             const std::vector<float>& host = tiles ? pg.tiles_chw : pg.global_chw;
-            if (dev && pg.dev_ordinal == device_)
+            if (dev && pg.dev_ordinal == device_) {
                 HIP_CHECK(hipMemcpyAsync(d + off, dev, nf * 4, hipMemcpyDeviceToDevice, st));
-            else if (host.size() == nf) {
+            } else if (host.size() == nf) {
                 HIP_CHECK(hipMemcpyAsync(d + off, host.data(), nf * 4, hipMemcpyHostToDevice, st));
                 host_copy = true;
-            }
-            else
+            } else {
                 throw std::runtime_error("EINVAL: page pixels live on another device");
+            }
             off += nf;
         }
         if (off != n_floats) throw std::runtime_error("EINTERNAL: pixel batch size mismatch");
@@ -1518,23 +1590,17 @@ std::vector<std::vector<int64_t>> Engine::generate(const std::vector<GenRequest>
     // (DSOCR_VIS_STREAMS=0: all on one stream), joined before the image rows are assembled
     std::vector<float*> g_img, t_img;
     std::vector<int> t_n;
-    for (auto& kv : gsz) {
-        const int S = kv.first;
-        g_img.push_back(gather(kv.second, false, kv.second.size() * 3 * (size_t)S * S));
-        ++pass_id;
-    }
+    for (auto& kv : gsz) g_img.push_back(gather(kv.second, false, kv.second.size() * 3 * (size_t)kv.first * kv.first));
     for (auto& kv : tsz) {
-        const int S = kv.first;
         int n = 0;
         for (int b : kv.second) n += reqs[b].page->n_tiles;
-        t_img.push_back(gather(kv.second, true, (size_t)n * 3 * S * S));
+        t_img.push_back(gather(kv.second, true, (size_t)n * 3 * kv.first * kv.first));
         t_n.push_back(n);
-        ++pass_id;
     }
     const bool two = vis_streams_on() && gsz.size() + tsz.size() >= 2;
     if (two && !vstream_) {
         HIP_CHECK(hipStreamCreateWithFlags(&vstream_, hipStreamNonBlocking));
-        for (auto& e : vis_ev_) HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        for (auto& e : vis_ev_) HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));  // (freed in ~Engine)
     }
     if (two) {
         HIP_CHECK(hipEventRecord(vis_ev_[0], st));  // pixels gathered
@@ -1545,115 +1611,94 @@ std::vector<std::vector<int64_t>> Engine::generate(const std::vector<GenRequest>
     auto run_pass = [&](float* dimg, int n, int S) -> float* {
         const std::string name = "vis_out" + std::to_string(vis_k);
         if (!two || (vis_k++ & 1) == 0) return vision_pass(dimg, n, S, name);
-        std::swap(stream_, vstream_);
-        ws_prefix_ = "vs1_";
-        float* r = nullptr;
-        try {
-            r = vision_pass(dimg, n, S, name);
-        } catch (...) {
-            std::swap(stream_, vstream_);
-            ws_prefix_.clear();
-            throw;
-        }
-        std::swap(stream_, vstream_);
-        ws_prefix_.clear();
+        // this pass alone on the second stream, with that stream's own workspaces
+        const hipStream_t first = stream_;
+        ScopedSet on_side(stream_, vstream_), off_side(vstream_, first);
+        ScopedSet prefix(ws_prefix_, "vs1_");
         side = true;
-        return r;
+        return vision_pass(dimg, n, S, name);
     };
-    {
-        size_t gi = 0;
-        for (auto& kv : gsz) {
-            const int S = kv.first;
-            float* post = run_pass(g_img[gi++], (int)kv.second.size(), S);
-            const int Sq = (S / 64) * (S / 64);
-            for (size_t i = 0; i < kv.second.size(); ++i) gpost[kv.second[i]] = post + (size_t)i * Sq * H;
-        }
-        size_t ti = 0;
-        for (auto& kv : tsz) {
-            const int S = kv.first;
-            float* post = run_pass(t_img[ti], t_n[ti], S);
-            ++ti;
-            const int Sq = (S / 64) * (S / 64);
-            size_t off = 0;
-            for (int b : kv.second) {
-                lpost[b] = post + off * Sq * H;
-                off += reqs[b].page->n_tiles;
-            }
+    size_t gi = 0, ti = 0;
+    for (auto& kv : gsz) {
+        const int S = kv.first, Sq = (S / 64) * (S / 64);
+        float* post = run_pass(g_img[gi++], (int)kv.second.size(), S);
+        for (size_t i = 0; i < kv.second.size(); ++i) g.gpost[kv.second[i]] = post + (size_t)i * Sq * H;
+    }
+    for (auto& kv : tsz) {
+        const int S = kv.first, Sq = (S / 64) * (S / 64);
+        float* post = run_pass(t_img[ti], t_n[ti], S);
+        ++ti;
+        size_t off = 0;
+        for (int b : kv.second) {
+            g.lpost[b] = post + off * Sq * H;
+            off += reqs[b].page->n_tiles;
         }
     }
     if (side) {
         HIP_CHECK(hipEventRecord(vis_ev_[1], vstream_));
         HIP_CHECK(hipStreamWaitEvent(st, vis_ev_[1], 0));
     }
-    HIP_CHECK(hipEventRecord(ev[1], st));
-    timings_.vision_flops = flops_acc_;
+}
 
-    // ---------------- 2. image rows for the injection (model/mod.rs:1208-1239)
-    // host image rows of all pages concatenated (kind 1), device vision rows via per-row pointers:
-    // we copy them into one contiguous device buffer per kind to keep the assemble kernel simple.
-    std::vector<float> host_rows;
+// ---------------- 2. image rows for the injection (model/mod.rs:1208-1239): g.host_rows (kind ROW_HOST),
+// g.vis_rows (one contiguous device buffer of every page's vision rows, to keep the assemble kernel simple)
+// and g.img; checks every prompt against its mask and the vocabulary
+void Engine::plan_image_rows(GenState& g) {
+    const std::vector<GenRequest>& reqs = g.reqs;
+    const int B = g.B, H = cfg_.lang.hidden;
+    hipStream_t st = stream_;
     std::vector<long> host_row_base(B, 0);
     for (int b = 0; b < B; ++b)
         if (!reqs[b].page && reqs[b].image_rows) {
-            host_row_base[b] = (long)(host_rows.size() / H);
-            host_rows.insert(host_rows.end(), reqs[b].image_rows, reqs[b].image_rows + reqs[b].n_image_rows * H);
+            host_row_base[b] = (long)(g.host_rows.size() / H);
+            g.host_rows.insert(g.host_rows.end(), reqs[b].image_rows, reqs[b].image_rows + reqs[b].n_image_rows * H);
         }
-    // device vision rows are gathered via srcB = one buffer holding every page's [local | global] post rows
     long vis_rows_total = 0;
     std::vector<long> vis_base(B, 0), vis_local_rows(B, 0), vis_global_rows(B, 0);
     for (int b = 0; b < B; ++b)
-        if (reqs[b].page) {
-            const PagePixels* pg = reqs[b].page;
+        if (const PagePixels* pg = reqs[b].page) {
             vis_base[b] = vis_rows_total;
             vis_local_rows[b] = (long)pg->n_tiles * (pg->tile / 64) * (pg->tile / 64);
             vis_global_rows[b] = (long)(pg->gsize / 64) * (pg->gsize / 64);
             vis_rows_total += vis_local_rows[b] + vis_global_rows[b];
         }
-    float* vis_rows = wsf("g_visrows", (size_t)std::max<long>(vis_rows_total, 1) * H);
+    g.vis_rows = wsf("g_visrows", (size_t)std::max<long>(vis_rows_total, 1) * H);
     for (int b = 0; b < B; ++b)
         if (reqs[b].page) {
             if (vis_local_rows[b])
-                HIP_CHECK(hipMemcpyAsync(vis_rows + vis_base[b] * H, lpost[b], vis_local_rows[b] * H * 4,
+                HIP_CHECK(hipMemcpyAsync(g.vis_rows + vis_base[b] * H, g.lpost[b], vis_local_rows[b] * H * 4,
                                          hipMemcpyDeviceToDevice, st));
-            HIP_CHECK(hipMemcpyAsync(vis_rows + (vis_base[b] + vis_local_rows[b]) * H, gpost[b],
+            HIP_CHECK(hipMemcpyAsync(g.vis_rows + (vis_base[b] + vis_local_rows[b]) * H, g.gpost[b],
                                      vis_global_rows[b] * H * 4, hipMemcpyDeviceToDevice, st));
         }
-    // image-row sequence of every page (format_local_tokens / format_global_tokens /
-    // assemble_artifacts order, model/mod.rs:656-709,879-923): (kind, index) per <image> slot
-    std::vector<std::vector<std::pair<int, long>>> img(B);
+    // image-row sequence of every page (assemble_artifacts order, model/mod.rs:879-923)
+    g.img.resize(B);
     for (int b = 0; b < B; ++b) {
         const GenRequest& rq = reqs[b];
         if (rq.page) {
-            const PagePixels* pg = rq.page;
-            if (pg->n_tiles > 0) {
-                const int ls = pg->tile / 64;
-                for (int R = 0; R < pg->crop_h * ls; ++R) {
-                    for (int Cc = 0; Cc < pg->crop_w * ls; ++Cc) {
-                        int crop = (R / ls) * pg->crop_w + (Cc / ls);
-                        img[b].push_back({2, vis_base[b] + ((long)crop * ls + R % ls) * ls + Cc % ls});
-                    }
-                    img[b].push_back({3, 0});
-                }
-            }
-            const int gs = pg->gsize / 64;
-            for (int R = 0; R < gs; ++R) {
-                for (int Cc = 0; Cc < gs; ++Cc) img[b].push_back({2, vis_base[b] + vis_local_rows[b] + (long)R * gs + Cc});
-                img[b].push_back({3, 0});
-            }
-            img[b].push_back({4, 0});
+            g.img[b] = image_row_order(*rq.page);
+            for (auto& r : g.img[b])
+                if (r.first == ROW_VISION) r.second += vis_base[b];
         } else if (rq.image_rows) {
-            for (size_t i = 0; i < rq.n_image_rows; ++i) img[b].push_back({1, host_row_base[b] + (long)i});
+            for (size_t i = 0; i < rq.n_image_rows; ++i) g.img[b].push_back({ROW_HOST, host_row_base[b] + (long)i});
         }
         size_t n_mask = 0;
-        for (int i = 0; i < prompt_len[b]; ++i) n_mask += (!rq.mask.empty() && rq.mask[i]) ? 1 : 0;
-        if (n_mask != img[b].size())
+        for (int i = 0; i < g.prompt_len[b]; ++i) n_mask += (!rq.mask.empty() && rq.mask[i]) ? 1 : 0;
+        if (n_mask != g.img[b].size())
             throw std::runtime_error("EINVAL: prompt/image embedding mismatch: image embeddings provide " +
-                                     std::to_string(img[b].size()) + " tokens but mask requires " + std::to_string(n_mask));
-        for (int i = 0; i < prompt_len[b]; ++i)
-            if ((rq.mask.empty() || !rq.mask[i]) && (rq.ids[i] < 0 || rq.ids[i] >= L.vocab))
+                                     std::to_string(g.img[b].size()) + " tokens but mask requires " + std::to_string(n_mask));
+        for (int i = 0; i < g.prompt_len[b]; ++i)
+            if ((rq.mask.empty() || !rq.mask[i]) && (rq.ids[i] < 0 || rq.ids[i] >= cfg_.lang.vocab))
                 throw std::runtime_error("EINVAL: token id out of bounds for vocab size");
     }
-    const int Lmax = max_p + (int)p.max_new + 1;
+}
+
+// KV cache sized for this call, the decode kernels' tickets zeroed and their polled rows sentinel-filled
+void Engine::reset_decode_state(GenState& g) {
+    const LangConfig& L = cfg_.lang;
+    const int B = g.B, H = L.hidden;
+    hipStream_t st = stream_;
+    const int Lmax = g.Lmax = g.max_p + (int)g.p.max_new + 1;
     ensure_rope(Lmax + 1);
     // KV cache [layers][B][kvh][Lmax][hd] f32 (block.rs:776-789 keeps the cache in f32)
     head_stride_ = (long)Lmax * L.head_dim;
@@ -1676,109 +1721,116 @@ std::vector<std::vector<int64_t>> Engine::generate(const std::vector<GenRequest>
     HIP_CHECK(hipMemsetAsync(wsi("s_dtick", dec_mm_splitk_ticks(H)), 0, sizeof(int) * dec_mm_splitk_ticks(H), st));
     HIP_CHECK(hipMemsetAsync(wsi("s_err", 4), 0, sizeof(int) * 4, st));  // fused-kernel give-up flag
     // one page: the persistent decode step (its granules: no tag of an earlier generate may match this one's)
-    persist_active_ = p.use_cache && persist_ok(B, Lmax);
+    persist_active_ = g.p.use_cache && persist_ok(B, Lmax);
     if (persist_active_) {
         ensure_persist();
         HIP_CHECK(hipMemsetAsync(persist_g_, 0xff, dec_persist_granules(L.layers) * 8, st));
     }
-    const int QKVN = layers_[0].qkv.N;
-    float* SX = wsf("s_x", (size_t)B * H);
-    float* SXN = wsf("s_xn", (size_t)B * H);
-    float* LOGITS = wsf("s_logits", (size_t)B * L.vocab);
+    g.SX = wsf("s_x", (size_t)B * H);
+    wsf("s_xn", (size_t)B * H);
+    g.LOGITS = wsf("s_logits", (size_t)B * L.vocab);
+    g.extra.resize(B);
+}
 
-    // ---------------- 3. the forward over whole token sequences (DeepseekOcrModel::forward,
-    // model/mod.rs:1181-1251): embed + inject (1208-1239), every layer, final norm + lm_head on the
-    // last row of each page (the reference projects every position, transformer/model.rs:243-270;
-    // only the last row is ever read).  The prefill runs it once on the prompts; use_cache = false
-    // (generate_without_cache, model/mod.rs:2051-2283) re-runs it on prompt + generated every step.
-    auto forward_rows = [&](const std::vector<int>& lens, const std::vector<std::vector<int>>& extra) {
-        long Tn = 0;
-        int maxl = 0;
-        for (int b = 0; b < B; ++b) { Tn += lens[b]; maxl = std::max(maxl, lens[b]); }
-        prefill_lens_ = lens;
-        std::vector<int> kind(Tn), index(Tn), row_page(Tn), row_pos(Tn);
-        std::vector<long> q_off(B), kv_off(B), o_off(B);
-        long r0 = 0;
-        for (int b = 0; b < B; ++b) {
-            const GenRequest& rq = reqs[b];
-            size_t j = 0;
-            for (int i = 0; i < lens[b]; ++i) {
-                const long r = r0 + i;
-                if (i < prompt_len[b] && !rq.mask.empty() && rq.mask[i]) {
-                    kind[r] = img[b][j].first;
-                    index[r] = (int)img[b][j].second;
-                    ++j;
-                } else {
-                    kind[r] = 0;
-                    index[r] = i < prompt_len[b] ? rq.ids[i] : extra[b][i - prompt_len[b]];
-                }
-                row_page[r] = b;
-                row_pos[r] = i;
-            }
-            q_off[b] = r0 * QKVN;
-            kv_off[b] = (long)b * page_stride_;
-            o_off[b] = r0 * H;
-            r0 += lens[b];
-        }
-        float* X = wsf("d_x", (size_t)Tn * H);
-        int* dk = upload("g_kind", kind);
-        int* di = upload("g_index", index);
-        float* hr = host_rows.empty() ? nullptr : upload("g_hostrows", host_rows);
-        launch_assemble_rows(dk, di, (int)Tn, H, embed_, embed_dt_, hr, vis_rows, newline_, separator_, X, H, st);
-        int* d_row_page = upload("g_rowpage", row_page);
-        int* d_row_pos = upload("g_rowpos", row_pos);
-        long* d_q_off = upload("g_qoff", q_off);
-        long* d_kv_off = upload("g_kvoff", kv_off);
-        long* d_o_off = upload("g_ooff", o_off);
-        int* d_plen = upload("g_plen", lens);
-        for (int l = 0; l < L.layers; ++l)
-            layer_forward_prefill(l, (int)Tn, B, d_row_page, d_row_pos, d_q_off, d_kv_off, d_o_off, d_plen, maxl, Lmax);
-        std::vector<int> last_rows(B), lr_kind(B, 1);
-        r0 = 0;
-        for (int b = 0; b < B; ++b) { r0 += lens[b]; last_rows[b] = (int)(r0 - 1); }
-        int* lk = upload("g_lrkind", lr_kind);
-        int* li = upload("g_lrindex", last_rows);
-        launch_assemble_rows(lk, li, B, H, nullptr, 0, X, nullptr, nullptr, nullptr, SX, H, st);
-        launch_rmsnorm(SX, H, SXN, H, B, H, final_norm_, L.rms_eps, st);
-        linear(SXN, B, H, lm_head_, LOGITS, L.vocab);
-    };
-    HIP_CHECK(hipEventRecord(ev[2], st));
-    flops_acc_ = 0;
-    std::vector<std::vector<int>> extra(B);
-    forward_rows(prompt_len, extra);
-
-    // sampling state: context = prompt ids (+ generated), sampling.rs:34-96
-    const long ctx_cap = max_p + (long)p.max_new + 1;
-    std::vector<int> ctx((size_t)B * ctx_cap, 0), ctx_len(B), kvpos(B), kvlen(B), zeros(B, 0);
+// ---------------- 3. the forward over whole token sequences (DeepseekOcrModel::forward,
+// model/mod.rs:1181-1251): embed + inject (1208-1239), every layer, final norm + lm_head on the
+// last row of each page (the reference projects every position, transformer/model.rs:243-270;
+// only the last row is ever read).  The prefill runs it once on the prompts; use_cache = false
+// (generate_without_cache, model/mod.rs:2051-2283) re-runs it on prompt + generated (g.extra) every step.
+void Engine::forward_rows(GenState& g, const std::vector<int>& lens) {
+    const LangConfig& L = cfg_.lang;
+    const int B = g.B, H = L.hidden, QKVN = layers_[0].qkv.N;
+    hipStream_t st = stream_;
+    long Tn = 0;
+    int maxl = 0;
+    for (int b = 0; b < B; ++b) { Tn += lens[b]; maxl = std::max(maxl, lens[b]); }
+    prefill_lens_ = lens;
+    std::vector<int> kind(Tn), index(Tn), row_page(Tn), row_pos(Tn);
+    std::vector<long> q_off(B), kv_off(B), o_off(B);
+    long r0 = 0;
     for (int b = 0; b < B; ++b) {
-        for (int i = 0; i < prompt_len[b]; ++i) ctx[(size_t)b * ctx_cap + i] = reqs[b].ids[i];
-        ctx_len[b] = prompt_len[b];
-        kvpos[b] = prompt_len[b];
-        kvlen[b] = prompt_len[b] + 1;
+        const GenRequest& rq = g.reqs[b];
+        const int plen = g.prompt_len[b];
+        size_t j = 0;
+        for (int i = 0; i < lens[b]; ++i) {
+            const long r = r0 + i;
+            if (i < plen && !rq.mask.empty() && rq.mask[i]) {
+                kind[r] = g.img[b][j].first;
+                index[r] = (int)g.img[b][j].second;
+                ++j;
+            } else {
+                kind[r] = ROW_TOKEN;
+                index[r] = i < plen ? rq.ids[i] : g.extra[b][i - plen];
+            }
+            row_page[r] = b;
+            row_pos[r] = i;
+        }
+        q_off[b] = r0 * QKVN;
+        kv_off[b] = (long)b * page_stride_;
+        o_off[b] = r0 * H;
+        r0 += lens[b];
     }
+    float* X = wsf("d_x", (size_t)Tn * H);
+    int* dk = upload("g_kind", kind);
+    int* di = upload("g_index", index);
+    float* hr = g.host_rows.empty() ? nullptr : upload("g_hostrows", g.host_rows);
+    launch_assemble_rows(dk, di, (int)Tn, H, embed_, embed_dt_, hr, g.vis_rows, newline_, separator_, X, H, st);
+    int* d_row_page = upload("g_rowpage", row_page);
+    int* d_row_pos = upload("g_rowpos", row_pos);
+    long* d_q_off = upload("g_qoff", q_off);
+    long* d_kv_off = upload("g_kvoff", kv_off);
+    long* d_o_off = upload("g_ooff", o_off);
+    int* d_plen = upload("g_plen", lens);
+    for (int l = 0; l < L.layers; ++l)
+        layer_forward_prefill(l, (int)Tn, B, d_row_page, d_row_pos, d_q_off, d_kv_off, d_o_off, d_plen, maxl, g.Lmax);
+    std::vector<int> last_rows(B), lr_kind(B, ROW_HOST);
+    r0 = 0;
+    for (int b = 0; b < B; ++b) { r0 += lens[b]; last_rows[b] = (int)(r0 - 1); }
+    int* lk = upload("g_lrkind", lr_kind);
+    int* li = upload("g_lrindex", last_rows);
+    launch_assemble_rows(lk, li, B, H, nullptr, 0, X, nullptr, nullptr, nullptr, g.SX, H, st);
+    float* SXN = wsf("s_xn", (size_t)B * H);
+    launch_rmsnorm(g.SX, H, SXN, H, B, H, final_norm_, L.rms_eps, st);
+    linear(SXN, B, H, lm_head_, g.LOGITS, L.vocab);
+}
+
+// sampling state (context = prompt ids (+ generated), sampling.rs:34-96), then the prefill's own selection:
+// the first token of every page
+void Engine::init_sampling(GenState& g) {
+    const LangConfig& L = cfg_.lang;
+    const GenParams& p = g.p;
+    const int B = g.B, H = L.hidden;
+    hipStream_t st = stream_;
+    const long ctx_cap = g.max_p + (long)p.max_new + 1;
+    std::vector<int> ctx((size_t)B * ctx_cap, 0), zeros(B, 0);
+    for (int b = 0; b < B; ++b)
+        for (int i = 0; i < g.prompt_len[b]; ++i) ctx[(size_t)b * ctx_cap + i] = g.reqs[b].ids[i];
+    g.kvpos = g.prompt_len;
+    g.kvlen = g.prompt_len;
+    for (int& v : g.kvlen) ++v;
     int* d_ctx = upload("s_ctx_ids", ctx);
-    int* d_ctx_len = upload("s_ctx_len", ctx_len);
-    int* d_kvpos = wsi("s_kvpos", B);
-    int* d_kvlen = wsi("s_kvlen", B);
-    HIP_CHECK(hipMemcpyAsync(d_kvpos, kvpos.data(), B * 4, hipMemcpyHostToDevice, st));
-    HIP_CHECK(hipMemcpyAsync(d_kvlen, kvlen.data(), B * 4, hipMemcpyHostToDevice, st));
+    int* d_ctx_len = upload("s_ctx_len", g.prompt_len);
+    g.d_kvpos = wsi("s_kvpos", B);
+    g.d_kvlen = wsi("s_kvlen", B);
+    HIP_CHECK(hipMemcpyAsync(g.d_kvpos, g.kvpos.data(), B * 4, hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(g.d_kvlen, g.kvlen.data(), B * 4, hipMemcpyHostToDevice, st));
     HIP_CHECK(hipStreamSynchronize(st));
-    int* d_done = upload("s_done", zeros);
-    int* d_outlen = upload("s_outlen", zeros);
-    int* d_out = wsi("s_out", (size_t)B * p.max_new);
-    int* d_tok = wsi("s_tok", B);
+    g.d_done = upload("s_done", zeros);
+    g.d_outlen = upload("s_outlen", zeros);
+    g.d_out = wsi("s_out", (size_t)B * p.max_new);
+    g.d_tok = wsi("s_tok", B);
     // penalty (applied in place to the logits when != 1) + fused greedy selection
-    SampleArgs pen;
-    pen.logits = LOGITS; pen.B = B; pen.V = L.vocab; pen.ld = L.vocab; pen.ctx = d_ctx; pen.ctx_cap = ctx_cap;
+    SampleArgs& pen = g.pen;
+    pen.logits = g.LOGITS; pen.B = B; pen.V = L.vocab; pen.ld = L.vocab; pen.ctx = d_ctx; pen.ctx_cap = ctx_cap;
     pen.ctx_len = d_ctx_len; pen.rep_penalty = p.rep_penalty;
-    DecSampleArgs sa;
-    sa.logits = LOGITS; sa.B = B; sa.V = L.vocab; sa.ld = L.vocab; sa.ctx = d_ctx; sa.ctx_cap = ctx_cap;
+    DecSampleArgs& sa = g.sa;
+    sa.logits = g.LOGITS; sa.B = B; sa.V = L.vocab; sa.ld = L.vocab; sa.ctx = d_ctx; sa.ctx_cap = ctx_cap;
     sa.ctx_len = d_ctx_len; sa.ngram = p.ngram;
     sa.red_blocks = (int)dec_sample_blocks(L.vocab);
     sa.red_val = wsf("s_redv", (size_t)B * sa.red_blocks); sa.red_idx = wsi("s_redi", (size_t)B * sa.red_blocks);
-    sa.out_tok = d_tok; sa.out_ids = d_out; sa.out_len = d_outlen; sa.out_cap = (long)p.max_new; sa.done = d_done;
+    sa.out_tok = g.d_tok; sa.out_ids = g.d_out; sa.out_len = g.d_outlen; sa.out_cap = (long)p.max_new; sa.done = g.d_done;
     sa.eos = p.ignore_eos ? -1 : (int)p.eos;
-    sa.table = embed_; sa.table_dt = embed_dt_; sa.H = H; sa.x_next = SX; sa.kv_pos = d_kvpos; sa.kv_len = d_kvlen;
+    sa.table = embed_; sa.table_dt = embed_dt_; sa.H = H; sa.x_next = g.SX; sa.kv_pos = g.d_kvpos; sa.kv_len = g.d_kvlen;
     if (p.do_sample) {
         // stochastic selection (sampling.hip): StdRng::seed_from_u64(seed) per page — every page starts
         // from init_rng(seed) like a single-page generate call (model/mod.rs:1917) — or entropy
@@ -1792,9 +1844,9 @@ std::vector<std::vector<int64_t>> Engine::generate(const std::vector<GenRequest>
             std::random_device rd;
             seed = ((uint64_t)rd() << 32) ^ rd();
         }
-        const std::vector<uint32_t> st = rng_state_from_u64(seed);
+        const std::vector<uint32_t> rng = rng_state_from_u64(seed);
         std::vector<int> all((size_t)B * RNG_WORDS);
-        for (int b = 0; b < B; ++b) memcpy(&all[(size_t)b * RNG_WORDS], st.data(), sizeof(uint32_t) * RNG_WORDS);
+        for (int b = 0; b < B; ++b) memcpy(&all[(size_t)b * RNG_WORDS], rng.data(), sizeof(uint32_t) * RNG_WORDS);
         sa.rng = reinterpret_cast<uint32_t*>(upload("s_rng", all));
     }
     ensure_mm_weights(B);
@@ -1812,119 +1864,165 @@ std::vector<std::vector<int64_t>> Engine::generate(const std::vector<GenRequest>
     trace_steps_ = (long)p.max_new;
     if (trace_) {
         HIP_CHECK(hipMemsetAsync(trace_, 0, sizeof(float) * B * p.max_new * L.vocab, st));
-        launch_trace_logits(LOGITS, B, L.vocab, L.vocab, d_outlen, d_done, trace_, trace_steps_, st);
+        launch_trace_logits(g.LOGITS, B, L.vocab, L.vocab, g.d_outlen, g.d_done, trace_, trace_steps_, st);
     }
     // the fused selection kernel advances the KV position; after the prefill the first
     // decode position must be P, so start one behind
     launch_rep_penalty(pen, st);
-    {
-        std::vector<int> pm1(B), lm1(B);
-        for (int b = 0; b < B; ++b) { pm1[b] = kvpos[b] - 1; lm1[b] = kvlen[b] - 1; }
-        HIP_CHECK(hipMemcpyAsync(d_kvpos, pm1.data(), B * 4, hipMemcpyHostToDevice, st));
-        HIP_CHECK(hipMemcpyAsync(d_kvlen, lm1.data(), B * 4, hipMemcpyHostToDevice, st));
-        launch_dec_sample(sa, st);
-        HIP_CHECK(hipStreamSynchronize(st));
-    }
-    HIP_CHECK(hipEventRecord(ev[3], st));
-    timings_.prefill_flops = flops_acc_;
-    std::vector<int> h_done(B), h_outlen(B);
-    std::vector<int> h_out;
-    size_t steps = 0;
-    int* pin_done = nullptr;
-    HIP_CHECK(hipHostMalloc((void**)&pin_done, sizeof(int) * (3 * B + 1)));
-    // stream callback with the tokens so far (B = 1; model/mod.rs:1980-1982 calls it after every token)
-    int streamed = 0;
-    auto stream_tokens = [&](int n) {
-        if (n <= streamed) return;  // no new token (EOS selected, or the page is done)
-        streamed = n;
-        std::vector<int> tmp(n);
-        if (n) HIP_CHECK(hipMemcpy(tmp.data(), d_out, n * 4, hipMemcpyDeviceToHost));
-        std::vector<int64_t> t64(tmp.begin(), tmp.end());
-        cb(t64.size(), t64.data(), user);
-    };
-    auto poll = [&]() {  // done flags, output lengths and the last tokens of every page
-        HIP_CHECK(hipMemcpyAsync(pin_done, d_done, B * 4, hipMemcpyDeviceToHost, st));
-        HIP_CHECK(hipMemcpyAsync(pin_done + B, d_outlen, B * 4, hipMemcpyDeviceToHost, st));
-        HIP_CHECK(hipMemcpyAsync(pin_done + 2 * B, d_tok, B * 4, hipMemcpyDeviceToHost, st));
-        HIP_CHECK(hipStreamSynchronize(st));
-        bool all = true;
-        for (int b = 0; b < B; ++b) all &= pin_done[b] != 0;
-        return all;
-    };
-    if (cb && B == 1 && p.max_new > 0) {
-        poll();
-        if (pin_done[B] > 0) stream_tokens(pin_done[B]);
-    }
-    if (!p.use_cache) {
-        // ---------------- 4'. generate_without_cache (model/mod.rs:2051-2283): every step re-runs the
-        // whole forward on prompt + generated tokens (image rows re-injected at the same slots), then
-        // the same selection / bookkeeping kernels as the cached loop
-        HIP_CHECK(hipEventRecord(ev[4], st));
-        std::vector<int> lens = prompt_len;
-        for (size_t i = 1; i < p.max_new; ++i) {
-            if (poll()) break;
-            for (int b = 0; b < B; ++b)
-                if (!pin_done[b]) { extra[b].push_back(pin_done[2 * B + b]); ++lens[b]; }
-            forward_rows(lens, extra);
-            if (trace_) launch_trace_logits(LOGITS, B, L.vocab, L.vocab, d_outlen, d_done, trace_, trace_steps_, st);
-            launch_rep_penalty(pen, st);
-            launch_dec_sample(sa, st);
-            ++steps;
-            if (cb && B == 1) {
-                poll();
-                stream_tokens(pin_done[B]);
-            }
+    std::vector<int> pm1(B), lm1(B);
+    for (int b = 0; b < B; ++b) { pm1[b] = g.kvpos[b] - 1; lm1[b] = g.kvlen[b] - 1; }
+    HIP_CHECK(hipMemcpyAsync(g.d_kvpos, pm1.data(), B * 4, hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(g.d_kvlen, lm1.data(), B * 4, hipMemcpyHostToDevice, st));
+    launch_dec_sample(sa, st);
+    HIP_CHECK(hipStreamSynchronize(st));
+}
+
+// done flags, output lengths and the last tokens of every page into g.pin; true when every page is done
+bool Engine::poll(GenState& g) {
+    const int B = g.B;
+    HIP_CHECK(hipMemcpyAsync(g.pin, g.d_done, B * 4, hipMemcpyDeviceToHost, stream_));
+    HIP_CHECK(hipMemcpyAsync(g.pin + B, g.d_outlen, B * 4, hipMemcpyDeviceToHost, stream_));
+    HIP_CHECK(hipMemcpyAsync(g.pin + 2 * B, g.d_tok, B * 4, hipMemcpyDeviceToHost, stream_));
+    HIP_CHECK(hipStreamSynchronize(stream_));
+    bool all = true;
+    for (int b = 0; b < B; ++b) all &= g.pin[b] != 0;
+    return all;
+}
+
+// stream callback with the n tokens so far (B = 1; model/mod.rs:1980-1982 calls it after every token)
+void Engine::stream_tokens(GenState& g, int n) {
+    if (n <= g.streamed) return;  // no new token (EOS selected, or the page is done)
+    g.streamed = n;
+    std::vector<int> tmp(n);
+    if (n) HIP_CHECK(hipMemcpy(tmp.data(), g.d_out, n * 4, hipMemcpyDeviceToHost));
+    std::vector<int64_t> t64(tmp.begin(), tmp.end());
+    g.cb(t64.size(), t64.data(), g.user);
+}
+
+// ---------------- 4'. generate_without_cache (model/mod.rs:2051-2283): every step re-runs the
+// whole forward on prompt + generated tokens (image rows re-injected at the same slots), then
+// the same selection / bookkeeping kernels as the cached loop
+void Engine::decode_uncached(GenState& g) {
+    const int B = g.B, V = cfg_.lang.vocab;
+    hipStream_t st = stream_;
+    HIP_CHECK(hipEventRecord(g.ev[4], st));
+    std::vector<int> lens = g.prompt_len;
+    for (size_t i = 1; i < g.p.max_new; ++i) {
+        if (poll(g)) break;
+        for (int b = 0; b < B; ++b)
+            if (!g.pin[b]) { g.extra[b].push_back(g.pin[2 * B + b]); ++lens[b]; }
+        forward_rows(g, lens);
+        if (trace_) launch_trace_logits(g.LOGITS, B, V, V, g.d_outlen, g.d_done, trace_, trace_steps_, st);
+        launch_rep_penalty(g.pen, st);
+        launch_dec_sample(g.sa, st);
+        ++g.steps;
+        if (g.cb && B == 1) {
+            poll(g);
+            stream_tokens(g, g.pin[B]);
         }
-        HIP_CHECK(hipEventRecord(ev[5], st));
-        HIP_CHECK(hipStreamSynchronize(st));
-    } else {
-    chain_active_ = false;
+    }
+    HIP_CHECK(hipEventRecord(g.ev[5], st));
+    HIP_CHECK(hipStreamSynchronize(st));
+}
+
+// launch spans (set_spans): this generate's record buffers; span_rec_ marks it as stamped
+void Engine::begin_spans(GenState& g) {
+    const int layers = cfg_.lang.layers;
+    hipStream_t st = stream_;
     spans_kinds_ = SPAN_KINDS;
     if (span_mode_ == SPAN_CHAIN) {
-        span_cap_ = (int)std::max<size_t>(p.max_new, 1) + 1;  // the fold records at (tokens emitted) <= max_new
-        const size_t nreg = (size_t)L.layers * SPAN_KINDS_CHAIN;
+        span_cap_ = (int)std::max<size_t>(g.p.max_new, 1) + 1;  // the fold records at (tokens emitted) <= max_new
+        const size_t nreg = (size_t)layers * SPAN_KINDS_CHAIN;
         span_chain_ = (unsigned long long*)ws("s_span_chain", nreg * SPAN_SLOTS * 16);
         span_chain_rec_ = (unsigned long long*)ws("s_span_chain_rec", (size_t)span_cap_ * nreg * 32);
         span_tmark_ = (unsigned long long*)ws("s_span_tmark", 16);
-        span_rec_ = span_chain_rec_;  // (marks the generate as stamped)
-        span_step_ = d_outlen;
+        span_rec_ = span_chain_rec_;
+        span_step_ = g.d_outlen;
         chain_active_ = true;
         HIP_CHECK(hipMemsetAsync(span_chain_rec_, 0, (size_t)span_cap_ * nreg * 32, st));
     } else if (span_mode_) {
-        span_cap_ = (int)std::max<size_t>(p.max_new, 1);
-        const size_t rec_bytes = (size_t)SPAN_KINDS * L.layers * span_cap_ * 4 * 8;
+        span_cap_ = (int)std::max<size_t>(g.p.max_new, 1);
+        const size_t rec_bytes = (size_t)SPAN_KINDS * layers * span_cap_ * 4 * 8;
         span_slots_ = (unsigned long long*)ws("s_span_slots", (size_t)SPAN_SLOTS * 16);
         span_rec_ = (unsigned long long*)ws("s_span_rec", rec_bytes);
-        span_step_ = d_outlen;
+        span_step_ = g.d_outlen;
         HIP_CHECK(hipMemsetAsync(span_slots_, 0, (size_t)SPAN_SLOTS * 16, st));
         HIP_CHECK(hipMemsetAsync(span_rec_, 0, rec_bytes, st));
-        if (span_ev_.empty()) {
-            span_ev_.resize((size_t)SPAN_KINDS * L.layers * 2);
-            for (auto& e : span_ev_) HIP_CHECK(hipEventCreate(&e));
-        }
-        span_ev_ns_.assign((size_t)SPAN_KINDS * L.layers * span_cap_, 0.0);
+        if (span_ev_.empty()) span_ev_.resize((size_t)SPAN_KINDS * layers * 2);
+        span_ev_ns_.assign((size_t)SPAN_KINDS * layers * span_cap_, 0.0);
     }
-    // after a stamped step: the dispatch-level duration of every bracketed launch, at the step's index
-    auto read_span_events = [&](size_t step) {
-        HIP_CHECK(hipEventSynchronize(span_ev_.back()));
-        const size_t k = std::min(step, (size_t)span_cap_ - 1);
-        for (size_t i = 0; i < (size_t)SPAN_KINDS * L.layers; ++i) {
-            float ms = 0.f;
-            if (hipEventElapsedTime(&ms, span_ev_[2 * i], span_ev_[2 * i + 1]) == hipSuccess)
-                span_ev_ns_[i * span_cap_ + k] = ms * 1e6;
-            else
-                (void)hipGetLastError();  // pair not recorded this step (e.g. the dense layer)
+}
+
+// after a stamped step: the dispatch-level duration of every bracketed launch, at the step's index
+void Engine::read_span_events(size_t step) {
+    HIP_CHECK(hipEventSynchronize(span_ev_.back()));
+    const size_t k = std::min(step, (size_t)span_cap_ - 1);
+    for (size_t i = 0; i < (size_t)SPAN_KINDS * cfg_.lang.layers; ++i) {
+        float ms = 0.f;
+        if (hipEventElapsedTime(&ms, span_ev_[2 * i], span_ev_[2 * i + 1]) == hipSuccess)
+            span_ev_ns_[i * span_cap_ + k] = ms * 1e6;
+        else
+            (void)hipGetLastError();  // pair not recorded this step (e.g. the dense layer)
+    }
+}
+
+// the stamped generate's records into spans_host_ (spans_steps_ is reported with the records it sizes)
+void Engine::collect_spans() {
+    const int layers = cfg_.lang.layers;
+    if (chain_active_) {
+        const size_t nreg = (size_t)layers * SPAN_KINDS_CHAIN;
+        std::vector<unsigned long long> dev((size_t)span_cap_ * nreg * 4);
+        HIP_CHECK(hipMemcpy(dev.data(), span_chain_rec_, dev.size() * 8, hipMemcpyDeviceToHost));
+        spans_host_.assign((size_t)SPAN_KINDS_CHAIN * layers * span_cap_ * SPAN_FIELDS, 0);
+        // fold at step s's end recorded at index (tokens emitted) = s + 1: shift back to s
+        for (int s = 1; s < span_cap_; ++s)
+            for (int l = 0; l < layers; ++l)
+                for (int k = 0; k < SPAN_KINDS_CHAIN; ++k) {
+                    const unsigned long long* r = &dev[((size_t)s * nreg + (size_t)l * SPAN_KINDS_CHAIN + k) * 4];
+                    unsigned long long* o = &spans_host_[(((size_t)k * layers + l) * span_cap_ + s - 1) * SPAN_FIELDS];
+                    o[0] = r[0]; o[1] = r[1]; o[3] = r[2];
+                }
+        spans_steps_ = span_cap_;
+        spans_kinds_ = SPAN_KINDS_CHAIN;
+    } else if (span_rec_) {
+        const size_t nrec = (size_t)SPAN_KINDS * layers * span_cap_;
+        std::vector<unsigned long long> dev(nrec * 4);
+        HIP_CHECK(hipMemcpy(dev.data(), span_rec_, dev.size() * 8, hipMemcpyDeviceToHost));
+        spans_host_.assign(nrec * SPAN_FIELDS, 0);
+        for (size_t r = 0; r < nrec; ++r) {
+            for (int f = 0; f < 4; ++f) spans_host_[r * SPAN_FIELDS + f] = dev[r * 4 + f];
+            if (span_mode_ & SPAN_EVENTS) spans_host_[r * SPAN_FIELDS + 4] = (unsigned long long)llround(span_ev_ns_[r]);
         }
-    };
+        spans_steps_ = span_cap_;
+    }
+}
+
+// one decode step: the layers, the head and the selection (captured once, replayed per token)
+void Engine::step_body(GenState& g) {
+    decode_step(g.B, g.Lmax);
+    decode_head(g.B, g.sa, g.pen);
+    // chain spans: the step's one fold, after the head (the step counter has advanced: record at count - 1)
+    if (chain_active_)
+        launch_span_chain_fold(span_chain_, cfg_.lang.layers * SPAN_KINDS_CHAIN, span_chain_rec_, span_step_, span_cap_,
+                               span_tmark_, stream_);
+}
+
+// ---------------- 4. decode loop (decode.iterative) as a replayed hipGraph (eager launches: graphs_on())
+void Engine::decode_cached(GenState& g) {
+    const LangConfig& L = cfg_.lang;
+    const GenParams& p = g.p;
+    const int B = g.B, H = L.hidden;
+    hipStream_t st = stream_;
+    begin_spans(g);
     // make sure every decode workspace exists before capture: a dry step allocates them
     // (it writes the step-0 K/V slot, which the real step rewrites), then the state is restored
-    decode_step(B, Lmax);
+    decode_step(B, g.Lmax);
     if (persist_active_) {  // the dry step's granules carry step 1's tags: reset them
         HIP_CHECK(hipMemsetAsync(persist_g_, 0xff, dec_persist_granules(L.layers) * 8, st));
         persist_stamps_host_.clear();
         persist_ev_us_.clear();
         if (persist_stamp_mode_) {
-            persist_stamp_pos0_ = kvpos[0];
+            persist_stamp_pos0_ = g.kvpos[0];
             persist_stamp_cap_ = (int)p.max_new;
             const size_t n = (size_t)persist_stamp_cap_ * PK_G * L.layers * PK_STAMPS;
             persist_stamps_ = (unsigned long long*)ws("p_pk_stamps", n * 8);
@@ -1935,43 +2033,24 @@ std::vector<std::vector<int64_t>> Engine::generate(const std::vector<GenRequest>
         HIP_CHECK(hipMemsetAsync(span_chain_, 0, (size_t)L.layers * SPAN_KINDS_CHAIN * SPAN_SLOTS * 16, st));
         HIP_CHECK(hipMemsetAsync(span_tmark_, 0, 16, st));
     }
-    HIP_CHECK(hipMemcpyAsync(d_kvpos, kvpos.data(), B * 4, hipMemcpyHostToDevice, st));
-    HIP_CHECK(hipMemcpyAsync(d_kvlen, kvlen.data(), B * 4, hipMemcpyHostToDevice, st));
-    launch_embed_tokens(embed_, embed_dt_, d_tok, B, H, SX, H, st);
+    HIP_CHECK(hipMemcpyAsync(g.d_kvpos, g.kvpos.data(), B * 4, hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(g.d_kvlen, g.kvlen.data(), B * 4, hipMemcpyHostToDevice, st));
+    launch_embed_tokens(embed_, embed_dt_, g.d_tok, B, H, g.SX, H, st);
     HIP_CHECK(hipStreamSynchronize(st));
 
-    // ---------------- 4. decode loop (decode.iterative) as a replayed hipGraph
-    // DSOCR_NO_GRAPH=1 launches the same kernels eagerly (rocprofv3 kernel tracing of
-    // graph replays is unreliable on this stack; kernel durations are unchanged).
-    const bool use_graph = !(getenv("DSOCR_NO_GRAPH") && atoi(getenv("DSOCR_NO_GRAPH")) != 0);
-    auto step_body = [&]() {
-        decode_step(B, Lmax);
-        decode_head(B, sa, pen);
-        // chain spans: the step's one fold, after the head (the step counter has advanced: record at count - 1)
-        if (chain_active_)
-            launch_span_chain_fold(span_chain_, L.layers * SPAN_KINDS_CHAIN, span_chain_rec_, span_step_, span_cap_,
-                                   span_tmark_, st);
-    };
+    const bool use_graph = graphs_on();
     const bool pk_timed = persist_active_ && persist_stamp_mode_ && !span_rec_;
-    if (pk_timed && persist_ev_.empty()) {
-        persist_ev_.resize(2);
-        for (auto& e : persist_ev_) HIP_CHECK(hipEventCreate(&e));
-    }
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t gexec = nullptr;
+    if (pk_timed && persist_ev_.empty()) persist_ev_.resize(2);
+    HipGraphExec gexec;
     if (use_graph && !pk_timed) {
-        capturing_ = true;
-        HIP_CHECK(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-        step_body();
-        HIP_CHECK(hipStreamEndCapture(st, &graph));
-        capturing_ = false;
-        HIP_CHECK(hipGraphInstantiate(&gexec, graph, nullptr, nullptr, 0));
+        StreamCapture cap(st, capturing_);
+        step_body(g);
+        gexec = cap.finish();
     }
-
-    HIP_CHECK(hipEventRecord(ev[4], st));
+    HIP_CHECK(hipEventRecord(g.ev[4], st));
     for (size_t i = 1; i < p.max_new; ++i) {
-        if (gexec) HIP_CHECK(hipGraphLaunch(gexec, st));
-        else step_body();
+        if (gexec) gexec.launch(st);
+        else step_body(g);
         if (span_rec_ && (span_mode_ & SPAN_EVENTS)) read_span_events(i);
         if (pk_timed) {  // the persistent launch's dispatch duration (events recorded around it in the step)
             HIP_CHECK(hipEventSynchronize(persist_ev_[1]));
@@ -1979,65 +2058,33 @@ std::vector<std::vector<int64_t>> Engine::generate(const std::vector<GenRequest>
             HIP_CHECK(hipEventElapsedTime(&ms, persist_ev_[0], persist_ev_[1]));
             persist_ev_us_.push_back(ms * 1e3);
         }
-        ++steps;
-        const bool check = cb != nullptr || (!p.ignore_eos && (i % 8 == 0 || i + 1 == p.max_new));
+        ++g.steps;
+        const bool check = g.cb != nullptr || (!p.ignore_eos && (i % 8 == 0 || i + 1 == p.max_new));
         if (check) {
-            const bool all = poll();
-            if (cb && B == 1) stream_tokens(pin_done[B]);
+            const bool all = poll(g);
+            if (g.cb && B == 1) stream_tokens(g, g.pin[B]);
             if (all) break;
         }
     }
-    HIP_CHECK(hipEventRecord(ev[5], st));
+    HIP_CHECK(hipEventRecord(g.ev[5], st));
     HIP_CHECK(hipStreamSynchronize(st));
-    if (gexec) (void)hipGraphExecDestroy(gexec);
-    if (graph) (void)hipGraphDestroy(graph);
     if (pk_timed) {
         persist_stamps_host_.resize((size_t)persist_stamp_cap_ * PK_G * L.layers * PK_STAMPS);
         HIP_CHECK(hipMemcpy(persist_stamps_host_.data(), persist_stamps_, persist_stamps_host_.size() * 8,
                             hipMemcpyDeviceToHost));
         persist_stamp_mode_ = 0;
     }
-    if (chain_active_) {
-        const size_t nreg = (size_t)L.layers * SPAN_KINDS_CHAIN;
-        std::vector<unsigned long long> dev((size_t)span_cap_ * nreg * 4);
-        HIP_CHECK(hipMemcpy(dev.data(), span_chain_rec_, dev.size() * 8, hipMemcpyDeviceToHost));
-        spans_host_.assign((size_t)SPAN_KINDS_CHAIN * L.layers * span_cap_ * SPAN_FIELDS, 0);
-        // fold at step s's end recorded at index (tokens emitted) = s + 1: shift back to s
-        for (int st_ = 1; st_ < span_cap_; ++st_)
-            for (int l = 0; l < L.layers; ++l)
-                for (int k = 0; k < SPAN_KINDS_CHAIN; ++k) {
-                    const unsigned long long* r = &dev[((size_t)st_ * nreg + (size_t)l * SPAN_KINDS_CHAIN + k) * 4];
-                    unsigned long long* o = &spans_host_[(((size_t)k * L.layers + l) * span_cap_ + st_ - 1) * SPAN_FIELDS];
-                    o[0] = r[0]; o[1] = r[1]; o[3] = r[2];
-                }
-        spans_steps_ = span_cap_;
-        spans_kinds_ = SPAN_KINDS_CHAIN;
-        chain_active_ = false;
-        span_rec_ = nullptr;
-        span_step_ = nullptr;
-    } else if (span_rec_) {
-        const size_t nrec = (size_t)SPAN_KINDS * L.layers * span_cap_;
-        std::vector<unsigned long long> dev(nrec * 4);
-        HIP_CHECK(hipMemcpy(dev.data(), span_rec_, dev.size() * 8, hipMemcpyDeviceToHost));
-        spans_host_.assign(nrec * SPAN_FIELDS, 0);
-        for (size_t r = 0; r < nrec; ++r) {
-            for (int f = 0; f < 4; ++f) spans_host_[r * SPAN_FIELDS + f] = dev[r * 4 + f];
-            if (span_mode_ & SPAN_EVENTS) spans_host_[r * SPAN_FIELDS + 4] = (unsigned long long)llround(span_ev_ns_[r]);
-        }
-        spans_steps_ = span_cap_;  // reported with the records it sizes (a throwing generate leaves both)
-        // profile_decode runs unstamped; every later generate is stamped again while span_mode_ is set
-        span_rec_ = nullptr;
-        span_slots_ = nullptr;
-        span_step_ = nullptr;
-    }
-    }  // cached decode loop
-    HIP_CHECK(hipHostFree(pin_done));
-    {
-        int e = 0;
-        HIP_CHECK(hipMemcpy(&e, wsi("s_err", 4), sizeof(int), hipMemcpyDeviceToHost));
-        if (e) throw std::runtime_error("EINTERNAL: decode hand-off timed out inside a fused kernel");
-    }
-    if (sa.ban_out && getenv("DSOCR_SCREEN_STATS")) {
+    collect_spans();
+}
+
+// the decode error flag, the generated ids of every page and the stage timings (and the parity trace)
+std::vector<std::vector<int64_t>> Engine::collect_outputs(GenState& g) {
+    const GenParams& p = g.p;
+    const int B = g.B;
+    int e = 0;
+    HIP_CHECK(hipMemcpy(&e, wsi("s_err", 4), sizeof(int), hipMemcpyDeviceToHost));
+    if (e) throw std::runtime_error("EINTERNAL: decode hand-off timed out inside a fused kernel");
+    if (g.sa.ban_out && getenv("DSOCR_SCREEN_STATS")) {
         unsigned long long h[16] = {0};
         HIP_CHECK(hipMemcpy(h, wsi("s_scrstats", 32), sizeof(h), hipMemcpyDeviceToHost));
         const double st = h[0] ? (double)h[0] : 1.0;
@@ -2045,24 +2092,64 @@ std::vector<std::vector<int64_t>> Engine::generate(const std::vector<GenRequest>
         for (int k = 0; k < 7; ++k) fprintf(stderr, " %.2f", h[4 + k] / st / 100.0);  // wall clock: 100 MHz
         fprintf(stderr, "\n");
     }
-    h_out.resize((size_t)B * p.max_new);
-    HIP_CHECK(hipMemcpy(h_out.data(), d_out, h_out.size() * 4, hipMemcpyDeviceToHost));
-    HIP_CHECK(hipMemcpy(h_outlen.data(), d_outlen, B * 4, hipMemcpyDeviceToHost));
+    std::vector<int> h_out((size_t)B * p.max_new), h_outlen(B);
+    HIP_CHECK(hipMemcpy(h_out.data(), g.d_out, h_out.size() * 4, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(h_outlen.data(), g.d_outlen, B * 4, hipMemcpyDeviceToHost));
+    std::vector<std::vector<int64_t>> out(B);
     for (int b = 0; b < B; ++b) out[b].assign(h_out.begin() + (size_t)b * p.max_new, h_out.begin() + (size_t)b * p.max_new + h_outlen[b]);
-
-    timings_.vision_compute_ms = ms_between(ev[0], ev[1]);
-    timings_.prefill_ms = ms_between(ev[2], ev[3]);
-    timings_.iterative_ms = ms_between(ev[4], ev[5]);
-    timings_.generate_ms = ms_between(ev[2], ev[3]) + ms_between(ev[4], ev[5]);
-    timings_.steps = steps;
+    timings_.vision_compute_ms = ms_between(g.ev[0], g.ev[1]);
+    timings_.prefill_ms = ms_between(g.ev[2], g.ev[3]);
+    timings_.iterative_ms = ms_between(g.ev[4], g.ev[5]);
+    timings_.generate_ms = timings_.prefill_ms + timings_.iterative_ms;
+    timings_.steps = g.steps;
     if (trace_ && p.trace)
-        HIP_CHECK(hipMemcpy(p.trace, trace_, sizeof(float) * B * p.max_new * L.vocab, hipMemcpyDeviceToHost));
-    trace_ = nullptr;
+        HIP_CHECK(hipMemcpy(p.trace, trace_, sizeof(float) * B * p.max_new * cfg_.lang.vocab, hipMemcpyDeviceToHost));
     last_B_ = B;
-    last_Lmax_ = Lmax;
-    (void)t0;
-    for (auto& e : ev) (void)hipEventDestroy(e);
+    last_Lmax_ = g.Lmax;
     return out;
+}
+
+// ============================================================================ profile_decode
+// `body` captured as one hipGraph on the engine stream, replayed once to warm, then n replays between two
+// events: the mean us of a replay
+double Engine::replay_us(int n, const std::function<void()>& body) {
+    hipStream_t st = stream_;
+    HipEvent e0, e1;
+    StreamCapture cap(st, capturing_);
+    body();
+    const HipGraphExec ge = cap.finish();
+    ge.launch(st);
+    HIP_CHECK(hipEventRecord(e0, st));
+    for (int i = 0; i < n; ++i) ge.launch(st);
+    HIP_CHECK(hipEventRecord(e1, st));
+    HIP_CHECK(hipEventSynchronize(e1));
+    return 1000.0 * ms_between(e0, e1) / n;
+}
+
+// Two figures per kernel (eager launches go host-bound below ~3.5 us per kernel, MI355X_MICROARCH.md
+// graph-replay-floor, so they cannot time the short decode kernels):
+//  * avg_us: every launch carries its own start / stop events on its dispatch packet
+//    (hipExtLaunchKernelGGL through DSOCR_LAUNCH: the begin / end timestamps rocprofv3's kernel
+//    trace reports), eager, one launch at a time — the figure the committed rocprof summaries
+//    corroborate;
+//  * replay_us: n launches back to back in one hipGraph replay, span / n - the kernel inside a
+//    dependent chain as the decode loop runs it (duration + the ~1.2 us kernel boundary, minus
+//    whatever startup the chained dispatch hides).
+void Engine::time_launches(KernelProfile& kp, int n, const std::function<void(int)>& body) {
+    body(0);  // warm (code objects, TLB) and every workspace allocated before capture
+    std::vector<HipEvent> ev(2 * n);
+    for (int i = 0; i < n; ++i) {
+        ScopedSet timing(prof_events(), ProfEvents{ev[2 * i], ev[2 * i + 1]});  // the body's first launch times itself
+        body(i);
+        if (prof_events().start) throw std::runtime_error("EINTERNAL: profiled body made no instrumented launch");
+    }
+    HIP_CHECK(hipEventSynchronize(ev[2 * n - 1]));
+    double sum = 0;
+    for (int i = 0; i < n; ++i) sum += ms_between(ev[2 * i], ev[2 * i + 1]);
+    kp.avg_us = 1000.0 * sum / n;
+    kp.launches = n;
+    if (graphs_on())
+        kp.replay_us = replay_us(1, [&] { for (int i = 0; i < n; ++i) body(i); }) / n;
 }
 
 Engine::DecodeProfile Engine::profile_decode(int iters) {
@@ -2070,7 +2157,7 @@ Engine::DecodeProfile Engine::profile_decode(int iters) {
     const LangConfig& L = cfg_.lang;
     const int B = last_B_, Lmax = last_Lmax_;
     if (B == 0 || Lmax == 0) throw std::runtime_error("EINVAL: run a generate() first");
-    const int H = L.hidden, hd = L.head_dim;
+    const int H = L.hidden, hd = L.head_dim, QKVN = layers_[0].qkv.N;
     hipStream_t st = stream_;
     std::vector<int> kvpos(B);
     HIP_CHECK(hipMemcpy(kvpos.data(), wsi("s_kvpos", B), B * 4, hipMemcpyDeviceToHost));
@@ -2082,11 +2169,10 @@ Engine::DecodeProfile Engine::profile_decode(int iters) {
     HIP_CHECK(hipMemcpy(d_pos, pm1.data(), B * 4, hipMemcpyHostToDevice));
     prof.tokens = B;
     prof.kv_len = pm1[0] + 1;
-    {
-        const size_t qn = (size_t)B * layers_[0].qkv.N;
-        HIP_CHECK(hipMemsetAsync(wsf("p_qkv_attn", qn), 0, qn * 4, st));
-    }
-    // the replays rewrite the K / V slot of pos - 1 in every layer (the attention replays from a scratch
+    // a scratch q/k/v row (zeros) for the attention replays: s_qkv holds the fused launch's sentinels
+    float* qkv0 = wsf("p_qkv_attn", (size_t)B * QKVN);
+    HIP_CHECK(hipMemsetAsync(qkv0, 0, (size_t)B * QKVN * 4, st));
+    // the replays rewrite the K / V slot of pos - 1 in every layer (the attention replays from the scratch
     // row): keep those slots and put them back after the attention replays and at the end, so the
     // step-graph replays and any later use of the engine state see the cache the generate left
     const size_t slot_w = (size_t)hd * 4, n_slots = (size_t)L.layers * B * 2;
@@ -2104,67 +2190,6 @@ Engine::DecodeProfile Engine::profile_decode(int iters) {
                 }
     };
     kv_slots(false);
-    // n back-to-back launches captured in one hipGraph, replayed between two events on the
-    // engine stream: per-launch time = span / n = device time + the dependent-kernel boundary
-    // (eager launches go host-bound below ~3.5 us per kernel, MI355X_MICROARCH.md
-    // graph-replay-floor, so they cannot time the short decode kernels)
-    // Two figures per kernel:
-    //  * avg_us: every launch carries its own start / stop events on its dispatch packet
-    //    (hipExtLaunchKernelGGL through DSOCR_LAUNCH: the begin / end timestamps rocprofv3's kernel
-    //    trace reports), eager, one launch at a time — the figure the committed rocprof summaries
-    //    corroborate;
-    //  * replay_us: n launches back to back in one hipGraph replay, span / n - the kernel inside a
-    //    dependent chain as the decode loop runs it (duration + the ~1.2 us kernel boundary, minus
-    //    whatever startup the chained dispatch hides).
-    auto timed = [&](KernelProfile& kp, int n, const std::function<void(int)>& body) {
-        body(0);  // warm (code objects, TLB) and every workspace allocated before capture
-        // the events are destroyed on every exit, the EINTERNAL / HIP-error throws below included
-        struct EventSet {
-            std::vector<hipEvent_t> v;
-            ~EventSet() {
-                for (auto& e : v)
-                    if (e) (void)hipEventDestroy(e);
-            }
-        } evs;
-        evs.v.assign(2 * n, nullptr);
-        std::vector<hipEvent_t>& ev = evs.v;
-        for (auto& e : ev) HIP_CHECK(hipEventCreate(&e));
-        for (int i = 0; i < n; ++i) {
-            prof_events() = ProfEvents{ev[2 * i], ev[2 * i + 1]};  // the body's first launch times itself
-            body(i);
-            if (prof_events().start) {  // the body launched nothing through DSOCR_LAUNCH: bracket it
-                prof_events() = ProfEvents();
-                throw std::runtime_error("EINTERNAL: profiled body made no instrumented launch");
-            }
-        }
-        HIP_CHECK(hipEventSynchronize(ev[2 * n - 1]));
-        double sum = 0;
-        for (int i = 0; i < n; ++i) sum += ms_between(ev[2 * i], ev[2 * i + 1]);
-        kp.avg_us = 1000.0 * sum / n;
-        kp.launches = n;
-        if (getenv("DSOCR_NO_GRAPH") && atoi(getenv("DSOCR_NO_GRAPH")) != 0) return;
-        hipEvent_t e0, e1;
-        HIP_CHECK(hipEventCreate(&e0));
-        HIP_CHECK(hipEventCreate(&e1));
-        hipGraph_t graph = nullptr;
-        hipGraphExec_t gexec = nullptr;
-        capturing_ = true;
-        HIP_CHECK(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-        for (int i = 0; i < n; ++i) body(i);
-        HIP_CHECK(hipStreamEndCapture(st, &graph));
-        capturing_ = false;
-        HIP_CHECK(hipGraphInstantiate(&gexec, graph, nullptr, nullptr, 0));
-        HIP_CHECK(hipGraphLaunch(gexec, st));  // warm replay
-        HIP_CHECK(hipEventRecord(e0, st));
-        HIP_CHECK(hipGraphLaunch(gexec, st));
-        HIP_CHECK(hipEventRecord(e1, st));
-        HIP_CHECK(hipEventSynchronize(e1));
-        kp.replay_us = 1000.0 * ms_between(e0, e1) / n;
-        (void)hipGraphExecDestroy(gexec);
-        (void)hipGraphDestroy(graph);
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
-    };
     std::vector<int> moe_layers;
     for (int l = 0; l < L.layers; ++l)
         if (layers_[l].moe) moe_layers.push_back(l);
@@ -2181,12 +2206,12 @@ Engine::DecodeProfile Engine::profile_decode(int iters) {
         HIP_CHECK(hipMemcpyAsync(Xs, Xc, (size_t)B * H * 4, hipMemcpyDeviceToDevice, st));
         // the gate/up and down launches of decode_step's dispatch (launch_moe_decode), replayed
         // alone on the routing state the last step left (logits, normalised rows, expert groups)
-        auto args = [&](int l) { return moe_args(l, B, Xs); };
+        auto args = [&](int i) { return moe_args(moe_layers[i % moe_layers.size()], B, Xs); };
         const int n = iters * (int)moe_layers.size();
-        moe_decode_kernel_names(args(moe_layers[0]), &prof.gateup_kernel, &prof.down_kernel);
+        moe_decode_kernel_names(args(0), &prof.gateup_kernel, &prof.down_kernel);
         // rotating over the layers (~55 MB each) defeats the 256 MB Infinity Cache
-        timed(prof.moe_gateup, n, [&](int i) { launch_moe_decode(args(moe_layers[i % moe_layers.size()]), st, MOE_GATEUP); });
-        timed(prof.moe_down, n, [&](int i) { launch_moe_decode(args(moe_layers[i % moe_layers.size()]), st, MOE_DOWN); });
+        time_launches(prof.moe_gateup, n, [&](int i) { launch_moe_decode(args(i), st, MOE_GATEUP); });
+        time_launches(prof.moe_down, n, [&](int i) { launch_moe_decode(args(i), st, MOE_DOWN); });
         const DecLayer& d0 = layers_[moe_layers[0]];
         const double Is = d0.has_shared ? d0.s_d.K : 0;
         const double touched = (double)prof.experts_touched;
@@ -2196,167 +2221,131 @@ Engine::DecodeProfile Engine::profile_decode(int iters) {
         prof.moe_down.bytes = (touched * I + Is) * H * 2.0 + (double)(TK * I + B * Is) * 4 + 2.0 * B * H * 4;
         prof.moe_down.flops = 2.0 * (TK * (double)I + B * Is) * H;
     }
-    {
-        const int QKVN = layers_[0].qkv.N;
-        float* part = wsf("s_part", dec_attn_workspace(B, L.heads, hd, Lmax) / 4 + 16);
-        float* CTX = wsf("p_ctx", (size_t)B * H);
-        const int n = iters * L.layers;
-        timed(prof.attention, n, [&](int i) {
-            const int l = i % L.layers;
-            DecAttn2Args da;
-            // a scratch q/k/v row (zeros): s_qkv holds the fused launch's sentinels, and the replays
-            // rewrite the K / V slot of pos - 1 from this row
-            da.qkv = wsf("p_qkv_attn", (size_t)B * QKVN); da.ld = QKVN; da.kv_pos = d_pos; da.B = B; da.heads = L.heads;
-            da.kv_heads = L.kv_heads; da.hd = hd; da.rope_dim = L.rope_dim; da.use_mla = L.use_mla; da.max_len = Lmax;
-            da.cos = rope_cos_; da.sin = rope_sin_;
-            da.kc = kc_ + (long)l * B * page_stride_; da.vc = vc_ + (long)l * B * page_stride_;
-            da.page_stride = page_stride_; da.head_stride = head_stride_;
-            da.scale = (float)(1.0 / std::sqrt((double)hd)); da.part = part; da.o = CTX; da.o_ld = H;
-            da.err = wsi("s_err", 4);
-            da.counters = wsi("s_attn_cnt", (size_t)B * L.heads);
-            launch_dec_attn(da, st);
-        });
-        kv_slots(true);
-        // K and V of every attended key (f32 cache) + q/k/v row + context out
-        prof.attention.bytes = (double)keys * L.kv_heads * hd * 4.0 * 2.0 + (double)B * (QKVN + H) * 4.0;
-        prof.attention.flops = 4.0 * keys * L.heads * hd;
-    }
-    {
-        float* LG = wsf("p_logits", (size_t)B * L.vocab);
-        const float* SX = wsf("s_x", (size_t)B * H);
-        float* SXN = wsf("p_xn", (size_t)B * H);
-        ensure_mm_weights(B);
-        const bool fused = B <= 2 || (lm_swz_ && B <= 8);
-        if (!fused) launch_rmsnorm(SX, H, SXN, H, B, H, final_norm_, L.rms_eps, st);
-        timed(prof.lm_head, iters, [&](int) {
-            DecGemvArgs g;
-            g.M = B; g.N = L.vocab; g.K = H; g.W = lm_head_.W; g.ldw = H; g.wdtype = lm_head_.wdt; g.bias = lm_head_.b;
-            g.y = LG; g.ldy = L.vocab;
-            if (fused) {
-                g.x = SX; g.ldx = H; g.norm_w = final_norm_; g.eps = L.rms_eps;
-                if (B > 2) g.w_swz = lm_swz_;
-            } else { g.x = SXN; g.ldx = H; }
-            launch_dec_gemv(g, st);
-        });
-        prof.lm_head.bytes = (double)L.vocab * H * 2.0 + (double)B * (L.vocab + H) * 4.0;
-        prof.lm_head.flops = 2.0 * B * (double)L.vocab * H;
-        if (screen_applies(B, 1.0f)) {
-            // screened head: int8 lm_head + selection (no bookkeeping, no ban: side-effect free)
-            const LmHeadQ8Args q = head_q8_args(B);
-            DecSampleArgs ss;
-            ss.B = B; ss.V = L.vocab; ss.ld = L.vocab; ss.ctx = wsi("p_sctx", 64); ss.ctx_cap = 64;
-            ss.ctx_len = wsi("p_ctxlen", B); ss.ngram = 0; ss.out_tok = wsi("p_tok", B);
-            ss.blk_cnt = q.blk_cnt; ss.blk_t = q.blk_t; ss.cand = q.cand; ss.cand_hi = q.cand_hi; ss.nblk = q.nblk;
-            ss.slot = q.slot; ss.w_exact = lm_head_.W; ss.w_exact_wdt = lm_head_.wdt; ss.xn = q.xn_out; ss.K = H;
-            HIP_CHECK(hipMemsetAsync(ss.ctx_len, 0, B * 4, st));
-            timed(prof.lm_head_screened, iters, [&](int) {
-                launch_lmhead_q8(q, st);
-                launch_dec_sample(ss, st);
-            });
-            prof.lm_head_screened.bytes = (double)L.vocab * H + (double)L.vocab * 8.0 + (double)B * H * 4.0;
-            prof.lm_head_screened.flops = 2.0 * B * (double)L.vocab * H;
-        }
-    }
-    {
-        // attention-side GEMVs of every layer, replayed on scratch outputs
-        const int QKVN = layers_[0].qkv.N;
-        const float* SX = wsf("s_x", (size_t)B * H);
-        float* Y = wsf("p_qkv", (size_t)B * QKVN);
-        float* XO = wsf("p_xo", (size_t)B * H);
-        const int n = iters * L.layers;
-        const bool fuse_norm = B <= 2;
-        timed(prof.qkv, n, [&](int i) {
-            const DecLayer& d = layers_[i % L.layers];
-            DecGemvArgs g;
-            g.M = B; g.N = QKVN; g.K = H; g.W = d.qkv.W; g.ldw = H; g.wdtype = d.qkv.wdt; g.bias = d.qkv.b;
-            g.y = Y; g.ldy = QKVN; g.x = SX; g.ldx = H;
-            if (fuse_norm) { g.norm_w = d.in_norm.w; g.eps = L.rms_eps; }
-            launch_dec_gemv(g, st);
-        });
-        prof.qkv.bytes = (double)QKVN * H * 2.0 + (double)B * (H + QKVN) * 4.0;
-        prof.qkv.flops = 2.0 * B * (double)QKVN * H;
-        timed(prof.o_proj, n, [&](int i) {
-            const DecLayer& d = layers_[i % L.layers];
-            DecGemvArgs go;
-            go.M = B; go.N = H; go.K = L.heads * hd; go.x = SX; go.ldx = H; go.W = d.o.W; go.ldw = go.K;
-            go.wdtype = d.o.wdt; go.bias = d.o.b; go.y = XO; go.ldy = H; go.accumulate = 0;
-            launch_dec_gemv(go, st);
-        });
-        prof.o_proj.bytes = (double)H * L.heads * hd * 2.0 + (double)B * 2 * H * 4.0;
-        prof.o_proj.flops = 2.0 * B * (double)H * L.heads * hd;
-        std::vector<int> moe_l;
-        for (int l = 0; l < L.layers; ++l)
-            if (layers_[l].moe) moe_l.push_back(l);
-        if (!moe_l.empty() && moe_decode_route_launch(moe_args(moe_l[0], B, XO))) {
-            // the routing launches of the dispatch ([RMSNorm +] router GEMV [+ routing / grouping]; none when the
-            // gate/up launch routes itself)
-            timed(prof.router, iters * (int)moe_l.size(), [&](int i) {
-                MoeDecodeArgs ma = moe_args(moe_l[i % moe_l.size()], B, XO);
-                ma.x = SX;
-                launch_moe_decode(ma, st, MOE_ROUTE);
-            });
-            prof.router.bytes = (double)L.n_routed * H * 2.0 + (double)B * (H + L.n_routed) * 4.0;
-            prof.router.flops = 2.0 * B * (double)L.n_routed * H;
-        }
-    }
-    if (!(getenv("DSOCR_NO_GRAPH") && atoi(getenv("DSOCR_NO_GRAPH")) != 0)) {
-        // every decoder layer of one step as one hipGraph (what the decode loop replays, minus
-        // lm_head and selection); the residual stream is restored at the head of each replay and
-        // the KV slot written is the next free position (past every generated token)
-        float* X = wsf("s_x", (size_t)B * H);
-        float* X0 = wsf("p_x0", (size_t)B * H);
-        HIP_CHECK(hipMemcpyAsync(X0, X, (size_t)B * H * 4, hipMemcpyDeviceToDevice, st));
-        decode_step(B, Lmax);  // every workspace exists before capture
-        // the step graph, and the same graph without one kernel's launches: the difference per launch is
-        // that kernel's in-context cost (its dispatch and its place in the dependent chain included)
-        auto step_us = [&](int skip) {
-            hipGraph_t g = nullptr;
-            hipGraphExec_t ge = nullptr;
-            step_skip_ = skip;
-            capturing_ = true;
-            HIP_CHECK(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-            HIP_CHECK(hipMemcpyAsync(X, X0, (size_t)B * H * 4, hipMemcpyDeviceToDevice, st));
-            decode_step(B, Lmax);
-            HIP_CHECK(hipStreamEndCapture(st, &g));
-            capturing_ = false;
-            step_skip_ = 0;
-            HIP_CHECK(hipGraphInstantiate(&ge, g, nullptr, nullptr, 0));
-            const int n = std::max(8, iters * 4);
-            hipEvent_t e0, e1;
-            HIP_CHECK(hipEventCreate(&e0));
-            HIP_CHECK(hipEventCreate(&e1));
-            HIP_CHECK(hipGraphLaunch(ge, st));
-            HIP_CHECK(hipEventRecord(e0, st));
-            for (int i = 0; i < n; ++i) HIP_CHECK(hipGraphLaunch(ge, st));
-            HIP_CHECK(hipEventRecord(e1, st));
-            HIP_CHECK(hipEventSynchronize(e1));
-            const double us = 1000.0 * ms_between(e0, e1) / n;
-            (void)hipEventDestroy(e0);
-            (void)hipEventDestroy(e1);
-            (void)hipGraphExecDestroy(ge);
-            (void)hipGraphDestroy(g);
-            return us;
-        };
-        int n_moe = 0;
-        for (const DecLayer& d : layers_) n_moe += d.moe ? 1 : 0;
-        double full = step_us(0);
-        const double no_gu = n_moe ? step_us(SKIP_GATEUP) : full;
-        const double no_dn = n_moe ? step_us(SKIP_DOWN) : full;
-        const double no_at = step_us(SKIP_ATTN);
-        full = 0.5 * (full + step_us(0));  // bracket the variants: replay-to-replay drift averages out
-        prof.layers_step.avg_us = full;
-        prof.layers_step.launches = std::max(8, iters * 4);
-        if (n_moe) {
-            prof.moe_gateup.ctx_us = (full - no_gu) / n_moe;
-            prof.moe_down.ctx_us = (full - no_dn) / n_moe;
-        }
-        prof.attention.ctx_us = (full - no_at) / L.layers;
-        HIP_CHECK(hipMemcpyAsync(X, X0, (size_t)B * H * 4, hipMemcpyDeviceToDevice, st));
-        HIP_CHECK(hipStreamSynchronize(st));
-    }
+    float* CTX = wsf("p_ctx", (size_t)B * H);
+    time_launches(prof.attention, iters * L.layers, [&](int i) {
+        DecAttn2Args da = attn_args(i % L.layers, B, Lmax);
+        da.qkv = qkv0; da.kv_pos = d_pos; da.o = CTX;  // (the replays rewrite the K / V slot of pos - 1 from qkv0)
+        launch_dec_attn(da, st);
+    });
+    kv_slots(true);
+    // K and V of every attended key (f32 cache) + q/k/v row + context out
+    prof.attention.bytes = (double)keys * L.kv_heads * hd * 4.0 * 2.0 + (double)B * (QKVN + H) * 4.0;
+    prof.attention.flops = 4.0 * keys * L.heads * hd;
+    profile_gemvs(prof, iters, moe_layers);
+    if (graphs_on()) profile_step_context(prof, iters, (int)moe_layers.size());
     kv_slots(true);
     HIP_CHECK(hipStreamSynchronize(st));
     return prof;
+}
+
+// lm_head (exact and screened) and the attention-side GEMVs and routing of every layer, on scratch outputs
+void Engine::profile_gemvs(DecodeProfile& prof, int iters, const std::vector<int>& moe_layers) {
+    const LangConfig& L = cfg_.lang;
+    const int B = last_B_, H = L.hidden, hd = L.head_dim, QKVN = layers_[0].qkv.N;
+    hipStream_t st = stream_;
+    const float* SX = wsf("s_x", (size_t)B * H);
+    float* LG = wsf("p_logits", (size_t)B * L.vocab);
+    float* SXN = wsf("p_xn", (size_t)B * H);
+    ensure_mm_weights(B);
+    const bool fused = B <= 2 || (lm_swz_ && B <= 8);
+    if (!fused) launch_rmsnorm(SX, H, SXN, H, B, H, final_norm_, L.rms_eps, st);
+    time_launches(prof.lm_head, iters, [&](int) {
+        DecGemvArgs g;
+        g.M = B; g.N = L.vocab; g.K = H; g.W = lm_head_.W; g.ldw = H; g.wdtype = lm_head_.wdt; g.bias = lm_head_.b;
+        g.y = LG; g.ldy = L.vocab;
+        if (fused) {
+            g.x = SX; g.ldx = H; g.norm_w = final_norm_; g.eps = L.rms_eps;
+            if (B > 2) g.w_swz = lm_swz_;
+        } else { g.x = SXN; g.ldx = H; }
+        launch_dec_gemv(g, st);
+    });
+    prof.lm_head.bytes = (double)L.vocab * H * 2.0 + (double)B * (L.vocab + H) * 4.0;
+    prof.lm_head.flops = 2.0 * B * (double)L.vocab * H;
+    if (screen_applies(B, 1.0f)) {
+        // screened head: int8 lm_head + selection (no bookkeeping, no ban: side-effect free)
+        const LmHeadQ8Args q = head_q8_args(B);
+        DecSampleArgs ss;
+        ss.B = B; ss.V = L.vocab; ss.ld = L.vocab; ss.ctx = wsi("p_sctx", 64); ss.ctx_cap = 64;
+        ss.ctx_len = wsi("p_ctxlen", B); ss.ngram = 0; ss.out_tok = wsi("p_tok", B);
+        ss.blk_cnt = q.blk_cnt; ss.blk_t = q.blk_t; ss.cand = q.cand; ss.cand_hi = q.cand_hi; ss.nblk = q.nblk;
+        ss.slot = q.slot; ss.w_exact = lm_head_.W; ss.w_exact_wdt = lm_head_.wdt; ss.xn = q.xn_out; ss.K = H;
+        HIP_CHECK(hipMemsetAsync(ss.ctx_len, 0, B * 4, st));
+        time_launches(prof.lm_head_screened, iters, [&](int) {
+            launch_lmhead_q8(q, st);
+            launch_dec_sample(ss, st);
+        });
+        prof.lm_head_screened.bytes = (double)L.vocab * H + (double)L.vocab * 8.0 + (double)B * H * 4.0;
+        prof.lm_head_screened.flops = 2.0 * B * (double)L.vocab * H;
+    }
+    float* Y = wsf("p_qkv", (size_t)B * QKVN);
+    float* XO = wsf("p_xo", (size_t)B * H);
+    const int n = iters * L.layers;
+    const bool fuse_norm = B <= 2;
+    time_launches(prof.qkv, n, [&](int i) {
+        const DecLayer& d = layers_[i % L.layers];
+        DecGemvArgs g;
+        g.M = B; g.N = QKVN; g.K = H; g.W = d.qkv.W; g.ldw = H; g.wdtype = d.qkv.wdt; g.bias = d.qkv.b;
+        g.y = Y; g.ldy = QKVN; g.x = SX; g.ldx = H;
+        if (fuse_norm) { g.norm_w = d.in_norm.w; g.eps = L.rms_eps; }
+        launch_dec_gemv(g, st);
+    });
+    prof.qkv.bytes = (double)QKVN * H * 2.0 + (double)B * (H + QKVN) * 4.0;
+    prof.qkv.flops = 2.0 * B * (double)QKVN * H;
+    time_launches(prof.o_proj, n, [&](int i) {
+        const DecLayer& d = layers_[i % L.layers];
+        DecGemvArgs go;
+        go.M = B; go.N = H; go.K = L.heads * hd; go.x = SX; go.ldx = H; go.W = d.o.W; go.ldw = go.K;
+        go.wdtype = d.o.wdt; go.bias = d.o.b; go.y = XO; go.ldy = H; go.accumulate = 0;
+        launch_dec_gemv(go, st);
+    });
+    prof.o_proj.bytes = (double)H * L.heads * hd * 2.0 + (double)B * 2 * H * 4.0;
+    prof.o_proj.flops = 2.0 * B * (double)H * L.heads * hd;
+    if (!moe_layers.empty() && moe_decode_route_launch(moe_args(moe_layers[0], B, XO))) {
+        // the routing launches of the dispatch ([RMSNorm +] router GEMV [+ routing / grouping]; none when the
+        // gate/up launch routes itself)
+        time_launches(prof.router, iters * (int)moe_layers.size(), [&](int i) {
+            MoeDecodeArgs ma = moe_args(moe_layers[i % moe_layers.size()], B, XO);
+            ma.x = SX;
+            launch_moe_decode(ma, st, MOE_ROUTE);
+        });
+        prof.router.bytes = (double)L.n_routed * H * 2.0 + (double)B * (H + L.n_routed) * 4.0;
+        prof.router.flops = 2.0 * B * (double)L.n_routed * H;
+    }
+}
+
+// every decoder layer of one step as one hipGraph (what the decode loop replays, minus lm_head and
+// selection), and the same graph without one kernel's launches: the difference per launch is that kernel's
+// in-context cost (its dispatch and its place in the dependent chain included).  The residual stream is
+// restored at the head of each replay and the KV slot written is the next free position (past every
+// generated token)
+void Engine::profile_step_context(DecodeProfile& prof, int iters, int n_moe) {
+    const int B = last_B_, Lmax = last_Lmax_, H = cfg_.lang.hidden, n = std::max(8, iters * 4);
+    hipStream_t st = stream_;
+    float* X = wsf("s_x", (size_t)B * H);
+    float* X0 = wsf("p_x0", (size_t)B * H);
+    HIP_CHECK(hipMemcpyAsync(X0, X, (size_t)B * H * 4, hipMemcpyDeviceToDevice, st));
+    decode_step(B, Lmax);  // every workspace exists before capture
+    auto step_us = [&](int skip) {
+        ScopedSet skipping(step_skip_, skip);
+        return replay_us(n, [&] {
+            HIP_CHECK(hipMemcpyAsync(X, X0, (size_t)B * H * 4, hipMemcpyDeviceToDevice, st));
+            decode_step(B, Lmax);
+        });
+    };
+    double full = step_us(0);
+    const double no_gu = n_moe ? step_us(SKIP_GATEUP) : full;
+    const double no_dn = n_moe ? step_us(SKIP_DOWN) : full;
+    const double no_at = step_us(SKIP_ATTN);
+    full = 0.5 * (full + step_us(0));  // bracket the variants: replay-to-replay drift averages out
+    prof.layers_step.avg_us = full;
+    prof.layers_step.launches = n;
+    if (n_moe) {
+        prof.moe_gateup.ctx_us = (full - no_gu) / n_moe;
+        prof.moe_down.ctx_us = (full - no_dn) / n_moe;
+    }
+    prof.attention.ctx_us = (full - no_at) / cfg_.lang.layers;
+    HIP_CHECK(hipMemcpyAsync(X, X0, (size_t)B * H * 4, hipMemcpyDeviceToDevice, st));
+    HIP_CHECK(hipStreamSynchronize(st));
 }
 
 }  // namespace dsocr

@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstring>
+#include <functional>
 #include <map>
 #include <memory>
 #include <stdexcept>
@@ -14,15 +15,9 @@
 
 #include "../kernels/kernels.hpp"
 #include "config.hpp"
+#include "hip_raii.hpp"
 
 namespace dsocr {
-
-#define HIP_CHECK(x)                                                                                   \
-    do {                                                                                               \
-        hipError_t _e = (x);                                                                           \
-        if (_e != hipSuccess)                                                                          \
-            throw std::runtime_error(std::string("EDEVICE: ") + #x + ": " + hipGetErrorString(_e));    \
-    } while (0)
 
 struct Lin {
     void* W = nullptr;
@@ -225,17 +220,38 @@ class Engine {
     float* clip_pos(int tokens);
     // runs SAM+CLIP+projector on n images of size S; returns device rows [n*(S/64)^2][H] in buffer `out`
     float* vision_pass(const float* imgs, int n, int S, const std::string& out);
-    void prefill(int B, const std::vector<int>& rows_per_page, const float* x0, int Lmax);
     void decode_step(int B, int Lmax);
     // one page: every decoder layer of a step as one persistent launch (decode_persist.hip) when the model's
     // shape and dtypes fit it, all 256 workgroups are resident and DSOCR_PERSIST=1 (opt-in)
     bool persist_ok(int B, int Lmax);
     void ensure_persist();
     MoeDecodeArgs moe_args(int l, int B, float* X);
+    DecAttn2Args attn_args(int l, int B, int Lmax);
     void decode_head(int B, DecSampleArgs& sa, const SampleArgs& pen);
     void reserve_head_ws(int B);
     LmHeadQ8Args head_q8_args(int B);
     bool screen_applies(int B, float rep_penalty) const;
+    // generate(): the state of one call (engine.cpp) and its phases, in call order
+    struct GenState;
+    void embed_pages(GenState& g);
+    void plan_image_rows(GenState& g);
+    void reset_decode_state(GenState& g);
+    void forward_rows(GenState& g, const std::vector<int>& lens);
+    void init_sampling(GenState& g);
+    bool poll(GenState& g);
+    void stream_tokens(GenState& g, int n);
+    void decode_uncached(GenState& g);
+    void decode_cached(GenState& g);
+    void step_body(GenState& g);
+    void begin_spans(GenState& g);
+    void read_span_events(size_t step);
+    void collect_spans();
+    std::vector<std::vector<int64_t>> collect_outputs(GenState& g);
+    // profile_decode: its two timers and the sections after the MoE and attention replays
+    double replay_us(int n, const std::function<void()>& body);
+    void time_launches(KernelProfile& kp, int n, const std::function<void(int)>& body);
+    void profile_gemvs(DecodeProfile& prof, int iters, const std::vector<int>& moe_layers);
+    void profile_step_context(DecodeProfile& prof, int iters, int n_moe);
     void layer_forward_prefill(int l, int T, int B, const int* row_page, const int* row_pos, const long* q_off,
                                const long* kv_off, const long* o_off, const int* seq_len, int max_len, int Lmax);
 
@@ -301,7 +317,7 @@ class Engine {
     int span_cap_ = 0;
     std::vector<unsigned long long> spans_host_;
     int spans_steps_ = 0;
-    std::vector<hipEvent_t> span_ev_;           // [SPAN_KINDS][layers][2]
+    std::vector<HipEvent> span_ev_;             // [SPAN_KINDS][layers][2]
     std::vector<double> span_ev_ns_;            // [SPAN_KINDS][layers][span_cap_]
     int spans_kinds_ = SPAN_KINDS;
     bool chain_active_ = false;                 // a SPAN_CHAIN generate is running
@@ -322,7 +338,7 @@ class Engine {
     int persist_stamp_mode_ = 0;                // 1: the next generate records stamps of its decode steps
     int persist_stamp_pos0_ = 0, persist_stamp_cap_ = 0;
     std::vector<unsigned long long> persist_stamps_host_;
-    std::vector<hipEvent_t> persist_ev_;        // [steps][2] HIP events around each persistent launch (timing mode)
+    std::vector<HipEvent> persist_ev_;          // [steps][2] HIP events around each persistent launch (timing mode)
     std::vector<double> persist_ev_us_;
 
     void* dev_alloc(size_t bytes);

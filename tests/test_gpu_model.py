@@ -309,3 +309,50 @@ def test_tiny_stream_callback_every_token(tiny_engine):
     got = tiny_engine.generate(ids, None, None, None, DecodeParameters(max_new_tokens=6),
                                stream=lambda n, toks: seen.append((n, list(toks))), ignore_eos=True)
     assert [n for n, _ in seen] == list(range(1, 7)) and seen[-1][1] == got
+
+
+def _einval_generate(engine, ids, mask, page):
+    with pytest.raises(DsocrError) as e:
+        engine.generate(ids, mask, page, None, DecodeParameters(max_new_tokens=4))
+    assert e.value.status == 1, e.value.message
+    return e.value.message
+
+
+def test_engine_state_survives_einval(tiny_engine):
+    """A generate that throws (after the vision pass: mask mismatch; at the bounds check: a token id equal to the
+    vocab size; with chain spans requested) leaves the engine as it was: the next generate and the page's image
+    embeddings are what they were before the errors."""
+    tok = SyntheticTokenizer(512)
+    page = Page(_img(1, 300, 300), TINY_VS)
+    ids, mask = _prompt(tok, page)
+    p = DecodeParameters(max_new_tokens=8)
+    ref = tiny_engine.generate(ids, mask, page, None, p)
+    emb = tiny_engine.image_embeddings([page])[0].copy()
+    bad_mask = list(mask)
+    bad_mask[-1] = 1  # one extra <image> slot (the last text token)
+    assert "mismatch" in _einval_generate(tiny_engine, ids, bad_mask, page)
+    bad_ids = list(ids)
+    bad_ids[-1] = tiny_engine.vocab
+    assert "out of bounds" in _einval_generate(tiny_engine, bad_ids, mask, page)
+    tiny_engine.set_spans(4)
+    try:
+        assert "mismatch" in _einval_generate(tiny_engine, ids, bad_mask, page)
+    finally:
+        tiny_engine.set_spans(0)
+    assert tiny_engine.generate(ids, mask, page, None, p) == ref
+    assert np.array_equal(tiny_engine.image_embeddings([page])[0], emb)
+
+
+def test_profile_after_error(tiny_engine):
+    """profile_decode after a failed generate runs on the last good generate's state and leaves it intact
+    (no launch skipped, no capture left open, the K/V slots it rewrote put back): the same ids again."""
+    tok = SyntheticTokenizer(512)
+    page = Page(_img(1, 300, 300), TINY_VS)
+    ids, mask = _prompt(tok, page)
+    p = DecodeParameters(max_new_tokens=8)
+    ref = tiny_engine.generate(ids, mask, page, None, p)
+    bad_mask = list(mask)
+    bad_mask[-1] = 1
+    assert "mismatch" in _einval_generate(tiny_engine, ids, bad_mask, page)
+    tiny_engine.profile_decode(1)
+    assert tiny_engine.generate(ids, mask, page, None, p) == ref
