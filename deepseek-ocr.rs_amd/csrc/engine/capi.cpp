@@ -146,6 +146,20 @@ extern "C" {
 const char* dsocr_last_error(void) { return g_last_error.c_str(); }
 
 dsocr_status dsocr_engine_load(const dsocr_load_args* args, dsocr_engine** out) {
+    const char* e = getenv("DSOCR_DSQ_PACKED");
+    const bool packed = e && atoi(e) != 0 && args && args->snapshot_path;
+    return dsocr_engine_load_flags(args, packed ? DSOCR_LOAD_PACKED_EXPERTS : 0u, out);
+}
+
+dsocr_status dsocr_engine_packed_info(const dsocr_engine* e, size_t* packed_layers, size_t* moe_layers,
+                                      size_t* packed_bytes) {
+    return guarded([&] {
+        if (!e) throw std::runtime_error("EINVAL: NULL engine");
+        e->impl->packed_info(packed_layers, moe_layers, packed_bytes);
+    });
+}
+
+dsocr_status dsocr_engine_load_flags(const dsocr_load_args* args, uint32_t flags, dsocr_engine** out) {
     return guarded([&] {
         if (!args || !out) throw std::runtime_error("EINVAL: NULL argument");
         if (!args->config_path) throw std::runtime_error("EINVAL: config_path is required");
@@ -155,7 +169,7 @@ dsocr_status dsocr_engine_load(const dsocr_load_args* args, dsocr_engine** out) 
         try {
             e->impl.reset(new dsocr::Engine(args->config_path, args->weights_path ? args->weights_path : "",
                                             args->device_ordinal, (int)args->dtype, args->synthetic_seed,
-                                            args->snapshot_path ? args->snapshot_path : ""));
+                                            args->snapshot_path ? args->snapshot_path : "", flags));
         } catch (...) {
             delete e;
             throw;
@@ -796,6 +810,91 @@ dsocr_status dsocr_k_moe(int T, int H, int E, int topk, int I, int Is, const flo
             throw;
         }
         for (void* p : bufs) (void)hipFree(p);
+    });
+}
+dsocr_status dsocr_k_moe_packed(int T, int H, int E, int topk, int I, int Is, const float* x, const float* norm_w,
+                                float eps, const void* router_f16, int gu_qtype, const void* Wgu_payload, int d_qtype,
+                                const void* Wd_payload, int sgu_qtype, const void* sWgu_payload, int sd_qtype,
+                                const void* sWd_payload, int norm_topk, float scaling, float* out, int* ids_out,
+                                float* w_out) {
+    return guarded([&] {
+        if (T <= 0 || T > 8 || H <= 0 || E <= 0 || topk <= 0 || I <= 0 || Is < 0) throw std::runtime_error("EINVAL: bad MoE shape");
+        if (!x || !router_f16 || !Wgu_payload || !Wd_payload || !out) throw std::runtime_error("EINVAL: NULL argument");
+        const bool shared = sWgu_payload && sWd_payload && Is > 0;
+        if (!dsocr::dsq_packed_ok(gu_qtype, H) || !dsocr::dsq_packed_ok(d_qtype, I) ||
+            (shared && (!dsocr::dsq_packed_ok(sgu_qtype, H) || !dsocr::dsq_packed_ok(sd_qtype, Is))))
+            throw std::runtime_error("EINVAL: packed experts take Q4_K (in_dim % 256 == 0) or Q8_0 (in_dim % 32 == 0) records");
+        std::vector<void*> bufs;
+        auto alloc = [&](size_t b) {
+            void* p = nullptr;
+            check_hip(hipMalloc(&p, b ? b : 16), "hipMalloc");
+            bufs.push_back(p);
+            return p;
+        };
+        try {
+            const int TK = T * topk;
+            auto pack = [&](int qt, const void* payload, long rows, long in_dim) {
+                void* buf = alloc(dsocr::dsq_packed_bytes(qt, rows, in_dim));
+                dsocr::QMat m = dsocr::dsq_packed_view(qt, buf, rows, in_dim);
+                dsocr::launch_dsq_repack(m, 0, payload, rows, in_dim, nullptr);
+                return m;
+            };
+            dsocr::MoeDecodeArgs a;
+            a.T = T; a.H = H; a.E = E; a.topk = topk; a.I = I;
+            a.x = x; a.norm_w = norm_w; a.eps = eps; a.out = out;
+            a.router = router_f16; a.router_wdt = dsocr::WDT_F16; a.wdtype = dsocr::WDT_F16;
+            a.qWgu = pack(gu_qtype, Wgu_payload, (long)E * 2 * I, H);
+            a.qWd = pack(d_qtype, Wd_payload, (long)E * H, I);
+            if (shared) {
+                a.Is = Is;
+                a.qsWgu = pack(sgu_qtype, sWgu_payload, 2L * Is, H);
+                a.qsWd = pack(sd_qtype, sWd_payload, H, Is);
+                a.hs = (float*)alloc(sizeof(float) * (size_t)T * Is);
+            }
+            a.softmax_scoring = 1; a.norm_topk = norm_topk; a.scaling = scaling;
+            a.xn = (float*)alloc(sizeof(float) * (size_t)T * H);
+            a.xn_router = (float*)alloc(sizeof(float) * (size_t)T * H);
+            a.logits = (float*)alloc(sizeof(float) * (size_t)T * E);
+            a.ids = (int*)alloc(sizeof(int) * TK);
+            a.wts = (float*)alloc(sizeof(float) * TK);
+            a.h = (float*)alloc(sizeof(float) * (size_t)TK * I);
+            a.grp = (int*)alloc(sizeof(int) * dsocr::moe_grp_ints(E, T, topk));
+            a.route_cnt = (int*)alloc(sizeof(int) * 16);
+            check_hip(hipMemset(a.route_cnt, 0, sizeof(int) * 16), "hipMemset");
+            const char* gu = nullptr;
+            dsocr::moe_decode_kernel_names(a, &gu, nullptr);
+            if (std::string(gu) != "moe_gateup_q_kernel") throw std::runtime_error("EINVAL: packed decode MoE outside its range");
+            dsocr::launch_moe_decode(a, nullptr);
+            check_hip(hipGetLastError(), "moe launch");
+            check_hip(hipDeviceSynchronize(), "moe");
+            if (ids_out) check_hip(hipMemcpy(ids_out, a.ids, sizeof(int) * TK, hipMemcpyDeviceToHost), "d2h");
+            if (w_out) check_hip(hipMemcpy(w_out, a.wts, sizeof(float) * TK, hipMemcpyDeviceToHost), "d2h");
+        } catch (...) {
+            for (void* p : bufs) (void)hipFree(p);
+            throw;
+        }
+        for (void* p : bufs) (void)hipFree(p);
+    });
+}
+dsocr_status dsocr_k_dsq_rows_dot(int qtype, size_t rows, size_t in_dim, const void* payload, int T, const float* x,
+                                  float* y) {
+    return guarded([&] {
+        if (!dsocr::dsq_packed_ok(qtype, (long)in_dim) || rows == 0)
+            throw std::runtime_error("EINVAL: rows_dot takes Q4_K (in_dim % 256 == 0) or Q8_0 (in_dim % 32 == 0) rows");
+        if (T < 1 || T > 8 || !payload || !x || !y) throw std::runtime_error("EINVAL: rows_dot takes 1..8 token rows");
+        void* buf = nullptr;
+        check_hip(hipMalloc(&buf, dsocr::dsq_packed_bytes(qtype, (long)rows, (long)in_dim)), "hipMalloc");
+        try {
+            const dsocr::QMat m = dsocr::dsq_packed_view(qtype, buf, (long)rows, (long)in_dim);
+            dsocr::launch_dsq_repack(m, 0, payload, (long)rows, (long)in_dim, nullptr);
+            dsocr::launch_dsq_rows_dot(m, (long)rows, (long)in_dim, T, x, y, nullptr);
+            check_hip(hipGetLastError(), "rows_dot launch");
+            check_hip(hipDeviceSynchronize(), "rows_dot");
+        } catch (...) {
+            (void)hipFree(buf);
+            throw;
+        }
+        (void)hipFree(buf);
     });
 }
 dsocr_status dsocr_k_moe_kernels(int T, int H, int E, int topk, int I, int Is, int has_norm, const char** gateup,

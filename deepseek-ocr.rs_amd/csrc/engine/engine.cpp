@@ -190,8 +190,11 @@ void* Engine::ws(const std::string& name0, size_t bytes) {
 }
 
 Engine::Engine(const std::string& config_path, const std::string& weights_path, int device, int dtype, uint64_t seed,
-               const std::string& snapshot_path)
+               const std::string& snapshot_path, uint32_t load_flags)
     : device_(device), dtype_(dtype) {
+    if (load_flags & ~1u) throw std::runtime_error("EINVAL: unknown load flags");
+    if ((load_flags & 1u) && snapshot_path.empty())
+        throw std::runtime_error("EINVAL: packed experts need a .dsq snapshot (snapshot_path)");
     int n = 0;
     HIP_CHECK(hipGetDeviceCount(&n));
     if (device < 0 || device >= n) throw std::runtime_error("EDEVICE: no HIP device with ordinal " + std::to_string(device));
@@ -211,7 +214,7 @@ Engine::Engine(const std::string& config_path, const std::string& weights_path, 
     if (L.topk > 8) throw std::runtime_error("EINVAL: at most 8 experts per token supported");
     if (!snapshot_path.empty() && dtype != 1)
         throw std::runtime_error("EINVAL: .dsq snapshots load as fp16 (dequant-on-load): use dtype f16");
-    load_weights(weights_path, seed, snapshot_path);
+    load_weights(weights_path, seed, snapshot_path, (load_flags & 1u) != 0);
     ensure_rope(4096);
     ensure_small(64);
     HIP_CHECK(hipStreamSynchronize(stream_));
@@ -365,7 +368,19 @@ void Engine::ensure_rope(int len) {
 }
 
 // ============================================================================ loading
-void Engine::load_weights(const std::string& path, uint64_t seed, const std::string& snapshot_path) {
+void Engine::packed_info(size_t* packed_layers, size_t* moe_layers, size_t* packed_bytes) const {
+    size_t pl = 0, ml = 0, pb = 0;
+    for (const DecLayer& d : layers_) {
+        if (!d.moe) continue;
+        ++ml;
+        if (d.packed) { ++pl; pb += d.packed_bytes; }
+    }
+    if (packed_layers) *packed_layers = pl;
+    if (moe_layers) *moe_layers = ml;
+    if (packed_bytes) *packed_bytes = pb;
+}
+
+void Engine::load_weights(const std::string& path, uint64_t seed, const std::string& snapshot_path, bool packed_experts) {
     Source src;
     src.mode = dtype_;
     if (path.empty()) {
@@ -393,6 +408,39 @@ void Engine::load_weights(const std::string& path, uint64_t seed, const std::str
             HIP_CHECK(hipStreamSynchronize(stream_));
         };
     }
+    // packed experts: the records `names` (each rows_each x in_dim, one Q4_K / Q8_0 dtype for all, no bias) kept
+    // as one packed table in that order; records_qtype: their common dtype, -1 when one is missing or of another kind
+    auto records_qtype = [&](const std::vector<std::string>& names, long rows_each, long in_dim) -> int {
+        if (!snap || names.empty()) return -1;
+        int qt = -1;
+        for (const std::string& n : names) {
+            const DsqRecord* r = snap->find(n);
+            if (!r || r->has_bias || (long)r->out_dim != rows_each || (long)r->in_dim != in_dim) return -1;
+            if (qt < 0) qt = r->q_dtype;
+            if (r->q_dtype != qt || !dsq_packed_ok(qt, in_dim)) return -1;
+            if (r->q_len != dsq_payload_bytes(qt, rows_each, in_dim)) return -1;
+        }
+        return qt;
+    };
+    auto pack_records = [&](const std::vector<std::string>& names, long rows_each, long in_dim, QMat& out, size_t& bytes) {
+        const int qt = records_qtype(names, rows_each, in_dim);
+        if (qt < 0) throw std::logic_error("pack_records on records that were not checked");
+        const long total = rows_each * (long)names.size();
+        const size_t nbytes = dsq_packed_bytes(qt, total, in_dim);
+        void* buf = dev_alloc(nbytes);
+        out = dsq_packed_view(qt, buf, total, in_dim);
+        long row0 = 0;
+        for (const std::string& n : names) {
+            const DsqRecord* r = snap->find(n);
+            void* d_src = ws("load_dsq_src", r->q_len);
+            HIP_CHECK(hipMemcpyAsync(d_src, snap->payload(*r), r->q_len, hipMemcpyHostToDevice, stream_));
+            launch_dsq_repack(out, row0, d_src, rows_each, in_dim, stream_);
+            HIP_CHECK(hipGetLastError());
+            HIP_CHECK(hipStreamSynchronize(stream_));  // (the staging buffer is reused by the next record)
+            row0 += rows_each;
+        }
+        bytes += nbytes;
+    };
     auto up16 = [&](const HostMat& m) -> void* {
         void* p = dev_alloc(m.data.size() * 2);
         HIP_CHECK(hipMemcpy(p, m.data.data(), m.data.size() * 2, hipMemcpyHostToDevice));
@@ -581,6 +629,33 @@ void Engine::load_weights(const std::string& path, uint64_t seed, const std::str
                 d.has_shared = true;
                 d.s_gu = lin_cat({lp + "mlp.shared_experts.gate_proj", lp + "mlp.shared_experts.up_proj"}, {Is, Is}, H);
                 d.s_d = lin(lp + "mlp.shared_experts.down_proj", H, Is, true);
+            }
+            if (packed_experts && d.e_wdt == WDT_F16 && dec_route_grp_ok(8, E, H, L.topk)) {
+                // every routed and shared record Q4_K / Q8_0 (one dtype per matrix role): keep the blocks; any
+                // other layer runs the fp16 kernels
+                std::vector<std::string> gu_n, dn_n;
+                for (int e = 0; e < E; ++e) {
+                    const std::string ep = lp + "mlp.experts." + std::to_string(e) + ".";
+                    gu_n.push_back(ep + "gate_proj.weight");
+                    gu_n.push_back(ep + "up_proj.weight");
+                    dn_n.push_back(ep + "down_proj.weight");
+                }
+                const long Is = (long)I * L.n_shared;
+                const std::vector<std::string> sgu_n = {lp + "mlp.shared_experts.gate_proj.weight",
+                                                        lp + "mlp.shared_experts.up_proj.weight"};
+                const std::vector<std::string> sdn_n = {lp + "mlp.shared_experts.down_proj.weight"};
+                bool ok = records_qtype(gu_n, I, H) >= 0 && records_qtype(dn_n, H, I) >= 0;
+                if (ok && d.has_shared)
+                    ok = !d.s_gu.b && !d.s_d.b && records_qtype(sgu_n, Is, H) >= 0 && records_qtype(sdn_n, H, Is) >= 0;
+                if (ok) {
+                    pack_records(gu_n, I, H, d.q_gu, d.packed_bytes);
+                    pack_records(dn_n, H, I, d.q_d, d.packed_bytes);
+                    if (d.has_shared) {
+                        pack_records(sgu_n, Is, H, d.q_sgu, d.packed_bytes);
+                        pack_records(sdn_n, H, Is, d.q_sd, d.packed_bytes);
+                    }
+                    d.packed = true;
+                }
             }
         }
         layers_.push_back(d);
@@ -1045,6 +1120,9 @@ MoeDecodeArgs Engine::moe_args(int l, int B, float* X) {
         a.dn_part = wsf("s_dnpart", moe_down_mm_part_floats(E, B, K, I, a.Is, H));
         a.dn_tick = wsi("s_dntick", (size_t)H / 64 + 1);  // one ticket per 64-row tile
     }
+    if (B <= 8 && d.packed) {  // the packed decode kernels (decode_q.hip)
+        a.qWgu = d.q_gu; a.qWd = d.q_d; a.qsWgu = d.q_sgu; a.qsWd = d.q_sd;
+    }
     if (B <= 8 && d.e_gu_swz && (!d.has_shared || d.s_gu_swz)) {  // fragment-ordered experts
         a.Wgu_swz = d.e_gu_swz; a.Wd_swz = d.e_d_swz; a.sWgu_swz = d.s_gu_swz; a.sWd_swz = d.s_d_swz;
         if (!router_swz_off()) a.router_swz = d.router_swz;
@@ -1090,6 +1168,8 @@ bool Engine::persist_ok(int B, int Lmax) {
     const char* e = getenv("DSOCR_PERSIST");
     if (!e || atoi(e) == 0) return false;
     const LangConfig& L = cfg_.lang;
+    for (const DecLayer& d : layers_)
+        if (d.packed) return false;  // the persistent launch streams the fp16 experts only
     if (B != 1 || L.use_mla || L.rope_dim != L.head_dim || L.v_head_dim != L.head_dim || L.n_shared <= 0 ||
         L.topk_method != "greedy" || L.hidden_act != "silu")
         return false;
@@ -1379,7 +1459,7 @@ void Engine::ensure_mm_weights(int B) {
         if (!d.moe) swz(d.gu, d.gu_swz);
     }
     for (DecLayer& d : layers_) {
-        if (!d.moe || d.e_gu_swz || d.e_wdt != WDT_F16 || H % 32 || I % 32) continue;
+        if (!d.moe || d.packed || d.e_gu_swz || d.e_wdt != WDT_F16 || H % 32 || I % 32) continue;
         d.e_gu_swz = dev_alloc(mm_swizzle_elems(E * 2 * I, H) * 2);
         launch_mm_swizzle(d.e_gu, E * 2 * I, H, d.e_gu_swz, stream_);
         d.e_d_swz = dev_alloc(mm_swizzle_elems(E * H, I) * 2);
@@ -2220,6 +2300,14 @@ Engine::DecodeProfile Engine::profile_decode(int iters) {
         prof.moe_gateup.flops = 2.0 * (TK * 2.0 * I + B * 2.0 * Is) * H;
         prof.moe_down.bytes = (touched * I + Is) * H * 2.0 + (double)(TK * I + B * Is) * 4 + 2.0 * B * H * 4;
         prof.moe_down.flops = 2.0 * (TK * (double)I + B * Is) * H;
+        if (d0.packed && B <= 8) {
+            // packed layers stream the blocks: 144 bytes per 256 weights (Q4_K), 34 per 32 (Q8_0)
+            auto bpw = [](const QMat& m) { return m.qtype == DSQ_Q4K ? 144.0 / 256.0 : 34.0 / 32.0; };
+            prof.moe_gateup.bytes = (touched * 2.0 * I * bpw(d0.q_gu) + 2.0 * Is * (Is ? bpw(d0.q_sgu) : 0.0)) * H
+                                    + (double)B * H * 4 + (double)(TK * I + B * Is) * 4;
+            prof.moe_down.bytes = (touched * I * bpw(d0.q_d) + Is * (Is ? bpw(d0.q_sd) : 0.0)) * H
+                                  + (double)(TK * I + B * Is) * 4 + 2.0 * B * H * 4;
+        }
     }
     float* CTX = wsf("p_ctx", (size_t)B * H);
     time_launches(prof.attention, iters * L.layers, [&](int i) {

@@ -79,6 +79,11 @@ struct DecLayer {
     // the persistent one-page decode (decode_persist.hip): down projections transposed to [inter][H] rows
     void* e_dT = nullptr;         // routed [E][Im][H]
     void* s_dT = nullptr;         // shared [Is][H] (MoE) / dense [I][H]
+    // packed experts (DSOCR_LOAD_PACKED_EXPERTS): the snapshot's Q4_K / Q8_0 blocks kept for the packed decode
+    // kernels (decode_q.hip), beside the fp16 copies above; routed [E][2Im][H], [E][H][Im], shared [2Is][H], [H][Is]
+    bool packed = false;
+    QMat q_gu, q_d, q_sgu, q_sd;
+    size_t packed_bytes = 0;
 };
 
 struct PagePixels {
@@ -135,8 +140,10 @@ std::vector<uint32_t> rng_state_from_u64(uint64_t seed);
 class Engine {
   public:
     Engine(const std::string& config_path, const std::string& weights_path, int device, int dtype, uint64_t seed,
-           const std::string& snapshot_path = "");
+           const std::string& snapshot_path = "", uint32_t load_flags = 0);
     ~Engine();
+    // MoE layers that kept their packed blocks / all MoE layers / device bytes of the packed tables
+    void packed_info(size_t* packed_layers, size_t* moe_layers, size_t* packed_bytes) const;
 
     const ModelConfig& cfg() const { return cfg_; }
     // vision embeddings of pages (host output rows per page concatenated)
@@ -191,7 +198,7 @@ class Engine {
 
   private:
     // ---- loading
-    void load_weights(const std::string& path, uint64_t seed, const std::string& snapshot_path);
+    void load_weights(const std::string& path, uint64_t seed, const std::string& snapshot_path, bool packed_experts);
     // ---- workspace
     void* ws(const std::string& name, size_t bytes);
     float* wsf(const std::string& name, size_t n) { return (float*)ws(name, n * sizeof(float)); }

@@ -2802,7 +2802,8 @@ namespace {
 struct MoePlan {
     MoeDec2Args m;
     DecGemvArgs router;
-    int mode = 0;  // 0 mix (T = 1), 1 slot (T <= 2), 2 grouped (3..8), 3 sorted (T > 8)
+    int mode = 0;  // 0 mix (T = 1), 1 slot (T <= 2), 2 grouped (3..8), 3 sorted (T > 8), 4 packed grouped (T <= 8)
+    MoeQArgs q;    // mode 4: the packed launches' arguments (decode_q.hip)
     bool mix_dn = false;  // one token: the split-K down (moe_down_mix)
     bool route1 = false;  // grouped mode: dec_route_grp (norm + router + top-k + records, one launch);
                           // else dec_router's last-block epilogue writes the records
@@ -2839,6 +2840,21 @@ MoePlan moe_plan(const MoeDecodeArgs& a) {
     DecGemvArgs& gr = p.router;
     gr.M = T; gr.N = E; gr.K = a.H; gr.x = mx; gr.ldx = a.H; gr.W = a.router; gr.ldw = a.H; gr.wdtype = a.router_wdt;
     gr.bias = a.router_bias; gr.y = a.logits; gr.ldy = E; gr.norm_w = mnorm; gr.eps = a.eps; gr.span = a.route_span;
+    if (a.qWgu.q && T <= 8) {
+        // packed experts: dec_route_grp (norm + router + top-k + expert records, rows -> a.xn), then the
+        // grouped packed gate/up and down
+        MoeQArgs& q = p.q;
+        q.T = T; q.topk = K; q.E = E; q.H = a.H; q.I = a.I; q.slots = std::min(E, TK);
+        q.x = a.norm_w ? a.xn : a.x; q.grp = a.grp; q.Wgu = a.qWgu; q.Wd = a.qWd; q.h = a.h; q.out = a.out;
+        if (a.qsWgu.q && a.qsWd.q && a.Is > 0) { q.Is = a.Is; q.sWgu = a.qsWgu; q.sWd = a.qsWd; q.hs = a.hs; }
+        q.span = a.span;
+        if (dec_route_grp_ok(T, E, a.H, K) && a.route_cnt && a.grp && a.xn && moe_q_ok(q)) {
+            p.mode = 4;
+            p.route1 = true;
+            return p;
+        }
+        if (!a.Wgu || !a.Wd) throw std::runtime_error("EINVAL: packed decode MoE outside its range (T <= 8, E <= 64, H <= 1536)");
+    }
     if (T >= 3 && T <= 8 && dec_router_ok(T, E, a.H, K) && a.route_cnt && a.grp) {
         p.mode = 2;
         m.slot_mode = 1; m.slots = TK; m.grp = a.grp; m.aw = a.wts;
@@ -2892,6 +2908,7 @@ void moe_decode_kernel_names(const MoeDecodeArgs& a, const char** gateup, const 
     else if (p.mode == 1) gu = (a.T > 2 && a.Is) ? "moe_gateup_slot_kernel+moe_gateup_shared_kernel" : "moe_gateup_slot_kernel";
     else if (p.mode == 2) gu = p.gu_mm ? "moe_gateup_mm_kernel" : "moe_gateup_grp_kernel";
     if (p.mode == 2) dn = p.dn_mm ? "moe_down_mm_kernel" : "moe_down_grp_kernel";
+    else if (p.mode == 4) { gu = "moe_gateup_q_kernel"; dn = "moe_down_q_kernel"; }
     else if (p.mode <= 1) dn = p.mix_dn ? "moe_down_mix_kernel" : "moe_down_slot_kernel";
     if (gateup) *gateup = gu;
     if (down) *down = dn;
@@ -2929,14 +2946,16 @@ void launch_moe_decode(const MoeDecodeArgs& a, hipStream_t s, int parts) {
         }
     }
     if (parts & MOE_GATEUP) {
-        if (p.mode == 0) launch_moe_gateup_mix(m, a.xn_router, s);
+        if (p.mode == 4) launch_moe_gateup_q(p.q, s);
+        else if (p.mode == 0) launch_moe_gateup_mix(m, a.xn_router, s);
         else if (p.mode == 2 && p.route_in_gu) launch_moe_gateup_mm(p.mr, s);
         else if (p.mode == 2 && p.gu_mm) launch_moe_gateup_mm(m, s);
         else if (p.mode == 2) launch_moe_gateup_grp(m, s);
         else launch_moe_gateup2(m, s);
     }
     if (parts & MOE_DOWN) {
-        if (p.mode == 2 && p.dn_mm) launch_moe_down_mm(m, s);
+        if (p.mode == 4) launch_moe_down_q(p.q, s);
+        else if (p.mode == 2 && p.dn_mm) launch_moe_down_mm(m, s);
         else if (p.mode == 2) launch_moe_down_grp(m, s);
         else if (p.mix_dn) launch_moe_down_mix(m, s);
         else launch_moe_down2(m, s);

@@ -17,35 +17,12 @@
 #include <stdexcept>
 
 #include "dev_common.hpp"
+#include "dsq_decode.hpp"
 #include "kernels.hpp"
 
 #pragma clang fp contract(off)
 
 namespace dsocr {
-
-__device__ __forceinline__ float f16_at(const uint8_t* p) {
-    const uint16_t bits = (uint16_t)p[0] | ((uint16_t)p[1] << 8);
-    return f16_bits_to_f32(bits);
-}
-
-// the f32 value is pinned in a register first: otherwise the backend folds the last multiply and
-// the conversion into v_fma_mix(a, b, +0) — one rounding straight to f16 (not f32 then f16) and
-// -0 * x + 0 = +0 — which is not the reference's arithmetic
-__device__ __forceinline__ uint16_t to_f16_rne(float v) {
-    asm volatile("" : "+v"(v));
-    return __half_as_ushort(__float2half_rn(v));
-}
-
-// get_scale_min_k4 (GGML k-quants): 6-bit scale / min codes of sub-block j from the 12 packed bytes
-__device__ __forceinline__ void scale_min_k4(int j, const uint8_t* q, int& d, int& m) {
-    if (j < 4) {
-        d = q[j] & 63;
-        m = q[j + 4] & 63;
-    } else {
-        d = (q[j + 4] & 0xF) | ((q[j - 4] >> 6) << 4);
-        m = (q[j + 4] >> 4) | ((q[j] >> 6) << 4);
-    }
-}
 
 // Q4_K: 144 bytes / 256 values: d f16, dmin f16, scales[12], qs[128]; chunk c of 64 values uses
 // qs[32c .. 32c+31] (low nibbles first, then high nibbles) and sub-blocks 2c, 2c+1
@@ -60,10 +37,9 @@ __global__ __launch_bounds__(256) void dsq_q4k_kernel(const uint8_t* __restrict_
         scale_min_k4(2 * c + hi, blk + 4, sc, m);
         const uint8_t q = blk[16 + 32 * c + l];
         const int nib = hi ? (q >> 4) : (q & 0xF);
-        const float d1 = __fmul_rn(d, (float)sc);
-        const float m1 = __fmul_rn(dmin, (float)m);
-        const float y = __fsub_rn(__fmul_rn(d1, (float)nib), m1);
-        out[b * 256 + e] = to_f16_rne(y);
+        float d1, m1;
+        q4k_sub(d, dmin, sc, m, d1, m1);
+        out[b * 256 + e] = q4k_f16(d1, m1, nib);
     }
 }
 
@@ -96,8 +72,7 @@ __global__ __launch_bounds__(256) void dsq_q8_0_kernel(const uint8_t* __restrict
         if (b >= nblocks) continue;
         const uint8_t* blk = src + b * 34;
         const int i = threadIdx.x & 31;
-        const float y = __fmul_rn(f16_at(blk), (float)(int8_t)blk[2 + i]);
-        out[b * 32 + i] = to_f16_rne(y);
+        out[b * 32 + i] = q8_0_f16(f16_at(blk), (int)(int8_t)blk[2 + i]);
     }
 }
 

@@ -7,6 +7,14 @@ namespace dsocr {
 
 enum WDType : int { WDT_BF16 = 0, WDT_F16 = 1 };
 
+// A matrix kept in DSQ blocks for the packed decode kernels (decode_q.hip, layout described there): qtype
+// DSQ_Q4K (q: the 144-byte super-blocks, d unused) or DSQ_Q8_0 (q: int8 plane, d: f16 scale plane)
+struct QMat {
+    const void* q = nullptr;
+    const void* d = nullptr;
+    int qtype = 0;
+};
+
 // Profiling hook: while prof_events() holds a (start, stop) pair, the next kernel launched through
 // DSOCR_LAUNCH (decode.hip, lmhead.hip) records its own dispatch begin / end into the two events
 // (hipExtLaunchKernelGGL: the dispatch-packet timestamps rocprofv3's kernel trace reports) and the
@@ -411,6 +419,10 @@ struct MoeDecodeArgs {
     unsigned long long* span = nullptr;  // launch-span slots for the gate/up and down launches (or null)
     unsigned long long* route_span = nullptr;  // launch-span slots for the router launch (or null)
     unsigned long long* stamps = nullptr;      // dev: the grouped gate/up's phase clocks (MoeDec2Args::stamps)
+    // packed experts (decode_q.hip): when qWgu.q is set and T <= 8 the gate/up and down launches decode these
+    // Q4_K / Q8_0 tables instead of streaming the fp16 matrices above (which may then be null); routed
+    // [E][2I][H] and [E][H][I], shared [2Is][H] and [H][Is], made by launch_dsq_repack
+    QMat qWgu, qWd, qsWgu, qsWd;
 };
 // ---- one-page decode step as ONE persistent launch (decode_persist.hip): every decoder layer inside 256 resident
 // workgroups handing their vectors over as {f32, tag} granules (tag = the decode position; the granule buffer is
@@ -532,6 +544,30 @@ void launch_lmhead_quantize(const void* w, int V, int K, void* q, float* scale, 
 constexpr int DSQ_F32 = 0, DSQ_F16 = 1, DSQ_Q8_0 = 8, DSQ_Q4K = 12, DSQ_Q6K = 14, DSQ_BF16 = 16;
 size_t dsq_payload_bytes(int qtype, long out_dim, long in_dim);
 void launch_dsq_dequant(int qtype, const void* src, long out_dim, long in_dim, void* out_f16, hipStream_t s);
+
+// Packed decode from DSQ blocks (decode_q.hip).  Repack: a record-layout payload (device) of `rows` rows into
+// rows [dst_row0, dst_row0 + rows) of a packed table of dsq_packed_bytes(qtype, total rows, in_dim) bytes
+// (16-byte aligned) viewed by dsq_packed_view.  The decoded values are those of launch_dsq_dequant.
+bool dsq_packed_ok(int qtype, long in_dim);  // Q4_K / Q8_0 with whole blocks per row
+size_t dsq_packed_bytes(int qtype, long rows, long in_dim);
+QMat dsq_packed_view(int qtype, const void* packed, long rows, long in_dim);
+void launch_dsq_repack(const QMat& dst, long dst_row0, const void* payload, long rows, long in_dim, hipStream_t s);
+// y[T][rows] = x[T][in_dim] . W^T through the packed kernels' unpack (parity hook; T <= 8)
+void launch_dsq_rows_dot(const QMat& m, long rows, long in_dim, int T, const float* x, float* y, hipStream_t s);
+// Packed gate/up (+ SwiGLU, routing weight folded into h) and down (+ combine + residual) for T <= 8 tokens in
+// grouped form: the expert records of the router launch (MOE_GRP_* layout), x = the normalised rows [T][H]
+struct MoeQArgs {
+    int T = 0, topk = 0, E = 0, H = 0, I = 0, Is = 0, slots = 0;
+    const float* x = nullptr;
+    const int* grp = nullptr;
+    QMat Wgu, Wd, sWgu, sWd;
+    float* h = nullptr; float* hs = nullptr;   // [T*topk][I], [T][Is]
+    float* out = nullptr;                      // [T][H], += combined
+    unsigned long long* span = nullptr;        // launch-span slots (SPAN_SLOTS pairs) or null
+};
+bool moe_q_ok(const MoeQArgs& a);
+void launch_moe_gateup_q(const MoeQArgs& a, hipStream_t s);
+void launch_moe_down_q(const MoeQArgs& a, hipStream_t s);
 
 // Page preprocessing on the GPU (preprocess.hip): Pillow 22-bit bicubic (tap tables from the host),
 // then a vertical pass fused with canvas placement / tile cropping and the CHW normalisation

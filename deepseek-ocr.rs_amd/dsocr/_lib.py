@@ -73,6 +73,7 @@ class DotsTimingsC(C.Structure):
                 ("attention_ms", C.c_double), ("merger_ms", C.c_double), ("tokens", C.c_size_t), ("groups", C.c_size_t)]
 
 
+LOAD_PACKED_EXPERTS = 1  # DSOCR_LOAD_PACKED_EXPERTS
 STREAM_CB = C.CFUNCTYPE(None, C.c_size_t, C.POINTER(C.c_int64), C.c_void_p)
 
 # every symbol include/dsocr.h declares (tests check the library exports all of them)
@@ -89,6 +90,7 @@ EXPORTS = [
     "dsocr_engine_set_spans", "dsocr_engine_spans", "dsocr_k_qkv_attention", "dsocr_k_poll_wait_fits",
     "dsocr_engine_set_persist_stamps", "dsocr_engine_persist_info",
     "dsocr_resize_catmull_rom",
+    "dsocr_engine_load_flags", "dsocr_engine_packed_info", "dsocr_k_moe_packed", "dsocr_k_dsq_rows_dot",
 ]
 
 _lib = None
@@ -104,6 +106,8 @@ def lib():
     vp, sz, i32, u32, f32, i64 = C.c_void_p, C.c_size_t, C.c_int, C.c_uint32, C.c_float, C.c_int64
     L.dsocr_last_error.restype = C.c_char_p
     L.dsocr_engine_load.argtypes = [C.POINTER(LoadArgs), C.POINTER(vp)]
+    L.dsocr_engine_load_flags.argtypes = [C.POINTER(LoadArgs), u32, C.POINTER(vp)]
+    L.dsocr_engine_packed_info.argtypes = [vp, C.POINTER(sz), C.POINTER(sz), C.POINTER(sz)]
     L.dsocr_engine_free.argtypes = [vp]
     L.dsocr_engine_free.restype = None
     L.dsocr_engine_info.argtypes = [vp, C.POINTER(sz), C.POINTER(sz), C.POINTER(i64), C.POINTER(sz)]
@@ -160,6 +164,9 @@ def lib():
     L.dsocr_k_qkv_attention.argtypes = [i32, i32, i32, i32, i32, i32, f32, f32, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp,
                                         vp, C.POINTER(i32)]
     L.dsocr_k_poll_wait_fits.argtypes = [C.c_long, i32, i32]
+    L.dsocr_k_moe_packed.argtypes = [i32, i32, i32, i32, i32, i32, vp, vp, f32, vp, i32, vp, i32, vp, i32, vp, i32, vp,
+                                     i32, f32, vp, vp, vp]
+    L.dsocr_k_dsq_rows_dot.argtypes = [i32, sz, sz, vp, i32, vp, vp]
     L.dsocr_k_moe.argtypes = [i32, i32, i32, i32, i32, i32, vp, vp, f32, vp, vp, vp, vp, vp, i32, i32, f32, vp, vp, vp]
     L.dsocr_k_sample_greedy.argtypes = [i32, i32, vp, vp, i32, vp, i32, f32, vp]
     L.dsocr_k_sample_stoch.argtypes = [i32, i32, vp, vp, i32, vp, i32, f32, C.c_double, C.c_size_t, C.c_double,

@@ -50,6 +50,9 @@ def add_model_args(p: argparse.ArgumentParser) -> None:
     g.add_argument("--tokenizer", metavar="PATH", help="tokenizer.json (default: synthetic tokenizer)")
     g.add_argument("--weights", metavar="PATH", help="model .safetensors (default: synthetic weights)")
     g.add_argument("--snapshot", metavar="PATH", help="DSQ snapshot (.dsq) to dequantise on load")
+    g.add_argument("--snapshot-packed", action="store_true", default=None,
+                   help="decode the MoE experts from the snapshot's packed Q4_K / Q8_0 blocks (needs --snapshot; "
+                        "default: the DSOCR_DSQ_PACKED environment switch decides)")
     g.add_argument("--synthetic-seed", type=int, default=0, help="seed of the synthetic checkpoint")
 
 
@@ -166,6 +169,7 @@ def run_inference(args, out=sys.stdout, err=sys.stderr) -> int:
     events = []
     t0 = time.perf_counter()
     engine = load_model(ModelLoadArgs(config_path=config, weights_path=args.weights, snapshot_path=args.snapshot,
+                                      snapshot_packed=getattr(args, "snapshot_packed", None),
                                       device=device, dtype=args.dtype, synthetic_seed=args.synthetic_seed))
     load_ms = (time.perf_counter() - t0) * 1e3
     events.append(_event("model.load", load_ms, model=args.model, kind="Deepseek", device=f"hip:{device}",

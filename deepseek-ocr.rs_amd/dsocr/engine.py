@@ -18,7 +18,7 @@ from typing import Callable, Optional, Sequence
 
 import numpy as np
 
-from ._lib import (DTYPES, DecodeParamsC, DsocrError, LoadArgs, RequestC, ResultC, STREAM_CB, TimingsC,
+from ._lib import (DTYPES, LOAD_PACKED_EXPERTS, DecodeParamsC, DsocrError, LoadArgs, RequestC, ResultC, STREAM_CB, TimingsC,
                    VisionSettingsC, check, lib)
 
 
@@ -57,6 +57,10 @@ class ModelLoadArgs:
     config_path: Optional[str] = None
     weights_path: Optional[str] = None   # None -> deterministic synthetic checkpoint
     snapshot_path: Optional[str] = None
+    # MoE experts decoded from the snapshot's packed Q4_K / Q8_0 blocks at 1..8 decode tokens
+    # (DSOCR_LOAD_PACKED_EXPERTS): None = dsocr_engine_load (the DSOCR_DSQ_PACKED environment switch decides),
+    # True / False = dsocr_engine_load_flags
+    snapshot_packed: Optional[bool] = None
     device: int = 0
     dtype: str = "f16"
     synthetic_seed: int = 0
@@ -177,12 +181,22 @@ class DeepseekOcrEngine:
                       args.snapshot_path.encode() if args.snapshot_path else None, args.device, DTYPES[args.dtype],
                       args.synthetic_seed)
         h = C.c_void_p()
-        check(lib().dsocr_engine_load(C.byref(la), C.byref(h)))
+        if args.snapshot_packed is None:
+            check(lib().dsocr_engine_load(C.byref(la), C.byref(h)))
+        else:
+            check(lib().dsocr_engine_load_flags(C.byref(la), LOAD_PACKED_EXPERTS if args.snapshot_packed else 0,
+                                                C.byref(h)))
         self._h = h
         self.args = args
         hid, voc, eos, nl = C.c_size_t(), C.c_size_t(), C.c_int64(), C.c_size_t()
         check(lib().dsocr_engine_info(h, C.byref(hid), C.byref(voc), C.byref(eos), C.byref(nl)))
         self.hidden, self.vocab, self.eos_token_id, self.num_layers = hid.value, voc.value, eos.value, nl.value
+
+    def packed_info(self) -> dict:
+        """MoE layers decoding from packed snapshot blocks: {"packed_layers", "moe_layers", "packed_bytes"}."""
+        pl, ml, pb = C.c_size_t(), C.c_size_t(), C.c_size_t()
+        check(lib().dsocr_engine_packed_info(self._h, C.byref(pl), C.byref(ml), C.byref(pb)))
+        return {"packed_layers": pl.value, "moe_layers": ml.value, "packed_bytes": pb.value}
 
     # OcrEngine accessors (inference.rs:189-198)
     def kind(self):

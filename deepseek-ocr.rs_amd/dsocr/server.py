@@ -418,6 +418,7 @@ def main(argv=None) -> int:
     args = p.parse_args(argv)
     config = args.model_config or FULL_CONFIG
     engine = load_model(ModelLoadArgs(config_path=config, weights_path=args.weights, snapshot_path=args.snapshot,
+                                      snapshot_packed=getattr(args, "snapshot_packed", None),
                                       device=parse_device(args.device), dtype=args.dtype,
                                       synthetic_seed=args.synthetic_seed))
     state = ServerState(engine, load_tokenizer(args.tokenizer, _vocab_of(config)), args.model,

@@ -114,6 +114,20 @@ typedef struct {
 
 /* ---- engine lifecycle (load_model, model/mod.rs:90-115; DeepseekOcrModel::load 946-1105) */
 dsocr_status dsocr_engine_load(const dsocr_load_args* args, dsocr_engine** out);
+/* Load flags.  DSOCR_LOAD_PACKED_EXPERTS (needs snapshot_path, else DSOCR_EINVAL): every MoE layer whose routed
+ * and shared gate / up / down records are all Q4_K or Q8_0 (one dtype per matrix role) keeps those blocks on
+ * the device beside the fp16 copies, and decode steps of 1..8 tokens stream and decode the blocks in the
+ * gate/up and down launches instead of the fp16 matrices (each weight is the fp16 value dequant-on-load
+ * stores, so only the order of the f32 sums differs).  A layer with any other record kind, prefill, more
+ * than 8 tokens, attention, the dense layer and the lm_head run the fp16 kernels as without the flag.
+ * dsocr_engine_load(args, out) is dsocr_engine_load_flags(args, flags, out) with flags =
+ * DSOCR_LOAD_PACKED_EXPERTS when args carries a snapshot and the environment has DSOCR_DSQ_PACKED set to a
+ * non-zero value, else 0. */
+#define DSOCR_LOAD_PACKED_EXPERTS 1u
+dsocr_status dsocr_engine_load_flags(const dsocr_load_args* args, uint32_t flags, dsocr_engine** out);
+/* MoE layers that kept packed blocks, MoE layers in all, device bytes of the packed tables (any may be NULL) */
+dsocr_status dsocr_engine_packed_info(const dsocr_engine* e, size_t* packed_layers, size_t* moe_layers,
+                                      size_t* packed_bytes);
 void dsocr_engine_free(dsocr_engine* e);
 const char* dsocr_last_error(void);
 /* hidden size (image-row width), vocab, eos id, layers */
@@ -334,6 +348,21 @@ dsocr_status dsocr_k_moe(int T, int H, int E, int topk, int I, int Is, const flo
                          float eps, const void* router,
                          const void* Wgu, const void* Wd, const void* sWgu, const void* sWd, int wdtype,
                          int norm_topk, float scaling, float* out, int* topk_ids_out, float* topk_w_out);
+/* The same layer from packed DSQ blocks (T <= 8): payloads are raw record bytes in record layout on the
+ * device, experts concatenated — Wgu_payload rows [E][2I] of in_dim H (per expert the gate record then the up
+ * record), Wd_payload [E][H] of in_dim I, shared [2Is] of H and [H] of Is (NULL / Is = 0: no shared expert);
+ * qtypes 8 (Q8_0) or 12 (Q4_K).  The call repacks them as the engine does at load and runs the engine's packed
+ * dispatch (router f16 [E][H]).  DSOCR_EINVAL for another qtype or an in_dim that is not whole blocks. */
+dsocr_status dsocr_k_moe_packed(int T, int H, int E, int topk, int I, int Is, const float* x, const float* norm_w,
+                                float eps, const void* router_f16, int gu_qtype, const void* Wgu_payload, int d_qtype,
+                                const void* Wd_payload, int sgu_qtype, const void* sWgu_payload, int sd_qtype,
+                                const void* sWd_payload, int norm_topk, float scaling, float* out, int* topk_ids_out,
+                                float* topk_w_out);
+/* y[T][rows] = x[T][in_dim] . W^T (T <= 8, device pointers) with W a record-layout payload of qtype 8 / 12,
+ * through the engine's repack and the unpack function the packed MoE kernels call.  Terms with x == 0 are
+ * skipped and the sums start from -0, so a one-hot x row returns the decoded weights bit for bit. */
+dsocr_status dsocr_k_dsq_rows_dot(int qtype, size_t rows, size_t in_dim, const void* payload, int T, const float* x,
+                                  float* y);
 /* Kernel names launch_moe_decode picks for a decode MoE of T tokens (static strings), e.g. the bench's
  * roofline label: "moe_gateup_mix_kernel" at T = 1, "moe_gateup_grp_kernel" at T = 3..8. */
 dsocr_status dsocr_k_moe_kernels(int T, int H, int E, int topk, int I, int Is, int has_norm, const char** gateup,
