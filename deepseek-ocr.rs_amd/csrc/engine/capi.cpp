@@ -747,8 +747,17 @@ dsocr_status dsocr_k_moe(int T, int H, int E, int topk, int I, int Is, const flo
                          float eps, const void* router, const void* Wgu, const void* Wd, const void* sWgu,
                          const void* sWd, int wdtype, int norm_topk, float scaling, float* out, int* ids_out,
                          float* w_out) {
+    return dsocr_k_moe_ex(T, H, E, topk, I, Is, x, norm_w, eps, router, Wgu, Wd, sWgu, sWd, wdtype, norm_topk, scaling,
+                          out, ids_out, w_out, 1, nullptr, nullptr);
+}
+dsocr_status dsocr_k_moe_ex(int T, int H, int E, int topk, int I, int Is, const float* x, const float* norm_w,
+                            float eps, const void* router, const void* Wgu, const void* Wd, const void* sWgu,
+                            const void* sWd, int wdtype, int norm_topk, float scaling, float* out, int* ids_out,
+                            float* w_out, int softmax_scoring, const float* router_bias, float* logits_out) {
     return guarded([&] {
         if (T <= 0 || H <= 0 || E <= 0 || topk <= 0 || I <= 0) throw std::runtime_error("EINVAL: bad MoE shape");
+        if (E > 256 || topk > 8 || topk > E) throw std::runtime_error("EINVAL: decode MoE takes <= 256 experts, top_k <= min(8, E)");
+        if (!x || !router || !Wgu || !Wd || !out) throw std::runtime_error("EINVAL: NULL argument");
         std::vector<void*> bufs;
         auto alloc = [&](size_t b) {
             void* p = nullptr;
@@ -764,10 +773,11 @@ dsocr_status dsocr_k_moe(int T, int H, int E, int topk, int I, int Is, const flo
             a.T = T; a.H = H; a.E = E; a.topk = topk; a.I = I;
             a.x = x; a.norm_w = norm_w; a.eps = eps; a.out = out;
             a.router = router; a.router_wdt = wdtype; a.Wgu = Wgu; a.Wd = Wd; a.wdtype = wdtype;
+            a.router_bias = router_bias;
             if (sWgu && sWd && Is > 0) {
                 a.Is = Is; a.sWgu = sWgu; a.sWd = sWd; a.hs = (float*)alloc(sizeof(float) * (size_t)T * Is);
             }
-            a.softmax_scoring = 1; a.norm_topk = norm_topk; a.scaling = scaling;
+            a.softmax_scoring = softmax_scoring ? 1 : 0; a.norm_topk = norm_topk; a.scaling = scaling;
             a.xn = (float*)alloc(sizeof(float) * (size_t)T * H);
             a.xn_router = (float*)alloc(sizeof(float) * (size_t)T * H);
             a.logits = (float*)alloc(sizeof(float) * (size_t)T * E);
@@ -805,11 +815,36 @@ dsocr_status dsocr_k_moe(int T, int H, int E, int topk, int I, int Is, const flo
             check_hip(hipDeviceSynchronize(), "moe");
             if (ids_out) check_hip(hipMemcpy(ids_out, a.ids, sizeof(int) * TK, hipMemcpyDeviceToHost), "d2h");
             if (w_out) check_hip(hipMemcpy(w_out, a.wts, sizeof(float) * TK, hipMemcpyDeviceToHost), "d2h");
+            if (logits_out)
+                check_hip(hipMemcpy(logits_out, a.logits, sizeof(float) * (size_t)T * E, hipMemcpyDeviceToHost), "d2h");
         } catch (...) {
             for (void* p : bufs) (void)hipFree(p);
             throw;
         }
         for (void* p : bufs) (void)hipFree(p);
+    });
+}
+dsocr_status dsocr_k_moe_prefill_route(int T, int E, int topk, const float* logits, int softmax_scoring, int norm_topk,
+                                       float scaling, int* ids, float* w, int* eoff, int* arow, int* apos) {
+    return guarded([&] {
+        if (T <= 0 || E <= 0 || topk <= 0) throw std::runtime_error("EINVAL: bad routing shape");
+        if (E > 256 || topk > 8 || topk > E) throw std::runtime_error("EINVAL: routing takes <= 256 experts, top_k <= min(8, E)");
+        if (!logits || !ids || !w || !eoff || !arow || !apos) throw std::runtime_error("EINVAL: NULL argument");
+        // the prefill's two launches (Engine::layer_forward_prefill)
+        dsocr::launch_router_topk(logits, T, E, topk, softmax_scoring ? 1 : 0, norm_topk, scaling, ids, w, nullptr);
+        dsocr::launch_moe_group(ids, T, topk, E, eoff, arow, apos, nullptr, nullptr);
+        check_hip(hipGetLastError(), "prefill route launch");
+        check_hip(hipDeviceSynchronize(), "prefill route");
+    });
+}
+dsocr_status dsocr_k_moe_combine(int T, int topk, int H, const float* y, const int* apos, const float* w,
+                                 const float* shared, float* out, int accumulate) {
+    return guarded([&] {
+        if (T <= 0 || H <= 0 || topk <= 0 || topk > 8) throw std::runtime_error("EINVAL: bad combine shape");
+        if (!y || !apos || !w || !out) throw std::runtime_error("EINVAL: NULL argument");
+        dsocr::launch_moe_combine(y, apos, w, shared, T, topk, H, out, accumulate ? 1 : 0, nullptr);
+        check_hip(hipGetLastError(), "combine launch");
+        check_hip(hipDeviceSynchronize(), "combine");
     });
 }
 dsocr_status dsocr_k_moe_packed(int T, int H, int E, int topk, int I, int Is, const float* x, const float* norm_w,
@@ -914,6 +949,28 @@ dsocr_status dsocr_k_moe_kernels(int T, int H, int E, int topk, int I, int Is, i
         if (Is > 0) a.sWgu_swz = a.sWd_swz = &dummy;
         if (T > 8) { a.eoff = a.arow = a.apos = a.active = a.n_active = &dummy; a.aw = &fd; }
         dsocr::moe_decode_kernel_names(a, gateup, down);
+    });
+}
+dsocr_status dsocr_k_moe_route_kind(int T, int H, int E, int topk, int I, int Is, int has_norm, const char** kind) {
+    return guarded([&] {
+        if (!kind) throw std::runtime_error("EINVAL: NULL argument");
+        // the arguments dsocr_k_moe_ex builds for f16 weights (which workspaces and fragment-ordered copies exist)
+        dsocr::MoeDecodeArgs a;
+        a.T = T; a.H = H; a.E = E; a.topk = topk; a.I = I;
+        int dummy = 0;
+        float fd = 0.f;
+        a.x = &fd; a.out = &fd; a.norm_w = has_norm ? &fd : nullptr;
+        a.router = a.Wgu = a.Wd = &dummy;
+        if (Is > 0) { a.Is = Is; a.sWgu = &dummy; a.sWd = &dummy; a.hs = &fd; }
+        a.xn = a.xn_router = a.logits = a.wts = a.h = &fd;
+        a.ids = a.grp = a.route_cnt = &dummy;
+        if (H % 32 == 0 && I % 32 == 0 && T <= 8) {
+            a.Wgu_swz = a.Wd_swz = &dummy;
+            if (Is > 0 && Is % 32 == 0) a.sWgu_swz = a.sWd_swz = &dummy;
+        }
+        if (T >= 3 && T <= 8) { a.dn_part = &fd; a.dn_tick = &dummy; }
+        if (T > 8) { a.eoff = a.arow = a.apos = a.active = a.n_active = &dummy; a.aw = &fd; }
+        *kind = dsocr::moe_decode_route_kind(a);
     });
 }
 dsocr_status dsocr_k_lmhead_screened(int B, int V, int K, const float* x, const float* norm_w, float eps,

@@ -2900,6 +2900,16 @@ bool moe_decode_route_launch(const MoeDecodeArgs& a) {
     return !p.route_in_gu;
 }
 
+const char* moe_decode_route_kind(const MoeDecodeArgs& a) {
+    const MoePlan p = moe_plan(a);
+    if (p.mode == 0) return "moe_gateup_mix";    // topk_rank_pick in every routed wave
+    if (p.mode == 1) return "moe_gateup_slot";   // topk_select in the slot gate/up and down blocks
+    if (p.mode == 3) return "moe_route";         // route_token + group_assignments
+    if (p.route_in_gu) return "moe_gateup_mm";   // topk_wave64 inside the matrix-core gate/up
+    if (p.route1) return "dec_route_grp";        // topk_wave64 in the one-launch router (also the packed path)
+    return "dec_router";                         // topk_write in dec_router's last-block epilogue
+}
+
 void moe_decode_kernel_names(const MoeDecodeArgs& a, const char** gateup, const char** down) {
     const MoePlan p = moe_plan(a);
     const char* gu = "moe_gateup2_kernel";

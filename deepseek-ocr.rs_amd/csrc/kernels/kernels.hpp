@@ -476,6 +476,9 @@ enum MoeParts : int { MOE_ROUTE = 1, MOE_GATEUP = 2, MOE_DOWN = 4, MOE_ALL = 7 }
 // false when the routing runs inside the gate/up launch (3..8 tokens, DSOCR_ROUTE_FUSED): MOE_ROUTE launches nothing
 bool moe_decode_route_launch(const MoeDecodeArgs& a);
 void moe_decode_kernel_names(const MoeDecodeArgs& a, const char** gateup, const char** down);
+// which of the routing implementations the dispatch picks (static string): "moe_gateup_mix", "moe_gateup_slot",
+// "dec_route_grp", "moe_gateup_mm" (the router inside gate/up), "dec_router", "moe_route"
+const char* moe_decode_route_kind(const MoeDecodeArgs& a);
 void launch_moe_decode(const MoeDecodeArgs& a, hipStream_t s, int parts = MOE_ALL);
 // Greedy selection (ngram ban evaluated in-kernel) + step bookkeeping + KV advance.
 struct DecSampleArgs {

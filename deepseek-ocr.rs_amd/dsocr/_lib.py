@@ -91,6 +91,7 @@ EXPORTS = [
     "dsocr_engine_set_persist_stamps", "dsocr_engine_persist_info",
     "dsocr_resize_catmull_rom",
     "dsocr_engine_load_flags", "dsocr_engine_packed_info", "dsocr_k_moe_packed", "dsocr_k_dsq_rows_dot",
+    "dsocr_k_moe_ex", "dsocr_k_moe_route_kind", "dsocr_k_moe_prefill_route", "dsocr_k_moe_combine",
 ]
 
 _lib = None
@@ -168,7 +169,11 @@ def lib():
                                      i32, f32, vp, vp, vp]
     L.dsocr_k_dsq_rows_dot.argtypes = [i32, sz, sz, vp, i32, vp, vp]
     L.dsocr_k_moe.argtypes = [i32, i32, i32, i32, i32, i32, vp, vp, f32, vp, vp, vp, vp, vp, i32, i32, f32, vp, vp, vp]
-    L.dsocr_k_sample_greedy.argtypes = [i32, i32, vp, vp, i32, vp, i32, f32, vp]
+    L.dsocr_k_moe_ex.argtypes = L.dsocr_k_moe.argtypes + [i32, vp, vp]
+    L.dsocr_k_moe_route_kind.argtypes = [i32, i32, i32, i32, i32, i32, i32, C.POINTER(C.c_char_p)]
+    L.dsocr_k_moe_prefill_route.argtypes = [i32, i32, i32, vp, i32, i32, f32, vp, vp, vp, vp, vp]
+    L.dsocr_k_moe_combine.argtypes = [i32, i32, i32, vp, vp, vp, vp, vp, i32]
+    L.dsocr_k_sample_greedy.argtypes =[i32, i32, vp, vp, i32, vp, i32, f32, vp]
     L.dsocr_k_sample_stoch.argtypes = [i32, i32, vp, vp, i32, vp, i32, f32, C.c_double, C.c_size_t, C.c_double,
                                        C.c_uint64, i32, vp]
     _lib = L

@@ -348,6 +348,30 @@ dsocr_status dsocr_k_moe(int T, int H, int E, int topk, int I, int Is, const flo
                          float eps, const void* router,
                          const void* Wgu, const void* Wd, const void* sWgu, const void* sWd, int wdtype,
                          int norm_topk, float scaling, float* out, int* topk_ids_out, float* topk_w_out);
+/* dsocr_k_moe with the router's other options: softmax_scoring 0 = sigmoid scores, router_bias = the
+ * e_score_correction_bias added to the logits (device [E], or NULL), logits_out = the router logits the
+ * launches left in their workspace (host [T][E], or NULL).  dsocr_k_moe is this with (1, NULL, NULL).
+ * DSOCR_EINVAL for E > 256, top_k > 8, top_k > E or a NULL x / router / Wgu / Wd / out. */
+dsocr_status dsocr_k_moe_ex(int T, int H, int E, int topk, int I, int Is, const float* x, const float* norm_w,
+                            float eps, const void* router,
+                            const void* Wgu, const void* Wd, const void* sWgu, const void* sWd, int wdtype,
+                            int norm_topk, float scaling, float* out, int* topk_ids_out, float* topk_w_out,
+                            int softmax_scoring, const float* router_bias, float* logits_out);
+/* Which routing implementation the decode dispatch picks for dsocr_k_moe_ex at this shape with f16 weights
+ * (static string): "moe_gateup_mix" (one token, E <= 64), "moe_gateup_slot" (every gate/up block routes itself),
+ * "dec_route_grp" (3..8 tokens, E <= 64: norm + router + top-k + records in one launch), "moe_gateup_mm" (the same
+ * routing inside the matrix-core gate/up launch; DSOCR_ROUTE_FUSED=0 turns it off), "dec_router" (3..8 tokens,
+ * E > 64: the router GEMV's last block routes), "moe_route" (more than 8 tokens). */
+dsocr_status dsocr_k_moe_route_kind(int T, int H, int E, int topk, int I, int Is, int has_norm, const char** kind);
+/* The prefill's routing (block.rs:1243-1324) from given logits [T][E]: scores, greedy top-k -> ids / w [T][topk],
+ * then the grouping by expert: eoff [E + 1], arow [T topk] (sorted position -> token), apos [T topk]
+ * (assignment t topk + k -> sorted position).  Device pointers.  E <= 256, top_k <= min(8, E). */
+dsocr_status dsocr_k_moe_prefill_route(int T, int E, int topk, const float* logits, int softmax_scoring, int norm_topk,
+                                       float scaling, int* ids, float* w, int* eoff, int* arow, int* apos);
+/* The prefill's combine: out[t] (+)= sum_k w[t][k] * y[apos[t topk + k]] (+ shared[t]); y [T topk][H], shared
+ * [T][H] or NULL, accumulate != 0 adds to out.  Device pointers. */
+dsocr_status dsocr_k_moe_combine(int T, int topk, int H, const float* y, const int* apos, const float* w,
+                                 const float* shared, float* out, int accumulate);
 /* The same layer from packed DSQ blocks (T <= 8): payloads are raw record bytes in record layout on the
  * device, experts concatenated — Wgu_payload rows [E][2I] of in_dim H (per expert the gate record then the up
  * record), Wd_payload [E][H] of in_dim I, shared [2Is] of H and [H] of Is (NULL / Is = 0: no shared expert);

@@ -1,5 +1,7 @@
 """Device buffers for GPU tests through the C ABI's plain-pointer helpers (no torch)."""
 import ctypes as C
+import json
+import struct
 
 import numpy as np
 
@@ -49,3 +51,20 @@ def bf16_to_f32(b):
 
 def f16_bits(x):
     return np.ascontiguousarray(x, np.float32).astype(np.float16).view(np.uint16)
+
+
+def write_bf16_safetensors(path, tensors):
+    """name -> uint16 bf16 bits, written as a safetensors file with BF16 headers (safetensors.numpy has no bf16)."""
+    header, off, blobs = {}, 0, []
+    for n, a in tensors.items():
+        b = np.ascontiguousarray(a, np.uint16).tobytes()
+        header[n] = {"dtype": "BF16", "shape": list(a.shape), "data_offsets": [off, off + len(b)]}
+        blobs.append(b)
+        off += len(b)
+    h = json.dumps(header).encode()
+    h += b" " * ((8 - len(h) % 8) % 8)
+    with open(path, "wb") as f:
+        f.write(struct.pack("<Q", len(h)))
+        f.write(h)
+        for b in blobs:
+            f.write(b)

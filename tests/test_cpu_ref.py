@@ -15,9 +15,18 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TINY = os.path.join(ROOT, "deepseek-ocr.rs_amd", "dsocr", "configs", "tiny.json")
 
 
-@pytest.mark.parametrize("seed,P,n_img,max_new,ngram", [(3, 40, 12, 24, 20), (5, 17, 0, 30, 3), (9, 64, 30, 16, 20)])
-def test_cpu_ref_matches_oracle_tiny(seed, P, n_img, max_new, ngram):
+# router options of the language config: the tiny config's own (softmax, no renormalisation, scaling 1) and the
+# other branch of each (sigmoid scores, norm_topk_prob, routed_scaling_factor 2.5)
+ROUTER_OPTS = {"scoring_func": "sigmoid", "norm_topk_prob": True, "routed_scaling_factor": 2.5}
+
+
+@pytest.mark.parametrize("seed,P,n_img,max_new,ngram,lang_opts",
+                         [(3, 40, 12, 24, 20, None), (5, 17, 0, 30, 3, None), (9, 64, 30, 16, 20, None),
+                          (3, 40, 12, 24, 20, ROUTER_OPTS)],
+                         ids=["3-40-12-24-20", "5-17-0-30-3", "9-64-30-16-20", "3-40-12-24-20-sigmoid_norm_scaling"])
+def test_cpu_ref_matches_oracle_tiny(seed, P, n_img, max_new, ngram, lang_opts):
     cfg = json.load(open(TINY))
+    cfg["language_config"].update(lang_opts or {})
     rng = np.random.default_rng(seed)
     ids = rng.integers(2, 500, P).astype(np.int64)
     mask = np.zeros(P, np.uint8)

@@ -15,6 +15,7 @@ from dsocr import DecodeParameters, DsocrError, ModelLoadArgs, Page, VisionSetti
 from dsocr.synth import SyntheticTokenizer, synthetic_page
 from oracle.model import OracleModel, build_prompt_tokens as o_build
 from oracle.weights import Weights
+from _dev import write_bf16_safetensors as _write_bf16_safetensors
 
 pytestmark = pytest.mark.gpu
 
@@ -154,23 +155,6 @@ def test_safetensors_checkpoint_matches_synthetic(tiny_engine, tmp_path):
     assert eng.generate(ids, mask, page, None, p) == tiny_engine.generate(ids, mask, page, None, p)
     eng.close()
     del save_file, oc
-
-
-def _write_bf16_safetensors(path, tensors):
-    import struct
-    header, off, blobs = {}, 0, []
-    for n, a in tensors.items():
-        b = np.ascontiguousarray(a, np.uint16).tobytes()
-        header[n] = {"dtype": "BF16", "shape": list(a.shape), "data_offsets": [off, off + len(b)]}
-        blobs.append(b)
-        off += len(b)
-    h = json.dumps(header).encode()
-    h += b" " * ((8 - len(h) % 8) % 8)
-    with open(path, "wb") as f:
-        f.write(struct.pack("<Q", len(h)))
-        f.write(h)
-        for b in blobs:
-            f.write(b)
 
 
 # ------------------------------------------------------------------ full-size DeepSeek-OCR
