@@ -653,6 +653,68 @@ dsocr_status dsocr_k_attention_bf16(int n_seq, int L, int heads, int hd, float s
         check_hip(hipDeviceSynchronize(), "attention_bf16");
     });
 }
+dsocr_status dsocr_k_gemm_bf16(int M, int N, int K, const void* A, long lda, const void* W, long ldw, const float* bias,
+                               void* C, long ldc, int out_bf16, int accumulate, int variant, int group_m, int swiglu,
+                               const float* rope_cos, const float* rope_sin, int rope_cols) {
+    return guarded([&] {
+        if (!A || !W || !C || M < 0 || N < 1 || K < 1) throw std::runtime_error("EINVAL: bad gemm_bf16 arguments");
+        if (lda < K || ldw < K || ldc < (swiglu ? N / 2 : N)) throw std::runtime_error("EINVAL: row strides too small");
+        if (variant != 0 && variant != 2 && variant != 3) throw std::runtime_error("EINVAL: variant must be 0, 2 or 3");
+        // variant 3 names the ping-pong kernel: refuse what the launcher would quietly hand to the 128 x 128 one
+        if (variant == 3 && (!out_bf16 || ldc % 8 || (reinterpret_cast<uintptr_t>(C) & 15)))
+            throw std::runtime_error("EINVAL: the ping-pong kernel needs bf16 out and 16-byte aligned C rows");
+        dsocr::GemmBf16Args g;
+        g.M = M; g.N = N; g.K = K; g.A = A; g.lda = lda; g.W = W; g.ldw = ldw; g.bias = bias;
+        g.C = reinterpret_cast<float*>(C); g.ldc = ldc; g.out_bf16 = out_bf16; g.accumulate = accumulate;
+        g.variant = variant; g.group_m = group_m; g.swiglu = swiglu;
+        g.rope_cos = rope_cos; g.rope_sin = rope_sin; g.rope_cols = rope_cols;
+        dsocr::launch_gemm_bf16(g, nullptr);
+        check_hip(hipGetLastError(), "gemm_bf16 launch");
+        check_hip(hipDeviceSynchronize(), "gemm_bf16");
+    });
+}
+dsocr_status dsocr_k_dots_op(int op, long rows, int cols, int aux, long ld, const void* x, const float* p0,
+                             const float* p1, float eps, void* y) {
+    return guarded([&] {
+        if (!y || rows < 0 || cols < 1) throw std::runtime_error("EINVAL: bad dots_op arguments");
+        auto need = [](bool ok, const char* what) {
+            if (!ok) throw std::runtime_error(std::string("EINVAL: dots_op needs ") + what);
+        };
+        switch (op) {
+        case DSOCR_DOTS_RMSNORM:
+            need(x && p0, "x and w");
+            dsocr::launch_dots_rmsnorm(x, aux, rows, cols, p0, eps, y, nullptr);
+            break;
+        case DSOCR_DOTS_LAYERNORM:
+            need(x && p0 && p1, "x, w and b");
+            dsocr::launch_dots_layernorm(x, rows, cols, p0, p1, eps, y, nullptr);
+            break;
+        case DSOCR_DOTS_SWIGLU:
+            need(x, "gu");
+            dsocr::launch_dots_swiglu(x, rows, cols, y, nullptr);
+            break;
+        case DSOCR_DOTS_GELU:
+            dsocr::launch_dots_gelu(y, rows * (long)cols, nullptr);
+            break;
+        case DSOCR_DOTS_ROPE_QK:
+            need(x && p0 && p1 && aux > 0, "qkv, cos, sin and a head count");
+            dsocr::launch_dots_rope_qk(x, rows, aux, cols, p0, p1, y, nullptr);
+            break;
+        case DSOCR_DOTS_TO_BF16:
+            need(x && ld >= cols && aux >= cols, "x and row strides >= cols");
+            dsocr::launch_dots_to_bf16(reinterpret_cast<const float*>(x), rows, cols, ld, y, aux, nullptr);
+            break;
+        case DSOCR_DOTS_BF16_TO_F32:
+            need(x, "x");
+            dsocr::launch_dots_bf16_to_f32(x, rows * (long)cols, reinterpret_cast<float*>(y), nullptr);
+            break;
+        default:
+            throw std::runtime_error("EINVAL: unknown dots op " + std::to_string(op));
+        }
+        check_hip(hipGetLastError(), "dots_op launch");
+        check_hip(hipDeviceSynchronize(), "dots_op");
+    });
+}
 dsocr_status dsocr_k_decode_attention(int B, int heads, int kv_heads, int hd, int rope_dim, int max_len, float scale,
                                       const float* qkv, const float* cos, const float* sin, float* kc, float* vc,
                                       const int* kv_pos, float* o, int prerot) {

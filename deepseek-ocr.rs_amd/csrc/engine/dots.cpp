@@ -19,16 +19,6 @@
 
 namespace dsocr {
 
-void launch_dots_rmsnorm(const void* x, int in_f32, long rows, int D, const float* w, float eps, void* y, hipStream_t s);
-void launch_dots_layernorm(const void* x, long rows, int D, const float* w, const float* b, float eps, void* y,
-                           hipStream_t s);
-void launch_dots_swiglu(const void* gu, long N, int I, void* h, hipStream_t s);
-void launch_dots_rope_qk(const void* qkv, long N, int heads, int hd, const float* cos_t, const float* sin_t, void* out,
-                         hipStream_t s);
-void launch_dots_gelu(void* x, long n, hipStream_t s);
-void launch_dots_to_bf16(const float* x, long N, int D, long ldi, void* y, int ldo, hipStream_t s);
-void launch_dots_bf16_to_f32(const void* x, long n, float* y, hipStream_t s);
-
 DotsConfig parse_dots_config(const Json& root) {
     DotsConfig c;
     const Json& v = root.has("vision_config") ? root["vision_config"] : root;

@@ -282,7 +282,7 @@ static void launch_splitk_reduce(const GemmBf16Args& g, hipStream_t s) {
 // XOR-swizzled by the SOURCE address (chunk ^ ((row >> 2) & 3)), which puts every ds_read_b128 lane group
 // on 16 distinct slots of the 256-byte bank row.  Every output element sees the same MFMA sequence as
 // gemm_bf16_nt_kernel (k ascending, 16 per instruction), so the results are bitwise equal to it
-// (tools/kbench dgemm compares them).
+// (tests/test_dots_kernels.py asserts it at ragged shapes, tools/kbench dgemm at the tower's).
 constexpr int PP_M = 256, PP_N = 256, PP_K = 32, PP_NST = 4;
 constexpr int PP_STAGE = (PP_M + PP_N) * PP_K;  // bf16 elements per stage (32 KiB)
 constexpr int PP_LDS = PP_NST * PP_STAGE * 2;    // bytes

@@ -175,6 +175,23 @@ struct RopeKvArgs {
 };
 void launch_rope_kv(const RopeKvArgs& a, hipStream_t s);
 
+// ------------------------------------------------------------------ dots.ocr tower row ops (dots_ops.hip)
+// bf16 tensors as uint16_t bits; every op computes in f32 and rounds its output to bf16 (RNE)
+// y = rnd(x / sqrt(mean(x^2) + eps) * w); x bf16 or (in_f32) f32 rows [rows][D]; y may alias a bf16 x
+void launch_dots_rmsnorm(const void* x, int in_f32, long rows, int D, const float* w, float eps, void* y, hipStream_t s);
+void launch_dots_layernorm(const void* x, long rows, int D, const float* w, const float* b, float eps, void* y,
+                           hipStream_t s);
+// gu [N][2I] = [fc1 | fc3] -> h [N][I] = rnd(silu(g) * u)
+void launch_dots_swiglu(const void* gu, long N, int I, void* h, hipStream_t s);
+// rotary of the q | k columns of qkv [N][3 * heads * hd] into out (the v columns of out are not written);
+// cos / sin f32 [N][hd]
+void launch_dots_rope_qk(const void* qkv, long N, int heads, int hd, const float* cos_t, const float* sin_t, void* out,
+                         hipStream_t s);
+void launch_dots_gelu(void* x, long n, hipStream_t s);  // in place
+// f32 rows [N][ldi] (first D columns) -> bf16 rows [N][ldo], zero padding up to ldo
+void launch_dots_to_bf16(const float* x, long N, int D, long ldi, void* y, int ldo, hipStream_t s);
+void launch_dots_bf16_to_f32(const void* x, long n, float* y, hipStream_t s);
+
 // ------------------------------------------------------------------ misc (misc.hip)
 void launch_patch_im2col(const float* img, int n, int H, int W, int ps, float* cols, hipStream_t s);
 void launch_conv_im2col_nhwc(const float* x, int n, int H, int W, int C, int kh, int kw, int stride, int pad,

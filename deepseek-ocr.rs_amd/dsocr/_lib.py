@@ -92,7 +92,11 @@ EXPORTS = [
     "dsocr_resize_catmull_rom",
     "dsocr_engine_load_flags", "dsocr_engine_packed_info", "dsocr_k_moe_packed", "dsocr_k_dsq_rows_dot",
     "dsocr_k_moe_ex", "dsocr_k_moe_route_kind", "dsocr_k_moe_prefill_route", "dsocr_k_moe_combine",
+    "dsocr_k_gemm_bf16", "dsocr_k_dots_op",
 ]
+
+# dsocr_k_dots_op op codes (DSOCR_DOTS_*)
+DOTS_RMSNORM, DOTS_LAYERNORM, DOTS_SWIGLU, DOTS_GELU, DOTS_ROPE_QK, DOTS_TO_BF16, DOTS_BF16_TO_F32 = range(7)
 
 _lib = None
 
@@ -127,6 +131,9 @@ def lib():
     L.dsocr_generate_trace.argtypes = [vp, sz, C.POINTER(RequestC), C.POINTER(DecodeParamsC), C.POINTER(ResultC), vp,
                                        sz]
     L.dsocr_k_attention_bf16.argtypes = [i32, i32, i32, i32, f32, vp, C.c_long, vp, C.c_long, i32]
+    L.dsocr_k_gemm_bf16.argtypes = [i32, i32, i32, vp, C.c_long, vp, C.c_long, vp, vp, C.c_long, i32, i32, i32, i32, i32,
+                                    vp, vp, i32]
+    L.dsocr_k_dots_op.argtypes = [i32, C.c_long, i32, i32, C.c_long, vp, vp, vp, f32, vp]
     L.dsocr_dots_load.argtypes = [C.c_char_p, C.c_char_p, C.c_uint64, i32, C.POINTER(vp)]
     L.dsocr_dots_free.argtypes = [vp]
     L.dsocr_dots_free.restype = None

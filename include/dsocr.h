@@ -314,6 +314,31 @@ dsocr_status dsocr_k_attention(int n_seq, int L, int heads, int hd, float scale,
  * f32 (o_bf16 = 0) or bf16 (o_bf16 = 1, RNE). */
 dsocr_status dsocr_k_attention_bf16(int n_seq, int L, int heads, int hd, float scale, const void* qkv, long ld,
                                     void* o, long o_ld, int o_bf16);
+/* The dots.ocr tower's linear (quant.rs:124-160 on bf16 tensors): A bf16 [M][lda], W bf16 [N][ldw], bias f32 [N]
+ * or NULL, K % 64 == 0.  out_bf16 = 1: C bf16 [M][ldc] with every reference op rounded on its own,
+ * v = rnd(A W^T); bias: v = rnd(v + b); accumulate: v = rnd(C + v); out_bf16 = 0: C f32.  variant 0: the engine's
+ * dispatch; 2: the 128 x 128 kernel with two LDS stages; 3: the 256 x 256 ping-pong kernel (bf16 out, ldc % 8 == 0).
+ * group_m: M bands per raster group (-1 the default).  swiglu != 0: W rows and bias interleaved per 32
+ * (fc1 32b..32b+31, then fc3 32b..32b+31), N = 2 I, C = h [M][ldc] of I columns.  rope_cos / rope_sin (f32
+ * [M][128], or NULL): columns below rope_cols (a multiple of 256) are heads of 128 dims, rotated in the epilogue. */
+dsocr_status dsocr_k_gemm_bf16(int M, int N, int K, const void* A, long lda, const void* W, long ldw, const float* bias,
+                               void* C, long ldc, int out_bf16, int accumulate, int variant, int group_m, int swiglu,
+                               const float* rope_cos, const float* rope_sin, int rope_cols);
+/* One row op of the dots.ocr tower (dots_vit.rs) on bf16 tensors, f32 math, bf16 (RNE) out:
+ *  RMSNORM     x [rows][cols] bf16 (aux = 0) or f32 (aux = 1), p0 = w, eps; y bf16 (may alias a bf16 x)
+ *  LAYERNORM   x bf16 [rows][cols], p0 = w, p1 = b, eps
+ *  SWIGLU      x = [fc1 | fc3] bf16 [rows][2 cols]; y = rnd(silu(g) * u) [rows][cols]
+ *  GELU        y bf16 [rows][cols] in place (x unused)
+ *  ROPE_QK     x = q|k|v bf16 [rows][3 aux cols] (aux heads of cols dims), p0 = cos, p1 = sin f32 [rows][cols];
+ *              y gets the rotated q | k columns (its v columns are not written)
+ *  TO_BF16     x f32 [rows][ld] (first cols columns) -> y bf16 [rows][aux], zeros from column cols on
+ *  BF16_TO_F32 x bf16 -> y f32, rows * cols values */
+enum {
+    DSOCR_DOTS_RMSNORM = 0, DSOCR_DOTS_LAYERNORM = 1, DSOCR_DOTS_SWIGLU = 2, DSOCR_DOTS_GELU = 3,
+    DSOCR_DOTS_ROPE_QK = 4, DSOCR_DOTS_TO_BF16 = 5, DSOCR_DOTS_BF16_TO_F32 = 6
+};
+dsocr_status dsocr_k_dots_op(int op, long rows, int cols, int aux, long ld, const void* x, const float* p0,
+                             const float* p1, float eps, void* y);
 /* Decode attention step (block.rs:608-789 at seq_len 1, rope block.rs:1403-1471): for page b the
  * token at position pos = kv_pos[b] has its q / k rotated (cos/sin tables [max_len][rope_dim]; prerot != 0:
  * the q / k rows of qkv are already rotated), k and v appended to the f32 cache [B][kv_heads][max_len][hd]
