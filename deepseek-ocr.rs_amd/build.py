@@ -24,7 +24,7 @@ CLANG = os.environ.get("DSOCR_CXX", "/opt/rocm/llvm/bin/clang++")
 ARCH = "gfx950"
 
 KERNELS = ["gemm", "gemm_bf16", "moe", "norm", "attention", "misc", "decode", "lmhead", "dsq", "preprocess", "sampling",
-           "dots_ops", "attention_bf16", "decode_mm", "decode_persist", "decode_q"]
+           "dots_ops", "attention_bf16", "decode_mm", "decode_persist", "decode_q", "attention_prefix", "ocr2_ops"]
 HOST = ["engine", "dots", "capi"]
 
 

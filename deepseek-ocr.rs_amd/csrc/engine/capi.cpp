@@ -141,6 +141,9 @@ dsocr::GenRequest to_request(const dsocr_request& r) {
 }
 }  // namespace
 
+static dsocr_status prepare_page_device_as(dsocr_engine* e, const uint8_t* rgb, uint32_t w, uint32_t h,
+                                           const dsocr_vision_settings* vs, int variant, dsocr_page_pixels** out);
+
 extern "C" {
 
 const char* dsocr_last_error(void) { return g_last_error.c_str(); }
@@ -193,21 +196,56 @@ dsocr_status dsocr_engine_info(const dsocr_engine* e, size_t* hidden, size_t* vo
 
 dsocr_status dsocr_prepare_page(const uint8_t* rgb, uint32_t w, uint32_t h, const dsocr_vision_settings* vs,
                                 dsocr_page_pixels** out) {
+    return dsocr_prepare_page_variant(rgb, w, h, vs, 0, out);
+}
+
+dsocr_status dsocr_config_variant(const char* config_path, int* variant, uint32_t* sam_out_channels, uint32_t* encoder) {
+    return guarded([&] {
+        if (!config_path) throw std::runtime_error("EINVAL: config_path is required");
+        std::ifstream f(config_path);
+        if (!f) throw std::runtime_error(std::string("ENOENT: cannot read config ") + config_path);
+        std::stringstream ss;
+        ss << f.rdbuf();
+        const dsocr::ModelConfig c = dsocr::resolve_config(dsocr::Json::parse(ss.str()));
+        if (variant) *variant = c.variant;
+        if (sam_out_channels) { sam_out_channels[0] = c.sam.out_ch[0]; sam_out_channels[1] = c.sam.out_ch[1]; }
+        if (encoder) {
+            const bool o2 = c.variant == dsocr::VARIANT_OCR2;
+            const dsocr::Qwen2EncConfig& q = c.enc;
+            const uint32_t v[5] = {(uint32_t)q.dim, (uint32_t)q.layers, (uint32_t)q.heads, (uint32_t)q.kv_heads, (uint32_t)q.inter};
+            for (int i = 0; i < 5; ++i) encoder[i] = o2 ? v[i] : 0u;
+        }
+    });
+}
+
+dsocr_status dsocr_engine_variant(const dsocr_engine* e, int* variant) {
+    return guarded([&] {
+        if (!e || !variant) throw std::runtime_error("EINVAL: NULL argument");
+        *variant = e->impl->variant();
+    });
+}
+
+dsocr_status dsocr_prepare_page_variant(const uint8_t* rgb, uint32_t w, uint32_t h, const dsocr_vision_settings* vs,
+                                        int variant, dsocr_page_pixels** out) {
     return guarded([&] {
         if (!rgb || !vs || !out) throw std::runtime_error("EINVAL: NULL argument");
+        if (variant != 0 && variant != 1) throw std::runtime_error("EINVAL: variant must be 0 (DeepSeek-OCR) or 1 (DeepSeek-OCR-2)");
         std::unique_ptr<dsocr_page_pixels> p(new dsocr_page_pixels);  // released only on success
         dsocr::PagePixels& px = p->px;
+        px.variant = variant;
         px.base = (int)vs->base_size;
         px.tile = (int)vs->image_size;
         px.crop = vs->crop_mode != 0;
         const int gsize = px.crop ? px.base : px.tile;  // model/mod.rs:1714
+        if (variant == 1) dsocr::check_ocr2_view_size(gsize, "global view");
         std::vector<uint8_t> gview = dsocr::build_global_view(rgb, (int)w, (int)h, gsize);
         px.gsize = gsize;
         px.global_chw.resize((size_t)3 * gsize * gsize);
         dsocr::image_to_chw(gview.data(), gsize, gsize, px.global_chw.data());
         if (px.crop) {
             int gw = 1, gh = 1;
-            auto tiles = dsocr::dynamic_preprocess(rgb, (int)w, (int)h, px.tile, 2, 9, &gw, &gh);
+            auto tiles = dsocr::dynamic_preprocess(rgb, (int)w, (int)h, px.tile, 2, dsocr::tile_max_num(variant), &gw, &gh);
+            if (variant == 1 && !tiles.empty()) dsocr::check_ocr2_view_size(px.tile, "tile");
             px.crop_w = gw;
             px.crop_h = gh;
             px.n_tiles = (int)tiles.size();
@@ -215,16 +253,27 @@ dsocr_status dsocr_prepare_page(const uint8_t* rgb, uint32_t w, uint32_t h, cons
             for (int i = 0; i < px.n_tiles; ++i)
                 dsocr::image_to_chw(tiles[i].data(), px.tile, px.tile, px.tiles_chw.data() + (size_t)i * 3 * px.tile * px.tile);
         }
-        px.n_image_tokens = dsocr::image_placeholder_count(px.base, px.tile, px.crop, px.crop_w, px.crop_h);
+        px.n_image_tokens = dsocr::image_placeholder_count(px.base, px.tile, px.crop, px.crop_w, px.crop_h, variant);
         *out = p.release();
     });
 }
 
 dsocr_status dsocr_prepare_page_device(dsocr_engine* e, const uint8_t* rgb, uint32_t w, uint32_t h,
                                        const dsocr_vision_settings* vs, dsocr_page_pixels** out) {
+    return prepare_page_device_as(e, rgb, w, h, vs, 0, out);
+}
+
+dsocr_status dsocr_prepare_page_device_variant(dsocr_engine* e, const uint8_t* rgb, uint32_t w, uint32_t h,
+                                               const dsocr_vision_settings* vs, dsocr_page_pixels** out) {
+    return prepare_page_device_as(e, rgb, w, h, vs, e ? e->impl->variant() : 0, out);
+}
+
+static dsocr_status prepare_page_device_as(dsocr_engine* e, const uint8_t* rgb, uint32_t w, uint32_t h,
+                                           const dsocr_vision_settings* vs, int variant, dsocr_page_pixels** out) {
     return guarded([&] {
         if (!e || !rgb || !vs || !out) throw std::runtime_error("EINVAL: NULL argument");
         auto* p = new dsocr_page_pixels;
+        p->px.variant = variant;
         p->px.base = (int)vs->base_size;
         p->px.tile = (int)vs->image_size;
         p->px.crop = vs->crop_mode != 0;
@@ -633,6 +682,22 @@ dsocr_status dsocr_k_attention(int n_seq, int L, int heads, int hd, float scale,
         if (rb) (void)hipFree(rb);
         if (part) (void)hipFree(part);
         check_hip(e, "attention");
+    });
+}
+dsocr_status dsocr_k_attention_prefix(int n_seq, int L, int prefix, int heads, int kv_heads, int hd, float scale,
+                                      const float* q, const float* k, const float* v, float* o) {
+    return guarded([&] {
+        dsocr::AttnPrefixArgs a;
+        a.q = q; a.k = k; a.v = v; a.o = o;
+        a.ldq = a.ldo = (long)heads * hd;
+        a.ldk = a.ldv = (long)kv_heads * hd;
+        a.n_seq = n_seq; a.L = L; a.prefix = prefix; a.heads = heads; a.kv_heads = kv_heads; a.hd = hd; a.scale = scale;
+        if (!dsocr::attention_prefix_ok(a))
+            throw std::runtime_error("EINVAL: attention_prefix needs hd 32 or 64, heads % kv_heads == 0, 0 <= prefix <= L "
+                                     "and 16-byte aligned device pointers");
+        dsocr::launch_attention_prefix(a, nullptr);
+        check_hip(hipGetLastError(), "attention_prefix launch");
+        check_hip(hipDeviceSynchronize(), "attention_prefix");
     });
 }
 dsocr_status dsocr_k_attention_bf16(int n_seq, int L, int heads, int hd, float scale, const void* qkv, long ld,

@@ -3,7 +3,13 @@
 //   SamBackboneParams::from_backbone_cfg (vision/sam.rs:40-112)
 //   ClipVisionParams::from_backbone (vision/clip.rs:35-52)
 //   should_use_moe (transformer/weights.rs:609-619)
+//   detect_ocr_variant (model/mod.rs:2691-2710), Qwen2DecoderParams::ocr2_default (vision/qwen2.rs:12-51)
+// DeepSeek-OCR-2 (variant 1): the `qwen2-0-5b` vision entry may also carry `layers`, `heads`, `kv_heads`,
+// `intermediate_size` and `width` / `dim`, which override the reference's fixed encoder constants.  The reference
+// reads only `width` / `dim` (for SAM's last channel count); the other overrides are a testing extension of this
+// engine (small encoders for the suite) and default to the reference's values.
 #pragma once
+#include <cctype>
 #include <cmath>
 #include <string>
 #include <vector>
@@ -43,10 +49,22 @@ struct ClipConfig {
     int hidden = 1024, layers = 24, heads = 16, ffn = 4096, image_size = 224, patch = 14, seq = 256;
 };
 
+// OCR2's Qwen2 decoder used as the vision encoder (vision/qwen2.rs:12-22, 53-103): q/k/v bias, no o_proj bias,
+// SiLU, rotate-half RoPE over the whole head
+struct Qwen2EncConfig {
+    int dim = 896, layers = 24, heads = 14, kv_heads = 2, inter = 4864, head_dim = 64;
+    float rms_eps = 1e-6f, rope_theta = 1000000.f;
+    int query_768 = 144, query_1024 = 256;  // query-table rows for the two supported view sizes
+};
+
+enum OcrVariant : int { VARIANT_OCR1 = 0, VARIANT_OCR2 = 1 };
+
 struct ModelConfig {
     LangConfig lang;
     SamConfig sam;
     ClipConfig clip;
+    int variant = VARIANT_OCR1;
+    Qwen2EncConfig enc;  // variant == VARIANT_OCR2
     int proj_in = 2048, proj_out = 1280;
     std::string proj_type = "linear";
 };
@@ -65,6 +83,18 @@ inline void merge_missing(Json& target, const Json& fallback) {
     } else if (target.is_null()) {
         target = fallback;
     }
+}
+
+// detect_ocr_variant (model/mod.rs:2691-2710)
+inline int detect_variant(const Json& cfg) {
+    const Json& vis = cfg["vision_config"];
+    if (vis.has("model_name") && vis["model_name"].kind == Json::String) {
+        std::string n = vis["model_name"].as_string();
+        for (auto& ch : n) ch = (char)std::tolower((unsigned char)ch);
+        if (n == "deepencoderv2") return VARIANT_OCR2;
+    }
+    if (!vis["width"]["qwen2-0-5b"].is_null()) return VARIANT_OCR2;
+    return VARIANT_OCR1;
 }
 
 inline ModelConfig resolve_config(const Json& cfg) {
@@ -138,6 +168,37 @@ inline ModelConfig resolve_config(const Json& cfg) {
     if (sb.has("global_attn_indexes")) {
         s.global_idx.clear();
         for (auto& v : sb["global_attn_indexes"].arr) s.global_idx.push_back((int)v.as_int());
+    }
+    m.variant = detect_variant(cfg);
+    if (m.variant == VARIANT_OCR2) {
+        // sam.rs:64-90: the last downsample stage feeds the encoder, so its channel count is the encoder width
+        // (the qwen2-0-5b entry's width / dim; 896 for a config detected by model_name alone); no CLIP entry
+        Qwen2EncConfig& q = m.enc;
+        const Json& qb = vis["width"]["qwen2-0-5b"];
+        if (!qb.is_null()) {
+            if (qb.has("width")) q.dim = (int)qb["width"].as_int();
+            else if (qb.has("dim")) q.dim = (int)qb["dim"].as_int();
+            if (qb.has("layers")) q.layers = (int)qb["layers"].as_int();
+            if (qb.has("heads")) q.heads = (int)qb["heads"].as_int();
+            if (qb.has("kv_heads")) q.kv_heads = (int)qb["kv_heads"].as_int();
+            if (qb.has("intermediate_size")) q.inter = (int)qb["intermediate_size"].as_int();
+        }
+        if (q.dim <= 0 || q.layers <= 0 || q.heads <= 0 || q.kv_heads <= 0 || q.inter <= 0 || q.dim % q.heads ||
+            q.heads % q.kv_heads)
+            throw std::runtime_error("EINVAL: bad qwen2-0-5b encoder dimensions");
+        q.head_dim = q.dim / q.heads;
+        if (q.head_dim != 32 && q.head_dim != 64)
+            throw std::runtime_error("EINVAL: qwen2-0-5b encoder head dim must be 32 or 64");
+        const int first = s.out_ch.empty() ? 512 : s.out_ch.front();
+        if (s.out_ch.empty() || s.out_ch.back() != q.dim) s.out_ch = {first, q.dim};
+        const Json& pc2 = cfg["projector_config"];
+        m.proj_in = q.dim;
+        m.proj_out = pc2.has("n_embed") ? (int)pc2["n_embed"].as_int() : l.hidden;
+        if (pc2.has("input_dim") && (int)pc2["input_dim"].as_int() != q.dim)
+            throw std::runtime_error("EINVAL: projector input_dim mismatches the qwen2-0-5b encoder width");
+        if (m.proj_out != l.hidden) throw std::runtime_error("EINVAL: projector n_embed mismatches language hidden size");
+        if (s.out_ch.size() != 2) throw std::runtime_error("EINVAL: expected exactly two downsample stages");
+        return m;
     }
     const Json& cb = vis["width"]["clip-l-14-224"];
     if (cb.is_null()) throw std::runtime_error("EINVAL: clip-l-14-224 vision backbone missing from config");

@@ -214,6 +214,8 @@ Engine::Engine(const std::string& config_path, const std::string& weights_path, 
     if (L.topk > 8) throw std::runtime_error("EINVAL: at most 8 experts per token supported");
     if (!snapshot_path.empty() && dtype != 1)
         throw std::runtime_error("EINVAL: .dsq snapshots load as fp16 (dequant-on-load): use dtype f16");
+    if (!snapshot_path.empty() && cfg_.variant == VARIANT_OCR2)
+        throw std::runtime_error("EINVAL: .dsq snapshots are not supported for DeepSeek-OCR-2 configs (load the checkpoint without snapshot_path)");
     load_weights(weights_path, seed, snapshot_path, (load_flags & 1u) != 0);
     ensure_rope(4096);
     ensure_small(64);
@@ -261,6 +263,7 @@ void Engine::upload_page(PagePixels& pg) {
 void Engine::prepare_page_device(const uint8_t* rgb, int w, int h, PagePixels& px) {
     hipStream_t st = stream_;
     const int G = px.crop ? px.base : px.tile;  // model/mod.rs:1714
+    if (px.variant == VARIANT_OCR2) check_ocr2_view_size(G, "global view");
     px.gsize = G;
     if (px.global_dev) { (void)hipFree(px.global_dev); px.global_dev = nullptr; }
     if (px.tiles_dev) { (void)hipFree(px.tiles_dev); px.tiles_dev = nullptr; }
@@ -297,7 +300,8 @@ void Engine::prepare_page_device(const uint8_t* rgb, int w, int h, PagePixels& p
     px.n_tiles = 0;
     px.crop_w = px.crop_h = 1;
     int gw = 1, gh = 1;
-    if (px.crop && w > 0 && h > 0 && choose_tile_grid(w, h, px.tile, 2, 9, &gw, &gh)) {
+    if (px.crop && w > 0 && h > 0 && choose_tile_grid(w, h, px.tile, 2, tile_max_num(px.variant), &gw, &gh)) {
+        if (px.variant == VARIANT_OCR2) check_ocr2_view_size(px.tile, "tile");
         const int T = px.tile, tw = T * gw, th = T * gh;
         px.crop_w = gw;
         px.crop_h = gh;
@@ -318,7 +322,7 @@ void Engine::prepare_page_device(const uint8_t* rgb, int w, int h, PagePixels& p
     px.global_chw.clear();
     px.tiles_chw.clear();
     px.dev_ordinal = device_;
-    px.n_image_tokens = image_placeholder_count(px.base, px.tile, px.crop, px.crop_w, px.crop_h);
+    px.n_image_tokens = image_placeholder_count(px.base, px.tile, px.crop, px.crop_w, px.crop_h, px.variant);
 }
 
 Engine::~Engine() {
@@ -551,6 +555,51 @@ void Engine::load_weights(const std::string& path, uint64_t seed, const std::str
     sam_.net2 = conv(sp + "net_2.weight", S.out_ch[0], S.neck, 3, 3);
     sam_.net3 = conv(sp + "net_3.weight", S.out_ch[1], S.out_ch[0], 3, 3);
 
+    if (cfg_.variant == VARIANT_OCR2) {
+        // ---------------- Qwen2 encoder (vision/qwen2.rs:116-144, transformer/weights.rs:180-262): names under
+        // model.qwen2_model. contain "model.layers." but are vision tensors (Source::is_language tests the prefix),
+        // so they keep the checkpoint's values in every dtype mode (model/mod.rs:1039-1071)
+        const Qwen2EncConfig& Q = cfg_.enc;
+        const std::string qp = "model.qwen2_model.";
+        const int D = Q.dim, hd = Q.head_dim, KV = Q.kv_heads * hd;
+        // biases: q/k/v only (attention_bias), none on o_proj or the MLP
+        auto lin_nobias = [&](const std::string& pre, int N, int K) { return lin(pre, N, K, false); };
+        for (int l = 0; l < Q.layers; ++l) {
+            EncLayer e;
+            const std::string lp = qp + "model.model.layers." + std::to_string(l) + ".";
+            e.in_norm = {vecf(lp + "input_layernorm.weight", D), nullptr};
+            e.post_norm = {vecf(lp + "post_attention_layernorm.weight", D), nullptr};
+            e.qkv = lin_cat({lp + "self_attn.q_proj", lp + "self_attn.k_proj", lp + "self_attn.v_proj"}, {Q.heads * hd, KV, KV}, D);
+            e.o = lin_nobias(lp + "self_attn.o_proj", D, Q.heads * hd);
+            HostMat g = src.h16(lp + "mlp.gate_proj.weight", (size_t)Q.inter * D, Q.inter, D);
+            HostMat u = src.h16(lp + "mlp.up_proj.weight", (size_t)Q.inter * D, Q.inter, D);
+            if (g.dt != u.dt) throw std::runtime_error("EINVAL: mixed dtypes in fused linear " + lp + "mlp");
+            g.data.insert(g.data.end(), u.data.begin(), u.data.end());
+            e.gu.W = up16(g);
+            e.gu.wdt = g.dt;
+            e.gu.N = 2 * Q.inter;
+            e.gu.K = D;
+            e.down = lin_nobias(lp + "mlp.down_proj", D, Q.inter);
+            enc_.layers.push_back(e);
+        }
+        enc_.norm = vecf(qp + "model.model.norm.weight", D);
+        enc_.query_768 = vecf(qp + "query_768.weight", (size_t)Q.query_768 * D);
+        enc_.query_1024 = vecf(qp + "query_1024.weight", (size_t)Q.query_1024 * D);
+        {   // build_rope_tables (qwen2.rs:573-604): inv_freq = 1 / theta^(i / half) (f32 powf), f32 angles, [half | half]
+            const int Lmax = 2 * Q.query_1024, half = hd / 2;
+            std::vector<float> inv(half), c((size_t)Lmax * hd), s((size_t)Lmax * hd);
+            for (int i = 0; i < half; ++i) inv[i] = 1.0f / powf(Q.rope_theta, (float)i / (float)half);
+            for (int p = 0; p < Lmax; ++p)
+                for (int i = 0; i < half; ++i) {
+                    const float a = (float)p * inv[i];
+                    c[(size_t)p * hd + i] = c[(size_t)p * hd + half + i] = cosf(a);
+                    s[(size_t)p * hd + i] = s[(size_t)p * hd + half + i] = sinf(a);
+                }
+            enc_.cos = upf(c);
+            enc_.sin = upf(s);
+        }
+        if (S.out_ch[1] != D) throw std::runtime_error("EINVAL: SAM output channels must equal the qwen2-0-5b encoder width");
+    } else {
     // ---------------- CLIP (vision/clip.rs:73-88)
     const ClipConfig& C = cfg_.clip;
     const std::string cp = "model.vision_model.";
@@ -570,11 +619,13 @@ void Engine::load_weights(const std::string& path, uint64_t seed, const std::str
     }
     if (C.hidden != S.out_ch[1]) throw std::runtime_error("EINVAL: CLIP width must equal SAM output channels");
     if (C.hidden + S.out_ch[1] != cfg_.proj_in) throw std::runtime_error("EINVAL: combined hidden dims do not match projector input");
+    }
 
-    // ---------------- projector (model/mod.rs:258-390)
+    // ---------------- projector (model/mod.rs:258-390; Ocr2: one biased linear, qwen2.rs:407-444)
     proj_ = lin("model.projector.layers", cfg_.proj_out, cfg_.proj_in, true);
-    newline_ = src.has("model.image_newline") ? vecf("model.image_newline", cfg_.proj_out)
-                                               : upf(std::vector<float>(cfg_.proj_out, 0.f));
+    newline_ = cfg_.variant != VARIANT_OCR2 && src.has("model.image_newline")
+                   ? vecf("model.image_newline", cfg_.proj_out)
+                   : upf(std::vector<float>(cfg_.proj_out, 0.f));  // (Ocr2 has no newline rows)
     separator_ = vecf("model.view_seperator", cfg_.proj_out);
 
     // ---------------- language model (transformer/weights.rs:444-606)
@@ -884,6 +935,8 @@ float* Engine::vision_pass(const float* imgs, int n, int Spx, const std::string&
     const int Sq = g4 * g4;
     float* sam_out = wsf("v_samout", (size_t)n * Sq * c1);
     linear(ncols2, n * Sq, 9 * c0, sam_.net3, sam_out, c1);
+    // Ocr2: the NHWC rows are already the reference's flatten(2,3).transpose(1,2) token rows (qwen2.rs:157-161)
+    if (cfg_.variant == VARIANT_OCR2) return encoder_pass(sam_out, n, Sq, out);
 
     // CLIP (clip.rs:165-309) on SAM features
     const int T = Sq + 1, CH = CC.hidden, chd = CH / CC.heads;
@@ -927,6 +980,60 @@ float* Engine::vision_pass(const float* imgs, int n, int Spx, const std::string&
     return post;
 }
 
+// Qwen2DecoderAsEncoder::forward_tokens (qwen2.rs:166-220) + Qwen2Projector (407-444) on n views of P SAM tokens:
+// [image tokens | queries] at positions 0 .. 2P-1, the decoder blocks (block.rs) under the hybrid mask, the final
+// RMSNorm, and the projector on the query half only (RMSNorm and the linear are row-wise, so taking the query rows
+// first gives the same values as the reference's narrow() after the norm)
+float* Engine::encoder_pass(const float* sam_out, int n, int P, const std::string& out) {
+    const Qwen2EncConfig& Q = cfg_.enc;
+    const float* query = P == Q.query_768 ? enc_.query_768 : P == Q.query_1024 ? enc_.query_1024 : nullptr;
+    if (!query)
+        throw std::runtime_error("EINVAL: unsupported Qwen2 query length " + std::to_string(P) + " (expected " +
+                                 std::to_string(Q.query_768) + " or " + std::to_string(Q.query_1024) + ")");
+    hipStream_t st = stream_;
+    const int D = Q.dim, hd = Q.head_dim, L = 2 * P, QW = Q.heads * hd, KW = Q.kv_heads * hd, W3 = QW + 2 * KW;
+    const long rows = (long)n * L;
+    float* x = wsf("q2_x", (size_t)rows * D);
+    float* xn = wsf("q2_xn", (size_t)rows * D);
+    float* qkv = wsf("q2_qkv", (size_t)rows * W3);
+    float* ctx = wsf("q2_ctx", (size_t)rows * QW);
+    float* gu = wsf("q2_gu", (size_t)rows * 2 * Q.inter);
+    float* hbuf = wsf("q2_h", (size_t)rows * Q.inter);
+    launch_ocr2_build_seq(sam_out, query, n, P, D, x, st);
+    for (const EncLayer& e : enc_.layers) {
+        launch_rmsnorm(x, D, xn, D, (int)rows, D, e.in_norm.w, Q.rms_eps, st);
+        linear(xn, (int)rows, D, e.qkv, qkv, W3);
+        launch_ocr2_rope(qkv, W3, rows, L, Q.heads + Q.kv_heads, hd, enc_.cos, enc_.sin, st);
+        AttnPrefixArgs a;
+        a.q = qkv; a.k = qkv + QW; a.v = qkv + QW + KW; a.o = ctx;
+        a.ldq = a.ldk = a.ldv = W3; a.ldo = QW;
+        a.n_seq = n; a.L = L; a.prefix = P; a.heads = Q.heads; a.kv_heads = Q.kv_heads; a.hd = hd;
+        a.scale = (float)(1.0 / std::sqrt((double)hd));
+        // visible (row, key) pairs per head and sequence: P^2 among the image rows, P^2 + P (P + 1) / 2 for the queries
+        flops_acc_ += 4.0 * n * Q.heads * hd * (2.0 * P * P + 0.5 * P * (P + 1.0));
+        launch_attention_prefix(a, st);
+        linear(ctx, (int)rows, QW, e.o, x, D, 0, 1);
+        launch_rmsnorm(x, D, xn, D, (int)rows, D, e.post_norm.w, Q.rms_eps, st);
+        linear(xn, (int)rows, D, e.gu, gu, 2 * Q.inter);
+        launch_silu_mul(gu, 2 * Q.inter, Q.inter, (int)rows, hbuf, Q.inter, st);
+        linear(hbuf, (int)rows, Q.inter, e.down, x, D, 0, 1);
+    }
+    float* qx = wsf("q2_q", (size_t)n * P * D);
+    launch_ocr2_take_queries(x, n, P, D, qx, st);
+    launch_rmsnorm(qx, D, qx, D, n * P, D, enc_.norm, Q.rms_eps, st);
+    float* post = wsf(out, (size_t)n * P * cfg_.proj_out);
+    linear(qx, n * P, D, proj_, post, cfg_.proj_out);
+    return post;
+}
+
+void Engine::check_page_variant(const PagePixels& pg) const {
+    if (pg.variant != cfg_.variant)
+        throw std::runtime_error(std::string("EINVAL: page was prepared for ") +
+                                 (pg.variant == VARIANT_OCR2 ? "DeepSeek-OCR-2" : "DeepSeek-OCR") + " but the engine runs " +
+                                 (cfg_.variant == VARIANT_OCR2 ? "DeepSeek-OCR-2" : "DeepSeek-OCR") +
+                                 " (image slot layout mismatch)");
+}
+
 // row kinds of launch_assemble_rows: token embedding, caller-supplied image row, vision row, the two markers
 enum RowKind : int { ROW_TOKEN = 0, ROW_HOST = 1, ROW_VISION = 2, ROW_NEWLINE = 3, ROW_SEPARATOR = 4 };
 
@@ -937,6 +1044,13 @@ static std::vector<std::pair<int, long>> image_row_order(const PagePixels& pg) {
     std::vector<std::pair<int, long>> seq;
     const int ls = pg.tile / 64, gs = pg.gsize / 64;
     const long n_local = pg.n_tiles > 0 ? (long)pg.n_tiles * ls * ls : 0;
+    if (pg.variant == VARIANT_OCR2) {
+        // Qwen2VisionEncoder::encode (qwen2.rs:337-372): the tiles' tokens tile-major, the global view's, the
+        // separator; no newline rows and no 2-D re-tiling, so the order is the vision rows' own
+        for (long i = 0; i < n_local + (long)gs * gs; ++i) seq.push_back({ROW_VISION, i});
+        seq.push_back({ROW_SEPARATOR, 0});
+        return seq;
+    }
     for (int R = 0; n_local && R < pg.crop_h * ls; ++R) {
         for (int Cc = 0; Cc < pg.crop_w * ls; ++Cc) {
             const int crop = (R / ls) * pg.crop_w + (Cc / ls);
@@ -956,6 +1070,7 @@ std::vector<std::vector<float>> Engine::image_embeddings(const std::vector<const
     std::vector<std::vector<float>> result;
     const int H = cfg_.proj_out;
     for (const PagePixels* p : pages) {
+        check_page_variant(*p);
         // one page at a time keeps this helper simple; generate() batches pages.
         float* gimg = p->global_dev && p->dev_ordinal == device_ ? p->global_dev : upload("e_gimg", p->global_chw);
         float* gpost = vision_pass(gimg, 1, p->gsize, "e_gpost");
@@ -1635,6 +1750,7 @@ void Engine::embed_pages(GenState& g) {
     std::map<int, std::vector<int>> gsz, tsz;
     for (int b = 0; b < B; ++b)
         if (reqs[b].page) {
+            check_page_variant(*reqs[b].page);
             gsz[reqs[b].page->gsize].push_back(b);
             if (reqs[b].page->n_tiles > 0) tsz[reqs[b].page->tile].push_back(b);
         }

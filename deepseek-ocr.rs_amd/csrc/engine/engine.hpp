@@ -86,7 +86,23 @@ struct DecLayer {
     size_t packed_bytes = 0;
 };
 
+// DeepSeek-OCR-2: the Qwen2 decoder used as the vision encoder (vision/qwen2.rs)
+struct EncLayer {
+    Ln in_norm, post_norm;
+    Lin qkv, o;    // q|k|v fused [(heads + 2 kv) hd][D] with biases; o_proj without
+    Lin gu, down;  // gate|up fused [2I][D], [D][I]
+};
+struct Qwen2EncW {
+    std::vector<EncLayer> layers;
+    float* norm = nullptr;
+    float* query_768 = nullptr;   // [144][D]
+    float* query_1024 = nullptr;  // [256][D]
+    float* cos = nullptr;         // [512][hd] (qwen2.rs:573-604)
+    float* sin = nullptr;
+};
+
 struct PagePixels {
+    int variant = 0;  // 0 = DeepSeek-OCR, 1 = DeepSeek-OCR-2: the tile budget and the <image> slot layout
     int base = 1024, tile = 640;
     bool crop = true;
     int crop_w = 1, crop_h = 1;
@@ -146,6 +162,7 @@ class Engine {
     void packed_info(size_t* packed_layers, size_t* moe_layers, size_t* packed_bytes) const;
 
     const ModelConfig& cfg() const { return cfg_; }
+    int variant() const { return cfg_.variant; }
     // vision embeddings of pages (host output rows per page concatenated)
     std::vector<std::vector<float>> image_embeddings(const std::vector<const PagePixels*>& pages);
     // batched generate; returns generated ids per page
@@ -227,6 +244,9 @@ class Engine {
     float* clip_pos(int tokens);
     // runs SAM+CLIP+projector on n images of size S; returns device rows [n*(S/64)^2][H] in buffer `out`
     float* vision_pass(const float* imgs, int n, int S, const std::string& out);
+    // OCR2: Qwen2 encoder + projector on n views' SAM token rows [n][P][D]; device rows [n*P][H] in buffer `out`
+    float* encoder_pass(const float* sam_out, int n, int P, const std::string& out);
+    void check_page_variant(const PagePixels& pg) const;
     void decode_step(int B, int Lmax);
     // one page: every decoder layer of a step as one persistent launch (decode_persist.hip) when the model's
     // shape and dtypes fit it, all 256 workgroups are resident and DSOCR_PERSIST=1 (opt-in)
@@ -277,6 +297,7 @@ class Engine {
 
     SamW sam_;
     ClipW clip_;
+    Qwen2EncW enc_;
     Lin proj_;
     float* newline_ = nullptr;
     float* separator_ = nullptr;

@@ -10,6 +10,8 @@
 #include <cmath>
 #include <cstdint>
 #include <set>
+#include <stdexcept>
+#include <string>
 #include <utility>
 #include <vector>
 
@@ -255,7 +257,15 @@ inline std::vector<uint8_t> build_global_view(const uint8_t* rgb, int w, int h, 
 }
 
 // vision/preprocess.rs:67-138: the tile grid (closest aspect ratio, larger grid on ties when the
-// page area exceeds half of it); false when the page needs no tiles
+// page area exceeds half of it); false when the page needs no tiles.  max_num: 9 for Ocr1, 6 for Ocr2
+// (preprocess.rs:27-35)
+inline int tile_max_num(int variant) { return variant == 1 ? 6 : 9; }
+// Ocr2's encoder has a query table for 768 px (144 tokens) and 1024 px (256 tokens) views only (qwen2.rs:222-234)
+inline void check_ocr2_view_size(int size, const char* what) {
+    if (size != 768 && size != 1024)
+        throw std::runtime_error(std::string("EINVAL: DeepSeek-OCR-2 ") + what + " must be 768 or 1024 px, got " +
+                                 std::to_string(size));
+}
 inline bool choose_tile_grid(int w, int h, int tile, int min_num, int max_num, int* grid_w, int* grid_h) {
     if (w <= tile && h <= tile) { *grid_w = 1; *grid_h = 1; return false; }
     const double aspect = (double)w / (double)h;
@@ -310,10 +320,23 @@ inline void image_to_chw(const uint8_t* rgb, int w, int h, float* out) {
             }
 }
 
-// build_image_placeholders (model/mod.rs:2605-2689, Ocr1): number of <image> slots.
-inline size_t image_placeholder_count(int base, int image_size, bool crop_mode, int cw, int ch) {
+// build_image_placeholders (model/mod.rs:2605-2689): number of <image> slots.  variant 0 (Ocr1): grids with a
+// newline slot per row; variant 1 (Ocr2, model/mod.rs:2630-2680): flat grids, no newlines; both end with the separator
+inline size_t image_placeholder_count(int base, int image_size, bool crop_mode, int cw, int ch, int variant = 0) {
     const int P = 16, D = 4;
     size_t n = 0;
+    if (variant == 1) {
+        if (crop_mode) {
+            const int ng = (int)std::ceil((float)(base / P) / (float)D);
+            const int nl = (int)std::ceil((float)(image_size / P) / (float)D);
+            if (cw > 1 || ch > 1) n += (size_t)(nl * ch) * (nl * cw);
+            n += (size_t)ng * ng + 1;
+        } else {
+            const int nq = (int)std::ceil((float)(image_size / P) / (float)D);
+            n += (size_t)nq * nq + 1;
+        }
+        return n;
+    }
     if (crop_mode) {
         int ng = (int)std::ceil((float)(base / P) / (float)D);
         int nl = (int)std::ceil((float)(image_size / P) / (float)D);

@@ -175,6 +175,31 @@ struct RopeKvArgs {
 };
 void launch_rope_kv(const RopeKvArgs& a, hipStream_t s);
 
+// ------------------------------------------------------------------ OCR2 encoder attention (attention_prefix.hip)
+// Grouped-query attention under the DeepSeek-OCR-2 encoder's hybrid mask (vision/qwen2.rs:519-571): n_seq
+// sequences of L rows, the first `prefix` rows image tokens, the rest queries; row i sees key j iff j < prefix or
+// (i >= prefix and j <= i).  q / o rows hold heads * hd floats, k / v rows kv_heads * hd, at row strides ld*
+// (floats, multiples of 4; 16-byte aligned bases).  hd 32 or 64, heads % kv_heads == 0, 0 <= prefix <= L.
+struct AttnPrefixArgs {
+    const float* q = nullptr; const float* k = nullptr; const float* v = nullptr;
+    float* o = nullptr;
+    long ldq = 0, ldk = 0, ldv = 0, ldo = 0;
+    int n_seq = 0, L = 0, prefix = 0, heads = 0, kv_heads = 0, hd = 0;
+    float scale = 1.f;
+};
+bool attention_prefix_ok(const AttnPrefixArgs& a);
+void launch_attention_prefix(const AttnPrefixArgs& a, hipStream_t s);  // throws EINVAL outside the contract
+
+// ------------------------------------------------------------------ OCR2 encoder row ops (ocr2_ops.hip)
+// out [n][2 P][D] = [feat rows of image i | query table] (qwen2.rs:157-177): feat [n][P][D] token rows, query [P][D]
+void launch_ocr2_build_seq(const float* feat, const float* query, int n, int P, int D, float* out, hipStream_t s);
+// rotate-half RoPE over the whole head (block.rs:1403-1471 without the MLA regroup) on the first n_heads heads of
+// every row of x [rows][ld] (the q | k columns of a fused q|k|v buffer), position = row % L; cos / sin [>= L][hd]
+void launch_ocr2_rope(float* x, long ld, long rows, int L, int n_heads, int hd, const float* cos_t, const float* sin_t,
+                      hipStream_t s);
+// dst [n][P][D] = the query half (rows P .. 2P-1) of src [n][2 P][D]
+void launch_ocr2_take_queries(const float* src, int n, int P, int D, float* dst, hipStream_t s);
+
 // ------------------------------------------------------------------ dots.ocr tower row ops (dots_ops.hip)
 // bf16 tensors as uint16_t bits; every op computes in f32 and rounds its output to bf16 (RNE)
 // y = rnd(x / sqrt(mean(x^2) + eps) * w); x bf16 or (in_f32) f32 rows [rows][D]; y may alias a bf16 x

@@ -9,3 +9,6 @@ from .engine import (DecodeOutcome, DecodeParameters, DeepseekOcrEngine, ModelLo
 CONFIG_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "configs")
 FULL_CONFIG = os.path.join(CONFIG_DIR, "deepseek-ocr.json")
 TINY_CONFIG = os.path.join(CONFIG_DIR, "tiny.json")
+OCR2_CONFIG = os.path.join(CONFIG_DIR, "deepseek-ocr-2.json")
+OCR2_TINY_CONFIG = os.path.join(CONFIG_DIR, "ocr2-tiny.json")
+OCR2_ENC_CONFIG = os.path.join(CONFIG_DIR, "ocr2-enc.json")

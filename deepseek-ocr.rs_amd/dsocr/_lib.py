@@ -93,7 +93,11 @@ EXPORTS = [
     "dsocr_engine_load_flags", "dsocr_engine_packed_info", "dsocr_k_moe_packed", "dsocr_k_dsq_rows_dot",
     "dsocr_k_moe_ex", "dsocr_k_moe_route_kind", "dsocr_k_moe_prefill_route", "dsocr_k_moe_combine",
     "dsocr_k_gemm_bf16", "dsocr_k_dots_op",
+    "dsocr_config_variant", "dsocr_engine_variant", "dsocr_prepare_page_variant", "dsocr_prepare_page_device_variant", "dsocr_k_attention_prefix",
 ]
+
+# model variants behind the deepseek engine (dsocr_engine_variant)
+VARIANT_OCR1, VARIANT_OCR2 = 0, 1
 
 # dsocr_k_dots_op op codes (DSOCR_DOTS_*)
 DOTS_RMSNORM, DOTS_LAYERNORM, DOTS_SWIGLU, DOTS_GELU, DOTS_ROPE_QK, DOTS_TO_BF16, DOTS_BF16_TO_F32 = range(7)
@@ -118,6 +122,11 @@ def lib():
     L.dsocr_engine_info.argtypes = [vp, C.POINTER(sz), C.POINTER(sz), C.POINTER(i64), C.POINTER(sz)]
     L.dsocr_prepare_page.argtypes = [vp, u32, u32, C.POINTER(VisionSettingsC), C.POINTER(vp)]
     L.dsocr_page_free.argtypes = [vp]
+    L.dsocr_engine_variant.argtypes = [vp, C.POINTER(i32)]
+    L.dsocr_config_variant.argtypes = [C.c_char_p, C.POINTER(i32), C.POINTER(u32), C.POINTER(u32)]
+    L.dsocr_prepare_page_variant.argtypes = [vp, u32, u32, C.POINTER(VisionSettingsC), i32, C.POINTER(vp)]
+    L.dsocr_prepare_page_device_variant.argtypes = [vp, vp, u32, u32, C.POINTER(VisionSettingsC), C.POINTER(vp)]
+    L.dsocr_k_attention_prefix.argtypes = [i32, i32, i32, i32, i32, i32, f32, vp, vp, vp, vp]
     L.dsocr_prepare_page_device.argtypes = [vp, vp, u32, u32, C.POINTER(VisionSettingsC), C.POINTER(vp)]
     L.dsocr_page_read_device.argtypes = [vp, vp, vp]
     L.dsocr_page_free.restype = None

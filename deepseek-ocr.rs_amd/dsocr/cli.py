@@ -25,7 +25,7 @@ import sys
 import time
 from typing import List, Optional
 
-from . import FULL_CONFIG
+from . import FULL_CONFIG, OCR2_CONFIG
 from ._lib import DsocrError
 from .engine import DecodeParameters, ModelLoadArgs, VisionSettings, load_model, render_prompt
 from .streaming import DeltaTracker, decode_ids
@@ -45,8 +45,9 @@ def add_model_args(p: argparse.ArgumentParser) -> None:
     g = p.add_argument_group("Application")
     g.add_argument("--config", metavar="PATH", help="application config (accepted for compatibility; unused)")
     g.add_argument("--model", metavar="ID", default="deepseek-ocr",
-                   help="model id: deepseek-ocr (MI355X engine) or paddleocr-vl (host CPU plumbing path, configs[0])")
-    g.add_argument("--model-config", metavar="PATH", help="model config.json (default: bundled DeepSeek-OCR)")
+                   help="model id: deepseek-ocr or deepseek-ocr-2 (MI355X engine), or paddleocr-vl (host CPU plumbing "
+                        "path, configs[0])")
+    g.add_argument("--model-config", metavar="PATH", help="model config.json (default: the bundled config of --model)")
     g.add_argument("--tokenizer", metavar="PATH", help="tokenizer.json (default: synthetic tokenizer)")
     g.add_argument("--weights", metavar="PATH", help="model .safetensors (default: synthetic weights)")
     g.add_argument("--snapshot", metavar="PATH", help="DSQ snapshot (.dsq) to dequantise on load")
@@ -62,8 +63,8 @@ def add_inference_args(p: argparse.ArgumentParser) -> None:
     g.add_argument("--device", default="hip", help="hip | hip:N (cuda[:N] is accepted as an alias)")
     g.add_argument("--dtype", default="f16", choices=["f32", "f16", "bf16"])
     g.add_argument("--template", default="plain")
-    g.add_argument("--base-size", type=int, default=1024)
-    g.add_argument("--image-size", type=int, default=640)
+    g.add_argument("--base-size", type=int, default=None, help="default: the model's (1024)")
+    g.add_argument("--image-size", type=int, default=None, help="default: the model's (640; deepseek-ocr-2: 768)")
     g.add_argument("--crop-mode", type=_bool, default=True, metavar="BOOL")
     g.add_argument("--max-new-tokens", type=int, default=512)
     g.add_argument("--no-cache", action="store_true")
@@ -90,6 +91,24 @@ def build_parser() -> argparse.ArgumentParser:
     b.add_argument("--bench-output", metavar="PATH", help="write benchmark events to a JSON file")
     p.add_argument("-q", "--quiet", action="store_true", help="print only the final result")
     return p
+
+
+# the engine's model ids -> (bundled config, base_size, image_size): the registry defaults of config.rs:96-110
+ENGINE_MODELS = {"deepseek-ocr": (FULL_CONFIG, 1024, 640), "deepseek": (FULL_CONFIG, 1024, 640),
+                 "deepseek-ocr-2": (OCR2_CONFIG, 1024, 768)}
+
+
+def model_config(args) -> str:
+    if args.model not in ENGINE_MODELS:
+        raise DsocrError(1, f"model `{args.model}` is not served by the MI355X engine (deepseek-ocr, deepseek-ocr-2)")
+    return args.model_config or ENGINE_MODELS[args.model][0]
+
+
+def vision_settings(args) -> VisionSettings:
+    """--base-size / --image-size, else the model's registry defaults."""
+    _, base, image = ENGINE_MODELS.get(args.model, (None, 1024, 640))
+    return VisionSettings(base if args.base_size is None else args.base_size,
+                          image if args.image_size is None else args.image_size, args.crop_mode)
 
 
 def parse_device(spec: str) -> int:
@@ -162,9 +181,7 @@ def run_inference(args, out=sys.stdout, err=sys.stderr) -> int:
     if args.model in PADDLE_IDS:
         return run_paddle(args, prompt_raw, out, err)
     device = parse_device(args.device)
-    if args.model not in ("deepseek-ocr", "deepseek"):
-        raise DsocrError(1, f"model `{args.model}` is not served by the MI355X engine (deepseek-ocr only)")
-    config = args.model_config or FULL_CONFIG
+    config = model_config(args)
     vocab = _vocab_of(config)
     events = []
     t0 = time.perf_counter()
@@ -184,7 +201,7 @@ def run_inference(args, out=sys.stdout, err=sys.stderr) -> int:
             raise DsocrError(1, f"prompt includes {slots} <image> tokens but {len(args.images)} image paths "
                                 f"were provided")
         images = [open_image(p) for p in args.images]
-        vision = VisionSettings(args.base_size, args.image_size, args.crop_mode)
+        vision = vision_settings(args)
         params = decode_params(args)
 
         tracker = DeltaTracker()
@@ -276,7 +293,7 @@ def run_paddle(args, prompt_raw: str, out=sys.stdout, err=sys.stderr) -> int:
     if slots != len(args.images):
         raise DsocrError(1, f"prompt includes {slots} <image> tokens but {len(args.images)} image paths were provided")
     images = [open_image(p) for p in args.images]
-    vision = VisionSettings(args.base_size, args.image_size, args.crop_mode)
+    vision = vision_settings(args)
     outcome = engine.decode(tokenizer, prompt, images, vision, decode_params(args))
     out.write(outcome.text + "\n")
     info(f"generated {outcome.response_tokens} tokens: {outcome.generated_tokens}")

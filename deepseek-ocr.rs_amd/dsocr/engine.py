@@ -105,10 +105,12 @@ def build_prompt_tokens(tokenizer, prompt: str, image_token_counts: Sequence[int
 class Page:
     """Preprocessed page pixels (a1-a3): global view + crop tiles.
 
-    ``engine=None``: host C++ (dsocr_prepare_page); with an engine: on that engine's GPU
-    (dsocr_prepare_page_device, bit-identical pixels, device-resident)."""
+    ``engine=None``: host C++ (dsocr_prepare_page_variant); with an engine: on that engine's GPU
+    (dsocr_prepare_page_device_variant, bit-identical pixels, device-resident).  ``variant`` (0 = DeepSeek-OCR,
+    1 = DeepSeek-OCR-2) sets the tile budget and the <image> slot layout; it defaults to the engine's when one is
+    given and to 0 otherwise."""
 
-    def __init__(self, rgb, vision: VisionSettings, engine=None):
+    def __init__(self, rgb, vision: VisionSettings, engine=None, variant=None):
         if hasattr(rgb, "convert"):  # PIL image
             rgb = np.asarray(rgb.convert("RGB"))
         rgb = np.ascontiguousarray(rgb, dtype=np.uint8)
@@ -116,12 +118,20 @@ class Page:
             raise DsocrError(1, "page must be HxWx3 uint8")
         vs = VisionSettingsC(vision.base_size, vision.image_size, 1 if vision.crop_mode else 0)
         h = C.c_void_p()
+        if variant is None:
+            variant = engine.variant if engine is not None else 0
         if engine is None:
-            check(lib().dsocr_prepare_page(rgb.ctypes.data_as(C.c_void_p), rgb.shape[1], rgb.shape[0], C.byref(vs),
-                                           C.byref(h)))
-        else:
+            check(lib().dsocr_prepare_page_variant(rgb.ctypes.data_as(C.c_void_p), rgb.shape[1], rgb.shape[0],
+                                                   C.byref(vs), int(variant), C.byref(h)))
+        elif int(variant) == engine.variant:
+            check(lib().dsocr_prepare_page_device_variant(engine._h, rgb.ctypes.data_as(C.c_void_p), rgb.shape[1],
+                                                          rgb.shape[0], C.byref(vs), C.byref(h)))
+        elif int(variant) == 0:
             check(lib().dsocr_prepare_page_device(engine._h, rgb.ctypes.data_as(C.c_void_p), rgb.shape[1],
                                                   rgb.shape[0], C.byref(vs), C.byref(h)))
+        else:
+            raise DsocrError(1, f"engine of variant {engine.variant} cannot prepare a page of variant {variant}")
+        self.variant = int(variant)
         self.on_device = engine is not None
         self._h = h
         cw, ch, nt, ntok = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_size_t()
@@ -191,6 +201,9 @@ class DeepseekOcrEngine:
         hid, voc, eos, nl = C.c_size_t(), C.c_size_t(), C.c_int64(), C.c_size_t()
         check(lib().dsocr_engine_info(h, C.byref(hid), C.byref(voc), C.byref(eos), C.byref(nl)))
         self.hidden, self.vocab, self.eos_token_id, self.num_layers = hid.value, voc.value, eos.value, nl.value
+        var = C.c_int()
+        check(lib().dsocr_engine_variant(h, C.byref(var)))
+        self.variant = var.value  # 0 = DeepSeek-OCR, 1 = DeepSeek-OCR-2
 
     def packed_info(self) -> dict:
         """MoE layers decoding from packed snapshot blocks: {"packed_layers", "moe_layers", "packed_bytes"}."""

@@ -406,8 +406,8 @@ def main(argv=None) -> int:
     """`deepseek-ocr-server` (server/src/args.rs + config defaults host 0.0.0.0, port 8000)."""
     import argparse
 
-    from .cli import _vocab_of, add_inference_args, add_model_args, decode_params, load_tokenizer, parse_device
-    from . import FULL_CONFIG
+    from .cli import (_vocab_of, add_inference_args, add_model_args, decode_params, load_tokenizer, model_config,
+                      parse_device, vision_settings)
     from .engine import ModelLoadArgs, load_model
 
     p = argparse.ArgumentParser(prog="deepseek-ocr-server", description="DeepSeek-OCR API Server (MI355X engine)")
@@ -416,13 +416,13 @@ def main(argv=None) -> int:
     p.add_argument("--host", default="0.0.0.0")
     p.add_argument("--port", type=int, default=8000)
     args = p.parse_args(argv)
-    config = args.model_config or FULL_CONFIG
+    config = model_config(args)  # --model deepseek-ocr | deepseek-ocr-2: the bundled config and vision defaults
     engine = load_model(ModelLoadArgs(config_path=config, weights_path=args.weights, snapshot_path=args.snapshot,
                                       snapshot_packed=getattr(args, "snapshot_packed", None),
                                       device=parse_device(args.device), dtype=args.dtype,
                                       synthetic_seed=args.synthetic_seed))
     state = ServerState(engine, load_tokenizer(args.tokenizer, _vocab_of(config)), args.model,
-                        VisionSettings(args.base_size, args.image_size, args.crop_mode), decode_params(args))
+                        vision_settings(args), decode_params(args))
     import uvicorn
     uvicorn.run(create_app(state), host=args.host, port=args.port)
     return 0

@@ -144,6 +144,24 @@ dsocr_status dsocr_prepare_page(const uint8_t* rgb, uint32_t width, uint32_t hei
  * NULL arrays; dsocr_page_read_device copies them back). */
 dsocr_status dsocr_prepare_page_device(dsocr_engine* e, const uint8_t* rgb, uint32_t w, uint32_t h,
                                        const dsocr_vision_settings* vs, dsocr_page_pixels** out);
+/* ---- model variants behind one engine type (detect_ocr_variant, model/mod.rs:2691-2710): 0 = DeepSeek-OCR,
+ *      1 = DeepSeek-OCR-2 (SAM -> Qwen2 decoder as encoder -> projector, vision/qwen2.rs).  A page decides its tile
+ *      grid (at most 9 tiles for variant 0, 6 for variant 1, preprocess.rs:27-35) and its <image> slot count (flat
+ *      grids without newline slots for variant 1, model/mod.rs:2630-2680) without an engine, so it carries the
+ *      variant it was prepared for; a page handed to an engine of the other variant is DSOCR_EINVAL.  Variant 1
+ *      views must be 768 or 1024 px (the encoder's two query tables); anything else is DSOCR_EINVAL. */
+dsocr_status dsocr_engine_variant(const dsocr_engine* e, int* variant);
+/* The same config resolution without an engine or a GPU (host only): the variant of a config.json, SAM's two
+ * downsample channel counts after the variant's rule (sam.rs:64-90: the last one is the encoder width for variant 1)
+ * and, for variant 1, the encoder's {width, layers, heads, kv_heads, intermediate_size} (zeros for variant 0).
+ * Any output may be NULL.  A config the engine would refuse is DSOCR_EINVAL here too. */
+dsocr_status dsocr_config_variant(const char* config_path, int* variant, uint32_t* sam_out_channels /* [2] */,
+                                  uint32_t* encoder /* [5] */);
+dsocr_status dsocr_prepare_page_variant(const uint8_t* rgb, uint32_t width, uint32_t height,
+                                        const dsocr_vision_settings* vs, int variant, dsocr_page_pixels** out);
+/* dsocr_prepare_page_device for the variant of `e` (dsocr_prepare_page_device itself always prepares variant 0) */
+dsocr_status dsocr_prepare_page_device_variant(dsocr_engine* e, const uint8_t* rgb, uint32_t w, uint32_t h,
+                                               const dsocr_vision_settings* vs, dsocr_page_pixels** out);
 dsocr_status dsocr_page_read_device(const dsocr_page_pixels* p, float* global_out /* [3][G][G] */,
                                     float* tiles_out /* [n_tiles][3][T][T] or NULL */);
 void dsocr_page_free(dsocr_page_pixels* p);
@@ -309,6 +327,12 @@ dsocr_status dsocr_k_rmsnorm(int rows, int cols, const float* x, const float* w,
 dsocr_status dsocr_k_attention(int n_seq, int L, int heads, int hd, float scale, int causal, const float* q,
                                const float* k, const float* v, float* o, const float* relh, const float* relw, int gh,
                                int gw);
+/* Grouped-query attention under the DeepSeek-OCR-2 encoder's hybrid mask (vision/qwen2.rs:519-571): n_seq
+ * sequences of L rows, the first `prefix` image tokens, the rest queries; row i sees key j iff j < prefix or
+ * (i >= prefix and j <= i).  q, o are [n_seq*L][heads*hd]; k, v are [n_seq*L][kv_heads*hd]; f32 device pointers.
+ * hd 32 or 64, heads % kv_heads == 0, 0 <= prefix <= L; anything else is DSOCR_EINVAL. */
+dsocr_status dsocr_k_attention_prefix(int n_seq, int L, int prefix, int heads, int kv_heads, int hd, float scale,
+                                      const float* q, const float* k, const float* v, float* o);
 /* Bidirectional attention over bf16 values with f32 math on the bf16 matrix cores (the dots.ocr ViT,
  * dots_vit.rs:433-498): qkv bf16 [n_seq*L][ld] holding q | k | v (heads*hd each) per row; o [n_seq*L][o_ld]
  * f32 (o_bf16 = 0) or bf16 (o_bf16 = 1, RNE). */
