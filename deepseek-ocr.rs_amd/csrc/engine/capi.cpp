@@ -597,14 +597,74 @@ dsocr_status dsocr_k_gemm_f32a(int M, int N, int K, const float* A, const void* 
 }
 dsocr_status dsocr_k_gemv(int M, int N, int K, const float* x, const float* norm_w, float eps, const void* W,
                           int wdtype, const float* bias, float* y, int act, int accumulate) {
+    return dsocr_k_gemv_ex(M, N, K, x, K, norm_w, eps, W, K, wdtype, bias, y, N, act, accumulate, 0, nullptr);
+}
+static bool gemv_kind_is_mm(const char* kind) { return std::strncmp(kind, "dec_mm_", 7) == 0; }
+dsocr_status dsocr_k_gemv_ex(int M, int N, int K, const float* x, int ldx, const float* norm_w, float eps,
+                             const void* W, int ldw, int wdtype, const float* bias, float* y, int ldy, int act,
+                             int accumulate, int swizzle, const char** kind) {
     return guarded([&] {
-        if (K % 8) throw std::runtime_error("EINVAL: K must be a multiple of 8");
+        if (K < 8 || K % 8) throw std::runtime_error("EINVAL: K must be a positive multiple of 8");
+        if (M < 0 || N < 0 || ldx < K || ldw < K || ldy < N || ldx % 4 || ldw % 8)
+            throw std::runtime_error("EINVAL: gemv strides (ldx >= K, ldx % 4 == 0, ldw >= K, ldw % 8 == 0, ldy >= N)");
+        if (wdtype != dsocr::WDT_BF16 && wdtype != dsocr::WDT_F16) throw std::runtime_error("EINVAL: weights must be bf16 or f16");
         dsocr::DecGemvArgs a;
-        a.M = M; a.N = N; a.K = K; a.x = x; a.ldx = K; a.W = W; a.ldw = K; a.wdtype = wdtype; a.bias = bias;
-        a.y = y; a.ldy = N; a.act = act; a.accumulate = accumulate; a.norm_w = norm_w; a.eps = eps;
-        dsocr::launch_dec_gemv(a, nullptr);
-        check_hip(hipGetLastError(), "gemv launch");
-        check_hip(hipDeviceSynchronize(), "gemv");
+        a.M = M; a.N = N; a.K = K; a.x = x; a.ldx = ldx; a.W = W; a.ldw = ldw; a.wdtype = wdtype; a.bias = bias;
+        a.y = y; a.ldy = ldy; a.act = act; a.accumulate = accumulate; a.norm_w = norm_w; a.eps = eps;
+        void* swz = nullptr;
+        if (swizzle) {
+            // the fragment-ordered form runs only where the dispatch takes dec_mm: anything else is refused, so
+            // a caller never believes it ran the swizzled kernel when it did not
+            if (ldw != K) throw std::runtime_error("EINVAL: swizzle needs row-major W with ldw == K");
+            if (!dsocr::dec_mm_ok(a) || !gemv_kind_is_mm(dsocr::dec_gemv_kernel_kind(a)))
+                throw std::runtime_error("EINVAL: swizzle outside dec_mm's range (M 3..8, K 1280, N >= 16)");
+            check_hip(hipMalloc(&swz, sizeof(uint16_t) * dsocr::mm_swizzle_elems(N, K)), "hipMalloc");
+            a.w_swz = swz;
+        }
+        if (kind) *kind = dsocr::dec_gemv_kernel_kind(a);
+        hipError_t e = hipSuccess;
+        try {
+            if (swz) dsocr::launch_mm_swizzle(W, N, K, swz, nullptr);
+            dsocr::launch_dec_gemv(a, nullptr);
+            e = hipGetLastError();
+        } catch (...) {
+            (void)hipDeviceSynchronize();
+            if (swz) (void)hipFree(swz);
+            throw;
+        }
+        if (e == hipSuccess) e = hipDeviceSynchronize();
+        if (swz) (void)hipFree(swz);
+        check_hip(e, "gemv");
+    });
+}
+dsocr_status dsocr_k_gemv_kind(int M, int N, int K, int ldw, int wdtype, int has_norm, int has_xn_out, int swizzle,
+                               const char** kind, int* rows_per_launch) {
+    return guarded([&] {
+        if (!kind) throw std::runtime_error("EINVAL: NULL argument");
+        // only which pointers are set matters to the decision; none is dereferenced
+        static float fd = 0.f;
+        static uint16_t wd = 0;
+        dsocr::DecGemvArgs a;
+        a.M = M; a.N = N; a.K = K; a.x = &fd; a.ldx = K; a.W = &wd; a.ldw = ldw; a.wdtype = wdtype;
+        a.y = &fd; a.ldy = N; a.norm_w = has_norm ? &fd : nullptr; a.xn_out = has_xn_out ? &fd : nullptr;
+        a.w_swz = swizzle ? &wd : nullptr;
+        *kind = dsocr::dec_gemv_kernel_kind(a, rows_per_launch);
+    });
+}
+dsocr_status dsocr_k_mm_swizzle(int N, int K, const void* w, void* out) {
+    return guarded([&] {
+        if (N < 1 || K < 32 || K % 32 || !w || !out) throw std::runtime_error("EINVAL: mm_swizzle needs N >= 1, K % 32 == 0, w, out");
+        dsocr::launch_mm_swizzle(w, N, K, out, nullptr);
+        check_hip(hipGetLastError(), "mm_swizzle launch");
+        check_hip(hipDeviceSynchronize(), "mm_swizzle");
+    });
+}
+dsocr_status dsocr_k_silu_mul(int rows, int I, const float* g, int ldg, float* h, int ldh) {
+    return guarded([&] {
+        if (rows < 0 || I < 1 || ldg < 2 * I || ldh < I || !g || !h) throw std::runtime_error("EINVAL: silu_mul needs ldg >= 2 I, ldh >= I");
+        dsocr::launch_silu_mul(g, ldg, I, rows, h, ldh, nullptr);
+        check_hip(hipGetLastError(), "silu_mul launch");
+        check_hip(hipDeviceSynchronize(), "silu_mul");
     });
 }
 dsocr_status dsocr_k_gemv_splitk(int M, int N, int K, const float* x, const void* W, int wdtype, const float* bias,

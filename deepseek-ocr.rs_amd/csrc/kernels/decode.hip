@@ -451,19 +451,58 @@ __global__ __launch_bounds__(256) void dec_gemv_stream_kernel(DecGemvArgs a) {
     }
 }
 
+// Which kernel one launch of a.M <= 16 rows runs: a pure host decision (no device call; the stream kernel's
+// residency query stays in the launch).  dec_gemv_rb switches on it and dec_gemv_kernel_kind names it.
+enum class GemvKind { MM, LDS_R1, LDS_R2, RB1, STREAM, RB4, RB2 };
+static int gemv_mt(int M) { return M <= 1 ? 1 : M <= 2 ? 2 : M <= 4 ? 4 : M <= 8 ? 8 : 16; }  // staged-row template
+static GemvKind gemv_kind(const DecGemvArgs& a) {
+    const int MT = gemv_mt(a.M);
+    if (MT >= 4 && MT <= 8) {  // several tokens: no LDS staging
+        // matrix-core form (decode_mm.hip): weights straight into MFMA, activations as 16-bit planes
+        if (dec_mm_ok(a)) return GemvKind::MM;
+        // rows per wave of dec_gemv_lds, measured on MI355X at M = 8, K = 1280 (tools/kbench gemv8): 2 for
+        // N = 3840 (8.4 us, 11.1 with the norm fused vs 5 + 10.6 for a separate RMSNorm), 1 for N = 1280 (5.9)
+        if (a.N <= 16384 && !a.xn_out && a.K <= 64 * 3 * 8 && a.K % 8 == 0)
+            return a.N >= 2560 ? GemvKind::LDS_R2 : GemvKind::LDS_R1;
+    }
+    // small N: one row per wave so the whole matrix is in flight at once; large N: RB rows per wave
+    if (a.N <= 16384) return GemvKind::RB1;
+    if (a.K <= 64 * 3 * 8 && MT <= 2) return GemvKind::STREAM;
+    return MT <= 2 ? GemvKind::RB4 : GemvKind::RB2;
+}
+// rows per launch: <= 16 and the staged rows must fit the 64 KB dynamic LDS window (0: K too large)
+static int gemv_rows_per_launch(int K) {
+    return (int)std::min<size_t>(16, (STAGE_LDS_MAX - sizeof(float) * XS_RED) / (sizeof(float) * (size_t)K));
+}
+
+const char* dec_gemv_kernel_kind(const DecGemvArgs& a, int* rows_per_launch) {
+    const int per = a.K > 0 ? gemv_rows_per_launch(a.K) : 0;
+    if (rows_per_launch) *rows_per_launch = per;
+    if (a.M <= 0 || a.N <= 0 || per < 1) return "none";
+    DecGemvArgs p = a;  // the first row chunk
+    p.M = std::min(per, a.M);
+    switch (gemv_kind(p)) {
+        case GemvKind::MM: return dec_mm_kernel_kind(p);
+        case GemvKind::LDS_R1: return "dec_gemv_lds_r1";
+        case GemvKind::LDS_R2: return "dec_gemv_lds_r2";
+        case GemvKind::RB1: return "dec_gemv_rb1";
+        case GemvKind::STREAM: return "dec_gemv_stream";
+        case GemvKind::RB4: return "dec_gemv_rb4";
+        case GemvKind::RB2: return "dec_gemv_rb2";
+    }
+    return "none";
+}
+
 template <typename WT, int MT>
 static void dec_gemv_rb(const DecGemvArgs& a, hipStream_t s) {
     const size_t lds = stage_bytes(a.M, a.K);
-    if constexpr (MT >= 4 && MT <= 8) {  // several tokens: no LDS staging
-        // matrix-core form (decode_mm.hip): weights straight into MFMA, activations as 16-bit planes
-        if (dec_mm_ok(a)) {
+    const GemvKind kind = gemv_kind(a);  // gemv_mt(a.M) == MT: every branch below exists for this MT
+    if constexpr (MT >= 4 && MT <= 8) {
+        if (kind == GemvKind::MM) {
             launch_dec_mm(a, s);
             return;
         }
-        // rows per wave of dec_gemv_lds, measured on MI355X at M = 8, K = 1280 (tools/kbench gemv8): 2 for
-        // N = 3840 (8.4 us, 11.1 with the norm fused vs 5 + 10.6 for a separate RMSNorm), 1 for N = 1280 (5.9)
-        const int rows_rb = a.N >= 2560 ? 2 : 1;
-        if (a.N <= 16384 && !a.xn_out && a.K <= 64 * 3 * 8 && a.K % 8 == 0) {
+        if (kind == GemvKind::LDS_R1 || kind == GemvKind::LDS_R2) {
             const size_t xl = sizeof(float) * MT * (size_t)a.K;
 #define DSOCR_GR(R)                                                                                                   \
     do {                                                                                                              \
@@ -471,46 +510,52 @@ static void dec_gemv_rb(const DecGemvArgs& a, hipStream_t s) {
         if (a.norm_w) DSOCR_LAUNCH((dec_gemv_lds_kernel<WT, MT, R, true>), g, dim3(256), xl, s, a);                   \
         else DSOCR_LAUNCH((dec_gemv_lds_kernel<WT, MT, R, false>), g, dim3(256), xl, s, a);                           \
     } while (0)
-            if (rows_rb == 1) DSOCR_GR(1); else DSOCR_GR(2);
+            if (kind == GemvKind::LDS_R1) DSOCR_GR(1); else DSOCR_GR(2);
 #undef DSOCR_GR
             return;
         }
     }
-    // small N: one row per wave so the whole matrix is in flight at once; large N: RB rows per wave
-    if (a.N <= 16384) {
+    if (kind == GemvKind::RB1) {
         constexpr int RB = 1;
         DSOCR_LAUNCH((dec_gemv_kernel<WT, MT, RB, 3>), dim3((a.N + 4 * RB - 1) / (4 * RB)), dim3(256), lds, s, a);
-    } else if (a.K <= 64 * 3 * 8 && MT <= 2) {
-        constexpr int RB = 4;
-        // exactly one resident wave of blocks (no tail of late-starting blocks)
-        static int resident = 0;
-        if (!resident) {
-            int per_cu = 0, dev = 0, cus = 0;
-            (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, dec_gemv_stream_kernel<WT, MT, RB>, 256, lds);
-            (void)hipGetDevice(&dev);
-            (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-            resident = std::max(1, per_cu) * std::max(1, cus);
-        }
-        const int groups = (a.N + RB - 1) / RB;
-        const int blocks = std::min((groups + 3) / 4, resident);
-        DSOCR_LAUNCH((dec_gemv_stream_kernel<WT, MT, RB>), dim3(blocks), dim3(256), lds, s, a);
-    } else {
-        constexpr int RB = MT <= 2 ? 4 : 2;
-        DSOCR_LAUNCH((dec_gemv_kernel<WT, MT, RB, 3>), dim3((a.N + 4 * RB - 1) / (4 * RB)), dim3(256), lds, s, a);
+        return;
     }
+    if constexpr (MT <= 2) {
+        if (kind == GemvKind::STREAM) {
+            constexpr int RB = 4;
+            // exactly one resident wave of blocks (no tail of late-starting blocks)
+            static int resident = 0;
+            if (!resident) {
+                int per_cu = 0, dev = 0, cus = 0;
+                (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, dec_gemv_stream_kernel<WT, MT, RB>, 256, lds);
+                (void)hipGetDevice(&dev);
+                (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+                resident = std::max(1, per_cu) * std::max(1, cus);
+            }
+            const int groups = (a.N + RB - 1) / RB;
+            const int blocks = std::min((groups + 3) / 4, resident);
+            DSOCR_LAUNCH((dec_gemv_stream_kernel<WT, MT, RB>), dim3(blocks), dim3(256), lds, s, a);
+            return;
+        }
+    }
+    // GemvKind::RB4 (one or two rows) / GemvKind::RB2 (more)
+    constexpr int RB = MT <= 2 ? 4 : 2;
+    if (kind != (MT <= 2 ? GemvKind::RB4 : GemvKind::RB2)) throw std::runtime_error("EINTERNAL: dec_gemv dispatch");
+    DSOCR_LAUNCH((dec_gemv_kernel<WT, MT, RB, 3>), dim3((a.N + 4 * RB - 1) / (4 * RB)), dim3(256), lds, s, a);
 }
 template <typename WT>
 static void dec_gemv_dispatch(const DecGemvArgs& a, hipStream_t s) {
-    if (a.M <= 1) dec_gemv_rb<WT, 1>(a, s);
-    else if (a.M <= 2) dec_gemv_rb<WT, 2>(a, s);
-    else if (a.M <= 4) dec_gemv_rb<WT, 4>(a, s);
-    else if (a.M <= 8) dec_gemv_rb<WT, 8>(a, s);
-    else dec_gemv_rb<WT, 16>(a, s);
+    switch (gemv_mt(a.M)) {
+        case 1: dec_gemv_rb<WT, 1>(a, s); break;
+        case 2: dec_gemv_rb<WT, 2>(a, s); break;
+        case 4: dec_gemv_rb<WT, 4>(a, s); break;
+        case 8: dec_gemv_rb<WT, 8>(a, s); break;
+        default: dec_gemv_rb<WT, 16>(a, s); break;
+    }
 }
 void launch_dec_gemv(const DecGemvArgs& a, hipStream_t s) {
     if (a.M == 0 || a.N == 0) return;
-    // rows per launch: <= 16 and the staged rows must fit the 64 KB dynamic LDS window
-    const int per = (int)std::min<size_t>(16, (STAGE_LDS_MAX - sizeof(float) * XS_RED) / (sizeof(float) * a.K));
+    const int per = gemv_rows_per_launch(a.K);
     if (per < 1) throw std::runtime_error("EINVAL: dec_gemv K too large for LDS staging");
     for (int m0 = 0; m0 < a.M; m0 += per) {
         DecGemvArgs p = a;

@@ -337,16 +337,21 @@ static void mm_launch(const DecGemvArgs& a, hipStream_t s) {
 // block shapes (K steps of 32 a multiple of 40: per-wave batches divide evenly): WR 8 persistent for the
 // large-N head, WK 8 (K split over 8 waves) otherwise (measured: WK 4, WR 4 persistent and a k-permuted A
 // fragment order were slower)
+static bool mm_wide(const DecGemvArgs& a) { return a.N >= 16384; }  // the WR 8 persistent shape
+const char* dec_mm_kernel_kind(const DecGemvArgs& a) {
+    if (a.w_swz) return mm_wide(a) ? "dec_mm_wr8_swz" : "dec_mm_wk8_swz";
+    return mm_wide(a) ? "dec_mm_wr8" : "dec_mm_wk8";
+}
 template <typename WT, bool NORM>
 static void mm_dispatch(const DecGemvArgs& a, hipStream_t s) {
     if (a.w_swz) {  // fragment-ordered weights (3..8 pages: the lm_head's copy, q/k/v, o_proj, dense gate|up)
         DecGemvArgs b = a;
         b.W = a.w_swz;
-        if (a.N >= 16384) mm_launch<WT, 8, 1, 10, 1, NORM, true>(b, s);
+        if (mm_wide(a)) mm_launch<WT, 8, 1, 10, 1, NORM, true>(b, s);
         else mm_launch<WT, 1, 8, 5, 1, NORM, true>(b, s);
         return;
     }
-    if (a.N >= 16384) mm_launch<WT, 8, 1, 10, 1, NORM>(a, s);
+    if (mm_wide(a)) mm_launch<WT, 8, 1, 10, 1, NORM>(a, s);
     else mm_launch<WT, 1, 8, 5, 1, NORM>(a, s);
 }
 

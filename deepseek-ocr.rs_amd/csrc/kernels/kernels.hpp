@@ -264,6 +264,12 @@ struct DecGemvArgs {
     unsigned long long* span = nullptr;  // launch-span slots (dec_gemv, dec_mm, dec_route_grp) or null
 };
 void launch_dec_gemv(const DecGemvArgs& a, hipStream_t s);
+// Which kernel launch_dec_gemv runs for its first row chunk (the decision the launch itself switches on; host
+// only, no device call), as a static string: dec_gemv_rb1 / _rb2 / _rb4 (dec_gemv_kernel, rows per wave),
+// dec_gemv_stream, dec_gemv_lds_r1 / _r2, dec_mm_wk8 / dec_mm_wr8 (+ _swz on a fragment-ordered copy), or
+// "none" for an empty or unlaunchable call.  rows_per_launch (optional): token rows per launch (0: K too large).
+const char* dec_gemv_kernel_kind(const DecGemvArgs& a, int* rows_per_launch = nullptr);
+const char* dec_mm_kernel_kind(const DecGemvArgs& a);  // block shape of launch_dec_mm (dec_mm_ok(a) holds)
 // 3..8 tokens on the matrix cores (decode_mm.hip): weight rows as MFMA A operands, the (optionally
 // RMS-normalised) activation rows as three exact 16-bit planes (f16: per-row power-of-two scaled)
 bool dec_mm_ok(const DecGemvArgs& a);

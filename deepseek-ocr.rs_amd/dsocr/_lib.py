@@ -93,6 +93,7 @@ EXPORTS = [
     "dsocr_engine_load_flags", "dsocr_engine_packed_info", "dsocr_k_moe_packed", "dsocr_k_dsq_rows_dot",
     "dsocr_k_moe_ex", "dsocr_k_moe_route_kind", "dsocr_k_moe_prefill_route", "dsocr_k_moe_combine",
     "dsocr_k_gemm_bf16", "dsocr_k_dots_op",
+    "dsocr_k_gemv_ex", "dsocr_k_gemv_kind", "dsocr_k_mm_swizzle", "dsocr_k_silu_mul",
     "dsocr_config_variant", "dsocr_engine_variant", "dsocr_prepare_page_variant", "dsocr_prepare_page_device_variant", "dsocr_k_attention_prefix",
 ]
 
@@ -173,6 +174,11 @@ def lib():
                                        i32, vp, i32, i32, i32]
     L.dsocr_k_gemv.argtypes = [i32, i32, i32, vp, vp, f32, vp, i32, vp, vp, i32, i32]
     L.dsocr_k_gemv_splitk.argtypes = [i32, i32, i32, vp, vp, i32, vp, vp, i32]
+    L.dsocr_k_gemv_ex.argtypes = [i32, i32, i32, vp, i32, vp, f32, vp, i32, i32, vp, vp, i32, i32, i32, i32,
+                                  C.POINTER(C.c_char_p)]
+    L.dsocr_k_gemv_kind.argtypes = [i32, i32, i32, i32, i32, i32, i32, i32, C.POINTER(C.c_char_p), C.POINTER(i32)]
+    L.dsocr_k_mm_swizzle.argtypes = [i32, i32, vp, vp]
+    L.dsocr_k_silu_mul.argtypes = [i32, i32, vp, i32, vp, i32]
     L.dsocr_k_layernorm.argtypes = [i32, i32, vp, vp, vp, f32, vp]
     L.dsocr_k_rmsnorm.argtypes = [i32, i32, vp, vp, f32, vp]
     L.dsocr_k_dsq_dequant.argtypes = [i32, vp, sz, sz, sz, vp]

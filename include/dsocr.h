@@ -309,6 +309,30 @@ dsocr_status dsocr_k_gemm_grouped(int M, int N, int K, const float* A, int lda, 
  * act(xn . W^T + bias) (+ y), xn = rmsnorm(x; norm_w, eps) when norm_w != NULL (block.rs:24-29), else x. */
 dsocr_status dsocr_k_gemv(int M, int N, int K, const float* x, const float* norm_w, float eps, const void* W,
                           int wdtype, const float* bias, float* y, int act, int accumulate);
+/* dsocr_k_gemv with every stride and form the engine passes: x [M][ldx], W [N][ldw] (16-bit), y [M][ldy].
+ * swizzle != 0: W (row-major, ldw == K) is first copied to dec_mm's fragment order and the launch reads the copy,
+ * as the engine does at 3..8 pages; DSOCR_EINVAL where the dispatch would not run dec_mm on it.  *kind (optional)
+ * receives the kernel the dispatch picked, as dsocr_k_gemv_kind names it.  dsocr_k_gemv is this with
+ * (ldx = K, ldw = K, ldy = N, swizzle = 0). */
+dsocr_status dsocr_k_gemv_ex(int M, int N, int K, const float* x, int ldx, const float* norm_w, float eps,
+                             const void* W, int ldw, int wdtype, const float* bias, float* y, int ldy, int act,
+                             int accumulate, int swizzle, const char** kind);
+/* Which kernel the decode-linear dispatch picks (pure host decision, no device call; static string):
+ * "dec_gemv_rb1" / "dec_gemv_rb2" / "dec_gemv_rb4" (dec_gemv_kernel, 1 / 2 / 4 weight rows per wave),
+ * "dec_gemv_stream" (1..2 tokens, N > 16384, K <= 1536), "dec_gemv_lds_r1" / "dec_gemv_lds_r2" (3..8 tokens,
+ * K <= 1536), "dec_mm_wk8" / "dec_mm_wr8" (3..8 tokens, K = 1280 on the matrix cores; wr8 from N = 16384) and
+ * "dec_mm_wk8_swz" / "dec_mm_wr8_swz" (the same on a fragment-ordered copy), "none" for an empty call.  The kind
+ * is that of the first launch; *rows_per_launch (optional) is how many token rows one launch takes (at most 16,
+ * fewer when K is long: the call is split into ceil(M / rows) launches). */
+dsocr_status dsocr_k_gemv_kind(int M, int N, int K, int ldw, int wdtype, int has_norm, int has_xn_out, int swizzle,
+                               const char** kind, int* rows_per_launch);
+/* W [N][K] row-major 16-bit -> dec_mm's fragment order [ceil(N/16) tiles][K/32 steps][64 lanes][8]: lane l of
+ * step t of tile T holds W[min(16 T + (l & 15), N - 1)][32 t + 8 (l >> 4) .. + 7].  out: 16 ceil(N/16) K
+ * elements.  K % 32 == 0.  Device pointers. */
+dsocr_status dsocr_k_mm_swizzle(int N, int K, const void* w, void* out);
+/* h[r][i] = silu(g[r][i]) * g[r][I + i] (candle silu: x / (1 + exp(-x))), g [rows][ldg] = gate | up, h [rows][ldh]:
+ * the launch between the two matrix-core linears of the dense MLP at 3..8 pages. */
+dsocr_status dsocr_k_silu_mul(int rows, int I, const float* g, int ldg, float* h, int ldh);
 /* Long-K decode linear for 1..8 rows on the matrix cores (the dense layer-0 down projection of the
  * 3..8-page decode, K = 6848): y[M][N] (+)= x . W^T + bias, split-K with an in-launch ordered sum. */
 dsocr_status dsocr_k_gemv_splitk(int M, int N, int K, const float* x, const void* W, int wdtype, const float* bias,

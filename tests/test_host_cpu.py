@@ -230,3 +230,58 @@ def test_moe_dispatch_kernel_names():
         g, d = C.c_char_p(), C.c_char_p()
         check(lib().dsocr_k_moe_kernels(T, 1280, 64, 6, 896, 1792, 1, C.byref(g), C.byref(d)))
         assert (g.value.decode(), d.value.decode()) == (gu, dn), T
+
+
+# (M, N, K, ldw, wdtype, norm, xn_out, swizzle) -> (kind, token rows per launch), worked out by hand from
+# dec_gemv_rb / launch_dec_gemv / mm_dispatch: rows = min(16, (64 KiB - 512 B) / (4 K)); the staged-row template
+# is 1, 2, 4, 8 or 16 by the first chunk's rows; 3..8 rows take dec_mm when K = 1280, N >= 16, ldw % 8 == 0 and no
+# xn_out (WR 8 from N = 16384), else dec_gemv_lds when N <= 16384 and K <= 1536 (2 rows per wave from N = 2560);
+# otherwise dec_gemv_kernel with 1 row per wave up to N = 16384, above it the stream kernel (1..2 rows, K <= 1536)
+# or 4 (1..2 rows) / 2 rows per wave.  wdtype 0 bf16, 1 f16.
+_GEMV_KINDS = [
+    # the engine's linears at 3..8 pages, on the fragment-ordered copies (Engine::ensure_mm_weights)
+    *[((B, 3840, 1280, 1280, 1, 1, 0, 1), ("dec_mm_wk8_swz", 12)) for B in (3, 4, 5, 8)],   # q/k/v, norm fused
+    *[((B, 1280, 1280, 1280, 1, 0, 0, 1), ("dec_mm_wk8_swz", 12)) for B in (3, 8)],         # o_proj
+    *[((B, 13696, 1280, 1280, 1, 1, 0, 1), ("dec_mm_wk8_swz", 12)) for B in (3, 8)],        # dense gate|up
+    *[((B, 129280, 1280, 1280, 0, 1, 0, 1), ("dec_mm_wr8_swz", 12)) for B in (3, 8)],       # lm_head
+    # the same without a copy (DSOCR_MM_SWZ=0, the screened-head tests)
+    ((8, 3840, 1280, 1280, 1, 1, 0, 0), ("dec_mm_wk8", 12)), ((3, 129280, 1280, 1280, 0, 1, 0, 0), ("dec_mm_wr8", 12)),
+    ((8, 16383, 1280, 1280, 1, 0, 0, 0), ("dec_mm_wk8", 12)), ((8, 16384, 1280, 1280, 1, 0, 0, 0), ("dec_mm_wr8", 12)),
+    ((8, 16, 1280, 1288, 0, 0, 0, 0), ("dec_mm_wk8", 12)),
+    # one or two pages at the lm_head: the stream kernel, whether or not a copy exists
+    ((1, 129280, 1280, 1280, 0, 1, 0, 0), ("dec_gemv_stream", 12)), ((2, 129280, 1280, 1280, 0, 1, 0, 1), ("dec_gemv_stream", 12)),
+    ((2, 16400, 256, 256, 0, 0, 0, 0), ("dec_gemv_stream", 16)),
+    # outside dec_mm: K, N < 16, a handed-on xn, an unaligned weight pitch, more than 8 rows
+    ((8, 896, 1792, 1792, 1, 0, 0, 0), ("dec_gemv_rb1", 9)), ((8, 8, 1280, 1280, 1, 0, 0, 0), ("dec_gemv_lds_r1", 12)),
+    ((8, 3840, 1280, 1280, 1, 1, 1, 0), ("dec_gemv_rb1", 12)), ((8, 3840, 1280, 1284, 1, 1, 0, 0), ("dec_gemv_lds_r2", 12)),
+    ((9, 3840, 1280, 1280, 1, 1, 0, 0), ("dec_gemv_rb1", 12)), ((13, 3840, 1280, 1280, 1, 1, 0, 1), ("dec_gemv_rb1", 12)),
+    # dec_gemv_lds and its rows per wave
+    ((4, 200, 512, 512, 0, 0, 0, 0), ("dec_gemv_lds_r1", 16)), ((8, 2600, 256, 256, 0, 1, 0, 0), ("dec_gemv_lds_r2", 16)),
+    ((3, 2559, 256, 256, 1, 0, 0, 0), ("dec_gemv_lds_r1", 16)), ((3, 2560, 256, 256, 1, 0, 0, 0), ("dec_gemv_lds_r2", 16)),
+    ((5, 16384, 1536, 1536, 1, 0, 0, 0), ("dec_gemv_lds_r2", 10)), ((5, 16384, 1544, 1544, 1, 0, 0, 0), ("dec_gemv_rb1", 10)),
+    # dec_gemv_kernel's rows per wave
+    ((1, 130, 64, 64, 1, 0, 0, 0), ("dec_gemv_rb1", 16)), ((2, 16384, 256, 256, 0, 0, 0, 0), ("dec_gemv_rb1", 16)),
+    ((1, 16400, 1544, 1544, 1, 0, 0, 0), ("dec_gemv_rb4", 10)), ((2, 20000, 1792, 1792, 0, 1, 0, 0), ("dec_gemv_rb4", 9)),
+    ((3, 16400, 256, 256, 0, 0, 0, 0), ("dec_gemv_rb2", 16)), ((16, 16400, 64, 64, 0, 0, 0, 0), ("dec_gemv_rb2", 16)),
+    ((8, 16385, 1792, 1792, 1, 0, 0, 0), ("dec_gemv_rb2", 9)),
+    # the row-chunk loop: the kind is the first chunk's
+    ((3, 64, 6848, 6848, 1, 0, 0, 0), ("dec_gemv_rb1", 2)), ((8, 1280, 6848, 6848, 1, 0, 0, 0), ("dec_gemv_rb1", 2)),
+    ((21, 513, 128, 128, 0, 1, 0, 0), ("dec_gemv_rb1", 16)), ((21, 16400, 128, 128, 0, 1, 0, 0), ("dec_gemv_rb2", 16)),
+    # nothing to launch
+    ((0, 1280, 1280, 1280, 1, 0, 0, 0), ("none", 12)), ((4, 0, 1280, 1280, 1, 0, 0, 0), ("none", 12)),
+    ((1, 64, 16384, 16384, 1, 0, 0, 0), ("none", 0)),
+]
+
+
+def test_gemv_dispatch_kernel_kinds():
+    """Which kernel launch_dec_gemv runs and how many token rows one launch takes (host-only query; the decision the
+    launch itself switches on), pinned for the engine's decode linears and every branch of the dispatch."""
+    import ctypes as C
+    from dsocr._lib import check, lib
+    for args, want in _GEMV_KINDS:
+        k, r = C.c_char_p(), C.c_int(-1)
+        check(lib().dsocr_k_gemv_kind(*args, C.byref(k), C.byref(r)))
+        assert (k.value.decode(), r.value) == want, args
+    kinds = {w[0] for _, w in _GEMV_KINDS}
+    assert kinds >= {"dec_gemv_rb1", "dec_gemv_rb2", "dec_gemv_rb4", "dec_gemv_stream", "dec_gemv_lds_r1", "dec_gemv_lds_r2",
+                     "dec_mm_wk8", "dec_mm_wr8", "dec_mm_wk8_swz", "dec_mm_wr8_swz"}
