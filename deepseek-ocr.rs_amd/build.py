@@ -23,8 +23,9 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 CLANG = os.environ.get("DSOCR_CXX", "/opt/rocm/llvm/bin/clang++")
 ARCH = "gfx950"
 
-KERNELS = ["gemm", "gemm_bf16", "moe", "norm", "attention", "misc", "decode", "lmhead", "dsq", "preprocess", "sampling",
-           "dots_ops", "attention_bf16", "decode_mm", "decode_persist", "decode_q", "attention_prefix", "ocr2_ops"]
+KERNELS = ["gemm", "gemm_bf16", "moe", "norm", "attention", "misc", "decode_gemv", "decode_attn", "decode_route",
+           "decode_moe", "decode_sample", "lmhead", "dsq", "preprocess", "sampling", "dots_ops", "attention_bf16",
+           "decode_mm", "decode_persist", "decode_q", "attention_prefix", "ocr2_ops"]
 HOST = ["engine", "dots", "capi"]
 
 

@@ -1209,7 +1209,7 @@ static bool mm_swz_off() {
 }
 
 // Decode MoE arguments of layer l for B pages (shared by decode_step and profile_decode): the
-// layer's weights and the named workspaces; launch_moe_decode (decode.hip) picks the kernels.
+// layer's weights and the named workspaces; launch_moe_decode (decode_moe.hip) picks the kernels.
 MoeDecodeArgs Engine::moe_args(int l, int B, float* X) {
     const LangConfig& L = cfg_.lang;
     DecLayer& d = layers_[l];
@@ -1366,7 +1366,7 @@ bool Engine::dense_mm_ok(const DecLayer& d, int B) const {
 }
 
 void Engine::decode_step(int B, int Lmax) {
-    // One token for each of B pages: 8 launches per layer (decode.hip).  For B <= 2 the
+    // One token for each of B pages: 8 launches per layer (decode_common.hpp).  For B <= 2 the
     // RMSNorms are fused into the consuming GEMV / expert kernels (x normalised on the fly).
     const LangConfig& L = cfg_.lang;
     hipStream_t st = stream_;

@@ -11,7 +11,7 @@
 //    [S,S]), causal masking (block.rs:1504-1526), variable sequence lengths.
 // 2. sam_relbias: per-query rel-pos dot products q.Rh / q.Rw.
 // 3. rope_kv: rotate_half RoPE (block.rs:1403-1471) + KV-cache append (prefill rows;
-//    the decode step fuses both into dec_attn_kernel, decode.hip).
+//    the decode step fuses both into dec_attn_kernel, decode_attn.hip).
 #include <algorithm>
 #include <cstdlib>
 

@@ -22,8 +22,7 @@
 #include <stdexcept>
 #include <string>
 
-#include "dev_common.hpp"
-#include "kernels.hpp"
+#include "decode_common.hpp"
 
 namespace dsocr {
 
@@ -380,11 +379,9 @@ void launch_mm_swizzle(const void* w, int N, int K, void* out, hipStream_t s) {
 
 void launch_dec_mm(const DecGemvArgs& a, hipStream_t s) {
     if (!dec_mm_ok(a)) throw std::runtime_error("EINVAL: dec_mm outside its range");
-    if (a.wdtype == WDT_BF16) {
-        if (a.norm_w) mm_dispatch<bf16_t, true>(a, s); else mm_dispatch<bf16_t, false>(a, s);
-    } else {
-        if (a.norm_w) mm_dispatch<f16_t, true>(a, s); else mm_dispatch<f16_t, false>(a, s);
-    }
+    with_wt(a.wdtype, [&](auto wt) {
+        if (a.norm_w) mm_dispatch<decltype(wt), true>(a, s); else mm_dispatch<decltype(wt), false>(a, s);
+    });
 }
 
 // ------------------------------------------------------------------ grouped decode MoE gate/up (3..8 tokens)
@@ -772,8 +769,10 @@ void launch_moe_gateup_mm(const MoeDec2Args& a, hipStream_t s) {
             else DSOCR_GM(WTY, SW, 1, false);                               \
         }                                                                   \
     } while (0)
-    if (a.wdtype == WDT_BF16) { if (a.Wgu_swz) DSOCR_GMK(bf16_t, true); else DSOCR_GMK(bf16_t, false); }
-    else { if (a.Wgu_swz) DSOCR_GMK(f16_t, true); else DSOCR_GMK(f16_t, false); }
+    with_wt(a.wdtype, [&](auto wt) {
+        using WT = decltype(wt);
+        if (a.Wgu_swz) DSOCR_GMK(WT, true); else DSOCR_GMK(WT, false);
+    });
 #undef DSOCR_GMK
 #undef DSOCR_GM
 }
@@ -1051,8 +1050,10 @@ void launch_moe_down_mm(const MoeDec2Args& a, hipStream_t s) {
         if (dn_ks() == 2 && ((a.I >> 5) / 7) % 2 == 0) DSOCR_LAUNCH((moe_down_mm_kernel<WTY, 7, SW, 4, 2>), grid, dim3(512), lds, s, a); \
         else DSOCR_LAUNCH((moe_down_mm_kernel<WTY, 7, SW, 4, 1>), grid, dim3(256), lds, s, a);          \
     } while (0)
-    if (a.wdtype == WDT_BF16) { if (a.Wd_swz) DSOCR_DM(bf16_t, true); else DSOCR_DM(bf16_t, false); }
-    else { if (a.Wd_swz) DSOCR_DM(f16_t, true); else DSOCR_DM(f16_t, false); }
+    with_wt(a.wdtype, [&](auto wt) {
+        using WT = decltype(wt);
+        if (a.Wd_swz) DSOCR_DM(WT, true); else DSOCR_DM(WT, false);
+    });
 #undef DSOCR_DM
 }
 
@@ -1173,8 +1174,9 @@ size_t dec_mm_splitk_ticks(int N) { return (size_t)(N + 63) / 64; }
 void launch_dec_mm_splitk(const DecGemvArgs& a, float* part, int* tick, hipStream_t s) {
     if (!dec_mm_splitk_ok(a) || !part || !tick) throw std::runtime_error("EINVAL: dec_mm_splitk outside its range");
     const int n_pieces = (a.K + MMK_PIECE - 1) / MMK_PIECE, tiles = (a.N + 63) / 64;
-    if (a.wdtype == WDT_BF16) DSOCR_LAUNCH((dec_mm_splitk_kernel<bf16_t>), dim3(n_pieces * tiles), dim3(256), 0, s, a, part, tick);
-    else DSOCR_LAUNCH((dec_mm_splitk_kernel<f16_t>), dim3(n_pieces * tiles), dim3(256), 0, s, a, part, tick);
+    with_wt(a.wdtype, [&](auto wt) {
+        DSOCR_LAUNCH((dec_mm_splitk_kernel<decltype(wt)>), dim3(n_pieces * tiles), dim3(256), 0, s, a, part, tick);
+    });
 }
 
 }  // namespace dsocr

@@ -16,7 +16,7 @@ struct QMat {
 };
 
 // Profiling hook: while prof_events() holds a (start, stop) pair, the next kernel launched through
-// DSOCR_LAUNCH (decode.hip, lmhead.hip) records its own dispatch begin / end into the two events
+// DSOCR_LAUNCH (the decode_*.hip units, lmhead.hip) records its own dispatch begin / end into the two events
 // (hipExtLaunchKernelGGL: the dispatch-packet timestamps rocprofv3's kernel trace reports) and the
 // pair is cleared.  Host-side, per thread; never set while a stream is being captured.
 // In-context launch spans (dev_common.hpp WaveSpan): per-wave (entry, exit) slots of one launch,
@@ -243,7 +243,7 @@ struct SampleArgs {
 };
 void launch_rep_penalty(const SampleArgs& a, hipStream_t s);
 
-// ------------------------------------------------------------------ fused decode step (decode.hip)
+// ------------------------------------------------------------------ fused decode step (decode_gemv / _attn / _route / _moe / _sample.hip)
 // Skinny linear with the preceding RMSNorm fused (norm_w != null: x is normalised on the fly).
 struct DecGemvArgs {
     int M = 0, N = 0, K = 0;

@@ -178,7 +178,7 @@ void launch_trace_logits(const float* logits, int B, int V, long ld, const int* 
 
 // ------------------------------------------------------------------ repetition penalty
 // sampling.rs:34-96: every distinct context token's logit is divided (>0) or multiplied
-// (<=0) by the penalty once.  Selection itself is dec_argmax_partial / dec_sample_final (decode.hip).
+// (<=0) by the penalty once.  Selection itself is dec_argmax_partial / dec_sample_final (decode_sample.hip).
 __global__ void rep_penalty_kernel(SampleArgs a) {
     // apply once per distinct context token: the first occurrence applies it
     const int b = blockIdx.y;
@@ -200,6 +200,13 @@ __global__ void rep_penalty_kernel(SampleArgs a) {
 void launch_rep_penalty(const SampleArgs& a, hipStream_t s) {
     if (a.rep_penalty > 0.f && fabsf(a.rep_penalty - 1.0f) > 1.1920929e-07f)
         hipLaunchKernelGGL(rep_penalty_kernel, dim3(8, a.B), dim3(256), 0, s, a);
+}
+
+// ------------------------------------------------------------------ launch profiling hook (diagnostics)
+// The event pair DSOCR_LAUNCH consumes (kernels.hpp ProfEvents): one per thread, for every launch in the library.
+ProfEvents& prof_events() {
+    static thread_local ProfEvents p;
+    return p;
 }
 
 // ------------------------------------------------------------------ launch spans (diagnostics)

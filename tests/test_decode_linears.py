@@ -1,5 +1,5 @@
 """The decode linears in every form the engine launches them (launch_dec_gemv and the kernels it picks in
-decode.hip / decode_mm.hip, launch_mm_swizzle, launch_silu_mul) on MI355X (gfx950), one launch at a time.
+decode_gemv.hip / decode_mm.hip, launch_mm_swizzle, launch_silu_mul) on MI355X (gfx950), one launch at a time.
 
 Reference of every linear: act((xn . W^T in f64) -> f32 + bias) (+ y0), xn the oracle's f32 rms_norm when a norm
 weight is given.  Tolerance (the project's bound for f32 sums in another order, tests/test_gpu_kernels.py):

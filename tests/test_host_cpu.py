@@ -219,17 +219,76 @@ def test_engine_load_errors_without_gpu_are_loud():
         load_model(ModelLoadArgs(config_path="/nonexistent/config.json"))
 
 
-def test_moe_dispatch_kernel_names():
-    """Which kernels the dispatch picks (host-only query; the bench labels its roofline with it)."""
+# Decode MoE dispatch over T = 1..9 tokens, I = 896, norm fused: (Is, (E, topk), H) -> "gate-up/down" per T, as the
+# query answered BEFORE the plan was made the launch's own switch (recorded from that build), then corrected by
+# _moe_names_fix for the two shapes where that answer named a kernel the launch did not run.
+_MOE_GU = {"mix": "moe_gateup_mix_kernel", "slot": "moe_gateup_slot_kernel", "gu2": "moe_gateup2_kernel",
+           "slot+sh": "moe_gateup_slot_kernel+moe_gateup_shared_kernel", "mm": "moe_gateup_mm_kernel"}
+_MOE_DN = {"mix": "moe_down_mix_kernel", "slot": "moe_down_slot_kernel", "dn2": "moe_down2_kernel", "mm": "moe_down_mm_kernel"}
+_MOE_NAMES_RECORDED = {
+    (0, (64, 6), 1280): "mix/mix slot/slot mm/mm mm/mm mm/mm mm/mm mm/mm mm/mm gu2/dn2",
+    (0, (64, 6), 2048): "slot/mix slot/slot slot/slot slot/slot slot/slot slot/slot slot/slot slot/slot gu2/dn2",
+    (0, (128, 8), 1280): "slot/mix slot/slot mm/mm mm/mm mm/mm mm/mm mm/mm mm/mm gu2/dn2",
+    (0, (128, 8), 2048): "slot/mix slot/slot slot/slot slot/slot slot/slot slot/slot slot/slot slot/slot gu2/dn2",
+    (1792, (64, 6), 1280): "mix/mix slot/slot mm/mm mm/mm mm/mm mm/mm mm/mm mm/mm gu2/dn2",
+    (1792, (64, 6), 2048): "slot/mix slot/slot slot+sh/slot slot+sh/slot slot+sh/slot slot+sh/slot slot+sh/slot slot+sh/slot gu2/dn2",
+    (1792, (128, 8), 1280): "slot/slot slot/slot mm/mm mm/mm mm/mm mm/mm mm/mm mm/mm gu2/dn2",
+    (1792, (128, 8), 2048): "slot/slot slot/slot slot+sh/slot slot+sh/slot slot+sh/slot slot+sh/slot slot+sh/slot slot+sh/slot gu2/dn2",
+}
+# (DSOCR_ROUTE_FUSED, (E, topk), H) -> routing implementation per T (the same with and without a shared expert); recorded
+# from the same build, nothing corrected
+_MOE_ROUTE_RECORDED = {
+    **{(f, (64, 6), 1280): ["moe_gateup_mix", "moe_gateup_slot"] + [k] * 6 + ["moe_route"]
+       for f, k in (("0", "dec_route_grp"), ("1", "moe_gateup_mm"))},
+    **{(f, (128, 8), 1280): ["moe_gateup_slot"] * 2 + ["dec_router"] * 6 + ["moe_route"] for f in "01"},
+    **{(f, ek, 2048): ["moe_gateup_slot"] * 8 + ["moe_route"] for f in "01" for ek in ((64, 6), (128, 8))},
+}
+
+
+def _moe_names_fix(gu, dn, H, topk):
+    # 1. H > 1536 in slot mode (T <= 8 here): the name said moe_gateup_slot_kernel (+ shared), but the slot kernels
+    #    stage K <= 1536 and launch_moe_gateup2 fell through to moe_gateup2_kernel (its self-routing slot branch)
+    if H > 1536 and gu in ("slot", "slot+sh"):
+        gu = "gu2"
+    # 2. top-k 8 in slot mode: moe_down_slot_kernel exists for top-k 6 and 3 only, so wherever the split-K
+    #    moe_down_mix_kernel did not take the token, launch_moe_down2 ran moe_down2_kernel under the name of the slot one
+    if topk == 8 and dn == "slot":
+        dn = "dn2"
+    return gu, dn
+
+
+_MOE_GRID = [(T, Is, ek, H) for T in range(1, 10) for Is in (0, 1792) for ek in ((64, 6), (128, 8)) for H in (1280, 2048)]
+
+
+def test_moe_dispatch_kernel_names(monkeypatch):
+    """Which kernels the dispatch picks (host-only query; the bench labels its roofline with it): the plan the launch
+    switches on, over every token count of the decode forms, with and without a shared expert, 64 x top-6 and
+    128 x top-8 experts, a hidden size the slot kernels stage and one they do not, both DSOCR_ROUTE_FUSED values."""
     import ctypes as C
     from dsocr._lib import check, lib
-    want = {1: ("moe_gateup_mix_kernel", "moe_down_mix_kernel"), 2: ("moe_gateup_slot_kernel", "moe_down_slot_kernel"),
-            3: ("moe_gateup_mm_kernel", "moe_down_mm_kernel"), 8: ("moe_gateup_mm_kernel", "moe_down_mm_kernel"),
-            9: ("moe_gateup2_kernel", "moe_down2_kernel")}
-    for T, (gu, dn) in want.items():
+    for fused, (T, Is, (E, topk), H) in [(f, g) for f in "01" for g in _MOE_GRID]:
+        monkeypatch.setenv("DSOCR_ROUTE_FUSED", fused)
+        gu, dn = _MOE_NAMES_RECORDED[(Is, (E, topk), H)].split()[T - 1].split("/")
+        gu, dn = _moe_names_fix(gu, dn, H, topk)
         g, d = C.c_char_p(), C.c_char_p()
-        check(lib().dsocr_k_moe_kernels(T, 1280, 64, 6, 896, 1792, 1, C.byref(g), C.byref(d)))
-        assert (g.value.decode(), d.value.decode()) == (gu, dn), T
+        check(lib().dsocr_k_moe_kernels(T, H, E, topk, 896, Is, 1, C.byref(g), C.byref(d)))
+        assert (g.value.decode(), d.value.decode()) == (_MOE_GU[gu], _MOE_DN[dn]), (fused, T, Is, E, topk, H)
+    # the flagship's forms (1280 hidden, 64 x top-6 + 2 shared) as they were pinned before the grid
+    want = {1: ("mix", "mix"), 2: ("slot", "slot"), 3: ("mm", "mm"), 8: ("mm", "mm"), 9: ("gu2", "dn2")}
+    flag = _MOE_NAMES_RECORDED[(1792, (64, 6), 1280)].split()
+    assert all(tuple(flag[T - 1].split("/")) == w for T, w in want.items())
+
+
+def test_moe_dispatch_route_kinds(monkeypatch):
+    """Which routing implementation the same plan picks (dsocr_k_moe_route_kind; test_moe_routing chooses its oracle
+    by it), over the same grid."""
+    import ctypes as C
+    from dsocr._lib import check, lib
+    for fused, (T, Is, (E, topk), H) in [(f, g) for f in "01" for g in _MOE_GRID]:
+        monkeypatch.setenv("DSOCR_ROUTE_FUSED", fused)
+        k = C.c_char_p()
+        check(lib().dsocr_k_moe_route_kind(T, H, E, topk, 896, Is, 1, C.byref(k)))
+        assert k.value.decode() == _MOE_ROUTE_RECORDED[(fused, (E, topk), H)][T - 1], (fused, T, Is, E, topk, H)
 
 
 # (M, N, K, ldw, wdtype, norm, xn_out, swizzle) -> (kind, token rows per launch), worked out by hand from
