@@ -872,6 +872,66 @@ dsocr_status dsocr_k_decode_attention(int B, int heads, int kv_heads, int hd, in
         if (herr) throw std::runtime_error("EINTERNAL: decode attention merge timed out");
     });
 }
+dsocr_status dsocr_k_prefill_attention(int B, int heads, int kv_heads, int hd, int rope_dim, int use_mla, int cap,
+                                       float scale, const int* lens, float* qkv, const float* cos, const float* sin,
+                                       float* kc, float* vc, float* o, int use_part) {
+    return guarded([&] {
+        if (hd != 32 && hd != 64 && hd != 128) throw std::runtime_error("EINVAL: head_dim must be 32, 64 or 128");
+        if (heads <= 0 || kv_heads <= 0 || heads % kv_heads || rope_dim < 0 || rope_dim > hd || rope_dim % 2)
+            throw std::runtime_error("EINVAL: bad head / rope configuration");
+        if (B <= 0 || !lens || !qkv || !cos || !sin || !kc || !vc || !o) throw std::runtime_error("EINVAL: NULL argument");
+        for (int b = 0; b < B; ++b)
+            if (lens[b] < 1) throw std::runtime_error("EINVAL: every sequence needs at least one row");
+        // the plan and the views of Engine::forward_rows / layer_forward_prefill, on a cache of `cap` slots per head
+        const long QKVN = (long)(heads + 2 * kv_heads) * hd, H = (long)heads * hd;
+        const long head_stride = (long)cap * hd, page_stride = (long)kv_heads * head_stride;
+        const dsocr::PrefillPlan plan = dsocr::prefill_row_plan(std::vector<int>(lens, lens + B), QKVN, H, page_stride);
+        if (cap < plan.max_len) throw std::runtime_error("EINVAL: cap is below the longest sequence");
+        std::vector<void*> bufs;
+        auto alloc = [&](size_t b) {
+            void* p = nullptr;
+            check_hip(hipMalloc(&p, b ? b : 16), "hipMalloc");
+            bufs.push_back(p);
+            return p;
+        };
+        auto upload = [&](const void* src, size_t b) {
+            void* p = alloc(b);
+            check_hip(hipMemcpy(p, src, b, hipMemcpyHostToDevice), "h2d");
+            return p;
+        };
+        try {
+            dsocr::RopeKvArgs r;
+            r.qkv = qkv; r.ld = QKVN; r.rows = (int)plan.T;
+            r.row_page = (const int*)upload(plan.row_page.data(), sizeof(int) * plan.row_page.size());
+            r.row_pos = (const int*)upload(plan.row_pos.data(), sizeof(int) * plan.row_pos.size());
+            r.heads = heads; r.kv_heads = kv_heads; r.hd = hd; r.rope_dim = rope_dim; r.use_mla = use_mla ? 1 : 0;
+            r.cos = cos; r.sin = sin; r.kc = kc; r.vc = vc; r.page_stride = page_stride; r.head_stride = head_stride;
+            dsocr::launch_rope_kv(r, nullptr);
+            const long* q_off = (const long*)upload(plan.q_off.data(), sizeof(long) * B);
+            const long* kv_off = (const long*)upload(plan.kv_off.data(), sizeof(long) * B);
+            const long* o_off = (const long*)upload(plan.o_off.data(), sizeof(long) * B);
+            dsocr::AttnArgs a;
+            a.q = {qkv, QKVN, hd, q_off};
+            a.k = {kc, hd, head_stride, kv_off};
+            a.v = {vc, hd, head_stride, kv_off};
+            a.o = o; a.o_row_stride = H; a.o_head_stride = hd; a.o_seq_off = o_off;
+            a.n_seq = B; a.L = plan.max_len; a.seq_len = (const int*)upload(lens, sizeof(int) * B);
+            a.heads = heads; a.kv_heads = kv_heads; a.hd = hd; a.scale = scale; a.causal = 1;
+            if (use_part) {  // a workspace no launch has written: NaN wherever the merge reads past its own pieces
+                a.part_floats = dsocr::attention_causal_part_floats(B, heads, plan.max_len, hd);
+                a.part = (float*)alloc(sizeof(float) * a.part_floats);
+                check_hip(hipMemset(a.part, 0xFF, sizeof(float) * a.part_floats), "hipMemset");
+            }
+            dsocr::launch_attention(a, nullptr);
+            check_hip(hipGetLastError(), "prefill attention launch");
+            check_hip(hipDeviceSynchronize(), "prefill attention");
+        } catch (...) {
+            for (void* p : bufs) (void)hipFree(p);
+            throw;
+        }
+        for (void* p : bufs) (void)hipFree(p);
+    });
+}
 dsocr_status dsocr_k_qkv_attention(int fused, int steps, int H, int heads, int hd, int max_len, float scale,
                                    float eps, const float* x, const float* norm_w, const void* Wqkv, int wdtype,
                                    const float* cos, const float* sin, float* kc, float* vc, const int* kv_pos,

@@ -1937,12 +1937,11 @@ void Engine::forward_rows(GenState& g, const std::vector<int>& lens) {
     const LangConfig& L = cfg_.lang;
     const int B = g.B, H = L.hidden, QKVN = layers_[0].qkv.N;
     hipStream_t st = stream_;
-    long Tn = 0;
-    int maxl = 0;
-    for (int b = 0; b < B; ++b) { Tn += lens[b]; maxl = std::max(maxl, lens[b]); }
+    const PrefillPlan plan = prefill_row_plan(lens, QKVN, H, page_stride_);
+    const long Tn = plan.T;
+    const int maxl = plan.max_len;
     prefill_lens_ = lens;
-    std::vector<int> kind(Tn), index(Tn), row_page(Tn), row_pos(Tn);
-    std::vector<long> q_off(B), kv_off(B), o_off(B);
+    std::vector<int> kind(Tn), index(Tn);
     long r0 = 0;
     for (int b = 0; b < B; ++b) {
         const GenRequest& rq = g.reqs[b];
@@ -1958,12 +1957,7 @@ void Engine::forward_rows(GenState& g, const std::vector<int>& lens) {
                 kind[r] = ROW_TOKEN;
                 index[r] = i < plen ? rq.ids[i] : g.extra[b][i - plen];
             }
-            row_page[r] = b;
-            row_pos[r] = i;
         }
-        q_off[b] = r0 * QKVN;
-        kv_off[b] = (long)b * page_stride_;
-        o_off[b] = r0 * H;
         r0 += lens[b];
     }
     float* X = wsf("d_x", (size_t)Tn * H);
@@ -1971,11 +1965,11 @@ void Engine::forward_rows(GenState& g, const std::vector<int>& lens) {
     int* di = upload("g_index", index);
     float* hr = g.host_rows.empty() ? nullptr : upload("g_hostrows", g.host_rows);
     launch_assemble_rows(dk, di, (int)Tn, H, embed_, embed_dt_, hr, g.vis_rows, newline_, separator_, X, H, st);
-    int* d_row_page = upload("g_rowpage", row_page);
-    int* d_row_pos = upload("g_rowpos", row_pos);
-    long* d_q_off = upload("g_qoff", q_off);
-    long* d_kv_off = upload("g_kvoff", kv_off);
-    long* d_o_off = upload("g_ooff", o_off);
+    int* d_row_page = upload("g_rowpage", plan.row_page);
+    int* d_row_pos = upload("g_rowpos", plan.row_pos);
+    long* d_q_off = upload("g_qoff", plan.q_off);
+    long* d_kv_off = upload("g_kvoff", plan.kv_off);
+    long* d_o_off = upload("g_ooff", plan.o_off);
     int* d_plen = upload("g_plen", lens);
     for (int l = 0; l < L.layers; ++l)
         layer_forward_prefill(l, (int)Tn, B, d_row_page, d_row_pos, d_q_off, d_kv_off, d_o_off, d_plen, maxl, g.Lmax);

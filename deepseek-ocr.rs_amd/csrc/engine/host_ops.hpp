@@ -7,6 +7,7 @@
 //   bicubic_resize_aa     vision/sam.rs:1000-1123 (pos-embed tables, f32)
 //   rel_pos_resize        vision/sam.rs:1194-1232 (linear, f32)
 #pragma once
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <set>
@@ -347,6 +348,40 @@ inline size_t image_placeholder_count(int base, int image_size, bool crop_mode, 
         n += (size_t)nq * (nq + 1) + 1;
     }
     return n;
+}
+
+// ---------------------------------------------------------------- prefill row plan
+// The decoder prefill runs a ragged batch: sequence b's lens[b] rows packed one after another (T rows in all),
+// row r of sequence b at position i going to page b, slot i of the KV cache.  Per row: its page and position
+// (rope_kv); per sequence: where its rows start in the q|k|v buffer (row width qkv_ld), in the attention output
+// (row width H) and in the cache (page_stride floats per page).  max_len is the attention grid's length.
+struct PrefillPlan {
+    std::vector<int> row_page, row_pos;
+    std::vector<long> q_off, kv_off, o_off;
+    long T = 0;
+    int max_len = 0;
+};
+inline PrefillPlan prefill_row_plan(const std::vector<int>& lens, long qkv_ld, long H, long page_stride) {
+    PrefillPlan p;
+    const int B = (int)lens.size();
+    for (int b = 0; b < B; ++b) { p.T += lens[b]; p.max_len = std::max(p.max_len, lens[b]); }
+    p.row_page.resize(p.T);
+    p.row_pos.resize(p.T);
+    p.q_off.resize(B);
+    p.kv_off.resize(B);
+    p.o_off.resize(B);
+    long r0 = 0;
+    for (int b = 0; b < B; ++b) {
+        for (int i = 0; i < lens[b]; ++i) {
+            p.row_page[r0 + i] = b;
+            p.row_pos[r0 + i] = i;
+        }
+        p.q_off[b] = r0 * qkv_ld;
+        p.kv_off[b] = (long)b * page_stride;
+        p.o_off[b] = r0 * H;
+        r0 += lens[b];
+    }
+    return p;
 }
 
 // ---------------------------------------------------------------- f32 table resizes

@@ -14,6 +14,7 @@
 //    the decode step fuses both into dec_attn_kernel, decode_attn.hip).
 #include <algorithm>
 #include <cstdlib>
+#include <stdexcept>
 
 #include "dev_common.hpp"
 #include "kernels.hpp"
@@ -875,6 +876,13 @@ __global__ __launch_bounds__(256) void rope_kv_kernel(RopeKvArgs a) {
 }
 
 void launch_rope_kv(const RopeKvArgs& a, hipStream_t s) {
+    // the kernel keeps a row's rotated q | k columns in 32 registers per thread of its 256 (MAXPER)
+    if (a.heads <= 0 || a.kv_heads <= 0 || a.hd <= 0 || a.heads % a.kv_heads)
+        throw std::runtime_error("EINVAL: rope_kv: heads must be a positive multiple of kv_heads");
+    if ((long)(a.heads + a.kv_heads) * a.hd > 8192)
+        throw std::runtime_error("EINVAL: rope_kv: (heads + kv_heads) * head_dim must be <= 8192");
+    if (a.rope_dim < 0 || a.rope_dim % 2 || a.rope_dim > a.hd)
+        throw std::runtime_error("EINVAL: rope_kv: rope_dim must be even and <= head_dim");
     if (a.rows == 0) return;
     hipLaunchKernelGGL(rope_kv_kernel, dim3(a.rows), dim3(256), 0, s, a);
 }

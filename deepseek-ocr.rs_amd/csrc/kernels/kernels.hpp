@@ -173,6 +173,7 @@ struct RopeKvArgs {
     const float* cos = nullptr; const float* sin = nullptr;       // [Lmax][rope_dim]
     float* kc = nullptr; float* vc = nullptr; long page_stride = 0, head_stride = 0;
 };
+// throws EINVAL unless heads % kv_heads == 0, (heads + kv_heads) * hd <= 8192 and rope_dim is even and <= hd
 void launch_rope_kv(const RopeKvArgs& a, hipStream_t s);
 
 // ------------------------------------------------------------------ OCR2 encoder attention (attention_prefix.hip)

@@ -95,6 +95,7 @@ EXPORTS = [
     "dsocr_k_gemm_bf16", "dsocr_k_dots_op",
     "dsocr_k_gemv_ex", "dsocr_k_gemv_kind", "dsocr_k_mm_swizzle", "dsocr_k_silu_mul",
     "dsocr_config_variant", "dsocr_engine_variant", "dsocr_prepare_page_variant", "dsocr_prepare_page_device_variant", "dsocr_k_attention_prefix",
+    "dsocr_k_prefill_attention",
 ]
 
 # model variants behind the deepseek engine (dsocr_engine_variant)
@@ -184,6 +185,8 @@ def lib():
     L.dsocr_k_dsq_dequant.argtypes = [i32, vp, sz, sz, sz, vp]
     L.dsocr_k_attention.argtypes = [i32, i32, i32, i32, f32, i32, vp, vp, vp, vp, vp, vp, i32, i32]
     L.dsocr_k_decode_attention.argtypes = [i32, i32, i32, i32, i32, i32, f32, vp, vp, vp, vp, vp, vp, vp, i32]
+    L.dsocr_k_prefill_attention.argtypes = [i32, i32, i32, i32, i32, i32, i32, f32, C.POINTER(i32), vp, vp, vp, vp, vp, vp,
+                                            i32]
     L.dsocr_k_qkv_attention.argtypes = [i32, i32, i32, i32, i32, i32, f32, f32, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp,
                                         vp, C.POINTER(i32)]
     L.dsocr_k_poll_wait_fits.argtypes = [C.c_long, i32, i32]

@@ -395,6 +395,19 @@ dsocr_status dsocr_k_dots_op(int op, long rows, int cols, int aux, long ld, cons
 dsocr_status dsocr_k_decode_attention(int B, int heads, int kv_heads, int hd, int rope_dim, int max_len, float scale,
                                       const float* qkv, const float* cos, const float* sin, float* kc, float* vc,
                                       const int* kv_pos, float* o, int prerot);
+/* The decoder prefill between the q|k|v linear and the o linear, as the engine launches it on a ragged batch
+ * (block.rs:608-789, rope block.rs:1403-1471): B sequences of lens[b] rows (host array) packed one after another,
+ * T = sum lens rows in all.  qkv [T][(heads + 2 kv_heads) * hd]: the q columns are rotated in place at the row's
+ * position in its sequence (cos / sin tables [>= max lens][rope_dim]; use_mla: the even/odd regroup first), the
+ * rotated k and the v columns appended to the f32 caches kc / vc [B][kv_heads][cap][hd] at (b, head, position);
+ * then o [T][heads * hd] = causal softmax(scale * q.K^T) . V per sequence, k / v read from the cache.
+ * use_part != 0: the key-piece form (one block per 128-query block and 128-key piece, then the piece combine; the
+ * workspace enters filled with NaN); 0: one block per query block.  hd 32 runs one kernel either way.
+ * DSOCR_EINVAL: hd not 32 / 64 / 128, heads % kv_heads != 0, rope_dim odd or > hd, cap < max lens, a sequence
+ * without rows, or (heads + kv_heads) * hd > 8192.  lens is a host pointer; the rest are device pointers. */
+dsocr_status dsocr_k_prefill_attention(int B, int heads, int kv_heads, int hd, int rope_dim, int use_mla, int cap,
+                                       float scale, const int* lens, float* qkv, const float* cos, const float* sin,
+                                       float* kc, float* vc, float* o, int use_part);
 /* One page's decode attention sub-layer as the engine runs it (block.rs:446-804 at seq_len 1): RMSNorm +
  * q/k/v projection (Wqkv [3H][H], 16-bit) with RoPE in the epilogue, K/V append at kv_pos[s], softmax
  * attention over positions 0..kv_pos[s], for `steps` launches back to back (x [steps][H], kv_pos [steps],
