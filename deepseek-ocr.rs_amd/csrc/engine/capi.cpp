@@ -404,6 +404,109 @@ dsocr_status dsocr_generate_trace(dsocr_engine* e, size_t n, const dsocr_request
     });
 }
 
+// ---- decode sessions
+dsocr_status dsocr_session_open(dsocr_engine* e, size_t slots, size_t max_context, const dsocr_decode_params* params) {
+    return guarded([&] {
+        if (!e) throw std::runtime_error("EINVAL: NULL argument");
+        if (slots > 8 || max_context > (size_t)INT32_MAX / 2) throw std::runtime_error("EINVAL: a session has 1..8 slots");
+        e->impl->session_open((int)slots, (int)max_context, to_params(params));
+    });
+}
+
+dsocr_status dsocr_session_admit(dsocr_engine* e, const dsocr_request* req, size_t max_new_tokens, int has_seed,
+                                 uint64_t seed, int* slot) {
+    return guarded([&] {
+        if (!e || !req) throw std::runtime_error("EINVAL: NULL argument");
+        const int s = e->impl->session_admit(to_request(*req), max_new_tokens, has_seed != 0, seed);
+        if (slot) *slot = s;
+    });
+}
+
+namespace {
+void session_report(dsocr_engine* e, bool step, size_t k, dsocr_slot_status* status, size_t cap_slots, size_t* n_slots,
+                    int64_t* tokens, size_t cap_tokens, size_t* n_tokens) {
+    if (!e || !status || !n_slots || !tokens || !n_tokens) throw std::runtime_error("EINVAL: NULL argument");
+    dsocr::Engine::SessionInfo si;
+    if (!e->impl->session_info(&si)) throw std::runtime_error("EINVAL: no decode session is open on this engine");
+    // checked before the poll: a poll hands its tokens out once
+    if (cap_slots < (size_t)si.slots || cap_tokens < (size_t)si.slots * si.out_cap)
+        throw std::runtime_error("EINVAL: status needs `slots` entries and tokens slots * out_cap");
+    if (step && (k == 0 || k > (size_t)INT32_MAX)) throw std::runtime_error("EINVAL: a burst has at least one step");
+    const auto st = step ? e->impl->session_step((int)k) : e->impl->session_poll();
+    size_t nt = 0;
+    for (size_t i = 0; i < st.size(); ++i) {
+        status[i].slot = st[i].slot;
+        status[i].done = st[i].done;
+        status[i].out_len = st[i].out_len;
+        status[i].n_new = (int32_t)st[i].fresh.size();
+        for (int64_t t : st[i].fresh) tokens[nt++] = t;
+    }
+    *n_slots = st.size();
+    *n_tokens = nt;
+}
+}  // namespace
+
+dsocr_status dsocr_session_step(dsocr_engine* e, size_t k, dsocr_slot_status* status, size_t cap_slots, size_t* n_slots,
+                                int64_t* tokens, size_t cap_tokens, size_t* n_tokens) {
+    return guarded([&] { session_report(e, true, k, status, cap_slots, n_slots, tokens, cap_tokens, n_tokens); });
+}
+
+dsocr_status dsocr_session_poll(dsocr_engine* e, dsocr_slot_status* status, size_t cap_slots, size_t* n_slots,
+                                int64_t* tokens, size_t cap_tokens, size_t* n_tokens) {
+    return guarded([&] { session_report(e, false, 0, status, cap_slots, n_slots, tokens, cap_tokens, n_tokens); });
+}
+
+dsocr_status dsocr_session_retire(dsocr_engine* e, int slot, int64_t* out_ids, size_t cap, size_t* n_out,
+                                  int* moved_from) {
+    return guarded([&] {
+        if (!e || !out_ids || !n_out) throw std::runtime_error("EINVAL: NULL argument");
+        dsocr::Engine::SessionInfo si;
+        if (!e->impl->session_info(&si)) throw std::runtime_error("EINVAL: no decode session is open on this engine");
+        if (cap < (size_t)si.out_cap) throw std::runtime_error("EINVAL: output capacity too small (the session's out_cap)");
+        const auto ids = e->impl->session_retire(slot, moved_from);
+        std::memcpy(out_ids, ids.data(), ids.size() * sizeof(int64_t));
+        *n_out = ids.size();
+    });
+}
+
+dsocr_status dsocr_session_close(dsocr_engine* e) {
+    return guarded([&] {
+        if (!e) throw std::runtime_error("EINVAL: NULL argument");
+        e->impl->session_close();
+    });
+}
+
+dsocr_status dsocr_session_info(const dsocr_engine* e, dsocr_session_desc* out) {
+    return guarded([&] {
+        if (!e || !out) throw std::runtime_error("EINVAL: NULL argument");
+        dsocr::Engine::SessionInfo si;
+        if (!e->impl->session_info(&si)) throw std::runtime_error("EINVAL: no decode session is open on this engine");
+        out->slots = (size_t)si.slots; out->active = (size_t)si.active; out->max_context = (size_t)si.max_context;
+        out->out_cap = (size_t)si.out_cap; out->kv_cap = (size_t)si.kv_cap; out->burst_cap = (size_t)si.burst_cap;
+        out->steps = si.steps;
+    });
+}
+
+dsocr_status dsocr_k_session_slot_move(int layers, int slots, int kv_heads, int cap, int hd, float* kc, float* vc,
+                                       int* kv_len, int* kv_pos, int* ctx, long long ctx_cap, int* ctx_len, int* out,
+                                       long long out_cap, int* out_len, int* done, int* tok, uint32_t* rng,
+                                       int rng_words, int* ban, long long ban_ld, float* x, int H, int src, int dst) {
+    return guarded([&] {
+        if (ctx_cap < 0 || out_cap < 0 || ban_ld < 0 || rng_words < 0 || H < 0)
+            throw std::runtime_error("EINVAL: negative row length");
+        dsocr::SlotMoveArgs m;
+        m.kc = kc; m.vc = vc; m.layers = layers; m.slots = slots; m.kv_heads = kv_heads; m.cap_rows = cap; m.hd = hd;
+        m.head_stride = (long)cap * hd; m.page_stride = (long)kv_heads * m.head_stride;
+        m.layer_stride = (long)slots * m.page_stride;
+        m.src = src; m.dst = dst; m.rows_bound = cap;
+        m.kv_len = kv_len; m.kv_pos = kv_pos; m.ctx = ctx; m.ctx_cap = ctx_cap; m.ctx_len = ctx_len;
+        m.out = out; m.out_cap = out_cap; m.out_len = out_len; m.done = done; m.tok = tok;
+        m.rng = rng; m.rng_words = rng_words; m.ban = ban; m.ban_ld = ban_ld; m.x = x; m.H = H;
+        dsocr::launch_session_slot_move(m, nullptr);
+        check_hip(hipDeviceSynchronize(), "session_slot_move");
+    });
+}
+
 dsocr_status dsocr_last_timings(const dsocr_engine* e, dsocr_timings* t) {
     return guarded([&] {
         if (!e || !t) throw std::runtime_error("EINVAL: NULL argument");

@@ -162,6 +162,30 @@ double ms_between(hipEvent_t a, hipEvent_t b) {
 
 }  // namespace
 
+// One decode session (Engine::session_*, after generate below): the state that outlives a call.  The device rows
+// live in the engine's named workspaces, reserved once at session_open for `S` slots; the graphs hold their addresses.
+struct Engine::Session {
+    static constexpr int kBurstCap = 8;  // k_max: the most steps one session_step replays
+    int S = 0, n = 0, max_context = 0, Lcap = 0;
+    long ctx_cap = 0, out_cap = 0, ban_ld = 0;
+    GenParams p;
+    bool screened = false;  // the screened head at every n (else the exact head at every n: one ban-list contract)
+    size_t part_floats = 0, qkv_floats = 0;
+    float *sx = nullptr, *logits = nullptr, *part = nullptr, *qkv = nullptr;
+    int *ctx = nullptr, *ctx_len = nullptr, *kvpos = nullptr, *kvlen = nullptr, *done = nullptr, *outlen = nullptr,
+        *out = nullptr, *tok = nullptr, *ban = nullptr, *stage = nullptr, *err = nullptr;
+    uint32_t* rng = nullptr;
+    struct Slot {
+        size_t max_new = 0;
+        int kv_pos = 0;    // the device kv_pos of the slot: prompt + steps replayed since its admission
+        int reported = 0;  // tokens the polls have handed out
+    };
+    std::vector<Slot> slot;
+    HipGraphExec graph[9];  // the step for n active pages, captured on first use
+    PinnedBuffer<int> pin;  // poll: [done | output length] x S, then the decode error flag
+    size_t steps = 0;
+};
+
 // ============================================================================ lifecycle
 void* Engine::dev_alloc(size_t bytes) {
     void* p = nullptr;
@@ -177,6 +201,7 @@ void* Engine::ws(const std::string& name0, size_t bytes) {
     auto it = ws_.find(name);
     if (it != ws_.end() && it->second.second >= bytes) return it->second.first;
     if (capturing_) throw std::runtime_error("EINTERNAL: workspace growth during graph capture: " + name);
+    if (ws_frozen_.count(name)) throw std::runtime_error("EINTERNAL: workspace growth inside a decode session: " + name);
     if (it != ws_.end()) {
         HIP_CHECK(hipDeviceSynchronize());  // both vision streams may still read it
         HIP_CHECK(hipFree(it->second.first));
@@ -1113,9 +1138,9 @@ void Engine::layer_forward_prefill(int l, int T, int B, const int* row_page, con
     float* XN = wsf("d_xn", (size_t)T * H);
     float* QKV = wsf("d_qkv", (size_t)T * QKVN);
     float* CTX = wsf("d_ctx", (size_t)T * H);
-    const long layer_kv = (long)B * page_stride_;
-    float* kc = kc_ + (long)l * layer_kv;
-    float* vc = vc_ + (long)l * layer_kv;
+    // (a session prefills one page into its own slot of the session cache: kv_page0_)
+    float* kc = kc_ + (long)l * layer_kv(B) + (long)kv_page0_ * page_stride_;
+    float* vc = vc_ + (long)l * layer_kv(B) + (long)kv_page0_ * page_stride_;
 
     launch_rmsnorm(X, H, XN, H, T, H, d.in_norm.w, L.rms_eps, st);
     linear(XN, T, H, d.qkv, QKV, QKVN);
@@ -1254,7 +1279,7 @@ MoeDecodeArgs Engine::moe_args(int l, int B, float* X) {
 DecAttn2Args Engine::attn_args(int l, int B, int Lmax) {
     const LangConfig& L = cfg_.lang;
     const int hd = L.head_dim, QKVN = layers_[l].qkv.N;
-    const long layer_kv = (long)B * page_stride_;
+    const long layer_kv = this->layer_kv(B);
     DecAttn2Args da;
     da.qkv = wsf("s_qkv", (size_t)B * QKVN); da.ld = QKVN; da.kv_pos = wsi("s_kvpos", B); da.B = B;
     da.heads = L.heads; da.kv_heads = L.kv_heads; da.hd = hd; da.rope_dim = L.rope_dim; da.use_mla = L.use_mla;
@@ -1699,6 +1724,7 @@ struct Engine::GenState {
 
 std::vector<std::vector<int64_t>> Engine::generate(const std::vector<GenRequest>& reqs, const GenParams& p, TokenCb cb,
                                                    void* user) {
+    if (sess_) throw std::runtime_error("EINVAL: a decode session is open on this engine (close it before generate)");
     timings_ = Timings();
     timings_.pages = reqs.size();
     if (reqs.empty() || p.max_new == 0) return std::vector<std::vector<int64_t>>(reqs.size());
@@ -2299,6 +2325,366 @@ std::vector<std::vector<int64_t>> Engine::collect_outputs(GenState& g) {
     return out;
 }
 
+// ============================================================================ decode sessions
+// A session keeps the decode state of up to S pages alive across calls.  Its step is decode_step + decode_head,
+// unchanged, captured once per active count n; admission runs generate's own phases (embed_pages,
+// plan_image_rows, forward_rows, the first selection) on one page, pointed at slot n of the session's rows.
+Engine::Session& Engine::open_session() {
+    if (!sess_) throw std::runtime_error("EINVAL: no decode session is open on this engine");
+    return *sess_;
+}
+
+void Engine::session_open(int S, int max_context, const GenParams& p) {
+    if (sess_) throw std::runtime_error("EINVAL: a decode session is already open on this engine");
+    if (S < 1 || S > 8) throw std::runtime_error("EINVAL: a session has 1..8 slots");
+    if (!p.use_cache || p.trace) throw std::runtime_error("EINVAL: a session decodes with the K/V cache and without a logits trace");
+    if (p.max_new == 0 || max_context < 3 || (size_t)max_context < p.max_new + 2)
+        throw std::runtime_error("EINVAL: max_context must hold a prompt row, max_new_tokens and one more row");
+    if (span_mode_ || persist_stamp_mode_) throw std::runtime_error("EINVAL: launch spans and persist stamps are off inside a session");
+    const LangConfig& L = cfg_.lang;
+    if (L.heads % L.kv_heads) throw std::runtime_error("EINVAL: num_attention_heads must be a multiple of num_key_value_heads");
+    if (L.head_dim % 4) throw std::runtime_error("EINVAL: a session needs head_dim % 4 == 0");
+    const int H = L.hidden, V = L.vocab, QKVN = layers_[0].qkv.N;
+    hipStream_t st = stream_;
+    auto sp = std::make_unique<Session>();
+    Session& s = *sp;
+    s.S = S; s.max_context = max_context; s.p = p;
+    // Capacity invariant.  The selection kernels advance kv_pos of every row on every step, done or not, so a
+    // finished page that waits for the end of its burst keeps appending K/V rows.  A page is admitted only with
+    // prompt + max_new + 1 <= max_context and produces its last token at kv_pos <= prompt + max_new - 1; it is
+    // retired at the next burst boundary, at most kBurstCap steps later.  Every slot therefore has
+    // max_context + kBurstCap rows, and session_step refuses (on the host, before any launch) a burst that would
+    // take a slot's kv_pos past them.  The context row has the same length; the output row stops on the device
+    // at out_cap (dec_sample: out_len < out_cap, n < ctx_cap).
+    s.Lcap = max_context + Session::kBurstCap;
+    s.ctx_cap = s.Lcap;
+    s.out_cap = (long)p.max_new;
+    s.ban_ld = s.ctx_cap + 1;
+    s.slot.resize(S);
+    s.pin = PinnedBuffer<int>(2 * S + 1);
+    ensure_small(64);
+    ensure_rope(s.Lcap + 1);
+    const long head_stride0 = head_stride_, page_stride0 = page_stride_;
+    try {
+        head_stride_ = (long)s.Lcap * L.head_dim;
+        page_stride_ = (long)L.kv_heads * head_stride_;
+        kv_pages_ = S;
+        kv_page0_ = 0;
+        persist_active_ = false;  // (DSOCR_PERSIST is a generate-only switch)
+        const size_t kv_floats = (size_t)L.layers * S * page_stride_;
+        kc_ = wsf("kv_k", kv_floats);
+        vc_ = wsf("kv_v", kv_floats);
+        HIP_CHECK(hipMemsetAsync(kc_, 0, kv_floats * 4, st));
+        HIP_CHECK(hipMemsetAsync(vc_, 0, kv_floats * 4, st));
+        // the decode kernels' tickets zeroed and their polled rows sentinel-filled, as reset_decode_state
+        HIP_CHECK(hipMemsetAsync(wsi("s_attn_cnt", (size_t)S * L.heads), 0, sizeof(int) * S * L.heads, st));
+        HIP_CHECK(hipMemsetAsync(wsi("s_route_cnt", 16), 0, sizeof(int) * 16, st));
+        HIP_CHECK(hipMemsetAsync(wsi("s_dntick", (size_t)H / 64 + 1), 0, sizeof(int) * (H / 64 + 1), st));
+        HIP_CHECK(hipMemsetAsync(wsi("s_dtick", dec_mm_splitk_ticks(H)), 0, sizeof(int) * dec_mm_splitk_ticks(H), st));
+        s.err = wsi("s_err", 4);
+        HIP_CHECK(hipMemsetAsync(s.err, 0, sizeof(int) * 4, st));
+        for (int n = 1; n <= S; ++n)
+            s.part_floats = std::max(s.part_floats, dec_attn_workspace(n, L.heads, L.head_dim, s.Lcap) / 4 + 16);
+        s.part = wsf("s_part", s.part_floats);
+        s.qkv_floats = (size_t)S * QKVN;
+        s.qkv = wsf("s_qkv", s.qkv_floats);
+        wsf("p_qkv_skip", s.qkv_floats);
+        // the per-slot rows, zeroed: the dry steps below read kv_pos 0 and a zero input row
+        s.sx = wsf("s_x", (size_t)S * H);
+        HIP_CHECK(hipMemsetAsync(s.sx, 0, sizeof(float) * S * H, st));
+        wsf("s_xn", (size_t)S * H);
+        s.logits = wsf("s_logits", (size_t)S * V);
+        auto zeroed = [&](const char* name, size_t n) {
+            int* d = wsi(name, n);
+            HIP_CHECK(hipMemsetAsync(d, 0, sizeof(int) * n, st));
+            return d;
+        };
+        s.ctx = zeroed("s_ctx_ids", (size_t)S * s.ctx_cap);
+        s.ctx_len = zeroed("s_ctx_len", S);
+        s.kvpos = zeroed("s_kvpos", S);
+        s.kvlen = zeroed("s_kvlen", S);
+        s.done = zeroed("s_done", S);
+        s.outlen = zeroed("s_outlen", S);
+        s.out = zeroed("s_out", (size_t)S * s.out_cap);
+        s.tok = zeroed("s_tok", S);
+        const size_t red = dec_sample_blocks(V);
+        wsf("s_redv", (size_t)S * red);
+        wsi("s_redi", (size_t)S * red);
+        if (p.do_sample) {
+            wsi("s_stkey", (size_t)S * 2 * V);
+            wsi("s_stidx", (size_t)S * 2 * V);
+            wsf("s_stw", (size_t)S * 2 * V);
+            s.rng = reinterpret_cast<uint32_t*>(zeroed("s_rng", (size_t)S * RNG_WORDS));
+        }
+        s.stage = wsi("ss_stage", (size_t)SS_HEAD + RNG_WORDS + s.ctx_cap);
+        ensure_mm_weights(S);
+        s.screened = !p.do_sample;
+        for (int n = 1; n <= S; ++n) s.screened = s.screened && screen_applies(n, p.rep_penalty);
+        if (s.screened) {
+            s.ban = zeroed("s_ban", (size_t)S * s.ban_ld);
+            for (int n = 1; n <= S; ++n) reserve_head_ws(n);
+        }
+        // every workspace the decode step asks for by name, at every n: a dry step per n allocates them (it
+        // appends K/V row 0 of the empty slots, which an admission's prefill rewrites)
+        if (s.screened && getenv("DSOCR_SCREEN_STATS")) zeroed("s_scrstats", 32);
+        for (int n = 1; n <= S; ++n) {
+            session_sentinels(s);
+            decode_step(n, s.Lcap);
+        }
+        HIP_CHECK(hipMemsetAsync(s.sx, 0, sizeof(float) * S * H, st));
+        session_sentinels(s);
+        HIP_CHECK(hipStreamSynchronize(st));
+        // from here on no admission may move one of them: the captured graphs hold their addresses
+        for (const auto& kv : ws_)
+            if (kv.first.rfind("s_", 0) == 0 || kv.first.rfind("kv_", 0) == 0 || kv.first.rfind("p_", 0) == 0 ||
+                kv.first.rfind("ss_", 0) == 0)
+                ws_frozen_.insert(kv.first);
+    } catch (...) {
+        kv_pages_ = 0;
+        ws_frozen_.clear();
+        head_stride_ = head_stride0;
+        page_stride_ = page_stride0;
+        throw;
+    }
+    sess_ = std::move(sp);
+}
+
+// the fused one-page launch takes q / k / v by polling s_qkv, and the attention merge polls its records: both
+// enter a launch sentinel-filled.  A step at another n leaves them in that n's layout, so they are refilled
+// whenever n changes (admit, retire)
+void Engine::session_sentinels(const Session& s) {
+    dec_attn_part_init(s.part, s.part_floats * 4, stream_);
+    dec_qkv_sentinel_init(s.qkv, s.qkv_floats, stream_);
+}
+
+// selection arguments for the B slots from slot0 on (the step: slot0 = 0, B = n; an admission: its slot, B = 1)
+void Engine::session_sample_args(const Session& s, int B, int slot0, DecSampleArgs& sa, SampleArgs& pen) {
+    const LangConfig& L = cfg_.lang;
+    const int V = L.vocab, H = L.hidden;
+    const GenParams& p = s.p;
+    pen = SampleArgs();
+    pen.logits = s.logits + (size_t)slot0 * V; pen.B = B; pen.V = V; pen.ld = V;
+    pen.ctx = s.ctx + (size_t)slot0 * s.ctx_cap; pen.ctx_cap = s.ctx_cap; pen.ctx_len = s.ctx_len + slot0;
+    pen.rep_penalty = p.rep_penalty;
+    sa = DecSampleArgs();
+    sa.logits = pen.logits; sa.B = B; sa.V = V; sa.ld = V;
+    sa.ctx = s.ctx + (size_t)slot0 * s.ctx_cap; sa.ctx_cap = s.ctx_cap; sa.ctx_len = s.ctx_len + slot0; sa.ngram = p.ngram;
+    sa.red_blocks = (int)dec_sample_blocks(V);
+    sa.red_val = wsf("s_redv", (size_t)s.S * sa.red_blocks) + (size_t)slot0 * sa.red_blocks;
+    sa.red_idx = wsi("s_redi", (size_t)s.S * sa.red_blocks) + (size_t)slot0 * sa.red_blocks;
+    sa.out_tok = s.tok + slot0; sa.out_ids = s.out + (size_t)slot0 * s.out_cap; sa.out_len = s.outlen + slot0;
+    sa.out_cap = s.out_cap; sa.done = s.done + slot0;
+    sa.eos = p.ignore_eos ? -1 : (int)p.eos;
+    sa.table = embed_; sa.table_dt = embed_dt_; sa.H = H; sa.x_next = s.sx + (size_t)slot0 * H;
+    sa.kv_pos = s.kvpos + slot0; sa.kv_len = s.kvlen + slot0;
+    if (p.do_sample) {
+        sa.do_sample = 1; sa.temperature = p.temperature; sa.top_p = p.top_p; sa.top_k = p.top_k;
+        sa.st_ld = V;
+        sa.st_key = reinterpret_cast<uint32_t*>(wsi("s_stkey", (size_t)s.S * 2 * V)) + (size_t)slot0 * 2 * V;
+        sa.st_idx = wsi("s_stidx", (size_t)s.S * 2 * V) + (size_t)slot0 * 2 * V;
+        sa.st_w = reinterpret_cast<double*>(wsf("s_stw", (size_t)s.S * 2 * V)) + (size_t)slot0 * V;
+        sa.rng = s.rng + (size_t)slot0 * RNG_WORDS;
+    }
+    if (s.screened) { sa.ban_ld = s.ban_ld; sa.ban_out = s.ban + (size_t)slot0 * s.ban_ld; }
+}
+
+int Engine::session_admit(const GenRequest& rq, size_t max_new, bool seed_set, uint64_t seed) {
+    Session& s = open_session();
+    const LangConfig& L = cfg_.lang;
+    const int H = L.hidden, V = L.vocab;
+    hipStream_t st = stream_;
+    // every check first: nothing below may fail on the request itself once device state changes
+    if (s.n >= s.S) throw std::runtime_error("EINVAL: every session slot is in use (retire one first)");
+    const size_t P = rq.ids.size();
+    if (P == 0) throw std::runtime_error("EINVAL: empty prompt");
+    if (max_new == 0 || (long)max_new > s.out_cap)
+        throw std::runtime_error("EINVAL: max_new_tokens must be 1.." + std::to_string(s.out_cap) + " in this session");
+    if (P + max_new + 1 > (size_t)s.max_context)
+        throw std::runtime_error("EINVAL: the page needs " + std::to_string(P + max_new + 1) +
+                                 " context rows (prompt + max_new_tokens + 1), the session has " + std::to_string(s.max_context));
+    if (!rq.mask.empty() && rq.mask.size() != P) throw std::runtime_error("EINVAL: image mask length differs from the prompt's");
+    size_t rows = 0, n_mask = 0;
+    if (rq.page) {
+        check_page_variant(*rq.page);
+        rows = image_row_order(*rq.page).size();
+    } else if (rq.image_rows) {
+        rows = rq.n_image_rows;
+    }
+    for (size_t i = 0; i < P; ++i) n_mask += (!rq.mask.empty() && rq.mask[i]) ? 1 : 0;
+    if (n_mask != rows)
+        throw std::runtime_error("EINVAL: prompt/image embedding mismatch: image embeddings provide " + std::to_string(rows) +
+                                 " tokens but mask requires " + std::to_string(n_mask));
+    for (size_t i = 0; i < P; ++i)
+        if ((rq.mask.empty() || !rq.mask[i]) && (rq.ids[i] < 0 || rq.ids[i] >= V))
+            throw std::runtime_error("EINVAL: token id out of bounds for vocab size");
+    const int slot = s.n;
+    const std::vector<GenRequest> reqs{rq};
+    GenParams gp = s.p;
+    gp.max_new = max_new;
+    GenState g(reqs, gp, nullptr, nullptr);
+    embed_pages(g);
+    plan_image_rows(g);
+    // the prefill of this page alone, into slot `slot` of the session cache and of s_x / s_logits
+    g.Lmax = s.Lcap;
+    g.SX = s.sx + (size_t)slot * H;
+    g.LOGITS = s.logits + (size_t)slot * V;
+    g.extra.resize(1);
+    {
+        ScopedSet page0(kv_page0_, slot);
+        forward_rows(g, g.prompt_len);
+    }
+    // the slot's rows in one launch from one staged buffer; the selection kernel advances the KV position, so
+    // it starts one behind (init_sampling)
+    const size_t stage_ints = (size_t)SS_HEAD + RNG_WORDS + P;
+    int* h = (int*)pinned("ss_stage", stage_ints * 4);
+    std::memset(h, 0, ((size_t)SS_HEAD + RNG_WORDS) * 4);
+    h[SS_CTX_LEN] = (int)P; h[SS_KV_POS] = (int)P - 1; h[SS_KV_LEN] = (int)P;
+    if (s.p.do_sample) {
+        if (!seed_set) {
+            std::random_device rd;
+            seed = ((uint64_t)rd() << 32) ^ rd();
+        }
+        const std::vector<uint32_t> rng = rng_state_from_u64(seed);
+        std::memcpy(h + SS_HEAD, rng.data(), sizeof(uint32_t) * RNG_WORDS);
+    }
+    std::memcpy(h + SS_HEAD + RNG_WORDS, rq.ids.data(), P * 4);
+    HIP_CHECK(hipMemcpyAsync(s.stage, h, stage_ints * 4, hipMemcpyHostToDevice, st));
+    SlotInitArgs ia;
+    ia.stage = s.stage; ia.slot = slot; ia.ctx = s.ctx; ia.ctx_cap = s.ctx_cap; ia.ctx_len = s.ctx_len;
+    ia.kv_pos = s.kvpos; ia.kv_len = s.kvlen; ia.done = s.done; ia.out_len = s.outlen; ia.tok = s.tok;
+    ia.rng = s.rng; ia.rng_words = RNG_WORDS; ia.ban = s.ban; ia.ban_ld = s.ban_ld;
+    launch_session_slot_init(ia, st);
+    DecSampleArgs sa;
+    SampleArgs pen;
+    session_sample_args(s, 1, slot, sa, pen);
+    launch_rep_penalty(pen, st);
+    launch_dec_sample(sa, st);  // the first token, its embedding into the slot's s_x row, the ban list
+    session_sentinels(s);
+    HIP_CHECK(hipStreamSynchronize(st));
+    s.slot[slot] = Session::Slot{max_new, (int)P, 0};
+    ++s.n;
+    return slot;
+}
+
+void Engine::session_step_body(Session& s) {
+    DecSampleArgs sa;
+    SampleArgs pen;
+    session_sample_args(s, s.n, 0, sa, pen);
+    decode_step(s.n, s.Lcap);
+    decode_head(s.n, sa, pen);
+}
+
+std::vector<Engine::SlotStatus> Engine::session_step(int k) {
+    Session& s = open_session();
+    if (k < 1) throw std::runtime_error("EINVAL: a burst has at least one step");
+    if (s.n == 0) return {};
+    k = std::min(k, (int)Session::kBurstCap);
+    // the capacity invariant (session_open), asserted before any launch: after this burst no slot's kv_pos may
+    // pass its cache rows.  A slot retired at the burst boundary after it finished never gets here
+    for (int b = 0; b < s.n; ++b) {
+        const int room = s.Lcap - s.slot[b].kv_pos;
+        if (room < 1)
+            throw std::runtime_error("EINVAL: slot " + std::to_string(b) + " has used its " + std::to_string(s.Lcap) +
+                                     " cache rows: retire finished slots at every burst boundary");
+        k = std::min(k, room);
+    }
+    hipStream_t st = stream_;
+    const bool use_graph = graphs_on();
+    if (use_graph && !s.graph[s.n]) {
+        StreamCapture cap(st, capturing_);
+        session_step_body(s);
+        s.graph[s.n] = cap.finish();
+    }
+    for (int i = 0; i < k; ++i) {
+        if (use_graph) s.graph[s.n].launch(st);
+        else session_step_body(s);
+    }
+    for (int b = 0; b < s.n; ++b) s.slot[b].kv_pos += k;
+    s.steps += (size_t)k;
+    return session_poll();
+}
+
+std::vector<Engine::SlotStatus> Engine::session_poll() {
+    Session& s = open_session();
+    hipStream_t st = stream_;
+    const int S = s.S;
+    HIP_CHECK(hipMemcpyAsync(s.pin, s.done, S * 4, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(s.pin + S, s.outlen, S * 4, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(s.pin + 2 * S, s.err, 4, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    if (s.pin[2 * S]) throw std::runtime_error("EINTERNAL: decode hand-off timed out inside a fused kernel");
+    std::vector<SlotStatus> out(s.n);
+    std::vector<int> tmp;
+    for (int b = 0; b < s.n; ++b) {
+        Session::Slot& sl = s.slot[b];
+        const int len = std::min(s.pin[S + b], (int)sl.max_new);
+        out[b].slot = b;
+        out[b].out_len = len;
+        out[b].done = (s.pin[b] != 0 || len >= (int)sl.max_new) ? 1 : 0;
+        if (len > sl.reported) {
+            tmp.resize(len - sl.reported);
+            HIP_CHECK(hipMemcpy(tmp.data(), s.out + (size_t)b * s.out_cap + sl.reported, tmp.size() * 4, hipMemcpyDeviceToHost));
+            out[b].fresh.assign(tmp.begin(), tmp.end());
+            sl.reported = len;
+        }
+    }
+    return out;
+}
+
+std::vector<int64_t> Engine::session_retire(int slot, int* moved_from) {
+    Session& s = open_session();
+    if (slot < 0 || slot >= s.n) throw std::runtime_error("EINVAL: slot " + std::to_string(slot) + " is not active");
+    const LangConfig& L = cfg_.lang;
+    hipStream_t st = stream_;
+    HIP_CHECK(hipStreamSynchronize(st));
+    int len = 0;
+    HIP_CHECK(hipMemcpy(&len, s.outlen + slot, 4, hipMemcpyDeviceToHost));
+    len = std::min(len, (int)s.slot[slot].max_new);
+    std::vector<int> ids(len);
+    if (len) HIP_CHECK(hipMemcpy(ids.data(), s.out + (size_t)slot * s.out_cap, (size_t)len * 4, hipMemcpyDeviceToHost));
+    const int last = s.n - 1;
+    if (moved_from) *moved_from = -1;
+    if (slot != last) {  // active pages stay dense: the last one moves into the freed slot
+        SlotMoveArgs m;
+        m.kc = kc_; m.vc = vc_; m.layers = L.layers; m.slots = s.S; m.kv_heads = L.kv_heads; m.cap_rows = s.Lcap;
+        m.hd = L.head_dim; m.layer_stride = (long)s.S * page_stride_; m.page_stride = page_stride_;
+        m.head_stride = head_stride_; m.src = last; m.dst = slot;
+        m.rows_bound = std::min(s.slot[last].kv_pos + 1, s.Lcap);
+        m.kv_len = s.kvlen; m.kv_pos = s.kvpos; m.ctx = s.ctx; m.ctx_cap = s.ctx_cap; m.ctx_len = s.ctx_len;
+        m.out = s.out; m.out_cap = s.out_cap; m.out_len = s.outlen; m.done = s.done; m.tok = s.tok;
+        m.rng = s.rng; m.rng_words = RNG_WORDS; m.ban = s.ban; m.ban_ld = s.ban_ld; m.x = s.sx; m.H = L.hidden;
+        launch_session_slot_move(m, st);
+        s.slot[slot] = s.slot[last];
+        if (moved_from) *moved_from = last;
+    }
+    --s.n;
+    session_sentinels(s);
+    HIP_CHECK(hipStreamSynchronize(st));
+    return std::vector<int64_t>(ids.begin(), ids.end());
+}
+
+void Engine::session_close() {
+    open_session();
+    (void)hipStreamSynchronize(stream_);
+    sess_.reset();
+    kv_pages_ = 0;
+    kv_page0_ = 0;
+    ws_frozen_.clear();
+    // the cache strides are the session's now: profile_decode replays the last generate, so it asks for a new one
+    last_B_ = 0;
+    last_Lmax_ = 0;
+}
+
+bool Engine::session_info(SessionInfo* out) const {
+    if (!sess_) return false;
+    if (out) {
+        out->slots = sess_->S; out->active = sess_->n; out->max_context = sess_->max_context;
+        out->out_cap = (int)sess_->out_cap; out->kv_cap = sess_->Lcap; out->burst_cap = Session::kBurstCap;
+        out->steps = sess_->steps;
+    }
+    return true;
+}
+
 // ============================================================================ profile_decode
 // `body` captured as one hipGraph on the engine stream, replayed once to warm, then n replays between two
 // events: the mean us of a replay
@@ -2343,6 +2729,7 @@ void Engine::time_launches(KernelProfile& kp, int n, const std::function<void(in
 }
 
 Engine::DecodeProfile Engine::profile_decode(int iters) {
+    if (sess_) throw std::runtime_error("EINVAL: a decode session is open on this engine (close it before profile_decode)");
     DecodeProfile prof;
     const LangConfig& L = cfg_.lang;
     const int B = last_B_, Lmax = last_Lmax_;

@@ -9,6 +9,7 @@
 #include <functional>
 #include <map>
 #include <memory>
+#include <set>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -213,6 +214,27 @@ class Engine {
     void upload_page(PagePixels& pg);
     void prepare_page_device(const uint8_t* rgb, int w, int h, PagePixels& px);
 
+    // ---- decode sessions: a long-lived batch of up to `slots` pages; pages are admitted
+    // (vision + prefill into their own slot) and retired between bursts of the unchanged decode step.  Active
+    // pages occupy slots [0, active).  A session and generate / profile_decode exclude each other (EINVAL).
+    struct SessionInfo {
+        int slots = 0, active = 0, max_context = 0, out_cap = 0, kv_cap = 0, burst_cap = 0;
+        size_t steps = 0;  // decode steps replayed since the session opened
+    };
+    struct SlotStatus {
+        int slot = 0, done = 0, out_len = 0;
+        std::vector<int64_t> fresh;  // the tokens since the last poll
+    };
+    // p: the session's sampling parameters (use_cache must be set, no trace); p.max_new = out_cap
+    void session_open(int slots, int max_context, const GenParams& p);
+    int session_admit(const GenRequest& rq, size_t max_new, bool seed_set, uint64_t seed);
+    std::vector<SlotStatus> session_step(int k);
+    std::vector<SlotStatus> session_poll();
+    // the page's ids; *moved_from = the slot whose page now lives in `slot` (the last active one), or -1
+    std::vector<int64_t> session_retire(int slot, int* moved_from);
+    void session_close();
+    bool session_info(SessionInfo* out) const;  // false: no session is open
+
   private:
     // ---- loading
     void load_weights(const std::string& path, uint64_t seed, const std::string& snapshot_path, bool packed_experts);
@@ -274,6 +296,13 @@ class Engine {
     void read_span_events(size_t step);
     void collect_spans();
     std::vector<std::vector<int64_t>> collect_outputs(GenState& g);
+    // decode sessions (engine.cpp, after generate)
+    struct Session;
+    std::unique_ptr<Session> sess_;
+    Session& open_session();
+    void session_sample_args(const Session& s, int B, int slot0, DecSampleArgs& sa, SampleArgs& pen);
+    void session_sentinels(const Session& s);
+    void session_step_body(Session& s);
     // profile_decode: its two timers and the sections after the MoE and attention replays
     double replay_us(int n, const std::function<void()>& body);
     void time_launches(KernelProfile& kp, int n, const std::function<void(int)>& body);
@@ -325,6 +354,11 @@ class Engine {
     float* vc_ = nullptr;
     size_t kv_bytes_ = 0;
     long page_stride_ = 0, head_stride_ = 0;
+    // a session's cache holds kv_pages_ pages per layer whatever the batch a launch runs (0: the launch's own
+    // B, as generate sizes it); its prefill writes page kv_page0_
+    int kv_pages_ = 0, kv_page0_ = 0;
+    long layer_kv(int B) const { return (long)(kv_pages_ ? kv_pages_ : B) * page_stride_; }
+    std::set<std::string> ws_frozen_;  // workspaces the session's captured graphs hold: growing one is EINTERNAL
     Timings timings_;
     double flops_acc_ = 0;  // FLOPs issued by linear() / attention since the last stage mark
     std::vector<int> prefill_lens_;  // rows per page of the prefill being issued

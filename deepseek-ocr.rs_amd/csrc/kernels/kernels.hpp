@@ -563,6 +563,37 @@ constexpr int RNG_KEY = 0, RNG_CTR = 8, RNG_IDX = 10, RNG_BUF = 16, RNG_WORDS = 
 void launch_dec_sample(const DecSampleArgs& a, hipStream_t s);
 void launch_dec_stoch_select(const DecSampleArgs& a, hipStream_t s);
 size_t dec_sample_blocks(int V);
+// Decode sessions (session.hip).  One page's decode state from slot src to slot dst (src != dst) in one launch:
+// K / V rows [0, min(kv_len[src], rows_bound)) of every layer and kv head (f32 caches [layers][slots][kv_heads]
+// [cap_rows][hd] with the given strides in floats; 16-byte nontemporal loads and stores, hd % 4 == 0), the whole
+// context / output / ban / RNG / x rows and the scalars (thread 0).  Rows past kv_len, the source slot and every
+// other slot are not written.  rows_bound <= 0: cap_rows.  Optional arrays may be null.
+struct SlotMoveArgs {
+    float* kc = nullptr; float* vc = nullptr;
+    int layers = 0, slots = 0, kv_heads = 0, cap_rows = 0, hd = 0;
+    long layer_stride = 0, page_stride = 0, head_stride = 0;
+    int src = 0, dst = 0, rows_bound = 0;
+    int* kv_len = nullptr; int* kv_pos = nullptr;
+    int* ctx = nullptr; long ctx_cap = 0; int* ctx_len = nullptr;
+    int* out = nullptr; long out_cap = 0; int* out_len = nullptr;
+    int* done = nullptr; int* tok = nullptr;
+    uint32_t* rng = nullptr; int rng_words = 0;
+    int* ban = nullptr; long ban_ld = 0;
+    float* x = nullptr; int H = 0;
+};
+void launch_session_slot_move(const SlotMoveArgs& a, hipStream_t s);
+// A new slot's rows from one staged device buffer [SS_HEAD header ints | rng_words words | ctx_len ids]: the context
+// row (zeros past ctx_len), ctx_len, kv_pos, kv_len, the RNG words; done = out_len = tok = 0 and an empty ban list
+constexpr int SS_CTX_LEN = 0, SS_KV_POS = 1, SS_KV_LEN = 2, SS_HEAD = 4;
+struct SlotInitArgs {
+    const int* stage = nullptr;
+    int slot = 0;
+    int* ctx = nullptr; long ctx_cap = 0; int* ctx_len = nullptr;
+    int* kv_pos = nullptr; int* kv_len = nullptr; int* done = nullptr; int* out_len = nullptr; int* tok = nullptr;
+    uint32_t* rng = nullptr; int rng_words = 0;
+    int* ban = nullptr; long ban_ld = 0;
+};
+void launch_session_slot_init(const SlotInitArgs& a, hipStream_t s);
 // Screened lm_head (lmhead.hip): int8 rows + per-row scale / error bound give every row an
 // interval [lo, hi] that provably contains the exact kernel's logit; each block keeps the best
 // lower bound of its unbanned rows and the rows whose hi reached its running threshold (its own

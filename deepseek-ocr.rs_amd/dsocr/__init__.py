@@ -3,7 +3,7 @@ engine API over the C ABI in include/dsocr.h)."""
 import os
 
 from ._lib import DsocrError, LIB_PATH, lib  # noqa: F401
-from .engine import (DecodeOutcome, DecodeParameters, DeepseekOcrEngine, ModelLoadArgs, Page,  # noqa: F401
+from .engine import (DecodeOutcome, DecodeParameters, DeepseekOcrEngine, ModelLoadArgs, Page, Session,  # noqa: F401
                      VisionSettings, build_prompt_tokens, load_model, normalize_text, render_prompt)
 
 CONFIG_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "configs")

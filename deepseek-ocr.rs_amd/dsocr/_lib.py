@@ -68,6 +68,15 @@ class DecodeProfileC(C.Structure):
                 ("moe_gateup_kernel", C.c_char_p), ("moe_down_kernel", C.c_char_p)]
 
 
+class SlotStatusC(C.Structure):
+    _fields_ = [("slot", C.c_int32), ("done", C.c_int32), ("out_len", C.c_int32), ("n_new", C.c_int32)]
+
+
+class SessionDescC(C.Structure):
+    _fields_ = [("slots", C.c_size_t), ("active", C.c_size_t), ("max_context", C.c_size_t), ("out_cap", C.c_size_t),
+                ("kv_cap", C.c_size_t), ("burst_cap", C.c_size_t), ("steps", C.c_size_t)]
+
+
 class DotsTimingsC(C.Structure):
     _fields_ = [("total_ms", C.c_double), ("patch_ms", C.c_double), ("blocks_ms", C.c_double),
                 ("attention_ms", C.c_double), ("merger_ms", C.c_double), ("tokens", C.c_size_t), ("groups", C.c_size_t)]
@@ -96,6 +105,8 @@ EXPORTS = [
     "dsocr_k_gemv_ex", "dsocr_k_gemv_kind", "dsocr_k_mm_swizzle", "dsocr_k_silu_mul",
     "dsocr_config_variant", "dsocr_engine_variant", "dsocr_prepare_page_variant", "dsocr_prepare_page_device_variant", "dsocr_k_attention_prefix",
     "dsocr_k_prefill_attention",
+    "dsocr_session_open", "dsocr_session_admit", "dsocr_session_step", "dsocr_session_poll", "dsocr_session_retire",
+    "dsocr_session_close", "dsocr_session_info", "dsocr_k_session_slot_move",
 ]
 
 # model variants behind the deepseek engine (dsocr_engine_variant)
@@ -201,6 +212,15 @@ def lib():
     L.dsocr_k_sample_greedy.argtypes =[i32, i32, vp, vp, i32, vp, i32, f32, vp]
     L.dsocr_k_sample_stoch.argtypes = [i32, i32, vp, vp, i32, vp, i32, f32, C.c_double, C.c_size_t, C.c_double,
                                        C.c_uint64, i32, vp]
+    L.dsocr_session_open.argtypes = [vp, sz, sz, C.POINTER(DecodeParamsC)]
+    L.dsocr_session_admit.argtypes = [vp, C.POINTER(RequestC), sz, i32, C.c_uint64, C.POINTER(i32)]
+    L.dsocr_session_step.argtypes = [vp, sz, C.POINTER(SlotStatusC), sz, C.POINTER(sz), vp, sz, C.POINTER(sz)]
+    L.dsocr_session_poll.argtypes = [vp, C.POINTER(SlotStatusC), sz, C.POINTER(sz), vp, sz, C.POINTER(sz)]
+    L.dsocr_session_retire.argtypes = [vp, i32, vp, sz, C.POINTER(sz), C.POINTER(i32)]
+    L.dsocr_session_close.argtypes = [vp]
+    L.dsocr_session_info.argtypes = [vp, C.POINTER(SessionDescC)]
+    L.dsocr_k_session_slot_move.argtypes = [i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, C.c_longlong, vp, vp,
+                                            C.c_longlong, vp, vp, vp, vp, i32, vp, C.c_longlong, vp, i32, i32, i32]
     _lib = L
     return L
 

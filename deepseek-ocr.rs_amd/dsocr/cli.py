@@ -90,6 +90,11 @@ def build_parser() -> argparse.ArgumentParser:
     b.add_argument("--bench", action="store_true", help="print per-stage timings")
     b.add_argument("--bench-output", metavar="PATH", help="write benchmark events to a JSON file")
     p.add_argument("-q", "--quiet", action="store_true", help="print only the final result")
+    p.add_argument("--slots", type=int, default=0, metavar="N",
+                   help="treat every --image as its own one-page document (the prompt has one <image>) and decode them "
+                        "together in a session of N slots (1..8); results print in input order.  0 = off")
+    p.add_argument("--max-context", type=int, default=4096,
+                   help="with --slots: context rows per slot (a page needs prompt + max_new_tokens + 1)")
     return p
 
 
@@ -197,6 +202,8 @@ def run_inference(args, out=sys.stdout, err=sys.stderr) -> int:
         tokenizer = load_tokenizer(args.tokenizer, vocab)
         prompt = render_prompt(args.template, "", prompt_raw)
         slots = prompt.count("<image>")
+        if getattr(args, "slots", 0):
+            return run_documents(args, engine, tokenizer, prompt, out, info)
         if slots != len(args.images):
             raise DsocrError(1, f"prompt includes {slots} <image> tokens but {len(args.images)} image paths "
                                 f"were provided")
@@ -260,6 +267,32 @@ def run_inference(args, out=sys.stdout, err=sys.stderr) -> int:
                           f"avg={s['avg_ms']:.2f}ms", file=err)
     finally:
         engine.close()
+    return 0
+
+
+def run_documents(args, engine, tokenizer, prompt: str, out, info) -> int:
+    """--slots N: every --image is a one-page document decoded with the same prompt; the pages share one decode
+    session (scheduler.BatchScheduler) and the results are written in input order."""
+    from .scheduler import BatchScheduler
+
+    if prompt.count("<image>") != 1:
+        raise DsocrError(1, "--slots decodes every --image as its own document: the prompt needs exactly one <image>")
+    if not args.images:
+        raise DsocrError(1, "--slots needs at least one --image")
+    images = [open_image(p) for p in args.images]
+    start = time.perf_counter()
+    with BatchScheduler(engine, tokenizer, args.slots, args.max_context, decode_params(args),
+                        vision_settings(args)) as sched:
+        futures = [sched.submit(prompt, [im]) for im in images]
+        outcomes = [f.result() for f in futures]
+    elapsed = time.perf_counter() - start
+    for path, o in zip(args.images, outcomes):
+        if not args.quiet:
+            out.write(f"==> {path} <==\n")
+        out.write(o.text + "\n")
+    out.flush()
+    info(f"{len(outcomes)} pages, {sum(o.response_tokens for o in outcomes)} tokens in {elapsed:.2f}s "
+         f"({len(outcomes) / elapsed if elapsed > 0 else 0.0:.2f} pages/s)")
     return 0
 
 

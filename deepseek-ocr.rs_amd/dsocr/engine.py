@@ -18,8 +18,8 @@ from typing import Callable, Optional, Sequence
 
 import numpy as np
 
-from ._lib import (DTYPES, LOAD_PACKED_EXPERTS, DecodeParamsC, DsocrError, LoadArgs, RequestC, ResultC, STREAM_CB, TimingsC,
-                   VisionSettingsC, check, lib)
+from ._lib import (DTYPES, LOAD_PACKED_EXPERTS, DecodeParamsC, DsocrError, LoadArgs, RequestC, ResultC, STREAM_CB,
+                   SessionDescC, SlotStatusC, TimingsC, VisionSettingsC, check, lib)
 
 
 @dataclass
@@ -362,6 +362,13 @@ class DeepseekOcrEngine:
                    moe_down_kernel=(p.moe_down_kernel or b"").decode())
         return out
 
+    # ------------------------------------------------------------------ decode sessions
+    def open_session(self, slots: int, max_context: int, params: DecodeParameters = DecodeParameters(),
+                     ignore_eos: bool = False) -> "Session":
+        """A long-lived batch of `slots` pages (dsocr_session_open): pages are admitted and retired between bursts
+        of decode steps.  `params` are the session's; params.max_new_tokens bounds a request's own."""
+        return Session(self, slots, max_context, params, ignore_eos)
+
     # ------------------------------------------------------------------ OcrEngine::decode
     def decode(self, tokenizer, prompt: str, images: Sequence, vision: VisionSettings,
                params: DecodeParameters, stream: Optional[Callable] = None) -> DecodeOutcome:
@@ -381,6 +388,87 @@ class DeepseekOcrEngine:
             except TypeError:
                 text = tokenizer.decode([int(t) for t in gen])
         return DecodeOutcome(normalize_text(text), len(ids), len(gen), gen)
+
+
+@dataclass
+class SlotStatus:
+    slot: int
+    done: bool
+    out_len: int
+    new_tokens: list
+
+
+class Session:
+    """One decode session of an engine (include/dsocr.h, "decode sessions").  Active pages occupy slots
+    [0, active); ``retire`` returns (ids, moved_from): the last active page moves into the freed slot."""
+
+    def __init__(self, engine: DeepseekOcrEngine, slots: int, max_context: int, params: DecodeParameters,
+                 ignore_eos: bool = False):
+        self._e = None
+        pc = _params_c(params, engine.eos_token_id, ignore_eos)
+        check(lib().dsocr_session_open(engine._h, int(slots), int(max_context), C.byref(pc)))
+        self._e = engine
+        self.params = params
+        d = self.info()
+        self.slots, self.max_context, self.out_cap = d["slots"], d["max_context"], d["out_cap"]
+        self.kv_cap, self.burst_cap = d["kv_cap"], d["burst_cap"]
+        self._status = (SlotStatusC * self.slots)()
+        self._tokens = np.empty(max(self.slots * self.out_cap, 1), np.int64)
+
+    def info(self) -> dict:
+        d = SessionDescC()
+        check(lib().dsocr_session_info(self._e._h, C.byref(d)))
+        return {k: int(getattr(d, k)) for k, _ in SessionDescC._fields_}
+
+    def admit(self, ids, mask=None, page: Optional[Page] = None, image_rows=None,
+              max_new_tokens: Optional[int] = None, seed: Optional[int] = None) -> int:
+        keep = []
+        req = self._e._request(ids, mask, page, image_rows, keep)
+        slot = C.c_int(-1)
+        check(lib().dsocr_session_admit(self._e._h, C.byref(req),
+                                        self.out_cap if max_new_tokens is None else int(max_new_tokens),
+                                        0 if seed is None else 1, seed or 0, C.byref(slot)))
+        return slot.value
+
+    def _report(self, ns, nt):
+        out, off = [], 0
+        for i in range(ns.value):
+            s = self._status[i]
+            out.append(SlotStatus(s.slot, bool(s.done), s.out_len, self._tokens[off:off + s.n_new].tolist()))
+            off += s.n_new
+        assert off == nt.value
+        return out
+
+    def step(self, k: int = 1) -> list:
+        ns, nt = C.c_size_t(), C.c_size_t()
+        check(lib().dsocr_session_step(self._e._h, int(k), self._status, self.slots, C.byref(ns),
+                                       self._tokens.ctypes.data_as(C.c_void_p), self._tokens.size, C.byref(nt)))
+        return self._report(ns, nt)
+
+    def poll(self) -> list:
+        ns, nt = C.c_size_t(), C.c_size_t()
+        check(lib().dsocr_session_poll(self._e._h, self._status, self.slots, C.byref(ns),
+                                       self._tokens.ctypes.data_as(C.c_void_p), self._tokens.size, C.byref(nt)))
+        return self._report(ns, nt)
+
+    def retire(self, slot: int):
+        out = np.empty(max(self.out_cap, 1), np.int64)
+        n, moved = C.c_size_t(), C.c_int(-1)
+        check(lib().dsocr_session_retire(self._e._h, int(slot), out.ctypes.data_as(C.c_void_p), out.size, C.byref(n),
+                                         C.byref(moved)))
+        return out[:n.value].tolist(), moved.value
+
+    def close(self):
+        if self._e is not None and getattr(self._e, "_h", None):
+            check(lib().dsocr_session_close(self._e._h))
+        self._e = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
 
 
 def load_model(args: ModelLoadArgs) -> DeepseekOcrEngine:

@@ -1,0 +1,278 @@
+"""Continuous batching over one engine: requests join and leave a decode session between bursts of steps.
+
+``BatchScheduler`` owns the engine from one worker thread (the engine is Send-not-Sync).  ``submit`` does the host
+work of a request on the caller's thread (page preprocessing on the host, prompt tokens) and returns a Future of
+the ``DecodeOutcome``.  The worker loop is: admit waiting requests while slots are free, poll (an admission's prefill
+yields the first token), step a burst, poll, hand every active request its new tokens, retire what finished.
+
+A request whose parameters differ from the session's in more than ``max_new_tokens`` / ``seed``, or that needs more
+context or output than the session has, waits until the session is empty and then runs alone through
+``engine.decode``.  Requests are served in arrival order: nothing behind such a request is admitted before it ran.
+
+The engine object needs ``open_session(slots, max_context, params)`` (admit / step / poll / retire / close, see
+``dsocr.engine.Session``), ``decode`` and, for prompts with several images, ``image_embeddings``; tests drive the
+scheduler with a scripted fake.
+"""
+from __future__ import annotations
+
+import threading
+from collections import deque
+from concurrent.futures import Future
+from dataclasses import dataclass, field, fields
+from typing import Any, Callable, Optional, Sequence
+
+from .engine import DecodeOutcome, DecodeParameters, Page, VisionSettings, build_prompt_tokens, normalize_text
+
+BURST = 8  # steps between polls while nobody streams: the cadence Engine::decode_cached polls at
+
+
+class CapacityError(RuntimeError):
+    """A burst would take a slot past its cache rows (the host-side capacity invariant)."""
+
+
+@dataclass
+class _Request:
+    prompt: str
+    images: Sequence
+    vision: VisionSettings
+    params: DecodeParameters
+    on_token: Optional[Callable]
+    future: Future
+    ids: list
+    mask: list
+    page: Any = None
+    pages: list = field(default_factory=list)  # several images: their rows are embedded by the worker
+    exclusive: bool = False
+    tokens: list = field(default_factory=list)
+    kv_pos: int = 0  # upper bound of the slot's device kv_pos: prompt + steps since admission
+    done: bool = False
+
+
+def _default_prepare(engine, tokenizer, prompt, images, vision):
+    """Host work of one request: the pages (preprocessed on the host: the worker thread owns the GPU) and the
+    prompt tokens.  Returns (ids, mask, pages)."""
+    pages = [Page(im, vision, None, getattr(engine, "variant", 0)) for im in images]
+    ids, mask = build_prompt_tokens(tokenizer, prompt, [p.n_image_tokens for p in pages])
+    return ids, mask, pages
+
+
+def _decode_text(tokenizer, ids) -> str:
+    if not hasattr(tokenizer, "decode"):
+        return ""
+    try:
+        return tokenizer.decode([int(t) for t in ids], skip_special_tokens=True)
+    except TypeError:
+        return tokenizer.decode([int(t) for t in ids])
+
+
+class BatchScheduler:
+    def __init__(self, engine, tokenizer, slots: int, max_context: int,
+                 defaults: DecodeParameters = DecodeParameters(), vision: Optional[VisionSettings] = None,
+                 prepare: Optional[Callable] = None):
+        if not 1 <= int(slots) <= 8:
+            raise ValueError("a session has 1..8 slots")
+        self.engine, self.tokenizer = engine, tokenizer
+        self.slots, self.max_context = int(slots), int(max_context)
+        self.defaults = defaults
+        self.vision = vision or VisionSettings()
+        self._prepare = prepare or _default_prepare
+        self._queue: deque = deque()
+        self._active: list = []  # index = slot
+        self._session = None
+        self._cv = threading.Condition()
+        self._stop = False
+        self.max_active = 0      # most pages the session held at once
+        self.bursts: list = []   # (active pages, steps asked) of every burst, for tests and tools
+        self._worker = threading.Thread(target=self._run, name="dsocr-scheduler", daemon=True)
+        self._worker.start()
+
+    # ------------------------------------------------------------------ caller's side
+    def compatible(self, params: DecodeParameters, prompt_len: int) -> bool:
+        """True when the request can share the session: only max_new_tokens / seed differ from the defaults."""
+        for f in fields(DecodeParameters):
+            if f.name in ("max_new_tokens", "seed"):
+                continue
+            if getattr(params, f.name) != getattr(self.defaults, f.name):
+                return False
+        if not params.use_cache or params.max_new_tokens < 1:
+            return False
+        if params.max_new_tokens > self.defaults.max_new_tokens:
+            return False
+        return prompt_len + params.max_new_tokens + 1 <= self.max_context
+
+    def submit(self, prompt: str, images: Sequence = (), vision: Optional[VisionSettings] = None,
+               params: Optional[DecodeParameters] = None, on_token: Optional[Callable] = None) -> Future:
+        fut: Future = Future()
+        params = params or self.defaults
+        vision = vision or self.vision
+        try:
+            ids, mask, pages = self._prepare(self.engine, self.tokenizer, prompt, list(images), vision)
+        except Exception as e:  # noqa: BLE001 - the request's own error, reported through its future
+            fut.set_exception(e)
+            return fut
+        rq = _Request(prompt, list(images), vision, params, on_token, fut, list(ids), list(mask))
+        if len(pages) == 1:
+            rq.page = pages[0]
+        else:
+            rq.pages = list(pages)
+        rq.exclusive = not self.compatible(params, len(rq.ids))
+        with self._cv:
+            if self._stop:
+                fut.set_exception(RuntimeError("scheduler is closed"))
+                return fut
+            self._queue.append(rq)
+            self._cv.notify_all()
+        return fut
+
+    def close(self):
+        with self._cv:
+            self._stop = True
+            self._cv.notify_all()
+        self._worker.join()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    # ------------------------------------------------------------------ worker
+    def _run(self):
+        try:
+            while True:
+                with self._cv:
+                    while not self._stop and not self._queue and not self._active:
+                        self._cv.wait()
+                    if self._stop:
+                        break
+                try:
+                    self._turn()
+                except Exception as e:  # noqa: BLE001 - a session-wide failure: every active request learns of it
+                    self._fail_active(e)
+        finally:
+            self._fail_active(RuntimeError("scheduler is closed"))
+            with self._cv:
+                pending, self._queue = list(self._queue), deque()
+            for rq in pending:
+                rq.future.set_exception(RuntimeError("scheduler is closed"))
+
+    def _fail_active(self, exc):
+        active, self._active = self._active, []
+        for rq in active:
+            if not rq.future.done():
+                rq.future.set_exception(exc)
+        self._close_session()
+
+    def _close_session(self):
+        s, self._session = self._session, None
+        if s is not None:
+            try:
+                s.close()
+            except Exception:  # noqa: BLE001 - closing after a failure must not hide it
+                pass
+
+    def _head(self):
+        with self._cv:
+            return self._queue[0] if self._queue else None
+
+    def _pop(self):
+        with self._cv:
+            return self._queue.popleft()
+
+    def _turn(self):
+        admitted = False
+        while True:
+            rq = self._head()
+            if rq is None:
+                break
+            if rq.exclusive:
+                if self._active:
+                    break  # it waits for the session to drain; nothing behind it overtakes it
+                self._pop()
+                self._run_exclusive(rq)
+                continue
+            if len(self._active) >= self.slots:
+                break
+            self._pop()
+            admitted |= self._admit(rq)
+        if not self._active:
+            return
+        if admitted:  # the prefill's own selection: every new page has its first token
+            self._deliver(self._session.poll())
+            self._retire_done()
+            if not self._active:
+                return
+        burst = 1 if any(rq.on_token is not None for rq in self._active) else min(BURST, self._session.burst_cap)
+        # host-side capacity invariant: a finished page is retired at every burst boundary, so no slot's KV
+        # position can pass the session's rows (max_context + burst cap); asserted before the burst is launched
+        for slot, rq in enumerate(self._active):
+            if rq.kv_pos + burst > self._session.kv_cap:
+                raise CapacityError(f"slot {slot}: kv_pos {rq.kv_pos} + burst {burst} exceeds the session's "
+                                    f"{self._session.kv_cap} cache rows")
+        self.bursts.append((len(self._active), burst))
+        status = self._session.step(burst)
+        for rq in self._active:
+            rq.kv_pos += burst
+        self._deliver(status)
+        self._retire_done()
+
+    def _admit(self, rq) -> bool:
+        try:
+            if self._session is None:
+                self._session = self.engine.open_session(self.slots, self.max_context, self.defaults)
+            rows = None
+            if rq.pages:
+                import numpy as np
+                rows = np.concatenate(self.engine.image_embeddings(rq.pages), axis=0)
+            slot = self._session.admit(rq.ids, rq.mask, rq.page, rows, max_new_tokens=rq.params.max_new_tokens,
+                                       seed=rq.params.seed)
+        except Exception as e:  # noqa: BLE001 - the request's own error: the running slots are untouched
+            rq.future.set_exception(e)
+            return False
+        if slot != len(self._active):
+            raise RuntimeError(f"session admitted into slot {slot}, expected {len(self._active)}")
+        rq.kv_pos = len(rq.ids)
+        self._active.append(rq)
+        self.max_active = max(self.max_active, len(self._active))
+        return True
+
+    def _deliver(self, status):
+        for st in status:
+            rq = self._active[st.slot]
+            room = rq.params.max_new_tokens - len(rq.tokens)
+            fresh = list(st.new_tokens)[:max(room, 0)]
+            for t in fresh:
+                rq.tokens.append(int(t))
+                if rq.on_token is not None:
+                    try:
+                        rq.on_token(len(rq.tokens), list(rq.tokens))
+                    except Exception:  # noqa: BLE001 - a consumer's failure is its own
+                        pass
+            rq.done = bool(st.done) or len(rq.tokens) >= rq.params.max_new_tokens
+
+    def _retire_done(self):
+        # highest slot first: the page that moves into a freed slot is then never one that is itself finished
+        for slot in range(len(self._active) - 1, -1, -1):
+            rq = self._active[slot]
+            if not rq.done:
+                continue
+            ids, moved = self._session.retire(slot)
+            last = len(self._active) - 1
+            if moved >= 0:
+                if moved != last:
+                    raise RuntimeError(f"session moved slot {moved}, expected the last active slot {last}")
+                self._active[slot] = self._active[last]
+            self._active.pop()
+            ids = [int(t) for t in ids][:rq.params.max_new_tokens]
+            rq.future.set_result(DecodeOutcome(normalize_text(_decode_text(self.tokenizer, ids)), len(rq.ids),
+                                               len(ids), ids))
+
+    def _run_exclusive(self, rq):
+        self._close_session()  # a session and a generate exclude each other on one engine
+        try:
+            out = self.engine.decode(self.tokenizer, rq.prompt, rq.images, rq.vision, rq.params, rq.on_token)
+        except Exception as e:  # noqa: BLE001
+            rq.future.set_exception(e)
+            return
+        rq.future.set_result(out)

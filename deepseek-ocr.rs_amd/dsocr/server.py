@@ -164,6 +164,9 @@ class ServerState:
     vision: VisionSettings = field(default_factory=VisionSettings)
     defaults: DecodeParameters = field(default_factory=DecodeParameters)
     lock: threading.Lock = field(default_factory=threading.Lock)
+    # continuous batching (scheduler.BatchScheduler over `engine`, --slots N): concurrent requests share one decode
+    # session instead of queueing behind the lock.  None (the default): one request at a time
+    scheduler: Any = None
 
     def validate_model(self, requested: str):
         if requested != self.model_id:
@@ -175,15 +178,29 @@ def _now() -> int:
 
 
 def generate_blocking(state: ServerState, prompt: str, images: list, params: DecodeParameters, on_token=None):
-    """generation.rs:75-163."""
-    with state.lock:
+    """generation.rs:75-163.  With a scheduler the request joins the running decode session (its error reaches only
+    its own future); without one it decodes alone behind the lock."""
+    def classify(e):
+        msg = str(e)
+        if "prompt formatting failed" in msg or "prompt/image embedding mismatch" in msg:
+            return ApiError.bad_request(msg)
+        return ApiError.internal(f"generation failed: {msg}")
+
+    if state.scheduler is not None:
         try:
-            outcome = state.engine.decode(state.tokenizer, prompt, images, state.vision, params, on_token)
+            outcome = state.scheduler.submit(prompt, images, state.vision, params, on_token).result()
         except DsocrError as e:
-            msg = str(e)
-            if "prompt formatting failed" in msg or "prompt/image embedding mismatch" in msg:
-                raise ApiError.bad_request(msg)
-            raise ApiError.internal(f"generation failed: {msg}")
+            raise classify(e)
+        except ApiError:
+            raise
+        except Exception as e:  # noqa: BLE001 - a scheduler failure is an internal error of this request
+            raise ApiError.internal(f"generation failed: {e}")
+    else:
+        with state.lock:
+            try:
+                outcome = state.engine.decode(state.tokenizer, prompt, images, state.vision, params, on_token)
+            except DsocrError as e:
+                raise classify(e)
     if outcome.response_tokens == 0 and not outcome.text.strip():
         raise ApiError.internal(EMPTY_GENERATION_ERROR)
     return outcome
@@ -402,6 +419,21 @@ def create_app(state: ServerState):
     return app
 
 
+def add_scheduler_args(p):
+    p.add_argument("--slots", type=int, default=0,
+                   help="decode-session slots (1..8): concurrent requests share one running batch; 0 = off")
+    p.add_argument("--max-context", type=int, default=4096,
+                   help="context rows per session slot (a request needs prompt + max_new_tokens + 1)")
+
+
+def make_scheduler(state: ServerState, slots: int, max_context: int):
+    """The state's scheduler for --slots N (None for 0: requests take the lock path)."""
+    if not slots:
+        return None
+    from .scheduler import BatchScheduler
+    return BatchScheduler(state.engine, state.tokenizer, slots, max_context, state.defaults, state.vision)
+
+
 def main(argv=None) -> int:
     """`deepseek-ocr-server` (server/src/args.rs + config defaults host 0.0.0.0, port 8000)."""
     import argparse
@@ -415,6 +447,7 @@ def main(argv=None) -> int:
     add_inference_args(p)
     p.add_argument("--host", default="0.0.0.0")
     p.add_argument("--port", type=int, default=8000)
+    add_scheduler_args(p)
     args = p.parse_args(argv)
     config = model_config(args)  # --model deepseek-ocr | deepseek-ocr-2: the bundled config and vision defaults
     engine = load_model(ModelLoadArgs(config_path=config, weights_path=args.weights, snapshot_path=args.snapshot,
@@ -423,6 +456,7 @@ def main(argv=None) -> int:
                                       synthetic_seed=args.synthetic_seed))
     state = ServerState(engine, load_tokenizer(args.tokenizer, _vocab_of(config)), args.model,
                         vision_settings(args), decode_params(args))
+    state.scheduler = make_scheduler(state, args.slots, args.max_context)
     import uvicorn
     uvicorn.run(create_app(state), host=args.host, port=args.port)
     return 0

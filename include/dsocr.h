@@ -201,6 +201,53 @@ dsocr_status dsocr_generate_trace(dsocr_engine* e, size_t n, const dsocr_request
                                   const dsocr_decode_params* params, dsocr_result* results, float* logits_out,
                                   size_t logits_cap);
 
+/* ---- decode sessions: pages join and leave a running batch between decode steps (no reference counterpart: the
+ * reference server decodes one request at a time behind its Mutex, server/src/state.rs:22).  A session is a
+ * long-lived batch of `slots` (1..8) pages with max_context rows each (a page needs prompt_len + max_new_tokens
+ * + 1).  Between bursts of decode steps a page is admitted (vision + prefill into its own slot; the other slots'
+ * state is untouched) or retired.  Active pages always occupy slots [0, active): retiring slot i < active - 1
+ * moves the last active page into slot i (one device launch), which dsocr_session_retire reports in *moved_from.
+ * Every page's ids equal dsocr_generate of that page alone with the same parameters and seed.
+ *   params are fixed for the session (do_sample, temperature, top_k, top_p, repetition_penalty,
+ *   no_repeat_ngram_size, eos_token_id, ignore_eos; use_cache must be non-zero); params->max_new_tokens is the
+ *   session's output capacity, the upper bound of a request's own max_new_tokens.  Per request only
+ *   max_new_tokens and the seed vary.  Launch spans, the persistent step and the logits trace are off.
+ *   dsocr_generate / _batch / _trace / dsocr_profile_decode on an engine with an open session are DSOCR_EINVAL,
+ *   and so is opening a second session.
+ *   A finished page keeps its slot until it is retired, and every step appends one K/V row to every active slot:
+ *   retire finished pages after every step call.  dsocr_session_step replays at most 8 steps (fewer where a slot
+ *   would run out of cache rows; DSOCR_EINVAL before any launch when a slot has none left). */
+typedef struct {
+    int32_t slot;     /* 0 .. active - 1 */
+    int32_t done;     /* eos was selected, or out_len reached the request's max_new_tokens */
+    int32_t out_len;  /* tokens generated so far (at most the request's max_new_tokens) */
+    int32_t n_new;    /* tokens since the last poll: the next n_new entries of `tokens` */
+} dsocr_slot_status;
+typedef struct {
+    size_t slots, active, max_context, out_cap;
+    size_t kv_cap;     /* cache rows per slot: max_context + burst_cap */
+    size_t burst_cap;  /* most steps one dsocr_session_step replays */
+    size_t steps;      /* decode steps replayed since the session opened */
+} dsocr_session_desc;
+dsocr_status dsocr_session_open(dsocr_engine* e, size_t slots, size_t max_context, const dsocr_decode_params* params);
+/* Every check (free slot, context need, prompt/image mismatch, token ids, page variant) happens before any device
+ * state changes; on an error the running slots are as they were.  *slot receives the page's slot (= active before). */
+dsocr_status dsocr_session_admit(dsocr_engine* e, const dsocr_request* req, size_t max_new_tokens, int has_seed,
+                                 uint64_t seed, int* slot);
+/* up to k decode steps for the active pages, then one poll.  status [cap_slots >= slots], tokens
+ * [cap_tokens >= slots * out_cap]: the new tokens of slot 0, then slot 1, ... (DSOCR_EINVAL if either is short) */
+dsocr_status dsocr_session_step(dsocr_engine* e, size_t k, dsocr_slot_status* status, size_t cap_slots, size_t* n_slots,
+                                int64_t* tokens, size_t cap_tokens, size_t* n_tokens);
+dsocr_status dsocr_session_poll(dsocr_engine* e, dsocr_slot_status* status, size_t cap_slots, size_t* n_slots,
+                                int64_t* tokens, size_t cap_tokens, size_t* n_tokens);
+/* the page's ids (truncated to its max_new_tokens) and its slot freed; *moved_from (optional): -1, or the slot
+ * whose page now lives in `slot` */
+dsocr_status dsocr_session_retire(dsocr_engine* e, int slot, int64_t* out_ids, size_t cap, size_t* n_out,
+                                  int* moved_from);
+dsocr_status dsocr_session_close(dsocr_engine* e);
+/* DSOCR_EINVAL when no session is open */
+dsocr_status dsocr_session_info(const dsocr_engine* e, dsocr_session_desc* out);
+
 /* Decode-kernel profile (bench roofline): replays the dominant decode kernels of the
  * last generate() call on its final routing / KV state, each timed with HIP events on
  * the engine stream.  avg_us = mean duration of one launch; bytes / flops = algorithmic
@@ -495,6 +542,17 @@ dsocr_status dsocr_k_sample_greedy(int B, int V, float* logits, const int* ctx, 
 dsocr_status dsocr_k_sample_stoch(int B, int V, float* logits, const int* ctx, int ctx_cap, const int* ctx_len,
                                   int ngram, float rep_penalty, double temperature, size_t top_k, double top_p,
                                   uint64_t seed, int draws, int* out_tok);
+
+/* One page's decode state from slot src to slot dst of a session (src != dst), one launch: K / V rows
+ * [0, kv_len[src]) of every layer and kv head of the f32 caches kc / vc [layers][slots][kv_heads][cap][hd]
+ * (16-byte vector copies, hd % 4 == 0), the rows ctx [slots][ctx_cap], out [slots][out_cap], ban [slots][ban_ld],
+ * rng [slots][rng_words], x [slots][H] and the per-slot scalars kv_len, kv_pos, ctx_len, out_len, done, tok.
+ * Rows from kv_len on, the source and every other slot are not written.  Any array but kc, vc, kv_len may be
+ * NULL.  Device pointers. */
+dsocr_status dsocr_k_session_slot_move(int layers, int slots, int kv_heads, int cap, int hd, float* kc, float* vc,
+                                       int* kv_len, int* kv_pos, int* ctx, long long ctx_cap, int* ctx_len, int* out,
+                                       long long out_cap, int* out_len, int* done, int* tok, uint32_t* rng,
+                                       int rng_words, int* ban, long long ban_ld, float* x, int H, int src, int dst);
 
 /* ---- dots.ocr vision tower (BASELINE configs[3]; crates/infer-dots/src/vision/dots_vit.rs
  *      DotsVisionModel::load / forward, vision/preprocess.rs preprocess_image).  The tower runs in the

@@ -1,0 +1,152 @@
+"""Mixed-length pages through three decode paths on one GPU.
+
+32 text pages of bench.py's kind (dsocr.synth.text_page_prompt), full-size synthetic weights, greedy, eos ignored.
+Page i generates MAX_NEW[i] tokens: drawn once, numpy default_rng(4011).choice(LENGTHS, 32).
+  (a) generate, one page after another (what the server does behind its lock)
+  (b) generate_batch in arrival-order groups of 8 (a closed batch runs to its longest page; ids truncated after)
+  (c) one 8-slot session fed in arrival order, bursts of 8 steps, finished pages retired at every burst boundary
+The three alternate ROUNDS times; pages/s and decode steps are reported as median [min, max].  Also: the wall time
+of one admission while other slots wait, and one session_slot_move of a 1200-row full-size page against its bytes.
+
+    python tools/session_bench.py [--rounds 3] [--pages 32] [--out profiles/session_bench.json]
+"""
+import argparse
+import ctypes as C
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "deepseek-ocr.rs_amd")]
+
+LENGTHS = [64, 96, 128, 192, 256, 384, 512]
+SLOTS = 8
+
+
+def mmm(v):
+    return {"median": statistics.median(v), "min": min(v), "max": max(v)}
+
+
+def run_single(eng, reqs, max_new, P):
+    steps = 0
+    for r, m in zip(reqs, max_new):
+        out = eng.generate(r, None, None, None, P(max_new_tokens=m), ignore_eos=True)
+        assert len(out) == m
+        steps += eng.last_timings()["decode_steps"]
+    return steps, {}
+
+
+def run_batches(eng, reqs, max_new, P):
+    steps = 0
+    for g in range(0, len(reqs), SLOTS):
+        group, ms = reqs[g:g + SLOTS], max_new[g:g + SLOTS]
+        out = eng.generate_batch([(r, None, None, None) for r in group], P(max_new_tokens=max(ms)), ignore_eos=True)
+        assert all(len(o) == max(ms) for o in out)
+        steps += eng.last_timings()["decode_steps"]
+    return steps, {}
+
+
+def run_session(eng, reqs, max_new, P):
+    need = max(len(r) + m + 1 for r, m in zip(reqs, max_new))
+    stalls, moves, done, nxt = [], [], 0, 0
+    with eng.open_session(SLOTS, need, P(max_new_tokens=max(max_new)), ignore_eos=True) as s:
+        active = 0
+        while done < len(reqs):
+            while active < SLOTS and nxt < len(reqs):
+                t = time.perf_counter()
+                s.admit(reqs[nxt], max_new_tokens=max_new[nxt])
+                if active:
+                    stalls.append((time.perf_counter() - t) * 1e3)
+                active, nxt = active + 1, nxt + 1
+            for st in sorted(s.step(8), key=lambda x: -x.slot):
+                if st.done:
+                    t = time.perf_counter()
+                    _, moved = s.retire(st.slot)
+                    if moved >= 0:
+                        moves.append((time.perf_counter() - t) * 1e3)
+                    active, done = active - 1, done + 1
+        steps = s.info()["steps"]
+    return steps, {"admit_stall_ms": stalls, "retire_with_move_ms": moves}
+
+
+def slot_move_alone(cfg, rows=1200, reps=10):
+    """dsocr_k_session_slot_move at the full-size cache shape, two slots: call wall time (launch + synchronise)."""
+    from dsocr._lib import check, lib
+    lang = cfg.get("language_config") or cfg
+    layers, heads = int(lang["num_hidden_layers"]), int(lang["num_attention_heads"])
+    kvh = int(lang.get("num_key_value_heads") or heads)
+    hd = int(lang.get("head_dim") or int(lang["hidden_size"]) // heads)
+    cap = rows + 8
+    L = lib()
+    n = layers * 2 * kvh * cap * hd * 4
+    kc, vc, kl = C.c_void_p(), C.c_void_p(), C.c_void_p()
+    for p, b in ((kc, n), (vc, n), (kl, 8)):
+        check(L.dsocr_dev_alloc(b, C.byref(p)))
+    lens = np.array([1, rows], np.int32)
+    check(L.dsocr_memcpy_h2d(kl, lens.ctypes.data_as(C.c_void_p), 8))
+    ms = []
+    try:
+        for i in range(reps + 2):
+            t = time.perf_counter()
+            check(L.dsocr_k_session_slot_move(layers, 2, kvh, cap, hd, kc, vc, kl, None, None, 0, None, None, 0, None,
+                                              None, None, None, 0, None, 0, None, 0, 1, 0))
+            if i >= 2:
+                ms.append((time.perf_counter() - t) * 1e3)
+            check(L.dsocr_memcpy_h2d(kl, lens.ctypes.data_as(C.c_void_p), 8))
+    finally:
+        for p in (kc, vc, kl):
+            L.dsocr_dev_free(p)
+    moved = 2 * layers * kvh * rows * hd * 4  # K and V, read once and written once each
+    r = mmm(ms)
+    r.update(rows=rows, bytes_copied=moved, gb_s_read_plus_write=2 * moved / (r["median"] * 1e-3) / 1e9)
+    return r
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--pages", type=int, default=32)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    import dsocr
+    from dsocr import DecodeParameters as P, ModelLoadArgs, load_model
+    from dsocr.synth import text_page_prompt
+    eng = load_model(ModelLoadArgs(config_path=dsocr.FULL_CONFIG, synthetic_seed=0, dtype="f16"))
+    max_new = [int(v) for v in np.random.default_rng(4011).choice(LENGTHS, a.pages)]
+    reqs = [text_page_prompt(i, vocab=eng.vocab) for i in range(a.pages)]
+    paths = {"a_generate": run_single, "b_generate_batch": run_batches, "c_session": run_session}
+    for f in paths.values():  # warm-up: workspaces, fragment-ordered weights, graphs
+        f(eng, reqs[:SLOTS], [16] * SLOTS, P)
+    res = {k: {"pages_s": [], "steps": [], "extra": []} for k in paths}
+    for _ in range(a.rounds):
+        for k, f in paths.items():
+            t = time.perf_counter()
+            steps, extra = f(eng, reqs, max_new, P)
+            res[k]["pages_s"].append(a.pages / (time.perf_counter() - t))
+            res[k]["steps"].append(int(steps))
+            res[k]["extra"].append(extra)
+    out = {"pages": a.pages, "max_new": max_new, "prompt_len": len(reqs[0]), "rounds": a.rounds}
+    for k, v in res.items():
+        out[k] = {"pages_s": mmm(v["pages_s"]), "steps": mmm(v["steps"])}
+    stalls = [x for e in res["c_session"]["extra"] for x in e["admit_stall_ms"]]
+    moves = [x for e in res["c_session"]["extra"] for x in e["retire_with_move_ms"]]
+    out["c_session"]["admit_stall_ms"] = mmm(stalls) if stalls else None
+    out["c_session"]["retire_with_move_ms"] = mmm(moves) if moves else None
+    out["c_over_a"] = out["c_session"]["pages_s"]["median"] / out["a_generate"]["pages_s"]["median"]
+    out["c_over_b"] = out["c_session"]["pages_s"]["median"] / out["b_generate_batch"]["pages_s"]["median"]
+    eng.close()
+    out["slot_move_1200_rows"] = slot_move_alone(json.load(open(dsocr.FULL_CONFIG)))
+    line = json.dumps(out)
+    print(line)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
