@@ -413,6 +413,35 @@ dsocr_status dsocr_session_open(dsocr_engine* e, size_t slots, size_t max_contex
     });
 }
 
+dsocr_status dsocr_session_open_ex(dsocr_engine* e, size_t slots, size_t max_context, const dsocr_decode_params* params,
+                                   uint32_t flags) {
+    return guarded([&] {
+        if (!e) throw std::runtime_error("EINVAL: NULL argument");
+        if (flags & ~(uint32_t)DSOCR_SESSION_PER_REQUEST) throw std::runtime_error("EINVAL: unknown session flags");
+        if (slots > 8 || max_context > (size_t)INT32_MAX / 2) throw std::runtime_error("EINVAL: a session has 1..8 slots");
+        e->impl->session_open((int)slots, (int)max_context, to_params(params), (flags & DSOCR_SESSION_PER_REQUEST) != 0);
+    });
+}
+
+dsocr_status dsocr_session_admit_params(dsocr_engine* e, const dsocr_request* req, const dsocr_decode_params* params,
+                                        int* slot) {
+    return guarded([&] {
+        if (!e || !req) throw std::runtime_error("EINVAL: NULL argument");
+        const int s = e->impl->session_admit(to_request(*req), to_params(params));
+        if (slot) *slot = s;
+    });
+}
+
+dsocr_status dsocr_session_head_steps(const dsocr_engine* e, size_t* screened, size_t* exact) {
+    return guarded([&] {
+        if (!e) throw std::runtime_error("EINVAL: NULL argument");
+        dsocr::Engine::SessionInfo si;
+        if (!e->impl->session_info(&si)) throw std::runtime_error("EINVAL: no decode session is open on this engine");
+        if (screened) *screened = si.steps_screened;
+        if (exact) *exact = si.steps_exact;
+    });
+}
+
 dsocr_status dsocr_session_admit(dsocr_engine* e, const dsocr_request* req, size_t max_new_tokens, int has_seed,
                                  uint64_t seed, int* slot) {
     return guarded([&] {
@@ -1455,6 +1484,69 @@ dsocr_status dsocr_k_sample_stoch(int B, int V, float* logits, const int* ctx, i
                 for (int i = 1; i < 8; ++i) fprintf(stderr, " %lld", h[i] ? (long long)(h[i] - h[0]) : -1LL);
                 fprintf(stderr, "\n");
             }
+        } catch (...) {
+            for (void* q : bufs) (void)hipFree(q);
+            throw;
+        }
+        for (void* q : bufs) (void)hipFree(q);
+    });
+}
+
+dsocr_status dsocr_k_select_rows(int B, int V, float* logits, const int* ctx, int ctx_cap, const int* ctx_len,
+                                 const dsocr_row_params* rows, const uint64_t* seeds, int draws, int* out_tok) {
+    return guarded([&] {
+        if (B <= 0 || V <= 0 || draws <= 0 || ctx_cap <= 0 || !logits || !ctx || !ctx_len || !rows || !seeds || !out_tok)
+            throw std::runtime_error("EINVAL: bad selection arguments");
+        // the records as an admission resolves them (host arrays)
+        std::vector<dsocr::RowParams> rp(B);
+        for (int b = 0; b < B; ++b) {
+            const dsocr_row_params& r = rows[b];
+            rp[b].do_sample = (r.do_sample != 0 && r.temperature > 0.0) ? 1 : 0;
+            rp[b].temperature = r.temperature; rp[b].top_p = r.top_p; rp[b].top_k = (long)r.top_k;
+            rp[b].rep_penalty = dsocr::rep_penalty_active(r.repetition_penalty) ? r.repetition_penalty : 1.0f;
+            rp[b].ngram = r.no_repeat_ngram_size > 1 ? (int)r.no_repeat_ngram_size : 0;
+            rp[b].eos = r.eos_token_id < 0 ? -1 : (int)r.eos_token_id;
+        }
+        const int rb = (int)dsocr::dec_sample_blocks(V);
+        std::vector<void*> bufs;
+        auto dalloc = [&](size_t bytes) {
+            void* p = nullptr;
+            check_hip(hipMalloc(&p, bytes), "hipMalloc");
+            bufs.push_back(p);
+            return p;
+        };
+        try {
+            dsocr::RowParams* d_rows = (dsocr::RowParams*)dalloc(sizeof(dsocr::RowParams) * B);
+            check_hip(hipMemcpy(d_rows, rp.data(), sizeof(dsocr::RowParams) * B, hipMemcpyHostToDevice), "hipMemcpy");
+            int* ridx = (int*)dalloc(sizeof(int) * B * rb);
+            float* rval = (float*)dalloc(sizeof(float) * B * rb);
+            int* done = (int*)dalloc(sizeof(int) * B);
+            check_hip(hipMemset(done, 0, sizeof(int) * B), "hipMemset");
+            dsocr::SampleArgs p;
+            p.logits = logits; p.B = B; p.V = V; p.ld = V; p.ctx = ctx; p.ctx_cap = ctx_cap; p.ctx_len = ctx_len;
+            p.rows = d_rows;
+            dsocr::launch_rep_penalty(p, nullptr);
+            dsocr::DecSampleArgs a;  // selection only: no output rows, so the context does not grow between draws
+            a.logits = logits; a.B = B; a.V = V; a.ld = V; a.ctx = const_cast<int*>(ctx); a.ctx_cap = ctx_cap;
+            a.ctx_len = const_cast<int*>(ctx_len); a.red_val = rval; a.red_idx = ridx; a.done = done;
+            a.rows = d_rows;
+            a.ban_ld = (long)ctx_cap + 1;
+            a.ban_out = (int*)dalloc(sizeof(int) * (size_t)B * a.ban_ld);
+            a.st_ld = V;
+            a.st_key = (uint32_t*)dalloc(sizeof(uint32_t) * 2 * (size_t)B * V);
+            a.st_idx = (int*)dalloc(sizeof(int) * 2 * (size_t)B * V);
+            a.st_w = (double*)dalloc(sizeof(double) * (size_t)B * V);
+            a.rng = (uint32_t*)dalloc(sizeof(uint32_t) * dsocr::RNG_WORDS * B);
+            for (int b = 0; b < B; ++b) {
+                const std::vector<uint32_t> st = dsocr::rng_state_from_u64(seeds[b]);
+                check_hip(hipMemcpy(a.rng + (size_t)b * dsocr::RNG_WORDS, st.data(), sizeof(uint32_t) * dsocr::RNG_WORDS,
+                                    hipMemcpyHostToDevice), "hipMemcpy");
+            }
+            for (int d = 0; d < draws; ++d) {
+                a.out_tok = out_tok + (size_t)d * B;
+                dsocr::launch_dec_sample(a, nullptr);
+            }
+            check_hip(hipDeviceSynchronize(), "select_rows");
         } catch (...) {
             for (void* q : bufs) (void)hipFree(q);
             throw;

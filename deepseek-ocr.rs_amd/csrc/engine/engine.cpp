@@ -169,19 +169,23 @@ struct Engine::Session {
     int S = 0, n = 0, max_context = 0, Lcap = 0;
     long ctx_cap = 0, out_cap = 0, ban_ld = 0;
     GenParams p;
-    bool screened = false;  // the screened head at every n (else the exact head at every n: one ban-list contract)
+    bool per_request = false;  // every slot has its own RowParams; the head is chosen per burst
+    bool screened = false;  // fixed parameters: the screened head at every n (else the exact head at every n)
     size_t part_floats = 0, qkv_floats = 0;
     float *sx = nullptr, *logits = nullptr, *part = nullptr, *qkv = nullptr;
     int *ctx = nullptr, *ctx_len = nullptr, *kvpos = nullptr, *kvlen = nullptr, *done = nullptr, *outlen = nullptr,
         *out = nullptr, *tok = nullptr, *ban = nullptr, *stage = nullptr, *err = nullptr;
     uint32_t* rng = nullptr;
+    RowParams* rowpar = nullptr;  // s_rowpar[S]: the per-row selection kernels' parameters (per_request)
     struct Slot {
         size_t max_new = 0;
         int kv_pos = 0;    // the device kv_pos of the slot: prompt + steps replayed since its admission
         int reported = 0;  // tokens the polls have handed out
+        RowParams rp;      // host copy of the slot's device record (per_request)
     };
     std::vector<Slot> slot;
-    HipGraphExec graph[9];  // the step for n active pages, captured on first use
+    HipGraphExec graph[9][2];  // the step for n active pages under the [exact, screened] head, captured on first use
+    size_t head_steps[2] = {0, 0};  // steps replayed under the [exact, screened] head
     PinnedBuffer<int> pin;  // poll: [done | output length] x S, then the decode error flag
     size_t steps = 0;
 };
@@ -1644,12 +1648,14 @@ bool Engine::screen_applies(int B, float rep_penalty) const {
 }
 
 // final norm + lm_head + greedy selection + step bookkeeping for the B decode rows in s_x
-void Engine::decode_head(int B, DecSampleArgs& sa, const SampleArgs& pen) {
+// screened: the int8 lm_head + screened final kernel (sa.ban_out holds the ban list the last step left, whichever
+// head wrote it); else the exact lm_head, the penalty and the selection kernels
+void Engine::decode_head(int B, DecSampleArgs& sa, const SampleArgs& pen, bool screened) {
     const LangConfig& L = cfg_.lang;
     hipStream_t st = stream_;
     const int H = L.hidden;
     float* SX = wsf("s_x", (size_t)B * H);
-    if (sa.ban_out) {
+    if (screened) {
         // screened selection: int8 lm_head intervals + running threshold, exact rescoring of the
         // few kept rows — the exact path's token from half the lm_head bytes
         LmHeadQ8Args q = head_q8_args(B);
@@ -2216,7 +2222,7 @@ void Engine::collect_spans() {
 // one decode step: the layers, the head and the selection (captured once, replayed per token)
 void Engine::step_body(GenState& g) {
     decode_step(g.B, g.Lmax);
-    decode_head(g.B, g.sa, g.pen);
+    decode_head(g.B, g.sa, g.pen, g.sa.ban_out != nullptr);
     // chain spans: the step's one fold, after the head (the step counter has advanced: record at count - 1)
     if (chain_active_)
         launch_span_chain_fold(span_chain_, cfg_.lang.layers * SPAN_KINDS_CHAIN, span_chain_rec_, span_step_, span_cap_,
@@ -2334,7 +2340,18 @@ Engine::Session& Engine::open_session() {
     return *sess_;
 }
 
-void Engine::session_open(int S, int max_context, const GenParams& p) {
+// a request's selection parameters as the device record the per-row kernels read (kernels.hpp RowParams)
+static RowParams resolve_row_params(const GenParams& p) {
+    RowParams r;
+    r.do_sample = (p.do_sample && p.temperature > 0.0) ? 1 : 0;
+    r.temperature = p.temperature; r.top_p = p.top_p; r.top_k = p.top_k;
+    r.rep_penalty = rep_penalty_active(p.rep_penalty) ? p.rep_penalty : 1.0f;
+    r.ngram = p.ngram;
+    r.eos = p.ignore_eos ? -1 : (int)p.eos;
+    return r;
+}
+
+void Engine::session_open(int S, int max_context, const GenParams& p, bool per_request) {
     if (sess_) throw std::runtime_error("EINVAL: a decode session is already open on this engine");
     if (S < 1 || S > 8) throw std::runtime_error("EINVAL: a session has 1..8 slots");
     if (!p.use_cache || p.trace) throw std::runtime_error("EINVAL: a session decodes with the K/V cache and without a logits trace");
@@ -2348,7 +2365,7 @@ void Engine::session_open(int S, int max_context, const GenParams& p) {
     hipStream_t st = stream_;
     auto sp = std::make_unique<Session>();
     Session& s = *sp;
-    s.S = S; s.max_context = max_context; s.p = p;
+    s.S = S; s.max_context = max_context; s.p = p; s.per_request = per_request;
     // Capacity invariant.  The selection kernels advance kv_pos of every row on every step, done or not, so a
     // finished page that waits for the end of its burst keeps appending K/V rows.  A page is admitted only with
     // prompt + max_new + 1 <= max_context and produces its last token at kv_pos <= prompt + max_new - 1; it is
@@ -2410,23 +2427,32 @@ void Engine::session_open(int S, int max_context, const GenParams& p) {
         const size_t red = dec_sample_blocks(V);
         wsf("s_redv", (size_t)S * red);
         wsi("s_redi", (size_t)S * red);
-        if (p.do_sample) {
+        // per-request parameters: what both heads need at every n, so nothing grows after the freeze (any slot may
+        // sample: the sampler's scratch and RNG rows for all of them)
+        if (p.do_sample || per_request) {
             wsi("s_stkey", (size_t)S * 2 * V);
             wsi("s_stidx", (size_t)S * 2 * V);
             wsf("s_stw", (size_t)S * 2 * V);
             s.rng = reinterpret_cast<uint32_t*>(zeroed("s_rng", (size_t)S * RNG_WORDS));
         }
+        s.rowpar = reinterpret_cast<RowParams*>(ws("s_rowpar", sizeof(RowParams) * S));
+        {
+            const std::vector<RowParams> init((size_t)S, resolve_row_params(p));
+            HIP_CHECK(hipMemcpy(s.rowpar, init.data(), sizeof(RowParams) * S, hipMemcpyHostToDevice));
+        }
         s.stage = wsi("ss_stage", (size_t)SS_HEAD + RNG_WORDS + s.ctx_cap);
         ensure_mm_weights(S);
-        s.screened = !p.do_sample;
+        s.screened = !p.do_sample && !per_request;
         for (int n = 1; n <= S; ++n) s.screened = s.screened && screen_applies(n, p.rep_penalty);
-        if (s.screened) {
+        if (s.screened || per_request) {
+            // (per request the ban rows are always kept and both final kernels write them every step: either head
+            // can take over from the other at a step boundary)
             s.ban = zeroed("s_ban", (size_t)S * s.ban_ld);
             for (int n = 1; n <= S; ++n) reserve_head_ws(n);
         }
         // every workspace the decode step asks for by name, at every n: a dry step per n allocates them (it
         // appends K/V row 0 of the empty slots, which an admission's prefill rewrites)
-        if (s.screened && getenv("DSOCR_SCREEN_STATS")) zeroed("s_scrstats", 32);
+        if ((s.screened || per_request) && getenv("DSOCR_SCREEN_STATS")) zeroed("s_scrstats", 32);
         for (int n = 1; n <= S; ++n) {
             session_sentinels(s);
             decode_step(n, s.Lcap);
@@ -2466,6 +2492,7 @@ void Engine::session_sample_args(const Session& s, int B, int slot0, DecSampleAr
     pen.logits = s.logits + (size_t)slot0 * V; pen.B = B; pen.V = V; pen.ld = V;
     pen.ctx = s.ctx + (size_t)slot0 * s.ctx_cap; pen.ctx_cap = s.ctx_cap; pen.ctx_len = s.ctx_len + slot0;
     pen.rep_penalty = p.rep_penalty;
+    if (s.per_request) pen.rows = s.rowpar + slot0;
     sa = DecSampleArgs();
     sa.logits = pen.logits; sa.B = B; sa.V = V; sa.ld = V;
     sa.ctx = s.ctx + (size_t)slot0 * s.ctx_cap; sa.ctx_cap = s.ctx_cap; sa.ctx_len = s.ctx_len + slot0; sa.ngram = p.ngram;
@@ -2477,23 +2504,42 @@ void Engine::session_sample_args(const Session& s, int B, int slot0, DecSampleAr
     sa.eos = p.ignore_eos ? -1 : (int)p.eos;
     sa.table = embed_; sa.table_dt = embed_dt_; sa.H = H; sa.x_next = s.sx + (size_t)slot0 * H;
     sa.kv_pos = s.kvpos + slot0; sa.kv_len = s.kvlen + slot0;
-    if (p.do_sample) {
-        sa.do_sample = 1; sa.temperature = p.temperature; sa.top_p = p.top_p; sa.top_k = p.top_k;
+    if (s.per_request) sa.rows = s.rowpar + slot0;  // (the scalars above and below are then not read)
+    if (p.do_sample || s.per_request) {
+        sa.do_sample = p.do_sample ? 1 : 0; sa.temperature = p.temperature; sa.top_p = p.top_p; sa.top_k = p.top_k;
         sa.st_ld = V;
         sa.st_key = reinterpret_cast<uint32_t*>(wsi("s_stkey", (size_t)s.S * 2 * V)) + (size_t)slot0 * 2 * V;
         sa.st_idx = wsi("s_stidx", (size_t)s.S * 2 * V) + (size_t)slot0 * 2 * V;
         sa.st_w = reinterpret_cast<double*>(wsf("s_stw", (size_t)s.S * 2 * V)) + (size_t)slot0 * V;
         sa.rng = s.rng + (size_t)slot0 * RNG_WORDS;
     }
-    if (s.screened) { sa.ban_ld = s.ban_ld; sa.ban_out = s.ban + (size_t)slot0 * s.ban_ld; }
+    if (s.ban) { sa.ban_ld = s.ban_ld; sa.ban_out = s.ban + (size_t)slot0 * s.ban_ld; }
 }
 
 int Engine::session_admit(const GenRequest& rq, size_t max_new, bool seed_set, uint64_t seed) {
+    GenParams p = open_session().p;
+    p.max_new = max_new; p.seed_set = seed_set; p.seed = seed;
+    return session_admit(rq, p);
+}
+
+int Engine::session_admit(const GenRequest& rq, const GenParams& rp) {
     Session& s = open_session();
+    const size_t max_new = rp.max_new;
+    const bool seed_set = rp.seed_set;
+    uint64_t seed = rp.seed;
     const LangConfig& L = cfg_.lang;
     const int H = L.hidden, V = L.vocab;
     hipStream_t st = stream_;
     // every check first: nothing below may fail on the request itself once device state changes
+    if (!rp.use_cache || rp.trace) throw std::runtime_error("EINVAL: a session decodes with the K/V cache and without a logits trace");
+    if (!s.per_request) {
+        const GenParams& q = s.p;
+        if (rp.do_sample != q.do_sample || rp.temperature != q.temperature || rp.top_p != q.top_p || rp.top_k != q.top_k ||
+            rp.rep_penalty != q.rep_penalty || rp.ngram != q.ngram || rp.eos != q.eos || rp.ignore_eos != q.ignore_eos)
+            throw std::runtime_error("EINVAL: this session's parameters are fixed (only max_new_tokens and the seed vary "
+                                     "per request): open it with DSOCR_SESSION_PER_REQUEST");
+    }
+    const RowParams row = resolve_row_params(rp);
     if (s.n >= s.S) throw std::runtime_error("EINVAL: every session slot is in use (retire one first)");
     const size_t P = rq.ids.size();
     if (P == 0) throw std::runtime_error("EINVAL: empty prompt");
@@ -2519,7 +2565,7 @@ int Engine::session_admit(const GenRequest& rq, size_t max_new, bool seed_set, u
             throw std::runtime_error("EINVAL: token id out of bounds for vocab size");
     const int slot = s.n;
     const std::vector<GenRequest> reqs{rq};
-    GenParams gp = s.p;
+    GenParams gp = s.per_request ? rp : s.p;
     gp.max_new = max_new;
     GenState g(reqs, gp, nullptr, nullptr);
     embed_pages(g);
@@ -2539,7 +2585,7 @@ int Engine::session_admit(const GenRequest& rq, size_t max_new, bool seed_set, u
     int* h = (int*)pinned("ss_stage", stage_ints * 4);
     std::memset(h, 0, ((size_t)SS_HEAD + RNG_WORDS) * 4);
     h[SS_CTX_LEN] = (int)P; h[SS_KV_POS] = (int)P - 1; h[SS_KV_LEN] = (int)P;
-    if (s.p.do_sample) {
+    if (s.per_request ? row.do_sample != 0 : s.p.do_sample) {
         if (!seed_set) {
             std::random_device rd;
             seed = ((uint64_t)rd() << 32) ^ rd();
@@ -2547,12 +2593,14 @@ int Engine::session_admit(const GenRequest& rq, size_t max_new, bool seed_set, u
         const std::vector<uint32_t> rng = rng_state_from_u64(seed);
         std::memcpy(h + SS_HEAD, rng.data(), sizeof(uint32_t) * RNG_WORDS);
     }
+    if (s.per_request) std::memcpy(h + SS_ROWPAR, &row, sizeof(RowParams));
     std::memcpy(h + SS_HEAD + RNG_WORDS, rq.ids.data(), P * 4);
     HIP_CHECK(hipMemcpyAsync(s.stage, h, stage_ints * 4, hipMemcpyHostToDevice, st));
     SlotInitArgs ia;
     ia.stage = s.stage; ia.slot = slot; ia.ctx = s.ctx; ia.ctx_cap = s.ctx_cap; ia.ctx_len = s.ctx_len;
     ia.kv_pos = s.kvpos; ia.kv_len = s.kvlen; ia.done = s.done; ia.out_len = s.outlen; ia.tok = s.tok;
     ia.rng = s.rng; ia.rng_words = RNG_WORDS; ia.ban = s.ban; ia.ban_ld = s.ban_ld;
+    if (s.per_request) ia.rowpar = s.rowpar;
     launch_session_slot_init(ia, st);
     DecSampleArgs sa;
     SampleArgs pen;
@@ -2561,17 +2609,27 @@ int Engine::session_admit(const GenRequest& rq, size_t max_new, bool seed_set, u
     launch_dec_sample(sa, st);  // the first token, its embedding into the slot's s_x row, the ban list
     session_sentinels(s);
     HIP_CHECK(hipStreamSynchronize(st));
-    s.slot[slot] = Session::Slot{max_new, (int)P, 0};
+    s.slot[slot] = Session::Slot{max_new, (int)P, 0, row};
     ++s.n;
     return slot;
 }
 
-void Engine::session_step_body(Session& s) {
+void Engine::session_step_body(Session& s, bool screened) {
     DecSampleArgs sa;
     SampleArgs pen;
     session_sample_args(s, s.n, 0, sa, pen);
     decode_step(s.n, s.Lcap);
-    decode_head(s.n, sa, pen);
+    decode_head(s.n, sa, pen, screened);
+}
+
+// the head of the next burst.  Fixed parameters: decided at session_open.  Per request: screened iff every active
+// slot is greedy with penalty 1.0 and the screened head applies at this n; it changes only where the set of
+// active slots does (admit, retire), and the ban rows both final kernels keep make the change a step boundary
+bool Engine::session_head_screened(const Session& s) const {
+    if (!s.per_request) return s.screened;
+    for (int b = 0; b < s.n; ++b)
+        if (s.slot[b].rp.do_sample || s.slot[b].rp.rep_penalty != 1.0f) return false;
+    return screen_applies(s.n, 1.0f);
 }
 
 std::vector<Engine::SlotStatus> Engine::session_step(int k) {
@@ -2590,17 +2648,20 @@ std::vector<Engine::SlotStatus> Engine::session_step(int k) {
     }
     hipStream_t st = stream_;
     const bool use_graph = graphs_on();
-    if (use_graph && !s.graph[s.n]) {
+    const bool screened = session_head_screened(s);
+    HipGraphExec& graph = s.graph[s.n][screened ? 1 : 0];
+    if (use_graph && !graph) {
         StreamCapture cap(st, capturing_);
-        session_step_body(s);
-        s.graph[s.n] = cap.finish();
+        session_step_body(s, screened);
+        graph = cap.finish();
     }
     for (int i = 0; i < k; ++i) {
-        if (use_graph) s.graph[s.n].launch(st);
-        else session_step_body(s);
+        if (use_graph) graph.launch(st);
+        else session_step_body(s, screened);
     }
     for (int b = 0; b < s.n; ++b) s.slot[b].kv_pos += k;
     s.steps += (size_t)k;
+    s.head_steps[screened ? 1 : 0] += (size_t)k;
     return session_poll();
 }
 
@@ -2653,6 +2714,7 @@ std::vector<int64_t> Engine::session_retire(int slot, int* moved_from) {
         m.kv_len = s.kvlen; m.kv_pos = s.kvpos; m.ctx = s.ctx; m.ctx_cap = s.ctx_cap; m.ctx_len = s.ctx_len;
         m.out = s.out; m.out_cap = s.out_cap; m.out_len = s.outlen; m.done = s.done; m.tok = s.tok;
         m.rng = s.rng; m.rng_words = RNG_WORDS; m.ban = s.ban; m.ban_ld = s.ban_ld; m.x = s.sx; m.H = L.hidden;
+        if (s.per_request) m.rowpar = s.rowpar;
         launch_session_slot_move(m, st);
         s.slot[slot] = s.slot[last];
         if (moved_from) *moved_from = last;
@@ -2681,6 +2743,8 @@ bool Engine::session_info(SessionInfo* out) const {
         out->slots = sess_->S; out->active = sess_->n; out->max_context = sess_->max_context;
         out->out_cap = (int)sess_->out_cap; out->kv_cap = sess_->Lcap; out->burst_cap = Session::kBurstCap;
         out->steps = sess_->steps;
+        out->steps_screened = sess_->head_steps[1]; out->steps_exact = sess_->head_steps[0];
+        out->per_request = sess_->per_request;
     }
     return true;
 }

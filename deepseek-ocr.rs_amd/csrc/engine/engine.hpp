@@ -220,14 +220,22 @@ class Engine {
     struct SessionInfo {
         int slots = 0, active = 0, max_context = 0, out_cap = 0, kv_cap = 0, burst_cap = 0;
         size_t steps = 0;  // decode steps replayed since the session opened
+        size_t steps_screened = 0, steps_exact = 0;  // ... under the screened / the exact lm_head + selection
+        bool per_request = false;
     };
     struct SlotStatus {
         int slot = 0, done = 0, out_len = 0;
         std::vector<int64_t> fresh;  // the tokens since the last poll
     };
     // p: the session's sampling parameters (use_cache must be set, no trace); p.max_new = out_cap
-    void session_open(int slots, int max_context, const GenParams& p);
+    // per_request: p are the defaults and every admission brings its own selection parameters (a RowParams record
+    // per slot, read by the per-row selection kernels); the head is chosen per burst: screened while every active
+    // slot is greedy without a penalty, else the exact head with both selectors
+    void session_open(int slots, int max_context, const GenParams& p, bool per_request = false);
     int session_admit(const GenRequest& rq, size_t max_new, bool seed_set, uint64_t seed);
+    // the request's whole parameter set (max_new, seed and what select_token_id reads).  Without per_request:
+    // EINVAL when it differs from the session's in more than max_new / seed
+    int session_admit(const GenRequest& rq, const GenParams& p);
     std::vector<SlotStatus> session_step(int k);
     std::vector<SlotStatus> session_poll();
     // the page's ids; *moved_from = the slot whose page now lives in `slot` (the last active one), or -1
@@ -276,7 +284,7 @@ class Engine {
     void ensure_persist();
     MoeDecodeArgs moe_args(int l, int B, float* X);
     DecAttn2Args attn_args(int l, int B, int Lmax);
-    void decode_head(int B, DecSampleArgs& sa, const SampleArgs& pen);
+    void decode_head(int B, DecSampleArgs& sa, const SampleArgs& pen, bool screened);
     void reserve_head_ws(int B);
     LmHeadQ8Args head_q8_args(int B);
     bool screen_applies(int B, float rep_penalty) const;
@@ -302,7 +310,8 @@ class Engine {
     Session& open_session();
     void session_sample_args(const Session& s, int B, int slot0, DecSampleArgs& sa, SampleArgs& pen);
     void session_sentinels(const Session& s);
-    void session_step_body(Session& s);
+    void session_step_body(Session& s, bool screened);
+    bool session_head_screened(const Session& s) const;
     // profile_decode: its two timers and the sections after the MoE and attention replays
     double replay_us(int n, const std::function<void()>& body);
     void time_launches(KernelProfile& kp, int n, const std::function<void(int)>& body);

@@ -28,13 +28,17 @@ __device__ __forceinline__ void block_argmax(float bv, int bi, float* sv, int* s
     __syncthreads();
 }
 
-template <bool LDSCTX>
+// ROWS (here and in the two final kernels): the page's ngram / eos come from its RowParams record a.rows[b]
+// instead of the launch arguments (a few scalar-uniform loads per block), and a page whose record says do_sample
+// leaves its selection slots to dec_stoch_select_kernel<true>: a block-uniform return before any barrier.
+template <bool LDSCTX, bool ROWS>
 __global__ __launch_bounds__(SP_BLOCK) void dec_argmax_partial_kernel(DecSampleArgs a) {
     extern __shared__ __attribute__((aligned(16))) int ctx_s[];  // the page's context, staged once per block (LDSCTX)
     __shared__ float sv[SP_BLOCK];
     __shared__ int si[SP_BLOCK];
     __shared__ unsigned ban[SP_PER_BLOCK / 32];  // banned-token bitmap of this block's vocab range
     const int b = blockIdx.y;
+    if (ROWS && a.rows[b].do_sample) return;
     const float* lg = a.logits + (long)b * a.ld;
     const int v0 = blockIdx.x * SP_PER_BLOCK, v1 = min(a.V, v0 + SP_PER_BLOCK);
     // this block's logits first (independent loads in flight during the n-gram scan)
@@ -46,7 +50,7 @@ __global__ __launch_bounds__(SP_BLOCK) void dec_argmax_partial_kernel(DecSampleA
         xv[j] = v < v1 ? lg[v] : -INFINITY;
     }
     for (int i = threadIdx.x; i < SP_PER_BLOCK / 32; i += SP_BLOCK) ban[i] = 0u;
-    const int n = a.ctx_len[b], g = a.ngram;
+    const int n = a.ctx_len[b], g = ROWS ? a.rows[b].ngram : a.ngram;
     const int* ctx = a.ctx + (long)b * a.ctx_cap;
     const bool use_ban = g > 1 && n >= g - 1;
     if (LDSCTX && use_ban)
@@ -148,7 +152,7 @@ __device__ __forceinline__ void screened_rescore(const DecSampleArgs& a, const u
     }
 }
 
-template <int NT>
+template <int NT, bool ROWS>
 __global__ __launch_bounds__(NT) void dec_screen_final_kernel(DecSampleArgs a) {
     extern __shared__ __attribute__((aligned(16))) float dyn[];  // [K] staged row | survivor list
     __shared__ float sv[NT / 64], sv2[NT / 64];
@@ -167,7 +171,8 @@ __global__ __launch_bounds__(NT) void dec_screen_final_kernel(DecSampleArgs a) {
     const unsigned long long t0 = a.stats ? wall_clock64() : 0;
 #define SP_STAMP(k) if (a.stats && tid == 0) a.stats[4 + (k)] += wall_clock64() - t0;
     // ---- token-independent loads
-    const int n = a.ctx_len[b], g = a.ngram;
+    const int n = a.ctx_len[b], g = ROWS ? a.rows[b].ngram : a.ngram;
+    const int eos = ROWS ? a.rows[b].eos : a.eos;
     int done0 = 0, olen0 = 0, kvp0 = 0, kvl0 = 0;
     if (tid == 0) {
         if (a.out_ids) { done0 = a.done[b]; olen0 = a.out_len[b]; }
@@ -305,7 +310,7 @@ __global__ __launch_bounds__(NT) void dec_screen_final_kernel(DecSampleArgs a) {
     if (tid == 0) {
         a.out_tok[b] = t;
         if (a.out_ids && !done0) {
-            if (a.eos >= 0 && t == a.eos) {
+            if (eos >= 0 && t == eos) {
                 a.done[b] = 1;
             } else {
                 if (olen0 < a.out_cap) { a.out_ids[(long)b * a.out_cap + olen0] = t; a.out_len[b] = olen0 + 1; }
@@ -376,12 +381,13 @@ __global__ __launch_bounds__(NT) void dec_screen_final_kernel(DecSampleArgs a) {
 #undef SP_STAMP
 }
 
-template <int NT>
+template <int NT, bool ROWS>
 __global__ __launch_bounds__(NT) void dec_sample_final_kernel(DecSampleArgs a) {
     __shared__ float sv[SP_BLOCK];
     __shared__ int si[SP_BLOCK];
     __shared__ int tok_s, nban_s;
     const int b = blockIdx.x;
+    const int eos = ROWS ? a.rows[b].eos : a.eos;
     float bv = -INFINITY;
     int bi = 0x7fffffff;
     for (int j = threadIdx.x; j < a.red_blocks; j += NT) {
@@ -418,7 +424,7 @@ __global__ __launch_bounds__(NT) void dec_sample_final_kernel(DecSampleArgs a) {
         nban_s = 0;
         a.out_tok[b] = t;
         if (a.out_ids && !a.done[b]) {
-            if (a.eos >= 0 && t == a.eos) {
+            if (eos >= 0 && t == eos) {
                 a.done[b] = 1;
             } else {
                 const int st = a.out_len[b];
@@ -436,7 +442,7 @@ __global__ __launch_bounds__(NT) void dec_sample_final_kernel(DecSampleArgs a) {
     __syncthreads();
     if (a.ban_out) {
         // the next step's banned tokens (sampling.rs:141-158 on the updated context)
-        const int n = a.ctx_len[b], g = a.ngram;
+        const int n = a.ctx_len[b], g = ROWS ? a.rows[b].ngram : a.ngram;
         const int* cx = a.ctx + (long)b * a.ctx_cap;
         int* out = a.ban_out + (long)b * a.ban_ld;
         if (g > 1 && n >= g - 1)
@@ -464,18 +470,29 @@ __global__ __launch_bounds__(NT) void dec_sample_final_kernel(DecSampleArgs a) {
 void launch_dec_sample(const DecSampleArgs& a0, hipStream_t s) {
     DecSampleArgs a = a0;
     a.red_blocks = (int)dec_sample_blocks(a.V);
-    const bool screen = !a.do_sample && a.blk_cnt && a.blk_t && a.cand && a.cand_hi && a.w_exact && a.xn && a.nblk > 0;
+    // (with per-row parameters the caller picks the screened head only when no row samples)
+    const bool screen = (a.rows || !a.do_sample) && a.blk_cnt && a.blk_t && a.cand && a.cand_hi && a.w_exact && a.xn && a.nblk > 0;
     if (a.ban_out && a.ban_ld < a.ctx_cap + 1) throw std::runtime_error("EINVAL: ban list shorter than the context");
     if (screen) {
         if (a.K % 8 || a.K > 1536) throw std::runtime_error("EINVAL: screened selection needs K % 8 == 0, K <= 1536");
         const size_t lds = sizeof(float) * a.K + sizeof(int) * SP_LIST;
-        DSOCR_LAUNCH((dec_screen_final_kernel<1024>), dim3(a.B), dim3(1024), lds, s, a);
+        if (a.rows) DSOCR_LAUNCH((dec_screen_final_kernel<1024, true>), dim3(a.B), dim3(1024), lds, s, a);
+        else DSOCR_LAUNCH((dec_screen_final_kernel<1024, false>), dim3(a.B), dim3(1024), lds, s, a);
+        return;
+    }
+    if (a.rows) {
+        // per-row exact head: both selectors every step (the mix of rows changes without the launches changing);
+        // every row's selection slots are written by exactly one of them
+        if (a.ctx_cap <= 16384) DSOCR_LAUNCH((dec_argmax_partial_kernel<true, true>), dim3(a.red_blocks, a.B), dim3(SP_BLOCK), sizeof(int) * a.ctx_cap, s, a);
+        else DSOCR_LAUNCH((dec_argmax_partial_kernel<false, true>), dim3(a.red_blocks, a.B), dim3(SP_BLOCK), 0, s, a);
+        launch_dec_stoch_select(a, s);
+        DSOCR_LAUNCH((dec_sample_final_kernel<SP_BLOCK, true>), dim3(a.B), dim3(SP_BLOCK), 0, s, a);
         return;
     }
     if (a.do_sample) launch_dec_stoch_select(a, s);  // sampling.hip: the chosen id in selection slot 0
-    else if (a.ctx_cap <= 16384) DSOCR_LAUNCH((dec_argmax_partial_kernel<true>), dim3(a.red_blocks, a.B), dim3(SP_BLOCK), sizeof(int) * a.ctx_cap, s, a);
-    else DSOCR_LAUNCH((dec_argmax_partial_kernel<false>), dim3(a.red_blocks, a.B), dim3(SP_BLOCK), 0, s, a);
-    DSOCR_LAUNCH((dec_sample_final_kernel<SP_BLOCK>), dim3(a.B), dim3(SP_BLOCK), 0, s, a);
+    else if (a.ctx_cap <= 16384) DSOCR_LAUNCH((dec_argmax_partial_kernel<true, false>), dim3(a.red_blocks, a.B), dim3(SP_BLOCK), sizeof(int) * a.ctx_cap, s, a);
+    else DSOCR_LAUNCH((dec_argmax_partial_kernel<false, false>), dim3(a.red_blocks, a.B), dim3(SP_BLOCK), 0, s, a);
+    DSOCR_LAUNCH((dec_sample_final_kernel<SP_BLOCK, false>), dim3(a.B), dim3(SP_BLOCK), 0, s, a);
 }
 
 }  // namespace dsocr

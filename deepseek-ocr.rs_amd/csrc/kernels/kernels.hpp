@@ -1,6 +1,7 @@
 // Host-side launch API for the gfx950 kernels.  All pointers are device pointers.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <stdint.h>
 
 namespace dsocr {
@@ -236,11 +237,26 @@ void launch_trace_logits(const float* logits, int B, int V, long ld, const int* 
                          long steps, hipStream_t s);
 void launch_embed_tokens(const void* table, int table_dt, const int* ids, int n, int H, float* out, long ld,
                          hipStream_t s);
+// One page's selection parameters as the per-row selection kernels read them from device memory (a decode
+// session with per-request parameters: one record per slot).  Resolved on the host: do_sample is 1 only when
+// do_sample && temperature > 0 (sampling.rs:67), eos is -1 under ignore_eos, and a penalty launch_rep_penalty
+// would skip is stored as exactly 1.0.
+struct RowParams {
+    double temperature = 0.0, top_p = -1.0;
+    long top_k = 0;
+    float rep_penalty = 1.f;
+    int do_sample = 0, ngram = 0, eos = -1;
+};
+constexpr int ROWPAR_INTS = (int)(sizeof(RowParams) / sizeof(int));
+static_assert(sizeof(RowParams) == 40 && sizeof(RowParams) % sizeof(int) == 0, "RowParams is staged as ints");
+inline bool rep_penalty_active(float p) { return p > 0.f && fabsf(p - 1.0f) > 1.1920929e-07f; }
 // Repetition penalty over the context tokens (sampling.rs:34-96), in place on the logits.
+// rows != null: every row reads its own penalty (launched unconditionally; a row at 1.0 leaves its logits alone)
 struct SampleArgs {
     float* logits = nullptr; int B = 0, V = 0; long ld = 0;
     const int* ctx = nullptr; long ctx_cap = 0; const int* ctx_len = nullptr;
     float rep_penalty = 1.f;
+    const RowParams* rows = nullptr;
 };
 void launch_rep_penalty(const SampleArgs& a, hipStream_t s);
 
@@ -557,6 +573,9 @@ struct DecSampleArgs {
     int do_sample = 0; double temperature = 0.0, top_p = -1.0; long top_k = 0;
     uint32_t* rng = nullptr; uint32_t* st_key = nullptr; int* st_idx = nullptr; double* st_w = nullptr; long st_ld = 0;
     unsigned long long* st_stamps = nullptr;  // diagnostics: shader clock at the sampler's phase points (page 0)
+    // per-row parameters (decode_select_rows.hip): when set, ngram / eos / do_sample / temperature / top_k / top_p
+    // above are not read; both selectors run and every row takes the one its record names
+    const RowParams* rows = nullptr;
 };
 // rand StdRng state words per page: ChaCha12 key, 64-bit block counter, buffer index, 64-word buffer
 constexpr int RNG_KEY = 0, RNG_CTR = 8, RNG_IDX = 10, RNG_BUF = 16, RNG_WORDS = 80;
@@ -580,11 +599,15 @@ struct SlotMoveArgs {
     uint32_t* rng = nullptr; int rng_words = 0;
     int* ban = nullptr; long ban_ld = 0;
     float* x = nullptr; int H = 0;
+    RowParams* rowpar = nullptr;  // [slots] per-row selection parameters
 };
 void launch_session_slot_move(const SlotMoveArgs& a, hipStream_t s);
 // A new slot's rows from one staged device buffer [SS_HEAD header ints | rng_words words | ctx_len ids]: the context
-// row (zeros past ctx_len), ctx_len, kv_pos, kv_len, the RNG words; done = out_len = tok = 0 and an empty ban list
-constexpr int SS_CTX_LEN = 0, SS_KV_POS = 1, SS_KV_LEN = 2, SS_HEAD = 4;
+// row (zeros past ctx_len), ctx_len, kv_pos, kv_len, the RNG words; done = out_len = tok = 0 and an empty ban list.
+// Header ints [SS_ROWPAR, SS_ROWPAR + ROWPAR_INTS) hold the slot's RowParams (8-byte aligned), written when
+// rowpar is set
+constexpr int SS_CTX_LEN = 0, SS_KV_POS = 1, SS_KV_LEN = 2, SS_ROWPAR = 4, SS_HEAD = 16;
+static_assert(SS_ROWPAR + ROWPAR_INTS <= SS_HEAD && SS_ROWPAR % 2 == 0, "the stage header holds one RowParams");
 struct SlotInitArgs {
     const int* stage = nullptr;
     int slot = 0;
@@ -592,6 +615,7 @@ struct SlotInitArgs {
     int* kv_pos = nullptr; int* kv_len = nullptr; int* done = nullptr; int* out_len = nullptr; int* tok = nullptr;
     uint32_t* rng = nullptr; int rng_words = 0;
     int* ban = nullptr; long ban_ld = 0;
+    RowParams* rowpar = nullptr;  // [slots] (optional)
 };
 void launch_session_slot_init(const SlotInitArgs& a, hipStream_t s);
 // Screened lm_head (lmhead.hip): int8 rows + per-row scale / error bound give every row an

@@ -179,9 +179,14 @@ void launch_trace_logits(const float* logits, int B, int V, long ld, const int* 
 // ------------------------------------------------------------------ repetition penalty
 // sampling.rs:34-96: every distinct context token's logit is divided (>0) or multiplied
 // (<=0) by the penalty once.  Selection itself is dec_argmax_partial / dec_sample_final (decode_sample.hip).
+// ROWS: the page's penalty comes from its RowParams record; a page at exactly 1.0 (the host stores that for every
+// penalty launch_rep_penalty would skip) returns before touching its logits
+template <bool ROWS>
 __global__ void rep_penalty_kernel(SampleArgs a) {
     // apply once per distinct context token: the first occurrence applies it
     const int b = blockIdx.y;
+    const float pen = ROWS ? a.rows[b].rep_penalty : a.rep_penalty;
+    if (ROWS && pen == 1.0f) return;
     const int n = a.ctx_len[b];
     const int* ctx = a.ctx + (long)b * a.ctx_cap;
     float* lg = a.logits + (long)b * a.ld;
@@ -193,13 +198,14 @@ __global__ void rep_penalty_kernel(SampleArgs a) {
             if (ctx[j] == t) { first = false; break; }
         if (!first) continue;
         float v = lg[t];
-        lg[t] = v > 0.f ? v / a.rep_penalty : v * a.rep_penalty;
+        lg[t] = v > 0.f ? v / pen : v * pen;
     }
 }
 
 void launch_rep_penalty(const SampleArgs& a, hipStream_t s) {
-    if (a.rep_penalty > 0.f && fabsf(a.rep_penalty - 1.0f) > 1.1920929e-07f)
-        hipLaunchKernelGGL(rep_penalty_kernel, dim3(8, a.B), dim3(256), 0, s, a);
+    if (a.rows) hipLaunchKernelGGL(rep_penalty_kernel<true>, dim3(8, a.B), dim3(256), 0, s, a);
+    else if (rep_penalty_active(a.rep_penalty))
+        hipLaunchKernelGGL(rep_penalty_kernel<false>, dim3(8, a.B), dim3(256), 0, s, a);
 }
 
 // ------------------------------------------------------------------ launch profiling hook (diagnostics)

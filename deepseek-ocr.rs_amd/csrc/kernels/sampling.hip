@@ -179,6 +179,10 @@ __device__ double block_serial_fold(int n, double* tiles, int* stop_s, double* c
     return total;
 }
 
+// ROWS: temperature / top_k / top_p / ngram come from the page's RowParams record a.rows[b]; a page whose record
+// does not sample returns at once (block-uniform, before the ban bitmap and any barrier): its selection slots are
+// dec_argmax_partial_kernel's
+template <bool ROWS>
 __global__ __launch_bounds__(ST_NT) void dec_stoch_select_kernel(DecSampleArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint32_t ban[];  // (V + 31) / 32 words: n-gram ban, later the kept set
     __shared__ double lds_big[ST_DIG * ST_NT / 2];  // radix histograms, later two fold tiles
@@ -189,6 +193,9 @@ __global__ __launch_bounds__(ST_NT) void dec_stoch_select_kernel(DecSampleArgs a
     __shared__ int keep_s, tok_s;
     __shared__ double total_s, chosen_s;
     const int b = blockIdx.x, tid = threadIdx.x, V = a.V;
+    if (ROWS && !a.rows[b].do_sample) return;
+    const long top_k = ROWS ? a.rows[b].top_k : a.top_k;
+    const double top_p = ROWS ? a.rows[b].top_p : a.top_p;
     const int nwords = (V + 31) >> 5;
     const float* lg = a.logits + (long)b * a.ld;
     uint32_t* sk0 = a.st_key + (long)b * 2 * a.st_ld;
@@ -196,7 +203,7 @@ __global__ __launch_bounds__(ST_NT) void dec_stoch_select_kernel(DecSampleArgs a
     int* si0 = a.st_idx + (long)b * 2 * a.st_ld;
     int* si1 = si0 + a.st_ld;
     double* sw = a.st_w + (long)b * a.st_ld;
-    const double T = a.temperature;
+    const double T = ROWS ? a.rows[b].temperature : a.temperature;
 #define ST_STAMP(i) \
     if (a.st_stamps && b == 0 && tid == 0) a.st_stamps[i] = __builtin_amdgcn_s_memtime();
     ST_STAMP(0)
@@ -205,7 +212,7 @@ __global__ __launch_bounds__(ST_NT) void dec_stoch_select_kernel(DecSampleArgs a
     for (int i = tid; i < nwords; i += ST_NT) ban[i] = 0u;
     __syncthreads();
     {
-        const int n = a.ctx_len[b], g = a.ngram;
+        const int n = a.ctx_len[b], g = ROWS ? a.rows[b].ngram : a.ngram;
         const int* cx = a.ctx + (long)b * a.ctx_cap;
         if (g > 1 && n >= g - 1)
             for (int i = tid; i <= n - g; i += ST_NT) {
@@ -273,8 +280,8 @@ __global__ __launch_bounds__(ST_NT) void dec_stoch_select_kernel(DecSampleArgs a
         return;
     }
 
-    const bool topk = a.top_k > 0 && a.top_k < V && nc > a.top_k;
-    const bool topp = a.top_p >= 0.0 && a.top_p < 1.0;
+    const bool topk = top_k > 0 && top_k < V && nc > top_k;
+    const bool topp = top_p >= 0.0 && top_p < 1.0;
     const int* kept = si0;
     int nk = nc;
     if (topk || topp) {
@@ -325,7 +332,7 @@ __global__ __launch_bounds__(ST_NT) void dec_stoch_select_kernel(DecSampleArgs a
         }
         // 8 passes: sorted data is back in (sk0, si0)
         ST_STAMP(3)
-        int m = topk ? (int)a.top_k : nc;
+        int m = topk ? (int)top_k : nc;
         if (topp) {
             // apply_top_p: weights exp(q - qmax) in sorted order; the total, then the cumulative share
             // until it exceeds top_p, both as in-order folds (sampling.rs:195-211)
@@ -337,7 +344,7 @@ __global__ __launch_bounds__(ST_NT) void dec_stoch_select_kernel(DecSampleArgs a
             __syncthreads();
             const double tot = total_s;
             if (tot > 0.0) {
-                const double tp = a.top_p;
+                const double tp = top_p;
                 (void)block_serial_fold(m, lds_big, &stop_s, nullptr, [&](int j) { return wsorted(j) / tot; },
                                         [&](double cumv) { return cumv > tp; }, [&](int j) { keep_s = j + 1; });
             }
@@ -358,7 +365,7 @@ __global__ __launch_bounds__(ST_NT) void dec_stoch_select_kernel(DecSampleArgs a
         // in index order — exactly the first k of the stable sort
         for (int i = tid; i < nwords; i += ST_NT) ban[i] = 0u;
         uint32_t prefix = 0u, pmask = 0u;
-        int need = (int)a.top_k;
+        int need = (int)top_k;
         for (int sh = 24; sh >= 0; sh -= 8) {
             for (int d = tid; d < 256; d += ST_NT) hist[d] = 0;
             __syncthreads();
@@ -474,13 +481,15 @@ __global__ __launch_bounds__(ST_NT) void dec_stoch_select_kernel(DecSampleArgs a
 }
 
 void launch_dec_stoch_select(const DecSampleArgs& a, hipStream_t s) {
-    if (!(a.temperature > 0.0)) throw std::runtime_error("EINVAL: sampling needs temperature > 0");
+    // (per-row parameters: a record has do_sample only with temperature > 0, checked where it is admitted)
+    if (!a.rows && !(a.temperature > 0.0)) throw std::runtime_error("EINVAL: sampling needs temperature > 0");
     if (!a.rng || !a.st_key || !a.st_idx || !a.st_w || a.st_ld < a.V)
         throw std::runtime_error("EINTERNAL: sampling workspaces missing");
     const size_t lds = sizeof(uint32_t) * (size_t)((a.V + 31) / 32);
     if (lds + sizeof(int) * (ST_DIG * ST_NT + 64) > 160 * 1024)
         throw std::runtime_error("EINVAL: vocabulary too large for the sampling kernel");
-    hipLaunchKernelGGL(dec_stoch_select_kernel, dim3(a.B), dim3(ST_NT), lds, s, a);
+    if (a.rows) hipLaunchKernelGGL(dec_stoch_select_kernel<true>, dim3(a.B), dim3(ST_NT), lds, s, a);
+    else hipLaunchKernelGGL(dec_stoch_select_kernel<false>, dim3(a.B), dim3(ST_NT), lds, s, a);
 }
 
 }  // namespace dsocr

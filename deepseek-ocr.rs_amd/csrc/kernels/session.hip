@@ -52,6 +52,8 @@ __global__ __launch_bounds__(SM_BLOCK) void session_slot_move_kernel(SlotMoveArg
         for (int i = t; i < a.rng_words; i += SM_BLOCK) a.rng[(long)d * a.rng_words + i] = a.rng[(long)s * a.rng_words + i];
     if (a.x)
         for (int i = t; i < a.H; i += SM_BLOCK) a.x[(long)d * a.H + i] = a.x[(long)s * a.H + i];
+    if (a.rowpar && t < ROWPAR_INTS)
+        reinterpret_cast<int*>(a.rowpar + d)[t] = reinterpret_cast<const int*>(a.rowpar + s)[t];
     if (t == 0) {
         a.kv_len[d] = a.kv_len[s];
         if (a.kv_pos) a.kv_pos[d] = a.kv_pos[s];
@@ -82,7 +84,7 @@ void launch_session_slot_move(const SlotMoveArgs& a, hipStream_t s) {
     DSOCR_LAUNCH(session_slot_move_kernel, dim3(nchunk + 1, a.kv_heads, a.layers), dim3(SM_BLOCK), 0, s, b);
 }
 
-// stage: [SS_HEAD header ints | rng words | ctx ids]; the slot's context row is written whole (zeros past ctx_len)
+// stage: [SS_HEAD header ints (RowParams at SS_ROWPAR) | rng words | ctx ids]; the slot's context row is written whole (zeros past ctx_len)
 __global__ __launch_bounds__(SM_BLOCK) void session_slot_init_kernel(SlotInitArgs a) {
     const int* h = a.stage;
     const int d = a.slot;
@@ -91,6 +93,7 @@ __global__ __launch_bounds__(SM_BLOCK) void session_slot_init_kernel(SlotInitArg
     if (i < a.ctx_cap) a.ctx[(long)d * a.ctx_cap + i] = i < n ? h[SS_HEAD + a.rng_words + i] : 0;
     if (blockIdx.x) return;
     if (a.rng && (int)threadIdx.x < a.rng_words) a.rng[(long)d * a.rng_words + threadIdx.x] = (uint32_t)h[SS_HEAD + threadIdx.x];
+    if (a.rowpar && (int)threadIdx.x < ROWPAR_INTS) reinterpret_cast<int*>(a.rowpar + d)[threadIdx.x] = h[SS_ROWPAR + threadIdx.x];
     if (threadIdx.x == 0) {
         a.ctx_len[d] = n;
         a.kv_pos[d] = h[SS_KV_POS];

@@ -77,6 +77,15 @@ class SessionDescC(C.Structure):
                 ("kv_cap", C.c_size_t), ("burst_cap", C.c_size_t), ("steps", C.c_size_t)]
 
 
+class RowParamsC(C.Structure):
+    """dsocr_row_params: one row of dsocr_k_select_rows."""
+    _fields_ = [("do_sample", C.c_int), ("temperature", C.c_double), ("top_p", C.c_double), ("top_k", C.c_size_t),
+                ("repetition_penalty", C.c_float), ("no_repeat_ngram_size", C.c_size_t), ("eos_token_id", C.c_int64)]
+
+
+SESSION_PER_REQUEST = 1  # DSOCR_SESSION_PER_REQUEST
+
+
 class DotsTimingsC(C.Structure):
     _fields_ = [("total_ms", C.c_double), ("patch_ms", C.c_double), ("blocks_ms", C.c_double),
                 ("attention_ms", C.c_double), ("merger_ms", C.c_double), ("tokens", C.c_size_t), ("groups", C.c_size_t)]
@@ -107,6 +116,7 @@ EXPORTS = [
     "dsocr_k_prefill_attention",
     "dsocr_session_open", "dsocr_session_admit", "dsocr_session_step", "dsocr_session_poll", "dsocr_session_retire",
     "dsocr_session_close", "dsocr_session_info", "dsocr_k_session_slot_move",
+    "dsocr_session_open_ex", "dsocr_session_admit_params", "dsocr_session_head_steps", "dsocr_k_select_rows",
 ]
 
 # model variants behind the deepseek engine (dsocr_engine_variant)
@@ -214,6 +224,10 @@ def lib():
                                        C.c_uint64, i32, vp]
     L.dsocr_session_open.argtypes = [vp, sz, sz, C.POINTER(DecodeParamsC)]
     L.dsocr_session_admit.argtypes = [vp, C.POINTER(RequestC), sz, i32, C.c_uint64, C.POINTER(i32)]
+    L.dsocr_session_open_ex.argtypes = [vp, sz, sz, C.POINTER(DecodeParamsC), u32]
+    L.dsocr_session_admit_params.argtypes = [vp, C.POINTER(RequestC), C.POINTER(DecodeParamsC), C.POINTER(i32)]
+    L.dsocr_session_head_steps.argtypes = [vp, C.POINTER(sz), C.POINTER(sz)]
+    L.dsocr_k_select_rows.argtypes = [i32, i32, vp, vp, i32, vp, C.POINTER(RowParamsC), C.POINTER(C.c_uint64), i32, vp]
     L.dsocr_session_step.argtypes = [vp, sz, C.POINTER(SlotStatusC), sz, C.POINTER(sz), vp, sz, C.POINTER(sz)]
     L.dsocr_session_poll.argtypes = [vp, C.POINTER(SlotStatusC), sz, C.POINTER(sz), vp, sz, C.POINTER(sz)]
     L.dsocr_session_retire.argtypes = [vp, i32, vp, sz, C.POINTER(sz), C.POINTER(i32)]

@@ -95,6 +95,9 @@ def build_parser() -> argparse.ArgumentParser:
                         "together in a session of N slots (1..8); results print in input order.  0 = off")
     p.add_argument("--max-context", type=int, default=4096,
                    help="with --slots: context rows per slot (a page needs prompt + max_new_tokens + 1)")
+    p.add_argument("--per-request-params", action="store_true",
+                   help="with --slots: open the session per request, every page admitted with its own decode "
+                        "parameters (device-side per-row selection); off by default")
     return p
 
 
@@ -281,9 +284,10 @@ def run_documents(args, engine, tokenizer, prompt: str, out, info) -> int:
         raise DsocrError(1, "--slots needs at least one --image")
     images = [open_image(p) for p in args.images]
     start = time.perf_counter()
+    per_request = bool(getattr(args, "per_request_params", False))
     with BatchScheduler(engine, tokenizer, args.slots, args.max_context, decode_params(args),
-                        vision_settings(args)) as sched:
-        futures = [sched.submit(prompt, [im]) for im in images]
+                        vision_settings(args), per_request_params=per_request) as sched:
+        futures = [sched.submit(prompt, [im], params=decode_params(args) if per_request else None) for im in images]
         outcomes = [f.result() for f in futures]
     elapsed = time.perf_counter() - start
     for path, o in zip(args.images, outcomes):

@@ -19,7 +19,7 @@ from typing import Callable, Optional, Sequence
 import numpy as np
 
 from ._lib import (DTYPES, LOAD_PACKED_EXPERTS, DecodeParamsC, DsocrError, LoadArgs, RequestC, ResultC, STREAM_CB,
-                   SessionDescC, SlotStatusC, TimingsC, VisionSettingsC, check, lib)
+                   SESSION_PER_REQUEST, SessionDescC, SlotStatusC, TimingsC, VisionSettingsC, check, lib)
 
 
 @dataclass
@@ -364,10 +364,12 @@ class DeepseekOcrEngine:
 
     # ------------------------------------------------------------------ decode sessions
     def open_session(self, slots: int, max_context: int, params: DecodeParameters = DecodeParameters(),
-                     ignore_eos: bool = False) -> "Session":
+                     ignore_eos: bool = False, per_request: bool = False) -> "Session":
         """A long-lived batch of `slots` pages (dsocr_session_open): pages are admitted and retired between bursts
-        of decode steps.  `params` are the session's; params.max_new_tokens bounds a request's own."""
-        return Session(self, slots, max_context, params, ignore_eos)
+        of decode steps.  `params` are the session's; params.max_new_tokens bounds a request's own.
+        ``per_request`` (dsocr_session_open_ex, DSOCR_SESSION_PER_REQUEST): `params` are only the defaults and
+        ``Session.admit(..., params=...)`` gives every page its own."""
+        return Session(self, slots, max_context, params, ignore_eos, per_request)
 
     # ------------------------------------------------------------------ OcrEngine::decode
     def decode(self, tokenizer, prompt: str, images: Sequence, vision: VisionSettings,
@@ -403,12 +405,17 @@ class Session:
     [0, active); ``retire`` returns (ids, moved_from): the last active page moves into the freed slot."""
 
     def __init__(self, engine: DeepseekOcrEngine, slots: int, max_context: int, params: DecodeParameters,
-                 ignore_eos: bool = False):
+                 ignore_eos: bool = False, per_request: bool = False):
         self._e = None
         pc = _params_c(params, engine.eos_token_id, ignore_eos)
-        check(lib().dsocr_session_open(engine._h, int(slots), int(max_context), C.byref(pc)))
+        if per_request:
+            check(lib().dsocr_session_open_ex(engine._h, int(slots), int(max_context), C.byref(pc), SESSION_PER_REQUEST))
+        else:
+            check(lib().dsocr_session_open(engine._h, int(slots), int(max_context), C.byref(pc)))
         self._e = engine
         self.params = params
+        self.per_request = bool(per_request)
+        self._eos, self._ignore_eos = engine.eos_token_id, bool(ignore_eos)
         d = self.info()
         self.slots, self.max_context, self.out_cap = d["slots"], d["max_context"], d["out_cap"]
         self.kv_cap, self.burst_cap = d["kv_cap"], d["burst_cap"]
@@ -421,14 +428,31 @@ class Session:
         return {k: int(getattr(d, k)) for k, _ in SessionDescC._fields_}
 
     def admit(self, ids, mask=None, page: Optional[Page] = None, image_rows=None,
-              max_new_tokens: Optional[int] = None, seed: Optional[int] = None) -> int:
+              max_new_tokens: Optional[int] = None, seed: Optional[int] = None,
+              params: Optional[DecodeParameters] = None, eos_token_id: Optional[int] = None,
+              ignore_eos: Optional[bool] = None) -> int:
+        """Without ``params``: the session's parameters with this page's ``max_new_tokens`` / ``seed``
+        (dsocr_session_admit).  With ``params``: the page's whole parameter set (dsocr_session_admit_params; its
+        max_new_tokens and seed count, the two keyword arguments are then not read); ``eos_token_id`` /
+        ``ignore_eos`` default to what the session was opened with."""
         keep = []
         req = self._e._request(ids, mask, page, image_rows, keep)
         slot = C.c_int(-1)
+        if params is not None:
+            pc = _params_c(params, self._eos if eos_token_id is None else int(eos_token_id),
+                           self._ignore_eos if ignore_eos is None else bool(ignore_eos))
+            check(lib().dsocr_session_admit_params(self._e._h, C.byref(req), C.byref(pc), C.byref(slot)))
+            return slot.value
         check(lib().dsocr_session_admit(self._e._h, C.byref(req),
                                         self.out_cap if max_new_tokens is None else int(max_new_tokens),
                                         0 if seed is None else 1, seed or 0, C.byref(slot)))
         return slot.value
+
+    def head_steps(self) -> dict:
+        """Decode steps replayed under each lm_head + selection head since the session opened."""
+        a, b = C.c_size_t(), C.c_size_t()
+        check(lib().dsocr_session_head_steps(self._e._h, C.byref(a), C.byref(b)))
+        return {"screened": int(a.value), "exact": int(b.value)}
 
     def _report(self, ns, nt):
         out, off = [], 0

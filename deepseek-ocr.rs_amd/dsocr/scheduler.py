@@ -7,7 +7,9 @@ yields the first token), step a burst, poll, hand every active request its new t
 
 A request whose parameters differ from the session's in more than ``max_new_tokens`` / ``seed``, or that needs more
 context or output than the session has, waits until the session is empty and then runs alone through
-``engine.decode``.  Requests are served in arrival order: nothing behind such a request is admitted before it ran.
+``engine.decode``.  With ``per_request_params`` the session is opened per request (``open_session(...,
+per_request=True)``) and every request is admitted with its own parameters: only one without ``use_cache``, or one
+that needs more output or context than the session has, still runs alone.  Requests are served in arrival order: nothing behind such a request is admitted before it ran.
 
 The engine object needs ``open_session(slots, max_context, params)`` (admit / step / poll / retire / close, see
 ``dsocr.engine.Session``), ``decode`` and, for prompts with several images, ``image_embeddings``; tests drive the
@@ -68,12 +70,13 @@ def _decode_text(tokenizer, ids) -> str:
 class BatchScheduler:
     def __init__(self, engine, tokenizer, slots: int, max_context: int,
                  defaults: DecodeParameters = DecodeParameters(), vision: Optional[VisionSettings] = None,
-                 prepare: Optional[Callable] = None):
+                 prepare: Optional[Callable] = None, per_request_params: bool = False):
         if not 1 <= int(slots) <= 8:
             raise ValueError("a session has 1..8 slots")
         self.engine, self.tokenizer = engine, tokenizer
         self.slots, self.max_context = int(slots), int(max_context)
         self.defaults = defaults
+        self.per_request_params = bool(per_request_params)
         self.vision = vision or VisionSettings()
         self._prepare = prepare or _default_prepare
         self._queue: deque = deque()
@@ -82,15 +85,17 @@ class BatchScheduler:
         self._cv = threading.Condition()
         self._stop = False
         self.max_active = 0      # most pages the session held at once
+        self.exclusive_runs = 0  # requests that ran alone through engine.decode
         self.bursts: list = []   # (active pages, steps asked) of every burst, for tests and tools
         self._worker = threading.Thread(target=self._run, name="dsocr-scheduler", daemon=True)
         self._worker.start()
 
     # ------------------------------------------------------------------ caller's side
     def compatible(self, params: DecodeParameters, prompt_len: int) -> bool:
-        """True when the request can share the session: only max_new_tokens / seed differ from the defaults."""
+        """True when the request can share the session: only max_new_tokens / seed differ from the defaults (with
+        per_request_params: whatever its selection parameters are)."""
         for f in fields(DecodeParameters):
-            if f.name in ("max_new_tokens", "seed"):
+            if self.per_request_params or f.name in ("max_new_tokens", "seed"):
                 continue
             if getattr(params, f.name) != getattr(self.defaults, f.name):
                 return False
@@ -220,13 +225,20 @@ class BatchScheduler:
     def _admit(self, rq) -> bool:
         try:
             if self._session is None:
-                self._session = self.engine.open_session(self.slots, self.max_context, self.defaults)
+                if self.per_request_params:
+                    self._session = self.engine.open_session(self.slots, self.max_context, self.defaults,
+                                                             per_request=True)
+                else:
+                    self._session = self.engine.open_session(self.slots, self.max_context, self.defaults)
             rows = None
             if rq.pages:
                 import numpy as np
                 rows = np.concatenate(self.engine.image_embeddings(rq.pages), axis=0)
-            slot = self._session.admit(rq.ids, rq.mask, rq.page, rows, max_new_tokens=rq.params.max_new_tokens,
-                                       seed=rq.params.seed)
+            if self.per_request_params:
+                slot = self._session.admit(rq.ids, rq.mask, rq.page, rows, params=rq.params)
+            else:
+                slot = self._session.admit(rq.ids, rq.mask, rq.page, rows, max_new_tokens=rq.params.max_new_tokens,
+                                           seed=rq.params.seed)
         except Exception as e:  # noqa: BLE001 - the request's own error: the running slots are untouched
             rq.future.set_exception(e)
             return False
@@ -270,6 +282,7 @@ class BatchScheduler:
 
     def _run_exclusive(self, rq):
         self._close_session()  # a session and a generate exclude each other on one engine
+        self.exclusive_runs += 1
         try:
             out = self.engine.decode(self.tokenizer, rq.prompt, rq.images, rq.vision, rq.params, rq.on_token)
         except Exception as e:  # noqa: BLE001

@@ -424,14 +424,20 @@ def add_scheduler_args(p):
                    help="decode-session slots (1..8): concurrent requests share one running batch; 0 = off")
     p.add_argument("--max-context", type=int, default=4096,
                    help="context rows per session slot (a request needs prompt + max_new_tokens + 1)")
+    p.add_argument("--per-request-params", action="store_true",
+                   help="with --slots: a request's own temperature / top_p / top_k / repetition_penalty / "
+                        "no_repeat_ngram_size join the running batch (per-row selection on the device) instead of "
+                        "waiting for it to drain; off by default")
 
 
-def make_scheduler(state: ServerState, slots: int, max_context: int):
-    """The state's scheduler for --slots N (None for 0: requests take the lock path)."""
+def make_scheduler(state: ServerState, slots: int, max_context: int, per_request_params: bool = False):
+    """The state's scheduler for --slots N (None for 0: requests take the lock path).  per_request_params: the
+    DecodeParameters merge_decode builds from a request body are admitted into the session as that request's own."""
     if not slots:
         return None
     from .scheduler import BatchScheduler
-    return BatchScheduler(state.engine, state.tokenizer, slots, max_context, state.defaults, state.vision)
+    return BatchScheduler(state.engine, state.tokenizer, slots, max_context, state.defaults, state.vision,
+                          per_request_params=per_request_params)
 
 
 def main(argv=None) -> int:
@@ -456,7 +462,7 @@ def main(argv=None) -> int:
                                       synthetic_seed=args.synthetic_seed))
     state = ServerState(engine, load_tokenizer(args.tokenizer, _vocab_of(config)), args.model,
                         vision_settings(args), decode_params(args))
-    state.scheduler = make_scheduler(state, args.slots, args.max_context)
+    state.scheduler = make_scheduler(state, args.slots, args.max_context, args.per_request_params)
     import uvicorn
     uvicorn.run(create_app(state), host=args.host, port=args.port)
     return 0

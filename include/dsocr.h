@@ -207,11 +207,20 @@ dsocr_status dsocr_generate_trace(dsocr_engine* e, size_t n, const dsocr_request
  * + 1).  Between bursts of decode steps a page is admitted (vision + prefill into its own slot; the other slots'
  * state is untouched) or retired.  Active pages always occupy slots [0, active): retiring slot i < active - 1
  * moves the last active page into slot i (one device launch), which dsocr_session_retire reports in *moved_from.
- * Every page's ids equal dsocr_generate of that page alone with the same parameters and seed.
- *   params are fixed for the session (do_sample, temperature, top_k, top_p, repetition_penalty,
- *   no_repeat_ngram_size, eos_token_id, ignore_eos; use_cache must be non-zero); params->max_new_tokens is the
- *   session's output capacity, the upper bound of a request's own max_new_tokens.  Per request only
- *   max_new_tokens and the seed vary.  Launch spans, the persistent step and the logits trace are off.
+ * Every page's ids equal dsocr_generate of that page alone with that page's parameters and seed, whatever else
+ * is in the batch.
+ *   dsocr_session_open: params are fixed for the session (do_sample, temperature, top_k, top_p,
+ *   repetition_penalty, no_repeat_ngram_size, eos_token_id, ignore_eos; use_cache must be non-zero);
+ *   params->max_new_tokens is the session's output capacity, the upper bound of a request's own max_new_tokens.
+ *   Per request only max_new_tokens and the seed vary.
+ *   dsocr_session_open_ex with DSOCR_SESSION_PER_REQUEST: params are the defaults (dsocr_session_admit uses them)
+ *   and params->max_new_tokens is still the output capacity; dsocr_session_admit_params gives a page its own
+ *   do_sample / temperature / top_k / top_p / repetition_penalty / no_repeat_ngram_size / eos_token_id /
+ *   ignore_eos beside max_new_tokens and the seed.  The parameters live in one device record per slot that the
+ *   selection kernels read per row.  Each burst runs under one lm_head + selection head: the screened one while
+ *   every active page is greedy without a repetition penalty (where a fixed greedy session would use it), else
+ *   the exact one with both the greedy and the sampling selector; dsocr_session_head_steps counts both.
+ *   Launch spans, the persistent step and the logits trace are off.
  *   dsocr_generate / _batch / _trace / dsocr_profile_decode on an engine with an open session are DSOCR_EINVAL,
  *   and so is opening a second session.
  *   A finished page keeps its slot until it is retired, and every step appends one K/V row to every active slot:
@@ -230,10 +239,23 @@ typedef struct {
     size_t steps;      /* decode steps replayed since the session opened */
 } dsocr_session_desc;
 dsocr_status dsocr_session_open(dsocr_engine* e, size_t slots, size_t max_context, const dsocr_decode_params* params);
+/* flags = 0: dsocr_session_open.  Unknown flag bits are DSOCR_EINVAL. */
+#define DSOCR_SESSION_PER_REQUEST 1u
+dsocr_status dsocr_session_open_ex(dsocr_engine* e, size_t slots, size_t max_context, const dsocr_decode_params* params,
+                                   uint32_t flags);
 /* Every check (free slot, context need, prompt/image mismatch, token ids, page variant) happens before any device
  * state changes; on an error the running slots are as they were.  *slot receives the page's slot (= active before). */
 dsocr_status dsocr_session_admit(dsocr_engine* e, const dsocr_request* req, size_t max_new_tokens, int has_seed,
                                  uint64_t seed, int* slot);
+/* dsocr_session_admit with the request's whole parameter set: params->max_new_tokens (1 .. the session's capacity),
+ * has_seed / seed and everything select_token_id reads (use_cache must be non-zero).  On a session opened without
+ * DSOCR_SESSION_PER_REQUEST it is DSOCR_EINVAL when params differ from the session's in more than max_new_tokens
+ * and the seed.  Like dsocr_session_admit, every check runs before any device state changes. */
+dsocr_status dsocr_session_admit_params(dsocr_engine* e, const dsocr_request* req, const dsocr_decode_params* params,
+                                        int* slot);
+/* decode steps replayed under the screened / the exact head since the session opened (either pointer may be NULL;
+ * both session kinds).  DSOCR_EINVAL when no session is open. */
+dsocr_status dsocr_session_head_steps(const dsocr_engine* e, size_t* screened, size_t* exact);
 /* up to k decode steps for the active pages, then one poll.  status [cap_slots >= slots], tokens
  * [cap_tokens >= slots * out_cap]: the new tokens of slot 0, then slot 1, ... (DSOCR_EINVAL if either is short) */
 dsocr_status dsocr_session_step(dsocr_engine* e, size_t k, dsocr_slot_status* status, size_t cap_slots, size_t* n_slots,
@@ -542,6 +564,22 @@ dsocr_status dsocr_k_sample_greedy(int B, int V, float* logits, const int* ctx, 
 dsocr_status dsocr_k_sample_stoch(int B, int V, float* logits, const int* ctx, int ctx_cap, const int* ctx_len,
                                   int ngram, float rep_penalty, double temperature, size_t top_k, double top_p,
                                   uint64_t seed, int draws, int* out_tok);
+/* Selection with per-row parameters, as the exact head of a DSOCR_SESSION_PER_REQUEST session launches it: the
+ * repetition penalty (once, each row its own), then `draws` times the greedy selector, the sampling selector and
+ * the final kernel on the same logits, each row taking the selector its record names, sampled rows' RNG state
+ * (seed_from_u64(seeds[b])) carried over (out_tok [draws][B]).  Row b equals dsocr_k_sample_greedy /
+ * dsocr_k_sample_stoch of that row alone.  rows / seeds: host arrays [B]; the rest device pointers. */
+typedef struct {
+    int do_sample;               /* sampling iff do_sample && temperature > 0 */
+    double temperature;
+    double top_p;
+    size_t top_k;
+    float repetition_penalty;
+    size_t no_repeat_ngram_size;
+    int64_t eos_token_id;        /* < 0: none */
+} dsocr_row_params;
+dsocr_status dsocr_k_select_rows(int B, int V, float* logits, const int* ctx, int ctx_cap, const int* ctx_len,
+                                 const dsocr_row_params* rows, const uint64_t* seeds, int draws, int* out_tok);
 
 /* One page's decode state from slot src to slot dst of a session (src != dst), one launch: K / V rows
  * [0, kv_len[src]) of every layer and kv head of the f32 caches kc / vc [layers][slots][kv_heads][cap][hd]

@@ -5,10 +5,15 @@ Page i generates MAX_NEW[i] tokens: drawn once, numpy default_rng(4011).choice(L
   (a) generate, one page after another (what the server does behind its lock)
   (b) generate_batch in arrival-order groups of 8 (a closed batch runs to its longest page; ids truncated after)
   (c) one 8-slot session fed in arrival order, bursts of 8 steps, finished pages retired at every burst boundary
-The three alternate ROUNDS times; pages/s and decode steps are reported as median [min, max].  Also: the wall time
+  (d) the same session opened per request (DSOCR_SESSION_PER_REQUEST), every request default greedy: it must replay
+      (c)'s launches (zero exact-head steps) and land inside (c)'s min-max spread
+  (e) (d) with every fourth request sampled (T 0.7, top-p 0.9, seeded): the per-row exact head whenever one is active
+  (f) (e)'s traffic through BatchScheduler over a fixed session: a sampled request waits for the session to drain
+      and runs alone (what (e) replaces)
+The arms alternate ROUNDS times; pages/s and decode steps are reported as median [min, max].  Also: the wall time
 of one admission while other slots wait, and one session_slot_move of a 1200-row full-size page against its bytes.
 
-    python tools/session_bench.py [--rounds 3] [--pages 32] [--out profiles/session_bench.json]
+    python tools/session_bench.py [--rounds 3] [--pages 32] [--arms a,b,c,d,e,f] [--out profiles/session_bench.json]
 """
 import argparse
 import ctypes as C
@@ -73,6 +78,70 @@ def run_session(eng, reqs, max_new, P):
     return steps, {"admit_stall_ms": stalls, "retire_with_move_ms": moves}
 
 
+SAMPLED = dict(do_sample=True, temperature=0.7, top_p=0.9)
+
+
+def request_params(i, m, P, mixed):
+    """Request i's own parameters: default greedy, or with `mixed` every fourth one sampled (seed 1000 + i)."""
+    if mixed and i % 4 == 3:
+        return P(max_new_tokens=m, seed=1000 + i, **SAMPLED)
+    return P(max_new_tokens=m)
+
+
+def run_session_params(eng, reqs, max_new, P, mixed):
+    need = max(len(r) + m + 1 for r, m in zip(reqs, max_new))
+    done, nxt = 0, 0
+    with eng.open_session(SLOTS, need, P(max_new_tokens=max(max_new)), ignore_eos=True, per_request=True) as s:
+        active = 0
+        while done < len(reqs):
+            while active < SLOTS and nxt < len(reqs):
+                s.admit(reqs[nxt], params=request_params(nxt, max_new[nxt], P, mixed))
+                active, nxt = active + 1, nxt + 1
+            for st in sorted(s.step(8), key=lambda x: -x.slot):
+                if st.done:
+                    s.retire(st.slot)
+                    active, done = active - 1, done + 1
+        steps, heads = s.info()["steps"], s.head_steps()
+    return steps, {"head_steps": heads}
+
+
+class _SchedEngine:
+    """The engine as BatchScheduler drives it, for prompts "KEY" that name one of the bench's token lists."""
+    variant = 0
+
+    def __init__(self, eng, reqs):
+        self.eng, self.reqs, self.steps = eng, reqs, 0
+
+    def open_session(self, slots, max_context, params):
+        self._s = self.eng.open_session(slots, max_context, params, ignore_eos=True)
+        close = self._s.close
+
+        def closing():
+            self.steps += self._s.info()["steps"]
+            close()
+        self._s.close = closing
+        return self._s
+
+    def decode(self, tokenizer, prompt, images, vision, params, stream=None):
+        from dsocr import DecodeOutcome
+        ids = self.eng.generate(self.reqs[int(prompt)], None, None, None, params, ignore_eos=True)
+        self.steps += self.eng.last_timings()["decode_steps"]
+        return DecodeOutcome("", len(self.reqs[int(prompt)]), len(ids), ids)
+
+
+def run_scheduler_fixed(eng, reqs, max_new, P, mixed=True):
+    from dsocr.scheduler import BatchScheduler
+    need = max(len(r) + m + 1 for r, m in zip(reqs, max_new))
+    se = _SchedEngine(eng, reqs)
+    with BatchScheduler(se, None, SLOTS, need, P(max_new_tokens=max(max_new)),
+                        prepare=lambda e, t, prompt, images, vision: (reqs[int(prompt)], [0] * len(reqs[int(prompt)]), [])) as sc:
+        futs = [sc.submit(str(i), params=request_params(i, m, P, mixed)) for i, m in enumerate(max_new)]
+        outs = [f.result() for f in futs]
+        alone = sc.exclusive_runs
+    assert all(o.response_tokens == m for o, m in zip(outs, max_new))
+    return se.steps, {"exclusive_runs": alone}
+
+
 def slot_move_alone(cfg, rows=1200, reps=10):
     """dsocr_k_session_slot_move at the full-size cache shape, two slots: call wall time (launch + synchronise)."""
     from dsocr._lib import check, lib
@@ -110,6 +179,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--pages", type=int, default=32)
+    ap.add_argument("--arms", default="a,b,c,d,e,f", help="which arms run (letters, comma separated)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     import dsocr
@@ -118,7 +188,11 @@ def main():
     eng = load_model(ModelLoadArgs(config_path=dsocr.FULL_CONFIG, synthetic_seed=0, dtype="f16"))
     max_new = [int(v) for v in np.random.default_rng(4011).choice(LENGTHS, a.pages)]
     reqs = [text_page_prompt(i, vocab=eng.vocab) for i in range(a.pages)]
-    paths = {"a_generate": run_single, "b_generate_batch": run_batches, "c_session": run_session}
+    paths = {"a_generate": run_single, "b_generate_batch": run_batches, "c_session": run_session,
+             "d_session_per_request_greedy": lambda *x: run_session_params(*x, mixed=False),
+             "e_session_per_request_mixed": lambda *x: run_session_params(*x, mixed=True),
+             "f_scheduler_fixed_mixed": run_scheduler_fixed}
+    paths = {k: f for k, f in paths.items() if k[0] in a.arms.split(",")}
     for f in paths.values():  # warm-up: workspaces, fragment-ordered weights, graphs
         f(eng, reqs[:SLOTS], [16] * SLOTS, P)
     res = {k: {"pages_s": [], "steps": [], "extra": []} for k in paths}
@@ -129,15 +203,28 @@ def main():
             res[k]["pages_s"].append(a.pages / (time.perf_counter() - t))
             res[k]["steps"].append(int(steps))
             res[k]["extra"].append(extra)
-    out = {"pages": a.pages, "max_new": max_new, "prompt_len": len(reqs[0]), "rounds": a.rounds}
+    out = {"pages": a.pages, "max_new": max_new, "prompt_len": len(reqs[0]), "rounds": a.rounds,
+           "sampled_requests": {"every_fourth": [i for i in range(a.pages) if i % 4 == 3], "seed": "1000 + index",
+                                "params": SAMPLED}}
     for k, v in res.items():
-        out[k] = {"pages_s": mmm(v["pages_s"]), "steps": mmm(v["steps"])}
-    stalls = [x for e in res["c_session"]["extra"] for x in e["admit_stall_ms"]]
-    moves = [x for e in res["c_session"]["extra"] for x in e["retire_with_move_ms"]]
-    out["c_session"]["admit_stall_ms"] = mmm(stalls) if stalls else None
-    out["c_session"]["retire_with_move_ms"] = mmm(moves) if moves else None
-    out["c_over_a"] = out["c_session"]["pages_s"]["median"] / out["a_generate"]["pages_s"]["median"]
-    out["c_over_b"] = out["c_session"]["pages_s"]["median"] / out["b_generate_batch"]["pages_s"]["median"]
+        out[k] = {"pages_s": mmm(v["pages_s"]), "pages_s_rounds": v["pages_s"], "steps": mmm(v["steps"])}
+        for key in ("head_steps", "exclusive_runs"):
+            if v["extra"] and key in v["extra"][0]:
+                out[k][key] = v["extra"][-1][key]
+    if "c_session" in res:
+        stalls = [x for e in res["c_session"]["extra"] for x in e["admit_stall_ms"]]
+        moves = [x for e in res["c_session"]["extra"] for x in e["retire_with_move_ms"]]
+        out["c_session"]["admit_stall_ms"] = mmm(stalls) if stalls else None
+        out["c_session"]["retire_with_move_ms"] = mmm(moves) if moves else None
+    med = lambda k: out[k]["pages_s"]["median"]  # noqa: E731
+    for name, (x, y) in {"c_over_a": ("c_session", "a_generate"), "c_over_b": ("c_session", "b_generate_batch"),
+                         "d_over_c": ("d_session_per_request_greedy", "c_session"),
+                         "e_over_f": ("e_session_per_request_mixed", "f_scheduler_fixed_mixed")}.items():
+        if x in out and y in out:
+            out[name] = med(x) / med(y)
+    if "d_over_c" in out:
+        c = out["c_session"]["pages_s"]
+        out["d_within_c_spread"] = bool(c["min"] <= med("d_session_per_request_greedy") <= c["max"])
     eng.close()
     out["slot_move_1200_rows"] = slot_move_alone(json.load(open(dsocr.FULL_CONFIG)))
     line = json.dumps(out)
