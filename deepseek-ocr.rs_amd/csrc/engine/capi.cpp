@@ -404,6 +404,42 @@ dsocr_status dsocr_generate_trace(dsocr_engine* e, size_t n, const dsocr_request
     });
 }
 
+dsocr_status dsocr_generate_logprobs(dsocr_engine* e, size_t n, const dsocr_request* reqs,
+                                     const dsocr_decode_params* params, dsocr_result* results, size_t top_k,
+                                     dsocr_logprobs* lp) {
+    return guarded([&] {
+        if (!e || (!reqs && n) || (!results && n) || (!lp && n) || !params) throw std::runtime_error("EINVAL: NULL argument");
+        if (top_k > DSOCR_MAX_TOP_LOGPROBS) throw std::runtime_error("EINVAL: top_k above DSOCR_MAX_TOP_LOGPROBS");
+        if (!params->use_cache) throw std::runtime_error("EINVAL: log-probabilities need use_cache = 1");
+        for (size_t i = 0; i < n; ++i) {
+            if (!lp[i].token_lp || (top_k && (!lp[i].top_id || !lp[i].top_lp))) throw std::runtime_error("EINVAL: NULL log-probability buffer");
+            if (lp[i].cap < (size_t)params->max_new_tokens) throw std::runtime_error("EINVAL: log-probability buffers hold fewer than max_new_tokens entries");
+        }
+        std::vector<dsocr::GenRequest> rq;
+        for (size_t i = 0; i < n; ++i) rq.push_back(to_request(reqs[i]));
+        dsocr::GenParams g = to_params(params);
+        g.lp_k = (int)top_k;
+        auto r = e->impl->generate(rq, g, nullptr, nullptr);
+        const dsocr::Engine::LogprobRows& rows = e->impl->last_logprobs();
+        for (size_t i = 0; i < n; ++i) {
+            results[i].status = DSOCR_OK;
+            size_t m = std::min(r[i].size(), results[i].cap);
+            if (results[i].out_ids) std::memcpy(results[i].out_ids, r[i].data(), m * sizeof(int64_t));
+            results[i].n_out = m;
+            if (m < r[i].size()) results[i].status = DSOCR_EINVAL;
+            const size_t ne = rows.n.empty() ? 0 : (size_t)rows.n[i];
+            lp[i].n = ne;
+            for (size_t t = 0; t < ne; ++t) {
+                lp[i].token_lp[t] = rows.lp[i * rows.cap + t];
+                for (size_t k = 0; k < top_k; ++k) {
+                    lp[i].top_id[t * top_k + k] = rows.top_id[(i * rows.cap + t) * top_k + k];
+                    lp[i].top_lp[t * top_k + k] = rows.top_lp[(i * rows.cap + t) * top_k + k];
+                }
+            }
+        }
+    });
+}
+
 // ---- decode sessions
 dsocr_status dsocr_session_open(dsocr_engine* e, size_t slots, size_t max_context, const dsocr_decode_params* params) {
     return guarded([&] {
@@ -417,9 +453,10 @@ dsocr_status dsocr_session_open_ex(dsocr_engine* e, size_t slots, size_t max_con
                                    uint32_t flags) {
     return guarded([&] {
         if (!e) throw std::runtime_error("EINVAL: NULL argument");
-        if (flags & ~(uint32_t)DSOCR_SESSION_PER_REQUEST) throw std::runtime_error("EINVAL: unknown session flags");
+        if (flags & ~(uint32_t)(DSOCR_SESSION_PER_REQUEST | DSOCR_SESSION_LOGPROBS)) throw std::runtime_error("EINVAL: unknown session flags");
         if (slots > 8 || max_context > (size_t)INT32_MAX / 2) throw std::runtime_error("EINVAL: a session has 1..8 slots");
-        e->impl->session_open((int)slots, (int)max_context, to_params(params), (flags & DSOCR_SESSION_PER_REQUEST) != 0);
+        e->impl->session_open((int)slots, (int)max_context, to_params(params), (flags & DSOCR_SESSION_PER_REQUEST) != 0,
+                                (flags & DSOCR_SESSION_LOGPROBS) != 0);
     });
 }
 
@@ -513,6 +550,16 @@ dsocr_status dsocr_session_info(const dsocr_engine* e, dsocr_session_desc* out) 
         out->slots = (size_t)si.slots; out->active = (size_t)si.active; out->max_context = (size_t)si.max_context;
         out->out_cap = (size_t)si.out_cap; out->kv_cap = (size_t)si.kv_cap; out->burst_cap = (size_t)si.burst_cap;
         out->steps = si.steps;
+        out->flags = (si.per_request ? DSOCR_SESSION_PER_REQUEST : 0u) | (si.logprobs ? DSOCR_SESSION_LOGPROBS : 0u);
+    });
+}
+
+dsocr_status dsocr_session_logprobs(dsocr_engine* e, int slot, size_t first, size_t count, size_t top_k, float* token_lp,
+                                    int64_t* top_id, float* top_lp) {
+    return guarded([&] {
+        if (!e) throw std::runtime_error("EINVAL: NULL argument");
+        if (top_k > DSOCR_MAX_TOP_LOGPROBS) throw std::runtime_error("EINVAL: top_k above DSOCR_MAX_TOP_LOGPROBS");
+        e->impl->session_logprobs(slot, first, count, (int)top_k, token_lp, top_id, top_lp);
     });
 }
 
@@ -1430,6 +1477,97 @@ dsocr_status dsocr_k_sample_greedy(int B, int V, float* logits, const int* ctx, 
         hipError_t e = hipDeviceSynchronize();
         (void)hipFree(ridx); (void)hipFree(rval); (void)hipFree(done);
         check_hip(e, "sample");
+    });
+}
+
+// the two log-probability launches once on host rows; ctx != NULL: the real penalty launch runs between them
+static void k_logprobs(int B, int V, int K, const float* logits, int ld, const int* tok, const uint8_t* emit, float* lp,
+                       int64_t* top_id, float* top_lp, const int* ctx, int ctx_cap, const int* ctx_len, float penalty) {
+    if (B <= 0 || V <= 0 || K < 0 || K > DSOCR_MAX_TOP_LOGPROBS || ld < V || !logits || !tok || !emit || !lp ||
+        (K && (!top_id || !top_lp)) || (ctx && (!ctx_len || ctx_cap <= 0)))
+        throw std::runtime_error("EINVAL: bad log-probability arguments");
+    for (int b = 0; b < B; ++b) {
+        if (tok[b] < 0 || tok[b] >= V) throw std::runtime_error("EINVAL: token id out of bounds for vocab size");
+        if (ctx && (ctx_len[b] < 0 || ctx_len[b] > ctx_cap)) throw std::runtime_error("EINVAL: context length");
+    }
+    std::vector<void*> bufs;
+    auto dalloc = [&](size_t bytes) {
+        void* p = nullptr;
+        check_hip(hipMalloc(&p, bytes ? bytes : 16), "hipMalloc");
+        bufs.push_back(p);
+        return p;
+    };
+    auto up = [&](const void* src, size_t bytes) {
+        void* p = dalloc(bytes);
+        check_hip(hipMemcpy(p, src, bytes, hipMemcpyHostToDevice), "hipMemcpy H2D");
+        return p;
+    };
+    try {
+        const size_t nch = dsocr::dec_lp_chunks(V), kk = (size_t)std::max(K, 1);
+        std::vector<int> grown(B);
+        for (int b = 0; b < B; ++b) grown[b] = emit[b] ? 1 : 0;
+        std::vector<float> h_lp(lp, lp + B), h_tl((size_t)B * kk, 0.f);
+        std::vector<int> h_ti((size_t)B * kk, 0);
+        for (size_t i = 0; i < (size_t)B * K; ++i) { h_ti[i] = (int)top_id[i]; h_tl[i] = top_lp[i]; }
+        dsocr::DecLpArgs a;
+        float* d_logits = (float*)up(logits, sizeof(float) * (size_t)B * ld);
+        a.logits = d_logits; a.B = B; a.V = V; a.ld = ld; a.K = K;
+        a.tok = (const int*)up(tok, sizeof(int) * B);
+        int* d_len = (int*)dalloc(sizeof(int) * B);
+        check_hip(hipMemset(d_len, 0, sizeof(int) * B), "hipMemset");
+        a.out_len = d_len; a.out_cap = 1;
+        if (ctx) {
+            a.ctx = (const int*)up(ctx, sizeof(int) * (size_t)B * ctx_cap);
+            a.ctx_cap = ctx_cap;
+            a.ctx_len = (const int*)up(ctx_len, sizeof(int) * B);
+            a.side = (float*)dalloc(sizeof(float) * (size_t)B * ctx_cap);
+        }
+        a.rec = (int*)dalloc(sizeof(int) * 2 * B);
+        a.part_max = (float*)dalloc(sizeof(float) * B * nch);
+        a.part_sum = (float*)dalloc(sizeof(float) * B * nch);
+        a.part_tv = (float*)dalloc(sizeof(float) * B * nch * kk);
+        a.part_ti = (int*)dalloc(sizeof(int) * B * nch * kk);
+        a.lp = (float*)up(h_lp.data(), sizeof(float) * B);
+        a.top_id = (int*)up(h_ti.data(), sizeof(int) * B * kk);
+        a.top_lp = (float*)up(h_tl.data(), sizeof(float) * B * kk);
+        dsocr::launch_dec_lp_partial(a, nullptr);
+        if (ctx) {
+            dsocr::SampleArgs p;
+            p.logits = d_logits; p.B = B; p.V = V; p.ld = ld; p.ctx = a.ctx; p.ctx_cap = ctx_cap; p.ctx_len = a.ctx_len;
+            p.rep_penalty = penalty;
+            dsocr::launch_rep_penalty(p, nullptr);
+        }
+        // the selection's part: the output length of every emitting row grows by one
+        check_hip(hipMemcpy(d_len, grown.data(), sizeof(int) * B, hipMemcpyHostToDevice), "hipMemcpy H2D");
+        dsocr::launch_dec_lp_final(a, nullptr);
+        check_hip(hipDeviceSynchronize(), "logprobs");
+        check_hip(hipMemcpy(h_lp.data(), a.lp, sizeof(float) * B, hipMemcpyDeviceToHost), "hipMemcpy D2H");
+        check_hip(hipMemcpy(h_ti.data(), a.top_id, sizeof(int) * B * kk, hipMemcpyDeviceToHost), "hipMemcpy D2H");
+        check_hip(hipMemcpy(h_tl.data(), a.top_lp, sizeof(float) * B * kk, hipMemcpyDeviceToHost), "hipMemcpy D2H");
+        // every row back, emitting or not: the device rows started as the caller's values, so a row with emit = 0
+        // shows whatever the final kernel did to it
+        for (int b = 0; b < B; ++b) {
+            lp[b] = h_lp[b];
+            for (int k = 0; k < K; ++k) { top_id[(size_t)b * K + k] = h_ti[(size_t)b * K + k]; top_lp[(size_t)b * K + k] = h_tl[(size_t)b * K + k]; }
+        }
+    } catch (...) {
+        for (void* p : bufs) (void)hipFree(p);
+        throw;
+    }
+    for (void* p : bufs) (void)hipFree(p);
+}
+
+dsocr_status dsocr_k_logprobs(int B, int V, int K, const float* logits, int ld, const int* tok, const uint8_t* emit,
+                              float* lp, int64_t* top_id, float* top_lp) {
+    return guarded([&] { k_logprobs(B, V, K, logits, ld, tok, emit, lp, top_id, top_lp, nullptr, 0, nullptr, 1.f); });
+}
+
+dsocr_status dsocr_k_logprobs_penalty(int B, int V, int K, const float* logits, int ld, const int* tok, const uint8_t* emit,
+                                      const int* ctx, int ctx_cap, const int* ctx_len, float penalty, float* lp,
+                                      int64_t* top_id, float* top_lp) {
+    return guarded([&] {
+        if (!ctx) throw std::runtime_error("EINVAL: NULL context");
+        k_logprobs(B, V, K, logits, ld, tok, emit, lp, top_id, top_lp, ctx, ctx_cap, ctx_len, penalty);
     });
 }
 

@@ -177,6 +177,8 @@ struct Engine::Session {
         *out = nullptr, *tok = nullptr, *ban = nullptr, *stage = nullptr, *err = nullptr;
     uint32_t* rng = nullptr;
     RowParams* rowpar = nullptr;  // s_rowpar[S]: the per-row selection kernels' parameters (per_request)
+    bool logprobs = false;  // every step and admission writes log-probability entries (s_lp*): the exact head at every n
+    bool lp_side = false;   // ... and keeps the raw logits at the context ids (a penalty can apply)
     struct Slot {
         size_t max_new = 0;
         int kv_pos = 0;    // the device kv_pos of the slot: prompt + steps replayed since its admission
@@ -1650,11 +1652,12 @@ bool Engine::screen_applies(int B, float rep_penalty) const {
 // final norm + lm_head + greedy selection + step bookkeeping for the B decode rows in s_x
 // screened: the int8 lm_head + screened final kernel (sa.ban_out holds the ban list the last step left, whichever
 // head wrote it); else the exact lm_head, the penalty and the selection kernels
-void Engine::decode_head(int B, DecSampleArgs& sa, const SampleArgs& pen, bool screened) {
+void Engine::decode_head(int B, DecSampleArgs& sa, const SampleArgs& pen, bool screened, const DecLpArgs* lp) {
     const LangConfig& L = cfg_.lang;
     hipStream_t st = stream_;
     const int H = L.hidden;
     float* SX = wsf("s_x", (size_t)B * H);
+    if (screened && lp) throw std::runtime_error("EINTERNAL: log-probabilities need the exact head");
     if (screened) {
         // screened selection: int8 lm_head intervals + running threshold, exact rescoring of the
         // few kept rows — the exact path's token from half the lm_head bytes
@@ -1681,8 +1684,30 @@ void Engine::decode_head(int B, DecSampleArgs& sa, const SampleArgs& pen, bool s
     }
     launch_dec_gemv(g, st);
     if (trace_) launch_trace_logits(sa.logits, B, L.vocab, sa.ld, sa.out_len, sa.done, trace_, trace_steps_, st);
+    if (lp) launch_dec_lp_partial(*lp, st);
     launch_rep_penalty(pen, st);
     launch_dec_sample(sa, st);
+    if (lp) launch_dec_lp_final(*lp, st);
+}
+
+// log-probability workspaces for `rows` pages (reserved before a step graph is captured), as the arguments of the
+// pages [row0, row0 + sa.B) whose selection sa describes
+DecLpArgs Engine::lp_args(const DecSampleArgs& sa, int rows, int row0, int K, bool side) {
+    const size_t R = (size_t)rows, nch = dec_lp_chunks(sa.V), cap = (size_t)sa.out_cap, kk = (size_t)std::max(K, 1);
+    DecLpArgs a;
+    a.logits = sa.logits; a.B = sa.B; a.V = sa.V; a.ld = sa.ld; a.K = K;
+    a.tok = sa.out_tok; a.out_len = sa.out_len; a.out_cap = sa.out_cap;
+    a.ctx = sa.ctx; a.ctx_cap = sa.ctx_cap; a.ctx_len = sa.ctx_len;
+    a.lp = wsf("s_lp", R * cap) + (size_t)row0 * cap;
+    a.top_lp = wsf("s_lptop", R * cap * kk) + (size_t)row0 * cap * K;
+    a.top_id = wsi("s_lptopid", R * cap * kk) + (size_t)row0 * cap * K;
+    if (side) a.side = wsf("s_lpctx", R * (size_t)sa.ctx_cap) + (size_t)row0 * sa.ctx_cap;
+    a.rec = wsi("s_lprec", R * 2) + (size_t)row0 * 2;
+    a.part_max = wsf("s_lppmax", R * nch) + (size_t)row0 * nch;
+    a.part_sum = wsf("s_lppsum", R * nch) + (size_t)row0 * nch;
+    a.part_tv = wsf("s_lpptv", R * nch * kk) + (size_t)row0 * nch * K;
+    a.part_ti = wsi("s_lppti", R * nch * kk) + (size_t)row0 * nch * K;
+    return a;
 }
 
 // rand_core 0.6.4 SeedableRng::seed_from_u64 for ChaCha12Rng (rand 0.8.5 StdRng): the 32-byte key
@@ -1723,6 +1748,7 @@ struct Engine::GenState {
     int *d_kvpos = nullptr, *d_kvlen = nullptr, *d_done = nullptr, *d_outlen = nullptr, *d_out = nullptr, *d_tok = nullptr;
     SampleArgs pen;
     DecSampleArgs sa;
+    DecLpArgs lp;           // p.lp_k >= 0: the log-probability rows of every page
     PinnedBuffer<int> pin;  // poll(): [done | output length | last token] x B
     int streamed = 0;       // tokens the stream callback has seen
     size_t steps = 0;
@@ -1733,6 +1759,9 @@ std::vector<std::vector<int64_t>> Engine::generate(const std::vector<GenRequest>
     if (sess_) throw std::runtime_error("EINVAL: a decode session is open on this engine (close it before generate)");
     timings_ = Timings();
     timings_.pages = reqs.size();
+    if (p.lp_k > LP_MAX_TOP) throw std::runtime_error("EINVAL: at most 20 alternatives per token (DSOCR_MAX_TOP_LOGPROBS)");
+    if (p.lp_k >= 0 && !p.use_cache) throw std::runtime_error("EINVAL: log-probabilities need the K/V cache (use_cache = 1)");
+    last_lp_ = LogprobRows();
     if (reqs.empty() || p.max_new == 0) return std::vector<std::vector<int64_t>>(reqs.size());
     ensure_small(std::max((int)reqs.size(), 64));
     GenState g(reqs, p, cb, user);
@@ -2072,7 +2101,7 @@ void Engine::init_sampling(GenState& g) {
         sa.rng = reinterpret_cast<uint32_t*>(upload("s_rng", all));
     }
     ensure_mm_weights(B);
-    if (!p.do_sample && !p.trace && screen_applies(B, p.rep_penalty)) {
+    if (!p.do_sample && !p.trace && p.lp_k < 0 && screen_applies(B, p.rep_penalty)) {
         // the screened head reads the n-gram ban list each selection kernel leaves for the next step
         sa.ban_ld = ctx_cap + 1;
         sa.ban_out = wsi("s_ban", (size_t)B * sa.ban_ld);
@@ -2088,6 +2117,11 @@ void Engine::init_sampling(GenState& g) {
         HIP_CHECK(hipMemsetAsync(trace_, 0, sizeof(float) * B * p.max_new * L.vocab, st));
         launch_trace_logits(g.LOGITS, B, L.vocab, L.vocab, g.d_outlen, g.d_done, trace_, trace_steps_, st);
     }
+    // log-probabilities: the exact head (no ban rows above), an entry for the prefill's own selection too
+    if (p.lp_k >= 0) {
+        g.lp = lp_args(sa, B, 0, p.lp_k, rep_penalty_active(p.rep_penalty));
+        launch_dec_lp_partial(g.lp, st);
+    }
     // the fused selection kernel advances the KV position; after the prefill the first
     // decode position must be P, so start one behind
     launch_rep_penalty(pen, st);
@@ -2096,6 +2130,7 @@ void Engine::init_sampling(GenState& g) {
     HIP_CHECK(hipMemcpyAsync(g.d_kvpos, pm1.data(), B * 4, hipMemcpyHostToDevice, st));
     HIP_CHECK(hipMemcpyAsync(g.d_kvlen, lm1.data(), B * 4, hipMemcpyHostToDevice, st));
     launch_dec_sample(sa, st);
+    if (p.lp_k >= 0) launch_dec_lp_final(g.lp, st);
     HIP_CHECK(hipStreamSynchronize(st));
 }
 
@@ -2222,7 +2257,7 @@ void Engine::collect_spans() {
 // one decode step: the layers, the head and the selection (captured once, replayed per token)
 void Engine::step_body(GenState& g) {
     decode_step(g.B, g.Lmax);
-    decode_head(g.B, g.sa, g.pen, g.sa.ban_out != nullptr);
+    decode_head(g.B, g.sa, g.pen, g.sa.ban_out != nullptr, g.p.lp_k >= 0 ? &g.lp : nullptr);
     // chain spans: the step's one fold, after the head (the step counter has advanced: record at count - 1)
     if (chain_active_)
         launch_span_chain_fold(span_chain_, cfg_.lang.layers * SPAN_KINDS_CHAIN, span_chain_rec_, span_step_, span_cap_,
@@ -2326,6 +2361,18 @@ std::vector<std::vector<int64_t>> Engine::collect_outputs(GenState& g) {
     timings_.steps = g.steps;
     if (trace_ && p.trace)
         HIP_CHECK(hipMemcpy(p.trace, trace_, sizeof(float) * B * p.max_new * cfg_.lang.vocab, hipMemcpyDeviceToHost));
+    if (p.lp_k >= 0) {  // the entries, once: a few bytes per token
+        LogprobRows& r = last_lp_;
+        r.K = p.lp_k; r.cap = p.max_new; r.n = h_outlen;
+        r.lp.resize((size_t)B * r.cap);
+        HIP_CHECK(hipMemcpy(r.lp.data(), g.lp.lp, r.lp.size() * 4, hipMemcpyDeviceToHost));
+        r.top_id.resize((size_t)B * r.cap * r.K);
+        r.top_lp.resize(r.top_id.size());
+        if (!r.top_id.empty()) {
+            HIP_CHECK(hipMemcpy(r.top_id.data(), g.lp.top_id, r.top_id.size() * 4, hipMemcpyDeviceToHost));
+            HIP_CHECK(hipMemcpy(r.top_lp.data(), g.lp.top_lp, r.top_lp.size() * 4, hipMemcpyDeviceToHost));
+        }
+    }
     last_B_ = B;
     last_Lmax_ = g.Lmax;
     return out;
@@ -2351,7 +2398,7 @@ static RowParams resolve_row_params(const GenParams& p) {
     return r;
 }
 
-void Engine::session_open(int S, int max_context, const GenParams& p, bool per_request) {
+void Engine::session_open(int S, int max_context, const GenParams& p, bool per_request, bool logprobs) {
     if (sess_) throw std::runtime_error("EINVAL: a decode session is already open on this engine");
     if (S < 1 || S > 8) throw std::runtime_error("EINVAL: a session has 1..8 slots");
     if (!p.use_cache || p.trace) throw std::runtime_error("EINVAL: a session decodes with the K/V cache and without a logits trace");
@@ -2366,6 +2413,7 @@ void Engine::session_open(int S, int max_context, const GenParams& p, bool per_r
     auto sp = std::make_unique<Session>();
     Session& s = *sp;
     s.S = S; s.max_context = max_context; s.p = p; s.per_request = per_request;
+    s.logprobs = logprobs; s.lp_side = logprobs && (per_request || rep_penalty_active(p.rep_penalty));
     // Capacity invariant.  The selection kernels advance kv_pos of every row on every step, done or not, so a
     // finished page that waits for the end of its burst keeps appending K/V rows.  A page is admitted only with
     // prompt + max_new + 1 <= max_context and produces its last token at kv_pos <= prompt + max_new - 1; it is
@@ -2442,7 +2490,7 @@ void Engine::session_open(int S, int max_context, const GenParams& p, bool per_r
         }
         s.stage = wsi("ss_stage", (size_t)SS_HEAD + RNG_WORDS + s.ctx_cap);
         ensure_mm_weights(S);
-        s.screened = !p.do_sample && !per_request;
+        s.screened = !p.do_sample && !per_request && !logprobs;
         for (int n = 1; n <= S; ++n) s.screened = s.screened && screen_applies(n, p.rep_penalty);
         if (s.screened || per_request) {
             // (per request the ban rows are always kept and both final kernels write them every step: either head
@@ -2453,6 +2501,17 @@ void Engine::session_open(int S, int max_context, const GenParams& p, bool per_r
         // every workspace the decode step asks for by name, at every n: a dry step per n allocates them (it
         // appends K/V row 0 of the empty slots, which an admission's prefill rewrites)
         if ((s.screened || per_request) && getenv("DSOCR_SCREEN_STATS")) zeroed("s_scrstats", 32);
+        if (logprobs) {  // the rows of every slot, before the freeze below (an admission resets its slot's)
+            DecSampleArgs sa;
+            SampleArgs pen;
+            session_sample_args(s, S, 0, sa, pen);
+            const DecLpArgs a = session_lp_args(s, sa, 0);
+            HIP_CHECK(hipMemsetAsync(a.rec, 0, sizeof(int) * 2 * S, st));
+            HIP_CHECK(hipMemsetAsync(a.lp, 0, sizeof(float) * S * s.out_cap, st));
+            HIP_CHECK(hipMemsetAsync(a.top_id, 0, sizeof(int) * S * s.out_cap * LP_MAX_TOP, st));
+            HIP_CHECK(hipMemsetAsync(a.top_lp, 0, sizeof(float) * S * s.out_cap * LP_MAX_TOP, st));
+            if (a.side) HIP_CHECK(hipMemsetAsync(a.side, 0, sizeof(float) * S * s.ctx_cap, st));
+        }
         for (int n = 1; n <= S; ++n) {
             session_sentinels(s);
             decode_step(n, s.Lcap);
@@ -2514,6 +2573,10 @@ void Engine::session_sample_args(const Session& s, int B, int slot0, DecSampleAr
         sa.rng = s.rng + (size_t)slot0 * RNG_WORDS;
     }
     if (s.ban) { sa.ban_ld = s.ban_ld; sa.ban_out = s.ban + (size_t)slot0 * s.ban_ld; }
+}
+
+DecLpArgs Engine::session_lp_args(const Session& s, const DecSampleArgs& sa, int slot0) {
+    return lp_args(sa, s.S, slot0, LP_MAX_TOP, s.lp_side);
 }
 
 int Engine::session_admit(const GenRequest& rq, size_t max_new, bool seed_set, uint64_t seed) {
@@ -2601,12 +2664,20 @@ int Engine::session_admit(const GenRequest& rq, const GenParams& rp) {
     ia.kv_pos = s.kvpos; ia.kv_len = s.kvlen; ia.done = s.done; ia.out_len = s.outlen; ia.tok = s.tok;
     ia.rng = s.rng; ia.rng_words = RNG_WORDS; ia.ban = s.ban; ia.ban_ld = s.ban_ld;
     if (s.per_request) ia.rowpar = s.rowpar;
-    launch_session_slot_init(ia, st);
     DecSampleArgs sa;
     SampleArgs pen;
     session_sample_args(s, 1, slot, sa, pen);
+    DecLpArgs lp;
+    if (s.logprobs) {
+        lp = session_lp_args(s, sa, 0);  // (slot init takes the rows' bases)
+        ia.lp = lp.lp; ia.lp_top_id = lp.top_id; ia.lp_top = lp.top_lp; ia.lp_k = lp.K; ia.out_cap = s.out_cap;
+        lp = session_lp_args(s, sa, slot);
+    }
+    launch_session_slot_init(ia, st);
+    if (s.logprobs) launch_dec_lp_partial(lp, st);
     launch_rep_penalty(pen, st);
     launch_dec_sample(sa, st);  // the first token, its embedding into the slot's s_x row, the ban list
+    if (s.logprobs) launch_dec_lp_final(lp, st);  // entry 0 of the slot
     session_sentinels(s);
     HIP_CHECK(hipStreamSynchronize(st));
     s.slot[slot] = Session::Slot{max_new, (int)P, 0, row};
@@ -2619,13 +2690,19 @@ void Engine::session_step_body(Session& s, bool screened) {
     SampleArgs pen;
     session_sample_args(s, s.n, 0, sa, pen);
     decode_step(s.n, s.Lcap);
-    decode_head(s.n, sa, pen, screened);
+    if (s.logprobs) {
+        const DecLpArgs lp = session_lp_args(s, sa, 0);
+        decode_head(s.n, sa, pen, screened, &lp);
+    } else {
+        decode_head(s.n, sa, pen, screened);
+    }
 }
 
 // the head of the next burst.  Fixed parameters: decided at session_open.  Per request: screened iff every active
 // slot is greedy with penalty 1.0 and the screened head applies at this n; it changes only where the set of
 // active slots does (admit, retire), and the ban rows both final kernels keep make the change a step boundary
 bool Engine::session_head_screened(const Session& s) const {
+    if (s.logprobs) return false;  // the screened head never forms the logits
     if (!s.per_request) return s.screened;
     for (int b = 0; b < s.n; ++b)
         if (s.slot[b].rp.do_sample || s.slot[b].rp.rep_penalty != 1.0f) return false;
@@ -2715,6 +2792,13 @@ std::vector<int64_t> Engine::session_retire(int slot, int* moved_from) {
         m.out = s.out; m.out_cap = s.out_cap; m.out_len = s.outlen; m.done = s.done; m.tok = s.tok;
         m.rng = s.rng; m.rng_words = RNG_WORDS; m.ban = s.ban; m.ban_ld = s.ban_ld; m.x = s.sx; m.H = L.hidden;
         if (s.per_request) m.rowpar = s.rowpar;
+        if (s.logprobs) {
+            DecSampleArgs sa;
+            SampleArgs pen;
+            session_sample_args(s, s.n, 0, sa, pen);
+            const DecLpArgs lp = session_lp_args(s, sa, 0);
+            m.lp = lp.lp; m.lp_top_id = lp.top_id; m.lp_top = lp.top_lp; m.lp_k = lp.K;
+        }
         launch_session_slot_move(m, st);
         s.slot[slot] = s.slot[last];
         if (moved_from) *moved_from = last;
@@ -2723,6 +2807,38 @@ std::vector<int64_t> Engine::session_retire(int slot, int* moved_from) {
     session_sentinels(s);
     HIP_CHECK(hipStreamSynchronize(st));
     return std::vector<int64_t>(ids.begin(), ids.end());
+}
+
+void Engine::session_logprobs(int slot, size_t first, size_t count, int top_k, float* token_lp, int64_t* top_id,
+                              float* top_lp) {
+    Session& s = open_session();
+    if (!s.logprobs) throw std::runtime_error("EINVAL: this session was opened without DSOCR_SESSION_LOGPROBS");
+    if (slot < 0 || slot >= s.n) throw std::runtime_error("EINVAL: slot " + std::to_string(slot) + " is not active");
+    if (top_k < 0 || top_k > LP_MAX_TOP) throw std::runtime_error("EINVAL: top_k must be 0..20");
+    if (count && (!token_lp || (top_k && (!top_id || !top_lp)))) throw std::runtime_error("EINVAL: NULL argument");
+    HIP_CHECK(hipStreamSynchronize(stream_));
+    int len = 0;
+    HIP_CHECK(hipMemcpy(&len, s.outlen + slot, 4, hipMemcpyDeviceToHost));
+    len = std::min(len, (int)s.slot[slot].max_new);
+    if (first > (size_t)len || count > (size_t)len - first)
+        throw std::runtime_error("EINVAL: entries [" + std::to_string(first) + ", " + std::to_string(first + count) +
+                                 ") pass the slot's " + std::to_string(len) + " tokens");
+    if (!count) return;
+    DecSampleArgs sa;
+    SampleArgs pen;
+    session_sample_args(s, 1, slot, sa, pen);
+    const DecLpArgs lp = session_lp_args(s, sa, slot);
+    HIP_CHECK(hipMemcpy(token_lp, lp.lp + first, count * 4, hipMemcpyDeviceToHost));
+    if (!top_k) return;
+    std::vector<int> ids(count * LP_MAX_TOP);
+    std::vector<float> lps(count * LP_MAX_TOP);
+    HIP_CHECK(hipMemcpy(ids.data(), lp.top_id + first * LP_MAX_TOP, ids.size() * 4, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(lps.data(), lp.top_lp + first * LP_MAX_TOP, lps.size() * 4, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < count; ++i)
+        for (int k = 0; k < top_k; ++k) {
+            top_id[i * top_k + k] = ids[i * LP_MAX_TOP + k];
+            top_lp[i * top_k + k] = lps[i * LP_MAX_TOP + k];
+        }
 }
 
 void Engine::session_close() {
@@ -2745,6 +2861,7 @@ bool Engine::session_info(SessionInfo* out) const {
         out->steps = sess_->steps;
         out->steps_screened = sess_->head_steps[1]; out->steps_exact = sess_->head_steps[0];
         out->per_request = sess_->per_request;
+        out->logprobs = sess_->logprobs;
     }
     return true;
 }

@@ -149,6 +149,7 @@ struct GenParams {
     uint64_t seed = 0;
     bool use_cache = true;  // false: generate_without_cache (model/mod.rs:2051-2283)
     float* trace = nullptr; // host [B][max_new][vocab]: raw logits of every step (parity hook)
+    int lp_k = -1;          // >= 0: per-token log-probabilities with lp_k alternatives (0..LP_MAX_TOP); the exact head runs
 };
 typedef void (*TokenCb)(size_t, const int64_t*, void*);
 // rand_core seed_from_u64 for rand 0.8.5 StdRng, in the layout sampling.hip reads (RNG_WORDS words)
@@ -170,6 +171,16 @@ class Engine {
     std::vector<std::vector<int64_t>> generate(const std::vector<GenRequest>& reqs, const GenParams& p, TokenCb cb,
                                                void* user);
     Timings last_timings() const { return timings_; }
+    // the log-probability entries of the last generate with p.lp_k >= 0: per page n[b] entries (one per emitted id,
+    // same index) of rows [b][cap]: lp, and [b][cap][K]: top_id / top_lp
+    struct LogprobRows {
+        int K = 0;
+        size_t cap = 0;
+        std::vector<int> n;
+        std::vector<float> lp, top_lp;
+        std::vector<int> top_id;
+    };
+    const LogprobRows& last_logprobs() const { return last_lp_; }
     // Replays the decode MoE grouped GEMV (routed experts, gate/up + down) of every MoE
     // layer on the last decode step's routing, timing each launch pair with HIP events.
     struct KernelProfile {
@@ -222,6 +233,7 @@ class Engine {
         size_t steps = 0;  // decode steps replayed since the session opened
         size_t steps_screened = 0, steps_exact = 0;  // ... under the screened / the exact lm_head + selection
         bool per_request = false;
+        bool logprobs = false;
     };
     struct SlotStatus {
         int slot = 0, done = 0, out_len = 0;
@@ -231,7 +243,10 @@ class Engine {
     // per_request: p are the defaults and every admission brings its own selection parameters (a RowParams record
     // per slot, read by the per-row selection kernels); the head is chosen per burst: screened while every active
     // slot is greedy without a penalty, else the exact head with both selectors
-    void session_open(int slots, int max_context, const GenParams& p, bool per_request = false);
+    // logprobs: every slot keeps out_cap x LP_MAX_TOP log-probability entries; the exact head runs at every n
+    void session_open(int slots, int max_context, const GenParams& p, bool per_request = false, bool logprobs = false);
+    // entries [first, first + count) of a live slot, trimmed to top_k <= LP_MAX_TOP alternatives ([count][top_k])
+    void session_logprobs(int slot, size_t first, size_t count, int top_k, float* token_lp, int64_t* top_id, float* top_lp);
     int session_admit(const GenRequest& rq, size_t max_new, bool seed_set, uint64_t seed);
     // the request's whole parameter set (max_new, seed and what select_token_id reads).  Without per_request:
     // EINVAL when it differs from the session's in more than max_new / seed
@@ -284,7 +299,7 @@ class Engine {
     void ensure_persist();
     MoeDecodeArgs moe_args(int l, int B, float* X);
     DecAttn2Args attn_args(int l, int B, int Lmax);
-    void decode_head(int B, DecSampleArgs& sa, const SampleArgs& pen, bool screened);
+    void decode_head(int B, DecSampleArgs& sa, const SampleArgs& pen, bool screened, const DecLpArgs* lp = nullptr);
     void reserve_head_ws(int B);
     LmHeadQ8Args head_q8_args(int B);
     bool screen_applies(int B, float rep_penalty) const;
@@ -309,6 +324,9 @@ class Engine {
     std::unique_ptr<Session> sess_;
     Session& open_session();
     void session_sample_args(const Session& s, int B, int slot0, DecSampleArgs& sa, SampleArgs& pen);
+    DecLpArgs session_lp_args(const Session& s, const DecSampleArgs& sa, int slot0);
+    // the log-probability workspaces (s_lp*) of `rows` pages, pointed at the pages from row0 on that sa selects for
+    DecLpArgs lp_args(const DecSampleArgs& sa, int rows, int row0, int K, bool side);
     void session_sentinels(const Session& s);
     void session_step_body(Session& s, bool screened);
     bool session_head_screened(const Session& s) const;
@@ -376,6 +394,7 @@ class Engine {
     std::map<std::pair<int, int>, std::pair<int*, int*>> winmaps_;  // (n, grid) -> tok2win, win2tok
     int last_Lmax_ = 0;
     float* trace_ = nullptr;  // device logits trace of the running generate (parity hook)
+    LogprobRows last_lp_;
     int span_mode_ = 0;
     // profile_decode: launches decode_step leaves out (the with / without step-graph differences)
     enum StepSkip : int { SKIP_GATEUP = 1, SKIP_DOWN = 2, SKIP_ATTN = 4 };

@@ -582,6 +582,29 @@ constexpr int RNG_KEY = 0, RNG_CTR = 8, RNG_IDX = 10, RNG_BUF = 16, RNG_WORDS = 
 void launch_dec_sample(const DecSampleArgs& a, hipStream_t s);
 void launch_dec_stoch_select(const DecSampleArgs& a, hipStream_t s);
 size_t dec_sample_blocks(int V);
+// Per-token log-probabilities (decode_logprob.hip): for every row whose selection emits an id, the entry at that
+// id's index in the output row: lp[b][i] = l[tok] - m - log sum exp(l - m) over the finite raw logits, and the K
+// largest raw logits (descending, lower id first on ties) with their log-probabilities; (-1, -inf) past the last
+// finite one.  launch_dec_lp_partial runs on the raw logits, before launch_rep_penalty: per chunk of the row the
+// maximum, the sum and the top K, plus out_len / ctx_len as they are before the selection (rec) and, when side is
+// set, the raw logits at the row's context ids (the only entries the penalty rewrites).  launch_dec_lp_final runs
+// after launch_dec_sample: merges the chunks in index order and writes the entry iff out_len grew.
+constexpr int LP_MAX_TOP = 20;
+struct DecLpArgs {
+    const float* logits = nullptr; int B = 0, V = 0; long ld = 0;
+    int K = 0;                                     // alternatives per entry (the row stride of top_id / top_lp)
+    const int* tok = nullptr; const int* out_len = nullptr; long out_cap = 0;
+    const int* ctx = nullptr; long ctx_cap = 0; const int* ctx_len = nullptr;
+    float* side = nullptr;                         // [B][ctx_cap] raw logits at the context ids (null: no penalty can apply)
+    int* rec = nullptr;                            // [B][2] out_len, ctx_len before the selection
+    float* part_max = nullptr; float* part_sum = nullptr;  // [B][chunks]
+    float* part_tv = nullptr; int* part_ti = nullptr;      // [B][chunks][K]
+    float* lp = nullptr;                           // [B][out_cap]
+    int* top_id = nullptr; float* top_lp = nullptr;        // [B][out_cap][K]
+};
+size_t dec_lp_chunks(int V);
+void launch_dec_lp_partial(const DecLpArgs& a, hipStream_t s);
+void launch_dec_lp_final(const DecLpArgs& a, hipStream_t s);
 // Decode sessions (session.hip).  One page's decode state from slot src to slot dst (src != dst) in one launch:
 // K / V rows [0, min(kv_len[src], rows_bound)) of every layer and kv head (f32 caches [layers][slots][kv_heads]
 // [cap_rows][hd] with the given strides in floats; 16-byte nontemporal loads and stores, hd % 4 == 0), the whole
@@ -600,6 +623,8 @@ struct SlotMoveArgs {
     int* ban = nullptr; long ban_ld = 0;
     float* x = nullptr; int H = 0;
     RowParams* rowpar = nullptr;  // [slots] per-row selection parameters
+    // log-probability rows (DecLpArgs lp / top_id / top_lp, lp_k alternatives per entry): entries [0, out_len[src])
+    float* lp = nullptr; int* lp_top_id = nullptr; float* lp_top = nullptr; int lp_k = 0;
 };
 void launch_session_slot_move(const SlotMoveArgs& a, hipStream_t s);
 // A new slot's rows from one staged device buffer [SS_HEAD header ints | rng_words words | ctx_len ids]: the context
@@ -616,6 +641,8 @@ struct SlotInitArgs {
     uint32_t* rng = nullptr; int rng_words = 0;
     int* ban = nullptr; long ban_ld = 0;
     RowParams* rowpar = nullptr;  // [slots] (optional)
+    // log-probability rows (optional): the slot's out_cap entries reset to (-inf, id -1)
+    float* lp = nullptr; int* lp_top_id = nullptr; float* lp_top = nullptr; int lp_k = 0; long out_cap = 0;
 };
 void launch_session_slot_init(const SlotInitArgs& a, hipStream_t s);
 // Screened lm_head (lmhead.hip): int8 rows + per-row scale / error bound give every row an

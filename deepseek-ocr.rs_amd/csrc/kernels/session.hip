@@ -54,6 +54,14 @@ __global__ __launch_bounds__(SM_BLOCK) void session_slot_move_kernel(SlotMoveArg
         for (int i = t; i < a.H; i += SM_BLOCK) a.x[(long)d * a.H + i] = a.x[(long)s * a.H + i];
     if (a.rowpar && t < ROWPAR_INTS)
         reinterpret_cast<int*>(a.rowpar + d)[t] = reinterpret_cast<const int*>(a.rowpar + s)[t];
+    if (a.lp && a.out_len) {
+        const long n = min((long)a.out_len[s], a.out_cap), so = (long)s * a.out_cap, dof = (long)d * a.out_cap;
+        for (long i = t; i < n; i += SM_BLOCK) a.lp[dof + i] = a.lp[so + i];
+        for (long i = t; i < n * a.lp_k; i += SM_BLOCK) {
+            a.lp_top_id[dof * a.lp_k + i] = a.lp_top_id[so * a.lp_k + i];
+            a.lp_top[dof * a.lp_k + i] = a.lp_top[so * a.lp_k + i];
+        }
+    }
     if (t == 0) {
         a.kv_len[d] = a.kv_len[s];
         if (a.kv_pos) a.kv_pos[d] = a.kv_pos[s];
@@ -75,6 +83,8 @@ void launch_session_slot_move(const SlotMoveArgs& a, hipStream_t s) {
         throw std::runtime_error("EINVAL: slot move strides do not hold the cache shape (or break 16-byte alignment)");
     if ((reinterpret_cast<uintptr_t>(a.kc) | reinterpret_cast<uintptr_t>(a.vc)) & 15)
         throw std::runtime_error("EINVAL: slot move needs 16-byte aligned caches");
+    if (a.lp && (!a.out_len || a.out_cap <= 0 || a.lp_k < 0 || (a.lp_k && (!a.lp_top_id || !a.lp_top))))
+        throw std::runtime_error("EINVAL: slot move log-probability rows");
     const int rows = a.rows_bound > 0 ? (a.rows_bound < a.cap_rows ? a.rows_bound : a.cap_rows) : a.cap_rows;
     const long n16 = (long)rows * a.hd / 4;
     const int per = SM_BLOCK * SM_VEC;
@@ -91,6 +101,14 @@ __global__ __launch_bounds__(SM_BLOCK) void session_slot_init_kernel(SlotInitArg
     const long i = (long)blockIdx.x * SM_BLOCK + threadIdx.x;
     const int n = h[SS_CTX_LEN];
     if (i < a.ctx_cap) a.ctx[(long)d * a.ctx_cap + i] = i < n ? h[SS_HEAD + a.rng_words + i] : 0;
+    if (a.lp) {
+        const long base = (long)d * a.out_cap, step = (long)gridDim.x * SM_BLOCK;
+        for (long j = i; j < a.out_cap; j += step) a.lp[base + j] = -INFINITY;
+        for (long j = i; j < a.out_cap * a.lp_k; j += step) {
+            a.lp_top_id[base * a.lp_k + j] = -1;
+            a.lp_top[base * a.lp_k + j] = -INFINITY;
+        }
+    }
     if (blockIdx.x) return;
     if (a.rng && (int)threadIdx.x < a.rng_words) a.rng[(long)d * a.rng_words + threadIdx.x] = (uint32_t)h[SS_HEAD + threadIdx.x];
     if (a.rowpar && (int)threadIdx.x < ROWPAR_INTS) reinterpret_cast<int*>(a.rowpar + d)[threadIdx.x] = h[SS_ROWPAR + threadIdx.x];
@@ -109,6 +127,8 @@ void launch_session_slot_init(const SlotInitArgs& a, hipStream_t s) {
     if (!a.stage || !a.ctx || !a.ctx_len || !a.kv_pos || !a.kv_len || !a.done || !a.out_len || !a.tok || a.slot < 0 ||
         a.ctx_cap <= 0 || a.rng_words < 0 || a.rng_words > SM_BLOCK)
         throw std::runtime_error("EINVAL: slot init arguments");
+    if (a.lp && (a.out_cap <= 0 || a.lp_k < 0 || (a.lp_k && (!a.lp_top_id || !a.lp_top))))
+        throw std::runtime_error("EINVAL: slot init log-probability rows");
     const int blocks = (int)((a.ctx_cap + SM_BLOCK - 1) / SM_BLOCK);
     DSOCR_LAUNCH(session_slot_init_kernel, dim3(blocks), dim3(SM_BLOCK), 0, s, a);
 }

@@ -74,7 +74,13 @@ class SlotStatusC(C.Structure):
 
 class SessionDescC(C.Structure):
     _fields_ = [("slots", C.c_size_t), ("active", C.c_size_t), ("max_context", C.c_size_t), ("out_cap", C.c_size_t),
-                ("kv_cap", C.c_size_t), ("burst_cap", C.c_size_t), ("steps", C.c_size_t)]
+                ("kv_cap", C.c_size_t), ("burst_cap", C.c_size_t), ("steps", C.c_size_t), ("flags", C.c_size_t)]
+
+
+class LogprobsC(C.Structure):
+    """dsocr_logprobs: one page's caller buffers of dsocr_generate_logprobs."""
+    _fields_ = [("token_lp", C.POINTER(C.c_float)), ("top_id", C.POINTER(C.c_int64)), ("top_lp", C.POINTER(C.c_float)),
+                ("cap", C.c_size_t), ("n", C.c_size_t)]
 
 
 class RowParamsC(C.Structure):
@@ -84,6 +90,8 @@ class RowParamsC(C.Structure):
 
 
 SESSION_PER_REQUEST = 1  # DSOCR_SESSION_PER_REQUEST
+SESSION_LOGPROBS = 2     # DSOCR_SESSION_LOGPROBS
+MAX_TOP_LOGPROBS = 20    # DSOCR_MAX_TOP_LOGPROBS
 
 
 class DotsTimingsC(C.Structure):
@@ -117,6 +125,7 @@ EXPORTS = [
     "dsocr_session_open", "dsocr_session_admit", "dsocr_session_step", "dsocr_session_poll", "dsocr_session_retire",
     "dsocr_session_close", "dsocr_session_info", "dsocr_k_session_slot_move",
     "dsocr_session_open_ex", "dsocr_session_admit_params", "dsocr_session_head_steps", "dsocr_k_select_rows",
+    "dsocr_generate_logprobs", "dsocr_session_logprobs", "dsocr_k_logprobs", "dsocr_k_logprobs_penalty",
 ]
 
 # model variants behind the deepseek engine (dsocr_engine_variant)
@@ -233,6 +242,11 @@ def lib():
     L.dsocr_session_retire.argtypes = [vp, i32, vp, sz, C.POINTER(sz), C.POINTER(i32)]
     L.dsocr_session_close.argtypes = [vp]
     L.dsocr_session_info.argtypes = [vp, C.POINTER(SessionDescC)]
+    L.dsocr_generate_logprobs.argtypes = [vp, sz, C.POINTER(RequestC), C.POINTER(DecodeParamsC), C.POINTER(ResultC), sz,
+                                          C.POINTER(LogprobsC)]
+    L.dsocr_session_logprobs.argtypes = [vp, i32, sz, sz, sz, vp, vp, vp]
+    L.dsocr_k_logprobs.argtypes = [i32, i32, i32, vp, i32, vp, vp, vp, vp, vp]
+    L.dsocr_k_logprobs_penalty.argtypes = [i32, i32, i32, vp, i32, vp, vp, vp, i32, vp, f32, vp, vp, vp]
     L.dsocr_k_session_slot_move.argtypes = [i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, C.c_longlong, vp, vp,
                                             C.c_longlong, vp, vp, vp, vp, i32, vp, C.c_longlong, vp, i32, i32, i32]
     _lib = L

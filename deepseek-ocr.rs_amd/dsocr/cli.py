@@ -90,6 +90,9 @@ def build_parser() -> argparse.ArgumentParser:
     b.add_argument("--bench", action="store_true", help="print per-stage timings")
     b.add_argument("--bench-output", metavar="PATH", help="write benchmark events to a JSON file")
     p.add_argument("-q", "--quiet", action="store_true", help="print only the final result")
+    p.add_argument("--logprobs", type=int, default=None, metavar="K",
+                   help="after the text, one JSON line per generated token: its id, its log-probability and the K "
+                        "(0..20) most likely alternatives")
     p.add_argument("--slots", type=int, default=0, metavar="N",
                    help="treat every --image as its own one-page document (the prompt has one <image>) and decode them "
                         "together in a session of N slots (1..8); results print in input order.  0 = off")
@@ -231,7 +234,13 @@ def run_inference(args, out=sys.stdout, err=sys.stderr) -> int:
                 out.flush()
 
         info(f"Starting generation with requested budget {params.max_new_tokens} tokens")
-        outcome = engine.decode(tokenizer, prompt, images, vision, params, None if args.quiet else on_token)
+        lp_k = getattr(args, "logprobs", None)
+        if lp_k is not None and not 0 <= lp_k <= 20:
+            raise DsocrError(1, "--logprobs takes 0..20")
+        if lp_k is None:
+            outcome = engine.decode(tokenizer, prompt, images, vision, params, None if args.quiet else on_token)
+        else:  # the entries arrive with the ids: the text is written once, below
+            outcome = engine.decode(tokenizer, prompt, images, vision, params, None, logprobs=lp_k)
         elapsed = time.perf_counter() - start
         decoded = decode_ids(tokenizer, outcome.generated_tokens)
         if args.quiet:
@@ -243,6 +252,12 @@ def run_inference(args, out=sys.stdout, err=sys.stderr) -> int:
             out.write("\n")
             out.flush()
             info(f"Final output:\n{outcome.text}")
+        if lp_k is not None:
+            for tok, lp, top in zip(outcome.generated_tokens, outcome.token_logprobs, outcome.top_logprobs):
+                out.write(json.dumps({"id": int(tok), "logprob": lp if lp > float("-inf") else -9999.0,
+                                      "top_logprobs": [{"id": int(i), "logprob": v if v > float("-inf") else -9999.0}
+                                                       for i, v in top if i >= 0]}) + "\n")
+            out.flush()
         prefill_s = state["prefill_s"] if state["prefill_s"] is not None and state["prefill_s"] <= elapsed \
             else elapsed
         decode_s = max(elapsed - prefill_s, 0.0)

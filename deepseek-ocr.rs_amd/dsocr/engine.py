@@ -18,8 +18,9 @@ from typing import Callable, Optional, Sequence
 
 import numpy as np
 
-from ._lib import (DTYPES, LOAD_PACKED_EXPERTS, DecodeParamsC, DsocrError, LoadArgs, RequestC, ResultC, STREAM_CB,
-                   SESSION_PER_REQUEST, SessionDescC, SlotStatusC, TimingsC, VisionSettingsC, check, lib)
+from ._lib import (DTYPES, LOAD_PACKED_EXPERTS, MAX_TOP_LOGPROBS, DecodeParamsC, DsocrError, LoadArgs, LogprobsC, RequestC,
+                   ResultC, STREAM_CB, SESSION_LOGPROBS, SESSION_PER_REQUEST, SessionDescC, SlotStatusC, TimingsC,
+                   VisionSettingsC, check, lib)
 
 
 @dataclass
@@ -49,6 +50,10 @@ class DecodeOutcome:
     prompt_tokens: int
     response_tokens: int
     generated_tokens: list = field(default_factory=list)
+    # decode(..., logprobs=K): one log-probability per generated token, and per token its K most likely
+    # alternatives as (id, logprob), most likely first
+    token_logprobs: Optional[list] = None
+    top_logprobs: Optional[list] = None
 
 
 @dataclass
@@ -301,6 +306,32 @@ class DeepseekOcrEngine:
                                          logits.ctypes.data_as(C.c_void_p), logits.size))
         return [outs[i][:res[i].n_out].tolist() for i in range(len(requests))], logits
 
+    def generate_logprobs(self, requests, top_k: int = 0, params: DecodeParameters = DecodeParameters(),
+                          ignore_eos: bool = False):
+        """generate_batch + per-token log-probabilities (dsocr_generate_logprobs): returns (ids per page,
+        token log-probabilities per page float32 [n_out], alternative ids per page int64 [n_out][top_k], their
+        log-probabilities float32 [n_out][top_k])."""
+        if not 0 <= int(top_k) <= MAX_TOP_LOGPROBS:
+            raise DsocrError(1, f"top_k must be 0..{MAX_TOP_LOGPROBS}")
+        keep = []
+        n, k, cap = len(requests), int(top_k), max(params.max_new_tokens, 1)
+        reqs = (RequestC * n)(*[self._request(*r, keep) for r in requests])
+        outs = [np.empty(cap, np.int64) for _ in requests]
+        res = (ResultC * n)(*[ResultC(o.ctypes.data_as(C.POINTER(C.c_int64)), len(o), 0, 0) for o in outs])
+        tlp = [np.zeros(cap, np.float32) for _ in requests]
+        tid = [np.zeros((cap, max(k, 1)), np.int64) for _ in requests]
+        tl = [np.zeros((cap, max(k, 1)), np.float32) for _ in requests]
+        lps = (LogprobsC * n)(*[LogprobsC(tlp[i].ctypes.data_as(C.POINTER(C.c_float)),
+                                         tid[i].ctypes.data_as(C.POINTER(C.c_int64)),
+                                         tl[i].ctypes.data_as(C.POINTER(C.c_float)), cap, 0) for i in range(n)])
+        pc = _params_c(params, self.eos_token_id, ignore_eos)
+        check(lib().dsocr_generate_logprobs(self._h, n, reqs, C.byref(pc), res, k, lps))
+        ids = [outs[i][:res[i].n_out].tolist() for i in range(n)]
+        cnt = [int(lps[i].n) for i in range(n)]
+        return (ids, [tlp[i][:cnt[i]].copy() for i in range(n)],
+                [tid[i].reshape(-1)[:cnt[i] * k].reshape(cnt[i], k).copy() for i in range(n)],
+                [tl[i].reshape(-1)[:cnt[i] * k].reshape(cnt[i], k).copy() for i in range(n)])
+
     def last_timings(self) -> dict:
         t = TimingsC()
         check(lib().dsocr_last_timings(self._h, C.byref(t)))
@@ -364,19 +395,31 @@ class DeepseekOcrEngine:
 
     # ------------------------------------------------------------------ decode sessions
     def open_session(self, slots: int, max_context: int, params: DecodeParameters = DecodeParameters(),
-                     ignore_eos: bool = False, per_request: bool = False) -> "Session":
+                     ignore_eos: bool = False, per_request: bool = False, logprobs: bool = False) -> "Session":
         """A long-lived batch of `slots` pages (dsocr_session_open): pages are admitted and retired between bursts
         of decode steps.  `params` are the session's; params.max_new_tokens bounds a request's own.
         ``per_request`` (dsocr_session_open_ex, DSOCR_SESSION_PER_REQUEST): `params` are only the defaults and
-        ``Session.admit(..., params=...)`` gives every page its own."""
-        return Session(self, slots, max_context, params, ignore_eos, per_request)
+        ``Session.admit(..., params=...)`` gives every page its own.  ``logprobs`` (DSOCR_SESSION_LOGPROBS): every
+        slot keeps per-token log-probabilities (``Session.logprobs``); the exact head runs."""
+        return Session(self, slots, max_context, params, ignore_eos, per_request, logprobs)
 
     # ------------------------------------------------------------------ OcrEngine::decode
     def decode(self, tokenizer, prompt: str, images: Sequence, vision: VisionSettings,
-               params: DecodeParameters, stream: Optional[Callable] = None) -> DecodeOutcome:
+               params: DecodeParameters, stream: Optional[Callable] = None,
+               logprobs: Optional[int] = None) -> DecodeOutcome:
+        """``logprobs`` = K (0..20): the outcome carries every token's log-probability and its K most likely
+        alternatives (``stream`` is then not called: the entries arrive with the ids)."""
         pages = [Page(im, vision, self) for im in images]
         ids, mask = build_prompt_tokens(tokenizer, prompt, [p.n_image_tokens for p in pages])
-        if len(pages) > 1:
+        token_lp = top = None
+        if logprobs is not None:
+            rows = np.concatenate(self.image_embeddings(pages), axis=0) if len(pages) > 1 else None
+            req = (ids, mask, pages[0] if len(pages) == 1 else None, rows)
+            g, lp, ti, tl = self.generate_logprobs([req], int(logprobs), params)
+            gen = g[0]
+            token_lp = [float(x) for x in lp[0]]
+            top = [[(int(i), float(v)) for i, v in zip(ti[0][t], tl[0][t])] for t in range(len(token_lp))]
+        elif len(pages) > 1:
             # several <image> slots: the pages' rows in image order (compute_image_embeddings over the
             # list, model/mod.rs:2387), injected at the mask positions in that order
             rows = np.concatenate(self.image_embeddings(pages), axis=0)
@@ -389,7 +432,7 @@ class DeepseekOcrEngine:
                 text = tokenizer.decode([int(t) for t in gen], skip_special_tokens=True)
             except TypeError:
                 text = tokenizer.decode([int(t) for t in gen])
-        return DecodeOutcome(normalize_text(text), len(ids), len(gen), gen)
+        return DecodeOutcome(normalize_text(text), len(ids), len(gen), gen, token_lp, top)
 
 
 @dataclass
@@ -405,11 +448,13 @@ class Session:
     [0, active); ``retire`` returns (ids, moved_from): the last active page moves into the freed slot."""
 
     def __init__(self, engine: DeepseekOcrEngine, slots: int, max_context: int, params: DecodeParameters,
-                 ignore_eos: bool = False, per_request: bool = False):
+                 ignore_eos: bool = False, per_request: bool = False, logprobs: bool = False):
         self._e = None
         pc = _params_c(params, engine.eos_token_id, ignore_eos)
-        if per_request:
-            check(lib().dsocr_session_open_ex(engine._h, int(slots), int(max_context), C.byref(pc), SESSION_PER_REQUEST))
+        flags = (SESSION_PER_REQUEST if per_request else 0) | (SESSION_LOGPROBS if logprobs else 0)
+        self.has_logprobs = bool(logprobs)
+        if flags:
+            check(lib().dsocr_session_open_ex(engine._h, int(slots), int(max_context), C.byref(pc), flags))
         else:
             check(lib().dsocr_session_open(engine._h, int(slots), int(max_context), C.byref(pc)))
         self._e = engine
@@ -430,11 +475,19 @@ class Session:
     def admit(self, ids, mask=None, page: Optional[Page] = None, image_rows=None,
               max_new_tokens: Optional[int] = None, seed: Optional[int] = None,
               params: Optional[DecodeParameters] = None, eos_token_id: Optional[int] = None,
-              ignore_eos: Optional[bool] = None) -> int:
+              ignore_eos: Optional[bool] = None, logprobs: Optional[int] = None) -> int:
         """Without ``params``: the session's parameters with this page's ``max_new_tokens`` / ``seed``
         (dsocr_session_admit).  With ``params``: the page's whole parameter set (dsocr_session_admit_params; its
         max_new_tokens and seed count, the two keyword arguments are then not read); ``eos_token_id`` /
-        ``ignore_eos`` default to what the session was opened with."""
+        ``ignore_eos`` default to what the session was opened with.  ``logprobs`` (0..20) is a check only, it changes
+        nothing on the device: a session opened with ``logprobs`` keeps 20 alternatives for every slot whatever is
+        passed here, and ``Session.logprobs(..., top_k)`` decides how many are read.  Passing it states that the
+        page's entries will be read, and is an error (EINVAL) on a session opened without ``logprobs``."""
+        if logprobs is not None:
+            if not self.has_logprobs:
+                raise DsocrError(1, "this session was opened without logprobs")
+            if not 0 <= int(logprobs) <= MAX_TOP_LOGPROBS:
+                raise DsocrError(1, f"logprobs must be 0..{MAX_TOP_LOGPROBS}")
         keep = []
         req = self._e._request(ids, mask, page, image_rows, keep)
         slot = C.c_int(-1)
@@ -453,6 +506,18 @@ class Session:
         a, b = C.c_size_t(), C.c_size_t()
         check(lib().dsocr_session_head_steps(self._e._h, C.byref(a), C.byref(b)))
         return {"screened": int(a.value), "exact": int(b.value)}
+
+    def logprobs(self, slot: int, first: int, count: int, top_k: int = 0):
+        """Entries [first, first + count) of a live slot (dsocr_session_logprobs): (token log-probabilities float32
+        [count], alternative ids int64 [count][top_k], their log-probabilities float32 [count][top_k]).  Read them
+        before ``retire``."""
+        n, k = int(count), int(top_k)
+        lp = np.zeros(max(n, 1), np.float32)
+        ti = np.zeros(max(n * k, 1), np.int64)
+        tl = np.zeros(max(n * k, 1), np.float32)
+        check(lib().dsocr_session_logprobs(self._e._h, int(slot), int(first), n, k, lp.ctypes.data_as(C.c_void_p),
+                                           ti.ctypes.data_as(C.c_void_p), tl.ctypes.data_as(C.c_void_p)))
+        return lp[:n], ti[:n * k].reshape(n, k), tl[:n * k].reshape(n, k)
 
     def _report(self, ns, nt):
         out, off = [], 0

@@ -11,6 +11,12 @@ context or output than the session has, waits until the session is empty and the
 per_request=True)``) and every request is admitted with its own parameters: only one without ``use_cache``, or one
 that needs more output or context than the session has, still runs alone.  Requests are served in arrival order: nothing behind such a request is admitted before it ran.
 
+Log-probabilities: ``BatchScheduler(..., logprobs=True)`` opens the session with ``logprobs=True`` (the exact head
+runs for everyone) and ``submit(..., logprobs=K)`` asks for a request's entries: they are fetched with its new tokens,
+``on_token`` then receives ``(n, tokens, entry)`` with ``entry = (logprob, [(id, logprob)] * K)`` of the newest token,
+and the outcome carries ``token_logprobs`` / ``top_logprobs``.  Without the scheduler's flag such a request runs alone
+through ``engine.decode(..., logprobs=K)`` after the session drained, like any request that does not fit.
+
 The engine object needs ``open_session(slots, max_context, params)`` (admit / step / poll / retire / close, see
 ``dsocr.engine.Session``), ``decode`` and, for prompts with several images, ``image_embeddings``; tests drive the
 scheduler with a scripted fake.
@@ -48,6 +54,9 @@ class _Request:
     tokens: list = field(default_factory=list)
     kv_pos: int = 0  # upper bound of the slot's device kv_pos: prompt + steps since admission
     done: bool = False
+    logprobs: Optional[int] = None  # alternatives per token the request asked for
+    token_lp: list = field(default_factory=list)
+    top_lp: list = field(default_factory=list)
 
 
 def _default_prepare(engine, tokenizer, prompt, images, vision):
@@ -56,6 +65,18 @@ def _default_prepare(engine, tokenizer, prompt, images, vision):
     pages = [Page(im, vision, None, getattr(engine, "variant", 0)) for im in images]
     ids, mask = build_prompt_tokens(tokenizer, prompt, [p.n_image_tokens for p in pages])
     return ids, mask, pages
+
+
+def _takes_entry(cb) -> bool:
+    """True when ``cb(n, tokens, entry)`` is a valid call (or the signature cannot be read)."""
+    import inspect
+    try:
+        inspect.signature(cb).bind(0, [], None)
+    except TypeError:
+        return False
+    except ValueError:
+        return True
+    return True
 
 
 def _decode_text(tokenizer, ids) -> str:
@@ -70,13 +91,14 @@ def _decode_text(tokenizer, ids) -> str:
 class BatchScheduler:
     def __init__(self, engine, tokenizer, slots: int, max_context: int,
                  defaults: DecodeParameters = DecodeParameters(), vision: Optional[VisionSettings] = None,
-                 prepare: Optional[Callable] = None, per_request_params: bool = False):
+                 prepare: Optional[Callable] = None, per_request_params: bool = False, logprobs: bool = False):
         if not 1 <= int(slots) <= 8:
             raise ValueError("a session has 1..8 slots")
         self.engine, self.tokenizer = engine, tokenizer
         self.slots, self.max_context = int(slots), int(max_context)
         self.defaults = defaults
         self.per_request_params = bool(per_request_params)
+        self.logprobs = bool(logprobs)
         self.vision = vision or VisionSettings()
         self._prepare = prepare or _default_prepare
         self._queue: deque = deque()
@@ -106,8 +128,20 @@ class BatchScheduler:
         return prompt_len + params.max_new_tokens + 1 <= self.max_context
 
     def submit(self, prompt: str, images: Sequence = (), vision: Optional[VisionSettings] = None,
-               params: Optional[DecodeParameters] = None, on_token: Optional[Callable] = None) -> Future:
+               params: Optional[DecodeParameters] = None, on_token: Optional[Callable] = None,
+               logprobs: Optional[int] = None) -> Future:
+        """``logprobs`` = K (0..20) asks for the request's per-token log-probabilities.  It changes the arity of
+        ``on_token``: the callback is then called as ``on_token(n, tokens, entry)``, with ``entry = (logprob,
+        [(id, logprob)] * K)`` of the newest token, instead of ``on_token(n, tokens)``.  A two-argument callback
+        given together with ``logprobs`` is refused here (ValueError through the future) rather than failing on
+        every token."""
         fut: Future = Future()
+        if logprobs is not None and on_token is not None and not _takes_entry(on_token):
+            fut.set_exception(ValueError("with logprobs, on_token is called as on_token(n, tokens, entry)"))
+            return fut
+        if logprobs is not None and not 0 <= int(logprobs) <= 20:
+            fut.set_exception(ValueError("logprobs must be 0..20"))
+            return fut
         params = params or self.defaults
         vision = vision or self.vision
         try:
@@ -120,7 +154,8 @@ class BatchScheduler:
             rq.page = pages[0]
         else:
             rq.pages = list(pages)
-        rq.exclusive = not self.compatible(params, len(rq.ids))
+        rq.logprobs = None if logprobs is None else int(logprobs)
+        rq.exclusive = not self.compatible(params, len(rq.ids)) or (rq.logprobs is not None and not self.logprobs)
         with self._cv:
             if self._stop:
                 fut.set_exception(RuntimeError("scheduler is closed"))
@@ -225,20 +260,22 @@ class BatchScheduler:
     def _admit(self, rq) -> bool:
         try:
             if self._session is None:
+                kw = {}
                 if self.per_request_params:
-                    self._session = self.engine.open_session(self.slots, self.max_context, self.defaults,
-                                                             per_request=True)
-                else:
-                    self._session = self.engine.open_session(self.slots, self.max_context, self.defaults)
+                    kw["per_request"] = True
+                if self.logprobs:
+                    kw["logprobs"] = True
+                self._session = self.engine.open_session(self.slots, self.max_context, self.defaults, **kw)
             rows = None
             if rq.pages:
                 import numpy as np
                 rows = np.concatenate(self.engine.image_embeddings(rq.pages), axis=0)
+            kw = {} if rq.logprobs is None else {"logprobs": rq.logprobs}
             if self.per_request_params:
-                slot = self._session.admit(rq.ids, rq.mask, rq.page, rows, params=rq.params)
+                slot = self._session.admit(rq.ids, rq.mask, rq.page, rows, params=rq.params, **kw)
             else:
                 slot = self._session.admit(rq.ids, rq.mask, rq.page, rows, max_new_tokens=rq.params.max_new_tokens,
-                                           seed=rq.params.seed)
+                                           seed=rq.params.seed, **kw)
         except Exception as e:  # noqa: BLE001 - the request's own error: the running slots are untouched
             rq.future.set_exception(e)
             return False
@@ -254,11 +291,21 @@ class BatchScheduler:
             rq = self._active[st.slot]
             room = rq.params.max_new_tokens - len(rq.tokens)
             fresh = list(st.new_tokens)[:max(room, 0)]
-            for t in fresh:
+            entries = []
+            if rq.logprobs is not None and fresh:  # the new tokens' entries with them (read before any retire)
+                lp, ti, tl = self._session.logprobs(st.slot, len(rq.tokens), len(fresh), rq.logprobs)
+                entries = [(float(lp[i]), [(int(a), float(b)) for a, b in zip(ti[i], tl[i])]) for i in range(len(fresh))]
+            for i, t in enumerate(fresh):
                 rq.tokens.append(int(t))
+                if entries:
+                    rq.token_lp.append(entries[i][0])
+                    rq.top_lp.append(entries[i][1])
                 if rq.on_token is not None:
                     try:
-                        rq.on_token(len(rq.tokens), list(rq.tokens))
+                        if entries:
+                            rq.on_token(len(rq.tokens), list(rq.tokens), entries[i])
+                        else:
+                            rq.on_token(len(rq.tokens), list(rq.tokens))
                     except Exception:  # noqa: BLE001 - a consumer's failure is its own
                         pass
             rq.done = bool(st.done) or len(rq.tokens) >= rq.params.max_new_tokens
@@ -277,14 +324,27 @@ class BatchScheduler:
                 self._active[slot] = self._active[last]
             self._active.pop()
             ids = [int(t) for t in ids][:rq.params.max_new_tokens]
-            rq.future.set_result(DecodeOutcome(normalize_text(_decode_text(self.tokenizer, ids)), len(rq.ids),
-                                               len(ids), ids))
+            out = DecodeOutcome(normalize_text(_decode_text(self.tokenizer, ids)), len(rq.ids), len(ids), ids)
+            if rq.logprobs is not None:
+                out.token_logprobs, out.top_logprobs = rq.token_lp[:len(ids)], rq.top_lp[:len(ids)]
+            rq.future.set_result(out)
 
     def _run_exclusive(self, rq):
         self._close_session()  # a session and a generate exclude each other on one engine
         self.exclusive_runs += 1
         try:
-            out = self.engine.decode(self.tokenizer, rq.prompt, rq.images, rq.vision, rq.params, rq.on_token)
+            if rq.logprobs is None:
+                out = self.engine.decode(self.tokenizer, rq.prompt, rq.images, rq.vision, rq.params, rq.on_token)
+            else:  # the entries arrive with the ids: the consumer gets every token with its entry afterwards
+                out = self.engine.decode(self.tokenizer, rq.prompt, rq.images, rq.vision, rq.params, None,
+                                         logprobs=rq.logprobs)
+                if rq.on_token is not None:
+                    toks = [int(t) for t in out.generated_tokens]
+                    for i in range(len(toks)):
+                        try:
+                            rq.on_token(i + 1, toks[:i + 1], (out.token_logprobs[i], out.top_logprobs[i]))
+                        except Exception:  # noqa: BLE001 - a consumer's failure is its own
+                            pass
         except Exception as e:  # noqa: BLE001
             rq.future.set_exception(e)
             return

@@ -155,6 +155,45 @@ def merge_decode(defaults: DecodeParameters, req: dict, max_tokens: Optional[int
     return replace(p, **patch)
 
 
+# ---------------------------------------------------------------- log-probabilities (chat completions)
+MAX_TOP_LOGPROBS = 20
+NEG_INF_LOGPROB = -9999.0  # how -inf is written (the OpenAI convention): the JSON stays valid
+
+
+def parse_logprobs(req: dict) -> Optional[int]:
+    """`logprobs: true|false` and `top_logprobs: 0..20` of a chat completion body: None when log-probabilities are
+    not asked for, else the number of alternatives per token.  400: top_logprobs without logprobs: true, or not an
+    integer in 0..20."""
+    want, top = req.get("logprobs"), req.get("top_logprobs")
+    if want is not None and not isinstance(want, bool):
+        raise ApiError.bad_request("`logprobs` must be a boolean")
+    if top is not None:
+        if isinstance(top, bool) or not isinstance(top, int) or not 0 <= top <= MAX_TOP_LOGPROBS:
+            raise ApiError.bad_request(f"`top_logprobs` must be an integer in 0..{MAX_TOP_LOGPROBS}")
+        if not want:
+            raise ApiError.bad_request("`top_logprobs` requires `logprobs: true`")
+    return (top or 0) if want else None
+
+
+def _lp_json(v: float) -> float:
+    return float(v) if v == v and v > float("-inf") else NEG_INF_LOGPROB
+
+
+def _token_json(tokenizer, tok: int, lp: float) -> dict:
+    text = decode_ids(tokenizer, [int(tok)]) if tok >= 0 else ""  # every token decoded on its own
+    return {"token": text, "logprob": _lp_json(lp), "bytes": list(text.encode("utf-8"))}
+
+
+def logprob_content(tokenizer, tokens, token_lp, top_lp) -> list:
+    """choices[0].logprobs.content: [{token, logprob, bytes, top_logprobs: [{token, logprob, bytes}]}]."""
+    out = []
+    for tok, lp, top in zip(tokens, token_lp, top_lp):
+        e = _token_json(tokenizer, int(tok), lp)
+        e["top_logprobs"] = [_token_json(tokenizer, int(i), v) for i, v in top if i >= 0]
+        out.append(e)
+    return out
+
+
 # ---------------------------------------------------------------- state
 @dataclass
 class ServerState:
@@ -177,7 +216,8 @@ def _now() -> int:
     return int(time.time())
 
 
-def generate_blocking(state: ServerState, prompt: str, images: list, params: DecodeParameters, on_token=None):
+def generate_blocking(state: ServerState, prompt: str, images: list, params: DecodeParameters, on_token=None,
+                      logprobs: Optional[int] = None):
     """generation.rs:75-163.  With a scheduler the request joins the running decode session (its error reaches only
     its own future); without one it decodes alone behind the lock."""
     def classify(e):
@@ -188,7 +228,8 @@ def generate_blocking(state: ServerState, prompt: str, images: list, params: Dec
 
     if state.scheduler is not None:
         try:
-            outcome = state.scheduler.submit(prompt, images, state.vision, params, on_token).result()
+            kw = {} if logprobs is None else {"logprobs": logprobs}
+            outcome = state.scheduler.submit(prompt, images, state.vision, params, on_token, **kw).result()
         except DsocrError as e:
             raise classify(e)
         except ApiError:
@@ -198,7 +239,14 @@ def generate_blocking(state: ServerState, prompt: str, images: list, params: Dec
     else:
         with state.lock:
             try:
-                outcome = state.engine.decode(state.tokenizer, prompt, images, state.vision, params, on_token)
+                if logprobs is None:
+                    outcome = state.engine.decode(state.tokenizer, prompt, images, state.vision, params, on_token)
+                else:  # the entries arrive with the ids: a streaming consumer gets every token with its entry
+                    outcome = state.engine.decode(state.tokenizer, prompt, images, state.vision, params, None,
+                                                  logprobs=logprobs)
+                    toks = [int(t) for t in outcome.generated_tokens]
+                    for i in range(len(toks) if on_token is not None else 0):
+                        on_token(i + 1, toks[:i + 1], (outcome.token_logprobs[i], outcome.top_logprobs[i]))
             except DsocrError as e:
                 raise classify(e)
     if outcome.response_tokens == 0 and not outcome.text.strip():
@@ -217,6 +265,7 @@ class StreamController:
         self.last_count = 0
         self.role_sent = False
         self.finished = False
+        self.pending_lp: list = []  # entries of the tokens since the last chunk (chat, logprobs: true)
         if kind == "chat":
             self.id = f"chatcmpl-{uuid.uuid4()}"
         else:
@@ -243,8 +292,11 @@ class StreamController:
             delta = {"content": text}
             if include_role:
                 delta["role"] = "assistant"
+            choice = {"index": 0, "delta": delta, "finish_reason": None}
+            if self.pending_lp:  # the entries of the tokens in this chunk
+                choice["logprobs"], self.pending_lp = {"content": self.pending_lp}, []
             self._send({"id": self.id, "object": "chat.completion.chunk", "created": self.created,
-                        "model": self.model, "choices": [{"index": 0, "delta": delta, "finish_reason": None}]})
+                        "model": self.model, "choices": [choice]})
         else:
             self._send({"type": "response.output_text.delta", "response": self._head(),
                         "output_id": self.output_id, "output_index": 0, "delta": text})
@@ -269,7 +321,11 @@ class StreamController:
             self.emit_delta(emit, include_role)
 
     def callback(self):
-        return lambda count, ids: self.process_tokens(count, ids, False)
+        def on_token(count, ids, entry=None):
+            if entry is not None and self.kind == "chat":
+                self.pending_lp += logprob_content(self.tokenizer, [ids[count - 1]], [entry[0]], [entry[1]])
+            self.process_tokens(count, ids, False)
+        return on_token
 
     def flush_remaining(self, ids):
         if ids:
@@ -280,8 +336,11 @@ class StreamController:
             return
         self.finished = True
         if self.kind == "chat":
+            choice = {"index": 0, "delta": {}, "finish_reason": "stop"}
+            if self.pending_lp:  # tokens that produced no text of their own
+                choice["logprobs"], self.pending_lp = {"content": self.pending_lp}, []
             self._send({"id": self.id, "object": "chat.completion.chunk", "created": self.created,
-                        "model": self.model, "choices": [{"index": 0, "delta": {}, "finish_reason": "stop"}],
+                        "model": self.model, "choices": [choice],
                         "usage": {"prompt_tokens": prompt_tokens, "completion_tokens": completion_tokens,
                                   "total_tokens": prompt_tokens + completion_tokens}})
         else:
@@ -350,13 +409,14 @@ def handle_generation(state: ServerState, req: dict, kind: str):
     if max_tokens is None:
         max_tokens = req.get("max_tokens")
     params = merge_decode(state.defaults, req, max_tokens)
+    logprobs = parse_logprobs(req) if kind == "chat" else None  # (/v1/responses has no log-probabilities)
     if stream:
         c = StreamController(state.tokenizer, kind, model)
 
         def work():
             try:
                 c.send_initial()
-                out = generate_blocking(state, prompt, images, params, c.callback())
+                out = generate_blocking(state, prompt, images, params, c.callback(), logprobs)
                 c.flush_remaining(out.generated_tokens)
                 c.finalize(out.text, out.prompt_tokens, out.response_tokens)
             except ApiError as e:
@@ -366,9 +426,13 @@ def handle_generation(state: ServerState, req: dict, kind: str):
 
         threading.Thread(target=work, daemon=True).start()
         return "stream", c
-    out = generate_blocking(state, prompt, images, params)
+    out = generate_blocking(state, prompt, images, params, None, logprobs)
     mk = _chat_response if kind == "chat" else _responses_response
-    return "json", mk(model, out.text, out.prompt_tokens, out.response_tokens)
+    body = mk(model, out.text, out.prompt_tokens, out.response_tokens)
+    if logprobs is not None:
+        body["choices"][0]["logprobs"] = {"content": logprob_content(state.tokenizer, out.generated_tokens,
+                                                                     out.token_logprobs or [], out.top_logprobs or [])}
+    return "json", body
 
 
 def create_app(state: ServerState):
@@ -428,16 +492,21 @@ def add_scheduler_args(p):
                    help="with --slots: a request's own temperature / top_p / top_k / repetition_penalty / "
                         "no_repeat_ngram_size join the running batch (per-row selection on the device) instead of "
                         "waiting for it to drain; off by default")
+    p.add_argument("--logprobs", action="store_true",
+                   help="with --slots: open the decode session with per-token log-probabilities (the exact lm_head "
+                        "runs for every request), so requests with `logprobs: true` join the running batch instead "
+                        "of waiting for it to drain; off by default")
 
 
-def make_scheduler(state: ServerState, slots: int, max_context: int, per_request_params: bool = False):
+def make_scheduler(state: ServerState, slots: int, max_context: int, per_request_params: bool = False,
+                   logprobs: bool = False):
     """The state's scheduler for --slots N (None for 0: requests take the lock path).  per_request_params: the
     DecodeParameters merge_decode builds from a request body are admitted into the session as that request's own."""
     if not slots:
         return None
     from .scheduler import BatchScheduler
     return BatchScheduler(state.engine, state.tokenizer, slots, max_context, state.defaults, state.vision,
-                          per_request_params=per_request_params)
+                          per_request_params=per_request_params, logprobs=logprobs)
 
 
 def main(argv=None) -> int:
@@ -462,7 +531,7 @@ def main(argv=None) -> int:
                                       synthetic_seed=args.synthetic_seed))
     state = ServerState(engine, load_tokenizer(args.tokenizer, _vocab_of(config)), args.model,
                         vision_settings(args), decode_params(args))
-    state.scheduler = make_scheduler(state, args.slots, args.max_context, args.per_request_params)
+    state.scheduler = make_scheduler(state, args.slots, args.max_context, args.per_request_params, args.logprobs)
     import uvicorn
     uvicorn.run(create_app(state), host=args.host, port=args.port)
     return 0

@@ -201,6 +201,27 @@ dsocr_status dsocr_generate_trace(dsocr_engine* e, size_t n, const dsocr_request
                                   const dsocr_decode_params* params, dsocr_result* results, float* logits_out,
                                   size_t logits_cap);
 
+/* Per-token log-probabilities.  dsocr_generate_batch plus, for every id a page emits and at the same index, its
+ * log-probability and the top_k (0 .. DSOCR_MAX_TOP_LOGPROBS) most likely alternatives, reduced on the device inside
+ * the decode step: lp = l[tok] - m - log sum_v exp(l[v] - m) over the finite raw logits l of the exact lm_head (f32,
+ * before repetition penalty, n-gram ban and temperature: the values dsocr_generate_trace exposes), m their maximum;
+ * -inf when l[tok] is not finite or the row has no finite entry.  Alternatives: the largest raw logits, descending,
+ * the lower id first on equal values, each with its own log-probability; (-1, -inf) past the last finite entry.
+ * An EOS that is not emitted has no entry.  Selection runs on the exact lm_head (as while tracing); the ids equal
+ * dsocr_generate_batch's.  lp[i] are caller buffers of page i: token_lp [cap], top_id / top_lp [cap][top_k] (may be
+ * NULL when top_k == 0), cap >= max_new_tokens; n is set on return.  use_cache = 0 is DSOCR_EINVAL. */
+#define DSOCR_MAX_TOP_LOGPROBS 20
+typedef struct {
+    float* token_lp;
+    int64_t* top_id;
+    float* top_lp;
+    size_t cap;
+    size_t n;
+} dsocr_logprobs;
+dsocr_status dsocr_generate_logprobs(dsocr_engine* e, size_t n, const dsocr_request* reqs,
+                                     const dsocr_decode_params* params, dsocr_result* results, size_t top_k,
+                                     dsocr_logprobs* lp);
+
 /* ---- decode sessions: pages join and leave a running batch between decode steps (no reference counterpart: the
  * reference server decodes one request at a time behind its Mutex, server/src/state.rs:22).  A session is a
  * long-lived batch of `slots` (1..8) pages with max_context rows each (a page needs prompt_len + max_new_tokens
@@ -237,10 +258,15 @@ typedef struct {
     size_t kv_cap;     /* cache rows per slot: max_context + burst_cap */
     size_t burst_cap;  /* most steps one dsocr_session_step replays */
     size_t steps;      /* decode steps replayed since the session opened */
+    size_t flags;      /* the DSOCR_SESSION_* flags the session was opened with */
 } dsocr_session_desc;
 dsocr_status dsocr_session_open(dsocr_engine* e, size_t slots, size_t max_context, const dsocr_decode_params* params);
 /* flags = 0: dsocr_session_open.  Unknown flag bits are DSOCR_EINVAL. */
 #define DSOCR_SESSION_PER_REQUEST 1u
+/* DSOCR_SESSION_LOGPROBS (combines with DSOCR_SESSION_PER_REQUEST): every slot keeps out_cap log-probability entries
+ * with DSOCR_MAX_TOP_LOGPROBS alternatives each (see dsocr_generate_logprobs), written by every step and by the
+ * admission's first selection; the exact head runs at every active count. */
+#define DSOCR_SESSION_LOGPROBS 2u
 dsocr_status dsocr_session_open_ex(dsocr_engine* e, size_t slots, size_t max_context, const dsocr_decode_params* params,
                                    uint32_t flags);
 /* Every check (free slot, context need, prompt/image mismatch, token ids, page variant) happens before any device
@@ -266,6 +292,11 @@ dsocr_status dsocr_session_poll(dsocr_engine* e, dsocr_slot_status* status, size
  * whose page now lives in `slot` */
 dsocr_status dsocr_session_retire(dsocr_engine* e, int slot, int64_t* out_ids, size_t cap, size_t* n_out,
                                   int* moved_from);
+/* entries [first, first + count) of a live slot: token_lp [count], top_id / top_lp [count][top_k], top_k <=
+ * DSOCR_MAX_TOP_LOGPROBS.  DSOCR_EINVAL when the session was opened without DSOCR_SESSION_LOGPROBS or the range
+ * passes the slot's out_len.  dsocr_session_retire does not return them: read them before it. */
+dsocr_status dsocr_session_logprobs(dsocr_engine* e, int slot, size_t first, size_t count, size_t top_k, float* token_lp,
+                                    int64_t* top_id, float* top_lp);
 dsocr_status dsocr_session_close(dsocr_engine* e);
 /* DSOCR_EINVAL when no session is open */
 dsocr_status dsocr_session_info(const dsocr_engine* e, dsocr_session_desc* out);
@@ -587,6 +618,15 @@ dsocr_status dsocr_k_select_rows(int B, int V, float* logits, const int* ctx, in
  * rng [slots][rng_words], x [slots][H] and the per-slot scalars kv_len, kv_pos, ctx_len, out_len, done, tok.
  * Rows from kv_len on, the source and every other slot are not written.  Any array but kc, vc, kv_len may be
  * NULL.  Device pointers. */
+/* The two log-probability launches (dec_lp_partial, dec_lp_final) once on host rows: logits [B][ld], tok [B];
+ * emit[b] = 0 leaves lp[b], top_id[b][0..K), top_lp[b][0..K) untouched.  _penalty: with a context row per page
+ * ([B][ctx_cap], ctx_len [B]) and the repetition-penalty launch between the two, as the engine's step runs them:
+ * the result equals the call without it on the same raw logits. */
+dsocr_status dsocr_k_logprobs(int B, int V, int K, const float* logits, int ld, const int* tok, const uint8_t* emit,
+                              float* lp, int64_t* top_id, float* top_lp);
+dsocr_status dsocr_k_logprobs_penalty(int B, int V, int K, const float* logits, int ld, const int* tok, const uint8_t* emit,
+                                      const int* ctx, int ctx_cap, const int* ctx_len, float penalty, float* lp,
+                                      int64_t* top_id, float* top_lp);
 dsocr_status dsocr_k_session_slot_move(int layers, int slots, int kv_heads, int cap, int hd, float* kc, float* vc,
                                        int* kv_len, int* kv_pos, int* ctx, long long ctx_cap, int* ctx_len, int* out,
                                        long long out_cap, int* out_len, int* done, int* tok, uint32_t* rng,

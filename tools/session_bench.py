@@ -10,10 +10,14 @@ Page i generates MAX_NEW[i] tokens: drawn once, numpy default_rng(4011).choice(L
   (e) (d) with every fourth request sampled (T 0.7, top-p 0.9, seeded): the per-row exact head whenever one is active
   (f) (e)'s traffic through BatchScheduler over a fixed session: a sampled request waits for the session to drain
       and runs alone (what (e) replaces)
+  (g) (c) opened with DSOCR_SESSION_LOGPROBS: the exact head plus the two log-probability launches every step, every
+      page's entries (20 alternatives) read before its retire
+  (h) (c) with DSOCR_SCREEN=0: the exact head without log-probabilities, so (h) - (g) is what the two launches and
+      the reads cost and (c) - (h) what the head switch costs
 The arms alternate ROUNDS times; pages/s and decode steps are reported as median [min, max].  Also: the wall time
 of one admission while other slots wait, and one session_slot_move of a 1200-row full-size page against its bytes.
 
-    python tools/session_bench.py [--rounds 3] [--pages 32] [--arms a,b,c,d,e,f] [--out profiles/session_bench.json]
+    python tools/session_bench.py [--rounds 3] [--pages 32] [--arms a,b,c,d,e,f,g,h] [--out profiles/session_bench.json]
 """
 import argparse
 import ctypes as C
@@ -55,10 +59,11 @@ def run_batches(eng, reqs, max_new, P):
     return steps, {}
 
 
-def run_session(eng, reqs, max_new, P):
+def run_session(eng, reqs, max_new, P, logprobs=False):
     need = max(len(r) + m + 1 for r, m in zip(reqs, max_new))
     stalls, moves, done, nxt = [], [], 0, 0
-    with eng.open_session(SLOTS, need, P(max_new_tokens=max(max_new)), ignore_eos=True) as s:
+    kw = {"logprobs": True} if logprobs else {}
+    with eng.open_session(SLOTS, need, P(max_new_tokens=max(max_new)), ignore_eos=True, **kw) as s:
         active = 0
         while done < len(reqs):
             while active < SLOTS and nxt < len(reqs):
@@ -69,13 +74,29 @@ def run_session(eng, reqs, max_new, P):
                 active, nxt = active + 1, nxt + 1
             for st in sorted(s.step(8), key=lambda x: -x.slot):
                 if st.done:
+                    if logprobs:
+                        lp, _, _ = s.logprobs(st.slot, 0, st.out_len, 20)
+                        assert len(lp) == st.out_len and np.isfinite(lp).all()
                     t = time.perf_counter()
                     _, moved = s.retire(st.slot)
                     if moved >= 0:
                         moves.append((time.perf_counter() - t) * 1e3)
                     active, done = active - 1, done + 1
-        steps = s.info()["steps"]
-    return steps, {"admit_stall_ms": stalls, "retire_with_move_ms": moves}
+        steps, heads = s.info()["steps"], s.head_steps()
+    return steps, {"admit_stall_ms": stalls, "retire_with_move_ms": moves, "head_steps": heads}
+
+
+def run_session_exact(eng, reqs, max_new, P):
+    """run_session under DSOCR_SCREEN=0 (read per call by the engine): the exact head, nothing else changed."""
+    old = os.environ.get("DSOCR_SCREEN")
+    os.environ["DSOCR_SCREEN"] = "0"
+    try:
+        return run_session(eng, reqs, max_new, P)
+    finally:
+        if old is None:
+            del os.environ["DSOCR_SCREEN"]
+        else:
+            os.environ["DSOCR_SCREEN"] = old
 
 
 SAMPLED = dict(do_sample=True, temperature=0.7, top_p=0.9)
@@ -191,7 +212,9 @@ def main():
     paths = {"a_generate": run_single, "b_generate_batch": run_batches, "c_session": run_session,
              "d_session_per_request_greedy": lambda *x: run_session_params(*x, mixed=False),
              "e_session_per_request_mixed": lambda *x: run_session_params(*x, mixed=True),
-             "f_scheduler_fixed_mixed": run_scheduler_fixed}
+             "f_scheduler_fixed_mixed": run_scheduler_fixed,
+             "g_session_logprobs": lambda *x: run_session(*x, logprobs=True),
+             "h_session_exact_head": run_session_exact}
     paths = {k: f for k, f in paths.items() if k[0] in a.arms.split(",")}
     for f in paths.values():  # warm-up: workspaces, fragment-ordered weights, graphs
         f(eng, reqs[:SLOTS], [16] * SLOTS, P)
@@ -219,7 +242,9 @@ def main():
     med = lambda k: out[k]["pages_s"]["median"]  # noqa: E731
     for name, (x, y) in {"c_over_a": ("c_session", "a_generate"), "c_over_b": ("c_session", "b_generate_batch"),
                          "d_over_c": ("d_session_per_request_greedy", "c_session"),
-                         "e_over_f": ("e_session_per_request_mixed", "f_scheduler_fixed_mixed")}.items():
+                         "e_over_f": ("e_session_per_request_mixed", "f_scheduler_fixed_mixed"),
+                         "g_over_c": ("g_session_logprobs", "c_session"),
+                         "g_over_h": ("g_session_logprobs", "h_session_exact_head")}.items():
         if x in out and y in out:
             out[name] = med(x) / med(y)
     if "d_over_c" in out:
