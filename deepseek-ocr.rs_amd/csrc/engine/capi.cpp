@@ -563,6 +563,57 @@ dsocr_status dsocr_session_logprobs(dsocr_engine* e, int slot, size_t first, siz
     });
 }
 
+// ---- page prefix cache
+dsocr_status dsocr_session_prefix_keep(dsocr_engine* e, int slot, size_t rows, int* handle) {
+    return guarded([&] {
+        if (!e || !handle) throw std::runtime_error("EINVAL: NULL argument");
+        if (rows > (size_t)INT32_MAX) throw std::runtime_error("EINVAL: a prefix has 1..prompt_len rows");
+        *handle = e->impl->session_prefix_keep(slot, (int)rows);
+    });
+}
+
+dsocr_status dsocr_session_admit_prefix(dsocr_engine* e, int handle, const dsocr_request* req,
+                                        const dsocr_decode_params* params, int* slot) {
+    return guarded([&] {
+        if (!e || !req) throw std::runtime_error("EINVAL: NULL argument");
+        const int s = e->impl->session_admit_prefix(handle, to_request(*req), to_params(params));
+        if (slot) *slot = s;
+    });
+}
+
+dsocr_status dsocr_session_prefix_drop(dsocr_engine* e, int handle) {
+    return guarded([&] {
+        if (!e) throw std::runtime_error("EINVAL: NULL argument");
+        e->impl->session_prefix_drop(handle);
+    });
+}
+
+dsocr_status dsocr_session_prefix_stats(const dsocr_engine* e, size_t* entries, size_t* bytes, size_t* admissions,
+                                        size_t* rows_reused) {
+    return guarded([&] {
+        if (!e) throw std::runtime_error("EINVAL: NULL argument");
+        const dsocr::Engine::PrefixStats st = e->impl->session_prefix_stats();
+        if (entries) *entries = st.entries;
+        if (bytes) *bytes = st.bytes;
+        if (admissions) *admissions = st.admissions;
+        if (rows_reused) *rows_reused = st.rows_reused;
+    });
+}
+
+dsocr_status dsocr_k_session_prefix_copy(int layers, int slots, int kv_heads, int cap, int hd, float* kc, float* vc,
+                                         int slot, int rows, float* entry, int to_slot) {
+    return guarded([&] {
+        dsocr::PrefixCopyArgs c;
+        c.kc = kc; c.vc = vc; c.layers = layers; c.slots = slots; c.kv_heads = kv_heads; c.cap_rows = cap; c.hd = hd;
+        c.head_stride = (long)cap * hd; c.page_stride = (long)kv_heads * c.head_stride;
+        c.layer_stride = (long)slots * c.page_stride;
+        c.slot = slot; c.rows = rows; c.to_slot = to_slot ? 1 : 0; c.entry = entry;
+        dsocr::launch_session_prefix_copy(c, nullptr);
+        check_hip(hipGetLastError(), "session_prefix_copy launch");
+        check_hip(hipDeviceSynchronize(), "session_prefix_copy");
+    });
+}
+
 dsocr_status dsocr_k_session_slot_move(int layers, int slots, int kv_heads, int cap, int hd, float* kc, float* vc,
                                        int* kv_len, int* kv_pos, int* ctx, long long ctx_cap, int* ctx_len, int* out,
                                        long long out_cap, int* out_len, int* done, int* tok, uint32_t* rng,
@@ -1104,6 +1155,68 @@ dsocr_status dsocr_k_prefill_attention(int B, int heads, int kv_heads, int hd, i
             dsocr::launch_attention(a, nullptr);
             check_hip(hipGetLastError(), "prefill attention launch");
             check_hip(hipDeviceSynchronize(), "prefill attention");
+        } catch (...) {
+            for (void* p : bufs) (void)hipFree(p);
+            throw;
+        }
+        for (void* p : bufs) (void)hipFree(p);
+    });
+}
+dsocr_status dsocr_k_prefill_attention_past(int B, int heads, int kv_heads, int hd, int rope_dim, int use_mla, int cap,
+                                            float scale, const int* past, const int* lens, float* qkv, const float* cos,
+                                            const float* sin, float* kc, float* vc, float* o) {
+    return guarded([&] {
+        if (hd != 32 && hd != 64 && hd != 128) throw std::runtime_error("EINVAL: head_dim must be 32, 64 or 128");
+        if (heads <= 0 || kv_heads <= 0 || heads % kv_heads || rope_dim < 0 || rope_dim > hd || rope_dim % 2)
+            throw std::runtime_error("EINVAL: bad head / rope configuration");
+        if (B <= 0 || !past || !lens || !qkv || !cos || !sin || !kc || !vc || !o) throw std::runtime_error("EINVAL: NULL argument");
+        for (int b = 0; b < B; ++b) {
+            if (lens[b] < 1) throw std::runtime_error("EINVAL: every sequence needs at least one new row");
+            if (past[b] < 0 || (long)past[b] + lens[b] > cap) throw std::runtime_error("EINVAL: past + new rows must fit in cap");
+        }
+        // the plan and the views of Engine::forward_rows / layer_forward_prefill behind a past
+        const long QKVN = (long)(heads + 2 * kv_heads) * hd, H = (long)heads * hd;
+        const long head_stride = (long)cap * hd, page_stride = (long)kv_heads * head_stride;
+        const std::vector<int> hl(lens, lens + B), hp(past, past + B);
+        const dsocr::PrefillPlan plan = dsocr::prefill_row_plan(hl, QKVN, H, page_stride, hp);
+        std::vector<void*> bufs;
+        auto alloc = [&](size_t b) {
+            void* p = nullptr;
+            check_hip(hipMalloc(&p, b ? b : 16), "hipMalloc");
+            bufs.push_back(p);
+            return p;
+        };
+        auto upload = [&](const void* src, size_t b) {
+            void* p = alloc(b);
+            check_hip(hipMemcpy(p, src, b, hipMemcpyHostToDevice), "h2d");
+            return p;
+        };
+        try {
+            dsocr::RopeKvArgs r;
+            r.qkv = qkv; r.ld = QKVN; r.rows = (int)plan.T;
+            r.row_page = (const int*)upload(plan.row_page.data(), sizeof(int) * plan.row_page.size());
+            r.row_pos = (const int*)upload(plan.row_pos.data(), sizeof(int) * plan.row_pos.size());
+            r.heads = heads; r.kv_heads = kv_heads; r.hd = hd; r.rope_dim = rope_dim; r.use_mla = use_mla ? 1 : 0;
+            r.cos = cos; r.sin = sin; r.kc = kc; r.vc = vc; r.page_stride = page_stride; r.head_stride = head_stride;
+            dsocr::AttnPastArgs a;
+            a.q = {qkv, QKVN, hd, (const long*)upload(plan.q_off.data(), sizeof(long) * B)};
+            const long* kv_off = (const long*)upload(plan.kv_off.data(), sizeof(long) * B);
+            a.k = {kc, hd, head_stride, kv_off};
+            a.v = {vc, hd, head_stride, kv_off};
+            a.o = o; a.o_row_stride = H; a.o_head_stride = hd;
+            a.o_seq_off = (const long*)upload(plan.o_off.data(), sizeof(long) * B);
+            a.n_seq = B; a.past = (const int*)upload(past, sizeof(int) * B); a.n_q = (const int*)upload(lens, sizeof(int) * B);
+            a.max_q = plan.max_len; a.max_total = plan.max_total;
+            a.heads = heads; a.kv_heads = kv_heads; a.hd = hd; a.scale = scale;
+            // a workspace no launch has written: NaN wherever the combine reads past its own records
+            a.part_floats = dsocr::attention_past_part_floats(B, heads, plan.max_len, plan.max_total, hd);
+            a.part = (float*)alloc(sizeof(float) * a.part_floats);
+            check_hip(hipMemset(a.part, 0xFF, sizeof(float) * a.part_floats), "hipMemset");
+            if (!dsocr::attention_past_ok(a)) throw std::runtime_error("EINVAL: attention_past: shape outside the kernel's contract");
+            dsocr::launch_rope_kv(r, nullptr);
+            dsocr::launch_attention_past(a, nullptr);
+            check_hip(hipGetLastError(), "prefill attention (past) launch");
+            check_hip(hipDeviceSynchronize(), "prefill attention (past)");
         } catch (...) {
             for (void* p : bufs) (void)hipFree(p);
             throw;

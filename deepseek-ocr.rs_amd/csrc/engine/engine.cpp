@@ -184,7 +184,22 @@ struct Engine::Session {
         int kv_pos = 0;    // the device kv_pos of the slot: prompt + steps replayed since its admission
         int reported = 0;  // tokens the polls have handed out
         RowParams rp;      // host copy of the slot's device record (per_request)
+        int prompt = 0;    // prompt rows: K/V rows [0, prompt) never change after the admission
+        std::vector<int> ids;       // the prompt's ids and mask (what a prefix entry kept from this slot carries)
+        std::vector<uint8_t> mask;
     };
+    // A page prefix: K/V rows [0, rows) of every layer and kv head ([layers][kv_heads][rows][hd] of K, then of V) in
+    // a device allocation of its own (no captured graph reads it: not a frozen workspace), with the ids and mask of
+    // those rows for checking a later prompt against them.  Freed with the session or by session_prefix_drop.
+    struct PrefixEntry {
+        DeviceBuffer kv;
+        int rows = 0;
+        std::vector<int> ids;
+        std::vector<uint8_t> mask;
+    };
+    std::map<int, PrefixEntry> prefix;  // handle -> entry (at most Engine::kMaxPrefixEntries)
+    int next_handle = 1;
+    size_t prefix_admissions = 0, prefix_rows_reused = 0;
     std::vector<Slot> slot;
     HipGraphExec graph[9][2];  // the step for n active pages under the [exact, screened] head, captured on first use
     size_t head_steps[2] = {0, 0};  // steps replayed under the [exact, screened] head
@@ -1135,7 +1150,8 @@ std::vector<std::vector<float>> Engine::image_embeddings(const std::vector<const
 
 // ============================================================================ decoder
 void Engine::layer_forward_prefill(int l, int T, int B, const int* row_page, const int* row_pos, const long* q_off,
-                                   const long* kv_off, const long* o_off, const int* seq_len, int max_len, int Lmax) {
+                                   const long* kv_off, const long* o_off, const int* seq_len, int max_len, int Lmax,
+                                   const int* past, int max_total) {
     const LangConfig& L = cfg_.lang;
     DecLayer& d = layers_[l];
     hipStream_t st = stream_;
@@ -1155,27 +1171,43 @@ void Engine::layer_forward_prefill(int l, int T, int B, const int* row_page, con
     r.heads = L.heads; r.kv_heads = L.kv_heads; r.hd = hd; r.rope_dim = L.rope_dim; r.use_mla = L.use_mla;
     r.cos = rope_cos_; r.sin = rope_sin_; r.kc = kc; r.vc = vc; r.page_stride = page_stride_; r.head_stride = head_stride_;
     launch_rope_kv(r, st);
-    AttnArgs a;
-    a.q = {QKV, QKVN, hd, q_off};
-    a.k = {kc, hd, head_stride_, kv_off};
-    a.v = {vc, hd, head_stride_, kv_off};
-    a.o = CTX; a.o_row_stride = H; a.o_head_stride = hd; a.o_seq_off = o_off;
-    a.n_seq = B; a.L = max_len; a.seq_len = seq_len;
-    a.heads = L.heads; a.kv_heads = L.kv_heads; a.hd = hd;
-    a.scale = (float)(1.0 / std::sqrt((double)hd));
-    a.causal = 1;
-    // the key-piece workspace grows as L^2 (n_seq * heads * sum over query blocks of their pieces * 128 * (hd + 2)
-    // floats: 89 MB at 8 x 706 tokens, 2.8 GB at 8 x 4096); above 512 MB the prefill runs the one-block-per-
-    // query-block kernel, which needs none
-    constexpr size_t kPartCapFloats = (size_t)128 << 20;
-    const size_t part_floats = attention_causal_part_floats(B, L.heads, max_len, hd);
-    if (part_floats <= kPartCapFloats) {
-        a.part_floats = part_floats;
-        a.part = wsf("d_attn_part", a.part_floats);
+    if (past) {
+        // behind a cached past (a page prefix entry): seq_len counts the new rows, row_pos starts at the past
+        AttnPastArgs a;
+        a.q = {QKV, QKVN, hd, q_off};
+        a.k = {kc, hd, head_stride_, kv_off};
+        a.v = {vc, hd, head_stride_, kv_off};
+        a.o = CTX; a.o_row_stride = H; a.o_head_stride = hd; a.o_seq_off = o_off;
+        a.n_seq = B; a.past = past; a.n_q = seq_len; a.max_q = max_len; a.max_total = max_total;
+        a.heads = L.heads; a.kv_heads = L.kv_heads; a.hd = hd;
+        a.scale = (float)(1.0 / std::sqrt((double)hd));
+        a.part_floats = attention_past_part_floats(B, L.heads, max_len, max_total, hd);
+        a.part = wsf("d_attn_past", a.part_floats);
+        flops_acc_ += 4.0 * (double)T * max_total * hd * L.heads;  // (upper bound: every new row against every key)
+        launch_attention_past(a, st);
+    } else {
+        AttnArgs a;
+        a.q = {QKV, QKVN, hd, q_off};
+        a.k = {kc, hd, head_stride_, kv_off};
+        a.v = {vc, hd, head_stride_, kv_off};
+        a.o = CTX; a.o_row_stride = H; a.o_head_stride = hd; a.o_seq_off = o_off;
+        a.n_seq = B; a.L = max_len; a.seq_len = seq_len;
+        a.heads = L.heads; a.kv_heads = L.kv_heads; a.hd = hd;
+        a.scale = (float)(1.0 / std::sqrt((double)hd));
+        a.causal = 1;
+        // the key-piece workspace grows as L^2 (n_seq * heads * sum over query blocks of their pieces * 128 * (hd + 2)
+        // floats: 89 MB at 8 x 706 tokens, 2.8 GB at 8 x 4096); above 512 MB the prefill runs the one-block-per-
+        // query-block kernel, which needs none
+        constexpr size_t kPartCapFloats = (size_t)128 << 20;
+        const size_t part_floats = attention_causal_part_floats(B, L.heads, max_len, hd);
+        if (part_floats <= kPartCapFloats) {
+            a.part_floats = part_floats;
+            a.part = wsf("d_attn_part", a.part_floats);
+        }
+        for (int q = 0; q < B && q < (int)prefill_lens_.size(); ++q)
+            flops_acc_ += 2.0 * (double)prefill_lens_[q] * (prefill_lens_[q] + 1) * hd * L.heads;
+        launch_attention(a, st);
     }
-    for (int q = 0; q < B && q < (int)prefill_lens_.size(); ++q)
-        flops_acc_ += 2.0 * (double)prefill_lens_[q] * (prefill_lens_[q] + 1) * hd * L.heads;
-    launch_attention(a, st);
     (void)Lmax;
     (void)KVH;
     linear(CTX, T, H, d.o, X, H, 0, 1);
@@ -1994,11 +2026,11 @@ void Engine::reset_decode_state(GenState& g) {
 // last row of each page (the reference projects every position, transformer/model.rs:243-270;
 // only the last row is ever read).  The prefill runs it once on the prompts; use_cache = false
 // (generate_without_cache, model/mod.rs:2051-2283) re-runs it on prompt + generated (g.extra) every step.
-void Engine::forward_rows(GenState& g, const std::vector<int>& lens) {
+void Engine::forward_rows(GenState& g, const std::vector<int>& lens, const std::vector<int>& past) {
     const LangConfig& L = cfg_.lang;
     const int B = g.B, H = L.hidden, QKVN = layers_[0].qkv.N;
     hipStream_t st = stream_;
-    const PrefillPlan plan = prefill_row_plan(lens, QKVN, H, page_stride_);
+    const PrefillPlan plan = prefill_row_plan(lens, QKVN, H, page_stride_, past);
     const long Tn = plan.T;
     const int maxl = plan.max_len;
     prefill_lens_ = lens;
@@ -2008,8 +2040,9 @@ void Engine::forward_rows(GenState& g, const std::vector<int>& lens) {
         const GenRequest& rq = g.reqs[b];
         const int plen = g.prompt_len[b];
         size_t j = 0;
-        for (int i = 0; i < lens[b]; ++i) {
-            const long r = r0 + i;
+        // (behind a past the rows are prompt positions past[b] .., all of them text: session_admit_prefix checks it)
+        for (int i = past.empty() ? 0 : past[b], end = i + lens[b]; i < end; ++i) {
+            const long r = r0 + i - (past.empty() ? 0 : past[b]);
             if (i < plen && !rq.mask.empty() && rq.mask[i]) {
                 kind[r] = g.img[b][j].first;
                 index[r] = (int)g.img[b][j].second;
@@ -2032,8 +2065,12 @@ void Engine::forward_rows(GenState& g, const std::vector<int>& lens) {
     long* d_kv_off = upload("g_kvoff", plan.kv_off);
     long* d_o_off = upload("g_ooff", plan.o_off);
     int* d_plen = upload("g_plen", lens);
+    // every past == 0 is the plain prefill: the same launches, workspaces and order as without the argument
+    const bool behind = std::any_of(past.begin(), past.end(), [](int p) { return p > 0; });
+    const int* d_past = behind ? upload("g_past", past) : nullptr;
     for (int l = 0; l < L.layers; ++l)
-        layer_forward_prefill(l, (int)Tn, B, d_row_page, d_row_pos, d_q_off, d_kv_off, d_o_off, d_plen, maxl, g.Lmax);
+        layer_forward_prefill(l, (int)Tn, B, d_row_page, d_row_pos, d_q_off, d_kv_off, d_o_off, d_plen, maxl, g.Lmax,
+                              d_past, plan.max_total);
     std::vector<int> last_rows(B), lr_kind(B, ROW_HOST);
     r0 = 0;
     for (int b = 0; b < B; ++b) { r0 += lens[b]; last_rows[b] = (int)(r0 - 1); }
@@ -2585,15 +2622,9 @@ int Engine::session_admit(const GenRequest& rq, size_t max_new, bool seed_set, u
     return session_admit(rq, p);
 }
 
-int Engine::session_admit(const GenRequest& rq, const GenParams& rp) {
-    Session& s = open_session();
+void Engine::session_admit_checks(const Session& s, const GenRequest& rq, const GenParams& rp, bool behind_prefix) const {
     const size_t max_new = rp.max_new;
-    const bool seed_set = rp.seed_set;
-    uint64_t seed = rp.seed;
-    const LangConfig& L = cfg_.lang;
-    const int H = L.hidden, V = L.vocab;
-    hipStream_t st = stream_;
-    // every check first: nothing below may fail on the request itself once device state changes
+    const int V = cfg_.lang.vocab;
     if (!rp.use_cache || rp.trace) throw std::runtime_error("EINVAL: a session decodes with the K/V cache and without a logits trace");
     if (!s.per_request) {
         const GenParams& q = s.p;
@@ -2602,7 +2633,6 @@ int Engine::session_admit(const GenRequest& rq, const GenParams& rp) {
             throw std::runtime_error("EINVAL: this session's parameters are fixed (only max_new_tokens and the seed vary "
                                      "per request): open it with DSOCR_SESSION_PER_REQUEST");
     }
-    const RowParams row = resolve_row_params(rp);
     if (s.n >= s.S) throw std::runtime_error("EINVAL: every session slot is in use (retire one first)");
     const size_t P = rq.ids.size();
     if (P == 0) throw std::runtime_error("EINVAL: empty prompt");
@@ -2620,12 +2650,25 @@ int Engine::session_admit(const GenRequest& rq, const GenParams& rp) {
         rows = rq.n_image_rows;
     }
     for (size_t i = 0; i < P; ++i) n_mask += (!rq.mask.empty() && rq.mask[i]) ? 1 : 0;
-    if (n_mask != rows)
+    if (behind_prefix) {  // its image rows are the entry's: the request brings none (the mask is checked against the entry)
+        if (rq.page || rq.image_rows) throw std::runtime_error("EINVAL: a prefix admission carries no page and no image rows");
+    } else if (n_mask != rows) {
         throw std::runtime_error("EINVAL: prompt/image embedding mismatch: image embeddings provide " + std::to_string(rows) +
                                  " tokens but mask requires " + std::to_string(n_mask));
+    }
     for (size_t i = 0; i < P; ++i)
         if ((rq.mask.empty() || !rq.mask[i]) && (rq.ids[i] < 0 || rq.ids[i] >= V))
             throw std::runtime_error("EINVAL: token id out of bounds for vocab size");
+}
+
+int Engine::session_admit(const GenRequest& rq, const GenParams& rp) {
+    Session& s = open_session();
+    const size_t max_new = rp.max_new;
+    const LangConfig& L = cfg_.lang;
+    const int H = L.hidden, V = L.vocab;
+    // every check first: nothing below may fail on the request itself once device state changes
+    session_admit_checks(s, rq, rp, false);
+    const RowParams row = resolve_row_params(rp);
     const int slot = s.n;
     const std::vector<GenRequest> reqs{rq};
     GenParams gp = s.per_request ? rp : s.p;
@@ -2642,8 +2685,17 @@ int Engine::session_admit(const GenRequest& rq, const GenParams& rp) {
         ScopedSet page0(kv_page0_, slot);
         forward_rows(g, g.prompt_len);
     }
-    // the slot's rows in one launch from one staged buffer; the selection kernel advances the KV position, so
-    // it starts one behind (init_sampling)
+    return session_admit_tail(s, rq, rp, row);
+}
+
+// the slot's rows in one launch from one staged buffer (the selection kernel advances the KV position, so it starts
+// one behind: init_sampling), then the first selection on the logits the prefill left in the slot's s_logits row
+int Engine::session_admit_tail(Session& s, const GenRequest& rq, const GenParams& rp, const RowParams& row) {
+    const size_t max_new = rp.max_new, P = rq.ids.size();
+    const bool seed_set = rp.seed_set;
+    uint64_t seed = rp.seed;
+    const int slot = s.n;
+    hipStream_t st = stream_;
     const size_t stage_ints = (size_t)SS_HEAD + RNG_WORDS + P;
     int* h = (int*)pinned("ss_stage", stage_ints * 4);
     std::memset(h, 0, ((size_t)SS_HEAD + RNG_WORDS) * 4);
@@ -2680,9 +2732,111 @@ int Engine::session_admit(const GenRequest& rq, const GenParams& rp) {
     if (s.logprobs) launch_dec_lp_final(lp, st);  // entry 0 of the slot
     session_sentinels(s);
     HIP_CHECK(hipStreamSynchronize(st));
-    s.slot[slot] = Session::Slot{max_new, (int)P, 0, row};
+    Session::Slot& sl = s.slot[slot];
+    sl.max_new = max_new; sl.kv_pos = (int)P; sl.reported = 0; sl.rp = row; sl.prompt = (int)P;
+    sl.ids = rq.ids;
+    sl.mask = rq.mask.empty() ? std::vector<uint8_t>(P, 0) : rq.mask;
     ++s.n;
     return slot;
+}
+
+// ---- page prefix cache.  The copy both ways is launch_session_prefix_copy between the slot's cache rows and the
+// entry's dense block; an entry never aliases a slot, so it survives the slot's retirement, moves and reuse.
+static PrefixCopyArgs prefix_copy_args(const LangConfig& L, float* kc, float* vc, int S, int Lcap, long page_stride,
+                                       long head_stride, int slot, int rows, float* entry, int to_slot) {
+    PrefixCopyArgs c;
+    c.kc = kc; c.vc = vc; c.layers = L.layers; c.slots = S; c.kv_heads = L.kv_heads; c.cap_rows = Lcap; c.hd = L.head_dim;
+    c.layer_stride = (long)S * page_stride; c.page_stride = page_stride; c.head_stride = head_stride;
+    c.slot = slot; c.rows = rows; c.to_slot = to_slot; c.entry = entry;
+    return c;
+}
+
+int Engine::session_prefix_keep(int slot, int rows) {
+    Session& s = open_session();
+    if (slot < 0 || slot >= s.n) throw std::runtime_error("EINVAL: slot " + std::to_string(slot) + " is not active");
+    const Session::Slot& sl = s.slot[slot];
+    if (rows < 1 || rows > sl.prompt)
+        throw std::runtime_error("EINVAL: a prefix has 1.." + std::to_string(sl.prompt) + " rows of this slot's prompt");
+    if ((int)s.prefix.size() >= kMaxPrefixEntries)
+        throw std::runtime_error("EINVAL: the session holds " + std::to_string(kMaxPrefixEntries) + " prefix entries (drop one first)");
+    const LangConfig& L = cfg_.lang;
+    Session::PrefixEntry e;
+    e.kv = DeviceBuffer(session_prefix_floats(L.layers, L.kv_heads, rows, L.head_dim) * sizeof(float));  // ENOMEM
+    e.rows = rows;
+    e.ids.assign(sl.ids.begin(), sl.ids.begin() + rows);
+    e.mask.assign(sl.mask.begin(), sl.mask.begin() + rows);
+    launch_session_prefix_copy(prefix_copy_args(L, kc_, vc_, s.S, s.Lcap, page_stride_, head_stride_, slot, rows,
+                                                (float*)e.kv.get(), 0), stream_);
+    HIP_CHECK(hipStreamSynchronize(stream_));
+    const int handle = s.next_handle++;
+    s.prefix.emplace(handle, std::move(e));
+    return handle;
+}
+
+int Engine::session_admit_prefix(int handle, const GenRequest& rq, const GenParams& rp) {
+    Session& s = open_session();
+    const LangConfig& L = cfg_.lang;
+    const int H = L.hidden, V = L.vocab;
+    // every check first: a refused admission changes nothing on the device
+    const auto it = s.prefix.find(handle);
+    if (it == s.prefix.end()) throw std::runtime_error("EINVAL: unknown prefix handle " + std::to_string(handle));
+    const Session::PrefixEntry& e = it->second;
+    session_admit_checks(s, rq, rp, true);
+    const int P = (int)rq.ids.size(), rows = e.rows;
+    if (P < rows + 1)
+        throw std::runtime_error("EINVAL: the prompt must be longer than the prefix's " + std::to_string(rows) +
+                                 " rows (the last row's logits come from a new row)");
+    for (int i = 0; i < P; ++i) {
+        const uint8_t m = rq.mask.empty() ? 0 : (rq.mask[i] ? 1 : 0);
+        if (i < rows) {
+            if (rq.ids[i] != e.ids[i] || m != (e.mask[i] ? 1 : 0))
+                throw std::runtime_error("EINVAL: the prompt differs from the prefix entry at position " + std::to_string(i));
+        } else if (m) {
+            throw std::runtime_error("EINVAL: image position " + std::to_string(i) + " lies behind the prefix (the request carries no image rows)");
+        }
+    }
+    const RowParams row = resolve_row_params(rp);
+    const int slot = s.n;
+    hipStream_t st = stream_;
+    launch_session_prefix_copy(prefix_copy_args(L, kc_, vc_, s.S, s.Lcap, page_stride_, head_stride_, slot, rows,
+                                                (float*)e.kv.get(), 1), st);
+    const std::vector<GenRequest> reqs{rq};
+    GenParams gp = s.per_request ? rp : s.p;
+    gp.max_new = rp.max_new;
+    GenState g(reqs, gp, nullptr, nullptr);
+    g.prompt_len = {P};
+    g.max_p = P;
+    g.img.resize(1);
+    g.Lmax = s.Lcap;
+    g.SX = s.sx + (size_t)slot * H;
+    g.LOGITS = s.logits + (size_t)slot * V;
+    g.extra.resize(1);
+    {
+        ScopedSet page0(kv_page0_, slot);
+        forward_rows(g, {P - rows}, {rows});  // the suffix alone, behind the copied rows
+    }
+    const int got = session_admit_tail(s, rq, rp, row);
+    ++s.prefix_admissions;
+    s.prefix_rows_reused += (size_t)rows;
+    return got;
+}
+
+void Engine::session_prefix_drop(int handle) {
+    Session& s = open_session();
+    const auto it = s.prefix.find(handle);
+    if (it == s.prefix.end()) throw std::runtime_error("EINVAL: unknown prefix handle " + std::to_string(handle));
+    HIP_CHECK(hipStreamSynchronize(stream_));  // (an admission that copied from it has finished: admissions synchronise)
+    s.prefix.erase(it);
+}
+
+Engine::PrefixStats Engine::session_prefix_stats() const {
+    if (!sess_) throw std::runtime_error("EINVAL: no decode session is open on this engine");
+    PrefixStats out;
+    out.entries = sess_->prefix.size();
+    for (const auto& kv : sess_->prefix) out.bytes += kv.second.kv.bytes();
+    out.admissions = sess_->prefix_admissions;
+    out.rows_reused = sess_->prefix_rows_reused;
+    return out;
 }
 
 void Engine::session_step_body(Session& s, bool screened) {

@@ -257,6 +257,17 @@ class Engine {
     std::vector<int64_t> session_retire(int slot, int* moved_from);
     void session_close();
     bool session_info(SessionInfo* out) const;  // false: no session is open
+    // ---- page prefix cache: K/V rows [0, rows) of a live slot's prompt kept in an entry of their
+    // own; a later request whose prompt starts with the same ids / mask is admitted behind a copy of them and
+    // prefills only its remaining rows.  Entries are not workspaces: no captured graph reads them.
+    static constexpr int kMaxPrefixEntries = 64;
+    struct PrefixStats {
+        size_t entries = 0, bytes = 0, admissions = 0, rows_reused = 0;
+    };
+    int session_prefix_keep(int slot, int rows);  // -> handle; ENOMEM when the allocation fails
+    int session_admit_prefix(int handle, const GenRequest& rq, const GenParams& p);
+    void session_prefix_drop(int handle);
+    PrefixStats session_prefix_stats() const;
 
   private:
     // ---- loading
@@ -308,7 +319,8 @@ class Engine {
     void embed_pages(GenState& g);
     void plan_image_rows(GenState& g);
     void reset_decode_state(GenState& g);
-    void forward_rows(GenState& g, const std::vector<int>& lens);
+    // past (optional, per sequence): rows [0, past[b]) are already in the cache and lens[b] counts the rows after them
+    void forward_rows(GenState& g, const std::vector<int>& lens, const std::vector<int>& past = {});
     void init_sampling(GenState& g);
     bool poll(GenState& g);
     void stream_tokens(GenState& g, int n);
@@ -336,7 +348,12 @@ class Engine {
     void profile_gemvs(DecodeProfile& prof, int iters, const std::vector<int>& moe_layers);
     void profile_step_context(DecodeProfile& prof, int iters, int n_moe);
     void layer_forward_prefill(int l, int T, int B, const int* row_page, const int* row_pos, const long* q_off,
-                               const long* kv_off, const long* o_off, const int* seq_len, int max_len, int Lmax);
+                               const long* kv_off, const long* o_off, const int* seq_len, int max_len, int Lmax,
+                               const int* past = nullptr, int max_total = 0);
+    // what both admissions check about the request's parameters, the free slot and the context it needs
+    void session_admit_checks(const Session& s, const GenRequest& rq, const GenParams& rp, bool behind_prefix) const;
+    // the tail both admissions share: the slot's rows from one staged buffer, then the first selection
+    int session_admit_tail(Session& s, const GenRequest& rq, const GenParams& rp, const RowParams& row);
 
     ModelConfig cfg_;
     int device_ = 0;

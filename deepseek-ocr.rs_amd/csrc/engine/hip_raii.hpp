@@ -95,6 +95,28 @@ class PinnedBuffer {
     T* p_ = nullptr;
 };
 
+// a device allocation of its own (beside the engine's named workspaces); throws ENOMEM when hipMalloc fails
+class DeviceBuffer {
+  public:
+    DeviceBuffer() = default;
+    explicit DeviceBuffer(size_t bytes) : bytes_(bytes) {
+        if (hipMalloc(&p_, bytes ? bytes : 16) != hipSuccess) {
+            (void)hipGetLastError();
+            p_ = nullptr;
+            throw std::runtime_error("ENOMEM: hipMalloc(" + std::to_string(bytes) + ") failed");
+        }
+    }
+    ~DeviceBuffer() { if (p_) (void)hipFree(p_); }
+    DeviceBuffer(DeviceBuffer&& o) noexcept : p_(std::exchange(o.p_, nullptr)), bytes_(std::exchange(o.bytes_, 0)) {}
+    DeviceBuffer& operator=(DeviceBuffer&& o) noexcept { std::swap(p_, o.p_); std::swap(bytes_, o.bytes_); return *this; }
+    void* get() const { return p_; }
+    size_t bytes() const { return bytes_; }
+
+  private:
+    void* p_ = nullptr;
+    size_t bytes_ = 0;
+};
+
 // sets `ref` for the scope and puts the old value back on every exit
 template <typename T>
 class ScopedSet {

@@ -355,16 +355,23 @@ inline size_t image_placeholder_count(int base, int image_size, bool crop_mode, 
 // row r of sequence b at position i going to page b, slot i of the KV cache.  Per row: its page and position
 // (rope_kv); per sequence: where its rows start in the q|k|v buffer (row width qkv_ld), in the attention output
 // (row width H) and in the cache (page_stride floats per page).  max_len is the attention grid's length.
+// A prefill behind a cached past (`past` given: rows [0, past[b]) of sequence b are already in the cache): the rows
+// are the new ones only, their positions start at past[b], and max_total is the longest past + new length.
 struct PrefillPlan {
     std::vector<int> row_page, row_pos;
     std::vector<long> q_off, kv_off, o_off;
     long T = 0;
-    int max_len = 0;
+    int max_len = 0, max_total = 0;
 };
-inline PrefillPlan prefill_row_plan(const std::vector<int>& lens, long qkv_ld, long H, long page_stride) {
+inline PrefillPlan prefill_row_plan(const std::vector<int>& lens, long qkv_ld, long H, long page_stride,
+                                    const std::vector<int>& past = {}) {
     PrefillPlan p;
     const int B = (int)lens.size();
-    for (int b = 0; b < B; ++b) { p.T += lens[b]; p.max_len = std::max(p.max_len, lens[b]); }
+    for (int b = 0; b < B; ++b) {
+        p.T += lens[b];
+        p.max_len = std::max(p.max_len, lens[b]);
+        p.max_total = std::max(p.max_total, lens[b] + (past.empty() ? 0 : past[b]));
+    }
     p.row_page.resize(p.T);
     p.row_pos.resize(p.T);
     p.q_off.resize(B);
@@ -374,7 +381,7 @@ inline PrefillPlan prefill_row_plan(const std::vector<int>& lens, long qkv_ld, l
     for (int b = 0; b < B; ++b) {
         for (int i = 0; i < lens[b]; ++i) {
             p.row_page[r0 + i] = b;
-            p.row_pos[r0 + i] = i;
+            p.row_pos[r0 + i] = (past.empty() ? 0 : past[b]) + i;
         }
         p.q_off[b] = r0 * qkv_ld;
         p.kv_off[b] = (long)b * page_stride;

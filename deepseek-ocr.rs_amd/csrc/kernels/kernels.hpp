@@ -192,6 +192,36 @@ struct AttnPrefixArgs {
 bool attention_prefix_ok(const AttnPrefixArgs& a);
 void launch_attention_prefix(const AttnPrefixArgs& a, hipStream_t s);  // throws EINVAL outside the contract
 
+// ------------------------------------------------------------------ prefill behind a cached past (attention_past.hip)
+// Causal attention of every sequence's n_q[s] new rows against its past[s] + n_q[s] cached keys: query row i has
+// position past[s] + i and sees keys [0, past[s] + i].  q rows come from the packed q|k|v buffer, k / v from the f32
+// cache (row_stride == hd), o rows go to the attention output, all at per-sequence element offsets (seq_off, never
+// null here).  One workgroup per (128-key piece, head, sequence x 32-query tile), one wave per 32 keys of the piece,
+// every wave writing its unnormalised (m, l, O) record per query into `part`; a second launch combines a query's
+// records in key order.  hd 32, 64 or 128, heads % kv_heads == 0, 1 <= n_q[s] <= max_q, past[s] >= 0,
+// past[s] + n_q[s] <= max_total (the host-side bounds size the grid and the workspace).
+// The workspace holds one record per (query, 32-key tile): n_seq * heads * ceil(max_q / 32) * ceil(max_total / 32)
+// * 32 * (hd + 2) floats, i.e. it grows as max_q * max_total (3.8 MB at 6 rows behind 700; 0.7 GB at 1024 rows
+// behind 3072, both with 10 heads of 128).  There is no form without it: a caller that prefills long chunks behind a
+// past has to bound max_q per launch.
+struct AttnPastArgs {
+    AttnView q, k, v;
+    float* o = nullptr;
+    long o_row_stride = 0, o_head_stride = 0;
+    const long* o_seq_off = nullptr;
+    int n_seq = 0;
+    const int* past = nullptr;  // [n_seq] (device)
+    const int* n_q = nullptr;   // [n_seq] (device)
+    int max_q = 0, max_total = 0;
+    int heads = 0, kv_heads = 0, hd = 0;
+    float scale = 1.f;
+    float* part = nullptr;      // attention_past_part_floats(...) floats
+    size_t part_floats = 0;
+};
+size_t attention_past_part_floats(int n_seq, int heads, int max_q, int max_total, int hd);
+bool attention_past_ok(const AttnPastArgs& a);
+void launch_attention_past(const AttnPastArgs& a, hipStream_t s);  // throws EINVAL outside the contract
+
 // ------------------------------------------------------------------ OCR2 encoder row ops (ocr2_ops.hip)
 // out [n][2 P][D] = [feat rows of image i | query table] (qwen2.rs:157-177): feat [n][P][D] token rows, query [P][D]
 void launch_ocr2_build_seq(const float* feat, const float* query, int n, int P, int D, float* out, hipStream_t s);
@@ -645,6 +675,21 @@ struct SlotInitArgs {
     float* lp = nullptr; int* lp_top_id = nullptr; float* lp_top = nullptr; int lp_k = 0; long out_cap = 0;
 };
 void launch_session_slot_init(const SlotInitArgs& a, hipStream_t s);
+// K / V rows [0, rows) of every layer and kv head between slot `slot` of the session caches (layout as SlotMoveArgs)
+// and a dense prefix entry [layers][kv_heads][rows][hd] floats of K followed by as many of V (16-byte aligned):
+// to_slot == 0 copies slot -> entry, 1 entry -> slot.  16-byte nontemporal loads and stores on a (row chunk, kv head,
+// layer) grid; rows >= `rows` of the slot, every other slot and (to_slot == 1) the entry are not written.
+struct PrefixCopyArgs {
+    float* kc = nullptr; float* vc = nullptr;
+    int layers = 0, slots = 0, kv_heads = 0, cap_rows = 0, hd = 0;
+    long layer_stride = 0, page_stride = 0, head_stride = 0;
+    int slot = 0, rows = 0, to_slot = 0;
+    float* entry = nullptr;
+};
+inline size_t session_prefix_floats(int layers, int kv_heads, int rows, int hd) {
+    return (size_t)2 * layers * kv_heads * rows * hd;
+}
+void launch_session_prefix_copy(const PrefixCopyArgs& a, hipStream_t s);  // throws EINVAL outside the contract
 // Screened lm_head (lmhead.hip): int8 rows + per-row scale / error bound give every row an
 // interval [lo, hi] that provably contains the exact kernel's logit; each block keeps the best
 // lower bound of its unbanned rows and the rows whose hi reached its running threshold (its own

@@ -94,6 +94,58 @@ void launch_session_slot_move(const SlotMoveArgs& a, hipStream_t s) {
     DSOCR_LAUNCH(session_slot_move_kernel, dim3(nchunk + 1, a.kv_heads, a.layers), dim3(SM_BLOCK), 0, s, b);
 }
 
+// Grid (row chunks, kv heads, layers): rows [0, rows) of one (layer, kv head) are one contiguous run of
+// rows * hd / 4 16-byte chunks on both sides (the slot's head starts at row 0, the entry's block is dense), copied
+// as in session_slot_move_kernel.  TO_SLOT picks the direction; the entry holds every K block, then every V block.
+template <bool TO_SLOT>
+__global__ __launch_bounds__(SM_BLOCK) void session_prefix_copy_kernel(PrefixCopyArgs a) {
+    const long n16 = (long)a.rows * a.hd / 4;
+    const long so = (long)blockIdx.z * a.layer_stride + (long)a.slot * a.page_stride + (long)blockIdx.y * a.head_stride;
+    const long eo = ((long)blockIdx.z * a.kv_heads + blockIdx.y) * a.rows * a.hd;
+    const long ev = (long)a.layers * a.kv_heads * a.rows * a.hd;  // the entry's V blocks follow its K blocks
+    const f32x4* ks = reinterpret_cast<const f32x4*>(TO_SLOT ? a.entry + eo : a.kc + so);
+    const f32x4* vs = reinterpret_cast<const f32x4*>(TO_SLOT ? a.entry + ev + eo : a.vc + so);
+    f32x4* kd = reinterpret_cast<f32x4*>(TO_SLOT ? a.kc + so : a.entry + eo);
+    f32x4* vd = reinterpret_cast<f32x4*>(TO_SLOT ? a.vc + so : a.entry + ev + eo);
+    const long c0 = (long)blockIdx.x * SM_BLOCK * SM_VEC + threadIdx.x;
+    f32x4 k[SM_VEC], v[SM_VEC];
+#pragma unroll
+    for (int u = 0; u < SM_VEC; ++u) {
+        const long c = c0 + (long)u * SM_BLOCK;
+        if (c < n16) {
+            k[u] = __builtin_nontemporal_load(ks + c);
+            v[u] = __builtin_nontemporal_load(vs + c);
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < SM_VEC; ++u) {
+        const long c = c0 + (long)u * SM_BLOCK;
+        if (c < n16) {
+            __builtin_nontemporal_store(k[u], kd + c);
+            __builtin_nontemporal_store(v[u], vd + c);
+        }
+    }
+}
+
+void launch_session_prefix_copy(const PrefixCopyArgs& a, hipStream_t s) {
+    if (!a.kc || !a.vc || !a.entry) throw std::runtime_error("EINVAL: prefix copy needs the K / V caches and an entry");
+    if (a.layers <= 0 || a.kv_heads <= 0 || a.hd <= 0 || a.hd % 4 || a.cap_rows <= 0 || a.slots <= 0)
+        throw std::runtime_error("EINVAL: prefix copy needs head_dim % 4 == 0 and a positive shape");
+    if (a.slot < 0 || a.slot >= a.slots) throw std::runtime_error("EINVAL: prefix copy slot outside the session");
+    if (a.rows < 1 || a.rows > a.cap_rows) throw std::runtime_error("EINVAL: prefix copy rows must be 1..cap_rows");
+    if (a.head_stride < (long)a.cap_rows * a.hd || a.page_stride < (long)a.kv_heads * a.head_stride ||
+        a.layer_stride < (long)a.slots * a.page_stride || a.head_stride % 4 || a.page_stride % 4 || a.layer_stride % 4)
+        throw std::runtime_error("EINVAL: prefix copy strides do not hold the cache shape (or break 16-byte alignment)");
+    if ((reinterpret_cast<uintptr_t>(a.kc) | reinterpret_cast<uintptr_t>(a.vc) | reinterpret_cast<uintptr_t>(a.entry)) & 15)
+        throw std::runtime_error("EINVAL: prefix copy needs 16-byte aligned caches and entry");
+    if (a.kv_heads > 65535 || a.layers > 65535) throw std::runtime_error("EINVAL: prefix copy grid");
+    const long n16 = (long)a.rows * a.hd / 4;
+    const int per = SM_BLOCK * SM_VEC;
+    const dim3 grid((unsigned)((n16 + per - 1) / per), a.kv_heads, a.layers);
+    if (a.to_slot) DSOCR_LAUNCH(session_prefix_copy_kernel<true>, grid, dim3(SM_BLOCK), 0, s, a);
+    else DSOCR_LAUNCH(session_prefix_copy_kernel<false>, grid, dim3(SM_BLOCK), 0, s, a);
+}
+
 // stage: [SS_HEAD header ints (RowParams at SS_ROWPAR) | rng words | ctx ids]; the slot's context row is written whole (zeros past ctx_len)
 __global__ __launch_bounds__(SM_BLOCK) void session_slot_init_kernel(SlotInitArgs a) {
     const int* h = a.stage;

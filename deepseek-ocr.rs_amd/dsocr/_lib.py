@@ -126,6 +126,8 @@ EXPORTS = [
     "dsocr_session_close", "dsocr_session_info", "dsocr_k_session_slot_move",
     "dsocr_session_open_ex", "dsocr_session_admit_params", "dsocr_session_head_steps", "dsocr_k_select_rows",
     "dsocr_generate_logprobs", "dsocr_session_logprobs", "dsocr_k_logprobs", "dsocr_k_logprobs_penalty",
+    "dsocr_session_prefix_keep", "dsocr_session_admit_prefix", "dsocr_session_prefix_drop", "dsocr_session_prefix_stats",
+    "dsocr_k_prefill_attention_past", "dsocr_k_session_prefix_copy",
 ]
 
 # model variants behind the deepseek engine (dsocr_engine_variant)
@@ -245,6 +247,13 @@ def lib():
     L.dsocr_generate_logprobs.argtypes = [vp, sz, C.POINTER(RequestC), C.POINTER(DecodeParamsC), C.POINTER(ResultC), sz,
                                           C.POINTER(LogprobsC)]
     L.dsocr_session_logprobs.argtypes = [vp, i32, sz, sz, sz, vp, vp, vp]
+    L.dsocr_session_prefix_keep.argtypes = [vp, i32, sz, C.POINTER(i32)]
+    L.dsocr_session_admit_prefix.argtypes = [vp, i32, C.POINTER(RequestC), C.POINTER(DecodeParamsC), C.POINTER(i32)]
+    L.dsocr_session_prefix_drop.argtypes = [vp, i32]
+    L.dsocr_session_prefix_stats.argtypes = [vp, C.POINTER(sz), C.POINTER(sz), C.POINTER(sz), C.POINTER(sz)]
+    L.dsocr_k_prefill_attention_past.argtypes = [i32, i32, i32, i32, i32, i32, i32, f32, C.POINTER(i32), C.POINTER(i32),
+                                                 vp, vp, vp, vp, vp, vp]
+    L.dsocr_k_session_prefix_copy.argtypes = [i32, i32, i32, i32, i32, vp, vp, i32, i32, vp, i32]
     L.dsocr_k_logprobs.argtypes = [i32, i32, i32, vp, i32, vp, vp, vp, vp, vp]
     L.dsocr_k_logprobs_penalty.argtypes = [i32, i32, i32, vp, i32, vp, vp, vp, i32, vp, f32, vp, vp, vp]
     L.dsocr_k_session_slot_move.argtypes = [i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, C.c_longlong, vp, vp,

@@ -501,6 +501,48 @@ class Session:
                                         0 if seed is None else 1, seed or 0, C.byref(slot)))
         return slot.value
 
+    # ------------------------------------------------------------------ page prefix cache
+    def keep_prefix(self, slot: int, rows: int) -> int:
+        """K/V rows [0, rows) of a live slot's prompt into a prefix entry (dsocr_session_prefix_keep); returns its
+        handle.  1 <= rows <= the slot's prompt length; the slot may have decoded any number of steps."""
+        h = C.c_int(-1)
+        check(lib().dsocr_session_prefix_keep(self._e._h, int(slot), int(rows), C.byref(h)))
+        return h.value
+
+    def admit_prefix(self, handle: int, ids, mask=None, max_new_tokens: Optional[int] = None,
+                     seed: Optional[int] = None, params: Optional[DecodeParameters] = None,
+                     eos_token_id: Optional[int] = None, ignore_eos: Optional[bool] = None,
+                     logprobs: Optional[int] = None) -> int:
+        """``admit`` for a prompt that starts with the entry's rows (dsocr_session_admit_prefix): ``ids`` / ``mask``
+        are the whole prompt's, no page and no image rows; vision and the prefill of the entry's rows are skipped.
+        The keywords are ``admit``'s (without ``params``: the session's parameters with this ``max_new_tokens`` /
+        ``seed``)."""
+        if logprobs is not None:
+            if not self.has_logprobs:
+                raise DsocrError(1, "this session was opened without logprobs")
+            if not 0 <= int(logprobs) <= MAX_TOP_LOGPROBS:
+                raise DsocrError(1, f"logprobs must be 0..{MAX_TOP_LOGPROBS}")
+        keep = []
+        req = self._e._request(ids, mask, None, None, keep)
+        if params is None:
+            params = DecodeParameters(**{**self.params.__dict__,
+                                         "max_new_tokens": self.out_cap if max_new_tokens is None else int(max_new_tokens),
+                                         "seed": seed})
+        pc = _params_c(params, self._eos if eos_token_id is None else int(eos_token_id),
+                       self._ignore_eos if ignore_eos is None else bool(ignore_eos))
+        slot = C.c_int(-1)
+        check(lib().dsocr_session_admit_prefix(self._e._h, int(handle), C.byref(req), C.byref(pc), C.byref(slot)))
+        return slot.value
+
+    def drop_prefix(self, handle: int) -> None:
+        check(lib().dsocr_session_prefix_drop(self._e._h, int(handle)))
+
+    def prefix_stats(self) -> dict:
+        """{"entries", "bytes", "admissions", "rows_reused"} of the session's prefix entries."""
+        v = [C.c_size_t() for _ in range(4)]
+        check(lib().dsocr_session_prefix_stats(self._e._h, *[C.byref(x) for x in v]))
+        return dict(zip(("entries", "bytes", "admissions", "rows_reused"), (int(x.value) for x in v)))
+
     def head_steps(self) -> dict:
         """Decode steps replayed under each lm_head + selection head since the session opened."""
         a, b = C.c_size_t(), C.c_size_t()

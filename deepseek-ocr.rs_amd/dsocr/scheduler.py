@@ -17,6 +17,14 @@ runs for everyone) and ``submit(..., logprobs=K)`` asks for a request's entries:
 and the outcome carries ``token_logprobs`` / ``top_logprobs``.  Without the scheduler's flag such a request runs alone
 through ``engine.decode(..., logprobs=K)`` after the session drained, like any request that does not fit.
 
+Page prefix cache: ``BatchScheduler(..., prefix_cache=N)`` (default 0: nothing changes) keeps the K/V rows of up to N
+pages' prompt prefixes (BOS and the image rows) in the session.  After a one-image request is admitted its prefix is
+kept (``Session.keep_prefix``, rows = index of the last image position + 1) under the key (SHA-256 of the image as
+submitted, the vision settings, the prefix ids); a later request with the same key is admitted through
+``Session.admit_prefix`` and skips vision and the prefill of those rows.  Eviction is LRU; an evicted handle is
+dropped before the next keep.  Prompts with several images, exclusive requests and prompts with no text after the
+image bypass the cache.  ``prefix_hits`` / ``prefix_misses`` count the lookups.
+
 The engine object needs ``open_session(slots, max_context, params)`` (admit / step / poll / retire / close, see
 ``dsocr.engine.Session``), ``decode`` and, for prompts with several images, ``image_embeddings``; tests drive the
 scheduler with a scripted fake.
@@ -24,7 +32,7 @@ scheduler with a scripted fake.
 from __future__ import annotations
 
 import threading
-from collections import deque
+from collections import OrderedDict, deque
 from concurrent.futures import Future
 from dataclasses import dataclass, field, fields
 from typing import Any, Callable, Optional, Sequence
@@ -57,6 +65,24 @@ class _Request:
     logprobs: Optional[int] = None  # alternatives per token the request asked for
     token_lp: list = field(default_factory=list)
     top_lp: list = field(default_factory=list)
+    prefix_key: Any = None  # prefix cache: (image digest, vision settings, prefix ids), or None to bypass it
+    prefix_rows: int = 0
+
+
+def _image_digest(im) -> str:
+    """SHA-256 of an image as it was submitted: raw bytes as they are, an array or a PIL image by shape and pixels."""
+    import hashlib
+    h = hashlib.sha256()
+    if isinstance(im, (bytes, bytearray, memoryview)):
+        h.update(bytes(im))
+        return h.hexdigest()
+    import numpy as np
+    if hasattr(im, "convert"):  # PIL image
+        h.update(str(getattr(im, "mode", "")).encode())
+    arr = np.ascontiguousarray(np.asarray(im))
+    h.update(repr((arr.shape, arr.dtype.str)).encode())
+    h.update(arr.tobytes())
+    return h.hexdigest()
 
 
 def _default_prepare(engine, tokenizer, prompt, images, vision):
@@ -91,9 +117,18 @@ def _decode_text(tokenizer, ids) -> str:
 class BatchScheduler:
     def __init__(self, engine, tokenizer, slots: int, max_context: int,
                  defaults: DecodeParameters = DecodeParameters(), vision: Optional[VisionSettings] = None,
-                 prepare: Optional[Callable] = None, per_request_params: bool = False, logprobs: bool = False):
+                 prepare: Optional[Callable] = None, per_request_params: bool = False, logprobs: bool = False,
+                 prefix_cache: int = 0):
         if not 1 <= int(slots) <= 8:
             raise ValueError("a session has 1..8 slots")
+        if not 0 <= int(prefix_cache) <= 64:
+            raise ValueError("prefix_cache is 0..64 entries (a session holds at most 64)")
+        self.prefix_cache = int(prefix_cache)
+        self._prefix: OrderedDict = OrderedDict()  # key -> handle of the open session, least recently used first
+        self.prefix_hits = 0
+        self.prefix_misses = 0
+        self.prefix_fallbacks = 0      # hits whose admit_prefix was refused and that were admitted plainly instead
+        self.prefix_keep_failures = 0  # keeps (or the evictions before them) the session refused
         self.engine, self.tokenizer = engine, tokenizer
         self.slots, self.max_context = int(slots), int(max_context)
         self.defaults = defaults
@@ -156,6 +191,15 @@ class BatchScheduler:
             rq.pages = list(pages)
         rq.logprobs = None if logprobs is None else int(logprobs)
         rq.exclusive = not self.compatible(params, len(rq.ids)) or (rq.logprobs is not None and not self.logprobs)
+        if self.prefix_cache and len(rq.images) == 1 and not rq.exclusive and any(rq.mask):
+            rows = max(i for i, m in enumerate(rq.mask) if m) + 1
+            if rows < len(rq.ids):  # some text follows the image: the last row's logits come from a new row
+                try:
+                    rq.prefix_key = (_image_digest(rq.images[0]),
+                                     (vision.base_size, vision.image_size, bool(vision.crop_mode)), tuple(rq.ids[:rows]))
+                    rq.prefix_rows = rows
+                except Exception:  # noqa: BLE001 - an image that cannot be hashed is served without the cache
+                    rq.prefix_key = None
         with self._cv:
             if self._stop:
                 fut.set_exception(RuntimeError("scheduler is closed"))
@@ -206,6 +250,7 @@ class BatchScheduler:
 
     def _close_session(self):
         s, self._session = self._session, None
+        self._prefix.clear()  # the handles die with their session
         if s is not None:
             try:
                 s.close()
@@ -272,19 +317,44 @@ class BatchScheduler:
                 rows = np.concatenate(self.engine.image_embeddings(rq.pages), axis=0)
             kw = {} if rq.logprobs is None else {"logprobs": rq.logprobs}
             if self.per_request_params:
-                slot = self._session.admit(rq.ids, rq.mask, rq.page, rows, params=rq.params, **kw)
+                kw["params"] = rq.params
             else:
-                slot = self._session.admit(rq.ids, rq.mask, rq.page, rows, max_new_tokens=rq.params.max_new_tokens,
-                                           seed=rq.params.seed, **kw)
+                kw.update(max_new_tokens=rq.params.max_new_tokens, seed=rq.params.seed)
+            handle = self._prefix.get(rq.prefix_key) if rq.prefix_key is not None else None
+            if handle is not None:  # the page's prefix is cached: no vision, only the rows behind it are prefilled
+                self._prefix.move_to_end(rq.prefix_key)
+                self.prefix_hits += 1
+                try:
+                    slot = self._session.admit_prefix(handle, rq.ids, rq.mask, **kw)
+                except Exception:  # noqa: BLE001 - refused behind the entry: the plain admission decides (and reports)
+                    self.prefix_fallbacks += 1
+                    slot = self._session.admit(rq.ids, rq.mask, rq.page, rows, **kw)
+            else:
+                slot = self._session.admit(rq.ids, rq.mask, rq.page, rows, **kw)
         except Exception as e:  # noqa: BLE001 - the request's own error: the running slots are untouched
             rq.future.set_exception(e)
             return False
         if slot != len(self._active):
             raise RuntimeError(f"session admitted into slot {slot}, expected {len(self._active)}")
+        if rq.prefix_key is not None and handle is None:
+            self.prefix_misses += 1
+            self._keep_prefix(rq, slot)
         rq.kv_pos = len(rq.ids)
         self._active.append(rq)
         self.max_active = max(self.max_active, len(self._active))
         return True
+
+    def _keep_prefix(self, rq, slot):
+        """The prefix of the page just admitted into `slot`, kept under its key; the least recently used handle is
+        dropped first when the cache is full.  Best effort: a keep the session refuses (memory, its 64 entries)
+        leaves the request as it is and the page uncached."""
+        try:
+            while len(self._prefix) >= self.prefix_cache:
+                _, old = self._prefix.popitem(last=False)
+                self._session.drop_prefix(old)
+            self._prefix[rq.prefix_key] = self._session.keep_prefix(slot, rq.prefix_rows)
+        except Exception:  # noqa: BLE001 - counted, so that a cache that keeps nothing shows
+            self.prefix_keep_failures += 1
 
     def _deliver(self, status):
         for st in status:

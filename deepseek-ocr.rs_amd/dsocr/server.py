@@ -496,17 +496,24 @@ def add_scheduler_args(p):
                    help="with --slots: open the decode session with per-token log-probabilities (the exact lm_head "
                         "runs for every request), so requests with `logprobs: true` join the running batch instead "
                         "of waiting for it to drain; off by default")
+    p.add_argument("--prefix-cache", type=int, default=0,
+                   help="with --slots: keep the K/V rows of up to N pages' image prefixes (LRU), so a later prompt on "
+                        "the same image under the same vision settings skips vision and the prefill of those rows; "
+                        "0 = off (the default)")
 
 
 def make_scheduler(state: ServerState, slots: int, max_context: int, per_request_params: bool = False,
-                   logprobs: bool = False):
+                   logprobs: bool = False, prefix_cache: int = 0):
     """The state's scheduler for --slots N (None for 0: requests take the lock path).  per_request_params: the
-    DecodeParameters merge_decode builds from a request body are admitted into the session as that request's own."""
+    DecodeParameters merge_decode builds from a request body are admitted into the session as that request's own.
+    prefix_cache: --prefix-cache N (ValueError without --slots: the entries live in the decode session)."""
+    if not 0 <= prefix_cache <= 64 or (prefix_cache and not slots):
+        raise ValueError("--prefix-cache needs --slots (the prefix entries live in the decode session) and N in 0..64")
     if not slots:
         return None
     from .scheduler import BatchScheduler
     return BatchScheduler(state.engine, state.tokenizer, slots, max_context, state.defaults, state.vision,
-                          per_request_params=per_request_params, logprobs=logprobs)
+                          per_request_params=per_request_params, logprobs=logprobs, prefix_cache=prefix_cache)
 
 
 def main(argv=None) -> int:
@@ -524,6 +531,8 @@ def main(argv=None) -> int:
     p.add_argument("--port", type=int, default=8000)
     add_scheduler_args(p)
     args = p.parse_args(argv)
+    if not 0 <= args.prefix_cache <= 64 or (args.prefix_cache and not args.slots):
+        p.error("--prefix-cache needs --slots and N in 0..64 (a session holds at most 64 prefix entries)")
     config = model_config(args)  # --model deepseek-ocr | deepseek-ocr-2: the bundled config and vision defaults
     engine = load_model(ModelLoadArgs(config_path=config, weights_path=args.weights, snapshot_path=args.snapshot,
                                       snapshot_packed=getattr(args, "snapshot_packed", None),
@@ -531,7 +540,8 @@ def main(argv=None) -> int:
                                       synthetic_seed=args.synthetic_seed))
     state = ServerState(engine, load_tokenizer(args.tokenizer, _vocab_of(config)), args.model,
                         vision_settings(args), decode_params(args))
-    state.scheduler = make_scheduler(state, args.slots, args.max_context, args.per_request_params, args.logprobs)
+    state.scheduler = make_scheduler(state, args.slots, args.max_context, args.per_request_params, args.logprobs,
+                                     args.prefix_cache)
     import uvicorn
     uvicorn.run(create_app(state), host=args.host, port=args.port)
     return 0

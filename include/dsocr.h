@@ -297,6 +297,27 @@ dsocr_status dsocr_session_retire(dsocr_engine* e, int slot, int64_t* out_ids, s
  * passes the slot's out_len.  dsocr_session_retire does not return them: read them before it. */
 dsocr_status dsocr_session_logprobs(dsocr_engine* e, int slot, size_t first, size_t count, size_t top_k, float* token_lp,
                                     int64_t* top_id, float* top_lp);
+/* ---- page prefix cache: the K/V rows of a prompt's first `rows` positions (BOS and the page's image rows) kept
+ * beside the session, so that a later prompt on the same page skips vision and the prefill of those rows.
+ *   dsocr_session_prefix_keep: copies rows [0, rows) of a live slot (1 <= rows <= the slot's prompt length; prompt
+ *   rows never change after the admission, so the slot may have decoded any number of steps) into a new entry that
+ *   also keeps the prompt's first `rows` ids and mask bytes.  The entry lives in its own device allocation until
+ *   dsocr_session_prefix_drop or dsocr_session_close; a session holds at most DSOCR_MAX_PREFIX_ENTRIES.
+ *   DSOCR_ENOMEM when the allocation fails, DSOCR_EINVAL for a bad slot / rows or a full table.
+ *   dsocr_session_admit_prefix: dsocr_session_admit_params for a request whose prompt starts with the entry's:
+ *   req carries ids and mask of the WHOLE prompt and neither a page nor image rows.  Every check runs before any
+ *   device state changes: the checks of dsocr_session_admit_params, prompt_len >= rows + 1 (the last row's logits
+ *   come from a new row), ids and mask equal to the entry's over [0, rows), no mask byte set from `rows` on.  Then
+ *   the entry is copied into the new slot and only rows [rows, prompt_len) are prefilled behind it.
+ *   dsocr_session_prefix_stats: entries alive, device bytes they hold, prefix admissions and the rows those
+ *   admissions did not prefill, since the session opened (any pointer may be NULL). */
+#define DSOCR_MAX_PREFIX_ENTRIES 64
+dsocr_status dsocr_session_prefix_keep(dsocr_engine* e, int slot, size_t rows, int* handle);
+dsocr_status dsocr_session_admit_prefix(dsocr_engine* e, int handle, const dsocr_request* req,
+                                        const dsocr_decode_params* params, int* slot);
+dsocr_status dsocr_session_prefix_drop(dsocr_engine* e, int handle);
+dsocr_status dsocr_session_prefix_stats(const dsocr_engine* e, size_t* entries, size_t* bytes, size_t* admissions,
+                                        size_t* rows_reused);
 dsocr_status dsocr_session_close(dsocr_engine* e);
 /* DSOCR_EINVAL when no session is open */
 dsocr_status dsocr_session_info(const dsocr_engine* e, dsocr_session_desc* out);
@@ -508,6 +529,15 @@ dsocr_status dsocr_k_decode_attention(int B, int heads, int kv_heads, int hd, in
 dsocr_status dsocr_k_prefill_attention(int B, int heads, int kv_heads, int hd, int rope_dim, int use_mla, int cap,
                                        float scale, const int* lens, float* qkv, const float* cos, const float* sin,
                                        float* kc, float* vc, float* o, int use_part);
+/* The same stage for a prefill behind a cached past (a prompt suffix admitted through a page prefix entry): sequence
+ * b brings lens[b] >= 1 new rows at positions past[b] .. past[b] + lens[b] - 1 (past[b] >= 0, past[b] + lens[b] <=
+ * cap; host arrays).  The caches arrive holding rows [0, past[b]) of every sequence; the new rows are rotated at
+ * their shifted positions and appended, then o [T][heads * hd] = softmax(scale * q.K^T) . V of every new row over
+ * keys [0, its own position] (launch_attention_past: key pieces + a combine launch; its workspace enters filled
+ * with NaN).  cos / sin [>= cap][rope_dim].  DSOCR_EINVAL as dsocr_k_prefill_attention, before any launch. */
+dsocr_status dsocr_k_prefill_attention_past(int B, int heads, int kv_heads, int hd, int rope_dim, int use_mla, int cap,
+                                            float scale, const int* past, const int* lens, float* qkv, const float* cos,
+                                            const float* sin, float* kc, float* vc, float* o);
 /* One page's decode attention sub-layer as the engine runs it (block.rs:446-804 at seq_len 1): RMSNorm +
  * q/k/v projection (Wqkv [3H][H], 16-bit) with RoPE in the epilogue, K/V append at kv_pos[s], softmax
  * attention over positions 0..kv_pos[s], for `steps` launches back to back (x [steps][H], kv_pos [steps],
@@ -631,6 +661,12 @@ dsocr_status dsocr_k_session_slot_move(int layers, int slots, int kv_heads, int 
                                        int* kv_len, int* kv_pos, int* ctx, long long ctx_cap, int* ctx_len, int* out,
                                        long long out_cap, int* out_len, int* done, int* tok, uint32_t* rng,
                                        int rng_words, int* ban, long long ban_ld, float* x, int H, int src, int dst);
+/* launch_session_prefix_copy once: K / V rows [0, rows) of every layer and kv head between slot `slot` of the f32
+ * caches kc / vc [layers][slots][kv_heads][cap][hd] and a dense entry of 2 * layers * kv_heads * rows * hd floats
+ * ([layers][kv_heads][rows][hd] of K, then of V); to_slot 0: slot -> entry, 1: entry -> slot.  Nothing else is
+ * written.  DSOCR_EINVAL: rows outside 1..cap, slot outside the caches, hd % 4 != 0.  Device pointers. */
+dsocr_status dsocr_k_session_prefix_copy(int layers, int slots, int kv_heads, int cap, int hd, float* kc, float* vc,
+                                         int slot, int rows, float* entry, int to_slot);
 
 /* ---- dots.ocr vision tower (BASELINE configs[3]; crates/infer-dots/src/vision/dots_vit.rs
  *      DotsVisionModel::load / forward, vision/preprocess.rs preprocess_image).  The tower runs in the

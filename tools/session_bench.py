@@ -14,10 +14,15 @@ Page i generates MAX_NEW[i] tokens: drawn once, numpy default_rng(4011).choice(L
       page's entries (20 alternatives) read before its retire
   (h) (c) with DSOCR_SCREEN=0: the exact head without log-probabilities, so (h) - (g) is what the two launches and
       the reads cost and (c) - (h) what the head switch costs
+  (p) the page prefix cache, on its own traffic: 16 full-size image pages, each asked two prompts in
+      arrival order (32 requests of 64 tokens) through one 8-slot session, with the cache off (every request pays
+      vision and the full prefill: the parent's code path) and on (the second prompt is admitted behind the kept
+      prefix); the two alternate ROUNDS times; requests/s, steps and the wall time of a plain admission, a keep and
+      a prefix admission
 The arms alternate ROUNDS times; pages/s and decode steps are reported as median [min, max].  Also: the wall time
 of one admission while other slots wait, and one session_slot_move of a 1200-row full-size page against its bytes.
 
-    python tools/session_bench.py [--rounds 3] [--pages 32] [--arms a,b,c,d,e,f,g,h] [--out profiles/session_bench.json]
+    python tools/session_bench.py [--rounds 3] [--pages 32] [--arms a,b,c,d,e,f,g,h,p] [--out profiles/session_bench.json]
 """
 import argparse
 import ctypes as C
@@ -163,6 +168,89 @@ def run_scheduler_fixed(eng, reqs, max_new, P, mixed=True):
     return se.steps, {"exclusive_runs": alone}
 
 
+PREFIX_PROMPTS = ["<image>\nConvert the document to markdown.", "<image>\nFree OCR."]
+PREFIX_NEW = 64  # tokens per request of the prefix arms
+
+
+def image_requests(eng, pages):
+    """`pages` full-size image pages (bench.py's synthetic_page, pixels HBM-resident), each under PREFIX_PROMPTS:
+    [(page, [(ids, mask)] per prompt, prefix rows)]."""
+    from dsocr import Page, VisionSettings, build_prompt_tokens
+    from dsocr.synth import SyntheticTokenizer, synthetic_page
+    tok, vs, out = SyntheticTokenizer(eng.vocab), VisionSettings(1024, 640, True), []
+    for i in range(pages):
+        page = Page(synthetic_page(i), vs, eng)
+        prompts = [build_prompt_tokens(tok, p, [page.n_image_tokens]) for p in PREFIX_PROMPTS]
+        out.append((page, prompts, max(j for j, m in enumerate(prompts[0][1]) if m) + 1))
+    return out
+
+
+def run_prefix(eng, docs, P, cache):
+    """Every page's prompts in arrival order (page 0 prompt 0, page 0 prompt 1, page 1 prompt 0, ...) through one
+    8-slot session.  cache: the first prompt's admission is followed by keep_prefix, the later prompts go through
+    admit_prefix, and the handle is dropped after the page's last prompt.  Wall times per call, in ms."""
+    reqs = [(d, j) for d in range(len(docs)) for j in range(len(PREFIX_PROMPTS))]
+    need = max(len(ids) for _, prompts, _ in docs for ids, _ in prompts) + PREFIX_NEW + 1
+    t_plain, t_prefix, t_keep, handles = [], [], [], {}
+    done, nxt, active = 0, 0, 0
+    with eng.open_session(SLOTS, need, P(max_new_tokens=PREFIX_NEW), ignore_eos=True) as s:
+        while done < len(reqs):
+            while active < SLOTS and nxt < len(reqs):
+                d, j = reqs[nxt]
+                page, prompts, rows = docs[d]
+                ids, mask = prompts[j]
+                t = time.perf_counter()
+                if cache and d in handles:
+                    s.admit_prefix(handles[d], ids, mask, max_new_tokens=PREFIX_NEW)
+                    t_prefix.append((time.perf_counter() - t) * 1e3)
+                    if j == len(PREFIX_PROMPTS) - 1:
+                        s.drop_prefix(handles.pop(d))
+                else:
+                    slot = s.admit(ids, mask, page, max_new_tokens=PREFIX_NEW)
+                    t_plain.append((time.perf_counter() - t) * 1e3)
+                    if cache:
+                        t = time.perf_counter()
+                        handles[d] = s.keep_prefix(slot, rows)
+                        t_keep.append((time.perf_counter() - t) * 1e3)
+                active, nxt = active + 1, nxt + 1
+            for st in sorted(s.step(8), key=lambda x: -x.slot):
+                if st.done:
+                    s.retire(st.slot)
+                    active, done = active - 1, done + 1
+        steps, stats = s.info()["steps"], s.prefix_stats()
+    return steps, {"admit_plain_ms": t_plain, "admit_prefix_ms": t_prefix, "keep_prefix_ms": t_keep,
+                   "prefix_stats": stats}
+
+
+def prefix_arms(eng, P, pages, rounds):
+    """The page prefix cache: cache off (the parent's code path) and on, alternating."""
+    docs = image_requests(eng, pages)
+    for cache in (False, True):  # warm-up: workspaces and graphs
+        run_prefix(eng, docs[:4], P, cache)
+    res = {k: {"pages_s": [], "steps": [], "plain": [], "prefix": [], "keep": []} for k in ("cache_off", "cache_on")}
+    for _ in range(rounds):
+        for k, cache in (("cache_off", False), ("cache_on", True)):
+            t = time.perf_counter()
+            steps, extra = run_prefix(eng, docs, P, cache)
+            r = res[k]
+            r["pages_s"].append(len(docs) * len(PREFIX_PROMPTS) / (time.perf_counter() - t))
+            r["steps"].append(int(steps))
+            r["plain"] += extra["admit_plain_ms"]
+            r["prefix"] += extra["admit_prefix_ms"]
+            r["keep"] += extra["keep_prefix_ms"]
+            r["stats"] = extra["prefix_stats"]
+    out = {"pages": pages, "prompts_per_page": len(PREFIX_PROMPTS), "max_new": PREFIX_NEW, "rounds": rounds,
+           "prefix_rows": docs[0][2], "prompt_len": [len(ids) for ids, _ in docs[0][1]]}
+    for k, r in res.items():
+        out[k] = {"requests_s": mmm(r["pages_s"]), "requests_s_rounds": r["pages_s"], "steps": mmm(r["steps"]),
+                  "admit_plain_ms": mmm(r["plain"]), "prefix_stats": r["stats"]}
+        if r["prefix"]:
+            out[k]["admit_prefix_ms"] = mmm(r["prefix"])
+            out[k]["keep_prefix_ms"] = mmm(r["keep"])
+    out["on_over_off"] = out["cache_on"]["requests_s"]["median"] / out["cache_off"]["requests_s"]["median"]
+    return out
+
+
 def slot_move_alone(cfg, rows=1200, reps=10):
     """dsocr_k_session_slot_move at the full-size cache shape, two slots: call wall time (launch + synchronise)."""
     from dsocr._lib import check, lib
@@ -201,6 +289,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--pages", type=int, default=32)
     ap.add_argument("--arms", default="a,b,c,d,e,f", help="which arms run (letters, comma separated)")
+    ap.add_argument("--prefix-pages", type=int, default=16, help="image pages of arm p (two prompts each)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     import dsocr
@@ -250,6 +339,8 @@ def main():
     if "d_over_c" in out:
         c = out["c_session"]["pages_s"]
         out["d_within_c_spread"] = bool(c["min"] <= med("d_session_per_request_greedy") <= c["max"])
+    if "p" in a.arms.split(","):
+        out["p_prefix_cache"] = prefix_arms(eng, P, a.prefix_pages, a.rounds)
     eng.close()
     out["slot_move_1200_rows"] = slot_move_alone(json.load(open(dsocr.FULL_CONFIG)))
     line = json.dumps(out)
