@@ -1279,6 +1279,70 @@ dsocr_status dsocr_k_qkv_attention(int fused, int steps, int H, int heads, int h
         if (used_fused) *used_fused = took ? 1 : 0;
     });
 }
+dsocr_status dsocr_k_qkv_attention_layers(int defer, int layers, int H, int heads, int hd, int max_len, float scale,
+                                          float eps, const float* x, const float* norm_w, const void* Wqkv, int wdtype,
+                                          const float* cos, const float* sin, float* kc, float* vc, const int* kv_pos,
+                                          float* o, uint32_t* qkv_copies, uint32_t* part_copies, int* err_word) {
+    return guarded([&] {
+        if (layers <= 0 || H <= 0 || heads <= 0 || hd != 128 || heads * hd != H || max_len <= 0)
+            throw std::runtime_error("EINVAL: qkv_attention_layers needs 128-dim MHA heads with heads * hd == H");
+        if (wdtype != dsocr::WDT_F16 && wdtype != dsocr::WDT_BF16) throw std::runtime_error("EINVAL: 16-bit weights only");
+        if (!x || !norm_w || !Wqkv || !cos || !sin || !kc || !vc || !kv_pos || !o || !qkv_copies || !part_copies || !err_word)
+            throw std::runtime_error("EINVAL: NULL argument");
+        const int QKVN = 3 * H;
+        const size_t pb = dsocr::dec_attn_workspace(1, heads, hd, max_len), pw = pb / 4;
+        const size_t cache = (size_t)heads * max_len * hd;
+        float* row[2] = {nullptr, nullptr};
+        float* part[2] = {nullptr, nullptr};
+        int* cnt = nullptr;
+        auto release = [&] {
+            for (int c = 0; c < 2; ++c) { (void)hipFree(row[c]); (void)hipFree(part[c]); }
+            (void)hipFree(cnt);
+        };
+        try {
+            for (int c = 0; c < 2; ++c) {
+                check_hip(hipMalloc(&row[c], sizeof(float) * QKVN), "hipMalloc");
+                check_hip(hipMalloc(&part[c], pb), "hipMalloc");
+                dsocr::dec_qkv_sentinel_init(row[c], QKVN, nullptr);
+                dsocr::dec_attn_part_init(part[c], pb, nullptr);
+            }
+            check_hip(hipMalloc(&cnt, sizeof(int) * (heads + 1)), "hipMalloc");
+            check_hip(hipMemset(cnt, 0, sizeof(int) * (heads + 1)), "hipMemset");
+            // the engine's plan (Engine::decode_step): deferred - layer l on copy l & 1, every layer but the last
+            // leaves its refill to the next, layer l >= 1 cleans copy (l - 1) & 1; else copy 0, refilled in-launch
+            for (int l = 0; l < layers; ++l) {
+                const int c = defer ? l & 1 : 0;
+                dsocr::DecGemvArgs g;
+                g.M = 1; g.N = QKVN; g.K = H; g.W = (const uint16_t*)Wqkv + (size_t)l * QKVN * H; g.ldw = H; g.wdtype = wdtype;
+                g.y = row[c]; g.ldy = QKVN; g.x = x + (size_t)l * H; g.ldx = H; g.norm_w = norm_w; g.eps = eps;
+                dsocr::DecRopeEpi re;
+                re.kv_pos = kv_pos + l; re.cos = cos; re.sin = sin; re.hd = hd; re.rot_rows = 2 * H;
+                dsocr::DecAttn2Args a;
+                a.qkv = row[c]; a.ld = QKVN; a.kv_pos = kv_pos + l; a.B = 1; a.heads = heads; a.kv_heads = heads;
+                a.hd = hd; a.rope_dim = hd; a.use_mla = 0; a.max_len = max_len; a.cos = cos; a.sin = sin;
+                a.kc = kc + (size_t)l * cache; a.vc = vc + (size_t)l * cache; a.head_stride = (long)max_len * hd;
+                a.page_stride = (long)heads * max_len * hd; a.scale = scale; a.part = part[c];
+                a.o = o + (size_t)l * H; a.o_ld = H; a.counters = cnt; a.err = cnt + heads; a.prerot = 1;
+                if (defer) {
+                    a.no_refill = l + 1 < layers;
+                    if (l >= 1) { a.clean_qkv = row[c ^ 1]; a.clean_part = part[c ^ 1]; }
+                }
+                if (!dsocr::dec_qkv_attn_ok(g, re, a)) throw std::runtime_error("EINVAL: outside dec_qkv_attn's range");
+                dsocr::launch_dec_qkv_attn(g, re, a, nullptr);
+            }
+            check_hip(hipDeviceSynchronize(), "qkv_attention_layers");
+            check_hip(hipMemcpy(err_word, cnt + heads, sizeof(int), hipMemcpyDeviceToHost), "d2h");
+            for (int c = 0; c < 2; ++c) {
+                check_hip(hipMemcpy(qkv_copies + (size_t)c * QKVN, row[c], sizeof(float) * QKVN, hipMemcpyDeviceToHost), "d2h");
+                check_hip(hipMemcpy(part_copies + (size_t)c * pw, part[c], pb, hipMemcpyDeviceToHost), "d2h");
+            }
+        } catch (...) {
+            release();
+            throw;
+        }
+        release();
+    });
+}
 int dsocr_k_poll_wait_fits(long waiting_blocks, int api_blocks_per_cu, int cus) {
     return dsocr::poll_wait_fits(waiting_blocks, api_blocks_per_cu, cus) ? 1 : 0;
 }

@@ -172,7 +172,8 @@ struct Engine::Session {
     bool per_request = false;  // every slot has its own RowParams; the head is chosen per burst
     bool screened = false;  // fixed parameters: the screened head at every n (else the exact head at every n)
     size_t part_floats = 0, qkv_floats = 0;
-    float *sx = nullptr, *logits = nullptr, *part = nullptr, *qkv = nullptr;
+    float *sx = nullptr, *logits = nullptr;
+    float *part[2] = {nullptr, nullptr}, *qkv[2] = {nullptr, nullptr};  // the two hand-off copies (attn_args)
     int *ctx = nullptr, *ctx_len = nullptr, *kvpos = nullptr, *kvlen = nullptr, *done = nullptr, *outlen = nullptr,
         *out = nullptr, *tok = nullptr, *ban = nullptr, *stage = nullptr, *err = nullptr;
     uint32_t* rng = nullptr;
@@ -1314,18 +1315,25 @@ MoeDecodeArgs Engine::moe_args(int l, int B, float* X) {
 
 // Decode attention arguments of layer l (shared by decode_step and profile_decode, which points q/k/v, the
 // position and the output at scratch rows): RoPE + K/V append + flash-decoding on the named workspaces
-DecAttn2Args Engine::attn_args(int l, int B, int Lmax) {
+// The hand-off buffers (the sentinel-filled q/k/v row and the flash-decoding records) exist in two copies,
+// "s_qkv" / "s_part" and "s_qkv1" / "s_part1".  Every launch but the fused one-page one uses copy 0 and leaves
+// it sentinel-filled itself.  With the deferred refill (att_refill_defer) layer l of the fused one-page path
+// uses copy l & 1, leaves the words it read as they are and cleans the copy of layer l - 1; the last layer of
+// the step refills its own.  Invariant: at every step boundary every word of both copies holds the sentinel.
+std::string Engine::handoff_ws(const char* base, int copy) { return copy ? std::string(base) + "1" : std::string(base); }
+
+DecAttn2Args Engine::attn_args(int l, int B, int Lmax, int copy) {
     const LangConfig& L = cfg_.lang;
     const int hd = L.head_dim, QKVN = layers_[l].qkv.N;
     const long layer_kv = this->layer_kv(B);
     DecAttn2Args da;
-    da.qkv = wsf("s_qkv", (size_t)B * QKVN); da.ld = QKVN; da.kv_pos = wsi("s_kvpos", B); da.B = B;
+    da.qkv = wsf(handoff_ws("s_qkv", copy), (size_t)B * QKVN); da.ld = QKVN; da.kv_pos = wsi("s_kvpos", B); da.B = B;
     da.heads = L.heads; da.kv_heads = L.kv_heads; da.hd = hd; da.rope_dim = L.rope_dim; da.use_mla = L.use_mla;
     da.max_len = Lmax; da.cos = rope_cos_; da.sin = rope_sin_;
     da.kc = kc_ + (long)l * layer_kv; da.vc = vc_ + (long)l * layer_kv;
     da.page_stride = page_stride_; da.head_stride = head_stride_;
     da.scale = (float)(1.0 / std::sqrt((double)hd));
-    da.part = wsf("s_part", dec_attn_workspace(B, L.heads, hd, Lmax) / 4 + 16);
+    da.part = wsf(handoff_ws("s_part", copy), dec_attn_workspace(B, L.heads, hd, Lmax) / 4 + 16);
     da.o = wsf("s_ctx", (size_t)B * L.hidden); da.o_ld = L.hidden;
     da.counters = wsi("s_attn_cnt", (size_t)B * L.heads);
     da.err = wsi("s_err", 4);
@@ -1475,25 +1483,51 @@ void Engine::decode_step(int B, int Lmax) {
         // markers (bench.py prices its launches with the expert counts of a wave-span generate of the same batch)
         if (waves) launch_span_reduce(span_slots_, span_rec(kind, l), span_step_, span_cap_, ids, n_ids, st);
     };
-    for (int l = 0; l < L.layers; ++l) {
-        DecLayer& d = layers_[l];
+    // the q/k/v projection, its RoPE epilogue (one page) and the attention of layer l on hand-off copy `copy`
+    const bool one_page = B == 1 && !L.use_mla && L.rope_dim == hd;
+    auto qkv_args = [&](int l, int copy, DecGemvArgs& g, DecRopeEpi& re, DecAttn2Args& da) {
+        const DecLayer& d = layers_[l];
         const int QKVN = d.qkv.N;
-        float* QKV = wsf("s_qkv", (size_t)B * QKVN);
-        // attention: [norm] qkv -> rope + append + flash-decoding -> o_proj + residual
-        DecAttn2Args da = attn_args(l, B, Lmax);
+        da = attn_args(l, B, Lmax, copy);
         da.kv_delay = att_kv_delay();
         da.span = chain_active_ ? chain_slots(l, SPAN_ATTN) : ((span_rec_ && (span_mode_ & SPAN_WAVES)) ? span_slots_ : nullptr);
-        // q/k/v projection with the input RMSNorm fused; one page: RoPE in the projection's epilogue, so the
-        // attention reads q / k already rotated (B <= 2: the row block-staged; 3..8: dec_gemv_lds / dec_mm)
-        DecGemvArgs g;
+        g = DecGemvArgs();
         g.M = B; g.N = QKVN; g.K = H; g.W = d.qkv.W; g.ldw = H; g.wdtype = d.qkv.wdt; g.bias = d.qkv.b;
-        g.y = QKV; g.ldy = QKVN; g.x = X; g.ldx = H; g.norm_w = d.in_norm.w; g.eps = L.rms_eps;
-        bool attn_done = false;
-        if (B == 1 && !L.use_mla && L.rope_dim == hd) {
-            DecRopeEpi re;
+        g.y = const_cast<float*>(da.qkv); g.ldy = QKVN; g.x = X; g.ldx = H; g.norm_w = d.in_norm.w; g.eps = L.rms_eps;
+        re = DecRopeEpi();
+        if (one_page) {
             re.kv_pos = kv_pos; re.cos = rope_cos_; re.sin = rope_sin_; re.hd = hd;
             re.rot_rows = (L.heads + L.kv_heads) * hd;
             da.prerot = 1;
+        }
+    };
+    // deferred refill (att_refill_defer, attn_args): the layers that take the fused one-page launch, known
+    // before the loop - a layer hands its refill on only to a fused launch right behind it in the same step,
+    // and cleans the other copy only behind a launch that handed its refill on
+    std::vector<char> defer_l(L.layers, 0);
+    if (one_page && qkv_attn_fused() && att_refill_defer() && !(step_skip_ & SKIP_ATTN))
+        for (int l = 0; l < L.layers; ++l) {
+            DecGemvArgs g; DecRopeEpi re; DecAttn2Args da;
+            qkv_args(l, l & 1, g, re, da);
+            defer_l[l] = dec_qkv_attn_ok(g, re, da);
+        }
+    for (int l = 0; l < L.layers; ++l) {
+        DecLayer& d = layers_[l];
+        const int QKVN = d.qkv.N;
+        // attention: [norm] qkv -> rope + append + flash-decoding -> o_proj + residual
+        // q/k/v projection with the input RMSNorm fused; one page: RoPE in the projection's epilogue, so the
+        // attention reads q / k already rotated (B <= 2: the row block-staged; 3..8: dec_gemv_lds / dec_mm)
+        DecGemvArgs g; DecRopeEpi re; DecAttn2Args da;
+        qkv_args(l, defer_l[l] ? l & 1 : 0, g, re, da);
+        if (defer_l[l]) {
+            da.no_refill = l + 1 < L.layers && defer_l[l + 1];
+            if (l >= 1 && defer_l[l - 1]) {
+                const DecAttn2Args prev = attn_args(l - 1, B, Lmax, (l - 1) & 1);
+                da.clean_qkv = const_cast<float*>(prev.qkv); da.clean_part = prev.part;
+            }
+        }
+        bool attn_done = false;
+        if (one_page) {
             if (qkv_attn_fused() && dec_qkv_attn_ok(g, re, da)) {
                 // one launch: the attention blocks stream their K / V chunk beside the projection
                 // (s_qkv stays sentinel-filled between launches; SKIP_ATTN, the profile's variant without
@@ -1665,6 +1699,16 @@ void Engine::ensure_mm_weights(int B) {
 int Engine::att_kv_delay() {
     const char* e = getenv("DSOCR_ATT_KV_DELAY");
     return e ? std::max(0, atoi(e)) : 150;
+}
+
+// the fused one-page launch's sentinel refill moved off the merging blocks' exit onto the next layer's
+// projection blocks (two hand-off copies, attn_args); DSOCR_ATT_REFILL_DEFER=0 (A/B switch): one copy, every
+// launch refills what it read.  Read once per decode step (so once per captured step graph): both forms leave
+// every hand-off word sentinel-filled at the step boundary, so either may follow the other - which is what lets
+// one process time both (tools/ab_trace.py)
+bool Engine::att_refill_defer() {
+    const char* e = getenv("DSOCR_ATT_REFILL_DEFER");
+    return !(e && atoi(e) == 0);
 }
 
 bool Engine::qkv_attn_fused() {
@@ -2001,10 +2045,12 @@ void Engine::reset_decode_state(GenState& g) {
     HIP_CHECK(hipMemsetAsync(wsi("s_dntick", (size_t)H / 64 + 1), 0, sizeof(int) * (H / 64 + 1), st));
     {  // decode attention records: sentinel-filled before the first launch (the polling merge refills them)
         const size_t pf = dec_attn_workspace(B, L.heads, L.head_dim, Lmax) / 4 + 16;
-        dec_attn_part_init(wsf("s_part", pf), pf * 4, st);
         // the fused q/k/v + attention launch (one page) takes q / k / v by polling this row: sentinel-filled
         const size_t qn = (size_t)B * layers_[0].qkv.N;
-        dec_qkv_sentinel_init(wsf("s_qkv", qn), qn, st);
+        for (int c = 0; c < 2; ++c) {  // both hand-off copies (attn_args)
+            dec_attn_part_init(wsf(handoff_ws("s_part", c), pf), pf * 4, st);
+            dec_qkv_sentinel_init(wsf(handoff_ws("s_qkv", c), qn), qn, st);
+        }
         wsf("p_qkv_skip", qn);  // the profile's variant without attention projects here (allocated before capture)
     }
     HIP_CHECK(hipMemsetAsync(wsi("s_dtick", dec_mm_splitk_ticks(H)), 0, sizeof(int) * dec_mm_splitk_ticks(H), st));
@@ -2487,9 +2533,11 @@ void Engine::session_open(int S, int max_context, const GenParams& p, bool per_r
         HIP_CHECK(hipMemsetAsync(s.err, 0, sizeof(int) * 4, st));
         for (int n = 1; n <= S; ++n)
             s.part_floats = std::max(s.part_floats, dec_attn_workspace(n, L.heads, L.head_dim, s.Lcap) / 4 + 16);
-        s.part = wsf("s_part", s.part_floats);
         s.qkv_floats = (size_t)S * QKVN;
-        s.qkv = wsf("s_qkv", s.qkv_floats);
+        for (int c = 0; c < 2; ++c) {
+            s.part[c] = wsf(handoff_ws("s_part", c), s.part_floats);
+            s.qkv[c] = wsf(handoff_ws("s_qkv", c), s.qkv_floats);
+        }
         wsf("p_qkv_skip", s.qkv_floats);
         // the per-slot rows, zeroed: the dry steps below read kv_pos 0 and a zero input row
         s.sx = wsf("s_x", (size_t)S * H);
@@ -2575,8 +2623,10 @@ void Engine::session_open(int S, int max_context, const GenParams& p, bool per_r
 // enter a launch sentinel-filled.  A step at another n leaves them in that n's layout, so they are refilled
 // whenever n changes (admit, retire)
 void Engine::session_sentinels(const Session& s) {
-    dec_attn_part_init(s.part, s.part_floats * 4, stream_);
-    dec_qkv_sentinel_init(s.qkv, s.qkv_floats, stream_);
+    for (int c = 0; c < 2; ++c) {
+        dec_attn_part_init(s.part[c], s.part_floats * 4, stream_);
+        dec_qkv_sentinel_init(s.qkv[c], s.qkv_floats, stream_);
+    }
 }
 
 // selection arguments for the B slots from slot0 on (the step: slot0 = 0, B = n; an admission: its slot, B = 1)

@@ -309,7 +309,8 @@ class Engine {
     bool persist_ok(int B, int Lmax);
     void ensure_persist();
     MoeDecodeArgs moe_args(int l, int B, float* X);
-    DecAttn2Args attn_args(int l, int B, int Lmax);
+    DecAttn2Args attn_args(int l, int B, int Lmax, int copy = 0);
+    static std::string handoff_ws(const char* base, int copy);
     void decode_head(int B, DecSampleArgs& sa, const SampleArgs& pen, bool screened, const DecLpArgs* lp = nullptr);
     void reserve_head_ws(int B);
     LmHeadQ8Args head_q8_args(int B);
@@ -417,6 +418,7 @@ class Engine {
     enum StepSkip : int { SKIP_GATEUP = 1, SKIP_DOWN = 2, SKIP_ATTN = 4 };
     int step_skip_ = 0;
     static bool qkv_attn_fused();
+    static bool att_refill_defer();
     static int att_kv_delay();
     unsigned long long* span_slots_ = nullptr;  // device [SPAN_SLOTS][2]
     unsigned long long* span_rec_ = nullptr;    // device [SPAN_KINDS][layers][span_cap_][4]

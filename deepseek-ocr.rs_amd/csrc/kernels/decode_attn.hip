@@ -127,7 +127,8 @@ __device__ __forceinline__ float group_sum(float v) {
 // same launch, stored write-through into a row that enters the launch sentinel-filled; this block
 // issues its K / V cache loads first, then polls its rows until no word holds the sentinel, and the
 // merging block (chunk 0) refills them once every chunk of the head has read them (its record is
-// written after that read).  The cache stream overlaps the projection's weight stream.
+// written after that read) - or, with DecAttn2Args::no_refill, leaves them to the next launch's projection
+// blocks, which clean the copy they do not use.  The cache stream overlaps the projection's weight stream.
 template <int HD, bool PREROT, bool POLL, bool FUSED>
 __device__ __forceinline__ void dec_attn_body(const DecAttn2Args& a, const int c, const int h, const int b) {
     constexpr int CH = DA_CH;
@@ -385,7 +386,8 @@ __device__ __forceinline__ void dec_attn_body(const DecAttn2Args& a, const int c
         __builtin_amdgcn_raw_buffer_store_b128(bits, rsrc, (c * PR + 4 + tid * 4) * 4, 0, 16);
     }
     if (tid == 0) {
-        const float ml[4] = {m, l_run, 0.f, 0.f};
+        // (the two padding words are never read: they carry the sentinel, so a refilled record is all sentinel)
+        const uint32_t ml[4] = {__float_as_uint(m), __float_as_uint(l_run), DA_SENT, DA_SENT};
         u32x4 bits;
         __builtin_memcpy(&bits, ml, 16);
         __builtin_amdgcn_raw_buffer_store_b128(bits, rsrc, c * PR * 4, 0, 16);
@@ -493,6 +495,13 @@ __device__ __forceinline__ void dec_attn_body(const DecAttn2Args& a, const int c
         for (int g = 0; g < KS; ++g) { at += accp[g * HD + tid]; lt += lp[g * HD + tid]; }
         a.o[(long)b * a.o_ld + (long)h * HD + tid] = at / lt;
     }
+    // deferred refill (two hand-off copies alternating by layer): the words read here stay as they are, the
+    // next launch's projection blocks clean this copy (dec_qkv_attn_kernel) - the merging block, the last of
+    // the launch to finish, leaves with the context row stored
+    if (FUSED && a.no_refill) {
+        da_stamp(a.stamps, 5);
+        return;
+    }
     if constexpr (FUSED) {
         // every chunk of this head has read its q / k / v (its record, merged above, came after): refill
         if (tid < HD) {
@@ -539,6 +548,23 @@ __global__ __launch_bounds__(256) void dec_qkv_attn_kernel(DecGemvArgs g, DecRop
     if ((int)blockIdx.x < nq) {
         qkv_rope_body<WT, true>(g, r, blockIdx.x);
         da_stamp(a.stamps, 1);
+        // deferred refill: these blocks are done well before the merging blocks; they write the sentinel over
+        // the OTHER hand-off copy (last read by the previous launch, next read by the following one), one word
+        // per thread, in the store form of the in-launch refill
+        if (a.clean_qkv || a.clean_part) {
+            const uint32_t sent = DA_SENT;
+            const int t = (int)blockIdx.x * 256 + (int)threadIdx.x, nt = nq * 256;
+            if (a.clean_qkv) {
+                const int words = (a.heads + 2 * a.kv_heads) * 128;
+                const auto rq = __builtin_amdgcn_make_buffer_rsrc(a.clean_qkv, (short)0, words * 4, 0x00020000);
+                for (int i = t; i < words; i += nt) __builtin_amdgcn_raw_buffer_store_b32(sent, rq, i * 4, 0, 16);
+            }
+            if (a.clean_part) {
+                const int words = a.heads * ((a.max_len + DA_CH - 1) / DA_CH) * (128 + 4);
+                const auto rp = __builtin_amdgcn_make_buffer_rsrc(a.clean_part, (short)0, words * 4, 0x00020000);
+                for (int i = t; i < words; i += nt) __builtin_amdgcn_raw_buffer_store_b32(sent, rp, i * 4, 0, 16);
+            }
+        }
         return;
     }
     const int chunks = (a.max_len + DA_CH - 1) / DA_CH;
@@ -584,6 +610,8 @@ bool dec_qkv_attn_ok(const DecGemvArgs& g, const DecRopeEpi& r, const DecAttn2Ar
           chunks <= 24 && a.max_len <= 512 * DA_CH && g.y == a.qkv && g.N == (a.heads + 2 * a.kv_heads) * a.hd &&
           r.rot_rows == (a.heads + a.kv_heads) * a.hd))
         return false;
+    // the copy a launch cleans is never the one its own blocks poll
+    if ((a.clean_qkv && a.clean_qkv == a.qkv) || (a.clean_part && a.clean_part == a.part)) return false;
     return poll_wait_fits((long)chunks * a.heads, qkv_attn_blocks_per_cu(g.wdtype, stage_bytes(1, g.K)), device_cus());
 }
 

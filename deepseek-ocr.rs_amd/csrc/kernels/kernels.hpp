@@ -375,6 +375,14 @@ struct DecAttn2Args {
     // softmax done (standalone), [3] chunk record stored, [4] merge poll done, [5] exit
     unsigned long long* stamps = nullptr;
     int kv_delay = 0;  // fused q/k/v + attention: ticks (10 ns) the K / V cache loads wait behind the projection
+    // fused q/k/v + attention with two hand-off copies alternating by layer (deferred refill):
+    // no_refill: the merging blocks leave the q / k / v and record words they read as they are (the next
+    // launch, on the other copy, cleans them); clean_qkv / clean_part: the OTHER copy's q/k/v row and record
+    // buffer (same shape as qkv / part; either may be null), sentinel-filled by this launch's projection blocks
+    // once their own rows are stored.  Nothing in this launch reads the other copy: kernel boundaries order it.
+    int no_refill = 0;
+    float* clean_qkv = nullptr;
+    float* clean_part = nullptr;
 };
 void launch_dec_attn(const DecAttn2Args& a, hipStream_t s);
 // q/k/v projection of one token with RoPE applied in the epilogue (rows < rot_rows rotated at
@@ -388,7 +396,8 @@ bool dec_qkv_rope_ok(const DecGemvArgs& a, const DecRopeEpi& r);
 void launch_dec_qkv_rope(const DecGemvArgs& a, const DecRopeEpi& r, hipStream_t s);
 // One page: q/k/v projection + RoPE and the decode attention in one launch (the attention blocks stream
 // their K / V chunk while the projection runs, then poll for q / k / v); the q/k/v row g.y == a.qkv must
-// enter the first launch sentinel-filled (dec_qkv_sentinel_init), every launch leaves it so
+// enter the first launch sentinel-filled (dec_qkv_sentinel_init), every launch leaves it so unless
+// a.no_refill hands the refill to the next launch (whose clean_qkv / clean_part name this launch's copy)
 // (includes the residency rule below: the launch is refused - the engine then takes the two-launch form -
 // when the polling attention blocks could fill every slot the device has for the kernel)
 bool dec_qkv_attn_ok(const DecGemvArgs& g, const DecRopeEpi& r, const DecAttn2Args& a);

@@ -128,6 +128,7 @@ EXPORTS = [
     "dsocr_generate_logprobs", "dsocr_session_logprobs", "dsocr_k_logprobs", "dsocr_k_logprobs_penalty",
     "dsocr_session_prefix_keep", "dsocr_session_admit_prefix", "dsocr_session_prefix_drop", "dsocr_session_prefix_stats",
     "dsocr_k_prefill_attention_past", "dsocr_k_session_prefix_copy",
+    "dsocr_k_qkv_attention_layers",
 ]
 
 # model variants behind the deepseek engine (dsocr_engine_variant)
@@ -221,6 +222,8 @@ def lib():
                                             i32]
     L.dsocr_k_qkv_attention.argtypes = [i32, i32, i32, i32, i32, i32, f32, f32, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp,
                                         vp, C.POINTER(i32)]
+    L.dsocr_k_qkv_attention_layers.argtypes = [i32, i32, i32, i32, i32, i32, f32, f32, vp, vp, vp, i32, vp, vp, vp, vp,
+                                               vp, vp, vp, vp, C.POINTER(i32)]
     L.dsocr_k_poll_wait_fits.argtypes = [C.c_long, i32, i32]
     L.dsocr_k_moe_packed.argtypes = [i32, i32, i32, i32, i32, i32, vp, vp, f32, vp, i32, vp, i32, vp, i32, vp, i32, vp,
                                      i32, f32, vp, vp, vp]

@@ -550,6 +550,18 @@ dsocr_status dsocr_k_qkv_attention(int fused, int steps, int H, int heads, int h
                                    float eps, const float* x, const float* norm_w, const void* Wqkv, int wdtype,
                                    const float* cos, const float* sin, float* kc, float* vc, const int* kv_pos,
                                    float* qkv_row, float* o, int* used_fused);
+/* `layers` consecutive fused launches (dec_qkv_attn) as the layer sequence of one decode step, on two hand-off
+ * copies the call allocates and fills with DSOCR_HANDOFF_SENTINEL.  defer != 0: the engine's deferred refill
+ * (launch l on copy l & 1; every launch but the last leaves the words it read to the next launch, which cleans
+ * that copy from its projection blocks; the last refills its own); defer == 0: every launch on copy 0, refilled
+ * in-launch.  Per launch l: x [layers][H], Wqkv [layers][3H][H] (16-bit), kc / vc [layers][heads][max_len][hd],
+ * kv_pos [layers], o [layers][H] (device pointers).  Returned to host memory: qkv_copies [2][3H] and
+ * part_copies [2][heads * ceil(max_len / 64) * (hd + 4)], the final words of both copies, and *err_word, the
+ * kernels' give-up flag.  128-dim MHA heads only; DSOCR_EINVAL when the fused launch is refused. */
+dsocr_status dsocr_k_qkv_attention_layers(int defer, int layers, int H, int heads, int hd, int max_len, float scale,
+                                          float eps, const float* x, const float* norm_w, const void* Wqkv, int wdtype,
+                                          const float* cos, const float* sin, float* kc, float* vc, const int* kv_pos,
+                                          float* o, uint32_t* qkv_copies, uint32_t* part_copies, int* err_word);
 /* Residency rule of the polled in-launch hand-offs (pure host decision, no device call): 1 when
  * waiting_blocks (blocks that may spin on blocks of the same grid) < usable slots = (min(api, 8), one fewer
  * where the occupancy API may over-admit) x cus; else 0 (the engine then launches the non-polling form). */

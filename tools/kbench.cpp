@@ -425,8 +425,10 @@ static void case_attn(int B, int pos, hipStream_t s) {
 }
 
 // one page's fused q/k/v projection + decode attention (dec_qkv_attn) at L = pos + 1, 12 layers' weights and
-// caches rotating, timed; then the phase clocks of three single launches (DecAttn2Args::stamps)
-static void case_qkvattn1(int pos, hipStream_t s) {
+// caches rotating, timed; then the phase clocks of three single launches (DecAttn2Args::stamps).
+// defer: the engine's deferred refill in its steady state - two hand-off copies alternating by launch, every
+// launch leaves the words it read to the next one, which cleans that copy from its projection blocks
+static void case_qkvattn1(int pos, bool defer, hipStream_t s) {
     const int max_len = 1218;
     constexpr int NLA = 12;
     const long head_stride = (long)max_len * HD, page_stride = (long)HEADS * head_stride;
@@ -438,15 +440,17 @@ static void case_qkvattn1(int pos, hipStream_t s) {
     }
     float* x = rand_f32(H);
     float* nw = rand_f32(H, 0.2f, 1.f);
-    float* row = (float*)dalloc((size_t)3 * H * 4);
-    dec_qkv_sentinel_init(row, 3 * H, nullptr);
+    float* rows[2];
+    for (float*& r : rows) { r = (float*)dalloc((size_t)3 * H * 4); dec_qkv_sentinel_init(r, 3 * H, nullptr); }
+    float* row = rows[0];
     int* kv_pos = (int*)dalloc(16);
     CK(hipMemcpy(kv_pos, &pos, 4, hipMemcpyHostToDevice));
     float* cs = rand_f32((size_t)max_len * HD, 1.f);
     float* sn = rand_f32((size_t)max_len * HD, 1.f);
     const size_t pb = dec_attn_workspace(1, HEADS, HD, max_len);
-    float* part = (float*)dalloc(pb + 64);
-    dec_attn_part_init(part, pb, nullptr);
+    float* parts[2];
+    for (float*& p : parts) { p = (float*)dalloc(pb + 64); dec_attn_part_init(p, pb, nullptr); }
+    float* part = parts[0];
     int* cnt = (int*)dalloc(HEADS * 4 + 16);
     float* o = (float*)dalloc((size_t)HEADS * HD * 4);
     DecGemvArgs g;
@@ -459,15 +463,23 @@ static void case_qkvattn1(int pos, hipStream_t s) {
     a.rope_dim = HD; a.max_len = max_len; a.cos = cs; a.sin = sn; a.page_stride = page_stride; a.head_stride = head_stride;
     a.scale = 1.f / sqrtf((float)HD); a.part = part; a.counters = cnt; a.o = o; a.o_ld = HEADS * HD; a.prerot = 1;
     a.err = cnt + HEADS;
-    auto set = [&](int i) { g.W = wq[i % NLA]; a.kc = kc[i % NLA]; a.vc = vc[i % NLA]; };
+    int n_launch = 0;  // (every launch below goes through set(): the copies alternate without a gap)
+    auto set = [&](int i) {
+        g.W = wq[i % NLA]; a.kc = kc[i % NLA]; a.vc = vc[i % NLA];
+        if (defer) {
+            const int c = n_launch++ & 1;
+            g.y = rows[c]; a.qkv = rows[c]; a.part = parts[c];
+            a.no_refill = 1; a.clean_qkv = rows[c ^ 1]; a.clean_part = parts[c ^ 1];
+        }
+    };
     if (!dec_qkv_attn_ok(g, re, a)) { printf("qkvattn1: fused launch refused\n"); return; }
     char nm[96];
-    snprintf(nm, sizeof nm, "qkv+attn B=1 L=%d", pos + 1);
+    snprintf(nm, sizeof nm, "qkv+attn B=1 L=%d%s", pos + 1, defer ? " refill deferred" : "");
     const double bytes = 3.0 * H * H * 2 + 2.0 * (pos + 1) * HEADS * HD * 4;
     report(nm, timeit(4 * NLA, [&](int i) { set(i); launch_dec_qkv_attn(g, re, a, s); }, s), bytes);
     for (int dl : {50, 100, 150, 200, 300}) {  // K / V loads held back behind the projection (10 ns ticks)
         a.kv_delay = dl;
-        snprintf(nm, sizeof nm, "qkv+attn B=1 L=%d kv_delay %d", pos + 1, dl);
+        snprintf(nm, sizeof nm, "qkv+attn B=1 L=%d%s kv_delay %d", pos + 1, defer ? " refill deferred" : "", dl);
         report(nm, timeit(4 * NLA, [&](int i) { set(i); launch_dec_qkv_attn(g, re, a, s); }, s), bytes);
     }
     a.kv_delay = getenv("KB_KV_DELAY") ? atoi(getenv("KB_KV_DELAY")) : 0;
@@ -482,7 +494,7 @@ static void case_qkvattn1(int pos, hipStream_t s) {
         CK(hipStreamSynchronize(s));
         std::vector<unsigned long long> h((size_t)nb * 8);
         CK(hipMemcpy(h.data(), st, h.size() * 8, hipMemcpyDeviceToHost));
-        print_stamps("qkv+attn", h, 0, nq, nq, nb);
+        print_stamps(defer ? "qkv+attn deferred" : "qkv+attn", h, 0, nq, nq, nb);
     }
     for (int l = 0; l < NLA; ++l) { (void)hipFree(kc[l]); (void)hipFree(vc[l]); (void)hipFree(wq[l]); }
 }
@@ -665,7 +677,10 @@ int main(int argc, char** argv) {
         else if (c == "gemv8") case_gemv(8, s);
         else if (c == "attn1") { case_attn(1, 706, s); case_attn(1, 1216, s); }
         else if (c == "attn8") { case_attn(8, 706, s); case_attn(8, 1216, s); }
-        else if (c == "qkvattn1") { case_qkvattn1(706, s); case_qkvattn1(1216, s); }
+        else if (c == "qkvattn1") {
+            for (int pos : {706, 1216})
+                for (bool defer : {false, true}) case_qkvattn1(pos, defer, s);
+        }
         else if (c == "lm8") case_lm(8, s);
         else if (c == "vgemm") case_vgemm(s);
         else if (c == "dgemm") case_dgemm(s);
