@@ -1632,6 +1632,187 @@ dsocr_status dsocr_k_lmhead_screened(int B, int V, int K, const float* x, const 
         for (void* p : bufs) (void)hipFree(p);
     });
 }
+// the screened head's contract for (B, V, K): EINVAL outside it; true: the matrix-core form runs
+static bool screen_shape_mm(int B, int V, int K) {
+    if (B < 1 || B > 8 || V < 1 || K < 16 || K % 16 || K > 1536)
+        throw std::runtime_error("EINVAL: screened lm_head needs 1..8 rows, V > 0, K % 16 == 0, 16 <= K <= 1536");
+    const bool mm = B >= 3;
+    if (mm && !dsocr::lmhead_q8mm_ok(B, V, K))
+        throw std::runtime_error("EINVAL: screened lm_head for 3..8 rows needs K in {768, 1024, 1280, 1536}, V >= 16");
+    return mm;
+}
+dsocr_status dsocr_k_lmhead_screen_grid(int B, int V, int K, int* nblk, long long* slot, int* matrix_core) {
+    return guarded([&] {
+        if (!nblk || !slot || !matrix_core) throw std::runtime_error("EINVAL: NULL argument");
+        const bool mm = screen_shape_mm(B, V, K);
+        int nb = 0;
+        long sl = 0;
+        if (mm) dsocr::lmhead_q8mm_grid(V, K, B, &nb, &sl);
+        else dsocr::lmhead_q8_grid(V, K, B, &nb, &sl);
+        *nblk = nb; *slot = sl; *matrix_core = mm ? 1 : 0;
+    });
+}
+dsocr_status dsocr_k_lmhead_screen_steps(const dsocr_screen_steps* sp) {
+    return guarded([&] {
+        if (!sp) throw std::runtime_error("EINVAL: NULL argument");
+        const dsocr_screen_steps& s = *sp;
+        const int B = s.B, V = s.V, K = s.K, steps = s.steps;
+        const bool mm = screen_shape_mm(B, V, K);
+        if (s.wdtype != dsocr::WDT_BF16 && s.wdtype != dsocr::WDT_F16) throw std::runtime_error("EINVAL: weights must be bf16 or f16");
+        if (!s.W || steps < 0) throw std::runtime_error("EINVAL: W / steps");
+        if (steps > 0) {
+            if (!s.x || !s.norm_w || !s.ctx || !s.ctx_len || s.ldx < K || s.ldx % 4 || s.ctx_cap < 1 || s.out_cap < 1 ||
+                s.ban_ld < s.ctx_cap + 1 || s.probe < 0 || s.probe >= steps)
+                throw std::runtime_error("EINVAL: screened steps need x (ldx >= K, ldx % 4 == 0), norm_w, ctx, ctx_len, "
+                                         "out_cap > 0, ban_ld >= ctx_cap + 1, 0 <= probe < steps");
+            for (int b = 0; b < B; ++b)
+                if (s.ctx_len[b] < 0 || s.ctx_len[b] > s.ctx_cap) throw std::runtime_error("EINVAL: context length");
+            if (s.table && (s.H < 1 || (s.table_dt != dsocr::WDT_BF16 && s.table_dt != dsocr::WDT_F16)))
+                throw std::runtime_error("EINVAL: embedding table needs H > 0 and a bf16 / f16 type");
+            if (s.ban)
+                for (int b = 0; b < B; ++b)
+                    if (s.ban[(size_t)b * s.ban_ld] < 0 || s.ban[(size_t)b * s.ban_ld] > s.ban_ld - 1)
+                        throw std::runtime_error("EINVAL: ban count");
+        }
+        std::vector<dsocr::RowParams> rp;
+        if (s.rows && steps > 0) {
+            rp.resize(B);
+            for (int b = 0; b < B; ++b) {
+                const dsocr_row_params& r = s.rows[b];
+                if (r.do_sample != 0 && r.temperature > 0.0) throw std::runtime_error("EINVAL: the screened head takes greedy rows only");
+                if (dsocr::rep_penalty_active(r.repetition_penalty)) throw std::runtime_error("EINVAL: the screened head takes no repetition penalty");
+                rp[b].ngram = r.no_repeat_ngram_size > 1 ? (int)r.no_repeat_ngram_size : 0;
+                rp[b].eos = r.eos_token_id < 0 ? -1 : (int)r.eos_token_id;
+            }
+        }
+        std::vector<void*> bufs;
+        auto alloc = [&](size_t b) {
+            void* p = nullptr;
+            check_hip(hipMalloc(&p, b ? b : 16), "hipMalloc");
+            bufs.push_back(p);
+            return p;
+        };
+        auto up = [&](const void* src, size_t b) {
+            void* p = alloc(b);
+            check_hip(hipMemcpy(p, src, b, hipMemcpyHostToDevice), "hipMemcpy H2D");
+            return p;
+        };
+        auto zeroed = [&](size_t b) {
+            void* p = alloc(b);
+            check_hip(hipMemset(p, 0, b ? b : 16), "hipMemset");
+            return p;
+        };
+        auto down = [&](void* dst, const void* src, size_t b) {
+            if (dst && b) check_hip(hipMemcpy(dst, src, b, hipMemcpyDeviceToHost), "hipMemcpy D2H");
+        };
+        try {
+            // ---- load time, as Engine::load: scale / bound / qnorm padded to whole 16-row tiles and zeroed
+            const size_t vp = (size_t)(V + 15) / 16 * 16, I = sizeof(int), F = sizeof(float);
+            const bool frag = K % 64 == 0 && (dsocr::lmhead_q8mm_ok(8, V, K) || s.qnorm || s.qfrag);
+            void* W = up(s.W, (size_t)V * K * 2);
+            void* q = alloc((size_t)V * K);
+            float* scale = (float*)zeroed(F * vp);
+            float* bound = (float*)zeroed(F * vp);
+            float* qnorm = frag ? (float*)zeroed(F * vp) : nullptr;
+            void* qfrag = frag ? alloc(dsocr::lmhead_qfrag_bytes(V, K)) : nullptr;
+            dsocr::launch_lmhead_quantize(W, V, K, q, scale, bound, nullptr, qnorm, qfrag, s.wdtype);
+            check_hip(hipGetLastError(), "lm_head quantisation launch");
+            check_hip(hipDeviceSynchronize(), "lm_head quantisation");
+            down(s.q, q, (size_t)V * K);
+            down(s.scale, scale, F * V);
+            down(s.bound, bound, F * V);
+            if (frag) {
+                down(s.qnorm, qnorm, F * V);
+                down(s.qfrag, qfrag, dsocr::lmhead_qfrag_bytes(V, K));
+            } else if (s.qnorm || s.qfrag) {
+                throw std::runtime_error("EINVAL: the fragment-ordered copy needs K % 64 == 0");
+            }
+            if (steps > 0) {
+                if (mm && !frag) throw std::runtime_error("EINTERNAL: matrix-core form without its copy");
+                // ---- per step, as Engine::decode_head's screened branch
+                const size_t cap = (size_t)s.ctx_cap, ocap = (size_t)s.out_cap, bld = (size_t)s.ban_ld;
+                float* x = (float*)up(s.x, F * (size_t)steps * B * s.ldx);
+                float* norm_w = (float*)up(s.norm_w, F * K);
+                dsocr::LmHeadQ8Args a;
+                a.norm_w = norm_w; a.ldx = s.ldx; a.eps = s.eps; a.q = q; a.scale = scale; a.bound = bound;
+                a.B = B; a.N = V; a.K = K;
+                if (mm) {
+                    a.qfrag = qfrag; a.qnorm = qnorm;
+                    dsocr::lmhead_q8mm_grid(V, K, B, &a.nblk, &a.slot);
+                } else {
+                    dsocr::lmhead_q8_grid(V, K, B, &a.nblk, &a.slot);
+                }
+                const size_t nb = (size_t)B * a.nblk, nc = nb * (size_t)a.slot;
+                a.blk_cnt = (int*)zeroed(I * nb); a.blk_t = (float*)zeroed(F * nb);
+                a.cand = (int*)zeroed(I * nc); a.cand_hi = (float*)zeroed(F * nc);
+                a.xn_out = (float*)zeroed(F * B * K);
+                dsocr::DecSampleArgs ss;
+                ss.B = B; ss.V = V; ss.ld = V;
+                ss.ctx = (int*)zeroed(I * B * cap); ss.ctx_cap = (long)cap;
+                check_hip(hipMemcpy(ss.ctx, s.ctx, I * B * cap, hipMemcpyHostToDevice), "hipMemcpy H2D");
+                ss.ctx_len = (int*)up(s.ctx_len, I * B);
+                ss.ngram = s.ngram > 1 ? s.ngram : 0; ss.eos = s.eos < 0 ? -1 : s.eos;
+                if (!rp.empty()) ss.rows = (const dsocr::RowParams*)up(rp.data(), sizeof(dsocr::RowParams) * B);
+                ss.out_tok = (int*)zeroed(I * B);
+                ss.out_ids = (int*)zeroed(I * B * ocap); ss.out_len = (int*)zeroed(I * B); ss.out_cap = (long)ocap;
+                ss.done = (int*)zeroed(I * B);
+                ss.kv_pos = (int*)up(s.ctx_len, I * B); ss.kv_len = (int*)up(s.ctx_len, I * B);
+                ss.ban_out = (int*)zeroed(I * B * bld); ss.ban_ld = (long)bld;
+                if (s.ban) check_hip(hipMemcpy(ss.ban_out, s.ban, I * B * bld, hipMemcpyHostToDevice), "hipMemcpy H2D");
+                if (s.table) {
+                    ss.table = up(s.table, (size_t)V * s.H * 2); ss.table_dt = s.table_dt; ss.H = s.H;
+                    ss.x_next = (float*)zeroed(F * B * s.H);
+                }
+                ss.blk_cnt = a.blk_cnt; ss.blk_t = a.blk_t; ss.cand = a.cand; ss.cand_hi = a.cand_hi; ss.nblk = a.nblk;
+                ss.slot = a.slot; ss.w_exact = W; ss.w_exact_wdt = s.wdtype; ss.xn = a.xn_out; ss.K = K;
+                for (int t = 0; t < steps; ++t) {
+                    a.x = x + (size_t)t * B * s.ldx;
+                    a.ban = ss.ban_out; a.ban_ld = ss.ban_ld;
+                    dsocr::launch_lmhead_q8(a, nullptr);
+                    dsocr::launch_dec_sample(ss, nullptr);
+                    check_hip(hipGetLastError(), "screened lm_head launch");
+                    check_hip(hipDeviceSynchronize(), "screened lm_head");
+                    const size_t tb = (size_t)t * B;
+                    down(s.out_tok ? s.out_tok + tb : nullptr, ss.out_tok, I * B);
+                    down(s.ban_out ? s.ban_out + tb * bld : nullptr, ss.ban_out, I * B * bld);
+                    down(s.ctx_out ? s.ctx_out + tb * cap : nullptr, ss.ctx, I * B * cap);
+                    down(s.ctx_len_out ? s.ctx_len_out + tb : nullptr, ss.ctx_len, I * B);
+                    down(s.out_ids ? s.out_ids + tb * ocap : nullptr, ss.out_ids, I * B * ocap);
+                    down(s.out_len ? s.out_len + tb : nullptr, ss.out_len, I * B);
+                    down(s.done ? s.done + tb : nullptr, ss.done, I * B);
+                    down(s.kv_pos ? s.kv_pos + tb : nullptr, ss.kv_pos, I * B);
+                    down(s.kv_len ? s.kv_len + tb : nullptr, ss.kv_len, I * B);
+                    if (s.table) down(s.x_next ? s.x_next + tb * s.H : nullptr, ss.x_next, F * B * s.H);
+                    if (t == s.probe) {
+                        down(s.blk_cnt, a.blk_cnt, I * nb);
+                        down(s.blk_t, a.blk_t, F * nb);
+                        down(s.cand, a.cand, I * nc);
+                        down(s.cand_hi, a.cand_hi, F * nc);
+                        down(s.xn_out, a.xn_out, F * B * K);
+                        if (s.xn_gemv) {
+                            // the rows the exact kernel stages from the same input (dec_gemv's own xn_out, on a few
+                            // rows of W: the staging does not depend on N)
+                            dsocr::DecGemvArgs g;
+                            g.M = B; g.N = std::min(V, 4); g.K = K; g.x = a.x; g.ldx = (int)s.ldx; g.W = W; g.ldw = K;
+                            g.wdtype = s.wdtype; g.norm_w = norm_w; g.eps = s.eps;
+                            g.y = (float*)zeroed(F * B * 4); g.ldy = 4;
+                            g.xn_out = (float*)zeroed(F * B * K);
+                            dsocr::launch_dec_gemv(g, nullptr);
+                            check_hip(hipGetLastError(), "dec_gemv launch");
+                            check_hip(hipDeviceSynchronize(), "dec_gemv");
+                            down(s.xn_gemv, g.xn_out, F * B * K);
+                        }
+                    }
+                }
+            }
+        } catch (...) {
+            (void)hipDeviceSynchronize();
+            for (void* p : bufs) (void)hipFree(p);
+            throw;
+        }
+        for (void* p : bufs) (void)hipFree(p);
+    });
+}
 dsocr_status dsocr_k_sample_greedy(int B, int V, float* logits, const int* ctx, int ctx_cap, const int* ctx_len,
                                    int ngram, float rep_penalty, int* out_tok) {
     return guarded([&] {

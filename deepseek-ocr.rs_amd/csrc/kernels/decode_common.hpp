@@ -27,6 +27,14 @@ namespace dsocr {
 // Dynamic LDS of the GEMV-type kernels: [XS_RED floats of row partial sums][M][K staged rows].
 constexpr int XS_RED = 128;  // >= M * (blockDim / 64)
 
+// Sum of the squares of one float4, every product and sum rounded on its own.  The compiler contracts the plain
+// expression into fused multiply-adds differently from one kernel to the next, which moved the RMSNorm divisor by
+// an ulp between kernels that claim the same staged row (dec_gemv's forms, the screened lm_head's rescoring).
+__device__ __forceinline__ float sumsq4(const float4 v) {
+#pragma clang fp contract(off)
+    return (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w);
+}
+
 // Block-wide: stage M rows of x (row m = rows ? rows[m] : m, stride ldx) into LDS, RMS-normalised
 // when nw != null (rms_norm_slow, block.rs:24-29: x / sqrt(mean(x^2) + eps) * w).  Every
 // thread of the block must call it (two barriers).
@@ -42,7 +50,7 @@ __device__ __forceinline__ void stage_rows(const float* x, long ldx, const int* 
             float q = 0.f;
             for (int k = tid * 4; k < K; k += step) {
                 const float4 v = *reinterpret_cast<const float4*>(xr + k);
-                q += (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w);
+                q = __fadd_rn(q, sumsq4(v));
             }
             q = wave_sum(q);
             if (lane == 0) red[m * nwv + wave] = q;
@@ -120,7 +128,7 @@ __device__ __forceinline__ void xstage(const XRegs<MT, XR>& r, int M, int K, boo
 #pragma unroll
                 for (int i = 0; i < XR; ++i) {
                     const float4 v = r.v[m][i];
-                    if ((tid + i * nt) * 4 < K) q += (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w);
+                    if ((tid + i * nt) * 4 < K) q = __fadd_rn(q, sumsq4(v));
                 }
                 q = wave_sum(q);
                 if (lane == 0) red[m * nwv + wave] = q;

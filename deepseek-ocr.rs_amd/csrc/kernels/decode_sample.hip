@@ -200,8 +200,10 @@ __global__ __launch_bounds__(NT) void dec_screen_final_kernel(DecSampleArgs a) {
     }
     if (tid >= a.nblk) T = -INFINITY;
     for (int j = tid + NT; j < a.nblk; j += NT) T = fmaxf(T, bt[j]);
-    const int lc = max(last_i, 0);
-    const int pa = cx[min(tid, lc)], pb = cx[min(tid + NT, lc)], s0 = cx[max(n + 2 - g, 0)];
+    // (preloaded whatever g is; read only when the ban applies, g > 1, where the indices are below n: clamped to the
+    // row for g < 2, where n + 1 - g and n + 2 - g reach past a full context)
+    const int lc = min(max(last_i, 0), (int)a.ctx_cap - 1);
+    const int pa = cx[min(tid, lc)], pb = cx[min(tid + NT, lc)], s0 = cx[min(max(n + 2 - g, 0), (int)a.ctx_cap - 1)];
     for (int k = tid * 4; k < a.K; k += NT * 4)
         *reinterpret_cast<float4*>(xs + k) = *reinterpret_cast<const float4*>(a.xn + (long)b * a.K + k);
     T = wave_max(T);

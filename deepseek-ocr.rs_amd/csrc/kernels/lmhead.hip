@@ -14,8 +14,7 @@
 #include <cstdint>
 #include <stdexcept>
 
-#include "dev_common.hpp"
-#include "kernels.hpp"
+#include "decode_common.hpp"
 
 namespace dsocr {
 
@@ -213,7 +212,7 @@ __global__ __launch_bounds__(256) void lmhead_q8_kernel(LmHeadQ8Args a) {
         float qs = 0.f;
 #pragma unroll
         for (int i = 0; i < 2; ++i)
-            if ((tid + i * 256) * 4 < K) qs += (v[i].x * v[i].x + v[i].y * v[i].y) + (v[i].z * v[i].z + v[i].w * v[i].w);
+            if ((tid + i * 256) * 4 < K) qs = __fadd_rn(qs, sumsq4(v[i]));
         qs = wave_sum(qs);
         if (lane == 0) xs[wave] = qs;
         if (tid == 0) { tkey_s = 0u; lst_n = 0; }
@@ -443,16 +442,20 @@ __global__ __launch_bounds__(512, 4) void lmhead_q8mm_kernel(LmHeadQ8Args a, int
             for (int i = lane; i < min(nb, LM_BANS); i += 64) ban_s[wave][i] = bg[1 + i];
         }
         if (lane == 0) nban_s[wave] = nb;
+        // the sum of squares in dec_gemv's staging order (xstage: 256 threads, float4 t and t + 256 each, a wave sum
+        // per 64 threads, the four partials in order), so the divisor - and the row the rescoring reads - is that
+        // kernel's bit for bit: float4 lane + 64 j of this wave is thread (lane + 64 j) % 256's
         float q = 0.f;
 #pragma unroll
-        for (int j = 0; j < J; ++j) {
-            const int k = (lane + 64 * j) * 4;
-            if (k < K) {
-                const float4 v = *reinterpret_cast<const float4*>(xr + k);
-                q += (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w);
+        for (int w4 = 0; w4 < 4; ++w4) {
+            float p = 0.f;
+#pragma unroll
+            for (int j = w4; j < J; j += 4) {
+                const int k = (lane + 64 * j) * 4;
+                if (k < K) p = __fadd_rn(p, sumsq4(*reinterpret_cast<const float4*>(xr + k)));
             }
+            q += wave_sum(p);
         }
-        q = wave_sum(q);
         const float den = sqrtf(q / (float)K + a.eps);
         if (lane == 0) den_s[wave] = den;
         auto xhat = [&](int k) {

@@ -89,6 +89,18 @@ class RowParamsC(C.Structure):
                 ("repetition_penalty", C.c_float), ("no_repeat_ngram_size", C.c_size_t), ("eos_token_id", C.c_int64)]
 
 
+class ScreenStepsC(C.Structure):
+    """dsocr_screen_steps: the arguments of dsocr_k_lmhead_screen_steps (host pointers)."""
+    _fields_ = ([(n, C.c_int) for n in ("B", "V", "K", "wdtype", "steps", "probe")] +
+                [("W", C.c_void_p), ("x", C.c_void_p), ("ldx", C.c_longlong), ("norm_w", C.c_void_p), ("eps", C.c_float),
+                 ("ctx", C.c_void_p), ("ctx_cap", C.c_int), ("ctx_len", C.c_void_p), ("ngram", C.c_int), ("eos", C.c_int),
+                 ("rows", C.POINTER(RowParamsC)), ("ban", C.c_void_p), ("ban_ld", C.c_int), ("out_cap", C.c_int),
+                 ("table", C.c_void_p), ("table_dt", C.c_int), ("H", C.c_int)] +
+                [(n, C.c_void_p) for n in ("out_tok", "ban_out", "ctx_out", "ctx_len_out", "out_ids", "out_len", "done",
+                                           "kv_pos", "kv_len", "x_next", "blk_cnt", "blk_t", "cand", "cand_hi", "xn_out", "xn_gemv",
+                                           "q", "scale", "bound", "qnorm", "qfrag")])
+
+
 SESSION_PER_REQUEST = 1  # DSOCR_SESSION_PER_REQUEST
 SESSION_LOGPROBS = 2     # DSOCR_SESSION_LOGPROBS
 MAX_TOP_LOGPROBS = 20    # DSOCR_MAX_TOP_LOGPROBS
@@ -129,6 +141,7 @@ EXPORTS = [
     "dsocr_session_prefix_keep", "dsocr_session_admit_prefix", "dsocr_session_prefix_drop", "dsocr_session_prefix_stats",
     "dsocr_k_prefill_attention_past", "dsocr_k_session_prefix_copy",
     "dsocr_k_qkv_attention_layers",
+    "dsocr_k_lmhead_screen_steps", "dsocr_k_lmhead_screen_grid",
 ]
 
 # model variants behind the deepseek engine (dsocr_engine_variant)
@@ -187,6 +200,8 @@ def lib():
     L.dsocr_dots_embed_device.argtypes = [vp, vp, u32, u32, u32, vp, i32]
     L.dsocr_dots_last_timings.argtypes = [vp, C.POINTER(DotsTimingsC)]
     L.dsocr_k_lmhead_screened.argtypes = [i32, i32, i32, vp, vp, f32, vp, vp, i32, vp]
+    L.dsocr_k_lmhead_screen_steps.argtypes = [C.POINTER(ScreenStepsC)]
+    L.dsocr_k_lmhead_screen_grid.argtypes = [i32, i32, i32, C.POINTER(i32), C.POINTER(C.c_longlong), C.POINTER(i32)]
     L.dsocr_k_moe_kernels.argtypes = [i32, i32, i32, i32, i32, i32, i32, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p)]
     L.dsocr_last_timings.argtypes = [vp, C.POINTER(TimingsC)]
     L.dsocr_profile_decode.argtypes = [vp, i32, C.POINTER(DecodeProfileC)]

@@ -653,6 +653,46 @@ typedef struct {
 } dsocr_row_params;
 dsocr_status dsocr_k_select_rows(int B, int V, float* logits, const int* ctx, int ctx_cap, const int* ctx_len,
                                  const dsocr_row_params* rows, const uint64_t* seeds, int draws, int* out_tok);
+/* The screened head with its parts shown: the launches of Engine::decode_head's screened branch (the load-time
+ * quantisation once, then per step the int8 lm_head and the screened final kernel) for `steps` consecutive steps
+ * on one set of state rows, every intermediate copied back.  Step t reads x [t][B][ldx] and the ban list step
+ * t - 1 left (step 0: `ban`, or empty lists); B <= 2 runs the single-token kernel, 3..8 the matrix-core form.
+ * rows == NULL: ngram / eos apply to every row; else row b takes rows[b] (greedy records only) and the kernels'
+ * per-row instantiations run.  table (optional): the embedding rows [V][H], table_dt 0 bf16 / 1 f16.  The state
+ * starts at out_len = done = 0, kv_pos = kv_len = ctx_len.  Every pointer is a HOST pointer; every output may be
+ * NULL.  Per step (leading dimension [steps]): out_tok [B], ban_out [B][ban_ld], ctx_out [B][ctx_cap],
+ * ctx_len_out [B], out_ids [B][out_cap], out_len / done / kv_pos / kv_len [B], x_next [B][H].  Of step `probe`,
+ * in the device layout (nblk, slot: dsocr_k_lmhead_screen_grid): blk_cnt / blk_t [B][nblk], cand / cand_hi
+ * [B][slot][nblk], xn_out [B][K], and xn_gemv [B][K], the rows the exact kernel (dec_gemv) stages from the same
+ * input.  Of the quantisation: q [V][K], scale / bound [V], and (K % 64 == 0) qnorm [V],
+ * qfrag [ceil(V / 16)][K / 64][64][16].  steps == 0 quantises only.
+ * DSOCR_EINVAL outside the kernels' contract: K % 16 != 0, K outside 16..1536, B outside 1..8, 3..8 rows at a K
+ * the matrix-core form does not take (768, 1024, 1280, 1536; V >= 16), ban_ld < ctx_cap + 1, a sampling record. */
+typedef struct {
+    int B, V, K, wdtype, steps, probe;
+    const void* W;               /* [V][K] 16-bit rows (wdtype 0 bf16, 1 f16) */
+    const float* x;              /* [steps][B][ldx] */
+    long long ldx;
+    const float* norm_w;         /* [K] */
+    float eps;
+    const int* ctx;              /* [B][ctx_cap] */
+    int ctx_cap;
+    const int* ctx_len;          /* [B] */
+    int ngram, eos;              /* rows == NULL; eos < 0: none */
+    const dsocr_row_params* rows;
+    const int* ban;              /* [B][ban_ld]: count, then tokens (NULL: empty) */
+    int ban_ld, out_cap;
+    const void* table;           /* [V][H] or NULL */
+    int table_dt, H;
+    int* out_tok; int* ban_out; int* ctx_out; int* ctx_len_out; int* out_ids; int* out_len; int* done;
+    int* kv_pos; int* kv_len; float* x_next;
+    int* blk_cnt; float* blk_t; int* cand; float* cand_hi; float* xn_out; float* xn_gemv;
+    int8_t* q; float* scale; float* bound; float* qnorm; int8_t* qfrag;
+} dsocr_screen_steps;
+dsocr_status dsocr_k_lmhead_screen_steps(const dsocr_screen_steps* s);
+/* The screened lm_head's grid for (B, V, K): blocks per row, entries per block slot, and whether the matrix-core
+ * form runs (B >= 3).  DSOCR_EINVAL as above. */
+dsocr_status dsocr_k_lmhead_screen_grid(int B, int V, int K, int* nblk, long long* slot, int* matrix_core);
 
 /* One page's decode state from slot src to slot dst of a session (src != dst), one launch: K / V rows
  * [0, kv_len[src]) of every layer and kv head of the f32 caches kc / vc [layers][slots][kv_heads][cap][hd]
