@@ -163,23 +163,15 @@ double ms_between(hipEvent_t a, hipEvent_t b) {
 }  // namespace
 
 // One decode session (Engine::session_*, after generate below): the state that outlives a call.  The device rows
-// live in the engine's named workspaces, reserved once at session_open for `S` slots; the graphs hold their addresses.
+// live in the engine's decode rows (rows_), reserved once at session_open for `S` slots; the graphs hold their addresses.
 struct Engine::Session {
     static constexpr int kBurstCap = 8;  // k_max: the most steps one session_step replays
-    int S = 0, n = 0, max_context = 0, Lcap = 0;
-    long ctx_cap = 0, out_cap = 0, ban_ld = 0;
+    int S = 0, n = 0, max_context = 0;
     GenParams p;
     bool per_request = false;  // every slot has its own RowParams; the head is chosen per burst
     bool screened = false;  // fixed parameters: the screened head at every n (else the exact head at every n)
-    size_t part_floats = 0, qkv_floats = 0;
-    float *sx = nullptr, *logits = nullptr;
-    float *part[2] = {nullptr, nullptr}, *qkv[2] = {nullptr, nullptr};  // the two hand-off copies (attn_args)
-    int *ctx = nullptr, *ctx_len = nullptr, *kvpos = nullptr, *kvlen = nullptr, *done = nullptr, *outlen = nullptr,
-        *out = nullptr, *tok = nullptr, *ban = nullptr, *stage = nullptr, *err = nullptr;
-    uint32_t* rng = nullptr;
-    RowParams* rowpar = nullptr;  // s_rowpar[S]: the per-row selection kernels' parameters (per_request)
+    int* stage = nullptr;   // ss_stage: an admission's staged slot rows
     bool logprobs = false;  // every step and admission writes log-probability entries (s_lp*): the exact head at every n
-    bool lp_side = false;   // ... and keeps the raw logits at the context ids (a penalty can apply)
     struct Slot {
         size_t max_new = 0;
         int kv_pos = 0;    // the device kv_pos of the slot: prompt + steps replayed since its admission
@@ -1294,10 +1286,10 @@ MoeDecodeArgs Engine::moe_args(int l, int B, float* X) {
     a.ids = wsi("s_ids", TK); a.wts = wsf("s_wts", TK);
     a.h = wsf("s_ehh", (size_t)TK * I);
     a.grp = wsi("s_grp", moe_grp_ints(E, B, K));
-    a.route_cnt = wsi("s_route_cnt", 16);
+    a.route_cnt = rows_.route_cnt;
     if (B >= 3 && B <= 8) {  // matrix-core grouped kernels: down partials + tickets
         a.dn_part = wsf("s_dnpart", moe_down_mm_part_floats(E, B, K, I, a.Is, H));
-        a.dn_tick = wsi("s_dntick", (size_t)H / 64 + 1);  // one ticket per 64-row tile
+        a.dn_tick = rows_.dn_tick;  // one ticket per 64-row tile
     }
     if (B <= 8 && d.packed) {  // the packed decode kernels (decode_q.hip)
         a.qWgu = d.q_gu; a.qWd = d.q_d; a.qsWgu = d.q_sgu; a.qsWd = d.q_sd;
@@ -1316,27 +1308,25 @@ MoeDecodeArgs Engine::moe_args(int l, int B, float* X) {
 // Decode attention arguments of layer l (shared by decode_step and profile_decode, which points q/k/v, the
 // position and the output at scratch rows): RoPE + K/V append + flash-decoding on the named workspaces
 // The hand-off buffers (the sentinel-filled q/k/v row and the flash-decoding records) exist in two copies,
-// "s_qkv" / "s_part" and "s_qkv1" / "s_part1".  Every launch but the fused one-page one uses copy 0 and leaves
+// rows_.qkv[c] / rows_.part[c] (workspaces "s_qkv" / "s_part" and "s_qkv1" / "s_part1").  Every launch but the fused one-page one uses copy 0 and leaves
 // it sentinel-filled itself.  With the deferred refill (att_refill_defer) layer l of the fused one-page path
 // uses copy l & 1, leaves the words it read as they are and cleans the copy of layer l - 1; the last layer of
 // the step refills its own.  Invariant: at every step boundary every word of both copies holds the sentinel.
-std::string Engine::handoff_ws(const char* base, int copy) { return copy ? std::string(base) + "1" : std::string(base); }
-
 DecAttn2Args Engine::attn_args(int l, int B, int Lmax, int copy) {
     const LangConfig& L = cfg_.lang;
     const int hd = L.head_dim, QKVN = layers_[l].qkv.N;
     const long layer_kv = this->layer_kv(B);
     DecAttn2Args da;
-    da.qkv = wsf(handoff_ws("s_qkv", copy), (size_t)B * QKVN); da.ld = QKVN; da.kv_pos = wsi("s_kvpos", B); da.B = B;
+    da.qkv = rows_.qkv[copy]; da.ld = QKVN; da.kv_pos = rows_.kv_pos; da.B = B;
     da.heads = L.heads; da.kv_heads = L.kv_heads; da.hd = hd; da.rope_dim = L.rope_dim; da.use_mla = L.use_mla;
     da.max_len = Lmax; da.cos = rope_cos_; da.sin = rope_sin_;
     da.kc = kc_ + (long)l * layer_kv; da.vc = vc_ + (long)l * layer_kv;
     da.page_stride = page_stride_; da.head_stride = head_stride_;
     da.scale = (float)(1.0 / std::sqrt((double)hd));
-    da.part = wsf(handoff_ws("s_part", copy), dec_attn_workspace(B, L.heads, hd, Lmax) / 4 + 16);
+    da.part = rows_.part[copy];
     da.o = wsf("s_ctx", (size_t)B * L.hidden); da.o_ld = L.hidden;
-    da.counters = wsi("s_attn_cnt", (size_t)B * L.heads);
-    da.err = wsi("s_err", 4);
+    da.counters = rows_.attn_cnt;
+    da.err = rows_.err;
     return da;
 }
 
@@ -1443,12 +1433,13 @@ void Engine::decode_step(int B, int Lmax) {
     hipStream_t st = stream_;
     const int H = L.hidden, hd = L.head_dim;
     const bool fuse_norm = B <= 2;
-    float* X = wsf("s_x", (size_t)B * H);
+    if (B > rows_.S || Lmax != rows_.Lcap) throw std::runtime_error("EINTERNAL: decode step outside the reserved decode rows");
+    float* X = rows_.x;
     float* XN = wsf("s_xn", (size_t)B * H);
-    int* kv_pos = wsi("s_kvpos", B);
+    int* kv_pos = rows_.kv_pos;
     float* CTX = wsf("s_ctx", (size_t)B * H);
     if (L.heads % L.kv_heads) throw std::runtime_error("EINVAL: num_attention_heads must be a multiple of num_key_value_heads");
-    int* err = wsi("s_err", 4);
+    int* err = rows_.err;
     if (B == 1 && persist_active_ && !step_skip_ && !span_rec_) {
         // every layer of the step in one persistent launch (decode_persist.hip)
         DecPersistArgs pa;
@@ -1573,7 +1564,7 @@ void Engine::decode_step(int B, int Lmax) {
             DecGemvArgs g2;
             g2.M = B; g2.N = H; g2.K = I; g2.x = HH; g2.ldx = I; g2.W = d.down.W; g2.ldw = I; g2.wdtype = d.down.wdt;
             g2.bias = d.down.b; g2.y = X; g2.ldy = H; g2.accumulate = 1;
-            launch_dec_mm_splitk(g2, wsf("s_dpart", dec_mm_splitk_part_floats(H, I)), wsi("s_dtick", dec_mm_splitk_ticks(H)), st);
+            launch_dec_mm_splitk(g2, wsf("s_dpart", dec_mm_splitk_part_floats(H, I)), rows_.d_tick, st);
             continue;
         }
         if (!d.moe) {
@@ -1618,7 +1609,7 @@ LmHeadQ8Args Engine::head_q8_args(int B) {
     const LangConfig& L = cfg_.lang;
     const int H = L.hidden;
     LmHeadQ8Args q;
-    q.x = wsf("s_x", (size_t)B * H); q.ldx = H; q.norm_w = final_norm_; q.eps = L.rms_eps;
+    q.x = rows_.x; q.ldx = H; q.norm_w = final_norm_; q.eps = L.rms_eps;
     q.q = lmq_; q.scale = lmq_scale_; q.bound = lmq_bound_; q.B = B; q.N = L.vocab; q.K = H;
     if (B >= 3) {
         q.qfrag = lmq_frag_; q.qnorm = lmq_qnorm_;
@@ -1732,7 +1723,7 @@ void Engine::decode_head(int B, DecSampleArgs& sa, const SampleArgs& pen, bool s
     const LangConfig& L = cfg_.lang;
     hipStream_t st = stream_;
     const int H = L.hidden;
-    float* SX = wsf("s_x", (size_t)B * H);
+    float* SX = rows_.x;
     if (screened && lp) throw std::runtime_error("EINTERNAL: log-probabilities need the exact head");
     if (screened) {
         // screened selection: int8 lm_head intervals + running threshold, exact rescoring of the
@@ -1766,23 +1757,146 @@ void Engine::decode_head(int B, DecSampleArgs& sa, const SampleArgs& pen, bool s
     if (lp) launch_dec_lp_final(*lp, st);
 }
 
-// log-probability workspaces for `rows` pages (reserved before a step graph is captured), as the arguments of the
-// pages [row0, row0 + sa.B) whose selection sa describes
-DecLpArgs Engine::lp_args(const DecSampleArgs& sa, int rows, int row0, int K, bool side) {
-    const size_t R = (size_t)rows, nch = dec_lp_chunks(sa.V), cap = (size_t)sa.out_cap, kk = (size_t)std::max(K, 1);
+// ---- the decode rows (engine.hpp DecodeRows).  Every buffer below has its size in this one function; the names
+// are the workspace names tools and a session's freeze-by-prefix know.
+void Engine::reserve_decode_rows(const DecodeRowsSpec& spec) {
+    const LangConfig& L = cfg_.lang;
+    const int S = spec.rows, H = L.hidden, V = L.vocab;
+    hipStream_t st = stream_;
+    last_B_ = last_Lmax_ = 0;  // profile_decode replays a generate that finished on these rows
+    rows_ = DecodeRows();
+    DecodeRows& r = rows_;
+    r.S = S; r.Lcap = spec.Lcap; r.ctx_cap = spec.ctx_cap; r.out_cap = spec.out_cap; r.ban_ld = r.ctx_cap + 1;
+    // KV cache [layers][S][kvh][Lcap][hd] f32 (block.rs:776-789 keeps the cache in f32)
+    head_stride_ = (long)r.Lcap * L.head_dim;
+    page_stride_ = (long)L.kv_heads * head_stride_;
+    const size_t kv_floats = (size_t)L.layers * S * page_stride_;
+    kc_ = wsf("kv_k", kv_floats);
+    vc_ = wsf("kv_v", kv_floats);
+    if (spec.zero_fill) {
+        HIP_CHECK(hipMemsetAsync(kc_, 0, kv_floats * 4, st));
+        HIP_CHECK(hipMemsetAsync(vc_, 0, kv_floats * 4, st));
+    }
+    // n ints under `name`, zeroed on request (+ pad bytes: rows the caller fills with upload()-sized copies)
+    auto ints = [&](const char* name, size_t n, bool zero, size_t pad = 0) {
+        int* d = (int*)ws(name, n * sizeof(int) + pad);
+        if (zero) HIP_CHECK(hipMemsetAsync(d, 0, sizeof(int) * n, st));
+        return d;
+    };
+    // the step-wide words: the arrival tickets (every launch leaves them zero) and the fused kernels' give-up flag
+    r.attn_cnt = ints("s_attn_cnt", (size_t)S * L.heads, true);
+    r.route_cnt = ints("s_route_cnt", 16, true);
+    r.dn_tick = ints("s_dntick", (size_t)H / 64 + 1, true);
+    r.d_tick = ints("s_dtick", dec_mm_splitk_ticks(H), true);
+    r.err = ints("s_err", 4, true);
+    // the hand-off copies: the attention records of `rows` pages, or of whichever n <= rows needs the most
+    for (int n = spec.handoff_max ? 1 : S; n <= S; ++n)
+        r.part_floats = std::max(r.part_floats, dec_attn_workspace(n, L.heads, L.head_dim, r.Lcap) / 4 + 16);
+    r.qkv_floats = (size_t)S * layers_[0].qkv.N;
+    r.part[0] = wsf("s_part", r.part_floats); r.qkv[0] = wsf("s_qkv", r.qkv_floats);
+    r.part[1] = wsf("s_part1", r.part_floats); r.qkv[1] = wsf("s_qkv1", r.qkv_floats);
+    wsf("p_qkv_skip", r.qkv_floats);  // the profile's variant without attention projects here (allocated before capture)
+    refill_handoffs();
+    // the per-row state
+    const bool z = spec.zero_fill;
+    const size_t pad = z ? 0 : 16;
+    r.x = wsf("s_x", (size_t)S * H);
+    if (z) HIP_CHECK(hipMemsetAsync(r.x, 0, sizeof(float) * S * H, st));
+    wsf("s_xn", (size_t)S * H);
+    r.logits = wsf("s_logits", (size_t)S * V);
+    r.ctx = ints("s_ctx_ids", (size_t)S * r.ctx_cap, z, pad);
+    r.ctx_len = ints("s_ctx_len", S, z, pad);
+    r.kv_pos = ints("s_kvpos", S, z);
+    r.kv_len = ints("s_kvlen", S, z);
+    r.done = ints("s_done", S, z, pad);
+    r.out_len = ints("s_outlen", S, z, pad);
+    r.out = ints("s_out", (size_t)S * r.out_cap, z);
+    r.tok = ints("s_tok", S, z);
+    const size_t red = dec_sample_blocks(V);
+    r.red_val = wsf("s_redv", (size_t)S * red);
+    r.red_idx = wsi("s_redi", (size_t)S * red);
+    if (spec.sampler) {
+        r.st_key = reinterpret_cast<uint32_t*>(wsi("s_stkey", (size_t)S * 2 * V));
+        r.st_idx = wsi("s_stidx", (size_t)S * 2 * V);
+        r.st_w = reinterpret_cast<double*>(wsf("s_stw", (size_t)S * 2 * V));
+        r.rng = reinterpret_cast<uint32_t*>(ints("s_rng", (size_t)S * RNG_WORDS, z, pad));
+    }
+    if (spec.rowpar) r.rowpar = reinterpret_cast<RowParams*>(ws("s_rowpar", sizeof(RowParams) * S));
+    // the n-gram ban list each selection kernel leaves for the screened head of the next step
+    if (spec.ban) r.ban = ints("s_ban", (size_t)S * r.ban_ld, z);
+    if (spec.lp_k >= 0) {
+        const size_t R = (size_t)S, nch = dec_lp_chunks(V), cap = (size_t)r.out_cap, kk = (size_t)std::max(spec.lp_k, 1);
+        r.lp_k = spec.lp_k;
+        r.lp = wsf("s_lp", R * cap);
+        r.lp_top = wsf("s_lptop", R * cap * kk);
+        r.lp_top_id = wsi("s_lptopid", R * cap * kk);
+        if (spec.lp_side) r.lp_side = wsf("s_lpctx", R * (size_t)r.ctx_cap);
+        r.lp_rec = wsi("s_lprec", R * 2);
+        r.lp_pmax = wsf("s_lppmax", R * nch); r.lp_psum = wsf("s_lppsum", R * nch);
+        r.lp_ptv = wsf("s_lpptv", R * nch * kk); r.lp_pti = wsi("s_lppti", R * nch * kk);
+        if (z) {  // (an admission resets its slot's entries)
+            HIP_CHECK(hipMemsetAsync(r.lp_rec, 0, sizeof(int) * 2 * R, st));
+            HIP_CHECK(hipMemsetAsync(r.lp, 0, sizeof(float) * R * cap, st));
+            HIP_CHECK(hipMemsetAsync(r.lp_top_id, 0, sizeof(int) * R * cap * r.lp_k, st));
+            HIP_CHECK(hipMemsetAsync(r.lp_top, 0, sizeof(float) * R * cap * r.lp_k, st));
+            if (r.lp_side) HIP_CHECK(hipMemsetAsync(r.lp_side, 0, sizeof(float) * R * r.ctx_cap, st));
+        }
+    }
+}
+
+// The fused one-page launch takes q / k / v by polling its hand-off row, and the attention merge polls its records:
+// both enter a launch sentinel-filled.  A step at another n leaves them in that n's layout, so a session refills them
+// whenever n changes (admit, retire)
+void Engine::refill_handoffs() {
+    for (int c = 0; c < 2; ++c) {
+        dec_attn_part_init(rows_.part[c], rows_.part_floats * 4, stream_);
+        dec_qkv_sentinel_init(rows_.qkv[c], rows_.qkv_floats, stream_);
+    }
+}
+
+// selection arguments for the B rows from slot0 on (generate and a session's step: slot0 = 0; an admission: its
+// slot, B = 1).  per_request: the kernels read the rows' RowParams records, not the scalars
+void Engine::sample_args(int B, int slot0, const GenParams& p, bool per_request, DecSampleArgs& sa, SampleArgs& pen) {
+    const DecodeRows& r = rows_;
+    const int V = cfg_.lang.vocab, H = cfg_.lang.hidden;
+    const size_t o = (size_t)slot0, red = dec_sample_blocks(V);
+    pen = SampleArgs();
+    pen.logits = r.logits + o * V; pen.B = B; pen.V = V; pen.ld = V;
+    pen.ctx = r.ctx + o * r.ctx_cap; pen.ctx_cap = r.ctx_cap; pen.ctx_len = r.ctx_len + o;
+    pen.rep_penalty = p.rep_penalty;
+    sa = DecSampleArgs();
+    sa.logits = pen.logits; sa.B = B; sa.V = V; sa.ld = V;
+    sa.ctx = r.ctx + o * r.ctx_cap; sa.ctx_cap = r.ctx_cap; sa.ctx_len = r.ctx_len + o; sa.ngram = p.ngram;
+    sa.red_blocks = (int)red; sa.red_val = r.red_val + o * red; sa.red_idx = r.red_idx + o * red;
+    sa.out_tok = r.tok + o; sa.out_ids = r.out + o * r.out_cap; sa.out_len = r.out_len + o;
+    sa.out_cap = r.out_cap; sa.done = r.done + o;
+    sa.eos = p.ignore_eos ? -1 : (int)p.eos;
+    sa.table = embed_; sa.table_dt = embed_dt_; sa.H = H; sa.x_next = r.x + o * H;
+    sa.kv_pos = r.kv_pos + o; sa.kv_len = r.kv_len + o;
+    if (per_request) pen.rows = sa.rows = r.rowpar + o;
+    if (p.do_sample || per_request) {
+        // stochastic selection (sampling.hip) on the sampler's scratch and the rows' RNG states
+        sa.do_sample = p.do_sample ? 1 : 0; sa.temperature = p.temperature; sa.top_p = p.top_p; sa.top_k = p.top_k;
+        sa.st_ld = V;
+        sa.st_key = r.st_key + o * 2 * V; sa.st_idx = r.st_idx + o * 2 * V; sa.st_w = r.st_w + o * V;
+        sa.rng = r.rng + o * RNG_WORDS;
+    }
+    if (r.ban) { sa.ban_ld = r.ban_ld; sa.ban_out = r.ban + o * r.ban_ld; }
+}
+
+// the log-probability rows as the arguments of the pages [row0, row0 + sa.B) whose selection sa describes
+DecLpArgs Engine::lp_args(const DecSampleArgs& sa, int row0) {
+    const DecodeRows& r = rows_;
+    const size_t o = (size_t)row0, nch = dec_lp_chunks(sa.V), cap = (size_t)r.out_cap, K = (size_t)r.lp_k;
     DecLpArgs a;
-    a.logits = sa.logits; a.B = sa.B; a.V = sa.V; a.ld = sa.ld; a.K = K;
+    a.logits = sa.logits; a.B = sa.B; a.V = sa.V; a.ld = sa.ld; a.K = r.lp_k;
     a.tok = sa.out_tok; a.out_len = sa.out_len; a.out_cap = sa.out_cap;
     a.ctx = sa.ctx; a.ctx_cap = sa.ctx_cap; a.ctx_len = sa.ctx_len;
-    a.lp = wsf("s_lp", R * cap) + (size_t)row0 * cap;
-    a.top_lp = wsf("s_lptop", R * cap * kk) + (size_t)row0 * cap * K;
-    a.top_id = wsi("s_lptopid", R * cap * kk) + (size_t)row0 * cap * K;
-    if (side) a.side = wsf("s_lpctx", R * (size_t)sa.ctx_cap) + (size_t)row0 * sa.ctx_cap;
-    a.rec = wsi("s_lprec", R * 2) + (size_t)row0 * 2;
-    a.part_max = wsf("s_lppmax", R * nch) + (size_t)row0 * nch;
-    a.part_sum = wsf("s_lppsum", R * nch) + (size_t)row0 * nch;
-    a.part_tv = wsf("s_lpptv", R * nch * kk) + (size_t)row0 * nch * K;
-    a.part_ti = wsi("s_lppti", R * nch * kk) + (size_t)row0 * nch * K;
+    a.lp = r.lp + o * cap; a.top_lp = r.lp_top + o * cap * K; a.top_id = r.lp_top_id + o * cap * K;
+    if (r.lp_side) a.side = r.lp_side + o * r.ctx_cap;
+    a.rec = r.lp_rec + o * 2;
+    a.part_max = r.lp_pmax + o * nch; a.part_sum = r.lp_psum + o * nch;
+    a.part_tv = r.lp_ptv + o * nch * K; a.part_ti = r.lp_pti + o * nch * K;
     return a;
 }
 
@@ -1813,18 +1927,13 @@ struct Engine::GenState {
     const int B;
     HipEvent ev[6];  // stream marks: vision [0, 1], prefill [2, 3], decode loop [4, 5]
     std::vector<int> prompt_len;
-    int max_p = 0, Lmax = 0;
+    int max_p = 0;
     std::vector<const float*> gpost, lpost;              // per page: its global / local post rows (device)
     std::vector<float> host_rows;                        // caller-supplied image rows of every page (ROW_HOST)
     float* vis_rows = nullptr;                           // every page's [local | global] post rows, contiguous
     std::vector<std::vector<std::pair<int, long>>> img;  // per page: (kind, index) of every <image> slot
     std::vector<std::vector<int>> extra;                 // per page: the tokens a forward without cache appends
-    float *SX = nullptr, *LOGITS = nullptr;
     std::vector<int> kvpos, kvlen;                       // first decode position / cache length of every page
-    int *d_kvpos = nullptr, *d_kvlen = nullptr, *d_done = nullptr, *d_outlen = nullptr, *d_out = nullptr, *d_tok = nullptr;
-    SampleArgs pen;
-    DecSampleArgs sa;
-    DecLpArgs lp;           // p.lp_k >= 0: the log-probability rows of every page
     PinnedBuffer<int> pin;  // poll(): [done | output length | last token] x B
     int streamed = 0;       // tokens the stream callback has seen
     size_t steps = 0;
@@ -2026,44 +2135,25 @@ void Engine::plan_image_rows(GenState& g) {
     }
 }
 
-// KV cache sized for this call, the decode kernels' tickets zeroed and their polled rows sentinel-filled
+// the decode rows of this call: a KV cache and context rows of prompt + max_new + 1 rows per page, nothing zero-filled
+// (init_sampling uploads the rows after the prefill), the scratch and rows only that its selection needs
 void Engine::reset_decode_state(GenState& g) {
-    const LangConfig& L = cfg_.lang;
-    const int B = g.B, H = L.hidden;
-    hipStream_t st = stream_;
-    const int Lmax = g.Lmax = g.max_p + (int)g.p.max_new + 1;
-    ensure_rope(Lmax + 1);
-    // KV cache [layers][B][kvh][Lmax][hd] f32 (block.rs:776-789 keeps the cache in f32)
-    head_stride_ = (long)Lmax * L.head_dim;
-    page_stride_ = (long)L.kv_heads * head_stride_;
-    const size_t kv_need = (size_t)L.layers * B * page_stride_ * 4;
-    kc_ = wsf("kv_k", kv_need / 4);
-    vc_ = wsf("kv_v", kv_need / 4);
-    // arrival tickets of the decode-attention combine: zero here, every launch leaves them zero
-    HIP_CHECK(hipMemsetAsync(wsi("s_attn_cnt", (size_t)B * L.heads), 0, sizeof(int) * B * L.heads, st));
-    HIP_CHECK(hipMemsetAsync(wsi("s_route_cnt", 16), 0, sizeof(int) * 16, st));
-    HIP_CHECK(hipMemsetAsync(wsi("s_dntick", (size_t)H / 64 + 1), 0, sizeof(int) * (H / 64 + 1), st));
-    {  // decode attention records: sentinel-filled before the first launch (the polling merge refills them)
-        const size_t pf = dec_attn_workspace(B, L.heads, L.head_dim, Lmax) / 4 + 16;
-        // the fused q/k/v + attention launch (one page) takes q / k / v by polling this row: sentinel-filled
-        const size_t qn = (size_t)B * layers_[0].qkv.N;
-        for (int c = 0; c < 2; ++c) {  // both hand-off copies (attn_args)
-            dec_attn_part_init(wsf(handoff_ws("s_part", c), pf), pf * 4, st);
-            dec_qkv_sentinel_init(wsf(handoff_ws("s_qkv", c), qn), qn, st);
-        }
-        wsf("p_qkv_skip", qn);  // the profile's variant without attention projects here (allocated before capture)
-    }
-    HIP_CHECK(hipMemsetAsync(wsi("s_dtick", dec_mm_splitk_ticks(H)), 0, sizeof(int) * dec_mm_splitk_ticks(H), st));
-    HIP_CHECK(hipMemsetAsync(wsi("s_err", 4), 0, sizeof(int) * 4, st));  // fused-kernel give-up flag
+    const GenParams& p = g.p;
+    const int B = g.B;
+    DecodeRowsSpec spec;
+    spec.rows = B; spec.Lcap = g.max_p + (int)p.max_new + 1; spec.ctx_cap = spec.Lcap; spec.out_cap = (long)p.max_new;
+    spec.sampler = p.do_sample;
+    // the screened head (exact lm_head instead while sampling, tracing or keeping log-probabilities)
+    spec.ban = !p.do_sample && !p.trace && p.lp_k < 0 && screen_applies(B, p.rep_penalty);
+    spec.lp_k = p.lp_k; spec.lp_side = rep_penalty_active(p.rep_penalty);
+    ensure_rope(spec.Lcap + 1);
+    reserve_decode_rows(spec);
     // one page: the persistent decode step (its granules: no tag of an earlier generate may match this one's)
-    persist_active_ = g.p.use_cache && persist_ok(B, Lmax);
+    persist_active_ = p.use_cache && persist_ok(B, spec.Lcap);
     if (persist_active_) {
         ensure_persist();
-        HIP_CHECK(hipMemsetAsync(persist_g_, 0xff, dec_persist_granules(L.layers) * 8, st));
+        HIP_CHECK(hipMemsetAsync(persist_g_, 0xff, dec_persist_granules(cfg_.lang.layers) * 8, stream_));
     }
-    g.SX = wsf("s_x", (size_t)B * H);
-    wsf("s_xn", (size_t)B * H);
-    g.LOGITS = wsf("s_logits", (size_t)B * L.vocab);
     g.extra.resize(B);
 }
 
@@ -2072,10 +2162,12 @@ void Engine::reset_decode_state(GenState& g) {
 // last row of each page (the reference projects every position, transformer/model.rs:243-270;
 // only the last row is ever read).  The prefill runs it once on the prompts; use_cache = false
 // (generate_without_cache, model/mod.rs:2051-2283) re-runs it on prompt + generated (g.extra) every step.
-void Engine::forward_rows(GenState& g, const std::vector<int>& lens, const std::vector<int>& past) {
+void Engine::forward_rows(GenState& g, const std::vector<int>& lens, const std::vector<int>& past, int row0) {
     const LangConfig& L = cfg_.lang;
     const int B = g.B, H = L.hidden, QKVN = layers_[0].qkv.N;
     hipStream_t st = stream_;
+    ScopedSet page0(kv_page0_, row0);
+    float* SX = rows_.x + (size_t)row0 * H;
     const PrefillPlan plan = prefill_row_plan(lens, QKVN, H, page_stride_, past);
     const long Tn = plan.T;
     const int maxl = plan.max_len;
@@ -2115,17 +2207,17 @@ void Engine::forward_rows(GenState& g, const std::vector<int>& lens, const std::
     const bool behind = std::any_of(past.begin(), past.end(), [](int p) { return p > 0; });
     const int* d_past = behind ? upload("g_past", past) : nullptr;
     for (int l = 0; l < L.layers; ++l)
-        layer_forward_prefill(l, (int)Tn, B, d_row_page, d_row_pos, d_q_off, d_kv_off, d_o_off, d_plen, maxl, g.Lmax,
+        layer_forward_prefill(l, (int)Tn, B, d_row_page, d_row_pos, d_q_off, d_kv_off, d_o_off, d_plen, maxl, rows_.Lcap,
                               d_past, plan.max_total);
     std::vector<int> last_rows(B), lr_kind(B, ROW_HOST);
     r0 = 0;
     for (int b = 0; b < B; ++b) { r0 += lens[b]; last_rows[b] = (int)(r0 - 1); }
     int* lk = upload("g_lrkind", lr_kind);
     int* li = upload("g_lrindex", last_rows);
-    launch_assemble_rows(lk, li, B, H, nullptr, 0, X, nullptr, nullptr, nullptr, g.SX, H, st);
+    launch_assemble_rows(lk, li, B, H, nullptr, 0, X, nullptr, nullptr, nullptr, SX, H, st);
     float* SXN = wsf("s_xn", (size_t)B * H);
-    launch_rmsnorm(g.SX, H, SXN, H, B, H, final_norm_, L.rms_eps, st);
-    linear(SXN, B, H, lm_head_, g.LOGITS, L.vocab);
+    launch_rmsnorm(SX, H, SXN, H, B, H, final_norm_, L.rms_eps, st);
+    linear(SXN, B, H, lm_head_, rows_.logits + (size_t)row0 * L.vocab, L.vocab);
 }
 
 // sampling state (context = prompt ids (+ generated), sampling.rs:34-96), then the prefill's own selection:
@@ -2133,61 +2225,42 @@ void Engine::forward_rows(GenState& g, const std::vector<int>& lens, const std::
 void Engine::init_sampling(GenState& g) {
     const LangConfig& L = cfg_.lang;
     const GenParams& p = g.p;
-    const int B = g.B, H = L.hidden;
+    const int B = g.B;
+    const DecodeRows& r = rows_;
     hipStream_t st = stream_;
-    const long ctx_cap = g.max_p + (long)p.max_new + 1;
+    const long ctx_cap = r.ctx_cap;
     std::vector<int> ctx((size_t)B * ctx_cap, 0), zeros(B, 0);
     for (int b = 0; b < B; ++b)
         for (int i = 0; i < g.prompt_len[b]; ++i) ctx[(size_t)b * ctx_cap + i] = g.reqs[b].ids[i];
     g.kvpos = g.prompt_len;
     g.kvlen = g.prompt_len;
     for (int& v : g.kvlen) ++v;
-    int* d_ctx = upload("s_ctx_ids", ctx);
-    int* d_ctx_len = upload("s_ctx_len", g.prompt_len);
-    g.d_kvpos = wsi("s_kvpos", B);
-    g.d_kvlen = wsi("s_kvlen", B);
-    HIP_CHECK(hipMemcpyAsync(g.d_kvpos, g.kvpos.data(), B * 4, hipMemcpyHostToDevice, st));
-    HIP_CHECK(hipMemcpyAsync(g.d_kvlen, g.kvlen.data(), B * 4, hipMemcpyHostToDevice, st));
+    upload_to(r.ctx, "s_ctx_ids", ctx);
+    upload_to(r.ctx_len, "s_ctx_len", g.prompt_len);
+    HIP_CHECK(hipMemcpyAsync(r.kv_pos, g.kvpos.data(), B * 4, hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(r.kv_len, g.kvlen.data(), B * 4, hipMemcpyHostToDevice, st));
     HIP_CHECK(hipStreamSynchronize(st));
-    g.d_done = upload("s_done", zeros);
-    g.d_outlen = upload("s_outlen", zeros);
-    g.d_out = wsi("s_out", (size_t)B * p.max_new);
-    g.d_tok = wsi("s_tok", B);
-    // penalty (applied in place to the logits when != 1) + fused greedy selection
-    SampleArgs& pen = g.pen;
-    pen.logits = g.LOGITS; pen.B = B; pen.V = L.vocab; pen.ld = L.vocab; pen.ctx = d_ctx; pen.ctx_cap = ctx_cap;
-    pen.ctx_len = d_ctx_len; pen.rep_penalty = p.rep_penalty;
-    DecSampleArgs& sa = g.sa;
-    sa.logits = g.LOGITS; sa.B = B; sa.V = L.vocab; sa.ld = L.vocab; sa.ctx = d_ctx; sa.ctx_cap = ctx_cap;
-    sa.ctx_len = d_ctx_len; sa.ngram = p.ngram;
-    sa.red_blocks = (int)dec_sample_blocks(L.vocab);
-    sa.red_val = wsf("s_redv", (size_t)B * sa.red_blocks); sa.red_idx = wsi("s_redi", (size_t)B * sa.red_blocks);
-    sa.out_tok = g.d_tok; sa.out_ids = g.d_out; sa.out_len = g.d_outlen; sa.out_cap = (long)p.max_new; sa.done = g.d_done;
-    sa.eos = p.ignore_eos ? -1 : (int)p.eos;
-    sa.table = embed_; sa.table_dt = embed_dt_; sa.H = H; sa.x_next = g.SX; sa.kv_pos = g.d_kvpos; sa.kv_len = g.d_kvlen;
+    upload_to(r.done, "s_done", zeros);
+    upload_to(r.out_len, "s_outlen", zeros);
     if (p.do_sample) {
-        // stochastic selection (sampling.hip): StdRng::seed_from_u64(seed) per page — every page starts
-        // from init_rng(seed) like a single-page generate call (model/mod.rs:1917) — or entropy
-        sa.do_sample = 1; sa.temperature = p.temperature; sa.top_p = p.top_p; sa.top_k = p.top_k;
-        sa.st_ld = L.vocab;
-        sa.st_key = reinterpret_cast<uint32_t*>(wsi("s_stkey", (size_t)B * 2 * L.vocab));
-        sa.st_idx = wsi("s_stidx", (size_t)B * 2 * L.vocab);
-        sa.st_w = reinterpret_cast<double*>(wsf("s_stw", (size_t)B * 2 * L.vocab));
+        // StdRng::seed_from_u64(seed) per page — every page starts from init_rng(seed) like a single-page
+        // generate call (model/mod.rs:1917) — or entropy
         uint64_t seed = p.seed;
         if (!p.seed_set) {
             std::random_device rd;
             seed = ((uint64_t)rd() << 32) ^ rd();
         }
         const std::vector<uint32_t> rng = rng_state_from_u64(seed);
-        std::vector<int> all((size_t)B * RNG_WORDS);
+        std::vector<uint32_t> all((size_t)B * RNG_WORDS);
         for (int b = 0; b < B; ++b) memcpy(&all[(size_t)b * RNG_WORDS], rng.data(), sizeof(uint32_t) * RNG_WORDS);
-        sa.rng = reinterpret_cast<uint32_t*>(upload("s_rng", all));
+        upload_to(r.rng, "s_rng", all);
     }
+    // penalty (applied in place to the logits when != 1) + fused greedy selection
+    SampleArgs pen;
+    DecSampleArgs sa;
+    sample_args(B, 0, p, false, sa, pen);
     ensure_mm_weights(B);
-    if (!p.do_sample && !p.trace && p.lp_k < 0 && screen_applies(B, p.rep_penalty)) {
-        // the screened head reads the n-gram ban list each selection kernel leaves for the next step
-        sa.ban_ld = ctx_cap + 1;
-        sa.ban_out = wsi("s_ban", (size_t)B * sa.ban_ld);
+    if (r.ban) {  // the screened head
         reserve_head_ws(B);
         if (getenv("DSOCR_SCREEN_STATS")) HIP_CHECK(hipMemsetAsync(wsi("s_scrstats", 32), 0, 128, st));
     }
@@ -2198,31 +2271,29 @@ void Engine::init_sampling(GenState& g) {
     trace_steps_ = (long)p.max_new;
     if (trace_) {
         HIP_CHECK(hipMemsetAsync(trace_, 0, sizeof(float) * B * p.max_new * L.vocab, st));
-        launch_trace_logits(g.LOGITS, B, L.vocab, L.vocab, g.d_outlen, g.d_done, trace_, trace_steps_, st);
+        launch_trace_logits(r.logits, B, L.vocab, L.vocab, r.out_len, r.done, trace_, trace_steps_, st);
     }
-    // log-probabilities: the exact head (no ban rows above), an entry for the prefill's own selection too
-    if (p.lp_k >= 0) {
-        g.lp = lp_args(sa, B, 0, p.lp_k, rep_penalty_active(p.rep_penalty));
-        launch_dec_lp_partial(g.lp, st);
-    }
+    // log-probabilities: the exact head (no ban rows), an entry for the prefill's own selection too
+    const DecLpArgs lp = p.lp_k >= 0 ? lp_args(sa, 0) : DecLpArgs();
+    if (p.lp_k >= 0) launch_dec_lp_partial(lp, st);
     // the fused selection kernel advances the KV position; after the prefill the first
     // decode position must be P, so start one behind
     launch_rep_penalty(pen, st);
     std::vector<int> pm1(B), lm1(B);
     for (int b = 0; b < B; ++b) { pm1[b] = g.kvpos[b] - 1; lm1[b] = g.kvlen[b] - 1; }
-    HIP_CHECK(hipMemcpyAsync(g.d_kvpos, pm1.data(), B * 4, hipMemcpyHostToDevice, st));
-    HIP_CHECK(hipMemcpyAsync(g.d_kvlen, lm1.data(), B * 4, hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(r.kv_pos, pm1.data(), B * 4, hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(r.kv_len, lm1.data(), B * 4, hipMemcpyHostToDevice, st));
     launch_dec_sample(sa, st);
-    if (p.lp_k >= 0) launch_dec_lp_final(g.lp, st);
+    if (p.lp_k >= 0) launch_dec_lp_final(lp, st);
     HIP_CHECK(hipStreamSynchronize(st));
 }
 
 // done flags, output lengths and the last tokens of every page into g.pin; true when every page is done
 bool Engine::poll(GenState& g) {
     const int B = g.B;
-    HIP_CHECK(hipMemcpyAsync(g.pin, g.d_done, B * 4, hipMemcpyDeviceToHost, stream_));
-    HIP_CHECK(hipMemcpyAsync(g.pin + B, g.d_outlen, B * 4, hipMemcpyDeviceToHost, stream_));
-    HIP_CHECK(hipMemcpyAsync(g.pin + 2 * B, g.d_tok, B * 4, hipMemcpyDeviceToHost, stream_));
+    HIP_CHECK(hipMemcpyAsync(g.pin, rows_.done, B * 4, hipMemcpyDeviceToHost, stream_));
+    HIP_CHECK(hipMemcpyAsync(g.pin + B, rows_.out_len, B * 4, hipMemcpyDeviceToHost, stream_));
+    HIP_CHECK(hipMemcpyAsync(g.pin + 2 * B, rows_.tok, B * 4, hipMemcpyDeviceToHost, stream_));
     HIP_CHECK(hipStreamSynchronize(stream_));
     bool all = true;
     for (int b = 0; b < B; ++b) all &= g.pin[b] != 0;
@@ -2234,7 +2305,7 @@ void Engine::stream_tokens(GenState& g, int n) {
     if (n <= g.streamed) return;  // no new token (EOS selected, or the page is done)
     g.streamed = n;
     std::vector<int> tmp(n);
-    if (n) HIP_CHECK(hipMemcpy(tmp.data(), g.d_out, n * 4, hipMemcpyDeviceToHost));
+    if (n) HIP_CHECK(hipMemcpy(tmp.data(), rows_.out, n * 4, hipMemcpyDeviceToHost));
     std::vector<int64_t> t64(tmp.begin(), tmp.end());
     g.cb(t64.size(), t64.data(), g.user);
 }
@@ -2247,14 +2318,17 @@ void Engine::decode_uncached(GenState& g) {
     hipStream_t st = stream_;
     HIP_CHECK(hipEventRecord(g.ev[4], st));
     std::vector<int> lens = g.prompt_len;
+    SampleArgs pen;
+    DecSampleArgs sa;
+    sample_args(B, 0, g.p, false, sa, pen);
     for (size_t i = 1; i < g.p.max_new; ++i) {
         if (poll(g)) break;
         for (int b = 0; b < B; ++b)
             if (!g.pin[b]) { g.extra[b].push_back(g.pin[2 * B + b]); ++lens[b]; }
         forward_rows(g, lens);
-        if (trace_) launch_trace_logits(g.LOGITS, B, V, V, g.d_outlen, g.d_done, trace_, trace_steps_, st);
-        launch_rep_penalty(g.pen, st);
-        launch_dec_sample(g.sa, st);
+        if (trace_) launch_trace_logits(rows_.logits, B, V, V, rows_.out_len, rows_.done, trace_, trace_steps_, st);
+        launch_rep_penalty(pen, st);
+        launch_dec_sample(sa, st);
         ++g.steps;
         if (g.cb && B == 1) {
             poll(g);
@@ -2277,7 +2351,7 @@ void Engine::begin_spans(GenState& g) {
         span_chain_rec_ = (unsigned long long*)ws("s_span_chain_rec", (size_t)span_cap_ * nreg * 32);
         span_tmark_ = (unsigned long long*)ws("s_span_tmark", 16);
         span_rec_ = span_chain_rec_;
-        span_step_ = g.d_outlen;
+        span_step_ = rows_.out_len;
         chain_active_ = true;
         HIP_CHECK(hipMemsetAsync(span_chain_rec_, 0, (size_t)span_cap_ * nreg * 32, st));
     } else if (span_mode_) {
@@ -2285,7 +2359,7 @@ void Engine::begin_spans(GenState& g) {
         const size_t rec_bytes = (size_t)SPAN_KINDS * layers * span_cap_ * 4 * 8;
         span_slots_ = (unsigned long long*)ws("s_span_slots", (size_t)SPAN_SLOTS * 16);
         span_rec_ = (unsigned long long*)ws("s_span_rec", rec_bytes);
-        span_step_ = g.d_outlen;
+        span_step_ = rows_.out_len;
         HIP_CHECK(hipMemsetAsync(span_slots_, 0, (size_t)SPAN_SLOTS * 16, st));
         HIP_CHECK(hipMemsetAsync(span_rec_, 0, rec_bytes, st));
         if (span_ev_.empty()) span_ev_.resize((size_t)SPAN_KINDS * layers * 2);
@@ -2339,8 +2413,12 @@ void Engine::collect_spans() {
 
 // one decode step: the layers, the head and the selection (captured once, replayed per token)
 void Engine::step_body(GenState& g) {
-    decode_step(g.B, g.Lmax);
-    decode_head(g.B, g.sa, g.pen, g.sa.ban_out != nullptr, g.p.lp_k >= 0 ? &g.lp : nullptr);
+    SampleArgs pen;
+    DecSampleArgs sa;
+    sample_args(g.B, 0, g.p, false, sa, pen);
+    const DecLpArgs lp = g.p.lp_k >= 0 ? lp_args(sa, 0) : DecLpArgs();
+    decode_step(g.B, rows_.Lcap);
+    decode_head(g.B, sa, pen, rows_.ban != nullptr, g.p.lp_k >= 0 ? &lp : nullptr);
     // chain spans: the step's one fold, after the head (the step counter has advanced: record at count - 1)
     if (chain_active_)
         launch_span_chain_fold(span_chain_, cfg_.lang.layers * SPAN_KINDS_CHAIN, span_chain_rec_, span_step_, span_cap_,
@@ -2356,7 +2434,7 @@ void Engine::decode_cached(GenState& g) {
     begin_spans(g);
     // make sure every decode workspace exists before capture: a dry step allocates them
     // (it writes the step-0 K/V slot, which the real step rewrites), then the state is restored
-    decode_step(B, g.Lmax);
+    decode_step(B, rows_.Lcap);
     if (persist_active_) {  // the dry step's granules carry step 1's tags: reset them
         HIP_CHECK(hipMemsetAsync(persist_g_, 0xff, dec_persist_granules(L.layers) * 8, st));
         persist_stamps_host_.clear();
@@ -2373,9 +2451,9 @@ void Engine::decode_cached(GenState& g) {
         HIP_CHECK(hipMemsetAsync(span_chain_, 0, (size_t)L.layers * SPAN_KINDS_CHAIN * SPAN_SLOTS * 16, st));
         HIP_CHECK(hipMemsetAsync(span_tmark_, 0, 16, st));
     }
-    HIP_CHECK(hipMemcpyAsync(g.d_kvpos, g.kvpos.data(), B * 4, hipMemcpyHostToDevice, st));
-    HIP_CHECK(hipMemcpyAsync(g.d_kvlen, g.kvlen.data(), B * 4, hipMemcpyHostToDevice, st));
-    launch_embed_tokens(embed_, embed_dt_, g.d_tok, B, H, g.SX, H, st);
+    HIP_CHECK(hipMemcpyAsync(rows_.kv_pos, g.kvpos.data(), B * 4, hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(rows_.kv_len, g.kvlen.data(), B * 4, hipMemcpyHostToDevice, st));
+    launch_embed_tokens(embed_, embed_dt_, rows_.tok, B, H, rows_.x, H, st);
     HIP_CHECK(hipStreamSynchronize(st));
 
     const bool use_graph = graphs_on();
@@ -2422,9 +2500,9 @@ std::vector<std::vector<int64_t>> Engine::collect_outputs(GenState& g) {
     const GenParams& p = g.p;
     const int B = g.B;
     int e = 0;
-    HIP_CHECK(hipMemcpy(&e, wsi("s_err", 4), sizeof(int), hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(&e, rows_.err, sizeof(int), hipMemcpyDeviceToHost));
     if (e) throw std::runtime_error("EINTERNAL: decode hand-off timed out inside a fused kernel");
-    if (g.sa.ban_out && getenv("DSOCR_SCREEN_STATS")) {
+    if (rows_.ban && getenv("DSOCR_SCREEN_STATS")) {
         unsigned long long h[16] = {0};
         HIP_CHECK(hipMemcpy(h, wsi("s_scrstats", 32), sizeof(h), hipMemcpyDeviceToHost));
         const double st = h[0] ? (double)h[0] : 1.0;
@@ -2433,8 +2511,8 @@ std::vector<std::vector<int64_t>> Engine::collect_outputs(GenState& g) {
         fprintf(stderr, "\n");
     }
     std::vector<int> h_out((size_t)B * p.max_new), h_outlen(B);
-    HIP_CHECK(hipMemcpy(h_out.data(), g.d_out, h_out.size() * 4, hipMemcpyDeviceToHost));
-    HIP_CHECK(hipMemcpy(h_outlen.data(), g.d_outlen, B * 4, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(h_out.data(), rows_.out, h_out.size() * 4, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(h_outlen.data(), rows_.out_len, B * 4, hipMemcpyDeviceToHost));
     std::vector<std::vector<int64_t>> out(B);
     for (int b = 0; b < B; ++b) out[b].assign(h_out.begin() + (size_t)b * p.max_new, h_out.begin() + (size_t)b * p.max_new + h_outlen[b]);
     timings_.vision_compute_ms = ms_between(g.ev[0], g.ev[1]);
@@ -2448,16 +2526,16 @@ std::vector<std::vector<int64_t>> Engine::collect_outputs(GenState& g) {
         LogprobRows& r = last_lp_;
         r.K = p.lp_k; r.cap = p.max_new; r.n = h_outlen;
         r.lp.resize((size_t)B * r.cap);
-        HIP_CHECK(hipMemcpy(r.lp.data(), g.lp.lp, r.lp.size() * 4, hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(r.lp.data(), rows_.lp, r.lp.size() * 4, hipMemcpyDeviceToHost));
         r.top_id.resize((size_t)B * r.cap * r.K);
         r.top_lp.resize(r.top_id.size());
         if (!r.top_id.empty()) {
-            HIP_CHECK(hipMemcpy(r.top_id.data(), g.lp.top_id, r.top_id.size() * 4, hipMemcpyDeviceToHost));
-            HIP_CHECK(hipMemcpy(r.top_lp.data(), g.lp.top_lp, r.top_lp.size() * 4, hipMemcpyDeviceToHost));
+            HIP_CHECK(hipMemcpy(r.top_id.data(), rows_.lp_top_id, r.top_id.size() * 4, hipMemcpyDeviceToHost));
+            HIP_CHECK(hipMemcpy(r.top_lp.data(), rows_.lp_top, r.top_lp.size() * 4, hipMemcpyDeviceToHost));
         }
     }
     last_B_ = B;
-    last_Lmax_ = g.Lmax;
+    last_Lmax_ = rows_.Lcap;
     return out;
 }
 
@@ -2491,12 +2569,12 @@ void Engine::session_open(int S, int max_context, const GenParams& p, bool per_r
     const LangConfig& L = cfg_.lang;
     if (L.heads % L.kv_heads) throw std::runtime_error("EINVAL: num_attention_heads must be a multiple of num_key_value_heads");
     if (L.head_dim % 4) throw std::runtime_error("EINVAL: a session needs head_dim % 4 == 0");
-    const int H = L.hidden, V = L.vocab, QKVN = layers_[0].qkv.N;
+    const int H = L.hidden;
     hipStream_t st = stream_;
     auto sp = std::make_unique<Session>();
     Session& s = *sp;
     s.S = S; s.max_context = max_context; s.p = p; s.per_request = per_request;
-    s.logprobs = logprobs; s.lp_side = logprobs && (per_request || rep_penalty_active(p.rep_penalty));
+    s.logprobs = logprobs;
     // Capacity invariant.  The selection kernels advance kv_pos of every row on every step, done or not, so a
     // finished page that waits for the end of its burst keeps appending K/V rows.  A page is admitted only with
     // prompt + max_new + 1 <= max_context and produces its last token at kv_pos <= prompt + max_new - 1; it is
@@ -2504,105 +2582,49 @@ void Engine::session_open(int S, int max_context, const GenParams& p, bool per_r
     // max_context + kBurstCap rows, and session_step refuses (on the host, before any launch) a burst that would
     // take a slot's kv_pos past them.  The context row has the same length; the output row stops on the device
     // at out_cap (dec_sample: out_len < out_cap, n < ctx_cap).
-    s.Lcap = max_context + Session::kBurstCap;
-    s.ctx_cap = s.Lcap;
-    s.out_cap = (long)p.max_new;
-    s.ban_ld = s.ctx_cap + 1;
+    DecodeRowsSpec spec;
+    spec.rows = S; spec.Lcap = max_context + Session::kBurstCap; spec.ctx_cap = spec.Lcap; spec.out_cap = (long)p.max_new;
+    s.screened = !p.do_sample && !per_request && !logprobs;
+    for (int n = 1; n <= S; ++n) s.screened = s.screened && screen_applies(n, p.rep_penalty);
+    // per-request parameters: what both heads need at every n, so nothing grows after the freeze (any slot may
+    // sample: the sampler's scratch and RNG rows for all of them; the ban rows are always kept and both final
+    // kernels write them every step: either head can take over from the other at a step boundary)
+    spec.sampler = p.do_sample || per_request;
+    spec.ban = s.screened || per_request;
+    spec.rowpar = true;
+    spec.handoff_max = true;  // the step runs at every n <= S
+    spec.zero_fill = true;    // the dry steps below read kv_pos 0 and a zero input row
+    if (logprobs) {  // (the raw logits at the context ids too where a penalty can apply)
+        spec.lp_k = LP_MAX_TOP;
+        spec.lp_side = per_request || rep_penalty_active(p.rep_penalty);
+    }
     s.slot.resize(S);
     s.pin = PinnedBuffer<int>(2 * S + 1);
     ensure_small(64);
-    ensure_rope(s.Lcap + 1);
+    ensure_rope(spec.Lcap + 1);
     const long head_stride0 = head_stride_, page_stride0 = page_stride_;
     try {
-        head_stride_ = (long)s.Lcap * L.head_dim;
-        page_stride_ = (long)L.kv_heads * head_stride_;
         kv_pages_ = S;
         kv_page0_ = 0;
         persist_active_ = false;  // (DSOCR_PERSIST is a generate-only switch)
-        const size_t kv_floats = (size_t)L.layers * S * page_stride_;
-        kc_ = wsf("kv_k", kv_floats);
-        vc_ = wsf("kv_v", kv_floats);
-        HIP_CHECK(hipMemsetAsync(kc_, 0, kv_floats * 4, st));
-        HIP_CHECK(hipMemsetAsync(vc_, 0, kv_floats * 4, st));
-        // the decode kernels' tickets zeroed and their polled rows sentinel-filled, as reset_decode_state
-        HIP_CHECK(hipMemsetAsync(wsi("s_attn_cnt", (size_t)S * L.heads), 0, sizeof(int) * S * L.heads, st));
-        HIP_CHECK(hipMemsetAsync(wsi("s_route_cnt", 16), 0, sizeof(int) * 16, st));
-        HIP_CHECK(hipMemsetAsync(wsi("s_dntick", (size_t)H / 64 + 1), 0, sizeof(int) * (H / 64 + 1), st));
-        HIP_CHECK(hipMemsetAsync(wsi("s_dtick", dec_mm_splitk_ticks(H)), 0, sizeof(int) * dec_mm_splitk_ticks(H), st));
-        s.err = wsi("s_err", 4);
-        HIP_CHECK(hipMemsetAsync(s.err, 0, sizeof(int) * 4, st));
-        for (int n = 1; n <= S; ++n)
-            s.part_floats = std::max(s.part_floats, dec_attn_workspace(n, L.heads, L.head_dim, s.Lcap) / 4 + 16);
-        s.qkv_floats = (size_t)S * QKVN;
-        for (int c = 0; c < 2; ++c) {
-            s.part[c] = wsf(handoff_ws("s_part", c), s.part_floats);
-            s.qkv[c] = wsf(handoff_ws("s_qkv", c), s.qkv_floats);
-        }
-        wsf("p_qkv_skip", s.qkv_floats);
-        // the per-slot rows, zeroed: the dry steps below read kv_pos 0 and a zero input row
-        s.sx = wsf("s_x", (size_t)S * H);
-        HIP_CHECK(hipMemsetAsync(s.sx, 0, sizeof(float) * S * H, st));
-        wsf("s_xn", (size_t)S * H);
-        s.logits = wsf("s_logits", (size_t)S * V);
-        auto zeroed = [&](const char* name, size_t n) {
-            int* d = wsi(name, n);
-            HIP_CHECK(hipMemsetAsync(d, 0, sizeof(int) * n, st));
-            return d;
-        };
-        s.ctx = zeroed("s_ctx_ids", (size_t)S * s.ctx_cap);
-        s.ctx_len = zeroed("s_ctx_len", S);
-        s.kvpos = zeroed("s_kvpos", S);
-        s.kvlen = zeroed("s_kvlen", S);
-        s.done = zeroed("s_done", S);
-        s.outlen = zeroed("s_outlen", S);
-        s.out = zeroed("s_out", (size_t)S * s.out_cap);
-        s.tok = zeroed("s_tok", S);
-        const size_t red = dec_sample_blocks(V);
-        wsf("s_redv", (size_t)S * red);
-        wsi("s_redi", (size_t)S * red);
-        // per-request parameters: what both heads need at every n, so nothing grows after the freeze (any slot may
-        // sample: the sampler's scratch and RNG rows for all of them)
-        if (p.do_sample || per_request) {
-            wsi("s_stkey", (size_t)S * 2 * V);
-            wsi("s_stidx", (size_t)S * 2 * V);
-            wsf("s_stw", (size_t)S * 2 * V);
-            s.rng = reinterpret_cast<uint32_t*>(zeroed("s_rng", (size_t)S * RNG_WORDS));
-        }
-        s.rowpar = reinterpret_cast<RowParams*>(ws("s_rowpar", sizeof(RowParams) * S));
+        reserve_decode_rows(spec);
         {
             const std::vector<RowParams> init((size_t)S, resolve_row_params(p));
-            HIP_CHECK(hipMemcpy(s.rowpar, init.data(), sizeof(RowParams) * S, hipMemcpyHostToDevice));
+            HIP_CHECK(hipMemcpy(rows_.rowpar, init.data(), sizeof(RowParams) * S, hipMemcpyHostToDevice));
         }
-        s.stage = wsi("ss_stage", (size_t)SS_HEAD + RNG_WORDS + s.ctx_cap);
+        s.stage = wsi("ss_stage", (size_t)SS_HEAD + RNG_WORDS + rows_.ctx_cap);
         ensure_mm_weights(S);
-        s.screened = !p.do_sample && !per_request && !logprobs;
-        for (int n = 1; n <= S; ++n) s.screened = s.screened && screen_applies(n, p.rep_penalty);
-        if (s.screened || per_request) {
-            // (per request the ban rows are always kept and both final kernels write them every step: either head
-            // can take over from the other at a step boundary)
-            s.ban = zeroed("s_ban", (size_t)S * s.ban_ld);
+        if (rows_.ban) {
             for (int n = 1; n <= S; ++n) reserve_head_ws(n);
+            if (getenv("DSOCR_SCREEN_STATS")) HIP_CHECK(hipMemsetAsync(wsi("s_scrstats", 32), 0, sizeof(int) * 32, st));
         }
         // every workspace the decode step asks for by name, at every n: a dry step per n allocates them (it
         // appends K/V row 0 of the empty slots, which an admission's prefill rewrites)
-        if ((s.screened || per_request) && getenv("DSOCR_SCREEN_STATS")) zeroed("s_scrstats", 32);
-        if (logprobs) {  // the rows of every slot, before the freeze below (an admission resets its slot's)
-            DecSampleArgs sa;
-            SampleArgs pen;
-            session_sample_args(s, S, 0, sa, pen);
-            const DecLpArgs a = session_lp_args(s, sa, 0);
-            HIP_CHECK(hipMemsetAsync(a.rec, 0, sizeof(int) * 2 * S, st));
-            HIP_CHECK(hipMemsetAsync(a.lp, 0, sizeof(float) * S * s.out_cap, st));
-            HIP_CHECK(hipMemsetAsync(a.top_id, 0, sizeof(int) * S * s.out_cap * LP_MAX_TOP, st));
-            HIP_CHECK(hipMemsetAsync(a.top_lp, 0, sizeof(float) * S * s.out_cap * LP_MAX_TOP, st));
-            if (a.side) HIP_CHECK(hipMemsetAsync(a.side, 0, sizeof(float) * S * s.ctx_cap, st));
-        }
         for (int n = 1; n <= S; ++n) {
-            session_sentinels(s);
-            decode_step(n, s.Lcap);
+            decode_step(n, rows_.Lcap);
+            refill_handoffs();
         }
-        HIP_CHECK(hipMemsetAsync(s.sx, 0, sizeof(float) * S * H, st));
-        session_sentinels(s);
+        HIP_CHECK(hipMemsetAsync(rows_.x, 0, sizeof(float) * S * H, st));
         HIP_CHECK(hipStreamSynchronize(st));
         // from here on no admission may move one of them: the captured graphs hold their addresses
         for (const auto& kv : ws_)
@@ -2617,53 +2639,6 @@ void Engine::session_open(int S, int max_context, const GenParams& p, bool per_r
         throw;
     }
     sess_ = std::move(sp);
-}
-
-// the fused one-page launch takes q / k / v by polling s_qkv, and the attention merge polls its records: both
-// enter a launch sentinel-filled.  A step at another n leaves them in that n's layout, so they are refilled
-// whenever n changes (admit, retire)
-void Engine::session_sentinels(const Session& s) {
-    for (int c = 0; c < 2; ++c) {
-        dec_attn_part_init(s.part[c], s.part_floats * 4, stream_);
-        dec_qkv_sentinel_init(s.qkv[c], s.qkv_floats, stream_);
-    }
-}
-
-// selection arguments for the B slots from slot0 on (the step: slot0 = 0, B = n; an admission: its slot, B = 1)
-void Engine::session_sample_args(const Session& s, int B, int slot0, DecSampleArgs& sa, SampleArgs& pen) {
-    const LangConfig& L = cfg_.lang;
-    const int V = L.vocab, H = L.hidden;
-    const GenParams& p = s.p;
-    pen = SampleArgs();
-    pen.logits = s.logits + (size_t)slot0 * V; pen.B = B; pen.V = V; pen.ld = V;
-    pen.ctx = s.ctx + (size_t)slot0 * s.ctx_cap; pen.ctx_cap = s.ctx_cap; pen.ctx_len = s.ctx_len + slot0;
-    pen.rep_penalty = p.rep_penalty;
-    if (s.per_request) pen.rows = s.rowpar + slot0;
-    sa = DecSampleArgs();
-    sa.logits = pen.logits; sa.B = B; sa.V = V; sa.ld = V;
-    sa.ctx = s.ctx + (size_t)slot0 * s.ctx_cap; sa.ctx_cap = s.ctx_cap; sa.ctx_len = s.ctx_len + slot0; sa.ngram = p.ngram;
-    sa.red_blocks = (int)dec_sample_blocks(V);
-    sa.red_val = wsf("s_redv", (size_t)s.S * sa.red_blocks) + (size_t)slot0 * sa.red_blocks;
-    sa.red_idx = wsi("s_redi", (size_t)s.S * sa.red_blocks) + (size_t)slot0 * sa.red_blocks;
-    sa.out_tok = s.tok + slot0; sa.out_ids = s.out + (size_t)slot0 * s.out_cap; sa.out_len = s.outlen + slot0;
-    sa.out_cap = s.out_cap; sa.done = s.done + slot0;
-    sa.eos = p.ignore_eos ? -1 : (int)p.eos;
-    sa.table = embed_; sa.table_dt = embed_dt_; sa.H = H; sa.x_next = s.sx + (size_t)slot0 * H;
-    sa.kv_pos = s.kvpos + slot0; sa.kv_len = s.kvlen + slot0;
-    if (s.per_request) sa.rows = s.rowpar + slot0;  // (the scalars above and below are then not read)
-    if (p.do_sample || s.per_request) {
-        sa.do_sample = p.do_sample ? 1 : 0; sa.temperature = p.temperature; sa.top_p = p.top_p; sa.top_k = p.top_k;
-        sa.st_ld = V;
-        sa.st_key = reinterpret_cast<uint32_t*>(wsi("s_stkey", (size_t)s.S * 2 * V)) + (size_t)slot0 * 2 * V;
-        sa.st_idx = wsi("s_stidx", (size_t)s.S * 2 * V) + (size_t)slot0 * 2 * V;
-        sa.st_w = reinterpret_cast<double*>(wsf("s_stw", (size_t)s.S * 2 * V)) + (size_t)slot0 * V;
-        sa.rng = s.rng + (size_t)slot0 * RNG_WORDS;
-    }
-    if (s.ban) { sa.ban_ld = s.ban_ld; sa.ban_out = s.ban + (size_t)slot0 * s.ban_ld; }
-}
-
-DecLpArgs Engine::session_lp_args(const Session& s, const DecSampleArgs& sa, int slot0) {
-    return lp_args(sa, s.S, slot0, LP_MAX_TOP, s.lp_side);
 }
 
 int Engine::session_admit(const GenRequest& rq, size_t max_new, bool seed_set, uint64_t seed) {
@@ -2686,8 +2661,8 @@ void Engine::session_admit_checks(const Session& s, const GenRequest& rq, const 
     if (s.n >= s.S) throw std::runtime_error("EINVAL: every session slot is in use (retire one first)");
     const size_t P = rq.ids.size();
     if (P == 0) throw std::runtime_error("EINVAL: empty prompt");
-    if (max_new == 0 || (long)max_new > s.out_cap)
-        throw std::runtime_error("EINVAL: max_new_tokens must be 1.." + std::to_string(s.out_cap) + " in this session");
+    if (max_new == 0 || (long)max_new > rows_.out_cap)
+        throw std::runtime_error("EINVAL: max_new_tokens must be 1.." + std::to_string(rows_.out_cap) + " in this session");
     if (P + max_new + 1 > (size_t)s.max_context)
         throw std::runtime_error("EINVAL: the page needs " + std::to_string(P + max_new + 1) +
                                  " context rows (prompt + max_new_tokens + 1), the session has " + std::to_string(s.max_context));
@@ -2714,8 +2689,6 @@ void Engine::session_admit_checks(const Session& s, const GenRequest& rq, const 
 int Engine::session_admit(const GenRequest& rq, const GenParams& rp) {
     Session& s = open_session();
     const size_t max_new = rp.max_new;
-    const LangConfig& L = cfg_.lang;
-    const int H = L.hidden, V = L.vocab;
     // every check first: nothing below may fail on the request itself once device state changes
     session_admit_checks(s, rq, rp, false);
     const RowParams row = resolve_row_params(rp);
@@ -2726,15 +2699,9 @@ int Engine::session_admit(const GenRequest& rq, const GenParams& rp) {
     GenState g(reqs, gp, nullptr, nullptr);
     embed_pages(g);
     plan_image_rows(g);
-    // the prefill of this page alone, into slot `slot` of the session cache and of s_x / s_logits
-    g.Lmax = s.Lcap;
-    g.SX = s.sx + (size_t)slot * H;
-    g.LOGITS = s.logits + (size_t)slot * V;
+    // the prefill of this page alone, into slot `slot` of the session cache and of the x / logits rows
     g.extra.resize(1);
-    {
-        ScopedSet page0(kv_page0_, slot);
-        forward_rows(g, g.prompt_len);
-    }
+    forward_rows(g, g.prompt_len, {}, slot);
     return session_admit_tail(s, rq, rp, row);
 }
 
@@ -2762,25 +2729,25 @@ int Engine::session_admit_tail(Session& s, const GenRequest& rq, const GenParams
     std::memcpy(h + SS_HEAD + RNG_WORDS, rq.ids.data(), P * 4);
     HIP_CHECK(hipMemcpyAsync(s.stage, h, stage_ints * 4, hipMemcpyHostToDevice, st));
     SlotInitArgs ia;
-    ia.stage = s.stage; ia.slot = slot; ia.ctx = s.ctx; ia.ctx_cap = s.ctx_cap; ia.ctx_len = s.ctx_len;
-    ia.kv_pos = s.kvpos; ia.kv_len = s.kvlen; ia.done = s.done; ia.out_len = s.outlen; ia.tok = s.tok;
-    ia.rng = s.rng; ia.rng_words = RNG_WORDS; ia.ban = s.ban; ia.ban_ld = s.ban_ld;
-    if (s.per_request) ia.rowpar = s.rowpar;
+    const DecodeRows& r = rows_;
+    ia.stage = s.stage; ia.slot = slot; ia.ctx = r.ctx; ia.ctx_cap = r.ctx_cap; ia.ctx_len = r.ctx_len;
+    ia.kv_pos = r.kv_pos; ia.kv_len = r.kv_len; ia.done = r.done; ia.out_len = r.out_len; ia.tok = r.tok;
+    ia.rng = r.rng; ia.rng_words = RNG_WORDS; ia.ban = r.ban; ia.ban_ld = r.ban_ld;
+    if (s.per_request) ia.rowpar = r.rowpar;
     DecSampleArgs sa;
     SampleArgs pen;
-    session_sample_args(s, 1, slot, sa, pen);
+    sample_args(1, slot, s.p, s.per_request, sa, pen);
     DecLpArgs lp;
-    if (s.logprobs) {
-        lp = session_lp_args(s, sa, 0);  // (slot init takes the rows' bases)
-        ia.lp = lp.lp; ia.lp_top_id = lp.top_id; ia.lp_top = lp.top_lp; ia.lp_k = lp.K; ia.out_cap = s.out_cap;
-        lp = session_lp_args(s, sa, slot);
+    if (s.logprobs) {  // (slot init takes the rows' bases)
+        ia.lp = r.lp; ia.lp_top_id = r.lp_top_id; ia.lp_top = r.lp_top; ia.lp_k = r.lp_k; ia.out_cap = r.out_cap;
+        lp = lp_args(sa, slot);
     }
     launch_session_slot_init(ia, st);
     if (s.logprobs) launch_dec_lp_partial(lp, st);
     launch_rep_penalty(pen, st);
     launch_dec_sample(sa, st);  // the first token, its embedding into the slot's s_x row, the ban list
     if (s.logprobs) launch_dec_lp_final(lp, st);  // entry 0 of the slot
-    session_sentinels(s);
+    refill_handoffs();
     HIP_CHECK(hipStreamSynchronize(st));
     Session::Slot& sl = s.slot[slot];
     sl.max_new = max_new; sl.kv_pos = (int)P; sl.reported = 0; sl.rp = row; sl.prompt = (int)P;
@@ -2815,7 +2782,7 @@ int Engine::session_prefix_keep(int slot, int rows) {
     e.rows = rows;
     e.ids.assign(sl.ids.begin(), sl.ids.begin() + rows);
     e.mask.assign(sl.mask.begin(), sl.mask.begin() + rows);
-    launch_session_prefix_copy(prefix_copy_args(L, kc_, vc_, s.S, s.Lcap, page_stride_, head_stride_, slot, rows,
+    launch_session_prefix_copy(prefix_copy_args(L, kc_, vc_, s.S, rows_.Lcap, page_stride_, head_stride_, slot, rows,
                                                 (float*)e.kv.get(), 0), stream_);
     HIP_CHECK(hipStreamSynchronize(stream_));
     const int handle = s.next_handle++;
@@ -2826,7 +2793,6 @@ int Engine::session_prefix_keep(int slot, int rows) {
 int Engine::session_admit_prefix(int handle, const GenRequest& rq, const GenParams& rp) {
     Session& s = open_session();
     const LangConfig& L = cfg_.lang;
-    const int H = L.hidden, V = L.vocab;
     // every check first: a refused admission changes nothing on the device
     const auto it = s.prefix.find(handle);
     if (it == s.prefix.end()) throw std::runtime_error("EINVAL: unknown prefix handle " + std::to_string(handle));
@@ -2848,7 +2814,7 @@ int Engine::session_admit_prefix(int handle, const GenRequest& rq, const GenPara
     const RowParams row = resolve_row_params(rp);
     const int slot = s.n;
     hipStream_t st = stream_;
-    launch_session_prefix_copy(prefix_copy_args(L, kc_, vc_, s.S, s.Lcap, page_stride_, head_stride_, slot, rows,
+    launch_session_prefix_copy(prefix_copy_args(L, kc_, vc_, s.S, rows_.Lcap, page_stride_, head_stride_, slot, rows,
                                                 (float*)e.kv.get(), 1), st);
     const std::vector<GenRequest> reqs{rq};
     GenParams gp = s.per_request ? rp : s.p;
@@ -2857,14 +2823,8 @@ int Engine::session_admit_prefix(int handle, const GenRequest& rq, const GenPara
     g.prompt_len = {P};
     g.max_p = P;
     g.img.resize(1);
-    g.Lmax = s.Lcap;
-    g.SX = s.sx + (size_t)slot * H;
-    g.LOGITS = s.logits + (size_t)slot * V;
     g.extra.resize(1);
-    {
-        ScopedSet page0(kv_page0_, slot);
-        forward_rows(g, {P - rows}, {rows});  // the suffix alone, behind the copied rows
-    }
+    forward_rows(g, {P - rows}, {rows}, slot);  // the suffix alone, behind the copied rows
     const int got = session_admit_tail(s, rq, rp, row);
     ++s.prefix_admissions;
     s.prefix_rows_reused += (size_t)rows;
@@ -2892,10 +2852,10 @@ Engine::PrefixStats Engine::session_prefix_stats() const {
 void Engine::session_step_body(Session& s, bool screened) {
     DecSampleArgs sa;
     SampleArgs pen;
-    session_sample_args(s, s.n, 0, sa, pen);
-    decode_step(s.n, s.Lcap);
+    sample_args(s.n, 0, s.p, s.per_request, sa, pen);
+    decode_step(s.n, rows_.Lcap);
     if (s.logprobs) {
-        const DecLpArgs lp = session_lp_args(s, sa, 0);
+        const DecLpArgs lp = lp_args(sa, 0);
         decode_head(s.n, sa, pen, screened, &lp);
     } else {
         decode_head(s.n, sa, pen, screened);
@@ -2921,9 +2881,9 @@ std::vector<Engine::SlotStatus> Engine::session_step(int k) {
     // the capacity invariant (session_open), asserted before any launch: after this burst no slot's kv_pos may
     // pass its cache rows.  A slot retired at the burst boundary after it finished never gets here
     for (int b = 0; b < s.n; ++b) {
-        const int room = s.Lcap - s.slot[b].kv_pos;
+        const int room = rows_.Lcap - s.slot[b].kv_pos;
         if (room < 1)
-            throw std::runtime_error("EINVAL: slot " + std::to_string(b) + " has used its " + std::to_string(s.Lcap) +
+            throw std::runtime_error("EINVAL: slot " + std::to_string(b) + " has used its " + std::to_string(rows_.Lcap) +
                                      " cache rows: retire finished slots at every burst boundary");
         k = std::min(k, room);
     }
@@ -2950,9 +2910,9 @@ std::vector<Engine::SlotStatus> Engine::session_poll() {
     Session& s = open_session();
     hipStream_t st = stream_;
     const int S = s.S;
-    HIP_CHECK(hipMemcpyAsync(s.pin, s.done, S * 4, hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipMemcpyAsync(s.pin + S, s.outlen, S * 4, hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipMemcpyAsync(s.pin + 2 * S, s.err, 4, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(s.pin, rows_.done, S * 4, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(s.pin + S, rows_.out_len, S * 4, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(s.pin + 2 * S, rows_.err, 4, hipMemcpyDeviceToHost, st));
     HIP_CHECK(hipStreamSynchronize(st));
     if (s.pin[2 * S]) throw std::runtime_error("EINTERNAL: decode hand-off timed out inside a fused kernel");
     std::vector<SlotStatus> out(s.n);
@@ -2965,7 +2925,7 @@ std::vector<Engine::SlotStatus> Engine::session_poll() {
         out[b].done = (s.pin[b] != 0 || len >= (int)sl.max_new) ? 1 : 0;
         if (len > sl.reported) {
             tmp.resize(len - sl.reported);
-            HIP_CHECK(hipMemcpy(tmp.data(), s.out + (size_t)b * s.out_cap + sl.reported, tmp.size() * 4, hipMemcpyDeviceToHost));
+            HIP_CHECK(hipMemcpy(tmp.data(), rows_.out + (size_t)b * rows_.out_cap + sl.reported, tmp.size() * 4, hipMemcpyDeviceToHost));
             out[b].fresh.assign(tmp.begin(), tmp.end());
             sl.reported = len;
         }
@@ -2977,38 +2937,33 @@ std::vector<int64_t> Engine::session_retire(int slot, int* moved_from) {
     Session& s = open_session();
     if (slot < 0 || slot >= s.n) throw std::runtime_error("EINVAL: slot " + std::to_string(slot) + " is not active");
     const LangConfig& L = cfg_.lang;
+    const DecodeRows& r = rows_;
     hipStream_t st = stream_;
     HIP_CHECK(hipStreamSynchronize(st));
     int len = 0;
-    HIP_CHECK(hipMemcpy(&len, s.outlen + slot, 4, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(&len, r.out_len + slot, 4, hipMemcpyDeviceToHost));
     len = std::min(len, (int)s.slot[slot].max_new);
     std::vector<int> ids(len);
-    if (len) HIP_CHECK(hipMemcpy(ids.data(), s.out + (size_t)slot * s.out_cap, (size_t)len * 4, hipMemcpyDeviceToHost));
+    if (len) HIP_CHECK(hipMemcpy(ids.data(), r.out + (size_t)slot * r.out_cap, (size_t)len * 4, hipMemcpyDeviceToHost));
     const int last = s.n - 1;
     if (moved_from) *moved_from = -1;
     if (slot != last) {  // active pages stay dense: the last one moves into the freed slot
         SlotMoveArgs m;
-        m.kc = kc_; m.vc = vc_; m.layers = L.layers; m.slots = s.S; m.kv_heads = L.kv_heads; m.cap_rows = s.Lcap;
+        m.kc = kc_; m.vc = vc_; m.layers = L.layers; m.slots = s.S; m.kv_heads = L.kv_heads; m.cap_rows = r.Lcap;
         m.hd = L.head_dim; m.layer_stride = (long)s.S * page_stride_; m.page_stride = page_stride_;
         m.head_stride = head_stride_; m.src = last; m.dst = slot;
-        m.rows_bound = std::min(s.slot[last].kv_pos + 1, s.Lcap);
-        m.kv_len = s.kvlen; m.kv_pos = s.kvpos; m.ctx = s.ctx; m.ctx_cap = s.ctx_cap; m.ctx_len = s.ctx_len;
-        m.out = s.out; m.out_cap = s.out_cap; m.out_len = s.outlen; m.done = s.done; m.tok = s.tok;
-        m.rng = s.rng; m.rng_words = RNG_WORDS; m.ban = s.ban; m.ban_ld = s.ban_ld; m.x = s.sx; m.H = L.hidden;
-        if (s.per_request) m.rowpar = s.rowpar;
-        if (s.logprobs) {
-            DecSampleArgs sa;
-            SampleArgs pen;
-            session_sample_args(s, s.n, 0, sa, pen);
-            const DecLpArgs lp = session_lp_args(s, sa, 0);
-            m.lp = lp.lp; m.lp_top_id = lp.top_id; m.lp_top = lp.top_lp; m.lp_k = lp.K;
-        }
+        m.rows_bound = std::min(s.slot[last].kv_pos + 1, r.Lcap);
+        m.kv_len = r.kv_len; m.kv_pos = r.kv_pos; m.ctx = r.ctx; m.ctx_cap = r.ctx_cap; m.ctx_len = r.ctx_len;
+        m.out = r.out; m.out_cap = r.out_cap; m.out_len = r.out_len; m.done = r.done; m.tok = r.tok;
+        m.rng = r.rng; m.rng_words = RNG_WORDS; m.ban = r.ban; m.ban_ld = r.ban_ld; m.x = r.x; m.H = L.hidden;
+        if (s.per_request) m.rowpar = r.rowpar;
+        if (s.logprobs) { m.lp = r.lp; m.lp_top_id = r.lp_top_id; m.lp_top = r.lp_top; m.lp_k = r.lp_k; }
         launch_session_slot_move(m, st);
         s.slot[slot] = s.slot[last];
         if (moved_from) *moved_from = last;
     }
     --s.n;
-    session_sentinels(s);
+    refill_handoffs();
     HIP_CHECK(hipStreamSynchronize(st));
     return std::vector<int64_t>(ids.begin(), ids.end());
 }
@@ -3022,22 +2977,19 @@ void Engine::session_logprobs(int slot, size_t first, size_t count, int top_k, f
     if (count && (!token_lp || (top_k && (!top_id || !top_lp)))) throw std::runtime_error("EINVAL: NULL argument");
     HIP_CHECK(hipStreamSynchronize(stream_));
     int len = 0;
-    HIP_CHECK(hipMemcpy(&len, s.outlen + slot, 4, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(&len, rows_.out_len + slot, 4, hipMemcpyDeviceToHost));
     len = std::min(len, (int)s.slot[slot].max_new);
     if (first > (size_t)len || count > (size_t)len - first)
         throw std::runtime_error("EINVAL: entries [" + std::to_string(first) + ", " + std::to_string(first + count) +
                                  ") pass the slot's " + std::to_string(len) + " tokens");
     if (!count) return;
-    DecSampleArgs sa;
-    SampleArgs pen;
-    session_sample_args(s, 1, slot, sa, pen);
-    const DecLpArgs lp = session_lp_args(s, sa, slot);
-    HIP_CHECK(hipMemcpy(token_lp, lp.lp + first, count * 4, hipMemcpyDeviceToHost));
+    const size_t e0 = (size_t)slot * rows_.out_cap + first;  // the slot's first entry asked for
+    HIP_CHECK(hipMemcpy(token_lp, rows_.lp + e0, count * 4, hipMemcpyDeviceToHost));
     if (!top_k) return;
     std::vector<int> ids(count * LP_MAX_TOP);
     std::vector<float> lps(count * LP_MAX_TOP);
-    HIP_CHECK(hipMemcpy(ids.data(), lp.top_id + first * LP_MAX_TOP, ids.size() * 4, hipMemcpyDeviceToHost));
-    HIP_CHECK(hipMemcpy(lps.data(), lp.top_lp + first * LP_MAX_TOP, lps.size() * 4, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(ids.data(), rows_.lp_top_id + e0 * LP_MAX_TOP, ids.size() * 4, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(lps.data(), rows_.lp_top + e0 * LP_MAX_TOP, lps.size() * 4, hipMemcpyDeviceToHost));
     for (size_t i = 0; i < count; ++i)
         for (int k = 0; k < top_k; ++k) {
             top_id[i * top_k + k] = ids[i * LP_MAX_TOP + k];
@@ -3061,7 +3013,7 @@ bool Engine::session_info(SessionInfo* out) const {
     if (!sess_) return false;
     if (out) {
         out->slots = sess_->S; out->active = sess_->n; out->max_context = sess_->max_context;
-        out->out_cap = (int)sess_->out_cap; out->kv_cap = sess_->Lcap; out->burst_cap = Session::kBurstCap;
+        out->out_cap = (int)rows_.out_cap; out->kv_cap = rows_.Lcap; out->burst_cap = Session::kBurstCap;
         out->steps = sess_->steps;
         out->steps_screened = sess_->head_steps[1]; out->steps_exact = sess_->head_steps[0];
         out->per_request = sess_->per_request;
@@ -3122,7 +3074,7 @@ Engine::DecodeProfile Engine::profile_decode(int iters) {
     const int H = L.hidden, hd = L.head_dim, QKVN = layers_[0].qkv.N;
     hipStream_t st = stream_;
     std::vector<int> kvpos(B);
-    HIP_CHECK(hipMemcpy(kvpos.data(), wsi("s_kvpos", B), B * 4, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(kvpos.data(), rows_.kv_pos, B * 4, hipMemcpyDeviceToHost));
     // the replays re-run the last decoded position (pos - 1): its K/V slot is rewritten with the same values
     std::vector<int> pm1(B);
     long keys = 0;
@@ -3162,7 +3114,7 @@ Engine::DecodeProfile Engine::profile_decode(int iters) {
         std::vector<char> seen(E, 0);
         for (int v : ids)
             if (v >= 0 && v < E && !seen[v]) { seen[v] = 1; ++prof.experts_touched; }
-        const float* Xc = wsf("s_x", (size_t)B * H);
+        const float* Xc = rows_.x;
         // replay on a scratch copy of the residual stream so the engine state is untouched
         float* Xs = wsf("p_x", (size_t)B * H);
         HIP_CHECK(hipMemcpyAsync(Xs, Xc, (size_t)B * H * 4, hipMemcpyDeviceToDevice, st));
@@ -3213,7 +3165,7 @@ void Engine::profile_gemvs(DecodeProfile& prof, int iters, const std::vector<int
     const LangConfig& L = cfg_.lang;
     const int B = last_B_, H = L.hidden, hd = L.head_dim, QKVN = layers_[0].qkv.N;
     hipStream_t st = stream_;
-    const float* SX = wsf("s_x", (size_t)B * H);
+    const float* SX = rows_.x;
     float* LG = wsf("p_logits", (size_t)B * L.vocab);
     float* SXN = wsf("p_xn", (size_t)B * H);
     ensure_mm_weights(B);
@@ -3291,7 +3243,7 @@ void Engine::profile_gemvs(DecodeProfile& prof, int iters, const std::vector<int
 void Engine::profile_step_context(DecodeProfile& prof, int iters, int n_moe) {
     const int B = last_B_, Lmax = last_Lmax_, H = cfg_.lang.hidden, n = std::max(8, iters * 4);
     hipStream_t st = stream_;
-    float* X = wsf("s_x", (size_t)B * H);
+    float* X = rows_.x;
     float* X0 = wsf("p_x0", (size_t)B * H);
     HIP_CHECK(hipMemcpyAsync(X0, X, (size_t)B * H * 4, hipMemcpyDeviceToDevice, st));
     decode_step(B, Lmax);  // every workspace exists before capture

@@ -151,6 +151,44 @@ struct GenParams {
     float* trace = nullptr; // host [B][max_new][vocab]: raw logits of every step (parity hook)
     int lp_k = -1;          // >= 0: per-token log-probabilities with lp_k alternatives (0..LP_MAX_TOP); the exact head runs
 };
+// The device rows a decode batch runs on, one record per engine: a generate call or a session
+// reserves and initialises them (Engine::reserve_decode_rows), and every decode launch, admission, poll and profile
+// takes its pointers from here.  Row b of a per-row buffer starts b x its capacity behind the base.
+struct DecodeRows {
+    // capacities: rows, cache rows per page, ints per context / output / ban row, floats per hand-off copy
+    int S = 0, Lcap = 0;
+    long ctx_cap = 0, out_cap = 0, ban_ld = 0;
+    size_t part_floats = 0, qkv_floats = 0;
+    // per-row state (ban, rng, rowpar: nullptr when the spec did not ask for them)
+    float *x = nullptr, *logits = nullptr;
+    int *ctx = nullptr, *ctx_len = nullptr, *kv_pos = nullptr, *kv_len = nullptr, *done = nullptr, *out_len = nullptr,
+        *out = nullptr, *tok = nullptr, *ban = nullptr;
+    uint32_t* rng = nullptr;
+    RowParams* rowpar = nullptr;
+    // selection scratch (st_*: the sampler's; st_w is 2 V floats per row viewed as V doubles)
+    float* red_val = nullptr;
+    int *red_idx = nullptr, *st_idx = nullptr;
+    uint32_t* st_key = nullptr;
+    double* st_w = nullptr;
+    // step-wide words: the fused kernels' give-up flag and the arrival tickets (zero between launches)
+    int *err = nullptr, *attn_cnt = nullptr, *route_cnt = nullptr, *dn_tick = nullptr, *d_tick = nullptr;
+    // the two hand-off copies (Engine::attn_args): sentinel-filled at every step boundary
+    float *qkv[2] = {nullptr, nullptr}, *part[2] = {nullptr, nullptr};
+    // log-probability rows (lp_k >= 0): entries [S][out_cap] (x lp_k alternatives), the side logits and the partials
+    int lp_k = -1;
+    float *lp = nullptr, *lp_top = nullptr, *lp_side = nullptr, *lp_pmax = nullptr, *lp_psum = nullptr, *lp_ptv = nullptr;
+    int *lp_top_id = nullptr, *lp_rec = nullptr, *lp_pti = nullptr;
+};
+// What a caller of Engine::reserve_decode_rows asks for
+struct DecodeRowsSpec {
+    int rows = 0, Lcap = 0;
+    long ctx_cap = 0, out_cap = 0;
+    bool sampler = false, ban = false, rowpar = false;  // sampler scratch + RNG rows / ban rows / RowParams rows
+    bool handoff_max = false;  // hand-off records sized for every n in 1..rows (else for exactly `rows`)
+    bool zero_fill = false;    // the cache and the per-row state start as zeros (else the caller uploads the rows)
+    int lp_k = -1;             // >= 0: log-probability rows with lp_k alternatives
+    bool lp_side = false;      // ... and the raw logits at the context ids
+};
 typedef void (*TokenCb)(size_t, const int64_t*, void*);
 // rand_core seed_from_u64 for rand 0.8.5 StdRng, in the layout sampling.hip reads (RNG_WORDS words)
 std::vector<uint32_t> rng_state_from_u64(uint64_t seed);
@@ -282,14 +320,18 @@ class Engine {
         // host vectors are often temporaries: stage them in a per-name pinned buffer and copy
         // asynchronously (each name is uploaded at most once per generate(), which ends with a
         // stream synchronisation, so a staging buffer is never rewritten while in flight)
-        const size_t bytes = v.size() * sizeof(T);
-        T* p = (T*)ws(name, bytes + 16);
-        if (!v.empty()) {
-            void* h = pinned(name, bytes);
-            std::memcpy(h, v.data(), bytes);
-            HIP_CHECK(hipMemcpyAsync(p, h, bytes, hipMemcpyHostToDevice, stream_));
-        }
+        T* p = (T*)ws(name, v.size() * sizeof(T) + 16);
+        upload_to(p, name, v);
         return p;
+    }
+    // ... into rows reserved elsewhere (DecodeRows), staged under `name`
+    template <typename T>
+    void upload_to(T* dst, const std::string& name, const std::vector<T>& v) {
+        const size_t bytes = v.size() * sizeof(T);
+        if (v.empty()) return;
+        void* h = pinned(name, bytes);
+        std::memcpy(h, v.data(), bytes);
+        HIP_CHECK(hipMemcpyAsync(dst, h, bytes, hipMemcpyHostToDevice, stream_));
     }
     void* pinned(const std::string& name, size_t bytes);
     // ---- compute pieces
@@ -310,7 +352,15 @@ class Engine {
     void ensure_persist();
     MoeDecodeArgs moe_args(int l, int B, float* X);
     DecAttn2Args attn_args(int l, int B, int Lmax, int copy = 0);
-    static std::string handoff_ws(const char* base, int copy);
+    // the decode rows: reserved under their workspace names and initialised (tickets and flag zeroed, hand-offs
+    // sentinel-filled) by the one function that knows their sizes
+    DecodeRows rows_;
+    void reserve_decode_rows(const DecodeRowsSpec& spec);
+    void refill_handoffs();
+    // selection arguments of rows [slot0, slot0 + B): p's scalars, and per_request the rows' own RowParams records
+    void sample_args(int B, int slot0, const GenParams& p, bool per_request, DecSampleArgs& sa, SampleArgs& pen);
+    // the log-probability rows of the pages from row0 on that sa selects for
+    DecLpArgs lp_args(const DecSampleArgs& sa, int row0);
     void decode_head(int B, DecSampleArgs& sa, const SampleArgs& pen, bool screened, const DecLpArgs* lp = nullptr);
     void reserve_head_ws(int B);
     LmHeadQ8Args head_q8_args(int B);
@@ -321,7 +371,8 @@ class Engine {
     void plan_image_rows(GenState& g);
     void reset_decode_state(GenState& g);
     // past (optional, per sequence): rows [0, past[b]) are already in the cache and lens[b] counts the rows after them
-    void forward_rows(GenState& g, const std::vector<int>& lens, const std::vector<int>& past = {});
+    // row0: the decode row (and cache page) of the first sequence - a session's admission prefills into its slot
+    void forward_rows(GenState& g, const std::vector<int>& lens, const std::vector<int>& past = {}, int row0 = 0);
     void init_sampling(GenState& g);
     bool poll(GenState& g);
     void stream_tokens(GenState& g, int n);
@@ -336,11 +387,6 @@ class Engine {
     struct Session;
     std::unique_ptr<Session> sess_;
     Session& open_session();
-    void session_sample_args(const Session& s, int B, int slot0, DecSampleArgs& sa, SampleArgs& pen);
-    DecLpArgs session_lp_args(const Session& s, const DecSampleArgs& sa, int slot0);
-    // the log-probability workspaces (s_lp*) of `rows` pages, pointed at the pages from row0 on that sa selects for
-    DecLpArgs lp_args(const DecSampleArgs& sa, int rows, int row0, int K, bool side);
-    void session_sentinels(const Session& s);
     void session_step_body(Session& s, bool screened);
     bool session_head_screened(const Session& s) const;
     // profile_decode: its two timers and the sections after the MoE and attention replays
@@ -397,7 +443,6 @@ class Engine {
     // kv cache
     float* kc_ = nullptr;
     float* vc_ = nullptr;
-    size_t kv_bytes_ = 0;
     long page_stride_ = 0, head_stride_ = 0;
     // a session's cache holds kv_pages_ pages per layer whatever the batch a launch runs (0: the launch's own
     // B, as generate sizes it); its prefill writes page kv_page0_
