@@ -550,7 +550,8 @@ dsocr_status dsocr_session_info(const dsocr_engine* e, dsocr_session_desc* out) 
         out->slots = (size_t)si.slots; out->active = (size_t)si.active; out->max_context = (size_t)si.max_context;
         out->out_cap = (size_t)si.out_cap; out->kv_cap = (size_t)si.kv_cap; out->burst_cap = (size_t)si.burst_cap;
         out->steps = si.steps;
-        out->flags = (si.per_request ? DSOCR_SESSION_PER_REQUEST : 0u) | (si.logprobs ? DSOCR_SESSION_LOGPROBS : 0u);
+        out->flags = (si.per_request ? DSOCR_SESSION_PER_REQUEST : 0u) | (si.logprobs ? DSOCR_SESSION_LOGPROBS : 0u) |
+                     (si.pending ? DSOCR_SESSION_ADMIT_PENDING : 0u);
     });
 }
 
@@ -578,6 +579,48 @@ dsocr_status dsocr_session_admit_prefix(dsocr_engine* e, int handle, const dsocr
         if (!e || !req) throw std::runtime_error("EINVAL: NULL argument");
         const int s = e->impl->session_admit_prefix(handle, to_request(*req), to_params(params));
         if (slot) *slot = s;
+    });
+}
+
+// ---- chunked admission
+dsocr_status dsocr_session_admit_begin(dsocr_engine* e, const dsocr_request* req, const dsocr_decode_params* params,
+                                       size_t chunk_rows, int* ticket) {
+    return guarded([&] {
+        if (!e || !req) throw std::runtime_error("EINVAL: NULL argument");
+        const int rows = (int)std::min(chunk_rows, (size_t)INT32_MAX);
+        const int t = e->impl->session_admit_begin(to_request(*req), to_params(params), rows);
+        if (ticket) *ticket = t;
+    });
+}
+
+dsocr_status dsocr_session_admit_advance(dsocr_engine* e, int* done, int* slot) {
+    return guarded([&] {
+        if (!e || !done) throw std::runtime_error("EINVAL: NULL argument");
+        int s = -1;
+        *done = e->impl->session_admit_advance(&s) ? 1 : 0;
+        if (slot) *slot = s;
+    });
+}
+
+dsocr_status dsocr_session_admit_cancel(dsocr_engine* e) {
+    return guarded([&] {
+        if (!e) throw std::runtime_error("EINVAL: NULL argument");
+        e->impl->session_admit_cancel();
+    });
+}
+
+dsocr_status dsocr_session_admit_progress(const dsocr_engine* e, int* pending, size_t* rows_done, size_t* rows_total,
+                                          size_t* slices, int* vision_stage, size_t* chunk_attn_launches) {
+    return guarded([&] {
+        if (!e) throw std::runtime_error("EINVAL: NULL argument");
+        dsocr::Engine::SessionInfo si;
+        if (!e->impl->session_info(&si)) throw std::runtime_error("EINVAL: no decode session is open on this engine");
+        if (pending) *pending = si.pending ? 1 : 0;
+        if (rows_done) *rows_done = (size_t)si.pending_rows_done;
+        if (rows_total) *rows_total = (size_t)si.pending_rows_total;
+        if (slices) *slices = (size_t)si.pending_slices;
+        if (vision_stage) *vision_stage = si.pending_stage;
+        if (chunk_attn_launches) *chunk_attn_launches = si.chunk_attn_launches;
     });
 }
 
@@ -1217,6 +1260,64 @@ dsocr_status dsocr_k_prefill_attention_past(int B, int heads, int kv_heads, int 
             dsocr::launch_attention_past(a, nullptr);
             check_hip(hipGetLastError(), "prefill attention (past) launch");
             check_hip(hipDeviceSynchronize(), "prefill attention (past)");
+        } catch (...) {
+            for (void* p : bufs) (void)hipFree(p);
+            throw;
+        }
+        for (void* p : bufs) (void)hipFree(p);
+    });
+}
+dsocr_status dsocr_k_attention_chunk(int B, int heads, int kv_heads, int hd, int rope_dim, int use_mla, int cap,
+                                     float scale, const int* past, const int* lens, float* qkv, const float* cos,
+                                     const float* sin, float* kc, float* vc, float* o, int page0, int pages) {
+    return guarded([&] {
+        if (heads <= 0 || kv_heads <= 0 || heads % kv_heads || rope_dim < 0 || rope_dim > hd || rope_dim % 2)
+            throw std::runtime_error("EINVAL: bad head / rope configuration");
+        if (B <= 0 || !past || !lens || !qkv || !cos || !sin || !kc || !vc || !o) throw std::runtime_error("EINVAL: NULL argument");
+        if (page0 < 0 || pages < 1 || (long)page0 + B > pages) throw std::runtime_error("EINVAL: pages [page0, page0 + B) must lie in the cache");
+        for (int b = 0; b < B; ++b) {
+            if (lens[b] < 1) throw std::runtime_error("EINVAL: every sequence needs at least one new row");
+            if (past[b] < 0 || (long)past[b] + lens[b] > cap) throw std::runtime_error("EINVAL: past + new rows must fit in cap");
+        }
+        // the plan and the views of Engine::forward_rows / layer_forward_prefill for a chunk behind a past, into pages
+        // [page0, page0 + B) of a session cache (kv_page0_)
+        const long QKVN = (long)(heads + 2 * kv_heads) * hd, H = (long)heads * hd;
+        const long head_stride = (long)cap * hd, page_stride = (long)kv_heads * head_stride;
+        const std::vector<int> hl(lens, lens + B), hp(past, past + B);
+        const dsocr::PrefillPlan plan = dsocr::prefill_row_plan(hl, QKVN, H, page_stride, hp);
+        float* kc0 = kc + (long)page0 * page_stride;
+        float* vc0 = vc + (long)page0 * page_stride;
+        std::vector<void*> bufs;
+        auto upload = [&](const void* src, size_t b) {
+            void* p = nullptr;
+            check_hip(hipMalloc(&p, b ? b : 16), "hipMalloc");
+            bufs.push_back(p);
+            check_hip(hipMemcpy(p, src, b, hipMemcpyHostToDevice), "h2d");
+            return p;
+        };
+        try {
+            dsocr::RopeKvArgs r;
+            r.qkv = qkv; r.ld = QKVN; r.rows = (int)plan.T;
+            r.row_page = (const int*)upload(plan.row_page.data(), sizeof(int) * plan.row_page.size());
+            r.row_pos = (const int*)upload(plan.row_pos.data(), sizeof(int) * plan.row_pos.size());
+            r.heads = heads; r.kv_heads = kv_heads; r.hd = hd; r.rope_dim = rope_dim; r.use_mla = use_mla ? 1 : 0;
+            r.cos = cos; r.sin = sin; r.kc = kc0; r.vc = vc0; r.page_stride = page_stride; r.head_stride = head_stride;
+            dsocr::AttnPastArgs a;
+            a.q = {qkv, QKVN, hd, (const long*)upload(plan.q_off.data(), sizeof(long) * B)};
+            const long* kv_off = (const long*)upload(plan.kv_off.data(), sizeof(long) * B);
+            a.k = {kc0, hd, head_stride, kv_off};
+            a.v = {vc0, hd, head_stride, kv_off};
+            a.o = o; a.o_row_stride = H; a.o_head_stride = hd;
+            a.o_seq_off = (const long*)upload(plan.o_off.data(), sizeof(long) * B);
+            a.n_seq = B; a.past = (const int*)upload(past, sizeof(int) * B); a.n_q = (const int*)upload(lens, sizeof(int) * B);
+            a.max_q = plan.max_len; a.max_total = plan.max_total;
+            a.heads = heads; a.kv_heads = kv_heads; a.hd = hd; a.scale = scale;
+            // refused before anything is rotated or appended
+            if (!dsocr::attention_chunk_ok(a)) throw std::runtime_error("EINVAL: attention_chunk: shape outside the kernel's contract");
+            dsocr::launch_rope_kv(r, nullptr);
+            dsocr::launch_attention_chunk(a, nullptr);
+            check_hip(hipGetLastError(), "attention_chunk launch");
+            check_hip(hipDeviceSynchronize(), "attention_chunk");
         } catch (...) {
             for (void* p : bufs) (void)hipFree(p);
             throw;

@@ -194,6 +194,8 @@ struct Engine::Session {
     int next_handle = 1;
     size_t prefix_admissions = 0, prefix_rows_reused = 0;
     std::vector<Slot> slot;
+    std::shared_ptr<PendingAdmit> pending;  // a chunked admission in flight, staged in slot S - 1 (session_admit_begin)
+    int next_ticket = 1;
     HipGraphExec graph[9][2];  // the step for n active pages under the [exact, screened] head, captured on first use
     size_t head_steps[2] = {0, 0};  // steps replayed under the [exact, screened] head
     PinnedBuffer<int> pin;  // poll: [done | output length] x S, then the decode error flag
@@ -872,7 +874,14 @@ float* Engine::vision_pass(const float* imgs, int n, int Spx, const std::string&
     if (g % 2 || (g / 2) % 2) throw std::runtime_error("EINVAL: spatial dims cannot be evenly downsampled by stride 2");
     const long rows = (long)n * g * g;
     hipStream_t st = stream_;
-
+    // a sliced admission runs one stage per call (vis_stage_: 1 SAM, 2 CLIP / the OCR2 encoder's layers, 3 projector);
+    // every call asks for the same workspaces by name and size, so a stage finds what the one before it left
+    const bool s1 = vis_stage_ == 0 || vis_stage_ == 1, s2 = vis_stage_ == 0 || vis_stage_ == 2;
+    const bool s3 = vis_stage_ == 0 || vis_stage_ == 3;
+    const int g2 = g / 2, g4 = g / 4, c0 = S.out_ch[0], c1 = S.out_ch[1];
+    const int Sq = g4 * g4;
+    float* sam_out = wsf("v_samout", (size_t)n * Sq * c1);
+    if (s1) {
     // patch embed
     float* cols = wsf("v_cols", (size_t)rows * 3 * S.patch * S.patch);
     launch_patch_im2col(imgs, n, Spx, Spx, S.patch, cols, st);
@@ -965,15 +974,13 @@ float* Engine::vision_pass(const float* imgs, int n, int Spx, const std::string&
     linear(ncols, (int)rows, 9 * NC, sam_.neck2, y, NC);
     launch_layernorm(y, NC, y, NC, nullptr, (int)rows, NC, sam_.neck3.w, sam_.neck3.b, 1e-6f, st);
     // downsample (sam.rs:550-575)
-    const int g2 = g / 2, g4 = g / 4, c0 = S.out_ch[0], c1 = S.out_ch[1];
     launch_conv_im2col_nhwc(y, n, g, g, NC, 3, 3, 2, 1, ncols, st);
     float* z = wsf("v_net2", (size_t)n * g2 * g2 * c0);
     linear(ncols, n * g2 * g2, 9 * NC, sam_.net2, z, c0);
     float* ncols2 = wsf("v_ncols2", (size_t)n * g4 * g4 * 9 * c0);
     launch_conv_im2col_nhwc(z, n, g2, g2, c0, 3, 3, 2, 1, ncols2, st);
-    const int Sq = g4 * g4;
-    float* sam_out = wsf("v_samout", (size_t)n * Sq * c1);
     linear(ncols2, n * Sq, 9 * c0, sam_.net3, sam_out, c1);
+    }  // s1
     // Ocr2: the NHWC rows are already the reference's flatten(2,3).transpose(1,2) token rows (qwen2.rs:157-161)
     if (cfg_.variant == VARIANT_OCR2) return encoder_pass(sam_out, n, Sq, out);
 
@@ -981,13 +988,15 @@ float* Engine::vision_pass(const float* imgs, int n, int Spx, const std::string&
     const int T = Sq + 1, CH = CC.hidden, chd = CH / CC.heads;
     const long crow = (long)n * T;
     float* cx = wsf("c_x", (size_t)crow * CH);
+    if (s2) {
     launch_clip_embed(sam_out, clip_.cls, clip_pos(T), n, Sq, CH, cx, st);
     launch_layernorm(cx, CH, cx, CH, nullptr, (int)crow, CH, clip_.pre.w, clip_.pre.b, 1e-5f, st);
+    }
     float* cxn = wsf("c_xn", (size_t)crow * CH);
     float* cqkv = wsf("c_qkv", (size_t)crow * 3 * CH);
     float* cctx = wsf("c_ctx", (size_t)crow * CH);
     float* ch = wsf("c_h", (size_t)crow * CC.ffn);
-    for (int l = 0; l < CC.layers; ++l) {
+    for (int l = 0; s2 && l < CC.layers; ++l) {
         ClipLayer& cl = clip_.layers[l];
         launch_layernorm(cx, CH, cxn, CH, nullptr, (int)crow, CH, cl.ln1.w, cl.ln1.b, 1e-5f, st);
         linear(cxn, (int)crow, CH, cl.qkv, cqkv, 3 * CH);
@@ -1013,9 +1022,11 @@ float* Engine::vision_pass(const float* imgs, int n, int Spx, const std::string&
     }
     // concat + projector
     float* pre = wsf("p_pre", (size_t)n * Sq * (CH + c1));
-    launch_concat_clip_sam(cx, sam_out, n, Sq, CH, c1, pre, st);
     float* post = wsf(out, (size_t)n * Sq * cfg_.proj_out);
-    linear(pre, n * Sq, CH + c1, proj_, post, cfg_.proj_out);
+    if (s3) {
+        launch_concat_clip_sam(cx, sam_out, n, Sq, CH, c1, pre, st);
+        linear(pre, n * Sq, CH + c1, proj_, post, cfg_.proj_out);
+    }
     return post;
 }
 
@@ -1038,8 +1049,10 @@ float* Engine::encoder_pass(const float* sam_out, int n, int P, const std::strin
     float* ctx = wsf("q2_ctx", (size_t)rows * QW);
     float* gu = wsf("q2_gu", (size_t)rows * 2 * Q.inter);
     float* hbuf = wsf("q2_h", (size_t)rows * Q.inter);
-    launch_ocr2_build_seq(sam_out, query, n, P, D, x, st);
+    const bool s2 = vis_stage_ == 0 || vis_stage_ == 2, s3 = vis_stage_ == 0 || vis_stage_ == 3;
+    if (s2) launch_ocr2_build_seq(sam_out, query, n, P, D, x, st);
     for (const EncLayer& e : enc_.layers) {
+        if (!s2) break;
         launch_rmsnorm(x, D, xn, D, (int)rows, D, e.in_norm.w, Q.rms_eps, st);
         linear(xn, (int)rows, D, e.qkv, qkv, W3);
         launch_ocr2_rope(qkv, W3, rows, L, Q.heads + Q.kv_heads, hd, enc_.cos, enc_.sin, st);
@@ -1058,10 +1071,12 @@ float* Engine::encoder_pass(const float* sam_out, int n, int P, const std::strin
         linear(hbuf, (int)rows, Q.inter, e.down, x, D, 0, 1);
     }
     float* qx = wsf("q2_q", (size_t)n * P * D);
-    launch_ocr2_take_queries(x, n, P, D, qx, st);
-    launch_rmsnorm(qx, D, qx, D, n * P, D, enc_.norm, Q.rms_eps, st);
     float* post = wsf(out, (size_t)n * P * cfg_.proj_out);
-    linear(qx, n * P, D, proj_, post, cfg_.proj_out);
+    if (s3) {
+        launch_ocr2_take_queries(x, n, P, D, qx, st);
+        launch_rmsnorm(qx, D, qx, D, n * P, D, enc_.norm, Q.rms_eps, st);
+        linear(qx, n * P, D, proj_, post, cfg_.proj_out);
+    }
     return post;
 }
 
@@ -1144,7 +1159,7 @@ std::vector<std::vector<float>> Engine::image_embeddings(const std::vector<const
 // ============================================================================ decoder
 void Engine::layer_forward_prefill(int l, int T, int B, const int* row_page, const int* row_pos, const long* q_off,
                                    const long* kv_off, const long* o_off, const int* seq_len, int max_len, int Lmax,
-                                   const int* past, int max_total) {
+                                   const int* past, int max_total, bool chunk_attn) {
     const LangConfig& L = cfg_.lang;
     DecLayer& d = layers_[l];
     hipStream_t st = stream_;
@@ -1174,10 +1189,15 @@ void Engine::layer_forward_prefill(int l, int T, int B, const int* row_page, con
         a.n_seq = B; a.past = past; a.n_q = seq_len; a.max_q = max_len; a.max_total = max_total;
         a.heads = L.heads; a.kv_heads = L.kv_heads; a.hd = hd;
         a.scale = (float)(1.0 / std::sqrt((double)hd));
-        a.part_floats = attention_past_part_floats(B, L.heads, max_len, max_total, hd);
-        a.part = wsf("d_attn_past", a.part_floats);
         flops_acc_ += 4.0 * (double)T * max_total * hd * L.heads;  // (upper bound: every new row against every key)
-        launch_attention_past(a, st);
+        if (chunk_attn) {  // a chunk of a sliced admission: query tiles, one launch, no record workspace
+            launch_attention_chunk(a, st);
+            ++chunk_attn_launches_;
+        } else {
+            a.part_floats = attention_past_part_floats(B, L.heads, max_len, max_total, hd);
+            a.part = wsf("d_attn_past", a.part_floats);
+            launch_attention_past(a, st);
+        }
     } else {
         AttnArgs a;
         a.q = {QKV, QKVN, hd, q_off};
@@ -2007,6 +2027,7 @@ void Engine::embed_pages(GenState& g) {
     // HBM-resident pages (dsocr_page_to_device / dsocr_prepare_page_device), host uploads otherwise
     auto gather = [&](const std::vector<int>& pages, bool tiles, size_t n_floats) -> float* {
         float* d = wsf("g_img" + std::to_string(pass_id++), n_floats);
+        if (vis_stage_ > 1) return d;  // (a later stage of a sliced admission: the SAM slice gathered the pixels)
         size_t off = 0;
         bool host_copy = false;
         for (int b : pages) {
@@ -2162,7 +2183,8 @@ void Engine::reset_decode_state(GenState& g) {
 // last row of each page (the reference projects every position, transformer/model.rs:243-270;
 // only the last row is ever read).  The prefill runs it once on the prompts; use_cache = false
 // (generate_without_cache, model/mod.rs:2051-2283) re-runs it on prompt + generated (g.extra) every step.
-void Engine::forward_rows(GenState& g, const std::vector<int>& lens, const std::vector<int>& past, int row0) {
+void Engine::forward_rows(GenState& g, const std::vector<int>& lens, const std::vector<int>& past, int row0, bool head,
+                          bool chunk_attn) {
     const LangConfig& L = cfg_.lang;
     const int B = g.B, H = L.hidden, QKVN = layers_[0].qkv.N;
     hipStream_t st = stream_;
@@ -2177,8 +2199,11 @@ void Engine::forward_rows(GenState& g, const std::vector<int>& lens, const std::
     for (int b = 0; b < B; ++b) {
         const GenRequest& rq = g.reqs[b];
         const int plen = g.prompt_len[b];
+        // the image rows before the first row of this call (behind a prefix entry there are none from past[b] on:
+        // session_admit_prefix checks it, and g.img is empty; a chunk of a sliced admission starts among them)
         size_t j = 0;
-        // (behind a past the rows are prompt positions past[b] .., all of them text: session_admit_prefix checks it)
+        if (!past.empty() && !rq.mask.empty() && !g.img[b].empty())
+            for (int i = 0; i < past[b] && i < plen; ++i) j += rq.mask[i] ? 1 : 0;
         for (int i = past.empty() ? 0 : past[b], end = i + lens[b]; i < end; ++i) {
             const long r = r0 + i - (past.empty() ? 0 : past[b]);
             if (i < plen && !rq.mask.empty() && rq.mask[i]) {
@@ -2208,7 +2233,8 @@ void Engine::forward_rows(GenState& g, const std::vector<int>& lens, const std::
     const int* d_past = behind ? upload("g_past", past) : nullptr;
     for (int l = 0; l < L.layers; ++l)
         layer_forward_prefill(l, (int)Tn, B, d_row_page, d_row_pos, d_q_off, d_kv_off, d_o_off, d_plen, maxl, rows_.Lcap,
-                              d_past, plan.max_total);
+                              d_past, plan.max_total, chunk_attn);
+    if (!head) return;  // (a chunk before the prompt's last: nobody reads its last row's logits)
     std::vector<int> last_rows(B), lr_kind(B, ROW_HOST);
     r0 = 0;
     for (int b = 0; b < B; ++b) { r0 += lens[b]; last_rows[b] = (int)(r0 - 1); }
@@ -2658,6 +2684,7 @@ void Engine::session_admit_checks(const Session& s, const GenRequest& rq, const 
             throw std::runtime_error("EINVAL: this session's parameters are fixed (only max_new_tokens and the seed vary "
                                      "per request): open it with DSOCR_SESSION_PER_REQUEST");
     }
+    if (s.pending) throw std::runtime_error("EINVAL: a chunked admission is pending (advance it to the end or cancel it)");
     if (s.n >= s.S) throw std::runtime_error("EINVAL: every session slot is in use (retire one first)");
     const size_t P = rq.ids.size();
     if (P == 0) throw std::runtime_error("EINVAL: empty prompt");
@@ -2707,11 +2734,12 @@ int Engine::session_admit(const GenRequest& rq, const GenParams& rp) {
 
 // the slot's rows in one launch from one staged buffer (the selection kernel advances the KV position, so it starts
 // one behind: init_sampling), then the first selection on the logits the prefill left in the slot's s_logits row
-int Engine::session_admit_tail(Session& s, const GenRequest& rq, const GenParams& rp, const RowParams& row) {
+int Engine::session_admit_tail(Session& s, const GenRequest& rq, const GenParams& rp, const RowParams& row, int at,
+                               bool finish) {
     const size_t max_new = rp.max_new, P = rq.ids.size();
     const bool seed_set = rp.seed_set;
     uint64_t seed = rp.seed;
-    const int slot = s.n;
+    const int slot = at < 0 ? s.n : at;
     hipStream_t st = stream_;
     const size_t stage_ints = (size_t)SS_HEAD + RNG_WORDS + P;
     int* h = (int*)pinned("ss_stage", stage_ints * 4);
@@ -2747,13 +2775,15 @@ int Engine::session_admit_tail(Session& s, const GenRequest& rq, const GenParams
     launch_rep_penalty(pen, st);
     launch_dec_sample(sa, st);  // the first token, its embedding into the slot's s_x row, the ban list
     if (s.logprobs) launch_dec_lp_final(lp, st);  // entry 0 of the slot
-    refill_handoffs();
-    HIP_CHECK(hipStreamSynchronize(st));
+    if (finish) {  // (else the caller has a launch to add before the one refill and synchronisation)
+        refill_handoffs();
+        HIP_CHECK(hipStreamSynchronize(st));
+    }
     Session::Slot& sl = s.slot[slot];
     sl.max_new = max_new; sl.kv_pos = (int)P; sl.reported = 0; sl.rp = row; sl.prompt = (int)P;
     sl.ids = rq.ids;
     sl.mask = rq.mask.empty() ? std::vector<uint8_t>(P, 0) : rq.mask;
-    ++s.n;
+    if (at < 0) ++s.n;
     return slot;
 }
 
@@ -2829,6 +2859,116 @@ int Engine::session_admit_prefix(int handle, const GenRequest& rq, const GenPara
     ++s.prefix_admissions;
     s.prefix_rows_reused += (size_t)rows;
     return got;
+}
+
+// ---- chunked admission: session_admit's phases as slices, one per call, so that bursts of the running slots fit
+// between them.  The page is staged in slot S - 1: active slots stay dense in [0, n) with n <= S - 1 while an
+// admission is pending (no other admission can raise n), so no step, retire or compaction touches the staging
+// slot's cache rows, and its per-slot rows are written only by the last slice.  When the last chunk's tail has made
+// the first selection there, the page moves to slot n (launch_session_slot_move) unless n == S - 1.  Everything a
+// slice leaves behind for the next lives in the staging slot's cache rows and in g_visrows, which only admissions
+// write; cancelling therefore only forgets the host state.
+struct Engine::PendingAdmit {
+    std::vector<GenRequest> reqs;    // the request (ids, mask; image rows re-pointed at `rows`), what `g` refers to
+    std::vector<float> rows;         // caller-supplied image rows, copied at begin
+    GenParams gp, rp;
+    RowParams row;
+    std::unique_ptr<GenState> g;
+    int chunk = 0, done = 0, total = 0, slices = 0, ticket = 0;
+    bool vision = false;             // vision slices are still to run
+    bool split = false;              // ... one per stage (vstage = the next: 1 SAM, 2 CLIP / encoder, 3 projector)
+    int vstage = 1;
+    bool planned = false;            // plan_image_rows has run
+};
+
+int Engine::session_admit_begin(const GenRequest& rq, const GenParams& rp, int chunk_rows) {
+    Session& s = open_session();
+    // every check first; nothing is launched here
+    session_admit_checks(s, rq, rp, false);  // (a pending admission and a full session among them)
+    if (chunk_rows < 32) throw std::runtime_error("EINVAL: a prefill chunk has at least 32 rows");
+    auto pa = std::make_shared<PendingAdmit>();
+    pa->reqs.push_back(rq);
+    if (!rq.page && rq.image_rows) {
+        pa->rows.assign(rq.image_rows, rq.image_rows + rq.n_image_rows * (size_t)cfg_.lang.hidden);
+        pa->reqs[0].image_rows = pa->rows.data();
+    }
+    pa->rp = rp;
+    pa->row = resolve_row_params(rp);
+    pa->gp = s.per_request ? rp : s.p;
+    pa->gp.max_new = rp.max_new;
+    pa->g = std::make_unique<GenState>(pa->reqs, pa->gp, nullptr, nullptr);
+    pa->g->extra.resize(1);
+    pa->chunk = chunk_rows;
+    pa->total = (int)rq.ids.size();
+    pa->vision = rq.page != nullptr;
+    // The stages can run one per call when every vision pass keeps its own workspaces between calls: one pass (no
+    // tiles), or two on the two vision streams (the second under the vs1_ prefix).  With DSOCR_VIS_STREAMS=0 both
+    // passes of a tiled page share the v_* / c_* workspaces, and vision stays one slice.
+    pa->split = pa->vision && (rq.page->n_tiles == 0 || vis_streams_on());
+    pa->ticket = s.next_ticket++;
+    s.pending = std::move(pa);
+    return s.pending->ticket;
+}
+
+bool Engine::session_admit_advance(int* slot_out) {
+    Session& s = open_session();
+    if (!s.pending) throw std::runtime_error("EINVAL: no chunked admission is pending");
+    PendingAdmit& pa = *s.pending;
+    GenState& g = *pa.g;
+    const int stage = s.S - 1;
+    hipStream_t st = stream_;
+    try {
+        if (pa.vision) {  // SAM, then CLIP / the OCR2 encoder, then projector + plan_image_rows (or all in one)
+            {
+                ScopedSet stage(vis_stage_, pa.split ? pa.vstage : 0);
+                embed_pages(g);
+            }
+            if (!pa.split || pa.vstage == 3) {
+                plan_image_rows(g);
+                pa.planned = true;
+                pa.vision = false;
+            }
+            ++pa.vstage;
+            HIP_CHECK(hipStreamSynchronize(st));
+            ++pa.slices;
+            return false;
+        }
+        if (!pa.planned) {  // no page: host work only (the prompt length, the caller's image rows), and g_visrows
+            embed_pages(g);
+            plan_image_rows(g);
+            pa.planned = true;
+        }
+        const int len = std::min(pa.chunk, pa.total - pa.done);
+        const bool last = pa.done + len == pa.total;
+        // the first chunk is the plain causal prefill of its rows; the others attend behind the rows already appended
+        if (pa.done == 0) forward_rows(g, {len}, {}, stage, last, true);
+        else forward_rows(g, {len}, {pa.done}, stage, last, true);
+        pa.done += len;
+        ++pa.slices;
+        if (!last) {
+            HIP_CHECK(hipStreamSynchronize(st));
+            return false;
+        }
+        session_admit_tail(s, pa.reqs[0], pa.rp, pa.row, stage, false);
+        const int slot = s.n;
+        if (slot != stage) session_slot_move(s, stage, slot, std::min(pa.total + 1, rows_.Lcap));
+        refill_handoffs();
+        HIP_CHECK(hipStreamSynchronize(st));
+        ++s.n;
+        s.pending.reset();
+        if (slot_out) *slot_out = slot;
+        return true;
+    } catch (...) {
+        s.pending.reset();  // a failed slice ends the admission; the running slots are as they were
+        throw;
+    }
+}
+
+void Engine::session_admit_cancel() {
+    Session& s = open_session();
+    if (!s.pending) throw std::runtime_error("EINVAL: no chunked admission is pending");
+    HIP_CHECK(hipStreamSynchronize(stream_));
+    s.pending.reset();
 }
 
 void Engine::session_prefix_drop(int handle) {
@@ -2948,24 +3088,31 @@ std::vector<int64_t> Engine::session_retire(int slot, int* moved_from) {
     const int last = s.n - 1;
     if (moved_from) *moved_from = -1;
     if (slot != last) {  // active pages stay dense: the last one moves into the freed slot
-        SlotMoveArgs m;
-        m.kc = kc_; m.vc = vc_; m.layers = L.layers; m.slots = s.S; m.kv_heads = L.kv_heads; m.cap_rows = r.Lcap;
-        m.hd = L.head_dim; m.layer_stride = (long)s.S * page_stride_; m.page_stride = page_stride_;
-        m.head_stride = head_stride_; m.src = last; m.dst = slot;
-        m.rows_bound = std::min(s.slot[last].kv_pos + 1, r.Lcap);
-        m.kv_len = r.kv_len; m.kv_pos = r.kv_pos; m.ctx = r.ctx; m.ctx_cap = r.ctx_cap; m.ctx_len = r.ctx_len;
-        m.out = r.out; m.out_cap = r.out_cap; m.out_len = r.out_len; m.done = r.done; m.tok = r.tok;
-        m.rng = r.rng; m.rng_words = RNG_WORDS; m.ban = r.ban; m.ban_ld = r.ban_ld; m.x = r.x; m.H = L.hidden;
-        if (s.per_request) m.rowpar = r.rowpar;
-        if (s.logprobs) { m.lp = r.lp; m.lp_top_id = r.lp_top_id; m.lp_top = r.lp_top; m.lp_k = r.lp_k; }
-        launch_session_slot_move(m, st);
-        s.slot[slot] = s.slot[last];
+        session_slot_move(s, last, slot, std::min(s.slot[last].kv_pos + 1, r.Lcap));
         if (moved_from) *moved_from = last;
     }
     --s.n;
     refill_handoffs();
     HIP_CHECK(hipStreamSynchronize(st));
     return std::vector<int64_t>(ids.begin(), ids.end());
+}
+
+// the page of slot `src` (cache rows [0, rows_bound) and every per-slot row) into slot `dst`, one launch
+void Engine::session_slot_move(Session& s, int src, int dst, int rows_bound) {
+    const LangConfig& L = cfg_.lang;
+    const DecodeRows& r = rows_;
+    SlotMoveArgs m;
+    m.kc = kc_; m.vc = vc_; m.layers = L.layers; m.slots = s.S; m.kv_heads = L.kv_heads; m.cap_rows = r.Lcap;
+    m.hd = L.head_dim; m.layer_stride = (long)s.S * page_stride_; m.page_stride = page_stride_;
+    m.head_stride = head_stride_; m.src = src; m.dst = dst;
+    m.rows_bound = rows_bound;
+    m.kv_len = r.kv_len; m.kv_pos = r.kv_pos; m.ctx = r.ctx; m.ctx_cap = r.ctx_cap; m.ctx_len = r.ctx_len;
+    m.out = r.out; m.out_cap = r.out_cap; m.out_len = r.out_len; m.done = r.done; m.tok = r.tok;
+    m.rng = r.rng; m.rng_words = RNG_WORDS; m.ban = r.ban; m.ban_ld = r.ban_ld; m.x = r.x; m.H = L.hidden;
+    if (s.per_request) m.rowpar = r.rowpar;
+    if (s.logprobs) { m.lp = r.lp; m.lp_top_id = r.lp_top_id; m.lp_top = r.lp_top; m.lp_k = r.lp_k; }
+    launch_session_slot_move(m, stream_);
+    s.slot[dst] = s.slot[src];
 }
 
 void Engine::session_logprobs(int slot, size_t first, size_t count, int top_k, float* token_lp, int64_t* top_id,
@@ -3018,6 +3165,12 @@ bool Engine::session_info(SessionInfo* out) const {
         out->steps_screened = sess_->head_steps[1]; out->steps_exact = sess_->head_steps[0];
         out->per_request = sess_->per_request;
         out->logprobs = sess_->logprobs;
+        out->chunk_attn_launches = chunk_attn_launches_;
+        if (const PendingAdmit* pa = sess_->pending.get()) {
+            out->pending = true;
+            out->pending_stage = pa->vision ? (pa->split ? pa->vstage : 1) : 0;
+            out->pending_rows_done = pa->done; out->pending_rows_total = pa->total; out->pending_slices = pa->slices;
+        }
     }
     return true;
 }

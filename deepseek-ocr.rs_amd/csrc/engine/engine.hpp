@@ -272,6 +272,11 @@ class Engine {
         size_t steps_screened = 0, steps_exact = 0;  // ... under the screened / the exact lm_head + selection
         bool per_request = false;
         bool logprobs = false;
+        // a chunked admission in flight (session_admit_begin): prompt rows prefilled so far / in all, slices run
+        bool pending = false;
+        int pending_rows_done = 0, pending_rows_total = 0, pending_slices = 0;
+        int pending_stage = 0;           // the vision stage the next slice runs (1 SAM, 2 CLIP / encoder, 3 projector), 0: none
+        size_t chunk_attn_launches = 0;  // launch_attention_chunk launches of this engine so far
     };
     struct SlotStatus {
         int slot = 0, done = 0, out_len = 0;
@@ -306,6 +311,14 @@ class Engine {
     int session_admit_prefix(int handle, const GenRequest& rq, const GenParams& p);
     void session_prefix_drop(int handle);
     PrefixStats session_prefix_stats() const;
+    // ---- chunked admission: session_admit in slices, so that session_step can run between them.
+    // begin: every check of session_admit, no device work; the page is staged in the session's last slot.
+    // advance: one slice (vision, then the prefill in chunks of chunk_rows prompt rows, the last one with the
+    // admission's tail), synchronised; true with *slot set when the page is active.  cancel drops it.
+    // rq.page must stay alive until the admission completes or is cancelled; rq.image_rows are copied at begin.
+    int session_admit_begin(const GenRequest& rq, const GenParams& p, int chunk_rows);
+    bool session_admit_advance(int* slot);
+    void session_admit_cancel();
 
   private:
     // ---- loading
@@ -372,7 +385,10 @@ class Engine {
     void reset_decode_state(GenState& g);
     // past (optional, per sequence): rows [0, past[b]) are already in the cache and lens[b] counts the rows after them
     // row0: the decode row (and cache page) of the first sequence - a session's admission prefills into its slot
-    void forward_rows(GenState& g, const std::vector<int>& lens, const std::vector<int>& past = {}, int row0 = 0);
+    // head: the final norm + lm_head on every sequence's last row (a chunk that is not the prompt's last needs none)
+    // chunk_attn: rows behind a past attend through launch_attention_chunk (query tiles), not launch_attention_past
+    void forward_rows(GenState& g, const std::vector<int>& lens, const std::vector<int>& past = {}, int row0 = 0,
+                      bool head = true, bool chunk_attn = false);
     void init_sampling(GenState& g);
     bool poll(GenState& g);
     void stream_tokens(GenState& g, int n);
@@ -396,11 +412,15 @@ class Engine {
     void profile_step_context(DecodeProfile& prof, int iters, int n_moe);
     void layer_forward_prefill(int l, int T, int B, const int* row_page, const int* row_pos, const long* q_off,
                                const long* kv_off, const long* o_off, const int* seq_len, int max_len, int Lmax,
-                               const int* past = nullptr, int max_total = 0);
+                               const int* past = nullptr, int max_total = 0, bool chunk_attn = false);
     // what both admissions check about the request's parameters, the free slot and the context it needs
     void session_admit_checks(const Session& s, const GenRequest& rq, const GenParams& rp, bool behind_prefix) const;
     // the tail both admissions share: the slot's rows from one staged buffer, then the first selection
-    int session_admit_tail(Session& s, const GenRequest& rq, const GenParams& rp, const RowParams& row);
+    // (slot: where the page's rows are; -1 = the first free slot, s.n.  The caller makes it active)
+    int session_admit_tail(Session& s, const GenRequest& rq, const GenParams& rp, const RowParams& row, int slot = -1,
+                           bool finish = true);
+    struct PendingAdmit;
+    void session_slot_move(Session& s, int src, int dst, int rows_bound);
 
     ModelConfig cfg_;
     int device_ = 0;
@@ -450,6 +470,8 @@ class Engine {
     long layer_kv(int B) const { return (long)(kv_pages_ ? kv_pages_ : B) * page_stride_; }
     std::set<std::string> ws_frozen_;  // workspaces the session's captured graphs hold: growing one is EINTERNAL
     Timings timings_;
+    int vis_stage_ = 0;  // vision_pass / encoder_pass: 0 every stage (the default), 1..3 that stage alone
+    size_t chunk_attn_launches_ = 0;
     double flops_acc_ = 0;  // FLOPs issued by linear() / attention since the last stage mark
     std::vector<int> prefill_lens_;  // rows per page of the prefill being issued
     int last_B_ = 0;

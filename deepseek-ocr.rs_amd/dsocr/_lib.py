@@ -103,6 +103,7 @@ class ScreenStepsC(C.Structure):
 
 SESSION_PER_REQUEST = 1  # DSOCR_SESSION_PER_REQUEST
 SESSION_LOGPROBS = 2     # DSOCR_SESSION_LOGPROBS
+SESSION_ADMIT_PENDING = 0x100  # DSOCR_SESSION_ADMIT_PENDING (dsocr_session_info flags while an admission is pending)
 MAX_TOP_LOGPROBS = 20    # DSOCR_MAX_TOP_LOGPROBS
 
 
@@ -142,6 +143,8 @@ EXPORTS = [
     "dsocr_k_prefill_attention_past", "dsocr_k_session_prefix_copy",
     "dsocr_k_qkv_attention_layers",
     "dsocr_k_lmhead_screen_steps", "dsocr_k_lmhead_screen_grid",
+    "dsocr_session_admit_begin", "dsocr_session_admit_advance", "dsocr_session_admit_cancel",
+    "dsocr_session_admit_progress", "dsocr_k_attention_chunk",
 ]
 
 # model variants behind the deepseek engine (dsocr_engine_variant)
@@ -271,6 +274,13 @@ def lib():
     L.dsocr_session_prefix_stats.argtypes = [vp, C.POINTER(sz), C.POINTER(sz), C.POINTER(sz), C.POINTER(sz)]
     L.dsocr_k_prefill_attention_past.argtypes = [i32, i32, i32, i32, i32, i32, i32, f32, C.POINTER(i32), C.POINTER(i32),
                                                  vp, vp, vp, vp, vp, vp]
+    L.dsocr_session_admit_begin.argtypes = [vp, C.POINTER(RequestC), C.POINTER(DecodeParamsC), sz, C.POINTER(i32)]
+    L.dsocr_session_admit_advance.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]
+    L.dsocr_session_admit_cancel.argtypes = [vp]
+    L.dsocr_session_admit_progress.argtypes = [vp, C.POINTER(i32), C.POINTER(sz), C.POINTER(sz), C.POINTER(sz),
+                                               C.POINTER(i32), C.POINTER(sz)]
+    L.dsocr_k_attention_chunk.argtypes = [i32, i32, i32, i32, i32, i32, i32, f32, C.POINTER(i32), C.POINTER(i32),
+                                          vp, vp, vp, vp, vp, vp, i32, i32]
     L.dsocr_k_session_prefix_copy.argtypes = [i32, i32, i32, i32, i32, vp, vp, i32, i32, vp, i32]
     L.dsocr_k_logprobs.argtypes = [i32, i32, i32, vp, i32, vp, vp, vp, vp, vp]
     L.dsocr_k_logprobs_penalty.argtypes = [i32, i32, i32, vp, i32, vp, vp, vp, i32, vp, f32, vp, vp, vp]

@@ -101,6 +101,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--per-request-params", action="store_true",
                    help="with --slots: open the session per request, every page admitted with its own decode "
                         "parameters (device-side per-row selection); off by default")
+    p.add_argument("--admit-chunk", type=int, default=0, metavar="ROWS",
+                   help="with --slots: admit every page in slices (its vision, then ROWS >= 32 prompt rows at a time) "
+                        "with a burst of the running pages between two slices; 0 = off (the default)")
     return p
 
 
@@ -183,11 +186,19 @@ def _event(stage: str, ms: float, **fields) -> dict:
             "fields": [{"key": k, "value": v} for k, v in fields.items()]}
 
 
+def check_admit_chunk(args) -> None:
+    """--admit-chunk is a setting of the decode session: refused without --slots and below 32 rows, before any load."""
+    rows = int(getattr(args, "admit_chunk", 0) or 0)
+    if rows and (not getattr(args, "slots", 0) or rows < 32):
+        raise DsocrError(1, "--admit-chunk needs --slots and ROWS >= 32 (a chunked admission runs in a decode session)")
+
+
 def run_inference(args, out=sys.stdout, err=sys.stderr) -> int:
     def info(msg):
         if not args.quiet:
             print(msg, file=err, flush=True)
 
+    check_admit_chunk(args)
     prompt_raw = load_prompt(args)
     if args.model in PADDLE_IDS:
         return run_paddle(args, prompt_raw, out, err)
@@ -301,7 +312,8 @@ def run_documents(args, engine, tokenizer, prompt: str, out, info) -> int:
     start = time.perf_counter()
     per_request = bool(getattr(args, "per_request_params", False))
     with BatchScheduler(engine, tokenizer, args.slots, args.max_context, decode_params(args),
-                        vision_settings(args), per_request_params=per_request) as sched:
+                        vision_settings(args), per_request_params=per_request,
+                        admit_chunk=int(getattr(args, "admit_chunk", 0) or 0)) as sched:
         futures = [sched.submit(prompt, [im], params=decode_params(args) if per_request else None) for im in images]
         outcomes = [f.result() for f in futures]
     elapsed = time.perf_counter() - start

@@ -458,6 +458,7 @@ class Session:
         else:
             check(lib().dsocr_session_open(engine._h, int(slots), int(max_context), C.byref(pc)))
         self._e = engine
+        self._pending_page = None
         self.params = params
         self.per_request = bool(per_request)
         self._eos, self._ignore_eos = engine.eos_token_id, bool(ignore_eos)
@@ -483,11 +484,7 @@ class Session:
         nothing on the device: a session opened with ``logprobs`` keeps 20 alternatives for every slot whatever is
         passed here, and ``Session.logprobs(..., top_k)`` decides how many are read.  Passing it states that the
         page's entries will be read, and is an error (EINVAL) on a session opened without ``logprobs``."""
-        if logprobs is not None:
-            if not self.has_logprobs:
-                raise DsocrError(1, "this session was opened without logprobs")
-            if not 0 <= int(logprobs) <= MAX_TOP_LOGPROBS:
-                raise DsocrError(1, f"logprobs must be 0..{MAX_TOP_LOGPROBS}")
+        self._check_logprobs(logprobs)
         keep = []
         req = self._e._request(ids, mask, page, image_rows, keep)
         slot = C.c_int(-1)
@@ -500,6 +497,73 @@ class Session:
                                         self.out_cap if max_new_tokens is None else int(max_new_tokens),
                                         0 if seed is None else 1, seed or 0, C.byref(slot)))
         return slot.value
+
+    def _check_logprobs(self, logprobs) -> None:
+        """The `logprobs` keyword of every admission: a check only (see ``admit``)."""
+        if logprobs is not None:
+            if not self.has_logprobs:
+                raise DsocrError(1, "this session was opened without logprobs")
+            if not 0 <= int(logprobs) <= MAX_TOP_LOGPROBS:
+                raise DsocrError(1, f"logprobs must be 0..{MAX_TOP_LOGPROBS}")
+
+    def _request_params(self, params, max_new_tokens, seed, eos_token_id, ignore_eos):
+        """A request's whole parameter record: `params`, or the session's with this max_new_tokens / seed."""
+        if params is None:
+            params = DecodeParameters(**{**self.params.__dict__,
+                                         "max_new_tokens": self.out_cap if max_new_tokens is None else int(max_new_tokens),
+                                         "seed": seed})
+        return _params_c(params, self._eos if eos_token_id is None else int(eos_token_id),
+                         self._ignore_eos if ignore_eos is None else bool(ignore_eos))
+
+    # ------------------------------------------------------------------ chunked admission
+    def admit_begin(self, ids, mask=None, page: Optional[Page] = None, image_rows=None, chunk_rows: int = 128,
+                    max_new_tokens: Optional[int] = None, seed: Optional[int] = None,
+                    params: Optional[DecodeParameters] = None, eos_token_id: Optional[int] = None,
+                    ignore_eos: Optional[bool] = None, logprobs: Optional[int] = None) -> int:
+        """``admit`` in slices (dsocr_session_admit_begin): every check runs here and nothing is launched; the work
+        is done by ``admit_advance``, one slice per call (the page's vision, then the prompt in chunks of
+        ``chunk_rows`` >= 32 rows), with ``step`` / ``retire`` legal in between.  Returns the admission's ticket.
+        The keywords are ``admit``'s.  One admission may be pending; ``admit`` / ``admit_prefix`` are refused while
+        it is."""
+        self._check_logprobs(logprobs)
+        keep = []
+        req = self._e._request(ids, mask, page, image_rows, keep)
+        pc = self._request_params(params, max_new_tokens, seed, eos_token_id, ignore_eos)
+        ticket = C.c_int(-1)
+        check(lib().dsocr_session_admit_begin(self._e._h, C.byref(req), C.byref(pc), max(int(chunk_rows), 0),
+                                              C.byref(ticket)))
+        self._pending_page = page  # the engine reads the page's pixels in the vision slice
+        return ticket.value
+
+    def admit_advance(self):
+        """One slice of the pending admission, synchronised (dsocr_session_admit_advance): (done, slot), slot = -1
+        until the last chunk has made the page active."""
+        done, slot = C.c_int(0), C.c_int(-1)
+        try:
+            check(lib().dsocr_session_admit_advance(self._e._h, C.byref(done), C.byref(slot)))
+        except DsocrError:
+            if not self.admit_progress()["pending"]:
+                self._pending_page = None
+            raise
+        if done.value:
+            self._pending_page = None
+        return bool(done.value), slot.value
+
+    def admit_cancel(self) -> None:
+        """Drops the pending admission (dsocr_session_admit_cancel); the running slots and later admissions see
+        nothing of it."""
+        check(lib().dsocr_session_admit_cancel(self._e._h))
+        self._pending_page = None
+
+    def admit_progress(self) -> dict:
+        """{"pending", "rows_done", "rows_total", "slices", "vision_stage"} of the pending admission (all zero without
+        one; vision_stage: the stage the next slice runs, 1 SAM, 2 CLIP / encoder, 3 projector, 0 none left) and
+        "chunk_attn_launches", the engine's launch_attention_chunk launches so far."""
+        p, st, v = C.c_int(0), C.c_int(0), [C.c_size_t() for _ in range(4)]
+        check(lib().dsocr_session_admit_progress(self._e._h, C.byref(p), C.byref(v[0]), C.byref(v[1]), C.byref(v[2]),
+                                                 C.byref(st), C.byref(v[3])))
+        return {"pending": bool(p.value), "rows_done": int(v[0].value), "rows_total": int(v[1].value),
+                "slices": int(v[2].value), "vision_stage": int(st.value), "chunk_attn_launches": int(v[3].value)}
 
     # ------------------------------------------------------------------ page prefix cache
     def keep_prefix(self, slot: int, rows: int) -> int:
@@ -517,19 +581,10 @@ class Session:
         are the whole prompt's, no page and no image rows; vision and the prefill of the entry's rows are skipped.
         The keywords are ``admit``'s (without ``params``: the session's parameters with this ``max_new_tokens`` /
         ``seed``)."""
-        if logprobs is not None:
-            if not self.has_logprobs:
-                raise DsocrError(1, "this session was opened without logprobs")
-            if not 0 <= int(logprobs) <= MAX_TOP_LOGPROBS:
-                raise DsocrError(1, f"logprobs must be 0..{MAX_TOP_LOGPROBS}")
+        self._check_logprobs(logprobs)
         keep = []
         req = self._e._request(ids, mask, None, None, keep)
-        if params is None:
-            params = DecodeParameters(**{**self.params.__dict__,
-                                         "max_new_tokens": self.out_cap if max_new_tokens is None else int(max_new_tokens),
-                                         "seed": seed})
-        pc = _params_c(params, self._eos if eos_token_id is None else int(eos_token_id),
-                       self._ignore_eos if ignore_eos is None else bool(ignore_eos))
+        pc = self._request_params(params, max_new_tokens, seed, eos_token_id, ignore_eos)
         slot = C.c_int(-1)
         check(lib().dsocr_session_admit_prefix(self._e._h, int(handle), C.byref(req), C.byref(pc), C.byref(slot)))
         return slot.value

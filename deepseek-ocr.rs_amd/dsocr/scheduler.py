@@ -25,6 +25,15 @@ submitted, the vision settings, the prefix ids); a later request with the same k
 dropped before the next keep.  Prompts with several images, exclusive requests and prompts with no text after the
 image bypass the cache.  ``prefix_hits`` / ``prefix_misses`` count the lookups.
 
+Chunked admission: ``BatchScheduler(..., admit_chunk=ROWS)`` (default 0: nothing changes; ROWS >= 32) admits a waiting
+request in slices (``Session.admit_begin`` / ``admit_advance``: the page's vision, then the prompt ``ROWS`` rows at a
+time) and alternates one slice with one burst of the running slots, so a running stream waits for a slice, not for a
+whole admission.  Bursts stay 1 step while any request streams, else 8; with no slot running the slices run back to
+back.  One admission is pending at a time and nothing behind it overtakes it.  Exclusive requests stay exclusive, a
+prefix-cache hit is still admitted through ``admit_prefix`` in one call, and the prefix of a page admitted in slices
+is kept when its last slice completes.  ``admit_slices`` counts the slices and ``events`` lists ``("slice", kind,
+pages active after it)`` and ``("burst", active, steps)`` in the order they ran.
+
 The engine object needs ``open_session(slots, max_context, params)`` (admit / step / poll / retire / close, see
 ``dsocr.engine.Session``), ``decode`` and, for prompts with several images, ``image_embeddings``; tests drive the
 scheduler with a scripted fake.
@@ -118,9 +127,16 @@ class BatchScheduler:
     def __init__(self, engine, tokenizer, slots: int, max_context: int,
                  defaults: DecodeParameters = DecodeParameters(), vision: Optional[VisionSettings] = None,
                  prepare: Optional[Callable] = None, per_request_params: bool = False, logprobs: bool = False,
-                 prefix_cache: int = 0):
+                 prefix_cache: int = 0, admit_chunk: int = 0):
         if not 1 <= int(slots) <= 8:
             raise ValueError("a session has 1..8 slots")
+        if int(admit_chunk) != 0 and int(admit_chunk) < 32:
+            raise ValueError("admit_chunk is 0 (off) or at least 32 prompt rows")
+        self.admit_chunk = int(admit_chunk)
+        self._pending = None           # the request whose admission is running in slices
+        self.admit_slices = 0          # slices run (vision and prefill chunks)
+        self.chunked_admissions = 0    # admissions completed in slices
+        self.events: list = []         # ("slice", kind, active) / ("burst", active, steps), chunked mode only
         if not 0 <= int(prefix_cache) <= 64:
             raise ValueError("prefix_cache is 0..64 entries (a session holds at most 64)")
         self.prefix_cache = int(prefix_cache)
@@ -226,7 +242,7 @@ class BatchScheduler:
         try:
             while True:
                 with self._cv:
-                    while not self._stop and not self._queue and not self._active:
+                    while not self._stop and not self._queue and not self._active and self._pending is None:
                         self._cv.wait()
                     if self._stop:
                         break
@@ -243,6 +259,8 @@ class BatchScheduler:
 
     def _fail_active(self, exc):
         active, self._active = self._active, []
+        if self._pending is not None:
+            active, self._pending = active + [self._pending], None
         for rq in active:
             if not rq.future.done():
                 rq.future.set_exception(exc)
@@ -272,15 +290,20 @@ class BatchScheduler:
             if rq is None:
                 break
             if rq.exclusive:
-                if self._active:
+                if self._active or self._pending is not None:
                     break  # it waits for the session to drain; nothing behind it overtakes it
                 self._pop()
                 self._run_exclusive(rq)
                 continue
-            if len(self._active) >= self.slots:
+            if self._pending is not None or len(self._active) >= self.slots:
                 break
             self._pop()
+            if self.admit_chunk and not self._prefix_hit(rq):
+                self._begin(rq)
+                break
             admitted |= self._admit(rq)
+        if self._pending is not None:  # one slice, then (below) one burst of the running slots
+            admitted |= self._advance()
         if not self._active:
             return
         if admitted:  # the prefill's own selection: every new page has its first token
@@ -296,30 +319,73 @@ class BatchScheduler:
                 raise CapacityError(f"slot {slot}: kv_pos {rq.kv_pos} + burst {burst} exceeds the session's "
                                     f"{self._session.kv_cap} cache rows")
         self.bursts.append((len(self._active), burst))
+        if self.admit_chunk:
+            self.events.append(("burst", len(self._active), burst))
         status = self._session.step(burst)
         for rq in self._active:
             rq.kv_pos += burst
         self._deliver(status)
         self._retire_done()
 
+    def _prefix_hit(self, rq) -> bool:
+        return rq.prefix_key is not None and rq.prefix_key in self._prefix
+
+    def _open(self):
+        if self._session is None:
+            kw = {}
+            if self.per_request_params:
+                kw["per_request"] = True
+            if self.logprobs:
+                kw["logprobs"] = True
+            self._session = self.engine.open_session(self.slots, self.max_context, self.defaults, **kw)
+
+    def _admit_args(self, rq):
+        """(image rows of a prompt with several images, the keywords of admit / admit_prefix / admit_begin)"""
+        rows = None
+        if rq.pages:
+            import numpy as np
+            rows = np.concatenate(self.engine.image_embeddings(rq.pages), axis=0)
+        kw = {} if rq.logprobs is None else {"logprobs": rq.logprobs}
+        if self.per_request_params:
+            kw["params"] = rq.params
+        else:
+            kw.update(max_new_tokens=rq.params.max_new_tokens, seed=rq.params.seed)
+        return rows, kw
+
+    def _begin(self, rq):
+        """The admission of `rq` in slices: every check now, no device work; `_advance` runs the slices."""
+        try:
+            self._open()
+            rows, kw = self._admit_args(rq)
+            self._session.admit_begin(rq.ids, rq.mask, rq.page, rows, chunk_rows=self.admit_chunk, **kw)
+        except Exception as e:  # noqa: BLE001 - the request's own error: the running slots are untouched
+            rq.future.set_exception(e)
+            return
+        self._pending = rq
+
+    def _advance(self) -> bool:
+        """One slice of the pending admission; True when it made the page active."""
+        rq = self._pending
+        progress = getattr(self._session, "admit_progress", None)
+        kind = "vision" if progress is not None and progress()["vision_stage"] else "prefill"
+        try:
+            done, slot = self._session.admit_advance()
+        except Exception as e:  # noqa: BLE001 - a failed slice ends that admission alone
+            self._pending = None
+            rq.future.set_exception(e)
+            return False
+        self.admit_slices += 1
+        if done:
+            self._pending = None
+            self.chunked_admissions += 1
+            self._admitted(rq, slot, None)
+        self.events.append(("slice", kind, len(self._active)))
+        return done
+
     def _admit(self, rq) -> bool:
         try:
-            if self._session is None:
-                kw = {}
-                if self.per_request_params:
-                    kw["per_request"] = True
-                if self.logprobs:
-                    kw["logprobs"] = True
-                self._session = self.engine.open_session(self.slots, self.max_context, self.defaults, **kw)
-            rows = None
-            if rq.pages:
-                import numpy as np
-                rows = np.concatenate(self.engine.image_embeddings(rq.pages), axis=0)
-            kw = {} if rq.logprobs is None else {"logprobs": rq.logprobs}
-            if self.per_request_params:
-                kw["params"] = rq.params
-            else:
-                kw.update(max_new_tokens=rq.params.max_new_tokens, seed=rq.params.seed)
+            self._open()
+            rows, kw = self._admit_args(rq)
             handle = self._prefix.get(rq.prefix_key) if rq.prefix_key is not None else None
             if handle is not None:  # the page's prefix is cached: no vision, only the rows behind it are prefilled
                 self._prefix.move_to_end(rq.prefix_key)
@@ -334,6 +400,10 @@ class BatchScheduler:
         except Exception as e:  # noqa: BLE001 - the request's own error: the running slots are untouched
             rq.future.set_exception(e)
             return False
+        self._admitted(rq, slot, handle)
+        return True
+
+    def _admitted(self, rq, slot, handle):
         if slot != len(self._active):
             raise RuntimeError(f"session admitted into slot {slot}, expected {len(self._active)}")
         if rq.prefix_key is not None and handle is None:
@@ -342,7 +412,6 @@ class BatchScheduler:
         rq.kv_pos = len(rq.ids)
         self._active.append(rq)
         self.max_active = max(self.max_active, len(self._active))
-        return True
 
     def _keep_prefix(self, rq, slot):
         """The prefix of the page just admitted into `slot`, kept under its key; the least recently used handle is

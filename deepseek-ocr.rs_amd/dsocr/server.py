@@ -500,20 +500,27 @@ def add_scheduler_args(p):
                    help="with --slots: keep the K/V rows of up to N pages' image prefixes (LRU), so a later prompt on "
                         "the same image under the same vision settings skips vision and the prefill of those rows; "
                         "0 = off (the default)")
+    p.add_argument("--admit-chunk", type=int, default=0, metavar="ROWS",
+                   help="with --slots: admit a waiting request in slices (its vision, then ROWS >= 32 prompt rows at a "
+                        "time) and run one burst of the running requests between two slices, so a stream waits for a "
+                        "slice, not for a whole admission; 0 = off (the default)")
 
 
 def make_scheduler(state: ServerState, slots: int, max_context: int, per_request_params: bool = False,
-                   logprobs: bool = False, prefix_cache: int = 0):
+                   logprobs: bool = False, prefix_cache: int = 0, admit_chunk: int = 0):
     """The state's scheduler for --slots N (None for 0: requests take the lock path).  per_request_params: the
     DecodeParameters merge_decode builds from a request body are admitted into the session as that request's own.
     prefix_cache: --prefix-cache N (ValueError without --slots: the entries live in the decode session)."""
     if not 0 <= prefix_cache <= 64 or (prefix_cache and not slots):
         raise ValueError("--prefix-cache needs --slots (the prefix entries live in the decode session) and N in 0..64")
+    if admit_chunk and (not slots or admit_chunk < 32):
+        raise ValueError("--admit-chunk needs --slots (a chunked admission runs in the decode session) and ROWS >= 32")
     if not slots:
         return None
     from .scheduler import BatchScheduler
     return BatchScheduler(state.engine, state.tokenizer, slots, max_context, state.defaults, state.vision,
-                          per_request_params=per_request_params, logprobs=logprobs, prefix_cache=prefix_cache)
+                          per_request_params=per_request_params, logprobs=logprobs, prefix_cache=prefix_cache,
+                          admit_chunk=admit_chunk)
 
 
 def main(argv=None) -> int:
@@ -533,6 +540,8 @@ def main(argv=None) -> int:
     args = p.parse_args(argv)
     if not 0 <= args.prefix_cache <= 64 or (args.prefix_cache and not args.slots):
         p.error("--prefix-cache needs --slots and N in 0..64 (a session holds at most 64 prefix entries)")
+    if args.admit_chunk and (not args.slots or args.admit_chunk < 32):
+        p.error("--admit-chunk needs --slots and ROWS >= 32 (a chunked admission runs in the decode session)")
     config = model_config(args)  # --model deepseek-ocr | deepseek-ocr-2: the bundled config and vision defaults
     engine = load_model(ModelLoadArgs(config_path=config, weights_path=args.weights, snapshot_path=args.snapshot,
                                       snapshot_packed=getattr(args, "snapshot_packed", None),
@@ -541,7 +550,7 @@ def main(argv=None) -> int:
     state = ServerState(engine, load_tokenizer(args.tokenizer, _vocab_of(config)), args.model,
                         vision_settings(args), decode_params(args))
     state.scheduler = make_scheduler(state, args.slots, args.max_context, args.per_request_params, args.logprobs,
-                                     args.prefix_cache)
+                                     args.prefix_cache, args.admit_chunk)
     import uvicorn
     uvicorn.run(create_app(state), host=args.host, port=args.port)
     return 0

@@ -258,7 +258,7 @@ typedef struct {
     size_t kv_cap;     /* cache rows per slot: max_context + burst_cap */
     size_t burst_cap;  /* most steps one dsocr_session_step replays */
     size_t steps;      /* decode steps replayed since the session opened */
-    size_t flags;      /* the DSOCR_SESSION_* flags the session was opened with */
+    size_t flags;      /* the DSOCR_SESSION_* flags the session was opened with (| DSOCR_SESSION_ADMIT_PENDING) */
 } dsocr_session_desc;
 dsocr_status dsocr_session_open(dsocr_engine* e, size_t slots, size_t max_context, const dsocr_decode_params* params);
 /* flags = 0: dsocr_session_open.  Unknown flag bits are DSOCR_EINVAL. */
@@ -318,6 +318,31 @@ dsocr_status dsocr_session_admit_prefix(dsocr_engine* e, int handle, const dsocr
 dsocr_status dsocr_session_prefix_drop(dsocr_engine* e, int handle);
 dsocr_status dsocr_session_prefix_stats(const dsocr_engine* e, size_t* entries, size_t* bytes, size_t* admissions,
                                         size_t* rows_reused);
+/* ---- chunked admission: dsocr_session_admit_params in slices, so that dsocr_session_step can run between them and a
+ * running stream never waits for a whole vision + prefill.  Off unless called: the calls above launch what they did.
+ *   dsocr_session_admit_begin: every check of dsocr_session_admit_params, then DSOCR_EINVAL when chunk_rows < 32, an
+ *   admission is already pending or no slot is free.  Launches nothing; *ticket numbers the admission.  req->page
+ *   must stay alive until the admission completes or is cancelled (ids, mask and image rows are copied).
+ *   dsocr_session_admit_advance: exactly one slice, synchronised.  Slices: the vision of the page in three (SAM;
+ *   CLIP or the OCR2 encoder; projector and the image-row plan.  None without a page; one slice for a tiled page
+ *   when DSOCR_VIS_STREAMS=0 makes both vision passes share their workspaces), then the prompt in chunks of chunk_rows rows, each a prefill of its rows behind the rows already
+ *   appended (the first is the plain causal prefill; the others attend through the query-tiled kernel of
+ *   dsocr_k_attention_chunk).  The last chunk also makes the first selection and sets *done = 1 and *slot (= active
+ *   before); until then *done = 0 and *slot = -1.  A slice that fails ends the admission.
+ *   dsocr_session_admit_cancel: forgets the pending admission; nothing a later step or admission reads was changed.
+ *   While an admission is pending the page is staged in the last slot: dsocr_session_step, _poll, _retire (with its
+ *   compaction), _logprobs and _prefix_keep stay legal, dsocr_session_admit* and _admit_prefix are DSOCR_EINVAL,
+ *   dsocr_session_close drops it, dsocr_session_info reports DSOCR_SESSION_ADMIT_PENDING in flags and
+ *   dsocr_session_admit_progress the prompt rows prefilled, the prompt's rows, the slices run and the vision stage
+ *   the next slice runs (1..3, 0: none left); *chunk_attn_launches counts the engine's launch_attention_chunk
+ *   launches so far, pending or not (any pointer may be NULL).  The session descriptor's layout is unchanged.  The ids of every page equal a plain admission's. */
+#define DSOCR_SESSION_ADMIT_PENDING 0x100u
+dsocr_status dsocr_session_admit_begin(dsocr_engine* e, const dsocr_request* req, const dsocr_decode_params* params,
+                                       size_t chunk_rows, int* ticket);
+dsocr_status dsocr_session_admit_advance(dsocr_engine* e, int* done, int* slot);
+dsocr_status dsocr_session_admit_cancel(dsocr_engine* e);
+dsocr_status dsocr_session_admit_progress(const dsocr_engine* e, int* pending, size_t* rows_done, size_t* rows_total,
+                                          size_t* slices, int* vision_stage, size_t* chunk_attn_launches);
 dsocr_status dsocr_session_close(dsocr_engine* e);
 /* DSOCR_EINVAL when no session is open */
 dsocr_status dsocr_session_info(const dsocr_engine* e, dsocr_session_desc* out);
@@ -538,6 +563,15 @@ dsocr_status dsocr_k_prefill_attention(int B, int heads, int kv_heads, int hd, i
 dsocr_status dsocr_k_prefill_attention_past(int B, int heads, int kv_heads, int hd, int rope_dim, int use_mla, int cap,
                                             float scale, const int* past, const int* lens, float* qkv, const float* cos,
                                             const float* sin, float* kc, float* vc, float* o);
+/* The same stage as a chunk of a sliced admission runs it (launch_attention_chunk: one workgroup per 32-query tile,
+ * head and sequence, the keys streamed in tiles with an online softmax; one launch, no workspace).  The arguments of
+ * dsocr_k_prefill_attention_past, plus the session cache's shape: kc / vc hold `pages` pages of [kv_heads][cap][hd]
+ * and sequence b lives in page page0 + b (0 <= page0, page0 + B <= pages).  Rows past past[b] + lens[b] are never
+ * read.  DSOCR_EINVAL, before any launch, for hd outside {32, 64, 128}, heads % kv_heads != 0, lens[b] < 1,
+ * past[b] < 0 or past[b] + lens[b] > cap. */
+dsocr_status dsocr_k_attention_chunk(int B, int heads, int kv_heads, int hd, int rope_dim, int use_mla, int cap,
+                                     float scale, const int* past, const int* lens, float* qkv, const float* cos,
+                                     const float* sin, float* kc, float* vc, float* o, int page0, int pages);
 /* One page's decode attention sub-layer as the engine runs it (block.rs:446-804 at seq_len 1): RMSNorm +
  * q/k/v projection (Wqkv [3H][H], 16-bit) with RoPE in the epilogue, K/V append at kv_pos[s], softmax
  * attention over positions 0..kv_pos[s], for `steps` launches back to back (x [steps][H], kv_pos [steps],

@@ -19,10 +19,14 @@ Page i generates MAX_NEW[i] tokens: drawn once, numpy default_rng(4011).choice(L
       vision and the full prefill: the parent's code path) and on (the second prompt is admitted behind the kept
       prefix); the two alternate ROUNDS times; requests/s, steps and the wall time of a plain admission, a keep and
       a prefix admission
+  (q) chunked admission, on (c)'s 32 text pages and on (p)'s image pages (one prompt each): plain
+      admission (the parent's code path) against admit_begin / admit_advance with 128-row chunks, one slice per burst
+      of 8 steps, alternating ROUNDS times; pages/s, the largest and 99th-percentile wall gap between two consecutive
+      bursts while a slot runs, and the wall time per slice by kind
 The arms alternate ROUNDS times; pages/s and decode steps are reported as median [min, max].  Also: the wall time
 of one admission while other slots wait, and one session_slot_move of a 1200-row full-size page against its bytes.
 
-    python tools/session_bench.py [--rounds 3] [--pages 32] [--arms a,b,c,d,e,f,g,h,p] [--out profiles/session_bench.json]
+    python tools/session_bench.py [--rounds 3] [--pages 32] [--arms a,b,c,d,e,f,g,h,p,q] [--out profiles/session_bench.json]
 """
 import argparse
 import ctypes as C
@@ -251,6 +255,82 @@ def prefix_arms(eng, P, pages, rounds):
     return out
 
 
+def run_admission(eng, items, P, chunk):
+    """items [(ids, mask, page, max_new)] in arrival order through one 8-slot session, a burst of 8 steps per turn.
+    chunk = 0: every free slot is filled by a plain admission before the burst.  chunk > 0: one admission at a time
+    in slices, one slice per turn.  Gaps: wall ms from the end of a burst to the start of the next while a slot ran."""
+    need = max(len(it[0]) + it[3] + 1 for it in items)
+    gaps, slices, admits = [], {"sam": [], "clip": [], "projector": [], "prefill": []}, []
+    done, nxt, active, pending, last_end = 0, 0, 0, False, None
+    with eng.open_session(SLOTS, need, P(max_new_tokens=max(it[3] for it in items)), ignore_eos=True) as s:
+        while done < len(items):
+            if chunk:
+                if not pending and active < SLOTS and nxt < len(items):
+                    ids, mask, page, m = items[nxt]
+                    s.admit_begin(ids, mask, page, chunk_rows=chunk, max_new_tokens=m)
+                    pending, nxt = True, nxt + 1
+                if pending:
+                    kind = ("prefill", "sam", "clip", "projector")[s.admit_progress()["vision_stage"]]
+                    t = time.perf_counter()
+                    fin, _ = s.admit_advance()
+                    slices[kind].append((time.perf_counter() - t) * 1e3)
+                    if fin:
+                        pending, active = False, active + 1
+            else:
+                while active < SLOTS and nxt < len(items):
+                    ids, mask, page, m = items[nxt]
+                    t = time.perf_counter()
+                    s.admit(ids, mask, page, max_new_tokens=m)
+                    admits.append((time.perf_counter() - t) * 1e3)
+                    active, nxt = active + 1, nxt + 1
+            if not active:
+                last_end = None
+                continue
+            t = time.perf_counter()
+            if last_end is not None:
+                gaps.append((t - last_end) * 1e3)
+            status = s.step(8)
+            last_end = time.perf_counter()
+            for st in sorted(status, key=lambda x: -x.slot):
+                if st.done:
+                    s.retire(st.slot)
+                    active, done = active - 1, done + 1
+            if not active:
+                last_end = None
+            elif any(st.done for st in status):
+                last_end = time.perf_counter()  # (a retire is not part of the gap an admission causes)
+        steps = s.info()["steps"]
+    return steps, {"gaps": gaps, "slices": slices, "admits": admits}
+
+
+def chunk_arms(eng, P, text_items, image_items, rounds, chunk=128):
+    out = {"chunk_rows": chunk, "rounds": rounds, "burst": 8}
+    for name, items in (("text_pages", text_items), ("image_pages", image_items)):
+        for c in (0, chunk):  # warm-up
+            run_admission(eng, items[:SLOTS + 2], P, c)
+        res = {k: {"pages_s": [], "gap_max": [], "gap_p99": [], "slices": {}, "admits": []} for k in ("plain", "chunked")}
+        for _ in range(rounds):
+            for k, c in (("plain", 0), ("chunked", chunk)):
+                t = time.perf_counter()
+                _, extra = run_admission(eng, items, P, c)
+                r = res[k]
+                r["pages_s"].append(len(items) / (time.perf_counter() - t))
+                r["gap_max"].append(max(extra["gaps"]))
+                r["gap_p99"].append(float(np.percentile(extra["gaps"], 99)))
+                r["admits"] += extra["admits"]
+                for kind, v in extra["slices"].items():
+                    r["slices"].setdefault(kind, []).extend(v)
+        out[name] = {"pages": len(items), "prompt_len": len(items[0][0])}
+        for k, r in res.items():
+            o = {"pages_s": mmm(r["pages_s"]), "gap_max_ms": mmm(r["gap_max"]), "gap_p99_ms": mmm(r["gap_p99"])}
+            if r["admits"]:
+                o["admit_ms"] = mmm(r["admits"])
+            o["slice_ms"] = {kind: dict(mmm(v), n=len(v)) for kind, v in r["slices"].items() if v}
+            out[name][k] = o
+        out[name]["chunked_over_plain"] = out[name]["chunked"]["pages_s"]["median"] / out[name]["plain"]["pages_s"]["median"]
+    return out
+
+
 def slot_move_alone(cfg, rows=1200, reps=10):
     """dsocr_k_session_slot_move at the full-size cache shape, two slots: call wall time (launch + synchronise)."""
     from dsocr._lib import check, lib
@@ -341,6 +421,11 @@ def main():
         out["d_within_c_spread"] = bool(c["min"] <= med("d_session_per_request_greedy") <= c["max"])
     if "p" in a.arms.split(","):
         out["p_prefix_cache"] = prefix_arms(eng, P, a.prefix_pages, a.rounds)
+    if "q" in a.arms.split(","):
+        docs = image_requests(eng, a.prefix_pages)
+        out["q_chunked_admission"] = chunk_arms(
+            eng, P, [(r, None, None, m) for r, m in zip(reqs, max_new)],
+            [(prompts[0][0], prompts[0][1], page, PREFIX_NEW) for page, prompts, _ in docs], a.rounds)
     eng.close()
     out["slot_move_1200_rows"] = slot_move_alone(json.load(open(dsocr.FULL_CONFIG)))
     line = json.dumps(out)
