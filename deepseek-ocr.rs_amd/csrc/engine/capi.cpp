@@ -1145,184 +1145,144 @@ dsocr_status dsocr_k_decode_attention(int B, int heads, int kv_heads, int hd, in
         if (herr) throw std::runtime_error("EINTERNAL: decode attention merge timed out");
     });
 }
+// The one body of the three prefill-attention hooks below: the plan and the views of Engine::forward_rows /
+// layer_forward_prefill on a cache of `cap` slots per head, into pages [page0, page0 + B) of a cache of `pages`.
+// `past` is null for the plain causal prefill.  Args is AttnArgs or AttnPastArgs (the fields filled here carry the same
+// names in both); run(a, rope, dev) sets what is its own (lengths, workspace), checks the kernel's contract, then
+// rotates, appends and launches.
+extern "C++" {  // (a template cannot have C linkage)
+struct DevBufs {  // device buffers freed on return or throw
+    std::vector<void*> bufs;
+    ~DevBufs() { for (void* p : bufs) (void)hipFree(p); }
+    void* alloc(size_t b) {
+        void* p = nullptr;
+        check_hip(hipMalloc(&p, b ? b : 16), "hipMalloc");
+        bufs.push_back(p);
+        return p;
+    }
+    void* upload(const void* src, size_t b) {
+        void* p = alloc(b);
+        check_hip(hipMemcpy(p, src, b, hipMemcpyHostToDevice), "h2d");
+        return p;
+    }
+    // a workspace no launch has written: NaN wherever a combine reads past its own records
+    float* workspace(size_t floats) {
+        float* p = (float*)alloc(sizeof(float) * floats);
+        check_hip(hipMemset(p, 0xFF, sizeof(float) * floats), "hipMemset");
+        return p;
+    }
+};
+struct PrefillCase {
+    const dsocr::PrefillPlan& plan;
+    const int* lens;  // device copies
+    const int* past;  // (null without a past)
+    DevBufs& dev;
+};
+template <class Args, class Run>
+static void prefill_attention_case(int B, int heads, int kv_heads, int hd, int rope_dim, int use_mla, int cap, float scale,
+                                   bool behind_past, const int* past, const int* lens, float* qkv, const float* cos,
+                                   const float* sin, float* kc, float* vc, float* o, int page0, int pages, Run run) {
+    if (heads <= 0 || kv_heads <= 0 || heads % kv_heads || rope_dim < 0 || rope_dim > hd || rope_dim % 2)
+        throw std::runtime_error("EINVAL: bad head / rope configuration");
+    if (B <= 0 || (behind_past && !past) || !lens || !qkv || !cos || !sin || !kc || !vc || !o)
+        throw std::runtime_error("EINVAL: NULL argument");
+    if (page0 < 0 || pages < 1 || (long)page0 + B > pages) throw std::runtime_error("EINVAL: pages [page0, page0 + B) must lie in the cache");
+    for (int b = 0; b < B; ++b) {
+        if (lens[b] < 1)
+            throw std::runtime_error(behind_past ? "EINVAL: every sequence needs at least one new row"
+                                                 : "EINVAL: every sequence needs at least one row");
+        if (behind_past && (past[b] < 0 || (long)past[b] + lens[b] > cap))
+            throw std::runtime_error("EINVAL: past + new rows must fit in cap");
+    }
+    const long QKVN = (long)(heads + 2 * kv_heads) * hd, H = (long)heads * hd;
+    const long head_stride = (long)cap * hd, page_stride = (long)kv_heads * head_stride;
+    const std::vector<int> hl(lens, lens + B), hp(behind_past ? past : nullptr, behind_past ? past + B : nullptr);
+    const dsocr::PrefillPlan plan = dsocr::prefill_row_plan(hl, QKVN, H, page_stride, hp);
+    if (!behind_past && cap < plan.max_len) throw std::runtime_error("EINVAL: cap is below the longest sequence");
+    float* kc0 = kc + (long)page0 * page_stride;
+    float* vc0 = vc + (long)page0 * page_stride;
+    DevBufs dev;
+    dsocr::RopeKvArgs r;
+    r.qkv = qkv; r.ld = QKVN; r.rows = (int)plan.T;
+    r.row_page = (const int*)dev.upload(plan.row_page.data(), sizeof(int) * plan.row_page.size());
+    r.row_pos = (const int*)dev.upload(plan.row_pos.data(), sizeof(int) * plan.row_pos.size());
+    r.heads = heads; r.kv_heads = kv_heads; r.hd = hd; r.rope_dim = rope_dim; r.use_mla = use_mla ? 1 : 0;
+    r.cos = cos; r.sin = sin; r.kc = kc0; r.vc = vc0; r.page_stride = page_stride; r.head_stride = head_stride;
+    Args a;
+    a.q = {qkv, QKVN, hd, (const long*)dev.upload(plan.q_off.data(), sizeof(long) * B)};
+    const long* kv_off = (const long*)dev.upload(plan.kv_off.data(), sizeof(long) * B);
+    a.k = {kc0, hd, head_stride, kv_off};
+    a.v = {vc0, hd, head_stride, kv_off};
+    a.o = o; a.o_row_stride = H; a.o_head_stride = hd;
+    a.o_seq_off = (const long*)dev.upload(plan.o_off.data(), sizeof(long) * B);
+    a.n_seq = B; a.heads = heads; a.kv_heads = kv_heads; a.hd = hd; a.scale = scale;
+    const PrefillCase c{plan, (const int*)dev.upload(lens, sizeof(int) * B),
+                        behind_past ? (const int*)dev.upload(past, sizeof(int) * B) : nullptr, dev};
+    run(a, r, c);
+}
+// AttnPastArgs: the per-sequence lengths and the host-side bounds of the plan
+static void set_past_lengths(dsocr::AttnPastArgs& a, const PrefillCase& c) {
+    a.past = c.past; a.n_q = c.lens; a.max_q = c.plan.max_len; a.max_total = c.plan.max_total;
+}
+static void require_head_dim(int hd) {
+    if (hd != 32 && hd != 64 && hd != 128) throw std::runtime_error("EINVAL: head_dim must be 32, 64 or 128");
+}
+}  // extern "C++"
 dsocr_status dsocr_k_prefill_attention(int B, int heads, int kv_heads, int hd, int rope_dim, int use_mla, int cap,
                                        float scale, const int* lens, float* qkv, const float* cos, const float* sin,
                                        float* kc, float* vc, float* o, int use_part) {
     return guarded([&] {
-        if (hd != 32 && hd != 64 && hd != 128) throw std::runtime_error("EINVAL: head_dim must be 32, 64 or 128");
-        if (heads <= 0 || kv_heads <= 0 || heads % kv_heads || rope_dim < 0 || rope_dim > hd || rope_dim % 2)
-            throw std::runtime_error("EINVAL: bad head / rope configuration");
-        if (B <= 0 || !lens || !qkv || !cos || !sin || !kc || !vc || !o) throw std::runtime_error("EINVAL: NULL argument");
-        for (int b = 0; b < B; ++b)
-            if (lens[b] < 1) throw std::runtime_error("EINVAL: every sequence needs at least one row");
-        // the plan and the views of Engine::forward_rows / layer_forward_prefill, on a cache of `cap` slots per head
-        const long QKVN = (long)(heads + 2 * kv_heads) * hd, H = (long)heads * hd;
-        const long head_stride = (long)cap * hd, page_stride = (long)kv_heads * head_stride;
-        const dsocr::PrefillPlan plan = dsocr::prefill_row_plan(std::vector<int>(lens, lens + B), QKVN, H, page_stride);
-        if (cap < plan.max_len) throw std::runtime_error("EINVAL: cap is below the longest sequence");
-        std::vector<void*> bufs;
-        auto alloc = [&](size_t b) {
-            void* p = nullptr;
-            check_hip(hipMalloc(&p, b ? b : 16), "hipMalloc");
-            bufs.push_back(p);
-            return p;
-        };
-        auto upload = [&](const void* src, size_t b) {
-            void* p = alloc(b);
-            check_hip(hipMemcpy(p, src, b, hipMemcpyHostToDevice), "h2d");
-            return p;
-        };
-        try {
-            dsocr::RopeKvArgs r;
-            r.qkv = qkv; r.ld = QKVN; r.rows = (int)plan.T;
-            r.row_page = (const int*)upload(plan.row_page.data(), sizeof(int) * plan.row_page.size());
-            r.row_pos = (const int*)upload(plan.row_pos.data(), sizeof(int) * plan.row_pos.size());
-            r.heads = heads; r.kv_heads = kv_heads; r.hd = hd; r.rope_dim = rope_dim; r.use_mla = use_mla ? 1 : 0;
-            r.cos = cos; r.sin = sin; r.kc = kc; r.vc = vc; r.page_stride = page_stride; r.head_stride = head_stride;
-            dsocr::launch_rope_kv(r, nullptr);
-            const long* q_off = (const long*)upload(plan.q_off.data(), sizeof(long) * B);
-            const long* kv_off = (const long*)upload(plan.kv_off.data(), sizeof(long) * B);
-            const long* o_off = (const long*)upload(plan.o_off.data(), sizeof(long) * B);
-            dsocr::AttnArgs a;
-            a.q = {qkv, QKVN, hd, q_off};
-            a.k = {kc, hd, head_stride, kv_off};
-            a.v = {vc, hd, head_stride, kv_off};
-            a.o = o; a.o_row_stride = H; a.o_head_stride = hd; a.o_seq_off = o_off;
-            a.n_seq = B; a.L = plan.max_len; a.seq_len = (const int*)upload(lens, sizeof(int) * B);
-            a.heads = heads; a.kv_heads = kv_heads; a.hd = hd; a.scale = scale; a.causal = 1;
-            if (use_part) {  // a workspace no launch has written: NaN wherever the merge reads past its own pieces
-                a.part_floats = dsocr::attention_causal_part_floats(B, heads, plan.max_len, hd);
-                a.part = (float*)alloc(sizeof(float) * a.part_floats);
-                check_hip(hipMemset(a.part, 0xFF, sizeof(float) * a.part_floats), "hipMemset");
-            }
-            dsocr::launch_attention(a, nullptr);
-            check_hip(hipGetLastError(), "prefill attention launch");
-            check_hip(hipDeviceSynchronize(), "prefill attention");
-        } catch (...) {
-            for (void* p : bufs) (void)hipFree(p);
-            throw;
-        }
-        for (void* p : bufs) (void)hipFree(p);
+        require_head_dim(hd);
+        prefill_attention_case<dsocr::AttnArgs>(
+            B, heads, kv_heads, hd, rope_dim, use_mla, cap, scale, false, nullptr, lens, qkv, cos, sin, kc, vc, o, 0,
+            B > 0 ? B : 1, [&](dsocr::AttnArgs& a, const dsocr::RopeKvArgs& r, const PrefillCase& c) {
+                a.L = c.plan.max_len; a.seq_len = c.lens; a.causal = 1;
+                if (use_part) {
+                    a.part_floats = dsocr::attention_causal_part_floats(B, heads, c.plan.max_len, hd);
+                    a.part = c.dev.workspace(a.part_floats);
+                }
+                dsocr::launch_rope_kv(r, nullptr);
+                dsocr::launch_attention(a, nullptr);
+                check_hip(hipGetLastError(), "prefill attention launch");
+                check_hip(hipDeviceSynchronize(), "prefill attention");
+            });
     });
 }
 dsocr_status dsocr_k_prefill_attention_past(int B, int heads, int kv_heads, int hd, int rope_dim, int use_mla, int cap,
                                             float scale, const int* past, const int* lens, float* qkv, const float* cos,
                                             const float* sin, float* kc, float* vc, float* o) {
     return guarded([&] {
-        if (hd != 32 && hd != 64 && hd != 128) throw std::runtime_error("EINVAL: head_dim must be 32, 64 or 128");
-        if (heads <= 0 || kv_heads <= 0 || heads % kv_heads || rope_dim < 0 || rope_dim > hd || rope_dim % 2)
-            throw std::runtime_error("EINVAL: bad head / rope configuration");
-        if (B <= 0 || !past || !lens || !qkv || !cos || !sin || !kc || !vc || !o) throw std::runtime_error("EINVAL: NULL argument");
-        for (int b = 0; b < B; ++b) {
-            if (lens[b] < 1) throw std::runtime_error("EINVAL: every sequence needs at least one new row");
-            if (past[b] < 0 || (long)past[b] + lens[b] > cap) throw std::runtime_error("EINVAL: past + new rows must fit in cap");
-        }
-        // the plan and the views of Engine::forward_rows / layer_forward_prefill behind a past
-        const long QKVN = (long)(heads + 2 * kv_heads) * hd, H = (long)heads * hd;
-        const long head_stride = (long)cap * hd, page_stride = (long)kv_heads * head_stride;
-        const std::vector<int> hl(lens, lens + B), hp(past, past + B);
-        const dsocr::PrefillPlan plan = dsocr::prefill_row_plan(hl, QKVN, H, page_stride, hp);
-        std::vector<void*> bufs;
-        auto alloc = [&](size_t b) {
-            void* p = nullptr;
-            check_hip(hipMalloc(&p, b ? b : 16), "hipMalloc");
-            bufs.push_back(p);
-            return p;
-        };
-        auto upload = [&](const void* src, size_t b) {
-            void* p = alloc(b);
-            check_hip(hipMemcpy(p, src, b, hipMemcpyHostToDevice), "h2d");
-            return p;
-        };
-        try {
-            dsocr::RopeKvArgs r;
-            r.qkv = qkv; r.ld = QKVN; r.rows = (int)plan.T;
-            r.row_page = (const int*)upload(plan.row_page.data(), sizeof(int) * plan.row_page.size());
-            r.row_pos = (const int*)upload(plan.row_pos.data(), sizeof(int) * plan.row_pos.size());
-            r.heads = heads; r.kv_heads = kv_heads; r.hd = hd; r.rope_dim = rope_dim; r.use_mla = use_mla ? 1 : 0;
-            r.cos = cos; r.sin = sin; r.kc = kc; r.vc = vc; r.page_stride = page_stride; r.head_stride = head_stride;
-            dsocr::AttnPastArgs a;
-            a.q = {qkv, QKVN, hd, (const long*)upload(plan.q_off.data(), sizeof(long) * B)};
-            const long* kv_off = (const long*)upload(plan.kv_off.data(), sizeof(long) * B);
-            a.k = {kc, hd, head_stride, kv_off};
-            a.v = {vc, hd, head_stride, kv_off};
-            a.o = o; a.o_row_stride = H; a.o_head_stride = hd;
-            a.o_seq_off = (const long*)upload(plan.o_off.data(), sizeof(long) * B);
-            a.n_seq = B; a.past = (const int*)upload(past, sizeof(int) * B); a.n_q = (const int*)upload(lens, sizeof(int) * B);
-            a.max_q = plan.max_len; a.max_total = plan.max_total;
-            a.heads = heads; a.kv_heads = kv_heads; a.hd = hd; a.scale = scale;
-            // a workspace no launch has written: NaN wherever the combine reads past its own records
-            a.part_floats = dsocr::attention_past_part_floats(B, heads, plan.max_len, plan.max_total, hd);
-            a.part = (float*)alloc(sizeof(float) * a.part_floats);
-            check_hip(hipMemset(a.part, 0xFF, sizeof(float) * a.part_floats), "hipMemset");
-            if (!dsocr::attention_past_ok(a)) throw std::runtime_error("EINVAL: attention_past: shape outside the kernel's contract");
-            dsocr::launch_rope_kv(r, nullptr);
-            dsocr::launch_attention_past(a, nullptr);
-            check_hip(hipGetLastError(), "prefill attention (past) launch");
-            check_hip(hipDeviceSynchronize(), "prefill attention (past)");
-        } catch (...) {
-            for (void* p : bufs) (void)hipFree(p);
-            throw;
-        }
-        for (void* p : bufs) (void)hipFree(p);
+        require_head_dim(hd);
+        prefill_attention_case<dsocr::AttnPastArgs>(
+            B, heads, kv_heads, hd, rope_dim, use_mla, cap, scale, true, past, lens, qkv, cos, sin, kc, vc, o, 0,
+            B > 0 ? B : 1, [&](dsocr::AttnPastArgs& a, const dsocr::RopeKvArgs& r, const PrefillCase& c) {
+                set_past_lengths(a, c);
+                a.part_floats = dsocr::attention_past_part_floats(B, heads, c.plan.max_len, c.plan.max_total, hd);
+                a.part = c.dev.workspace(a.part_floats);
+                // refused before anything is rotated or appended
+                if (!dsocr::attention_past_ok(a)) throw std::runtime_error("EINVAL: attention_past: shape outside the kernel's contract");
+                dsocr::launch_rope_kv(r, nullptr);
+                dsocr::launch_attention_past(a, nullptr);
+                check_hip(hipGetLastError(), "prefill attention (past) launch");
+                check_hip(hipDeviceSynchronize(), "prefill attention (past)");
+            });
     });
 }
 dsocr_status dsocr_k_attention_chunk(int B, int heads, int kv_heads, int hd, int rope_dim, int use_mla, int cap,
                                      float scale, const int* past, const int* lens, float* qkv, const float* cos,
                                      const float* sin, float* kc, float* vc, float* o, int page0, int pages) {
     return guarded([&] {
-        if (heads <= 0 || kv_heads <= 0 || heads % kv_heads || rope_dim < 0 || rope_dim > hd || rope_dim % 2)
-            throw std::runtime_error("EINVAL: bad head / rope configuration");
-        if (B <= 0 || !past || !lens || !qkv || !cos || !sin || !kc || !vc || !o) throw std::runtime_error("EINVAL: NULL argument");
-        if (page0 < 0 || pages < 1 || (long)page0 + B > pages) throw std::runtime_error("EINVAL: pages [page0, page0 + B) must lie in the cache");
-        for (int b = 0; b < B; ++b) {
-            if (lens[b] < 1) throw std::runtime_error("EINVAL: every sequence needs at least one new row");
-            if (past[b] < 0 || (long)past[b] + lens[b] > cap) throw std::runtime_error("EINVAL: past + new rows must fit in cap");
-        }
-        // the plan and the views of Engine::forward_rows / layer_forward_prefill for a chunk behind a past, into pages
-        // [page0, page0 + B) of a session cache (kv_page0_)
-        const long QKVN = (long)(heads + 2 * kv_heads) * hd, H = (long)heads * hd;
-        const long head_stride = (long)cap * hd, page_stride = (long)kv_heads * head_stride;
-        const std::vector<int> hl(lens, lens + B), hp(past, past + B);
-        const dsocr::PrefillPlan plan = dsocr::prefill_row_plan(hl, QKVN, H, page_stride, hp);
-        float* kc0 = kc + (long)page0 * page_stride;
-        float* vc0 = vc + (long)page0 * page_stride;
-        std::vector<void*> bufs;
-        auto upload = [&](const void* src, size_t b) {
-            void* p = nullptr;
-            check_hip(hipMalloc(&p, b ? b : 16), "hipMalloc");
-            bufs.push_back(p);
-            check_hip(hipMemcpy(p, src, b, hipMemcpyHostToDevice), "h2d");
-            return p;
-        };
-        try {
-            dsocr::RopeKvArgs r;
-            r.qkv = qkv; r.ld = QKVN; r.rows = (int)plan.T;
-            r.row_page = (const int*)upload(plan.row_page.data(), sizeof(int) * plan.row_page.size());
-            r.row_pos = (const int*)upload(plan.row_pos.data(), sizeof(int) * plan.row_pos.size());
-            r.heads = heads; r.kv_heads = kv_heads; r.hd = hd; r.rope_dim = rope_dim; r.use_mla = use_mla ? 1 : 0;
-            r.cos = cos; r.sin = sin; r.kc = kc0; r.vc = vc0; r.page_stride = page_stride; r.head_stride = head_stride;
-            dsocr::AttnPastArgs a;
-            a.q = {qkv, QKVN, hd, (const long*)upload(plan.q_off.data(), sizeof(long) * B)};
-            const long* kv_off = (const long*)upload(plan.kv_off.data(), sizeof(long) * B);
-            a.k = {kc0, hd, head_stride, kv_off};
-            a.v = {vc0, hd, head_stride, kv_off};
-            a.o = o; a.o_row_stride = H; a.o_head_stride = hd;
-            a.o_seq_off = (const long*)upload(plan.o_off.data(), sizeof(long) * B);
-            a.n_seq = B; a.past = (const int*)upload(past, sizeof(int) * B); a.n_q = (const int*)upload(lens, sizeof(int) * B);
-            a.max_q = plan.max_len; a.max_total = plan.max_total;
-            a.heads = heads; a.kv_heads = kv_heads; a.hd = hd; a.scale = scale;
-            // refused before anything is rotated or appended
-            if (!dsocr::attention_chunk_ok(a)) throw std::runtime_error("EINVAL: attention_chunk: shape outside the kernel's contract");
-            dsocr::launch_rope_kv(r, nullptr);
-            dsocr::launch_attention_chunk(a, nullptr);
-            check_hip(hipGetLastError(), "attention_chunk launch");
-            check_hip(hipDeviceSynchronize(), "attention_chunk");
-        } catch (...) {
-            for (void* p : bufs) (void)hipFree(p);
-            throw;
-        }
-        for (void* p : bufs) (void)hipFree(p);
+        prefill_attention_case<dsocr::AttnPastArgs>(
+            B, heads, kv_heads, hd, rope_dim, use_mla, cap, scale, true, past, lens, qkv, cos, sin, kc, vc, o, page0,
+            pages, [&](dsocr::AttnPastArgs& a, const dsocr::RopeKvArgs& r, const PrefillCase& c) {
+                set_past_lengths(a, c);
+                // refused before anything is rotated or appended
+                if (!dsocr::attention_chunk_ok(a)) throw std::runtime_error("EINVAL: attention_chunk: shape outside the kernel's contract");
+                dsocr::launch_rope_kv(r, nullptr);
+                dsocr::launch_attention_chunk(a, nullptr);
+                check_hip(hipGetLastError(), "attention_chunk launch");
+                check_hip(hipDeviceSynchronize(), "attention_chunk");
+            });
     });
 }
 dsocr_status dsocr_k_qkv_attention(int fused, int steps, int H, int heads, int hd, int max_len, float scale,

@@ -16,6 +16,7 @@
 #include <cstdlib>
 #include <stdexcept>
 
+#include "attn_tile.hpp"
 #include "dev_common.hpp"
 #include "kernels.hpp"
 
@@ -151,6 +152,7 @@ __global__ __launch_bounds__(256) void attention_fwd_kernel(AttnArgs a) {
 // every K fragment is a 16-byte LDS read, V staged transposed in LDS (16-byte reads of 4 keys),
 // K/V tile t+1 prefetched into registers while tile t is consumed (one barrier per tile), and the
 // rel-pos bias column indices of a tile computed once per tile in LDS (no per-score division).
+// The tile arithmetic (query load, both MFMA products, the online-softmax step, the partial record) is attn_tile.hpp's.
 //
 // SPLIT (the causal prefill, round 4): the keys of a 128-query block are split into pieces of AT_KSPLIT keys,
 // one block per (query block, piece) — at one 706-token page 60 blocks with 1..6 pieces of work became 210
@@ -200,14 +202,7 @@ __global__ __launch_bounds__(256, 1) void attention_fwd2_kernel(AttnArgs a) {
     const int q_lane = qb0 + wave * AT_Q + l32;
     const bool q_valid = q_lane < len;
     float qreg[HD / 2];
-    {
-        const float* qr = Q + (long)(q_valid ? q_lane : 0) * a.q.row_stride + half * (HD / 2);
-#pragma unroll
-        for (int i = 0; i < HD / 2; i += 4) {
-            const float4 v4 = *reinterpret_cast<const float4*>(qr + i);
-            qreg[i] = v4.x; qreg[i + 1] = v4.y; qreg[i + 2] = v4.z; qreg[i + 3] = v4.w;
-        }
-    }
+    attn_tile_load_q<HD>(Q + (long)(q_valid ? q_lane : 0) * a.q.row_stride, half, qreg);
     // REL: the block's 128 query rows of the rel-pos table staged once into LDS (row pitch R + 1:
     // the lanes of a wave read 32 different rows at one column without bank conflicts)
     extern __shared__ __attribute__((aligned(16))) float rbs[];
@@ -269,67 +264,28 @@ __global__ __launch_bounds__(256, 1) void attention_fwd2_kernel(AttnArgs a) {
         AT2_GLOAD(k0 + AT_KT);  // unconditional (clamped keys): a guarded prefetch demotes rk/rv to scratch
         // S^T = K . Q^T: lane (half, l32) feeds dims i + half*HD/2
         f32x16 sc;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) sc[r] = 0.f;
-#pragma unroll
-        for (int i = 0; i < HD / 2; i += 4) {
-            const float4 k4 = *reinterpret_cast<const float4*>(&Ks[buf][l32][half * (HD / 2) + i]);
-            sc = __builtin_amdgcn_mfma_f32_32x32x2f32(k4.x, qreg[i], sc, 0, 0, 0);
-            sc = __builtin_amdgcn_mfma_f32_32x32x2f32(k4.y, qreg[i + 1], sc, 0, 0, 0);
-            sc = __builtin_amdgcn_mfma_f32_32x32x2f32(k4.z, qreg[i + 2], sc, 0, 0, 0);
-            sc = __builtin_amdgcn_mfma_f32_32x32x2f32(k4.w, qreg[i + 3], sc, 0, 0, 0);
-        }
+        attn_tile_scores<HD>(&Ks[buf][l32][0], half, qreg, sc);
         // rel-pos bias: every table load of the tile issued together (REL is a template flag:
         // a runtime `if (rb)` per score became 16 exec-masked branches with a vmcnt(0) each)
         float bias[16];
         if (REL) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int kl = (r & 3) + 8 * (r >> 2) + 4 * half;
+                const int kl = attn_tile_key(r, half);
                 bias[r] = rb[rbh[buf][kl]] + rb[rbw[buf][kl]];
             }
         }
-        float tmax = -INFINITY;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int kl = (r & 3) + 8 * (r >> 2) + 4 * half;
-            const int key = k0 + kl;
+            const int key = k0 + attn_tile_key(r, half);
             float v = sc[r] * a.scale;
             if (REL) v += bias[r];
             if (key >= len || (a.causal && key > q_lane)) v = -INFINITY;
             sc[r] = v;
-            tmax = fmaxf(tmax, v);
         }
-        tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
-        const float m_new = fmaxf(m_run, tmax);
-        const float alpha = (m_new == -INFINITY) ? 1.f : __expf(m_run - m_new);
-        float psum = 0.f;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const float p = (m_new == -INFINITY) ? 0.f : __expf(sc[r] - m_new);
-            sc[r] = p;
-            psum += p;
-        }
-        psum += __shfl_xor(psum, 32, 64);
-        l_run = l_run * alpha + psum;
-        m_run = m_new;
-#pragma unroll
-        for (int t = 0; t < HD / 32; ++t)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) o[t][r] *= alpha;
-        // O^T += V^T . P^T, keys in the accumulator's permuted order kappa(st, half)
-#pragma unroll
-        for (int g4 = 0; g4 < 4; ++g4) {
-            const int kb = 8 * g4 + 4 * half;
-#pragma unroll
-            for (int t = 0; t < HD / 32; ++t) {
-                const float4 v4 = *reinterpret_cast<const float4*>(&Vt[buf][t * 32 + l32][kb]);
-                o[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(v4.x, sc[4 * g4 + 0], o[t], 0, 0, 0);
-                o[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(v4.y, sc[4 * g4 + 1], o[t], 0, 0, 0);
-                o[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(v4.z, sc[4 * g4 + 2], o[t], 0, 0, 0);
-                o[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(v4.w, sc[4 * g4 + 3], o[t], 0, 0, 0);
-            }
-        }
+        attn_tile_softmax<HD>(sc, m_run, l_run, o);
+        // O^T += V^T . P^T, keys in the accumulator's permuted order
+        attn_tile_pv_lds<HD>(&Vt[buf][0][0], half, l32, sc, o);
         AT2_LSTORE(buf ^ 1, k0 + AT_KT);
         __syncthreads();
     }
@@ -337,11 +293,7 @@ __global__ __launch_bounds__(256, 1) void attention_fwd2_kernel(AttnArgs a) {
         if (q_valid) {
             const int npairs = split_first_pair((a.L + 4 * AT_Q - 1) / (4 * AT_Q), a.L);
             float* rec = a.part + ((((long)s * a.heads + h) * npairs + blockIdx.x) * (4 * AT_Q) + (q_lane - qb0)) * (HD + 2);
-            if (half == 0) { rec[0] = m_run; rec[1] = l_run; }
-#pragma unroll
-            for (int t = 0; t < HD / 32; ++t)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) rec[2 + t * 32 + (r & 3) + 8 * (r >> 2) + 4 * half] = o[t][r];
+            attn_rec_write<HD>(rec, 2, half, m_run, l_run, o);
         }
         return;
     }
@@ -351,14 +303,13 @@ __global__ __launch_bounds__(256, 1) void attention_fwd2_kernel(AttnArgs a) {
 #pragma unroll
         for (int t = 0; t < HD / 32; ++t)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) op[t * 32 + (r & 3) + 8 * (r >> 2) + 4 * half] = o[t][r] / l_run;
+            for (int r = 0; r < 16; ++r) op[t * 32 + attn_tile_key(r, half)] = o[t][r] / l_run;
     }
 #undef AT2_GLOAD
 #undef AT2_LSTORE
 }
 
-// combine of the key pieces (SPLIT above): thread (query, d); m = max m_i, l = sum l_i e^(m_i - m),
-// o = sum o_i e^(m_i - m), all in piece order; out = o / l
+// combine of the key pieces (SPLIT above): thread (query, d), the pieces in piece order (attn_rec_combine)
 template <int HD>
 __global__ __launch_bounds__(256) void attention_merge_kernel(AttnArgs a) {
     const int s = blockIdx.z, h = blockIdx.y;
@@ -371,18 +322,9 @@ __global__ __launch_bounds__(256) void attention_merge_kernel(AttnArgs a) {
     const int n = (kend + AT_KSPLIT - 1) / AT_KSPLIT;
     const int npairs = split_first_pair((a.L + 4 * AT_Q - 1) / (4 * AT_Q), a.L);
     const float* rec0 = a.part + ((((long)s * a.heads + h) * npairs + split_first_pair(qb, a.L)) * (4 * AT_Q) + ql) * (HD + 2);
-    const long pstride = (long)(4 * AT_Q) * (HD + 2);
-    float m = -INFINITY;
-    for (int i = 0; i < n; ++i) m = fmaxf(m, rec0[i * pstride]);
-    float l = 0.f, acc = 0.f;
-    for (int i = 0; i < n; ++i) {
-        const float* r = rec0 + i * pstride;
-        const float w = r[0] == -INFINITY ? 0.f : __expf(r[0] - m);
-        l += r[1] * w;
-        acc += r[2 + d] * w;
-    }
     const long ooff = a.o_seq_off ? a.o_seq_off[s] : (long)s * a.L * a.o_row_stride;
-    a.o[ooff + (long)q * a.o_row_stride + (long)h * a.o_head_stride + d] = acc / l;
+    a.o[ooff + (long)q * a.o_row_stride + (long)h * a.o_head_stride + d] =
+        attn_rec_combine(rec0, (long)(4 * AT_Q) * (HD + 2), n, 2, d);
 }
 
 size_t attention_causal_part_floats(int n_seq, int heads, int L, int hd) {

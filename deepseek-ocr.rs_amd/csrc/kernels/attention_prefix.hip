@@ -13,8 +13,8 @@
 //     knows its last visible key: P for an image block, its own last row for a query block.  Tiles past it are
 //     never visited, and keys past it inside the last tile are staged as zeros (nothing is read from them).
 //   * The element mask runs only on the tiles that straddle P or the diagonal; every other tile is all visible.
-//   * The math is attention_fwd2's: S^T = K.Q^T on v_mfma_f32_32x32x2_f32 with the lane's own query in the
-//     accumulator column, P fed to the O^T = V^T.P^T MFMA straight from that accumulator (keys in its permuted
+//   * The math is attention_fwd2's (the shared tile of attn_tile.hpp): S^T = K.Q^T on v_mfma_f32_32x32x2_f32 with
+//     the lane's own query in the accumulator column, P fed to the O^T = V^T.P^T MFMA straight from that accumulator (keys in its permuted
 //     order), online softmax without cross-lane shuffles, tile t + 1 in registers while tile t is consumed.
 //   * Synchronisation is the in-block LDS barrier only (one per tile); the sequences are short (288 / 512 rows),
 //     so the keys are not split across workgroups.
@@ -22,6 +22,7 @@
 #include <cstdint>
 #include <stdexcept>
 
+#include "attn_tile.hpp"
 #include "dev_common.hpp"
 #include "kernels.hpp"
 
@@ -65,14 +66,7 @@ __global__ __launch_bounds__(64 * NW) void attention_prefix_kernel(AttnPrefixArg
     const int q_lane = r0 + l32;
     const bool q_valid = active && q_lane < r1;
     float qreg[HD / 2];
-    {
-        const float* qr = Q + (long)min(q_lane, r1 - 1) * a.ldq + half * (HD / 2);
-#pragma unroll
-        for (int i = 0; i < HD / 2; i += 4) {
-            const float4 v4 = *reinterpret_cast<const float4*>(qr + i);
-            qreg[i] = v4.x; qreg[i + 1] = v4.y; qreg[i + 2] = v4.z; qreg[i + 3] = v4.w;
-        }
-    }
+    attn_tile_load_q<HD>(Q + (long)min(q_lane, r1 - 1) * a.ldq, half, qreg);
     // staging: thread covers float4 f = tid + NT j of the tile (clamped to the last one: a duplicate writes the
     // same value): key f / (HD/4), cols (f % (HD/4)) * 4; keys at or past kend come out as zeros
     // (macros, not lambdas: a captured register array is demoted to scratch)
@@ -112,58 +106,20 @@ __global__ __launch_bounds__(64 * NW) void attention_prefix_kernel(AttnPrefixArg
         if (active) {
             // S^T = K . Q^T: lane (half, l32) feeds dims i + half*HD/2
             f32x16 sc;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) sc[r] = 0.f;
-#pragma unroll
-            for (int i = 0; i < HD / 2; i += 4) {
-                const float4 k4 = *reinterpret_cast<const float4*>(&Ks[buf][l32][half * (HD / 2) + i]);
-                sc = __builtin_amdgcn_mfma_f32_32x32x2f32(k4.x, qreg[i], sc, 0, 0, 0);
-                sc = __builtin_amdgcn_mfma_f32_32x32x2f32(k4.y, qreg[i + 1], sc, 0, 0, 0);
-                sc = __builtin_amdgcn_mfma_f32_32x32x2f32(k4.z, qreg[i + 2], sc, 0, 0, 0);
-                sc = __builtin_amdgcn_mfma_f32_32x32x2f32(k4.w, qreg[i + 3], sc, 0, 0, 0);
-            }
+            attn_tile_scores<HD>(&Ks[buf][l32][0], half, qreg, sc);
             // all of the tile visible to every row of the block: it lies inside the prefix, or the block is a
             // query block and the tile ends at or before its first row (block-uniform)
             const bool all_visible = k0 + AP_KT <= P || (r0 >= P && k0 + AP_KT - 1 <= r0);
-            float tmax = -INFINITY;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int key = k0 + (r & 3) + 8 * (r >> 2) + 4 * half;
+                const int key = k0 + attn_tile_key(r, half);
                 float v = sc[r] * a.scale;
                 if (!all_visible && !(key < P || (q_lane >= P && key <= q_lane))) v = -INFINITY;
                 sc[r] = v;
-                tmax = fmaxf(tmax, v);
             }
-            tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
-            const float m_new = fmaxf(m_run, tmax);
-            const float alpha = (m_new == -INFINITY) ? 1.f : __expf(m_run - m_new);
-            float psum = 0.f;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const float p = (m_new == -INFINITY) ? 0.f : __expf(sc[r] - m_new);
-                sc[r] = p;
-                psum += p;
-            }
-            psum += __shfl_xor(psum, 32, 64);
-            l_run = l_run * alpha + psum;
-            m_run = m_new;
-#pragma unroll
-            for (int t = 0; t < HD / 32; ++t)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) o[t][r] *= alpha;
-            // O^T += V^T . P^T, keys in the accumulator's permuted order kappa(st, half)
-#pragma unroll
-            for (int g4 = 0; g4 < 4; ++g4) {
-                const int kb = 8 * g4 + 4 * half;
-#pragma unroll
-                for (int t = 0; t < HD / 32; ++t) {
-                    const float4 v4 = *reinterpret_cast<const float4*>(&Vt[buf][t * 32 + l32][kb]);
-                    o[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(v4.x, sc[4 * g4 + 0], o[t], 0, 0, 0);
-                    o[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(v4.y, sc[4 * g4 + 1], o[t], 0, 0, 0);
-                    o[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(v4.z, sc[4 * g4 + 2], o[t], 0, 0, 0);
-                    o[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(v4.w, sc[4 * g4 + 3], o[t], 0, 0, 0);
-                }
-            }
+            attn_tile_softmax<HD>(sc, m_run, l_run, o);
+            // O^T += V^T . P^T, keys in the accumulator's permuted order
+            attn_tile_pv_lds<HD>(&Vt[buf][0][0], half, l32, sc, o);
         }
         AP_LSTORE(buf ^ 1);
         __syncthreads();

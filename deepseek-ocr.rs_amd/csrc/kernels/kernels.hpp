@@ -221,7 +221,7 @@ struct AttnPastArgs {
 size_t attention_past_part_floats(int n_seq, int heads, int max_q, int max_total, int hd);
 bool attention_past_ok(const AttnPastArgs& a);
 void launch_attention_past(const AttnPastArgs& a, hipStream_t s);  // throws EINVAL outside the contract
-// The same contract tiled over the queries (attention_chunk.hip), for a chunk of many new rows behind a few hundred
+// The same contract tiled over the queries (attention_chunk_kernel, attention_past.hip), for a chunk of many new rows behind a few hundred
 // keys: one workgroup per (32-query tile, head, sequence), eight waves that each stream every eighth 32-key tile in
 // ascending order with an online softmax of their own and combine their eight records in LDS.  One launch; `part`
 // and `part_floats` are not read.  hd 32, 64 or 128, heads % kv_heads == 0, any n_q[s] >= 1, any past[s] >= 0.

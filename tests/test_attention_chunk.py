@@ -1,4 +1,4 @@
-"""launch_attention_chunk (attention_chunk.hip) through dsocr_k_attention_chunk: the attention of a prefill chunk
+"""launch_attention_chunk (attention_past.hip) through dsocr_k_attention_chunk: the attention of a prefill chunk
 behind a cached past, tiled over the queries, in the form Engine::layer_forward_prefill launches it for a sliced
 admission (RoPE at the shifted positions + KV append + attention into pages [page0, page0 + B) of a session cache).
 
