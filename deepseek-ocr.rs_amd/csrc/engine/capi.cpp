@@ -22,6 +22,7 @@
 
 struct dsocr_engine {
     std::unique_ptr<dsocr::Engine> impl;
+    dsocr::LogitBias staged_bias;  // dsocr_session_stage_logit_bias: consumed by the next admission call
 };
 struct dsocr_page_pixels {
     dsocr::PagePixels px;
@@ -137,6 +138,32 @@ dsocr::GenRequest to_request(const dsocr_request& r) {
     g.page = r.page ? &r.page->px : nullptr;
     g.image_rows = r.image_rows;
     g.n_image_rows = r.n_image_rows;
+    return g;
+}
+// the constraint as the engine takes it, checked against `vocab` (NULL: none)
+dsocr::LogitBias to_bias(const dsocr_logit_bias* lb, size_t vocab) {
+    dsocr::LogitBias b;
+    if (!lb) return b;
+    if (lb->n && (!lb->ids || !lb->values)) throw std::runtime_error("EINVAL: logit bias: NULL ids / values");
+    if (lb->n > vocab) throw std::runtime_error("EINVAL: logit bias: more entries than the vocabulary has ids");
+    b.allow_only = lb->allow_only != 0;
+    b.ids.resize(lb->n);
+    b.values.assign(lb->values, lb->values + lb->n);
+    for (size_t i = 0; i < lb->n; ++i) {
+        if (lb->ids[i] < 0 || lb->ids[i] >= (int64_t)vocab)
+            throw std::runtime_error("EINVAL: logit bias: token id " + std::to_string(lb->ids[i]) + " outside the vocabulary");
+        b.ids[i] = (int)lb->ids[i];
+    }
+    dsocr::validate_logit_bias(b, (int)vocab);
+    return b;
+}
+
+// a session admission's request: the staged constraint moves into it (consumed whatever the admission does)
+dsocr::GenRequest to_admission(dsocr_engine* e, const dsocr_request& r) {
+    dsocr::LogitBias b = std::move(e->staged_bias);
+    e->staged_bias = dsocr::LogitBias();
+    dsocr::GenRequest g = to_request(r);
+    g.bias = std::move(b);
     return g;
 }
 }  // namespace
@@ -440,6 +467,69 @@ dsocr_status dsocr_generate_logprobs(dsocr_engine* e, size_t n, const dsocr_requ
     });
 }
 
+dsocr_status dsocr_logit_bias_check(const dsocr_logit_bias* lb, size_t vocab) {
+    return guarded([&] {
+        if (vocab == 0 || vocab > (size_t)INT32_MAX) throw std::runtime_error("EINVAL: vocab must be 1..2^31 - 1");
+        (void)to_bias(lb, vocab);
+    });
+}
+
+dsocr_status dsocr_generate_logit_bias(dsocr_engine* e, size_t n, const dsocr_request* reqs,
+                                       const dsocr_decode_params* params, dsocr_result* results,
+                                       const dsocr_logit_bias* const* bias, size_t top_k, dsocr_logprobs* lp) {
+    return guarded([&] {
+        if (!e || (!reqs && n) || (!results && n) || !params) throw std::runtime_error("EINVAL: NULL argument");
+        if (top_k > DSOCR_MAX_TOP_LOGPROBS) throw std::runtime_error("EINVAL: top_k above DSOCR_MAX_TOP_LOGPROBS");
+        if (!lp && top_k) throw std::runtime_error("EINVAL: top_k without log-probability buffers");
+        if (lp) {
+            if (!params->use_cache) throw std::runtime_error("EINVAL: log-probabilities need use_cache = 1");
+            for (size_t i = 0; i < n; ++i) {
+                if (!lp[i].token_lp || (top_k && (!lp[i].top_id || !lp[i].top_lp))) throw std::runtime_error("EINVAL: NULL log-probability buffer");
+                if (lp[i].cap < (size_t)params->max_new_tokens) throw std::runtime_error("EINVAL: log-probability buffers hold fewer than max_new_tokens entries");
+            }
+        }
+        const size_t vocab = (size_t)e->impl->cfg().lang.vocab;
+        std::vector<dsocr::GenRequest> rq;
+        for (size_t i = 0; i < n; ++i) {
+            rq.push_back(to_request(reqs[i]));
+            if (bias) rq.back().bias = to_bias(bias[i], vocab);
+        }
+        dsocr::GenParams g = to_params(params);
+        if (lp) g.lp_k = (int)top_k;
+        auto r = e->impl->generate(rq, g, nullptr, nullptr);
+        const dsocr::Engine::LogprobRows& rows = e->impl->last_logprobs();
+        for (size_t i = 0; i < n; ++i) {
+            results[i].status = DSOCR_OK;
+            size_t m = std::min(r[i].size(), results[i].cap);
+            if (results[i].out_ids) std::memcpy(results[i].out_ids, r[i].data(), m * sizeof(int64_t));
+            results[i].n_out = m;
+            if (m < r[i].size()) results[i].status = DSOCR_EINVAL;
+            if (!lp) continue;
+            const size_t ne = rows.n.empty() ? 0 : (size_t)rows.n[i];
+            lp[i].n = ne;
+            for (size_t t = 0; t < ne; ++t) {
+                lp[i].token_lp[t] = rows.lp[i * rows.cap + t];
+                for (size_t k = 0; k < top_k; ++k) {
+                    lp[i].top_id[t * top_k + k] = rows.top_id[(i * rows.cap + t) * top_k + k];
+                    lp[i].top_lp[t * top_k + k] = rows.top_lp[(i * rows.cap + t) * top_k + k];
+                }
+            }
+        }
+    });
+}
+
+dsocr_status dsocr_session_stage_logit_bias(dsocr_engine* e, const dsocr_logit_bias* lb) {
+    return guarded([&] {
+        if (!e) throw std::runtime_error("EINVAL: NULL argument");
+        e->staged_bias = dsocr::LogitBias();
+        dsocr::Engine::SessionInfo si;
+        if (!e->impl->session_info(&si)) throw std::runtime_error("EINVAL: no decode session is open on this engine");
+        dsocr::LogitBias b = to_bias(lb, (size_t)e->impl->cfg().lang.vocab);
+        if (b.active() && !si.logit_bias) throw std::runtime_error("EINVAL: this session was opened without DSOCR_SESSION_LOGIT_BIAS");
+        e->staged_bias = std::move(b);
+    });
+}
+
 // ---- decode sessions
 dsocr_status dsocr_session_open(dsocr_engine* e, size_t slots, size_t max_context, const dsocr_decode_params* params) {
     return guarded([&] {
@@ -453,10 +543,11 @@ dsocr_status dsocr_session_open_ex(dsocr_engine* e, size_t slots, size_t max_con
                                    uint32_t flags) {
     return guarded([&] {
         if (!e) throw std::runtime_error("EINVAL: NULL argument");
-        if (flags & ~(uint32_t)(DSOCR_SESSION_PER_REQUEST | DSOCR_SESSION_LOGPROBS)) throw std::runtime_error("EINVAL: unknown session flags");
+        if (flags & ~(uint32_t)(DSOCR_SESSION_PER_REQUEST | DSOCR_SESSION_LOGPROBS | DSOCR_SESSION_LOGIT_BIAS))
+            throw std::runtime_error("EINVAL: unknown session flags");
         if (slots > 8 || max_context > (size_t)INT32_MAX / 2) throw std::runtime_error("EINVAL: a session has 1..8 slots");
         e->impl->session_open((int)slots, (int)max_context, to_params(params), (flags & DSOCR_SESSION_PER_REQUEST) != 0,
-                                (flags & DSOCR_SESSION_LOGPROBS) != 0);
+                                (flags & DSOCR_SESSION_LOGPROBS) != 0, (flags & DSOCR_SESSION_LOGIT_BIAS) != 0);
     });
 }
 
@@ -464,7 +555,7 @@ dsocr_status dsocr_session_admit_params(dsocr_engine* e, const dsocr_request* re
                                         int* slot) {
     return guarded([&] {
         if (!e || !req) throw std::runtime_error("EINVAL: NULL argument");
-        const int s = e->impl->session_admit(to_request(*req), to_params(params));
+        const int s = e->impl->session_admit(to_admission(e, *req), to_params(params));
         if (slot) *slot = s;
     });
 }
@@ -483,7 +574,7 @@ dsocr_status dsocr_session_admit(dsocr_engine* e, const dsocr_request* req, size
                                  uint64_t seed, int* slot) {
     return guarded([&] {
         if (!e || !req) throw std::runtime_error("EINVAL: NULL argument");
-        const int s = e->impl->session_admit(to_request(*req), max_new_tokens, has_seed != 0, seed);
+        const int s = e->impl->session_admit(to_admission(e, *req), max_new_tokens, has_seed != 0, seed);
         if (slot) *slot = s;
     });
 }
@@ -551,6 +642,7 @@ dsocr_status dsocr_session_info(const dsocr_engine* e, dsocr_session_desc* out) 
         out->out_cap = (size_t)si.out_cap; out->kv_cap = (size_t)si.kv_cap; out->burst_cap = (size_t)si.burst_cap;
         out->steps = si.steps;
         out->flags = (si.per_request ? DSOCR_SESSION_PER_REQUEST : 0u) | (si.logprobs ? DSOCR_SESSION_LOGPROBS : 0u) |
+                     (si.logit_bias ? DSOCR_SESSION_LOGIT_BIAS : 0u) |
                      (si.pending ? DSOCR_SESSION_ADMIT_PENDING : 0u);
     });
 }
@@ -577,7 +669,7 @@ dsocr_status dsocr_session_admit_prefix(dsocr_engine* e, int handle, const dsocr
                                         const dsocr_decode_params* params, int* slot) {
     return guarded([&] {
         if (!e || !req) throw std::runtime_error("EINVAL: NULL argument");
-        const int s = e->impl->session_admit_prefix(handle, to_request(*req), to_params(params));
+        const int s = e->impl->session_admit_prefix(handle, to_admission(e, *req), to_params(params));
         if (slot) *slot = s;
     });
 }
@@ -588,7 +680,7 @@ dsocr_status dsocr_session_admit_begin(dsocr_engine* e, const dsocr_request* req
     return guarded([&] {
         if (!e || !req) throw std::runtime_error("EINVAL: NULL argument");
         const int rows = (int)std::min(chunk_rows, (size_t)INT32_MAX);
-        const int t = e->impl->session_admit_begin(to_request(*req), to_params(params), rows);
+        const int t = e->impl->session_admit_begin(to_admission(e, *req), to_params(params), rows);
         if (ticket) *ticket = t;
     });
 }
@@ -1974,6 +2066,49 @@ static void k_logprobs(int B, int V, int K, const float* logits, int ld, const i
         throw;
     }
     for (void* p : bufs) (void)hipFree(p);
+}
+
+dsocr_status dsocr_k_logit_bias(int B, int V, int ld, int offset, float* logits, const int64_t* ids, const float* values,
+                                const int* first, const int* count, const int* flags, const int* allow_only,
+                                float* dense, int dense_ld) {
+    return guarded([&] {
+        if (B <= 0 || V <= 0 || ld < V || offset < 0 || !logits || !first || !count || !flags || !allow_only || !dense)
+            throw std::runtime_error("EINVAL: bad logit bias hook arguments");
+        if ((long)dense_ld != dsocr::logit_bias_ld(V)) throw std::runtime_error("EINVAL: dense_ld must be (V + 3) / 4 * 4");
+        size_t total = 0;
+        for (int b = 0; b < B; ++b) {
+            if (first[b] < 0 || count[b] < 0 || count[b] > V) throw std::runtime_error("EINVAL: bad list range");
+            total = std::max(total, (size_t)first[b] + (size_t)count[b]);
+        }
+        if (total && (!ids || !values)) throw std::runtime_error("EINVAL: NULL list");
+        std::vector<int> h_ids(total);
+        for (size_t i = 0; i < total; ++i) h_ids[i] = (int)std::min<int64_t>(std::max<int64_t>(ids[i], -1), INT32_MAX);
+        const size_t nl = (size_t)B * ld, nd = (size_t)B * dense_ld;
+        dsocr::DeviceBuffer d_logits((nl + (size_t)offset + 4) * 4), d_dense(nd * 4), d_on((size_t)B * 4),
+            d_ids(std::max<size_t>(total, 1) * 4), d_vals(std::max<size_t>(total, 1) * 4);
+        float* lg = (float*)d_logits.get() + offset;
+        check_hip(hipMemcpy(lg, logits, nl * 4, hipMemcpyHostToDevice), "hipMemcpy H2D");
+        check_hip(hipMemset(d_dense.get(), 0, nd * 4), "hipMemset");
+        check_hip(hipMemset(d_on.get(), 0, (size_t)B * 4), "hipMemset");
+        if (total) {
+            check_hip(hipMemcpy(d_ids.get(), h_ids.data(), total * 4, hipMemcpyHostToDevice), "hipMemcpy H2D");
+            check_hip(hipMemcpy(d_vals.get(), values, total * 4, hipMemcpyHostToDevice), "hipMemcpy H2D");
+        }
+        for (int b = 0; b < B; ++b) {
+            dsocr::LogitBiasBuildArgs a;
+            a.row = (float*)d_dense.get() + (size_t)b * dense_ld; a.V = V; a.ld = dense_ld;
+            a.ids = (const int*)d_ids.get() + first[b]; a.values = (const float*)d_vals.get() + first[b]; a.n = count[b];
+            a.allow_only = allow_only[b]; a.on = (int*)d_on.get() + b; a.on_value = flags[b] ? 1 : 0;
+            dsocr::launch_logit_bias_build(a, nullptr);
+        }
+        dsocr::DecBiasArgs d;
+        d.logits = lg; d.B = B; d.V = V; d.ld = ld; d.bias = (const float*)d_dense.get(); d.bias_ld = dense_ld;
+        d.on = (const int*)d_on.get();
+        dsocr::launch_dec_logit_bias(d, nullptr);
+        check_hip(hipDeviceSynchronize(), "logit bias");
+        check_hip(hipMemcpy(logits, lg, nl * 4, hipMemcpyDeviceToHost), "hipMemcpy D2H");
+        check_hip(hipMemcpy(dense, d_dense.get(), nd * 4, hipMemcpyDeviceToHost), "hipMemcpy D2H");
+    });
 }
 
 dsocr_status dsocr_k_logprobs(int B, int V, int K, const float* logits, int ld, const int* tok, const uint8_t* emit,

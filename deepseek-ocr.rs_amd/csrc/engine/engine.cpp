@@ -172,7 +172,9 @@ struct Engine::Session {
     bool screened = false;  // fixed parameters: the screened head at every n (else the exact head at every n)
     int* stage = nullptr;   // ss_stage: an admission's staged slot rows
     bool logprobs = false;  // every step and admission writes log-probability entries (s_lp*): the exact head at every n
+    bool logit_bias = false;  // every slot has a dense bias row (s_bias); a burst with a constrained slot runs the exact head
     struct Slot {
+        bool biased = false;  // the slot's device flag (rows_.bias_on): its request carried a constraint
         size_t max_new = 0;
         int kv_pos = 0;    // the device kv_pos of the slot: prompt + steps replayed since its admission
         int reported = 0;  // tokens the polls have handed out
@@ -1745,6 +1747,7 @@ void Engine::decode_head(int B, DecSampleArgs& sa, const SampleArgs& pen, bool s
     const int H = L.hidden;
     float* SX = rows_.x;
     if (screened && lp) throw std::runtime_error("EINTERNAL: log-probabilities need the exact head");
+    if (screened && rows_.bias && !sess_) throw std::runtime_error("EINTERNAL: a logit bias needs the exact head");
     if (screened) {
         // screened selection: int8 lm_head intervals + running threshold, exact rescoring of the
         // few kept rows — the exact path's token from half the lm_head bytes
@@ -1771,6 +1774,7 @@ void Engine::decode_head(int B, DecSampleArgs& sa, const SampleArgs& pen, bool s
     }
     launch_dec_gemv(g, st);
     if (trace_) launch_trace_logits(sa.logits, B, L.vocab, sa.ld, sa.out_len, sa.done, trace_, trace_steps_, st);
+    if (rows_.bias) launch_dec_logit_bias(bias_args(sa, 0), st);  // l' = l + b: what everything below reads
     if (lp) launch_dec_lp_partial(*lp, st);
     launch_rep_penalty(pen, st);
     launch_dec_sample(sa, st);
@@ -1862,6 +1866,13 @@ void Engine::reserve_decode_rows(const DecodeRowsSpec& spec) {
             if (r.lp_side) HIP_CHECK(hipMemsetAsync(r.lp_side, 0, sizeof(float) * R * r.ctx_cap, st));
         }
     }
+    if (spec.bias) {  // (the dense rows are written by launch_logit_bias_build before a flag is set)
+        r.bias_ld = logit_bias_ld(V);
+        r.bias = wsf("s_bias", (size_t)S * r.bias_ld);
+        r.bias_on = ints("s_biason", S, true);
+        r.bias_stage_cap = std::max<size_t>(spec.bias_stage, 1);
+        r.bias_stage = wsi("s_biasstage", 2 * r.bias_stage_cap);
+    }
 }
 
 // The fused one-page launch takes q / k / v by polling its hand-off row, and the attention merge polls its records:
@@ -1920,6 +1931,53 @@ DecLpArgs Engine::lp_args(const DecSampleArgs& sa, int row0) {
     return a;
 }
 
+DecBiasArgs Engine::bias_args(const DecSampleArgs& sa, int row0) {
+    const DecodeRows& r = rows_;
+    DecBiasArgs a;
+    a.logits = const_cast<float*>(sa.logits); a.B = sa.B; a.V = sa.V; a.ld = sa.ld;
+    a.bias = r.bias + (size_t)row0 * r.bias_ld; a.bias_ld = r.bias_ld; a.on = r.bias_on + row0;
+    return a;
+}
+
+void validate_logit_bias(const LogitBias& lb, int vocab) {
+    const size_t n = lb.ids.size();
+    if (lb.values.size() != n) throw std::runtime_error("EINVAL: logit bias: ids and values differ in length");
+    if (n > (size_t)vocab) throw std::runtime_error("EINVAL: logit bias: more entries than the vocabulary has ids");
+    if (lb.allow_only && n == 0) throw std::runtime_error("EINVAL: logit bias: allow_only with an empty list permits no token");
+    std::vector<uint8_t> seen((size_t)vocab, 0);
+    for (size_t i = 0; i < n; ++i) {
+        const int t = lb.ids[i];
+        if (t < 0 || t >= vocab) throw std::runtime_error("EINVAL: logit bias: token id " + std::to_string(t) + " outside the vocabulary");
+        if (seen[t]) throw std::runtime_error("EINVAL: logit bias: duplicate token id " + std::to_string(t));
+        seen[t] = 1;
+        const float v = lb.values[i];
+        if (std::isnan(v) || v == INFINITY) throw std::runtime_error("EINVAL: logit bias: a value is NaN or +inf");
+    }
+}
+
+// One row's list over PCIe ([ids | values], pinned staging under "s_biasstage"), then the fill + scatter on the
+// stream.  The caller synchronises before the staging region is reused
+void Engine::build_logit_bias(const LogitBias& lb, int row, size_t stage_off) {
+    const DecodeRows& r = rows_;
+    if (!r.bias) throw std::runtime_error("EINTERNAL: no logit bias rows are reserved");
+    const size_t n = lb.ids.size(), cap = r.bias_stage_cap;
+    if (stage_off + n > cap) throw std::runtime_error("EINTERNAL: logit bias staging buffer too small");
+    LogitBiasBuildArgs a;
+    a.row = r.bias + (size_t)row * r.bias_ld; a.V = cfg_.lang.vocab; a.ld = r.bias_ld;
+    a.on = r.bias_on + row; a.on_value = lb.active() ? 1 : 0; a.allow_only = lb.allow_only ? 1 : 0;
+    if (a.on_value && n) {
+        int* h = (int*)pinned("s_biasstage", 2 * cap * sizeof(int));
+        std::memcpy(h + stage_off, lb.ids.data(), n * sizeof(int));
+        std::memcpy(h + cap + stage_off, lb.values.data(), n * sizeof(float));
+        HIP_CHECK(hipMemcpyAsync(r.bias_stage + stage_off, h + stage_off, n * sizeof(int), hipMemcpyHostToDevice, stream_));
+        HIP_CHECK(hipMemcpyAsync(r.bias_stage + cap + stage_off, h + cap + stage_off, n * sizeof(float), hipMemcpyHostToDevice, stream_));
+        a.ids = r.bias_stage + stage_off;
+        a.values = reinterpret_cast<const float*>(r.bias_stage + cap + stage_off);
+        a.n = (int)n;
+    }
+    launch_logit_bias_build(a, stream_);
+}
+
 // rand_core 0.6.4 SeedableRng::seed_from_u64 for ChaCha12Rng (rand 0.8.5 StdRng): the 32-byte key
 // is filled by PCG32 (state advanced first, XSH-RR output, little-endian words); block counter 0,
 // stream 0, empty result buffer (sampling.hip reads this layout)
@@ -1967,6 +2025,15 @@ std::vector<std::vector<int64_t>> Engine::generate(const std::vector<GenRequest>
     if (p.lp_k > LP_MAX_TOP) throw std::runtime_error("EINVAL: at most 20 alternatives per token (DSOCR_MAX_TOP_LOGPROBS)");
     if (p.lp_k >= 0 && !p.use_cache) throw std::runtime_error("EINVAL: log-probabilities need the K/V cache (use_cache = 1)");
     last_lp_ = LogprobRows();
+    // constraints: every check before any device work
+    bool any_bias = false;
+    for (const GenRequest& rq : reqs) {
+        if (!rq.bias.active()) continue;
+        any_bias = true;
+        validate_logit_bias(rq.bias, cfg_.lang.vocab);
+    }
+    if (any_bias && (!p.use_cache || p.trace))
+        throw std::runtime_error("EINVAL: a logit bias needs the K/V cache (use_cache = 1) and no logits trace");
     if (reqs.empty() || p.max_new == 0) return std::vector<std::vector<int64_t>>(reqs.size());
     ensure_small(std::max((int)reqs.size(), 64));
     GenState g(reqs, p, cb, user);
@@ -2165,12 +2232,19 @@ void Engine::reset_decode_state(GenState& g) {
     spec.rows = B; spec.Lcap = g.max_p + (int)p.max_new + 1; spec.ctx_cap = spec.Lcap; spec.out_cap = (long)p.max_new;
     spec.sampler = p.do_sample;
     // the screened head (exact lm_head instead while sampling, tracing or keeping log-probabilities)
-    spec.ban = !p.do_sample && !p.trace && p.lp_k < 0 && screen_applies(B, p.rep_penalty);
+    // a constrained page: the exact head too, with the bias rows and one staging region per list
+    for (const GenRequest& rq : g.reqs)
+        if (rq.bias.active()) { spec.bias = true; spec.bias_stage += rq.bias.ids.size(); }
+    spec.ban = !p.do_sample && !p.trace && p.lp_k < 0 && !spec.bias && screen_applies(B, p.rep_penalty);
     spec.lp_k = p.lp_k; spec.lp_side = rep_penalty_active(p.rep_penalty);
     ensure_rope(spec.Lcap + 1);
     reserve_decode_rows(spec);
     // one page: the persistent decode step (its granules: no tag of an earlier generate may match this one's)
     persist_active_ = p.use_cache && persist_ok(B, spec.Lcap);
+    if (persist_active_ && spec.bias) {
+        persist_active_ = false;
+        throw std::runtime_error("EINVAL: a logit bias does not combine with the persistent decode step (DSOCR_PERSIST)");
+    }
     if (persist_active_) {
         ensure_persist();
         HIP_CHECK(hipMemsetAsync(persist_g_, 0xff, dec_persist_granules(cfg_.lang.layers) * 8, stream_));
@@ -2300,6 +2374,15 @@ void Engine::init_sampling(GenState& g) {
         launch_trace_logits(r.logits, B, L.vocab, L.vocab, r.out_len, r.done, trace_, trace_steps_, st);
     }
     // log-probabilities: the exact head (no ban rows), an entry for the prefill's own selection too
+    // constraints: every page's dense row from its list, then the add on the prefill's logits
+    if (r.bias) {
+        size_t off = 0;
+        for (int b = 0; b < B; ++b) {
+            build_logit_bias(g.reqs[b].bias, b, off);
+            off += g.reqs[b].bias.ids.size();
+        }
+        launch_dec_logit_bias(bias_args(sa, 0), st);
+    }
     const DecLpArgs lp = p.lp_k >= 0 ? lp_args(sa, 0) : DecLpArgs();
     if (p.lp_k >= 0) launch_dec_lp_partial(lp, st);
     // the fused selection kernel advances the KV position; after the prefill the first
@@ -2585,7 +2668,7 @@ static RowParams resolve_row_params(const GenParams& p) {
     return r;
 }
 
-void Engine::session_open(int S, int max_context, const GenParams& p, bool per_request, bool logprobs) {
+void Engine::session_open(int S, int max_context, const GenParams& p, bool per_request, bool logprobs, bool logit_bias) {
     if (sess_) throw std::runtime_error("EINVAL: a decode session is already open on this engine");
     if (S < 1 || S > 8) throw std::runtime_error("EINVAL: a session has 1..8 slots");
     if (!p.use_cache || p.trace) throw std::runtime_error("EINVAL: a session decodes with the K/V cache and without a logits trace");
@@ -2601,6 +2684,7 @@ void Engine::session_open(int S, int max_context, const GenParams& p, bool per_r
     Session& s = *sp;
     s.S = S; s.max_context = max_context; s.p = p; s.per_request = per_request;
     s.logprobs = logprobs;
+    s.logit_bias = logit_bias;
     // Capacity invariant.  The selection kernels advance kv_pos of every row on every step, done or not, so a
     // finished page that waits for the end of its burst keeps appending K/V rows.  A page is admitted only with
     // prompt + max_new + 1 <= max_context and produces its last token at kv_pos <= prompt + max_new - 1; it is
@@ -2620,6 +2704,10 @@ void Engine::session_open(int S, int max_context, const GenParams& p, bool per_r
     spec.rowpar = true;
     spec.handoff_max = true;  // the step runs at every n <= S
     spec.zero_fill = true;    // the dry steps below read kv_pos 0 and a zero input row
+    if (logit_bias) {         // every slot's row, and one admission's list at a time (at most vocab pairs)
+        spec.bias = true;
+        spec.bias_stage = (size_t)L.vocab;
+    }
     if (logprobs) {  // (the raw logits at the context ids too where a penalty can apply)
         spec.lp_k = LP_MAX_TOP;
         spec.lp_side = per_request || rep_penalty_active(p.rep_penalty);
@@ -2683,6 +2771,10 @@ void Engine::session_admit_checks(const Session& s, const GenRequest& rq, const 
             rp.rep_penalty != q.rep_penalty || rp.ngram != q.ngram || rp.eos != q.eos || rp.ignore_eos != q.ignore_eos)
             throw std::runtime_error("EINVAL: this session's parameters are fixed (only max_new_tokens and the seed vary "
                                      "per request): open it with DSOCR_SESSION_PER_REQUEST");
+    }
+    if (rq.bias.active()) {
+        if (!s.logit_bias) throw std::runtime_error("EINVAL: this session was opened without DSOCR_SESSION_LOGIT_BIAS");
+        validate_logit_bias(rq.bias, V);
     }
     if (s.pending) throw std::runtime_error("EINVAL: a chunked admission is pending (advance it to the end or cancel it)");
     if (s.n >= s.S) throw std::runtime_error("EINVAL: every session slot is in use (retire one first)");
@@ -2771,6 +2863,10 @@ int Engine::session_admit_tail(Session& s, const GenRequest& rq, const GenParams
         lp = lp_args(sa, slot);
     }
     launch_session_slot_init(ia, st);
+    if (s.logit_bias) {  // the slot's constraint (none: the flag alone is cleared), then the add on the prefill's logits
+        build_logit_bias(rq.bias, slot, 0);
+        launch_dec_logit_bias(bias_args(sa, slot), st);
+    }
     if (s.logprobs) launch_dec_lp_partial(lp, st);
     launch_rep_penalty(pen, st);
     launch_dec_sample(sa, st);  // the first token, its embedding into the slot's s_x row, the ban list
@@ -2781,6 +2877,7 @@ int Engine::session_admit_tail(Session& s, const GenRequest& rq, const GenParams
     }
     Session::Slot& sl = s.slot[slot];
     sl.max_new = max_new; sl.kv_pos = (int)P; sl.reported = 0; sl.rp = row; sl.prompt = (int)P;
+    sl.biased = rq.bias.active();
     sl.ids = rq.ids;
     sl.mask = rq.mask.empty() ? std::vector<uint8_t>(P, 0) : rq.mask;
     if (at < 0) ++s.n;
@@ -3007,6 +3104,8 @@ void Engine::session_step_body(Session& s, bool screened) {
 // active slots does (admit, retire), and the ban rows both final kernels keep make the change a step boundary
 bool Engine::session_head_screened(const Session& s) const {
     if (s.logprobs) return false;  // the screened head never forms the logits
+    for (int b = 0; b < s.n; ++b)
+        if (s.slot[b].biased) return false;  // ... which a constraint is added to
     if (!s.per_request) return s.screened;
     for (int b = 0; b < s.n; ++b)
         if (s.slot[b].rp.do_sample || s.slot[b].rp.rep_penalty != 1.0f) return false;
@@ -3112,6 +3211,12 @@ void Engine::session_slot_move(Session& s, int src, int dst, int rows_bound) {
     if (s.per_request) m.rowpar = r.rowpar;
     if (s.logprobs) { m.lp = r.lp; m.lp_top_id = r.lp_top_id; m.lp_top = r.lp_top; m.lp_k = r.lp_k; }
     launch_session_slot_move(m, stream_);
+    if (s.logit_bias) {  // the constraint travels as a copy of its row (an unconstrained page: the flag alone)
+        if (s.slot[src].biased)
+            HIP_CHECK(hipMemcpyAsync(r.bias + (size_t)dst * r.bias_ld, r.bias + (size_t)src * r.bias_ld,
+                                     sizeof(float) * r.bias_ld, hipMemcpyDeviceToDevice, stream_));
+        HIP_CHECK(hipMemcpyAsync(r.bias_on + dst, r.bias_on + src, sizeof(int), hipMemcpyDeviceToDevice, stream_));
+    }
     s.slot[dst] = s.slot[src];
 }
 
@@ -3165,6 +3270,7 @@ bool Engine::session_info(SessionInfo* out) const {
         out->steps_screened = sess_->head_steps[1]; out->steps_exact = sess_->head_steps[0];
         out->per_request = sess_->per_request;
         out->logprobs = sess_->logprobs;
+        out->logit_bias = sess_->logit_bias;
         out->chunk_attn_launches = chunk_attn_launches_;
         if (const PendingAdmit* pa = sess_->pending.get()) {
             out->pending = true;

@@ -128,7 +128,19 @@ struct Timings {
     double vision_flops = 0, prefill_flops = 0;
 };
 
+// One request's constraint on the tokens it may emit: the logits row becomes l + b with
+// b[ids[i]] = values[i] and, elsewhere, 0 or (allow_only) -inf.  Checked by validate_logit_bias before any device work.
+struct LogitBias {
+    std::vector<int> ids;
+    std::vector<float> values;
+    bool allow_only = false;
+    bool active() const { return allow_only || !ids.empty(); }
+};
+// EINVAL: an id outside [0, vocab), a duplicate id, a NaN or +inf value, allow_only without ids, more ids than vocab
+void validate_logit_bias(const LogitBias& lb, int vocab);
+
 struct GenRequest {
+    LogitBias bias;
     std::vector<int> ids;
     std::vector<uint8_t> mask;
     const PagePixels* page = nullptr;
@@ -178,6 +190,12 @@ struct DecodeRows {
     int lp_k = -1;
     float *lp = nullptr, *lp_top = nullptr, *lp_side = nullptr, *lp_pmax = nullptr, *lp_psum = nullptr, *lp_ptv = nullptr;
     int *lp_top_id = nullptr, *lp_rec = nullptr, *lp_pti = nullptr;
+    // logit bias rows (spec.bias): the dense rows [S][bias_ld], the per-row flag, and the staging buffer an
+    // admission's sparse list is uploaded to ([ids | values], bias_stage_cap pairs)
+    float* bias = nullptr;
+    long bias_ld = 0;
+    int *bias_on = nullptr, *bias_stage = nullptr;
+    size_t bias_stage_cap = 0;
 };
 // What a caller of Engine::reserve_decode_rows asks for
 struct DecodeRowsSpec {
@@ -188,6 +206,8 @@ struct DecodeRowsSpec {
     bool zero_fill = false;    // the cache and the per-row state start as zeros (else the caller uploads the rows)
     int lp_k = -1;             // >= 0: log-probability rows with lp_k alternatives
     bool lp_side = false;      // ... and the raw logits at the context ids
+    bool bias = false;         // logit bias rows (every flag starts 0) ...
+    size_t bias_stage = 0;     // ... and a list staging buffer of this many (id, value) pairs
 };
 typedef void (*TokenCb)(size_t, const int64_t*, void*);
 // rand_core seed_from_u64 for rand 0.8.5 StdRng, in the layout sampling.hip reads (RNG_WORDS words)
@@ -272,6 +292,7 @@ class Engine {
         size_t steps_screened = 0, steps_exact = 0;  // ... under the screened / the exact lm_head + selection
         bool per_request = false;
         bool logprobs = false;
+        bool logit_bias = false;
         // a chunked admission in flight (session_admit_begin): prompt rows prefilled so far / in all, slices run
         bool pending = false;
         int pending_rows_done = 0, pending_rows_total = 0, pending_slices = 0;
@@ -287,7 +308,10 @@ class Engine {
     // per slot, read by the per-row selection kernels); the head is chosen per burst: screened while every active
     // slot is greedy without a penalty, else the exact head with both selectors
     // logprobs: every slot keeps out_cap x LP_MAX_TOP log-probability entries; the exact head runs at every n
-    void session_open(int slots, int max_context, const GenParams& p, bool per_request = false, bool logprobs = false);
+    // logit_bias: every slot keeps a dense bias row; an admission may carry a constraint (GenRequest::bias), and a
+    // burst runs the exact head iff an active slot carries one
+    void session_open(int slots, int max_context, const GenParams& p, bool per_request = false, bool logprobs = false,
+                      bool logit_bias = false);
     // entries [first, first + count) of a live slot, trimmed to top_k <= LP_MAX_TOP alternatives ([count][top_k])
     void session_logprobs(int slot, size_t first, size_t count, int top_k, float* token_lp, int64_t* top_id, float* top_lp);
     int session_admit(const GenRequest& rq, size_t max_new, bool seed_set, uint64_t seed);
@@ -374,6 +398,11 @@ class Engine {
     void sample_args(int B, int slot0, const GenParams& p, bool per_request, DecSampleArgs& sa, SampleArgs& pen);
     // the log-probability rows of the pages from row0 on that sa selects for
     DecLpArgs lp_args(const DecSampleArgs& sa, int row0);
+    // the logit bias rows of the same pages (only where rows_.bias is set)
+    DecBiasArgs bias_args(const DecSampleArgs& sa, int row0);
+    // row `row`'s dense bias row and flag from the constraint (an inactive one clears the flag); `stage_off`: where
+    // in the staging buffer its list goes (pairs)
+    void build_logit_bias(const LogitBias& lb, int row, size_t stage_off);
     void decode_head(int B, DecSampleArgs& sa, const SampleArgs& pen, bool screened, const DecLpArgs* lp = nullptr);
     void reserve_head_ws(int B);
     LmHeadQ8Args head_q8_args(int B);

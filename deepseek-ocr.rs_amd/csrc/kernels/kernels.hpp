@@ -650,6 +650,29 @@ struct DecLpArgs {
 size_t dec_lp_chunks(int V);
 void launch_dec_lp_partial(const DecLpArgs& a, hipStream_t s);
 void launch_dec_lp_final(const DecLpArgs& a, hipStream_t s);
+// Per-request logit bias and token allow / deny sets (decode_bias.hip): row b of the exact head's f32
+// logits becomes l + bias[b] where on[b] != 0; a row with on[b] == 0 is neither read nor written.  The dense rows
+// [rows][bias_ld] (bias_ld = logit_bias_ld(V): every row 16-byte aligned) are built at admission from the request's
+// sparse list, outside the captured step.
+inline long logit_bias_ld(int V) { return ((long)V + 3) / 4 * 4; }
+// One row: filled with 0 (allow_only == 0) or -inf over [0, V) (0 over the pad [V, ld)), then values[i] stored at
+// ids[i] (unique, in [0, V): checked on the host; an id outside is skipped), and *on = on_value.  on_value == 0
+// writes the flag alone.  ids / values are device pointers.
+struct LogitBiasBuildArgs {
+    float* row = nullptr; int V = 0; long ld = 0;
+    const int* ids = nullptr; const float* values = nullptr; int n = 0;
+    int allow_only = 0;
+    int* on = nullptr; int on_value = 0;
+};
+void launch_logit_bias_build(const LogitBiasBuildArgs& a, hipStream_t s);
+// The add of the step: grid (chunks of 2048 of V, B), after the lm_head and before launch_dec_lp_partial /
+// launch_rep_penalty.  Columns [V, ld) of the logits are not written.
+struct DecBiasArgs {
+    float* logits = nullptr; int B = 0, V = 0; long ld = 0;
+    const float* bias = nullptr; long bias_ld = 0;
+    const int* on = nullptr;  // [B]
+};
+void launch_dec_logit_bias(const DecBiasArgs& a, hipStream_t s);
 // Decode sessions (session.hip).  One page's decode state from slot src to slot dst (src != dst) in one launch:
 // K / V rows [0, min(kv_len[src], rows_bound)) of every layer and kv head (f32 caches [layers][slots][kv_heads]
 // [cap_rows][hd] with the given strides in floats; 16-byte nontemporal loads and stores, hd % 4 == 0), the whole

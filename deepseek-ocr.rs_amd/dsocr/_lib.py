@@ -83,6 +83,12 @@ class LogprobsC(C.Structure):
                 ("cap", C.c_size_t), ("n", C.c_size_t)]
 
 
+class LogitBiasC(C.Structure):
+    """dsocr_logit_bias: one request's constraint (host pointers)."""
+    _fields_ = [("ids", C.POINTER(C.c_int64)), ("values", C.POINTER(C.c_float)), ("n", C.c_size_t),
+                ("allow_only", C.c_int)]
+
+
 class RowParamsC(C.Structure):
     """dsocr_row_params: one row of dsocr_k_select_rows."""
     _fields_ = [("do_sample", C.c_int), ("temperature", C.c_double), ("top_p", C.c_double), ("top_k", C.c_size_t),
@@ -103,6 +109,7 @@ class ScreenStepsC(C.Structure):
 
 SESSION_PER_REQUEST = 1  # DSOCR_SESSION_PER_REQUEST
 SESSION_LOGPROBS = 2     # DSOCR_SESSION_LOGPROBS
+SESSION_LOGIT_BIAS = 4   # DSOCR_SESSION_LOGIT_BIAS
 SESSION_ADMIT_PENDING = 0x100  # DSOCR_SESSION_ADMIT_PENDING (dsocr_session_info flags while an admission is pending)
 MAX_TOP_LOGPROBS = 20    # DSOCR_MAX_TOP_LOGPROBS
 
@@ -145,6 +152,7 @@ EXPORTS = [
     "dsocr_k_lmhead_screen_steps", "dsocr_k_lmhead_screen_grid",
     "dsocr_session_admit_begin", "dsocr_session_admit_advance", "dsocr_session_admit_cancel",
     "dsocr_session_admit_progress", "dsocr_k_attention_chunk",
+    "dsocr_logit_bias_check", "dsocr_generate_logit_bias", "dsocr_session_stage_logit_bias", "dsocr_k_logit_bias",
 ]
 
 # model variants behind the deepseek engine (dsocr_engine_variant)
@@ -286,6 +294,11 @@ def lib():
     L.dsocr_k_logprobs_penalty.argtypes = [i32, i32, i32, vp, i32, vp, vp, vp, i32, vp, f32, vp, vp, vp]
     L.dsocr_k_session_slot_move.argtypes = [i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, C.c_longlong, vp, vp,
                                             C.c_longlong, vp, vp, vp, vp, i32, vp, C.c_longlong, vp, i32, i32, i32]
+    L.dsocr_logit_bias_check.argtypes = [C.POINTER(LogitBiasC), sz]
+    L.dsocr_generate_logit_bias.argtypes = [vp, sz, C.POINTER(RequestC), C.POINTER(DecodeParamsC), C.POINTER(ResultC),
+                                            C.POINTER(C.POINTER(LogitBiasC)), sz, C.POINTER(LogprobsC)]
+    L.dsocr_session_stage_logit_bias.argtypes = [vp, C.POINTER(LogitBiasC)]
+    L.dsocr_k_logit_bias.argtypes = [i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32]
     _lib = L
     return L
 

@@ -93,6 +93,12 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--logprobs", type=int, default=None, metavar="K",
                    help="after the text, one JSON line per generated token: its id, its log-probability and the K "
                         "(0..20) most likely alternatives")
+    p.add_argument("--ban-token", dest="ban_tokens", action="append", type=int, default=[], metavar="ID",
+                   help="never emit this token id (repeatable)")
+    p.add_argument("--allow-tokens-file", metavar="PATH",
+                   help="emit only the token ids listed in this file, one id per line (blank lines and # comments skipped)")
+    p.add_argument("--logit-bias", dest="logit_biases", action="append", default=[], metavar="ID=VALUE",
+                   help="add VALUE to the logit of token ID before every selection (repeatable)")
     p.add_argument("--slots", type=int, default=0, metavar="N",
                    help="treat every --image as its own one-page document (the prompt has one <image>) and decode them "
                         "together in a session of N slots (1..8); results print in input order.  0 = off")
@@ -186,6 +192,48 @@ def _event(stage: str, ms: float, **fields) -> dict:
             "fields": [{"key": k, "value": v} for k, v in fields.items()]}
 
 
+def token_constraint(args) -> dict:
+    """--ban-token / --allow-tokens-file / --logit-bias as the keywords of ``engine.decode`` ({} when none is given).
+    Syntax errors are reported here, before any load; ids are checked against the vocabulary by ``decode``."""
+    kw = {}
+    bias = {}
+    for item in getattr(args, "logit_biases", None) or []:
+        k, sep, v = item.partition("=")
+        try:
+            if not sep:
+                raise ValueError
+            t, f = int(k), float(v)
+        except ValueError:
+            raise DsocrError(1, f"--logit-bias takes ID=VALUE (an integer id, a number), not {item!r}") from None
+        if t in bias:
+            raise DsocrError(1, f"--logit-bias names token {t} twice")
+        bias[t] = f
+    if bias:
+        kw["logit_bias"] = bias
+    if getattr(args, "ban_tokens", None):
+        kw["banned_token_ids"] = list(args.ban_tokens)
+    path = getattr(args, "allow_tokens_file", None)
+    if path:
+        ids = []
+        try:
+            with open(path, encoding="utf-8") as f:
+                for n, line in enumerate(f, 1):
+                    text = line.split("#", 1)[0].strip()
+                    if text:
+                        try:
+                            ids.append(int(text))
+                        except ValueError:
+                            raise DsocrError(1, f"{path}:{n}: {text!r} is not a token id") from None
+        except OSError as e:
+            raise DsocrError(2, f"cannot read --allow-tokens-file {path}: {e}") from None
+        if not ids:
+            raise DsocrError(1, f"--allow-tokens-file {path} lists no token id")
+        kw["allowed_token_ids"] = ids
+    if kw and getattr(args, "slots", 0):
+        raise DsocrError(1, "--ban-token / --allow-tokens-file / --logit-bias apply to one document: not with --slots")
+    return kw
+
+
 def check_admit_chunk(args) -> None:
     """--admit-chunk is a setting of the decode session: refused without --slots and below 32 rows, before any load."""
     rows = int(getattr(args, "admit_chunk", 0) or 0)
@@ -199,6 +247,7 @@ def run_inference(args, out=sys.stdout, err=sys.stderr) -> int:
             print(msg, file=err, flush=True)
 
     check_admit_chunk(args)
+    constraint = token_constraint(args)
     prompt_raw = load_prompt(args)
     if args.model in PADDLE_IDS:
         return run_paddle(args, prompt_raw, out, err)
@@ -248,10 +297,12 @@ def run_inference(args, out=sys.stdout, err=sys.stderr) -> int:
         lp_k = getattr(args, "logprobs", None)
         if lp_k is not None and not 0 <= lp_k <= 20:
             raise DsocrError(1, "--logprobs takes 0..20")
-        if lp_k is None:
+        if lp_k is None and not constraint:
             outcome = engine.decode(tokenizer, prompt, images, vision, params, None if args.quiet else on_token)
+        elif lp_k is None:  # a constrained decode does not stream: the text is written once, below
+            outcome = engine.decode(tokenizer, prompt, images, vision, params, None, **constraint)
         else:  # the entries arrive with the ids: the text is written once, below
-            outcome = engine.decode(tokenizer, prompt, images, vision, params, None, logprobs=lp_k)
+            outcome = engine.decode(tokenizer, prompt, images, vision, params, None, logprobs=lp_k, **constraint)
         elapsed = time.perf_counter() - start
         decoded = decode_ids(tokenizer, outcome.generated_tokens)
         if args.quiet:

@@ -18,9 +18,28 @@ from typing import Callable, Optional, Sequence
 
 import numpy as np
 
-from ._lib import (DTYPES, LOAD_PACKED_EXPERTS, MAX_TOP_LOGPROBS, DecodeParamsC, DsocrError, LoadArgs, LogprobsC, RequestC,
-                   ResultC, STREAM_CB, SESSION_LOGPROBS, SESSION_PER_REQUEST, SessionDescC, SlotStatusC, TimingsC,
-                   VisionSettingsC, check, lib)
+from ._lib import (DTYPES, LOAD_PACKED_EXPERTS, MAX_TOP_LOGPROBS, DecodeParamsC, DsocrError, LoadArgs, LogitBiasC, LogprobsC,
+                   RequestC, ResultC, STREAM_CB, SESSION_LOGIT_BIAS, SESSION_LOGPROBS, SESSION_PER_REQUEST, SessionDescC,
+                   SlotStatusC, TimingsC, VisionSettingsC, check, lib)
+from .constraint import ConstraintError, LogitConstraint, merge_constraint
+
+
+def _constraint(logit_bias, allowed_token_ids, banned_token_ids, vocab) -> Optional[LogitConstraint]:
+    """The three request arguments merged (dsocr.constraint); a bad one is the engine's EINVAL."""
+    try:
+        return merge_constraint(logit_bias, allowed_token_ids, banned_token_ids, vocab)
+    except ConstraintError as e:
+        raise DsocrError(1, f"EINVAL: logit bias: {e}") from None
+
+
+def _bias_c(c: Optional[LogitConstraint], keep) -> Optional[LogitBiasC]:
+    if c is None:
+        return None
+    ids = np.ascontiguousarray(c.ids, np.int64)
+    vals = np.ascontiguousarray(c.values, np.float32)
+    keep += [ids, vals]
+    return LogitBiasC(ids.ctypes.data_as(C.POINTER(C.c_int64)), vals.ctypes.data_as(C.POINTER(C.c_float)), len(ids),
+                      1 if c.allow_only else 0)
 
 
 @dataclass
@@ -332,6 +351,39 @@ class DeepseekOcrEngine:
                 [tid[i].reshape(-1)[:cnt[i] * k].reshape(cnt[i], k).copy() for i in range(n)],
                 [tl[i].reshape(-1)[:cnt[i] * k].reshape(cnt[i], k).copy() for i in range(n)])
 
+    def generate_constrained(self, requests, constraints, params: DecodeParameters = DecodeParameters(),
+                             ignore_eos: bool = False, top_k: Optional[int] = None):
+        """generate_batch with one constraint per request (dsocr_generate_logit_bias): ``constraints[i]`` is a
+        ``LogitConstraint`` (``dsocr.constraint.merge_constraint``) or None.  Returns the ids per page; with
+        ``top_k`` (0..20) the tuple ``generate_logprobs`` returns, of the constrained distribution."""
+        if len(constraints) != len(requests):
+            raise DsocrError(1, "one constraint (or None) per request")
+        if top_k is not None and not 0 <= int(top_k) <= MAX_TOP_LOGPROBS:
+            raise DsocrError(1, f"top_k must be 0..{MAX_TOP_LOGPROBS}")
+        keep = []
+        n, k, cap = len(requests), int(top_k or 0), max(params.max_new_tokens, 1)
+        reqs = (RequestC * n)(*[self._request(*r, keep) for r in requests])
+        outs = [np.empty(cap, np.int64) for _ in requests]
+        res = (ResultC * n)(*[ResultC(o.ctypes.data_as(C.POINTER(C.c_int64)), len(o), 0, 0) for o in outs])
+        recs = [_bias_c(c, keep) for c in constraints]
+        bias = (C.POINTER(LogitBiasC) * n)(*[C.pointer(r) if r is not None else C.POINTER(LogitBiasC)() for r in recs])
+        pc = _params_c(params, self.eos_token_id, ignore_eos)
+        if top_k is None:
+            check(lib().dsocr_generate_logit_bias(self._h, n, reqs, C.byref(pc), res, bias, 0, None))
+            return [outs[i][:res[i].n_out].tolist() for i in range(n)]
+        tlp = [np.zeros(cap, np.float32) for _ in requests]
+        tid = [np.zeros((cap, max(k, 1)), np.int64) for _ in requests]
+        tl = [np.zeros((cap, max(k, 1)), np.float32) for _ in requests]
+        lps = (LogprobsC * n)(*[LogprobsC(tlp[i].ctypes.data_as(C.POINTER(C.c_float)),
+                                         tid[i].ctypes.data_as(C.POINTER(C.c_int64)),
+                                         tl[i].ctypes.data_as(C.POINTER(C.c_float)), cap, 0) for i in range(n)])
+        check(lib().dsocr_generate_logit_bias(self._h, n, reqs, C.byref(pc), res, bias, k, lps))
+        ids = [outs[i][:res[i].n_out].tolist() for i in range(n)]
+        cnt = [int(lps[i].n) for i in range(n)]
+        return (ids, [tlp[i][:cnt[i]].copy() for i in range(n)],
+                [tid[i].reshape(-1)[:cnt[i] * k].reshape(cnt[i], k).copy() for i in range(n)],
+                [tl[i].reshape(-1)[:cnt[i] * k].reshape(cnt[i], k).copy() for i in range(n)])
+
     def last_timings(self) -> dict:
         t = TimingsC()
         check(lib().dsocr_last_timings(self._h, C.byref(t)))
@@ -395,27 +447,40 @@ class DeepseekOcrEngine:
 
     # ------------------------------------------------------------------ decode sessions
     def open_session(self, slots: int, max_context: int, params: DecodeParameters = DecodeParameters(),
-                     ignore_eos: bool = False, per_request: bool = False, logprobs: bool = False) -> "Session":
+                     ignore_eos: bool = False, per_request: bool = False, logprobs: bool = False,
+                     logit_bias: bool = False) -> "Session":
         """A long-lived batch of `slots` pages (dsocr_session_open): pages are admitted and retired between bursts
         of decode steps.  `params` are the session's; params.max_new_tokens bounds a request's own.
         ``per_request`` (dsocr_session_open_ex, DSOCR_SESSION_PER_REQUEST): `params` are only the defaults and
         ``Session.admit(..., params=...)`` gives every page its own.  ``logprobs`` (DSOCR_SESSION_LOGPROBS): every
-        slot keeps per-token log-probabilities (``Session.logprobs``); the exact head runs."""
-        return Session(self, slots, max_context, params, ignore_eos, per_request, logprobs)
+        slot keeps per-token log-probabilities (``Session.logprobs``); the exact head runs.  ``logit_bias``
+        (DSOCR_SESSION_LOGIT_BIAS): every admission may carry ``logit_bias`` / ``allowed_token_ids`` /
+        ``banned_token_ids``; a burst with a constrained page runs the exact head."""
+        return Session(self, slots, max_context, params, ignore_eos, per_request, logprobs, logit_bias)
 
     # ------------------------------------------------------------------ OcrEngine::decode
     def decode(self, tokenizer, prompt: str, images: Sequence, vision: VisionSettings,
                params: DecodeParameters, stream: Optional[Callable] = None,
-               logprobs: Optional[int] = None) -> DecodeOutcome:
+               logprobs: Optional[int] = None, logit_bias=None, allowed_token_ids=None,
+               banned_token_ids=None) -> DecodeOutcome:
         """``logprobs`` = K (0..20): the outcome carries every token's log-probability and its K most likely
-        alternatives (``stream`` is then not called: the entries arrive with the ids)."""
+        alternatives (``stream`` is then not called: the entries arrive with the ids).
+        ``logit_bias`` ({id: value}), ``allowed_token_ids`` and ``banned_token_ids`` constrain the tokens the page
+        may emit (merged by ``dsocr.constraint.merge_constraint``; ``stream`` is not called either)."""
+        con = _constraint(logit_bias, allowed_token_ids, banned_token_ids, self.vocab)
         pages = [Page(im, vision, self) for im in images]
         ids, mask = build_prompt_tokens(tokenizer, prompt, [p.n_image_tokens for p in pages])
         token_lp = top = None
-        if logprobs is not None:
+        if logprobs is not None or con is not None:
             rows = np.concatenate(self.image_embeddings(pages), axis=0) if len(pages) > 1 else None
             req = (ids, mask, pages[0] if len(pages) == 1 else None, rows)
-            g, lp, ti, tl = self.generate_logprobs([req], int(logprobs), params)
+        if con is not None and logprobs is None:
+            gen = self.generate_constrained([req], [con], params)[0]
+        elif logprobs is not None:
+            if con is not None:
+                g, lp, ti, tl = self.generate_constrained([req], [con], params, top_k=int(logprobs))
+            else:
+                g, lp, ti, tl = self.generate_logprobs([req], int(logprobs), params)
             gen = g[0]
             token_lp = [float(x) for x in lp[0]]
             top = [[(int(i), float(v)) for i, v in zip(ti[0][t], tl[0][t])] for t in range(len(token_lp))]
@@ -448,11 +513,13 @@ class Session:
     [0, active); ``retire`` returns (ids, moved_from): the last active page moves into the freed slot."""
 
     def __init__(self, engine: DeepseekOcrEngine, slots: int, max_context: int, params: DecodeParameters,
-                 ignore_eos: bool = False, per_request: bool = False, logprobs: bool = False):
+                 ignore_eos: bool = False, per_request: bool = False, logprobs: bool = False, logit_bias: bool = False):
         self._e = None
         pc = _params_c(params, engine.eos_token_id, ignore_eos)
-        flags = (SESSION_PER_REQUEST if per_request else 0) | (SESSION_LOGPROBS if logprobs else 0)
+        flags = ((SESSION_PER_REQUEST if per_request else 0) | (SESSION_LOGPROBS if logprobs else 0) |
+                 (SESSION_LOGIT_BIAS if logit_bias else 0))
         self.has_logprobs = bool(logprobs)
+        self.has_logit_bias = bool(logit_bias)
         if flags:
             check(lib().dsocr_session_open_ex(engine._h, int(slots), int(max_context), C.byref(pc), flags))
         else:
@@ -476,17 +543,21 @@ class Session:
     def admit(self, ids, mask=None, page: Optional[Page] = None, image_rows=None,
               max_new_tokens: Optional[int] = None, seed: Optional[int] = None,
               params: Optional[DecodeParameters] = None, eos_token_id: Optional[int] = None,
-              ignore_eos: Optional[bool] = None, logprobs: Optional[int] = None) -> int:
+              ignore_eos: Optional[bool] = None, logprobs: Optional[int] = None, logit_bias=None,
+              allowed_token_ids=None, banned_token_ids=None) -> int:
         """Without ``params``: the session's parameters with this page's ``max_new_tokens`` / ``seed``
         (dsocr_session_admit).  With ``params``: the page's whole parameter set (dsocr_session_admit_params; its
         max_new_tokens and seed count, the two keyword arguments are then not read); ``eos_token_id`` /
         ``ignore_eos`` default to what the session was opened with.  ``logprobs`` (0..20) is a check only, it changes
         nothing on the device: a session opened with ``logprobs`` keeps 20 alternatives for every slot whatever is
         passed here, and ``Session.logprobs(..., top_k)`` decides how many are read.  Passing it states that the
-        page's entries will be read, and is an error (EINVAL) on a session opened without ``logprobs``."""
+        page's entries will be read, and is an error (EINVAL) on a session opened without ``logprobs``.
+        ``logit_bias`` / ``allowed_token_ids`` / ``banned_token_ids``: the page's constraint (a session opened with
+        ``logit_bias``; EINVAL otherwise), applied from its first token on."""
         self._check_logprobs(logprobs)
         keep = []
         req = self._e._request(ids, mask, page, image_rows, keep)
+        self._stage_constraint(logit_bias, allowed_token_ids, banned_token_ids)
         slot = C.c_int(-1)
         if params is not None:
             pc = _params_c(params, self._eos if eos_token_id is None else int(eos_token_id),
@@ -497,6 +568,18 @@ class Session:
                                         self.out_cap if max_new_tokens is None else int(max_new_tokens),
                                         0 if seed is None else 1, seed or 0, C.byref(slot)))
         return slot.value
+
+    def _stage_constraint(self, logit_bias, allowed_token_ids, banned_token_ids) -> None:
+        """The constraint of the admission call that follows (dsocr_session_stage_logit_bias): merged and checked
+        here, consumed by that call."""
+        con = _constraint(logit_bias, allowed_token_ids, banned_token_ids, self._e.vocab)
+        if con is None:
+            return
+        if not self.has_logit_bias:
+            raise DsocrError(1, "EINVAL: this session was opened without logit_bias")
+        keep = []
+        rec = _bias_c(con, keep)
+        check(lib().dsocr_session_stage_logit_bias(self._e._h, C.byref(rec)))
 
     def _check_logprobs(self, logprobs) -> None:
         """The `logprobs` keyword of every admission: a check only (see ``admit``)."""
@@ -519,7 +602,8 @@ class Session:
     def admit_begin(self, ids, mask=None, page: Optional[Page] = None, image_rows=None, chunk_rows: int = 128,
                     max_new_tokens: Optional[int] = None, seed: Optional[int] = None,
                     params: Optional[DecodeParameters] = None, eos_token_id: Optional[int] = None,
-                    ignore_eos: Optional[bool] = None, logprobs: Optional[int] = None) -> int:
+                    ignore_eos: Optional[bool] = None, logprobs: Optional[int] = None, logit_bias=None,
+                    allowed_token_ids=None, banned_token_ids=None) -> int:
         """``admit`` in slices (dsocr_session_admit_begin): every check runs here and nothing is launched; the work
         is done by ``admit_advance``, one slice per call (the page's vision, then the prompt in chunks of
         ``chunk_rows`` >= 32 rows), with ``step`` / ``retire`` legal in between.  Returns the admission's ticket.
@@ -529,6 +613,7 @@ class Session:
         keep = []
         req = self._e._request(ids, mask, page, image_rows, keep)
         pc = self._request_params(params, max_new_tokens, seed, eos_token_id, ignore_eos)
+        self._stage_constraint(logit_bias, allowed_token_ids, banned_token_ids)
         ticket = C.c_int(-1)
         check(lib().dsocr_session_admit_begin(self._e._h, C.byref(req), C.byref(pc), max(int(chunk_rows), 0),
                                               C.byref(ticket)))
@@ -576,7 +661,8 @@ class Session:
     def admit_prefix(self, handle: int, ids, mask=None, max_new_tokens: Optional[int] = None,
                      seed: Optional[int] = None, params: Optional[DecodeParameters] = None,
                      eos_token_id: Optional[int] = None, ignore_eos: Optional[bool] = None,
-                     logprobs: Optional[int] = None) -> int:
+                     logprobs: Optional[int] = None, logit_bias=None, allowed_token_ids=None,
+                     banned_token_ids=None) -> int:
         """``admit`` for a prompt that starts with the entry's rows (dsocr_session_admit_prefix): ``ids`` / ``mask``
         are the whole prompt's, no page and no image rows; vision and the prefill of the entry's rows are skipped.
         The keywords are ``admit``'s (without ``params``: the session's parameters with this ``max_new_tokens`` /
@@ -585,6 +671,7 @@ class Session:
         keep = []
         req = self._e._request(ids, mask, None, None, keep)
         pc = self._request_params(params, max_new_tokens, seed, eos_token_id, ignore_eos)
+        self._stage_constraint(logit_bias, allowed_token_ids, banned_token_ids)
         slot = C.c_int(-1)
         check(lib().dsocr_session_admit_prefix(self._e._h, int(handle), C.byref(req), C.byref(pc), C.byref(slot)))
         return slot.value

@@ -17,6 +17,13 @@ runs for everyone) and ``submit(..., logprobs=K)`` asks for a request's entries:
 and the outcome carries ``token_logprobs`` / ``top_logprobs``.  Without the scheduler's flag such a request runs alone
 through ``engine.decode(..., logprobs=K)`` after the session drained, like any request that does not fit.
 
+Token constraints: ``submit(..., logit_bias={id: value}, allowed_token_ids=[...], banned_token_ids=[...])`` are merged
+into one constraint on the caller's thread (``dsocr.constraint.merge_constraint``; a bad one fails the future).
+``BatchScheduler(..., logit_bias=True)`` opens the session with ``logit_bias=True`` and such a request shares it (a
+burst with a constrained page runs the exact head); without the flag it runs alone through ``engine.decode(...)``
+with the same three arguments after the session drained.  Prefix-cache keys do not see the constraint: a constrained
+retry on a cached page is a prefix hit.
+
 Page prefix cache: ``BatchScheduler(..., prefix_cache=N)`` (default 0: nothing changes) keeps the K/V rows of up to N
 pages' prompt prefixes (BOS and the image rows) in the session.  After a one-image request is admitted its prefix is
 kept (``Session.keep_prefix``, rows = index of the last image position + 1) under the key (SHA-256 of the image as
@@ -46,6 +53,7 @@ from concurrent.futures import Future
 from dataclasses import dataclass, field, fields
 from typing import Any, Callable, Optional, Sequence
 
+from .constraint import merge_constraint
 from .engine import DecodeOutcome, DecodeParameters, Page, VisionSettings, build_prompt_tokens, normalize_text
 
 BURST = 8  # steps between polls while nobody streams: the cadence Engine::decode_cached polls at
@@ -76,6 +84,7 @@ class _Request:
     top_lp: list = field(default_factory=list)
     prefix_key: Any = None  # prefix cache: (image digest, vision settings, prefix ids), or None to bypass it
     prefix_rows: int = 0
+    constraint: Any = None  # the request's merged LogitConstraint, or None
 
 
 def _image_digest(im) -> str:
@@ -127,7 +136,7 @@ class BatchScheduler:
     def __init__(self, engine, tokenizer, slots: int, max_context: int,
                  defaults: DecodeParameters = DecodeParameters(), vision: Optional[VisionSettings] = None,
                  prepare: Optional[Callable] = None, per_request_params: bool = False, logprobs: bool = False,
-                 prefix_cache: int = 0, admit_chunk: int = 0):
+                 prefix_cache: int = 0, admit_chunk: int = 0, logit_bias: bool = False):
         if not 1 <= int(slots) <= 8:
             raise ValueError("a session has 1..8 slots")
         if int(admit_chunk) != 0 and int(admit_chunk) < 32:
@@ -150,6 +159,7 @@ class BatchScheduler:
         self.defaults = defaults
         self.per_request_params = bool(per_request_params)
         self.logprobs = bool(logprobs)
+        self.logit_bias = bool(logit_bias)
         self.vision = vision or VisionSettings()
         self._prepare = prepare or _default_prepare
         self._queue: deque = deque()
@@ -180,8 +190,10 @@ class BatchScheduler:
 
     def submit(self, prompt: str, images: Sequence = (), vision: Optional[VisionSettings] = None,
                params: Optional[DecodeParameters] = None, on_token: Optional[Callable] = None,
-               logprobs: Optional[int] = None) -> Future:
-        """``logprobs`` = K (0..20) asks for the request's per-token log-probabilities.  It changes the arity of
+               logprobs: Optional[int] = None, logit_bias=None, allowed_token_ids=None,
+               banned_token_ids=None) -> Future:
+        """``logit_bias`` / ``allowed_token_ids`` / ``banned_token_ids``: the request's token constraint (see the
+        module text).  ``logprobs`` = K (0..20) asks for the request's per-token log-probabilities.  It changes the arity of
         ``on_token``: the callback is then called as ``on_token(n, tokens, entry)``, with ``entry = (logprob,
         [(id, logprob)] * K)`` of the newest token, instead of ``on_token(n, tokens)``.  A two-argument callback
         given together with ``logprobs`` is refused here (ValueError through the future) rather than failing on
@@ -192,6 +204,12 @@ class BatchScheduler:
             return fut
         if logprobs is not None and not 0 <= int(logprobs) <= 20:
             fut.set_exception(ValueError("logprobs must be 0..20"))
+            return fut
+        try:
+            constraint = merge_constraint(logit_bias, allowed_token_ids, banned_token_ids,
+                                          getattr(self.engine, "vocab", None))
+        except ValueError as e:
+            fut.set_exception(e)
             return fut
         params = params or self.defaults
         vision = vision or self.vision
@@ -206,7 +224,9 @@ class BatchScheduler:
         else:
             rq.pages = list(pages)
         rq.logprobs = None if logprobs is None else int(logprobs)
-        rq.exclusive = not self.compatible(params, len(rq.ids)) or (rq.logprobs is not None and not self.logprobs)
+        rq.constraint = constraint
+        rq.exclusive = (not self.compatible(params, len(rq.ids)) or (rq.logprobs is not None and not self.logprobs) or
+                        (constraint is not None and not self.logit_bias))
         if self.prefix_cache and len(rq.images) == 1 and not rq.exclusive and any(rq.mask):
             rows = max(i for i, m in enumerate(rq.mask) if m) + 1
             if rows < len(rq.ids):  # some text follows the image: the last row's logits come from a new row
@@ -337,6 +357,8 @@ class BatchScheduler:
                 kw["per_request"] = True
             if self.logprobs:
                 kw["logprobs"] = True
+            if self.logit_bias:
+                kw["logit_bias"] = True
             self._session = self.engine.open_session(self.slots, self.max_context, self.defaults, **kw)
 
     def _admit_args(self, rq):
@@ -346,6 +368,8 @@ class BatchScheduler:
             import numpy as np
             rows = np.concatenate(self.engine.image_embeddings(rq.pages), axis=0)
         kw = {} if rq.logprobs is None else {"logprobs": rq.logprobs}
+        if rq.constraint is not None:
+            kw.update(rq.constraint.kwargs())
         if self.per_request_params:
             kw["params"] = rq.params
         else:
@@ -471,12 +495,22 @@ class BatchScheduler:
     def _run_exclusive(self, rq):
         self._close_session()  # a session and a generate exclude each other on one engine
         self.exclusive_runs += 1
+        ckw = {} if rq.constraint is None else rq.constraint.kwargs()
         try:
-            if rq.logprobs is None:
+            if rq.logprobs is None and not ckw:
                 out = self.engine.decode(self.tokenizer, rq.prompt, rq.images, rq.vision, rq.params, rq.on_token)
+            elif rq.logprobs is None:  # a constrained decode does not stream: the consumer gets the tokens afterwards
+                out = self.engine.decode(self.tokenizer, rq.prompt, rq.images, rq.vision, rq.params, None, **ckw)
+                if rq.on_token is not None:
+                    toks = [int(t) for t in out.generated_tokens]
+                    for i in range(len(toks)):
+                        try:
+                            rq.on_token(i + 1, toks[:i + 1])
+                        except Exception:  # noqa: BLE001 - a consumer's failure is its own
+                            pass
             else:  # the entries arrive with the ids: the consumer gets every token with its entry afterwards
                 out = self.engine.decode(self.tokenizer, rq.prompt, rq.images, rq.vision, rq.params, None,
-                                         logprobs=rq.logprobs)
+                                         logprobs=rq.logprobs, **ckw)
                 if rq.on_token is not None:
                     toks = [int(t) for t in out.generated_tokens]
                     for i in range(len(toks)):

@@ -175,6 +175,53 @@ def parse_logprobs(req: dict) -> Optional[int]:
     return (top or 0) if want else None
 
 
+def _id_list(req: dict, name: str, vocab: Optional[int]) -> Optional[list]:
+    ids = req.get(name)
+    if ids is None:
+        return None
+    if not isinstance(ids, list):
+        raise ApiError.bad_request(f"`{name}` must be a list of token ids")
+    for t in ids:
+        if isinstance(t, bool) or not isinstance(t, int) or t < 0 or (vocab is not None and t >= vocab):
+            raise ApiError.bad_request(f"`{name}`: {t!r} is not a token id of this model")
+    return ids
+
+
+def parse_token_constraint(req: dict, vocab: Optional[int] = None) -> Optional[dict]:
+    """OpenAI `logit_bias` ({"<token id>": number in [-100, 100]}) and the extension fields `allowed_token_ids` /
+    `banned_token_ids` (lists of token ids) of a request body, as the keywords ``decode`` / ``submit`` take; None when
+    the body constrains nothing.  400: a key that is not an integer token id, an id outside the vocabulary, a value
+    that is not a number in [-100, 100], a field of the wrong type, an empty allow list."""
+    from .constraint import ConstraintError, merge_constraint
+    raw = req.get("logit_bias")
+    bias = None
+    if raw is not None:
+        if not isinstance(raw, dict):
+            raise ApiError.bad_request("`logit_bias` must map token ids to numbers")
+        bias = {}
+        for k, v in raw.items():
+            try:
+                t = int(k) if isinstance(k, str) and k.strip().lstrip("+-").isdigit() else None
+            except ValueError:
+                t = None
+            if isinstance(k, int) and not isinstance(k, bool):
+                t = k
+            if t is None or t < 0 or (vocab is not None and t >= vocab):
+                raise ApiError.bad_request(f"`logit_bias`: key {k!r} is not a token id of this model")
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or v != v or not -100 <= v <= 100:
+                raise ApiError.bad_request(f"`logit_bias`: the value of {k!r} must be a number in [-100, 100]")
+            if t in bias:
+                raise ApiError.bad_request(f"`logit_bias`: token id {t} is listed twice")
+            bias[t] = float(v)
+    allowed = _id_list(req, "allowed_token_ids", vocab)
+    banned = _id_list(req, "banned_token_ids", vocab)
+    try:
+        con = merge_constraint(bias, allowed, banned, vocab)
+    except ConstraintError as e:
+        raise ApiError.bad_request(f"token constraint: {e}")
+    return None if con is None else con.kwargs()
+
+
 def _lp_json(v: float) -> float:
     return float(v) if v == v and v > float("-inf") else NEG_INF_LOGPROB
 
@@ -217,8 +264,8 @@ def _now() -> int:
 
 
 def generate_blocking(state: ServerState, prompt: str, images: list, params: DecodeParameters, on_token=None,
-                      logprobs: Optional[int] = None):
-    """generation.rs:75-163.  With a scheduler the request joins the running decode session (its error reaches only
+                      logprobs: Optional[int] = None, constraint: Optional[dict] = None):
+    """generation.rs:75-163.  ``constraint``: the keywords of parse_token_constraint.  With a scheduler the request joins the running decode session (its error reaches only
     its own future); without one it decodes alone behind the lock."""
     def classify(e):
         msg = str(e)
@@ -229,6 +276,7 @@ def generate_blocking(state: ServerState, prompt: str, images: list, params: Dec
     if state.scheduler is not None:
         try:
             kw = {} if logprobs is None else {"logprobs": logprobs}
+            kw.update(constraint or {})
             outcome = state.scheduler.submit(prompt, images, state.vision, params, on_token, **kw).result()
         except DsocrError as e:
             raise classify(e)
@@ -239,11 +287,17 @@ def generate_blocking(state: ServerState, prompt: str, images: list, params: Dec
     else:
         with state.lock:
             try:
-                if logprobs is None:
+                if logprobs is None and not constraint:
                     outcome = state.engine.decode(state.tokenizer, prompt, images, state.vision, params, on_token)
+                elif logprobs is None:  # a constrained decode does not stream: the tokens arrive at the end
+                    outcome = state.engine.decode(state.tokenizer, prompt, images, state.vision, params, None,
+                                                  **constraint)
+                    toks = [int(t) for t in outcome.generated_tokens]
+                    for i in range(len(toks) if on_token is not None else 0):
+                        on_token(i + 1, toks[:i + 1])
                 else:  # the entries arrive with the ids: a streaming consumer gets every token with its entry
                     outcome = state.engine.decode(state.tokenizer, prompt, images, state.vision, params, None,
-                                                  logprobs=logprobs)
+                                                  logprobs=logprobs, **(constraint or {}))
                     toks = [int(t) for t in outcome.generated_tokens]
                     for i in range(len(toks) if on_token is not None else 0):
                         on_token(i + 1, toks[:i + 1], (outcome.token_logprobs[i], outcome.top_logprobs[i]))
@@ -410,13 +464,14 @@ def handle_generation(state: ServerState, req: dict, kind: str):
         max_tokens = req.get("max_tokens")
     params = merge_decode(state.defaults, req, max_tokens)
     logprobs = parse_logprobs(req) if kind == "chat" else None  # (/v1/responses has no log-probabilities)
+    constraint = parse_token_constraint(req, getattr(state.engine, "vocab", None))
     if stream:
         c = StreamController(state.tokenizer, kind, model)
 
         def work():
             try:
                 c.send_initial()
-                out = generate_blocking(state, prompt, images, params, c.callback(), logprobs)
+                out = generate_blocking(state, prompt, images, params, c.callback(), logprobs, constraint)
                 c.flush_remaining(out.generated_tokens)
                 c.finalize(out.text, out.prompt_tokens, out.response_tokens)
             except ApiError as e:
@@ -426,7 +481,7 @@ def handle_generation(state: ServerState, req: dict, kind: str):
 
         threading.Thread(target=work, daemon=True).start()
         return "stream", c
-    out = generate_blocking(state, prompt, images, params, None, logprobs)
+    out = generate_blocking(state, prompt, images, params, None, logprobs, constraint)
     mk = _chat_response if kind == "chat" else _responses_response
     body = mk(model, out.text, out.prompt_tokens, out.response_tokens)
     if logprobs is not None:
@@ -496,6 +551,10 @@ def add_scheduler_args(p):
                    help="with --slots: open the decode session with per-token log-probabilities (the exact lm_head "
                         "runs for every request), so requests with `logprobs: true` join the running batch instead "
                         "of waiting for it to drain; off by default")
+    p.add_argument("--logit-bias", action="store_true",
+                   help="with --slots: open the decode session with a logit-bias row per slot, so requests with "
+                        "`logit_bias` / `allowed_token_ids` / `banned_token_ids` join the running batch (a burst with "
+                        "such a request runs the exact lm_head) instead of waiting for it to drain; off by default")
     p.add_argument("--prefix-cache", type=int, default=0,
                    help="with --slots: keep the K/V rows of up to N pages' image prefixes (LRU), so a later prompt on "
                         "the same image under the same vision settings skips vision and the prefill of those rows; "
@@ -507,7 +566,7 @@ def add_scheduler_args(p):
 
 
 def make_scheduler(state: ServerState, slots: int, max_context: int, per_request_params: bool = False,
-                   logprobs: bool = False, prefix_cache: int = 0, admit_chunk: int = 0):
+                   logprobs: bool = False, prefix_cache: int = 0, admit_chunk: int = 0, logit_bias: bool = False):
     """The state's scheduler for --slots N (None for 0: requests take the lock path).  per_request_params: the
     DecodeParameters merge_decode builds from a request body are admitted into the session as that request's own.
     prefix_cache: --prefix-cache N (ValueError without --slots: the entries live in the decode session)."""
@@ -515,12 +574,14 @@ def make_scheduler(state: ServerState, slots: int, max_context: int, per_request
         raise ValueError("--prefix-cache needs --slots (the prefix entries live in the decode session) and N in 0..64")
     if admit_chunk and (not slots or admit_chunk < 32):
         raise ValueError("--admit-chunk needs --slots (a chunked admission runs in the decode session) and ROWS >= 32")
+    if logit_bias and not slots:
+        raise ValueError("--logit-bias needs --slots (the bias rows live in the decode session)")
     if not slots:
         return None
     from .scheduler import BatchScheduler
     return BatchScheduler(state.engine, state.tokenizer, slots, max_context, state.defaults, state.vision,
                           per_request_params=per_request_params, logprobs=logprobs, prefix_cache=prefix_cache,
-                          admit_chunk=admit_chunk)
+                          admit_chunk=admit_chunk, **({"logit_bias": True} if logit_bias else {}))
 
 
 def main(argv=None) -> int:
@@ -542,6 +603,8 @@ def main(argv=None) -> int:
         p.error("--prefix-cache needs --slots and N in 0..64 (a session holds at most 64 prefix entries)")
     if args.admit_chunk and (not args.slots or args.admit_chunk < 32):
         p.error("--admit-chunk needs --slots and ROWS >= 32 (a chunked admission runs in the decode session)")
+    if args.logit_bias and not args.slots:
+        p.error("--logit-bias needs --slots (the bias rows live in the decode session)")
     config = model_config(args)  # --model deepseek-ocr | deepseek-ocr-2: the bundled config and vision defaults
     engine = load_model(ModelLoadArgs(config_path=config, weights_path=args.weights, snapshot_path=args.snapshot,
                                       snapshot_packed=getattr(args, "snapshot_packed", None),
@@ -550,7 +613,7 @@ def main(argv=None) -> int:
     state = ServerState(engine, load_tokenizer(args.tokenizer, _vocab_of(config)), args.model,
                         vision_settings(args), decode_params(args))
     state.scheduler = make_scheduler(state, args.slots, args.max_context, args.per_request_params, args.logprobs,
-                                     args.prefix_cache, args.admit_chunk)
+                                     args.prefix_cache, args.admit_chunk, args.logit_bias)
     import uvicorn
     uvicorn.run(create_app(state), host=args.host, port=args.port)
     return 0

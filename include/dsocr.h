@@ -222,6 +222,44 @@ dsocr_status dsocr_generate_logprobs(dsocr_engine* e, size_t n, const dsocr_requ
                                      const dsocr_decode_params* params, dsocr_result* results, size_t top_k,
                                      dsocr_logprobs* lp);
 
+/* ---- per-request logit bias and token allow / deny sets.  A constraint belongs to one request: n pairs
+ * (ids[i], values[i]) and the flag allow_only.  The exact lm_head's f32 logits row l of that request becomes
+ * l' = l + b with b[ids[i]] = values[i] and, for every id not listed, b = 0 (allow_only == 0) or -inf (allow_only
+ * != 0).  An allow list is allow_only = 1 with values 0; a deny list is allow_only = 0 with values -inf.  l' replaces
+ * l for everything downstream, in this order: the log-probability partials (log-probabilities and alternatives are
+ * those of the constrained distribution), the repetition penalty, the n-gram ban, greedy or stochastic selection.
+ * A -inf entry behaves exactly like an n-gram-banned token under select_token_id: argmax_first skips it, in the
+ * fallbacks too, and the sampler gives it weight 0, so a denied id is never emitted while any id of the row has a
+ * finite l'; if none has, the reference's last resort (id 0) stands.
+ * Checked on the host before any device state changes, each DSOCR_EINVAL: an id outside [0, vocab), a duplicate id,
+ * a NaN or +inf value, allow_only with n == 0, n > vocab.  n == 0 with allow_only == 0 (or a NULL pointer where one
+ * is taken) is "no constraint".  A call or session burst in which any active page carries a constraint runs the
+ * exact lm_head and selectors (as log-probabilities do); a page without one in such a batch produces bit for bit
+ * the ids and log-probability entries it produces alone.  A constraint together with the logits trace, use_cache = 0
+ * or the persistent step (DSOCR_PERSIST) is DSOCR_EINVAL.  With no constraint anywhere nothing changes.
+ *   dsocr_logit_bias_check: the checks alone, against a vocabulary size; needs no engine and no device.
+ *   dsocr_generate_logit_bias: dsocr_generate_batch with one constraint per request (bias [n], entries may be
+ *   NULL; bias itself NULL: none).  lp != NULL: also dsocr_generate_logprobs' entries with top_k alternatives
+ *   (lp NULL: top_k must be 0).
+ *   dsocr_session_stage_logit_bias: stages one constraint (copied) for the NEXT admission call on this engine's
+ *   session, whichever form it takes: dsocr_session_admit, _admit_params, _admit_prefix or _admit_begin (the
+ *   constraint then belongs to the chunked admission: it is applied by the slice that makes the first selection,
+ *   and dsocr_session_admit_cancel drops it with the admission).  That call consumes it whether it succeeds or not;
+ *   staging again before it replaces it, and lb == NULL (or "no constraint") clears it.  DSOCR_EINVAL, nothing
+ *   staged, when the list fails a check, no session is open, or the session was opened without
+ *   DSOCR_SESSION_LOGIT_BIAS. */
+typedef struct {
+    const int64_t* ids;
+    const float* values;
+    size_t n;
+    int allow_only;
+} dsocr_logit_bias;
+dsocr_status dsocr_logit_bias_check(const dsocr_logit_bias* lb, size_t vocab);
+dsocr_status dsocr_generate_logit_bias(dsocr_engine* e, size_t n, const dsocr_request* reqs,
+                                       const dsocr_decode_params* params, dsocr_result* results,
+                                       const dsocr_logit_bias* const* bias, size_t top_k, dsocr_logprobs* lp);
+dsocr_status dsocr_session_stage_logit_bias(dsocr_engine* e, const dsocr_logit_bias* lb);
+
 /* ---- decode sessions: pages join and leave a running batch between decode steps (no reference counterpart: the
  * reference server decodes one request at a time behind its Mutex, server/src/state.rs:22).  A session is a
  * long-lived batch of `slots` (1..8) pages with max_context rows each (a page needs prompt_len + max_new_tokens
@@ -267,6 +305,12 @@ dsocr_status dsocr_session_open(dsocr_engine* e, size_t slots, size_t max_contex
  * with DSOCR_MAX_TOP_LOGPROBS alternatives each (see dsocr_generate_logprobs), written by every step and by the
  * admission's first selection; the exact head runs at every active count. */
 #define DSOCR_SESSION_LOGPROBS 2u
+/* DSOCR_SESSION_LOGIT_BIAS (combines with both flags above): every slot keeps a dense f32 bias row (vocab floats,
+ * reserved at open), the add launch is part of the exact step, and an admission may carry a constraint
+ * (dsocr_session_stage_logit_bias).  A burst runs the exact head iff an active slot carries a constraint
+ * (dsocr_session_head_steps shows it); the constraint follows its page through the compaction of
+ * dsocr_session_retire (the row is copied) and ends with the page. */
+#define DSOCR_SESSION_LOGIT_BIAS 4u
 dsocr_status dsocr_session_open_ex(dsocr_engine* e, size_t slots, size_t max_context, const dsocr_decode_params* params,
                                    uint32_t flags);
 /* Every check (free slot, context need, prompt/image mismatch, token ids, page variant) happens before any device
@@ -740,6 +784,14 @@ dsocr_status dsocr_k_lmhead_screen_grid(int B, int V, int K, int* nblk, long lon
  * the result equals the call without it on the same raw logits. */
 dsocr_status dsocr_k_logprobs(int B, int V, int K, const float* logits, int ld, const int* tok, const uint8_t* emit,
                               float* lp, int64_t* top_id, float* top_lp);
+/* The logit bias launches once on host rows: launch_logit_bias_build for every row with flags[b] != 0 (its list:
+ * pairs [first[b], first[b] + count[b]) of ids / values, and allow_only[b]), then launch_dec_logit_bias on logits
+ * [B][ld] (in / out), which sit `offset` floats behind a 16-byte aligned device address (an odd offset: the scalar
+ * path).  dense [B][dense_ld] receives the dense rows (dense_ld = (V + 3) / 4 * 4; zeros for a row without flag).
+ * Lists are not validated here (an id outside [0, V) is skipped). */
+dsocr_status dsocr_k_logit_bias(int B, int V, int ld, int offset, float* logits, const int64_t* ids, const float* values,
+                                const int* first, const int* count, const int* flags, const int* allow_only,
+                                float* dense, int dense_ld);
 dsocr_status dsocr_k_logprobs_penalty(int B, int V, int K, const float* logits, int ld, const int* tok, const uint8_t* emit,
                                       const int* ctx, int ctx_cap, const int* ctx_len, float penalty, float* lp,
                                       int64_t* top_id, float* top_lp);
