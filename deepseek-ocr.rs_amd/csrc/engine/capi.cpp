@@ -23,6 +23,7 @@
 struct dsocr_engine {
     std::unique_ptr<dsocr::Engine> impl;
     dsocr::LogitBias staged_bias;  // dsocr_session_stage_logit_bias: consumed by the next admission call
+    dsocr::StopSet staged_stop;    // dsocr_session_stage_stop: the same
 };
 struct dsocr_page_pixels {
     dsocr::PagePixels px;
@@ -158,12 +159,39 @@ dsocr::LogitBias to_bias(const dsocr_logit_bias* lb, size_t vocab) {
     return b;
 }
 
-// a session admission's request: the staged constraint moves into it (consumed whatever the admission does)
+// the stop set as the engine takes it, checked against `vocab` (NULL or n == 0: none)
+dsocr::StopSet to_stops(const dsocr_stop_set* ss, size_t vocab) {
+    dsocr::StopSet st;
+    if (!ss || ss->n == 0) return st;
+    if (!ss->ids || !ss->lens) throw std::runtime_error("EINVAL: stop set: NULL ids / lens");
+    if (ss->n > DSOCR_MAX_STOP_SEQS) throw std::runtime_error("EINVAL: stop set: more than DSOCR_MAX_STOP_SEQS sequences");
+    size_t off = 0;
+    for (size_t i = 0; i < ss->n; ++i) {
+        const size_t m = ss->lens[i];
+        if (m == 0 || m > DSOCR_MAX_STOP_LEN) throw std::runtime_error("EINVAL: stop set: a sequence has 1..DSOCR_MAX_STOP_LEN token ids");
+        std::vector<int> q(m);
+        for (size_t j = 0; j < m; ++j) {
+            const int64_t t = ss->ids[off + j];
+            if (t < 0 || t >= (int64_t)vocab)
+                throw std::runtime_error("EINVAL: stop set: token id " + std::to_string(t) + " outside the vocabulary");
+            q[j] = (int)t;
+        }
+        off += m;
+        st.seqs.push_back(std::move(q));
+    }
+    dsocr::validate_stop_set(st, (int)vocab);
+    return st;
+}
+
+// a session admission's request: the staged constraint and stop set move into it (consumed whatever the admission does)
 dsocr::GenRequest to_admission(dsocr_engine* e, const dsocr_request& r) {
     dsocr::LogitBias b = std::move(e->staged_bias);
     e->staged_bias = dsocr::LogitBias();
+    dsocr::StopSet st = std::move(e->staged_stop);
+    e->staged_stop = dsocr::StopSet();
     dsocr::GenRequest g = to_request(r);
     g.bias = std::move(b);
+    g.stops = std::move(st);
     return g;
 }
 }  // namespace
@@ -474,9 +502,11 @@ dsocr_status dsocr_logit_bias_check(const dsocr_logit_bias* lb, size_t vocab) {
     });
 }
 
-dsocr_status dsocr_generate_logit_bias(dsocr_engine* e, size_t n, const dsocr_request* reqs,
-                                       const dsocr_decode_params* params, dsocr_result* results,
-                                       const dsocr_logit_bias* const* bias, size_t top_k, dsocr_logprobs* lp) {
+// dsocr_generate_logit_bias and dsocr_generate_stop: one constraint and one stop set per request, either list NULL
+static dsocr_status generate_constrained(dsocr_engine* e, size_t n, const dsocr_request* reqs,
+                                         const dsocr_decode_params* params, dsocr_result* results,
+                                         const dsocr_stop_set* const* stops, dsocr_stop_hit* hits,
+                                         const dsocr_logit_bias* const* bias, size_t top_k, dsocr_logprobs* lp) {
     return guarded([&] {
         if (!e || (!reqs && n) || (!results && n) || !params) throw std::runtime_error("EINVAL: NULL argument");
         if (top_k > DSOCR_MAX_TOP_LOGPROBS) throw std::runtime_error("EINVAL: top_k above DSOCR_MAX_TOP_LOGPROBS");
@@ -493,12 +523,18 @@ dsocr_status dsocr_generate_logit_bias(dsocr_engine* e, size_t n, const dsocr_re
         for (size_t i = 0; i < n; ++i) {
             rq.push_back(to_request(reqs[i]));
             if (bias) rq.back().bias = to_bias(bias[i], vocab);
+            if (stops) rq.back().stops = to_stops(stops[i], vocab);
         }
         dsocr::GenParams g = to_params(params);
         if (lp) g.lp_k = (int)top_k;
         auto r = e->impl->generate(rq, g, nullptr, nullptr);
         const dsocr::Engine::LogprobRows& rows = e->impl->last_logprobs();
+        const std::vector<int>& sh = e->impl->last_stop_hits();
         for (size_t i = 0; i < n; ++i) {
+            if (hits) {
+                hits[i].seq = sh.size() >= 2 * (i + 1) ? sh[2 * i] : -1;
+                hits[i].match_len = hits[i].seq >= 0 ? sh[2 * i + 1] : 0;
+            }
             results[i].status = DSOCR_OK;
             size_t m = std::min(r[i].size(), results[i].cap);
             if (results[i].out_ids) std::memcpy(results[i].out_ids, r[i].data(), m * sizeof(int64_t));
@@ -515,6 +551,72 @@ dsocr_status dsocr_generate_logit_bias(dsocr_engine* e, size_t n, const dsocr_re
                 }
             }
         }
+    });
+}
+
+dsocr_status dsocr_generate_logit_bias(dsocr_engine* e, size_t n, const dsocr_request* reqs,
+                                       const dsocr_decode_params* params, dsocr_result* results,
+                                       const dsocr_logit_bias* const* bias, size_t top_k, dsocr_logprobs* lp) {
+    return generate_constrained(e, n, reqs, params, results, nullptr, nullptr, bias, top_k, lp);
+}
+
+dsocr_status dsocr_stop_set_check(const dsocr_stop_set* ss, size_t vocab) {
+    return guarded([&] {
+        if (vocab == 0 || vocab > (size_t)INT32_MAX) throw std::runtime_error("EINVAL: vocab must be 1..2^31 - 1");
+        (void)to_stops(ss, vocab);
+    });
+}
+
+dsocr_status dsocr_generate_stop(dsocr_engine* e, size_t n, const dsocr_request* reqs, const dsocr_decode_params* params,
+                                 dsocr_result* results, const dsocr_stop_set* const* stops, dsocr_stop_hit* hits,
+                                 const dsocr_logit_bias* const* bias, size_t top_k, dsocr_logprobs* lp) {
+    return generate_constrained(e, n, reqs, params, results, stops, hits, bias, top_k, lp);
+}
+
+dsocr_status dsocr_generate_stop_stream(dsocr_engine* e, const dsocr_request* req, const dsocr_decode_params* params,
+                                        const dsocr_stop_set* stops, dsocr_stream_cb cb, void* user, int64_t* out_ids,
+                                        size_t cap, size_t* n_out, dsocr_stop_hit* hit) {
+    return guarded([&] {
+        if (!e || !req || !out_ids || !n_out) throw std::runtime_error("EINVAL: NULL argument");
+        std::vector<dsocr::GenRequest> reqs{to_request(*req)};
+        reqs[0].stops = to_stops(stops, (size_t)e->impl->cfg().lang.vocab);
+        auto r = e->impl->generate(reqs, to_params(params), cb, user);
+        if (r[0].size() > cap) throw std::runtime_error("EINVAL: output capacity too small");
+        std::memcpy(out_ids, r[0].data(), r[0].size() * sizeof(int64_t));
+        *n_out = r[0].size();
+        if (hit) {
+            const std::vector<int>& sh = e->impl->last_stop_hits();
+            hit->seq = sh.size() >= 2 ? sh[0] : -1;
+            hit->match_len = hit->seq >= 0 ? sh[1] : 0;
+        }
+    });
+}
+
+dsocr_status dsocr_session_stage_stop(dsocr_engine* e, const dsocr_stop_set* ss) {
+    return guarded([&] {
+        if (!e) throw std::runtime_error("EINVAL: NULL argument");
+        e->staged_stop = dsocr::StopSet();
+        dsocr::Engine::SessionInfo si;
+        if (!e->impl->session_info(&si)) throw std::runtime_error("EINVAL: no decode session is open on this engine");
+        dsocr::StopSet st = to_stops(ss, (size_t)e->impl->cfg().lang.vocab);
+        if (st.active() && !si.stops) throw std::runtime_error("EINVAL: this session was opened without DSOCR_SESSION_STOP");
+        e->staged_stop = std::move(st);
+    });
+}
+
+dsocr_status dsocr_session_stop_hit(dsocr_engine* e, int slot, dsocr_stop_hit* out) {
+    return guarded([&] {
+        if (!e || !out) throw std::runtime_error("EINVAL: NULL argument");
+        int seq = -1, len = 0;
+        e->impl->session_stop_hit(slot, &seq, &len);
+        out->seq = seq; out->match_len = len;
+    });
+}
+
+dsocr_status dsocr_stop_launches(const dsocr_engine* e, size_t* n) {
+    return guarded([&] {
+        if (!e || !n) throw std::runtime_error("EINVAL: NULL argument");
+        *n = e->impl->stop_launches();
     });
 }
 
@@ -543,11 +645,12 @@ dsocr_status dsocr_session_open_ex(dsocr_engine* e, size_t slots, size_t max_con
                                    uint32_t flags) {
     return guarded([&] {
         if (!e) throw std::runtime_error("EINVAL: NULL argument");
-        if (flags & ~(uint32_t)(DSOCR_SESSION_PER_REQUEST | DSOCR_SESSION_LOGPROBS | DSOCR_SESSION_LOGIT_BIAS))
+        if (flags & ~(uint32_t)(DSOCR_SESSION_PER_REQUEST | DSOCR_SESSION_LOGPROBS | DSOCR_SESSION_LOGIT_BIAS | DSOCR_SESSION_STOP))
             throw std::runtime_error("EINVAL: unknown session flags");
         if (slots > 8 || max_context > (size_t)INT32_MAX / 2) throw std::runtime_error("EINVAL: a session has 1..8 slots");
         e->impl->session_open((int)slots, (int)max_context, to_params(params), (flags & DSOCR_SESSION_PER_REQUEST) != 0,
-                                (flags & DSOCR_SESSION_LOGPROBS) != 0, (flags & DSOCR_SESSION_LOGIT_BIAS) != 0);
+                                (flags & DSOCR_SESSION_LOGPROBS) != 0, (flags & DSOCR_SESSION_LOGIT_BIAS) != 0,
+                                (flags & DSOCR_SESSION_STOP) != 0);
     });
 }
 
@@ -642,7 +745,7 @@ dsocr_status dsocr_session_info(const dsocr_engine* e, dsocr_session_desc* out) 
         out->out_cap = (size_t)si.out_cap; out->kv_cap = (size_t)si.kv_cap; out->burst_cap = (size_t)si.burst_cap;
         out->steps = si.steps;
         out->flags = (si.per_request ? DSOCR_SESSION_PER_REQUEST : 0u) | (si.logprobs ? DSOCR_SESSION_LOGPROBS : 0u) |
-                     (si.logit_bias ? DSOCR_SESSION_LOGIT_BIAS : 0u) |
+                     (si.logit_bias ? DSOCR_SESSION_LOGIT_BIAS : 0u) | (si.stops ? DSOCR_SESSION_STOP : 0u) |
                      (si.pending ? DSOCR_SESSION_ADMIT_PENDING : 0u);
     });
 }
@@ -2108,6 +2211,82 @@ dsocr_status dsocr_k_logit_bias(int B, int V, int ld, int offset, float* logits,
         check_hip(hipDeviceSynchronize(), "logit bias");
         check_hip(hipMemcpy(logits, lg, nl * 4, hipMemcpyDeviceToHost), "hipMemcpy D2H");
         check_hip(hipMemcpy(dense, d_dense.get(), nd * 4, hipMemcpyDeviceToHost), "hipMemcpy D2H");
+    });
+}
+
+dsocr_status dsocr_k_stop_match(int B, int steps, int out_cap, const int* n_seq, const int* lens, const int64_t* ids,
+                                const int* tokens, const uint8_t* emit, int* out, int* out_len, int* done, int* seen,
+                                int* hit, int* done_steps, int* seen_steps, int* hit_steps, int* out_len_steps) {
+    return guarded([&] {
+        if (B <= 0 || steps < 0 || out_cap <= 0 || !n_seq || !lens || !ids || (steps && (!tokens || !emit)) || !out ||
+            !out_len || !done || !seen || !hit)
+            throw std::runtime_error("EINVAL: bad stop match hook arguments");
+        const size_t nb = (size_t)B, cap = (size_t)out_cap;
+        constexpr size_t MS = DSOCR_MAX_STOP_SEQS, ML = DSOCR_MAX_STOP_LEN;
+        for (size_t b = 0; b < nb; ++b) {
+            if (n_seq[b] < 0 || n_seq[b] > (int)MS) throw std::runtime_error("EINVAL: n_seq outside 0..DSOCR_MAX_STOP_SEQS");
+            if (out_len[b] < 0 || out_len[b] > out_cap) throw std::runtime_error("EINVAL: out_len outside 0..out_cap");
+            for (int s = 0; s < n_seq[b]; ++s)
+                if (lens[b * MS + s] < 1 || lens[b * MS + s] > (int)ML)
+                    throw std::runtime_error("EINVAL: a sequence length outside 1..DSOCR_MAX_STOP_LEN");
+        }
+        const size_t RI = dsocr::STOP_ROW_INTS, SI = dsocr::STOP_STAGE_INTS;
+        dsocr::DeviceBuffer d_out(nb * cap * 4), d_len(nb * 4), d_done(nb * 4), d_tab(nb * RI * 4), d_n(nb * 4),
+            d_seen(nb * 4), d_hit(nb * 8), d_stage(nb * SI * 4);
+        check_hip(hipMemset(d_tab.get(), 0xff, nb * RI * 4), "hipMemset");
+        check_hip(hipMemset(d_n.get(), 0, nb * 4), "hipMemset");
+        std::vector<int> stage(nb * SI, 0);
+        for (size_t b = 0; b < nb; ++b) {
+            int* h = &stage[b * SI];
+            h[0] = n_seq[b];
+            size_t off = 0;
+            for (int s = 0; s < n_seq[b]; ++s) {
+                const int m = lens[b * MS + s];
+                h[1 + s] = m;
+                for (int j = 0; j < m; ++j)
+                    h[1 + MS + off + j] = (int)std::min<int64_t>(std::max<int64_t>(ids[b * MS * ML + off + j], -1), INT32_MAX);
+                off += (size_t)m;
+            }
+        }
+        check_hip(hipMemcpy(d_stage.get(), stage.data(), stage.size() * 4, hipMemcpyHostToDevice), "hipMemcpy H2D");
+        for (size_t b = 0; b < nb; ++b) {  // (a row without sequences: nothing is built, its cells keep the caller's values)
+            if (!n_seq[b]) continue;
+            dsocr::StopBuildArgs a;
+            a.stage = (const int*)d_stage.get() + b * SI;
+            a.tab = (int*)d_tab.get() + b * RI; a.n_seq = (int*)d_n.get() + b;
+            a.seen = (int*)d_seen.get() + b; a.hit = (int*)d_hit.get() + 2 * b;
+            dsocr::launch_stop_table_build(a, nullptr);
+        }
+        check_hip(hipDeviceSynchronize(), "stop table build");
+        // the caller's initial cells over what the build reset
+        check_hip(hipMemcpy(d_seen.get(), seen, nb * 4, hipMemcpyHostToDevice), "hipMemcpy H2D");
+        check_hip(hipMemcpy(d_hit.get(), hit, nb * 8, hipMemcpyHostToDevice), "hipMemcpy H2D");
+        dsocr::DecStopArgs m;
+        m.B = B; m.out = (const int*)d_out.get(); m.out_cap = out_cap; m.out_len = (const int*)d_len.get();
+        m.done = (int*)d_done.get(); m.tab = (const int*)d_tab.get(); m.n_seq = (const int*)d_n.get();
+        m.seen = (int*)d_seen.get(); m.hit = (int*)d_hit.get();
+        for (int t = 0; t < steps; ++t) {
+            // what a final selection kernel does with its token: a done row keeps everything, EOS sets done alone
+            for (size_t b = 0; b < nb; ++b) {
+                if (done[b]) continue;
+                if (!emit[(size_t)t * nb + b]) { done[b] = 1; continue; }
+                const int st = out_len[b];
+                if (st < out_cap) { out[b * cap + st] = tokens[(size_t)t * nb + b]; out_len[b] = st + 1; }
+                if (st + 1 >= out_cap) done[b] = 1;
+            }
+            check_hip(hipMemcpy(d_out.get(), out, nb * cap * 4, hipMemcpyHostToDevice), "hipMemcpy H2D");
+            check_hip(hipMemcpy(d_len.get(), out_len, nb * 4, hipMemcpyHostToDevice), "hipMemcpy H2D");
+            check_hip(hipMemcpy(d_done.get(), done, nb * 4, hipMemcpyHostToDevice), "hipMemcpy H2D");
+            dsocr::launch_dec_stop_match(m, nullptr);
+            check_hip(hipDeviceSynchronize(), "stop match");
+            check_hip(hipMemcpy(done, d_done.get(), nb * 4, hipMemcpyDeviceToHost), "hipMemcpy D2H");
+            check_hip(hipMemcpy(seen, d_seen.get(), nb * 4, hipMemcpyDeviceToHost), "hipMemcpy D2H");
+            check_hip(hipMemcpy(hit, d_hit.get(), nb * 8, hipMemcpyDeviceToHost), "hipMemcpy D2H");
+            if (done_steps) std::memcpy(done_steps + (size_t)t * nb, done, nb * 4);
+            if (seen_steps) std::memcpy(seen_steps + (size_t)t * nb, seen, nb * 4);
+            if (hit_steps) std::memcpy(hit_steps + (size_t)t * nb * 2, hit, nb * 8);
+            if (out_len_steps) std::memcpy(out_len_steps + (size_t)t * nb, out_len, nb * 4);
+        }
     });
 }
 

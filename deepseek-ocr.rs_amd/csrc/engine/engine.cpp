@@ -173,7 +173,9 @@ struct Engine::Session {
     int* stage = nullptr;   // ss_stage: an admission's staged slot rows
     bool logprobs = false;  // every step and admission writes log-probability entries (s_lp*): the exact head at every n
     bool logit_bias = false;  // every slot has a dense bias row (s_bias); a burst with a constrained slot runs the exact head
+    bool stops = false;  // every slot has a stop table (s_stop*); a burst with a slot that carries a stop set runs the match launch
     struct Slot {
+        bool stopped = false;  // the slot's request carried a stop set (rows_.stop_n[slot] != 0)
         bool biased = false;  // the slot's device flag (rows_.bias_on): its request carried a constraint
         size_t max_new = 0;
         int kv_pos = 0;    // the device kv_pos of the slot: prompt + steps replayed since its admission
@@ -198,7 +200,8 @@ struct Engine::Session {
     std::vector<Slot> slot;
     std::shared_ptr<PendingAdmit> pending;  // a chunked admission in flight, staged in slot S - 1 (session_admit_begin)
     int next_ticket = 1;
-    HipGraphExec graph[9][2];  // the step for n active pages under the [exact, screened] head, captured on first use
+    // the step for n active pages under the [exact, screened] head, [without, with] the stop match launch, captured on first use
+    HipGraphExec graph[9][2][2];
     size_t head_steps[2] = {0, 0};  // steps replayed under the [exact, screened] head
     PinnedBuffer<int> pin;  // poll: [done | output length] x S, then the decode error flag
     size_t steps = 0;
@@ -1741,7 +1744,7 @@ bool Engine::screen_applies(int B, float rep_penalty) const {
 // final norm + lm_head + greedy selection + step bookkeeping for the B decode rows in s_x
 // screened: the int8 lm_head + screened final kernel (sa.ban_out holds the ban list the last step left, whichever
 // head wrote it); else the exact lm_head, the penalty and the selection kernels
-void Engine::decode_head(int B, DecSampleArgs& sa, const SampleArgs& pen, bool screened, const DecLpArgs* lp) {
+void Engine::decode_head(int B, DecSampleArgs& sa, const SampleArgs& pen, bool screened, const DecLpArgs* lp, bool stops) {
     const LangConfig& L = cfg_.lang;
     hipStream_t st = stream_;
     const int H = L.hidden;
@@ -1759,6 +1762,7 @@ void Engine::decode_head(int B, DecSampleArgs& sa, const SampleArgs& pen, bool s
         ss.w_exact = lm_head_.W; ss.w_exact_wdt = lm_head_.wdt; ss.xn = q.xn_out; ss.K = H;
         if (getenv("DSOCR_SCREEN_STATS")) ss.stats = reinterpret_cast<unsigned long long*>(wsi("s_scrstats", 32));
         launch_dec_sample(ss, st);
+        if (stops) stop_match(sa, 0);  // (selection is untouched: the match only reads what the final kernel appended)
         return;
     }
     DecGemvArgs g;
@@ -1778,6 +1782,7 @@ void Engine::decode_head(int B, DecSampleArgs& sa, const SampleArgs& pen, bool s
     if (lp) launch_dec_lp_partial(*lp, st);
     launch_rep_penalty(pen, st);
     launch_dec_sample(sa, st);
+    if (stops) stop_match(sa, 0);
     if (lp) launch_dec_lp_final(*lp, st);
 }
 
@@ -1872,6 +1877,14 @@ void Engine::reserve_decode_rows(const DecodeRowsSpec& spec) {
         r.bias_on = ints("s_biason", S, true);
         r.bias_stage_cap = std::max<size_t>(spec.bias_stage, 1);
         r.bias_stage = wsi("s_biasstage", 2 * r.bias_stage_cap);
+    }
+    if (spec.stops) {  // (a table is written by launch_stop_table_build before its count is set)
+        r.stop_tab = wsi("s_stoptab", (size_t)S * STOP_ROW_INTS);
+        r.stop_n = ints("s_stopn", S, true);
+        r.stop_seen = ints("s_stopseen", S, true);
+        r.stop_hit = ints("s_stophit", (size_t)S * 2, true);
+        r.stop_stage_rows = std::max(spec.stop_stage_rows, 1);
+        r.stop_stage = wsi("s_stopstage", (size_t)r.stop_stage_rows * STOP_STAGE_INTS);
     }
 }
 
@@ -1978,6 +1991,62 @@ void Engine::build_logit_bias(const LogitBias& lb, int row, size_t stage_off) {
     launch_logit_bias_build(a, stream_);
 }
 
+DecStopArgs Engine::stop_args(const DecSampleArgs& sa, int row0) {
+    const DecodeRows& r = rows_;
+    DecStopArgs a;
+    a.B = sa.B; a.out = sa.out_ids; a.out_cap = sa.out_cap; a.out_len = sa.out_len; a.done = sa.done;
+    a.tab = r.stop_tab + (size_t)row0 * STOP_ROW_INTS; a.n_seq = r.stop_n + row0;
+    a.seen = r.stop_seen + row0; a.hit = r.stop_hit + (size_t)row0 * 2;
+    return a;
+}
+
+// (a launch recorded into a step graph is counted where the graph is replayed)
+void Engine::stop_match(const DecSampleArgs& sa, int row0) {
+    if (!rows_.stop_tab) throw std::runtime_error("EINTERNAL: no stop rows are reserved");
+    launch_dec_stop_match(stop_args(sa, row0), stream_);
+    if (!capturing_) ++stop_launches_;
+}
+
+void validate_stop_set(const StopSet& st, int vocab) {
+    if (st.seqs.size() > (size_t)STOP_MAX_SEQS)
+        throw std::runtime_error("EINVAL: stop set: more than " + std::to_string(STOP_MAX_SEQS) + " sequences");
+    for (size_t i = 0; i < st.seqs.size(); ++i) {
+        const std::vector<int>& q = st.seqs[i];
+        if (q.empty() || q.size() > (size_t)STOP_MAX_LEN)
+            throw std::runtime_error("EINVAL: stop set: a sequence has 1.." + std::to_string(STOP_MAX_LEN) + " token ids");
+        for (int t : q)
+            if (t < 0 || t >= vocab) throw std::runtime_error("EINVAL: stop set: token id " + std::to_string(t) + " outside the vocabulary");
+        for (size_t j = 0; j < i; ++j)
+            if (st.seqs[j] == q) throw std::runtime_error("EINVAL: stop set: sequences " + std::to_string(j) + " and " + std::to_string(i) + " are identical");
+    }
+}
+
+// One row's list over PCIe ([n | lens | ids], pinned staging under "s_stopstage"), then the table build on the
+// stream.  The caller synchronises before the staging region is reused
+void Engine::build_stop_table(const StopSet& stp, int row, int stage_row) {
+    const DecodeRows& r = rows_;
+    if (!r.stop_tab) throw std::runtime_error("EINTERNAL: no stop rows are reserved");
+    if (stage_row < 0 || stage_row >= r.stop_stage_rows) throw std::runtime_error("EINTERNAL: stop staging buffer too small");
+    StopBuildArgs a;
+    a.tab = r.stop_tab + (size_t)row * STOP_ROW_INTS; a.n_seq = r.stop_n + row; a.seen = r.stop_seen + row;
+    a.hit = r.stop_hit + (size_t)row * 2;
+    if (stp.active()) {
+        int* h = (int*)pinned("s_stopstage", (size_t)r.stop_stage_rows * STOP_STAGE_INTS * sizeof(int)) + (size_t)stage_row * STOP_STAGE_INTS;
+        std::memset(h, 0, STOP_STAGE_INTS * sizeof(int));
+        h[0] = (int)stp.seqs.size();
+        size_t off = 0;
+        for (size_t i = 0; i < stp.seqs.size(); ++i) {
+            h[1 + i] = (int)stp.seqs[i].size();
+            std::memcpy(h + 1 + STOP_MAX_SEQS + off, stp.seqs[i].data(), stp.seqs[i].size() * sizeof(int));
+            off += stp.seqs[i].size();
+        }
+        int* d = r.stop_stage + (size_t)stage_row * STOP_STAGE_INTS;
+        HIP_CHECK(hipMemcpyAsync(d, h, STOP_STAGE_INTS * sizeof(int), hipMemcpyHostToDevice, stream_));
+        a.stage = d;
+    }
+    launch_stop_table_build(a, stream_);
+}
+
 // rand_core 0.6.4 SeedableRng::seed_from_u64 for ChaCha12Rng (rand 0.8.5 StdRng): the 32-byte key
 // is filled by PCG32 (state advanced first, XSH-RR output, little-endian words); block counter 0,
 // stream 0, empty result buffer (sampling.hip reads this layout)
@@ -2034,6 +2103,21 @@ std::vector<std::vector<int64_t>> Engine::generate(const std::vector<GenRequest>
     }
     if (any_bias && (!p.use_cache || p.trace))
         throw std::runtime_error("EINVAL: a logit bias needs the K/V cache (use_cache = 1) and no logits trace");
+    // stop sets: the same
+    last_stop_hits_.clear();
+    bool any_stop = false;
+    for (const GenRequest& rq : reqs) {
+        if (!rq.stops.active()) continue;
+        any_stop = true;
+        validate_stop_set(rq.stops, cfg_.lang.vocab);
+    }
+    if (any_stop && (!p.use_cache || p.trace))
+        throw std::runtime_error("EINVAL: stop sequences need the K/V cache (use_cache = 1) and no logits trace");
+    if (any_stop) {  // (refused on the switch itself, whether or not the persistent step would fit this model and batch)
+        const char* e = getenv("DSOCR_PERSIST");
+        if (e && atoi(e) != 0)
+            throw std::runtime_error("EINVAL: stop sequences do not combine with the persistent decode step (DSOCR_PERSIST)");
+    }
     if (reqs.empty() || p.max_new == 0) return std::vector<std::vector<int64_t>>(reqs.size());
     ensure_small(std::max((int)reqs.size(), 64));
     GenState g(reqs, p, cb, user);
@@ -2237,6 +2321,9 @@ void Engine::reset_decode_state(GenState& g) {
         if (rq.bias.active()) { spec.bias = true; spec.bias_stage += rq.bias.ids.size(); }
     spec.ban = !p.do_sample && !p.trace && p.lp_k < 0 && !spec.bias && screen_applies(B, p.rep_penalty);
     spec.lp_k = p.lp_k; spec.lp_side = rep_penalty_active(p.rep_penalty);
+    // stop sets: the stop rows and one staging region per page (the head is whichever runs without them)
+    for (const GenRequest& rq : g.reqs)
+        if (rq.stops.active()) { spec.stops = true; spec.stop_stage_rows = B; }
     ensure_rope(spec.Lcap + 1);
     reserve_decode_rows(spec);
     // one page: the persistent decode step (its granules: no tag of an earlier generate may match this one's)
@@ -2393,6 +2480,10 @@ void Engine::init_sampling(GenState& g) {
     HIP_CHECK(hipMemcpyAsync(r.kv_pos, pm1.data(), B * 4, hipMemcpyHostToDevice, st));
     HIP_CHECK(hipMemcpyAsync(r.kv_len, lm1.data(), B * 4, hipMemcpyHostToDevice, st));
     launch_dec_sample(sa, st);
+    if (r.stop_tab) {  // every page's table from its stop set, then the match on the prefill's own selection
+        for (int b = 0; b < B; ++b) build_stop_table(g.reqs[b].stops, b, b);
+        stop_match(sa, 0);
+    }
     if (p.lp_k >= 0) launch_dec_lp_final(lp, st);
     HIP_CHECK(hipStreamSynchronize(st));
 }
@@ -2527,7 +2618,7 @@ void Engine::step_body(GenState& g) {
     sample_args(g.B, 0, g.p, false, sa, pen);
     const DecLpArgs lp = g.p.lp_k >= 0 ? lp_args(sa, 0) : DecLpArgs();
     decode_step(g.B, rows_.Lcap);
-    decode_head(g.B, sa, pen, rows_.ban != nullptr, g.p.lp_k >= 0 ? &lp : nullptr);
+    decode_head(g.B, sa, pen, rows_.ban != nullptr, g.p.lp_k >= 0 ? &lp : nullptr, rows_.stop_tab != nullptr);
     // chain spans: the step's one fold, after the head (the step counter has advanced: record at count - 1)
     if (chain_active_)
         launch_span_chain_fold(span_chain_, cfg_.lang.layers * SPAN_KINDS_CHAIN, span_chain_rec_, span_step_, span_cap_,
@@ -2575,9 +2666,14 @@ void Engine::decode_cached(GenState& g) {
         gexec = cap.finish();
     }
     HIP_CHECK(hipEventRecord(g.ev[4], st));
-    for (size_t i = 1; i < p.max_new; ++i) {
+    // stop sets: a stop ends a page under ignore_eos too, so the done flags are polled at the usual cadence, and once
+    // before the first step (a stop may have fired on the prefill's selection)
+    const bool stops = rows_.stop_tab != nullptr;
+    const bool finished = stops && poll(g);
+    for (size_t i = 1; i < p.max_new && !finished; ++i) {
         if (gexec) gexec.launch(st);
         else step_body(g);
+        if (gexec && stops) ++stop_launches_;
         if (span_rec_ && (span_mode_ & SPAN_EVENTS)) read_span_events(i);
         if (pk_timed) {  // the persistent launch's dispatch duration (events recorded around it in the step)
             HIP_CHECK(hipEventSynchronize(persist_ev_[1]));
@@ -2586,7 +2682,7 @@ void Engine::decode_cached(GenState& g) {
             persist_ev_us_.push_back(ms * 1e3);
         }
         ++g.steps;
-        const bool check = g.cb != nullptr || (!p.ignore_eos && (i % 8 == 0 || i + 1 == p.max_new));
+        const bool check = g.cb != nullptr || ((!p.ignore_eos || stops) && (i % 8 == 0 || i + 1 == p.max_new));
         if (check) {
             const bool all = poll(g);
             if (g.cb && B == 1) stream_tokens(g, g.pin[B]);
@@ -2643,6 +2739,10 @@ std::vector<std::vector<int64_t>> Engine::collect_outputs(GenState& g) {
             HIP_CHECK(hipMemcpy(r.top_lp.data(), rows_.lp_top, r.top_lp.size() * 4, hipMemcpyDeviceToHost));
         }
     }
+    if (rows_.stop_tab) {
+        last_stop_hits_.resize((size_t)B * 2);
+        HIP_CHECK(hipMemcpy(last_stop_hits_.data(), rows_.stop_hit, (size_t)B * 2 * 4, hipMemcpyDeviceToHost));
+    }
     last_B_ = B;
     last_Lmax_ = rows_.Lcap;
     return out;
@@ -2668,7 +2768,8 @@ static RowParams resolve_row_params(const GenParams& p) {
     return r;
 }
 
-void Engine::session_open(int S, int max_context, const GenParams& p, bool per_request, bool logprobs, bool logit_bias) {
+void Engine::session_open(int S, int max_context, const GenParams& p, bool per_request, bool logprobs, bool logit_bias,
+                          bool stops) {
     if (sess_) throw std::runtime_error("EINVAL: a decode session is already open on this engine");
     if (S < 1 || S > 8) throw std::runtime_error("EINVAL: a session has 1..8 slots");
     if (!p.use_cache || p.trace) throw std::runtime_error("EINVAL: a session decodes with the K/V cache and without a logits trace");
@@ -2685,6 +2786,7 @@ void Engine::session_open(int S, int max_context, const GenParams& p, bool per_r
     s.S = S; s.max_context = max_context; s.p = p; s.per_request = per_request;
     s.logprobs = logprobs;
     s.logit_bias = logit_bias;
+    s.stops = stops;
     // Capacity invariant.  The selection kernels advance kv_pos of every row on every step, done or not, so a
     // finished page that waits for the end of its burst keeps appending K/V rows.  A page is admitted only with
     // prompt + max_new + 1 <= max_context and produces its last token at kv_pos <= prompt + max_new - 1; it is
@@ -2708,6 +2810,7 @@ void Engine::session_open(int S, int max_context, const GenParams& p, bool per_r
         spec.bias = true;
         spec.bias_stage = (size_t)L.vocab;
     }
+    spec.stops = stops;  // every slot's table, and one admission's list at a time
     if (logprobs) {  // (the raw logits at the context ids too where a penalty can apply)
         spec.lp_k = LP_MAX_TOP;
         spec.lp_side = per_request || rep_penalty_active(p.rep_penalty);
@@ -2775,6 +2878,10 @@ void Engine::session_admit_checks(const Session& s, const GenRequest& rq, const 
     if (rq.bias.active()) {
         if (!s.logit_bias) throw std::runtime_error("EINVAL: this session was opened without DSOCR_SESSION_LOGIT_BIAS");
         validate_logit_bias(rq.bias, V);
+    }
+    if (rq.stops.active()) {
+        if (!s.stops) throw std::runtime_error("EINVAL: this session was opened without DSOCR_SESSION_STOP");
+        validate_stop_set(rq.stops, V);
     }
     if (s.pending) throw std::runtime_error("EINVAL: a chunked admission is pending (advance it to the end or cancel it)");
     if (s.n >= s.S) throw std::runtime_error("EINVAL: every session slot is in use (retire one first)");
@@ -2870,6 +2977,10 @@ int Engine::session_admit_tail(Session& s, const GenRequest& rq, const GenParams
     if (s.logprobs) launch_dec_lp_partial(lp, st);
     launch_rep_penalty(pen, st);
     launch_dec_sample(sa, st);  // the first token, its embedding into the slot's s_x row, the ban list
+    if (s.stops) {  // the slot's table (none: the count alone is cleared), then the match on this first selection
+        build_stop_table(rq.stops, slot, 0);
+        if (rq.stops.active()) stop_match(sa, slot);
+    }
     if (s.logprobs) launch_dec_lp_final(lp, st);  // entry 0 of the slot
     if (finish) {  // (else the caller has a launch to add before the one refill and synchronisation)
         refill_handoffs();
@@ -2878,6 +2989,7 @@ int Engine::session_admit_tail(Session& s, const GenRequest& rq, const GenParams
     Session::Slot& sl = s.slot[slot];
     sl.max_new = max_new; sl.kv_pos = (int)P; sl.reported = 0; sl.rp = row; sl.prompt = (int)P;
     sl.biased = rq.bias.active();
+    sl.stopped = rq.stops.active();
     sl.ids = rq.ids;
     sl.mask = rq.mask.empty() ? std::vector<uint8_t>(P, 0) : rq.mask;
     if (at < 0) ++s.n;
@@ -3086,16 +3198,16 @@ Engine::PrefixStats Engine::session_prefix_stats() const {
     return out;
 }
 
-void Engine::session_step_body(Session& s, bool screened) {
+void Engine::session_step_body(Session& s, bool screened, bool stops) {
     DecSampleArgs sa;
     SampleArgs pen;
     sample_args(s.n, 0, s.p, s.per_request, sa, pen);
     decode_step(s.n, rows_.Lcap);
     if (s.logprobs) {
         const DecLpArgs lp = lp_args(sa, 0);
-        decode_head(s.n, sa, pen, screened, &lp);
+        decode_head(s.n, sa, pen, screened, &lp, stops);
     } else {
-        decode_head(s.n, sa, pen, screened);
+        decode_head(s.n, sa, pen, screened, nullptr, stops);
     }
 }
 
@@ -3129,16 +3241,20 @@ std::vector<Engine::SlotStatus> Engine::session_step(int k) {
     hipStream_t st = stream_;
     const bool use_graph = graphs_on();
     const bool screened = session_head_screened(s);
-    HipGraphExec& graph = s.graph[s.n][screened ? 1 : 0];
+    // the match launch is part of the step iff an active slot carries a stop set: resolved here, once per burst
+    bool stops = false;
+    for (int b = 0; b < s.n; ++b) stops = stops || s.slot[b].stopped;
+    HipGraphExec& graph = s.graph[s.n][screened ? 1 : 0][stops ? 1 : 0];
     if (use_graph && !graph) {
         StreamCapture cap(st, capturing_);
-        session_step_body(s, screened);
+        session_step_body(s, screened, stops);
         graph = cap.finish();
     }
     for (int i = 0; i < k; ++i) {
         if (use_graph) graph.launch(st);
-        else session_step_body(s, screened);
+        else session_step_body(s, screened, stops);
     }
+    if (use_graph && stops) stop_launches_ += (size_t)k;
     for (int b = 0; b < s.n; ++b) s.slot[b].kv_pos += k;
     s.steps += (size_t)k;
     s.head_steps[screened ? 1 : 0] += (size_t)k;
@@ -3217,7 +3333,24 @@ void Engine::session_slot_move(Session& s, int src, int dst, int rows_bound) {
                                      sizeof(float) * r.bias_ld, hipMemcpyDeviceToDevice, stream_));
         HIP_CHECK(hipMemcpyAsync(r.bias_on + dst, r.bias_on + src, sizeof(int), hipMemcpyDeviceToDevice, stream_));
     }
+    // the stop set travels with its page: a launch of its own (a page without one: the count, seen and hit alone)
+    if (s.stops) launch_stop_slot_move(r.stop_tab, r.stop_n, r.stop_seen, r.stop_hit, src, dst, stream_);
     s.slot[dst] = s.slot[src];
+}
+
+void Engine::session_stop_hit(int slot, int* seq, int* match_len) {
+    Session& s = open_session();
+    if (!s.stops) throw std::runtime_error("EINVAL: this session was opened without DSOCR_SESSION_STOP");
+    if (slot < 0 || slot >= s.n) throw std::runtime_error("EINVAL: slot " + std::to_string(slot) + " is not active");
+    HIP_CHECK(hipStreamSynchronize(stream_));
+    int hit[2] = {-1, 0}, len = 0;
+    HIP_CHECK(hipMemcpy(hit, rows_.stop_hit + (size_t)slot * 2, 8, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(&len, rows_.out_len + slot, 4, hipMemcpyDeviceToHost));
+    // a match ends the page, so out_len is where it fired: one behind the slot's own max_new_tokens (the session's
+    // output rows are longer) is outside what the page returns
+    if (hit[0] < 0 || len > (int)s.slot[slot].max_new) { hit[0] = -1; hit[1] = 0; }
+    if (seq) *seq = hit[0];
+    if (match_len) *match_len = hit[1];
 }
 
 void Engine::session_logprobs(int slot, size_t first, size_t count, int top_k, float* token_lp, int64_t* top_id,
@@ -3271,6 +3404,7 @@ bool Engine::session_info(SessionInfo* out) const {
         out->per_request = sess_->per_request;
         out->logprobs = sess_->logprobs;
         out->logit_bias = sess_->logit_bias;
+        out->stops = sess_->stops;
         out->chunk_attn_launches = chunk_attn_launches_;
         if (const PendingAdmit* pa = sess_->pending.get()) {
             out->pending = true;

@@ -139,8 +139,18 @@ struct LogitBias {
 // EINVAL: an id outside [0, vocab), a duplicate id, a NaN or +inf value, allow_only without ids, more ids than vocab
 void validate_logit_bias(const LogitBias& lb, int vocab);
 
+// One request's stop set: 1..STOP_MAX_SEQS sequences of 1..STOP_MAX_LEN token ids; the page is done
+// from the step on whose output tail equals one of them.  Checked by validate_stop_set before any device work.
+struct StopSet {
+    std::vector<std::vector<int>> seqs;
+    bool active() const { return !seqs.empty(); }
+};
+// EINVAL: more than 16 sequences, a length of 0 or above 32, an id outside [0, vocab), two identical sequences
+void validate_stop_set(const StopSet& st, int vocab);
+
 struct GenRequest {
     LogitBias bias;
+    StopSet stops;
     std::vector<int> ids;
     std::vector<uint8_t> mask;
     const PagePixels* page = nullptr;
@@ -196,6 +206,10 @@ struct DecodeRows {
     long bias_ld = 0;
     int *bias_on = nullptr, *bias_stage = nullptr;
     size_t bias_stage_cap = 0;
+    // stop sequences (spec.stops): the tables [S][STOP_ROW_INTS], the sequence counts, the output lengths already
+    // examined and the hits [S][2], and the staging buffer the admissions' lists are uploaded to
+    int *stop_tab = nullptr, *stop_n = nullptr, *stop_seen = nullptr, *stop_hit = nullptr, *stop_stage = nullptr;
+    int stop_stage_rows = 0;
 };
 // What a caller of Engine::reserve_decode_rows asks for
 struct DecodeRowsSpec {
@@ -208,6 +222,8 @@ struct DecodeRowsSpec {
     bool lp_side = false;      // ... and the raw logits at the context ids
     bool bias = false;         // logit bias rows (every flag starts 0) ...
     size_t bias_stage = 0;     // ... and a list staging buffer of this many (id, value) pairs
+    bool stops = false;        // stop-sequence rows (every count starts 0) ...
+    int stop_stage_rows = 1;   // ... and staging for this many lists at a time
 };
 typedef void (*TokenCb)(size_t, const int64_t*, void*);
 // rand_core seed_from_u64 for rand 0.8.5 StdRng, in the layout sampling.hip reads (RNG_WORDS words)
@@ -239,6 +255,10 @@ class Engine {
         std::vector<int> top_id;
     };
     const LogprobRows& last_logprobs() const { return last_lp_; }
+    // the stop hits of the last generate: {seq, match_len} per page ({-1, 0}: no stop fired; empty: no page had stops)
+    const std::vector<int>& last_stop_hits() const { return last_stop_hits_; }
+    // dec_stop_match launches of this engine so far (issued or replayed inside a step graph)
+    size_t stop_launches() const { return stop_launches_; }
     // Replays the decode MoE grouped GEMV (routed experts, gate/up + down) of every MoE
     // layer on the last decode step's routing, timing each launch pair with HIP events.
     struct KernelProfile {
@@ -293,6 +313,7 @@ class Engine {
         bool per_request = false;
         bool logprobs = false;
         bool logit_bias = false;
+        bool stops = false;
         // a chunked admission in flight (session_admit_begin): prompt rows prefilled so far / in all, slices run
         bool pending = false;
         int pending_rows_done = 0, pending_rows_total = 0, pending_slices = 0;
@@ -310,8 +331,12 @@ class Engine {
     // logprobs: every slot keeps out_cap x LP_MAX_TOP log-probability entries; the exact head runs at every n
     // logit_bias: every slot keeps a dense bias row; an admission may carry a constraint (GenRequest::bias), and a
     // burst runs the exact head iff an active slot carries one
+    // stops: every slot keeps a stop table; an admission may carry a stop set (GenRequest::stops), and a burst's
+    // step graph contains the match launch iff an active slot carries one
     void session_open(int slots, int max_context, const GenParams& p, bool per_request = false, bool logprobs = false,
-                      bool logit_bias = false);
+                      bool logit_bias = false, bool stops = false);
+    // {seq, match_len} of a live slot ({-1, 0}: no stop fired within its max_new_tokens)
+    void session_stop_hit(int slot, int* seq, int* match_len);
     // entries [first, first + count) of a live slot, trimmed to top_k <= LP_MAX_TOP alternatives ([count][top_k])
     void session_logprobs(int slot, size_t first, size_t count, int top_k, float* token_lp, int64_t* top_id, float* top_lp);
     int session_admit(const GenRequest& rq, size_t max_new, bool seed_set, uint64_t seed);
@@ -403,7 +428,14 @@ class Engine {
     // row `row`'s dense bias row and flag from the constraint (an inactive one clears the flag); `stage_off`: where
     // in the staging buffer its list goes (pairs)
     void build_logit_bias(const LogitBias& lb, int row, size_t stage_off);
-    void decode_head(int B, DecSampleArgs& sa, const SampleArgs& pen, bool screened, const DecLpArgs* lp = nullptr);
+    // the stop rows of the same pages (only where rows_.stop_tab is set), and the match launch on them (counted)
+    DecStopArgs stop_args(const DecSampleArgs& sa, int row0);
+    void stop_match(const DecSampleArgs& sa, int row0);
+    // row `row`'s table from the stop set (an inactive one clears the count), staged in list region `stage_row`
+    void build_stop_table(const StopSet& st, int row, int stage_row);
+    // stops: the match launch follows the final selection kernel
+    void decode_head(int B, DecSampleArgs& sa, const SampleArgs& pen, bool screened, const DecLpArgs* lp = nullptr,
+                     bool stops = false);
     void reserve_head_ws(int B);
     LmHeadQ8Args head_q8_args(int B);
     bool screen_applies(int B, float rep_penalty) const;
@@ -432,7 +464,7 @@ class Engine {
     struct Session;
     std::unique_ptr<Session> sess_;
     Session& open_session();
-    void session_step_body(Session& s, bool screened);
+    void session_step_body(Session& s, bool screened, bool stops);
     bool session_head_screened(const Session& s) const;
     // profile_decode: its two timers and the sections after the MoE and attention replays
     double replay_us(int n, const std::function<void()>& body);
@@ -501,6 +533,8 @@ class Engine {
     Timings timings_;
     int vis_stage_ = 0;  // vision_pass / encoder_pass: 0 every stage (the default), 1..3 that stage alone
     size_t chunk_attn_launches_ = 0;
+    size_t stop_launches_ = 0;
+    std::vector<int> last_stop_hits_;
     double flops_acc_ = 0;  // FLOPs issued by linear() / attention since the last stage mark
     std::vector<int> prefill_lens_;  // rows per page of the prefill being issued
     int last_B_ = 0;

@@ -673,6 +673,36 @@ struct DecBiasArgs {
     const int* on = nullptr;  // [B]
 };
 void launch_dec_logit_bias(const DecBiasArgs& a, hipStream_t s);
+// Stop sequences matched inside the decode step (decode_stop.hip).  Per row: a table
+// [STOP_MAX_SEQS][1 + STOP_MAX_LEN] of int32 (a length, then the ids), n_seq, `seen` (the out_len already examined)
+// and hit[2] = {lowest matching sequence or -1, its length}.
+constexpr int STOP_MAX_SEQS = 16, STOP_MAX_LEN = 32;
+constexpr int STOP_ROW_INTS = STOP_MAX_SEQS * (1 + STOP_MAX_LEN);
+// an admission's staged list: [n | lens[STOP_MAX_SEQS] | the ids back to back]
+constexpr int STOP_STAGE_INTS = 1 + STOP_MAX_SEQS + STOP_MAX_SEQS * STOP_MAX_LEN;
+// The match of the step: one block of one wave per row, right after the step's final selection kernel.  A row with
+// n_seq[b] == 0 is neither read further nor written; a row with out_len[b] == seen[b] (an EOS step, a done row) is
+// not written.  Else the tail out[L - m, L) is compared with every sequence of length m <= L = out_len[b]; the lowest
+// matching index s gives done[b] = 1 and hit[b] = {s, m}; seen[b] = L either way.
+struct DecStopArgs {
+    int B = 0;
+    const int* out = nullptr; long out_cap = 0;  // [B][out_cap]
+    const int* out_len = nullptr;                // [B]
+    int* done = nullptr;                         // [B]
+    const int* tab = nullptr;                    // [B][STOP_ROW_INTS]
+    const int* n_seq = nullptr;                  // [B]
+    int *seen = nullptr, *hit = nullptr;         // [B], [B][2]
+};
+void launch_dec_stop_match(const DecStopArgs& a, hipStream_t s);
+// One row's table from the staged list (device pointer, STOP_STAGE_INTS ints; lengths and ids were checked on the
+// host), with n_seq = n, seen = 0 and hit = {-1, 0}.  stage == nullptr: "no stops" (n_seq = 0, the table is not written).
+struct StopBuildArgs {
+    const int* stage = nullptr;
+    int *tab = nullptr, *n_seq = nullptr, *seen = nullptr, *hit = nullptr;  // the row's own cells
+};
+void launch_stop_table_build(const StopBuildArgs& a, hipStream_t s);
+// A page's stop state from row src to row dst of the four arrays (the compaction of a session; src != dst)
+void launch_stop_slot_move(int* tab, int* n_seq, int* seen, int* hit, int src, int dst, hipStream_t s);
 // Decode sessions (session.hip).  One page's decode state from slot src to slot dst (src != dst) in one launch:
 // K / V rows [0, min(kv_len[src], rows_bound)) of every layer and kv head (f32 caches [layers][slots][kv_heads]
 // [cap_rows][hd] with the given strides in floats; 16-byte nontemporal loads and stores, hd % 4 == 0), the whole

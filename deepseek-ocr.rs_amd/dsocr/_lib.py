@@ -89,6 +89,16 @@ class LogitBiasC(C.Structure):
                 ("allow_only", C.c_int)]
 
 
+class StopSetC(C.Structure):
+    """dsocr_stop_set: one request's stop sequences, back to back (host pointers)."""
+    _fields_ = [("ids", C.POINTER(C.c_int64)), ("lens", C.POINTER(C.c_size_t)), ("n", C.c_size_t)]
+
+
+class StopHitC(C.Structure):
+    """dsocr_stop_hit: the lowest matching sequence and its length (seq = -1: no stop fired)."""
+    _fields_ = [("seq", C.c_int32), ("match_len", C.c_int32)]
+
+
 class RowParamsC(C.Structure):
     """dsocr_row_params: one row of dsocr_k_select_rows."""
     _fields_ = [("do_sample", C.c_int), ("temperature", C.c_double), ("top_p", C.c_double), ("top_k", C.c_size_t),
@@ -110,6 +120,9 @@ class ScreenStepsC(C.Structure):
 SESSION_PER_REQUEST = 1  # DSOCR_SESSION_PER_REQUEST
 SESSION_LOGPROBS = 2     # DSOCR_SESSION_LOGPROBS
 SESSION_LOGIT_BIAS = 4   # DSOCR_SESSION_LOGIT_BIAS
+SESSION_STOP = 8         # DSOCR_SESSION_STOP
+MAX_STOP_SEQS = 16       # DSOCR_MAX_STOP_SEQS
+MAX_STOP_LEN = 32        # DSOCR_MAX_STOP_LEN
 SESSION_ADMIT_PENDING = 0x100  # DSOCR_SESSION_ADMIT_PENDING (dsocr_session_info flags while an admission is pending)
 MAX_TOP_LOGPROBS = 20    # DSOCR_MAX_TOP_LOGPROBS
 
@@ -153,6 +166,8 @@ EXPORTS = [
     "dsocr_session_admit_begin", "dsocr_session_admit_advance", "dsocr_session_admit_cancel",
     "dsocr_session_admit_progress", "dsocr_k_attention_chunk",
     "dsocr_logit_bias_check", "dsocr_generate_logit_bias", "dsocr_session_stage_logit_bias", "dsocr_k_logit_bias",
+    "dsocr_stop_set_check", "dsocr_generate_stop", "dsocr_session_stage_stop", "dsocr_session_stop_hit",
+    "dsocr_stop_launches", "dsocr_k_stop_match", "dsocr_generate_stop_stream",
 ]
 
 # model variants behind the deepseek engine (dsocr_engine_variant)
@@ -299,6 +314,16 @@ def lib():
                                             C.POINTER(C.POINTER(LogitBiasC)), sz, C.POINTER(LogprobsC)]
     L.dsocr_session_stage_logit_bias.argtypes = [vp, C.POINTER(LogitBiasC)]
     L.dsocr_k_logit_bias.argtypes = [i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32]
+    L.dsocr_stop_set_check.argtypes = [C.POINTER(StopSetC), sz]
+    L.dsocr_generate_stop.argtypes = [vp, sz, C.POINTER(RequestC), C.POINTER(DecodeParamsC), C.POINTER(ResultC),
+                                      C.POINTER(C.POINTER(StopSetC)), C.POINTER(StopHitC),
+                                      C.POINTER(C.POINTER(LogitBiasC)), sz, C.POINTER(LogprobsC)]
+    L.dsocr_generate_stop_stream.argtypes = [vp, C.POINTER(RequestC), C.POINTER(DecodeParamsC), C.POINTER(StopSetC),
+                                             STREAM_CB, vp, vp, sz, C.POINTER(sz), C.POINTER(StopHitC)]
+    L.dsocr_session_stage_stop.argtypes = [vp, C.POINTER(StopSetC)]
+    L.dsocr_session_stop_hit.argtypes = [vp, i32, C.POINTER(StopHitC)]
+    L.dsocr_stop_launches.argtypes = [vp, C.POINTER(sz)]
+    L.dsocr_k_stop_match.argtypes = [i32, i32, i32] + [vp] * 14
     _lib = L
     return L
 

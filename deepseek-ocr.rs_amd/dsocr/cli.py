@@ -99,6 +99,11 @@ def build_parser() -> argparse.ArgumentParser:
                    help="emit only the token ids listed in this file, one id per line (blank lines and # comments skipped)")
     p.add_argument("--logit-bias", dest="logit_biases", action="append", default=[], metavar="ID=VALUE",
                    help="add VALUE to the logit of token ID before every selection (repeatable)")
+    p.add_argument("--stop", dest="stops", action="append", default=[], metavar="STR",
+                   help="end the generation in front of this string (repeatable, at most 16 stops in all)")
+    p.add_argument("--stop-token-ids", metavar="ID,ID,...",
+                   help="end the generation in front of any of these token ids")
+    p.add_argument("--include-stop", action="store_true", help="keep the matched stop in the output")
     p.add_argument("--slots", type=int, default=0, metavar="N",
                    help="treat every --image as its own one-page document (the prompt has one <image>) and decode them "
                         "together in a session of N slots (1..8); results print in input order.  0 = off")
@@ -231,6 +236,30 @@ def token_constraint(args) -> dict:
         kw["allowed_token_ids"] = ids
     if kw and getattr(args, "slots", 0):
         raise DsocrError(1, "--ban-token / --allow-tokens-file / --logit-bias apply to one document: not with --slots")
+    kw.update(stop_arguments(args))
+    return kw
+
+
+def stop_arguments(args) -> dict:
+    """--stop / --stop-token-ids / --include-stop as the keywords of ``engine.decode`` ({} when none is given).
+    Syntax errors are reported here, before any load; the stops are encoded and checked by ``decode``."""
+    kw = {}
+    if getattr(args, "stops", None):
+        if any(not s for s in args.stops):
+            raise DsocrError(1, "--stop takes a non-empty string")
+        kw["stop"] = list(args.stops)
+    raw = getattr(args, "stop_token_ids", None)
+    if raw:
+        try:
+            kw["stop_token_ids"] = [int(t) for t in raw.split(",") if t.strip()]
+        except ValueError:
+            raise DsocrError(1, f"--stop-token-ids takes integers separated by commas, not {raw!r}") from None
+    if kw and getattr(args, "slots", 0):
+        raise DsocrError(1, "--stop / --stop-token-ids apply to one document: not with --slots")
+    if kw:
+        kw["include_stop_in_output"] = bool(getattr(args, "include_stop", False))
+    elif getattr(args, "include_stop", False):
+        raise DsocrError(1, "--include-stop needs --stop or --stop-token-ids")
     return kw
 
 
@@ -305,6 +334,8 @@ def run_inference(args, out=sys.stdout, err=sys.stderr) -> int:
             outcome = engine.decode(tokenizer, prompt, images, vision, params, None, logprobs=lp_k, **constraint)
         elapsed = time.perf_counter() - start
         decoded = decode_ids(tokenizer, outcome.generated_tokens)
+        if "include_stop_in_output" in constraint:  # stops: the text as the outcome cut it
+            decoded = outcome.text
         if args.quiet:
             out.write(outcome.text + "\n")
         else:

@@ -14,14 +14,35 @@ from __future__ import annotations
 
 import ctypes as C
 from dataclasses import dataclass, field
-from typing import Callable, Optional, Sequence
+from typing import Any, Callable, Optional, Sequence
 
 import numpy as np
 
 from ._lib import (DTYPES, LOAD_PACKED_EXPERTS, MAX_TOP_LOGPROBS, DecodeParamsC, DsocrError, LoadArgs, LogitBiasC, LogprobsC,
-                   RequestC, ResultC, STREAM_CB, SESSION_LOGIT_BIAS, SESSION_LOGPROBS, SESSION_PER_REQUEST, SessionDescC,
-                   SlotStatusC, TimingsC, VisionSettingsC, check, lib)
+                   RequestC, ResultC, STREAM_CB, SESSION_LOGIT_BIAS, SESSION_LOGPROBS, SESSION_PER_REQUEST, SESSION_STOP,
+                   SessionDescC, SlotStatusC, StopHitC, StopSetC, TimingsC, VisionSettingsC, check, lib)
 from .constraint import ConstraintError, LogitConstraint, merge_constraint
+from .stops import StopError, StopSet, apply_stops, merge_stops
+
+
+def _stops(stop, stop_token_ids, tokenizer, vocab, stops: Optional[StopSet] = None) -> Optional[StopSet]:
+    """The request's stop set: ``stops`` as merged elsewhere, or the two request arguments merged (dsocr.stops); a bad
+    one is the engine's EINVAL."""
+    if stops is not None:
+        return stops
+    try:
+        return merge_stops(stop, stop_token_ids, tokenizer, vocab)
+    except StopError as e:
+        raise DsocrError(1, f"EINVAL: stop set: {e}") from None
+
+
+def _stop_c(ss: Optional[StopSet], keep) -> Optional[StopSetC]:
+    if ss is None:
+        return None
+    ids = np.ascontiguousarray([t for q in ss.seqs for t in q], np.int64)
+    lens = (C.c_size_t * len(ss.seqs))(*[len(q) for q in ss.seqs])
+    keep += [ids, lens]
+    return StopSetC(ids.ctypes.data_as(C.POINTER(C.c_int64)), lens, len(ss.seqs))
 
 
 def _constraint(logit_bias, allowed_token_ids, banned_token_ids, vocab) -> Optional[LogitConstraint]:
@@ -73,6 +94,9 @@ class DecodeOutcome:
     # alternatives as (id, logprob), most likely first
     token_logprobs: Optional[list] = None
     top_logprobs: Optional[list] = None
+    # decode(..., stop=... / stop_token_ids=...): the matched stop string or token id; None when EOS or the length
+    # limit ended the request (and for a request without stops)
+    stop_reason: Any = None
 
 
 @dataclass
@@ -384,6 +408,70 @@ class DeepseekOcrEngine:
                 [tid[i].reshape(-1)[:cnt[i] * k].reshape(cnt[i], k).copy() for i in range(n)],
                 [tl[i].reshape(-1)[:cnt[i] * k].reshape(cnt[i], k).copy() for i in range(n)])
 
+    def generate_stops(self, requests, stop_sets, params: DecodeParameters = DecodeParameters(), ignore_eos: bool = False,
+                       top_k: Optional[int] = None, constraints=None):
+        """generate_batch with one stop set per request (dsocr_generate_stop): ``stop_sets[i]`` is a ``StopSet``
+        (``dsocr.stops.merge_stops``) or None, ``constraints`` likewise (or None for none).  Returns ``(ids, hits)``:
+        the ids per page, matched tokens included (the device never trims), and per page ``(seq, match_len)`` with
+        ``seq = -1`` when no stop fired; with ``top_k`` (0..20) followed by the three lists ``generate_logprobs``
+        returns."""
+        if len(stop_sets) != len(requests) or (constraints is not None and len(constraints) != len(requests)):
+            raise DsocrError(1, "one stop set (or None) per request")
+        if top_k is not None and not 0 <= int(top_k) <= MAX_TOP_LOGPROBS:
+            raise DsocrError(1, f"top_k must be 0..{MAX_TOP_LOGPROBS}")
+        keep = []
+        n, k, cap = len(requests), int(top_k or 0), max(params.max_new_tokens, 1)
+        reqs = (RequestC * n)(*[self._request(*r, keep) for r in requests])
+        outs = [np.empty(cap, np.int64) for _ in requests]
+        res = (ResultC * n)(*[ResultC(o.ctypes.data_as(C.POINTER(C.c_int64)), len(o), 0, 0) for o in outs])
+        srecs = [_stop_c(ss, keep) for ss in stop_sets]
+        stops = (C.POINTER(StopSetC) * n)(*[C.pointer(r) if r is not None else C.POINTER(StopSetC)() for r in srecs])
+        hits = (StopHitC * n)()
+        bias = None
+        if constraints is not None:
+            recs = [_bias_c(c, keep) for c in constraints]
+            bias = (C.POINTER(LogitBiasC) * n)(*[C.pointer(r) if r is not None else C.POINTER(LogitBiasC)() for r in recs])
+        pc = _params_c(params, self.eos_token_id, ignore_eos)
+        if top_k is None:
+            check(lib().dsocr_generate_stop(self._h, n, reqs, C.byref(pc), res, stops, hits, bias, 0, None))
+            return ([outs[i][:res[i].n_out].tolist() for i in range(n)],
+                    [(int(hits[i].seq), int(hits[i].match_len)) for i in range(n)])
+        tlp = [np.zeros(cap, np.float32) for _ in requests]
+        tid = [np.zeros((cap, max(k, 1)), np.int64) for _ in requests]
+        tl = [np.zeros((cap, max(k, 1)), np.float32) for _ in requests]
+        lps = (LogprobsC * n)(*[LogprobsC(tlp[i].ctypes.data_as(C.POINTER(C.c_float)),
+                                         tid[i].ctypes.data_as(C.POINTER(C.c_int64)),
+                                         tl[i].ctypes.data_as(C.POINTER(C.c_float)), cap, 0) for i in range(n)])
+        check(lib().dsocr_generate_stop(self._h, n, reqs, C.byref(pc), res, stops, hits, bias, k, lps))
+        ids = [outs[i][:res[i].n_out].tolist() for i in range(n)]
+        cnt = [int(lps[i].n) for i in range(n)]
+        return (ids, [(int(hits[i].seq), int(hits[i].match_len)) for i in range(n)],
+                [tlp[i][:cnt[i]].copy() for i in range(n)],
+                [tid[i].reshape(-1)[:cnt[i] * k].reshape(cnt[i], k).copy() for i in range(n)],
+                [tl[i].reshape(-1)[:cnt[i] * k].reshape(cnt[i], k).copy() for i in range(n)])
+
+    def generate_stop_stream(self, request, stop_set, params: DecodeParameters = DecodeParameters(),
+                             stream: Optional[Callable] = None, ignore_eos: bool = False):
+        """``generate`` (one page, its stream callback) with a stop set (dsocr_generate_stop_stream): ``(ids, (seq,
+        match_len))``.  ``stream(n, tokens)`` sees the tokens as they are emitted, matched ones included."""
+        keep = []
+        req = self._request(*request, keep)
+        pc = _params_c(params, self.eos_token_id, ignore_eos)
+        out = np.empty(max(params.max_new_tokens, 1), np.int64)
+        n, hit = C.c_size_t(), StopHitC()
+        rec = _stop_c(stop_set, keep)
+        cb = STREAM_CB(lambda k, toks, _u: stream(k, [toks[i] for i in range(k)])) if stream else STREAM_CB()
+        check(lib().dsocr_generate_stop_stream(self._h, C.byref(req), C.byref(pc), C.byref(rec) if rec is not None else None,
+                                               cb, None, out.ctypes.data_as(C.c_void_p), len(out), C.byref(n),
+                                               C.byref(hit)))
+        return out[:n.value].tolist(), (int(hit.seq), int(hit.match_len))
+
+    def stop_launches(self) -> int:
+        """dec_stop_match launches of this engine so far (dsocr_stop_launches)."""
+        n = C.c_size_t()
+        check(lib().dsocr_stop_launches(self._h, C.byref(n)))
+        return int(n.value)
+
     def last_timings(self) -> dict:
         t = TimingsC()
         check(lib().dsocr_last_timings(self._h, C.byref(t)))
@@ -448,32 +536,57 @@ class DeepseekOcrEngine:
     # ------------------------------------------------------------------ decode sessions
     def open_session(self, slots: int, max_context: int, params: DecodeParameters = DecodeParameters(),
                      ignore_eos: bool = False, per_request: bool = False, logprobs: bool = False,
-                     logit_bias: bool = False) -> "Session":
+                     logit_bias: bool = False, stops: bool = False) -> "Session":
         """A long-lived batch of `slots` pages (dsocr_session_open): pages are admitted and retired between bursts
         of decode steps.  `params` are the session's; params.max_new_tokens bounds a request's own.
         ``per_request`` (dsocr_session_open_ex, DSOCR_SESSION_PER_REQUEST): `params` are only the defaults and
         ``Session.admit(..., params=...)`` gives every page its own.  ``logprobs`` (DSOCR_SESSION_LOGPROBS): every
         slot keeps per-token log-probabilities (``Session.logprobs``); the exact head runs.  ``logit_bias``
         (DSOCR_SESSION_LOGIT_BIAS): every admission may carry ``logit_bias`` / ``allowed_token_ids`` /
-        ``banned_token_ids``; a burst with a constrained page runs the exact head."""
-        return Session(self, slots, max_context, params, ignore_eos, per_request, logprobs, logit_bias)
+        ``banned_token_ids``; a burst with a constrained page runs the exact head.  ``stops`` (DSOCR_SESSION_STOP):
+        every admission may carry ``stop`` / ``stop_token_ids``; the step of a burst with such a page contains the
+        match launch."""
+        return Session(self, slots, max_context, params, ignore_eos, per_request, logprobs, logit_bias, stops)
 
     # ------------------------------------------------------------------ OcrEngine::decode
     def decode(self, tokenizer, prompt: str, images: Sequence, vision: VisionSettings,
                params: DecodeParameters, stream: Optional[Callable] = None,
                logprobs: Optional[int] = None, logit_bias=None, allowed_token_ids=None,
-               banned_token_ids=None) -> DecodeOutcome:
-        """``logprobs`` = K (0..20): the outcome carries every token's log-probability and its K most likely
+               banned_token_ids=None, stop=None, stop_token_ids=None,
+               include_stop_in_output: bool = False) -> DecodeOutcome:
+        """``stop`` (a string or a list of strings) and ``stop_token_ids`` end the page on the step that completes one
+        of them (merged by ``dsocr.stops.merge_stops``).  ``stream`` is called live, with every token as it is
+        emitted, matched ones included (dsocr_generate_stop_stream: ``dsocr.stops.TokenHoldback`` tells a consumer
+        what is safe to show); together with ``logprobs`` or a constraint it is not called (dsocr_generate_stop).  The matched tokens are trimmed from the ids, the text and the log-probability
+        entries unless ``include_stop_in_output``; a stop string the token match cannot see (another tokenisation)
+        cuts the text on the host.  ``outcome.stop_reason`` names the stop that fired.
+        ``logprobs`` = K (0..20): the outcome carries every token's log-probability and its K most likely
         alternatives (``stream`` is then not called: the entries arrive with the ids).
         ``logit_bias`` ({id: value}), ``allowed_token_ids`` and ``banned_token_ids`` constrain the tokens the page
         may emit (merged by ``dsocr.constraint.merge_constraint``; ``stream`` is not called either)."""
         con = _constraint(logit_bias, allowed_token_ids, banned_token_ids, self.vocab)
+        ss = _stops(stop, stop_token_ids, tokenizer, self.vocab)
         pages = [Page(im, vision, self) for im in images]
         ids, mask = build_prompt_tokens(tokenizer, prompt, [p.n_image_tokens for p in pages])
         token_lp = top = None
-        if logprobs is not None or con is not None:
+        if logprobs is not None or con is not None or ss is not None:
             rows = np.concatenate(self.image_embeddings(pages), axis=0) if len(pages) > 1 else None
             req = (ids, mask, pages[0] if len(pages) == 1 else None, rows)
+        if ss is not None:
+            if stream is not None and logprobs is None and con is None:
+                # live: the callback sees every token as it is emitted, matched ones included (the caller holds back)
+                got = self.generate_stop_stream(req, ss, params, stream)
+                got = ([got[0]], [got[1]])
+            else:
+                got = self.generate_stops([req], [ss], params, top_k=None if logprobs is None else int(logprobs),
+                                          constraints=None if con is None else [con])
+            gen, (hit_seq, match_len) = got[0][0], got[1][0]
+            res = apply_stops(lambda t: _decode_tokens(tokenizer, t), gen, ss, hit_seq, match_len, include_stop_in_output)
+            if logprobs is not None:
+                token_lp = [float(x) for x in got[2][0]][:len(res.tokens)]
+                top = [[(int(i), float(v)) for i, v in zip(got[3][0][t], got[4][0][t])] for t in range(len(token_lp))]
+            return DecodeOutcome(normalize_text(res.text), len(ids), len(res.tokens), res.tokens, token_lp, top,
+                                 res.stop_reason)
         if con is not None and logprobs is None:
             gen = self.generate_constrained([req], [con], params)[0]
         elif logprobs is not None:
@@ -500,6 +613,15 @@ class DeepseekOcrEngine:
         return DecodeOutcome(normalize_text(text), len(ids), len(gen), gen, token_lp, top)
 
 
+def _decode_tokens(tokenizer, toks) -> str:
+    if not hasattr(tokenizer, "decode"):
+        return ""
+    try:
+        return tokenizer.decode([int(t) for t in toks], skip_special_tokens=True)
+    except TypeError:
+        return tokenizer.decode([int(t) for t in toks])
+
+
 @dataclass
 class SlotStatus:
     slot: int
@@ -513,11 +635,13 @@ class Session:
     [0, active); ``retire`` returns (ids, moved_from): the last active page moves into the freed slot."""
 
     def __init__(self, engine: DeepseekOcrEngine, slots: int, max_context: int, params: DecodeParameters,
-                 ignore_eos: bool = False, per_request: bool = False, logprobs: bool = False, logit_bias: bool = False):
+                 ignore_eos: bool = False, per_request: bool = False, logprobs: bool = False, logit_bias: bool = False,
+                 stops: bool = False):
         self._e = None
         pc = _params_c(params, engine.eos_token_id, ignore_eos)
         flags = ((SESSION_PER_REQUEST if per_request else 0) | (SESSION_LOGPROBS if logprobs else 0) |
-                 (SESSION_LOGIT_BIAS if logit_bias else 0))
+                 (SESSION_LOGIT_BIAS if logit_bias else 0) | (SESSION_STOP if stops else 0))
+        self.has_stops = bool(stops)
         self.has_logprobs = bool(logprobs)
         self.has_logit_bias = bool(logit_bias)
         if flags:
@@ -544,7 +668,8 @@ class Session:
               max_new_tokens: Optional[int] = None, seed: Optional[int] = None,
               params: Optional[DecodeParameters] = None, eos_token_id: Optional[int] = None,
               ignore_eos: Optional[bool] = None, logprobs: Optional[int] = None, logit_bias=None,
-              allowed_token_ids=None, banned_token_ids=None) -> int:
+              allowed_token_ids=None, banned_token_ids=None, stop=None, stop_token_ids=None,
+              include_stop_in_output: bool = False, tokenizer=None, stops: Optional[StopSet] = None) -> int:
         """Without ``params``: the session's parameters with this page's ``max_new_tokens`` / ``seed``
         (dsocr_session_admit).  With ``params``: the page's whole parameter set (dsocr_session_admit_params; its
         max_new_tokens and seed count, the two keyword arguments are then not read); ``eos_token_id`` /
@@ -553,21 +678,81 @@ class Session:
         passed here, and ``Session.logprobs(..., top_k)`` decides how many are read.  Passing it states that the
         page's entries will be read, and is an error (EINVAL) on a session opened without ``logprobs``.
         ``logit_bias`` / ``allowed_token_ids`` / ``banned_token_ids``: the page's constraint (a session opened with
-        ``logit_bias``; EINVAL otherwise), applied from its first token on."""
+        ``logit_bias``; EINVAL otherwise), applied from its first token on.
+        ``stop`` / ``stop_token_ids`` (or ``stops``, a ``StopSet`` merged elsewhere): the page's stop set (a session
+        opened with ``stops``; EINVAL otherwise), matched from its first token on; a stop string needs ``tokenizer``.
+        The session returns ids as the device wrote them, matched tokens included: ``stop_hit(slot)`` names the hit
+        and ``retire_stopped`` trims by it unless ``include_stop_in_output``."""
         self._check_logprobs(logprobs)
         keep = []
         req = self._e._request(ids, mask, page, image_rows, keep)
+        checked = self._check_stops(stop, stop_token_ids, include_stop_in_output, tokenizer, stops)
         self._stage_constraint(logit_bias, allowed_token_ids, banned_token_ids)
+        self._stage_stops(checked)
         slot = C.c_int(-1)
         if params is not None:
             pc = _params_c(params, self._eos if eos_token_id is None else int(eos_token_id),
                            self._ignore_eos if ignore_eos is None else bool(ignore_eos))
             check(lib().dsocr_session_admit_params(self._e._h, C.byref(req), C.byref(pc), C.byref(slot)))
-            return slot.value
+            return self._admitted_stops(slot.value)
         check(lib().dsocr_session_admit(self._e._h, C.byref(req),
                                         self.out_cap if max_new_tokens is None else int(max_new_tokens),
                                         0 if seed is None else 1, seed or 0, C.byref(slot)))
-        return slot.value
+        return self._admitted_stops(slot.value)
+
+    def _check_stops(self, stop, stop_token_ids, include, tokenizer, stops):
+        """The stop set of an admission, merged and checked before anything is staged for it: ``(StopSet, include)``
+        or None.  A bad set, or a session without ``stops``, raises here, while no constraint is staged yet."""
+        self._staged_stops = None
+        ss = _stops(stop, stop_token_ids, tokenizer, self._e.vocab, stops)
+        if ss is None:
+            return None
+        if not self.has_stops:
+            raise DsocrError(1, "EINVAL: this session was opened without stops")
+        return ss, bool(include)
+
+    def _stage_stops(self, checked) -> None:
+        """Stages the checked stop set for the admission call that follows (dsocr_session_stage_stop), which
+        consumes it.  Should the staging itself fail, the constraint staged just before is cleared with it: nothing
+        staged may outlive a failed admission."""
+        if checked is None:
+            return
+        keep = []
+        rec = _stop_c(checked[0], keep)
+        try:
+            check(lib().dsocr_session_stage_stop(self._e._h, C.byref(rec)))
+        except DsocrError:
+            lib().dsocr_session_stage_logit_bias(self._e._h, None)
+            raise
+        self._staged_stops = checked
+
+    def _admitted_stops(self, slot: int) -> int:
+        """The staged (stop set, include) record follows its page: into its slot, or with a chunked admission."""
+        rec, self._staged_stops = getattr(self, "_staged_stops", None), None
+        self._slot_stops = getattr(self, "_slot_stops", {})
+        self._slot_stops.pop(slot, None)
+        if rec is not None:
+            self._slot_stops[slot] = rec
+        return slot
+
+    def stop_hit(self, slot: int):
+        """``(seq, match_len)`` of a live slot (dsocr_session_stop_hit); ``seq = -1``: no stop fired."""
+        h = StopHitC()
+        check(lib().dsocr_session_stop_hit(self._e._h, int(slot), C.byref(h)))
+        return int(h.seq), int(h.match_len)
+
+    def slot_stops(self, slot: int):
+        """``(StopSet, include_stop_in_output)`` the page in ``slot`` was admitted with, or None."""
+        return getattr(self, "_slot_stops", {}).get(int(slot))
+
+    def retire_stopped(self, slot: int, decode: Callable):
+        """``retire`` for a page admitted with stops: ``(StopResult, moved_from)`` with the matched tokens trimmed
+        unless the page asked for them (``dsocr.stops.apply_stops``; ``decode(ids) -> text``)."""
+        rec = self.slot_stops(slot)
+        hit = self.stop_hit(slot) if rec is not None and self.has_stops else (-1, 0)
+        ids, moved = self.retire(slot)
+        ss, include = rec if rec is not None else (None, False)
+        return apply_stops(decode, ids, ss, hit[0], hit[1], include), moved
 
     def _stage_constraint(self, logit_bias, allowed_token_ids, banned_token_ids) -> None:
         """The constraint of the admission call that follows (dsocr_session_stage_logit_bias): merged and checked
@@ -603,7 +788,8 @@ class Session:
                     max_new_tokens: Optional[int] = None, seed: Optional[int] = None,
                     params: Optional[DecodeParameters] = None, eos_token_id: Optional[int] = None,
                     ignore_eos: Optional[bool] = None, logprobs: Optional[int] = None, logit_bias=None,
-                    allowed_token_ids=None, banned_token_ids=None) -> int:
+                    allowed_token_ids=None, banned_token_ids=None, stop=None, stop_token_ids=None,
+                    include_stop_in_output: bool = False, tokenizer=None, stops: Optional[StopSet] = None) -> int:
         """``admit`` in slices (dsocr_session_admit_begin): every check runs here and nothing is launched; the work
         is done by ``admit_advance``, one slice per call (the page's vision, then the prompt in chunks of
         ``chunk_rows`` >= 32 rows), with ``step`` / ``retire`` legal in between.  Returns the admission's ticket.
@@ -613,10 +799,18 @@ class Session:
         keep = []
         req = self._e._request(ids, mask, page, image_rows, keep)
         pc = self._request_params(params, max_new_tokens, seed, eos_token_id, ignore_eos)
+        checked = self._check_stops(stop, stop_token_ids, include_stop_in_output, tokenizer, stops)
         self._stage_constraint(logit_bias, allowed_token_ids, banned_token_ids)
+        self._stage_stops(checked)
+        self._pending_stops, staged = None, None
         ticket = C.c_int(-1)
-        check(lib().dsocr_session_admit_begin(self._e._h, C.byref(req), C.byref(pc), max(int(chunk_rows), 0),
-                                              C.byref(ticket)))
+        try:
+            check(lib().dsocr_session_admit_begin(self._e._h, C.byref(req), C.byref(pc), max(int(chunk_rows), 0),
+                                                  C.byref(ticket)))
+            staged = self._staged_stops
+        finally:  # (the call consumed the staged set whether it succeeded or not)
+            self._staged_stops = None
+        self._pending_stops = staged
         self._pending_page = page  # the engine reads the page's pixels in the vision slice
         return ticket.value
 
@@ -629,9 +823,12 @@ class Session:
         except DsocrError:
             if not self.admit_progress()["pending"]:
                 self._pending_page = None
+                self._pending_stops = None
             raise
         if done.value:
             self._pending_page = None
+            self._staged_stops, self._pending_stops = getattr(self, "_pending_stops", None), None
+            self._admitted_stops(slot.value)
         return bool(done.value), slot.value
 
     def admit_cancel(self) -> None:
@@ -639,6 +836,7 @@ class Session:
         nothing of it."""
         check(lib().dsocr_session_admit_cancel(self._e._h))
         self._pending_page = None
+        self._pending_stops = None
 
     def admit_progress(self) -> dict:
         """{"pending", "rows_done", "rows_total", "slices", "vision_stage"} of the pending admission (all zero without
@@ -662,7 +860,8 @@ class Session:
                      seed: Optional[int] = None, params: Optional[DecodeParameters] = None,
                      eos_token_id: Optional[int] = None, ignore_eos: Optional[bool] = None,
                      logprobs: Optional[int] = None, logit_bias=None, allowed_token_ids=None,
-                     banned_token_ids=None) -> int:
+                     banned_token_ids=None, stop=None, stop_token_ids=None, include_stop_in_output: bool = False,
+                     tokenizer=None, stops: Optional[StopSet] = None) -> int:
         """``admit`` for a prompt that starts with the entry's rows (dsocr_session_admit_prefix): ``ids`` / ``mask``
         are the whole prompt's, no page and no image rows; vision and the prefill of the entry's rows are skipped.
         The keywords are ``admit``'s (without ``params``: the session's parameters with this ``max_new_tokens`` /
@@ -671,10 +870,16 @@ class Session:
         keep = []
         req = self._e._request(ids, mask, None, None, keep)
         pc = self._request_params(params, max_new_tokens, seed, eos_token_id, ignore_eos)
+        checked = self._check_stops(stop, stop_token_ids, include_stop_in_output, tokenizer, stops)
         self._stage_constraint(logit_bias, allowed_token_ids, banned_token_ids)
+        self._stage_stops(checked)
         slot = C.c_int(-1)
-        check(lib().dsocr_session_admit_prefix(self._e._h, int(handle), C.byref(req), C.byref(pc), C.byref(slot)))
-        return slot.value
+        try:
+            check(lib().dsocr_session_admit_prefix(self._e._h, int(handle), C.byref(req), C.byref(pc), C.byref(slot)))
+        except DsocrError:
+            self._staged_stops = None
+            raise
+        return self._admitted_stops(slot.value)
 
     def drop_prefix(self, handle: int) -> None:
         check(lib().dsocr_session_prefix_drop(self._e._h, int(handle)))
@@ -729,6 +934,11 @@ class Session:
         n, moved = C.c_size_t(), C.c_int(-1)
         check(lib().dsocr_session_retire(self._e._h, int(slot), out.ctypes.data_as(C.c_void_p), out.size, C.byref(n),
                                          C.byref(moved)))
+        recs = getattr(self, "_slot_stops", None)
+        if recs is not None:  # the (stop set, include) records follow the compaction
+            recs.pop(int(slot), None)
+            if moved.value >= 0 and moved.value in recs:
+                recs[int(slot)] = recs.pop(moved.value)
         return out[:n.value].tolist(), moved.value
 
     def close(self):

@@ -24,6 +24,14 @@ burst with a constrained page runs the exact head); without the flag it runs alo
 with the same three arguments after the session drained.  Prefix-cache keys do not see the constraint: a constrained
 retry on a cached page is a prefix hit.
 
+Stop sequences: ``submit(..., stop="...", stop_token_ids=[...], include_stop_in_output=False)`` are merged into one stop
+set on the caller's thread (``dsocr.stops.merge_stops``; a bad one fails the future).  ``BatchScheduler(...,
+stops=True)`` opens the session with ``stops=True`` and such a request shares it: the device ends the page on the step
+that completes a sequence, the worker also searches the decoded text for the stop strings after every delivery (a stop
+string can arise from another tokenisation) and retires the slot on a hit, ``on_token`` sees only tokens no later hit
+can remove, and the outcome is trimmed unless ``include_stop_in_output``.  Without the flag the request runs alone
+through ``engine.decode(...)`` with the same arguments after the session drained.
+
 Page prefix cache: ``BatchScheduler(..., prefix_cache=N)`` (default 0: nothing changes) keeps the K/V rows of up to N
 pages' prompt prefixes (BOS and the image rows) in the session.  After a one-image request is admitted its prefix is
 kept (``Session.keep_prefix``, rows = index of the last image position + 1) under the key (SHA-256 of the image as
@@ -54,6 +62,7 @@ from dataclasses import dataclass, field, fields
 from typing import Any, Callable, Optional, Sequence
 
 from .constraint import merge_constraint
+from .stops import TextStop, TokenHoldback, merge_stops
 from .engine import DecodeOutcome, DecodeParameters, Page, VisionSettings, build_prompt_tokens, normalize_text
 
 BURST = 8  # steps between polls while nobody streams: the cadence Engine::decode_cached polls at
@@ -85,6 +94,12 @@ class _Request:
     prefix_key: Any = None  # prefix cache: (image digest, vision settings, prefix ids), or None to bypass it
     prefix_rows: int = 0
     constraint: Any = None  # the request's merged LogitConstraint, or None
+    stops: Any = None       # the request's merged StopSet, or None
+    stop_args: dict = field(default_factory=dict)  # ... as the keywords engine.decode takes
+    include_stop: bool = False
+    holdback: Any = None    # TokenHoldback of a streaming request with stops
+    text_stop: Any = None   # TextStop of a request with stop strings
+    shown: int = 0          # tokens on_token has seen
 
 
 def _image_digest(im) -> str:
@@ -136,7 +151,7 @@ class BatchScheduler:
     def __init__(self, engine, tokenizer, slots: int, max_context: int,
                  defaults: DecodeParameters = DecodeParameters(), vision: Optional[VisionSettings] = None,
                  prepare: Optional[Callable] = None, per_request_params: bool = False, logprobs: bool = False,
-                 prefix_cache: int = 0, admit_chunk: int = 0, logit_bias: bool = False):
+                 prefix_cache: int = 0, admit_chunk: int = 0, logit_bias: bool = False, stops: bool = False):
         if not 1 <= int(slots) <= 8:
             raise ValueError("a session has 1..8 slots")
         if int(admit_chunk) != 0 and int(admit_chunk) < 32:
@@ -160,6 +175,7 @@ class BatchScheduler:
         self.per_request_params = bool(per_request_params)
         self.logprobs = bool(logprobs)
         self.logit_bias = bool(logit_bias)
+        self.stops = bool(stops)
         self.vision = vision or VisionSettings()
         self._prepare = prepare or _default_prepare
         self._queue: deque = deque()
@@ -191,8 +207,10 @@ class BatchScheduler:
     def submit(self, prompt: str, images: Sequence = (), vision: Optional[VisionSettings] = None,
                params: Optional[DecodeParameters] = None, on_token: Optional[Callable] = None,
                logprobs: Optional[int] = None, logit_bias=None, allowed_token_ids=None,
-               banned_token_ids=None) -> Future:
-        """``logit_bias`` / ``allowed_token_ids`` / ``banned_token_ids``: the request's token constraint (see the
+               banned_token_ids=None, stop=None, stop_token_ids=None,
+               include_stop_in_output: bool = False) -> Future:
+        """``stop`` / ``stop_token_ids`` / ``include_stop_in_output``: the request's stop set (see the module text).
+        ``logit_bias`` / ``allowed_token_ids`` / ``banned_token_ids``: the request's token constraint (see the
         module text).  ``logprobs`` = K (0..20) asks for the request's per-token log-probabilities.  It changes the arity of
         ``on_token``: the callback is then called as ``on_token(n, tokens, entry)``, with ``entry = (logprob,
         [(id, logprob)] * K)`` of the newest token, instead of ``on_token(n, tokens)``.  A two-argument callback
@@ -208,6 +226,7 @@ class BatchScheduler:
         try:
             constraint = merge_constraint(logit_bias, allowed_token_ids, banned_token_ids,
                                           getattr(self.engine, "vocab", None))
+            stops = merge_stops(stop, stop_token_ids, self.tokenizer, getattr(self.engine, "vocab", None))
         except ValueError as e:
             fut.set_exception(e)
             return fut
@@ -225,8 +244,15 @@ class BatchScheduler:
             rq.pages = list(pages)
         rq.logprobs = None if logprobs is None else int(logprobs)
         rq.constraint = constraint
+        if stops is not None:
+            rq.stops, rq.include_stop = stops, bool(include_stop_in_output)
+            rq.stop_args = dict(stop=stop, stop_token_ids=stop_token_ids, include_stop_in_output=rq.include_stop)
+            if on_token is not None:
+                rq.holdback = TokenHoldback(stops.seqs, rq.include_stop)
+            if stops.strings:
+                rq.text_stop = TextStop(stops.strings, rq.include_stop)
         rq.exclusive = (not self.compatible(params, len(rq.ids)) or (rq.logprobs is not None and not self.logprobs) or
-                        (constraint is not None and not self.logit_bias))
+                        (constraint is not None and not self.logit_bias) or (stops is not None and not self.stops))
         if self.prefix_cache and len(rq.images) == 1 and not rq.exclusive and any(rq.mask):
             rows = max(i for i, m in enumerate(rq.mask) if m) + 1
             if rows < len(rq.ids):  # some text follows the image: the last row's logits come from a new row
@@ -359,6 +385,8 @@ class BatchScheduler:
                 kw["logprobs"] = True
             if self.logit_bias:
                 kw["logit_bias"] = True
+            if self.stops:
+                kw["stops"] = True
             self._session = self.engine.open_session(self.slots, self.max_context, self.defaults, **kw)
 
     def _admit_args(self, rq):
@@ -370,6 +398,8 @@ class BatchScheduler:
         kw = {} if rq.logprobs is None else {"logprobs": rq.logprobs}
         if rq.constraint is not None:
             kw.update(rq.constraint.kwargs())
+        if rq.stops is not None:
+            kw.update(stops=rq.stops, include_stop_in_output=rq.include_stop)
         if self.per_request_params:
             kw["params"] = rq.params
         else:
@@ -464,14 +494,26 @@ class BatchScheduler:
                     rq.token_lp.append(entries[i][0])
                     rq.top_lp.append(entries[i][1])
                 if rq.on_token is not None:
-                    try:
-                        if entries:
-                            rq.on_token(len(rq.tokens), list(rq.tokens), entries[i])
-                        else:
-                            rq.on_token(len(rq.tokens), list(rq.tokens))
-                    except Exception:  # noqa: BLE001 - a consumer's failure is its own
-                        pass
+                    # with stops only what no later hit can remove (the rest follows, or arrives at the retirement)
+                    self._show(rq, len(rq.tokens) if rq.holdback is None else rq.holdback.feed(rq.tokens))
             rq.done = bool(st.done) or len(rq.tokens) >= rq.params.max_new_tokens
+            if rq.text_stop is not None and fresh and not rq.done:
+                # the text-level backstop: a stop string the token match cannot see ends the request here
+                if rq.text_stop.find(_decode_text(self.tokenizer, rq.tokens)) is not None:
+                    rq.done = True
+
+    def _show(self, rq, n):
+        """``on_token`` for the tokens ``rq.shown .. n``, one call per token, each with its own entry (the entry of
+        token j, not of the newest one: under a hold-back the two differ)."""
+        for j in range(rq.shown + 1, n + 1):
+            rq.shown = j
+            try:
+                if rq.logprobs is not None:
+                    rq.on_token(j, list(rq.tokens[:j]), (rq.token_lp[j - 1], rq.top_lp[j - 1]))
+                else:
+                    rq.on_token(j, list(rq.tokens[:j]))
+            except Exception:  # noqa: BLE001 - a consumer's failure is its own
+                pass
 
     def _retire_done(self):
         # highest slot first: the page that moves into a freed slot is then never one that is itself finished
@@ -479,7 +521,12 @@ class BatchScheduler:
             rq = self._active[slot]
             if not rq.done:
                 continue
-            ids, moved = self._session.retire(slot)
+            res = None
+            if rq.stops is not None:
+                res, moved = self._session.retire_stopped(slot, lambda t: _decode_text(self.tokenizer, t))
+                ids = res.tokens
+            else:
+                ids, moved = self._session.retire(slot)
             last = len(self._active) - 1
             if moved >= 0:
                 if moved != last:
@@ -487,7 +534,12 @@ class BatchScheduler:
                 self._active[slot] = self._active[last]
             self._active.pop()
             ids = [int(t) for t in ids][:rq.params.max_new_tokens]
-            out = DecodeOutcome(normalize_text(_decode_text(self.tokenizer, ids)), len(rq.ids), len(ids), ids)
+            if res is not None and rq.on_token is not None:
+                self._show(rq, len(ids))  # what the hold-back kept and no hit removed
+            if res is not None:  # trimmed by the hit, the text cut at a stop string
+                out = DecodeOutcome(normalize_text(res.text), len(rq.ids), len(ids), ids, stop_reason=res.stop_reason)
+            else:
+                out = DecodeOutcome(normalize_text(_decode_text(self.tokenizer, ids)), len(rq.ids), len(ids), ids)
             if rq.logprobs is not None:
                 out.token_logprobs, out.top_logprobs = rq.token_lp[:len(ids)], rq.top_lp[:len(ids)]
             rq.future.set_result(out)
@@ -496,6 +548,7 @@ class BatchScheduler:
         self._close_session()  # a session and a generate exclude each other on one engine
         self.exclusive_runs += 1
         ckw = {} if rq.constraint is None else rq.constraint.kwargs()
+        ckw.update(rq.stop_args)  # (a decode with stops does not stream either)
         try:
             if rq.logprobs is None and not ckw:
                 out = self.engine.decode(self.tokenizer, rq.prompt, rq.images, rq.vision, rq.params, rq.on_token)

@@ -222,6 +222,51 @@ def parse_token_constraint(req: dict, vocab: Optional[int] = None) -> Optional[d
     return None if con is None else con.kwargs()
 
 
+MAX_STOP_STRINGS = 4  # the OpenAI limit on `stop`
+
+
+def parse_stops(req: dict, tokenizer=None, vocab: Optional[int] = None) -> Optional[dict]:
+    """OpenAI `stop` (a string, or a list of at most 4 strings) and the extension fields `stop_token_ids` (a list of
+    token ids) and `include_stop_in_output` (a boolean) of a request body, as the keywords ``decode`` / ``submit``
+    take; None when the body names no stop (`stop: null`, an empty list).  400: anything else in those fields, an
+    empty string, a string that encodes to no or to more than 32 token ids, an id outside the vocabulary, more than
+    16 sequences in all."""
+    from .stops import StopError, merge_stops
+    stop = req.get("stop")
+    if stop is not None:
+        if isinstance(stop, str):
+            stop = [stop]
+        if not isinstance(stop, list) or any(not isinstance(x, str) for x in stop):
+            raise ApiError.bad_request("`stop` must be a string or a list of strings")
+        if len(stop) > MAX_STOP_STRINGS:
+            raise ApiError.bad_request(f"`stop` takes at most {MAX_STOP_STRINGS} strings")
+    ids = _id_list(req, "stop_token_ids", vocab)
+    include = req.get("include_stop_in_output")
+    if include is not None and not isinstance(include, bool):
+        raise ApiError.bad_request("`include_stop_in_output` must be a boolean")
+    try:
+        ss = merge_stops(stop, ids, tokenizer, vocab)
+    except StopError as e:
+        raise ApiError.bad_request(f"stop: {e}")
+    if ss is None:
+        return None
+    return {"stop": stop, "stop_token_ids": ids, "include_stop_in_output": bool(include)}
+
+
+def _held_back(on_token, stops: dict, tokenizer, vocab):
+    """``on_token`` behind a ``dsocr.stops.TokenHoldback``: it is called once per token that no later hit can remove."""
+    from .stops import TokenHoldback, merge_stops
+    ss = merge_stops(stops["stop"], stops["stop_token_ids"], tokenizer, vocab)
+    hb, shown = TokenHoldback(ss.seqs, stops["include_stop_in_output"]), [0]
+
+    def cb(n, toks):
+        toks = [int(t) for t in toks[:n]]
+        for j in range(shown[0] + 1, hb.feed(toks) + 1):
+            shown[0] = j
+            on_token(j, toks[:j])
+    return cb
+
+
 def _lp_json(v: float) -> float:
     return float(v) if v == v and v > float("-inf") else NEG_INF_LOGPROB
 
@@ -264,8 +309,9 @@ def _now() -> int:
 
 
 def generate_blocking(state: ServerState, prompt: str, images: list, params: DecodeParameters, on_token=None,
-                      logprobs: Optional[int] = None, constraint: Optional[dict] = None):
-    """generation.rs:75-163.  ``constraint``: the keywords of parse_token_constraint.  With a scheduler the request joins the running decode session (its error reaches only
+                      logprobs: Optional[int] = None, constraint: Optional[dict] = None, stops: Optional[dict] = None):
+    """generation.rs:75-163.  ``stops``: the keywords of parse_stops (merged into ``constraint``'s: both are keywords
+    of ``decode`` / ``submit``, and a decode with either does not stream).  ``constraint``: the keywords of parse_token_constraint.  With a scheduler the request joins the running decode session (its error reaches only
     its own future); without one it decodes alone behind the lock."""
     def classify(e):
         msg = str(e)
@@ -273,6 +319,9 @@ def generate_blocking(state: ServerState, prompt: str, images: list, params: Dec
             return ApiError.bad_request(msg)
         return ApiError.internal(f"generation failed: {msg}")
 
+    live_stops = bool(stops) and not constraint and logprobs is None and on_token is not None
+    if stops:
+        constraint = dict(constraint or {}, **stops)
     if state.scheduler is not None:
         try:
             kw = {} if logprobs is None else {"logprobs": logprobs}
@@ -289,6 +338,10 @@ def generate_blocking(state: ServerState, prompt: str, images: list, params: Dec
             try:
                 if logprobs is None and not constraint:
                     outcome = state.engine.decode(state.tokenizer, prompt, images, state.vision, params, on_token)
+                elif live_stops:  # stops alone stream live, behind the hold-back of a tail that may become a stop
+                    outcome = state.engine.decode(state.tokenizer, prompt, images, state.vision, params,
+                                                  _held_back(on_token, stops, state.tokenizer,
+                                                             getattr(state.engine, "vocab", None)), **constraint)
                 elif logprobs is None:  # a constrained decode does not stream: the tokens arrive at the end
                     outcome = state.engine.decode(state.tokenizer, prompt, images, state.vision, params, None,
                                                   **constraint)
@@ -320,6 +373,9 @@ class StreamController:
         self.role_sent = False
         self.finished = False
         self.pending_lp: list = []  # entries of the tokens since the last chunk (chat, logprobs: true)
+        self.text_stop = None  # dsocr.stops.TextStop of a request with stop strings: nothing of a stop is ever sent
+        self.stop_reason = None
+        self.has_stops = False
         if kind == "chat":
             self.id = f"chatcmpl-{uuid.uuid4()}"
         else:
@@ -363,6 +419,8 @@ class StreamController:
             return
         include_role = self.kind == "chat" and not self.role_sent
         full = decode_ids(self.tokenizer, ids[:count])
+        if self.text_stop is not None:
+            full, _ = self.text_stop.advance(full, is_final)
         emit = None
         if full:
             d = self.delta.advance(full, is_final)
@@ -385,12 +443,24 @@ class StreamController:
         if ids:
             self.process_tokens(len(ids), ids, True)
 
+    def emit_rest(self, text: str):
+        """A request with stops: what the outcome's text holds beyond the deltas sent (a cut inside a token's text)."""
+        sent = self.delta.snapshot()
+        if not text.startswith(sent):
+            sent = sent.lstrip()
+        rest = text[len(sent):] if text.startswith(sent) else ""
+        if rest:
+            self.delta.previous += rest
+            self.emit_delta(rest, self.kind == "chat" and not self.role_sent)
+
     def finalize(self, normalized: str, prompt_tokens: int, completion_tokens: int):
         if self.finished:
             return
         self.finished = True
         if self.kind == "chat":
             choice = {"index": 0, "delta": {}, "finish_reason": "stop"}
+            if self.has_stops:
+                choice["stop_reason"] = self.stop_reason
             if self.pending_lp:  # tokens that produced no text of their own
                 choice["logprobs"], self.pending_lp = {"content": self.pending_lp}, []
             self._send({"id": self.id, "object": "chat.completion.chunk", "created": self.created,
@@ -402,7 +472,8 @@ class StreamController:
                 {"id": self.output_id, "type": "message", "role": "assistant",
                  "content": [{"type": "output_text", "text": normalized}]}],
                 usage={"input_tokens": prompt_tokens, "output_tokens": completion_tokens,
-                       "total_tokens": prompt_tokens + completion_tokens})})
+                       "total_tokens": prompt_tokens + completion_tokens},
+                **({"stop_reason": self.stop_reason} if self.has_stops else {}))})
         self.q.put("[DONE]")
         self.q.put(None)
 
@@ -465,14 +536,23 @@ def handle_generation(state: ServerState, req: dict, kind: str):
     params = merge_decode(state.defaults, req, max_tokens)
     logprobs = parse_logprobs(req) if kind == "chat" else None  # (/v1/responses has no log-probabilities)
     constraint = parse_token_constraint(req, getattr(state.engine, "vocab", None))
+    stops = parse_stops(req, state.tokenizer, getattr(state.engine, "vocab", None))
     if stream:
         c = StreamController(state.tokenizer, kind, model)
+        if stops:
+            from .stops import TextStop
+            c.has_stops = True
+            if stops["stop"]:
+                c.text_stop = TextStop(stops["stop"], stops["include_stop_in_output"])
 
         def work():
             try:
                 c.send_initial()
-                out = generate_blocking(state, prompt, images, params, c.callback(), logprobs, constraint)
+                out = generate_blocking(state, prompt, images, params, c.callback(), logprobs, constraint, stops)
+                c.stop_reason = getattr(out, "stop_reason", None)
                 c.flush_remaining(out.generated_tokens)
+                if c.has_stops:
+                    c.emit_rest(out.text)
                 c.finalize(out.text, out.prompt_tokens, out.response_tokens)
             except ApiError as e:
                 c.send_error(e.message)
@@ -481,9 +561,14 @@ def handle_generation(state: ServerState, req: dict, kind: str):
 
         threading.Thread(target=work, daemon=True).start()
         return "stream", c
-    out = generate_blocking(state, prompt, images, params, None, logprobs, constraint)
+    out = generate_blocking(state, prompt, images, params, None, logprobs, constraint, stops)
     mk = _chat_response if kind == "chat" else _responses_response
     body = mk(model, out.text, out.prompt_tokens, out.response_tokens)
+    if stops:  # the matched string or token id; null when EOS or the length limit ended the request
+        if kind == "chat":
+            body["choices"][0]["stop_reason"] = getattr(out, "stop_reason", None)
+        else:
+            body["stop_reason"] = getattr(out, "stop_reason", None)
     if logprobs is not None:
         body["choices"][0]["logprobs"] = {"content": logprob_content(state.tokenizer, out.generated_tokens,
                                                                      out.token_logprobs or [], out.top_logprobs or [])}
@@ -555,6 +640,10 @@ def add_scheduler_args(p):
                    help="with --slots: open the decode session with a logit-bias row per slot, so requests with "
                         "`logit_bias` / `allowed_token_ids` / `banned_token_ids` join the running batch (a burst with "
                         "such a request runs the exact lm_head) instead of waiting for it to drain; off by default")
+    p.add_argument("--stops", action="store_true",
+                   help="with --slots: open the decode session with a stop table per slot, so requests with `stop` / "
+                        "`stop_token_ids` join the running batch (the device ends such a page on the step that "
+                        "completes a stop) instead of waiting for it to drain; off by default")
     p.add_argument("--prefix-cache", type=int, default=0,
                    help="with --slots: keep the K/V rows of up to N pages' image prefixes (LRU), so a later prompt on "
                         "the same image under the same vision settings skips vision and the prefill of those rows; "
@@ -566,7 +655,8 @@ def add_scheduler_args(p):
 
 
 def make_scheduler(state: ServerState, slots: int, max_context: int, per_request_params: bool = False,
-                   logprobs: bool = False, prefix_cache: int = 0, admit_chunk: int = 0, logit_bias: bool = False):
+                   logprobs: bool = False, prefix_cache: int = 0, admit_chunk: int = 0, logit_bias: bool = False,
+                   stops: bool = False):
     """The state's scheduler for --slots N (None for 0: requests take the lock path).  per_request_params: the
     DecodeParameters merge_decode builds from a request body are admitted into the session as that request's own.
     prefix_cache: --prefix-cache N (ValueError without --slots: the entries live in the decode session)."""
@@ -576,12 +666,15 @@ def make_scheduler(state: ServerState, slots: int, max_context: int, per_request
         raise ValueError("--admit-chunk needs --slots (a chunked admission runs in the decode session) and ROWS >= 32")
     if logit_bias and not slots:
         raise ValueError("--logit-bias needs --slots (the bias rows live in the decode session)")
+    if stops and not slots:
+        raise ValueError("--stops needs --slots (the stop tables live in the decode session)")
     if not slots:
         return None
     from .scheduler import BatchScheduler
     return BatchScheduler(state.engine, state.tokenizer, slots, max_context, state.defaults, state.vision,
                           per_request_params=per_request_params, logprobs=logprobs, prefix_cache=prefix_cache,
-                          admit_chunk=admit_chunk, **({"logit_bias": True} if logit_bias else {}))
+                          admit_chunk=admit_chunk, **({"logit_bias": True} if logit_bias else {}),
+                          **({"stops": True} if stops else {}))
 
 
 def main(argv=None) -> int:
@@ -605,6 +698,8 @@ def main(argv=None) -> int:
         p.error("--admit-chunk needs --slots and ROWS >= 32 (a chunked admission runs in the decode session)")
     if args.logit_bias and not args.slots:
         p.error("--logit-bias needs --slots (the bias rows live in the decode session)")
+    if args.stops and not args.slots:
+        p.error("--stops needs --slots (the stop tables live in the decode session)")
     config = model_config(args)  # --model deepseek-ocr | deepseek-ocr-2: the bundled config and vision defaults
     engine = load_model(ModelLoadArgs(config_path=config, weights_path=args.weights, snapshot_path=args.snapshot,
                                       snapshot_packed=getattr(args, "snapshot_packed", None),
@@ -613,7 +708,7 @@ def main(argv=None) -> int:
     state = ServerState(engine, load_tokenizer(args.tokenizer, _vocab_of(config)), args.model,
                         vision_settings(args), decode_params(args))
     state.scheduler = make_scheduler(state, args.slots, args.max_context, args.per_request_params, args.logprobs,
-                                     args.prefix_cache, args.admit_chunk, args.logit_bias)
+                                     args.prefix_cache, args.admit_chunk, args.logit_bias, args.stops)
     import uvicorn
     uvicorn.run(create_app(state), host=args.host, port=args.port)
     return 0

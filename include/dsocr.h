@@ -260,6 +260,71 @@ dsocr_status dsocr_generate_logit_bias(dsocr_engine* e, size_t n, const dsocr_re
                                        const dsocr_logit_bias* const* bias, size_t top_k, dsocr_logprobs* lp);
 dsocr_status dsocr_session_stage_logit_bias(dsocr_engine* e, const dsocr_logit_bias* lb);
 
+/* ---- stop sequences matched inside the decode step, per request.  A stop set belongs to one request.  It holds n
+ * sequences (1 <= n <= DSOCR_MAX_STOP_SEQS = 16), each of 1 .. DSOCR_MAX_STOP_LEN = 32 token ids in [0, vocab).
+ *   When a match fires.  After a step appends token number L to a page's output, sequence s of length m <= L matches
+ *   when out[L-m .. L) == s.  The prompt is never matched against.  Only the tail is looked at, because one token
+ *   arrives per step.
+ *   What a match does.  The page is done from that step on, exactly as for EOS.  No later step appends a token, a
+ *   context id or a log-probability entry for it.
+ *   What is recorded.  The page records (seq, match_len) with seq the lowest matching index.
+ *   EOS in the same step.  A step in which EOS was selected emits nothing and therefore matches nothing.
+ *   max_new_tokens in the same step.  A stop that completes on the step that also reaches max_new_tokens still
+ *   records its hit.
+ *   No trimming on the device.  out_len, the ids that dsocr_session_retire and dsocr_generate* return, and the
+ *   log-probability entries all include the matched tokens.  Trimming is the caller's job.
+ *   Selection is untouched.  Stops never change which token is selected.  A page's ids are a prefix of the ids it
+ *   produces without stops, for any head, any batch and any neighbour.
+ *   Heads.  Stops do not force the exact head; the screened head keeps running where it runs today.
+ *   Refusals.  A stop set together with the logits trace, use_cache = 0 or with the persistent step (DSOCR_PERSIST=1
+ *   in the environment, whether or not that step would fit the model) is DSOCR_EINVAL.
+ *   Off by default.  With no stop set anywhere, nothing is launched and nothing changes.
+ * The match is one launch (dec_stop_match, one wave per page) right after the step's final selection kernel, and after
+ * the first selection a prefill or an admission makes; it writes the done word EOS writes.
+ * dsocr_stop_set_check: the checks alone, against a vocabulary size; needs no engine and no device.  Each of these is
+ * DSOCR_EINVAL, before any device state changes: n > 16, a length of 0 or above 32, an id outside [0, vocab), two
+ * identical sequences.  n == 0 or a NULL pointer means "no stops".
+ * dsocr_generate_stop: dsocr_generate_logit_bias with one stop set per request (stops [n], entries may be NULL;
+ * stops itself NULL: none) and the hits [n] (may be NULL); bias and lp may be NULL (lp NULL: top_k must be 0).  The call
+ * polls the done words every 8 steps (under ignore_eos too, and once before the first step), so decode_steps of
+ * dsocr_last_timings is 0 when every page stopped on its first token and else the steps run when the poll saw every
+ * page done: the first multiple of 8 at or behind the last page's end, at most max_new_tokens - 1.  It takes no
+ * stream callback.
+ * dsocr_generate_stop_stream: dsocr_generate, one page with its stream callback, with a stop set (NULL: none) and
+ * the hit (may be NULL).  The callback sees the tokens as they are emitted, matched ones included: holding back a
+ * tail that may still become a stop is the caller's job.  With a callback the done word is polled after every step,
+ * so decode_steps is the number of steps up to the match.
+ * dsocr_session_stage_stop: stages one stop set (copied) for the NEXT admission call on this engine's session,
+ * whichever form it takes, exactly like dsocr_session_stage_logit_bias: that call consumes it whether it succeeds or
+ * not, a chunked admission owns it until its last slice applies it (dsocr_session_admit_cancel drops it), staging
+ * again replaces it, NULL or n == 0 clears it.  DSOCR_EINVAL, nothing staged, when the set fails a check, no session
+ * is open, or the session was opened without DSOCR_SESSION_STOP.
+ * dsocr_session_stop_hit: the hit of a live slot (it follows its page through the compaction of
+ * dsocr_session_retire); seq = -1 while no stop has fired within the slot's own max_new_tokens.
+ * dsocr_stop_launches: match launches of this engine so far, issued or replayed inside a step graph (0 for ever
+ * while no request carries a stop set). */
+#define DSOCR_MAX_STOP_SEQS 16
+#define DSOCR_MAX_STOP_LEN 32
+typedef struct {
+    const int64_t* ids; /* the sequences back to back */
+    const size_t* lens;
+    size_t n;
+} dsocr_stop_set;
+typedef struct {
+    int32_t seq; /* -1: no stop fired */
+    int32_t match_len;
+} dsocr_stop_hit;
+dsocr_status dsocr_stop_set_check(const dsocr_stop_set* stops, size_t vocab);
+dsocr_status dsocr_generate_stop(dsocr_engine* e, size_t n, const dsocr_request* reqs, const dsocr_decode_params* params,
+                                 dsocr_result* results, const dsocr_stop_set* const* stops, dsocr_stop_hit* hits,
+                                 const dsocr_logit_bias* const* bias, size_t top_k, dsocr_logprobs* lp);
+dsocr_status dsocr_generate_stop_stream(dsocr_engine* e, const dsocr_request* req, const dsocr_decode_params* params,
+                                        const dsocr_stop_set* stops, dsocr_stream_cb cb, void* user, int64_t* out_ids,
+                                        size_t cap, size_t* n_out, dsocr_stop_hit* hit);
+dsocr_status dsocr_session_stage_stop(dsocr_engine* e, const dsocr_stop_set* stops);
+dsocr_status dsocr_session_stop_hit(dsocr_engine* e, int slot, dsocr_stop_hit* out);
+dsocr_status dsocr_stop_launches(const dsocr_engine* e, size_t* n);
+
 /* ---- decode sessions: pages join and leave a running batch between decode steps (no reference counterpart: the
  * reference server decodes one request at a time behind its Mutex, server/src/state.rs:22).  A session is a
  * long-lived batch of `slots` (1..8) pages with max_context rows each (a page needs prompt_len + max_new_tokens
@@ -311,6 +376,11 @@ dsocr_status dsocr_session_open(dsocr_engine* e, size_t slots, size_t max_contex
  * (dsocr_session_head_steps shows it); the constraint follows its page through the compaction of
  * dsocr_session_retire (the row is copied) and ends with the page. */
 #define DSOCR_SESSION_LOGIT_BIAS 4u
+/* DSOCR_SESSION_STOP (combines with the three flags above): every slot keeps a stop table (16 x 33 int32, reserved
+ * at open) with its count, examined length and hit, and an admission may carry a stop set
+ * (dsocr_session_stage_stop).  The step graph of a burst contains the match launch iff an active slot carries a stop
+ * set; the head is whichever runs without it.  A stop that fires in the middle of a burst leaves out_len at the match. */
+#define DSOCR_SESSION_STOP 8u
 dsocr_status dsocr_session_open_ex(dsocr_engine* e, size_t slots, size_t max_context, const dsocr_decode_params* params,
                                    uint32_t flags);
 /* Every check (free slot, context need, prompt/image mismatch, token ids, page variant) happens before any device
@@ -792,6 +862,16 @@ dsocr_status dsocr_k_logprobs(int B, int V, int K, const float* logits, int ld, 
 dsocr_status dsocr_k_logit_bias(int B, int V, int ld, int offset, float* logits, const int64_t* ids, const float* values,
                                 const int* first, const int* count, const int* flags, const int* allow_only,
                                 float* dense, int dense_ld);
+/* The stop launches on host rows: launch_stop_table_build for every row with n_seq[b] != 0 (lens [B][16], ids [B][512]:
+ * the row's sequences back to back), then `steps` rounds.  Round t does per row what a final selection kernel does
+ * with tokens[t][b]: a done row keeps everything, emit[t][b] == 0 (EOS selected) sets done alone, else the token is
+ * appended to out [B][out_cap] / out_len (done when out_cap is reached); then one launch_dec_stop_match over the B
+ * rows.  out, out_len, done, seen and hit [B][2] are in / out (the cells of a row with n_seq == 0 reach the device as
+ * given and come back as the device left them); *_steps, each optional, receive every round's values ([steps][B],
+ * hit [steps][B][2]). */
+dsocr_status dsocr_k_stop_match(int B, int steps, int out_cap, const int* n_seq, const int* lens, const int64_t* ids,
+                                const int* tokens, const uint8_t* emit, int* out, int* out_len, int* done, int* seen,
+                                int* hit, int* done_steps, int* seen_steps, int* hit_steps, int* out_len_steps);
 dsocr_status dsocr_k_logprobs_penalty(int B, int V, int K, const float* logits, int ld, const int* tok, const uint8_t* emit,
                                       const int* ctx, int ctx_cap, const int* ctx_len, float penalty, float* lp,
                                       int64_t* top_id, float* top_lp);
