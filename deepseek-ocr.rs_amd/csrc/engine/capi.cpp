@@ -194,6 +194,116 @@ dsocr::GenRequest to_admission(dsocr_engine* e, const dsocr_request& r) {
     g.stops = std::move(st);
     return g;
 }
+
+// the DSOCR_SESSION_* feature bits as the engine takes them, and back (DSOCR_SESSION_ADMIT_PENDING is state, not one of them)
+dsocr::Engine::SessionFeatures to_features(uint32_t flags) {
+    if (flags & ~(uint32_t)(DSOCR_SESSION_PER_REQUEST | DSOCR_SESSION_LOGPROBS | DSOCR_SESSION_LOGIT_BIAS | DSOCR_SESSION_STOP))
+        throw std::runtime_error("EINVAL: unknown session flags");
+    dsocr::Engine::SessionFeatures f;
+    f.per_request = (flags & DSOCR_SESSION_PER_REQUEST) != 0;
+    f.logprobs = (flags & DSOCR_SESSION_LOGPROBS) != 0;
+    f.logit_bias = (flags & DSOCR_SESSION_LOGIT_BIAS) != 0;
+    f.stops = (flags & DSOCR_SESSION_STOP) != 0;
+    return f;
+}
+uint32_t feature_flags(const dsocr::Engine::SessionFeatures& f) {
+    return (f.per_request ? DSOCR_SESSION_PER_REQUEST : 0u) | (f.logprobs ? DSOCR_SESSION_LOGPROBS : 0u) |
+           (f.logit_bias ? DSOCR_SESSION_LOGIT_BIAS : 0u) | (f.stops ? DSOCR_SESSION_STOP : 0u);
+}
+
+// ---- generate: the exported forms marshal through generate_page (one page, the stream callback) or generate_pages
+// (a batch).  They differ in what an output longer than its buffer is: an error there, a truncation here.
+
+// a page's ids into its batch result: what fits, and DSOCR_EINVAL when that is not all of them
+void write_result(const std::vector<int64_t>& ids, dsocr_result& out) {
+    out.status = DSOCR_OK;
+    const size_t m = std::min(ids.size(), out.cap);
+    if (out.out_ids) std::memcpy(out.out_ids, ids.data(), m * sizeof(int64_t));
+    out.n_out = m;
+    if (m < ids.size()) out.status = DSOCR_EINVAL;
+}
+
+// page i's entries of the last generate, which ran with lp_k = top_k
+void write_logprobs(const dsocr::Engine::LogprobRows& rows, size_t i, size_t top_k, dsocr_logprobs& out) {
+    const size_t ne = rows.n.empty() ? 0 : (size_t)rows.n[i];
+    out.n = ne;
+    for (size_t t = 0; t < ne; ++t) {
+        out.token_lp[t] = rows.lp[i * rows.cap + t];
+        for (size_t k = 0; k < top_k; ++k) {
+            out.top_id[t * top_k + k] = rows.top_id[(i * rows.cap + t) * top_k + k];
+            out.top_lp[t * top_k + k] = rows.top_lp[(i * rows.cap + t) * top_k + k];
+        }
+    }
+}
+
+// page i's pair of Engine::last_stop_hits ({-1, 0}: no stop fired, or no page had stops)
+void write_stop_hit(const std::vector<int>& sh, size_t i, dsocr_stop_hit& out) {
+    out.seq = sh.size() >= 2 * (i + 1) ? sh[2 * i] : -1;
+    out.match_len = out.seq >= 0 ? sh[2 * i + 1] : 0;
+}
+
+void generate_page(dsocr_engine* e, const dsocr_request* req, const dsocr_decode_params* params,
+                   const dsocr_stop_set* stops, dsocr_stream_cb cb, void* user, int64_t* out_ids, size_t cap,
+                   size_t* n_out, dsocr_stop_hit* hit) {
+    if (!e || !req || !out_ids || !n_out) throw std::runtime_error("EINVAL: NULL argument");
+    std::vector<dsocr::GenRequest> reqs{to_request(*req)};
+    reqs[0].stops = to_stops(stops, (size_t)e->impl->cfg().lang.vocab);
+    auto r = e->impl->generate(reqs, to_params(params), cb, user);
+    if (r[0].size() > cap) throw std::runtime_error("EINVAL: output capacity too small");
+    std::memcpy(out_ids, r[0].data(), r[0].size() * sizeof(int64_t));
+    *n_out = r[0].size();
+    if (hit) write_stop_hit(e->impl->last_stop_hits(), 0, *hit);
+}
+
+// What a batch form asks for beyond the ids.  A new per-request feature adds its fields here and its step to
+// generate_pages; its exported form fills the record.
+struct GenExtras {
+    const dsocr_stop_set* const* stops = nullptr;   // one stop set per request (the list or an entry may be NULL) ...
+    dsocr_stop_hit* hits = nullptr;                 // ... and where every request's hit goes
+    const dsocr_logit_bias* const* bias = nullptr;  // one constraint per request (the list or an entry may be NULL)
+    bool lp_on = false;  // per-token log-probabilities with top_k alternatives into lp[n] (NULL only with n == 0)
+    size_t top_k = 0;
+    dsocr_logprobs* lp = nullptr;
+    float* logits_out = nullptr;  // the raw logits of every step (logits_cap floats)
+    size_t logits_cap = 0;
+};
+
+void generate_pages(dsocr_engine* e, size_t n, const dsocr_request* reqs, const dsocr_decode_params* params,
+                    dsocr_result* results, const GenExtras& x) {
+    if (!e || (!reqs && n) || (!results && n) || (x.lp_on && !x.lp && n) || (!params && (x.lp_on || x.logits_out)))
+        throw std::runtime_error("EINVAL: NULL argument");
+    if (x.top_k > DSOCR_MAX_TOP_LOGPROBS) throw std::runtime_error("EINVAL: top_k above DSOCR_MAX_TOP_LOGPROBS");
+    if (!x.lp_on && x.top_k) throw std::runtime_error("EINVAL: top_k without log-probability buffers");
+    if (x.lp_on) {
+        if (!params->use_cache) throw std::runtime_error("EINVAL: log-probabilities need use_cache = 1");
+        for (size_t i = 0; i < n; ++i) {
+            if (!x.lp[i].token_lp || (x.top_k && (!x.lp[i].top_id || !x.lp[i].top_lp))) throw std::runtime_error("EINVAL: NULL log-probability buffer");
+            if (x.lp[i].cap < (size_t)params->max_new_tokens) throw std::runtime_error("EINVAL: log-probability buffers hold fewer than max_new_tokens entries");
+        }
+    }
+    const size_t vocab = (size_t)e->impl->cfg().lang.vocab;
+    if (x.logits_out) {
+        const size_t need = n * (size_t)params->max_new_tokens * vocab;
+        if (need > x.logits_cap)
+            throw std::runtime_error("EINVAL: logits_out holds " + std::to_string(x.logits_cap) + " floats, the trace needs " +
+                                     std::to_string(need) + " (n * max_new_tokens * vocab)");
+    }
+    std::vector<dsocr::GenRequest> rq;
+    for (size_t i = 0; i < n; ++i) {
+        rq.push_back(to_request(reqs[i]));
+        if (x.bias) rq.back().bias = to_bias(x.bias[i], vocab);
+        if (x.stops) rq.back().stops = to_stops(x.stops[i], vocab);
+    }
+    dsocr::GenParams g = to_params(params);
+    g.trace = x.logits_out;
+    if (x.lp_on) g.lp_k = (int)x.top_k;
+    auto r = e->impl->generate(rq, g, nullptr, nullptr);
+    for (size_t i = 0; i < n; ++i) {
+        write_result(r[i], results[i]);
+        if (x.hits) write_stop_hit(e->impl->last_stop_hits(), i, x.hits[i]);
+        if (x.lp) write_logprobs(e->impl->last_logprobs(), i, x.top_k, x.lp[i]);
+    }
+}
 }  // namespace
 
 static dsocr_status prepare_page_device_as(dsocr_engine* e, const uint8_t* rgb, uint32_t w, uint32_t h,
@@ -408,54 +518,30 @@ dsocr_status dsocr_image_embeddings(dsocr_engine* e, const dsocr_page_pixels* co
 
 dsocr_status dsocr_generate(dsocr_engine* e, const dsocr_request* req, const dsocr_decode_params* params,
                             dsocr_stream_cb cb, void* user, int64_t* out_ids, size_t cap, size_t* n_out) {
-    return guarded([&] {
-        if (!e || !req || !out_ids || !n_out) throw std::runtime_error("EINVAL: NULL argument");
-        std::vector<dsocr::GenRequest> reqs{to_request(*req)};
-        auto r = e->impl->generate(reqs, to_params(params), cb, user);
-        if (r[0].size() > cap) throw std::runtime_error("EINVAL: output capacity too small");
-        std::memcpy(out_ids, r[0].data(), r[0].size() * sizeof(int64_t));
-        *n_out = r[0].size();
-    });
+    return guarded([&] { generate_page(e, req, params, nullptr, cb, user, out_ids, cap, n_out, nullptr); });
+}
+
+dsocr_status dsocr_generate_stop_stream(dsocr_engine* e, const dsocr_request* req, const dsocr_decode_params* params,
+                                        const dsocr_stop_set* stops, dsocr_stream_cb cb, void* user, int64_t* out_ids,
+                                        size_t cap, size_t* n_out, dsocr_stop_hit* hit) {
+    return guarded([&] { generate_page(e, req, params, stops, cb, user, out_ids, cap, n_out, hit); });
 }
 
 dsocr_status dsocr_generate_batch(dsocr_engine* e, size_t n, const dsocr_request* reqs,
                                   const dsocr_decode_params* params, dsocr_result* results) {
-    return guarded([&] {
-        if (!e || (!reqs && n) || (!results && n)) throw std::runtime_error("EINVAL: NULL argument");
-        std::vector<dsocr::GenRequest> rq;
-        for (size_t i = 0; i < n; ++i) rq.push_back(to_request(reqs[i]));
-        auto r = e->impl->generate(rq, to_params(params), nullptr, nullptr);
-        for (size_t i = 0; i < n; ++i) {
-            results[i].status = DSOCR_OK;
-            size_t m = std::min(r[i].size(), results[i].cap);
-            if (results[i].out_ids) std::memcpy(results[i].out_ids, r[i].data(), m * sizeof(int64_t));
-            results[i].n_out = m;
-            if (m < r[i].size()) results[i].status = DSOCR_EINVAL;
-        }
-    });
+    // (NULL params: to_params' error, after the requests')
+    return guarded([&] { generate_pages(e, n, reqs, params, results, GenExtras()); });
 }
 
 dsocr_status dsocr_generate_trace(dsocr_engine* e, size_t n, const dsocr_request* reqs,
                                   const dsocr_decode_params* params, dsocr_result* results, float* logits_out,
                                   size_t logits_cap) {
     return guarded([&] {
-        if (!e || (!reqs && n) || (!results && n) || !logits_out || !params) throw std::runtime_error("EINVAL: NULL argument");
-        const size_t need = n * (size_t)params->max_new_tokens * e->impl->cfg().lang.vocab;
-        if (need > logits_cap)
-            throw std::runtime_error("EINVAL: logits_out holds " + std::to_string(logits_cap) + " floats, the trace needs " +
-                                     std::to_string(need) + " (n * max_new_tokens * vocab)");
-        std::vector<dsocr::GenRequest> rq;
-        for (size_t i = 0; i < n; ++i) rq.push_back(to_request(reqs[i]));
-        dsocr::GenParams g = to_params(params);
-        g.trace = logits_out;
-        auto r = e->impl->generate(rq, g, nullptr, nullptr);
-        for (size_t i = 0; i < n; ++i) {
-            results[i].status = DSOCR_OK;
-            size_t m = std::min(r[i].size(), results[i].cap);
-            if (results[i].out_ids) std::memcpy(results[i].out_ids, r[i].data(), m * sizeof(int64_t));
-            results[i].n_out = m;
-            if (m < r[i].size()) results[i].status = DSOCR_EINVAL;
-        }
+        if (!logits_out || !params) throw std::runtime_error("EINVAL: NULL argument");
+        GenExtras x;
+        x.logits_out = logits_out;
+        x.logits_cap = logits_cap;
+        generate_pages(e, n, reqs, params, results, x);
     });
 }
 
@@ -463,36 +549,34 @@ dsocr_status dsocr_generate_logprobs(dsocr_engine* e, size_t n, const dsocr_requ
                                      const dsocr_decode_params* params, dsocr_result* results, size_t top_k,
                                      dsocr_logprobs* lp) {
     return guarded([&] {
-        if (!e || (!reqs && n) || (!results && n) || (!lp && n) || !params) throw std::runtime_error("EINVAL: NULL argument");
-        if (top_k > DSOCR_MAX_TOP_LOGPROBS) throw std::runtime_error("EINVAL: top_k above DSOCR_MAX_TOP_LOGPROBS");
-        if (!params->use_cache) throw std::runtime_error("EINVAL: log-probabilities need use_cache = 1");
-        for (size_t i = 0; i < n; ++i) {
-            if (!lp[i].token_lp || (top_k && (!lp[i].top_id || !lp[i].top_lp))) throw std::runtime_error("EINVAL: NULL log-probability buffer");
-            if (lp[i].cap < (size_t)params->max_new_tokens) throw std::runtime_error("EINVAL: log-probability buffers hold fewer than max_new_tokens entries");
-        }
-        std::vector<dsocr::GenRequest> rq;
-        for (size_t i = 0; i < n; ++i) rq.push_back(to_request(reqs[i]));
-        dsocr::GenParams g = to_params(params);
-        g.lp_k = (int)top_k;
-        auto r = e->impl->generate(rq, g, nullptr, nullptr);
-        const dsocr::Engine::LogprobRows& rows = e->impl->last_logprobs();
-        for (size_t i = 0; i < n; ++i) {
-            results[i].status = DSOCR_OK;
-            size_t m = std::min(r[i].size(), results[i].cap);
-            if (results[i].out_ids) std::memcpy(results[i].out_ids, r[i].data(), m * sizeof(int64_t));
-            results[i].n_out = m;
-            if (m < r[i].size()) results[i].status = DSOCR_EINVAL;
-            const size_t ne = rows.n.empty() ? 0 : (size_t)rows.n[i];
-            lp[i].n = ne;
-            for (size_t t = 0; t < ne; ++t) {
-                lp[i].token_lp[t] = rows.lp[i * rows.cap + t];
-                for (size_t k = 0; k < top_k; ++k) {
-                    lp[i].top_id[t * top_k + k] = rows.top_id[(i * rows.cap + t) * top_k + k];
-                    lp[i].top_lp[t * top_k + k] = rows.top_lp[(i * rows.cap + t) * top_k + k];
-                }
-            }
-        }
+        GenExtras x;
+        x.lp_on = true;  // whatever lp is: a NULL lp with n > 0 is refused
+        x.top_k = top_k;
+        x.lp = lp;
+        generate_pages(e, n, reqs, params, results, x);
     });
+}
+
+dsocr_status dsocr_generate_stop(dsocr_engine* e, size_t n, const dsocr_request* reqs, const dsocr_decode_params* params,
+                                 dsocr_result* results, const dsocr_stop_set* const* stops, dsocr_stop_hit* hits,
+                                 const dsocr_logit_bias* const* bias, size_t top_k, dsocr_logprobs* lp) {
+    return guarded([&] {
+        if (!params) throw std::runtime_error("EINVAL: NULL argument");
+        GenExtras x;
+        x.stops = stops;
+        x.hits = hits;
+        x.bias = bias;
+        x.lp_on = lp != nullptr;  // (top_k without lp is refused)
+        x.top_k = top_k;
+        x.lp = lp;
+        generate_pages(e, n, reqs, params, results, x);
+    });
+}
+
+dsocr_status dsocr_generate_logit_bias(dsocr_engine* e, size_t n, const dsocr_request* reqs,
+                                       const dsocr_decode_params* params, dsocr_result* results,
+                                       const dsocr_logit_bias* const* bias, size_t top_k, dsocr_logprobs* lp) {
+    return dsocr_generate_stop(e, n, reqs, params, results, nullptr, nullptr, bias, top_k, lp);
 }
 
 dsocr_status dsocr_logit_bias_check(const dsocr_logit_bias* lb, size_t vocab) {
@@ -502,93 +586,10 @@ dsocr_status dsocr_logit_bias_check(const dsocr_logit_bias* lb, size_t vocab) {
     });
 }
 
-// dsocr_generate_logit_bias and dsocr_generate_stop: one constraint and one stop set per request, either list NULL
-static dsocr_status generate_constrained(dsocr_engine* e, size_t n, const dsocr_request* reqs,
-                                         const dsocr_decode_params* params, dsocr_result* results,
-                                         const dsocr_stop_set* const* stops, dsocr_stop_hit* hits,
-                                         const dsocr_logit_bias* const* bias, size_t top_k, dsocr_logprobs* lp) {
-    return guarded([&] {
-        if (!e || (!reqs && n) || (!results && n) || !params) throw std::runtime_error("EINVAL: NULL argument");
-        if (top_k > DSOCR_MAX_TOP_LOGPROBS) throw std::runtime_error("EINVAL: top_k above DSOCR_MAX_TOP_LOGPROBS");
-        if (!lp && top_k) throw std::runtime_error("EINVAL: top_k without log-probability buffers");
-        if (lp) {
-            if (!params->use_cache) throw std::runtime_error("EINVAL: log-probabilities need use_cache = 1");
-            for (size_t i = 0; i < n; ++i) {
-                if (!lp[i].token_lp || (top_k && (!lp[i].top_id || !lp[i].top_lp))) throw std::runtime_error("EINVAL: NULL log-probability buffer");
-                if (lp[i].cap < (size_t)params->max_new_tokens) throw std::runtime_error("EINVAL: log-probability buffers hold fewer than max_new_tokens entries");
-            }
-        }
-        const size_t vocab = (size_t)e->impl->cfg().lang.vocab;
-        std::vector<dsocr::GenRequest> rq;
-        for (size_t i = 0; i < n; ++i) {
-            rq.push_back(to_request(reqs[i]));
-            if (bias) rq.back().bias = to_bias(bias[i], vocab);
-            if (stops) rq.back().stops = to_stops(stops[i], vocab);
-        }
-        dsocr::GenParams g = to_params(params);
-        if (lp) g.lp_k = (int)top_k;
-        auto r = e->impl->generate(rq, g, nullptr, nullptr);
-        const dsocr::Engine::LogprobRows& rows = e->impl->last_logprobs();
-        const std::vector<int>& sh = e->impl->last_stop_hits();
-        for (size_t i = 0; i < n; ++i) {
-            if (hits) {
-                hits[i].seq = sh.size() >= 2 * (i + 1) ? sh[2 * i] : -1;
-                hits[i].match_len = hits[i].seq >= 0 ? sh[2 * i + 1] : 0;
-            }
-            results[i].status = DSOCR_OK;
-            size_t m = std::min(r[i].size(), results[i].cap);
-            if (results[i].out_ids) std::memcpy(results[i].out_ids, r[i].data(), m * sizeof(int64_t));
-            results[i].n_out = m;
-            if (m < r[i].size()) results[i].status = DSOCR_EINVAL;
-            if (!lp) continue;
-            const size_t ne = rows.n.empty() ? 0 : (size_t)rows.n[i];
-            lp[i].n = ne;
-            for (size_t t = 0; t < ne; ++t) {
-                lp[i].token_lp[t] = rows.lp[i * rows.cap + t];
-                for (size_t k = 0; k < top_k; ++k) {
-                    lp[i].top_id[t * top_k + k] = rows.top_id[(i * rows.cap + t) * top_k + k];
-                    lp[i].top_lp[t * top_k + k] = rows.top_lp[(i * rows.cap + t) * top_k + k];
-                }
-            }
-        }
-    });
-}
-
-dsocr_status dsocr_generate_logit_bias(dsocr_engine* e, size_t n, const dsocr_request* reqs,
-                                       const dsocr_decode_params* params, dsocr_result* results,
-                                       const dsocr_logit_bias* const* bias, size_t top_k, dsocr_logprobs* lp) {
-    return generate_constrained(e, n, reqs, params, results, nullptr, nullptr, bias, top_k, lp);
-}
-
 dsocr_status dsocr_stop_set_check(const dsocr_stop_set* ss, size_t vocab) {
     return guarded([&] {
         if (vocab == 0 || vocab > (size_t)INT32_MAX) throw std::runtime_error("EINVAL: vocab must be 1..2^31 - 1");
         (void)to_stops(ss, vocab);
-    });
-}
-
-dsocr_status dsocr_generate_stop(dsocr_engine* e, size_t n, const dsocr_request* reqs, const dsocr_decode_params* params,
-                                 dsocr_result* results, const dsocr_stop_set* const* stops, dsocr_stop_hit* hits,
-                                 const dsocr_logit_bias* const* bias, size_t top_k, dsocr_logprobs* lp) {
-    return generate_constrained(e, n, reqs, params, results, stops, hits, bias, top_k, lp);
-}
-
-dsocr_status dsocr_generate_stop_stream(dsocr_engine* e, const dsocr_request* req, const dsocr_decode_params* params,
-                                        const dsocr_stop_set* stops, dsocr_stream_cb cb, void* user, int64_t* out_ids,
-                                        size_t cap, size_t* n_out, dsocr_stop_hit* hit) {
-    return guarded([&] {
-        if (!e || !req || !out_ids || !n_out) throw std::runtime_error("EINVAL: NULL argument");
-        std::vector<dsocr::GenRequest> reqs{to_request(*req)};
-        reqs[0].stops = to_stops(stops, (size_t)e->impl->cfg().lang.vocab);
-        auto r = e->impl->generate(reqs, to_params(params), cb, user);
-        if (r[0].size() > cap) throw std::runtime_error("EINVAL: output capacity too small");
-        std::memcpy(out_ids, r[0].data(), r[0].size() * sizeof(int64_t));
-        *n_out = r[0].size();
-        if (hit) {
-            const std::vector<int>& sh = e->impl->last_stop_hits();
-            hit->seq = sh.size() >= 2 ? sh[0] : -1;
-            hit->match_len = hit->seq >= 0 ? sh[1] : 0;
-        }
     });
 }
 
@@ -599,7 +600,7 @@ dsocr_status dsocr_session_stage_stop(dsocr_engine* e, const dsocr_stop_set* ss)
         dsocr::Engine::SessionInfo si;
         if (!e->impl->session_info(&si)) throw std::runtime_error("EINVAL: no decode session is open on this engine");
         dsocr::StopSet st = to_stops(ss, (size_t)e->impl->cfg().lang.vocab);
-        if (st.active() && !si.stops) throw std::runtime_error("EINVAL: this session was opened without DSOCR_SESSION_STOP");
+        if (st.active() && !si.feat.stops) throw std::runtime_error("EINVAL: this session was opened without DSOCR_SESSION_STOP");
         e->staged_stop = std::move(st);
     });
 }
@@ -627,7 +628,7 @@ dsocr_status dsocr_session_stage_logit_bias(dsocr_engine* e, const dsocr_logit_b
         dsocr::Engine::SessionInfo si;
         if (!e->impl->session_info(&si)) throw std::runtime_error("EINVAL: no decode session is open on this engine");
         dsocr::LogitBias b = to_bias(lb, (size_t)e->impl->cfg().lang.vocab);
-        if (b.active() && !si.logit_bias) throw std::runtime_error("EINVAL: this session was opened without DSOCR_SESSION_LOGIT_BIAS");
+        if (b.active() && !si.feat.logit_bias) throw std::runtime_error("EINVAL: this session was opened without DSOCR_SESSION_LOGIT_BIAS");
         e->staged_bias = std::move(b);
     });
 }
@@ -637,7 +638,7 @@ dsocr_status dsocr_session_open(dsocr_engine* e, size_t slots, size_t max_contex
     return guarded([&] {
         if (!e) throw std::runtime_error("EINVAL: NULL argument");
         if (slots > 8 || max_context > (size_t)INT32_MAX / 2) throw std::runtime_error("EINVAL: a session has 1..8 slots");
-        e->impl->session_open((int)slots, (int)max_context, to_params(params));
+        e->impl->session_open((int)slots, (int)max_context, to_params(params), dsocr::Engine::SessionFeatures());
     });
 }
 
@@ -645,12 +646,9 @@ dsocr_status dsocr_session_open_ex(dsocr_engine* e, size_t slots, size_t max_con
                                    uint32_t flags) {
     return guarded([&] {
         if (!e) throw std::runtime_error("EINVAL: NULL argument");
-        if (flags & ~(uint32_t)(DSOCR_SESSION_PER_REQUEST | DSOCR_SESSION_LOGPROBS | DSOCR_SESSION_LOGIT_BIAS | DSOCR_SESSION_STOP))
-            throw std::runtime_error("EINVAL: unknown session flags");
+        const dsocr::Engine::SessionFeatures feat = to_features(flags);
         if (slots > 8 || max_context > (size_t)INT32_MAX / 2) throw std::runtime_error("EINVAL: a session has 1..8 slots");
-        e->impl->session_open((int)slots, (int)max_context, to_params(params), (flags & DSOCR_SESSION_PER_REQUEST) != 0,
-                                (flags & DSOCR_SESSION_LOGPROBS) != 0, (flags & DSOCR_SESSION_LOGIT_BIAS) != 0,
-                                (flags & DSOCR_SESSION_STOP) != 0);
+        e->impl->session_open((int)slots, (int)max_context, to_params(params), feat);
     });
 }
 
@@ -744,9 +742,7 @@ dsocr_status dsocr_session_info(const dsocr_engine* e, dsocr_session_desc* out) 
         out->slots = (size_t)si.slots; out->active = (size_t)si.active; out->max_context = (size_t)si.max_context;
         out->out_cap = (size_t)si.out_cap; out->kv_cap = (size_t)si.kv_cap; out->burst_cap = (size_t)si.burst_cap;
         out->steps = si.steps;
-        out->flags = (si.per_request ? DSOCR_SESSION_PER_REQUEST : 0u) | (si.logprobs ? DSOCR_SESSION_LOGPROBS : 0u) |
-                     (si.logit_bias ? DSOCR_SESSION_LOGIT_BIAS : 0u) | (si.stops ? DSOCR_SESSION_STOP : 0u) |
-                     (si.pending ? DSOCR_SESSION_ADMIT_PENDING : 0u);
+        out->flags = feature_flags(si.feat) | (si.pending ? DSOCR_SESSION_ADMIT_PENDING : 0u);
     });
 }
 

@@ -168,12 +168,9 @@ struct Engine::Session {
     static constexpr int kBurstCap = 8;  // k_max: the most steps one session_step replays
     int S = 0, n = 0, max_context = 0;
     GenParams p;
-    bool per_request = false;  // every slot has its own RowParams; the head is chosen per burst
+    SessionFeatures feat;   // what the session was opened with: which rows every slot has (RowParams, s_lp*, s_bias, s_stop*)
     bool screened = false;  // fixed parameters: the screened head at every n (else the exact head at every n)
     int* stage = nullptr;   // ss_stage: an admission's staged slot rows
-    bool logprobs = false;  // every step and admission writes log-probability entries (s_lp*): the exact head at every n
-    bool logit_bias = false;  // every slot has a dense bias row (s_bias); a burst with a constrained slot runs the exact head
-    bool stops = false;  // every slot has a stop table (s_stop*); a burst with a slot that carries a stop set runs the match launch
     struct Slot {
         bool stopped = false;  // the slot's request carried a stop set (rows_.stop_n[slot] != 0)
         bool biased = false;  // the slot's device flag (rows_.bias_on): its request carried a constraint
@@ -2768,8 +2765,7 @@ static RowParams resolve_row_params(const GenParams& p) {
     return r;
 }
 
-void Engine::session_open(int S, int max_context, const GenParams& p, bool per_request, bool logprobs, bool logit_bias,
-                          bool stops) {
+void Engine::session_open(int S, int max_context, const GenParams& p, const SessionFeatures& feat) {
     if (sess_) throw std::runtime_error("EINVAL: a decode session is already open on this engine");
     if (S < 1 || S > 8) throw std::runtime_error("EINVAL: a session has 1..8 slots");
     if (!p.use_cache || p.trace) throw std::runtime_error("EINVAL: a session decodes with the K/V cache and without a logits trace");
@@ -2783,10 +2779,7 @@ void Engine::session_open(int S, int max_context, const GenParams& p, bool per_r
     hipStream_t st = stream_;
     auto sp = std::make_unique<Session>();
     Session& s = *sp;
-    s.S = S; s.max_context = max_context; s.p = p; s.per_request = per_request;
-    s.logprobs = logprobs;
-    s.logit_bias = logit_bias;
-    s.stops = stops;
+    s.S = S; s.max_context = max_context; s.p = p; s.feat = feat;
     // Capacity invariant.  The selection kernels advance kv_pos of every row on every step, done or not, so a
     // finished page that waits for the end of its burst keeps appending K/V rows.  A page is admitted only with
     // prompt + max_new + 1 <= max_context and produces its last token at kv_pos <= prompt + max_new - 1; it is
@@ -2796,24 +2789,24 @@ void Engine::session_open(int S, int max_context, const GenParams& p, bool per_r
     // at out_cap (dec_sample: out_len < out_cap, n < ctx_cap).
     DecodeRowsSpec spec;
     spec.rows = S; spec.Lcap = max_context + Session::kBurstCap; spec.ctx_cap = spec.Lcap; spec.out_cap = (long)p.max_new;
-    s.screened = !p.do_sample && !per_request && !logprobs;
+    s.screened = !p.do_sample && !feat.per_request && !feat.logprobs;
     for (int n = 1; n <= S; ++n) s.screened = s.screened && screen_applies(n, p.rep_penalty);
     // per-request parameters: what both heads need at every n, so nothing grows after the freeze (any slot may
     // sample: the sampler's scratch and RNG rows for all of them; the ban rows are always kept and both final
     // kernels write them every step: either head can take over from the other at a step boundary)
-    spec.sampler = p.do_sample || per_request;
-    spec.ban = s.screened || per_request;
+    spec.sampler = p.do_sample || feat.per_request;
+    spec.ban = s.screened || feat.per_request;
     spec.rowpar = true;
     spec.handoff_max = true;  // the step runs at every n <= S
     spec.zero_fill = true;    // the dry steps below read kv_pos 0 and a zero input row
-    if (logit_bias) {         // every slot's row, and one admission's list at a time (at most vocab pairs)
+    if (feat.logit_bias) {    // every slot's row, and one admission's list at a time (at most vocab pairs)
         spec.bias = true;
         spec.bias_stage = (size_t)L.vocab;
     }
-    spec.stops = stops;  // every slot's table, and one admission's list at a time
-    if (logprobs) {  // (the raw logits at the context ids too where a penalty can apply)
+    spec.stops = feat.stops;  // every slot's table, and one admission's list at a time
+    if (feat.logprobs) {  // (the raw logits at the context ids too where a penalty can apply)
         spec.lp_k = LP_MAX_TOP;
-        spec.lp_side = per_request || rep_penalty_active(p.rep_penalty);
+        spec.lp_side = feat.per_request || rep_penalty_active(p.rep_penalty);
     }
     s.slot.resize(S);
     s.pin = PinnedBuffer<int>(2 * S + 1);
@@ -2868,7 +2861,7 @@ void Engine::session_admit_checks(const Session& s, const GenRequest& rq, const 
     const size_t max_new = rp.max_new;
     const int V = cfg_.lang.vocab;
     if (!rp.use_cache || rp.trace) throw std::runtime_error("EINVAL: a session decodes with the K/V cache and without a logits trace");
-    if (!s.per_request) {
+    if (!s.feat.per_request) {
         const GenParams& q = s.p;
         if (rp.do_sample != q.do_sample || rp.temperature != q.temperature || rp.top_p != q.top_p || rp.top_k != q.top_k ||
             rp.rep_penalty != q.rep_penalty || rp.ngram != q.ngram || rp.eos != q.eos || rp.ignore_eos != q.ignore_eos)
@@ -2876,11 +2869,11 @@ void Engine::session_admit_checks(const Session& s, const GenRequest& rq, const 
                                      "per request): open it with DSOCR_SESSION_PER_REQUEST");
     }
     if (rq.bias.active()) {
-        if (!s.logit_bias) throw std::runtime_error("EINVAL: this session was opened without DSOCR_SESSION_LOGIT_BIAS");
+        if (!s.feat.logit_bias) throw std::runtime_error("EINVAL: this session was opened without DSOCR_SESSION_LOGIT_BIAS");
         validate_logit_bias(rq.bias, V);
     }
     if (rq.stops.active()) {
-        if (!s.stops) throw std::runtime_error("EINVAL: this session was opened without DSOCR_SESSION_STOP");
+        if (!s.feat.stops) throw std::runtime_error("EINVAL: this session was opened without DSOCR_SESSION_STOP");
         validate_stop_set(rq.stops, V);
     }
     if (s.pending) throw std::runtime_error("EINVAL: a chunked admission is pending (advance it to the end or cancel it)");
@@ -2920,7 +2913,7 @@ int Engine::session_admit(const GenRequest& rq, const GenParams& rp) {
     const RowParams row = resolve_row_params(rp);
     const int slot = s.n;
     const std::vector<GenRequest> reqs{rq};
-    GenParams gp = s.per_request ? rp : s.p;
+    GenParams gp = s.feat.per_request ? rp : s.p;
     gp.max_new = max_new;
     GenState g(reqs, gp, nullptr, nullptr);
     embed_pages(g);
@@ -2944,7 +2937,7 @@ int Engine::session_admit_tail(Session& s, const GenRequest& rq, const GenParams
     int* h = (int*)pinned("ss_stage", stage_ints * 4);
     std::memset(h, 0, ((size_t)SS_HEAD + RNG_WORDS) * 4);
     h[SS_CTX_LEN] = (int)P; h[SS_KV_POS] = (int)P - 1; h[SS_KV_LEN] = (int)P;
-    if (s.per_request ? row.do_sample != 0 : s.p.do_sample) {
+    if (s.feat.per_request ? row.do_sample != 0 : s.p.do_sample) {
         if (!seed_set) {
             std::random_device rd;
             seed = ((uint64_t)rd() << 32) ^ rd();
@@ -2952,7 +2945,7 @@ int Engine::session_admit_tail(Session& s, const GenRequest& rq, const GenParams
         const std::vector<uint32_t> rng = rng_state_from_u64(seed);
         std::memcpy(h + SS_HEAD, rng.data(), sizeof(uint32_t) * RNG_WORDS);
     }
-    if (s.per_request) std::memcpy(h + SS_ROWPAR, &row, sizeof(RowParams));
+    if (s.feat.per_request) std::memcpy(h + SS_ROWPAR, &row, sizeof(RowParams));
     std::memcpy(h + SS_HEAD + RNG_WORDS, rq.ids.data(), P * 4);
     HIP_CHECK(hipMemcpyAsync(s.stage, h, stage_ints * 4, hipMemcpyHostToDevice, st));
     SlotInitArgs ia;
@@ -2960,28 +2953,28 @@ int Engine::session_admit_tail(Session& s, const GenRequest& rq, const GenParams
     ia.stage = s.stage; ia.slot = slot; ia.ctx = r.ctx; ia.ctx_cap = r.ctx_cap; ia.ctx_len = r.ctx_len;
     ia.kv_pos = r.kv_pos; ia.kv_len = r.kv_len; ia.done = r.done; ia.out_len = r.out_len; ia.tok = r.tok;
     ia.rng = r.rng; ia.rng_words = RNG_WORDS; ia.ban = r.ban; ia.ban_ld = r.ban_ld;
-    if (s.per_request) ia.rowpar = r.rowpar;
+    if (s.feat.per_request) ia.rowpar = r.rowpar;
     DecSampleArgs sa;
     SampleArgs pen;
-    sample_args(1, slot, s.p, s.per_request, sa, pen);
+    sample_args(1, slot, s.p, s.feat.per_request, sa, pen);
     DecLpArgs lp;
-    if (s.logprobs) {  // (slot init takes the rows' bases)
+    if (s.feat.logprobs) {  // (slot init takes the rows' bases)
         ia.lp = r.lp; ia.lp_top_id = r.lp_top_id; ia.lp_top = r.lp_top; ia.lp_k = r.lp_k; ia.out_cap = r.out_cap;
         lp = lp_args(sa, slot);
     }
     launch_session_slot_init(ia, st);
-    if (s.logit_bias) {  // the slot's constraint (none: the flag alone is cleared), then the add on the prefill's logits
+    if (s.feat.logit_bias) {  // the slot's constraint (none: the flag alone is cleared), then the add on the prefill's logits
         build_logit_bias(rq.bias, slot, 0);
         launch_dec_logit_bias(bias_args(sa, slot), st);
     }
-    if (s.logprobs) launch_dec_lp_partial(lp, st);
+    if (s.feat.logprobs) launch_dec_lp_partial(lp, st);
     launch_rep_penalty(pen, st);
     launch_dec_sample(sa, st);  // the first token, its embedding into the slot's s_x row, the ban list
-    if (s.stops) {  // the slot's table (none: the count alone is cleared), then the match on this first selection
+    if (s.feat.stops) {  // the slot's table (none: the count alone is cleared), then the match on this first selection
         build_stop_table(rq.stops, slot, 0);
         if (rq.stops.active()) stop_match(sa, slot);
     }
-    if (s.logprobs) launch_dec_lp_final(lp, st);  // entry 0 of the slot
+    if (s.feat.logprobs) launch_dec_lp_final(lp, st);  // entry 0 of the slot
     if (finish) {  // (else the caller has a launch to add before the one refill and synchronisation)
         refill_handoffs();
         HIP_CHECK(hipStreamSynchronize(st));
@@ -3056,7 +3049,7 @@ int Engine::session_admit_prefix(int handle, const GenRequest& rq, const GenPara
     launch_session_prefix_copy(prefix_copy_args(L, kc_, vc_, s.S, rows_.Lcap, page_stride_, head_stride_, slot, rows,
                                                 (float*)e.kv.get(), 1), st);
     const std::vector<GenRequest> reqs{rq};
-    GenParams gp = s.per_request ? rp : s.p;
+    GenParams gp = s.feat.per_request ? rp : s.p;
     gp.max_new = rp.max_new;
     GenState g(reqs, gp, nullptr, nullptr);
     g.prompt_len = {P};
@@ -3103,7 +3096,7 @@ int Engine::session_admit_begin(const GenRequest& rq, const GenParams& rp, int c
     }
     pa->rp = rp;
     pa->row = resolve_row_params(rp);
-    pa->gp = s.per_request ? rp : s.p;
+    pa->gp = s.feat.per_request ? rp : s.p;
     pa->gp.max_new = rp.max_new;
     pa->g = std::make_unique<GenState>(pa->reqs, pa->gp, nullptr, nullptr);
     pa->g->extra.resize(1);
@@ -3201,9 +3194,9 @@ Engine::PrefixStats Engine::session_prefix_stats() const {
 void Engine::session_step_body(Session& s, bool screened, bool stops) {
     DecSampleArgs sa;
     SampleArgs pen;
-    sample_args(s.n, 0, s.p, s.per_request, sa, pen);
+    sample_args(s.n, 0, s.p, s.feat.per_request, sa, pen);
     decode_step(s.n, rows_.Lcap);
-    if (s.logprobs) {
+    if (s.feat.logprobs) {
         const DecLpArgs lp = lp_args(sa, 0);
         decode_head(s.n, sa, pen, screened, &lp, stops);
     } else {
@@ -3215,10 +3208,10 @@ void Engine::session_step_body(Session& s, bool screened, bool stops) {
 // slot is greedy with penalty 1.0 and the screened head applies at this n; it changes only where the set of
 // active slots does (admit, retire), and the ban rows both final kernels keep make the change a step boundary
 bool Engine::session_head_screened(const Session& s) const {
-    if (s.logprobs) return false;  // the screened head never forms the logits
+    if (s.feat.logprobs) return false;  // the screened head never forms the logits
     for (int b = 0; b < s.n; ++b)
         if (s.slot[b].biased) return false;  // ... which a constraint is added to
-    if (!s.per_request) return s.screened;
+    if (!s.feat.per_request) return s.screened;
     for (int b = 0; b < s.n; ++b)
         if (s.slot[b].rp.do_sample || s.slot[b].rp.rep_penalty != 1.0f) return false;
     return screen_applies(s.n, 1.0f);
@@ -3324,23 +3317,23 @@ void Engine::session_slot_move(Session& s, int src, int dst, int rows_bound) {
     m.kv_len = r.kv_len; m.kv_pos = r.kv_pos; m.ctx = r.ctx; m.ctx_cap = r.ctx_cap; m.ctx_len = r.ctx_len;
     m.out = r.out; m.out_cap = r.out_cap; m.out_len = r.out_len; m.done = r.done; m.tok = r.tok;
     m.rng = r.rng; m.rng_words = RNG_WORDS; m.ban = r.ban; m.ban_ld = r.ban_ld; m.x = r.x; m.H = L.hidden;
-    if (s.per_request) m.rowpar = r.rowpar;
-    if (s.logprobs) { m.lp = r.lp; m.lp_top_id = r.lp_top_id; m.lp_top = r.lp_top; m.lp_k = r.lp_k; }
+    if (s.feat.per_request) m.rowpar = r.rowpar;
+    if (s.feat.logprobs) { m.lp = r.lp; m.lp_top_id = r.lp_top_id; m.lp_top = r.lp_top; m.lp_k = r.lp_k; }
     launch_session_slot_move(m, stream_);
-    if (s.logit_bias) {  // the constraint travels as a copy of its row (an unconstrained page: the flag alone)
+    if (s.feat.logit_bias) {  // the constraint travels as a copy of its row (an unconstrained page: the flag alone)
         if (s.slot[src].biased)
             HIP_CHECK(hipMemcpyAsync(r.bias + (size_t)dst * r.bias_ld, r.bias + (size_t)src * r.bias_ld,
                                      sizeof(float) * r.bias_ld, hipMemcpyDeviceToDevice, stream_));
         HIP_CHECK(hipMemcpyAsync(r.bias_on + dst, r.bias_on + src, sizeof(int), hipMemcpyDeviceToDevice, stream_));
     }
     // the stop set travels with its page: a launch of its own (a page without one: the count, seen and hit alone)
-    if (s.stops) launch_stop_slot_move(r.stop_tab, r.stop_n, r.stop_seen, r.stop_hit, src, dst, stream_);
+    if (s.feat.stops) launch_stop_slot_move(r.stop_tab, r.stop_n, r.stop_seen, r.stop_hit, src, dst, stream_);
     s.slot[dst] = s.slot[src];
 }
 
 void Engine::session_stop_hit(int slot, int* seq, int* match_len) {
     Session& s = open_session();
-    if (!s.stops) throw std::runtime_error("EINVAL: this session was opened without DSOCR_SESSION_STOP");
+    if (!s.feat.stops) throw std::runtime_error("EINVAL: this session was opened without DSOCR_SESSION_STOP");
     if (slot < 0 || slot >= s.n) throw std::runtime_error("EINVAL: slot " + std::to_string(slot) + " is not active");
     HIP_CHECK(hipStreamSynchronize(stream_));
     int hit[2] = {-1, 0}, len = 0;
@@ -3356,7 +3349,7 @@ void Engine::session_stop_hit(int slot, int* seq, int* match_len) {
 void Engine::session_logprobs(int slot, size_t first, size_t count, int top_k, float* token_lp, int64_t* top_id,
                               float* top_lp) {
     Session& s = open_session();
-    if (!s.logprobs) throw std::runtime_error("EINVAL: this session was opened without DSOCR_SESSION_LOGPROBS");
+    if (!s.feat.logprobs) throw std::runtime_error("EINVAL: this session was opened without DSOCR_SESSION_LOGPROBS");
     if (slot < 0 || slot >= s.n) throw std::runtime_error("EINVAL: slot " + std::to_string(slot) + " is not active");
     if (top_k < 0 || top_k > LP_MAX_TOP) throw std::runtime_error("EINVAL: top_k must be 0..20");
     if (count && (!token_lp || (top_k && (!top_id || !top_lp)))) throw std::runtime_error("EINVAL: NULL argument");
@@ -3401,10 +3394,7 @@ bool Engine::session_info(SessionInfo* out) const {
         out->out_cap = (int)rows_.out_cap; out->kv_cap = rows_.Lcap; out->burst_cap = Session::kBurstCap;
         out->steps = sess_->steps;
         out->steps_screened = sess_->head_steps[1]; out->steps_exact = sess_->head_steps[0];
-        out->per_request = sess_->per_request;
-        out->logprobs = sess_->logprobs;
-        out->logit_bias = sess_->logit_bias;
-        out->stops = sess_->stops;
+        out->feat = sess_->feat;
         out->chunk_attn_launches = chunk_attn_launches_;
         if (const PendingAdmit* pa = sess_->pending.get()) {
             out->pending = true;

@@ -306,14 +306,26 @@ class Engine {
     // ---- decode sessions: a long-lived batch of up to `slots` pages; pages are admitted
     // (vision + prefill into their own slot) and retired between bursts of the unchanged decode step.  Active
     // pages occupy slots [0, active).  A session and generate / profile_decode exclude each other (EINVAL).
+    // What a session is opened with, fixed until it closes (the DSOCR_SESSION_* bits):
+    struct SessionFeatures {
+        // p are the defaults and every admission brings its own selection parameters (a RowParams record per slot,
+        // read by the per-row selection kernels); the head is chosen per burst: screened while every active slot is
+        // greedy without a penalty, else the exact head with both selectors
+        bool per_request = false;
+        // every slot keeps out_cap x LP_MAX_TOP log-probability entries; the exact head runs at every n
+        bool logprobs = false;
+        // every slot keeps a dense bias row; an admission may carry a constraint (GenRequest::bias), and a burst runs
+        // the exact head iff an active slot carries one
+        bool logit_bias = false;
+        // every slot keeps a stop table; an admission may carry a stop set (GenRequest::stops), and a burst's step
+        // graph contains the match launch iff an active slot carries one
+        bool stops = false;
+    };
     struct SessionInfo {
         int slots = 0, active = 0, max_context = 0, out_cap = 0, kv_cap = 0, burst_cap = 0;
         size_t steps = 0;  // decode steps replayed since the session opened
         size_t steps_screened = 0, steps_exact = 0;  // ... under the screened / the exact lm_head + selection
-        bool per_request = false;
-        bool logprobs = false;
-        bool logit_bias = false;
-        bool stops = false;
+        SessionFeatures feat;
         // a chunked admission in flight (session_admit_begin): prompt rows prefilled so far / in all, slices run
         bool pending = false;
         int pending_rows_done = 0, pending_rows_total = 0, pending_slices = 0;
@@ -325,16 +337,7 @@ class Engine {
         std::vector<int64_t> fresh;  // the tokens since the last poll
     };
     // p: the session's sampling parameters (use_cache must be set, no trace); p.max_new = out_cap
-    // per_request: p are the defaults and every admission brings its own selection parameters (a RowParams record
-    // per slot, read by the per-row selection kernels); the head is chosen per burst: screened while every active
-    // slot is greedy without a penalty, else the exact head with both selectors
-    // logprobs: every slot keeps out_cap x LP_MAX_TOP log-probability entries; the exact head runs at every n
-    // logit_bias: every slot keeps a dense bias row; an admission may carry a constraint (GenRequest::bias), and a
-    // burst runs the exact head iff an active slot carries one
-    // stops: every slot keeps a stop table; an admission may carry a stop set (GenRequest::stops), and a burst's
-    // step graph contains the match launch iff an active slot carries one
-    void session_open(int slots, int max_context, const GenParams& p, bool per_request = false, bool logprobs = false,
-                      bool logit_bias = false, bool stops = false);
+    void session_open(int slots, int max_context, const GenParams& p, const SessionFeatures& feat);
     // {seq, match_len} of a live slot ({-1, 0}: no stop fired within its max_new_tokens)
     void session_stop_hit(int slot, int* seq, int* match_len);
     // entries [first, first + count) of a live slot, trimmed to top_k <= LP_MAX_TOP alternatives ([count][top_k])

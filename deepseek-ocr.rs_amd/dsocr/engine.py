@@ -227,6 +227,64 @@ def _params_c(p: DecodeParameters, eos: int, ignore_eos: bool) -> DecodeParamsC:
                          has_seed=0 if p.seed is None else 1)
 
 
+# ---------------------------------------------------------------------- what the generate* methods marshal with
+# (a new per-request feature adds its record here: a `_x_c` like `_stop_c` / `_bias_c`, passed through `_ptr_array`)
+def _check_top_k(top_k) -> None:
+    if top_k is not None and not 0 <= int(top_k) <= MAX_TOP_LOGPROBS:
+        raise DsocrError(1, f"top_k must be 0..{MAX_TOP_LOGPROBS}")
+
+
+def _ptr_array(T, recs, keep):
+    """``POINTER(T) * n`` over a list of optional records (None: a NULL entry)."""
+    keep.append(recs)
+    return (C.POINTER(T) * len(recs))(*[C.pointer(r) if r is not None else C.POINTER(T)() for r in recs])
+
+
+def _stream_cb(stream: Optional[Callable]):
+    """The C callback of ``stream(n, tokens)`` (None: a NULL one)."""
+    return STREAM_CB(lambda k, toks, _u: stream(k, [toks[i] for i in range(k)])) if stream else STREAM_CB()
+
+
+class _Batch:
+    """The ``RequestC`` and ``ResultC`` arrays of a batch call over ``requests`` (each ``(ids, mask, page_or_None,
+    image_rows_or_None)``), with room for ``cap`` ids per page; ``keep`` holds what the arrays point into."""
+
+    def __init__(self, engine, requests, params):
+        self.keep = []
+        self.n, self.cap = len(requests), max(params.max_new_tokens, 1)
+        self.reqs = (RequestC * self.n)(*[engine._request(*r, self.keep) for r in requests])
+        self._outs = [np.empty(self.cap, np.int64) for _ in requests]
+        self.res = (ResultC * self.n)(*[ResultC(o.ctypes.data_as(C.POINTER(C.c_int64)), len(o), 0, 0)
+                                        for o in self._outs])
+
+    def ids(self) -> list:
+        """The ids per page, after the call."""
+        return [self._outs[i][:self.res[i].n_out].tolist() for i in range(self.n)]
+
+
+class _LogprobBuffers:
+    """The log-probability buffers of ``n`` pages (``cap`` entries of ``k`` alternatives each) and their ``LogprobsC``
+    array ``c``."""
+
+    def __init__(self, n: int, cap: int, k: int):
+        self.k = k
+        self._tlp = [np.zeros(cap, np.float32) for _ in range(n)]
+        self._tid = [np.zeros((cap, max(k, 1)), np.int64) for _ in range(n)]
+        self._tl = [np.zeros((cap, max(k, 1)), np.float32) for _ in range(n)]
+        self.c = (LogprobsC * n)(*[LogprobsC(self._tlp[i].ctypes.data_as(C.POINTER(C.c_float)),
+                                             self._tid[i].ctypes.data_as(C.POINTER(C.c_int64)),
+                                             self._tl[i].ctypes.data_as(C.POINTER(C.c_float)), cap, 0)
+                                   for i in range(n)])
+
+    def unpack(self) -> tuple:
+        """After the call, per page: (token log-probabilities float32 [n_out], alternative ids int64 [n_out][k], their
+        log-probabilities float32 [n_out][k])."""
+        k, cnt = self.k, [int(r.n) for r in self.c]
+        return ([a[:m].copy() for a, m in zip(self._tlp, cnt)],
+                [a.reshape(-1)[:m * k].reshape(m, k).copy() for a, m in zip(self._tid, cnt)],
+                [a.reshape(-1)[:m * k].reshape(m, k).copy() for a, m in zip(self._tl, cnt)])
+
+
 class DeepseekOcrEngine:
     """OcrEngine implementation backed by the MI355X engine (one per GPU)."""
 
@@ -319,61 +377,39 @@ class DeepseekOcrEngine:
         pc = _params_c(params, self.eos_token_id, ignore_eos)
         out = np.empty(max(params.max_new_tokens, 1), np.int64)
         n = C.c_size_t()
-        cb = STREAM_CB(lambda k, toks, _u: stream(k, [toks[i] for i in range(k)])) if stream else STREAM_CB()
+        cb = _stream_cb(stream)
         check(lib().dsocr_generate(self._h, C.byref(req), C.byref(pc), cb, None, out.ctypes.data_as(C.c_void_p),
                                    len(out), C.byref(n)))
         return out[:n.value].tolist()
 
     def generate_batch(self, requests, params: DecodeParameters = DecodeParameters(), ignore_eos: bool = False):
         """requests: list of (ids, mask, page_or_None, image_rows_or_None)."""
-        keep = []
-        reqs = (RequestC * len(requests))(*[self._request(*r, keep) for r in requests])
-        outs = [np.empty(max(params.max_new_tokens, 1), np.int64) for _ in requests]
-        res = (ResultC * len(requests))(*[ResultC(o.ctypes.data_as(C.POINTER(C.c_int64)), len(o), 0, 0)
-                                          for o in outs])
+        b = _Batch(self, requests, params)
         pc = _params_c(params, self.eos_token_id, ignore_eos)
-        check(lib().dsocr_generate_batch(self._h, len(requests), reqs, C.byref(pc), res))
-        return [outs[i][:res[i].n_out].tolist() for i in range(len(requests))]
+        check(lib().dsocr_generate_batch(self._h, b.n, b.reqs, C.byref(pc), b.res))
+        return b.ids()
 
     def generate_trace(self, requests, params: DecodeParameters = DecodeParameters(), ignore_eos: bool = False):
         """generate_batch + the raw logits of every step (dsocr_generate_trace): returns
         (ids per page, logits [n][max_new][vocab] float32; rows past a page's last token are 0)."""
-        keep = []
-        reqs = (RequestC * len(requests))(*[self._request(*r, keep) for r in requests])
-        outs = [np.empty(max(params.max_new_tokens, 1), np.int64) for _ in requests]
-        res = (ResultC * len(requests))(*[ResultC(o.ctypes.data_as(C.POINTER(C.c_int64)), len(o), 0, 0)
-                                          for o in outs])
-        logits = np.zeros((len(requests), max(params.max_new_tokens, 1), self.vocab), np.float32)
+        b = _Batch(self, requests, params)
+        logits = np.zeros((b.n, b.cap, self.vocab), np.float32)
         pc = _params_c(params, self.eos_token_id, ignore_eos)
-        check(lib().dsocr_generate_trace(self._h, len(requests), reqs, C.byref(pc), res,
+        check(lib().dsocr_generate_trace(self._h, b.n, b.reqs, C.byref(pc), b.res,
                                          logits.ctypes.data_as(C.c_void_p), logits.size))
-        return [outs[i][:res[i].n_out].tolist() for i in range(len(requests))], logits
+        return b.ids(), logits
 
     def generate_logprobs(self, requests, top_k: int = 0, params: DecodeParameters = DecodeParameters(),
                           ignore_eos: bool = False):
         """generate_batch + per-token log-probabilities (dsocr_generate_logprobs): returns (ids per page,
         token log-probabilities per page float32 [n_out], alternative ids per page int64 [n_out][top_k], their
         log-probabilities float32 [n_out][top_k])."""
-        if not 0 <= int(top_k) <= MAX_TOP_LOGPROBS:
-            raise DsocrError(1, f"top_k must be 0..{MAX_TOP_LOGPROBS}")
-        keep = []
-        n, k, cap = len(requests), int(top_k), max(params.max_new_tokens, 1)
-        reqs = (RequestC * n)(*[self._request(*r, keep) for r in requests])
-        outs = [np.empty(cap, np.int64) for _ in requests]
-        res = (ResultC * n)(*[ResultC(o.ctypes.data_as(C.POINTER(C.c_int64)), len(o), 0, 0) for o in outs])
-        tlp = [np.zeros(cap, np.float32) for _ in requests]
-        tid = [np.zeros((cap, max(k, 1)), np.int64) for _ in requests]
-        tl = [np.zeros((cap, max(k, 1)), np.float32) for _ in requests]
-        lps = (LogprobsC * n)(*[LogprobsC(tlp[i].ctypes.data_as(C.POINTER(C.c_float)),
-                                         tid[i].ctypes.data_as(C.POINTER(C.c_int64)),
-                                         tl[i].ctypes.data_as(C.POINTER(C.c_float)), cap, 0) for i in range(n)])
+        _check_top_k(int(top_k))
+        b = _Batch(self, requests, params)
+        lp = _LogprobBuffers(b.n, b.cap, int(top_k))
         pc = _params_c(params, self.eos_token_id, ignore_eos)
-        check(lib().dsocr_generate_logprobs(self._h, n, reqs, C.byref(pc), res, k, lps))
-        ids = [outs[i][:res[i].n_out].tolist() for i in range(n)]
-        cnt = [int(lps[i].n) for i in range(n)]
-        return (ids, [tlp[i][:cnt[i]].copy() for i in range(n)],
-                [tid[i].reshape(-1)[:cnt[i] * k].reshape(cnt[i], k).copy() for i in range(n)],
-                [tl[i].reshape(-1)[:cnt[i] * k].reshape(cnt[i], k).copy() for i in range(n)])
+        check(lib().dsocr_generate_logprobs(self._h, b.n, b.reqs, C.byref(pc), b.res, lp.k, lp.c))
+        return (b.ids(), *lp.unpack())
 
     def generate_constrained(self, requests, constraints, params: DecodeParameters = DecodeParameters(),
                              ignore_eos: bool = False, top_k: Optional[int] = None):
@@ -382,31 +418,14 @@ class DeepseekOcrEngine:
         ``top_k`` (0..20) the tuple ``generate_logprobs`` returns, of the constrained distribution."""
         if len(constraints) != len(requests):
             raise DsocrError(1, "one constraint (or None) per request")
-        if top_k is not None and not 0 <= int(top_k) <= MAX_TOP_LOGPROBS:
-            raise DsocrError(1, f"top_k must be 0..{MAX_TOP_LOGPROBS}")
-        keep = []
-        n, k, cap = len(requests), int(top_k or 0), max(params.max_new_tokens, 1)
-        reqs = (RequestC * n)(*[self._request(*r, keep) for r in requests])
-        outs = [np.empty(cap, np.int64) for _ in requests]
-        res = (ResultC * n)(*[ResultC(o.ctypes.data_as(C.POINTER(C.c_int64)), len(o), 0, 0) for o in outs])
-        recs = [_bias_c(c, keep) for c in constraints]
-        bias = (C.POINTER(LogitBiasC) * n)(*[C.pointer(r) if r is not None else C.POINTER(LogitBiasC)() for r in recs])
+        _check_top_k(top_k)
+        b = _Batch(self, requests, params)
+        bias = _ptr_array(LogitBiasC, [_bias_c(c, b.keep) for c in constraints], b.keep)
+        lp = None if top_k is None else _LogprobBuffers(b.n, b.cap, int(top_k))
         pc = _params_c(params, self.eos_token_id, ignore_eos)
-        if top_k is None:
-            check(lib().dsocr_generate_logit_bias(self._h, n, reqs, C.byref(pc), res, bias, 0, None))
-            return [outs[i][:res[i].n_out].tolist() for i in range(n)]
-        tlp = [np.zeros(cap, np.float32) for _ in requests]
-        tid = [np.zeros((cap, max(k, 1)), np.int64) for _ in requests]
-        tl = [np.zeros((cap, max(k, 1)), np.float32) for _ in requests]
-        lps = (LogprobsC * n)(*[LogprobsC(tlp[i].ctypes.data_as(C.POINTER(C.c_float)),
-                                         tid[i].ctypes.data_as(C.POINTER(C.c_int64)),
-                                         tl[i].ctypes.data_as(C.POINTER(C.c_float)), cap, 0) for i in range(n)])
-        check(lib().dsocr_generate_logit_bias(self._h, n, reqs, C.byref(pc), res, bias, k, lps))
-        ids = [outs[i][:res[i].n_out].tolist() for i in range(n)]
-        cnt = [int(lps[i].n) for i in range(n)]
-        return (ids, [tlp[i][:cnt[i]].copy() for i in range(n)],
-                [tid[i].reshape(-1)[:cnt[i] * k].reshape(cnt[i], k).copy() for i in range(n)],
-                [tl[i].reshape(-1)[:cnt[i] * k].reshape(cnt[i], k).copy() for i in range(n)])
+        check(lib().dsocr_generate_logit_bias(self._h, b.n, b.reqs, C.byref(pc), b.res, bias, lp.k if lp else 0,
+                                              lp.c if lp else None))
+        return (b.ids(), *lp.unpack()) if lp else b.ids()
 
     def generate_stops(self, requests, stop_sets, params: DecodeParameters = DecodeParameters(), ignore_eos: bool = False,
                        top_k: Optional[int] = None, constraints=None):
@@ -417,38 +436,19 @@ class DeepseekOcrEngine:
         returns."""
         if len(stop_sets) != len(requests) or (constraints is not None and len(constraints) != len(requests)):
             raise DsocrError(1, "one stop set (or None) per request")
-        if top_k is not None and not 0 <= int(top_k) <= MAX_TOP_LOGPROBS:
-            raise DsocrError(1, f"top_k must be 0..{MAX_TOP_LOGPROBS}")
-        keep = []
-        n, k, cap = len(requests), int(top_k or 0), max(params.max_new_tokens, 1)
-        reqs = (RequestC * n)(*[self._request(*r, keep) for r in requests])
-        outs = [np.empty(cap, np.int64) for _ in requests]
-        res = (ResultC * n)(*[ResultC(o.ctypes.data_as(C.POINTER(C.c_int64)), len(o), 0, 0) for o in outs])
-        srecs = [_stop_c(ss, keep) for ss in stop_sets]
-        stops = (C.POINTER(StopSetC) * n)(*[C.pointer(r) if r is not None else C.POINTER(StopSetC)() for r in srecs])
-        hits = (StopHitC * n)()
+        _check_top_k(top_k)
+        b = _Batch(self, requests, params)
+        stops = _ptr_array(StopSetC, [_stop_c(ss, b.keep) for ss in stop_sets], b.keep)
+        hits = (StopHitC * b.n)()
         bias = None
         if constraints is not None:
-            recs = [_bias_c(c, keep) for c in constraints]
-            bias = (C.POINTER(LogitBiasC) * n)(*[C.pointer(r) if r is not None else C.POINTER(LogitBiasC)() for r in recs])
+            bias = _ptr_array(LogitBiasC, [_bias_c(c, b.keep) for c in constraints], b.keep)
+        lp = None if top_k is None else _LogprobBuffers(b.n, b.cap, int(top_k))
         pc = _params_c(params, self.eos_token_id, ignore_eos)
-        if top_k is None:
-            check(lib().dsocr_generate_stop(self._h, n, reqs, C.byref(pc), res, stops, hits, bias, 0, None))
-            return ([outs[i][:res[i].n_out].tolist() for i in range(n)],
-                    [(int(hits[i].seq), int(hits[i].match_len)) for i in range(n)])
-        tlp = [np.zeros(cap, np.float32) for _ in requests]
-        tid = [np.zeros((cap, max(k, 1)), np.int64) for _ in requests]
-        tl = [np.zeros((cap, max(k, 1)), np.float32) for _ in requests]
-        lps = (LogprobsC * n)(*[LogprobsC(tlp[i].ctypes.data_as(C.POINTER(C.c_float)),
-                                         tid[i].ctypes.data_as(C.POINTER(C.c_int64)),
-                                         tl[i].ctypes.data_as(C.POINTER(C.c_float)), cap, 0) for i in range(n)])
-        check(lib().dsocr_generate_stop(self._h, n, reqs, C.byref(pc), res, stops, hits, bias, k, lps))
-        ids = [outs[i][:res[i].n_out].tolist() for i in range(n)]
-        cnt = [int(lps[i].n) for i in range(n)]
-        return (ids, [(int(hits[i].seq), int(hits[i].match_len)) for i in range(n)],
-                [tlp[i][:cnt[i]].copy() for i in range(n)],
-                [tid[i].reshape(-1)[:cnt[i] * k].reshape(cnt[i], k).copy() for i in range(n)],
-                [tl[i].reshape(-1)[:cnt[i] * k].reshape(cnt[i], k).copy() for i in range(n)])
+        check(lib().dsocr_generate_stop(self._h, b.n, b.reqs, C.byref(pc), b.res, stops, hits, bias, lp.k if lp else 0,
+                                        lp.c if lp else None))
+        got = (b.ids(), [(int(h.seq), int(h.match_len)) for h in hits])
+        return (*got, *lp.unpack()) if lp else got
 
     def generate_stop_stream(self, request, stop_set, params: DecodeParameters = DecodeParameters(),
                              stream: Optional[Callable] = None, ignore_eos: bool = False):
@@ -460,7 +460,7 @@ class DeepseekOcrEngine:
         out = np.empty(max(params.max_new_tokens, 1), np.int64)
         n, hit = C.c_size_t(), StopHitC()
         rec = _stop_c(stop_set, keep)
-        cb = STREAM_CB(lambda k, toks, _u: stream(k, [toks[i] for i in range(k)])) if stream else STREAM_CB()
+        cb = _stream_cb(stream)
         check(lib().dsocr_generate_stop_stream(self._h, C.byref(req), C.byref(pc), C.byref(rec) if rec is not None else None,
                                                cb, None, out.ctypes.data_as(C.c_void_p), len(out), C.byref(n),
                                                C.byref(hit)))
@@ -638,6 +638,10 @@ class Session:
                  ignore_eos: bool = False, per_request: bool = False, logprobs: bool = False, logit_bias: bool = False,
                  stops: bool = False):
         self._e = None
+        # the (StopSet, include) record of an admission follows its page: staged for the C call that admits it,
+        # pending while a chunked admission runs, then its slot's
+        self._staged_stops, self._pending_stops, self._slot_stops = None, None, {}
+        self._pending_page = None  # the page of the pending chunked admission (the engine reads its pixels)
         pc = _params_c(params, engine.eos_token_id, ignore_eos)
         flags = ((SESSION_PER_REQUEST if per_request else 0) | (SESSION_LOGPROBS if logprobs else 0) |
                  (SESSION_LOGIT_BIAS if logit_bias else 0) | (SESSION_STOP if stops else 0))
@@ -649,7 +653,6 @@ class Session:
         else:
             check(lib().dsocr_session_open(engine._h, int(slots), int(max_context), C.byref(pc)))
         self._e = engine
-        self._pending_page = None
         self.params = params
         self.per_request = bool(per_request)
         self._eos, self._ignore_eos = engine.eos_token_id, bool(ignore_eos)
@@ -683,22 +686,44 @@ class Session:
         opened with ``stops``; EINVAL otherwise), matched from its first token on; a stop string needs ``tokenizer``.
         The session returns ids as the device wrote them, matched tokens included: ``stop_hit(slot)`` names the hit
         and ``retire_stopped`` trims by it unless ``include_stop_in_output``."""
-        self._check_logprobs(logprobs)
-        keep = []
-        req = self._e._request(ids, mask, page, image_rows, keep)
-        checked = self._check_stops(stop, stop_token_ids, include_stop_in_output, tokenizer, stops)
-        self._stage_constraint(logit_bias, allowed_token_ids, banned_token_ids)
-        self._stage_stops(checked)
+        req, _, _keep = self._admission((ids, mask, page, image_rows), None, logprobs,
+                                        (logit_bias, allowed_token_ids, banned_token_ids),
+                                        (stop, stop_token_ids, include_stop_in_output, tokenizer, stops))
         slot = C.c_int(-1)
         if params is not None:
             pc = _params_c(params, self._eos if eos_token_id is None else int(eos_token_id),
                            self._ignore_eos if ignore_eos is None else bool(ignore_eos))
-            check(lib().dsocr_session_admit_params(self._e._h, C.byref(req), C.byref(pc), C.byref(slot)))
-            return self._admitted_stops(slot.value)
-        check(lib().dsocr_session_admit(self._e._h, C.byref(req),
-                                        self.out_cap if max_new_tokens is None else int(max_new_tokens),
-                                        0 if seed is None else 1, seed or 0, C.byref(slot)))
+            self._admission_call(lib().dsocr_session_admit_params, C.byref(req), C.byref(pc), C.byref(slot))
+        else:
+            self._admission_call(lib().dsocr_session_admit, C.byref(req),
+                                 self.out_cap if max_new_tokens is None else int(max_new_tokens),
+                                 0 if seed is None else 1, seed or 0, C.byref(slot))
         return self._admitted_stops(slot.value)
+
+    def _admission(self, request, request_params, logprobs, constraint, stops):
+        """What every admission form does before its C call, in this order: the ``logprobs`` check, the request
+        (``request``: ids, mask, page, image rows), its parameter record (``request_params``: ``_request_params``'
+        arguments, or None for none), the stop set merged and checked (``stops``: ``_check_stops``' arguments), then
+        the constraint staged (``constraint``: ``_stage_constraint``'s arguments) and the stop set staged.  Returns
+        the request, the parameter record and the list that keeps their arrays alive; the checked stop record is
+        ``_staged_stops``."""
+        self._check_logprobs(logprobs)
+        keep = []
+        req = self._e._request(*request, keep)
+        pc = None if request_params is None else self._request_params(*request_params)
+        checked = self._check_stops(*stops)
+        self._stage_constraint(*constraint)
+        self._stage_stops(checked)
+        return req, pc, keep
+
+    def _admission_call(self, fn, *args) -> None:
+        """The C call of an admission.  It consumes what was staged whether it succeeds or not, so after a failure
+        nothing is staged here either."""
+        try:
+            check(fn(self._e._h, *args))
+        except Exception:
+            self._staged_stops = None
+            raise
 
     def _check_stops(self, stop, stop_token_ids, include, tokenizer, stops):
         """The stop set of an admission, merged and checked before anything is staged for it: ``(StopSet, include)``
@@ -728,8 +753,7 @@ class Session:
 
     def _admitted_stops(self, slot: int) -> int:
         """The staged (stop set, include) record follows its page: into its slot, or with a chunked admission."""
-        rec, self._staged_stops = getattr(self, "_staged_stops", None), None
-        self._slot_stops = getattr(self, "_slot_stops", {})
+        rec, self._staged_stops = self._staged_stops, None
         self._slot_stops.pop(slot, None)
         if rec is not None:
             self._slot_stops[slot] = rec
@@ -743,7 +767,7 @@ class Session:
 
     def slot_stops(self, slot: int):
         """``(StopSet, include_stop_in_output)`` the page in ``slot`` was admitted with, or None."""
-        return getattr(self, "_slot_stops", {}).get(int(slot))
+        return self._slot_stops.get(int(slot))
 
     def retire_stopped(self, slot: int, decode: Callable):
         """``retire`` for a page admitted with stops: ``(StopResult, moved_from)`` with the matched tokens trimmed
@@ -795,22 +819,15 @@ class Session:
         ``chunk_rows`` >= 32 rows), with ``step`` / ``retire`` legal in between.  Returns the admission's ticket.
         The keywords are ``admit``'s.  One admission may be pending; ``admit`` / ``admit_prefix`` are refused while
         it is."""
-        self._check_logprobs(logprobs)
-        keep = []
-        req = self._e._request(ids, mask, page, image_rows, keep)
-        pc = self._request_params(params, max_new_tokens, seed, eos_token_id, ignore_eos)
-        checked = self._check_stops(stop, stop_token_ids, include_stop_in_output, tokenizer, stops)
-        self._stage_constraint(logit_bias, allowed_token_ids, banned_token_ids)
-        self._stage_stops(checked)
-        self._pending_stops, staged = None, None
+        req, pc, _keep = self._admission((ids, mask, page, image_rows),
+                                         (params, max_new_tokens, seed, eos_token_id, ignore_eos), logprobs,
+                                         (logit_bias, allowed_token_ids, banned_token_ids),
+                                         (stop, stop_token_ids, include_stop_in_output, tokenizer, stops))
+        self._pending_stops = None
         ticket = C.c_int(-1)
-        try:
-            check(lib().dsocr_session_admit_begin(self._e._h, C.byref(req), C.byref(pc), max(int(chunk_rows), 0),
-                                                  C.byref(ticket)))
-            staged = self._staged_stops
-        finally:  # (the call consumed the staged set whether it succeeded or not)
-            self._staged_stops = None
-        self._pending_stops = staged
+        self._admission_call(lib().dsocr_session_admit_begin, C.byref(req), C.byref(pc), max(int(chunk_rows), 0),
+                             C.byref(ticket))
+        self._pending_stops, self._staged_stops = self._staged_stops, None  # (admit_advance hands it to the slot)
         self._pending_page = page  # the engine reads the page's pixels in the vision slice
         return ticket.value
 
@@ -827,7 +844,7 @@ class Session:
             raise
         if done.value:
             self._pending_page = None
-            self._staged_stops, self._pending_stops = getattr(self, "_pending_stops", None), None
+            self._staged_stops, self._pending_stops = self._pending_stops, None
             self._admitted_stops(slot.value)
         return bool(done.value), slot.value
 
@@ -866,19 +883,12 @@ class Session:
         are the whole prompt's, no page and no image rows; vision and the prefill of the entry's rows are skipped.
         The keywords are ``admit``'s (without ``params``: the session's parameters with this ``max_new_tokens`` /
         ``seed``)."""
-        self._check_logprobs(logprobs)
-        keep = []
-        req = self._e._request(ids, mask, None, None, keep)
-        pc = self._request_params(params, max_new_tokens, seed, eos_token_id, ignore_eos)
-        checked = self._check_stops(stop, stop_token_ids, include_stop_in_output, tokenizer, stops)
-        self._stage_constraint(logit_bias, allowed_token_ids, banned_token_ids)
-        self._stage_stops(checked)
+        req, pc, _keep = self._admission((ids, mask, None, None),
+                                         (params, max_new_tokens, seed, eos_token_id, ignore_eos), logprobs,
+                                         (logit_bias, allowed_token_ids, banned_token_ids),
+                                         (stop, stop_token_ids, include_stop_in_output, tokenizer, stops))
         slot = C.c_int(-1)
-        try:
-            check(lib().dsocr_session_admit_prefix(self._e._h, int(handle), C.byref(req), C.byref(pc), C.byref(slot)))
-        except DsocrError:
-            self._staged_stops = None
-            raise
+        self._admission_call(lib().dsocr_session_admit_prefix, int(handle), C.byref(req), C.byref(pc), C.byref(slot))
         return self._admitted_stops(slot.value)
 
     def drop_prefix(self, handle: int) -> None:
@@ -934,11 +944,10 @@ class Session:
         n, moved = C.c_size_t(), C.c_int(-1)
         check(lib().dsocr_session_retire(self._e._h, int(slot), out.ctypes.data_as(C.c_void_p), out.size, C.byref(n),
                                          C.byref(moved)))
-        recs = getattr(self, "_slot_stops", None)
-        if recs is not None:  # the (stop set, include) records follow the compaction
-            recs.pop(int(slot), None)
-            if moved.value >= 0 and moved.value in recs:
-                recs[int(slot)] = recs.pop(moved.value)
+        recs = self._slot_stops  # the (stop set, include) records follow the compaction
+        recs.pop(int(slot), None)
+        if moved.value >= 0 and moved.value in recs:
+            recs[int(slot)] = recs.pop(moved.value)
         return out[:n.value].tolist(), moved.value
 
     def close(self):

@@ -100,6 +100,28 @@ def test_tiny_batch_equals_single(tiny_engine, n):
     assert batch == singles
 
 
+def test_tiny_every_generate_form_agrees(tiny_engine):
+    """The generate forms marshal through one body, and with nothing asked of a feature (no constraint, no stop set)
+    they run the same kernels on the same inputs: the same ids, bitwise the same log-probabilities, no stop hit."""
+    e, params = tiny_engine, DecodeParameters(max_new_tokens=6)
+    reqs = [([0] + list(range(20, 20 + m - 1)), None, None, None) for m in (5, 9)]
+    ids = e.generate_batch(reqs, params)
+    assert all(1 <= len(g) <= 6 for g in ids)
+    lp = e.generate_logprobs(reqs, 2, params)
+    con = e.generate_constrained(reqs, [None, None], params, top_k=2)
+    ids_s, hits, *lp_s = e.generate_stops(reqs, [None, None], params, top_k=2)
+    assert lp[0] == ids and con[0] == ids and ids_s == ids
+    assert hits == [(-1, 0), (-1, 0)]
+    for other in (con[1:], lp_s):
+        for a, b in zip(lp[1:], other):   # token log-probabilities, alternative ids, their log-probabilities
+            assert len(a) == len(b) == 2
+            for x, y in zip(a, b):
+                assert x.dtype == y.dtype and x.shape == y.shape and x.tobytes() == y.tobytes()
+    assert [len(x) for x in lp[1]] == [len(g) for g in ids] and all(x.shape[1] == 2 for x in lp[2] + lp[3])
+    assert e.generate(*reqs[0], params) == ids[0]
+    assert e.generate_stop_stream(reqs[0], None, params) == (ids[0], (-1, 0))
+
+
 def test_tiny_text_only_and_penalty(tiny_engine, tiny_oracle):
     ids = [0] + list(range(20, 60))
     params = DecodeParameters(max_new_tokens=16, repetition_penalty=1.3, no_repeat_ngram_size=3)

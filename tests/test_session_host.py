@@ -235,6 +235,78 @@ def test_capacity_assertion_fires_before_the_burst():
         assert s.submit("<image>doc:2").result(timeout=20).generated_tokens == _stream(2, 4)
 
 
+# ------------------------------------------------------------------ the real Session over a scripted library
+class FakeLib:
+    """The library's session entry points as ``dsocr.engine.Session`` calls them: every staging and admission call is
+    logged, and an admission raises while ``fail`` is set (after it has consumed what was staged, as the library
+    does)."""
+
+    def __init__(self):
+        self.calls, self.fail, self.active = [], False, 0
+
+    def dsocr_session_open_ex(self, h, slots, max_context, pc, flags):
+        return 0
+
+    def dsocr_session_info(self, h, desc):
+        desc._obj.slots, desc._obj.max_context, desc._obj.out_cap = 4, 128, 16
+        return 0
+
+    def dsocr_session_stage_logit_bias(self, h, rec):
+        self.calls.append("constraint")
+        return 0
+
+    def dsocr_session_stage_stop(self, h, rec):
+        self.calls.append("stop")
+        return 0
+
+    def _admission(self, out):
+        self.calls.append("admission")
+        if self.fail:
+            raise DsocrError(1, "scripted admission failure")
+        out._obj.value = self.active
+        self.active += 1
+        return 0
+
+    def dsocr_session_admit(self, h, req, max_new, has_seed, seed, slot):
+        return self._admission(slot)
+
+    def dsocr_session_admit_prefix(self, h, handle, req, pc, slot):
+        return self._admission(slot)
+
+    def dsocr_session_admit_begin(self, h, req, pc, chunk_rows, ticket):
+        return self._admission(ticket)
+
+
+@pytest.mark.parametrize("form", ["admit", "admit_begin", "admit_prefix"])
+def test_a_failed_admission_leaves_nothing_staged(monkeypatch, form):
+    """Every admission form stages the constraint, then the stop set, then makes its C call; when that call fails
+    no stop record is left staged or pending, and the records of the pages admitted before are untouched."""
+    from dsocr import engine as E
+    from dsocr.stops import merge_stops
+    fake = FakeLib()
+    monkeypatch.setattr(E, "lib", lambda: fake)
+    eng = E.DeepseekOcrEngine.__new__(E.DeepseekOcrEngine)
+    eng._h, eng.eos_token_id, eng.vocab = None, 1, 512
+    sess = E.Session(eng, 4, 128, DecodeParameters(max_new_tokens=16), logit_bias=True, stops=True)
+    assert (sess._staged_stops, sess._pending_stops, sess._pending_page, sess._slot_stops) == (None, None, None, {})
+    first = [merge_stops(None, [7], None, 512), merge_stops(None, [8, 9], None, 512)]
+    assert [sess.admit([0, 5, 6], stops=ss, include_stop_in_output=bool(k)) for k, ss in enumerate(first)] == [0, 1]
+    before = {k: sess.slot_stops(k) for k in range(4)}
+    assert before == {0: (first[0], False), 1: (first[1], True), 2: None, 3: None}
+
+    fake.fail, fake.calls = True, []
+    args = ((3, [0, 5, 6]) if form == "admit_prefix" else ([0, 5, 6],))
+    with pytest.raises(DsocrError, match="scripted"):
+        getattr(sess, form)(*args, logit_bias={5: 1.0}, stop_token_ids=[11])
+    assert fake.calls == ["constraint", "stop", "admission"]
+    assert sess._staged_stops is None and sess._pending_stops is None
+    assert {k: sess.slot_stops(k) for k in range(4)} == before
+
+    fake.fail = False   # the next page carries no stops: none of the failed admission's reach its slot
+    assert sess.admit([0, 5, 6]) == 2 and sess.slot_stops(2) is None
+    assert {k: sess.slot_stops(k) for k in range(4)} == before
+
+
 # ------------------------------------------------------------------ server and CLI
 def _data_url(seed):
     from PIL import Image
