@@ -24,6 +24,7 @@ struct dsocr_engine {
     std::unique_ptr<dsocr::Engine> impl;
     dsocr::LogitBias staged_bias;  // dsocr_session_stage_logit_bias: consumed by the next admission call
     dsocr::StopSet staged_stop;    // dsocr_session_stage_stop: the same
+    dsocr::Penalties staged_pen;   // dsocr_session_stage_penalties: the same
 };
 struct dsocr_page_pixels {
     dsocr::PagePixels px;
@@ -183,8 +184,20 @@ dsocr::StopSet to_stops(const dsocr_stop_set* ss, size_t vocab) {
     return st;
 }
 
-// a session admission's request: the staged constraint and stop set move into it (consumed whatever the admission does)
+// the penalty record as the engine takes it, checked (NULL: off)
+dsocr::Penalties to_penalties(const dsocr_penalties* pn) {
+    dsocr::Penalties p;
+    if (!pn) return p;
+    p.frequency = pn->frequency; p.presence = pn->presence; p.min_p = pn->min_p;
+    dsocr::validate_penalties(p);
+    return p;
+}
+
+// a session admission's request: the staged constraint, stop set and penalties move into it (consumed whatever the
+// admission does)
 dsocr::GenRequest to_admission(dsocr_engine* e, const dsocr_request& r) {
+    const dsocr::Penalties pn = e->staged_pen;
+    e->staged_pen = dsocr::Penalties();
     dsocr::LogitBias b = std::move(e->staged_bias);
     e->staged_bias = dsocr::LogitBias();
     dsocr::StopSet st = std::move(e->staged_stop);
@@ -192,23 +205,27 @@ dsocr::GenRequest to_admission(dsocr_engine* e, const dsocr_request& r) {
     dsocr::GenRequest g = to_request(r);
     g.bias = std::move(b);
     g.stops = std::move(st);
+    g.pen = pn;
     return g;
 }
 
 // the DSOCR_SESSION_* feature bits as the engine takes them, and back (DSOCR_SESSION_ADMIT_PENDING is state, not one of them)
 dsocr::Engine::SessionFeatures to_features(uint32_t flags) {
-    if (flags & ~(uint32_t)(DSOCR_SESSION_PER_REQUEST | DSOCR_SESSION_LOGPROBS | DSOCR_SESSION_LOGIT_BIAS | DSOCR_SESSION_STOP))
+    if (flags & ~(uint32_t)(DSOCR_SESSION_PER_REQUEST | DSOCR_SESSION_LOGPROBS | DSOCR_SESSION_LOGIT_BIAS | DSOCR_SESSION_STOP |
+                             DSOCR_SESSION_PENALTIES))
         throw std::runtime_error("EINVAL: unknown session flags");
     dsocr::Engine::SessionFeatures f;
     f.per_request = (flags & DSOCR_SESSION_PER_REQUEST) != 0;
     f.logprobs = (flags & DSOCR_SESSION_LOGPROBS) != 0;
     f.logit_bias = (flags & DSOCR_SESSION_LOGIT_BIAS) != 0;
     f.stops = (flags & DSOCR_SESSION_STOP) != 0;
+    f.penalties = (flags & DSOCR_SESSION_PENALTIES) != 0;
     return f;
 }
 uint32_t feature_flags(const dsocr::Engine::SessionFeatures& f) {
     return (f.per_request ? DSOCR_SESSION_PER_REQUEST : 0u) | (f.logprobs ? DSOCR_SESSION_LOGPROBS : 0u) |
-           (f.logit_bias ? DSOCR_SESSION_LOGIT_BIAS : 0u) | (f.stops ? DSOCR_SESSION_STOP : 0u);
+           (f.logit_bias ? DSOCR_SESSION_LOGIT_BIAS : 0u) | (f.stops ? DSOCR_SESSION_STOP : 0u) |
+           (f.penalties ? DSOCR_SESSION_PENALTIES : 0u);
 }
 
 // ---- generate: the exported forms marshal through generate_page (one page, the stream callback) or generate_pages
@@ -261,6 +278,7 @@ struct GenExtras {
     const dsocr_stop_set* const* stops = nullptr;   // one stop set per request (the list or an entry may be NULL) ...
     dsocr_stop_hit* hits = nullptr;                 // ... and where every request's hit goes
     const dsocr_logit_bias* const* bias = nullptr;  // one constraint per request (the list or an entry may be NULL)
+    const dsocr_penalties* const* pen = nullptr;    // one penalty record per request (the same)
     bool lp_on = false;  // per-token log-probabilities with top_k alternatives into lp[n] (NULL only with n == 0)
     size_t top_k = 0;
     dsocr_logprobs* lp = nullptr;
@@ -293,6 +311,7 @@ void generate_pages(dsocr_engine* e, size_t n, const dsocr_request* reqs, const 
         rq.push_back(to_request(reqs[i]));
         if (x.bias) rq.back().bias = to_bias(x.bias[i], vocab);
         if (x.stops) rq.back().stops = to_stops(x.stops[i], vocab);
+        if (x.pen) rq.back().pen = to_penalties(x.pen[i]);
     }
     dsocr::GenParams g = to_params(params);
     g.trace = x.logits_out;
@@ -570,6 +589,41 @@ dsocr_status dsocr_generate_stop(dsocr_engine* e, size_t n, const dsocr_request*
         x.top_k = top_k;
         x.lp = lp;
         generate_pages(e, n, reqs, params, results, x);
+    });
+}
+
+dsocr_status dsocr_generate_penalties(dsocr_engine* e, size_t n, const dsocr_request* reqs,
+                                      const dsocr_decode_params* params, dsocr_result* results,
+                                      const dsocr_penalties* const* pen, const dsocr_stop_set* const* stops,
+                                      dsocr_stop_hit* hits, const dsocr_logit_bias* const* bias, size_t top_k,
+                                      dsocr_logprobs* lp) {
+    return guarded([&] {
+        if (!params) throw std::runtime_error("EINVAL: NULL argument");
+        GenExtras x;
+        x.pen = pen;
+        x.stops = stops;
+        x.hits = hits;
+        x.bias = bias;
+        x.lp_on = lp != nullptr;  // (top_k without lp is refused)
+        x.top_k = top_k;
+        x.lp = lp;
+        generate_pages(e, n, reqs, params, results, x);
+    });
+}
+
+dsocr_status dsocr_penalties_check(const dsocr_penalties* pen) {
+    return guarded([&] { (void)to_penalties(pen); });
+}
+
+dsocr_status dsocr_session_stage_penalties(dsocr_engine* e, const dsocr_penalties* pen) {
+    return guarded([&] {
+        if (!e) throw std::runtime_error("EINVAL: NULL argument");
+        e->staged_pen = dsocr::Penalties();
+        dsocr::Engine::SessionInfo si;
+        if (!e->impl->session_info(&si)) throw std::runtime_error("EINVAL: no decode session is open on this engine");
+        const dsocr::Penalties p = to_penalties(pen);
+        if (p.active() && !si.feat.penalties) throw std::runtime_error("EINVAL: this session was opened without DSOCR_SESSION_PENALTIES");
+        e->staged_pen = p;
     });
 }
 
@@ -2300,9 +2354,10 @@ dsocr_status dsocr_k_logprobs_penalty(int B, int V, int K, const float* logits, 
     });
 }
 
-dsocr_status dsocr_k_sample_stoch(int B, int V, float* logits, const int* ctx, int ctx_cap, const int* ctx_len,
-                                  int ngram, float rep_penalty, double temperature, size_t top_k, double top_p,
-                                  uint64_t seed, int draws, int* out_tok) {
+// ln_min_p (host [B], optional): one PenaltyRec per row for the sampler (DecSampleArgs::pen)
+static dsocr_status k_sample_stoch(int B, int V, float* logits, const int* ctx, int ctx_cap, const int* ctx_len,
+                                   int ngram, float rep_penalty, double temperature, size_t top_k, double top_p,
+                                   const double* ln_min_p, uint64_t seed, int draws, int* out_tok) {
     return guarded([&] {
         if (B <= 0 || V <= 0 || draws <= 0 || !(temperature > 0.0)) throw std::runtime_error("EINVAL: bad sampling arguments");
         const int rb = (int)dsocr::dec_sample_blocks(V);
@@ -2334,6 +2389,16 @@ dsocr_status dsocr_k_sample_stoch(int B, int V, float* logits, const int* ctx, i
             for (int b = 0; b < B; ++b)
                 check_hip(hipMemcpy(a.rng + (size_t)b * dsocr::RNG_WORDS, st.data(), sizeof(uint32_t) * dsocr::RNG_WORDS,
                                     hipMemcpyHostToDevice), "hipMemcpy");
+            if (ln_min_p) {
+                std::vector<dsocr::PenaltyRec> recs(B);
+                for (int b = 0; b < B; ++b) {
+                    if (std::isnan(ln_min_p[b]) || ln_min_p[b] > 0.0) throw std::runtime_error("EINVAL: ln_min_p must be <= 0");
+                    recs[b].ln_min_p = ln_min_p[b];
+                }
+                dsocr::PenaltyRec* d_pen = (dsocr::PenaltyRec*)dalloc(sizeof(dsocr::PenaltyRec) * B);
+                check_hip(hipMemcpy(d_pen, recs.data(), sizeof(dsocr::PenaltyRec) * B, hipMemcpyHostToDevice), "hipMemcpy");
+                a.pen = d_pen;
+            }
             const bool stamps = getenv("DSOCR_SAMPLE_STAMPS") != nullptr;  // diagnostics: phase clocks to stderr
             if (stamps) {
                 a.st_stamps = (unsigned long long*)dalloc(sizeof(unsigned long long) * 8);
@@ -2356,6 +2421,47 @@ dsocr_status dsocr_k_sample_stoch(int B, int V, float* logits, const int* ctx, i
             throw;
         }
         for (void* q : bufs) (void)hipFree(q);
+    });
+}
+
+dsocr_status dsocr_k_sample_stoch(int B, int V, float* logits, const int* ctx, int ctx_cap, const int* ctx_len,
+                                  int ngram, float rep_penalty, double temperature, size_t top_k, double top_p,
+                                  uint64_t seed, int draws, int* out_tok) {
+    return k_sample_stoch(B, V, logits, ctx, ctx_cap, ctx_len, ngram, rep_penalty, temperature, top_k, top_p, nullptr, seed,
+                          draws, out_tok);
+}
+
+dsocr_status dsocr_k_sample_stoch_min_p(int B, int V, float* logits, const int* ctx, int ctx_cap, const int* ctx_len,
+                                        int ngram, float rep_penalty, double temperature, size_t top_k, double top_p,
+                                        const double* ln_min_p, uint64_t seed, int draws, int* out_tok) {
+    if (!ln_min_p) return guarded([] { throw std::runtime_error("EINVAL: NULL ln_min_p"); });
+    return k_sample_stoch(B, V, logits, ctx, ctx_cap, ctx_len, ngram, rep_penalty, temperature, top_k, top_p, ln_min_p, seed,
+                          draws, out_tok);
+}
+
+dsocr_status dsocr_k_out_penalty(int B, int V, int ld, float* logits, const int* out_ids, int out_cap,
+                                 const int* out_len, const dsocr_penalties* pen) {
+    return guarded([&] {
+        if (B <= 0 || V <= 0 || ld < V || out_cap <= 0 || !logits || !out_ids || !out_len || !pen)
+            throw std::runtime_error("EINVAL: bad output penalty hook arguments");
+        const size_t nb = (size_t)B, nl = nb * (size_t)ld, cap = (size_t)out_cap;
+        std::vector<dsocr::PenaltyRec> recs(nb);
+        for (size_t b = 0; b < nb; ++b) {
+            if (out_len[b] < 0 || out_len[b] > out_cap) throw std::runtime_error("EINVAL: out_len outside 0..out_cap");
+            recs[b].frequency = pen[b].frequency; recs[b].presence = pen[b].presence;
+        }
+        dsocr::DeviceBuffer d_logits(nl * 4), d_out(nb * cap * 4), d_len(nb * 4), d_rec(nb * sizeof(dsocr::PenaltyRec));
+        check_hip(hipMemcpy(d_logits.get(), logits, nl * 4, hipMemcpyHostToDevice), "hipMemcpy H2D");
+        check_hip(hipMemcpy(d_out.get(), out_ids, nb * cap * 4, hipMemcpyHostToDevice), "hipMemcpy H2D");
+        check_hip(hipMemcpy(d_len.get(), out_len, nb * 4, hipMemcpyHostToDevice), "hipMemcpy H2D");
+        check_hip(hipMemcpy(d_rec.get(), recs.data(), nb * sizeof(dsocr::PenaltyRec), hipMemcpyHostToDevice), "hipMemcpy H2D");
+        dsocr::DecPenaltyArgs a;
+        a.logits = (float*)d_logits.get(); a.B = B; a.V = V; a.ld = ld;
+        a.out_ids = (const int*)d_out.get(); a.out_cap = out_cap; a.out_len = (const int*)d_len.get();
+        a.rec = (const dsocr::PenaltyRec*)d_rec.get();
+        dsocr::launch_dec_out_penalty(a, nullptr);
+        check_hip(hipDeviceSynchronize(), "output penalty");
+        check_hip(hipMemcpy(logits, d_logits.get(), nl * 4, hipMemcpyDeviceToHost), "hipMemcpy D2H");
     });
 }
 

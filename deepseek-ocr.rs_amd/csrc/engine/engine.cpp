@@ -174,6 +174,7 @@ struct Engine::Session {
     struct Slot {
         bool stopped = false;  // the slot's request carried a stop set (rows_.stop_n[slot] != 0)
         bool biased = false;  // the slot's device flag (rows_.bias_on): its request carried a constraint
+        bool penalised = false;  // the slot's device record (rows_.pen) is on
         size_t max_new = 0;
         int kv_pos = 0;    // the device kv_pos of the slot: prompt + steps replayed since its admission
         int reported = 0;  // tokens the polls have handed out
@@ -1748,6 +1749,7 @@ void Engine::decode_head(int B, DecSampleArgs& sa, const SampleArgs& pen, bool s
     float* SX = rows_.x;
     if (screened && lp) throw std::runtime_error("EINTERNAL: log-probabilities need the exact head");
     if (screened && rows_.bias && !sess_) throw std::runtime_error("EINTERNAL: a logit bias needs the exact head");
+    if (screened && rows_.pen && !sess_) throw std::runtime_error("EINTERNAL: penalties need the exact head");
     if (screened) {
         // screened selection: int8 lm_head intervals + running threshold, exact rescoring of the
         // few kept rows — the exact path's token from half the lm_head bytes
@@ -1778,6 +1780,7 @@ void Engine::decode_head(int B, DecSampleArgs& sa, const SampleArgs& pen, bool s
     if (rows_.bias) launch_dec_logit_bias(bias_args(sa, 0), st);  // l' = l + b: what everything below reads
     if (lp) launch_dec_lp_partial(*lp, st);
     launch_rep_penalty(pen, st);
+    if (rows_.pen) launch_dec_out_penalty(penalty_args(sa, 0), st);  // frequency / presence, per row
     launch_dec_sample(sa, st);
     if (stops) stop_match(sa, 0);
     if (lp) launch_dec_lp_final(*lp, st);
@@ -1883,6 +1886,11 @@ void Engine::reserve_decode_rows(const DecodeRowsSpec& spec) {
         r.stop_stage_rows = std::max(spec.stop_stage_rows, 1);
         r.stop_stage = wsi("s_stopstage", (size_t)r.stop_stage_rows * STOP_STAGE_INTS);
     }
+    if (spec.penalties) {  // every record off until an admission / init_sampling writes it
+        r.pen = reinterpret_cast<PenaltyRec*>(ws("s_pen", sizeof(PenaltyRec) * S));
+        const std::vector<PenaltyRec> off((size_t)S);
+        upload_to(r.pen, "s_penstage", off);
+    }
 }
 
 // The fused one-page launch takes q / k / v by polling its hand-off row, and the attention merge polls its records:
@@ -1923,6 +1931,7 @@ void Engine::sample_args(int B, int slot0, const GenParams& p, bool per_request,
         sa.rng = r.rng + o * RNG_WORDS;
     }
     if (r.ban) { sa.ban_ld = r.ban_ld; sa.ban_out = r.ban + o * r.ban_ld; }
+    if (r.pen) sa.pen = r.pen + o;  // min-p of the sampled rows
 }
 
 // the log-probability rows as the arguments of the pages [row0, row0 + sa.B) whose selection sa describes
@@ -1947,6 +1956,37 @@ DecBiasArgs Engine::bias_args(const DecSampleArgs& sa, int row0) {
     a.logits = const_cast<float*>(sa.logits); a.B = sa.B; a.V = sa.V; a.ld = sa.ld;
     a.bias = r.bias + (size_t)row0 * r.bias_ld; a.bias_ld = r.bias_ld; a.on = r.bias_on + row0;
     return a;
+}
+
+DecPenaltyArgs Engine::penalty_args(const DecSampleArgs& sa, int row0) {
+    DecPenaltyArgs a;
+    a.logits = const_cast<float*>(sa.logits); a.B = sa.B; a.V = sa.V; a.ld = sa.ld;
+    a.out_ids = sa.out_ids; a.out_cap = sa.out_cap; a.out_len = sa.out_len;
+    a.rec = rows_.pen + row0;
+    return a;
+}
+
+PenaltyRec Penalties::rec() const {
+    PenaltyRec r;
+    r.frequency = frequency; r.presence = presence;
+    r.ln_min_p = min_p > 0.0 ? std::log(min_p) : -INFINITY;
+    return r;
+}
+
+void validate_penalties(const Penalties& pn) {
+    if (!std::isfinite(pn.frequency) || !std::isfinite(pn.presence))
+        throw std::runtime_error("EINVAL: penalties: frequency_penalty and presence_penalty must be finite");
+    if (std::isnan(pn.min_p) || pn.min_p < 0.0 || pn.min_p > 1.0)
+        throw std::runtime_error("EINVAL: penalties: min_p must lie in [0, 1]");
+}
+
+// (the staging buffer holds one record per row: rows written between two synchronisations do not overlap)
+void Engine::write_penalties(const Penalties* const* pn, int row0, int n) {
+    const DecodeRows& r = rows_;
+    if (!r.pen) throw std::runtime_error("EINTERNAL: no penalty records are reserved");
+    PenaltyRec* h = (PenaltyRec*)pinned("s_penstage", sizeof(PenaltyRec) * (size_t)r.S);
+    for (int i = 0; i < n; ++i) h[row0 + i] = pn[i] ? pn[i]->rec() : PenaltyRec();
+    HIP_CHECK(hipMemcpyAsync(r.pen + row0, h + row0, sizeof(PenaltyRec) * (size_t)n, hipMemcpyHostToDevice, stream_));
 }
 
 void validate_logit_bias(const LogitBias& lb, int vocab) {
@@ -2114,6 +2154,20 @@ std::vector<std::vector<int64_t>> Engine::generate(const std::vector<GenRequest>
         const char* e = getenv("DSOCR_PERSIST");
         if (e && atoi(e) != 0)
             throw std::runtime_error("EINVAL: stop sequences do not combine with the persistent decode step (DSOCR_PERSIST)");
+    }
+    // penalties: the same (a record that is off asks for nothing)
+    bool any_pen = false;
+    for (const GenRequest& rq : reqs) {
+        validate_penalties(rq.pen);
+        any_pen = any_pen || rq.pen.active();
+    }
+    // (no exported form passes a trace together with a record; the check guards the engine's own interface)
+    if (any_pen && (!p.use_cache || p.trace))
+        throw std::runtime_error("EINVAL: penalties need the K/V cache (use_cache = 1) and no logits trace");
+    if (any_pen) {
+        const char* e = getenv("DSOCR_PERSIST");
+        if (e && atoi(e) != 0)
+            throw std::runtime_error("EINVAL: penalties do not combine with the persistent decode step (DSOCR_PERSIST)");
     }
     if (reqs.empty() || p.max_new == 0) return std::vector<std::vector<int64_t>>(reqs.size());
     ensure_small(std::max((int)reqs.size(), 64));
@@ -2316,8 +2370,13 @@ void Engine::reset_decode_state(GenState& g) {
     // a constrained page: the exact head too, with the bias rows and one staging region per list
     for (const GenRequest& rq : g.reqs)
         if (rq.bias.active()) { spec.bias = true; spec.bias_stage += rq.bias.ids.size(); }
-    spec.ban = !p.do_sample && !p.trace && p.lp_k < 0 && !spec.bias && screen_applies(B, p.rep_penalty);
-    spec.lp_k = p.lp_k; spec.lp_side = rep_penalty_active(p.rep_penalty);
+    // a penalised page: the exact head as well, with one record per page
+    for (const GenRequest& rq : g.reqs) spec.penalties = spec.penalties || rq.pen.active();
+    spec.ban = !p.do_sample && !p.trace && p.lp_k < 0 && !spec.bias && !spec.penalties && screen_applies(B, p.rep_penalty);
+    // (the side row: dec_lp_final takes an emitted token's raw logit from it wherever a penalty may have rewritten
+    // logits[tok]: the repetition penalty at the context ids, the frequency / presence penalty at the generated ones,
+    // which the context row holds as well)
+    spec.lp_k = p.lp_k; spec.lp_side = rep_penalty_active(p.rep_penalty) || spec.penalties;
     // stop sets: the stop rows and one staging region per page (the head is whichever runs without them)
     for (const GenRequest& rq : g.reqs)
         if (rq.stops.active()) { spec.stops = true; spec.stop_stage_rows = B; }
@@ -2472,6 +2531,12 @@ void Engine::init_sampling(GenState& g) {
     // the fused selection kernel advances the KV position; after the prefill the first
     // decode position must be P, so start one behind
     launch_rep_penalty(pen, st);
+    if (r.pen) {  // every page's record, then the penalty on the prefill's logits (out_len is 0: only min-p can act)
+        std::vector<const Penalties*> pn(B);
+        for (int b = 0; b < B; ++b) pn[b] = &g.reqs[b].pen;
+        write_penalties(pn.data(), 0, B);
+        launch_dec_out_penalty(penalty_args(sa, 0), st);
+    }
     std::vector<int> pm1(B), lm1(B);
     for (int b = 0; b < B; ++b) { pm1[b] = g.kvpos[b] - 1; lm1[b] = g.kvlen[b] - 1; }
     HIP_CHECK(hipMemcpyAsync(r.kv_pos, pm1.data(), B * 4, hipMemcpyHostToDevice, st));
@@ -2804,9 +2869,10 @@ void Engine::session_open(int S, int max_context, const GenParams& p, const Sess
         spec.bias_stage = (size_t)L.vocab;
     }
     spec.stops = feat.stops;  // every slot's table, and one admission's list at a time
+    spec.penalties = feat.penalties;  // every slot's record
     if (feat.logprobs) {  // (the raw logits at the context ids too where a penalty can apply)
         spec.lp_k = LP_MAX_TOP;
-        spec.lp_side = feat.per_request || rep_penalty_active(p.rep_penalty);
+        spec.lp_side = feat.per_request || rep_penalty_active(p.rep_penalty) || feat.penalties;
     }
     s.slot.resize(S);
     s.pin = PinnedBuffer<int>(2 * S + 1);
@@ -2876,6 +2942,9 @@ void Engine::session_admit_checks(const Session& s, const GenRequest& rq, const 
         if (!s.feat.stops) throw std::runtime_error("EINVAL: this session was opened without DSOCR_SESSION_STOP");
         validate_stop_set(rq.stops, V);
     }
+    validate_penalties(rq.pen);
+    if (rq.pen.active() && !s.feat.penalties)
+        throw std::runtime_error("EINVAL: this session was opened without DSOCR_SESSION_PENALTIES");
     if (s.pending) throw std::runtime_error("EINVAL: a chunked admission is pending (advance it to the end or cancel it)");
     if (s.n >= s.S) throw std::runtime_error("EINVAL: every session slot is in use (retire one first)");
     const size_t P = rq.ids.size();
@@ -2969,6 +3038,11 @@ int Engine::session_admit_tail(Session& s, const GenRequest& rq, const GenParams
     }
     if (s.feat.logprobs) launch_dec_lp_partial(lp, st);
     launch_rep_penalty(pen, st);
+    if (s.feat.penalties) {  // the slot's record (none: an off record), then the penalty on the prefill's logits
+        const Penalties* pn = &rq.pen;
+        write_penalties(&pn, slot, 1);
+        launch_dec_out_penalty(penalty_args(sa, slot), st);
+    }
     launch_dec_sample(sa, st);  // the first token, its embedding into the slot's s_x row, the ban list
     if (s.feat.stops) {  // the slot's table (none: the count alone is cleared), then the match on this first selection
         build_stop_table(rq.stops, slot, 0);
@@ -2982,6 +3056,7 @@ int Engine::session_admit_tail(Session& s, const GenRequest& rq, const GenParams
     Session::Slot& sl = s.slot[slot];
     sl.max_new = max_new; sl.kv_pos = (int)P; sl.reported = 0; sl.rp = row; sl.prompt = (int)P;
     sl.biased = rq.bias.active();
+    sl.penalised = rq.pen.active();
     sl.stopped = rq.stops.active();
     sl.ids = rq.ids;
     sl.mask = rq.mask.empty() ? std::vector<uint8_t>(P, 0) : rq.mask;
@@ -3210,7 +3285,7 @@ void Engine::session_step_body(Session& s, bool screened, bool stops) {
 bool Engine::session_head_screened(const Session& s) const {
     if (s.feat.logprobs) return false;  // the screened head never forms the logits
     for (int b = 0; b < s.n; ++b)
-        if (s.slot[b].biased) return false;  // ... which a constraint is added to
+        if (s.slot[b].biased || s.slot[b].penalised) return false;  // ... which a constraint or a penalty acts on
     if (!s.feat.per_request) return s.screened;
     for (int b = 0; b < s.n; ++b)
         if (s.slot[b].rp.do_sample || s.slot[b].rp.rep_penalty != 1.0f) return false;
@@ -3326,6 +3401,8 @@ void Engine::session_slot_move(Session& s, int src, int dst, int rows_bound) {
                                      sizeof(float) * r.bias_ld, hipMemcpyDeviceToDevice, stream_));
         HIP_CHECK(hipMemcpyAsync(r.bias_on + dst, r.bias_on + src, sizeof(int), hipMemcpyDeviceToDevice, stream_));
     }
+    if (s.feat.penalties)  // the record travels with its page: 16 bytes
+        HIP_CHECK(hipMemcpyAsync(r.pen + dst, r.pen + src, sizeof(PenaltyRec), hipMemcpyDeviceToDevice, stream_));
     // the stop set travels with its page: a launch of its own (a page without one: the count, seen and hit alone)
     if (s.feat.stops) launch_stop_slot_move(r.stop_tab, r.stop_n, r.stop_seen, r.stop_hit, src, dst, stream_);
     s.slot[dst] = s.slot[src];

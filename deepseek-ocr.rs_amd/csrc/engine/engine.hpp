@@ -148,9 +148,21 @@ struct StopSet {
 // EINVAL: more than 16 sequences, a length of 0 or above 32, an id outside [0, vocab), two identical sequences
 void validate_stop_set(const StopSet& st, int vocab);
 
+// One request's frequency / presence penalties and min-p.  Off: all three at their defaults.
+struct Penalties {
+    float frequency = 0.f, presence = 0.f;
+    double min_p = 0.0;
+    bool active() const { return frequency != 0.f || presence != 0.f || min_p > 0.0; }
+    // the record the kernels read: ln_min_p = log(min_p) in f64, -inf when the filter is off
+    PenaltyRec rec() const;
+};
+// EINVAL: a non-finite frequency or presence; min_p NaN, below 0 or above 1
+void validate_penalties(const Penalties& pn);
+
 struct GenRequest {
     LogitBias bias;
     StopSet stops;
+    Penalties pen;
     std::vector<int> ids;
     std::vector<uint8_t> mask;
     const PagePixels* page = nullptr;
@@ -210,6 +222,8 @@ struct DecodeRows {
     // examined and the hits [S][2], and the staging buffer the admissions' lists are uploaded to
     int *stop_tab = nullptr, *stop_n = nullptr, *stop_seen = nullptr, *stop_hit = nullptr, *stop_stage = nullptr;
     int stop_stage_rows = 0;
+    // frequency / presence / min-p records (spec.penalties): one per row, every one starts off
+    PenaltyRec* pen = nullptr;
 };
 // What a caller of Engine::reserve_decode_rows asks for
 struct DecodeRowsSpec {
@@ -224,6 +238,7 @@ struct DecodeRowsSpec {
     size_t bias_stage = 0;     // ... and a list staging buffer of this many (id, value) pairs
     bool stops = false;        // stop-sequence rows (every count starts 0) ...
     int stop_stage_rows = 1;   // ... and staging for this many lists at a time
+    bool penalties = false;    // PenaltyRec rows (every record starts off)
 };
 typedef void (*TokenCb)(size_t, const int64_t*, void*);
 // rand_core seed_from_u64 for rand 0.8.5 StdRng, in the layout sampling.hip reads (RNG_WORDS words)
@@ -320,6 +335,9 @@ class Engine {
         // every slot keeps a stop table; an admission may carry a stop set (GenRequest::stops), and a burst's step
         // graph contains the match launch iff an active slot carries one
         bool stops = false;
+        // every slot keeps a PenaltyRec; an admission may carry penalties (GenRequest::pen), and a burst runs the
+        // exact head iff an active slot carries a record that is on
+        bool penalties = false;
     };
     struct SessionInfo {
         int slots = 0, active = 0, max_context = 0, out_cap = 0, kv_cap = 0, burst_cap = 0;
@@ -431,6 +449,10 @@ class Engine {
     // row `row`'s dense bias row and flag from the constraint (an inactive one clears the flag); `stage_off`: where
     // in the staging buffer its list goes (pairs)
     void build_logit_bias(const LogitBias& lb, int row, size_t stage_off);
+    // the penalty records of the same pages (only where rows_.pen is set), and rows [row0, row0 + n)'s records
+    // written from the requests' (pinned staging under "s_penstage"; the caller synchronises before the next write)
+    DecPenaltyArgs penalty_args(const DecSampleArgs& sa, int row0);
+    void write_penalties(const Penalties* const* pn, int row0, int n);
     // the stop rows of the same pages (only where rows_.stop_tab is set), and the match launch on them (counted)
     DecStopArgs stop_args(const DecSampleArgs& sa, int row0);
     void stop_match(const DecSampleArgs& sa, int row0);

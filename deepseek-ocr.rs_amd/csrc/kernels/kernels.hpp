@@ -286,6 +286,14 @@ struct RowParams {
 constexpr int ROWPAR_INTS = (int)(sizeof(RowParams) / sizeof(int));
 static_assert(sizeof(RowParams) == 40 && sizeof(RowParams) % sizeof(int) == 0, "RowParams is staged as ints");
 inline bool rep_penalty_active(float p) { return p > 0.f && fabsf(p - 1.0f) > 1.1920929e-07f; }
+// One page's frequency / presence penalties and min-p as the kernels read them: a record of its own,
+// so RowParams keeps its layout.  ln_min_p = log(min_p) formed on the host in f64; -inf: no min-p filter.
+struct PenaltyRec {
+    float frequency = 0.f, presence = 0.f;
+    double ln_min_p = -INFINITY;
+    bool on() const { return frequency != 0.f || presence != 0.f || ln_min_p > -INFINITY; }
+};
+static_assert(sizeof(PenaltyRec) == 16, "PenaltyRec is staged and moved as 16 bytes");
 // Repetition penalty over the context tokens (sampling.rs:34-96), in place on the logits.
 // rows != null: every row reads its own penalty (launched unconditionally; a row at 1.0 leaves its logits alone)
 struct SampleArgs {
@@ -621,6 +629,10 @@ struct DecSampleArgs {
     // per-row parameters (decode_select_rows.hip): when set, ngram / eos / do_sample / temperature / top_k / top_p
     // above are not read; both selectors run and every row takes the one its record names
     const RowParams* rows = nullptr;
+    // min-p (sampled rows only): a candidate stays iff q - qmax >= ln_min_p; per row from pen[b] when
+    // set, else the scalar.  -inf: no filter, and the sampler's outputs are those of a build without it
+    double ln_min_p = -INFINITY;
+    const PenaltyRec* pen = nullptr;
 };
 // rand StdRng state words per page: ChaCha12 key, 64-bit block counter, buffer index, 64-word buffer
 constexpr int RNG_KEY = 0, RNG_CTR = 8, RNG_IDX = 10, RNG_BUF = 16, RNG_WORDS = 80;
@@ -673,6 +685,17 @@ struct DecBiasArgs {
     const int* on = nullptr;  // [B]
 };
 void launch_dec_logit_bias(const DecBiasArgs& a, hipStream_t s);
+// Frequency / presence penalties over the generated tokens (decode_penalty.hip): for every id t that
+// occurs c > 0 times in out_ids[b][0 .. out_len[b]) (ids outside [0, V) skipped), l[b][t] -= frequency * c + presence
+// in f32, each operation rounded.  After launch_rep_penalty, before the selection.  A row whose record has
+// frequency == presence == 0 is neither read nor written; columns [V, ld) are never written.
+struct DecPenaltyArgs {
+    float* logits = nullptr; int B = 0, V = 0; long ld = 0;
+    const int* out_ids = nullptr; long out_cap = 0;  // [B][out_cap]
+    const int* out_len = nullptr;                    // [B]
+    const PenaltyRec* rec = nullptr;                 // [B]
+};
+void launch_dec_out_penalty(const DecPenaltyArgs& a, hipStream_t s);
 // Stop sequences matched inside the decode step (decode_stop.hip).  Per row: a table
 // [STOP_MAX_SEQS][1 + STOP_MAX_LEN] of int32 (a length, then the ids), n_seq, `seen` (the out_len already examined)
 // and hit[2] = {lowest matching sequence or -1, its length}.

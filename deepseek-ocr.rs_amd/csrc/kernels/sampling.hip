@@ -6,7 +6,8 @@
 //
 // One block of 1024 threads per page, after the lm_head + repetition penalty:
 //   1. n-gram ban bitmap of the whole vocabulary in LDS; ban ignored if it leaves nothing
-//   2. candidates = finite logit/T, compacted in index order (contiguous per-thread ranges)
+//   2. candidates = finite logit/T, compacted in index order (contiguous per-thread ranges); with min-p
+//      (not in the reference) only those with q - qmax >= ln(min_p)
 //   3. top-k / top-p: stable LSD radix sort (8 x 4-bit digits) of the candidates by descending
 //      logit — ties keep the lower index first, as Rust's stable sort_by does; top-p's f64 sums
 //      run in sorted order on one thread (the reference's sequential fold, bit for bit)
@@ -239,12 +240,33 @@ __global__ __launch_bounds__(ST_NT) void dec_stoch_select_kernel(DecSampleArgs a
     // ---- 2. candidates in index order: finite logit / T (f64), contiguous range per thread
     const int chunk = (V + ST_NT - 1) / ST_NT;
     const int v0 = min(V, tid * chunk), v1 = min(V, v0 + chunk);
+    // min-p: the maximum of q over the same set first, then one more condition on a candidate.
+    // Off (-inf, block-uniform): no pass, and `mp_keep` is true for every q, so nothing below changes
+    const double ln_min_p = a.pen ? a.pen[b].ln_min_p : a.ln_min_p;
+    const bool minp = ln_min_p > -INFINITY;
+    double mp_qmax = 0.0;
+    if (minp) {
+        float m = -INFINITY;
+        for (int v = v0; v < v1; ++v) {
+            const float x = lg[v];
+            const double q = (double)x / T;
+            if (q > -INFINITY && q < INFINITY && !(use_ban && is_banned(ban, v))) m = fmaxf(m, x);
+        }
+        for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+        if ((tid & 63) == 0) fmax_s[tid >> 6] = m;
+        __syncthreads();
+        m = fmax_s[0];
+        for (int w = 1; w < ST_NT / 64; ++w) m = fmaxf(m, fmax_s[w]);
+        __syncthreads();  // (fmax_s is written again below)
+        mp_qmax = (double)m / T;  // the division is monotonic: the maximum of q is q of the maximum
+    }
+    auto mp_keep = [&](double q) { return !minp || __dsub_rn(q, mp_qmax) >= ln_min_p; };
     int c = 0;
     float lmax = -INFINITY;
     for (int v = v0; v < v1; ++v) {
         const float x = lg[v];
         const double q = (double)x / T;
-        if (q > -INFINITY && q < INFINITY && !(use_ban && is_banned(ban, v))) {
+        if (q > -INFINITY && q < INFINITY && !(use_ban && is_banned(ban, v)) && mp_keep(q)) {
             ++c;
             lmax = fmaxf(lmax, x);
         }
@@ -259,7 +281,7 @@ __global__ __launch_bounds__(ST_NT) void dec_stoch_select_kernel(DecSampleArgs a
         for (int j = 0; j < 8; ++j) {
             const int v = u0 + j;
             const double q = (double)xx[j] / T;
-            if (v < v1 && q > -INFINITY && q < INFINITY && !(use_ban && is_banned(ban, v))) {
+            if (v < v1 && q > -INFINITY && q < INFINITY && !(use_ban && is_banned(ban, v)) && mp_keep(q)) {
                 sk0[off] = desc_key(xx[j]);
                 si0[off] = v;
                 ++off;

@@ -99,6 +99,11 @@ class StopHitC(C.Structure):
     _fields_ = [("seq", C.c_int32), ("match_len", C.c_int32)]
 
 
+class PenaltiesC(C.Structure):
+    """dsocr_penalties: one request's frequency / presence penalties and min-p."""
+    _fields_ = [("frequency", C.c_float), ("presence", C.c_float), ("min_p", C.c_double)]
+
+
 class RowParamsC(C.Structure):
     """dsocr_row_params: one row of dsocr_k_select_rows."""
     _fields_ = [("do_sample", C.c_int), ("temperature", C.c_double), ("top_p", C.c_double), ("top_k", C.c_size_t),
@@ -121,6 +126,7 @@ SESSION_PER_REQUEST = 1  # DSOCR_SESSION_PER_REQUEST
 SESSION_LOGPROBS = 2     # DSOCR_SESSION_LOGPROBS
 SESSION_LOGIT_BIAS = 4   # DSOCR_SESSION_LOGIT_BIAS
 SESSION_STOP = 8         # DSOCR_SESSION_STOP
+SESSION_PENALTIES = 16   # DSOCR_SESSION_PENALTIES
 MAX_STOP_SEQS = 16       # DSOCR_MAX_STOP_SEQS
 MAX_STOP_LEN = 32        # DSOCR_MAX_STOP_LEN
 SESSION_ADMIT_PENDING = 0x100  # DSOCR_SESSION_ADMIT_PENDING (dsocr_session_info flags while an admission is pending)
@@ -168,6 +174,8 @@ EXPORTS = [
     "dsocr_logit_bias_check", "dsocr_generate_logit_bias", "dsocr_session_stage_logit_bias", "dsocr_k_logit_bias",
     "dsocr_stop_set_check", "dsocr_generate_stop", "dsocr_session_stage_stop", "dsocr_session_stop_hit",
     "dsocr_stop_launches", "dsocr_k_stop_match", "dsocr_generate_stop_stream",
+    "dsocr_penalties_check", "dsocr_generate_penalties", "dsocr_session_stage_penalties", "dsocr_k_out_penalty",
+    "dsocr_k_sample_stoch_min_p",
 ]
 
 # model variants behind the deepseek engine (dsocr_engine_variant)
@@ -324,6 +332,15 @@ def lib():
     L.dsocr_session_stop_hit.argtypes = [vp, i32, C.POINTER(StopHitC)]
     L.dsocr_stop_launches.argtypes = [vp, C.POINTER(sz)]
     L.dsocr_k_stop_match.argtypes = [i32, i32, i32] + [vp] * 14
+    L.dsocr_penalties_check.argtypes = [C.POINTER(PenaltiesC)]
+    L.dsocr_generate_penalties.argtypes = [vp, sz, C.POINTER(RequestC), C.POINTER(DecodeParamsC), C.POINTER(ResultC),
+                                           C.POINTER(C.POINTER(PenaltiesC)), C.POINTER(C.POINTER(StopSetC)),
+                                           C.POINTER(StopHitC), C.POINTER(C.POINTER(LogitBiasC)), sz,
+                                           C.POINTER(LogprobsC)]
+    L.dsocr_session_stage_penalties.argtypes = [vp, C.POINTER(PenaltiesC)]
+    L.dsocr_k_out_penalty.argtypes = [i32, i32, i32, vp, vp, i32, vp, C.POINTER(PenaltiesC)]
+    L.dsocr_k_sample_stoch_min_p.argtypes = [i32, i32, vp, vp, i32, vp, i32, f32, C.c_double, C.c_size_t, C.c_double,
+                                             vp, C.c_uint64, i32, vp]
     _lib = L
     return L
 

@@ -104,6 +104,12 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--stop-token-ids", metavar="ID,ID,...",
                    help="end the generation in front of any of these token ids")
     p.add_argument("--include-stop", action="store_true", help="keep the matched stop in the output")
+    p.add_argument("--frequency-penalty", type=float, default=None, metavar="X",
+                   help="lower a generated token's logit by X for every time it was generated so far")
+    p.add_argument("--presence-penalty", type=float, default=None, metavar="X",
+                   help="lower the logit of every token generated so far by X")
+    p.add_argument("--min-p", type=float, default=None, metavar="X",
+                   help="when sampling, keep only tokens at least X (0..1) times as likely as the most likely one")
     p.add_argument("--slots", type=int, default=0, metavar="N",
                    help="treat every --image as its own one-page document (the prompt has one <image>) and decode them "
                         "together in a session of N slots (1..8); results print in input order.  0 = off")
@@ -237,7 +243,24 @@ def token_constraint(args) -> dict:
     if kw and getattr(args, "slots", 0):
         raise DsocrError(1, "--ban-token / --allow-tokens-file / --logit-bias apply to one document: not with --slots")
     kw.update(stop_arguments(args))
+    kw.update(penalty_arguments(args))
     return kw
+
+
+def penalty_arguments(args) -> dict:
+    """--frequency-penalty / --presence-penalty / --min-p as the keywords of ``engine.decode`` ({} when they ask for
+    nothing).  Checked here, before any load."""
+    from .penalties import PenaltyError, make_penalties
+    try:
+        pn = make_penalties(getattr(args, "frequency_penalty", None), getattr(args, "presence_penalty", None),
+                            getattr(args, "min_p", None))
+    except PenaltyError as e:
+        raise DsocrError(1, f"--frequency-penalty / --presence-penalty / --min-p: {e}") from None
+    if pn is None:
+        return {}
+    if getattr(args, "slots", 0):
+        raise DsocrError(1, "--frequency-penalty / --presence-penalty / --min-p apply to one document: not with --slots")
+    return {"frequency_penalty": pn.frequency, "presence_penalty": pn.presence, "min_p": pn.min_p}
 
 
 def stop_arguments(args) -> dict:

@@ -19,9 +19,11 @@ from typing import Any, Callable, Optional, Sequence
 import numpy as np
 
 from ._lib import (DTYPES, LOAD_PACKED_EXPERTS, MAX_TOP_LOGPROBS, DecodeParamsC, DsocrError, LoadArgs, LogitBiasC, LogprobsC,
-                   RequestC, ResultC, STREAM_CB, SESSION_LOGIT_BIAS, SESSION_LOGPROBS, SESSION_PER_REQUEST, SESSION_STOP,
+                   PenaltiesC, RequestC, ResultC, STREAM_CB, SESSION_LOGIT_BIAS, SESSION_LOGPROBS, SESSION_PENALTIES,
+                   SESSION_PER_REQUEST, SESSION_STOP,
                    SessionDescC, SlotStatusC, StopHitC, StopSetC, TimingsC, VisionSettingsC, check, lib)
 from .constraint import ConstraintError, LogitConstraint, merge_constraint
+from .penalties import Penalties, PenaltyError, make_penalties
 from .stops import StopError, StopSet, apply_stops, merge_stops
 
 
@@ -61,6 +63,22 @@ def _bias_c(c: Optional[LogitConstraint], keep) -> Optional[LogitBiasC]:
     keep += [ids, vals]
     return LogitBiasC(ids.ctypes.data_as(C.POINTER(C.c_int64)), vals.ctypes.data_as(C.POINTER(C.c_float)), len(ids),
                       1 if c.allow_only else 0)
+
+
+def _penalties(frequency_penalty, presence_penalty, min_p) -> Optional[Penalties]:
+    """The three request arguments as one checked record (dsocr.penalties), None when they ask for nothing; a bad
+    one is the engine's EINVAL."""
+    try:
+        return make_penalties(frequency_penalty, presence_penalty, min_p)
+    except PenaltyError as e:
+        raise DsocrError(1, f"EINVAL: penalties: {e}") from None
+
+
+def _penalties_c(pn: Optional[Penalties]) -> Optional[PenaltiesC]:
+    """(a record of three numbers: nothing for the caller to keep alive)"""
+    if pn is None:
+        return None
+    return PenaltiesC(pn.frequency, pn.presence, pn.min_p)
 
 
 @dataclass
@@ -450,6 +468,27 @@ class DeepseekOcrEngine:
         got = (b.ids(), [(int(h.seq), int(h.match_len)) for h in hits])
         return (*got, *lp.unpack()) if lp else got
 
+    def generate_penalties(self, requests, penalties, params: DecodeParameters = DecodeParameters(),
+                           ignore_eos: bool = False, top_k: Optional[int] = None, constraints=None, stop_sets=None):
+        """generate_batch with one penalty record per request (dsocr_generate_penalties): ``penalties[i]`` is a
+        ``dsocr.penalties.Penalties`` or None; ``constraints`` and ``stop_sets`` likewise (or None for none).  Returns
+        what ``generate_stops`` returns: ``(ids, hits)``, with ``top_k`` followed by the three log-probability lists."""
+        n = len(requests)
+        if len(penalties) != n or any(x is not None and len(x) != n for x in (constraints, stop_sets)):
+            raise DsocrError(1, "one penalty record (or None) per request")
+        _check_top_k(top_k)
+        b = _Batch(self, requests, params)
+        pen = _ptr_array(PenaltiesC, [_penalties_c(pn) for pn in penalties], b.keep)
+        stops = None if stop_sets is None else _ptr_array(StopSetC, [_stop_c(ss, b.keep) for ss in stop_sets], b.keep)
+        bias = None if constraints is None else _ptr_array(LogitBiasC, [_bias_c(c, b.keep) for c in constraints], b.keep)
+        hits = (StopHitC * b.n)()
+        lp = None if top_k is None else _LogprobBuffers(b.n, b.cap, int(top_k))
+        pc = _params_c(params, self.eos_token_id, ignore_eos)
+        check(lib().dsocr_generate_penalties(self._h, b.n, b.reqs, C.byref(pc), b.res, pen, stops, hits, bias,
+                                             lp.k if lp else 0, lp.c if lp else None))
+        got = (b.ids(), [(int(h.seq), int(h.match_len)) for h in hits])
+        return (*got, *lp.unpack()) if lp else got
+
     def generate_stop_stream(self, request, stop_set, params: DecodeParameters = DecodeParameters(),
                              stream: Optional[Callable] = None, ignore_eos: bool = False):
         """``generate`` (one page, its stream callback) with a stop set (dsocr_generate_stop_stream): ``(ids, (seq,
@@ -536,7 +575,7 @@ class DeepseekOcrEngine:
     # ------------------------------------------------------------------ decode sessions
     def open_session(self, slots: int, max_context: int, params: DecodeParameters = DecodeParameters(),
                      ignore_eos: bool = False, per_request: bool = False, logprobs: bool = False,
-                     logit_bias: bool = False, stops: bool = False) -> "Session":
+                     logit_bias: bool = False, stops: bool = False, penalties: bool = False) -> "Session":
         """A long-lived batch of `slots` pages (dsocr_session_open): pages are admitted and retired between bursts
         of decode steps.  `params` are the session's; params.max_new_tokens bounds a request's own.
         ``per_request`` (dsocr_session_open_ex, DSOCR_SESSION_PER_REQUEST): `params` are only the defaults and
@@ -545,16 +584,22 @@ class DeepseekOcrEngine:
         (DSOCR_SESSION_LOGIT_BIAS): every admission may carry ``logit_bias`` / ``allowed_token_ids`` /
         ``banned_token_ids``; a burst with a constrained page runs the exact head.  ``stops`` (DSOCR_SESSION_STOP):
         every admission may carry ``stop`` / ``stop_token_ids``; the step of a burst with such a page contains the
-        match launch."""
-        return Session(self, slots, max_context, params, ignore_eos, per_request, logprobs, logit_bias, stops)
+        match launch.  ``penalties`` (DSOCR_SESSION_PENALTIES): every admission may carry ``frequency_penalty`` /
+        ``presence_penalty`` / ``min_p``; a burst with such a page runs the exact head."""
+        return Session(self, slots, max_context, params, ignore_eos, per_request, logprobs, logit_bias, stops, penalties)
 
     # ------------------------------------------------------------------ OcrEngine::decode
     def decode(self, tokenizer, prompt: str, images: Sequence, vision: VisionSettings,
                params: DecodeParameters, stream: Optional[Callable] = None,
                logprobs: Optional[int] = None, logit_bias=None, allowed_token_ids=None,
                banned_token_ids=None, stop=None, stop_token_ids=None,
-               include_stop_in_output: bool = False) -> DecodeOutcome:
-        """``stop`` (a string or a list of strings) and ``stop_token_ids`` end the page on the step that completes one
+               include_stop_in_output: bool = False, frequency_penalty=None, presence_penalty=None,
+               min_p=None) -> DecodeOutcome:
+        """``frequency_penalty`` / ``presence_penalty`` lower the logit of every id the page has already generated
+        (by ``frequency * count + presence``; prompt and image slots do not count) and ``min_p`` keeps, when sampling,
+        only tokens at least ``min_p`` times as likely as the most likely one (``dsocr.penalties``; ``stream`` is not
+        called).
+        ``stop`` (a string or a list of strings) and ``stop_token_ids`` end the page on the step that completes one
         of them (merged by ``dsocr.stops.merge_stops``).  ``stream`` is called live, with every token as it is
         emitted, matched ones included (dsocr_generate_stop_stream: ``dsocr.stops.TokenHoldback`` tells a consumer
         what is safe to show); together with ``logprobs`` or a constraint it is not called (dsocr_generate_stop).  The matched tokens are trimmed from the ids, the text and the log-probability
@@ -566,14 +611,19 @@ class DeepseekOcrEngine:
         may emit (merged by ``dsocr.constraint.merge_constraint``; ``stream`` is not called either)."""
         con = _constraint(logit_bias, allowed_token_ids, banned_token_ids, self.vocab)
         ss = _stops(stop, stop_token_ids, tokenizer, self.vocab)
+        pen = _penalties(frequency_penalty, presence_penalty, min_p)
         pages = [Page(im, vision, self) for im in images]
         ids, mask = build_prompt_tokens(tokenizer, prompt, [p.n_image_tokens for p in pages])
         token_lp = top = None
-        if logprobs is not None or con is not None or ss is not None:
+        if logprobs is not None or con is not None or ss is not None or pen is not None:
             rows = np.concatenate(self.image_embeddings(pages), axis=0) if len(pages) > 1 else None
             req = (ids, mask, pages[0] if len(pages) == 1 else None, rows)
-        if ss is not None:
-            if stream is not None and logprobs is None and con is None:
+        if ss is not None or pen is not None:
+            if pen is not None:
+                got = self.generate_penalties([req], [pen], params, top_k=None if logprobs is None else int(logprobs),
+                                              constraints=None if con is None else [con],
+                                              stop_sets=None if ss is None else [ss])
+            elif stream is not None and logprobs is None and con is None:
                 # live: the callback sees every token as it is emitted, matched ones included (the caller holds back)
                 got = self.generate_stop_stream(req, ss, params, stream)
                 got = ([got[0]], [got[1]])
@@ -636,7 +686,7 @@ class Session:
 
     def __init__(self, engine: DeepseekOcrEngine, slots: int, max_context: int, params: DecodeParameters,
                  ignore_eos: bool = False, per_request: bool = False, logprobs: bool = False, logit_bias: bool = False,
-                 stops: bool = False):
+                 stops: bool = False, penalties: bool = False):
         self._e = None
         # the (StopSet, include) record of an admission follows its page: staged for the C call that admits it,
         # pending while a chunked admission runs, then its slot's
@@ -644,7 +694,9 @@ class Session:
         self._pending_page = None  # the page of the pending chunked admission (the engine reads its pixels)
         pc = _params_c(params, engine.eos_token_id, ignore_eos)
         flags = ((SESSION_PER_REQUEST if per_request else 0) | (SESSION_LOGPROBS if logprobs else 0) |
-                 (SESSION_LOGIT_BIAS if logit_bias else 0) | (SESSION_STOP if stops else 0))
+                 (SESSION_LOGIT_BIAS if logit_bias else 0) | (SESSION_STOP if stops else 0) |
+                 (SESSION_PENALTIES if penalties else 0))
+        self.has_penalties = bool(penalties)
         self.has_stops = bool(stops)
         self.has_logprobs = bool(logprobs)
         self.has_logit_bias = bool(logit_bias)
@@ -672,7 +724,8 @@ class Session:
               params: Optional[DecodeParameters] = None, eos_token_id: Optional[int] = None,
               ignore_eos: Optional[bool] = None, logprobs: Optional[int] = None, logit_bias=None,
               allowed_token_ids=None, banned_token_ids=None, stop=None, stop_token_ids=None,
-              include_stop_in_output: bool = False, tokenizer=None, stops: Optional[StopSet] = None) -> int:
+              include_stop_in_output: bool = False, tokenizer=None, stops: Optional[StopSet] = None,
+              frequency_penalty=None, presence_penalty=None, min_p=None) -> int:
         """Without ``params``: the session's parameters with this page's ``max_new_tokens`` / ``seed``
         (dsocr_session_admit).  With ``params``: the page's whole parameter set (dsocr_session_admit_params; its
         max_new_tokens and seed count, the two keyword arguments are then not read); ``eos_token_id`` /
@@ -685,10 +738,13 @@ class Session:
         ``stop`` / ``stop_token_ids`` (or ``stops``, a ``StopSet`` merged elsewhere): the page's stop set (a session
         opened with ``stops``; EINVAL otherwise), matched from its first token on; a stop string needs ``tokenizer``.
         The session returns ids as the device wrote them, matched tokens included: ``stop_hit(slot)`` names the hit
-        and ``retire_stopped`` trims by it unless ``include_stop_in_output``."""
+        and ``retire_stopped`` trims by it unless ``include_stop_in_output``.
+        ``frequency_penalty`` / ``presence_penalty`` / ``min_p``: the page's penalties (a session opened with
+        ``penalties``; EINVAL otherwise), applied from its first token on; ``min_p`` acts on a sampled page only."""
         req, _, _keep = self._admission((ids, mask, page, image_rows), None, logprobs,
                                         (logit_bias, allowed_token_ids, banned_token_ids),
-                                        (stop, stop_token_ids, include_stop_in_output, tokenizer, stops))
+                                        (stop, stop_token_ids, include_stop_in_output, tokenizer, stops),
+                                        (frequency_penalty, presence_penalty, min_p))
         slot = C.c_int(-1)
         if params is not None:
             pc = _params_c(params, self._eos if eos_token_id is None else int(eos_token_id),
@@ -700,11 +756,13 @@ class Session:
                                  0 if seed is None else 1, seed or 0, C.byref(slot))
         return self._admitted_stops(slot.value)
 
-    def _admission(self, request, request_params, logprobs, constraint, stops):
+    def _admission(self, request, request_params, logprobs, constraint, stops, penalties=(None, None, None)):
         """What every admission form does before its C call, in this order: the ``logprobs`` check, the request
         (``request``: ids, mask, page, image rows), its parameter record (``request_params``: ``_request_params``'
         arguments, or None for none), the stop set merged and checked (``stops``: ``_check_stops``' arguments), then
-        the constraint staged (``constraint``: ``_stage_constraint``'s arguments) and the stop set staged.  Returns
+        the constraint staged (``constraint``: ``_stage_constraint``'s arguments) and the stop set staged; the
+        penalties (``penalties``: frequency_penalty, presence_penalty, min_p) are checked with the stop set, before
+        anything is staged, and staged last.  Returns
         the request, the parameter record and the list that keeps their arrays alive; the checked stop record is
         ``_staged_stops``."""
         self._check_logprobs(logprobs)
@@ -712,9 +770,33 @@ class Session:
         req = self._e._request(*request, keep)
         pc = None if request_params is None else self._request_params(*request_params)
         checked = self._check_stops(*stops)
+        pen = self._check_penalties(*penalties)
         self._stage_constraint(*constraint)
         self._stage_stops(checked)
+        self._stage_penalties(pen)
         return req, pc, keep
+
+    def _check_penalties(self, frequency_penalty, presence_penalty, min_p) -> Optional[Penalties]:
+        """The penalties of an admission, checked before anything is staged for it (None: none)."""
+        pen = _penalties(frequency_penalty, presence_penalty, min_p)
+        if pen is not None and not self.has_penalties:
+            raise DsocrError(1, "EINVAL: this session was opened without penalties")
+        return pen
+
+    def _stage_penalties(self, pen: Optional[Penalties]) -> None:
+        """Stages the checked record for the admission call that follows (dsocr_session_stage_penalties), which
+        consumes it.  Should the staging itself fail, what was staged before it is cleared: nothing staged may
+        outlive a failed admission."""
+        if pen is None:
+            return
+        rec = _penalties_c(pen)
+        try:
+            check(lib().dsocr_session_stage_penalties(self._e._h, C.byref(rec)))
+        except DsocrError:
+            lib().dsocr_session_stage_logit_bias(self._e._h, None)
+            lib().dsocr_session_stage_stop(self._e._h, None)
+            self._staged_stops = None
+            raise
 
     def _admission_call(self, fn, *args) -> None:
         """The C call of an admission.  It consumes what was staged whether it succeeds or not, so after a failure
@@ -813,7 +895,8 @@ class Session:
                     params: Optional[DecodeParameters] = None, eos_token_id: Optional[int] = None,
                     ignore_eos: Optional[bool] = None, logprobs: Optional[int] = None, logit_bias=None,
                     allowed_token_ids=None, banned_token_ids=None, stop=None, stop_token_ids=None,
-                    include_stop_in_output: bool = False, tokenizer=None, stops: Optional[StopSet] = None) -> int:
+                    include_stop_in_output: bool = False, tokenizer=None, stops: Optional[StopSet] = None,
+                    frequency_penalty=None, presence_penalty=None, min_p=None) -> int:
         """``admit`` in slices (dsocr_session_admit_begin): every check runs here and nothing is launched; the work
         is done by ``admit_advance``, one slice per call (the page's vision, then the prompt in chunks of
         ``chunk_rows`` >= 32 rows), with ``step`` / ``retire`` legal in between.  Returns the admission's ticket.
@@ -822,7 +905,8 @@ class Session:
         req, pc, _keep = self._admission((ids, mask, page, image_rows),
                                          (params, max_new_tokens, seed, eos_token_id, ignore_eos), logprobs,
                                          (logit_bias, allowed_token_ids, banned_token_ids),
-                                         (stop, stop_token_ids, include_stop_in_output, tokenizer, stops))
+                                         (stop, stop_token_ids, include_stop_in_output, tokenizer, stops),
+                                         (frequency_penalty, presence_penalty, min_p))
         self._pending_stops = None
         ticket = C.c_int(-1)
         self._admission_call(lib().dsocr_session_admit_begin, C.byref(req), C.byref(pc), max(int(chunk_rows), 0),
@@ -878,7 +962,8 @@ class Session:
                      eos_token_id: Optional[int] = None, ignore_eos: Optional[bool] = None,
                      logprobs: Optional[int] = None, logit_bias=None, allowed_token_ids=None,
                      banned_token_ids=None, stop=None, stop_token_ids=None, include_stop_in_output: bool = False,
-                     tokenizer=None, stops: Optional[StopSet] = None) -> int:
+                     tokenizer=None, stops: Optional[StopSet] = None, frequency_penalty=None,
+                     presence_penalty=None, min_p=None) -> int:
         """``admit`` for a prompt that starts with the entry's rows (dsocr_session_admit_prefix): ``ids`` / ``mask``
         are the whole prompt's, no page and no image rows; vision and the prefill of the entry's rows are skipped.
         The keywords are ``admit``'s (without ``params``: the session's parameters with this ``max_new_tokens`` /
@@ -886,7 +971,8 @@ class Session:
         req, pc, _keep = self._admission((ids, mask, None, None),
                                          (params, max_new_tokens, seed, eos_token_id, ignore_eos), logprobs,
                                          (logit_bias, allowed_token_ids, banned_token_ids),
-                                         (stop, stop_token_ids, include_stop_in_output, tokenizer, stops))
+                                         (stop, stop_token_ids, include_stop_in_output, tokenizer, stops),
+                                         (frequency_penalty, presence_penalty, min_p))
         slot = C.c_int(-1)
         self._admission_call(lib().dsocr_session_admit_prefix, int(handle), C.byref(req), C.byref(pc), C.byref(slot))
         return self._admitted_stops(slot.value)

@@ -32,6 +32,12 @@ string can arise from another tokenisation) and retires the slot on a hit, ``on_
 can remove, and the outcome is trimmed unless ``include_stop_in_output``.  Without the flag the request runs alone
 through ``engine.decode(...)`` with the same arguments after the session drained.
 
+Penalties: ``submit(..., frequency_penalty=X, presence_penalty=X, min_p=X)`` are checked on the caller's thread
+(``dsocr.penalties.make_penalties``; a bad one fails the future).  ``BatchScheduler(..., penalties=True)`` opens the
+session with ``penalties=True`` and such a request shares it (a burst with a penalised page runs the exact head);
+without the flag it runs alone through ``engine.decode(...)`` with the same arguments after the session drained.
+Prefix-cache keys do not see the record.
+
 Page prefix cache: ``BatchScheduler(..., prefix_cache=N)`` (default 0: nothing changes) keeps the K/V rows of up to N
 pages' prompt prefixes (BOS and the image rows) in the session.  After a one-image request is admitted its prefix is
 kept (``Session.keep_prefix``, rows = index of the last image position + 1) under the key (SHA-256 of the image as
@@ -62,6 +68,7 @@ from dataclasses import dataclass, field, fields
 from typing import Any, Callable, Optional, Sequence
 
 from .constraint import merge_constraint
+from .penalties import make_penalties
 from .stops import TextStop, TokenHoldback, merge_stops
 from .engine import DecodeOutcome, DecodeParameters, Page, VisionSettings, build_prompt_tokens, normalize_text
 
@@ -95,6 +102,7 @@ class _Request:
     prefix_rows: int = 0
     constraint: Any = None  # the request's merged LogitConstraint, or None
     stops: Any = None       # the request's merged StopSet, or None
+    penalties: Any = None   # the request's checked Penalties, or None
     stop_args: dict = field(default_factory=dict)  # ... as the keywords engine.decode takes
     include_stop: bool = False
     holdback: Any = None    # TokenHoldback of a streaming request with stops
@@ -138,6 +146,11 @@ def _takes_entry(cb) -> bool:
     return True
 
 
+def _penalty_kwargs(pn) -> dict:
+    """A checked Penalties record as the keywords ``Session.admit`` and ``engine.decode`` take."""
+    return dict(frequency_penalty=pn.frequency, presence_penalty=pn.presence, min_p=pn.min_p)
+
+
 def _decode_text(tokenizer, ids) -> str:
     if not hasattr(tokenizer, "decode"):
         return ""
@@ -151,7 +164,8 @@ class BatchScheduler:
     def __init__(self, engine, tokenizer, slots: int, max_context: int,
                  defaults: DecodeParameters = DecodeParameters(), vision: Optional[VisionSettings] = None,
                  prepare: Optional[Callable] = None, per_request_params: bool = False, logprobs: bool = False,
-                 prefix_cache: int = 0, admit_chunk: int = 0, logit_bias: bool = False, stops: bool = False):
+                 prefix_cache: int = 0, admit_chunk: int = 0, logit_bias: bool = False, stops: bool = False,
+                 penalties: bool = False):
         if not 1 <= int(slots) <= 8:
             raise ValueError("a session has 1..8 slots")
         if int(admit_chunk) != 0 and int(admit_chunk) < 32:
@@ -176,6 +190,7 @@ class BatchScheduler:
         self.logprobs = bool(logprobs)
         self.logit_bias = bool(logit_bias)
         self.stops = bool(stops)
+        self.penalties = bool(penalties)
         self.vision = vision or VisionSettings()
         self._prepare = prepare or _default_prepare
         self._queue: deque = deque()
@@ -208,8 +223,10 @@ class BatchScheduler:
                params: Optional[DecodeParameters] = None, on_token: Optional[Callable] = None,
                logprobs: Optional[int] = None, logit_bias=None, allowed_token_ids=None,
                banned_token_ids=None, stop=None, stop_token_ids=None,
-               include_stop_in_output: bool = False) -> Future:
-        """``stop`` / ``stop_token_ids`` / ``include_stop_in_output``: the request's stop set (see the module text).
+               include_stop_in_output: bool = False, frequency_penalty=None, presence_penalty=None,
+               min_p=None) -> Future:
+        """``frequency_penalty`` / ``presence_penalty`` / ``min_p``: the request's penalties (see the module text).
+        ``stop`` / ``stop_token_ids`` / ``include_stop_in_output``: the request's stop set (see the module text).
         ``logit_bias`` / ``allowed_token_ids`` / ``banned_token_ids``: the request's token constraint (see the
         module text).  ``logprobs`` = K (0..20) asks for the request's per-token log-probabilities.  It changes the arity of
         ``on_token``: the callback is then called as ``on_token(n, tokens, entry)``, with ``entry = (logprob,
@@ -227,6 +244,7 @@ class BatchScheduler:
             constraint = merge_constraint(logit_bias, allowed_token_ids, banned_token_ids,
                                           getattr(self.engine, "vocab", None))
             stops = merge_stops(stop, stop_token_ids, self.tokenizer, getattr(self.engine, "vocab", None))
+            penalties = make_penalties(frequency_penalty, presence_penalty, min_p)
         except ValueError as e:
             fut.set_exception(e)
             return fut
@@ -244,6 +262,7 @@ class BatchScheduler:
             rq.pages = list(pages)
         rq.logprobs = None if logprobs is None else int(logprobs)
         rq.constraint = constraint
+        rq.penalties = penalties
         if stops is not None:
             rq.stops, rq.include_stop = stops, bool(include_stop_in_output)
             rq.stop_args = dict(stop=stop, stop_token_ids=stop_token_ids, include_stop_in_output=rq.include_stop)
@@ -252,7 +271,8 @@ class BatchScheduler:
             if stops.strings:
                 rq.text_stop = TextStop(stops.strings, rq.include_stop)
         rq.exclusive = (not self.compatible(params, len(rq.ids)) or (rq.logprobs is not None and not self.logprobs) or
-                        (constraint is not None and not self.logit_bias) or (stops is not None and not self.stops))
+                        (constraint is not None and not self.logit_bias) or (stops is not None and not self.stops) or
+                        (penalties is not None and not self.penalties))
         if self.prefix_cache and len(rq.images) == 1 and not rq.exclusive and any(rq.mask):
             rows = max(i for i, m in enumerate(rq.mask) if m) + 1
             if rows < len(rq.ids):  # some text follows the image: the last row's logits come from a new row
@@ -387,6 +407,8 @@ class BatchScheduler:
                 kw["logit_bias"] = True
             if self.stops:
                 kw["stops"] = True
+            if self.penalties:
+                kw["penalties"] = True
             self._session = self.engine.open_session(self.slots, self.max_context, self.defaults, **kw)
 
     def _admit_args(self, rq):
@@ -400,6 +422,8 @@ class BatchScheduler:
             kw.update(rq.constraint.kwargs())
         if rq.stops is not None:
             kw.update(stops=rq.stops, include_stop_in_output=rq.include_stop)
+        if rq.penalties is not None:
+            kw.update(_penalty_kwargs(rq.penalties))
         if self.per_request_params:
             kw["params"] = rq.params
         else:
@@ -549,6 +573,8 @@ class BatchScheduler:
         self.exclusive_runs += 1
         ckw = {} if rq.constraint is None else rq.constraint.kwargs()
         ckw.update(rq.stop_args)  # (a decode with stops does not stream either)
+        if rq.penalties is not None:  # (nor does a penalised one)
+            ckw.update(_penalty_kwargs(rq.penalties))
         try:
             if rq.logprobs is None and not ckw:
                 out = self.engine.decode(self.tokenizer, rq.prompt, rq.images, rq.vision, rq.params, rq.on_token)

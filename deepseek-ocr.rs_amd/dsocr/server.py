@@ -253,6 +253,24 @@ def parse_stops(req: dict, tokenizer=None, vocab: Optional[int] = None) -> Optio
     return {"stop": stop, "stop_token_ids": ids, "include_stop_in_output": bool(include)}
 
 
+PENALTY_BOUND = 2.0  # OpenAI's range of `frequency_penalty` / `presence_penalty`
+
+
+def parse_penalties(req: dict) -> Optional[dict]:
+    """OpenAI `frequency_penalty` / `presence_penalty` (numbers in [-2, 2]) and the extension field `min_p` (a number
+    in [0, 1]) of a request body, as the keywords ``decode`` / ``submit`` take; None when the body asks for nothing
+    (absent, null or zero fields).  400: anything else in those fields."""
+    from .penalties import PenaltyError, make_penalties
+    try:
+        pn = make_penalties(req.get("frequency_penalty"), req.get("presence_penalty"), req.get("min_p"),
+                            bound=PENALTY_BOUND)
+    except PenaltyError as e:
+        raise ApiError.bad_request(f"penalties: {e}")
+    if pn is None:
+        return None
+    return {"frequency_penalty": pn.frequency, "presence_penalty": pn.presence, "min_p": pn.min_p}
+
+
 def _held_back(on_token, stops: dict, tokenizer, vocab):
     """``on_token`` behind a ``dsocr.stops.TokenHoldback``: it is called once per token that no later hit can remove."""
     from .stops import TokenHoldback, merge_stops
@@ -311,7 +329,7 @@ def _now() -> int:
 def generate_blocking(state: ServerState, prompt: str, images: list, params: DecodeParameters, on_token=None,
                       logprobs: Optional[int] = None, constraint: Optional[dict] = None, stops: Optional[dict] = None):
     """generation.rs:75-163.  ``stops``: the keywords of parse_stops (merged into ``constraint``'s: both are keywords
-    of ``decode`` / ``submit``, and a decode with either does not stream).  ``constraint``: the keywords of parse_token_constraint.  With a scheduler the request joins the running decode session (its error reaches only
+    of ``decode`` / ``submit``, and a decode with either does not stream).  ``constraint``: the keywords of parse_token_constraint and of parse_penalties.  With a scheduler the request joins the running decode session (its error reaches only
     its own future); without one it decodes alone behind the lock."""
     def classify(e):
         msg = str(e)
@@ -537,6 +555,9 @@ def handle_generation(state: ServerState, req: dict, kind: str):
     logprobs = parse_logprobs(req) if kind == "chat" else None  # (/v1/responses has no log-probabilities)
     constraint = parse_token_constraint(req, getattr(state.engine, "vocab", None))
     stops = parse_stops(req, state.tokenizer, getattr(state.engine, "vocab", None))
+    penalties = parse_penalties(req)
+    if penalties:  # keywords of decode / submit beside the constraint's; a penalised decode does not stream either
+        constraint = dict(constraint or {}, **penalties)
     if stream:
         c = StreamController(state.tokenizer, kind, model)
         if stops:
@@ -644,6 +665,10 @@ def add_scheduler_args(p):
                    help="with --slots: open the decode session with a stop table per slot, so requests with `stop` / "
                         "`stop_token_ids` join the running batch (the device ends such a page on the step that "
                         "completes a stop) instead of waiting for it to drain; off by default")
+    p.add_argument("--penalties", action="store_true",
+                   help="with --slots: open the decode session with a penalty record per slot, so requests with "
+                        "`frequency_penalty` / `presence_penalty` / `min_p` join the running batch (a burst with such "
+                        "a request runs the exact lm_head) instead of waiting for it to drain; off by default")
     p.add_argument("--prefix-cache", type=int, default=0,
                    help="with --slots: keep the K/V rows of up to N pages' image prefixes (LRU), so a later prompt on "
                         "the same image under the same vision settings skips vision and the prefill of those rows; "
@@ -656,7 +681,7 @@ def add_scheduler_args(p):
 
 def make_scheduler(state: ServerState, slots: int, max_context: int, per_request_params: bool = False,
                    logprobs: bool = False, prefix_cache: int = 0, admit_chunk: int = 0, logit_bias: bool = False,
-                   stops: bool = False):
+                   stops: bool = False, penalties: bool = False):
     """The state's scheduler for --slots N (None for 0: requests take the lock path).  per_request_params: the
     DecodeParameters merge_decode builds from a request body are admitted into the session as that request's own.
     prefix_cache: --prefix-cache N (ValueError without --slots: the entries live in the decode session)."""
@@ -668,13 +693,15 @@ def make_scheduler(state: ServerState, slots: int, max_context: int, per_request
         raise ValueError("--logit-bias needs --slots (the bias rows live in the decode session)")
     if stops and not slots:
         raise ValueError("--stops needs --slots (the stop tables live in the decode session)")
+    if penalties and not slots:
+        raise ValueError("--penalties needs --slots (the penalty records live in the decode session)")
     if not slots:
         return None
     from .scheduler import BatchScheduler
     return BatchScheduler(state.engine, state.tokenizer, slots, max_context, state.defaults, state.vision,
                           per_request_params=per_request_params, logprobs=logprobs, prefix_cache=prefix_cache,
                           admit_chunk=admit_chunk, **({"logit_bias": True} if logit_bias else {}),
-                          **({"stops": True} if stops else {}))
+                          **({"stops": True} if stops else {}), **({"penalties": True} if penalties else {}))
 
 
 def main(argv=None) -> int:
@@ -700,6 +727,8 @@ def main(argv=None) -> int:
         p.error("--logit-bias needs --slots (the bias rows live in the decode session)")
     if args.stops and not args.slots:
         p.error("--stops needs --slots (the stop tables live in the decode session)")
+    if args.penalties and not args.slots:
+        p.error("--penalties needs --slots (the penalty records live in the decode session)")
     config = model_config(args)  # --model deepseek-ocr | deepseek-ocr-2: the bundled config and vision defaults
     engine = load_model(ModelLoadArgs(config_path=config, weights_path=args.weights, snapshot_path=args.snapshot,
                                       snapshot_packed=getattr(args, "snapshot_packed", None),
@@ -708,7 +737,8 @@ def main(argv=None) -> int:
     state = ServerState(engine, load_tokenizer(args.tokenizer, _vocab_of(config)), args.model,
                         vision_settings(args), decode_params(args))
     state.scheduler = make_scheduler(state, args.slots, args.max_context, args.per_request_params, args.logprobs,
-                                     args.prefix_cache, args.admit_chunk, args.logit_bias, args.stops)
+                                     args.prefix_cache, args.admit_chunk, args.logit_bias, args.stops,
+                                     args.penalties)
     import uvicorn
     uvicorn.run(create_app(state), host=args.host, port=args.port)
     return 0

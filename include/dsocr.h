@@ -325,6 +325,35 @@ dsocr_status dsocr_session_stage_stop(dsocr_engine* e, const dsocr_stop_set* sto
 dsocr_status dsocr_session_stop_hit(dsocr_engine* e, int slot, dsocr_stop_hit* out);
 dsocr_status dsocr_stop_launches(const dsocr_engine* e, size_t* n);
 
+/* ---- frequency / presence penalties and min-p, per request (no reference counterpart: the
+ * reference has the multiplicative repetition_penalty only).  With c[t] the number of times id t occurs in the page's
+ * GENERATED tokens so far (the prefill's own selection included; prompt and image slots do not count), every step's
+ * logits become l[t] - (frequency * c[t] + presence) where c[t] > 0, in f32 with each operation rounded, after the
+ * logit bias, the log-probability partials and the repetition penalty, before the n-gram ban and the selection.
+ * min_p acts on sampled rows only: a candidate stays iff logit / T - max(logit / T) >= log(min_p), the maximum taken
+ * over the finite logits the n-gram ban leaves; top-k, top-p and the draw then run on the survivors.  Off:
+ * frequency == 0, presence == 0 and min_p <= 0 (a NULL record too).  A call or burst in which a record is on runs
+ * the exact lm_head and selectors.  DSOCR_EINVAL, before any device state changes: a non-finite frequency or
+ * presence; min_p NaN, below 0 or above 1; a record that is on with the logits trace, use_cache = 0 or DSOCR_PERSIST.
+ *   dsocr_penalties_check: the checks alone; needs no engine and no device.
+ *   dsocr_generate_penalties: dsocr_generate_stop with one record per request (pen [n], entries may be NULL; pen
+ *   itself NULL: none).
+ *   dsocr_session_stage_penalties: stages one record (copied) for the NEXT admission call on this engine's session,
+ *   whichever form it takes, exactly like dsocr_session_stage_stop.  DSOCR_EINVAL, nothing staged, when the record
+ *   fails a check, no session is open, or it is on and the session was opened without DSOCR_SESSION_PENALTIES. */
+typedef struct {
+    float frequency;
+    float presence;
+    double min_p;
+} dsocr_penalties;
+dsocr_status dsocr_penalties_check(const dsocr_penalties* pen);
+dsocr_status dsocr_generate_penalties(dsocr_engine* e, size_t n, const dsocr_request* reqs,
+                                      const dsocr_decode_params* params, dsocr_result* results,
+                                      const dsocr_penalties* const* pen, const dsocr_stop_set* const* stops,
+                                      dsocr_stop_hit* hits, const dsocr_logit_bias* const* bias, size_t top_k,
+                                      dsocr_logprobs* lp);
+dsocr_status dsocr_session_stage_penalties(dsocr_engine* e, const dsocr_penalties* pen);
+
 /* ---- decode sessions: pages join and leave a running batch between decode steps (no reference counterpart: the
  * reference server decodes one request at a time behind its Mutex, server/src/state.rs:22).  A session is a
  * long-lived batch of `slots` (1..8) pages with max_context rows each (a page needs prompt_len + max_new_tokens
@@ -381,6 +410,11 @@ dsocr_status dsocr_session_open(dsocr_engine* e, size_t slots, size_t max_contex
  * (dsocr_session_stage_stop).  The step graph of a burst contains the match launch iff an active slot carries a stop
  * set; the head is whichever runs without it.  A stop that fires in the middle of a burst leaves out_len at the match. */
 #define DSOCR_SESSION_STOP 8u
+/* DSOCR_SESSION_PENALTIES (combines with the four flags above): every slot keeps a 16-byte penalty record (reserved
+ * at open, off until an admission brings one: dsocr_session_stage_penalties), and the penalty launch is part of the
+ * exact step.  A burst runs the exact head iff an active slot carries a record that is on; the record follows its
+ * page through the compaction of dsocr_session_retire and ends with the page. */
+#define DSOCR_SESSION_PENALTIES 16u
 dsocr_status dsocr_session_open_ex(dsocr_engine* e, size_t slots, size_t max_context, const dsocr_decode_params* params,
                                    uint32_t flags);
 /* Every check (free slot, context need, prompt/image mismatch, token ids, page variant) happens before any device
@@ -872,6 +906,16 @@ dsocr_status dsocr_k_logit_bias(int B, int V, int ld, int offset, float* logits,
 dsocr_status dsocr_k_stop_match(int B, int steps, int out_cap, const int* n_seq, const int* lens, const int64_t* ids,
                                 const int* tokens, const uint8_t* emit, int* out, int* out_len, int* done, int* seen,
                                 int* hit, int* done_steps, int* seen_steps, int* hit_steps, int* out_len_steps);
+/* launch_dec_out_penalty once on host rows: logits [B][ld] (in / out), out_ids [B][out_cap], out_len [B] and one
+ * record per row (never NULL; min_p is not read by this kernel). */
+dsocr_status dsocr_k_out_penalty(int B, int V, int ld, float* logits, const int* out_ids, int out_cap,
+                                 const int* out_len, const dsocr_penalties* pen);
+/* dsocr_k_sample_stoch with a per-row ln_min_p (host array [B]; -inf: no filter): the sampling selector and the
+ * final kernel `draws` times on the same logits, the RNG state carried over (out_tok [draws][B]).  The other
+ * pointers are device pointers, as there. */
+dsocr_status dsocr_k_sample_stoch_min_p(int B, int V, float* logits, const int* ctx, int ctx_cap, const int* ctx_len,
+                                        int ngram, float rep_penalty, double temperature, size_t top_k, double top_p,
+                                        const double* ln_min_p, uint64_t seed, int draws, int* out_tok);
 dsocr_status dsocr_k_logprobs_penalty(int B, int V, int K, const float* logits, int ld, const int* tok, const uint8_t* emit,
                                       const int* ctx, int ctx_cap, const int* ctx_len, float penalty, float* lp,
                                       int64_t* top_id, float* top_lp);
