@@ -26,7 +26,8 @@ ARCH = "gfx950"
 KERNELS = ["gemm", "gemm_bf16", "moe", "norm", "attention", "misc", "decode_gemv", "decode_attn", "decode_route",
            "decode_moe", "decode_sample", "lmhead", "dsq", "preprocess", "sampling", "dots_ops", "attention_bf16",
            "decode_mm", "decode_persist", "decode_q", "attention_prefix", "ocr2_ops", "session",
-           "decode_logprob", "attention_past", "decode_bias", "decode_stop", "decode_penalty"]
+           "decode_logprob", "attention_past", "decode_bias", "decode_stop", "decode_penalty",
+           "decode_ngram_window"]
 HOST = ["engine", "dots", "capi"]
 
 

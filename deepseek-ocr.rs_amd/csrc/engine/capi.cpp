@@ -25,6 +25,7 @@ struct dsocr_engine {
     dsocr::LogitBias staged_bias;  // dsocr_session_stage_logit_bias: consumed by the next admission call
     dsocr::StopSet staged_stop;    // dsocr_session_stage_stop: the same
     dsocr::Penalties staged_pen;   // dsocr_session_stage_penalties: the same
+    dsocr::NgramWindow staged_ngw; // dsocr_session_stage_ngram_window: the same
 };
 struct dsocr_page_pixels {
     dsocr::PagePixels px;
@@ -193,9 +194,23 @@ dsocr::Penalties to_penalties(const dsocr_penalties* pn) {
     return p;
 }
 
-// a session admission's request: the staged constraint, stop set and penalties move into it (consumed whatever the
-// admission does)
+// the windowed n-gram ban as the engine takes it, checked against `vocab` (NULL: off)
+dsocr::NgramWindow to_ngram_window(const dsocr_ngram_window* nw, size_t vocab) {
+    dsocr::NgramWindow w;
+    if (!nw) return w;
+    if (nw->n_whitelist && !nw->whitelist) throw std::runtime_error("EINVAL: n-gram window: NULL whitelist");
+    if (nw->n_whitelist > (size_t)vocab) throw std::runtime_error("EINVAL: n-gram window: more whitelist ids than the vocabulary has");
+    w.g = nw->ngram_size; w.w = nw->window;
+    w.whitelist.assign(nw->whitelist, nw->whitelist + nw->n_whitelist);
+    dsocr::validate_ngram_window(w, (int)vocab);
+    return w;
+}
+
+// a session admission's request: the staged constraint, stop set, penalties and windowed ban move into it (consumed
+// whatever the admission does)
 dsocr::GenRequest to_admission(dsocr_engine* e, const dsocr_request& r) {
+    dsocr::NgramWindow nw = std::move(e->staged_ngw);
+    e->staged_ngw = dsocr::NgramWindow();
     const dsocr::Penalties pn = e->staged_pen;
     e->staged_pen = dsocr::Penalties();
     dsocr::LogitBias b = std::move(e->staged_bias);
@@ -206,13 +221,14 @@ dsocr::GenRequest to_admission(dsocr_engine* e, const dsocr_request& r) {
     g.bias = std::move(b);
     g.stops = std::move(st);
     g.pen = pn;
+    g.ngw = std::move(nw);
     return g;
 }
 
 // the DSOCR_SESSION_* feature bits as the engine takes them, and back (DSOCR_SESSION_ADMIT_PENDING is state, not one of them)
 dsocr::Engine::SessionFeatures to_features(uint32_t flags) {
     if (flags & ~(uint32_t)(DSOCR_SESSION_PER_REQUEST | DSOCR_SESSION_LOGPROBS | DSOCR_SESSION_LOGIT_BIAS | DSOCR_SESSION_STOP |
-                             DSOCR_SESSION_PENALTIES))
+                             DSOCR_SESSION_PENALTIES | DSOCR_SESSION_NGRAM_WINDOW))
         throw std::runtime_error("EINVAL: unknown session flags");
     dsocr::Engine::SessionFeatures f;
     f.per_request = (flags & DSOCR_SESSION_PER_REQUEST) != 0;
@@ -220,12 +236,13 @@ dsocr::Engine::SessionFeatures to_features(uint32_t flags) {
     f.logit_bias = (flags & DSOCR_SESSION_LOGIT_BIAS) != 0;
     f.stops = (flags & DSOCR_SESSION_STOP) != 0;
     f.penalties = (flags & DSOCR_SESSION_PENALTIES) != 0;
+    f.ngram_window = (flags & DSOCR_SESSION_NGRAM_WINDOW) != 0;
     return f;
 }
 uint32_t feature_flags(const dsocr::Engine::SessionFeatures& f) {
     return (f.per_request ? DSOCR_SESSION_PER_REQUEST : 0u) | (f.logprobs ? DSOCR_SESSION_LOGPROBS : 0u) |
            (f.logit_bias ? DSOCR_SESSION_LOGIT_BIAS : 0u) | (f.stops ? DSOCR_SESSION_STOP : 0u) |
-           (f.penalties ? DSOCR_SESSION_PENALTIES : 0u);
+           (f.penalties ? DSOCR_SESSION_PENALTIES : 0u) | (f.ngram_window ? DSOCR_SESSION_NGRAM_WINDOW : 0u);
 }
 
 // ---- generate: the exported forms marshal through generate_page (one page, the stream callback) or generate_pages
@@ -279,6 +296,7 @@ struct GenExtras {
     dsocr_stop_hit* hits = nullptr;                 // ... and where every request's hit goes
     const dsocr_logit_bias* const* bias = nullptr;  // one constraint per request (the list or an entry may be NULL)
     const dsocr_penalties* const* pen = nullptr;    // one penalty record per request (the same)
+    const dsocr_ngram_window* const* ngw = nullptr; // one windowed n-gram ban per request (the same)
     bool lp_on = false;  // per-token log-probabilities with top_k alternatives into lp[n] (NULL only with n == 0)
     size_t top_k = 0;
     dsocr_logprobs* lp = nullptr;
@@ -312,6 +330,7 @@ void generate_pages(dsocr_engine* e, size_t n, const dsocr_request* reqs, const 
         if (x.bias) rq.back().bias = to_bias(x.bias[i], vocab);
         if (x.stops) rq.back().stops = to_stops(x.stops[i], vocab);
         if (x.pen) rq.back().pen = to_penalties(x.pen[i]);
+        if (x.ngw) rq.back().ngw = to_ngram_window(x.ngw[i], vocab);
     }
     dsocr::GenParams g = to_params(params);
     g.trace = x.logits_out;
@@ -608,6 +627,46 @@ dsocr_status dsocr_generate_penalties(dsocr_engine* e, size_t n, const dsocr_req
         x.top_k = top_k;
         x.lp = lp;
         generate_pages(e, n, reqs, params, results, x);
+    });
+}
+
+dsocr_status dsocr_generate_ngram_window(dsocr_engine* e, size_t n, const dsocr_request* reqs,
+                                         const dsocr_decode_params* params, dsocr_result* results,
+                                         const dsocr_ngram_window* const* ngw, const dsocr_penalties* const* pen,
+                                         const dsocr_stop_set* const* stops, dsocr_stop_hit* hits,
+                                         const dsocr_logit_bias* const* bias, size_t top_k, dsocr_logprobs* lp) {
+    return guarded([&] {
+        if (!params) throw std::runtime_error("EINVAL: NULL argument");
+        GenExtras x;
+        x.ngw = ngw;
+        x.pen = pen;
+        x.stops = stops;
+        x.hits = hits;
+        x.bias = bias;
+        x.lp_on = lp != nullptr;  // (top_k without lp is refused)
+        x.top_k = top_k;
+        x.lp = lp;
+        generate_pages(e, n, reqs, params, results, x);
+    });
+}
+
+dsocr_status dsocr_ngram_window_check(const dsocr_ngram_window* ngw, size_t vocab) {
+    return guarded([&] {
+        if (vocab == 0 || vocab > (size_t)INT32_MAX) throw std::runtime_error("EINVAL: bad vocabulary size");
+        (void)to_ngram_window(ngw, vocab);
+    });
+}
+
+dsocr_status dsocr_session_stage_ngram_window(dsocr_engine* e, const dsocr_ngram_window* ngw) {
+    return guarded([&] {
+        if (!e) throw std::runtime_error("EINVAL: NULL argument");
+        e->staged_ngw = dsocr::NgramWindow();
+        dsocr::Engine::SessionInfo si;
+        if (!e->impl->session_info(&si)) throw std::runtime_error("EINVAL: no decode session is open on this engine");
+        dsocr::NgramWindow w = to_ngram_window(ngw, (size_t)e->impl->cfg().lang.vocab);
+        if (w.active() && !si.feat.ngram_window)
+            throw std::runtime_error("EINVAL: this session was opened without DSOCR_SESSION_NGRAM_WINDOW");
+        e->staged_ngw = std::move(w);
     });
 }
 
@@ -2461,6 +2520,33 @@ dsocr_status dsocr_k_out_penalty(int B, int V, int ld, float* logits, const int*
         a.rec = (const dsocr::PenaltyRec*)d_rec.get();
         dsocr::launch_dec_out_penalty(a, nullptr);
         check_hip(hipDeviceSynchronize(), "output penalty");
+        check_hip(hipMemcpy(logits, d_logits.get(), nl * 4, hipMemcpyDeviceToHost), "hipMemcpy D2H");
+    });
+}
+
+dsocr_status dsocr_k_ngram_window(int B, int V, int ld, float* logits, const int* ctx, int ctx_cap, const int* ctx_len,
+                                  const dsocr_ngram_window* const* recs, int plain) {
+    return guarded([&] {
+        if (B <= 0 || V <= 0 || ld < V || ctx_cap <= 0 || !logits || !ctx || !ctx_len || !recs)
+            throw std::runtime_error("EINVAL: bad n-gram window hook arguments");
+        const size_t nb = (size_t)B, nl = nb * (size_t)ld, cap = (size_t)ctx_cap;
+        std::vector<dsocr::NgramWindowRec> rec(nb);
+        for (size_t b = 0; b < nb; ++b) {
+            if (ctx_len[b] < 0 || ctx_len[b] > ctx_cap) throw std::runtime_error("EINVAL: ctx_len outside 0..ctx_cap");
+            rec[b] = to_ngram_window(recs[b], (size_t)V).rec();
+        }
+        dsocr::DeviceBuffer d_logits(nl * 4), d_ctx(nb * cap * 4), d_len(nb * 4), d_rec(nb * sizeof(dsocr::NgramWindowRec));
+        check_hip(hipMemcpy(d_logits.get(), logits, nl * 4, hipMemcpyHostToDevice), "hipMemcpy H2D");
+        check_hip(hipMemcpy(d_ctx.get(), ctx, nb * cap * 4, hipMemcpyHostToDevice), "hipMemcpy H2D");
+        check_hip(hipMemcpy(d_len.get(), ctx_len, nb * 4, hipMemcpyHostToDevice), "hipMemcpy H2D");
+        check_hip(hipMemcpy(d_rec.get(), rec.data(), nb * sizeof(dsocr::NgramWindowRec), hipMemcpyHostToDevice), "hipMemcpy H2D");
+        dsocr::DecNgramWindowArgs a;
+        a.logits = (float*)d_logits.get(); a.B = B; a.V = V; a.ld = ld;
+        a.ctx = (const int*)d_ctx.get(); a.ctx_cap = ctx_cap; a.ctx_len = (const int*)d_len.get();
+        a.rec = (const dsocr::NgramWindowRec*)d_rec.get();
+        a.plain = plain;
+        dsocr::launch_dec_ngram_window(a, nullptr);
+        check_hip(hipDeviceSynchronize(), "n-gram window");
         check_hip(hipMemcpy(logits, d_logits.get(), nl * 4, hipMemcpyDeviceToHost), "hipMemcpy D2H");
     });
 }

@@ -175,6 +175,7 @@ struct Engine::Session {
         bool stopped = false;  // the slot's request carried a stop set (rows_.stop_n[slot] != 0)
         bool biased = false;  // the slot's device flag (rows_.bias_on): its request carried a constraint
         bool penalised = false;  // the slot's device record (rows_.pen) is on
+        bool windowed = false;  // the slot's windowed-ban record (rows_.ngw) is on
         size_t max_new = 0;
         int kv_pos = 0;    // the device kv_pos of the slot: prompt + steps replayed since its admission
         int reported = 0;  // tokens the polls have handed out
@@ -198,8 +199,10 @@ struct Engine::Session {
     std::vector<Slot> slot;
     std::shared_ptr<PendingAdmit> pending;  // a chunked admission in flight, staged in slot S - 1 (session_admit_begin)
     int next_ticket = 1;
-    // the step for n active pages under the [exact, screened] head, [without, with] the stop match launch, captured on first use
-    HipGraphExec graph[9][2][2];
+    // the step for n active pages under the [exact, screened] head, [without, with] the stop match launch,
+    // [without, with] the windowed-ban launch, captured on first use
+    HipGraphExec graph[9][2][2][2];
+    bool ban_stale = false;  // the last burst ran its selections at ngram 0 (a windowed burst, fixed parameters)
     size_t head_steps[2] = {0, 0};  // steps replayed under the [exact, screened] head
     PinnedBuffer<int> pin;  // poll: [done | output length] x S, then the decode error flag
     size_t steps = 0;
@@ -1742,7 +1745,8 @@ bool Engine::screen_applies(int B, float rep_penalty) const {
 // final norm + lm_head + greedy selection + step bookkeeping for the B decode rows in s_x
 // screened: the int8 lm_head + screened final kernel (sa.ban_out holds the ban list the last step left, whichever
 // head wrote it); else the exact lm_head, the penalty and the selection kernels
-void Engine::decode_head(int B, DecSampleArgs& sa, const SampleArgs& pen, bool screened, const DecLpArgs* lp, bool stops) {
+void Engine::decode_head(int B, DecSampleArgs& sa, const SampleArgs& pen, bool screened, const DecLpArgs* lp, bool stops,
+                         int window) {
     const LangConfig& L = cfg_.lang;
     hipStream_t st = stream_;
     const int H = L.hidden;
@@ -1750,6 +1754,7 @@ void Engine::decode_head(int B, DecSampleArgs& sa, const SampleArgs& pen, bool s
     if (screened && lp) throw std::runtime_error("EINTERNAL: log-probabilities need the exact head");
     if (screened && rows_.bias && !sess_) throw std::runtime_error("EINTERNAL: a logit bias needs the exact head");
     if (screened && rows_.pen && !sess_) throw std::runtime_error("EINTERNAL: penalties need the exact head");
+    if (screened && window >= 0) throw std::runtime_error("EINTERNAL: a windowed n-gram ban needs the exact head");
     if (screened) {
         // screened selection: int8 lm_head intervals + running threshold, exact rescoring of the
         // few kept rows — the exact path's token from half the lm_head bytes
@@ -1781,7 +1786,14 @@ void Engine::decode_head(int B, DecSampleArgs& sa, const SampleArgs& pen, bool s
     if (lp) launch_dec_lp_partial(*lp, st);
     launch_rep_penalty(pen, st);
     if (rows_.pen) launch_dec_out_penalty(penalty_args(sa, 0), st);  // frequency / presence, per row
-    launch_dec_sample(sa, st);
+    if (window >= 0) {  // every row's ban in the window launch, the selection without one
+        launch_dec_ngram_window(ngram_window_args(sa, 0, window), st);
+        DecSampleArgs s0 = sa;
+        s0.ngram = 0;  // (per-request rows: a windowed row's RowParams carry ngram 0, the others keep their own ban)
+        launch_dec_sample(s0, st);
+    } else {
+        launch_dec_sample(sa, st);
+    }
     if (stops) stop_match(sa, 0);
     if (lp) launch_dec_lp_final(*lp, st);
 }
@@ -1891,6 +1903,11 @@ void Engine::reserve_decode_rows(const DecodeRowsSpec& spec) {
         const std::vector<PenaltyRec> off((size_t)S);
         upload_to(r.pen, "s_penstage", off);
     }
+    if (spec.ngram_window) {  // the same
+        r.ngw = reinterpret_cast<NgramWindowRec*>(ws("s_ngw", sizeof(NgramWindowRec) * S));
+        const std::vector<NgramWindowRec> off((size_t)S);
+        upload_to(r.ngw, "s_ngwstage", off);
+    }
 }
 
 // The fused one-page launch takes q / k / v by polling its hand-off row, and the attention merge polls its records:
@@ -1971,6 +1988,47 @@ PenaltyRec Penalties::rec() const {
     r.frequency = frequency; r.presence = presence;
     r.ln_min_p = min_p > 0.0 ? std::log(min_p) : -INFINITY;
     return r;
+}
+
+DecNgramWindowArgs Engine::ngram_window_args(const DecSampleArgs& sa, int row0, int plain) {
+    DecNgramWindowArgs a;
+    a.logits = const_cast<float*>(sa.logits); a.B = sa.B; a.V = sa.V; a.ld = sa.ld;
+    a.ctx = sa.ctx; a.ctx_cap = sa.ctx_cap; a.ctx_len = sa.ctx_len;
+    a.rec = rows_.ngw + row0;
+    a.plain = plain;
+    return a;
+}
+
+NgramWindowRec NgramWindow::rec() const {
+    NgramWindowRec r;
+    if (!active()) return r;
+    r.g = g; r.w = w;
+    for (int t : whitelist) {
+        bool seen = false;
+        for (int q = 0; q < r.n_white; ++q) seen = seen || r.white[q] == t;
+        if (!seen && r.n_white < NGRAM_MAX_WHITELIST) r.white[r.n_white++] = t;
+    }
+    return r;
+}
+
+void validate_ngram_window(const NgramWindow& nw, int vocab) {
+    if (nw.g >= 2 && nw.w < 1) throw std::runtime_error("EINVAL: n-gram window: window must be at least 1");
+    std::vector<int> uniq;
+    for (int t : nw.whitelist) {
+        if (t < 0 || t >= vocab) throw std::runtime_error("EINVAL: n-gram window: whitelist id outside the vocabulary");
+        if (std::find(uniq.begin(), uniq.end(), t) == uniq.end()) uniq.push_back(t);
+    }
+    if (uniq.size() > (size_t)NGRAM_MAX_WHITELIST)
+        throw std::runtime_error("EINVAL: n-gram window: more than " + std::to_string(NGRAM_MAX_WHITELIST) + " whitelist ids");
+}
+
+// (one record per row in the staging buffer, as for the penalties)
+void Engine::write_ngram_windows(const NgramWindow* const* nw, int row0, int n) {
+    const DecodeRows& r = rows_;
+    if (!r.ngw) throw std::runtime_error("EINTERNAL: no n-gram window records are reserved");
+    NgramWindowRec* h = (NgramWindowRec*)pinned("s_ngwstage", sizeof(NgramWindowRec) * (size_t)r.S);
+    for (int i = 0; i < n; ++i) h[row0 + i] = nw[i] ? nw[i]->rec() : NgramWindowRec();
+    HIP_CHECK(hipMemcpyAsync(r.ngw + row0, h + row0, sizeof(NgramWindowRec) * (size_t)n, hipMemcpyHostToDevice, stream_));
 }
 
 void validate_penalties(const Penalties& pn) {
@@ -2168,6 +2226,19 @@ std::vector<std::vector<int64_t>> Engine::generate(const std::vector<GenRequest>
         const char* e = getenv("DSOCR_PERSIST");
         if (e && atoi(e) != 0)
             throw std::runtime_error("EINVAL: penalties do not combine with the persistent decode step (DSOCR_PERSIST)");
+    }
+    // a windowed n-gram ban: the same
+    bool any_ngw = false;
+    for (const GenRequest& rq : reqs) {
+        validate_ngram_window(rq.ngw, cfg_.lang.vocab);
+        any_ngw = any_ngw || rq.ngw.active();
+    }
+    if (any_ngw && (!p.use_cache || p.trace))
+        throw std::runtime_error("EINVAL: a windowed n-gram ban needs the K/V cache (use_cache = 1) and no logits trace");
+    if (any_ngw) {
+        const char* e = getenv("DSOCR_PERSIST");
+        if (e && atoi(e) != 0)
+            throw std::runtime_error("EINVAL: a windowed n-gram ban does not combine with the persistent decode step (DSOCR_PERSIST)");
     }
     if (reqs.empty() || p.max_new == 0) return std::vector<std::vector<int64_t>>(reqs.size());
     ensure_small(std::max((int)reqs.size(), 64));
@@ -2372,7 +2443,10 @@ void Engine::reset_decode_state(GenState& g) {
         if (rq.bias.active()) { spec.bias = true; spec.bias_stage += rq.bias.ids.size(); }
     // a penalised page: the exact head as well, with one record per page
     for (const GenRequest& rq : g.reqs) spec.penalties = spec.penalties || rq.pen.active();
-    spec.ban = !p.do_sample && !p.trace && p.lp_k < 0 && !spec.bias && !spec.penalties && screen_applies(B, p.rep_penalty);
+    // a page with a windowed n-gram ban: the exact head too, with one record per page
+    for (const GenRequest& rq : g.reqs) spec.ngram_window = spec.ngram_window || rq.ngw.active();
+    spec.ban = !p.do_sample && !p.trace && p.lp_k < 0 && !spec.bias && !spec.penalties && !spec.ngram_window &&
+               screen_applies(B, p.rep_penalty);
     // (the side row: dec_lp_final takes an emitted token's raw logit from it wherever a penalty may have rewritten
     // logits[tok]: the repetition penalty at the context ids, the frequency / presence penalty at the generated ones,
     // which the context row holds as well)
@@ -2537,6 +2611,13 @@ void Engine::init_sampling(GenState& g) {
         write_penalties(pn.data(), 0, B);
         launch_dec_out_penalty(penalty_args(sa, 0), st);
     }
+    if (r.ngw) {  // every page's record, then every page's ban on the prefill's logits; the selection runs without one
+        std::vector<const NgramWindow*> nw(B);
+        for (int b = 0; b < B; ++b) nw[b] = &g.reqs[b].ngw;
+        write_ngram_windows(nw.data(), 0, B);
+        launch_dec_ngram_window(ngram_window_args(sa, 0, p.ngram), st);
+        sa.ngram = 0;
+    }
     std::vector<int> pm1(B), lm1(B);
     for (int b = 0; b < B; ++b) { pm1[b] = g.kvpos[b] - 1; lm1[b] = g.kvlen[b] - 1; }
     HIP_CHECK(hipMemcpyAsync(r.kv_pos, pm1.data(), B * 4, hipMemcpyHostToDevice, st));
@@ -2680,7 +2761,8 @@ void Engine::step_body(GenState& g) {
     sample_args(g.B, 0, g.p, false, sa, pen);
     const DecLpArgs lp = g.p.lp_k >= 0 ? lp_args(sa, 0) : DecLpArgs();
     decode_step(g.B, rows_.Lcap);
-    decode_head(g.B, sa, pen, rows_.ban != nullptr, g.p.lp_k >= 0 ? &lp : nullptr, rows_.stop_tab != nullptr);
+    decode_head(g.B, sa, pen, rows_.ban != nullptr, g.p.lp_k >= 0 ? &lp : nullptr, rows_.stop_tab != nullptr,
+                rows_.ngw ? g.p.ngram : -1);
     // chain spans: the step's one fold, after the head (the step counter has advanced: record at count - 1)
     if (chain_active_)
         launch_span_chain_fold(span_chain_, cfg_.lang.layers * SPAN_KINDS_CHAIN, span_chain_rec_, span_step_, span_cap_,
@@ -2870,6 +2952,7 @@ void Engine::session_open(int S, int max_context, const GenParams& p, const Sess
     }
     spec.stops = feat.stops;  // every slot's table, and one admission's list at a time
     spec.penalties = feat.penalties;  // every slot's record
+    spec.ngram_window = feat.ngram_window;  // the same
     if (feat.logprobs) {  // (the raw logits at the context ids too where a penalty can apply)
         spec.lp_k = LP_MAX_TOP;
         spec.lp_side = feat.per_request || rep_penalty_active(p.rep_penalty) || feat.penalties;
@@ -2945,6 +3028,9 @@ void Engine::session_admit_checks(const Session& s, const GenRequest& rq, const 
     validate_penalties(rq.pen);
     if (rq.pen.active() && !s.feat.penalties)
         throw std::runtime_error("EINVAL: this session was opened without DSOCR_SESSION_PENALTIES");
+    validate_ngram_window(rq.ngw, V);
+    if (rq.ngw.active() && !s.feat.ngram_window)
+        throw std::runtime_error("EINVAL: this session was opened without DSOCR_SESSION_NGRAM_WINDOW");
     if (s.pending) throw std::runtime_error("EINVAL: a chunked admission is pending (advance it to the end or cancel it)");
     if (s.n >= s.S) throw std::runtime_error("EINVAL: every session slot is in use (retire one first)");
     const size_t P = rq.ids.size();
@@ -2995,8 +3081,12 @@ int Engine::session_admit(const GenRequest& rq, const GenParams& rp) {
 
 // the slot's rows in one launch from one staged buffer (the selection kernel advances the KV position, so it starts
 // one behind: init_sampling), then the first selection on the logits the prefill left in the slot's s_logits row
-int Engine::session_admit_tail(Session& s, const GenRequest& rq, const GenParams& rp, const RowParams& row, int at,
+int Engine::session_admit_tail(Session& s, const GenRequest& rq, const GenParams& rp, const RowParams& row_in, int at,
                                bool finish) {
+    // a windowed ban replaces the page's plain one: its RowParams carry ngram 0 from here on
+    RowParams row = row_in;
+    const bool windowed = rq.ngw.active();
+    if (windowed) row.ngram = 0;
     const size_t max_new = rp.max_new, P = rq.ids.size();
     const bool seed_set = rp.seed_set;
     uint64_t seed = rp.seed;
@@ -3043,6 +3133,14 @@ int Engine::session_admit_tail(Session& s, const GenRequest& rq, const GenParams
         write_penalties(&pn, slot, 1);
         launch_dec_out_penalty(penalty_args(sa, slot), st);
     }
+    if (s.feat.ngram_window) {  // the slot's record (none: an off record); on: its ban on the prefill's logits
+        const NgramWindow* nw = &rq.ngw;
+        write_ngram_windows(&nw, slot, 1);
+        if (windowed) {
+            launch_dec_ngram_window(ngram_window_args(sa, slot, 0), st);
+            sa.ngram = 0;
+        }
+    }
     launch_dec_sample(sa, st);  // the first token, its embedding into the slot's s_x row, the ban list
     if (s.feat.stops) {  // the slot's table (none: the count alone is cleared), then the match on this first selection
         build_stop_table(rq.stops, slot, 0);
@@ -3057,6 +3155,7 @@ int Engine::session_admit_tail(Session& s, const GenRequest& rq, const GenParams
     sl.max_new = max_new; sl.kv_pos = (int)P; sl.reported = 0; sl.rp = row; sl.prompt = (int)P;
     sl.biased = rq.bias.active();
     sl.penalised = rq.pen.active();
+    sl.windowed = windowed;
     sl.stopped = rq.stops.active();
     sl.ids = rq.ids;
     sl.mask = rq.mask.empty() ? std::vector<uint8_t>(P, 0) : rq.mask;
@@ -3266,16 +3365,19 @@ Engine::PrefixStats Engine::session_prefix_stats() const {
     return out;
 }
 
-void Engine::session_step_body(Session& s, bool screened, bool stops) {
+void Engine::session_step_body(Session& s, bool screened, bool stops, bool windowed) {
+    // fixed parameters: the one ngram is switched off for the launch and the window kernel bans for every row;
+    // per request: only the rows with a record (their RowParams carry ngram 0)
+    const int window = windowed ? (s.feat.per_request ? 0 : s.p.ngram) : -1;
     DecSampleArgs sa;
     SampleArgs pen;
     sample_args(s.n, 0, s.p, s.feat.per_request, sa, pen);
     decode_step(s.n, rows_.Lcap);
     if (s.feat.logprobs) {
         const DecLpArgs lp = lp_args(sa, 0);
-        decode_head(s.n, sa, pen, screened, &lp, stops);
+        decode_head(s.n, sa, pen, screened, &lp, stops, window);
     } else {
-        decode_head(s.n, sa, pen, screened, nullptr, stops);
+        decode_head(s.n, sa, pen, screened, nullptr, stops, window);
     }
 }
 
@@ -3285,7 +3387,7 @@ void Engine::session_step_body(Session& s, bool screened, bool stops) {
 bool Engine::session_head_screened(const Session& s) const {
     if (s.feat.logprobs) return false;  // the screened head never forms the logits
     for (int b = 0; b < s.n; ++b)
-        if (s.slot[b].biased || s.slot[b].penalised) return false;  // ... which a constraint or a penalty acts on
+        if (s.slot[b].biased || s.slot[b].penalised || s.slot[b].windowed) return false;  // ... which a constraint, a penalty or a windowed ban acts on
     if (!s.feat.per_request) return s.screened;
     for (int b = 0; b < s.n; ++b)
         if (s.slot[b].rp.do_sample || s.slot[b].rp.rep_penalty != 1.0f) return false;
@@ -3308,20 +3410,26 @@ std::vector<Engine::SlotStatus> Engine::session_step(int k) {
     }
     hipStream_t st = stream_;
     const bool use_graph = graphs_on();
-    const bool screened = session_head_screened(s);
+    // a windowed ban is part of the step iff an active slot carries one.  With fixed parameters such a step runs
+    // every selection at ngram 0, so the ban lists it leaves for a screened head are empty: the burst after it
+    // runs the exact head once more, which writes them again
+    bool windowed = false;
+    for (int b = 0; b < s.n; ++b) windowed = windowed || s.slot[b].windowed;
+    const bool screened = session_head_screened(s) && !s.ban_stale;
     // the match launch is part of the step iff an active slot carries a stop set: resolved here, once per burst
     bool stops = false;
     for (int b = 0; b < s.n; ++b) stops = stops || s.slot[b].stopped;
-    HipGraphExec& graph = s.graph[s.n][screened ? 1 : 0][stops ? 1 : 0];
+    HipGraphExec& graph = s.graph[s.n][screened ? 1 : 0][stops ? 1 : 0][windowed ? 1 : 0];
     if (use_graph && !graph) {
         StreamCapture cap(st, capturing_);
-        session_step_body(s, screened, stops);
+        session_step_body(s, screened, stops, windowed);
         graph = cap.finish();
     }
     for (int i = 0; i < k; ++i) {
         if (use_graph) graph.launch(st);
-        else session_step_body(s, screened, stops);
+        else session_step_body(s, screened, stops, windowed);
     }
+    s.ban_stale = windowed && !s.feat.per_request && rows_.ban != nullptr;
     if (use_graph && stops) stop_launches_ += (size_t)k;
     for (int b = 0; b < s.n; ++b) s.slot[b].kv_pos += k;
     s.steps += (size_t)k;
@@ -3403,6 +3511,8 @@ void Engine::session_slot_move(Session& s, int src, int dst, int rows_bound) {
     }
     if (s.feat.penalties)  // the record travels with its page: 16 bytes
         HIP_CHECK(hipMemcpyAsync(r.pen + dst, r.pen + src, sizeof(PenaltyRec), hipMemcpyDeviceToDevice, stream_));
+    if (s.feat.ngram_window)  // the same: 144 bytes
+        HIP_CHECK(hipMemcpyAsync(r.ngw + dst, r.ngw + src, sizeof(NgramWindowRec), hipMemcpyDeviceToDevice, stream_));
     // the stop set travels with its page: a launch of its own (a page without one: the count, seen and hit alone)
     if (s.feat.stops) launch_stop_slot_move(r.stop_tab, r.stop_n, r.stop_seen, r.stop_hit, src, dst, stream_);
     s.slot[dst] = s.slot[src];

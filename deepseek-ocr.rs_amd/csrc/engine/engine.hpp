@@ -159,10 +159,23 @@ struct Penalties {
 // EINVAL: a non-finite frequency or presence; min_p NaN, below 0 or above 1
 void validate_penalties(const Penalties& pn);
 
+// One request's windowed no-repeat n-gram ban: size g, window w, and ids that are never banned.
+// Off: g < 2.  On: the record replaces the request's plain no_repeat_ngram_size ban.
+struct NgramWindow {
+    int g = 0, w = 0;
+    std::vector<int> whitelist;
+    bool active() const { return g >= 2; }
+    // the record the kernel reads (the whitelist without repeats)
+    NgramWindowRec rec() const;
+};
+// EINVAL: on with w < 1; more than NGRAM_MAX_WHITELIST ids; an id outside [0, vocab)
+void validate_ngram_window(const NgramWindow& nw, int vocab);
+
 struct GenRequest {
     LogitBias bias;
     StopSet stops;
     Penalties pen;
+    NgramWindow ngw;
     std::vector<int> ids;
     std::vector<uint8_t> mask;
     const PagePixels* page = nullptr;
@@ -224,6 +237,8 @@ struct DecodeRows {
     int stop_stage_rows = 0;
     // frequency / presence / min-p records (spec.penalties): one per row, every one starts off
     PenaltyRec* pen = nullptr;
+    // windowed n-gram ban records (spec.ngram_window): one per row, every one starts off
+    NgramWindowRec* ngw = nullptr;
 };
 // What a caller of Engine::reserve_decode_rows asks for
 struct DecodeRowsSpec {
@@ -239,6 +254,7 @@ struct DecodeRowsSpec {
     bool stops = false;        // stop-sequence rows (every count starts 0) ...
     int stop_stage_rows = 1;   // ... and staging for this many lists at a time
     bool penalties = false;    // PenaltyRec rows (every record starts off)
+    bool ngram_window = false; // NgramWindowRec rows (every record starts off)
 };
 typedef void (*TokenCb)(size_t, const int64_t*, void*);
 // rand_core seed_from_u64 for rand 0.8.5 StdRng, in the layout sampling.hip reads (RNG_WORDS words)
@@ -338,6 +354,9 @@ class Engine {
         // every slot keeps a PenaltyRec; an admission may carry penalties (GenRequest::pen), and a burst runs the
         // exact head iff an active slot carries a record that is on
         bool penalties = false;
+        // every slot keeps an NgramWindowRec; an admission may carry a windowed ban (GenRequest::ngw), and a burst
+        // runs the exact head with the window launch iff an active slot carries a record that is on
+        bool ngram_window = false;
     };
     struct SessionInfo {
         int slots = 0, active = 0, max_context = 0, out_cap = 0, kv_cap = 0, burst_cap = 0;
@@ -453,6 +472,10 @@ class Engine {
     // written from the requests' (pinned staging under "s_penstage"; the caller synchronises before the next write)
     DecPenaltyArgs penalty_args(const DecSampleArgs& sa, int row0);
     void write_penalties(const Penalties* const* pn, int row0, int n);
+    // the windowed-ban records likewise (only where rows_.ngw is set; staging under "s_ngwstage").  plain: the
+    // n-gram size the launch applies, with an unbounded window, to rows whose record is off (0: such rows are skipped)
+    DecNgramWindowArgs ngram_window_args(const DecSampleArgs& sa, int row0, int plain);
+    void write_ngram_windows(const NgramWindow* const* nw, int row0, int n);
     // the stop rows of the same pages (only where rows_.stop_tab is set), and the match launch on them (counted)
     DecStopArgs stop_args(const DecSampleArgs& sa, int row0);
     void stop_match(const DecSampleArgs& sa, int row0);
@@ -460,7 +483,7 @@ class Engine {
     void build_stop_table(const StopSet& st, int row, int stage_row);
     // stops: the match launch follows the final selection kernel
     void decode_head(int B, DecSampleArgs& sa, const SampleArgs& pen, bool screened, const DecLpArgs* lp = nullptr,
-                     bool stops = false);
+                     bool stops = false, int window = -1);  // window >= 0: the windowed-ban launch, with this plain size
     void reserve_head_ws(int B);
     LmHeadQ8Args head_q8_args(int B);
     bool screen_applies(int B, float rep_penalty) const;
@@ -489,7 +512,7 @@ class Engine {
     struct Session;
     std::unique_ptr<Session> sess_;
     Session& open_session();
-    void session_step_body(Session& s, bool screened, bool stops);
+    void session_step_body(Session& s, bool screened, bool stops, bool windowed);
     bool session_head_screened(const Session& s) const;
     // profile_decode: its two timers and the sections after the MoE and attention replays
     double replay_us(int n, const std::function<void()>& body);

@@ -294,6 +294,15 @@ struct PenaltyRec {
     bool on() const { return frequency != 0.f || presence != 0.f || ln_min_p > -INFINITY; }
 };
 static_assert(sizeof(PenaltyRec) == 16, "PenaltyRec is staged and moved as 16 bytes");
+// One page's windowed n-gram ban as the kernel reads it: size g, window w and up to
+// NGRAM_MAX_WHITELIST ids that are never banned.  Off: g < 2.
+constexpr int NGRAM_MAX_WHITELIST = 32;
+struct NgramWindowRec {
+    int g = 0, w = 0, n_white = 0, pad = 0;
+    int white[NGRAM_MAX_WHITELIST] = {};
+    bool on() const { return g >= 2; }
+};
+static_assert(sizeof(NgramWindowRec) == 144, "NgramWindowRec is staged and moved as 144 bytes");
 // Repetition penalty over the context tokens (sampling.rs:34-96), in place on the logits.
 // rows != null: every row reads its own penalty (launched unconditionally; a row at 1.0 leaves its logits alone)
 struct SampleArgs {
@@ -696,6 +705,21 @@ struct DecPenaltyArgs {
     const PenaltyRec* rec = nullptr;                 // [B]
 };
 void launch_dec_out_penalty(const DecPenaltyArgs& a, hipStream_t s);
+// Windowed no-repeat n-gram ban with a whitelist (decode_ngram_window.hip): for every start i in
+// [max(0, n - w), n - g] (n = ctx_len[b]) with ctx[i .. i+g-1) == ctx[n-g+1 .. n), the id t = ctx[i+g-1] gets
+// l[b][t] = -inf unless t lies outside [0, V) or in the whitelist; a ban that would leave the row without a finite
+// logit is not applied.  After launch_dec_out_penalty, in the plain ban's place: the selection that follows runs with
+// ngram = 0 for these rows.  plain >= 2: a row whose record is off is banned as {plain, unbounded window, no
+// whitelist}, which is the selection kernels' own ban; plain < 2: such a row is neither read nor written.  Columns
+// [V, ld) are never written.
+struct DecNgramWindowArgs {
+    float* logits = nullptr; int B = 0, V = 0; long ld = 0;
+    const int* ctx = nullptr; long ctx_cap = 0;  // [B][ctx_cap]
+    const int* ctx_len = nullptr;                // [B]
+    const NgramWindowRec* rec = nullptr;         // [B]
+    int plain = 0;
+};
+void launch_dec_ngram_window(const DecNgramWindowArgs& a, hipStream_t s);
 // Stop sequences matched inside the decode step (decode_stop.hip).  Per row: a table
 // [STOP_MAX_SEQS][1 + STOP_MAX_LEN] of int32 (a length, then the ids), n_seq, `seen` (the out_len already examined)
 // and hit[2] = {lowest matching sequence or -1, its length}.

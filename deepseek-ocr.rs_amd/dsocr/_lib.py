@@ -104,6 +104,12 @@ class PenaltiesC(C.Structure):
     _fields_ = [("frequency", C.c_float), ("presence", C.c_float), ("min_p", C.c_double)]
 
 
+class NgramWindowC(C.Structure):
+    """dsocr_ngram_window: one request's windowed no-repeat n-gram ban."""
+    _fields_ = [("ngram_size", C.c_int32), ("window", C.c_int32), ("whitelist", C.POINTER(C.c_int32)),
+                ("n_whitelist", C.c_size_t)]
+
+
 class RowParamsC(C.Structure):
     """dsocr_row_params: one row of dsocr_k_select_rows."""
     _fields_ = [("do_sample", C.c_int), ("temperature", C.c_double), ("top_p", C.c_double), ("top_k", C.c_size_t),
@@ -127,6 +133,8 @@ SESSION_LOGPROBS = 2     # DSOCR_SESSION_LOGPROBS
 SESSION_LOGIT_BIAS = 4   # DSOCR_SESSION_LOGIT_BIAS
 SESSION_STOP = 8         # DSOCR_SESSION_STOP
 SESSION_PENALTIES = 16   # DSOCR_SESSION_PENALTIES
+SESSION_NGRAM_WINDOW = 32  # DSOCR_SESSION_NGRAM_WINDOW
+MAX_NGRAM_WHITELIST = 32   # DSOCR_MAX_NGRAM_WHITELIST
 MAX_STOP_SEQS = 16       # DSOCR_MAX_STOP_SEQS
 MAX_STOP_LEN = 32        # DSOCR_MAX_STOP_LEN
 SESSION_ADMIT_PENDING = 0x100  # DSOCR_SESSION_ADMIT_PENDING (dsocr_session_info flags while an admission is pending)
@@ -176,6 +184,8 @@ EXPORTS = [
     "dsocr_stop_launches", "dsocr_k_stop_match", "dsocr_generate_stop_stream",
     "dsocr_penalties_check", "dsocr_generate_penalties", "dsocr_session_stage_penalties", "dsocr_k_out_penalty",
     "dsocr_k_sample_stoch_min_p",
+    "dsocr_ngram_window_check", "dsocr_generate_ngram_window", "dsocr_session_stage_ngram_window",
+    "dsocr_k_ngram_window",
 ]
 
 # model variants behind the deepseek engine (dsocr_engine_variant)
@@ -341,6 +351,13 @@ def lib():
     L.dsocr_k_out_penalty.argtypes = [i32, i32, i32, vp, vp, i32, vp, C.POINTER(PenaltiesC)]
     L.dsocr_k_sample_stoch_min_p.argtypes = [i32, i32, vp, vp, i32, vp, i32, f32, C.c_double, C.c_size_t, C.c_double,
                                              vp, C.c_uint64, i32, vp]
+    L.dsocr_ngram_window_check.argtypes = [C.POINTER(NgramWindowC), sz]
+    L.dsocr_generate_ngram_window.argtypes = [vp, sz, C.POINTER(RequestC), C.POINTER(DecodeParamsC), C.POINTER(ResultC),
+                                              C.POINTER(C.POINTER(NgramWindowC)), C.POINTER(C.POINTER(PenaltiesC)),
+                                              C.POINTER(C.POINTER(StopSetC)), C.POINTER(StopHitC),
+                                              C.POINTER(C.POINTER(LogitBiasC)), sz, C.POINTER(LogprobsC)]
+    L.dsocr_session_stage_ngram_window.argtypes = [vp, C.POINTER(NgramWindowC)]
+    L.dsocr_k_ngram_window.argtypes = [i32, i32, i32, vp, vp, i32, vp, C.POINTER(C.POINTER(NgramWindowC)), i32]
     _lib = L
     return L
 

@@ -110,6 +110,13 @@ def build_parser() -> argparse.ArgumentParser:
                    help="lower the logit of every token generated so far by X")
     p.add_argument("--min-p", type=float, default=None, metavar="X",
                    help="when sampling, keep only tokens at least X (0..1) times as likely as the most likely one")
+    p.add_argument("--ngram-window-size", type=int, default=None, metavar="N",
+                   help="ban the continuation of every N-gram that already occurs within the last --ngram-window "
+                        "context tokens (replaces --no-repeat-ngram-size for the run); 0 = off")
+    p.add_argument("--ngram-window", type=int, default=None, metavar="W",
+                   help="the window of --ngram-window-size in tokens (default 100)")
+    p.add_argument("--ngram-whitelist", metavar="ID,ID,...",
+                   help="token ids --ngram-window-size never bans (at most 32)")
     p.add_argument("--slots", type=int, default=0, metavar="N",
                    help="treat every --image as its own one-page document (the prompt has one <image>) and decode them "
                         "together in a session of N slots (1..8); results print in input order.  0 = off")
@@ -244,7 +251,30 @@ def token_constraint(args) -> dict:
         raise DsocrError(1, "--ban-token / --allow-tokens-file / --logit-bias apply to one document: not with --slots")
     kw.update(stop_arguments(args))
     kw.update(penalty_arguments(args))
+    kw.update(ngram_window_arguments(args))
     return kw
+
+
+def ngram_window_arguments(args) -> dict:
+    """--ngram-window-size / --ngram-window / --ngram-whitelist as the keyword of ``engine.decode`` ({} when they ask
+    for nothing).  Checked here, before any load."""
+    from .ngram_window import NgramWindowError, make_ngram_window
+    white = getattr(args, "ngram_whitelist", None)
+    try:
+        ids = None
+        if white is not None:
+            try:
+                ids = [int(t) for t in white.split(",") if t.strip()]
+            except ValueError:
+                raise NgramWindowError("--ngram-whitelist takes token ids separated by commas") from None
+        rec = make_ngram_window(getattr(args, "ngram_window_size", None), getattr(args, "ngram_window", None), ids)
+    except NgramWindowError as e:
+        raise DsocrError(1, f"--ngram-window-size / --ngram-window / --ngram-whitelist: {e}") from None
+    if rec is None:
+        return {}
+    if getattr(args, "slots", 0):
+        raise DsocrError(1, "--ngram-window-size applies to one document: not with --slots")
+    return rec.kwargs()
 
 
 def penalty_arguments(args) -> dict:

@@ -19,10 +19,12 @@ from typing import Any, Callable, Optional, Sequence
 import numpy as np
 
 from ._lib import (DTYPES, LOAD_PACKED_EXPERTS, MAX_TOP_LOGPROBS, DecodeParamsC, DsocrError, LoadArgs, LogitBiasC, LogprobsC,
-                   PenaltiesC, RequestC, ResultC, STREAM_CB, SESSION_LOGIT_BIAS, SESSION_LOGPROBS, SESSION_PENALTIES,
+                   NgramWindowC, PenaltiesC, RequestC, ResultC, STREAM_CB, SESSION_LOGIT_BIAS, SESSION_LOGPROBS,
+                   SESSION_NGRAM_WINDOW, SESSION_PENALTIES,
                    SESSION_PER_REQUEST, SESSION_STOP,
                    SessionDescC, SlotStatusC, StopHitC, StopSetC, TimingsC, VisionSettingsC, check, lib)
 from .constraint import ConstraintError, LogitConstraint, merge_constraint
+from .ngram_window import NgramWindow, NgramWindowError, make_ngram_window
 from .penalties import Penalties, PenaltyError, make_penalties
 from .stops import StopError, StopSet, apply_stops, merge_stops
 
@@ -79,6 +81,33 @@ def _penalties_c(pn: Optional[Penalties]) -> Optional[PenaltiesC]:
     if pn is None:
         return None
     return PenaltiesC(pn.frequency, pn.presence, pn.min_p)
+
+
+def _ngram_window(ngram_window, vocab) -> Optional[NgramWindow]:
+    """The ``ngram_window=`` argument (a ``dsocr.ngram_window.NgramWindow``, a mapping with ``ngram_size`` / ``window``
+    / ``whitelist``, or None) as one checked record, None when it asks for nothing; a bad one is the engine's EINVAL."""
+    try:
+        if ngram_window is None or isinstance(ngram_window, NgramWindow):
+            return make_ngram_window(ngram_window, vocab=vocab)
+        if isinstance(ngram_window, dict):
+            extra = set(ngram_window) - {"ngram_size", "window", "whitelist"}
+            if extra:
+                raise NgramWindowError(f"unknown field {sorted(extra)[0]!r}")
+            return make_ngram_window(ngram_window.get("ngram_size"), ngram_window.get("window"),
+                                     ngram_window.get("whitelist"), vocab=vocab)
+        raise NgramWindowError("ngram_window must be a NgramWindow record or a mapping")
+    except NgramWindowError as e:
+        raise DsocrError(1, f"EINVAL: n-gram window: {e}") from None
+
+
+def _ngram_window_c(nw: Optional[NgramWindow], keep) -> Optional[NgramWindowC]:
+    """(``keep`` holds the whitelist array alive until the call returns)"""
+    if nw is None:
+        return None
+    n = len(nw.whitelist)
+    arr = (C.c_int32 * max(n, 1))(*nw.whitelist)
+    keep.append(arr)
+    return NgramWindowC(nw.ngram_size, nw.window, C.cast(arr, C.POINTER(C.c_int32)), n)
 
 
 @dataclass
@@ -489,6 +518,29 @@ class DeepseekOcrEngine:
         got = (b.ids(), [(int(h.seq), int(h.match_len)) for h in hits])
         return (*got, *lp.unpack()) if lp else got
 
+    def generate_ngram_window(self, requests, ngram_windows, params: DecodeParameters = DecodeParameters(),
+                              ignore_eos: bool = False, top_k: Optional[int] = None, constraints=None, stop_sets=None,
+                              penalties=None):
+        """generate_batch with one windowed n-gram ban per request (dsocr_generate_ngram_window): ``ngram_windows[i]``
+        is a ``dsocr.ngram_window.NgramWindow`` or None; ``penalties``, ``constraints`` and ``stop_sets`` likewise (or
+        None for none).  Returns what ``generate_penalties`` returns."""
+        n = len(requests)
+        if len(ngram_windows) != n or any(x is not None and len(x) != n for x in (constraints, stop_sets, penalties)):
+            raise DsocrError(1, "one n-gram window record (or None) per request")
+        _check_top_k(top_k)
+        b = _Batch(self, requests, params)
+        ngw = _ptr_array(NgramWindowC, [_ngram_window_c(_ngram_window(w, self.vocab), b.keep) for w in ngram_windows], b.keep)
+        pen = None if penalties is None else _ptr_array(PenaltiesC, [_penalties_c(pn) for pn in penalties], b.keep)
+        stops = None if stop_sets is None else _ptr_array(StopSetC, [_stop_c(ss, b.keep) for ss in stop_sets], b.keep)
+        bias = None if constraints is None else _ptr_array(LogitBiasC, [_bias_c(c, b.keep) for c in constraints], b.keep)
+        hits = (StopHitC * b.n)()
+        lp = None if top_k is None else _LogprobBuffers(b.n, b.cap, int(top_k))
+        pc = _params_c(params, self.eos_token_id, ignore_eos)
+        check(lib().dsocr_generate_ngram_window(self._h, b.n, b.reqs, C.byref(pc), b.res, ngw, pen, stops, hits, bias,
+                                                lp.k if lp else 0, lp.c if lp else None))
+        got = (b.ids(), [(int(h.seq), int(h.match_len)) for h in hits])
+        return (*got, *lp.unpack()) if lp else got
+
     def generate_stop_stream(self, request, stop_set, params: DecodeParameters = DecodeParameters(),
                              stream: Optional[Callable] = None, ignore_eos: bool = False):
         """``generate`` (one page, its stream callback) with a stop set (dsocr_generate_stop_stream): ``(ids, (seq,
@@ -575,7 +627,8 @@ class DeepseekOcrEngine:
     # ------------------------------------------------------------------ decode sessions
     def open_session(self, slots: int, max_context: int, params: DecodeParameters = DecodeParameters(),
                      ignore_eos: bool = False, per_request: bool = False, logprobs: bool = False,
-                     logit_bias: bool = False, stops: bool = False, penalties: bool = False) -> "Session":
+                     logit_bias: bool = False, stops: bool = False, penalties: bool = False,
+                     ngram_window: bool = False) -> "Session":
         """A long-lived batch of `slots` pages (dsocr_session_open): pages are admitted and retired between bursts
         of decode steps.  `params` are the session's; params.max_new_tokens bounds a request's own.
         ``per_request`` (dsocr_session_open_ex, DSOCR_SESSION_PER_REQUEST): `params` are only the defaults and
@@ -585,8 +638,11 @@ class DeepseekOcrEngine:
         ``banned_token_ids``; a burst with a constrained page runs the exact head.  ``stops`` (DSOCR_SESSION_STOP):
         every admission may carry ``stop`` / ``stop_token_ids``; the step of a burst with such a page contains the
         match launch.  ``penalties`` (DSOCR_SESSION_PENALTIES): every admission may carry ``frequency_penalty`` /
-        ``presence_penalty`` / ``min_p``; a burst with such a page runs the exact head."""
-        return Session(self, slots, max_context, params, ignore_eos, per_request, logprobs, logit_bias, stops, penalties)
+        ``presence_penalty`` / ``min_p``; a burst with such a page runs the exact head.  ``ngram_window``
+        (DSOCR_SESSION_NGRAM_WINDOW): every admission may carry ``ngram_window``; a burst with such a page runs the
+        exact head with the window launch."""
+        return Session(self, slots, max_context, params, ignore_eos, per_request, logprobs, logit_bias, stops, penalties,
+                       ngram_window)
 
     # ------------------------------------------------------------------ OcrEngine::decode
     def decode(self, tokenizer, prompt: str, images: Sequence, vision: VisionSettings,
@@ -594,8 +650,11 @@ class DeepseekOcrEngine:
                logprobs: Optional[int] = None, logit_bias=None, allowed_token_ids=None,
                banned_token_ids=None, stop=None, stop_token_ids=None,
                include_stop_in_output: bool = False, frequency_penalty=None, presence_penalty=None,
-               min_p=None) -> DecodeOutcome:
-        """``frequency_penalty`` / ``presence_penalty`` lower the logit of every id the page has already generated
+               min_p=None, ngram_window=None) -> DecodeOutcome:
+        """``ngram_window`` (a ``dsocr.ngram_window.NgramWindow``): the windowed no-repeat n-gram ban with its
+        whitelist, which replaces the plain ``no_repeat_ngram_size`` ban of ``params`` for this page (``stream`` is not
+        called).
+        ``frequency_penalty`` / ``presence_penalty`` lower the logit of every id the page has already generated
         (by ``frequency * count + presence``; prompt and image slots do not count) and ``min_p`` keeps, when sampling,
         only tokens at least ``min_p`` times as likely as the most likely one (``dsocr.penalties``; ``stream`` is not
         called).
@@ -612,14 +671,20 @@ class DeepseekOcrEngine:
         con = _constraint(logit_bias, allowed_token_ids, banned_token_ids, self.vocab)
         ss = _stops(stop, stop_token_ids, tokenizer, self.vocab)
         pen = _penalties(frequency_penalty, presence_penalty, min_p)
+        ngw = _ngram_window(ngram_window, self.vocab)
         pages = [Page(im, vision, self) for im in images]
         ids, mask = build_prompt_tokens(tokenizer, prompt, [p.n_image_tokens for p in pages])
         token_lp = top = None
-        if logprobs is not None or con is not None or ss is not None or pen is not None:
+        if logprobs is not None or con is not None or ss is not None or pen is not None or ngw is not None:
             rows = np.concatenate(self.image_embeddings(pages), axis=0) if len(pages) > 1 else None
             req = (ids, mask, pages[0] if len(pages) == 1 else None, rows)
-        if ss is not None or pen is not None:
-            if pen is not None:
+        if ss is not None or pen is not None or ngw is not None:
+            if ngw is not None:
+                got = self.generate_ngram_window([req], [ngw], params, top_k=None if logprobs is None else int(logprobs),
+                                                 constraints=None if con is None else [con],
+                                                 stop_sets=None if ss is None else [ss],
+                                                 penalties=None if pen is None else [pen])
+            elif pen is not None:
                 got = self.generate_penalties([req], [pen], params, top_k=None if logprobs is None else int(logprobs),
                                               constraints=None if con is None else [con],
                                               stop_sets=None if ss is None else [ss])
@@ -686,7 +751,7 @@ class Session:
 
     def __init__(self, engine: DeepseekOcrEngine, slots: int, max_context: int, params: DecodeParameters,
                  ignore_eos: bool = False, per_request: bool = False, logprobs: bool = False, logit_bias: bool = False,
-                 stops: bool = False, penalties: bool = False):
+                 stops: bool = False, penalties: bool = False, ngram_window: bool = False):
         self._e = None
         # the (StopSet, include) record of an admission follows its page: staged for the C call that admits it,
         # pending while a chunked admission runs, then its slot's
@@ -695,7 +760,8 @@ class Session:
         pc = _params_c(params, engine.eos_token_id, ignore_eos)
         flags = ((SESSION_PER_REQUEST if per_request else 0) | (SESSION_LOGPROBS if logprobs else 0) |
                  (SESSION_LOGIT_BIAS if logit_bias else 0) | (SESSION_STOP if stops else 0) |
-                 (SESSION_PENALTIES if penalties else 0))
+                 (SESSION_PENALTIES if penalties else 0) | (SESSION_NGRAM_WINDOW if ngram_window else 0))
+        self.has_ngram_window = bool(ngram_window)
         self.has_penalties = bool(penalties)
         self.has_stops = bool(stops)
         self.has_logprobs = bool(logprobs)
@@ -725,7 +791,7 @@ class Session:
               ignore_eos: Optional[bool] = None, logprobs: Optional[int] = None, logit_bias=None,
               allowed_token_ids=None, banned_token_ids=None, stop=None, stop_token_ids=None,
               include_stop_in_output: bool = False, tokenizer=None, stops: Optional[StopSet] = None,
-              frequency_penalty=None, presence_penalty=None, min_p=None) -> int:
+              frequency_penalty=None, presence_penalty=None, min_p=None, ngram_window=None) -> int:
         """Without ``params``: the session's parameters with this page's ``max_new_tokens`` / ``seed``
         (dsocr_session_admit).  With ``params``: the page's whole parameter set (dsocr_session_admit_params; its
         max_new_tokens and seed count, the two keyword arguments are then not read); ``eos_token_id`` /
@@ -740,11 +806,13 @@ class Session:
         The session returns ids as the device wrote them, matched tokens included: ``stop_hit(slot)`` names the hit
         and ``retire_stopped`` trims by it unless ``include_stop_in_output``.
         ``frequency_penalty`` / ``presence_penalty`` / ``min_p``: the page's penalties (a session opened with
-        ``penalties``; EINVAL otherwise), applied from its first token on; ``min_p`` acts on a sampled page only."""
+        ``penalties``; EINVAL otherwise), applied from its first token on; ``min_p`` acts on a sampled page only.
+        ``ngram_window``: the page's windowed n-gram ban (a session opened with ``ngram_window``; EINVAL otherwise),
+        which replaces its plain ``no_repeat_ngram_size`` ban."""
         req, _, _keep = self._admission((ids, mask, page, image_rows), None, logprobs,
                                         (logit_bias, allowed_token_ids, banned_token_ids),
                                         (stop, stop_token_ids, include_stop_in_output, tokenizer, stops),
-                                        (frequency_penalty, presence_penalty, min_p))
+                                        (frequency_penalty, presence_penalty, min_p), ngram_window)
         slot = C.c_int(-1)
         if params is not None:
             pc = _params_c(params, self._eos if eos_token_id is None else int(eos_token_id),
@@ -756,13 +824,14 @@ class Session:
                                  0 if seed is None else 1, seed or 0, C.byref(slot))
         return self._admitted_stops(slot.value)
 
-    def _admission(self, request, request_params, logprobs, constraint, stops, penalties=(None, None, None)):
+    def _admission(self, request, request_params, logprobs, constraint, stops, penalties=(None, None, None),
+                   ngram_window=None):
         """What every admission form does before its C call, in this order: the ``logprobs`` check, the request
         (``request``: ids, mask, page, image rows), its parameter record (``request_params``: ``_request_params``'
         arguments, or None for none), the stop set merged and checked (``stops``: ``_check_stops``' arguments), then
         the constraint staged (``constraint``: ``_stage_constraint``'s arguments) and the stop set staged; the
         penalties (``penalties``: frequency_penalty, presence_penalty, min_p) are checked with the stop set, before
-        anything is staged, and staged last.  Returns
+        anything is staged, and staged after it; the windowed n-gram ban (``ngram_window``) likewise, staged last.  Returns
         the request, the parameter record and the list that keeps their arrays alive; the checked stop record is
         ``_staged_stops``."""
         self._check_logprobs(logprobs)
@@ -771,10 +840,35 @@ class Session:
         pc = None if request_params is None else self._request_params(*request_params)
         checked = self._check_stops(*stops)
         pen = self._check_penalties(*penalties)
+        ngw = self._check_ngram_window(ngram_window)
         self._stage_constraint(*constraint)
         self._stage_stops(checked)
         self._stage_penalties(pen)
+        self._stage_ngram_window(ngw)
         return req, pc, keep
+
+    def _check_ngram_window(self, ngram_window) -> Optional[NgramWindow]:
+        """The windowed n-gram ban of an admission, checked before anything is staged for it (None: none)."""
+        ngw = _ngram_window(ngram_window, self._e.vocab)
+        if ngw is not None and not self.has_ngram_window:
+            raise DsocrError(1, "EINVAL: this session was opened without ngram_window")
+        return ngw
+
+    def _stage_ngram_window(self, ngw: Optional[NgramWindow]) -> None:
+        """Stages the checked record for the admission call that follows (dsocr_session_stage_ngram_window), which
+        consumes it.  Should the staging itself fail, what was staged before it is cleared."""
+        if ngw is None:
+            return
+        keep = []
+        rec = _ngram_window_c(ngw, keep)
+        try:
+            check(lib().dsocr_session_stage_ngram_window(self._e._h, C.byref(rec)))
+        except DsocrError:
+            lib().dsocr_session_stage_logit_bias(self._e._h, None)
+            lib().dsocr_session_stage_stop(self._e._h, None)
+            lib().dsocr_session_stage_penalties(self._e._h, None)
+            self._staged_stops = None
+            raise
 
     def _check_penalties(self, frequency_penalty, presence_penalty, min_p) -> Optional[Penalties]:
         """The penalties of an admission, checked before anything is staged for it (None: none)."""
@@ -896,7 +990,7 @@ class Session:
                     ignore_eos: Optional[bool] = None, logprobs: Optional[int] = None, logit_bias=None,
                     allowed_token_ids=None, banned_token_ids=None, stop=None, stop_token_ids=None,
                     include_stop_in_output: bool = False, tokenizer=None, stops: Optional[StopSet] = None,
-                    frequency_penalty=None, presence_penalty=None, min_p=None) -> int:
+                    frequency_penalty=None, presence_penalty=None, min_p=None, ngram_window=None) -> int:
         """``admit`` in slices (dsocr_session_admit_begin): every check runs here and nothing is launched; the work
         is done by ``admit_advance``, one slice per call (the page's vision, then the prompt in chunks of
         ``chunk_rows`` >= 32 rows), with ``step`` / ``retire`` legal in between.  Returns the admission's ticket.
@@ -906,7 +1000,7 @@ class Session:
                                          (params, max_new_tokens, seed, eos_token_id, ignore_eos), logprobs,
                                          (logit_bias, allowed_token_ids, banned_token_ids),
                                          (stop, stop_token_ids, include_stop_in_output, tokenizer, stops),
-                                         (frequency_penalty, presence_penalty, min_p))
+                                         (frequency_penalty, presence_penalty, min_p), ngram_window)
         self._pending_stops = None
         ticket = C.c_int(-1)
         self._admission_call(lib().dsocr_session_admit_begin, C.byref(req), C.byref(pc), max(int(chunk_rows), 0),
@@ -963,7 +1057,7 @@ class Session:
                      logprobs: Optional[int] = None, logit_bias=None, allowed_token_ids=None,
                      banned_token_ids=None, stop=None, stop_token_ids=None, include_stop_in_output: bool = False,
                      tokenizer=None, stops: Optional[StopSet] = None, frequency_penalty=None,
-                     presence_penalty=None, min_p=None) -> int:
+                     presence_penalty=None, min_p=None, ngram_window=None) -> int:
         """``admit`` for a prompt that starts with the entry's rows (dsocr_session_admit_prefix): ``ids`` / ``mask``
         are the whole prompt's, no page and no image rows; vision and the prefill of the entry's rows are skipped.
         The keywords are ``admit``'s (without ``params``: the session's parameters with this ``max_new_tokens`` /
@@ -972,7 +1066,7 @@ class Session:
                                          (params, max_new_tokens, seed, eos_token_id, ignore_eos), logprobs,
                                          (logit_bias, allowed_token_ids, banned_token_ids),
                                          (stop, stop_token_ids, include_stop_in_output, tokenizer, stops),
-                                         (frequency_penalty, presence_penalty, min_p))
+                                         (frequency_penalty, presence_penalty, min_p), ngram_window)
         slot = C.c_int(-1)
         self._admission_call(lib().dsocr_session_admit_prefix, int(handle), C.byref(req), C.byref(pc), C.byref(slot))
         return self._admitted_stops(slot.value)

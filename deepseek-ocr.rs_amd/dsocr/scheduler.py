@@ -38,6 +38,12 @@ session with ``penalties=True`` and such a request shares it (a burst with a pen
 without the flag it runs alone through ``engine.decode(...)`` with the same arguments after the session drained.
 Prefix-cache keys do not see the record.
 
+Windowed n-gram ban: ``submit(..., ngram_window=NgramWindow(...))`` is checked on the caller's thread
+(``dsocr.ngram_window.make_ngram_window``; a bad one fails the future).  ``BatchScheduler(..., ngram_window=True)``
+opens the session with ``ngram_window=True`` and such a request shares it (a burst with such a page runs the exact
+head); without the flag it runs alone through ``engine.decode(...)`` with the same argument after the session drained.
+Prefix-cache keys do not see the record.
+
 Page prefix cache: ``BatchScheduler(..., prefix_cache=N)`` (default 0: nothing changes) keeps the K/V rows of up to N
 pages' prompt prefixes (BOS and the image rows) in the session.  After a one-image request is admitted its prefix is
 kept (``Session.keep_prefix``, rows = index of the last image position + 1) under the key (SHA-256 of the image as
@@ -68,6 +74,7 @@ from dataclasses import dataclass, field, fields
 from typing import Any, Callable, Optional, Sequence
 
 from .constraint import merge_constraint
+from .ngram_window import make_ngram_window
 from .penalties import make_penalties
 from .stops import TextStop, TokenHoldback, merge_stops
 from .engine import DecodeOutcome, DecodeParameters, Page, VisionSettings, build_prompt_tokens, normalize_text
@@ -103,6 +110,7 @@ class _Request:
     constraint: Any = None  # the request's merged LogitConstraint, or None
     stops: Any = None       # the request's merged StopSet, or None
     penalties: Any = None   # the request's checked Penalties, or None
+    ngram_window: Any = None  # the request's checked NgramWindow, or None
     stop_args: dict = field(default_factory=dict)  # ... as the keywords engine.decode takes
     include_stop: bool = False
     holdback: Any = None    # TokenHoldback of a streaming request with stops
@@ -165,7 +173,7 @@ class BatchScheduler:
                  defaults: DecodeParameters = DecodeParameters(), vision: Optional[VisionSettings] = None,
                  prepare: Optional[Callable] = None, per_request_params: bool = False, logprobs: bool = False,
                  prefix_cache: int = 0, admit_chunk: int = 0, logit_bias: bool = False, stops: bool = False,
-                 penalties: bool = False):
+                 penalties: bool = False, ngram_window: bool = False):
         if not 1 <= int(slots) <= 8:
             raise ValueError("a session has 1..8 slots")
         if int(admit_chunk) != 0 and int(admit_chunk) < 32:
@@ -191,6 +199,7 @@ class BatchScheduler:
         self.logit_bias = bool(logit_bias)
         self.stops = bool(stops)
         self.penalties = bool(penalties)
+        self.ngram_window = bool(ngram_window)
         self.vision = vision or VisionSettings()
         self._prepare = prepare or _default_prepare
         self._queue: deque = deque()
@@ -224,8 +233,9 @@ class BatchScheduler:
                logprobs: Optional[int] = None, logit_bias=None, allowed_token_ids=None,
                banned_token_ids=None, stop=None, stop_token_ids=None,
                include_stop_in_output: bool = False, frequency_penalty=None, presence_penalty=None,
-               min_p=None) -> Future:
-        """``frequency_penalty`` / ``presence_penalty`` / ``min_p``: the request's penalties (see the module text).
+               min_p=None, ngram_window=None) -> Future:
+        """``ngram_window``: the request's windowed n-gram ban (see the module text).
+        ``frequency_penalty`` / ``presence_penalty`` / ``min_p``: the request's penalties (see the module text).
         ``stop`` / ``stop_token_ids`` / ``include_stop_in_output``: the request's stop set (see the module text).
         ``logit_bias`` / ``allowed_token_ids`` / ``banned_token_ids``: the request's token constraint (see the
         module text).  ``logprobs`` = K (0..20) asks for the request's per-token log-probabilities.  It changes the arity of
@@ -245,6 +255,9 @@ class BatchScheduler:
                                           getattr(self.engine, "vocab", None))
             stops = merge_stops(stop, stop_token_ids, self.tokenizer, getattr(self.engine, "vocab", None))
             penalties = make_penalties(frequency_penalty, presence_penalty, min_p)
+            if ngram_window is not None and not hasattr(ngram_window, "ngram_size"):
+                raise ValueError("ngram_window must be a dsocr.ngram_window.NgramWindow")
+            window = make_ngram_window(ngram_window, vocab=getattr(self.engine, "vocab", None))
         except ValueError as e:
             fut.set_exception(e)
             return fut
@@ -263,6 +276,7 @@ class BatchScheduler:
         rq.logprobs = None if logprobs is None else int(logprobs)
         rq.constraint = constraint
         rq.penalties = penalties
+        rq.ngram_window = window
         if stops is not None:
             rq.stops, rq.include_stop = stops, bool(include_stop_in_output)
             rq.stop_args = dict(stop=stop, stop_token_ids=stop_token_ids, include_stop_in_output=rq.include_stop)
@@ -272,7 +286,8 @@ class BatchScheduler:
                 rq.text_stop = TextStop(stops.strings, rq.include_stop)
         rq.exclusive = (not self.compatible(params, len(rq.ids)) or (rq.logprobs is not None and not self.logprobs) or
                         (constraint is not None and not self.logit_bias) or (stops is not None and not self.stops) or
-                        (penalties is not None and not self.penalties))
+                        (penalties is not None and not self.penalties) or
+                        (window is not None and not self.ngram_window))
         if self.prefix_cache and len(rq.images) == 1 and not rq.exclusive and any(rq.mask):
             rows = max(i for i, m in enumerate(rq.mask) if m) + 1
             if rows < len(rq.ids):  # some text follows the image: the last row's logits come from a new row
@@ -409,6 +424,8 @@ class BatchScheduler:
                 kw["stops"] = True
             if self.penalties:
                 kw["penalties"] = True
+            if self.ngram_window:
+                kw["ngram_window"] = True
             self._session = self.engine.open_session(self.slots, self.max_context, self.defaults, **kw)
 
     def _admit_args(self, rq):
@@ -424,6 +441,8 @@ class BatchScheduler:
             kw.update(stops=rq.stops, include_stop_in_output=rq.include_stop)
         if rq.penalties is not None:
             kw.update(_penalty_kwargs(rq.penalties))
+        if rq.ngram_window is not None:
+            kw.update(rq.ngram_window.kwargs())
         if self.per_request_params:
             kw["params"] = rq.params
         else:
@@ -575,6 +594,8 @@ class BatchScheduler:
         ckw.update(rq.stop_args)  # (a decode with stops does not stream either)
         if rq.penalties is not None:  # (nor does a penalised one)
             ckw.update(_penalty_kwargs(rq.penalties))
+        if rq.ngram_window is not None:  # (nor one with a windowed ban)
+            ckw.update(rq.ngram_window.kwargs())
         try:
             if rq.logprobs is None and not ckw:
                 out = self.engine.decode(self.tokenizer, rq.prompt, rq.images, rq.vision, rq.params, rq.on_token)

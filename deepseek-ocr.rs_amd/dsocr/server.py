@@ -271,6 +271,28 @@ def parse_penalties(req: dict) -> Optional[dict]:
     return {"frequency_penalty": pn.frequency, "presence_penalty": pn.presence, "min_p": pn.min_p}
 
 
+def parse_ngram_window(req: dict, vocab: Optional[int] = None) -> Optional[dict]:
+    """The windowed no-repeat n-gram ban of a request body: `ngram_size`, `window_size` (100 when only `ngram_size`
+    is sent, as upstream) and `whitelist_token_ids`, at top level or inside `vllm_xargs` (where the model's published
+    serving recipe puts them; a top-level field wins).  Returns the keyword ``decode`` / ``submit`` take, None when the
+    body asks for nothing (absent or null fields, `ngram_size` 0).  400: anything else in those fields."""
+    from .ngram_window import NgramWindowError, make_ngram_window
+    xargs = req.get("vllm_xargs")
+    if xargs is None:
+        xargs = {}
+    if not isinstance(xargs, dict):
+        raise ApiError.bad_request("vllm_xargs must be an object")
+    got = {}
+    for name in ("ngram_size", "window_size", "whitelist_token_ids"):
+        v = req.get(name)
+        got[name] = xargs.get(name) if v is None else v
+    try:
+        rec = make_ngram_window(got["ngram_size"], got["window_size"], got["whitelist_token_ids"], vocab=vocab)
+    except NgramWindowError as e:
+        raise ApiError.bad_request(f"ngram window: {e}")
+    return None if rec is None else rec.kwargs()
+
+
 def _held_back(on_token, stops: dict, tokenizer, vocab):
     """``on_token`` behind a ``dsocr.stops.TokenHoldback``: it is called once per token that no later hit can remove."""
     from .stops import TokenHoldback, merge_stops
@@ -558,6 +580,9 @@ def handle_generation(state: ServerState, req: dict, kind: str):
     penalties = parse_penalties(req)
     if penalties:  # keywords of decode / submit beside the constraint's; a penalised decode does not stream either
         constraint = dict(constraint or {}, **penalties)
+    window = parse_ngram_window(req, getattr(state.engine, "vocab", None))
+    if window:  # the same
+        constraint = dict(constraint or {}, **window)
     if stream:
         c = StreamController(state.tokenizer, kind, model)
         if stops:
@@ -669,6 +694,10 @@ def add_scheduler_args(p):
                    help="with --slots: open the decode session with a penalty record per slot, so requests with "
                         "`frequency_penalty` / `presence_penalty` / `min_p` join the running batch (a burst with such "
                         "a request runs the exact lm_head) instead of waiting for it to drain; off by default")
+    p.add_argument("--ngram-window", action="store_true",
+                   help="with --slots: open the decode session with a windowed n-gram ban record per slot, so requests "
+                        "with `ngram_size` / `window_size` / `whitelist_token_ids` join the running batch (a burst with "
+                        "such a request runs the exact lm_head) instead of waiting for it to drain; off by default")
     p.add_argument("--prefix-cache", type=int, default=0,
                    help="with --slots: keep the K/V rows of up to N pages' image prefixes (LRU), so a later prompt on "
                         "the same image under the same vision settings skips vision and the prefill of those rows; "
@@ -681,7 +710,7 @@ def add_scheduler_args(p):
 
 def make_scheduler(state: ServerState, slots: int, max_context: int, per_request_params: bool = False,
                    logprobs: bool = False, prefix_cache: int = 0, admit_chunk: int = 0, logit_bias: bool = False,
-                   stops: bool = False, penalties: bool = False):
+                   stops: bool = False, penalties: bool = False, ngram_window: bool = False):
     """The state's scheduler for --slots N (None for 0: requests take the lock path).  per_request_params: the
     DecodeParameters merge_decode builds from a request body are admitted into the session as that request's own.
     prefix_cache: --prefix-cache N (ValueError without --slots: the entries live in the decode session)."""
@@ -695,13 +724,16 @@ def make_scheduler(state: ServerState, slots: int, max_context: int, per_request
         raise ValueError("--stops needs --slots (the stop tables live in the decode session)")
     if penalties and not slots:
         raise ValueError("--penalties needs --slots (the penalty records live in the decode session)")
+    if ngram_window and not slots:
+        raise ValueError("--ngram-window needs --slots (the window records live in the decode session)")
     if not slots:
         return None
     from .scheduler import BatchScheduler
     return BatchScheduler(state.engine, state.tokenizer, slots, max_context, state.defaults, state.vision,
                           per_request_params=per_request_params, logprobs=logprobs, prefix_cache=prefix_cache,
                           admit_chunk=admit_chunk, **({"logit_bias": True} if logit_bias else {}),
-                          **({"stops": True} if stops else {}), **({"penalties": True} if penalties else {}))
+                          **({"stops": True} if stops else {}), **({"penalties": True} if penalties else {}),
+                          **({"ngram_window": True} if ngram_window else {}))
 
 
 def main(argv=None) -> int:
@@ -729,6 +761,8 @@ def main(argv=None) -> int:
         p.error("--stops needs --slots (the stop tables live in the decode session)")
     if args.penalties and not args.slots:
         p.error("--penalties needs --slots (the penalty records live in the decode session)")
+    if args.ngram_window and not args.slots:
+        p.error("--ngram-window needs --slots (the window records live in the decode session)")
     config = model_config(args)  # --model deepseek-ocr | deepseek-ocr-2: the bundled config and vision defaults
     engine = load_model(ModelLoadArgs(config_path=config, weights_path=args.weights, snapshot_path=args.snapshot,
                                       snapshot_packed=getattr(args, "snapshot_packed", None),
@@ -738,7 +772,7 @@ def main(argv=None) -> int:
                         vision_settings(args), decode_params(args))
     state.scheduler = make_scheduler(state, args.slots, args.max_context, args.per_request_params, args.logprobs,
                                      args.prefix_cache, args.admit_chunk, args.logit_bias, args.stops,
-                                     args.penalties)
+                                     args.penalties, args.ngram_window)
     import uvicorn
     uvicorn.run(create_app(state), host=args.host, port=args.port)
     return 0

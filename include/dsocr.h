@@ -354,6 +354,42 @@ dsocr_status dsocr_generate_penalties(dsocr_engine* e, size_t n, const dsocr_req
                                       dsocr_logprobs* lp);
 dsocr_status dsocr_session_stage_penalties(dsocr_engine* e, const dsocr_penalties* pen);
 
+/* ---- windowed no-repeat n-gram ban with a token whitelist, per request (no reference counterpart:
+ * the reference's no_repeat_ngram_size looks through the whole context).  A record {ngram_size g, window w,
+ * whitelist[0..k)} is off when it is NULL or g < 2.  With ctx[0..n) the page's context row (prompt and generated
+ * ids: what the plain ban reads) and n >= g: for every start i with max(0, n - w) <= i <= n - g and
+ * ctx[i .. i+g-1) == ctx[n-g+1 .. n), the id t = ctx[i+g-1] is a candidate; a candidate outside [0, vocab) or in the
+ * whitelist is skipped, every other one gets l[t] = -inf.  A ban that would leave the row without a finite logit is
+ * dropped for that step (sampling.rs:61-63).  With w >= n and an empty whitelist this is the plain ban.  The window
+ * counts context positions, prompt included: the upstream vLLM processor counts generated tokens only, so the two
+ * differ while the window still reaches into the prompt.  The step order: lm_head, logit bias, log-probability
+ * partials, repetition penalty, frequency / presence, this ban (in the plain ban's place), selection.  A record that
+ * is on replaces the request's no_repeat_ngram_size: the plain ban is not applied on top of it.  A call or burst in
+ * which a record is on runs the exact lm_head and selectors.  DSOCR_EINVAL, before any device state changes: w < 1
+ * with g >= 2 (w < g is legal and never matches); more than DSOCR_MAX_NGRAM_WHITELIST distinct ids (repeats count
+ * once); a whitelist id outside [0, vocab); a record that is on with the logits trace, use_cache = 0 or DSOCR_PERSIST.
+ *   dsocr_ngram_window_check: the record's own checks against `vocab`; needs no engine and no device.
+ *   dsocr_generate_ngram_window: dsocr_generate_penalties with one record per request (ngw [n], entries may be
+ *   NULL; ngw itself NULL: none).
+ *   dsocr_session_stage_ngram_window: stages one record (copied) for the NEXT admission call on this engine's
+ *   session, whichever form it takes, exactly like dsocr_session_stage_penalties.  DSOCR_EINVAL, nothing staged, when
+ *   the record fails a check, no session is open, or it is on and the session was opened without
+ *   DSOCR_SESSION_NGRAM_WINDOW. */
+#define DSOCR_MAX_NGRAM_WHITELIST 32
+typedef struct {
+    int32_t ngram_size;
+    int32_t window;
+    const int32_t* whitelist;
+    size_t n_whitelist;
+} dsocr_ngram_window;
+dsocr_status dsocr_ngram_window_check(const dsocr_ngram_window* ngw, size_t vocab);
+dsocr_status dsocr_generate_ngram_window(dsocr_engine* e, size_t n, const dsocr_request* reqs,
+                                         const dsocr_decode_params* params, dsocr_result* results,
+                                         const dsocr_ngram_window* const* ngw, const dsocr_penalties* const* pen,
+                                         const dsocr_stop_set* const* stops, dsocr_stop_hit* hits,
+                                         const dsocr_logit_bias* const* bias, size_t top_k, dsocr_logprobs* lp);
+dsocr_status dsocr_session_stage_ngram_window(dsocr_engine* e, const dsocr_ngram_window* ngw);
+
 /* ---- decode sessions: pages join and leave a running batch between decode steps (no reference counterpart: the
  * reference server decodes one request at a time behind its Mutex, server/src/state.rs:22).  A session is a
  * long-lived batch of `slots` (1..8) pages with max_context rows each (a page needs prompt_len + max_new_tokens
@@ -415,6 +451,11 @@ dsocr_status dsocr_session_open(dsocr_engine* e, size_t slots, size_t max_contex
  * exact step.  A burst runs the exact head iff an active slot carries a record that is on; the record follows its
  * page through the compaction of dsocr_session_retire and ends with the page. */
 #define DSOCR_SESSION_PENALTIES 16u
+/* DSOCR_SESSION_NGRAM_WINDOW (combines with the five flags above): every slot keeps a 144-byte windowed-ban record
+ * (reserved at open, off until an admission brings one: dsocr_session_stage_ngram_window).  A burst runs the exact
+ * head with the window launch iff an active slot carries a record that is on; the record follows its page through
+ * the compaction of dsocr_session_retire and ends with the page. */
+#define DSOCR_SESSION_NGRAM_WINDOW 32u
 dsocr_status dsocr_session_open_ex(dsocr_engine* e, size_t slots, size_t max_context, const dsocr_decode_params* params,
                                    uint32_t flags);
 /* Every check (free slot, context need, prompt/image mismatch, token ids, page variant) happens before any device
@@ -910,6 +951,11 @@ dsocr_status dsocr_k_stop_match(int B, int steps, int out_cap, const int* n_seq,
  * record per row (never NULL; min_p is not read by this kernel). */
 dsocr_status dsocr_k_out_penalty(int B, int V, int ld, float* logits, const int* out_ids, int out_cap,
                                  const int* out_len, const dsocr_penalties* pen);
+/* launch_dec_ngram_window once on host rows: logits [B][ld] (in / out), ctx [B][ctx_cap], ctx_len [B] and one record
+ * pointer per row (an entry may be NULL: off).  plain >= 2: a row whose record is off is banned as {plain, unbounded
+ * window, no whitelist}; else it is left alone. */
+dsocr_status dsocr_k_ngram_window(int B, int V, int ld, float* logits, const int* ctx, int ctx_cap, const int* ctx_len,
+                                  const dsocr_ngram_window* const* recs, int plain);
 /* dsocr_k_sample_stoch with a per-row ln_min_p (host array [B]; -inf: no filter): the sampling selector and the
  * final kernel `draws` times on the same logits, the RNG state carried over (out_tok [draws][B]).  The other
  * pointers are device pointers, as there. */
