@@ -27,7 +27,7 @@ KERNELS = ["gemm", "gemm_bf16", "moe", "norm", "attention", "misc", "decode_gemv
            "decode_moe", "decode_sample", "lmhead", "dsq", "preprocess", "sampling", "dots_ops", "attention_bf16",
            "decode_mm", "decode_persist", "decode_q", "attention_prefix", "ocr2_ops", "session",
            "decode_logprob", "attention_past", "decode_bias", "decode_stop", "decode_penalty",
-           "decode_ngram_window"]
+           "decode_ngram_window", "decode_guided"]
 HOST = ["engine", "dots", "capi"]
 
 

@@ -26,6 +26,7 @@ struct dsocr_engine {
     dsocr::StopSet staged_stop;    // dsocr_session_stage_stop: the same
     dsocr::Penalties staged_pen;   // dsocr_session_stage_penalties: the same
     dsocr::NgramWindow staged_ngw; // dsocr_session_stage_ngram_window: the same
+    dsocr::Guided staged_guided;   // dsocr_session_stage_guided: the same
 };
 struct dsocr_page_pixels {
     dsocr::PagePixels px;
@@ -206,9 +207,38 @@ dsocr::NgramWindow to_ngram_window(const dsocr_ngram_window* nw, size_t vocab) {
     return w;
 }
 
-// a session admission's request: the staged constraint, stop set, penalties and windowed ban move into it (consumed
-// whatever the admission does)
+// the token automaton as the engine takes it, checked against `vocab` and `eos` (negative: no EOS rule; NULL: off).
+// Nothing is read past what the checks so far allow: E comes from a row_ptr already known to be sane
+dsocr::Guided to_guided(const dsocr_guided* gd, int vocab, long long eos) {
+    dsocr::Guided g;
+    if (!gd) return g;
+    if (gd->n_states < 1 || gd->n_states > DSOCR_MAX_GUIDED_STATES)
+        throw std::runtime_error("EINVAL: token automaton: n_states must be 1.." + std::to_string(DSOCR_MAX_GUIDED_STATES));
+    if (!gd->accepting || !gd->row_ptr) throw std::runtime_error("EINVAL: token automaton: NULL accepting or row_ptr");
+    const size_t n = (size_t)gd->n_states;
+    if (gd->row_ptr[0] != 0) throw std::runtime_error("EINVAL: token automaton: row_ptr must start at 0");
+    for (size_t i = 0; i < n; ++i)
+        if (gd->row_ptr[i + 1] < gd->row_ptr[i]) throw std::runtime_error("EINVAL: token automaton: row_ptr must not decrease");
+    const long E = gd->row_ptr[n];
+    if (E > (long)DSOCR_MAX_GUIDED_EDGES)
+        throw std::runtime_error("EINVAL: token automaton: more than " + std::to_string(DSOCR_MAX_GUIDED_EDGES) + " edges");
+    if (E && (!gd->edge_tok || !gd->edge_next)) throw std::runtime_error("EINVAL: token automaton: NULL edge arrays");
+    g.n_states = gd->n_states; g.start = gd->start;
+    g.accepting.assign(gd->accepting, gd->accepting + n);
+    g.row_ptr.assign(gd->row_ptr, gd->row_ptr + n + 1);
+    if (E) {
+        g.edge_tok.assign(gd->edge_tok, gd->edge_tok + E);
+        g.edge_next.assign(gd->edge_next, gd->edge_next + E);
+    }
+    dsocr::validate_guided(g, vocab, eos < 0 ? -1L : (long)std::min<long long>(eos, INT32_MAX));
+    return g;
+}
+
+// a session admission's request: the staged constraint, stop set, penalties, windowed ban and automaton move into it
+// (consumed whatever the admission does)
 dsocr::GenRequest to_admission(dsocr_engine* e, const dsocr_request& r) {
+    dsocr::Guided gd = std::move(e->staged_guided);
+    e->staged_guided = dsocr::Guided();
     dsocr::NgramWindow nw = std::move(e->staged_ngw);
     e->staged_ngw = dsocr::NgramWindow();
     const dsocr::Penalties pn = e->staged_pen;
@@ -222,13 +252,14 @@ dsocr::GenRequest to_admission(dsocr_engine* e, const dsocr_request& r) {
     g.stops = std::move(st);
     g.pen = pn;
     g.ngw = std::move(nw);
+    g.guided = std::move(gd);
     return g;
 }
 
 // the DSOCR_SESSION_* feature bits as the engine takes them, and back (DSOCR_SESSION_ADMIT_PENDING is state, not one of them)
 dsocr::Engine::SessionFeatures to_features(uint32_t flags) {
     if (flags & ~(uint32_t)(DSOCR_SESSION_PER_REQUEST | DSOCR_SESSION_LOGPROBS | DSOCR_SESSION_LOGIT_BIAS | DSOCR_SESSION_STOP |
-                             DSOCR_SESSION_PENALTIES | DSOCR_SESSION_NGRAM_WINDOW))
+                             DSOCR_SESSION_PENALTIES | DSOCR_SESSION_NGRAM_WINDOW | DSOCR_SESSION_GUIDED))
         throw std::runtime_error("EINVAL: unknown session flags");
     dsocr::Engine::SessionFeatures f;
     f.per_request = (flags & DSOCR_SESSION_PER_REQUEST) != 0;
@@ -237,12 +268,14 @@ dsocr::Engine::SessionFeatures to_features(uint32_t flags) {
     f.stops = (flags & DSOCR_SESSION_STOP) != 0;
     f.penalties = (flags & DSOCR_SESSION_PENALTIES) != 0;
     f.ngram_window = (flags & DSOCR_SESSION_NGRAM_WINDOW) != 0;
+    f.guided = (flags & DSOCR_SESSION_GUIDED) != 0;
     return f;
 }
 uint32_t feature_flags(const dsocr::Engine::SessionFeatures& f) {
     return (f.per_request ? DSOCR_SESSION_PER_REQUEST : 0u) | (f.logprobs ? DSOCR_SESSION_LOGPROBS : 0u) |
            (f.logit_bias ? DSOCR_SESSION_LOGIT_BIAS : 0u) | (f.stops ? DSOCR_SESSION_STOP : 0u) |
-           (f.penalties ? DSOCR_SESSION_PENALTIES : 0u) | (f.ngram_window ? DSOCR_SESSION_NGRAM_WINDOW : 0u);
+           (f.penalties ? DSOCR_SESSION_PENALTIES : 0u) | (f.ngram_window ? DSOCR_SESSION_NGRAM_WINDOW : 0u) |
+           (f.guided ? DSOCR_SESSION_GUIDED : 0u);
 }
 
 // ---- generate: the exported forms marshal through generate_page (one page, the stream callback) or generate_pages
@@ -276,6 +309,13 @@ void write_stop_hit(const std::vector<int>& sh, size_t i, dsocr_stop_hit& out) {
     out.match_len = out.seq >= 0 ? sh[2 * i + 1] : 0;
 }
 
+// page i's pair of Engine::last_guided ({0, 0}: the page, or every page, had no automaton)
+void write_guided(const std::vector<int>& gs, size_t i, dsocr_guided_result& out) {
+    const bool have = gs.size() >= 2 * (i + 1);
+    out.state = have ? gs[2 * i] : 0;
+    out.status = have ? gs[2 * i + 1] : 0;
+}
+
 void generate_page(dsocr_engine* e, const dsocr_request* req, const dsocr_decode_params* params,
                    const dsocr_stop_set* stops, dsocr_stream_cb cb, void* user, int64_t* out_ids, size_t cap,
                    size_t* n_out, dsocr_stop_hit* hit) {
@@ -297,6 +337,8 @@ struct GenExtras {
     const dsocr_logit_bias* const* bias = nullptr;  // one constraint per request (the list or an entry may be NULL)
     const dsocr_penalties* const* pen = nullptr;    // one penalty record per request (the same)
     const dsocr_ngram_window* const* ngw = nullptr; // one windowed n-gram ban per request (the same)
+    const dsocr_guided* const* guided = nullptr;    // one token automaton per request (the same) ...
+    dsocr_guided_result* gres = nullptr;            // ... and where every request's final state and status go
     bool lp_on = false;  // per-token log-probabilities with top_k alternatives into lp[n] (NULL only with n == 0)
     size_t top_k = 0;
     dsocr_logprobs* lp = nullptr;
@@ -331,6 +373,7 @@ void generate_pages(dsocr_engine* e, size_t n, const dsocr_request* reqs, const 
         if (x.stops) rq.back().stops = to_stops(x.stops[i], vocab);
         if (x.pen) rq.back().pen = to_penalties(x.pen[i]);
         if (x.ngw) rq.back().ngw = to_ngram_window(x.ngw[i], vocab);
+        if (x.guided) rq.back().guided = to_guided(x.guided[i], (int)vocab, !params || params->ignore_eos ? -1 : (long long)params->eos_token_id);
     }
     dsocr::GenParams g = to_params(params);
     g.trace = x.logits_out;
@@ -340,6 +383,7 @@ void generate_pages(dsocr_engine* e, size_t n, const dsocr_request* reqs, const 
         write_result(r[i], results[i]);
         if (x.hits) write_stop_hit(e->impl->last_stop_hits(), i, x.hits[i]);
         if (x.lp) write_logprobs(e->impl->last_logprobs(), i, x.top_k, x.lp[i]);
+        if (x.gres) write_guided(e->impl->last_guided(), i, x.gres[i]);
     }
 }
 }  // namespace
@@ -667,6 +711,58 @@ dsocr_status dsocr_session_stage_ngram_window(dsocr_engine* e, const dsocr_ngram
         if (w.active() && !si.feat.ngram_window)
             throw std::runtime_error("EINVAL: this session was opened without DSOCR_SESSION_NGRAM_WINDOW");
         e->staged_ngw = std::move(w);
+    });
+}
+
+dsocr_status dsocr_generate_guided(dsocr_engine* e, size_t n, const dsocr_request* reqs,
+                                   const dsocr_decode_params* params, dsocr_result* results,
+                                   const dsocr_guided* const* guided, dsocr_guided_result* gres,
+                                   const dsocr_ngram_window* const* ngw, const dsocr_penalties* const* pen,
+                                   const dsocr_stop_set* const* stops, dsocr_stop_hit* hits,
+                                   const dsocr_logit_bias* const* bias, size_t top_k, dsocr_logprobs* lp) {
+    return guarded([&] {
+        if (!params) throw std::runtime_error("EINVAL: NULL argument");
+        GenExtras x;
+        x.guided = guided;
+        x.gres = gres;
+        x.ngw = ngw;
+        x.pen = pen;
+        x.stops = stops;
+        x.hits = hits;
+        x.bias = bias;
+        x.lp_on = lp != nullptr;  // (top_k without lp is refused)
+        x.top_k = top_k;
+        x.lp = lp;
+        generate_pages(e, n, reqs, params, results, x);
+    });
+}
+
+dsocr_status dsocr_guided_check(const dsocr_guided* g, int vocab, long long eos) {
+    return guarded([&] {
+        if (vocab <= 0) throw std::runtime_error("EINVAL: bad vocabulary size");
+        (void)to_guided(g, vocab, eos);
+    });
+}
+
+dsocr_status dsocr_session_stage_guided(dsocr_engine* e, const dsocr_guided* g) {
+    return guarded([&] {
+        if (!e) throw std::runtime_error("EINVAL: NULL argument");
+        e->staged_guided = dsocr::Guided();
+        dsocr::Engine::SessionInfo si;
+        if (!e->impl->session_info(&si)) throw std::runtime_error("EINVAL: no decode session is open on this engine");
+        dsocr::Guided gd = to_guided(g, e->impl->cfg().lang.vocab, -1);  // (the EOS rule: the admission's own check)
+        if (gd.active() && !si.feat.guided)
+            throw std::runtime_error("EINVAL: this session was opened without DSOCR_SESSION_GUIDED");
+        e->staged_guided = std::move(gd);
+    });
+}
+
+dsocr_status dsocr_session_guided_state(dsocr_engine* e, int slot, dsocr_guided_result* out) {
+    return guarded([&] {
+        if (!e || !out) throw std::runtime_error("EINVAL: NULL argument");
+        int st = 0, stat = 0;
+        e->impl->session_guided_state(slot, &st, &stat);
+        out->state = st; out->status = stat;
     });
 }
 
@@ -2521,6 +2617,115 @@ dsocr_status dsocr_k_out_penalty(int B, int V, int ld, float* logits, const int*
         dsocr::launch_dec_out_penalty(a, nullptr);
         check_hip(hipDeviceSynchronize(), "output penalty");
         check_hip(hipMemcpy(logits, d_logits.get(), nl * 4, hipMemcpyDeviceToHost), "hipMemcpy D2H");
+    });
+}
+
+namespace {
+// the hooks' device tables for B rows of one automaton, and its staged copy
+struct GuidedHookRows {
+    dsocr::DeviceBuffer mask, rowptr, tok, next, words, stage;
+    dsocr::GuidedTables t;
+    GuidedHookRows(int B, int V, const dsocr::Guided& g) {
+        const size_t nb = (size_t)B, E = (size_t)std::max<long>(g.edges(), 1), n = (size_t)g.n_states;
+        t.mask_ld = dsocr::guided_mask_ld(V); t.cap_states = g.n_states; t.cap_edges = (long)E;
+        mask = dsocr::DeviceBuffer(nb * n * (size_t)t.mask_ld * 4);
+        rowptr = dsocr::DeviceBuffer(nb * (n + 1) * 4);
+        tok = dsocr::DeviceBuffer(nb * E * 4);
+        next = dsocr::DeviceBuffer(nb * E * 4);
+        words = dsocr::DeviceBuffer(nb * 4 * 4);
+        check_hip(hipMemset(mask.get(), 0xff, nb * n * (size_t)t.mask_ld * 4), "hipMemset");  // (the build must clear it)
+        check_hip(hipMemset(words.get(), 0, nb * 16), "hipMemset");
+        t.mask = (uint32_t*)mask.get(); t.rowptr = (int*)rowptr.get(); t.tok = (int*)tok.get(); t.next = (int*)next.get();
+        t.state = (int*)words.get(); t.seen = t.state + nb; t.status = t.seen + nb; t.on = t.status + nb;
+        std::vector<int> h(dsocr::guided_stage_ints(g.n_states, g.edges()));
+        for (size_t i = 0; i < n; ++i) h[i] = g.accepting[i] ? 1 : 0;
+        std::memcpy(h.data() + n, g.row_ptr.data(), (n + 1) * 4);
+        if (g.edges()) {
+            std::memcpy(h.data() + 2 * n + 1, g.edge_tok.data(), (size_t)g.edges() * 4);
+            std::memcpy(h.data() + 2 * n + 1 + g.edges(), g.edge_next.data(), (size_t)g.edges() * 4);
+        }
+        stage = dsocr::DeviceBuffer(h.size() * 4);
+        check_hip(hipMemcpy(stage.get(), h.data(), h.size() * 4, hipMemcpyHostToDevice), "hipMemcpy H2D");
+    }
+    void build(int B, int V, const dsocr::Guided& g, long long eos, const int* on) {
+        for (int b = 0; b < B; ++b) {
+            dsocr::GuidedBuildArgs a;
+            a.t = t.at(b);
+            if (on[b]) {
+                a.stage = (const int*)stage.get();
+                a.n_states = g.n_states; a.start = g.start; a.V = V; a.E = g.edges();
+                a.eos = (eos >= 0 && eos < V) ? (int)eos : -1;
+            }
+            dsocr::launch_guided_build(a, nullptr);
+        }
+        check_hip(hipDeviceSynchronize(), "guided build");
+    }
+};
+}  // namespace
+
+dsocr_status dsocr_k_guided_mask(int B, int V, int ld, int row_off, float* logits, const dsocr_guided* gd, long long eos,
+                                 const int* on, const int* state, const int* done, uint32_t* mask_out) {
+    return guarded([&] {
+        if (B <= 0 || V <= 0 || ld < V || row_off < 0 || row_off > 3 || !logits || !gd || !on || !state || !done || !mask_out)
+            throw std::runtime_error("EINVAL: bad guided mask hook arguments");
+        const dsocr::Guided g = to_guided(gd, V, eos);
+        const size_t nb = (size_t)B, nl = nb * (size_t)ld;
+        for (size_t b = 0; b < nb; ++b)
+            if (state[b] < -1 || state[b] >= g.n_states) throw std::runtime_error("EINVAL: state outside -1..n_states - 1");
+        GuidedHookRows rows(B, V, g);
+        rows.build(B, V, g, eos, on);
+        dsocr::DeviceBuffer d_logits((nl + (size_t)row_off + 4) * 4), d_done(nb * 4);
+        float* lg = (float*)d_logits.get() + row_off;
+        check_hip(hipMemcpy(lg, logits, nl * 4, hipMemcpyHostToDevice), "hipMemcpy H2D");
+        check_hip(hipMemcpy(d_done.get(), done, nb * 4, hipMemcpyHostToDevice), "hipMemcpy H2D");
+        check_hip(hipMemcpy(rows.t.state, state, nb * 4, hipMemcpyHostToDevice), "hipMemcpy H2D");
+        dsocr::DecGuidedMaskArgs a;
+        a.logits = lg; a.B = B; a.V = V; a.ld = ld; a.done = (const int*)d_done.get(); a.t = rows.t;
+        dsocr::launch_dec_guided_mask(a, nullptr);
+        check_hip(hipDeviceSynchronize(), "guided mask");
+        check_hip(hipMemcpy(logits, lg, nl * 4, hipMemcpyDeviceToHost), "hipMemcpy D2H");
+        const size_t row_words = (size_t)g.n_states * (size_t)rows.t.mask_ld;
+        std::memset(mask_out, 0, row_words * 4);
+        for (size_t b = 0; b < nb; ++b)
+            if (on[b]) {
+                check_hip(hipMemcpy(mask_out, rows.t.mask + b * row_words, row_words * 4, hipMemcpyDeviceToHost), "hipMemcpy D2H");
+                break;
+            }
+    });
+}
+
+dsocr_status dsocr_k_guided_advance(int B, int steps, const dsocr_guided* gd, const int* on, const int* tokens,
+                                    const uint8_t* emit, int* steps_out) {
+    return guarded([&] {
+        if (B <= 0 || steps < 0 || !gd || !on || (steps && (!tokens || !emit || !steps_out)))
+            throw std::runtime_error("EINVAL: bad guided advance hook arguments");
+        const dsocr::Guided g = to_guided(gd, INT32_MAX, -1);
+        const size_t nb = (size_t)B, cap = (size_t)std::max(steps, 1);
+        GuidedHookRows rows(B, 32, g);  // (the bitmask is not read here: the smallest one)
+        rows.build(B, 32, g, -1, on);
+        std::vector<int> out(nb * cap, 0), out_len(nb, 0), done(nb, 0), w(nb * 4);
+        dsocr::DeviceBuffer d_out(nb * cap * 4), d_len(nb * 4), d_done(nb * 4);
+        dsocr::DecGuidedAdvanceArgs a;
+        a.B = B; a.out = (const int*)d_out.get(); a.out_cap = (long)cap; a.out_len = (const int*)d_len.get();
+        a.done = (int*)d_done.get(); a.t = rows.t;
+        for (int i = 0; i < steps; ++i) {
+            for (size_t b = 0; b < nb; ++b) {  // what a final selection kernel appends
+                if (done[b] || !emit[(size_t)i * nb + b]) continue;
+                out[b * cap + (size_t)out_len[b]] = tokens[(size_t)i * nb + b];
+                ++out_len[b];
+            }
+            check_hip(hipMemcpy(d_out.get(), out.data(), nb * cap * 4, hipMemcpyHostToDevice), "hipMemcpy H2D");
+            check_hip(hipMemcpy(d_len.get(), out_len.data(), nb * 4, hipMemcpyHostToDevice), "hipMemcpy H2D");
+            check_hip(hipMemcpy(d_done.get(), done.data(), nb * 4, hipMemcpyHostToDevice), "hipMemcpy H2D");
+            dsocr::launch_dec_guided_advance(a, nullptr);
+            check_hip(hipDeviceSynchronize(), "guided advance");
+            check_hip(hipMemcpy(done.data(), d_done.get(), nb * 4, hipMemcpyDeviceToHost), "hipMemcpy D2H");
+            check_hip(hipMemcpy(w.data(), rows.words.get(), nb * 16, hipMemcpyDeviceToHost), "hipMemcpy D2H");
+            for (size_t b = 0; b < nb; ++b) {
+                int* o = steps_out + ((size_t)i * nb + b) * 4;
+                o[0] = w[b]; o[1] = w[nb + b]; o[2] = w[2 * nb + b]; o[3] = done[b];
+            }
+        }
     });
 }
 

@@ -176,6 +176,9 @@ struct Engine::Session {
         bool biased = false;  // the slot's device flag (rows_.bias_on): its request carried a constraint
         bool penalised = false;  // the slot's device record (rows_.pen) is on
         bool windowed = false;  // the slot's windowed-ban record (rows_.ngw) is on
+        bool guided = false;    // the slot's automaton flag (rows_.g_on), with the sizes a move copies
+        int g_states = 0;
+        long g_edges = 0;
         size_t max_new = 0;
         int kv_pos = 0;    // the device kv_pos of the slot: prompt + steps replayed since its admission
         int reported = 0;  // tokens the polls have handed out
@@ -1755,6 +1758,7 @@ void Engine::decode_head(int B, DecSampleArgs& sa, const SampleArgs& pen, bool s
     if (screened && rows_.bias && !sess_) throw std::runtime_error("EINTERNAL: a logit bias needs the exact head");
     if (screened && rows_.pen && !sess_) throw std::runtime_error("EINTERNAL: penalties need the exact head");
     if (screened && window >= 0) throw std::runtime_error("EINTERNAL: a windowed n-gram ban needs the exact head");
+    if (screened && rows_.g_on && !sess_) throw std::runtime_error("EINTERNAL: a token automaton needs the exact head");
     if (screened) {
         // screened selection: int8 lm_head intervals + running threshold, exact rescoring of the
         // few kept rows — the exact path's token from half the lm_head bytes
@@ -1783,6 +1787,7 @@ void Engine::decode_head(int B, DecSampleArgs& sa, const SampleArgs& pen, bool s
     launch_dec_gemv(g, st);
     if (trace_) launch_trace_logits(sa.logits, B, L.vocab, sa.ld, sa.out_len, sa.done, trace_, trace_steps_, st);
     if (rows_.bias) launch_dec_logit_bias(bias_args(sa, 0), st);  // l' = l + b: what everything below reads
+    if (rows_.g_on) launch_dec_guided_mask(guided_mask_args(sa, 0), st);  // -inf wherever the row's state has no edge
     if (lp) launch_dec_lp_partial(*lp, st);
     launch_rep_penalty(pen, st);
     if (rows_.pen) launch_dec_out_penalty(penalty_args(sa, 0), st);  // frequency / presence, per row
@@ -1794,6 +1799,7 @@ void Engine::decode_head(int B, DecSampleArgs& sa, const SampleArgs& pen, bool s
     } else {
         launch_dec_sample(sa, st);
     }
+    if (rows_.g_on) launch_dec_guided_advance(guided_advance_args(sa, 0), st);  // the appended token's edge
     if (stops) stop_match(sa, 0);
     if (lp) launch_dec_lp_final(*lp, st);
 }
@@ -1907,6 +1913,22 @@ void Engine::reserve_decode_rows(const DecodeRowsSpec& spec) {
         r.ngw = reinterpret_cast<NgramWindowRec*>(ws("s_ngw", sizeof(NgramWindowRec) * S));
         const std::vector<NgramWindowRec> off((size_t)S);
         upload_to(r.ngw, "s_ngwstage", off);
+    }
+    if (spec.guided) {  // (a row's tables are written by launch_guided_build, which sets its flag)
+        const size_t R = (size_t)S;
+        r.g_states = std::min(std::max(spec.guided_states, 1), GUIDED_MAX_STATES);
+        r.g_edges = std::min(std::max<long>(spec.guided_edges, 1), GUIDED_MAX_EDGES);
+        r.g_mask_ld = guided_mask_ld(V);
+        r.g_mask = reinterpret_cast<uint32_t*>(wsi("s_gmask", R * r.g_states * r.g_mask_ld));
+        r.g_rowptr = wsi("s_growptr", R * (r.g_states + 1));
+        r.g_tok = wsi("s_gtok", R * r.g_edges);
+        r.g_next = wsi("s_gnext", R * r.g_edges);
+        r.g_state = ints("s_gstate", S, true);
+        r.g_seen = ints("s_gseen", S, true);
+        r.g_status = ints("s_gstatus", S, true);
+        r.g_on = ints("s_gon", S, true);
+        r.g_stage_cap = std::max<size_t>(spec.guided_stage, 1);
+        r.g_stage = wsi("s_gstage", r.g_stage_cap);
     }
 }
 
@@ -2086,6 +2108,75 @@ void Engine::build_logit_bias(const LogitBias& lb, int row, size_t stage_off) {
     launch_logit_bias_build(a, stream_);
 }
 
+DecGuidedMaskArgs Engine::guided_mask_args(const DecSampleArgs& sa, int row0) {
+    DecGuidedMaskArgs a;
+    a.logits = const_cast<float*>(sa.logits); a.B = sa.B; a.V = sa.V; a.ld = sa.ld;
+    a.done = sa.done;
+    a.t = rows_.guided_tables().at(row0);
+    return a;
+}
+
+DecGuidedAdvanceArgs Engine::guided_advance_args(const DecSampleArgs& sa, int row0) {
+    DecGuidedAdvanceArgs a;
+    a.B = sa.B; a.out = sa.out_ids; a.out_cap = sa.out_cap; a.out_len = sa.out_len; a.done = sa.done;
+    a.t = rows_.guided_tables().at(row0);
+    return a;
+}
+
+void validate_guided(const Guided& g, int vocab, long eos) {
+    if (!g.active() && g.accepting.empty() && g.row_ptr.empty() && g.edge_tok.empty() && g.edge_next.empty()) return;
+    const int n = g.n_states;
+    if (n < 1 || n > GUIDED_MAX_STATES)
+        throw std::runtime_error("EINVAL: token automaton: n_states must be 1.." + std::to_string(GUIDED_MAX_STATES));
+    if (g.accepting.size() != (size_t)n || g.row_ptr.size() != (size_t)n + 1)
+        throw std::runtime_error("EINVAL: token automaton: accepting has n_states entries and row_ptr n_states + 1");
+    if (g.row_ptr[0] != 0) throw std::runtime_error("EINVAL: token automaton: row_ptr must start at 0");
+    for (int s = 0; s < n; ++s)
+        if (g.row_ptr[s + 1] < g.row_ptr[s]) throw std::runtime_error("EINVAL: token automaton: row_ptr must not decrease");
+    const long E = g.row_ptr[n];
+    if (E > GUIDED_MAX_EDGES)
+        throw std::runtime_error("EINVAL: token automaton: more than " + std::to_string(GUIDED_MAX_EDGES) + " edges");
+    if (g.edge_tok.size() != (size_t)E || g.edge_next.size() != (size_t)E)
+        throw std::runtime_error("EINVAL: token automaton: row_ptr must end at the number of edges");
+    for (int s = 0; s < n; ++s)
+        for (int e = g.row_ptr[s]; e < g.row_ptr[s + 1]; ++e) {
+            const int t = g.edge_tok[e];
+            if (t < 0 || t >= vocab) throw std::runtime_error("EINVAL: token automaton: token id " + std::to_string(t) + " outside the vocabulary");
+            if ((long)t == eos) throw std::runtime_error("EINVAL: token automaton: an edge on the EOS id (mark the state accepting instead)");
+            if (e > g.row_ptr[s] && g.edge_tok[e - 1] >= t)
+                throw std::runtime_error("EINVAL: token automaton: token ids must ascend strictly within a state");
+            if (g.edge_next[e] < 0 || g.edge_next[e] >= n) throw std::runtime_error("EINVAL: token automaton: edge_next outside [0, n_states)");
+        }
+    if (g.start < 0 || g.start >= n) throw std::runtime_error("EINVAL: token automaton: start outside [0, n_states)");
+    if (g.row_ptr[g.start] == g.row_ptr[g.start + 1]) throw std::runtime_error("EINVAL: token automaton: the start state is terminal");
+}
+
+// One row's automaton over PCIe ([accepting | row_ptr | edge_tok | edge_next], pinned staging under "s_gstage"),
+// then the fill + scatter on the stream.  The caller synchronises before the staging region is reused
+void Engine::build_guided(const Guided& g, int row, size_t stage_off, long eos) {
+    const DecodeRows& r = rows_;
+    if (!r.g_on) throw std::runtime_error("EINTERNAL: no token automaton rows are reserved");
+    GuidedBuildArgs a;
+    a.t = r.guided_tables().at(row);
+    if (g.active()) {
+        const size_t n = (size_t)g.n_states, E = (size_t)g.edges(), ints = guided_stage_ints(g.n_states, g.edges());
+        if (stage_off + ints > r.g_stage_cap) throw std::runtime_error("EINTERNAL: token automaton staging buffer too small");
+        if (g.n_states > r.g_states || g.edges() > r.g_edges) throw std::runtime_error("EINTERNAL: token automaton rows too small");
+        int* h = (int*)pinned("s_gstage", r.g_stage_cap * sizeof(int)) + stage_off;
+        for (size_t i = 0; i < n; ++i) h[i] = g.accepting[i] ? 1 : 0;
+        std::memcpy(h + n, g.row_ptr.data(), (n + 1) * sizeof(int));
+        if (E) {
+            std::memcpy(h + 2 * n + 1, g.edge_tok.data(), E * sizeof(int));
+            std::memcpy(h + 2 * n + 1 + E, g.edge_next.data(), E * sizeof(int));
+        }
+        HIP_CHECK(hipMemcpyAsync(r.g_stage + stage_off, h, ints * sizeof(int), hipMemcpyHostToDevice, stream_));
+        a.stage = r.g_stage + stage_off;
+        a.n_states = g.n_states; a.start = g.start; a.V = cfg_.lang.vocab; a.E = g.edges();
+        a.eos = (eos >= 0 && eos < cfg_.lang.vocab) ? (int)eos : -1;
+    }
+    launch_guided_build(a, stream_);
+}
+
 DecStopArgs Engine::stop_args(const DecSampleArgs& sa, int row0) {
     const DecodeRows& r = rows_;
     DecStopArgs a;
@@ -2239,6 +2330,21 @@ std::vector<std::vector<int64_t>> Engine::generate(const std::vector<GenRequest>
         const char* e = getenv("DSOCR_PERSIST");
         if (e && atoi(e) != 0)
             throw std::runtime_error("EINVAL: a windowed n-gram ban does not combine with the persistent decode step (DSOCR_PERSIST)");
+    }
+    // a token automaton: the same
+    last_guided_.clear();
+    bool any_guided = false;
+    for (const GenRequest& rq : reqs) {
+        validate_guided(rq.guided, cfg_.lang.vocab, p.ignore_eos ? -1 : p.eos);
+        any_guided = any_guided || rq.guided.active();
+    }
+    // (no entry point can pass a logits trace together with an automaton: the trace form takes none)
+    if (any_guided && !p.use_cache)
+        throw std::runtime_error("EINVAL: a token automaton needs the K/V cache (use_cache = 1)");
+    if (any_guided) {
+        const char* e = getenv("DSOCR_PERSIST");
+        if (e && atoi(e) != 0)
+            throw std::runtime_error("EINVAL: a token automaton does not combine with the persistent decode step (DSOCR_PERSIST)");
     }
     if (reqs.empty() || p.max_new == 0) return std::vector<std::vector<int64_t>>(reqs.size());
     ensure_small(std::max((int)reqs.size(), 64));
@@ -2445,8 +2551,17 @@ void Engine::reset_decode_state(GenState& g) {
     for (const GenRequest& rq : g.reqs) spec.penalties = spec.penalties || rq.pen.active();
     // a page with a windowed n-gram ban: the exact head too, with one record per page
     for (const GenRequest& rq : g.reqs) spec.ngram_window = spec.ngram_window || rq.ngw.active();
+    // a guided page: the exact head too, with tables sized for the call's largest automaton and one staging region
+    // per page
+    for (const GenRequest& rq : g.reqs)
+        if (rq.guided.active()) {
+            if (!spec.guided) { spec.guided = true; spec.guided_states = 1; spec.guided_edges = 1; }
+            spec.guided_states = std::max(spec.guided_states, rq.guided.n_states);
+            spec.guided_edges = std::max(spec.guided_edges, rq.guided.edges());
+            spec.guided_stage += guided_stage_ints(rq.guided.n_states, rq.guided.edges());
+        }
     spec.ban = !p.do_sample && !p.trace && p.lp_k < 0 && !spec.bias && !spec.penalties && !spec.ngram_window &&
-               screen_applies(B, p.rep_penalty);
+               !spec.guided && screen_applies(B, p.rep_penalty);
     // (the side row: dec_lp_final takes an emitted token's raw logit from it wherever a penalty may have rewritten
     // logits[tok]: the repetition penalty at the context ids, the frequency / presence penalty at the generated ones,
     // which the context row holds as well)
@@ -2600,6 +2715,14 @@ void Engine::init_sampling(GenState& g) {
         }
         launch_dec_logit_bias(bias_args(sa, 0), st);
     }
+    if (r.g_on) {  // every page's tables from its automaton, then the start state's mask on the prefill's logits
+        size_t off = 0;
+        for (int b = 0; b < B; ++b) {
+            build_guided(g.reqs[b].guided, b, off, p.ignore_eos ? -1 : p.eos);
+            if (g.reqs[b].guided.active()) off += guided_stage_ints(g.reqs[b].guided.n_states, g.reqs[b].guided.edges());
+        }
+        launch_dec_guided_mask(guided_mask_args(sa, 0), st);
+    }
     const DecLpArgs lp = p.lp_k >= 0 ? lp_args(sa, 0) : DecLpArgs();
     if (p.lp_k >= 0) launch_dec_lp_partial(lp, st);
     // the fused selection kernel advances the KV position; after the prefill the first
@@ -2623,6 +2746,7 @@ void Engine::init_sampling(GenState& g) {
     HIP_CHECK(hipMemcpyAsync(r.kv_pos, pm1.data(), B * 4, hipMemcpyHostToDevice, st));
     HIP_CHECK(hipMemcpyAsync(r.kv_len, lm1.data(), B * 4, hipMemcpyHostToDevice, st));
     launch_dec_sample(sa, st);
+    if (r.g_on) launch_dec_guided_advance(guided_advance_args(sa, 0), st);  // the prefill's own selection advances too
     if (r.stop_tab) {  // every page's table from its stop set, then the match on the prefill's own selection
         for (int b = 0; b < B; ++b) build_stop_table(g.reqs[b].stops, b, b);
         stop_match(sa, 0);
@@ -2812,12 +2936,14 @@ void Engine::decode_cached(GenState& g) {
     HIP_CHECK(hipEventRecord(g.ev[4], st));
     // stop sets: a stop ends a page under ignore_eos too, so the done flags are polled at the usual cadence, and once
     // before the first step (a stop may have fired on the prefill's selection)
-    const bool stops = rows_.stop_tab != nullptr;
+    // (an automaton ends its page the same way: complete or violated)
+    const bool stop_rows = rows_.stop_tab != nullptr;
+    const bool stops = stop_rows || rows_.g_on != nullptr;
     const bool finished = stops && poll(g);
     for (size_t i = 1; i < p.max_new && !finished; ++i) {
         if (gexec) gexec.launch(st);
         else step_body(g);
-        if (gexec && stops) ++stop_launches_;
+        if (gexec && stop_rows) ++stop_launches_;
         if (span_rec_ && (span_mode_ & SPAN_EVENTS)) read_span_events(i);
         if (pk_timed) {  // the persistent launch's dispatch duration (events recorded around it in the step)
             HIP_CHECK(hipEventSynchronize(persist_ev_[1]));
@@ -2887,6 +3013,17 @@ std::vector<std::vector<int64_t>> Engine::collect_outputs(GenState& g) {
         last_stop_hits_.resize((size_t)B * 2);
         HIP_CHECK(hipMemcpy(last_stop_hits_.data(), rows_.stop_hit, (size_t)B * 2 * 4, hipMemcpyDeviceToHost));
     }
+    if (rows_.g_on) {
+        std::vector<int> st((size_t)B), stat((size_t)B);
+        HIP_CHECK(hipMemcpy(st.data(), rows_.g_state, (size_t)B * 4, hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(stat.data(), rows_.g_status, (size_t)B * 4, hipMemcpyDeviceToHost));
+        last_guided_.resize((size_t)B * 2);
+        for (int b = 0; b < B; ++b) {  // (a page without an automaton: its words were never written past the zero fill)
+            const bool on = g.reqs[b].guided.active();
+            last_guided_[2 * b] = on ? st[b] : 0;
+            last_guided_[2 * b + 1] = on ? stat[b] : 0;
+        }
+    }
     last_B_ = B;
     last_Lmax_ = rows_.Lcap;
     return out;
@@ -2953,6 +3090,10 @@ void Engine::session_open(int S, int max_context, const GenParams& p, const Sess
     spec.stops = feat.stops;  // every slot's table, and one admission's list at a time
     spec.penalties = feat.penalties;  // every slot's record
     spec.ngram_window = feat.ngram_window;  // the same
+    if (feat.guided) {  // every slot's tables at the caps, and one admission's automaton at a time
+        spec.guided = true;
+        spec.guided_stage = guided_stage_ints(GUIDED_MAX_STATES, GUIDED_MAX_EDGES);
+    }
     if (feat.logprobs) {  // (the raw logits at the context ids too where a penalty can apply)
         spec.lp_k = LP_MAX_TOP;
         spec.lp_side = feat.per_request || rep_penalty_active(p.rep_penalty) || feat.penalties;
@@ -3031,6 +3172,9 @@ void Engine::session_admit_checks(const Session& s, const GenRequest& rq, const 
     validate_ngram_window(rq.ngw, V);
     if (rq.ngw.active() && !s.feat.ngram_window)
         throw std::runtime_error("EINVAL: this session was opened without DSOCR_SESSION_NGRAM_WINDOW");
+    validate_guided(rq.guided, V, rp.ignore_eos ? -1 : rp.eos);
+    if (rq.guided.active() && !s.feat.guided)
+        throw std::runtime_error("EINVAL: this session was opened without DSOCR_SESSION_GUIDED");
     if (s.pending) throw std::runtime_error("EINVAL: a chunked admission is pending (advance it to the end or cancel it)");
     if (s.n >= s.S) throw std::runtime_error("EINVAL: every session slot is in use (retire one first)");
     const size_t P = rq.ids.size();
@@ -3126,6 +3270,10 @@ int Engine::session_admit_tail(Session& s, const GenRequest& rq, const GenParams
         build_logit_bias(rq.bias, slot, 0);
         launch_dec_logit_bias(bias_args(sa, slot), st);
     }
+    if (s.feat.guided) {  // the slot's tables (none: the flag alone is cleared), then the start state's mask
+        build_guided(rq.guided, slot, 0, rp.ignore_eos ? -1 : rp.eos);
+        if (rq.guided.active()) launch_dec_guided_mask(guided_mask_args(sa, slot), st);
+    }
     if (s.feat.logprobs) launch_dec_lp_partial(lp, st);
     launch_rep_penalty(pen, st);
     if (s.feat.penalties) {  // the slot's record (none: an off record), then the penalty on the prefill's logits
@@ -3142,6 +3290,7 @@ int Engine::session_admit_tail(Session& s, const GenRequest& rq, const GenParams
         }
     }
     launch_dec_sample(sa, st);  // the first token, its embedding into the slot's s_x row, the ban list
+    if (rq.guided.active()) launch_dec_guided_advance(guided_advance_args(sa, slot), st);
     if (s.feat.stops) {  // the slot's table (none: the count alone is cleared), then the match on this first selection
         build_stop_table(rq.stops, slot, 0);
         if (rq.stops.active()) stop_match(sa, slot);
@@ -3156,6 +3305,9 @@ int Engine::session_admit_tail(Session& s, const GenRequest& rq, const GenParams
     sl.biased = rq.bias.active();
     sl.penalised = rq.pen.active();
     sl.windowed = windowed;
+    sl.guided = rq.guided.active();
+    sl.g_states = rq.guided.n_states;
+    sl.g_edges = rq.guided.edges();
     sl.stopped = rq.stops.active();
     sl.ids = rq.ids;
     sl.mask = rq.mask.empty() ? std::vector<uint8_t>(P, 0) : rq.mask;
@@ -3387,7 +3539,7 @@ void Engine::session_step_body(Session& s, bool screened, bool stops, bool windo
 bool Engine::session_head_screened(const Session& s) const {
     if (s.feat.logprobs) return false;  // the screened head never forms the logits
     for (int b = 0; b < s.n; ++b)
-        if (s.slot[b].biased || s.slot[b].penalised || s.slot[b].windowed) return false;  // ... which a constraint, a penalty or a windowed ban acts on
+        if (s.slot[b].biased || s.slot[b].penalised || s.slot[b].windowed || s.slot[b].guided) return false;  // ... which a constraint, a penalty, a windowed ban or an automaton acts on
     if (!s.feat.per_request) return s.screened;
     for (int b = 0; b < s.n; ++b)
         if (s.slot[b].rp.do_sample || s.slot[b].rp.rep_penalty != 1.0f) return false;
@@ -3513,9 +3665,27 @@ void Engine::session_slot_move(Session& s, int src, int dst, int rows_bound) {
         HIP_CHECK(hipMemcpyAsync(r.pen + dst, r.pen + src, sizeof(PenaltyRec), hipMemcpyDeviceToDevice, stream_));
     if (s.feat.ngram_window)  // the same: 144 bytes
         HIP_CHECK(hipMemcpyAsync(r.ngw + dst, r.ngw + src, sizeof(NgramWindowRec), hipMemcpyDeviceToDevice, stream_));
+    // the automaton travels with its page: the used part of its tables (a page without one: the flag and scalars alone)
+    if (s.feat.guided)
+        launch_guided_slot_move(r.guided_tables(), src, dst, s.slot[src].guided ? s.slot[src].g_states : 0,
+                                s.slot[src].guided ? s.slot[src].g_edges : 0, stream_);
     // the stop set travels with its page: a launch of its own (a page without one: the count, seen and hit alone)
     if (s.feat.stops) launch_stop_slot_move(r.stop_tab, r.stop_n, r.stop_seen, r.stop_hit, src, dst, stream_);
     s.slot[dst] = s.slot[src];
+}
+
+void Engine::session_guided_state(int slot, int* state, int* status) {
+    Session& s = open_session();
+    if (!s.feat.guided) throw std::runtime_error("EINVAL: this session was opened without DSOCR_SESSION_GUIDED");
+    if (slot < 0 || slot >= s.n) throw std::runtime_error("EINVAL: slot " + std::to_string(slot) + " is not active");
+    int st = 0, stat = 0;
+    if (s.slot[slot].guided) {
+        HIP_CHECK(hipStreamSynchronize(stream_));
+        HIP_CHECK(hipMemcpy(&st, rows_.g_state + slot, 4, hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(&stat, rows_.g_status + slot, 4, hipMemcpyDeviceToHost));
+    }
+    if (state) *state = st;
+    if (status) *status = stat;
 }
 
 void Engine::session_stop_hit(int slot, int* seq, int* match_len) {

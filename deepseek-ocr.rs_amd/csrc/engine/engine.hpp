@@ -171,11 +171,27 @@ struct NgramWindow {
 // EINVAL: on with w < 1; more than NGRAM_MAX_WHITELIST ids; an id outside [0, vocab)
 void validate_ngram_window(const NgramWindow& nw, int vocab);
 
+// One request's token automaton: n_states states, a start state, a byte per state (accepting: the
+// EOS id is kept there) and the edges in CSR form, ids strictly ascending within a state.  A state without an
+// outgoing edge is terminal: reaching it completes the page.  Off: n_states == 0.
+struct Guided {
+    int n_states = 0, start = 0;
+    std::vector<uint8_t> accepting;
+    std::vector<int> row_ptr, edge_tok, edge_next;
+    bool active() const { return n_states > 0; }
+    long edges() const { return (long)edge_tok.size(); }
+};
+// EINVAL: n_states outside [1, GUIDED_MAX_STATES]; more than GUIDED_MAX_EDGES edges; row_ptr not non-decreasing from
+// 0 to E; a token outside [0, vocab) or equal to eos; tokens not strictly ascending within a state; edge_next or
+// start outside [0, n_states); a terminal start.  (A record that is off passes.)
+void validate_guided(const Guided& g, int vocab, long eos);
+
 struct GenRequest {
     LogitBias bias;
     StopSet stops;
     Penalties pen;
     NgramWindow ngw;
+    Guided guided;
     std::vector<int> ids;
     std::vector<uint8_t> mask;
     const PagePixels* page = nullptr;
@@ -239,6 +255,21 @@ struct DecodeRows {
     PenaltyRec* pen = nullptr;
     // windowed n-gram ban records (spec.ngram_window): one per row, every one starts off
     NgramWindowRec* ngw = nullptr;
+    // guided decoding (spec.guided): every row's bitmask [g_states][g_mask_ld] and CSR (g_states + 1 row pointers,
+    // g_edges edges), the state / seen / status / flag words, and the staging buffer automata are uploaded to
+    uint32_t* g_mask = nullptr;
+    long g_mask_ld = 0, g_edges = 0;
+    int g_states = 0;
+    int *g_rowptr = nullptr, *g_tok = nullptr, *g_next = nullptr, *g_state = nullptr, *g_seen = nullptr,
+        *g_status = nullptr, *g_on = nullptr, *g_stage = nullptr;
+    size_t g_stage_cap = 0;
+    GuidedTables guided_tables() const {
+        GuidedTables t;
+        t.mask = g_mask; t.mask_ld = g_mask_ld; t.cap_states = g_states; t.cap_edges = g_edges;
+        t.rowptr = g_rowptr; t.tok = g_tok; t.next = g_next;
+        t.state = g_state; t.seen = g_seen; t.status = g_status; t.on = g_on;
+        return t;
+    }
 };
 // What a caller of Engine::reserve_decode_rows asks for
 struct DecodeRowsSpec {
@@ -255,6 +286,10 @@ struct DecodeRowsSpec {
     int stop_stage_rows = 1;   // ... and staging for this many lists at a time
     bool penalties = false;    // PenaltyRec rows (every record starts off)
     bool ngram_window = false; // NgramWindowRec rows (every record starts off)
+    bool guided = false;       // token-automaton rows (every flag starts 0) of guided_states states and guided_edges
+    int guided_states = GUIDED_MAX_STATES;  // edges each ...
+    long guided_edges = GUIDED_MAX_EDGES;
+    size_t guided_stage = 0;   // ... and a staging buffer of this many ints
 };
 typedef void (*TokenCb)(size_t, const int64_t*, void*);
 // rand_core seed_from_u64 for rand 0.8.5 StdRng, in the layout sampling.hip reads (RNG_WORDS words)
@@ -288,6 +323,8 @@ class Engine {
     const LogprobRows& last_logprobs() const { return last_lp_; }
     // the stop hits of the last generate: {seq, match_len} per page ({-1, 0}: no stop fired; empty: no page had stops)
     const std::vector<int>& last_stop_hits() const { return last_stop_hits_; }
+    // the last generate's [state, status] per request (empty when no request carried an automaton)
+    const std::vector<int>& last_guided() const { return last_guided_; }
     // dec_stop_match launches of this engine so far (issued or replayed inside a step graph)
     size_t stop_launches() const { return stop_launches_; }
     // Replays the decode MoE grouped GEMV (routed experts, gate/up + down) of every MoE
@@ -357,6 +394,9 @@ class Engine {
         // every slot keeps an NgramWindowRec; an admission may carry a windowed ban (GenRequest::ngw), and a burst
         // runs the exact head with the window launch iff an active slot carries a record that is on
         bool ngram_window = false;
+        // every slot keeps the tables of a token automaton; an admission may carry one
+        // (GenRequest::guided), and a burst runs the exact head iff an active slot carries one
+        bool guided = false;
     };
     struct SessionInfo {
         int slots = 0, active = 0, max_context = 0, out_cap = 0, kv_cap = 0, burst_cap = 0;
@@ -377,6 +417,8 @@ class Engine {
     void session_open(int slots, int max_context, const GenParams& p, const SessionFeatures& feat);
     // {seq, match_len} of a live slot ({-1, 0}: no stop fired within its max_new_tokens)
     void session_stop_hit(int slot, int* seq, int* match_len);
+    // the automaton state and status (0 running, 1 complete, 2 violated) of an active slot; both 0 without an automaton
+    void session_guided_state(int slot, int* state, int* status);
     // entries [first, first + count) of a live slot, trimmed to top_k <= LP_MAX_TOP alternatives ([count][top_k])
     void session_logprobs(int slot, size_t first, size_t count, int top_k, float* token_lp, int64_t* top_id, float* top_lp);
     int session_admit(const GenRequest& rq, size_t max_new, bool seed_set, uint64_t seed);
@@ -476,6 +518,12 @@ class Engine {
     // n-gram size the launch applies, with an unbounded window, to rows whose record is off (0: such rows are skipped)
     DecNgramWindowArgs ngram_window_args(const DecSampleArgs& sa, int row0, int plain);
     void write_ngram_windows(const NgramWindow* const* nw, int row0, int n);
+    // the automaton rows of the same pages (only where rows_.g_on is set): one row's tables from a request's automaton
+    // (staged at stage_off ints of "s_gstage"; the caller synchronises before the region is reused), the mask and the
+    // advance launches
+    void build_guided(const Guided& g, int row, size_t stage_off, long eos);
+    DecGuidedMaskArgs guided_mask_args(const DecSampleArgs& sa, int row0);
+    DecGuidedAdvanceArgs guided_advance_args(const DecSampleArgs& sa, int row0);
     // the stop rows of the same pages (only where rows_.stop_tab is set), and the match launch on them (counted)
     DecStopArgs stop_args(const DecSampleArgs& sa, int row0);
     void stop_match(const DecSampleArgs& sa, int row0);
@@ -583,6 +631,7 @@ class Engine {
     size_t chunk_attn_launches_ = 0;
     size_t stop_launches_ = 0;
     std::vector<int> last_stop_hits_;
+    std::vector<int> last_guided_;
     double flops_acc_ = 0;  // FLOPs issued by linear() / attention since the last stage mark
     std::vector<int> prefill_lens_;  // rows per page of the prefill being issued
     int last_B_ = 0;

@@ -750,6 +750,64 @@ struct StopBuildArgs {
 void launch_stop_table_build(const StopBuildArgs& a, hipStream_t s);
 // A page's stop state from row src to row dst of the four arrays (the compaction of a session; src != dst)
 void launch_stop_slot_move(int* tab, int* n_seq, int* seen, int* hit, int src, int dst, hipStream_t s);
+// Guided decoding: a per-row token automaton (decode_guided.hip).  Per row: a dense bitmask
+// [cap_states][mask_ld] of u32 words (bit t of state s: id t is kept in state s; the EOS bit iff s is accepting), the
+// automaton's CSR (row_ptr [cap_states + 1], edge_tok / edge_next [cap_edges], ids ascending within a state) and the
+// words state (-1: violated), seen (the out_len already examined), status (0 running, 1 complete, 2 violated), on.
+constexpr int GUIDED_MAX_STATES = 1024;
+constexpr long GUIDED_MAX_EDGES = 1L << 20;
+inline long guided_mask_ld(int V) { return (((long)V + 31) / 32 + 3) / 4 * 4; }  // every state's words 16-byte aligned
+// an admission's staged automaton: [accepting[n] | row_ptr[n + 1] | edge_tok[E] | edge_next[E]], all int32
+inline size_t guided_stage_ints(int n_states, long E) { return (size_t)n_states * 2 + 1 + (size_t)E * 2; }
+struct GuidedTables {
+    uint32_t* mask = nullptr; long mask_ld = 0;  // [rows][cap_states][mask_ld], 16-byte aligned
+    int cap_states = 0; long cap_edges = 0;
+    int *rowptr = nullptr, *tok = nullptr, *next = nullptr;  // [rows][cap_states + 1], [rows][cap_edges] twice
+    int *state = nullptr, *seen = nullptr, *status = nullptr, *on = nullptr;  // [rows]
+    // the same tables from row `r` on
+    GuidedTables at(int r) const {
+        GuidedTables t = *this;
+        t.mask += (size_t)r * cap_states * mask_ld; t.rowptr += (size_t)r * (cap_states + 1);
+        t.tok += (size_t)r * cap_edges; t.next += (size_t)r * cap_edges;
+        t.state += r; t.seen += r; t.status += r; t.on += r;
+        return t;
+    }
+};
+// Row 0 of `t` from the staged automaton (device pointer, guided_stage_ints(n_states, E) ints, checked on the host):
+// a fill launch (the bitmask's used part zeroed but for the EOS bits, the CSR copied, state = start, seen = status
+// = 0, on = 1) and a scatter launch over the edges.  stage == nullptr: "no automaton" (on = 0, nothing else written).
+// eos outside [0, V): no EOS bit.  Outside the step graph.
+struct GuidedBuildArgs {
+    GuidedTables t;
+    const int* stage = nullptr;
+    int n_states = 0, start = 0, V = 0, eos = -1;
+    long E = 0;
+};
+void launch_guided_build(const GuidedBuildArgs& a, hipStream_t s);
+// The mask of the step: grid (chunks of 2048 of V, B), after launch_dec_logit_bias and before launch_dec_lp_partial.
+// Every id whose bit is clear in the row's state gets l = -inf; nothing else is written and no logit is read.  A row
+// with on == 0, state < 0 or done != 0 is neither read further nor written; columns [V, ld) are never written.
+struct DecGuidedMaskArgs {
+    float* logits = nullptr; int B = 0, V = 0; long ld = 0;
+    const int* done = nullptr;  // [B]
+    GuidedTables t;             // from the first of the B rows on
+};
+void launch_dec_guided_mask(const DecGuidedMaskArgs& a, hipStream_t s);
+// The advance of the step: one wave per row, right after the final selection kernel and before the stop match.  A row
+// with on == 0, state < 0 or out_len == seen is not written.  Else t = out[out_len - 1] is searched among the state's
+// edges: found, state = edge_next (terminal: done = 1, status = 1); not found, state = -1, status = 2, done = 1;
+// seen = out_len either way.
+struct DecGuidedAdvanceArgs {
+    int B = 0;
+    const int* out = nullptr; long out_cap = 0;  // [B][out_cap]
+    const int* out_len = nullptr;                // [B]
+    int* done = nullptr;                         // [B]
+    GuidedTables t;
+};
+void launch_dec_guided_advance(const DecGuidedAdvanceArgs& a, hipStream_t s);
+// A page's automaton from row src to row dst (a session's compaction; src != dst): the flag and the scalars, and,
+// where the flag is set, n_states mask rows, n_states + 1 row pointers and E edges (the source's, known to the host)
+void launch_guided_slot_move(const GuidedTables& t, int src, int dst, int n_states, long E, hipStream_t s);
 // Decode sessions (session.hip).  One page's decode state from slot src to slot dst (src != dst) in one launch:
 // K / V rows [0, min(kv_len[src], rows_bound)) of every layer and kv head (f32 caches [layers][slots][kv_heads]
 // [cap_rows][hd] with the given strides in floats; 16-byte nontemporal loads and stores, hd % 4 == 0), the whole

@@ -110,6 +110,18 @@ class NgramWindowC(C.Structure):
                 ("n_whitelist", C.c_size_t)]
 
 
+class GuidedC(C.Structure):
+    """dsocr_guided: one request's token automaton."""
+    _fields_ = [("n_states", C.c_int32), ("start", C.c_int32), ("accepting", C.POINTER(C.c_uint8)),
+                ("row_ptr", C.POINTER(C.c_int32)), ("edge_tok", C.POINTER(C.c_int32)),
+                ("edge_next", C.POINTER(C.c_int32))]
+
+
+class GuidedResultC(C.Structure):
+    """dsocr_guided_result: the automaton state and status (0 running, 1 complete, 2 violated) of a page."""
+    _fields_ = [("state", C.c_int32), ("status", C.c_int32)]
+
+
 class RowParamsC(C.Structure):
     """dsocr_row_params: one row of dsocr_k_select_rows."""
     _fields_ = [("do_sample", C.c_int), ("temperature", C.c_double), ("top_p", C.c_double), ("top_k", C.c_size_t),
@@ -135,6 +147,7 @@ SESSION_STOP = 8         # DSOCR_SESSION_STOP
 SESSION_PENALTIES = 16   # DSOCR_SESSION_PENALTIES
 SESSION_NGRAM_WINDOW = 32  # DSOCR_SESSION_NGRAM_WINDOW
 MAX_NGRAM_WHITELIST = 32   # DSOCR_MAX_NGRAM_WHITELIST
+SESSION_GUIDED = 64        # DSOCR_SESSION_GUIDED
 MAX_STOP_SEQS = 16       # DSOCR_MAX_STOP_SEQS
 MAX_STOP_LEN = 32        # DSOCR_MAX_STOP_LEN
 SESSION_ADMIT_PENDING = 0x100  # DSOCR_SESSION_ADMIT_PENDING (dsocr_session_info flags while an admission is pending)
@@ -186,6 +199,8 @@ EXPORTS = [
     "dsocr_k_sample_stoch_min_p",
     "dsocr_ngram_window_check", "dsocr_generate_ngram_window", "dsocr_session_stage_ngram_window",
     "dsocr_k_ngram_window",
+    "dsocr_guided_check", "dsocr_generate_guided", "dsocr_session_stage_guided", "dsocr_session_guided_state",
+    "dsocr_k_guided_mask", "dsocr_k_guided_advance",
 ]
 
 # model variants behind the deepseek engine (dsocr_engine_variant)
@@ -358,6 +373,16 @@ def lib():
                                               C.POINTER(C.POINTER(LogitBiasC)), sz, C.POINTER(LogprobsC)]
     L.dsocr_session_stage_ngram_window.argtypes = [vp, C.POINTER(NgramWindowC)]
     L.dsocr_k_ngram_window.argtypes = [i32, i32, i32, vp, vp, i32, vp, C.POINTER(C.POINTER(NgramWindowC)), i32]
+    L.dsocr_guided_check.argtypes = [C.POINTER(GuidedC), i32, C.c_longlong]
+    L.dsocr_generate_guided.argtypes = [vp, sz, C.POINTER(RequestC), C.POINTER(DecodeParamsC), C.POINTER(ResultC),
+                                        C.POINTER(C.POINTER(GuidedC)), C.POINTER(GuidedResultC),
+                                        C.POINTER(C.POINTER(NgramWindowC)), C.POINTER(C.POINTER(PenaltiesC)),
+                                        C.POINTER(C.POINTER(StopSetC)), C.POINTER(StopHitC),
+                                        C.POINTER(C.POINTER(LogitBiasC)), sz, C.POINTER(LogprobsC)]
+    L.dsocr_session_stage_guided.argtypes = [vp, C.POINTER(GuidedC)]
+    L.dsocr_session_guided_state.argtypes = [vp, i32, C.POINTER(GuidedResultC)]
+    L.dsocr_k_guided_mask.argtypes = [i32, i32, i32, i32, vp, C.POINTER(GuidedC), C.c_longlong, vp, vp, vp, vp]
+    L.dsocr_k_guided_advance.argtypes = [i32, i32, C.POINTER(GuidedC), vp, vp, vp, vp]
     _lib = L
     return L
 

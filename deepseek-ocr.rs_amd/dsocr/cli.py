@@ -110,6 +110,9 @@ def build_parser() -> argparse.ArgumentParser:
                    help="lower the logit of every token generated so far by X")
     p.add_argument("--min-p", type=float, default=None, metavar="X",
                    help="when sampling, keep only tokens at least X (0..1) times as likely as the most likely one")
+    p.add_argument("--guided-choice", action="append", default=None, metavar="STR",
+                   help="the output must be one of the given strings (repeat the option once per string): a token "
+                        "automaton over their tokenisations constrains every step on the device")
     p.add_argument("--ngram-window-size", type=int, default=None, metavar="N",
                    help="ban the continuation of every N-gram that already occurs within the last --ngram-window "
                         "context tokens (replaces --no-repeat-ngram-size for the run); 0 = off")
@@ -252,7 +255,31 @@ def token_constraint(args) -> dict:
     kw.update(stop_arguments(args))
     kw.update(penalty_arguments(args))
     kw.update(ngram_window_arguments(args))
+    guided_choices(args)
     return kw
+
+
+def guided_choices(args) -> list:
+    """--guided-choice as the list of strings ([] when the option is absent).  Checked here, before any load; the
+    automaton needs the tokenizer and is built by ``guided_arguments``."""
+    choices = getattr(args, "guided_choice", None) or []
+    if any(c == "" for c in choices):
+        raise DsocrError(1, "--guided-choice takes a non-empty string")
+    if choices and getattr(args, "slots", 0):
+        raise DsocrError(1, "--guided-choice applies to one document: not with --slots")
+    return list(choices)
+
+
+def guided_arguments(args, tokenizer) -> dict:
+    """--guided-choice as the keyword of ``engine.decode`` ({} when the option is absent)."""
+    from .guided import GuidedError, choice_automaton
+    choices = guided_choices(args)
+    if not choices:
+        return {}
+    try:
+        return {"guided": choice_automaton(tokenizer, choices)}
+    except GuidedError as e:
+        raise DsocrError(1, f"--guided-choice: {e}") from None
 
 
 def ngram_window_arguments(args) -> dict:
@@ -348,6 +375,7 @@ def run_inference(args, out=sys.stdout, err=sys.stderr) -> int:
          f"{args.weights or f'synthetic(seed={args.synthetic_seed})'})")
     try:
         tokenizer = load_tokenizer(args.tokenizer, vocab)
+        constraint.update(guided_arguments(args, tokenizer))
         prompt = render_prompt(args.template, "", prompt_raw)
         slots = prompt.count("<image>")
         if getattr(args, "slots", 0):

@@ -19,11 +19,12 @@ from typing import Any, Callable, Optional, Sequence
 import numpy as np
 
 from ._lib import (DTYPES, LOAD_PACKED_EXPERTS, MAX_TOP_LOGPROBS, DecodeParamsC, DsocrError, LoadArgs, LogitBiasC, LogprobsC,
-                   NgramWindowC, PenaltiesC, RequestC, ResultC, STREAM_CB, SESSION_LOGIT_BIAS, SESSION_LOGPROBS,
+                   GuidedC, GuidedResultC, NgramWindowC, PenaltiesC, SESSION_GUIDED, RequestC, ResultC, STREAM_CB, SESSION_LOGIT_BIAS, SESSION_LOGPROBS,
                    SESSION_NGRAM_WINDOW, SESSION_PENALTIES,
                    SESSION_PER_REQUEST, SESSION_STOP,
                    SessionDescC, SlotStatusC, StopHitC, StopSetC, TimingsC, VisionSettingsC, check, lib)
 from .constraint import ConstraintError, LogitConstraint, merge_constraint
+from .guided import STATUS_NAMES, GuidedError, TokenAutomaton
 from .ngram_window import NgramWindow, NgramWindowError, make_ngram_window
 from .penalties import Penalties, PenaltyError, make_penalties
 from .stops import StopError, StopSet, apply_stops, merge_stops
@@ -110,6 +111,34 @@ def _ngram_window_c(nw: Optional[NgramWindow], keep) -> Optional[NgramWindowC]:
     return NgramWindowC(nw.ngram_size, nw.window, C.cast(arr, C.POINTER(C.c_int32)), n)
 
 
+def _guided(guided, vocab) -> Optional[TokenAutomaton]:
+    """The ``guided=`` argument (a ``dsocr.guided.TokenAutomaton`` or None), checked against the vocabulary; the EOS
+    rule is the engine's own check.  A bad one is the engine's EINVAL."""
+    if guided is None:
+        return None
+    if not isinstance(guided, TokenAutomaton):
+        raise DsocrError(1, "EINVAL: token automaton: guided must be a dsocr.guided.TokenAutomaton")
+    try:
+        return guided.validate(vocab, None)
+    except GuidedError as e:
+        raise DsocrError(1, f"EINVAL: token automaton: {e}") from None
+
+
+def _guided_c(ta: Optional[TokenAutomaton], keep) -> Optional[GuidedC]:
+    """(``keep`` holds the four arrays alive until the call returns)"""
+    if ta is None:
+        return None
+    def arr(values, dtype):  # (one element at least, so the pointer is never NULL; NumPy: no Python int per edge)
+        a = np.ascontiguousarray(values, dtype) if len(values) else np.zeros(1, dtype)
+        keep.append(a)
+        return a
+
+    acc = arr(np.asarray(ta.accepting, np.int64) != 0, np.uint8)
+    rp, tk, nx = arr(ta.row_ptr, np.int32), arr(ta.edge_tok, np.int32), arr(ta.edge_next, np.int32)
+    return GuidedC(ta.n_states, ta.start, acc.ctypes.data_as(C.POINTER(C.c_uint8)), rp.ctypes.data_as(C.POINTER(C.c_int32)),
+                   tk.ctypes.data_as(C.POINTER(C.c_int32)), nx.ctypes.data_as(C.POINTER(C.c_int32)))
+
+
 @dataclass
 class VisionSettings:
     base_size: int = 1024
@@ -144,6 +173,8 @@ class DecodeOutcome:
     # decode(..., stop=... / stop_token_ids=...): the matched stop string or token id; None when EOS or the length
     # limit ended the request (and for a request without stops)
     stop_reason: Any = None
+    # decode(..., guided=...): "complete" (the automaton reached a terminal state), "violated", or None
+    guided_status: Optional[str] = None
 
 
 @dataclass
@@ -541,6 +572,33 @@ class DeepseekOcrEngine:
         got = (b.ids(), [(int(h.seq), int(h.match_len)) for h in hits])
         return (*got, *lp.unpack()) if lp else got
 
+    def generate_guided(self, requests, automata, params: DecodeParameters = DecodeParameters(),
+                        ignore_eos: bool = False, top_k: Optional[int] = None, constraints=None, stop_sets=None,
+                        penalties=None, ngram_windows=None):
+        """generate_batch with one token automaton per request (dsocr_generate_guided): ``automata[i]`` is a
+        ``dsocr.guided.TokenAutomaton`` or None; the other lists as in ``generate_ngram_window`` (or None for none).
+        Returns ``(ids, stop_hits, guided)`` with ``guided[i] = (state, status)`` (status 0 running or cut, 1 complete,
+        2 violated), followed by the three log-probability lists when ``top_k`` is given."""
+        n = len(requests)
+        if len(automata) != n or any(x is not None and len(x) != n for x in (constraints, stop_sets, penalties, ngram_windows)):
+            raise DsocrError(1, "one token automaton (or None) per request")
+        _check_top_k(top_k)
+        b = _Batch(self, requests, params)
+        gd = _ptr_array(GuidedC, [_guided_c(_guided(a, self.vocab), b.keep) for a in automata], b.keep)
+        ngw = None if ngram_windows is None else _ptr_array(
+            NgramWindowC, [_ngram_window_c(_ngram_window(w, self.vocab), b.keep) for w in ngram_windows], b.keep)
+        pen = None if penalties is None else _ptr_array(PenaltiesC, [_penalties_c(pn) for pn in penalties], b.keep)
+        stops = None if stop_sets is None else _ptr_array(StopSetC, [_stop_c(ss, b.keep) for ss in stop_sets], b.keep)
+        bias = None if constraints is None else _ptr_array(LogitBiasC, [_bias_c(c, b.keep) for c in constraints], b.keep)
+        hits = (StopHitC * b.n)()
+        gres = (GuidedResultC * b.n)()
+        lp = None if top_k is None else _LogprobBuffers(b.n, b.cap, int(top_k))
+        pc = _params_c(params, self.eos_token_id, ignore_eos)
+        check(lib().dsocr_generate_guided(self._h, b.n, b.reqs, C.byref(pc), b.res, gd, gres, ngw, pen, stops, hits, bias,
+                                          lp.k if lp else 0, lp.c if lp else None))
+        got = (b.ids(), [(int(h.seq), int(h.match_len)) for h in hits], [(int(g.state), int(g.status)) for g in gres])
+        return (*got, *lp.unpack()) if lp else got
+
     def generate_stop_stream(self, request, stop_set, params: DecodeParameters = DecodeParameters(),
                              stream: Optional[Callable] = None, ignore_eos: bool = False):
         """``generate`` (one page, its stream callback) with a stop set (dsocr_generate_stop_stream): ``(ids, (seq,
@@ -628,7 +686,7 @@ class DeepseekOcrEngine:
     def open_session(self, slots: int, max_context: int, params: DecodeParameters = DecodeParameters(),
                      ignore_eos: bool = False, per_request: bool = False, logprobs: bool = False,
                      logit_bias: bool = False, stops: bool = False, penalties: bool = False,
-                     ngram_window: bool = False) -> "Session":
+                     ngram_window: bool = False, guided: bool = False) -> "Session":
         """A long-lived batch of `slots` pages (dsocr_session_open): pages are admitted and retired between bursts
         of decode steps.  `params` are the session's; params.max_new_tokens bounds a request's own.
         ``per_request`` (dsocr_session_open_ex, DSOCR_SESSION_PER_REQUEST): `params` are only the defaults and
@@ -640,9 +698,10 @@ class DeepseekOcrEngine:
         match launch.  ``penalties`` (DSOCR_SESSION_PENALTIES): every admission may carry ``frequency_penalty`` /
         ``presence_penalty`` / ``min_p``; a burst with such a page runs the exact head.  ``ngram_window``
         (DSOCR_SESSION_NGRAM_WINDOW): every admission may carry ``ngram_window``; a burst with such a page runs the
-        exact head with the window launch."""
+        exact head with the window launch.  ``guided`` (DSOCR_SESSION_GUIDED): every admission may carry ``guided``,
+        a token automaton; a burst with such a page runs the exact head with the mask and advance launches."""
         return Session(self, slots, max_context, params, ignore_eos, per_request, logprobs, logit_bias, stops, penalties,
-                       ngram_window)
+                       ngram_window, guided)
 
     # ------------------------------------------------------------------ OcrEngine::decode
     def decode(self, tokenizer, prompt: str, images: Sequence, vision: VisionSettings,
@@ -650,8 +709,10 @@ class DeepseekOcrEngine:
                logprobs: Optional[int] = None, logit_bias=None, allowed_token_ids=None,
                banned_token_ids=None, stop=None, stop_token_ids=None,
                include_stop_in_output: bool = False, frequency_penalty=None, presence_penalty=None,
-               min_p=None, ngram_window=None) -> DecodeOutcome:
-        """``ngram_window`` (a ``dsocr.ngram_window.NgramWindow``): the windowed no-repeat n-gram ban with its
+               min_p=None, ngram_window=None, guided=None) -> DecodeOutcome:
+        """``guided`` (a ``dsocr.guided.TokenAutomaton``): the page may only emit what the automaton allows, and ends
+        when it reaches a terminal state; ``outcome.guided_status`` is then "complete" (``stream`` is not called).
+        ``ngram_window`` (a ``dsocr.ngram_window.NgramWindow``): the windowed no-repeat n-gram ban with its
         whitelist, which replaces the plain ``no_repeat_ngram_size`` ban of ``params`` for this page (``stream`` is not
         called).
         ``frequency_penalty`` / ``presence_penalty`` lower the logit of every id the page has already generated
@@ -672,14 +733,24 @@ class DeepseekOcrEngine:
         ss = _stops(stop, stop_token_ids, tokenizer, self.vocab)
         pen = _penalties(frequency_penalty, presence_penalty, min_p)
         ngw = _ngram_window(ngram_window, self.vocab)
+        gd = _guided(guided, self.vocab)
         pages = [Page(im, vision, self) for im in images]
         ids, mask = build_prompt_tokens(tokenizer, prompt, [p.n_image_tokens for p in pages])
         token_lp = top = None
-        if logprobs is not None or con is not None or ss is not None or pen is not None or ngw is not None:
+        if logprobs is not None or con is not None or ss is not None or pen is not None or ngw is not None or gd is not None:
             rows = np.concatenate(self.image_embeddings(pages), axis=0) if len(pages) > 1 else None
             req = (ids, mask, pages[0] if len(pages) == 1 else None, rows)
-        if ss is not None or pen is not None or ngw is not None:
-            if ngw is not None:
+        if ss is not None or pen is not None or ngw is not None or gd is not None:
+            guided_status = None
+            if gd is not None:
+                got = self.generate_guided([req], [gd], params, top_k=None if logprobs is None else int(logprobs),
+                                           constraints=None if con is None else [con],
+                                           stop_sets=None if ss is None else [ss],
+                                           penalties=None if pen is None else [pen],
+                                           ngram_windows=None if ngw is None else [ngw])
+                guided_status = STATUS_NAMES.get(got[2][0][1])
+                got = (got[0], got[1], *got[3:])
+            elif ngw is not None:
                 got = self.generate_ngram_window([req], [ngw], params, top_k=None if logprobs is None else int(logprobs),
                                                  constraints=None if con is None else [con],
                                                  stop_sets=None if ss is None else [ss],
@@ -701,7 +772,7 @@ class DeepseekOcrEngine:
                 token_lp = [float(x) for x in got[2][0]][:len(res.tokens)]
                 top = [[(int(i), float(v)) for i, v in zip(got[3][0][t], got[4][0][t])] for t in range(len(token_lp))]
             return DecodeOutcome(normalize_text(res.text), len(ids), len(res.tokens), res.tokens, token_lp, top,
-                                 res.stop_reason)
+                                 res.stop_reason, guided_status)
         if con is not None and logprobs is None:
             gen = self.generate_constrained([req], [con], params)[0]
         elif logprobs is not None:
@@ -751,7 +822,7 @@ class Session:
 
     def __init__(self, engine: DeepseekOcrEngine, slots: int, max_context: int, params: DecodeParameters,
                  ignore_eos: bool = False, per_request: bool = False, logprobs: bool = False, logit_bias: bool = False,
-                 stops: bool = False, penalties: bool = False, ngram_window: bool = False):
+                 stops: bool = False, penalties: bool = False, ngram_window: bool = False, guided: bool = False):
         self._e = None
         # the (StopSet, include) record of an admission follows its page: staged for the C call that admits it,
         # pending while a chunked admission runs, then its slot's
@@ -760,7 +831,9 @@ class Session:
         pc = _params_c(params, engine.eos_token_id, ignore_eos)
         flags = ((SESSION_PER_REQUEST if per_request else 0) | (SESSION_LOGPROBS if logprobs else 0) |
                  (SESSION_LOGIT_BIAS if logit_bias else 0) | (SESSION_STOP if stops else 0) |
-                 (SESSION_PENALTIES if penalties else 0) | (SESSION_NGRAM_WINDOW if ngram_window else 0))
+                 (SESSION_PENALTIES if penalties else 0) | (SESSION_NGRAM_WINDOW if ngram_window else 0) |
+                 (SESSION_GUIDED if guided else 0))
+        self.has_guided = bool(guided)
         self.has_ngram_window = bool(ngram_window)
         self.has_penalties = bool(penalties)
         self.has_stops = bool(stops)
@@ -791,7 +864,7 @@ class Session:
               ignore_eos: Optional[bool] = None, logprobs: Optional[int] = None, logit_bias=None,
               allowed_token_ids=None, banned_token_ids=None, stop=None, stop_token_ids=None,
               include_stop_in_output: bool = False, tokenizer=None, stops: Optional[StopSet] = None,
-              frequency_penalty=None, presence_penalty=None, min_p=None, ngram_window=None) -> int:
+              frequency_penalty=None, presence_penalty=None, min_p=None, ngram_window=None, guided=None) -> int:
         """Without ``params``: the session's parameters with this page's ``max_new_tokens`` / ``seed``
         (dsocr_session_admit).  With ``params``: the page's whole parameter set (dsocr_session_admit_params; its
         max_new_tokens and seed count, the two keyword arguments are then not read); ``eos_token_id`` /
@@ -812,7 +885,7 @@ class Session:
         req, _, _keep = self._admission((ids, mask, page, image_rows), None, logprobs,
                                         (logit_bias, allowed_token_ids, banned_token_ids),
                                         (stop, stop_token_ids, include_stop_in_output, tokenizer, stops),
-                                        (frequency_penalty, presence_penalty, min_p), ngram_window)
+                                        (frequency_penalty, presence_penalty, min_p), ngram_window, guided)
         slot = C.c_int(-1)
         if params is not None:
             pc = _params_c(params, self._eos if eos_token_id is None else int(eos_token_id),
@@ -825,7 +898,7 @@ class Session:
         return self._admitted_stops(slot.value)
 
     def _admission(self, request, request_params, logprobs, constraint, stops, penalties=(None, None, None),
-                   ngram_window=None):
+                   ngram_window=None, guided=None):
         """What every admission form does before its C call, in this order: the ``logprobs`` check, the request
         (``request``: ids, mask, page, image rows), its parameter record (``request_params``: ``_request_params``'
         arguments, or None for none), the stop set merged and checked (``stops``: ``_check_stops``' arguments), then
@@ -833,7 +906,7 @@ class Session:
         penalties (``penalties``: frequency_penalty, presence_penalty, min_p) are checked with the stop set, before
         anything is staged, and staged after it; the windowed n-gram ban (``ngram_window``) likewise, staged last.  Returns
         the request, the parameter record and the list that keeps their arrays alive; the checked stop record is
-        ``_staged_stops``."""
+        ``_staged_stops``.  The token automaton (``guided``) is checked with the others and staged after them all."""
         self._check_logprobs(logprobs)
         keep = []
         req = self._e._request(*request, keep)
@@ -841,11 +914,44 @@ class Session:
         checked = self._check_stops(*stops)
         pen = self._check_penalties(*penalties)
         ngw = self._check_ngram_window(ngram_window)
+        gd = self._check_guided(guided)
         self._stage_constraint(*constraint)
         self._stage_stops(checked)
         self._stage_penalties(pen)
         self._stage_ngram_window(ngw)
+        self._stage_guided(gd)
         return req, pc, keep
+
+    def _check_guided(self, guided) -> Optional[TokenAutomaton]:
+        """The token automaton of an admission, checked before anything is staged for it (None: none)."""
+        gd = _guided(guided, self._e.vocab)
+        if gd is not None and not self.has_guided:
+            raise DsocrError(1, "EINVAL: this session was opened without guided")
+        return gd
+
+    def _stage_guided(self, gd: Optional[TokenAutomaton]) -> None:
+        """Stages the checked automaton for the admission call that follows (dsocr_session_stage_guided), which
+        consumes it.  Should the staging itself fail, what was staged before it is cleared."""
+        if gd is None:
+            return
+        keep = []
+        rec = _guided_c(gd, keep)
+        try:
+            check(lib().dsocr_session_stage_guided(self._e._h, C.byref(rec)))
+        except DsocrError:
+            lib().dsocr_session_stage_logit_bias(self._e._h, None)
+            lib().dsocr_session_stage_stop(self._e._h, None)
+            lib().dsocr_session_stage_penalties(self._e._h, None)
+            lib().dsocr_session_stage_ngram_window(self._e._h, None)
+            self._staged_stops = None
+            raise
+
+    def guided_state(self, slot: int):
+        """``(state, status)`` of a live slot's automaton (dsocr_session_guided_state): status 0 running or cut, 1
+        complete, 2 violated; ``(0, 0)`` for a page without one."""
+        g = GuidedResultC()
+        check(lib().dsocr_session_guided_state(self._e._h, int(slot), C.byref(g)))
+        return int(g.state), int(g.status)
 
     def _check_ngram_window(self, ngram_window) -> Optional[NgramWindow]:
         """The windowed n-gram ban of an admission, checked before anything is staged for it (None: none)."""
@@ -990,7 +1096,7 @@ class Session:
                     ignore_eos: Optional[bool] = None, logprobs: Optional[int] = None, logit_bias=None,
                     allowed_token_ids=None, banned_token_ids=None, stop=None, stop_token_ids=None,
                     include_stop_in_output: bool = False, tokenizer=None, stops: Optional[StopSet] = None,
-                    frequency_penalty=None, presence_penalty=None, min_p=None, ngram_window=None) -> int:
+                    frequency_penalty=None, presence_penalty=None, min_p=None, ngram_window=None, guided=None) -> int:
         """``admit`` in slices (dsocr_session_admit_begin): every check runs here and nothing is launched; the work
         is done by ``admit_advance``, one slice per call (the page's vision, then the prompt in chunks of
         ``chunk_rows`` >= 32 rows), with ``step`` / ``retire`` legal in between.  Returns the admission's ticket.
@@ -1000,7 +1106,7 @@ class Session:
                                          (params, max_new_tokens, seed, eos_token_id, ignore_eos), logprobs,
                                          (logit_bias, allowed_token_ids, banned_token_ids),
                                          (stop, stop_token_ids, include_stop_in_output, tokenizer, stops),
-                                         (frequency_penalty, presence_penalty, min_p), ngram_window)
+                                         (frequency_penalty, presence_penalty, min_p), ngram_window, guided)
         self._pending_stops = None
         ticket = C.c_int(-1)
         self._admission_call(lib().dsocr_session_admit_begin, C.byref(req), C.byref(pc), max(int(chunk_rows), 0),
@@ -1057,7 +1163,7 @@ class Session:
                      logprobs: Optional[int] = None, logit_bias=None, allowed_token_ids=None,
                      banned_token_ids=None, stop=None, stop_token_ids=None, include_stop_in_output: bool = False,
                      tokenizer=None, stops: Optional[StopSet] = None, frequency_penalty=None,
-                     presence_penalty=None, min_p=None, ngram_window=None) -> int:
+                     presence_penalty=None, min_p=None, ngram_window=None, guided=None) -> int:
         """``admit`` for a prompt that starts with the entry's rows (dsocr_session_admit_prefix): ``ids`` / ``mask``
         are the whole prompt's, no page and no image rows; vision and the prefill of the entry's rows are skipped.
         The keywords are ``admit``'s (without ``params``: the session's parameters with this ``max_new_tokens`` /
@@ -1066,7 +1172,7 @@ class Session:
                                          (params, max_new_tokens, seed, eos_token_id, ignore_eos), logprobs,
                                          (logit_bias, allowed_token_ids, banned_token_ids),
                                          (stop, stop_token_ids, include_stop_in_output, tokenizer, stops),
-                                         (frequency_penalty, presence_penalty, min_p), ngram_window)
+                                         (frequency_penalty, presence_penalty, min_p), ngram_window, guided)
         slot = C.c_int(-1)
         self._admission_call(lib().dsocr_session_admit_prefix, int(handle), C.byref(req), C.byref(pc), C.byref(slot))
         return self._admitted_stops(slot.value)

@@ -44,6 +44,12 @@ opens the session with ``ngram_window=True`` and such a request shares it (a bur
 head); without the flag it runs alone through ``engine.decode(...)`` with the same argument after the session drained.
 Prefix-cache keys do not see the record.
 
+Guided decoding: ``submit(..., guided=TokenAutomaton(...))`` (``dsocr.guided``) is checked on the caller's thread (a
+bad one fails the future).  ``BatchScheduler(..., guided=True)`` opens the session with ``guided=True`` and such a
+request shares it: the automaton goes to the admission call, whichever form it takes, and the outcome carries
+``guided_status`` (read from the slot before it is retired).  Without the flag the request runs alone through
+``engine.decode``.  Prefix-cache keys do not see the automaton: a guided retry on a cached page is a prefix hit.
+
 Page prefix cache: ``BatchScheduler(..., prefix_cache=N)`` (default 0: nothing changes) keeps the K/V rows of up to N
 pages' prompt prefixes (BOS and the image rows) in the session.  After a one-image request is admitted its prefix is
 kept (``Session.keep_prefix``, rows = index of the last image position + 1) under the key (SHA-256 of the image as
@@ -74,6 +80,7 @@ from dataclasses import dataclass, field, fields
 from typing import Any, Callable, Optional, Sequence
 
 from .constraint import merge_constraint
+from .guided import STATUS_NAMES
 from .ngram_window import make_ngram_window
 from .penalties import make_penalties
 from .stops import TextStop, TokenHoldback, merge_stops
@@ -111,6 +118,8 @@ class _Request:
     stops: Any = None       # the request's merged StopSet, or None
     penalties: Any = None   # the request's checked Penalties, or None
     ngram_window: Any = None  # the request's checked NgramWindow, or None
+    guided: Any = None        # the request's checked TokenAutomaton, or None
+    guided_status: Any = None  # "complete" / "violated" / None, read from the slot before it is retired
     stop_args: dict = field(default_factory=dict)  # ... as the keywords engine.decode takes
     include_stop: bool = False
     holdback: Any = None    # TokenHoldback of a streaming request with stops
@@ -173,7 +182,7 @@ class BatchScheduler:
                  defaults: DecodeParameters = DecodeParameters(), vision: Optional[VisionSettings] = None,
                  prepare: Optional[Callable] = None, per_request_params: bool = False, logprobs: bool = False,
                  prefix_cache: int = 0, admit_chunk: int = 0, logit_bias: bool = False, stops: bool = False,
-                 penalties: bool = False, ngram_window: bool = False):
+                 penalties: bool = False, ngram_window: bool = False, guided: bool = False):
         if not 1 <= int(slots) <= 8:
             raise ValueError("a session has 1..8 slots")
         if int(admit_chunk) != 0 and int(admit_chunk) < 32:
@@ -200,6 +209,7 @@ class BatchScheduler:
         self.stops = bool(stops)
         self.penalties = bool(penalties)
         self.ngram_window = bool(ngram_window)
+        self.guided = bool(guided)
         self.vision = vision or VisionSettings()
         self._prepare = prepare or _default_prepare
         self._queue: deque = deque()
@@ -233,8 +243,9 @@ class BatchScheduler:
                logprobs: Optional[int] = None, logit_bias=None, allowed_token_ids=None,
                banned_token_ids=None, stop=None, stop_token_ids=None,
                include_stop_in_output: bool = False, frequency_penalty=None, presence_penalty=None,
-               min_p=None, ngram_window=None) -> Future:
-        """``ngram_window``: the request's windowed n-gram ban (see the module text).
+               min_p=None, ngram_window=None, guided=None) -> Future:
+        """``guided``: the request's token automaton (see the module text).
+        ``ngram_window``: the request's windowed n-gram ban (see the module text).
         ``frequency_penalty`` / ``presence_penalty`` / ``min_p``: the request's penalties (see the module text).
         ``stop`` / ``stop_token_ids`` / ``include_stop_in_output``: the request's stop set (see the module text).
         ``logit_bias`` / ``allowed_token_ids`` / ``banned_token_ids``: the request's token constraint (see the
@@ -258,6 +269,10 @@ class BatchScheduler:
             if ngram_window is not None and not hasattr(ngram_window, "ngram_size"):
                 raise ValueError("ngram_window must be a dsocr.ngram_window.NgramWindow")
             window = make_ngram_window(ngram_window, vocab=getattr(self.engine, "vocab", None))
+            if guided is not None:
+                if not hasattr(guided, "validate"):
+                    raise ValueError("guided must be a dsocr.guided.TokenAutomaton")
+                guided.validate(getattr(self.engine, "vocab", None) or (1 << 31))
         except ValueError as e:
             fut.set_exception(e)
             return fut
@@ -277,6 +292,7 @@ class BatchScheduler:
         rq.constraint = constraint
         rq.penalties = penalties
         rq.ngram_window = window
+        rq.guided = guided
         if stops is not None:
             rq.stops, rq.include_stop = stops, bool(include_stop_in_output)
             rq.stop_args = dict(stop=stop, stop_token_ids=stop_token_ids, include_stop_in_output=rq.include_stop)
@@ -287,7 +303,8 @@ class BatchScheduler:
         rq.exclusive = (not self.compatible(params, len(rq.ids)) or (rq.logprobs is not None and not self.logprobs) or
                         (constraint is not None and not self.logit_bias) or (stops is not None and not self.stops) or
                         (penalties is not None and not self.penalties) or
-                        (window is not None and not self.ngram_window))
+                        (window is not None and not self.ngram_window) or
+                        (guided is not None and not self.guided))
         if self.prefix_cache and len(rq.images) == 1 and not rq.exclusive and any(rq.mask):
             rows = max(i for i, m in enumerate(rq.mask) if m) + 1
             if rows < len(rq.ids):  # some text follows the image: the last row's logits come from a new row
@@ -426,6 +443,8 @@ class BatchScheduler:
                 kw["penalties"] = True
             if self.ngram_window:
                 kw["ngram_window"] = True
+            if self.guided:
+                kw["guided"] = True
             self._session = self.engine.open_session(self.slots, self.max_context, self.defaults, **kw)
 
     def _admit_args(self, rq):
@@ -443,6 +462,8 @@ class BatchScheduler:
             kw.update(_penalty_kwargs(rq.penalties))
         if rq.ngram_window is not None:
             kw.update(rq.ngram_window.kwargs())
+        if rq.guided is not None:
+            kw["guided"] = rq.guided
         if self.per_request_params:
             kw["params"] = rq.params
         else:
@@ -565,6 +586,8 @@ class BatchScheduler:
             if not rq.done:
                 continue
             res = None
+            if rq.guided is not None:  # how the automaton ended, while the slot is still live
+                rq.guided_status = STATUS_NAMES.get(self._session.guided_state(slot)[1])
             if rq.stops is not None:
                 res, moved = self._session.retire_stopped(slot, lambda t: _decode_text(self.tokenizer, t))
                 ids = res.tokens
@@ -585,6 +608,7 @@ class BatchScheduler:
                 out = DecodeOutcome(normalize_text(_decode_text(self.tokenizer, ids)), len(rq.ids), len(ids), ids)
             if rq.logprobs is not None:
                 out.token_logprobs, out.top_logprobs = rq.token_lp[:len(ids)], rq.top_lp[:len(ids)]
+            out.guided_status = rq.guided_status
             rq.future.set_result(out)
 
     def _run_exclusive(self, rq):
@@ -596,6 +620,8 @@ class BatchScheduler:
             ckw.update(_penalty_kwargs(rq.penalties))
         if rq.ngram_window is not None:  # (nor one with a windowed ban)
             ckw.update(rq.ngram_window.kwargs())
+        if rq.guided is not None:  # (nor a guided one)
+            ckw["guided"] = rq.guided
         try:
             if rq.logprobs is None and not ckw:
                 out = self.engine.decode(self.tokenizer, rq.prompt, rq.images, rq.vision, rq.params, rq.on_token)

@@ -293,6 +293,45 @@ def parse_ngram_window(req: dict, vocab: Optional[int] = None) -> Optional[dict]
     return None if rec is None else rec.kwargs()
 
 
+def parse_guided(req: dict, tokenizer, vocab: Optional[int] = None) -> Optional[dict]:
+    """Guided decoding of a request body: `guided_choice` ([str, ...]), `structured_outputs` ({"choice": [...]}) or a
+    raw `token_automaton` object (n_states, start, accepting, row_ptr, edge_tok, edge_next), at top level or inside
+    `vllm_xargs` (a top-level field wins).  Returns the keyword ``decode`` / ``submit`` take, None when the body asks
+    for nothing (absent or null fields).  400: more than one of them, or anything else in those fields.  A guided
+    decode does not stream: a streaming request gets its tokens when the page has ended."""
+    from .guided import GuidedError, automaton_from_mapping, choice_automaton
+    xargs = req.get("vllm_xargs")
+    if xargs is None:
+        xargs = {}
+    if not isinstance(xargs, dict):
+        raise ApiError.bad_request("vllm_xargs must be an object")
+    got = {}
+    for name in ("guided_choice", "structured_outputs", "token_automaton"):
+        v = req.get(name)
+        v = xargs.get(name) if v is None else v
+        if v is not None:
+            got[name] = v
+    if not got:
+        return None
+    if len(got) > 1:
+        raise ApiError.bad_request("guided decoding: give one of guided_choice, structured_outputs and token_automaton")
+    try:
+        if "token_automaton" in got:
+            aut = automaton_from_mapping(got["token_automaton"])
+        else:
+            choice = got.get("guided_choice")
+            if "structured_outputs" in got:
+                so = got["structured_outputs"]
+                if not isinstance(so, dict) or set(so) != {"choice"}:
+                    raise GuidedError("structured_outputs supports {\"choice\": [...]} only")
+                choice = so["choice"]
+            aut = choice_automaton(tokenizer, choice)
+        aut.validate(vocab if vocab else 1 << 31)
+    except GuidedError as e:
+        raise ApiError.bad_request(f"guided decoding: {e}")
+    return {"guided": aut}
+
+
 def _held_back(on_token, stops: dict, tokenizer, vocab):
     """``on_token`` behind a ``dsocr.stops.TokenHoldback``: it is called once per token that no later hit can remove."""
     from .stops import TokenHoldback, merge_stops
@@ -583,6 +622,9 @@ def handle_generation(state: ServerState, req: dict, kind: str):
     window = parse_ngram_window(req, getattr(state.engine, "vocab", None))
     if window:  # the same
         constraint = dict(constraint or {}, **window)
+    guided = parse_guided(req, state.tokenizer, getattr(state.engine, "vocab", None))
+    if guided:  # the same; the response names how the automaton ended
+        constraint = dict(constraint or {}, **guided)
     if stream:
         c = StreamController(state.tokenizer, kind, model)
         if stops:
@@ -615,6 +657,11 @@ def handle_generation(state: ServerState, req: dict, kind: str):
             body["choices"][0]["stop_reason"] = getattr(out, "stop_reason", None)
         else:
             body["stop_reason"] = getattr(out, "stop_reason", None)
+    if guided:  # "complete" (the page ended in a terminal state: finish_reason "stop"), "violated" or null
+        if kind == "chat":
+            body["choices"][0]["guided_status"] = getattr(out, "guided_status", None)
+        else:
+            body["guided_status"] = getattr(out, "guided_status", None)
     if logprobs is not None:
         body["choices"][0]["logprobs"] = {"content": logprob_content(state.tokenizer, out.generated_tokens,
                                                                      out.token_logprobs or [], out.top_logprobs or [])}
@@ -698,6 +745,11 @@ def add_scheduler_args(p):
                    help="with --slots: open the decode session with a windowed n-gram ban record per slot, so requests "
                         "with `ngram_size` / `window_size` / `whitelist_token_ids` join the running batch (a burst with "
                         "such a request runs the exact lm_head) instead of waiting for it to drain; off by default")
+    p.add_argument("--guided", action="store_true",
+                   help="with --slots: open the decode session with the tables of a token automaton per slot (about "
+                        "25 MB each at the full vocabulary), so requests with `guided_choice` / `structured_outputs` / "
+                        "`token_automaton` join the running batch (a burst with such a request runs the exact "
+                        "lm_head) instead of waiting for it to drain; off by default")
     p.add_argument("--prefix-cache", type=int, default=0,
                    help="with --slots: keep the K/V rows of up to N pages' image prefixes (LRU), so a later prompt on "
                         "the same image under the same vision settings skips vision and the prefill of those rows; "
@@ -710,7 +762,7 @@ def add_scheduler_args(p):
 
 def make_scheduler(state: ServerState, slots: int, max_context: int, per_request_params: bool = False,
                    logprobs: bool = False, prefix_cache: int = 0, admit_chunk: int = 0, logit_bias: bool = False,
-                   stops: bool = False, penalties: bool = False, ngram_window: bool = False):
+                   stops: bool = False, penalties: bool = False, ngram_window: bool = False, guided: bool = False):
     """The state's scheduler for --slots N (None for 0: requests take the lock path).  per_request_params: the
     DecodeParameters merge_decode builds from a request body are admitted into the session as that request's own.
     prefix_cache: --prefix-cache N (ValueError without --slots: the entries live in the decode session)."""
@@ -726,6 +778,8 @@ def make_scheduler(state: ServerState, slots: int, max_context: int, per_request
         raise ValueError("--penalties needs --slots (the penalty records live in the decode session)")
     if ngram_window and not slots:
         raise ValueError("--ngram-window needs --slots (the window records live in the decode session)")
+    if guided and not slots:
+        raise ValueError("--guided needs --slots (the automaton tables live in the decode session)")
     if not slots:
         return None
     from .scheduler import BatchScheduler
@@ -733,7 +787,7 @@ def make_scheduler(state: ServerState, slots: int, max_context: int, per_request
                           per_request_params=per_request_params, logprobs=logprobs, prefix_cache=prefix_cache,
                           admit_chunk=admit_chunk, **({"logit_bias": True} if logit_bias else {}),
                           **({"stops": True} if stops else {}), **({"penalties": True} if penalties else {}),
-                          **({"ngram_window": True} if ngram_window else {}))
+                          **({"ngram_window": True} if ngram_window else {}), **({"guided": True} if guided else {}))
 
 
 def main(argv=None) -> int:
@@ -763,6 +817,8 @@ def main(argv=None) -> int:
         p.error("--penalties needs --slots (the penalty records live in the decode session)")
     if args.ngram_window and not args.slots:
         p.error("--ngram-window needs --slots (the window records live in the decode session)")
+    if args.guided and not args.slots:
+        p.error("--guided needs --slots (the automaton tables live in the decode session)")
     config = model_config(args)  # --model deepseek-ocr | deepseek-ocr-2: the bundled config and vision defaults
     engine = load_model(ModelLoadArgs(config_path=config, weights_path=args.weights, snapshot_path=args.snapshot,
                                       snapshot_packed=getattr(args, "snapshot_packed", None),
@@ -772,7 +828,7 @@ def main(argv=None) -> int:
                         vision_settings(args), decode_params(args))
     state.scheduler = make_scheduler(state, args.slots, args.max_context, args.per_request_params, args.logprobs,
                                      args.prefix_cache, args.admit_chunk, args.logit_bias, args.stops,
-                                     args.penalties, args.ngram_window)
+                                     args.penalties, args.ngram_window, args.guided)
     import uvicorn
     uvicorn.run(create_app(state), host=args.host, port=args.port)
     return 0

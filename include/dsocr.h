@@ -390,6 +390,54 @@ dsocr_status dsocr_generate_ngram_window(dsocr_engine* e, size_t n, const dsocr_
                                          const dsocr_logit_bias* const* bias, size_t top_k, dsocr_logprobs* lp);
 dsocr_status dsocr_session_stage_ngram_window(dsocr_engine* e, const dsocr_ngram_window* ngw);
 
+/* ---- guided decoding: a per-request token automaton (no reference counterpart).  The request carries n_states
+ * states, a start state, one byte per state (accepting: the request's EOS id may be selected there) and the edges in
+ * CSR form: the edges of state s are row_ptr[s] .. row_ptr[s + 1] - 1, edge_tok strictly ascending within a state,
+ * edge_next the state an edge leads to.  A state without an outgoing edge is terminal.  In every step (the prefill's
+ * own selection included) a page in state s gets l[t] = -inf for every id t without an edge from s, except its EOS
+ * id, which is kept iff accepting[s]; ids with an edge keep their logits bit for bit.  The step order: lm_head, logit
+ * bias, this mask, log-probability partials (entries and alternatives are those of the constrained distribution),
+ * repetition penalty, frequency / presence, n-gram ban, selection, the advance, the stop match.  The advance: when the
+ * step appended a token, the state follows its edge; arriving at a terminal state ends the page (status 1, complete);
+ * a token without an edge, which only the selection's last resort (id 0 when no finite logit remains) can produce,
+ * ends it with state -1 and status 2 (violated).  A call or burst in which a page carries an automaton runs the exact
+ * lm_head and selectors; a page without one in such a batch keeps its ids and log-probability entries bit for bit.
+ * DSOCR_EINVAL, before any device state changes: n_states outside [1, DSOCR_MAX_GUIDED_STATES]; more than
+ * DSOCR_MAX_GUIDED_EDGES edges; row_ptr not non-decreasing from 0; an edge token outside [0, vocab) or equal to the
+ * request's EOS id; tokens not strictly ascending within a state; edge_next or start outside [0, n_states); a
+ * terminal start; a NULL array; an automaton with use_cache = 0 or DSOCR_PERSIST.  (The logits trace cannot be asked
+ * for together with an automaton: dsocr_generate_trace takes none.)  Under ignore_eos no id is the EOS id.
+ *   dsocr_guided_check: the record's own checks against `vocab` and `eos` (negative: none); needs no engine and no
+ *   device.
+ *   dsocr_generate_guided: dsocr_generate_ngram_window with one automaton (guided [n], entries may be NULL; guided
+ *   itself NULL: none) and one result (gres [n] or NULL) per request.
+ *   dsocr_session_stage_guided: stages one automaton (copied) for the NEXT admission call on this engine's session,
+ *   whichever form it takes, exactly like dsocr_session_stage_ngram_window; a chunked admission keeps it on the host
+ *   until its last slice.  DSOCR_EINVAL, nothing staged, when the record fails a check that needs no EOS id, no
+ *   session is open, or the session was opened without DSOCR_SESSION_GUIDED; the EOS rule is checked by the admission.
+ *   dsocr_session_guided_state: the state and status of a live slot ({0, 0} for a page without an automaton); it
+ *   follows its page through the compaction of dsocr_session_retire. */
+#define DSOCR_MAX_GUIDED_STATES 1024
+#define DSOCR_MAX_GUIDED_EDGES (1 << 20)
+typedef struct {
+    int32_t n_states, start;
+    const uint8_t* accepting;    /* [n_states] */
+    const int32_t *row_ptr, *edge_tok, *edge_next; /* [n_states + 1], [E], [E] with E = row_ptr[n_states] */
+} dsocr_guided;
+typedef struct {
+    int32_t state;   /* the automaton state after the last appended token (-1: violated) */
+    int32_t status;  /* 0 running, or cut by max_new_tokens / EOS / a stop; 1 complete; 2 violated */
+} dsocr_guided_result;
+dsocr_status dsocr_guided_check(const dsocr_guided* g, int vocab, long long eos);
+dsocr_status dsocr_generate_guided(dsocr_engine* e, size_t n, const dsocr_request* reqs,
+                                   const dsocr_decode_params* params, dsocr_result* results,
+                                   const dsocr_guided* const* guided, dsocr_guided_result* gres,
+                                   const dsocr_ngram_window* const* ngw, const dsocr_penalties* const* pen,
+                                   const dsocr_stop_set* const* stops, dsocr_stop_hit* hits,
+                                   const dsocr_logit_bias* const* bias, size_t top_k, dsocr_logprobs* lp);
+dsocr_status dsocr_session_stage_guided(dsocr_engine* e, const dsocr_guided* g);
+dsocr_status dsocr_session_guided_state(dsocr_engine* e, int slot, dsocr_guided_result* out);
+
 /* ---- decode sessions: pages join and leave a running batch between decode steps (no reference counterpart: the
  * reference server decodes one request at a time behind its Mutex, server/src/state.rs:22).  A session is a
  * long-lived batch of `slots` (1..8) pages with max_context rows each (a page needs prompt_len + max_new_tokens
@@ -456,6 +504,12 @@ dsocr_status dsocr_session_open(dsocr_engine* e, size_t slots, size_t max_contex
  * head with the window launch iff an active slot carries a record that is on; the record follows its page through
  * the compaction of dsocr_session_retire and ends with the page. */
 #define DSOCR_SESSION_NGRAM_WINDOW 32u
+/* DSOCR_SESSION_GUIDED (combines with the six flags above): every slot keeps the tables of a token automaton at the
+ * caps (a bitmask of 1024 x ceil(vocab / 32) words and 1025 + 2 x 2^20 int32 of edges: about 25 MB per slot at a
+ * vocabulary of 129280, reserved at open), and an admission may carry one (dsocr_session_stage_guided).  A burst runs
+ * the exact head, with the mask and advance launches, iff an active slot carries an automaton; the tables follow
+ * their page through the compaction of dsocr_session_retire (the used part is copied) and end with the page. */
+#define DSOCR_SESSION_GUIDED 64u
 dsocr_status dsocr_session_open_ex(dsocr_engine* e, size_t slots, size_t max_context, const dsocr_decode_params* params,
                                    uint32_t flags);
 /* Every check (free slot, context need, prompt/image mismatch, token ids, page variant) happens before any device
@@ -951,6 +1005,18 @@ dsocr_status dsocr_k_stop_match(int B, int steps, int out_cap, const int* n_seq,
  * record per row (never NULL; min_p is not read by this kernel). */
 dsocr_status dsocr_k_out_penalty(int B, int V, int ld, float* logits, const int* out_ids, int out_cap,
                                  const int* out_len, const dsocr_penalties* pen);
+/* launch_guided_build + launch_dec_guided_mask once on host rows.  Every row with on[b] != 0 is built from the one
+ * automaton `g` (checked like dsocr_guided_check) with the EOS id `eos`; then its state is set to state[b] and the
+ * mask runs over logits (in / out): B rows of ld floats that start row_off floats behind a 16-byte aligned address.
+ * mask_out [n_states][mask_ld] (mask_ld = ceil(V / 32) rounded up to a multiple of 4) receives the bitmask of the
+ * first row that is on. */
+dsocr_status dsocr_k_guided_mask(int B, int V, int ld, int row_off, float* logits, const dsocr_guided* g, long long eos,
+                                 const int* on, const int* state, const int* done, uint32_t* mask_out);
+/* launch_dec_guided_advance over a scripted run: rows with on[b] != 0 are built from `g`; in step i a row that is not
+ * done and has emit[i][b] != 0 appends tokens[i][b] to its output, then the advance runs; steps_out [steps][B][4]
+ * receives {state, seen, status, done} of every row after every step. */
+dsocr_status dsocr_k_guided_advance(int B, int steps, const dsocr_guided* g, const int* on, const int* tokens,
+                                    const uint8_t* emit, int* steps_out);
 /* launch_dec_ngram_window once on host rows: logits [B][ld] (in / out), ctx [B][ctx_cap], ctx_len [B] and one record
  * pointer per row (an entry may be NULL: off).  plain >= 2: a row whose record is off is banned as {plain, unbounded
  * window, no whitelist}; else it is left alone. */
