@@ -14,6 +14,7 @@
 #include <memory>
 #include <sstream>
 #include <string>
+#include <utility>
 
 #include "../common/host_util.hpp"
 #include "dots.hpp"
@@ -22,11 +23,7 @@
 
 struct dsocr_engine {
     std::unique_ptr<dsocr::Engine> impl;
-    dsocr::LogitBias staged_bias;  // dsocr_session_stage_logit_bias: consumed by the next admission call
-    dsocr::StopSet staged_stop;    // dsocr_session_stage_stop: the same
-    dsocr::Penalties staged_pen;   // dsocr_session_stage_penalties: the same
-    dsocr::NgramWindow staged_ngw; // dsocr_session_stage_ngram_window: the same
-    dsocr::Guided staged_guided;   // dsocr_session_stage_guided: the same
+    dsocr::Controls staged;  // the dsocr_session_stage_* calls fill it: consumed by the next admission call
 };
 struct dsocr_page_pixels {
     dsocr::PagePixels px;
@@ -234,48 +231,51 @@ dsocr::Guided to_guided(const dsocr_guided* gd, int vocab, long long eos) {
     return g;
 }
 
-// a session admission's request: the staged constraint, stop set, penalties, windowed ban and automaton move into it
-// (consumed whatever the admission does)
+// a session admission's request: the staged controls move into it (consumed whatever the admission does)
 dsocr::GenRequest to_admission(dsocr_engine* e, const dsocr_request& r) {
-    dsocr::Guided gd = std::move(e->staged_guided);
-    e->staged_guided = dsocr::Guided();
-    dsocr::NgramWindow nw = std::move(e->staged_ngw);
-    e->staged_ngw = dsocr::NgramWindow();
-    const dsocr::Penalties pn = e->staged_pen;
-    e->staged_pen = dsocr::Penalties();
-    dsocr::LogitBias b = std::move(e->staged_bias);
-    e->staged_bias = dsocr::LogitBias();
-    dsocr::StopSet st = std::move(e->staged_stop);
-    e->staged_stop = dsocr::StopSet();
+    dsocr::Controls c = std::exchange(e->staged, dsocr::Controls());
     dsocr::GenRequest g = to_request(r);
-    g.bias = std::move(b);
-    g.stops = std::move(st);
-    g.pen = pn;
-    g.ngw = std::move(nw);
-    g.guided = std::move(gd);
+    g.ctl = std::move(c);
     return g;
 }
 
+// What every dsocr_session_stage_* call does with its control: the staged one is cleared, then `convert` (a to_*
+// above: conversion and checks) gives the new one, which needs a session opened with `feature`
+template <typename T, typename Convert>
+void stage_control(dsocr_engine* e, T dsocr::Controls::*member, bool dsocr::Engine::SessionFeatures::*feature,
+                   const char* flag, Convert convert) {
+    if (!e) throw std::runtime_error("EINVAL: NULL argument");
+    e->staged.*member = T();
+    dsocr::Engine::SessionInfo si;
+    if (!e->impl->session_info(&si)) throw std::runtime_error("EINVAL: no decode session is open on this engine");
+    T v = convert((size_t)e->impl->cfg().lang.vocab);
+    if (v.active() && !(si.feat.*feature)) throw std::runtime_error(std::string("EINVAL: this session was opened without ") + flag);
+    e->staged.*member = std::move(v);
+}
+
 // the DSOCR_SESSION_* feature bits as the engine takes them, and back (DSOCR_SESSION_ADMIT_PENDING is state, not one of them)
+const struct { uint32_t bit; bool dsocr::Engine::SessionFeatures::*member; } kSessionFeatures[] = {
+    {DSOCR_SESSION_PER_REQUEST, &dsocr::Engine::SessionFeatures::per_request},
+    {DSOCR_SESSION_LOGPROBS, &dsocr::Engine::SessionFeatures::logprobs},
+    {DSOCR_SESSION_LOGIT_BIAS, &dsocr::Engine::SessionFeatures::logit_bias},
+    {DSOCR_SESSION_STOP, &dsocr::Engine::SessionFeatures::stops},
+    {DSOCR_SESSION_PENALTIES, &dsocr::Engine::SessionFeatures::penalties},
+    {DSOCR_SESSION_NGRAM_WINDOW, &dsocr::Engine::SessionFeatures::ngram_window},
+    {DSOCR_SESSION_GUIDED, &dsocr::Engine::SessionFeatures::guided},
+};
 dsocr::Engine::SessionFeatures to_features(uint32_t flags) {
-    if (flags & ~(uint32_t)(DSOCR_SESSION_PER_REQUEST | DSOCR_SESSION_LOGPROBS | DSOCR_SESSION_LOGIT_BIAS | DSOCR_SESSION_STOP |
-                             DSOCR_SESSION_PENALTIES | DSOCR_SESSION_NGRAM_WINDOW | DSOCR_SESSION_GUIDED))
-        throw std::runtime_error("EINVAL: unknown session flags");
     dsocr::Engine::SessionFeatures f;
-    f.per_request = (flags & DSOCR_SESSION_PER_REQUEST) != 0;
-    f.logprobs = (flags & DSOCR_SESSION_LOGPROBS) != 0;
-    f.logit_bias = (flags & DSOCR_SESSION_LOGIT_BIAS) != 0;
-    f.stops = (flags & DSOCR_SESSION_STOP) != 0;
-    f.penalties = (flags & DSOCR_SESSION_PENALTIES) != 0;
-    f.ngram_window = (flags & DSOCR_SESSION_NGRAM_WINDOW) != 0;
-    f.guided = (flags & DSOCR_SESSION_GUIDED) != 0;
+    for (const auto& k : kSessionFeatures) {
+        f.*k.member = (flags & k.bit) != 0;
+        flags &= ~k.bit;
+    }
+    if (flags) throw std::runtime_error("EINVAL: unknown session flags");
     return f;
 }
 uint32_t feature_flags(const dsocr::Engine::SessionFeatures& f) {
-    return (f.per_request ? DSOCR_SESSION_PER_REQUEST : 0u) | (f.logprobs ? DSOCR_SESSION_LOGPROBS : 0u) |
-           (f.logit_bias ? DSOCR_SESSION_LOGIT_BIAS : 0u) | (f.stops ? DSOCR_SESSION_STOP : 0u) |
-           (f.penalties ? DSOCR_SESSION_PENALTIES : 0u) | (f.ngram_window ? DSOCR_SESSION_NGRAM_WINDOW : 0u) |
-           (f.guided ? DSOCR_SESSION_GUIDED : 0u);
+    uint32_t flags = 0;
+    for (const auto& k : kSessionFeatures) flags |= f.*k.member ? k.bit : 0u;
+    return flags;
 }
 
 // ---- generate: the exported forms marshal through generate_page (one page, the stream callback) or generate_pages
@@ -321,7 +321,7 @@ void generate_page(dsocr_engine* e, const dsocr_request* req, const dsocr_decode
                    size_t* n_out, dsocr_stop_hit* hit) {
     if (!e || !req || !out_ids || !n_out) throw std::runtime_error("EINVAL: NULL argument");
     std::vector<dsocr::GenRequest> reqs{to_request(*req)};
-    reqs[0].stops = to_stops(stops, (size_t)e->impl->cfg().lang.vocab);
+    reqs[0].ctl.stops = to_stops(stops, (size_t)e->impl->cfg().lang.vocab);
     auto r = e->impl->generate(reqs, to_params(params), cb, user);
     if (r[0].size() > cap) throw std::runtime_error("EINVAL: output capacity too small");
     std::memcpy(out_ids, r[0].data(), r[0].size() * sizeof(int64_t));
@@ -369,11 +369,12 @@ void generate_pages(dsocr_engine* e, size_t n, const dsocr_request* reqs, const 
     std::vector<dsocr::GenRequest> rq;
     for (size_t i = 0; i < n; ++i) {
         rq.push_back(to_request(reqs[i]));
-        if (x.bias) rq.back().bias = to_bias(x.bias[i], vocab);
-        if (x.stops) rq.back().stops = to_stops(x.stops[i], vocab);
-        if (x.pen) rq.back().pen = to_penalties(x.pen[i]);
-        if (x.ngw) rq.back().ngw = to_ngram_window(x.ngw[i], vocab);
-        if (x.guided) rq.back().guided = to_guided(x.guided[i], (int)vocab, !params || params->ignore_eos ? -1 : (long long)params->eos_token_id);
+        dsocr::Controls& c = rq.back().ctl;
+        if (x.bias) c.bias = to_bias(x.bias[i], vocab);
+        if (x.stops) c.stops = to_stops(x.stops[i], vocab);
+        if (x.pen) c.pen = to_penalties(x.pen[i]);
+        if (x.ngw) c.ngw = to_ngram_window(x.ngw[i], vocab);
+        if (x.guided) c.guided = to_guided(x.guided[i], (int)vocab, !params || params->ignore_eos ? -1 : (long long)params->eos_token_id);
     }
     dsocr::GenParams g = to_params(params);
     g.trace = x.logits_out;
@@ -639,20 +640,11 @@ dsocr_status dsocr_generate_logprobs(dsocr_engine* e, size_t n, const dsocr_requ
     });
 }
 
+// (the narrower control forms are the widest one with NULL lists)
 dsocr_status dsocr_generate_stop(dsocr_engine* e, size_t n, const dsocr_request* reqs, const dsocr_decode_params* params,
                                  dsocr_result* results, const dsocr_stop_set* const* stops, dsocr_stop_hit* hits,
                                  const dsocr_logit_bias* const* bias, size_t top_k, dsocr_logprobs* lp) {
-    return guarded([&] {
-        if (!params) throw std::runtime_error("EINVAL: NULL argument");
-        GenExtras x;
-        x.stops = stops;
-        x.hits = hits;
-        x.bias = bias;
-        x.lp_on = lp != nullptr;  // (top_k without lp is refused)
-        x.top_k = top_k;
-        x.lp = lp;
-        generate_pages(e, n, reqs, params, results, x);
-    });
+    return dsocr_generate_guided(e, n, reqs, params, results, nullptr, nullptr, nullptr, nullptr, stops, hits, bias, top_k, lp);
 }
 
 dsocr_status dsocr_generate_penalties(dsocr_engine* e, size_t n, const dsocr_request* reqs,
@@ -660,18 +652,7 @@ dsocr_status dsocr_generate_penalties(dsocr_engine* e, size_t n, const dsocr_req
                                       const dsocr_penalties* const* pen, const dsocr_stop_set* const* stops,
                                       dsocr_stop_hit* hits, const dsocr_logit_bias* const* bias, size_t top_k,
                                       dsocr_logprobs* lp) {
-    return guarded([&] {
-        if (!params) throw std::runtime_error("EINVAL: NULL argument");
-        GenExtras x;
-        x.pen = pen;
-        x.stops = stops;
-        x.hits = hits;
-        x.bias = bias;
-        x.lp_on = lp != nullptr;  // (top_k without lp is refused)
-        x.top_k = top_k;
-        x.lp = lp;
-        generate_pages(e, n, reqs, params, results, x);
-    });
+    return dsocr_generate_guided(e, n, reqs, params, results, nullptr, nullptr, nullptr, pen, stops, hits, bias, top_k, lp);
 }
 
 dsocr_status dsocr_generate_ngram_window(dsocr_engine* e, size_t n, const dsocr_request* reqs,
@@ -679,19 +660,7 @@ dsocr_status dsocr_generate_ngram_window(dsocr_engine* e, size_t n, const dsocr_
                                          const dsocr_ngram_window* const* ngw, const dsocr_penalties* const* pen,
                                          const dsocr_stop_set* const* stops, dsocr_stop_hit* hits,
                                          const dsocr_logit_bias* const* bias, size_t top_k, dsocr_logprobs* lp) {
-    return guarded([&] {
-        if (!params) throw std::runtime_error("EINVAL: NULL argument");
-        GenExtras x;
-        x.ngw = ngw;
-        x.pen = pen;
-        x.stops = stops;
-        x.hits = hits;
-        x.bias = bias;
-        x.lp_on = lp != nullptr;  // (top_k without lp is refused)
-        x.top_k = top_k;
-        x.lp = lp;
-        generate_pages(e, n, reqs, params, results, x);
-    });
+    return dsocr_generate_guided(e, n, reqs, params, results, nullptr, nullptr, ngw, pen, stops, hits, bias, top_k, lp);
 }
 
 dsocr_status dsocr_ngram_window_check(const dsocr_ngram_window* ngw, size_t vocab) {
@@ -703,14 +672,8 @@ dsocr_status dsocr_ngram_window_check(const dsocr_ngram_window* ngw, size_t voca
 
 dsocr_status dsocr_session_stage_ngram_window(dsocr_engine* e, const dsocr_ngram_window* ngw) {
     return guarded([&] {
-        if (!e) throw std::runtime_error("EINVAL: NULL argument");
-        e->staged_ngw = dsocr::NgramWindow();
-        dsocr::Engine::SessionInfo si;
-        if (!e->impl->session_info(&si)) throw std::runtime_error("EINVAL: no decode session is open on this engine");
-        dsocr::NgramWindow w = to_ngram_window(ngw, (size_t)e->impl->cfg().lang.vocab);
-        if (w.active() && !si.feat.ngram_window)
-            throw std::runtime_error("EINVAL: this session was opened without DSOCR_SESSION_NGRAM_WINDOW");
-        e->staged_ngw = std::move(w);
+        stage_control(e, &dsocr::Controls::ngw, &dsocr::Engine::SessionFeatures::ngram_window, "DSOCR_SESSION_NGRAM_WINDOW",
+                      [&](size_t vocab) { return to_ngram_window(ngw, vocab); });
     });
 }
 
@@ -746,14 +709,8 @@ dsocr_status dsocr_guided_check(const dsocr_guided* g, int vocab, long long eos)
 
 dsocr_status dsocr_session_stage_guided(dsocr_engine* e, const dsocr_guided* g) {
     return guarded([&] {
-        if (!e) throw std::runtime_error("EINVAL: NULL argument");
-        e->staged_guided = dsocr::Guided();
-        dsocr::Engine::SessionInfo si;
-        if (!e->impl->session_info(&si)) throw std::runtime_error("EINVAL: no decode session is open on this engine");
-        dsocr::Guided gd = to_guided(g, e->impl->cfg().lang.vocab, -1);  // (the EOS rule: the admission's own check)
-        if (gd.active() && !si.feat.guided)
-            throw std::runtime_error("EINVAL: this session was opened without DSOCR_SESSION_GUIDED");
-        e->staged_guided = std::move(gd);
+        stage_control(e, &dsocr::Controls::guided, &dsocr::Engine::SessionFeatures::guided, "DSOCR_SESSION_GUIDED",
+                      [&](size_t vocab) { return to_guided(g, (int)vocab, -1); });  // (the EOS rule: the admission's own check)
     });
 }
 
@@ -772,13 +729,8 @@ dsocr_status dsocr_penalties_check(const dsocr_penalties* pen) {
 
 dsocr_status dsocr_session_stage_penalties(dsocr_engine* e, const dsocr_penalties* pen) {
     return guarded([&] {
-        if (!e) throw std::runtime_error("EINVAL: NULL argument");
-        e->staged_pen = dsocr::Penalties();
-        dsocr::Engine::SessionInfo si;
-        if (!e->impl->session_info(&si)) throw std::runtime_error("EINVAL: no decode session is open on this engine");
-        const dsocr::Penalties p = to_penalties(pen);
-        if (p.active() && !si.feat.penalties) throw std::runtime_error("EINVAL: this session was opened without DSOCR_SESSION_PENALTIES");
-        e->staged_pen = p;
+        stage_control(e, &dsocr::Controls::pen, &dsocr::Engine::SessionFeatures::penalties, "DSOCR_SESSION_PENALTIES",
+                      [&](size_t) { return to_penalties(pen); });
     });
 }
 
@@ -804,13 +756,8 @@ dsocr_status dsocr_stop_set_check(const dsocr_stop_set* ss, size_t vocab) {
 
 dsocr_status dsocr_session_stage_stop(dsocr_engine* e, const dsocr_stop_set* ss) {
     return guarded([&] {
-        if (!e) throw std::runtime_error("EINVAL: NULL argument");
-        e->staged_stop = dsocr::StopSet();
-        dsocr::Engine::SessionInfo si;
-        if (!e->impl->session_info(&si)) throw std::runtime_error("EINVAL: no decode session is open on this engine");
-        dsocr::StopSet st = to_stops(ss, (size_t)e->impl->cfg().lang.vocab);
-        if (st.active() && !si.feat.stops) throw std::runtime_error("EINVAL: this session was opened without DSOCR_SESSION_STOP");
-        e->staged_stop = std::move(st);
+        stage_control(e, &dsocr::Controls::stops, &dsocr::Engine::SessionFeatures::stops, "DSOCR_SESSION_STOP",
+                      [&](size_t vocab) { return to_stops(ss, vocab); });
     });
 }
 
@@ -832,13 +779,8 @@ dsocr_status dsocr_stop_launches(const dsocr_engine* e, size_t* n) {
 
 dsocr_status dsocr_session_stage_logit_bias(dsocr_engine* e, const dsocr_logit_bias* lb) {
     return guarded([&] {
-        if (!e) throw std::runtime_error("EINVAL: NULL argument");
-        e->staged_bias = dsocr::LogitBias();
-        dsocr::Engine::SessionInfo si;
-        if (!e->impl->session_info(&si)) throw std::runtime_error("EINVAL: no decode session is open on this engine");
-        dsocr::LogitBias b = to_bias(lb, (size_t)e->impl->cfg().lang.vocab);
-        if (b.active() && !si.feat.logit_bias) throw std::runtime_error("EINVAL: this session was opened without DSOCR_SESSION_LOGIT_BIAS");
-        e->staged_bias = std::move(b);
+        stage_control(e, &dsocr::Controls::bias, &dsocr::Engine::SessionFeatures::logit_bias, "DSOCR_SESSION_LOGIT_BIAS",
+                      [&](size_t vocab) { return to_bias(lb, vocab); });
     });
 }
 

@@ -172,11 +172,9 @@ struct Engine::Session {
     bool screened = false;  // fixed parameters: the screened head at every n (else the exact head at every n)
     int* stage = nullptr;   // ss_stage: an admission's staged slot rows
     struct Slot {
-        bool stopped = false;  // the slot's request carried a stop set (rows_.stop_n[slot] != 0)
-        bool biased = false;  // the slot's device flag (rows_.bias_on): its request carried a constraint
-        bool penalised = false;  // the slot's device record (rows_.pen) is on
-        bool windowed = false;  // the slot's windowed-ban record (rows_.ngw) is on
-        bool guided = false;    // the slot's automaton flag (rows_.g_on), with the sizes a move copies
+        // Controls::active() of the slot's page: which of its device flags / records are on (rows_.bias_on, stop_n,
+        // pen, ngw, g_on), and the automaton's sizes, which a move copies
+        unsigned ctl = 0;
         int g_states = 0;
         long g_edges = 0;
         size_t max_new = 0;
@@ -200,6 +198,12 @@ struct Engine::Session {
     int next_handle = 1;
     size_t prefix_admissions = 0, prefix_rows_reused = 0;
     std::vector<Slot> slot;
+    // the controls some active slot carries: what a burst's head and step graph depend on
+    unsigned carried() const {
+        unsigned m = 0;
+        for (int b = 0; b < n; ++b) m |= slot[b].ctl;
+        return m;
+    }
     std::shared_ptr<PendingAdmit> pending;  // a chunked admission in flight, staged in slot S - 1 (session_admit_begin)
     int next_ticket = 1;
     // the step for n active pages under the [exact, screened] head, [without, with] the stop match launch,
@@ -1786,22 +1790,30 @@ void Engine::decode_head(int B, DecSampleArgs& sa, const SampleArgs& pen, bool s
     }
     launch_dec_gemv(g, st);
     if (trace_) launch_trace_logits(sa.logits, B, L.vocab, sa.ld, sa.out_len, sa.done, trace_, trace_steps_, st);
-    if (rows_.bias) launch_dec_logit_bias(bias_args(sa, 0), st);  // l' = l + b: what everything below reads
-    if (rows_.g_on) launch_dec_guided_mask(guided_mask_args(sa, 0), st);  // -inf wherever the row's state has no edge
-    if (lp) launch_dec_lp_partial(*lp, st);
+    TailPlan t;
+    t.bias = rows_.bias != nullptr; t.guided = rows_.g_on != nullptr; t.penalties = rows_.pen != nullptr;
+    t.stops = stops; t.window = window; t.lp = lp;
+    selection_tail(sa, pen, 0, t);
+}
+
+// The exact selection on logits already formed (the decode step's lm_head, or a prefill's), in the one order every
+// control is defined against
+void Engine::selection_tail(const DecSampleArgs& sa, const SampleArgs& pen, int row0, const TailPlan& t) {
+    hipStream_t st = stream_;
+    if (t.bias) launch_dec_logit_bias(bias_args(sa, row0), st);  // l' = l + b: what everything below reads
+    if (t.guided) launch_dec_guided_mask(guided_mask_args(sa, row0), st);  // -inf wherever the row's state has no edge
+    if (t.lp) launch_dec_lp_partial(*t.lp, st);
     launch_rep_penalty(pen, st);
-    if (rows_.pen) launch_dec_out_penalty(penalty_args(sa, 0), st);  // frequency / presence, per row
-    if (window >= 0) {  // every row's ban in the window launch, the selection without one
-        launch_dec_ngram_window(ngram_window_args(sa, 0, window), st);
-        DecSampleArgs s0 = sa;
+    if (t.penalties) launch_dec_out_penalty(penalty_args(sa, row0), st);  // frequency / presence, per row
+    DecSampleArgs s0 = sa;
+    if (t.window >= 0) {  // every row's ban in the window launch, the selection without one
+        launch_dec_ngram_window(ngram_window_args(sa, row0, t.window), st);
         s0.ngram = 0;  // (per-request rows: a windowed row's RowParams carry ngram 0, the others keep their own ban)
-        launch_dec_sample(s0, st);
-    } else {
-        launch_dec_sample(sa, st);
     }
-    if (rows_.g_on) launch_dec_guided_advance(guided_advance_args(sa, 0), st);  // the appended token's edge
-    if (stops) stop_match(sa, 0);
-    if (lp) launch_dec_lp_final(*lp, st);
+    launch_dec_sample(s0, st);  // the token, its embedding into the row's s_x, the ban list, the KV position
+    if (t.guided) launch_dec_guided_advance(guided_advance_args(sa, row0), st);  // the appended token's edge
+    if (t.stops) stop_match(sa, row0);
+    if (t.lp) launch_dec_lp_final(*t.lp, st);
 }
 
 // ---- the decode rows (engine.hpp DecodeRows).  Every buffer below has its size in this one function; the names
@@ -2045,11 +2057,11 @@ void validate_ngram_window(const NgramWindow& nw, int vocab) {
 }
 
 // (one record per row in the staging buffer, as for the penalties)
-void Engine::write_ngram_windows(const NgramWindow* const* nw, int row0, int n) {
+void Engine::write_ngram_windows(const GenRequest* reqs, int row0, int n) {
     const DecodeRows& r = rows_;
     if (!r.ngw) throw std::runtime_error("EINTERNAL: no n-gram window records are reserved");
     NgramWindowRec* h = (NgramWindowRec*)pinned("s_ngwstage", sizeof(NgramWindowRec) * (size_t)r.S);
-    for (int i = 0; i < n; ++i) h[row0 + i] = nw[i] ? nw[i]->rec() : NgramWindowRec();
+    for (int i = 0; i < n; ++i) h[row0 + i] = reqs[i].ctl.ngw.rec();
     HIP_CHECK(hipMemcpyAsync(r.ngw + row0, h + row0, sizeof(NgramWindowRec) * (size_t)n, hipMemcpyHostToDevice, stream_));
 }
 
@@ -2061,11 +2073,11 @@ void validate_penalties(const Penalties& pn) {
 }
 
 // (the staging buffer holds one record per row: rows written between two synchronisations do not overlap)
-void Engine::write_penalties(const Penalties* const* pn, int row0, int n) {
+void Engine::write_penalties(const GenRequest* reqs, int row0, int n) {
     const DecodeRows& r = rows_;
     if (!r.pen) throw std::runtime_error("EINTERNAL: no penalty records are reserved");
     PenaltyRec* h = (PenaltyRec*)pinned("s_penstage", sizeof(PenaltyRec) * (size_t)r.S);
-    for (int i = 0; i < n; ++i) h[row0 + i] = pn[i] ? pn[i]->rec() : PenaltyRec();
+    for (int i = 0; i < n; ++i) h[row0 + i] = reqs[i].ctl.pen.rec();
     HIP_CHECK(hipMemcpyAsync(r.pen + row0, h + row0, sizeof(PenaltyRec) * (size_t)n, hipMemcpyHostToDevice, stream_));
 }
 
@@ -2233,6 +2245,36 @@ void Engine::build_stop_table(const StopSet& stp, int row, int stage_row) {
     launch_stop_table_build(a, stream_);
 }
 
+void Controls::validate(int vocab, long eos) const {
+    if (bias.active()) validate_logit_bias(bias, vocab);  // (a record that is off passes the other four)
+    validate_stop_set(stops, vocab);
+    validate_penalties(pen);
+    validate_ngram_window(ngw, vocab);
+    validate_guided(guided, vocab, eos);
+}
+
+// Every write goes to a buffer that no launch of the selection tail before its own reads, so all of them can precede
+// the tail.  A request without a control clears the row's flag / count or writes an off record.  The caller
+// synchronises before the staging regions are reused
+void Engine::write_controls(const GenRequest* reqs, int row0, int n, long eos) {
+    const DecodeRows& r = rows_;
+    size_t bias_off = 0, guided_off = 0;
+    for (int i = 0; i < n; ++i) {
+        const Controls& c = reqs[i].ctl;
+        if (r.bias) {
+            build_logit_bias(c.bias, row0 + i, bias_off);
+            bias_off += c.bias.ids.size();
+        }
+        if (r.g_on) {
+            build_guided(c.guided, row0 + i, guided_off, eos);
+            if (c.guided.active()) guided_off += guided_stage_ints(c.guided.n_states, c.guided.edges());
+        }
+        if (r.stop_tab) build_stop_table(c.stops, row0 + i, i);
+    }
+    if (r.pen) write_penalties(reqs, row0, n);
+    if (r.ngw) write_ngram_windows(reqs, row0, n);
+}
+
 // rand_core 0.6.4 SeedableRng::seed_from_u64 for ChaCha12Rng (rand 0.8.5 StdRng): the 32-byte key
 // is filled by PCG32 (state advanced first, XSH-RR output, little-endian words); block counter 0,
 // stream 0, empty result buffer (sampling.hip reads this layout)
@@ -2280,71 +2322,35 @@ std::vector<std::vector<int64_t>> Engine::generate(const std::vector<GenRequest>
     if (p.lp_k > LP_MAX_TOP) throw std::runtime_error("EINVAL: at most 20 alternatives per token (DSOCR_MAX_TOP_LOGPROBS)");
     if (p.lp_k >= 0 && !p.use_cache) throw std::runtime_error("EINVAL: log-probabilities need the K/V cache (use_cache = 1)");
     last_lp_ = LogprobRows();
-    // constraints: every check before any device work
-    bool any_bias = false;
-    for (const GenRequest& rq : reqs) {
-        if (!rq.bias.active()) continue;
-        any_bias = true;
-        validate_logit_bias(rq.bias, cfg_.lang.vocab);
-    }
-    if (any_bias && (!p.use_cache || p.trace))
-        throw std::runtime_error("EINVAL: a logit bias needs the K/V cache (use_cache = 1) and no logits trace");
-    // stop sets: the same
     last_stop_hits_.clear();
-    bool any_stop = false;
-    for (const GenRequest& rq : reqs) {
-        if (!rq.stops.active()) continue;
-        any_stop = true;
-        validate_stop_set(rq.stops, cfg_.lang.vocab);
-    }
-    if (any_stop && (!p.use_cache || p.trace))
-        throw std::runtime_error("EINVAL: stop sequences need the K/V cache (use_cache = 1) and no logits trace");
-    if (any_stop) {  // (refused on the switch itself, whether or not the persistent step would fit this model and batch)
-        const char* e = getenv("DSOCR_PERSIST");
-        if (e && atoi(e) != 0)
-            throw std::runtime_error("EINVAL: stop sequences do not combine with the persistent decode step (DSOCR_PERSIST)");
-    }
-    // penalties: the same (a record that is off asks for nothing)
-    bool any_pen = false;
-    for (const GenRequest& rq : reqs) {
-        validate_penalties(rq.pen);
-        any_pen = any_pen || rq.pen.active();
-    }
-    // (no exported form passes a trace together with a record; the check guards the engine's own interface)
-    if (any_pen && (!p.use_cache || p.trace))
-        throw std::runtime_error("EINVAL: penalties need the K/V cache (use_cache = 1) and no logits trace");
-    if (any_pen) {
-        const char* e = getenv("DSOCR_PERSIST");
-        if (e && atoi(e) != 0)
-            throw std::runtime_error("EINVAL: penalties do not combine with the persistent decode step (DSOCR_PERSIST)");
-    }
-    // a windowed n-gram ban: the same
-    bool any_ngw = false;
-    for (const GenRequest& rq : reqs) {
-        validate_ngram_window(rq.ngw, cfg_.lang.vocab);
-        any_ngw = any_ngw || rq.ngw.active();
-    }
-    if (any_ngw && (!p.use_cache || p.trace))
-        throw std::runtime_error("EINVAL: a windowed n-gram ban needs the K/V cache (use_cache = 1) and no logits trace");
-    if (any_ngw) {
-        const char* e = getenv("DSOCR_PERSIST");
-        if (e && atoi(e) != 0)
-            throw std::runtime_error("EINVAL: a windowed n-gram ban does not combine with the persistent decode step (DSOCR_PERSIST)");
-    }
-    // a token automaton: the same
     last_guided_.clear();
-    bool any_guided = false;
+    // the controls: every check before any device work.  Each record, then what the call must offer the ones that are
+    // on: the K/V cache, no logits trace, no persistent step.  (The blocks differ on purpose.  A bias is refused
+    // under DSOCR_PERSIST only where the persistent step would really run: reset_decode_state.  No exported form
+    // passes a trace together with a penalty record or a windowed ban, and none can with an automaton: the first two
+    // checks guard the engine's own interface, the third does not exist.)
+    unsigned on = 0;
     for (const GenRequest& rq : reqs) {
-        validate_guided(rq.guided, cfg_.lang.vocab, p.ignore_eos ? -1 : p.eos);
-        any_guided = any_guided || rq.guided.active();
+        rq.ctl.validate(cfg_.lang.vocab, p.ignore_eos ? -1 : p.eos);
+        on |= rq.ctl.active();
     }
-    // (no entry point can pass a logits trace together with an automaton: the trace form takes none)
-    if (any_guided && !p.use_cache)
-        throw std::runtime_error("EINVAL: a token automaton needs the K/V cache (use_cache = 1)");
-    if (any_guided) {
-        const char* e = getenv("DSOCR_PERSIST");
-        if (e && atoi(e) != 0)
-            throw std::runtime_error("EINVAL: a token automaton does not combine with the persistent decode step (DSOCR_PERSIST)");
+    const char* pe = getenv("DSOCR_PERSIST");
+    const bool persist = pe && atoi(pe) != 0;  // (the switch itself, whether or not the step would fit this model and batch)
+    const struct { unsigned bit; bool trace; const char *cache, *persist; } needs[] = {
+        {Controls::BIAS, true, "EINVAL: a logit bias needs the K/V cache (use_cache = 1) and no logits trace", nullptr},
+        {Controls::STOPS, true, "EINVAL: stop sequences need the K/V cache (use_cache = 1) and no logits trace",
+         "EINVAL: stop sequences do not combine with the persistent decode step (DSOCR_PERSIST)"},
+        {Controls::PEN, true, "EINVAL: penalties need the K/V cache (use_cache = 1) and no logits trace",
+         "EINVAL: penalties do not combine with the persistent decode step (DSOCR_PERSIST)"},
+        {Controls::NGW, true, "EINVAL: a windowed n-gram ban needs the K/V cache (use_cache = 1) and no logits trace",
+         "EINVAL: a windowed n-gram ban does not combine with the persistent decode step (DSOCR_PERSIST)"},
+        {Controls::GUIDED, false, "EINVAL: a token automaton needs the K/V cache (use_cache = 1)",
+         "EINVAL: a token automaton does not combine with the persistent decode step (DSOCR_PERSIST)"},
+    };
+    for (const auto& c : needs) {
+        if (!(on & c.bit)) continue;
+        if (!p.use_cache || (c.trace && p.trace)) throw std::runtime_error(c.cache);
+        if (c.persist && persist) throw std::runtime_error(c.persist);
     }
     if (reqs.empty() || p.max_new == 0) return std::vector<std::vector<int64_t>>(reqs.size());
     ensure_small(std::max((int)reqs.size(), 64));
@@ -2543,32 +2549,30 @@ void Engine::reset_decode_state(GenState& g) {
     DecodeRowsSpec spec;
     spec.rows = B; spec.Lcap = g.max_p + (int)p.max_new + 1; spec.ctx_cap = spec.Lcap; spec.out_cap = (long)p.max_new;
     spec.sampler = p.do_sample;
-    // the screened head (exact lm_head instead while sampling, tracing or keeping log-probabilities)
-    // a constrained page: the exact head too, with the bias rows and one staging region per list
-    for (const GenRequest& rq : g.reqs)
-        if (rq.bias.active()) { spec.bias = true; spec.bias_stage += rq.bias.ids.size(); }
-    // a penalised page: the exact head as well, with one record per page
-    for (const GenRequest& rq : g.reqs) spec.penalties = spec.penalties || rq.pen.active();
-    // a page with a windowed n-gram ban: the exact head too, with one record per page
-    for (const GenRequest& rq : g.reqs) spec.ngram_window = spec.ngram_window || rq.ngw.active();
-    // a guided page: the exact head too, with tables sized for the call's largest automaton and one staging region
-    // per page
-    for (const GenRequest& rq : g.reqs)
-        if (rq.guided.active()) {
+    // what the requests' controls ask for, in one pass: the rows of each control some page carries, one staging
+    // region per list / automaton / stop set, automaton tables sized for the call's largest
+    bool exact = false;
+    for (const GenRequest& rq : g.reqs) {
+        const Controls& c = rq.ctl;
+        exact = exact || c.needs_exact_head();
+        if (c.bias.active()) { spec.bias = true; spec.bias_stage += c.bias.ids.size(); }
+        if (c.stops.active()) { spec.stops = true; spec.stop_stage_rows = B; }
+        spec.penalties = spec.penalties || c.pen.active();
+        spec.ngram_window = spec.ngram_window || c.ngw.active();
+        if (c.guided.active()) {
             if (!spec.guided) { spec.guided = true; spec.guided_states = 1; spec.guided_edges = 1; }
-            spec.guided_states = std::max(spec.guided_states, rq.guided.n_states);
-            spec.guided_edges = std::max(spec.guided_edges, rq.guided.edges());
-            spec.guided_stage += guided_stage_ints(rq.guided.n_states, rq.guided.edges());
+            spec.guided_states = std::max(spec.guided_states, c.guided.n_states);
+            spec.guided_edges = std::max(spec.guided_edges, c.guided.edges());
+            spec.guided_stage += guided_stage_ints(c.guided.n_states, c.guided.edges());
         }
-    spec.ban = !p.do_sample && !p.trace && p.lp_k < 0 && !spec.bias && !spec.penalties && !spec.ngram_window &&
-               !spec.guided && screen_applies(B, p.rep_penalty);
+    }
+    // the screened head (exact lm_head instead while sampling, tracing, keeping log-probabilities, or with a control
+    // that acts on the logits row; a stop set runs under whichever head runs without it)
+    spec.ban = !p.do_sample && !p.trace && p.lp_k < 0 && !exact && screen_applies(B, p.rep_penalty);
     // (the side row: dec_lp_final takes an emitted token's raw logit from it wherever a penalty may have rewritten
     // logits[tok]: the repetition penalty at the context ids, the frequency / presence penalty at the generated ones,
     // which the context row holds as well)
     spec.lp_k = p.lp_k; spec.lp_side = rep_penalty_active(p.rep_penalty) || spec.penalties;
-    // stop sets: the stop rows and one staging region per page (the head is whichever runs without them)
-    for (const GenRequest& rq : g.reqs)
-        if (rq.stops.active()) { spec.stops = true; spec.stop_stage_rows = B; }
     ensure_rope(spec.Lcap + 1);
     reserve_decode_rows(spec);
     // one page: the persistent decode step (its granules: no tag of an earlier generate may match this one's)
@@ -2705,53 +2709,20 @@ void Engine::init_sampling(GenState& g) {
         HIP_CHECK(hipMemsetAsync(trace_, 0, sizeof(float) * B * p.max_new * L.vocab, st));
         launch_trace_logits(r.logits, B, L.vocab, L.vocab, r.out_len, r.done, trace_, trace_steps_, st);
     }
-    // log-probabilities: the exact head (no ban rows), an entry for the prefill's own selection too
-    // constraints: every page's dense row from its list, then the add on the prefill's logits
-    if (r.bias) {
-        size_t off = 0;
-        for (int b = 0; b < B; ++b) {
-            build_logit_bias(g.reqs[b].bias, b, off);
-            off += g.reqs[b].bias.ids.size();
-        }
-        launch_dec_logit_bias(bias_args(sa, 0), st);
-    }
-    if (r.g_on) {  // every page's tables from its automaton, then the start state's mask on the prefill's logits
-        size_t off = 0;
-        for (int b = 0; b < B; ++b) {
-            build_guided(g.reqs[b].guided, b, off, p.ignore_eos ? -1 : p.eos);
-            if (g.reqs[b].guided.active()) off += guided_stage_ints(g.reqs[b].guided.n_states, g.reqs[b].guided.edges());
-        }
-        launch_dec_guided_mask(guided_mask_args(sa, 0), st);
-    }
-    const DecLpArgs lp = p.lp_k >= 0 ? lp_args(sa, 0) : DecLpArgs();
-    if (p.lp_k >= 0) launch_dec_lp_partial(lp, st);
-    // the fused selection kernel advances the KV position; after the prefill the first
-    // decode position must be P, so start one behind
-    launch_rep_penalty(pen, st);
-    if (r.pen) {  // every page's record, then the penalty on the prefill's logits (out_len is 0: only min-p can act)
-        std::vector<const Penalties*> pn(B);
-        for (int b = 0; b < B; ++b) pn[b] = &g.reqs[b].pen;
-        write_penalties(pn.data(), 0, B);
-        launch_dec_out_penalty(penalty_args(sa, 0), st);
-    }
-    if (r.ngw) {  // every page's record, then every page's ban on the prefill's logits; the selection runs without one
-        std::vector<const NgramWindow*> nw(B);
-        for (int b = 0; b < B; ++b) nw[b] = &g.reqs[b].ngw;
-        write_ngram_windows(nw.data(), 0, B);
-        launch_dec_ngram_window(ngram_window_args(sa, 0, p.ngram), st);
-        sa.ngram = 0;
-    }
+    // every page's controls, then the prefill's own selection: the first token of every page (with log-probabilities:
+    // an entry for it too).  The fused selection kernel advances the KV position; after the prefill the first decode
+    // position must be P, so it starts one behind (no launch of the tail before it reads kv_pos / kv_len)
+    write_controls(g.reqs.data(), 0, B, p.ignore_eos ? -1 : p.eos);
     std::vector<int> pm1(B), lm1(B);
     for (int b = 0; b < B; ++b) { pm1[b] = g.kvpos[b] - 1; lm1[b] = g.kvlen[b] - 1; }
     HIP_CHECK(hipMemcpyAsync(r.kv_pos, pm1.data(), B * 4, hipMemcpyHostToDevice, st));
     HIP_CHECK(hipMemcpyAsync(r.kv_len, lm1.data(), B * 4, hipMemcpyHostToDevice, st));
-    launch_dec_sample(sa, st);
-    if (r.g_on) launch_dec_guided_advance(guided_advance_args(sa, 0), st);  // the prefill's own selection advances too
-    if (r.stop_tab) {  // every page's table from its stop set, then the match on the prefill's own selection
-        for (int b = 0; b < B; ++b) build_stop_table(g.reqs[b].stops, b, b);
-        stop_match(sa, 0);
-    }
-    if (p.lp_k >= 0) launch_dec_lp_final(lp, st);
+    const DecLpArgs lp = p.lp_k >= 0 ? lp_args(sa, 0) : DecLpArgs();
+    TailPlan t;
+    t.bias = r.bias != nullptr; t.guided = r.g_on != nullptr; t.penalties = r.pen != nullptr; t.stops = r.stop_tab != nullptr;
+    t.window = r.ngw ? p.ngram : -1;
+    t.lp = p.lp_k >= 0 ? &lp : nullptr;
+    selection_tail(sa, pen, 0, t);
     HIP_CHECK(hipStreamSynchronize(st));
 }
 
@@ -3019,7 +2990,7 @@ std::vector<std::vector<int64_t>> Engine::collect_outputs(GenState& g) {
         HIP_CHECK(hipMemcpy(stat.data(), rows_.g_status, (size_t)B * 4, hipMemcpyDeviceToHost));
         last_guided_.resize((size_t)B * 2);
         for (int b = 0; b < B; ++b) {  // (a page without an automaton: its words were never written past the zero fill)
-            const bool on = g.reqs[b].guided.active();
+            const bool on = g.reqs[b].ctl.guided.active();
             last_guided_[2 * b] = on ? st[b] : 0;
             last_guided_[2 * b + 1] = on ? stat[b] : 0;
         }
@@ -3158,23 +3129,16 @@ void Engine::session_admit_checks(const Session& s, const GenRequest& rq, const 
             throw std::runtime_error("EINVAL: this session's parameters are fixed (only max_new_tokens and the seed vary "
                                      "per request): open it with DSOCR_SESSION_PER_REQUEST");
     }
-    if (rq.bias.active()) {
-        if (!s.feat.logit_bias) throw std::runtime_error("EINVAL: this session was opened without DSOCR_SESSION_LOGIT_BIAS");
-        validate_logit_bias(rq.bias, V);
-    }
-    if (rq.stops.active()) {
-        if (!s.feat.stops) throw std::runtime_error("EINVAL: this session was opened without DSOCR_SESSION_STOP");
-        validate_stop_set(rq.stops, V);
-    }
-    validate_penalties(rq.pen);
-    if (rq.pen.active() && !s.feat.penalties)
-        throw std::runtime_error("EINVAL: this session was opened without DSOCR_SESSION_PENALTIES");
-    validate_ngram_window(rq.ngw, V);
-    if (rq.ngw.active() && !s.feat.ngram_window)
-        throw std::runtime_error("EINVAL: this session was opened without DSOCR_SESSION_NGRAM_WINDOW");
-    validate_guided(rq.guided, V, rp.ignore_eos ? -1 : rp.eos);
-    if (rq.guided.active() && !s.feat.guided)
-        throw std::runtime_error("EINVAL: this session was opened without DSOCR_SESSION_GUIDED");
+    rq.ctl.validate(V, rp.ignore_eos ? -1 : rp.eos);
+    const struct { unsigned bit; bool have; const char* refusal; } feats[] = {
+        {Controls::BIAS, s.feat.logit_bias, "EINVAL: this session was opened without DSOCR_SESSION_LOGIT_BIAS"},
+        {Controls::STOPS, s.feat.stops, "EINVAL: this session was opened without DSOCR_SESSION_STOP"},
+        {Controls::PEN, s.feat.penalties, "EINVAL: this session was opened without DSOCR_SESSION_PENALTIES"},
+        {Controls::NGW, s.feat.ngram_window, "EINVAL: this session was opened without DSOCR_SESSION_NGRAM_WINDOW"},
+        {Controls::GUIDED, s.feat.guided, "EINVAL: this session was opened without DSOCR_SESSION_GUIDED"},
+    };
+    for (const auto& f : feats)
+        if ((rq.ctl.active() & f.bit) && !f.have) throw std::runtime_error(f.refusal);
     if (s.pending) throw std::runtime_error("EINVAL: a chunked admission is pending (advance it to the end or cancel it)");
     if (s.n >= s.S) throw std::runtime_error("EINVAL: every session slot is in use (retire one first)");
     const size_t P = rq.ids.size();
@@ -3229,7 +3193,8 @@ int Engine::session_admit_tail(Session& s, const GenRequest& rq, const GenParams
                                bool finish) {
     // a windowed ban replaces the page's plain one: its RowParams carry ngram 0 from here on
     RowParams row = row_in;
-    const bool windowed = rq.ngw.active();
+    const Controls& c = rq.ctl;
+    const bool windowed = c.ngw.active();
     if (windowed) row.ngram = 0;
     const size_t max_new = rp.max_new, P = rq.ids.size();
     const bool seed_set = rp.seed_set;
@@ -3266,49 +3231,25 @@ int Engine::session_admit_tail(Session& s, const GenRequest& rq, const GenParams
         lp = lp_args(sa, slot);
     }
     launch_session_slot_init(ia, st);
-    if (s.feat.logit_bias) {  // the slot's constraint (none: the flag alone is cleared), then the add on the prefill's logits
-        build_logit_bias(rq.bias, slot, 0);
-        launch_dec_logit_bias(bias_args(sa, slot), st);
-    }
-    if (s.feat.guided) {  // the slot's tables (none: the flag alone is cleared), then the start state's mask
-        build_guided(rq.guided, slot, 0, rp.ignore_eos ? -1 : rp.eos);
-        if (rq.guided.active()) launch_dec_guided_mask(guided_mask_args(sa, slot), st);
-    }
-    if (s.feat.logprobs) launch_dec_lp_partial(lp, st);
-    launch_rep_penalty(pen, st);
-    if (s.feat.penalties) {  // the slot's record (none: an off record), then the penalty on the prefill's logits
-        const Penalties* pn = &rq.pen;
-        write_penalties(&pn, slot, 1);
-        launch_dec_out_penalty(penalty_args(sa, slot), st);
-    }
-    if (s.feat.ngram_window) {  // the slot's record (none: an off record); on: its ban on the prefill's logits
-        const NgramWindow* nw = &rq.ngw;
-        write_ngram_windows(&nw, slot, 1);
-        if (windowed) {
-            launch_dec_ngram_window(ngram_window_args(sa, slot, 0), st);
-            sa.ngram = 0;
-        }
-    }
-    launch_dec_sample(sa, st);  // the first token, its embedding into the slot's s_x row, the ban list
-    if (rq.guided.active()) launch_dec_guided_advance(guided_advance_args(sa, slot), st);
-    if (s.feat.stops) {  // the slot's table (none: the count alone is cleared), then the match on this first selection
-        build_stop_table(rq.stops, slot, 0);
-        if (rq.stops.active()) stop_match(sa, slot);
-    }
-    if (s.feat.logprobs) launch_dec_lp_final(lp, st);  // entry 0 of the slot
+    // the slot's controls (none: the flag or count alone is cleared, or an off record written), then the first
+    // selection on the prefill's logits: the first token, its embedding into the slot's s_x row, the ban list, entry 0
+    // of the slot's log-probabilities.  The mask, the advance, the window ban and the match run only for a request that
+    // carries the control
+    write_controls(&rq, slot, 1, rp.ignore_eos ? -1 : rp.eos);
+    TailPlan t;
+    t.bias = s.feat.logit_bias; t.guided = c.guided.active(); t.penalties = s.feat.penalties; t.stops = c.stops.active();
+    t.window = windowed ? 0 : -1;
+    t.lp = s.feat.logprobs ? &lp : nullptr;
+    selection_tail(sa, pen, slot, t);
     if (finish) {  // (else the caller has a launch to add before the one refill and synchronisation)
         refill_handoffs();
         HIP_CHECK(hipStreamSynchronize(st));
     }
     Session::Slot& sl = s.slot[slot];
     sl.max_new = max_new; sl.kv_pos = (int)P; sl.reported = 0; sl.rp = row; sl.prompt = (int)P;
-    sl.biased = rq.bias.active();
-    sl.penalised = rq.pen.active();
-    sl.windowed = windowed;
-    sl.guided = rq.guided.active();
-    sl.g_states = rq.guided.n_states;
-    sl.g_edges = rq.guided.edges();
-    sl.stopped = rq.stops.active();
+    sl.ctl = c.active();
+    sl.g_states = c.guided.n_states;
+    sl.g_edges = c.guided.edges();
     sl.ids = rq.ids;
     sl.mask = rq.mask.empty() ? std::vector<uint8_t>(P, 0) : rq.mask;
     if (at < 0) ++s.n;
@@ -3536,10 +3477,9 @@ void Engine::session_step_body(Session& s, bool screened, bool stops, bool windo
 // the head of the next burst.  Fixed parameters: decided at session_open.  Per request: screened iff every active
 // slot is greedy with penalty 1.0 and the screened head applies at this n; it changes only where the set of
 // active slots does (admit, retire), and the ban rows both final kernels keep make the change a step boundary
-bool Engine::session_head_screened(const Session& s) const {
+bool Engine::session_head_screened(const Session& s, unsigned carried) const {
     if (s.feat.logprobs) return false;  // the screened head never forms the logits
-    for (int b = 0; b < s.n; ++b)
-        if (s.slot[b].biased || s.slot[b].penalised || s.slot[b].windowed || s.slot[b].guided) return false;  // ... which a constraint, a penalty, a windowed ban or an automaton acts on
+    if (carried & Controls::EXACT_HEAD) return false;  // ... which a constraint, a penalty, a windowed ban or an automaton acts on
     if (!s.feat.per_request) return s.screened;
     for (int b = 0; b < s.n; ++b)
         if (s.slot[b].rp.do_sample || s.slot[b].rp.rep_penalty != 1.0f) return false;
@@ -3565,12 +3505,11 @@ std::vector<Engine::SlotStatus> Engine::session_step(int k) {
     // a windowed ban is part of the step iff an active slot carries one.  With fixed parameters such a step runs
     // every selection at ngram 0, so the ban lists it leaves for a screened head are empty: the burst after it
     // runs the exact head once more, which writes them again
-    bool windowed = false;
-    for (int b = 0; b < s.n; ++b) windowed = windowed || s.slot[b].windowed;
-    const bool screened = session_head_screened(s) && !s.ban_stale;
+    const unsigned carried = s.carried();
+    const bool windowed = (carried & Controls::NGW) != 0;
+    const bool screened = session_head_screened(s, carried) && !s.ban_stale;
     // the match launch is part of the step iff an active slot carries a stop set: resolved here, once per burst
-    bool stops = false;
-    for (int b = 0; b < s.n; ++b) stops = stops || s.slot[b].stopped;
+    const bool stops = (carried & Controls::STOPS) != 0;
     HipGraphExec& graph = s.graph[s.n][screened ? 1 : 0][stops ? 1 : 0][windowed ? 1 : 0];
     if (use_graph && !graph) {
         StreamCapture cap(st, capturing_);
@@ -3656,7 +3595,7 @@ void Engine::session_slot_move(Session& s, int src, int dst, int rows_bound) {
     if (s.feat.logprobs) { m.lp = r.lp; m.lp_top_id = r.lp_top_id; m.lp_top = r.lp_top; m.lp_k = r.lp_k; }
     launch_session_slot_move(m, stream_);
     if (s.feat.logit_bias) {  // the constraint travels as a copy of its row (an unconstrained page: the flag alone)
-        if (s.slot[src].biased)
+        if (s.slot[src].ctl & Controls::BIAS)
             HIP_CHECK(hipMemcpyAsync(r.bias + (size_t)dst * r.bias_ld, r.bias + (size_t)src * r.bias_ld,
                                      sizeof(float) * r.bias_ld, hipMemcpyDeviceToDevice, stream_));
         HIP_CHECK(hipMemcpyAsync(r.bias_on + dst, r.bias_on + src, sizeof(int), hipMemcpyDeviceToDevice, stream_));
@@ -3667,8 +3606,8 @@ void Engine::session_slot_move(Session& s, int src, int dst, int rows_bound) {
         HIP_CHECK(hipMemcpyAsync(r.ngw + dst, r.ngw + src, sizeof(NgramWindowRec), hipMemcpyDeviceToDevice, stream_));
     // the automaton travels with its page: the used part of its tables (a page without one: the flag and scalars alone)
     if (s.feat.guided)
-        launch_guided_slot_move(r.guided_tables(), src, dst, s.slot[src].guided ? s.slot[src].g_states : 0,
-                                s.slot[src].guided ? s.slot[src].g_edges : 0, stream_);
+        launch_guided_slot_move(r.guided_tables(), src, dst, (s.slot[src].ctl & Controls::GUIDED) ? s.slot[src].g_states : 0,
+                                (s.slot[src].ctl & Controls::GUIDED) ? s.slot[src].g_edges : 0, stream_);
     // the stop set travels with its page: a launch of its own (a page without one: the count, seen and hit alone)
     if (s.feat.stops) launch_stop_slot_move(r.stop_tab, r.stop_n, r.stop_seen, r.stop_hit, src, dst, stream_);
     s.slot[dst] = s.slot[src];
@@ -3679,7 +3618,7 @@ void Engine::session_guided_state(int slot, int* state, int* status) {
     if (!s.feat.guided) throw std::runtime_error("EINVAL: this session was opened without DSOCR_SESSION_GUIDED");
     if (slot < 0 || slot >= s.n) throw std::runtime_error("EINVAL: slot " + std::to_string(slot) + " is not active");
     int st = 0, stat = 0;
-    if (s.slot[slot].guided) {
+    if (s.slot[slot].ctl & Controls::GUIDED) {
         HIP_CHECK(hipStreamSynchronize(stream_));
         HIP_CHECK(hipMemcpy(&st, rows_.g_state + slot, 4, hipMemcpyDeviceToHost));
         HIP_CHECK(hipMemcpy(&stat, rows_.g_status + slot, 4, hipMemcpyDeviceToHost));

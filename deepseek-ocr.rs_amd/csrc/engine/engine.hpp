@@ -186,12 +186,28 @@ struct Guided {
 // start outside [0, n_states); a terminal start.  (A record that is off passes.)
 void validate_guided(const Guided& g, int vocab, long eos);
 
-struct GenRequest {
+// The per-request decode controls: what a request carries beyond its prompt and GenParams.  A new
+// control is a member here, a step of Engine::write_controls and a launch of Engine::selection_tail.
+struct Controls {
     LogitBias bias;
     StopSet stops;
     Penalties pen;
     NgramWindow ngw;
     Guided guided;
+    // which of them are on, as one mask (a session's slots keep it; a batch's is the OR over its requests)
+    enum : unsigned { BIAS = 1, STOPS = 2, PEN = 4, NGW = 8, GUIDED = 16, EXACT_HEAD = BIAS | PEN | NGW | GUIDED };
+    unsigned active() const {
+        return (bias.active() ? BIAS : 0u) | (stops.active() ? STOPS : 0u) | (pen.active() ? PEN : 0u) |
+               (ngw.active() ? NGW : 0u) | (guided.active() ? GUIDED : 0u);
+    }
+    // the controls that act on the logits row: the screened head never forms it (a stop set runs under either head)
+    bool needs_exact_head() const { return (active() & EXACT_HEAD) != 0; }
+    // every validate_* above (a bias or stop set that is off is not looked at); eos < 0: no EOS rule
+    void validate(int vocab, long eos) const;
+};
+
+struct GenRequest {
+    Controls ctl;
     std::vector<int> ids;
     std::vector<uint8_t> mask;
     const PagePixels* page = nullptr;
@@ -513,11 +529,11 @@ class Engine {
     // the penalty records of the same pages (only where rows_.pen is set), and rows [row0, row0 + n)'s records
     // written from the requests' (pinned staging under "s_penstage"; the caller synchronises before the next write)
     DecPenaltyArgs penalty_args(const DecSampleArgs& sa, int row0);
-    void write_penalties(const Penalties* const* pn, int row0, int n);
+    void write_penalties(const GenRequest* reqs, int row0, int n);
     // the windowed-ban records likewise (only where rows_.ngw is set; staging under "s_ngwstage").  plain: the
     // n-gram size the launch applies, with an unbounded window, to rows whose record is off (0: such rows are skipped)
     DecNgramWindowArgs ngram_window_args(const DecSampleArgs& sa, int row0, int plain);
-    void write_ngram_windows(const NgramWindow* const* nw, int row0, int n);
+    void write_ngram_windows(const GenRequest* reqs, int row0, int n);
     // the automaton rows of the same pages (only where rows_.g_on is set): one row's tables from a request's automaton
     // (staged at stage_off ints of "s_gstage"; the caller synchronises before the region is reused), the mask and the
     // advance launches
@@ -532,6 +548,20 @@ class Engine {
     // stops: the match launch follows the final selection kernel
     void decode_head(int B, DecSampleArgs& sa, const SampleArgs& pen, bool screened, const DecLpArgs* lp = nullptr,
                      bool stops = false, int window = -1);  // window >= 0: the windowed-ban launch, with this plain size
+    // Which launches of the exact selection tail run.  window >= 0: the window launch with this plain size, and the
+    // selection on a copy of sa with ngram = 0
+    struct TailPlan {
+        bool bias = false, guided = false, penalties = false, stops = false;
+        int window = -1;
+        const DecLpArgs* lp = nullptr;
+    };
+    // The one place that issues the exact selection on logits already formed, for the pages from row0 on that sa
+    // describes: bias add, automaton mask, log-prob partial, repetition penalty, output penalty, window ban,
+    // selection, automaton advance, stop match, log-prob final
+    void selection_tail(const DecSampleArgs& sa, const SampleArgs& pen, int row0, const TailPlan& t);
+    // rows [row0, row0 + n)'s bias row, automaton tables, penalty record, window record and stop table from the
+    // requests, each only where rows_ has that buffer; staging offsets are packed from 0 in request order
+    void write_controls(const GenRequest* reqs, int row0, int n, long eos);
     void reserve_head_ws(int B);
     LmHeadQ8Args head_q8_args(int B);
     bool screen_applies(int B, float rep_penalty) const;
@@ -561,7 +591,7 @@ class Engine {
     std::unique_ptr<Session> sess_;
     Session& open_session();
     void session_step_body(Session& s, bool screened, bool stops, bool windowed);
-    bool session_head_screened(const Session& s) const;
+    bool session_head_screened(const Session& s, unsigned carried) const;  // carried: Session::carried()
     // profile_decode: its two timers and the sections after the MoE and attention replays
     double replay_us(int n, const std::function<void()>& body);
     void time_launches(KernelProfile& kp, int n, const std::function<void(int)>& body);

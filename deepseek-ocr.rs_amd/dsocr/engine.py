@@ -489,21 +489,53 @@ class DeepseekOcrEngine:
         check(lib().dsocr_generate_logprobs(self._h, b.n, b.reqs, C.byref(pc), b.res, lp.k, lp.c))
         return (b.ids(), *lp.unpack())
 
+    _NA = object()  # _generate_controls: a list the C form does not take
+
+    def _generate_controls(self, fn, mismatch, requests, params, ignore_eos, top_k, constraints, stop_sets=_NA,
+                           penalties=_NA, ngram_windows=_NA, automata=_NA):
+        """What the generate_* control methods share.  ``fn``: the C entry point; its arguments behind the results are
+        the lists it takes, in the order [automata, guided results, ngram_windows, penalties, stop_sets, stop hits,
+        constraints], then top_k and the log-probability buffers.  A list is one record (or None) per request, None
+        for a NULL list; the first one ``fn`` takes is the method's own and is required.  Returns the ids per page,
+        then the stop hits and the automaton results where ``fn`` has them, then the log-probability lists with
+        ``top_k``; the ids alone when that is all."""
+        na, vocab = self._NA, self.vocab
+        taken = [x for x in (automata, ngram_windows, penalties, stop_sets, constraints) if x is not na]
+        if len(taken[0]) != len(requests) or any(x is not None and len(x) != len(requests) for x in taken[1:]):
+            raise DsocrError(1, mismatch)
+        _check_top_k(top_k)
+        b = _Batch(self, requests, params)
+        hits = None if stop_sets is na else (StopHitC * b.n)()
+        gres = None if automata is na else (GuidedResultC * b.n)()
+        args = []
+        for recs, T, conv, result in ((automata, GuidedC, lambda a, keep: _guided_c(_guided(a, vocab), keep), gres),
+                                      (ngram_windows, NgramWindowC,
+                                       lambda w, keep: _ngram_window_c(_ngram_window(w, vocab), keep), None),
+                                      (penalties, PenaltiesC, lambda pn, keep: _penalties_c(pn), None),
+                                      (stop_sets, StopSetC, _stop_c, hits),
+                                      (constraints, LogitBiasC, _bias_c, None)):
+            if recs is not na:
+                args.append(None if recs is None else _ptr_array(T, [conv(r, b.keep) for r in recs], b.keep))
+                args += [] if result is None else [result]
+        lp = None if top_k is None else _LogprobBuffers(b.n, b.cap, int(top_k))
+        pc = _params_c(params, self.eos_token_id, ignore_eos)
+        check(fn(self._h, b.n, b.reqs, C.byref(pc), b.res, *args, lp.k if lp else 0, lp.c if lp else None))
+        got = [b.ids()]
+        if hits is not None:
+            got.append([(int(h.seq), int(h.match_len)) for h in hits])
+        if gres is not None:
+            got.append([(int(g.state), int(g.status)) for g in gres])
+        if lp:
+            got += lp.unpack()
+        return tuple(got) if len(got) > 1 else got[0]
+
     def generate_constrained(self, requests, constraints, params: DecodeParameters = DecodeParameters(),
                              ignore_eos: bool = False, top_k: Optional[int] = None):
         """generate_batch with one constraint per request (dsocr_generate_logit_bias): ``constraints[i]`` is a
         ``LogitConstraint`` (``dsocr.constraint.merge_constraint``) or None.  Returns the ids per page; with
         ``top_k`` (0..20) the tuple ``generate_logprobs`` returns, of the constrained distribution."""
-        if len(constraints) != len(requests):
-            raise DsocrError(1, "one constraint (or None) per request")
-        _check_top_k(top_k)
-        b = _Batch(self, requests, params)
-        bias = _ptr_array(LogitBiasC, [_bias_c(c, b.keep) for c in constraints], b.keep)
-        lp = None if top_k is None else _LogprobBuffers(b.n, b.cap, int(top_k))
-        pc = _params_c(params, self.eos_token_id, ignore_eos)
-        check(lib().dsocr_generate_logit_bias(self._h, b.n, b.reqs, C.byref(pc), b.res, bias, lp.k if lp else 0,
-                                              lp.c if lp else None))
-        return (b.ids(), *lp.unpack()) if lp else b.ids()
+        return self._generate_controls(lib().dsocr_generate_logit_bias, "one constraint (or None) per request", requests,
+                                       params, ignore_eos, top_k, constraints)
 
     def generate_stops(self, requests, stop_sets, params: DecodeParameters = DecodeParameters(), ignore_eos: bool = False,
                        top_k: Optional[int] = None, constraints=None):
@@ -512,42 +544,16 @@ class DeepseekOcrEngine:
         the ids per page, matched tokens included (the device never trims), and per page ``(seq, match_len)`` with
         ``seq = -1`` when no stop fired; with ``top_k`` (0..20) followed by the three lists ``generate_logprobs``
         returns."""
-        if len(stop_sets) != len(requests) or (constraints is not None and len(constraints) != len(requests)):
-            raise DsocrError(1, "one stop set (or None) per request")
-        _check_top_k(top_k)
-        b = _Batch(self, requests, params)
-        stops = _ptr_array(StopSetC, [_stop_c(ss, b.keep) for ss in stop_sets], b.keep)
-        hits = (StopHitC * b.n)()
-        bias = None
-        if constraints is not None:
-            bias = _ptr_array(LogitBiasC, [_bias_c(c, b.keep) for c in constraints], b.keep)
-        lp = None if top_k is None else _LogprobBuffers(b.n, b.cap, int(top_k))
-        pc = _params_c(params, self.eos_token_id, ignore_eos)
-        check(lib().dsocr_generate_stop(self._h, b.n, b.reqs, C.byref(pc), b.res, stops, hits, bias, lp.k if lp else 0,
-                                        lp.c if lp else None))
-        got = (b.ids(), [(int(h.seq), int(h.match_len)) for h in hits])
-        return (*got, *lp.unpack()) if lp else got
+        return self._generate_controls(lib().dsocr_generate_stop, "one stop set (or None) per request", requests, params,
+                                       ignore_eos, top_k, constraints, stop_sets)
 
     def generate_penalties(self, requests, penalties, params: DecodeParameters = DecodeParameters(),
                            ignore_eos: bool = False, top_k: Optional[int] = None, constraints=None, stop_sets=None):
         """generate_batch with one penalty record per request (dsocr_generate_penalties): ``penalties[i]`` is a
         ``dsocr.penalties.Penalties`` or None; ``constraints`` and ``stop_sets`` likewise (or None for none).  Returns
         what ``generate_stops`` returns: ``(ids, hits)``, with ``top_k`` followed by the three log-probability lists."""
-        n = len(requests)
-        if len(penalties) != n or any(x is not None and len(x) != n for x in (constraints, stop_sets)):
-            raise DsocrError(1, "one penalty record (or None) per request")
-        _check_top_k(top_k)
-        b = _Batch(self, requests, params)
-        pen = _ptr_array(PenaltiesC, [_penalties_c(pn) for pn in penalties], b.keep)
-        stops = None if stop_sets is None else _ptr_array(StopSetC, [_stop_c(ss, b.keep) for ss in stop_sets], b.keep)
-        bias = None if constraints is None else _ptr_array(LogitBiasC, [_bias_c(c, b.keep) for c in constraints], b.keep)
-        hits = (StopHitC * b.n)()
-        lp = None if top_k is None else _LogprobBuffers(b.n, b.cap, int(top_k))
-        pc = _params_c(params, self.eos_token_id, ignore_eos)
-        check(lib().dsocr_generate_penalties(self._h, b.n, b.reqs, C.byref(pc), b.res, pen, stops, hits, bias,
-                                             lp.k if lp else 0, lp.c if lp else None))
-        got = (b.ids(), [(int(h.seq), int(h.match_len)) for h in hits])
-        return (*got, *lp.unpack()) if lp else got
+        return self._generate_controls(lib().dsocr_generate_penalties, "one penalty record (or None) per request", requests,
+                                       params, ignore_eos, top_k, constraints, stop_sets, penalties)
 
     def generate_ngram_window(self, requests, ngram_windows, params: DecodeParameters = DecodeParameters(),
                               ignore_eos: bool = False, top_k: Optional[int] = None, constraints=None, stop_sets=None,
@@ -555,22 +561,8 @@ class DeepseekOcrEngine:
         """generate_batch with one windowed n-gram ban per request (dsocr_generate_ngram_window): ``ngram_windows[i]``
         is a ``dsocr.ngram_window.NgramWindow`` or None; ``penalties``, ``constraints`` and ``stop_sets`` likewise (or
         None for none).  Returns what ``generate_penalties`` returns."""
-        n = len(requests)
-        if len(ngram_windows) != n or any(x is not None and len(x) != n for x in (constraints, stop_sets, penalties)):
-            raise DsocrError(1, "one n-gram window record (or None) per request")
-        _check_top_k(top_k)
-        b = _Batch(self, requests, params)
-        ngw = _ptr_array(NgramWindowC, [_ngram_window_c(_ngram_window(w, self.vocab), b.keep) for w in ngram_windows], b.keep)
-        pen = None if penalties is None else _ptr_array(PenaltiesC, [_penalties_c(pn) for pn in penalties], b.keep)
-        stops = None if stop_sets is None else _ptr_array(StopSetC, [_stop_c(ss, b.keep) for ss in stop_sets], b.keep)
-        bias = None if constraints is None else _ptr_array(LogitBiasC, [_bias_c(c, b.keep) for c in constraints], b.keep)
-        hits = (StopHitC * b.n)()
-        lp = None if top_k is None else _LogprobBuffers(b.n, b.cap, int(top_k))
-        pc = _params_c(params, self.eos_token_id, ignore_eos)
-        check(lib().dsocr_generate_ngram_window(self._h, b.n, b.reqs, C.byref(pc), b.res, ngw, pen, stops, hits, bias,
-                                                lp.k if lp else 0, lp.c if lp else None))
-        got = (b.ids(), [(int(h.seq), int(h.match_len)) for h in hits])
-        return (*got, *lp.unpack()) if lp else got
+        return self._generate_controls(lib().dsocr_generate_ngram_window, "one n-gram window record (or None) per request",
+                                       requests, params, ignore_eos, top_k, constraints, stop_sets, penalties, ngram_windows)
 
     def generate_guided(self, requests, automata, params: DecodeParameters = DecodeParameters(),
                         ignore_eos: bool = False, top_k: Optional[int] = None, constraints=None, stop_sets=None,
@@ -579,25 +571,8 @@ class DeepseekOcrEngine:
         ``dsocr.guided.TokenAutomaton`` or None; the other lists as in ``generate_ngram_window`` (or None for none).
         Returns ``(ids, stop_hits, guided)`` with ``guided[i] = (state, status)`` (status 0 running or cut, 1 complete,
         2 violated), followed by the three log-probability lists when ``top_k`` is given."""
-        n = len(requests)
-        if len(automata) != n or any(x is not None and len(x) != n for x in (constraints, stop_sets, penalties, ngram_windows)):
-            raise DsocrError(1, "one token automaton (or None) per request")
-        _check_top_k(top_k)
-        b = _Batch(self, requests, params)
-        gd = _ptr_array(GuidedC, [_guided_c(_guided(a, self.vocab), b.keep) for a in automata], b.keep)
-        ngw = None if ngram_windows is None else _ptr_array(
-            NgramWindowC, [_ngram_window_c(_ngram_window(w, self.vocab), b.keep) for w in ngram_windows], b.keep)
-        pen = None if penalties is None else _ptr_array(PenaltiesC, [_penalties_c(pn) for pn in penalties], b.keep)
-        stops = None if stop_sets is None else _ptr_array(StopSetC, [_stop_c(ss, b.keep) for ss in stop_sets], b.keep)
-        bias = None if constraints is None else _ptr_array(LogitBiasC, [_bias_c(c, b.keep) for c in constraints], b.keep)
-        hits = (StopHitC * b.n)()
-        gres = (GuidedResultC * b.n)()
-        lp = None if top_k is None else _LogprobBuffers(b.n, b.cap, int(top_k))
-        pc = _params_c(params, self.eos_token_id, ignore_eos)
-        check(lib().dsocr_generate_guided(self._h, b.n, b.reqs, C.byref(pc), b.res, gd, gres, ngw, pen, stops, hits, bias,
-                                          lp.k if lp else 0, lp.c if lp else None))
-        got = (b.ids(), [(int(h.seq), int(h.match_len)) for h in hits], [(int(g.state), int(g.status)) for g in gres])
-        return (*got, *lp.unpack()) if lp else got
+        return self._generate_controls(lib().dsocr_generate_guided, "one token automaton (or None) per request", requests,
+                                       params, ignore_eos, top_k, constraints, stop_sets, penalties, ngram_windows, automata)
 
     def generate_stop_stream(self, request, stop_set, params: DecodeParameters = DecodeParameters(),
                              stream: Optional[Callable] = None, ignore_eos: bool = False):

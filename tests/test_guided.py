@@ -18,8 +18,12 @@ import pytest
 
 from dsocr import DecodeParameters, DsocrError, ModelLoadArgs, Page, VisionSettings, build_prompt_tokens, load_model
 from dsocr._lib import SESSION_GUIDED, GuidedC, lib
+from dsocr.constraint import merge_constraint
 from dsocr.engine import _guided_c
 from dsocr.guided import TokenAutomaton, automaton_from_sequences
+from dsocr.ngram_window import NgramWindow
+from dsocr.penalties import Penalties
+from dsocr.stops import StopSet
 from dsocr.synth import SyntheticTokenizer
 
 pytestmark = pytest.mark.gpu
@@ -379,6 +383,70 @@ def test_session_admission_forms(engine, pages, plain):
     assert got["admit"] == got["prefix"] == got["chunked"] == want
     assert res["admit"] == res["prefix"] == res["chunked"] == wres and wres[1] == 1
     assert got["after_cancel"] == plain1
+
+
+def test_all_controls_agree_across_entry_points(engine, pages):
+    """Page 0 under all five controls at once (deny / bias list, stop set, frequency / presence penalties, windowed
+    2-gram ban, the cyclic automaton) with K = 2 log-probability alternatives: generate_guided alone, a session opened
+    with every feature through admit, and the same session through admit_begin / admit_advance (the page is staged in
+    slot 1 and moves to slot 0) give the same ids, stop hit, automaton (state, status) and log-probability entries,
+    bit for bit (the page runs alone, at n = 1, every time).  The chunked admission takes the prompt as one chunk:
+    in two, the chunk attention rounds the cache rows differently from the one-pass prefill and entry 3 moves by one
+    ulp, with or without controls (ids, hit and state still agree).  Then two pages: slot 0 retires mid-run, the controlled
+    page moves into it with every record and finishes with the same ids.  The stop is the run's own 2-gram at
+    positions 5, 6 (the windowed ban makes that its first occurrence), so it fires at 7 tokens, after the move."""
+    ids, mask, page = pages[0]
+    K, M = 2, 12
+    aut = _cyclic()
+    con = merge_constraint(logit_bias={101: 1.5, 203: -1.0}, banned_token_ids=[100, 200])
+    pen, win = Penalties(0.8, 0.4, 0.0), NgramWindow(2, 6)
+    p = DecodeParameters(max_new_tokens=M)
+
+    def alone(ss):
+        got = engine.generate_guided([(ids, mask, page, None)], [aut], p, top_k=K, constraints=[con], stop_sets=[ss],
+                                     penalties=[pen], ngram_windows=[win])
+        return [g[0] for g in got]
+
+    base = alone(None)[0]
+    assert len(base) == M and set(base) <= set(aut.edge_tok) - {100, 200}
+    ss = StopSet(((base[5], base[6]), (7, 8, 9)), (0, 1), ())
+    want = alone(ss)
+    assert want[0] == base[:7] and want[1] == (0, 2) and want[2] == aut.walk(base[:7])
+    kw = dict(params=p, logprobs=K, stops=ss, frequency_penalty=pen.frequency, presence_penalty=pen.presence,
+              min_p=pen.min_p, ngram_window=win, guided=aut, **con.kwargs())
+    need = max(len(pages[i][0]) for i in (0, 1)) + M + 1 + 8
+    got = {}
+
+    def finish(sess, key, slot):
+        st = sess.step(8)
+        sess.step(8)
+        assert st[slot].done and st[slot].out_len == 7
+        got[key] = [None, sess.stop_hit(slot), sess.guided_state(slot), *sess.logprobs(slot, 0, 7, K)]
+        got[key][0] = sess.retire(slot)[0]
+
+    with engine.open_session(2, need, p, per_request=True, logprobs=True, logit_bias=True, stops=True, penalties=True,
+                             ngram_window=True, guided=True) as sess:
+        assert sess.admit(ids, mask, page, **kw) == 0
+        finish(sess, "admit", 0)
+        sess.admit_begin(ids, mask, page, chunk_rows=max(32, len(ids)), **kw)
+        done = False
+        while not done:
+            done, slot = sess.admit_advance()
+        assert slot == 0
+        finish(sess, "chunked", 0)
+        # two pages: the plain one (3 tokens) leaves first and the controlled page moves from slot 1 to slot 0
+        assert sess.admit(*pages[1], params=DecodeParameters(max_new_tokens=3)) == 0
+        assert sess.admit(ids, mask, page, **kw) == 1
+        assert sess.step(3)[0].done
+        assert sess.retire(0)[1] == 1
+        sess.step(8)
+        moved = [sess.stop_hit(0), sess.guided_state(0)]
+        moved.insert(0, sess.retire(0)[0])
+    for key in ("admit", "chunked"):
+        assert got[key][:3] == want[:3], key
+        for a, b in zip(got[key][3:], want[3:]):
+            assert np.asarray(a).tobytes() == np.asarray(b).tobytes(), key
+    assert moved == want[:3]
 
 
 def test_session_compaction(engine, pages):
