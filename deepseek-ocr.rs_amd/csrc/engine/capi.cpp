@@ -1455,6 +1455,218 @@ dsocr_status dsocr_k_dots_op(int op, long rows, int cols, int aux, long ld, cons
         check_hip(hipDeviceSynchronize(), "dots_op");
     });
 }
+// ---------------------------------------------------------------- the vision tower's kernels in the engine's forms
+// a device row map (c_rows / out_rows) read back and checked against the rows of the buffer it scatters into
+static void check_row_map(const int* d_map, int n, int cap, const char* what) {
+    std::vector<int> h((size_t)n);
+    if (n) check_hip(hipMemcpy(h.data(), d_map, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost), "hipMemcpy row map");
+    for (int v : h)
+        if (v < -1 || v >= cap) throw std::runtime_error(std::string("EINVAL: ") + what + " entry outside [-1, rows of the target)");
+}
+dsocr_status dsocr_k_gemm_f32a_ex(int M, int N, int K, const float* A, long lda, const void* W, int wdtype,
+                                  const float* bias, float* C, long ldc, const int* c_rows, int c_cap, int act,
+                                  int accumulate, int variant, int splits, int* splits_used) {
+    return guarded([&] {
+        if (!A || !W || !C || M < 1 || N < 1 || K < 1) throw std::runtime_error("EINVAL: bad gemm_f32a arguments");
+        if (wdtype != dsocr::WDT_BF16 && wdtype != dsocr::WDT_F16) throw std::runtime_error("EINVAL: weights must be bf16 or f16");
+        if (lda < K || ldc < N) throw std::runtime_error("EINVAL: row strides too small");
+        if (variant != 0 && variant != 2) throw std::runtime_error("EINVAL: variant must be 0 or 2");
+        if (splits < 0 || splits > std::max(1, K / 32)) throw std::runtime_error("EINVAL: splits must be 0 .. K / 32");
+        if (c_rows) check_row_map(c_rows, M, c_cap, "c_rows");
+        dsocr::GemmBf16Args g;
+        g.M = M; g.N = N; g.K = K; g.A = A; g.lda = lda; g.W = W; g.ldw = K; g.bias = bias;
+        g.w_f16 = wdtype == dsocr::WDT_F16;
+        g.C = C; g.ldc = ldc; g.c_rows = c_rows; g.act = act; g.accumulate = accumulate; g.variant = variant;
+        if (!dsocr::gemm_f32a_ok(g)) throw std::runtime_error("EINVAL: gemm_f32a needs K % 32 == 0 and 16-byte aligned rows");
+        // Engine::linear: the split count by the shape, the workspace [splits][M][N] only when there is a reduce
+        g.splits = splits > 0 ? splits : dsocr::gemm_f32a_splits(M, N, K);
+        float* part = nullptr;
+        if (g.splits > 1) {
+            check_hip(hipMalloc(&part, sizeof(float) * (size_t)g.splits * M * N), "hipMalloc");
+            g.part = part;
+        }
+        if (splits_used) *splits_used = g.splits;
+        dsocr::launch_gemm_f32a(g, nullptr);
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) e = hipDeviceSynchronize();
+        if (part) (void)hipFree(part);
+        check_hip(e, "gemm_f32a_ex");
+    });
+}
+dsocr_status dsocr_k_layernorm_ex(int rows, int cols, const float* x, int ldx, const float* w, const float* b, float eps,
+                                  float* y, int ldy, const int* out_rows, int y_rows) {
+    return guarded([&] {
+        if (!x || !w || !b || !y || rows < 0 || cols < 1) throw std::runtime_error("EINVAL: bad layernorm arguments");
+        if (cols % 4 || ldx % 4 || ldy % 4 || ldx < cols || ldy < cols)
+            throw std::runtime_error("EINVAL: cols and the row strides must be multiples of 4, strides >= cols");
+        if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(w) |
+             reinterpret_cast<uintptr_t>(b)) & 15)
+            throw std::runtime_error("EINVAL: layernorm needs 16-byte aligned pointers");
+        if (out_rows) check_row_map(out_rows, rows, y_rows, "out_rows");
+        dsocr::launch_layernorm(x, ldx, y, ldy, out_rows, rows, cols, w, b, eps, nullptr);
+        check_hip(hipGetLastError(), "layernorm launch");
+        check_hip(hipDeviceSynchronize(), "layernorm");
+    });
+}
+dsocr_status dsocr_k_rmsnorm_ex(int rows, int cols, const float* x, int ldx, const float* w, float eps, float* y,
+                                int ldy) {
+    return guarded([&] {
+        if (!x || !w || !y || rows < 0 || cols < 1) throw std::runtime_error("EINVAL: bad rmsnorm arguments");
+        if (cols % 4 || ldx % 4 || ldy % 4 || ldx < cols || ldy < cols)
+            throw std::runtime_error("EINVAL: cols and the row strides must be multiples of 4, strides >= cols");
+        if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(w)) & 15)
+            throw std::runtime_error("EINVAL: rmsnorm needs 16-byte aligned pointers");
+        dsocr::launch_rmsnorm(x, ldx, y, ldy, rows, cols, w, eps, nullptr);
+        check_hip(hipGetLastError(), "rmsnorm launch");
+        check_hip(hipDeviceSynchronize(), "rmsnorm");
+    });
+}
+static void check_relbias_args(int n_seq, int gh, int gw, int heads, int hd, const float* q, long q_ld) {
+    if (!q || n_seq < 1 || gh < 1 || gw < 1 || heads < 1) throw std::runtime_error("EINVAL: bad rel-pos arguments");
+    if (hd < 4 || hd % 4 || q_ld % 4 || q_ld < (long)heads * hd || (reinterpret_cast<uintptr_t>(q) & 15))
+        throw std::runtime_error("EINVAL: rel-pos bias needs hd % 4 == 0 and 16-byte aligned q rows of >= heads * hd floats");
+}
+dsocr_status dsocr_k_sam_relbias(int n_seq, int gh, int gw, int heads, int hd, const float* q, long q_ld,
+                                 const float* relh, const float* relw, float* out) {
+    return guarded([&] {
+        check_relbias_args(n_seq, gh, gw, heads, hd, q, q_ld);
+        if (!relh || !relw || !out || ((reinterpret_cast<uintptr_t>(relh) | reinterpret_cast<uintptr_t>(relw)) & 15))
+            throw std::runtime_error("EINVAL: rel-pos bias needs 16-byte aligned tables and an output");
+        dsocr::launch_sam_relbias(q, q_ld, n_seq, gh, gw, heads, hd, relh, relw, out, nullptr);
+        check_hip(hipGetLastError(), "sam_relbias launch");
+        check_hip(hipDeviceSynchronize(), "sam_relbias");
+    });
+}
+dsocr_status dsocr_k_attention_fused(int n_seq, int L, int heads, int hd, float scale, const float* qkv, long ld,
+                                     float* o, long o_ld, const float* relh, const float* relw, int gh, int gw) {
+    return guarded([&] {
+        if (!qkv || !o || n_seq < 1 || L < 1 || heads < 1) throw std::runtime_error("EINVAL: bad attention arguments");
+        if (hd != 32 && hd != 64 && hd != 128) throw std::runtime_error("EINVAL: head_dim must be 32, 64 or 128");
+        const long C = (long)heads * hd;
+        if (ld < 3 * C || o_ld < C || ld % 4 || (reinterpret_cast<uintptr_t>(qkv) & 15))
+            throw std::runtime_error("EINVAL: attention needs ld >= 3 heads hd, o_ld >= heads hd and 16-byte aligned qkv rows");
+        if ((relh == nullptr) != (relw == nullptr)) throw std::runtime_error("EINVAL: both rel-pos tables or neither");
+        // Engine::vision_pass: q | k | v views of one buffer, the bias table from the fused buffer's q columns
+        dsocr::AttnArgs a;
+        a.q = {qkv, ld, hd, nullptr};
+        a.k = {qkv + C, ld, hd, nullptr};
+        a.v = {qkv + 2 * C, ld, hd, nullptr};
+        a.o = o; a.o_row_stride = o_ld; a.o_head_stride = hd; a.n_seq = n_seq; a.L = L; a.heads = heads;
+        a.kv_heads = heads; a.hd = hd; a.scale = scale;
+        float* rb = nullptr;
+        if (relh) {
+            if ((long)gh * gw != L) throw std::runtime_error("EINVAL: rel-pos grid does not match L");
+            check_relbias_args(n_seq, gh, gw, heads, hd, qkv, ld);
+            if ((reinterpret_cast<uintptr_t>(relh) | reinterpret_cast<uintptr_t>(relw)) & 15)
+                throw std::runtime_error("EINVAL: rel-pos bias needs 16-byte aligned tables");
+            check_hip(hipMalloc(&rb, sizeof(float) * (size_t)n_seq * heads * L * (gh + gw)), "hipMalloc relbias");
+            dsocr::launch_sam_relbias(qkv, ld, n_seq, gh, gw, heads, hd, relh, relw, rb, nullptr);
+            a.relbias = rb; a.rel_h = gh; a.rel_w = gw;
+        }
+        dsocr::launch_attention(a, nullptr);
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) e = hipDeviceSynchronize();
+        if (rb) (void)hipFree(rb);
+        check_hip(e, "attention_fused");
+    });
+}
+dsocr_status dsocr_k_vision_op(int op, const long long* d, int nd, const void* const* p, int np) {
+    return guarded([&] {
+        auto shape = [&](int want_d, int want_p) {
+            if (!d || !p || nd != want_d || np != want_p)
+                throw std::runtime_error("EINVAL: vision op " + std::to_string(op) + " takes " + std::to_string(want_d) +
+                                         " dims and " + std::to_string(want_p) + " pointers");
+            for (int i = 0; i < np; ++i)
+                if (!p[i]) throw std::runtime_error("EINVAL: vision op: NULL pointer " + std::to_string(i));
+        };
+        auto need = [](bool ok, const char* what) {
+            if (!ok) throw std::runtime_error(std::string("EINVAL: vision op needs ") + what);
+        };
+        auto aligned = [&](std::initializer_list<int> idx) {
+            for (int i : idx) need((reinterpret_cast<uintptr_t>(p[i]) & 15) == 0, "16-byte aligned pointers");
+        };
+        auto positive = [&](int n) {
+            for (int i = 0; i < n; ++i) need(d[i] > 0 && d[i] <= 0x7fffffffLL, "positive 32-bit dims");
+        };
+        auto F = [&](int i) { return reinterpret_cast<const float*>(p[i]); };
+        auto Fm = [&](int i) { return reinterpret_cast<float*>(const_cast<void*>(p[i])); };
+        auto I = [&](int i) { return reinterpret_cast<const int*>(p[i]); };
+        switch (op) {
+        case DSOCR_VIS_PATCH_IM2COL:  // d: n, H, W, ps; p: img, cols
+            shape(4, 2); positive(4);
+            need(d[1] % d[3] == 0 && d[2] % d[3] == 0, "H and W divisible by the patch size");
+            dsocr::launch_patch_im2col(F(0), (int)d[0], (int)d[1], (int)d[2], (int)d[3], Fm(1), nullptr);
+            break;
+        case DSOCR_VIS_CONV_IM2COL_NHWC:  // d: n, H, W, C, kh, kw, stride, pad; p: x, cols
+            shape(8, 2); positive(7);
+            need(d[7] >= 0 && d[7] < d[4] && d[7] < d[5] && d[3] % 4 == 0, "0 <= pad < kernel and C % 4 == 0");
+            need(d[1] + 2 * d[7] >= d[4] && d[2] + 2 * d[7] >= d[5], "a kernel no larger than the padded image");
+            aligned({0, 1});
+            dsocr::launch_conv_im2col_nhwc(F(0), (int)d[0], (int)d[1], (int)d[2], (int)d[3], (int)d[4], (int)d[5], (int)d[6],
+                                           (int)d[7], Fm(1), nullptr);
+            break;
+        case DSOCR_VIS_ADD_BROADCAST:  // d: rows_per_rep, cols, reps; p: t, x (in place)
+            shape(3, 2); positive(3);
+            dsocr::launch_add_broadcast(Fm(1), F(0), (long)d[0], (int)d[1], (int)d[2], nullptr);
+            break;
+        case DSOCR_VIS_CLIP_EMBED:  // d: n, S, C; p: sam, cls, pos, out
+            shape(3, 4); positive(3);
+            dsocr::launch_clip_embed(F(0), F(1), F(2), (int)d[0], (int)d[1], (int)d[2], Fm(3), nullptr);
+            break;
+        case DSOCR_VIS_CONCAT_CLIP_SAM:  // d: n, S, C1, C2; p: clip, sam, out
+            shape(4, 3); positive(4);
+            dsocr::launch_concat_clip_sam(F(0), F(1), (int)d[0], (int)d[1], (int)d[2], (int)d[3], Fm(2), nullptr);
+            break;
+        case DSOCR_VIS_ASSEMBLE_ROWS:  // d: rows, H, table_dt, ld_dst; p: kind, index, table, srcA, srcB, vecA, vecB, dst
+            shape(4, 8); positive(2);
+            need((d[2] == dsocr::WDT_BF16 || d[2] == dsocr::WDT_F16) && d[3] >= d[1], "a bf16 / f16 table and ld_dst >= H");
+            dsocr::launch_assemble_rows(I(0), I(1), (int)d[0], (int)d[1], p[2], (int)d[2], F(3), F(4), F(5), F(6), Fm(7),
+                                        (long)d[3], nullptr);
+            break;
+        case DSOCR_VIS_EMBED_TOKENS:  // d: n, H, table_dt, ld; p: table, ids, out
+            shape(4, 3); positive(2);
+            need((d[2] == dsocr::WDT_BF16 || d[2] == dsocr::WDT_F16) && d[3] >= d[1], "a bf16 / f16 table and ld >= H");
+            dsocr::launch_embed_tokens(p[0], (int)d[2], I(1), (int)d[0], (int)d[1], Fm(2), (long)d[3], nullptr);
+            break;
+        case DSOCR_VIS_TRACE_LOGITS:  // d: B, V, ld, steps; p: logits, out_len, done, trace
+            shape(4, 4); positive(4);
+            need(d[2] >= d[1], "ld >= V");
+            dsocr::launch_trace_logits(F(0), (int)d[0], (int)d[1], (long)d[2], I(1), I(2), Fm(3), (long)d[3], nullptr);
+            break;
+        case DSOCR_VIS_OCR2_BUILD_SEQ:  // d: n, P, D; p: feat, query, out
+            shape(3, 3); positive(3);
+            need(d[2] % 4 == 0, "D % 4 == 0");
+            aligned({0, 1, 2});
+            dsocr::launch_ocr2_build_seq(F(0), F(1), (int)d[0], (int)d[1], (int)d[2], Fm(2), nullptr);
+            break;
+        case DSOCR_VIS_OCR2_ROPE:  // d: rows, L, n_heads, hd, ld; p: cos, sin, x (in place)
+            shape(5, 3); positive(5);
+            need(d[3] % 2 == 0 && d[4] >= d[2] * d[3], "an even head dim and ld >= n_heads * hd");
+            dsocr::launch_ocr2_rope(Fm(2), (long)d[4], (long)d[0], (int)d[1], (int)d[2], (int)d[3], F(0), F(1), nullptr);
+            break;
+        case DSOCR_VIS_OCR2_TAKE_QUERIES:  // d: n, P, D; p: src, dst
+            shape(3, 2); positive(3);
+            need(d[2] % 4 == 0, "D % 4 == 0");
+            aligned({0, 1});
+            dsocr::launch_ocr2_take_queries(F(0), (int)d[0], (int)d[1], (int)d[2], Fm(1), nullptr);
+            break;
+        default:
+            throw std::runtime_error("EINVAL: unknown vision op " + std::to_string(op));
+        }
+        check_hip(hipGetLastError(), "vision_op launch");
+        check_hip(hipDeviceSynchronize(), "vision_op");
+    });
+}
+dsocr_status dsocr_window_maps(int n, int g, int W, int* tok2win, int* win2tok) {
+    return guarded([&] {
+        if (n < 1 || g < 1 || W < 1 || !tok2win || !win2tok) throw std::runtime_error("EINVAL: bad window map arguments");
+        const long gp = g + (W - g % W) % W;
+        if ((long)n * gp * gp > 0x7fffffffL) throw std::runtime_error("EINVAL: window rows exceed 32 bits");
+        const dsocr::WindowMaps m = dsocr::window_maps(n, g, W);
+        std::copy(m.tok2win.begin(), m.tok2win.end(), tok2win);
+        std::copy(m.win2tok.begin(), m.win2tok.end(), win2tok);
+    });
+}
 dsocr_status dsocr_k_decode_attention(int B, int heads, int kv_heads, int hd, int rope_dim, int max_len, float scale,
                                       const float* qkv, const float* cos, const float* sin, float* kc, float* vc,
                                       const int* kv_pos, float* o, int prerot) {

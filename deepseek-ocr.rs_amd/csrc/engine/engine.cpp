@@ -908,15 +908,9 @@ float* Engine::vision_pass(const float* imgs, int n, int Spx, const std::string&
     const long wrows = (long)n * nw * nw * W * W;
     auto wm = winmaps_.find({n, g});
     if (wm == winmaps_.end()) {  // built once per (images, grid): tok -> window slot and back
-        std::vector<int> tok2win(rows), win2tok(wrows, -1);
-        for (int b = 0; b < n; ++b)
-            for (int y = 0; y < g; ++y)
-                for (int xx = 0; xx < g; ++xx) {
-                    long t = ((long)b * g + y) * g + xx;
-                    long w = (((long)b * nw + y / W) * nw + xx / W) * W * W + (y % W) * W + (xx % W);
-                    tok2win[t] = (int)w;
-                    win2tok[w] = (int)t;
-                }
+        const WindowMaps maps = window_maps(n, g, W);
+        const std::vector<int>& tok2win = maps.tok2win;
+        const std::vector<int>& win2tok = maps.win2tok;
         int *a = nullptr, *b2 = nullptr;
         HIP_CHECK(hipMalloc(&a, tok2win.size() * 4));
         HIP_CHECK(hipMalloc(&b2, win2tok.size() * 4));

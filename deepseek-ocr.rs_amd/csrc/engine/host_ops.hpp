@@ -391,6 +391,31 @@ inline PrefillPlan prefill_row_plan(const std::vector<int>& lens, long qkv_ld, l
     return p;
 }
 
+// ---------------------------------------------------------------- SAM window maps
+// window_partition / window_unpartition (sam.rs:926-980) as row maps: n images of a g x g token grid, padded at the
+// bottom / right to gp = the next multiple of W and cut into nw x nw windows of W x W (nw = gp / W).  Token
+// t = (b, y, x) lives at window row tok2win[t] = ((b nw + y / W) nw + x / W) W W + (y % W) W + x % W;
+// win2tok is the inverse over the n nw nw W W window rows, -1 on the padding rows.
+struct WindowMaps {
+    std::vector<int> tok2win, win2tok;
+};
+inline WindowMaps window_maps(int n, int g, int W) {
+    const int gp = g + (W - g % W) % W, nw = gp / W;
+    const long rows = (long)n * g * g, wrows = (long)n * nw * nw * W * W;
+    WindowMaps m;
+    m.tok2win.resize(rows);
+    m.win2tok.assign(wrows, -1);
+    for (int b = 0; b < n; ++b)
+        for (int y = 0; y < g; ++y)
+            for (int xx = 0; xx < g; ++xx) {
+                long t = ((long)b * g + y) * g + xx;
+                long w = (((long)b * nw + y / W) * nw + xx / W) * W * W + (y % W) * W + (xx % W);
+                m.tok2win[t] = (int)w;
+                m.win2tok[w] = (int)t;
+            }
+    return m;
+}
+
 // ---------------------------------------------------------------- f32 table resizes
 inline float bicubic_filter_pillow(float x) {
     const float a = -0.5f;

@@ -201,6 +201,8 @@ EXPORTS = [
     "dsocr_k_ngram_window",
     "dsocr_guided_check", "dsocr_generate_guided", "dsocr_session_stage_guided", "dsocr_session_guided_state",
     "dsocr_k_guided_mask", "dsocr_k_guided_advance",
+    "dsocr_k_gemm_f32a_ex", "dsocr_k_layernorm_ex", "dsocr_k_rmsnorm_ex", "dsocr_k_sam_relbias", "dsocr_k_attention_fused",
+    "dsocr_k_vision_op", "dsocr_window_maps",
 ]
 
 # model variants behind the deepseek engine (dsocr_engine_variant)
@@ -208,6 +210,10 @@ VARIANT_OCR1, VARIANT_OCR2 = 0, 1
 
 # dsocr_k_dots_op op codes (DSOCR_DOTS_*)
 DOTS_RMSNORM, DOTS_LAYERNORM, DOTS_SWIGLU, DOTS_GELU, DOTS_ROPE_QK, DOTS_TO_BF16, DOTS_BF16_TO_F32 = range(7)
+
+# dsocr_k_vision_op op codes (DSOCR_VIS_*)
+(VIS_PATCH_IM2COL, VIS_CONV_IM2COL_NHWC, VIS_ADD_BROADCAST, VIS_CLIP_EMBED, VIS_CONCAT_CLIP_SAM, VIS_ASSEMBLE_ROWS,
+ VIS_EMBED_TOKENS, VIS_TRACE_LOGITS, VIS_OCR2_BUILD_SEQ, VIS_OCR2_ROPE, VIS_OCR2_TAKE_QUERIES) = range(11)
 
 _lib = None
 
@@ -250,6 +256,14 @@ def lib():
     L.dsocr_k_gemm_bf16.argtypes = [i32, i32, i32, vp, C.c_long, vp, C.c_long, vp, vp, C.c_long, i32, i32, i32, i32, i32,
                                     vp, vp, i32]
     L.dsocr_k_dots_op.argtypes = [i32, C.c_long, i32, i32, C.c_long, vp, vp, vp, f32, vp]
+    L.dsocr_k_gemm_f32a_ex.argtypes = [i32, i32, i32, vp, C.c_long, vp, i32, vp, vp, C.c_long, vp, i32, i32, i32, i32, i32,
+                                       C.POINTER(i32)]
+    L.dsocr_k_layernorm_ex.argtypes = [i32, i32, vp, i32, vp, vp, f32, vp, i32, vp, i32]
+    L.dsocr_k_rmsnorm_ex.argtypes = [i32, i32, vp, i32, vp, f32, vp, i32]
+    L.dsocr_k_sam_relbias.argtypes = [i32, i32, i32, i32, i32, vp, C.c_long, vp, vp, vp]
+    L.dsocr_k_attention_fused.argtypes = [i32, i32, i32, i32, f32, vp, C.c_long, vp, C.c_long, vp, vp, i32, i32]
+    L.dsocr_k_vision_op.argtypes = [i32, C.POINTER(C.c_longlong), i32, C.POINTER(vp), i32]
+    L.dsocr_window_maps.argtypes = [i32, i32, i32, vp, vp]
     L.dsocr_dots_load.argtypes = [C.c_char_p, C.c_char_p, C.c_uint64, i32, C.POINTER(vp)]
     L.dsocr_dots_free.argtypes = [vp]
     L.dsocr_dots_free.restype = None

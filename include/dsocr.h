@@ -776,6 +776,62 @@ enum {
 };
 dsocr_status dsocr_k_dots_op(int op, long rows, int cols, int aux, long ld, const void* x, const float* p0,
                              const float* p1, float eps, void* y);
+/* ---- the vision tower's kernels (SAM / CLIP / projector, the OCR-2 encoder's row ops) in the forms the engine
+ * launches them.  Every call forwards to the launch the engine makes. */
+/* dsocr_k_gemm_f32a with everything the engine's linear passes: A [M][lda], C [.][ldc], c_rows (device, M ints or
+ * NULL): row r of the product goes to C row c_rows[r], -1 drops it (the window un-partition); c_cap: rows C holds
+ * (every c_rows entry is checked against it).  variant 0: the default kernel; 2: two LDS stages (bf16 weights).
+ * splits 0: the engine's split-K count for (M, N, K); > 0: that many K slices (<= K / 32).  With more than one slice
+ * the bias, activation, accumulate and row scatter run in the split-K reduce over a [splits][M][N] workspace.
+ * *splits_used (optional) receives the count launched. */
+dsocr_status dsocr_k_gemm_f32a_ex(int M, int N, int K, const float* A, long lda, const void* W, int wdtype,
+                                  const float* bias, float* C, long ldc, const int* c_rows, int c_cap, int act,
+                                  int accumulate, int variant, int splits, int* splits_used);
+/* Row norms with row strides (floats, multiples of 4, >= cols; cols % 4 == 0); y may be x.  out_rows (device, rows
+ * ints or NULL): row r is written to y row out_rows[r], -1 drops it (the window partition); y_rows: rows y holds. */
+dsocr_status dsocr_k_layernorm_ex(int rows, int cols, const float* x, int ldx, const float* w, const float* b, float eps,
+                                  float* y, int ldy, const int* out_rows, int y_rows);
+dsocr_status dsocr_k_rmsnorm_ex(int rows, int cols, const float* x, int ldx, const float* w, float eps, float* y,
+                                int ldy);
+/* SAM's decomposed rel-pos terms (sam.rs:1124-1192): q [n_seq * gh * gw][q_ld] with head h at columns h * hd,
+ * relh [2 gh - 1][hd], relw [2 gw - 1][hd]; out [n_seq][heads][gh * gw][gh + gw]: entry kh < gh is
+ * q . relh[qh - kh + gh - 1], entry gh + kw is q . relw[qw - kw + gw - 1]. */
+dsocr_status dsocr_k_sam_relbias(int n_seq, int gh, int gw, int heads, int hd, const float* q, long q_ld,
+                                 const float* relh, const float* relw, float* out);
+/* Bidirectional attention over n_seq uniform sequences of L rows of one fused buffer qkv [n_seq * L][ld] holding
+ * q | k | v (heads * hd floats each; ld >= 3 heads hd, ld % 4 == 0); o [n_seq * L][o_ld], o_ld >= heads * hd; columns
+ * past heads * hd of an o row are not written.  relh / relw (both or neither): SAM's rel-pos tables of a gh x gw
+ * grid (gh * gw == L), the bias table built from the buffer's q columns as the engine does.  hd 32, 64 or 128. */
+dsocr_status dsocr_k_attention_fused(int n_seq, int L, int heads, int hd, float scale, const float* qkv, long ld,
+                                     float* o, long o_ld, const float* relh, const float* relw, int gh, int gw);
+/* One data-movement kernel of the page path: op, its nd dims d[] and np device pointers p[] (the last one is the
+ * destination), all f32 unless noted:
+ *  PATCH_IM2COL      d: n, H, W, ps              p: img [n][3][H][W], cols [n (H/ps) (W/ps)][3 ps ps] (K order c, ky, kx)
+ *  CONV_IM2COL_NHWC  d: n, H, W, C, kh, kw, stride, pad   p: x [n][H][W][C], cols [n oh ow][kh kw C] (K order ky, kx, c)
+ *  ADD_BROADCAST     d: rows_per_rep, cols, reps p: t [rows_per_rep][cols], x [reps][rows_per_rep][cols] (x += t)
+ *  CLIP_EMBED        d: n, S, C                  p: sam [n][S][C], cls [C], pos [S + 1][C], out [n][S + 1][C]
+ *  CONCAT_CLIP_SAM   d: n, S, C1, C2             p: clip [n][S + 1][C1], sam [n][S][C2], out [n][S][C1 + C2]
+ *  ASSEMBLE_ROWS     d: rows, H, table_dt, ld_dst   p: kind [rows] int, index [rows] int, table [.][H] 16-bit,
+ *                    srcA [.][H], srcB [.][H], vecA [H], vecB [H], dst [rows][ld_dst]; kind 0: table row index
+ *                    (widened), 1: srcA row, 2: srcB row, 3: vecA, 4: vecB
+ *  EMBED_TOKENS      d: n, H, table_dt, ld       p: table [.][H] 16-bit, ids [n] int, out [n][ld]
+ *  TRACE_LOGITS      d: B, V, ld, steps          p: logits [B][ld], out_len [B] int, done [B] int, trace [B][steps][V]:
+ *                    page b's row goes to trace[b][out_len[b]] unless done[b] or out_len[b] >= steps
+ *  OCR2_BUILD_SEQ    d: n, P, D                  p: feat [n][P][D], query [P][D], out [n][2 P][D]
+ *  OCR2_ROPE         d: rows, L, n_heads, hd, ld p: cos [L][hd], sin [L][hd], x [rows][ld] (in place: the first
+ *                    n_heads heads of every row, position = row % L)
+ *  OCR2_TAKE_QUERIES d: n, P, D                  p: src [n][2 P][D], dst [n][P][D]
+ * table_dt 0 = bf16, 1 = f16.  The row indices in kind / index / ids / out_len are the caller's to keep in range. */
+enum {
+    DSOCR_VIS_PATCH_IM2COL = 0, DSOCR_VIS_CONV_IM2COL_NHWC = 1, DSOCR_VIS_ADD_BROADCAST = 2, DSOCR_VIS_CLIP_EMBED = 3,
+    DSOCR_VIS_CONCAT_CLIP_SAM = 4, DSOCR_VIS_ASSEMBLE_ROWS = 5, DSOCR_VIS_EMBED_TOKENS = 6, DSOCR_VIS_TRACE_LOGITS = 7,
+    DSOCR_VIS_OCR2_BUILD_SEQ = 8, DSOCR_VIS_OCR2_ROPE = 9, DSOCR_VIS_OCR2_TAKE_QUERIES = 10
+};
+dsocr_status dsocr_k_vision_op(int op, const long long* d, int nd, const void* const* p, int np);
+/* host: SAM's window partition as row maps (sam.rs:926-980) for n images of a g x g token grid and windows of
+ * W x W, the grid padded to nw = ceil(g / W) windows a side: tok2win [n g g] is each token's window row,
+ * win2tok [n nw nw W W] the inverse, -1 on the padding rows. */
+dsocr_status dsocr_window_maps(int n, int g, int W, int* tok2win, int* win2tok);
 /* Decode attention step (block.rs:608-789 at seq_len 1, rope block.rs:1403-1471): for page b the
  * token at position pos = kv_pos[b] has its q / k rotated (cos/sin tables [max_len][rope_dim]; prerot != 0:
  * the q / k rows of qkv are already rotated), k and v appended to the f32 cache [B][kv_heads][max_len][hd]
