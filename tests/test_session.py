@@ -15,6 +15,8 @@ from dsocr._lib import check, lib
 from dsocr.scheduler import BatchScheduler
 from dsocr.synth import SyntheticTokenizer
 
+from _sched import arriving_together
+
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -211,7 +213,9 @@ def test_slot_reuse_through_scheduler(engine, pages):
     imgs = [_img(100 + i, *hw) for i, hw in enumerate(SIZES)]
     need = _need(pages, range(5), max_new)
     with BatchScheduler(engine, tok, 2, need, DecodeParameters(max_new_tokens=20), TINY_VS) as sched:
-        futs = [sched.submit(PROMPT, [im], params=DecodeParameters(max_new_tokens=m)) for im, m in zip(imgs, max_new)]
+        with arriving_together(sched):  # five waiting for two slots, however fast the host prepares a page
+            futs = [sched.submit(PROMPT, [im], params=DecodeParameters(max_new_tokens=m))
+                    for im, m in zip(imgs, max_new)]
         outs = [f.result(timeout=120) for f in futs]
         assert sched.max_active == 2
         assert all(n <= 2 for n, _ in sched.bursts)

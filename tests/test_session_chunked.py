@@ -22,6 +22,8 @@ from dsocr._lib import EINVAL, SESSION_ADMIT_PENDING
 from dsocr.scheduler import BatchScheduler
 from dsocr.synth import SyntheticTokenizer
 
+from _sched import arriving_together
+
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -280,8 +282,9 @@ def test_scheduler(engine, reqs, stream):
     params = DecodeParameters(max_new_tokens=MAX_NEW)
     seen = []
     with BatchScheduler(engine, tok, 3, _need(reqs), params, VS, admit_chunk=32) as s:
-        futs = [s.submit(p, [img], on_token=(lambda n, t: seen.append(n)) if stream and i == 0 else None)
-                for i, p in enumerate(PROMPTS)]
+        with arriving_together(s):  # the other three wait while the first is admitted, whatever the host's speed
+            futs = [s.submit(p, [img], on_token=(lambda n, t: seen.append(n)) if stream and i == 0 else None)
+                    for i, p in enumerate(PROMPTS)]
         outs = [f.result(timeout=120) for f in futs]
         events = list(s.events)
         assert s.chunked_admissions == 4 and s.admit_slices == 4 * 9  # three vision slices + six chunks of 185 rows

@@ -15,6 +15,8 @@ from dsocr._lib import RowParamsC, check, lib
 from dsocr.scheduler import BatchScheduler
 from dsocr.synth import SyntheticTokenizer
 
+from _sched import arriving_together
+
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -325,8 +327,9 @@ def test_scheduler_admits_mixed_parameters(engine, pages):
     need = _need(pages, range(5), max_new)
     with BatchScheduler(engine, tok, 2, need, DecodeParameters(max_new_tokens=20), TINY_VS,
                         per_request_params=True) as sched:
-        futs = [sched.submit(PROMPT, [im], params=DecodeParameters(max_new_tokens=m, **kw))
-                for im, m, kw in zip(imgs, max_new, kws)]
+        with arriving_together(sched):  # five waiting for two slots, however fast the host prepares a page
+            futs = [sched.submit(PROMPT, [im], params=DecodeParameters(max_new_tokens=m, **kw))
+                    for im, m, kw in zip(imgs, max_new, kws)]
         outs = [f.result(timeout=120) for f in futs]
         assert sched.max_active == 2 and sched.exclusive_runs == 0
         assert all(n <= 2 for n, _ in sched.bursts)
