@@ -25,10 +25,12 @@ ARCH = "gfx950"
 
 KERNELS = ["gemm", "gemm_bf16", "moe", "norm", "attention", "misc", "decode_gemv", "decode_attn", "decode_route",
            "decode_moe", "decode_sample", "lmhead", "dsq", "preprocess", "sampling", "dots_ops", "attention_bf16",
-           "decode_mm", "decode_persist", "decode_q", "attention_prefix", "ocr2_ops", "session",
+           "decode_mm", "decode_persist", "decode_q", "decode_qdot", "attention_prefix", "ocr2_ops", "session",
            "decode_logprob", "attention_past", "decode_bias", "decode_stop", "decode_penalty",
            "decode_ngram_window", "decode_guided"]
 HOST = ["engine", "dots", "capi"]
+# units compiled without the packed f32 VALU forms (v_pk_*_f32)
+NO_PACKED_F32 = {"decode_qdot"}
 
 
 def sources():
@@ -60,7 +62,10 @@ def stale(obj, src, hdrs):
 def compile_one(src, obj, is_kernel):
     common = ["-O3", "-std=c++17", "-fPIC", "-Wno-unused-result", "-Wno-unused-command-line-argument"]
     if is_kernel:
-        cmd = [HIPCC, f"--offload-arch={ARCH}", "-x", "hip"] + common + ["-c", src, "-o", obj]
+        cmd = [HIPCC, f"--offload-arch={ARCH}", "-x", "hip"] + common
+        if os.path.splitext(os.path.basename(src))[0] in NO_PACKED_F32:
+            cmd += ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+        cmd += ["-c", src, "-o", obj]
     else:
         # host code: strict IEEE (no FMA contraction) for the table resizes / RoPE tables
         cmd = [CLANG, "-x", "c++", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", "-ffp-contract=off",

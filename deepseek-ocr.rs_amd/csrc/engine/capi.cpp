@@ -399,7 +399,16 @@ const char* dsocr_last_error(void) { return g_last_error.c_str(); }
 dsocr_status dsocr_engine_load(const dsocr_load_args* args, dsocr_engine** out) {
     const char* e = getenv("DSOCR_DSQ_PACKED");
     const bool packed = e && atoi(e) != 0 && args && args->snapshot_path;
-    return dsocr_engine_load_flags(args, packed ? DSOCR_LOAD_PACKED_EXPERTS : 0u, out);
+    const char* i8 = getenv("DSOCR_DSQ_INT8");
+    const bool int8 = i8 && atoi(i8) != 0 && args && args->snapshot_path;
+    return dsocr_engine_load_flags(args, (packed ? DSOCR_LOAD_PACKED_EXPERTS : 0u) | (int8 ? DSOCR_LOAD_PACKED_INT8_DOT : 0u), out);
+}
+
+dsocr_status dsocr_engine_packed_mode(const dsocr_engine* e, int* mode) {
+    return guarded([&] {
+        if (!e || !mode) throw std::runtime_error("EINVAL: NULL argument");
+        *mode = e->impl->packed_mode();
+    });
 }
 
 dsocr_status dsocr_engine_packed_info(const dsocr_engine* e, size_t* packed_layers, size_t* moe_layers,
@@ -2065,11 +2074,15 @@ dsocr_status dsocr_k_moe_combine(int T, int topk, int H, const float* y, const i
         check_hip(hipDeviceSynchronize(), "combine");
     });
 }
-dsocr_status dsocr_k_moe_packed(int T, int H, int E, int topk, int I, int Is, const float* x, const float* norm_w,
-                                float eps, const void* router_f16, int gu_qtype, const void* Wgu_payload, int d_qtype,
-                                const void* Wd_payload, int sgu_qtype, const void* sWgu_payload, int sd_qtype,
-                                const void* sWd_payload, int norm_topk, float scaling, float* out, int* ids_out,
-                                float* w_out) {
+// one MoE layer from record-layout payloads; q8: the integer-dot form, its code planes copied out to q8->*
+struct MoePackedQ8Out {
+    int8_t* xn_codes; float* xn_d; int8_t* h_codes; float* h_d; int8_t* hs_codes; float* hs_d;
+};
+static dsocr_status moe_packed_impl(int T, int H, int E, int topk, int I, int Is, const float* x, const float* norm_w,
+                                    float eps, const void* router_f16, int gu_qtype, const void* Wgu_payload, int d_qtype,
+                                    const void* Wd_payload, int sgu_qtype, const void* sWgu_payload, int sd_qtype,
+                                    const void* sWd_payload, int norm_topk, float scaling, float* out, int* ids_out,
+                                    float* w_out, const MoePackedQ8Out* q8) {
     return guarded([&] {
         if (T <= 0 || T > 8 || H <= 0 || E <= 0 || topk <= 0 || I <= 0 || Is < 0) throw std::runtime_error("EINVAL: bad MoE shape");
         if (!x || !router_f16 || !Wgu_payload || !Wd_payload || !out) throw std::runtime_error("EINVAL: NULL argument");
@@ -2114,19 +2127,83 @@ dsocr_status dsocr_k_moe_packed(int T, int H, int E, int topk, int I, int Is, co
             a.grp = (int*)alloc(sizeof(int) * dsocr::moe_grp_ints(E, T, topk));
             a.route_cnt = (int*)alloc(sizeof(int) * 16);
             check_hip(hipMemset(a.route_cnt, 0, sizeof(int) * 16), "hipMemset");
+            if (q8) a.q8_ws = alloc(dsocr::moe_qdot_ws_bytes(T, topk, H, I, a.Is));
             const char* gu = nullptr;
             dsocr::moe_decode_kernel_names(a, &gu, nullptr);
-            if (std::string(gu) != "moe_gateup_q_kernel") throw std::runtime_error("EINVAL: packed decode MoE outside its range");
+            if (std::string(gu) != (q8 ? "moe_gateup_qdot_kernel" : "moe_gateup_q_kernel"))
+                throw std::runtime_error("EINVAL: packed decode MoE outside its range");
             dsocr::launch_moe_decode(a, nullptr);
             check_hip(hipGetLastError(), "moe launch");
             check_hip(hipDeviceSynchronize(), "moe");
             if (ids_out) check_hip(hipMemcpy(ids_out, a.ids, sizeof(int) * TK, hipMemcpyDeviceToHost), "d2h");
             if (w_out) check_hip(hipMemcpy(w_out, a.wts, sizeof(float) * TK, hipMemcpyDeviceToHost), "d2h");
+            if (q8) {
+                dsocr::Q8Planes qx, qh, qhs;
+                dsocr::moe_qdot_planes(a.q8_ws, T, topk, H, I, a.Is, &qx, &qh, &qhs);
+                auto copy_out = [&](const dsocr::Q8Planes& p, int qt, long rows, long in_dim, int8_t* codes, float* d) {
+                    if (codes) check_hip(hipMemcpy(codes, p.q, (size_t)rows * in_dim, hipMemcpyDeviceToHost), "d2h");
+                    if (d) check_hip(hipMemcpy(d, p.d, sizeof(float) * rows * (in_dim / (qt == dsocr::DSQ_Q4K ? 256 : 32)), hipMemcpyDeviceToHost), "d2h");
+                };
+                copy_out(qx, gu_qtype, T, H, q8->xn_codes, q8->xn_d);
+                copy_out(qh, d_qtype, TK, I, q8->h_codes, q8->h_d);
+                if (shared) copy_out(qhs, sd_qtype, T, Is, q8->hs_codes, q8->hs_d);
+            }
         } catch (...) {
             for (void* p : bufs) (void)hipFree(p);
             throw;
         }
         for (void* p : bufs) (void)hipFree(p);
+    });
+}
+dsocr_status dsocr_k_moe_packed(int T, int H, int E, int topk, int I, int Is, const float* x, const float* norm_w,
+                                float eps, const void* router_f16, int gu_qtype, const void* Wgu_payload, int d_qtype,
+                                const void* Wd_payload, int sgu_qtype, const void* sWgu_payload, int sd_qtype,
+                                const void* sWd_payload, int norm_topk, float scaling, float* out, int* ids_out,
+                                float* w_out) {
+    return moe_packed_impl(T, H, E, topk, I, Is, x, norm_w, eps, router_f16, gu_qtype, Wgu_payload, d_qtype, Wd_payload,
+                           sgu_qtype, sWgu_payload, sd_qtype, sWd_payload, norm_topk, scaling, out, ids_out, w_out, nullptr);
+}
+dsocr_status dsocr_k_moe_packed_q8(int T, int H, int E, int topk, int I, int Is, const float* x, const float* norm_w,
+                                   float eps, const void* router_f16, int gu_qtype, const void* Wgu_payload, int d_qtype,
+                                   const void* Wd_payload, int sgu_qtype, const void* sWgu_payload, int sd_qtype,
+                                   const void* sWd_payload, int norm_topk, float scaling, float* out, int* ids_out,
+                                   float* w_out, int8_t* xn_codes, float* xn_d, int8_t* h_codes, float* h_d,
+                                   int8_t* hs_codes, float* hs_d) {
+    const MoePackedQ8Out q8{xn_codes, xn_d, h_codes, h_d, hs_codes, hs_d};
+    return moe_packed_impl(T, H, E, topk, I, Is, x, norm_w, eps, router_f16, gu_qtype, Wgu_payload, d_qtype, Wd_payload,
+                           sgu_qtype, sWgu_payload, sd_qtype, sWd_payload, norm_topk, scaling, out, ids_out, w_out, &q8);
+}
+dsocr_status dsocr_k_q8_quantize(int kind, int T, size_t in_dim, const float* x, int8_t* codes, float* d, int16_t* bs) {
+    return guarded([&] {
+        if (T < 1 || !x || !codes || !d || (kind == dsocr::DSQ_Q4K && !bs)) throw std::runtime_error("EINVAL: NULL argument");
+        dsocr::Q8Planes o;
+        o.q = codes; o.d = d; o.bs = bs;
+        dsocr::launch_q8_quantize(kind, T, (int)in_dim, x, o, nullptr);
+        check_hip(hipGetLastError(), "q8_quantize launch");
+        check_hip(hipDeviceSynchronize(), "q8_quantize");
+    });
+}
+dsocr_status dsocr_k_dsq_rows_dot_q8(int qtype, size_t rows, size_t in_dim, const void* payload, int T, const int8_t* codes,
+                                     const float* d, const int16_t* bs, float* y) {
+    return guarded([&] {
+        if (!dsocr::dsq_packed_ok(qtype, (long)in_dim) || rows == 0)
+            throw std::runtime_error("EINVAL: rows_dot_q8 takes Q4_K (in_dim % 256 == 0) or Q8_0 (in_dim % 32 == 0) rows");
+        if (T < 1 || T > 8 || !payload || !codes || !d || !y) throw std::runtime_error("EINVAL: rows_dot_q8 takes 1..8 code rows");
+        void* buf = nullptr;
+        check_hip(hipMalloc(&buf, dsocr::dsq_packed_bytes(qtype, (long)rows, (long)in_dim)), "hipMalloc");
+        try {
+            const dsocr::QMat m = dsocr::dsq_packed_view(qtype, buf, (long)rows, (long)in_dim);
+            dsocr::launch_dsq_repack(m, 0, payload, (long)rows, (long)in_dim, nullptr);
+            dsocr::Q8Planes p;
+            p.q = const_cast<int8_t*>(codes); p.d = const_cast<float*>(d); p.bs = const_cast<int16_t*>(bs);
+            dsocr::launch_dsq_rows_dot_q8(m, (long)rows, (long)in_dim, T, p, y, nullptr);
+            check_hip(hipGetLastError(), "rows_dot_q8 launch");
+            check_hip(hipDeviceSynchronize(), "rows_dot_q8");
+        } catch (...) {
+            (void)hipFree(buf);
+            throw;
+        }
+        (void)hipFree(buf);
     });
 }
 dsocr_status dsocr_k_dsq_rows_dot(int qtype, size_t rows, size_t in_dim, const void* payload, int T, const float* x,

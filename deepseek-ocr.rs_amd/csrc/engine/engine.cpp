@@ -246,7 +246,9 @@ void* Engine::ws(const std::string& name0, size_t bytes) {
 Engine::Engine(const std::string& config_path, const std::string& weights_path, int device, int dtype, uint64_t seed,
                const std::string& snapshot_path, uint32_t load_flags)
     : device_(device), dtype_(dtype) {
-    if (load_flags & ~1u) throw std::runtime_error("EINVAL: unknown load flags");
+    if (load_flags & ~3u) throw std::runtime_error("EINVAL: unknown load flags");
+    if (load_flags & 2u) load_flags |= 1u;  // the integer-dot form runs on the packed tables
+    packed_mode_ = (load_flags & 2u) ? 2 : (int)(load_flags & 1u);
     if ((load_flags & 1u) && snapshot_path.empty())
         throw std::runtime_error("EINVAL: packed experts need a .dsq snapshot (snapshot_path)");
     int n = 0;
@@ -760,6 +762,7 @@ void Engine::load_weights(const std::string& path, uint64_t seed, const std::str
                         pack_records(sdn_n, H, Is, d.q_sd, d.packed_bytes);
                     }
                     d.packed = true;
+                    d.int8dot = packed_mode_ == 2;
                 }
             }
         }
@@ -1320,6 +1323,7 @@ MoeDecodeArgs Engine::moe_args(int l, int B, float* X) {
     }
     if (B <= 8 && d.packed) {  // the packed decode kernels (decode_q.hip)
         a.qWgu = d.q_gu; a.qWd = d.q_d; a.qsWgu = d.q_sgu; a.qsWd = d.q_sd;
+        if (d.int8dot) a.q8_ws = ws("s_q8", moe_qdot_ws_bytes(B, K, H, I, a.Is));
     }
     if (B <= 8 && d.e_gu_swz && (!d.has_shared || d.s_gu_swz)) {  // fragment-ordered experts
         a.Wgu_swz = d.e_gu_swz; a.Wd_swz = d.e_d_swz; a.sWgu_swz = d.s_gu_swz; a.sWd_swz = d.s_d_swz;
@@ -3814,6 +3818,12 @@ Engine::DecodeProfile Engine::profile_decode(int iters) {
                                     + (double)B * H * 4 + (double)(TK * I + B * Is) * 4;
             prof.moe_down.bytes = (touched * I * bpw(d0.q_d) + Is * (Is ? bpw(d0.q_sd) : 0.0)) * H
                                   + (double)(TK * I + B * Is) * 4 + 2.0 * B * H * 4;
+            if (std::string(prof.gateup_kernel) == "moe_gateup_qdot_kernel") {
+                // the integer-dot form also writes and reads the code planes: 1 byte per activation, d and bs beside
+                auto planes = [](double rows, double in_dim) { return rows * (in_dim + in_dim / 32 * 6); };
+                prof.moe_gateup.bytes += 2.0 * planes(B, H);
+                prof.moe_down.bytes += 2.0 * (planes(TK, I) + planes(B, Is));
+            }
         }
     }
     float* CTX = wsf("p_ctx", (size_t)B * H);

@@ -83,6 +83,7 @@ struct DecLayer {
     // packed experts (DSOCR_LOAD_PACKED_EXPERTS): the snapshot's Q4_K / Q8_0 blocks kept for the packed decode
     // kernels (decode_q.hip), beside the fp16 copies above; routed [E][2Im][H], [E][H][Im], shared [2Is][H], [H][Is]
     bool packed = false;
+    bool int8dot = false;  // DSOCR_LOAD_PACKED_INT8_DOT: the packed launches in their integer-dot form (decode_qdot.hip)
     QMat q_gu, q_d, q_sgu, q_sd;
     size_t packed_bytes = 0;
 };
@@ -318,6 +319,8 @@ class Engine {
     ~Engine();
     // MoE layers that kept their packed blocks / all MoE layers / device bytes of the packed tables
     void packed_info(size_t* packed_layers, size_t* moe_layers, size_t* packed_bytes) const;
+    // 0 dequant-on-load, 1 packed experts (fp16-exact), 2 packed experts with integer block dots
+    int packed_mode() const { return packed_mode_; }
 
     const ModelConfig& cfg() const { return cfg_; }
     int variant() const { return cfg_.variant; }
@@ -470,6 +473,7 @@ class Engine {
   private:
     // ---- loading
     void load_weights(const std::string& path, uint64_t seed, const std::string& snapshot_path, bool packed_experts);
+    int packed_mode_ = 0;
     // ---- workspace
     void* ws(const std::string& name, size_t bytes);
     float* wsf(const std::string& name, size_t n) { return (float*)ws(name, n * sizeof(float)); }

@@ -836,6 +836,7 @@ enum class GateUp {
     Grp,         // moe_gateup_grp_kernel
     Mm,          // moe_gateup_mm_kernel (decode_mm.hip); routes too under Route::InGateupMm
     Q,           // moe_gateup_q_kernel (decode_q.hip)
+    Qdot,        // q8_quantize_kernel over xn, then moe_gateup_qdot_kernel (decode_qdot.hip)
 };
 enum class Down {
     Mix,          // moe_down_mix_kernel (T = 1)
@@ -845,6 +846,7 @@ enum class Down {
     Grp,          // moe_down_grp_kernel
     Mm,           // moe_down_mm_kernel (decode_mm.hip)
     Q,            // moe_down_q_kernel (decode_q.hip)
+    Qdot,         // q8_quantize_kernel over h and hs, then moe_down_qdot_kernel (decode_qdot.hip)
 };
 
 // The forms behind launch_moe_gateup2 / launch_moe_down2, read off the launch's own arguments (the two are entry
@@ -1216,7 +1218,8 @@ static bool route_fused_on() {
 }
 
 // The only place that reads the layer's shapes: T = 1 mix, T <= 2 (or no grouped form) self-routing slots, 3..8
-// grouped by expert, more than 8 sorted; packed experts (T <= 8) take the grouped packed kernels.
+// grouped by expert, more than 8 sorted; packed experts (T <= 8) take the grouped packed kernels, in their
+// integer-dot form when the arguments carry the code-plane workspace.
 MoePlan moe_plan(const MoeDecodeArgs& a) {
     const int T = a.T, E = a.E, K = a.topk, TK = T * K;
     if (T <= 0 || TK > 512 || E > 256 || K > 8 || K > E)
@@ -1247,6 +1250,13 @@ MoePlan moe_plan(const MoeDecodeArgs& a) {
             p.route = Route::DecRouteGrp;
             p.gu = GateUp::Q;
             p.dn = Down::Q;
+            if (a.q8_ws) {  // the integer-dot form where its shapes allow, else the fp16-exact packed kernels
+                moe_qdot_planes(a.q8_ws, T, K, a.H, a.I, q.Is, &q.qx, &q.qh, &q.qhs);
+                if (moe_qdot_ok(q)) {
+                    p.gu = GateUp::Qdot;
+                    p.dn = Down::Qdot;
+                }
+            }
             return p;
         }
         if (!a.Wgu || !a.Wd) throw std::runtime_error("EINVAL: packed decode MoE outside its range (T <= 8, E <= 64, H <= 1536)");
@@ -1324,6 +1334,7 @@ void moe_decode_kernel_names(const MoeDecodeArgs& a, const char** gateup, const 
         case GateUp::Grp: gu = "moe_gateup_grp_kernel"; break;
         case GateUp::Mm: gu = "moe_gateup_mm_kernel"; break;
         case GateUp::Q: gu = "moe_gateup_q_kernel"; break;
+        case GateUp::Qdot: gu = "moe_gateup_qdot_kernel"; break;
     }
     switch (p.dn) {
         case Down::Mix: dn = "moe_down_mix_kernel"; break;
@@ -1333,6 +1344,7 @@ void moe_decode_kernel_names(const MoeDecodeArgs& a, const char** gateup, const 
         case Down::Grp: dn = "moe_down_grp_kernel"; break;
         case Down::Mm: dn = "moe_down_mm_kernel"; break;
         case Down::Q: dn = "moe_down_q_kernel"; break;
+        case Down::Qdot: dn = "moe_down_qdot_kernel"; break;
     }
     if (gateup) *gateup = gu;
     if (down) *down = dn;
@@ -1374,6 +1386,7 @@ void launch_moe_decode(const MoeDecodeArgs& a, hipStream_t s, int parts) {
     if (parts & MOE_GATEUP) {
         switch (p.gu) {
             case GateUp::Q: launch_moe_gateup_q(p.q, s); break;
+            case GateUp::Qdot: launch_moe_gateup_qdot(p.q, s); break;
             case GateUp::Mix: launch_moe_gateup_mix(m, a.xn_router, s); break;
             case GateUp::Mm: launch_moe_gateup_mm(p.route == Route::InGateupMm ? p.mr : m, s); break;
             case GateUp::Grp: launch_moe_gateup_grp(m, s); break;
@@ -1386,6 +1399,7 @@ void launch_moe_decode(const MoeDecodeArgs& a, hipStream_t s, int parts) {
     if (parts & MOE_DOWN) {
         switch (p.dn) {
             case Down::Q: launch_moe_down_q(p.q, s); break;
+            case Down::Qdot: launch_moe_down_qdot(p.q, s); break;
             case Down::Mm: launch_moe_down_mm(m, s); break;
             case Down::Grp: launch_moe_down_grp(m, s); break;
             case Down::Mix: launch_moe_down_mix(m, s); break;

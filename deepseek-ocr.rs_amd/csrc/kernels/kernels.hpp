@@ -15,6 +15,14 @@ struct QMat {
     const void* d = nullptr;
     int qtype = 0;
 };
+// Activation rows quantised to 8-bit blocks for the integer-dot kernels (decode_qdot.hip): codes [rows][in_dim];
+// d [rows][in_dim / 256] (Q8_K) or [rows][in_dim / 32] (Q8_0: the f16 scale, held widened); bs [rows][in_dim / 32]
+// (Q8_K only: the code sum of every 32 values)
+struct Q8Planes {
+    int8_t* q = nullptr;
+    float* d = nullptr;
+    int16_t* bs = nullptr;
+};
 
 // Profiling hook: while prof_events() holds a (start, stop) pair, the next kernel launched through
 // DSOCR_LAUNCH (the decode_*.hip units, lmhead.hip) records its own dispatch begin / end into the two events
@@ -550,6 +558,9 @@ struct MoeDecodeArgs {
     // Q4_K / Q8_0 tables instead of streaming the fp16 matrices above (which may then be null); routed
     // [E][2I][H] and [E][H][I], shared [2Is][H] and [H][Is], made by launch_dsq_repack
     QMat qWgu, qWd, qsWgu, qsWd;
+    // integer-dot form of the packed launches (decode_qdot.hip): a workspace of moe_qdot_ws_bytes(T, topk, H, I, Is)
+    // bytes for the activation code planes; null = the fp16-exact packed kernels
+    void* q8_ws = nullptr;
 };
 // ---- one-page decode step as ONE persistent launch (decode_persist.hip): every decoder layer inside 256 resident
 // workgroups handing their vectors over as {f32, tag} granules (tag = the decode position; the granule buffer is
@@ -916,10 +927,24 @@ struct MoeQArgs {
     float* h = nullptr; float* hs = nullptr;   // [T*topk][I], [T][Is]
     float* out = nullptr;                      // [T][H], += combined
     unsigned long long* span = nullptr;        // launch-span slots (SPAN_SLOTS pairs) or null
+    Q8Planes qx, qh, qhs;                      // integer-dot form only: the code planes of x, h and hs
 };
 bool moe_q_ok(const MoeQArgs& a);
 void launch_moe_gateup_q(const MoeQArgs& a, hipStream_t s);
 void launch_moe_down_q(const MoeQArgs& a, hipStream_t s);
+
+// Integer-dot form of the packed decode MoE (decode_qdot.hip; contract: DESIGN.md section 4.4.2): the activation
+// rows are quantised to 8-bit blocks (Q8_K for a Q4_K table, Q8_0 for a Q8_0 one) and every block dot is int32.
+// launch_q8_quantize: x [rows][in_dim] -> planes (kind = the table's qtype).  launch_dsq_rows_dot_q8: y[T][rows] =
+// codes . W^T (parity hook).  The gate/up launch quantises a.x into a.qx first, the down launch a.h / a.hs into
+// a.qh / a.qhs; moe_qdot_planes carves the three plane sets out of one workspace of moe_qdot_ws_bytes bytes.
+size_t moe_qdot_ws_bytes(int T, int topk, int H, int I, int Is);
+void moe_qdot_planes(void* ws, int T, int topk, int H, int I, int Is, Q8Planes* qx, Q8Planes* qh, Q8Planes* qhs);
+void launch_q8_quantize(int kind, int rows, int in_dim, const float* x, const Q8Planes& o, hipStream_t s);
+void launch_dsq_rows_dot_q8(const QMat& m, long rows, long in_dim, int T, const Q8Planes& p, float* y, hipStream_t s);
+bool moe_qdot_ok(const MoeQArgs& a);
+void launch_moe_gateup_qdot(const MoeQArgs& a, hipStream_t s);
+void launch_moe_down_qdot(const MoeQArgs& a, hipStream_t s);
 
 // Page preprocessing on the GPU (preprocess.hip): Pillow 22-bit bicubic (tap tables from the host),
 // then a vertical pass fused with canvas placement / tile cropping and the CHW normalisation

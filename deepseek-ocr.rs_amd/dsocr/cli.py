@@ -31,6 +31,11 @@ from .engine import DecodeParameters, ModelLoadArgs, VisionSettings, load_model,
 from .streaming import DeltaTracker, decode_ids
 
 
+def snapshot_packed_arg(args):
+    """ModelLoadArgs.snapshot_packed from --snapshot-packed / --snapshot-int8-dot."""
+    return "int8" if getattr(args, "snapshot_int8_dot", False) else getattr(args, "snapshot_packed", None)
+
+
 def _bool(v: str) -> bool:
     s = v.strip().lower()
     if s in ("1", "true", "yes", "on"):
@@ -54,6 +59,9 @@ def add_model_args(p: argparse.ArgumentParser) -> None:
     g.add_argument("--snapshot-packed", action="store_true", default=None,
                    help="decode the MoE experts from the snapshot's packed Q4_K / Q8_0 blocks (needs --snapshot; "
                         "default: the DSOCR_DSQ_PACKED environment switch decides)")
+    g.add_argument("--snapshot-int8-dot", action="store_true", default=False,
+                   help="as --snapshot-packed, with the activations quantised to 8-bit blocks and integer block dots "
+                        "(needs --snapshot; results differ from dequant-on-load by the activation rounding)")
     g.add_argument("--synthetic-seed", type=int, default=0, help="seed of the synthetic checkpoint")
 
 
@@ -366,7 +374,7 @@ def run_inference(args, out=sys.stdout, err=sys.stderr) -> int:
     events = []
     t0 = time.perf_counter()
     engine = load_model(ModelLoadArgs(config_path=config, weights_path=args.weights, snapshot_path=args.snapshot,
-                                      snapshot_packed=getattr(args, "snapshot_packed", None),
+                                      snapshot_packed=snapshot_packed_arg(args),
                                       device=device, dtype=args.dtype, synthetic_seed=args.synthetic_seed))
     load_ms = (time.perf_counter() - t0) * 1e3
     events.append(_event("model.load", load_ms, model=args.model, kind="Deepseek", device=f"hip:{device}",

@@ -14,11 +14,11 @@ from __future__ import annotations
 
 import ctypes as C
 from dataclasses import dataclass, field
-from typing import Any, Callable, Optional, Sequence
+from typing import Any, Callable, Optional, Sequence, Union
 
 import numpy as np
 
-from ._lib import (DTYPES, LOAD_PACKED_EXPERTS, MAX_TOP_LOGPROBS, DecodeParamsC, DsocrError, LoadArgs, LogitBiasC, LogprobsC,
+from ._lib import (DTYPES, LOAD_PACKED_EXPERTS, LOAD_PACKED_INT8_DOT, MAX_TOP_LOGPROBS, DecodeParamsC, DsocrError, LoadArgs, LogitBiasC, LogprobsC,
                    GuidedC, GuidedResultC, NgramWindowC, PenaltiesC, SESSION_GUIDED, RequestC, ResultC, STREAM_CB, SESSION_LOGIT_BIAS, SESSION_LOGPROBS,
                    SESSION_NGRAM_WINDOW, SESSION_PENALTIES,
                    SESSION_PER_REQUEST, SESSION_STOP,
@@ -185,8 +185,9 @@ class ModelLoadArgs:
     snapshot_path: Optional[str] = None
     # MoE experts decoded from the snapshot's packed Q4_K / Q8_0 blocks at 1..8 decode tokens
     # (DSOCR_LOAD_PACKED_EXPERTS): None = dsocr_engine_load (the DSOCR_DSQ_PACKED environment switch decides),
-    # True / False = dsocr_engine_load_flags
-    snapshot_packed: Optional[bool] = None
+    # True / False = dsocr_engine_load_flags; "int8" = the packed launches in integer-dot form
+    # (DSOCR_LOAD_PACKED_INT8_DOT: 8-bit activation blocks, int32 block dots)
+    snapshot_packed: Union[None, bool, str] = None
     device: int = 0
     dtype: str = "f16"
     synthetic_seed: int = 0
@@ -378,8 +379,11 @@ class DeepseekOcrEngine:
         if args.snapshot_packed is None:
             check(lib().dsocr_engine_load(C.byref(la), C.byref(h)))
         else:
-            check(lib().dsocr_engine_load_flags(C.byref(la), LOAD_PACKED_EXPERTS if args.snapshot_packed else 0,
-                                                C.byref(h)))
+            if isinstance(args.snapshot_packed, str) and args.snapshot_packed != "int8":
+                raise DsocrError(1, f"snapshot_packed takes None, True, False or 'int8', not {args.snapshot_packed!r}")
+            flags = (LOAD_PACKED_EXPERTS | LOAD_PACKED_INT8_DOT if args.snapshot_packed == "int8"
+                     else LOAD_PACKED_EXPERTS if args.snapshot_packed else 0)
+            check(lib().dsocr_engine_load_flags(C.byref(la), flags, C.byref(h)))
         self._h = h
         self.args = args
         hid, voc, eos, nl = C.c_size_t(), C.c_size_t(), C.c_int64(), C.c_size_t()
@@ -394,6 +398,12 @@ class DeepseekOcrEngine:
         pl, ml, pb = C.c_size_t(), C.c_size_t(), C.c_size_t()
         check(lib().dsocr_engine_packed_info(self._h, C.byref(pl), C.byref(ml), C.byref(pb)))
         return {"packed_layers": pl.value, "moe_layers": ml.value, "packed_bytes": pb.value}
+
+    def packed_mode(self) -> int:
+        """0 dequant-on-load, 1 packed experts, 2 packed experts with integer block dots."""
+        m = C.c_int()
+        check(lib().dsocr_engine_packed_mode(self._h, C.byref(m)))
+        return m.value
 
     # OcrEngine accessors (inference.rs:189-198)
     def kind(self):

@@ -122,12 +122,20 @@ dsocr_status dsocr_engine_load(const dsocr_load_args* args, dsocr_engine** out);
  * than 8 tokens, attention, the dense layer and the lm_head run the fp16 kernels as without the flag.
  * dsocr_engine_load(args, out) is dsocr_engine_load_flags(args, flags, out) with flags =
  * DSOCR_LOAD_PACKED_EXPERTS when args carries a snapshot and the environment has DSOCR_DSQ_PACKED set to a
- * non-zero value, else 0. */
+ * non-zero value, else 0.
+ * DSOCR_LOAD_PACKED_INT8_DOT (implies DSOCR_LOAD_PACKED_EXPERTS; DSOCR_EINVAL without a snapshot): the packed
+ * layers run their gate/up and down launches in integer-dot form — the activation rows are quantised to 8-bit
+ * blocks (Q8_K against Q4_K rows, Q8_0 against Q8_0 rows) and every block dot is int32 (DESIGN.md section
+ * 4.4.2).  Results then differ from dequant-on-load by the 8-bit activation rounding.  dsocr_engine_load adds
+ * the flag when args carries a snapshot and the environment has DSOCR_DSQ_INT8 set to a non-zero value. */
 #define DSOCR_LOAD_PACKED_EXPERTS 1u
+#define DSOCR_LOAD_PACKED_INT8_DOT 2u
 dsocr_status dsocr_engine_load_flags(const dsocr_load_args* args, uint32_t flags, dsocr_engine** out);
 /* MoE layers that kept packed blocks, MoE layers in all, device bytes of the packed tables (any may be NULL) */
 dsocr_status dsocr_engine_packed_info(const dsocr_engine* e, size_t* packed_layers, size_t* moe_layers,
                                       size_t* packed_bytes);
+/* How the engine was loaded: 0 dequant-on-load, 1 packed experts, 2 packed experts with integer block dots */
+dsocr_status dsocr_engine_packed_mode(const dsocr_engine* e, int* mode);
 void dsocr_engine_free(dsocr_engine* e);
 const char* dsocr_last_error(void);
 /* hidden size (image-row width), vocab, eos id, layers */
@@ -948,6 +956,24 @@ dsocr_status dsocr_k_moe_packed(int T, int H, int E, int topk, int I, int Is, co
  * skipped and the sums start from -0, so a one-hot x row returns the decoded weights bit for bit. */
 dsocr_status dsocr_k_dsq_rows_dot(int qtype, size_t rows, size_t in_dim, const void* payload, int T, const float* x,
                                   float* y);
+/* Parity hooks of the integer-dot form (DSOCR_LOAD_PACKED_INT8_DOT; device pointers unless said otherwise).
+ * dsocr_k_q8_quantize: T rows x [T][in_dim] to 8-bit blocks, kind 12 -> Q8_K (codes, d [T][in_dim / 256], bs
+ * [T][in_dim / 32]: the code sum of every 32 values), kind 8 -> Q8_0 (codes, d [T][in_dim / 32]: the f16 scale
+ * widened to f32; bs unused, may be NULL). */
+dsocr_status dsocr_k_q8_quantize(int kind, int T, size_t in_dim, const float* x, int8_t* codes, float* d, int16_t* bs);
+/* y[T][rows] = (d . codes) . W^T by integer block dots, W a record-layout payload of qtype 8 / 12 and the planes
+ * those of dsocr_k_q8_quantize for the same kind (T <= 8). */
+dsocr_status dsocr_k_dsq_rows_dot_q8(int qtype, size_t rows, size_t in_dim, const void* payload, int T, const int8_t* codes,
+                                     const float* d, const int16_t* bs, float* y);
+/* dsocr_k_moe_packed through the integer-dot launches.  The optional outputs (HOST pointers, NULL to skip) receive
+ * the code and d planes the launches used: of the normalised rows (xn: [T][H]), of the routed h rows ([T topk][I])
+ * and of the shared expert's h rows ([T][Is]); d planes are per 256 values for a Q4_K table, per 32 for a Q8_0 one. */
+dsocr_status dsocr_k_moe_packed_q8(int T, int H, int E, int topk, int I, int Is, const float* x, const float* norm_w,
+                                   float eps, const void* router_f16, int gu_qtype, const void* Wgu_payload, int d_qtype,
+                                   const void* Wd_payload, int sgu_qtype, const void* sWgu_payload, int sd_qtype,
+                                   const void* sWd_payload, int norm_topk, float scaling, float* out, int* topk_ids_out,
+                                   float* topk_w_out, int8_t* xn_codes, float* xn_d, int8_t* h_codes, float* h_d,
+                                   int8_t* hs_codes, float* hs_d);
 /* Kernel names launch_moe_decode picks for a decode MoE of T tokens (static strings), e.g. the bench's
  * roofline label: "moe_gateup_mix_kernel" at T = 1, "moe_gateup_grp_kernel" at T = 3..8. */
 dsocr_status dsocr_k_moe_kernels(int T, int H, int E, int topk, int I, int Is, int has_norm, const char** gateup,
