@@ -401,7 +401,17 @@ dsocr_status dsocr_engine_load(const dsocr_load_args* args, dsocr_engine** out) 
     const bool packed = e && atoi(e) != 0 && args && args->snapshot_path;
     const char* i8 = getenv("DSOCR_DSQ_INT8");
     const bool int8 = i8 && atoi(i8) != 0 && args && args->snapshot_path;
-    return dsocr_engine_load_flags(args, (packed ? DSOCR_LOAD_PACKED_EXPERTS : 0u) | (int8 ? DSOCR_LOAD_PACKED_INT8_DOT : 0u), out);
+    const char* f8 = getenv("DSOCR_EXPERT_FP8");
+    const bool fp8 = f8 && atoi(f8) != 0;
+    return dsocr_engine_load_flags(args, (packed ? DSOCR_LOAD_PACKED_EXPERTS : 0u) | (int8 ? DSOCR_LOAD_PACKED_INT8_DOT : 0u) |
+                                             (fp8 ? DSOCR_LOAD_FP8_EXPERTS : 0u), out);
+}
+
+dsocr_status dsocr_engine_fp8_info(const dsocr_engine* e, size_t* fp8_layers, size_t* moe_layers, size_t* fp8_bytes) {
+    return guarded([&] {
+        if (!e) throw std::runtime_error("EINVAL: NULL engine");
+        e->impl->fp8_info(fp8_layers, moe_layers, fp8_bytes);
+    });
 }
 
 dsocr_status dsocr_engine_packed_mode(const dsocr_engine* e, int* mode) {
@@ -2204,6 +2214,89 @@ dsocr_status dsocr_k_dsq_rows_dot_q8(int qtype, size_t rows, size_t in_dim, cons
             throw;
         }
         (void)hipFree(buf);
+    });
+}
+// ---- FP8 experts (decode_f8.hip)
+dsocr_status dsocr_k_fp8_quantize_rows(size_t rows, size_t cols, const void* w_f16, uint8_t* codes_out, int8_t* exps_out) {
+    return guarded([&] {
+        if (!rows || !w_f16 || !codes_out || !exps_out) throw std::runtime_error("EINVAL: NULL argument");
+        dsocr::launch_fp8_quantize_rows((long)rows, (long)cols, w_f16, codes_out, exps_out, nullptr);
+        check_hip(hipGetLastError(), "fp8_quantize_rows launch");
+        check_hip(hipDeviceSynchronize(), "fp8_quantize_rows");
+    });
+}
+dsocr_status dsocr_k_fp8_rows_dot(size_t rows, size_t cols, const uint8_t* codes, const int8_t* exps, int T, const float* x,
+                                  float* y) {
+    return guarded([&] {
+        dsocr::F8Mat m;
+        m.q = codes; m.e = exps;
+        dsocr::launch_fp8_rows_dot(m, (long)rows, (long)cols, T, x, y, nullptr);
+        check_hip(hipGetLastError(), "fp8_rows_dot launch");
+        check_hip(hipDeviceSynchronize(), "fp8_rows_dot");
+    });
+}
+dsocr_status dsocr_k_moe_fp8(int T, int H, int E, int topk, int I, int Is, const float* x, const float* norm_w, float eps,
+                             const void* router_f16, const void* Wgu_f16, const void* Wd_f16, const void* sWgu_f16,
+                             const void* sWd_f16, int norm_topk, float scaling, float* out, int* ids_out, float* w_out) {
+    return guarded([&] {
+        if (T <= 0 || T > 8 || H <= 0 || E <= 0 || topk <= 0 || I <= 0 || Is < 0) throw std::runtime_error("EINVAL: bad MoE shape");
+        if (!x || !router_f16 || !Wgu_f16 || !Wd_f16 || !out) throw std::runtime_error("EINVAL: NULL argument");
+        const bool shared = sWgu_f16 && sWd_f16 && Is > 0;
+        if (!dsocr::fp8_rows_ok(H) || !dsocr::fp8_rows_ok(I) || (shared && !dsocr::fp8_rows_ok(Is)))
+            throw std::runtime_error("EINVAL: FP8 experts take widths that are multiples of 16");
+        std::vector<void*> bufs;
+        auto alloc = [&](size_t b) {
+            void* p = nullptr;
+            check_hip(hipMalloc(&p, b ? b : 16), "hipMalloc");
+            bufs.push_back(p);
+            return p;
+        };
+        try {
+            const int TK = T * topk;
+            auto quantise = [&](const void* w, long rows, long cols) {
+                dsocr::F8Mat m;
+                uint8_t* q = (uint8_t*)alloc((size_t)rows * cols);
+                int8_t* e = (int8_t*)alloc((size_t)rows);
+                dsocr::launch_fp8_quantize_rows(rows, cols, w, q, e, nullptr);
+                m.q = q; m.e = e;
+                return m;
+            };
+            dsocr::MoeDecodeArgs a;
+            a.T = T; a.H = H; a.E = E; a.topk = topk; a.I = I;
+            a.x = x; a.norm_w = norm_w; a.eps = eps; a.out = out;
+            a.router = router_f16; a.router_wdt = dsocr::WDT_F16; a.wdtype = dsocr::WDT_F16;
+            a.Wgu = Wgu_f16; a.Wd = Wd_f16;
+            a.f8Wgu = quantise(Wgu_f16, (long)E * 2 * I, H);
+            a.f8Wd = quantise(Wd_f16, (long)E * H, I);
+            if (shared) {
+                a.Is = Is; a.sWgu = sWgu_f16; a.sWd = sWd_f16;
+                a.f8sWgu = quantise(sWgu_f16, 2L * Is, H);
+                a.f8sWd = quantise(sWd_f16, H, Is);
+                a.hs = (float*)alloc(sizeof(float) * (size_t)T * Is);
+            }
+            a.softmax_scoring = 1; a.norm_topk = norm_topk; a.scaling = scaling;
+            a.xn = (float*)alloc(sizeof(float) * (size_t)T * H);
+            a.xn_router = (float*)alloc(sizeof(float) * (size_t)T * H);
+            a.logits = (float*)alloc(sizeof(float) * (size_t)T * E);
+            a.ids = (int*)alloc(sizeof(int) * TK);
+            a.wts = (float*)alloc(sizeof(float) * TK);
+            a.h = (float*)alloc(sizeof(float) * (size_t)TK * I);
+            a.grp = (int*)alloc(sizeof(int) * dsocr::moe_grp_ints(E, T, topk));
+            a.route_cnt = (int*)alloc(sizeof(int) * 16);
+            check_hip(hipMemset(a.route_cnt, 0, sizeof(int) * 16), "hipMemset");
+            const char* gu = nullptr;
+            dsocr::moe_decode_kernel_names(a, &gu, nullptr);
+            if (std::string(gu) != "moe_gateup_f8_kernel") throw std::runtime_error("EINVAL: FP8 decode MoE outside its range");
+            dsocr::launch_moe_decode(a, nullptr);
+            check_hip(hipGetLastError(), "moe launch");
+            check_hip(hipDeviceSynchronize(), "moe");
+            if (ids_out) check_hip(hipMemcpy(ids_out, a.ids, sizeof(int) * TK, hipMemcpyDeviceToHost), "d2h");
+            if (w_out) check_hip(hipMemcpy(w_out, a.wts, sizeof(float) * TK, hipMemcpyDeviceToHost), "d2h");
+        } catch (...) {
+            for (void* p : bufs) (void)hipFree(p);
+            throw;
+        }
+        for (void* p : bufs) (void)hipFree(p);
     });
 }
 dsocr_status dsocr_k_dsq_rows_dot(int qtype, size_t rows, size_t in_dim, const void* payload, int T, const float* x,

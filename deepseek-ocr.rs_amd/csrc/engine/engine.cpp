@@ -246,7 +246,11 @@ void* Engine::ws(const std::string& name0, size_t bytes) {
 Engine::Engine(const std::string& config_path, const std::string& weights_path, int device, int dtype, uint64_t seed,
                const std::string& snapshot_path, uint32_t load_flags)
     : device_(device), dtype_(dtype) {
-    if (load_flags & ~3u) throw std::runtime_error("EINVAL: unknown load flags");
+    if (load_flags & ~7u) throw std::runtime_error("EINVAL: unknown load flags");
+    if ((load_flags & 4u) && (load_flags & 3u))
+        throw std::runtime_error("EINVAL: FP8 experts cannot be combined with packed snapshot experts");
+    if ((load_flags & 4u) && dtype != 1) throw std::runtime_error("EINVAL: FP8 experts quantise the fp16 engine's weights: use dtype f16");
+    fp8_experts_ = (load_flags & 4u) != 0;
     if (load_flags & 2u) load_flags |= 1u;  // the integer-dot form runs on the packed tables
     packed_mode_ = (load_flags & 2u) ? 2 : (int)(load_flags & 1u);
     if ((load_flags & 1u) && snapshot_path.empty())
@@ -273,6 +277,11 @@ Engine::Engine(const std::string& config_path, const std::string& weights_path, 
     if (!snapshot_path.empty() && cfg_.variant == VARIANT_OCR2)
         throw std::runtime_error("EINVAL: .dsq snapshots are not supported for DeepSeek-OCR-2 configs (load the checkpoint without snapshot_path)");
     load_weights(weights_path, seed, snapshot_path, (load_flags & 1u) != 0);
+    if (fp8_experts_ && cfg_.variant == VARIANT_OCR2) {
+        size_t fl = 0;
+        fp8_info(&fl, nullptr, nullptr);
+        if (!fl) throw std::runtime_error("EINVAL: FP8 experts: no MoE layer of this DeepSeek-OCR-2 decoder fits the FP8 kernels");
+    }
     ensure_rope(4096);
     ensure_small(64);
     HIP_CHECK(hipStreamSynchronize(stream_));
@@ -438,6 +447,18 @@ void Engine::packed_info(size_t* packed_layers, size_t* moe_layers, size_t* pack
     if (packed_layers) *packed_layers = pl;
     if (moe_layers) *moe_layers = ml;
     if (packed_bytes) *packed_bytes = pb;
+}
+
+void Engine::fp8_info(size_t* fp8_layers, size_t* moe_layers, size_t* fp8_bytes) const {
+    size_t fl = 0, ml = 0, fb = 0;
+    for (const DecLayer& d : layers_) {
+        if (!d.moe) continue;
+        ++ml;
+        if (d.fp8) { ++fl; fb += d.fp8_bytes; }
+    }
+    if (fp8_layers) *fp8_layers = fl;
+    if (moe_layers) *moe_layers = ml;
+    if (fp8_bytes) *fp8_bytes = fb;
 }
 
 void Engine::load_weights(const std::string& path, uint64_t seed, const std::string& snapshot_path, bool packed_experts) {
@@ -764,6 +785,31 @@ void Engine::load_weights(const std::string& path, uint64_t seed, const std::str
                     d.packed = true;
                     d.int8dot = packed_mode_ == 2;
                 }
+            }
+            // FP8 experts (DSOCR_LOAD_FP8_EXPERTS): E4M3 codes and a row exponent beside the fp16 tables, for the
+            // layers whose router fits dec_route_grp and whose widths are whole 16-code granules; any other layer
+            // runs the fp16 kernels.  The fp16 tables of an FP8 layer then hold W8 (an fp16 tensor), so prefill and
+            // batches above 8 run on the weights the FP8 launches stream.
+            const int Is8 = d.has_shared ? d.s_d.K : 0;
+            if (fp8_experts_ && d.e_wdt == WDT_F16 && dec_route_grp_ok(8, E, H, L.topk) && H % 16 == 0 && I % 16 == 0 &&
+                Is8 % 16 == 0 && (!d.has_shared || (d.s_gu.wdt == WDT_F16 && d.s_d.wdt == WDT_F16 && !d.s_gu.b && !d.s_d.b))) {
+                auto quantise = [&](void* w, long rows, long cols, F8Mat& out) {
+                    const size_t codes = ((size_t)rows * cols + 15) & ~(size_t)15, exps = ((size_t)rows + 15) & ~(size_t)15;
+                    uint8_t* q = (uint8_t*)dev_alloc(codes);
+                    int8_t* e = (int8_t*)dev_alloc(exps);
+                    launch_fp8_quantize_rows(rows, cols, w, q, e, stream_);
+                    out.q = q; out.e = e;
+                    launch_fp8_dequant_rows(rows, cols, out, w, stream_);
+                    d.fp8_bytes += codes + exps;
+                };
+                quantise(d.e_gu, (long)E * 2 * I, H, d.f8_gu);
+                quantise(d.e_d, (long)E * H, I, d.f8_d);
+                if (d.has_shared) {
+                    quantise(d.s_gu.W, 2L * Is8, H, d.f8_sgu);
+                    quantise(d.s_d.W, H, Is8, d.f8_sd);
+                }
+                HIP_CHECK(hipStreamSynchronize(stream_));
+                d.fp8 = true;
             }
         }
         layers_.push_back(d);
@@ -1325,6 +1371,9 @@ MoeDecodeArgs Engine::moe_args(int l, int B, float* X) {
         a.qWgu = d.q_gu; a.qWd = d.q_d; a.qsWgu = d.q_sgu; a.qsWd = d.q_sd;
         if (d.int8dot) a.q8_ws = ws("s_q8", moe_qdot_ws_bytes(B, K, H, I, a.Is));
     }
+    if (B <= 8 && d.fp8) {  // the FP8 decode kernels (decode_f8.hip)
+        a.f8Wgu = d.f8_gu; a.f8Wd = d.f8_d; a.f8sWgu = d.f8_sgu; a.f8sWd = d.f8_sd;
+    }
     if (B <= 8 && d.e_gu_swz && (!d.has_shared || d.s_gu_swz)) {  // fragment-ordered experts
         a.Wgu_swz = d.e_gu_swz; a.Wd_swz = d.e_d_swz; a.sWgu_swz = d.s_gu_swz; a.sWd_swz = d.s_d_swz;
         if (!router_swz_off()) a.router_swz = d.router_swz;
@@ -1376,7 +1425,7 @@ bool Engine::persist_ok(int B, int Lmax) {
     if (!e || atoi(e) == 0) return false;
     const LangConfig& L = cfg_.lang;
     for (const DecLayer& d : layers_)
-        if (d.packed) return false;  // the persistent launch streams the fp16 experts only
+        if (d.packed || d.fp8) return false;  // the persistent launch streams the fp16 experts only
     if (B != 1 || L.use_mla || L.rope_dim != L.head_dim || L.v_head_dim != L.head_dim || L.n_shared <= 0 ||
         L.topk_method != "greedy" || L.hidden_act != "silu")
         return false;
@@ -1693,7 +1742,7 @@ void Engine::ensure_mm_weights(int B) {
         if (!d.moe) swz(d.gu, d.gu_swz);
     }
     for (DecLayer& d : layers_) {
-        if (!d.moe || d.packed || d.e_gu_swz || d.e_wdt != WDT_F16 || H % 32 || I % 32) continue;
+        if (!d.moe || d.packed || d.fp8 || d.e_gu_swz || d.e_wdt != WDT_F16 || H % 32 || I % 32) continue;
         d.e_gu_swz = dev_alloc(mm_swizzle_elems(E * 2 * I, H) * 2);
         launch_mm_swizzle(d.e_gu, E * 2 * I, H, d.e_gu_swz, stream_);
         d.e_d_swz = dev_alloc(mm_swizzle_elems(E * H, I) * 2);
@@ -3824,6 +3873,13 @@ Engine::DecodeProfile Engine::profile_decode(int iters) {
                 prof.moe_gateup.bytes += 2.0 * planes(B, H);
                 prof.moe_down.bytes += 2.0 * (planes(TK, I) + planes(B, Is));
             }
+        }
+        if (std::string(prof.gateup_kernel) == "moe_gateup_f8_kernel") {
+            // FP8 layers stream one byte per weight and one exponent byte per row
+            prof.moe_gateup.bytes = (touched * 2.0 * I + 2.0 * Is) * (H + 1.0)
+                                    + (double)B * H * 4 + (double)(TK * I + B * Is) * 4;
+            prof.moe_down.bytes = touched * H * (I + 1.0) + (Is ? H * (Is + 1.0) : 0.0)
+                                  + (double)(TK * I + B * Is) * 4 + 2.0 * B * H * 4;
         }
     }
     float* CTX = wsf("p_ctx", (size_t)B * H);

@@ -86,6 +86,11 @@ struct DecLayer {
     bool int8dot = false;  // DSOCR_LOAD_PACKED_INT8_DOT: the packed launches in their integer-dot form (decode_qdot.hip)
     QMat q_gu, q_d, q_sgu, q_sd;
     size_t packed_bytes = 0;
+    // FP8 experts (DSOCR_LOAD_FP8_EXPERTS): E4M3 codes and row exponents for the FP8 decode kernels (decode_f8.hip),
+    // beside the fp16 copies above, in their layouts
+    bool fp8 = false;
+    F8Mat f8_gu, f8_d, f8_sgu, f8_sd;
+    size_t fp8_bytes = 0;
 };
 
 // DeepSeek-OCR-2: the Qwen2 decoder used as the vision encoder (vision/qwen2.rs)
@@ -321,6 +326,8 @@ class Engine {
     void packed_info(size_t* packed_layers, size_t* moe_layers, size_t* packed_bytes) const;
     // 0 dequant-on-load, 1 packed experts (fp16-exact), 2 packed experts with integer block dots
     int packed_mode() const { return packed_mode_; }
+    // MoE layers that run the FP8 decode kernels / all MoE layers / device bytes of the FP8 tables
+    void fp8_info(size_t* fp8_layers, size_t* moe_layers, size_t* fp8_bytes) const;
 
     const ModelConfig& cfg() const { return cfg_; }
     int variant() const { return cfg_.variant; }
@@ -474,6 +481,7 @@ class Engine {
     // ---- loading
     void load_weights(const std::string& path, uint64_t seed, const std::string& snapshot_path, bool packed_experts);
     int packed_mode_ = 0;
+    bool fp8_experts_ = false;
     // ---- workspace
     void* ws(const std::string& name, size_t bytes);
     float* wsf(const std::string& name, size_t n) { return (float*)ws(name, n * sizeof(float)); }

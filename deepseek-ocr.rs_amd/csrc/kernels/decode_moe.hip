@@ -837,6 +837,7 @@ enum class GateUp {
     Mm,          // moe_gateup_mm_kernel (decode_mm.hip); routes too under Route::InGateupMm
     Q,           // moe_gateup_q_kernel (decode_q.hip)
     Qdot,        // q8_quantize_kernel over xn, then moe_gateup_qdot_kernel (decode_qdot.hip)
+    F8,          // moe_gateup_f8_kernel (decode_f8.hip)
 };
 enum class Down {
     Mix,          // moe_down_mix_kernel (T = 1)
@@ -847,6 +848,7 @@ enum class Down {
     Mm,           // moe_down_mm_kernel (decode_mm.hip)
     Q,            // moe_down_q_kernel (decode_q.hip)
     Qdot,         // q8_quantize_kernel over h and hs, then moe_down_qdot_kernel (decode_qdot.hip)
+    F8,           // moe_down_f8_kernel (decode_f8.hip)
 };
 
 // The forms behind launch_moe_gateup2 / launch_moe_down2, read off the launch's own arguments (the two are entry
@@ -1205,6 +1207,7 @@ struct MoePlan {
     MoeDec2Args m;
     DecGemvArgs router;
     MoeQArgs q;      // GateUp::Q / Down::Q: the packed launches' arguments (decode_q.hip)
+    MoeF8Args f8;    // GateUp::F8 / Down::F8: the FP8 launches' arguments (decode_f8.hip)
     MoeDec2Args mr;  // Route::InGateupMm: the arguments of the gate/up launch that also routes
 };
 
@@ -1219,7 +1222,8 @@ static bool route_fused_on() {
 
 // The only place that reads the layer's shapes: T = 1 mix, T <= 2 (or no grouped form) self-routing slots, 3..8
 // grouped by expert, more than 8 sorted; packed experts (T <= 8) take the grouped packed kernels, in their
-// integer-dot form when the arguments carry the code-plane workspace.
+// integer-dot form when the arguments carry the code-plane workspace; FP8 experts (T <= 8) take the grouped FP8
+// kernels where the router and the shapes fit, else the fp16 forms.
 MoePlan moe_plan(const MoeDecodeArgs& a) {
     const int T = a.T, E = a.E, K = a.topk, TK = T * K;
     if (T <= 0 || TK > 512 || E > 256 || K > 8 || K > E)
@@ -1238,6 +1242,20 @@ MoePlan moe_plan(const MoeDecodeArgs& a) {
     DecGemvArgs& gr = p.router;
     gr.M = T; gr.N = E; gr.K = a.H; gr.x = mx; gr.ldx = a.H; gr.W = a.router; gr.ldw = a.H; gr.wdtype = a.router_wdt;
     gr.bias = a.router_bias; gr.y = a.logits; gr.ldy = E; gr.norm_w = mnorm; gr.eps = a.eps; gr.span = a.route_span;
+    if (a.f8Wgu.q && T <= 8) {
+        // FP8 experts: dec_route_grp on the unquantised rows (rows -> a.xn), then the grouped FP8 gate/up and down
+        MoeF8Args& f = p.f8;
+        f.T = T; f.topk = K; f.E = E; f.H = a.H; f.I = a.I; f.slots = std::min(E, TK);
+        f.x = a.norm_w ? a.xn : a.x; f.grp = a.grp; f.Wgu = a.f8Wgu; f.Wd = a.f8Wd; f.h = a.h; f.out = a.out;
+        if (a.f8sWgu.q && a.f8sWd.q && a.Is > 0) { f.Is = a.Is; f.sWgu = a.f8sWgu; f.sWd = a.f8sWd; f.hs = a.hs; }
+        f.span = a.span;
+        if (dec_route_grp_ok(T, E, a.H, K) && a.route_cnt && a.grp && a.xn && (f.Is > 0) == (m.Is > 0) && moe_f8_ok(f)) {
+            p.route = Route::DecRouteGrp;
+            p.gu = GateUp::F8;
+            p.dn = Down::F8;
+            return p;
+        }
+    }
     if (a.qWgu.q && T <= 8) {
         // packed experts: dec_route_grp (norm + router + top-k + expert records, rows -> a.xn), then the
         // grouped packed gate/up and down
@@ -1335,6 +1353,7 @@ void moe_decode_kernel_names(const MoeDecodeArgs& a, const char** gateup, const 
         case GateUp::Mm: gu = "moe_gateup_mm_kernel"; break;
         case GateUp::Q: gu = "moe_gateup_q_kernel"; break;
         case GateUp::Qdot: gu = "moe_gateup_qdot_kernel"; break;
+        case GateUp::F8: gu = "moe_gateup_f8_kernel"; break;
     }
     switch (p.dn) {
         case Down::Mix: dn = "moe_down_mix_kernel"; break;
@@ -1345,6 +1364,7 @@ void moe_decode_kernel_names(const MoeDecodeArgs& a, const char** gateup, const 
         case Down::Mm: dn = "moe_down_mm_kernel"; break;
         case Down::Q: dn = "moe_down_q_kernel"; break;
         case Down::Qdot: dn = "moe_down_qdot_kernel"; break;
+        case Down::F8: dn = "moe_down_f8_kernel"; break;
     }
     if (gateup) *gateup = gu;
     if (down) *down = dn;
@@ -1387,6 +1407,7 @@ void launch_moe_decode(const MoeDecodeArgs& a, hipStream_t s, int parts) {
         switch (p.gu) {
             case GateUp::Q: launch_moe_gateup_q(p.q, s); break;
             case GateUp::Qdot: launch_moe_gateup_qdot(p.q, s); break;
+            case GateUp::F8: launch_moe_gateup_f8(p.f8, s); break;
             case GateUp::Mix: launch_moe_gateup_mix(m, a.xn_router, s); break;
             case GateUp::Mm: launch_moe_gateup_mm(p.route == Route::InGateupMm ? p.mr : m, s); break;
             case GateUp::Grp: launch_moe_gateup_grp(m, s); break;
@@ -1400,6 +1421,7 @@ void launch_moe_decode(const MoeDecodeArgs& a, hipStream_t s, int parts) {
         switch (p.dn) {
             case Down::Q: launch_moe_down_q(p.q, s); break;
             case Down::Qdot: launch_moe_down_qdot(p.q, s); break;
+            case Down::F8: launch_moe_down_f8(p.f8, s); break;
             case Down::Mm: launch_moe_down_mm(m, s); break;
             case Down::Grp: launch_moe_down_grp(m, s); break;
             case Down::Mix: launch_moe_down_mix(m, s); break;

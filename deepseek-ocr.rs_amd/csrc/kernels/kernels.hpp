@@ -24,6 +24,13 @@ struct Q8Planes {
     int16_t* bs = nullptr;
 };
 
+// FP8 expert rows (decode_f8.hip; contract: DESIGN.md section 4.4.3): q [rows][cols] OCP E4M3 codes, e [rows] the
+// row's power-of-two exponent; the weight is 2^e[r] * e4m3(q[r][k]).  Both 16-byte aligned.
+struct F8Mat {
+    const uint8_t* q = nullptr;
+    const int8_t* e = nullptr;
+};
+
 // Profiling hook: while prof_events() holds a (start, stop) pair, the next kernel launched through
 // DSOCR_LAUNCH (the decode_*.hip units, lmhead.hip) records its own dispatch begin / end into the two events
 // (hipExtLaunchKernelGGL: the dispatch-packet timestamps rocprofv3's kernel trace reports) and the
@@ -561,6 +568,9 @@ struct MoeDecodeArgs {
     // integer-dot form of the packed launches (decode_qdot.hip): a workspace of moe_qdot_ws_bytes(T, topk, H, I, Is)
     // bytes for the activation code planes; null = the fp16-exact packed kernels
     void* q8_ws = nullptr;
+    // FP8 experts (decode_f8.hip): when f8Wgu.q is set and T <= 8 the gate/up and down launches stream these E4M3
+    // tables (layouts of Wgu / Wd / sWgu / sWd, one exponent per row) where moe_f8_ok holds; else the fp16 kernels
+    F8Mat f8Wgu, f8Wd, f8sWgu, f8sWd;
 };
 // ---- one-page decode step as ONE persistent launch (decode_persist.hip): every decoder layer inside 256 resident
 // workgroups handing their vectors over as {f32, tag} granules (tag = the decode position; the granule buffer is
@@ -945,6 +955,28 @@ void launch_dsq_rows_dot_q8(const QMat& m, long rows, long in_dim, int T, const 
 bool moe_qdot_ok(const MoeQArgs& a);
 void launch_moe_gateup_qdot(const MoeQArgs& a, hipStream_t s);
 void launch_moe_down_qdot(const MoeQArgs& a, hipStream_t s);
+
+// FP8 (E4M3) expert weights for the decode MoE (decode_f8.hip; contract: DESIGN.md section 4.4.3).
+// launch_fp8_quantize_rows: fp16 rows [rows][cols] -> codes and one exponent per row (cols % 16 == 0).
+// launch_fp8_rows_dot: y[T][rows] = x[T][cols] . W8^T (parity hook, T <= 8).  The MoE launches are MoeQArgs' in
+// grouped form behind dec_route_grp: x = the normalised rows, h carries the routing weight.
+bool fp8_rows_ok(long cols);
+void launch_fp8_quantize_rows(long rows, long cols, const void* w_f16, uint8_t* codes, int8_t* exps, hipStream_t s);
+// W8 = 2^e e4m3(code) as fp16 (exact), e.g. over the rows the codes were made from
+void launch_fp8_dequant_rows(long rows, long cols, const F8Mat& m, void* w8_f16, hipStream_t s);
+void launch_fp8_rows_dot(const F8Mat& m, long rows, long cols, int T, const float* x, float* y, hipStream_t s);
+struct MoeF8Args {
+    int T = 0, topk = 0, E = 0, H = 0, I = 0, Is = 0, slots = 0;
+    const float* x = nullptr;
+    const int* grp = nullptr;
+    F8Mat Wgu, Wd, sWgu, sWd;
+    float* h = nullptr; float* hs = nullptr;   // [T*topk][I], [T][Is]
+    float* out = nullptr;                      // [T][H], += combined
+    unsigned long long* span = nullptr;        // launch-span slots (SPAN_SLOTS pairs) or null
+};
+bool moe_f8_ok(const MoeF8Args& a);
+void launch_moe_gateup_f8(const MoeF8Args& a, hipStream_t s);
+void launch_moe_down_f8(const MoeF8Args& a, hipStream_t s);
 
 // Page preprocessing on the GPU (preprocess.hip): Pillow 22-bit bicubic (tap tables from the host),
 // then a vertical pass fused with canvas placement / tile cropping and the CHW normalisation

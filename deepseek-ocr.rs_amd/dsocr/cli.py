@@ -62,6 +62,9 @@ def add_model_args(p: argparse.ArgumentParser) -> None:
     g.add_argument("--snapshot-int8-dot", action="store_true", default=False,
                    help="as --snapshot-packed, with the activations quantised to 8-bit blocks and integer block dots "
                         "(needs --snapshot; results differ from dequant-on-load by the activation rounding)")
+    g.add_argument("--expert-fp8", action="store_true", default=None,
+                   help="keep the MoE experts as FP8 (E4M3) codes with a power-of-two row exponent for decode steps of "
+                        "1..8 tokens (dtype f16; default: the DSOCR_EXPERT_FP8 environment switch decides)")
     g.add_argument("--synthetic-seed", type=int, default=0, help="seed of the synthetic checkpoint")
 
 
@@ -375,6 +378,7 @@ def run_inference(args, out=sys.stdout, err=sys.stderr) -> int:
     t0 = time.perf_counter()
     engine = load_model(ModelLoadArgs(config_path=config, weights_path=args.weights, snapshot_path=args.snapshot,
                                       snapshot_packed=snapshot_packed_arg(args),
+                                      expert_fp8=getattr(args, "expert_fp8", None),
                                       device=device, dtype=args.dtype, synthetic_seed=args.synthetic_seed))
     load_ms = (time.perf_counter() - t0) * 1e3
     events.append(_event("model.load", load_ms, model=args.model, kind="Deepseek", device=f"hip:{device}",

@@ -18,7 +18,7 @@ from typing import Any, Callable, Optional, Sequence, Union
 
 import numpy as np
 
-from ._lib import (DTYPES, LOAD_PACKED_EXPERTS, LOAD_PACKED_INT8_DOT, MAX_TOP_LOGPROBS, DecodeParamsC, DsocrError, LoadArgs, LogitBiasC, LogprobsC,
+from ._lib import (DTYPES, LOAD_FP8_EXPERTS, LOAD_PACKED_EXPERTS, LOAD_PACKED_INT8_DOT, MAX_TOP_LOGPROBS, DecodeParamsC, DsocrError, LoadArgs, LogitBiasC, LogprobsC,
                    GuidedC, GuidedResultC, NgramWindowC, PenaltiesC, SESSION_GUIDED, RequestC, ResultC, STREAM_CB, SESSION_LOGIT_BIAS, SESSION_LOGPROBS,
                    SESSION_NGRAM_WINDOW, SESSION_PENALTIES,
                    SESSION_PER_REQUEST, SESSION_STOP,
@@ -188,6 +188,10 @@ class ModelLoadArgs:
     # True / False = dsocr_engine_load_flags; "int8" = the packed launches in integer-dot form
     # (DSOCR_LOAD_PACKED_INT8_DOT: 8-bit activation blocks, int32 block dots)
     snapshot_packed: Union[None, bool, str] = None
+    # MoE experts kept as FP8 (E4M3) codes with a power-of-two exponent per row for decode steps of 1..8 tokens
+    # (DSOCR_LOAD_FP8_EXPERTS; dtype f16, no snapshot needed, not with snapshot_packed): None = the DSOCR_EXPERT_FP8
+    # environment switch decides (when snapshot_packed is None too), True / False = dsocr_engine_load_flags
+    expert_fp8: Optional[bool] = None
     device: int = 0
     dtype: str = "f16"
     synthetic_seed: int = 0
@@ -376,13 +380,15 @@ class DeepseekOcrEngine:
                       args.snapshot_path.encode() if args.snapshot_path else None, args.device, DTYPES[args.dtype],
                       args.synthetic_seed)
         h = C.c_void_p()
-        if args.snapshot_packed is None:
+        if args.snapshot_packed is None and args.expert_fp8 is None:
             check(lib().dsocr_engine_load(C.byref(la), C.byref(h)))
         else:
             if isinstance(args.snapshot_packed, str) and args.snapshot_packed != "int8":
                 raise DsocrError(1, f"snapshot_packed takes None, True, False or 'int8', not {args.snapshot_packed!r}")
             flags = (LOAD_PACKED_EXPERTS | LOAD_PACKED_INT8_DOT if args.snapshot_packed == "int8"
                      else LOAD_PACKED_EXPERTS if args.snapshot_packed else 0)
+            if args.expert_fp8:
+                flags |= LOAD_FP8_EXPERTS
             check(lib().dsocr_engine_load_flags(C.byref(la), flags, C.byref(h)))
         self._h = h
         self.args = args
@@ -398,6 +404,12 @@ class DeepseekOcrEngine:
         pl, ml, pb = C.c_size_t(), C.c_size_t(), C.c_size_t()
         check(lib().dsocr_engine_packed_info(self._h, C.byref(pl), C.byref(ml), C.byref(pb)))
         return {"packed_layers": pl.value, "moe_layers": ml.value, "packed_bytes": pb.value}
+
+    def fp8_info(self) -> dict:
+        """MoE layers that run the FP8 decode kernels, MoE layers in all, device bytes of the FP8 tables."""
+        fl, ml, fb = C.c_size_t(), C.c_size_t(), C.c_size_t()
+        check(lib().dsocr_engine_fp8_info(self._h, C.byref(fl), C.byref(ml), C.byref(fb)))
+        return {"fp8_layers": fl.value, "moe_layers": ml.value, "fp8_bytes": fb.value}
 
     def packed_mode(self) -> int:
         """0 dequant-on-load, 1 packed experts, 2 packed experts with integer block dots."""

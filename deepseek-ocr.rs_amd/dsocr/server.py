@@ -822,6 +822,7 @@ def main(argv=None) -> int:
     config = model_config(args)  # --model deepseek-ocr | deepseek-ocr-2: the bundled config and vision defaults
     engine = load_model(ModelLoadArgs(config_path=config, weights_path=args.weights, snapshot_path=args.snapshot,
                                       snapshot_packed=snapshot_packed_arg(args),
+                                      expert_fp8=getattr(args, "expert_fp8", None),
                                       device=parse_device(args.device), dtype=args.dtype,
                                       synthetic_seed=args.synthetic_seed))
     state = ServerState(engine, load_tokenizer(args.tokenizer, _vocab_of(config)), args.model,

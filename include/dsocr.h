@@ -130,12 +130,23 @@ dsocr_status dsocr_engine_load(const dsocr_load_args* args, dsocr_engine** out);
  * the flag when args carries a snapshot and the environment has DSOCR_DSQ_INT8 set to a non-zero value. */
 #define DSOCR_LOAD_PACKED_EXPERTS 1u
 #define DSOCR_LOAD_PACKED_INT8_DOT 2u
+/* DSOCR_LOAD_FP8_EXPERTS (dtype DSOCR_F16 only; DSOCR_EINVAL with either packed flag): at load every MoE layer whose
+ * router fits the one-launch grouped router (at most 64 experts, hidden size at most 1536) and whose hidden and
+ * intermediate sizes are multiples of 16 also keeps its routed and shared expert matrices as OCP E4M3 codes with one
+ * power-of-two exponent per output row, and decode steps of 1..8 tokens stream those instead of the fp16 rows
+ * (DESIGN.md section 4.4.3).  The effective weights 2^e_r e4m3(code) are fp16 values, so the result is the fp16
+ * engine's on those weights up to summation order.  Other layers, prefill and larger batches run the fp16 kernels.
+ * Needs no snapshot.  dsocr_engine_load adds the flag when the environment has DSOCR_EXPERT_FP8 set to a non-zero
+ * value.  dsocr_engine_packed_info / dsocr_engine_packed_mode keep reporting 0 for such an engine. */
+#define DSOCR_LOAD_FP8_EXPERTS 4u
 dsocr_status dsocr_engine_load_flags(const dsocr_load_args* args, uint32_t flags, dsocr_engine** out);
 /* MoE layers that kept packed blocks, MoE layers in all, device bytes of the packed tables (any may be NULL) */
 dsocr_status dsocr_engine_packed_info(const dsocr_engine* e, size_t* packed_layers, size_t* moe_layers,
                                       size_t* packed_bytes);
 /* How the engine was loaded: 0 dequant-on-load, 1 packed experts, 2 packed experts with integer block dots */
 dsocr_status dsocr_engine_packed_mode(const dsocr_engine* e, int* mode);
+/* MoE layers that run the FP8 decode kernels, MoE layers in all, device bytes of the FP8 tables (any may be NULL) */
+dsocr_status dsocr_engine_fp8_info(const dsocr_engine* e, size_t* fp8_layers, size_t* moe_layers, size_t* fp8_bytes);
 void dsocr_engine_free(dsocr_engine* e);
 const char* dsocr_last_error(void);
 /* hidden size (image-row width), vocab, eos id, layers */
@@ -974,6 +985,19 @@ dsocr_status dsocr_k_moe_packed_q8(int T, int H, int E, int topk, int I, int Is,
                                    const void* sWd_payload, int norm_topk, float scaling, float* out, int* topk_ids_out,
                                    float* topk_w_out, int8_t* xn_codes, float* xn_d, int8_t* h_codes, float* h_d,
                                    int8_t* hs_codes, float* hs_d);
+/* Parity hooks of the FP8 experts (DSOCR_LOAD_FP8_EXPERTS; device pointers unless said otherwise; cols % 16 == 0).
+ * dsocr_k_fp8_quantize_rows: fp16 rows [rows][cols] to E4M3 codes [rows][cols] and one exponent per row (the
+ * load-time quantiser).  dsocr_k_fp8_rows_dot: y[T][rows] = x[T][cols] . W8^T, W8[r][k] = 2^exps[r] e4m3(codes[r][k]),
+ * through the decode kernels' row walk (T <= 8, T cols f32 within 64 KiB).  dsocr_k_moe_fp8: dsocr_k_moe_packed
+ * from fp16 tables (routed [E][2I][H] gate rows then up rows, [E][H][I]; shared [2Is][H], [H][Is] or NULL),
+ * quantised inside; topk_ids_out / topk_w_out are HOST pointers (NULL to skip). */
+dsocr_status dsocr_k_fp8_quantize_rows(size_t rows, size_t cols, const void* w_f16, uint8_t* codes_out, int8_t* exps_out);
+dsocr_status dsocr_k_fp8_rows_dot(size_t rows, size_t cols, const uint8_t* codes, const int8_t* exps, int T, const float* x,
+                                  float* y);
+dsocr_status dsocr_k_moe_fp8(int T, int H, int E, int topk, int I, int Is, const float* x, const float* norm_w, float eps,
+                             const void* router_f16, const void* Wgu_f16, const void* Wd_f16, const void* sWgu_f16,
+                             const void* sWd_f16, int norm_topk, float scaling, float* out, int* topk_ids_out,
+                             float* topk_w_out);
 /* Kernel names launch_moe_decode picks for a decode MoE of T tokens (static strings), e.g. the bench's
  * roofline label: "moe_gateup_mix_kernel" at T = 1, "moe_gateup_grp_kernel" at T = 3..8. */
 dsocr_status dsocr_k_moe_kernels(int T, int H, int E, int topk, int I, int Is, int has_norm, const char** gateup,
