@@ -403,8 +403,17 @@ dsocr_status dsocr_engine_load(const dsocr_load_args* args, dsocr_engine** out) 
     const bool int8 = i8 && atoi(i8) != 0 && args && args->snapshot_path;
     const char* f8 = getenv("DSOCR_EXPERT_FP8");
     const bool fp8 = f8 && atoi(f8) != 0;
+    const char* f8m = getenv("DSOCR_EXPERT_FP8_MM");
+    const bool fp8mm = f8m && atoi(f8m) != 0;
     return dsocr_engine_load_flags(args, (packed ? DSOCR_LOAD_PACKED_EXPERTS : 0u) | (int8 ? DSOCR_LOAD_PACKED_INT8_DOT : 0u) |
-                                             (fp8 ? DSOCR_LOAD_FP8_EXPERTS : 0u), out);
+                                             (fp8 ? DSOCR_LOAD_FP8_EXPERTS : 0u) | (fp8mm ? DSOCR_LOAD_FP8_EXPERTS_MM : 0u), out);
+}
+
+dsocr_status dsocr_engine_fp8_mode(const dsocr_engine* e, int* mode) {
+    return guarded([&] {
+        if (!e || !mode) throw std::runtime_error("EINVAL: NULL argument");
+        *mode = e->impl->fp8_mode();
+    });
 }
 
 dsocr_status dsocr_engine_fp8_info(const dsocr_engine* e, size_t* fp8_layers, size_t* moe_layers, size_t* fp8_bytes) {
@@ -2235,9 +2244,11 @@ dsocr_status dsocr_k_fp8_rows_dot(size_t rows, size_t cols, const uint8_t* codes
         check_hip(hipDeviceSynchronize(), "fp8_rows_dot");
     });
 }
-dsocr_status dsocr_k_moe_fp8(int T, int H, int E, int topk, int I, int Is, const float* x, const float* norm_w, float eps,
-                             const void* router_f16, const void* Wgu_f16, const void* Wd_f16, const void* sWgu_f16,
-                             const void* sWd_f16, int norm_topk, float scaling, float* out, int* ids_out, float* w_out) {
+// dsocr_k_moe_fp8 (mm = false) / dsocr_k_moe_fp8_mm (mm = true: tile-ordered copies, a down workspace, and the
+// matrix-core form forced at every T)
+static dsocr_status k_moe_fp8(bool mm, int T, int H, int E, int topk, int I, int Is, const float* x, const float* norm_w, float eps,
+                              const void* router_f16, const void* Wgu_f16, const void* Wd_f16, const void* sWgu_f16,
+                              const void* sWd_f16, int norm_topk, float scaling, float* out, int* ids_out, float* w_out) {
     return guarded([&] {
         if (T <= 0 || T > 8 || H <= 0 || E <= 0 || topk <= 0 || I <= 0 || Is < 0) throw std::runtime_error("EINVAL: bad MoE shape");
         if (!x || !router_f16 || !Wgu_f16 || !Wd_f16 || !out) throw std::runtime_error("EINVAL: NULL argument");
@@ -2259,6 +2270,11 @@ dsocr_status dsocr_k_moe_fp8(int T, int H, int E, int topk, int I, int Is, const
                 int8_t* e = (int8_t*)alloc((size_t)rows);
                 dsocr::launch_fp8_quantize_rows(rows, cols, w, q, e, nullptr);
                 m.q = q; m.e = e;
+                if (mm && dsocr::fp8_tile_ok(cols) && rows % 16 == 0) {
+                    uint8_t* t = (uint8_t*)alloc(dsocr::fp8_tile_bytes(rows, cols));
+                    dsocr::launch_fp8_tile_order(rows, cols, q, t, nullptr);
+                    m.t = t;
+                }
                 return m;
             };
             dsocr::MoeDecodeArgs a;
@@ -2284,9 +2300,16 @@ dsocr_status dsocr_k_moe_fp8(int T, int H, int E, int topk, int I, int Is, const
             a.grp = (int*)alloc(sizeof(int) * dsocr::moe_grp_ints(E, T, topk));
             a.route_cnt = (int*)alloc(sizeof(int) * 16);
             check_hip(hipMemset(a.route_cnt, 0, sizeof(int) * 16), "hipMemset");
+            if (mm) {
+                a.f8mm_any_T = true;
+                a.dn_part = (float*)alloc(sizeof(float) * dsocr::moe_down_mm_part_floats(E, T, topk, I, a.Is, H));
+                a.dn_tick = (int*)alloc(sizeof(int) * ((size_t)H / 64 + 1));
+                check_hip(hipMemset(a.dn_tick, 0, sizeof(int) * ((size_t)H / 64 + 1)), "hipMemset");
+            }
             const char* gu = nullptr;
             dsocr::moe_decode_kernel_names(a, &gu, nullptr);
-            if (std::string(gu) != "moe_gateup_f8_kernel") throw std::runtime_error("EINVAL: FP8 decode MoE outside its range");
+            if (std::string(gu) != (mm ? "moe_gateup_f8mm_kernel" : "moe_gateup_f8_kernel"))
+                throw std::runtime_error("EINVAL: FP8 decode MoE outside its range");
             dsocr::launch_moe_decode(a, nullptr);
             check_hip(hipGetLastError(), "moe launch");
             check_hip(hipDeviceSynchronize(), "moe");
@@ -2297,6 +2320,44 @@ dsocr_status dsocr_k_moe_fp8(int T, int H, int E, int topk, int I, int Is, const
             throw;
         }
         for (void* p : bufs) (void)hipFree(p);
+    });
+}
+dsocr_status dsocr_k_moe_fp8(int T, int H, int E, int topk, int I, int Is, const float* x, const float* norm_w, float eps,
+                             const void* router_f16, const void* Wgu_f16, const void* Wd_f16, const void* sWgu_f16,
+                             const void* sWd_f16, int norm_topk, float scaling, float* out, int* ids_out, float* w_out) {
+    return k_moe_fp8(false, T, H, E, topk, I, Is, x, norm_w, eps, router_f16, Wgu_f16, Wd_f16, sWgu_f16, sWd_f16, norm_topk, scaling,
+                     out, ids_out, w_out);
+}
+dsocr_status dsocr_k_moe_fp8_mm(int T, int H, int E, int topk, int I, int Is, const float* x, const float* norm_w, float eps,
+                                const void* router_f16, const void* Wgu_f16, const void* Wd_f16, const void* sWgu_f16,
+                                const void* sWd_f16, int norm_topk, float scaling, float* out, int* ids_out, float* w_out) {
+    return k_moe_fp8(true, T, H, E, topk, I, Is, x, norm_w, eps, router_f16, Wgu_f16, Wd_f16, sWgu_f16, sWd_f16, norm_topk, scaling,
+                     out, ids_out, w_out);
+}
+// ---- FP8 experts on the matrix cores (decode_f8mm.hip)
+dsocr_status dsocr_k_fp8_tile_order(size_t rows, size_t cols, const uint8_t* codes, uint8_t* out) {
+    return guarded([&] {
+        dsocr::launch_fp8_tile_order((long)rows, (long)cols, codes, out, nullptr);
+        check_hip(hipGetLastError(), "fp8_tile_order launch");
+        check_hip(hipDeviceSynchronize(), "fp8_tile_order");
+    });
+}
+dsocr_status dsocr_k_fp8_mm_rows_dot(size_t rows, size_t cols, const uint8_t* codes, const int8_t* exps, int T, const float* x,
+                                     float* y) {
+    return guarded([&] {
+        if (!rows || !dsocr::fp8_tile_ok((long)cols) || !codes) throw std::runtime_error("EINVAL: fp8_mm_rows_dot takes rows of a multiple of 64 codes");
+        void* t = nullptr;  // the tile-ordered copy, a ragged last row tile padded with zero codes
+        check_hip(hipMalloc(&t, dsocr::fp8_tile_bytes((long)rows, (long)cols)), "hipMalloc");
+        try {
+            dsocr::launch_fp8_tile_order((long)rows, (long)cols, codes, (uint8_t*)t, nullptr);
+            dsocr::launch_fp8_mm_rows_dot((const uint8_t*)t, exps, (long)rows, (long)cols, T, x, y, nullptr);
+            check_hip(hipGetLastError(), "fp8_mm_rows_dot launch");
+            check_hip(hipDeviceSynchronize(), "fp8_mm_rows_dot");
+        } catch (...) {
+            (void)hipFree(t);
+            throw;
+        }
+        (void)hipFree(t);
     });
 }
 dsocr_status dsocr_k_dsq_rows_dot(int qtype, size_t rows, size_t in_dim, const void* payload, int T, const float* x,

@@ -246,7 +246,9 @@ void* Engine::ws(const std::string& name0, size_t bytes) {
 Engine::Engine(const std::string& config_path, const std::string& weights_path, int device, int dtype, uint64_t seed,
                const std::string& snapshot_path, uint32_t load_flags)
     : device_(device), dtype_(dtype) {
-    if (load_flags & ~7u) throw std::runtime_error("EINVAL: unknown load flags");
+    if (load_flags & ~15u) throw std::runtime_error("EINVAL: unknown load flags");
+    if (load_flags & 8u) load_flags |= 4u;  // the matrix-core form runs on the FP8 tables
+    fp8_mm_ = (load_flags & 8u) != 0;
     if ((load_flags & 4u) && (load_flags & 3u))
         throw std::runtime_error("EINVAL: FP8 experts cannot be combined with packed snapshot experts");
     if ((load_flags & 4u) && dtype != 1) throw std::runtime_error("EINVAL: FP8 experts quantise the fp16 engine's weights: use dtype f16");
@@ -807,6 +809,22 @@ void Engine::load_weights(const std::string& path, uint64_t seed, const std::str
                 if (d.has_shared) {
                     quantise(d.s_gu.W, 2L * Is8, H, d.f8_sgu);
                     quantise(d.s_d.W, H, Is8, d.f8_sd);
+                }
+                // DSOCR_LOAD_FP8_EXPERTS_MM: the tile-ordered copies the matrix-core form streams at 3..8 tokens
+                // (decode_f8mm.hip), for the layers whose widths are whole 64-code steps
+                if (fp8_mm_ && H % 64 == 0 && I % 64 == 0 && Is8 % 64 == 0 && H <= 1536 && I <= 1024) {
+                    auto tile_order = [&](long rows, long cols, F8Mat& m) {
+                        uint8_t* t = (uint8_t*)dev_alloc(fp8_tile_bytes(rows, cols));
+                        launch_fp8_tile_order(rows, cols, m.q, t, stream_);
+                        m.t = t;
+                        d.fp8_bytes += fp8_tile_bytes(rows, cols);
+                    };
+                    tile_order((long)E * 2 * I, H, d.f8_gu);
+                    tile_order((long)E * H, I, d.f8_d);
+                    if (d.has_shared) {
+                        tile_order(2L * Is8, H, d.f8_sgu);
+                        tile_order(H, Is8, d.f8_sd);
+                    }
                 }
                 HIP_CHECK(hipStreamSynchronize(stream_));
                 d.fp8 = true;
@@ -3874,7 +3892,7 @@ Engine::DecodeProfile Engine::profile_decode(int iters) {
                 prof.moe_down.bytes += 2.0 * (planes(TK, I) + planes(B, Is));
             }
         }
-        if (std::string(prof.gateup_kernel) == "moe_gateup_f8_kernel") {
+        if (std::string(prof.gateup_kernel) == "moe_gateup_f8_kernel" || std::string(prof.gateup_kernel) == "moe_gateup_f8mm_kernel") {
             // FP8 layers stream one byte per weight and one exponent byte per row
             prof.moe_gateup.bytes = (touched * 2.0 * I + 2.0 * Is) * (H + 1.0)
                                     + (double)B * H * 4 + (double)(TK * I + B * Is) * 4;

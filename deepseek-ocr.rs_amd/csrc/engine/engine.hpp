@@ -328,6 +328,8 @@ class Engine {
     int packed_mode() const { return packed_mode_; }
     // MoE layers that run the FP8 decode kernels / all MoE layers / device bytes of the FP8 tables
     void fp8_info(size_t* fp8_layers, size_t* moe_layers, size_t* fp8_bytes) const;
+    // 0 fp16 experts, 1 FP8 experts, 2 FP8 experts with the matrix-core form at 3..8 tokens
+    int fp8_mode() const { return fp8_mm_ ? 2 : fp8_experts_ ? 1 : 0; }
 
     const ModelConfig& cfg() const { return cfg_; }
     int variant() const { return cfg_.variant; }
@@ -482,6 +484,7 @@ class Engine {
     void load_weights(const std::string& path, uint64_t seed, const std::string& snapshot_path, bool packed_experts);
     int packed_mode_ = 0;
     bool fp8_experts_ = false;
+    bool fp8_mm_ = false;  // DSOCR_LOAD_FP8_EXPERTS_MM
     // ---- workspace
     void* ws(const std::string& name, size_t bytes);
     float* wsf(const std::string& name, size_t n) { return (float*)ws(name, n * sizeof(float)); }

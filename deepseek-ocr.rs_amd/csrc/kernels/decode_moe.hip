@@ -838,6 +838,7 @@ enum class GateUp {
     Q,           // moe_gateup_q_kernel (decode_q.hip)
     Qdot,        // q8_quantize_kernel over xn, then moe_gateup_qdot_kernel (decode_qdot.hip)
     F8,          // moe_gateup_f8_kernel (decode_f8.hip)
+    F8mm,        // moe_gateup_f8mm_kernel (decode_f8mm.hip)
 };
 enum class Down {
     Mix,          // moe_down_mix_kernel (T = 1)
@@ -849,6 +850,7 @@ enum class Down {
     Q,            // moe_down_q_kernel (decode_q.hip)
     Qdot,         // q8_quantize_kernel over h and hs, then moe_down_qdot_kernel (decode_qdot.hip)
     F8,           // moe_down_f8_kernel (decode_f8.hip)
+    F8mm,         // moe_down_f8mm_kernel (decode_f8mm.hip)
 };
 
 // The forms behind launch_moe_gateup2 / launch_moe_down2, read off the launch's own arguments (the two are entry
@@ -1223,7 +1225,8 @@ static bool route_fused_on() {
 // The only place that reads the layer's shapes: T = 1 mix, T <= 2 (or no grouped form) self-routing slots, 3..8
 // grouped by expert, more than 8 sorted; packed experts (T <= 8) take the grouped packed kernels, in their
 // integer-dot form when the arguments carry the code-plane workspace; FP8 experts (T <= 8) take the grouped FP8
-// kernels where the router and the shapes fit, else the fp16 forms.
+// kernels where the router and the shapes fit (at 3..8 tokens their matrix-core form when the tables carry the
+// tile-ordered copies and moe_f8mm_ok holds), else the fp16 forms.
 MoePlan moe_plan(const MoeDecodeArgs& a) {
     const int T = a.T, E = a.E, K = a.topk, TK = T * K;
     if (T <= 0 || TK > 512 || E > 256 || K > 8 || K > E)
@@ -1253,6 +1256,12 @@ MoePlan moe_plan(const MoeDecodeArgs& a) {
             p.route = Route::DecRouteGrp;
             p.gu = GateUp::F8;
             p.dn = Down::F8;
+            // 3..8 tokens from the tile-ordered copies: the matrix-core form (T = 1, 2 keep the VALU form)
+            f.dn_part = a.dn_part; f.dn_tick = a.dn_tick;
+            if ((T >= 3 || a.f8mm_any_T) && moe_f8mm_ok(f)) {
+                p.gu = GateUp::F8mm;
+                p.dn = Down::F8mm;
+            }
             return p;
         }
     }
@@ -1354,6 +1363,7 @@ void moe_decode_kernel_names(const MoeDecodeArgs& a, const char** gateup, const 
         case GateUp::Q: gu = "moe_gateup_q_kernel"; break;
         case GateUp::Qdot: gu = "moe_gateup_qdot_kernel"; break;
         case GateUp::F8: gu = "moe_gateup_f8_kernel"; break;
+        case GateUp::F8mm: gu = "moe_gateup_f8mm_kernel"; break;
     }
     switch (p.dn) {
         case Down::Mix: dn = "moe_down_mix_kernel"; break;
@@ -1365,6 +1375,7 @@ void moe_decode_kernel_names(const MoeDecodeArgs& a, const char** gateup, const 
         case Down::Q: dn = "moe_down_q_kernel"; break;
         case Down::Qdot: dn = "moe_down_qdot_kernel"; break;
         case Down::F8: dn = "moe_down_f8_kernel"; break;
+        case Down::F8mm: dn = "moe_down_f8mm_kernel"; break;
     }
     if (gateup) *gateup = gu;
     if (down) *down = dn;
@@ -1408,6 +1419,7 @@ void launch_moe_decode(const MoeDecodeArgs& a, hipStream_t s, int parts) {
             case GateUp::Q: launch_moe_gateup_q(p.q, s); break;
             case GateUp::Qdot: launch_moe_gateup_qdot(p.q, s); break;
             case GateUp::F8: launch_moe_gateup_f8(p.f8, s); break;
+            case GateUp::F8mm: launch_moe_gateup_f8mm(p.f8, s); break;
             case GateUp::Mix: launch_moe_gateup_mix(m, a.xn_router, s); break;
             case GateUp::Mm: launch_moe_gateup_mm(p.route == Route::InGateupMm ? p.mr : m, s); break;
             case GateUp::Grp: launch_moe_gateup_grp(m, s); break;
@@ -1422,6 +1434,7 @@ void launch_moe_decode(const MoeDecodeArgs& a, hipStream_t s, int parts) {
             case Down::Q: launch_moe_down_q(p.q, s); break;
             case Down::Qdot: launch_moe_down_qdot(p.q, s); break;
             case Down::F8: launch_moe_down_f8(p.f8, s); break;
+            case Down::F8mm: launch_moe_down_f8mm(p.f8, s); break;
             case Down::Mm: launch_moe_down_mm(m, s); break;
             case Down::Grp: launch_moe_down_grp(m, s); break;
             case Down::Mix: launch_moe_down_mix(m, s); break;

@@ -29,6 +29,9 @@ struct Q8Planes {
 struct F8Mat {
     const uint8_t* q = nullptr;
     const int8_t* e = nullptr;
+    // tile-ordered copy of q for the matrix-core form (decode_f8mm.hip) or null:
+    // [rows / 16][cols / 64][64 lanes][16 B], rows % 16 == 0, cols % 64 == 0
+    const uint8_t* t = nullptr;
 };
 
 // Profiling hook: while prof_events() holds a (start, stop) pair, the next kernel launched through
@@ -571,6 +574,10 @@ struct MoeDecodeArgs {
     // FP8 experts (decode_f8.hip): when f8Wgu.q is set and T <= 8 the gate/up and down launches stream these E4M3
     // tables (layouts of Wgu / Wd / sWgu / sWd, one exponent per row) where moe_f8_ok holds; else the fp16 kernels
     F8Mat f8Wgu, f8Wd, f8sWgu, f8sWd;
+    // matrix-core form of the FP8 launches (decode_f8mm.hip): taken at 3 <= T <= 8 (f8mm_any_T: at every T <= 8, the
+    // parity hook) when the four tables carry their tile-ordered copies and moe_f8mm_ok holds; its down launch meets
+    // through dn_part / dn_tick above when both are set
+    bool f8mm_any_T = false;
 };
 // ---- one-page decode step as ONE persistent launch (decode_persist.hip): every decoder layer inside 256 resident
 // workgroups handing their vectors over as {f32, tag} granules (tag = the decode position; the granule buffer is
@@ -973,10 +980,27 @@ struct MoeF8Args {
     float* h = nullptr; float* hs = nullptr;   // [T*topk][I], [T][Is]
     float* out = nullptr;                      // [T][H], += combined
     unsigned long long* span = nullptr;        // launch-span slots (SPAN_SLOTS pairs) or null
+    // matrix-core down (decode_f8mm.hip): group partials [groups][8][H] (at least min(E, T topk) groups) and one
+    // ticket per 64-row tile, zero between launches; null = one group per row tile, no workspace
+    float* dn_part = nullptr; int* dn_tick = nullptr;
 };
 bool moe_f8_ok(const MoeF8Args& a);
 void launch_moe_gateup_f8(const MoeF8Args& a, hipStream_t s);
 void launch_moe_down_f8(const MoeF8Args& a, hipStream_t s);
+
+// The FP8 experts on the matrix cores (decode_f8mm.hip): the launches above from the
+// tile-ordered copies (F8Mat::t), the codes widened to f16 into v_mfma_f32_16x16x32_f16 against the token rows as
+// three f16 planes.  moe_f8mm_ok: moe_f8_ok, H / I / Is multiples of 64, H <= 1536, I <= 1024, every table with its copy.
+bool fp8_tile_ok(long cols);
+size_t fp8_tile_bytes(long rows, long cols);  // the copy's bytes: rows rounded up to whole 16-row tiles
+void launch_fp8_tile_order(long rows, long cols, const uint8_t* codes, uint8_t* out, hipStream_t s);
+// y[T][rows] = x[T][cols] . W8^T from a tile-ordered copy (parity hook, T <= 8, cols <= 1536)
+void launch_fp8_mm_rows_dot(const uint8_t* tiles, const int8_t* exps, long rows, long cols, int T, const float* x, float* y,
+                            hipStream_t s);
+bool moe_f8mm_ok(const MoeF8Args& a);
+int moe_down_f8mm_groups(const MoeF8Args& a);
+void launch_moe_gateup_f8mm(const MoeF8Args& a, hipStream_t s);
+void launch_moe_down_f8mm(const MoeF8Args& a, hipStream_t s);
 
 // Page preprocessing on the GPU (preprocess.hip): Pillow 22-bit bicubic (tap tables from the host),
 // then a vertical pass fused with canvas placement / tile cropping and the CHW normalisation

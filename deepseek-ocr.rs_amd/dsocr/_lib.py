@@ -162,6 +162,7 @@ class DotsTimingsC(C.Structure):
 LOAD_PACKED_EXPERTS = 1  # DSOCR_LOAD_PACKED_EXPERTS
 LOAD_PACKED_INT8_DOT = 2  # DSOCR_LOAD_PACKED_INT8_DOT (implies LOAD_PACKED_EXPERTS)
 LOAD_FP8_EXPERTS = 4  # DSOCR_LOAD_FP8_EXPERTS
+LOAD_FP8_EXPERTS_MM = 8  # DSOCR_LOAD_FP8_EXPERTS_MM (implies LOAD_FP8_EXPERTS)
 STREAM_CB = C.CFUNCTYPE(None, C.c_size_t, C.POINTER(C.c_int64), C.c_void_p)
 
 # every symbol include/dsocr.h declares (tests check the library exports all of them)
@@ -180,6 +181,7 @@ EXPORTS = [
     "dsocr_resize_catmull_rom",
     "dsocr_engine_load_flags", "dsocr_engine_packed_info", "dsocr_k_moe_packed", "dsocr_k_dsq_rows_dot",
     "dsocr_engine_fp8_info", "dsocr_k_fp8_quantize_rows", "dsocr_k_fp8_rows_dot", "dsocr_k_moe_fp8",
+    "dsocr_engine_fp8_mode", "dsocr_k_fp8_tile_order", "dsocr_k_fp8_mm_rows_dot", "dsocr_k_moe_fp8_mm",
     "dsocr_engine_packed_mode", "dsocr_k_q8_quantize", "dsocr_k_dsq_rows_dot_q8", "dsocr_k_moe_packed_q8",
     "dsocr_k_moe_ex", "dsocr_k_moe_route_kind", "dsocr_k_moe_prefill_route", "dsocr_k_moe_combine",
     "dsocr_k_gemm_bf16", "dsocr_k_dots_op",
@@ -328,6 +330,10 @@ def lib():
     L.dsocr_k_fp8_quantize_rows.argtypes = [sz, sz, vp, vp, vp]
     L.dsocr_k_fp8_rows_dot.argtypes = [sz, sz, vp, vp, i32, vp, vp]
     L.dsocr_k_moe_fp8.argtypes = [i32, i32, i32, i32, i32, i32, vp, vp, f32, vp, vp, vp, vp, vp, i32, f32, vp, vp, vp]
+    L.dsocr_engine_fp8_mode.argtypes = [vp, C.POINTER(i32)]
+    L.dsocr_k_fp8_tile_order.argtypes = [sz, sz, vp, vp]
+    L.dsocr_k_fp8_mm_rows_dot.argtypes = L.dsocr_k_fp8_rows_dot.argtypes
+    L.dsocr_k_moe_fp8_mm.argtypes = L.dsocr_k_moe_fp8.argtypes
     L.dsocr_k_moe.argtypes = [i32, i32, i32, i32, i32, i32, vp, vp, f32, vp, vp, vp, vp, vp, i32, i32, f32, vp, vp, vp]
     L.dsocr_k_moe_ex.argtypes = L.dsocr_k_moe.argtypes + [i32, vp, vp]
     L.dsocr_k_moe_route_kind.argtypes = [i32, i32, i32, i32, i32, i32, i32, C.POINTER(C.c_char_p)]

@@ -36,6 +36,11 @@ def snapshot_packed_arg(args):
     return "int8" if getattr(args, "snapshot_int8_dot", False) else getattr(args, "snapshot_packed", None)
 
 
+def expert_fp8_arg(args):
+    """ModelLoadArgs.expert_fp8 from --expert-fp8 / --expert-fp8-mm."""
+    return "mm" if getattr(args, "expert_fp8_mm", False) else getattr(args, "expert_fp8", None)
+
+
 def _bool(v: str) -> bool:
     s = v.strip().lower()
     if s in ("1", "true", "yes", "on"):
@@ -65,6 +70,8 @@ def add_model_args(p: argparse.ArgumentParser) -> None:
     g.add_argument("--expert-fp8", action="store_true", default=None,
                    help="keep the MoE experts as FP8 (E4M3) codes with a power-of-two row exponent for decode steps of "
                         "1..8 tokens (dtype f16; default: the DSOCR_EXPERT_FP8 environment switch decides)")
+    g.add_argument("--expert-fp8-mm", action="store_true", default=False,
+                   help="as --expert-fp8, with decode steps of 3..8 tokens running the FP8 codes on the matrix cores")
     g.add_argument("--synthetic-seed", type=int, default=0, help="seed of the synthetic checkpoint")
 
 
@@ -378,7 +385,7 @@ def run_inference(args, out=sys.stdout, err=sys.stderr) -> int:
     t0 = time.perf_counter()
     engine = load_model(ModelLoadArgs(config_path=config, weights_path=args.weights, snapshot_path=args.snapshot,
                                       snapshot_packed=snapshot_packed_arg(args),
-                                      expert_fp8=getattr(args, "expert_fp8", None),
+                                      expert_fp8=expert_fp8_arg(args),
                                       device=device, dtype=args.dtype, synthetic_seed=args.synthetic_seed))
     load_ms = (time.perf_counter() - t0) * 1e3
     events.append(_event("model.load", load_ms, model=args.model, kind="Deepseek", device=f"hip:{device}",

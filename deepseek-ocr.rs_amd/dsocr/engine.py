@@ -18,7 +18,7 @@ from typing import Any, Callable, Optional, Sequence, Union
 
 import numpy as np
 
-from ._lib import (DTYPES, LOAD_FP8_EXPERTS, LOAD_PACKED_EXPERTS, LOAD_PACKED_INT8_DOT, MAX_TOP_LOGPROBS, DecodeParamsC, DsocrError, LoadArgs, LogitBiasC, LogprobsC,
+from ._lib import (DTYPES, LOAD_FP8_EXPERTS, LOAD_FP8_EXPERTS_MM, LOAD_PACKED_EXPERTS, LOAD_PACKED_INT8_DOT, MAX_TOP_LOGPROBS, DecodeParamsC, DsocrError, LoadArgs, LogitBiasC, LogprobsC,
                    GuidedC, GuidedResultC, NgramWindowC, PenaltiesC, SESSION_GUIDED, RequestC, ResultC, STREAM_CB, SESSION_LOGIT_BIAS, SESSION_LOGPROBS,
                    SESSION_NGRAM_WINDOW, SESSION_PENALTIES,
                    SESSION_PER_REQUEST, SESSION_STOP,
@@ -191,7 +191,8 @@ class ModelLoadArgs:
     # MoE experts kept as FP8 (E4M3) codes with a power-of-two exponent per row for decode steps of 1..8 tokens
     # (DSOCR_LOAD_FP8_EXPERTS; dtype f16, no snapshot needed, not with snapshot_packed): None = the DSOCR_EXPERT_FP8
     # environment switch decides (when snapshot_packed is None too), True / False = dsocr_engine_load_flags
-    expert_fp8: Optional[bool] = None
+    # "mm" = DSOCR_LOAD_FP8_EXPERTS_MM: as True, and decode steps of 3..8 tokens run the codes on the matrix cores
+    expert_fp8: Union[None, bool, str] = None
     device: int = 0
     dtype: str = "f16"
     synthetic_seed: int = 0
@@ -387,8 +388,10 @@ class DeepseekOcrEngine:
                 raise DsocrError(1, f"snapshot_packed takes None, True, False or 'int8', not {args.snapshot_packed!r}")
             flags = (LOAD_PACKED_EXPERTS | LOAD_PACKED_INT8_DOT if args.snapshot_packed == "int8"
                      else LOAD_PACKED_EXPERTS if args.snapshot_packed else 0)
+            if isinstance(args.expert_fp8, str) and args.expert_fp8 != "mm":
+                raise DsocrError(1, f"expert_fp8 takes None, True, False or 'mm', not {args.expert_fp8!r}")
             if args.expert_fp8:
-                flags |= LOAD_FP8_EXPERTS
+                flags |= LOAD_FP8_EXPERTS | LOAD_FP8_EXPERTS_MM if args.expert_fp8 == "mm" else LOAD_FP8_EXPERTS
             check(lib().dsocr_engine_load_flags(C.byref(la), flags, C.byref(h)))
         self._h = h
         self.args = args
@@ -410,6 +413,12 @@ class DeepseekOcrEngine:
         fl, ml, fb = C.c_size_t(), C.c_size_t(), C.c_size_t()
         check(lib().dsocr_engine_fp8_info(self._h, C.byref(fl), C.byref(ml), C.byref(fb)))
         return {"fp8_layers": fl.value, "moe_layers": ml.value, "fp8_bytes": fb.value}
+
+    def fp8_mode(self) -> int:
+        """0 fp16 experts, 1 FP8 experts, 2 FP8 experts with the matrix-core form at 3..8 tokens."""
+        m = C.c_int()
+        check(lib().dsocr_engine_fp8_mode(self._h, C.byref(m)))
+        return m.value
 
     def packed_mode(self) -> int:
         """0 dequant-on-load, 1 packed experts, 2 packed experts with integer block dots."""

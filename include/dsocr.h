@@ -139,6 +139,14 @@ dsocr_status dsocr_engine_load(const dsocr_load_args* args, dsocr_engine** out);
  * Needs no snapshot.  dsocr_engine_load adds the flag when the environment has DSOCR_EXPERT_FP8 set to a non-zero
  * value.  dsocr_engine_packed_info / dsocr_engine_packed_mode keep reporting 0 for such an engine. */
 #define DSOCR_LOAD_FP8_EXPERTS 4u
+/* DSOCR_LOAD_FP8_EXPERTS_MM (implies DSOCR_LOAD_FP8_EXPERTS; the same DSOCR_EINVAL cases): an FP8 layer whose hidden
+ * and intermediate sizes are multiples of 64 (hidden at most 1536, routed intermediate at most 1024) also keeps a
+ * tile-ordered copy of its codes, and decode steps of 3..8 tokens run the FP8 experts on the matrix cores from it (the
+ * codes widened to f16 into v_mfma_f32_16x16x32_f16 against the token rows as three f16 planes: DESIGN.md section
+ * 4.4.4).  Same weights, same contract; the result differs from DSOCR_LOAD_FP8_EXPERTS in summation order only.  Steps
+ * of 1 or 2 tokens and layers that do not fit keep the kernels of DSOCR_LOAD_FP8_EXPERTS.  dsocr_engine_load adds the
+ * flag when the environment has DSOCR_EXPERT_FP8_MM set to a non-zero value. */
+#define DSOCR_LOAD_FP8_EXPERTS_MM 8u
 dsocr_status dsocr_engine_load_flags(const dsocr_load_args* args, uint32_t flags, dsocr_engine** out);
 /* MoE layers that kept packed blocks, MoE layers in all, device bytes of the packed tables (any may be NULL) */
 dsocr_status dsocr_engine_packed_info(const dsocr_engine* e, size_t* packed_layers, size_t* moe_layers,
@@ -147,6 +155,8 @@ dsocr_status dsocr_engine_packed_info(const dsocr_engine* e, size_t* packed_laye
 dsocr_status dsocr_engine_packed_mode(const dsocr_engine* e, int* mode);
 /* MoE layers that run the FP8 decode kernels, MoE layers in all, device bytes of the FP8 tables (any may be NULL) */
 dsocr_status dsocr_engine_fp8_info(const dsocr_engine* e, size_t* fp8_layers, size_t* moe_layers, size_t* fp8_bytes);
+/* How the engine was loaded: 0 fp16 experts, 1 FP8 experts, 2 FP8 experts with the matrix-core form at 3..8 tokens */
+dsocr_status dsocr_engine_fp8_mode(const dsocr_engine* e, int* mode);
 void dsocr_engine_free(dsocr_engine* e);
 const char* dsocr_last_error(void);
 /* hidden size (image-row width), vocab, eos id, layers */
@@ -998,6 +1008,19 @@ dsocr_status dsocr_k_moe_fp8(int T, int H, int E, int topk, int I, int Is, const
                              const void* router_f16, const void* Wgu_f16, const void* Wd_f16, const void* sWgu_f16,
                              const void* sWd_f16, int norm_topk, float scaling, float* out, int* topk_ids_out,
                              float* topk_w_out);
+/* Parity hooks of the FP8 experts' matrix-core form (DSOCR_LOAD_FP8_EXPERTS_MM; device pointers; cols % 64 == 0).
+ * dsocr_k_fp8_tile_order: codes [rows][cols] to the tile-ordered copy [ceil(rows / 16)][cols / 64][64 lanes][16 B]
+ * (lane (r, g) of block (n, s): row 16n + r, codes 64s + 8g .. +7 then 64s + 32 + 8g .. +7; rows past the end are zero
+ * codes).  dsocr_k_fp8_mm_rows_dot: dsocr_k_fp8_rows_dot through that copy (made inside), the f16 converts, the
+ * three-plane staging and the epilogue scales of the MoE launches (cols <= 1536).  dsocr_k_moe_fp8_mm: dsocr_k_moe_fp8
+ * with the matrix-core launches at every T in 1..8; DSOCR_EINVAL when the shapes do not fit them. */
+dsocr_status dsocr_k_fp8_tile_order(size_t rows, size_t cols, const uint8_t* codes, uint8_t* out);
+dsocr_status dsocr_k_fp8_mm_rows_dot(size_t rows, size_t cols, const uint8_t* codes, const int8_t* exps, int T, const float* x,
+                                     float* y);
+dsocr_status dsocr_k_moe_fp8_mm(int T, int H, int E, int topk, int I, int Is, const float* x, const float* norm_w, float eps,
+                                const void* router_f16, const void* Wgu_f16, const void* Wd_f16, const void* sWgu_f16,
+                                const void* sWd_f16, int norm_topk, float scaling, float* out, int* topk_ids_out,
+                                float* topk_w_out);
 /* Kernel names launch_moe_decode picks for a decode MoE of T tokens (static strings), e.g. the bench's
  * roofline label: "moe_gateup_mix_kernel" at T = 1, "moe_gateup_grp_kernel" at T = 3..8. */
 dsocr_status dsocr_k_moe_kernels(int T, int H, int E, int topk, int I, int Is, int has_norm, const char** gateup,
