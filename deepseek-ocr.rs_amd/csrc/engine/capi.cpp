@@ -405,14 +405,24 @@ dsocr_status dsocr_engine_load(const dsocr_load_args* args, dsocr_engine** out) 
     const bool fp8 = f8 && atoi(f8) != 0;
     const char* f8m = getenv("DSOCR_EXPERT_FP8_MM");
     const bool fp8mm = f8m && atoi(f8m) != 0;
+    const char* k16 = getenv("DSOCR_KV_F16");
+    const bool kv16 = k16 && atoi(k16) != 0;
     return dsocr_engine_load_flags(args, (packed ? DSOCR_LOAD_PACKED_EXPERTS : 0u) | (int8 ? DSOCR_LOAD_PACKED_INT8_DOT : 0u) |
-                                             (fp8 ? DSOCR_LOAD_FP8_EXPERTS : 0u) | (fp8mm ? DSOCR_LOAD_FP8_EXPERTS_MM : 0u), out);
+                                             (fp8 ? DSOCR_LOAD_FP8_EXPERTS : 0u) | (fp8mm ? DSOCR_LOAD_FP8_EXPERTS_MM : 0u) |
+                                             (kv16 ? DSOCR_LOAD_KV_F16 : 0u), out);
 }
 
 dsocr_status dsocr_engine_fp8_mode(const dsocr_engine* e, int* mode) {
     return guarded([&] {
         if (!e || !mode) throw std::runtime_error("EINVAL: NULL argument");
         *mode = e->impl->fp8_mode();
+    });
+}
+
+dsocr_status dsocr_engine_kv_info(const dsocr_engine* e, int* elem_bytes, size_t* cache_bytes) {
+    return guarded([&] {
+        if (!e) throw std::runtime_error("EINVAL: NULL engine");
+        e->impl->kv_info(elem_bytes, cache_bytes);
     });
 }
 
@@ -1725,6 +1735,38 @@ dsocr_status dsocr_k_decode_attention(int B, int heads, int kv_heads, int hd, in
         (void)hipFree(cnt);
         check_hip(e, "decode attention");
         if (herr) throw std::runtime_error("EINTERNAL: decode attention merge timed out");
+    });
+}
+dsocr_status dsocr_k_decode_attention_kv16(int B, int heads, int kv_heads, int hd, int rope_dim, int max_len, float scale,
+                                           const float* qkv, const float* cos, const float* sin, uint16_t* kc,
+                                           uint16_t* vc, const int* kv_pos, float* o, int prerot) {
+    return guarded([&] {
+        if (hd != 32 && hd != 64 && hd != 128) throw std::runtime_error("EINVAL: head_dim must be 32, 64 or 128");
+        if (prerot && rope_dim != hd) throw std::runtime_error("EINVAL: pre-rotated rows need rope_dim == head_dim");
+        if (B <= 0 || max_len <= 0 || kv_heads <= 0 || heads % kv_heads || rope_dim > hd || rope_dim % 2)
+            throw std::runtime_error("EINVAL: bad head / rope configuration");
+        // (the ticket merge reads no sentinel: the records enter as allocated; the tickets enter zero)
+        float* part = nullptr;
+        int* cnt = nullptr;
+        check_hip(hipMalloc(&part, dsocr::dec_attn_workspace(B, heads, hd, max_len)), "hipMalloc");
+        check_hip(hipMalloc(&cnt, sizeof(int) * B * heads), "hipMalloc");
+        check_hip(hipMemset(cnt, 0, sizeof(int) * B * heads), "hipMemset");
+        dsocr::DecAttnKv16Args a;
+        a.qkv = qkv; a.ld = (long)(heads + 2 * kv_heads) * hd; a.kv_pos = kv_pos; a.B = B; a.heads = heads;
+        a.kv_heads = kv_heads; a.hd = hd; a.rope_dim = rope_dim; a.use_mla = 0; a.max_len = max_len;
+        a.cos = cos; a.sin = sin; a.kc16 = kc; a.vc16 = vc; a.head_stride = (long)max_len * hd;
+        a.page_stride = (long)kv_heads * max_len * hd; a.scale = scale; a.part = part; a.o = o;
+        a.o_ld = (long)heads * hd; a.counters = cnt;
+        a.prerot = prerot != 0;
+        dsocr::launch_dec_attn_kv16(a, nullptr);
+        hipError_t e = hipDeviceSynchronize();
+        std::vector<int> left((size_t)B * heads, 0);
+        if (e == hipSuccess) e = hipMemcpy(left.data(), cnt, sizeof(int) * left.size(), hipMemcpyDeviceToHost);
+        (void)hipFree(part);
+        (void)hipFree(cnt);
+        check_hip(e, "decode attention (f16 cache)");
+        for (int v : left)
+            if (v) throw std::runtime_error("EINTERNAL: decode attention left an arrival ticket non-zero");
     });
 }
 // The one body of the three prefill-attention hooks below: the plan and the views of Engine::forward_rows /

@@ -246,7 +246,8 @@ void* Engine::ws(const std::string& name0, size_t bytes) {
 Engine::Engine(const std::string& config_path, const std::string& weights_path, int device, int dtype, uint64_t seed,
                const std::string& snapshot_path, uint32_t load_flags)
     : device_(device), dtype_(dtype) {
-    if (load_flags & ~15u) throw std::runtime_error("EINVAL: unknown load flags");
+    if (load_flags & ~31u) throw std::runtime_error("EINVAL: unknown load flags");
+    kv_f16_ = (load_flags & 16u) != 0;
     if (load_flags & 8u) load_flags |= 4u;  // the matrix-core form runs on the FP8 tables
     fp8_mm_ = (load_flags & 8u) != 0;
     if ((load_flags & 4u) && (load_flags & 3u))
@@ -1243,8 +1244,12 @@ void Engine::layer_forward_prefill(int l, int T, int B, const int* row_page, con
     float* QKV = wsf("d_qkv", (size_t)T * QKVN);
     float* CTX = wsf("d_ctx", (size_t)T * H);
     // (a session prefills one page into its own slot of the session cache: kv_page0_)
-    float* kc = kc_ + (long)l * layer_kv(B) + (long)kv_page0_ * page_stride_;
-    float* vc = vc_ + (long)l * layer_kv(B) + (long)kv_page0_ * page_stride_;
+    // (f16 cache: the layer's f32 rows go to a one-layer scratch every layer reuses - the prefill's own attention
+    // reads them - and rope_kv stores the rounded rows into the cache beside)
+    if (kv_f16_ && (past || chunk_attn || kv_page0_ || kv_pages_))
+        throw std::runtime_error("EINTERNAL: the f16 KV cache serves no session, prefix or chunked prefill");
+    float* kc = kv_f16_ ? kv_scratch_k_ : kc_ + (long)l * layer_kv(B) + (long)kv_page0_ * page_stride_;
+    float* vc = kv_f16_ ? kv_scratch_v_ : vc_ + (long)l * layer_kv(B) + (long)kv_page0_ * page_stride_;
 
     launch_rmsnorm(X, H, XN, H, T, H, d.in_norm.w, L.rms_eps, st);
     linear(XN, T, H, d.qkv, QKV, QKVN);
@@ -1252,6 +1257,7 @@ void Engine::layer_forward_prefill(int l, int T, int B, const int* row_page, con
     r.qkv = QKV; r.ld = QKVN; r.rows = T; r.row_page = row_page; r.row_pos = row_pos;
     r.heads = L.heads; r.kv_heads = L.kv_heads; r.hd = hd; r.rope_dim = L.rope_dim; r.use_mla = L.use_mla;
     r.cos = rope_cos_; r.sin = rope_sin_; r.kc = kc; r.vc = vc; r.page_stride = page_stride_; r.head_stride = head_stride_;
+    if (kv_f16_) { r.kc16 = kc16_ + (long)l * layer_kv(B); r.vc16 = vc16_ + (long)l * layer_kv(B); }
     launch_rope_kv(r, st);
     if (past) {
         // behind a cached past (a page prefix entry): seq_len counts the new rows, row_pos starts at the past
@@ -1418,7 +1424,7 @@ DecAttn2Args Engine::attn_args(int l, int B, int Lmax, int copy) {
     da.qkv = rows_.qkv[copy]; da.ld = QKVN; da.kv_pos = rows_.kv_pos; da.B = B;
     da.heads = L.heads; da.kv_heads = L.kv_heads; da.hd = hd; da.rope_dim = L.rope_dim; da.use_mla = L.use_mla;
     da.max_len = Lmax; da.cos = rope_cos_; da.sin = rope_sin_;
-    da.kc = kc_ + (long)l * layer_kv; da.vc = vc_ + (long)l * layer_kv;
+    if (!kv_f16_) { da.kc = kc_ + (long)l * layer_kv; da.vc = vc_ + (long)l * layer_kv; }
     da.page_stride = page_stride_; da.head_stride = head_stride_;
     da.scale = (float)(1.0 / std::sqrt((double)hd));
     da.part = rows_.part[copy];
@@ -1426,6 +1432,14 @@ DecAttn2Args Engine::attn_args(int l, int B, int Lmax, int copy) {
     da.counters = rows_.attn_cnt;
     da.err = rows_.err;
     return da;
+}
+
+// the f16 cache's form of layer l's arguments (launch_dec_attn_kv16)
+DecAttnKv16Args Engine::attn_args_kv16(const DecAttn2Args& da, int l) {
+    DecAttnKv16Args k;
+    static_cast<DecAttn2Args&>(k) = da;
+    k.kc16 = kc16_ + (long)l * layer_kv(da.B); k.vc16 = vc16_ + (long)l * layer_kv(da.B);
+    return k;
 }
 
 // DSOCR_NO_GRAPH=1 (read per generate and per profile section): the decode step's kernels launched eagerly
@@ -1440,7 +1454,7 @@ bool Engine::persist_ok(int B, int Lmax) {
     // opt-in (DSOCR_PERSIST=1, read per generate): measured slower than the per-layer launch chain on MI355X
     // (43.5 vs 33.5 us per layer), kept as the A/B of the persistent-layer design
     const char* e = getenv("DSOCR_PERSIST");
-    if (!e || atoi(e) == 0) return false;
+    if (!e || atoi(e) == 0 || kv_f16_) return false;  // (the persistent launch reads an f32 cache)
     const LangConfig& L = cfg_.lang;
     for (const DecLayer& d : layers_)
         if (d.packed || d.fp8) return false;  // the persistent launch streams the fp16 experts only
@@ -1594,7 +1608,9 @@ void Engine::decode_step(int B, int Lmax) {
     // before the loop - a layer hands its refill on only to a fused launch right behind it in the same step,
     // and cleans the other copy only behind a launch that handed its refill on
     std::vector<char> defer_l(L.layers, 0);
-    if (one_page && qkv_attn_fused() && att_refill_defer() && !(step_skip_ & SKIP_ATTN))
+    // (f16 cache: no fused one-page launch - the projection, then launch_dec_attn_kv16)
+    const bool fused_ok = qkv_attn_fused() && !kv_f16_;
+    if (one_page && fused_ok && att_refill_defer() && !(step_skip_ & SKIP_ATTN))
         for (int l = 0; l < L.layers; ++l) {
             DecGemvArgs g; DecRopeEpi re; DecAttn2Args da;
             qkv_args(l, l & 1, g, re, da);
@@ -1617,7 +1633,7 @@ void Engine::decode_step(int B, int Lmax) {
         }
         bool attn_done = false;
         if (one_page) {
-            if (qkv_attn_fused() && dec_qkv_attn_ok(g, re, da)) {
+            if (fused_ok && dec_qkv_attn_ok(g, re, da)) {
                 // one launch: the attention blocks stream their K / V chunk beside the projection
                 // (s_qkv stays sentinel-filled between launches; SKIP_ATTN, the profile's variant without
                 // attention, projects into a scratch row so the hand-off row keeps its sentinels)
@@ -1639,7 +1655,8 @@ void Engine::decode_step(int B, int Lmax) {
             g.x = XN; g.norm_w = nullptr;
             launch_dec_gemv(g, st);
         }
-        if (!attn_done && !(step_skip_ & SKIP_ATTN)) stamped(SPAN_ATTN, l, [&] { launch_dec_attn(da, st); }, nullptr, 0);
+        if (!attn_done && !(step_skip_ & SKIP_ATTN))
+            stamped(SPAN_ATTN, l, [&] { kv_f16_ ? launch_dec_attn_kv16(attn_args_kv16(da, l), st) : launch_dec_attn(da, st); }, nullptr, 0);
         // o_proj + residual
         DecGemvArgs go;
         go.M = B; go.N = H; go.K = L.heads * hd; go.x = CTX; go.ldx = H; go.W = d.o.W; go.ldw = go.K;
@@ -1895,11 +1912,18 @@ void Engine::reserve_decode_rows(const DecodeRowsSpec& spec) {
     head_stride_ = (long)r.Lcap * L.head_dim;
     page_stride_ = (long)L.kv_heads * head_stride_;
     const size_t kv_floats = (size_t)L.layers * S * page_stride_;
-    kc_ = wsf("kv_k", kv_floats);
-    vc_ = wsf("kv_v", kv_floats);
+    const size_t kv_eb = kv_f16_ ? 2 : 4;
+    void* kcv = ws("kv_k", kv_floats * kv_eb);
+    void* vcv = ws("kv_v", kv_floats * kv_eb);
+    kc_ = kv_f16_ ? nullptr : (float*)kcv; vc_ = kv_f16_ ? nullptr : (float*)vcv;
+    kc16_ = kv_f16_ ? (uint16_t*)kcv : nullptr; vc16_ = kv_f16_ ? (uint16_t*)vcv : nullptr;
+    if (kv_f16_) {
+        kv_scratch_k_ = wsf("kv_k_f32", (size_t)S * page_stride_);
+        kv_scratch_v_ = wsf("kv_v_f32", (size_t)S * page_stride_);
+    }
     if (spec.zero_fill) {
-        HIP_CHECK(hipMemsetAsync(kc_, 0, kv_floats * 4, st));
-        HIP_CHECK(hipMemsetAsync(vc_, 0, kv_floats * 4, st));
+        HIP_CHECK(hipMemsetAsync(kcv, 0, kv_floats * kv_eb, st));
+        HIP_CHECK(hipMemsetAsync(vcv, 0, kv_floats * kv_eb, st));
     }
     // n ints under `name`, zeroed on request (+ pad bytes: rows the caller fills with upload()-sized copies)
     auto ints = [&](const char* name, size_t n, bool zero, size_t pad = 0) {
@@ -3086,6 +3110,7 @@ static RowParams resolve_row_params(const GenParams& p) {
 }
 
 void Engine::session_open(int S, int max_context, const GenParams& p, const SessionFeatures& feat) {
+    if (kv_f16_) throw std::runtime_error(kKvF16NoSession);
     if (sess_) throw std::runtime_error("EINVAL: a decode session is already open on this engine");
     if (S < 1 || S > 8) throw std::runtime_error("EINVAL: a session has 1..8 slots");
     if (!p.use_cache || p.trace) throw std::runtime_error("EINVAL: a session decodes with the K/V cache and without a logits trace");
@@ -3809,6 +3834,12 @@ void Engine::time_launches(KernelProfile& kp, int n, const std::function<void(in
         kp.replay_us = replay_us(1, [&] { for (int i = 0; i < n; ++i) body(i); }) / n;
 }
 
+void Engine::kv_info(int* elem_bytes, size_t* cache_bytes) const {
+    const size_t eb = kv_f16_ ? 2 : 4;
+    if (elem_bytes) *elem_bytes = (int)eb;
+    if (cache_bytes) *cache_bytes = 2 * (size_t)cfg_.lang.layers * rows_.S * page_stride_ * eb;
+}
+
 Engine::DecodeProfile Engine::profile_decode(int iters) {
     if (sess_) throw std::runtime_error("EINVAL: a decode session is open on this engine (close it before profile_decode)");
     DecodeProfile prof;
@@ -3833,18 +3864,20 @@ Engine::DecodeProfile Engine::profile_decode(int iters) {
     // the replays rewrite the K / V slot of pos - 1 in every layer (the attention replays from the scratch
     // row): keep those slots and put them back after the attention replays and at the end, so the
     // step-graph replays and any later use of the engine state see the cache the generate left
-    const size_t slot_w = (size_t)hd * 4, n_slots = (size_t)L.layers * B * 2;
-    float* kv_saved = wsf("p_kv_saved", n_slots * L.kv_heads * hd);
+    const size_t eb = kv_f16_ ? 2 : 4;  // the cache's element size
+    const size_t slot_w = (size_t)hd * eb, n_slots = (size_t)L.layers * B * 2;
+    char* kv_saved = (char*)ws("p_kv_saved", n_slots * L.kv_heads * slot_w);
     auto kv_slots = [&](bool restore) {
         for (int l = 0; l < L.layers; ++l)
             for (int b = 0; b < B; ++b)
                 for (int kv = 0; kv < 2; ++kv) {
-                    float* base = (kv ? vc_ : kc_) + (long)l * B * page_stride_ + (long)b * page_stride_ + (long)pm1[b] * hd;
-                    float* keep = kv_saved + (((size_t)l * B + b) * 2 + kv) * L.kv_heads * hd;
+                    char* cache = kv_f16_ ? (char*)(kv ? vc16_ : kc16_) : (char*)(kv ? vc_ : kc_);
+                    char* base = cache + ((long)l * B * page_stride_ + (long)b * page_stride_ + (long)pm1[b] * hd) * eb;
+                    char* keep = kv_saved + (((size_t)l * B + b) * 2 + kv) * L.kv_heads * slot_w;
                     if (restore)
-                        HIP_CHECK(hipMemcpy2DAsync(base, head_stride_ * 4, keep, slot_w, slot_w, L.kv_heads, hipMemcpyDeviceToDevice, st));
+                        HIP_CHECK(hipMemcpy2DAsync(base, head_stride_ * eb, keep, slot_w, slot_w, L.kv_heads, hipMemcpyDeviceToDevice, st));
                     else
-                        HIP_CHECK(hipMemcpy2DAsync(keep, slot_w, base, head_stride_ * 4, slot_w, L.kv_heads, hipMemcpyDeviceToDevice, st));
+                        HIP_CHECK(hipMemcpy2DAsync(keep, slot_w, base, head_stride_ * eb, slot_w, L.kv_heads, hipMemcpyDeviceToDevice, st));
                 }
     };
     kv_slots(false);
@@ -3904,11 +3937,11 @@ Engine::DecodeProfile Engine::profile_decode(int iters) {
     time_launches(prof.attention, iters * L.layers, [&](int i) {
         DecAttn2Args da = attn_args(i % L.layers, B, Lmax);
         da.qkv = qkv0; da.kv_pos = d_pos; da.o = CTX;  // (the replays rewrite the K / V slot of pos - 1 from qkv0)
-        launch_dec_attn(da, st);
+        kv_f16_ ? launch_dec_attn_kv16(attn_args_kv16(da, i % L.layers), st) : launch_dec_attn(da, st);
     });
     kv_slots(true);
     // K and V of every attended key (f32 cache) + q/k/v row + context out
-    prof.attention.bytes = (double)keys * L.kv_heads * hd * 4.0 * 2.0 + (double)B * (QKVN + H) * 4.0;
+    prof.attention.bytes = (double)keys * L.kv_heads * hd * (double)eb * 2.0 + (double)B * (QKVN + H) * 4.0;
     prof.attention.flops = 4.0 * keys * L.heads * hd;
     profile_gemvs(prof, iters, moe_layers);
     if (graphs_on()) profile_step_context(prof, iters, (int)moe_layers.size());

@@ -330,6 +330,13 @@ class Engine {
     void fp8_info(size_t* fp8_layers, size_t* moe_layers, size_t* fp8_bytes) const;
     // 0 fp16 experts, 1 FP8 experts, 2 FP8 experts with the matrix-core form at 3..8 tokens
     int fp8_mode() const { return fp8_mm_ ? 2 : fp8_experts_ ? 1 : 0; }
+    // KV cache: bytes per element (4, or 2 under DSOCR_LOAD_KV_F16) and the bytes of K + V of the current decode
+    // rows (0 before any generate)
+    void kv_info(int* elem_bytes, size_t* cache_bytes) const;
+    // what session_open answers on an engine with the f16 cache (the server's start-up check says the same)
+    static constexpr const char* kKvF16NoSession =
+        "EINVAL: decode sessions (with page prefixes and chunked admission) need the f32 KV cache: this engine was loaded "
+        "with the f16 KV cache (DSOCR_LOAD_KV_F16)";
 
     const ModelConfig& cfg() const { return cfg_; }
     int variant() const { return cfg_.variant; }
@@ -527,6 +534,7 @@ class Engine {
     void ensure_persist();
     MoeDecodeArgs moe_args(int l, int B, float* X);
     DecAttn2Args attn_args(int l, int B, int Lmax, int copy = 0);
+    DecAttnKv16Args attn_args_kv16(const DecAttn2Args& da, int l);
     // the decode rows: reserved under their workspace names and initialised (tickets and flag zeroed, hand-offs
     // sentinel-filled) by the one function that knows their sizes
     DecodeRows rows_;
@@ -665,6 +673,13 @@ class Engine {
     // kv cache
     float* kc_ = nullptr;
     float* vc_ = nullptr;
+    // f16 cache (kv_f16_): kc16_ / vc16_ replace kc_ / vc_ (null then) at the same element strides;
+    // kv_scratch_k_ / _v_ are the one-layer f32 rows [S][kv_heads][Lcap][hd] the prefill's own attention reads
+    bool kv_f16_ = false;
+    uint16_t* kc16_ = nullptr;
+    uint16_t* vc16_ = nullptr;
+    float* kv_scratch_k_ = nullptr;
+    float* kv_scratch_v_ = nullptr;
     long page_stride_ = 0, head_stride_ = 0;
     // a session's cache holds kv_pages_ pages per layer whatever the batch a launch runs (0: the launch's own
     // B, as generate sizes it); its prefill writes page kv_page0_

@@ -764,6 +764,14 @@ void launch_sam_relbias(const float* q, long q_row_stride, int n_seq, int gh, in
 }
 
 // ------------------------------------------------------------------ RoPE + KV append
+// the f16 cache's rounding (decode_attn16.hip): nearest even, clamped to +-65504, NaN kept
+__device__ __forceinline__ uint16_t f16_rne_clamp(float x) {
+    x = x > 65504.f ? 65504.f : (x < -65504.f ? -65504.f : x);
+    const _Float16 h = (_Float16)x;
+    uint16_t b;
+    __builtin_memcpy(&b, &h, 2);
+    return b;
+}
 __global__ __launch_bounds__(256) void rope_kv_kernel(RopeKvArgs a) {
     const int r = blockIdx.x;
     const int page = a.row_page[r], pos = a.row_pos[r];
@@ -808,12 +816,14 @@ __global__ __launch_bounds__(256) void rope_kv_kernel(RopeKvArgs a) {
         } else {
             const int kh = hh - nq;
             a.kc[(long)page * a.page_stride + (long)kh * a.head_stride + (long)pos * a.hd + d] = outv[it];
+            if (a.kc16) a.kc16[(long)page * a.page_stride + (long)kh * a.head_stride + (long)pos * a.hd + d] = f16_rne_clamp(outv[it]);
         }
     }
     for (int idx = threadIdx.x; idx < nk * a.hd; idx += blockDim.x) {
         const int kh = idx / a.hd, d = idx % a.hd;
         float* vc = a.vc + (long)page * a.page_stride + (long)kh * a.head_stride + (long)pos * a.hd;
         vc[d] = row[H + KVH + kh * a.hd + d];
+        if (a.vc16) a.vc16[(long)page * a.page_stride + (long)kh * a.head_stride + (long)pos * a.hd + d] = f16_rne_clamp(vc[d]);
     }
 }
 

@@ -191,6 +191,9 @@ struct RopeKvArgs {
     int heads = 0, kv_heads = 0, hd = 0, rope_dim = 0, use_mla = 0;
     const float* cos = nullptr; const float* sin = nullptr;       // [Lmax][rope_dim]
     float* kc = nullptr; float* vc = nullptr; long page_stride = 0, head_stride = 0;
+    // optional second output (f16 KV cache, DSOCR_LOAD_KV_F16): the same rows rounded to f16 (nearest even, clamped
+    // to +-65504) at the same element strides; null: nothing but the f32 rows is written
+    uint16_t* kc16 = nullptr; uint16_t* vc16 = nullptr;
 };
 // throws EINVAL unless heads % kv_heads == 0, (heads + kv_heads) * hd <= 8192 and rope_dim is even and <= hd
 void launch_rope_kv(const RopeKvArgs& a, hipStream_t s);
@@ -426,6 +429,17 @@ struct DecAttn2Args {
     float* clean_part = nullptr;
 };
 void launch_dec_attn(const DecAttn2Args& a, hipStream_t s);
+// DecAttn2Args with the cache as f16 (kc / vc unused): same layout and element strides.  A struct of its own, so
+// the f32 kernels' arguments are what they were.
+struct DecAttnKv16Args : DecAttn2Args {
+    uint16_t* kc16 = nullptr; uint16_t* vc16 = nullptr;
+};
+// Decode attention over an f16 K/V cache (decode_attn16.hip): a.kc16 / a.vc16 hold f16(K_rot) / f16(V), rounded
+// once at append (nearest even, clamped to +-65504); the step's own key / value enter unrounded; q, scores, softmax,
+// P.V, the records and the merge are f32.  128-key chunks, arrival-ticket merge only (a.part sized by
+// dec_attn_workspace, a.counters zero between launches; no sentinel is read or written).  Any B, hd 32 / 64 / 128,
+// heads % kv_heads == 0, prerot or not, max_len <= 512 * 128.
+void launch_dec_attn_kv16(const DecAttnKv16Args& a, hipStream_t s);
 // q/k/v projection of one token with RoPE applied in the epilogue (rows < rot_rows rotated at
 // position kv_pos[0]; table layout [pos][hd], rope on the full head dim, rotate_half pairing).
 struct DecRopeEpi {

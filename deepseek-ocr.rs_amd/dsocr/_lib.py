@@ -163,6 +163,10 @@ LOAD_PACKED_EXPERTS = 1  # DSOCR_LOAD_PACKED_EXPERTS
 LOAD_PACKED_INT8_DOT = 2  # DSOCR_LOAD_PACKED_INT8_DOT (implies LOAD_PACKED_EXPERTS)
 LOAD_FP8_EXPERTS = 4  # DSOCR_LOAD_FP8_EXPERTS
 LOAD_FP8_EXPERTS_MM = 8  # DSOCR_LOAD_FP8_EXPERTS_MM (implies LOAD_FP8_EXPERTS)
+LOAD_KV_F16 = 16  # DSOCR_LOAD_KV_F16
+# what dsocr_session_open* answers on an engine with the f16 KV cache (the server's start-up check says the same)
+KV_F16_NO_SESSION = ("decode sessions (with page prefixes and chunked admission) need the f32 KV cache: this engine was "
+                     "loaded with the f16 KV cache (DSOCR_LOAD_KV_F16)")
 STREAM_CB = C.CFUNCTYPE(None, C.c_size_t, C.POINTER(C.c_int64), C.c_void_p)
 
 # every symbol include/dsocr.h declares (tests check the library exports all of them)
@@ -181,6 +185,7 @@ EXPORTS = [
     "dsocr_resize_catmull_rom",
     "dsocr_engine_load_flags", "dsocr_engine_packed_info", "dsocr_k_moe_packed", "dsocr_k_dsq_rows_dot",
     "dsocr_engine_fp8_info", "dsocr_k_fp8_quantize_rows", "dsocr_k_fp8_rows_dot", "dsocr_k_moe_fp8",
+    "dsocr_engine_kv_info", "dsocr_k_decode_attention_kv16",
     "dsocr_engine_fp8_mode", "dsocr_k_fp8_tile_order", "dsocr_k_fp8_mm_rows_dot", "dsocr_k_moe_fp8_mm",
     "dsocr_engine_packed_mode", "dsocr_k_q8_quantize", "dsocr_k_dsq_rows_dot_q8", "dsocr_k_moe_packed_q8",
     "dsocr_k_moe_ex", "dsocr_k_moe_route_kind", "dsocr_k_moe_prefill_route", "dsocr_k_moe_combine",
@@ -327,6 +332,8 @@ def lib():
     L.dsocr_k_dsq_rows_dot_q8.argtypes = [i32, sz, sz, vp, i32, vp, vp, vp, vp]
     L.dsocr_k_moe_packed_q8.argtypes = L.dsocr_k_moe_packed.argtypes + [vp] * 6
     L.dsocr_engine_fp8_info.argtypes = [vp, C.POINTER(sz), C.POINTER(sz), C.POINTER(sz)]
+    L.dsocr_engine_kv_info.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(sz)]
+    L.dsocr_k_decode_attention_kv16.argtypes = [i32, i32, i32, i32, i32, i32, f32, vp, vp, vp, vp, vp, vp, vp, i32]
     L.dsocr_k_fp8_quantize_rows.argtypes = [sz, sz, vp, vp, vp]
     L.dsocr_k_fp8_rows_dot.argtypes = [sz, sz, vp, vp, i32, vp, vp]
     L.dsocr_k_moe_fp8.argtypes = [i32, i32, i32, i32, i32, i32, vp, vp, f32, vp, vp, vp, vp, vp, i32, f32, vp, vp, vp]

@@ -18,7 +18,7 @@ from typing import Any, Callable, Optional, Sequence, Union
 
 import numpy as np
 
-from ._lib import (DTYPES, LOAD_FP8_EXPERTS, LOAD_FP8_EXPERTS_MM, LOAD_PACKED_EXPERTS, LOAD_PACKED_INT8_DOT, MAX_TOP_LOGPROBS, DecodeParamsC, DsocrError, LoadArgs, LogitBiasC, LogprobsC,
+from ._lib import (DTYPES, LOAD_FP8_EXPERTS, LOAD_FP8_EXPERTS_MM, LOAD_KV_F16, LOAD_PACKED_EXPERTS, LOAD_PACKED_INT8_DOT, MAX_TOP_LOGPROBS, DecodeParamsC, DsocrError, LoadArgs, LogitBiasC, LogprobsC,
                    GuidedC, GuidedResultC, NgramWindowC, PenaltiesC, SESSION_GUIDED, RequestC, ResultC, STREAM_CB, SESSION_LOGIT_BIAS, SESSION_LOGPROBS,
                    SESSION_NGRAM_WINDOW, SESSION_PENALTIES,
                    SESSION_PER_REQUEST, SESSION_STOP,
@@ -193,6 +193,10 @@ class ModelLoadArgs:
     # environment switch decides (when snapshot_packed is None too), True / False = dsocr_engine_load_flags
     # "mm" = DSOCR_LOAD_FP8_EXPERTS_MM: as True, and decode steps of 3..8 tokens run the codes on the matrix cores
     expert_fp8: Union[None, bool, str] = None
+    # the decoder's K/V cache: "f16" = DSOCR_LOAD_KV_F16 (K / V rounded once at append, half the cache bytes, a decode
+    # attention kernel of its own; no decode session on such an engine), "f32" = the f32 cache, None = the DSOCR_KV_F16
+    # environment switch decides (when snapshot_packed and expert_fp8 are None too; else f32)
+    kv_dtype: Optional[str] = None
     device: int = 0
     dtype: str = "f16"
     synthetic_seed: int = 0
@@ -377,11 +381,13 @@ class DeepseekOcrEngine:
             raise DsocrError(1, f"ModelKind::{args.kind} cannot be loaded by the Deepseek engine")
         if args.config_path is None:
             raise DsocrError(1, "config_path is required")
+        if args.kv_dtype not in (None, "f32", "f16"):
+            raise DsocrError(1, f"kv_dtype takes None, 'f32' or 'f16', not {args.kv_dtype!r}")
         la = LoadArgs(args.config_path.encode(), args.weights_path.encode() if args.weights_path else None,
                       args.snapshot_path.encode() if args.snapshot_path else None, args.device, DTYPES[args.dtype],
                       args.synthetic_seed)
         h = C.c_void_p()
-        if args.snapshot_packed is None and args.expert_fp8 is None:
+        if args.snapshot_packed is None and args.expert_fp8 is None and args.kv_dtype is None:
             check(lib().dsocr_engine_load(C.byref(la), C.byref(h)))
         else:
             if isinstance(args.snapshot_packed, str) and args.snapshot_packed != "int8":
@@ -392,6 +398,8 @@ class DeepseekOcrEngine:
                 raise DsocrError(1, f"expert_fp8 takes None, True, False or 'mm', not {args.expert_fp8!r}")
             if args.expert_fp8:
                 flags |= LOAD_FP8_EXPERTS | LOAD_FP8_EXPERTS_MM if args.expert_fp8 == "mm" else LOAD_FP8_EXPERTS
+            if args.kv_dtype == "f16":
+                flags |= LOAD_KV_F16
             check(lib().dsocr_engine_load_flags(C.byref(la), flags, C.byref(h)))
         self._h = h
         self.args = args
@@ -413,6 +421,13 @@ class DeepseekOcrEngine:
         fl, ml, fb = C.c_size_t(), C.c_size_t(), C.c_size_t()
         check(lib().dsocr_engine_fp8_info(self._h, C.byref(fl), C.byref(ml), C.byref(fb)))
         return {"fp8_layers": fl.value, "moe_layers": ml.value, "fp8_bytes": fb.value}
+
+    def kv_info(self) -> dict:
+        """The K/V cache: {"elem_bytes": 4 or 2 (kv_dtype f16), "cache_bytes": K + V of the current decode rows (0
+        before any generate)}."""
+        eb, cb = C.c_int(), C.c_size_t()
+        check(lib().dsocr_engine_kv_info(self._h, C.byref(eb), C.byref(cb)))
+        return {"elem_bytes": eb.value, "cache_bytes": cb.value}
 
     def fp8_mode(self) -> int:
         """0 fp16 experts, 1 FP8 experts, 2 FP8 experts with the matrix-core form at 3..8 tokens."""

@@ -147,6 +147,16 @@ dsocr_status dsocr_engine_load(const dsocr_load_args* args, dsocr_engine** out);
  * of 1 or 2 tokens and layers that do not fit keep the kernels of DSOCR_LOAD_FP8_EXPERTS.  dsocr_engine_load adds the
  * flag when the environment has DSOCR_EXPERT_FP8_MM set to a non-zero value. */
 #define DSOCR_LOAD_FP8_EXPERTS_MM 8u
+/* DSOCR_LOAD_KV_F16 (combines with every flag above): the decoder's K/V cache keeps f16(K_rot) and f16(V) - rounded
+ * once at append, to nearest even, clamped to +-65504 - in the f32 cache's layout, at half its bytes, and the decode
+ * attention runs a kernel of its own over it (decode_attn16.hip).  Everything else stays f32
+ * (q, scores, softmax, P.V, the merge); a step's own key / value enter its attention unrounded; the prefill's own
+ * attention runs on the f32 rows of the layer.  A numerics change, so off by default.  Limits: decode sessions, page
+ * prefixes and chunked admission need the f32 cache - dsocr_session_open* on such an engine is DSOCR_EINVAL;
+ * DSOCR_PERSIST=1 and the fused one-page q/k/v + attention launch are not used (one page runs the projection and then
+ * the attention); there is no FP8 cache.  dsocr_engine_load adds the flag when the environment has DSOCR_KV_F16 set to
+ * a non-zero value. */
+#define DSOCR_LOAD_KV_F16 16u
 dsocr_status dsocr_engine_load_flags(const dsocr_load_args* args, uint32_t flags, dsocr_engine** out);
 /* MoE layers that kept packed blocks, MoE layers in all, device bytes of the packed tables (any may be NULL) */
 dsocr_status dsocr_engine_packed_info(const dsocr_engine* e, size_t* packed_layers, size_t* moe_layers,
@@ -155,6 +165,9 @@ dsocr_status dsocr_engine_packed_info(const dsocr_engine* e, size_t* packed_laye
 dsocr_status dsocr_engine_packed_mode(const dsocr_engine* e, int* mode);
 /* MoE layers that run the FP8 decode kernels, MoE layers in all, device bytes of the FP8 tables (any may be NULL) */
 dsocr_status dsocr_engine_fp8_info(const dsocr_engine* e, size_t* fp8_layers, size_t* moe_layers, size_t* fp8_bytes);
+/* The K/V cache: bytes per element (4; 2 with DSOCR_LOAD_KV_F16) and the device bytes of K + V of the current decode
+ * rows (0 before any generate); either may be NULL */
+dsocr_status dsocr_engine_kv_info(const dsocr_engine* e, int* elem_bytes, size_t* cache_bytes);
 /* How the engine was loaded: 0 fp16 experts, 1 FP8 experts, 2 FP8 experts with the matrix-core form at 3..8 tokens */
 dsocr_status dsocr_engine_fp8_mode(const dsocr_engine* e, int* mode);
 void dsocr_engine_free(dsocr_engine* e);
@@ -869,6 +882,12 @@ dsocr_status dsocr_window_maps(int n, int g, int W, int* tok2win, int* win2tok);
 dsocr_status dsocr_k_decode_attention(int B, int heads, int kv_heads, int hd, int rope_dim, int max_len, float scale,
                                       const float* qkv, const float* cos, const float* sin, float* kc, float* vc,
                                       const int* kv_pos, float* o, int prerot);
+/* The same step over f16 caches [B][kv_heads][max_len][hd] (DSOCR_LOAD_KV_F16, decode_attn16.hip): k and v are
+ * appended rounded to f16 (nearest even, clamped to +-65504) and enter this call's attention unrounded; the cached
+ * rows widen exactly.  Every other argument as above.  DSOCR_EINVAL unless hd is 32, 64 or 128. */
+dsocr_status dsocr_k_decode_attention_kv16(int B, int heads, int kv_heads, int hd, int rope_dim, int max_len, float scale,
+                                           const float* qkv, const float* cos, const float* sin, uint16_t* kc,
+                                           uint16_t* vc, const int* kv_pos, float* o, int prerot);
 /* The decoder prefill between the q|k|v linear and the o linear, as the engine launches it on a ragged batch
  * (block.rs:608-789, rope block.rs:1403-1471): B sequences of lens[b] rows (host array) packed one after another,
  * T = sum lens rows in all.  qkv [T][(heads + 2 kv_heads) * hd]: the q columns are rotated in place at the row's
