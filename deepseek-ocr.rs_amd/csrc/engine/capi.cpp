@@ -2038,6 +2038,50 @@ dsocr_status dsocr_k_moe(int T, int H, int E, int topk, int I, int Is, const flo
     return dsocr_k_moe_ex(T, H, E, topk, I, Is, x, norm_w, eps, router, Wgu, Wd, sWgu, sWd, wdtype, norm_topk, scaling,
                           out, ids_out, w_out, 1, nullptr, nullptr);
 }
+// The harness of the hooks that run one whole decode MoE layer (dsocr_k_moe_ex, dsocr_k_moe_packed[_q8],
+// dsocr_k_moe_fp8[_mm]): the hook builds the tables of its form into a.w (device memory of its own through alloc),
+// run() does the rest the way Engine::moe_args does: the workspaces by moe_workspaces, the tickets zeroed.
+struct MoeHookRun {
+    dsocr::MoeDecodeArgs a;
+    std::vector<dsocr::DeviceBuffer> bufs;
+    MoeHookRun(int T, int H, int E, int topk, int I, const float* x, const float* norm_w, float eps, const void* router,
+               int router_wdt, float* out, int softmax_scoring, int norm_topk, float scaling) {
+        a.T = T; a.H = H; a.E = E; a.topk = topk; a.I = I;
+        a.x = x; a.norm_w = norm_w; a.eps = eps; a.out = out;
+        a.router = router; a.router_wdt = router_wdt; a.w.wdtype = router_wdt;
+        a.softmax_scoring = softmax_scoring ? 1 : 0; a.norm_topk = norm_topk; a.scaling = scaling;
+    }
+    void* alloc(size_t bytes) {
+        bufs.emplace_back(bytes);
+        return bufs.back().get();
+    }
+    // want: the gate/up kind the hook stands for (else EINVAL `outside`), or null; ids / w / logits: HOST outputs or null
+    void run(const dsocr::MoeGateUp* want, const char* outside, int* ids_out, float* w_out, float* logits_out) {
+        const dsocr::MoeWorkspaces n = dsocr::moe_workspaces(a.T, a.E, a.topk, a.H, a.I, a.w.Is, a.w.int8dot);
+        auto f = [&](size_t count) { return count ? (float*)alloc(sizeof(float) * count) : nullptr; };
+        auto i = [&](size_t count, bool zero = false) {
+            int* p = count ? (int*)alloc(sizeof(int) * count) : nullptr;
+            if (p && zero) check_hip(hipMemset(p, 0, sizeof(int) * count), "hipMemset");
+            return p;
+        };
+        a.xn = f(n.xn); a.xn_router = f(n.xn_router); a.logits = f(n.logits);
+        a.ids = i(n.ids); a.wts = f(n.wts); a.h = f(n.h); a.hs = f(n.hs); a.grp = i(n.grp);
+        a.route_cnt = i(n.route_cnt, true);
+        a.dn_part = f(n.dn_part); a.dn_tick = i(n.dn_tick, true);
+        if (n.q8_ws) a.q8_ws = alloc(n.q8_ws);
+        a.eoff = i(n.eoff); a.arow = i(n.arow); a.apos = i(n.apos); a.active = i(n.active); a.n_active = i(n.n_active);
+        a.aw = f(n.aw);
+        if (want && dsocr::moe_decode_gateup_kind(a) != *want) throw std::runtime_error(outside);
+        dsocr::launch_moe_decode(a, nullptr);
+        check_hip(hipGetLastError(), "moe launch");
+        check_hip(hipDeviceSynchronize(), "moe");
+        const size_t TK = (size_t)a.T * a.topk;
+        if (ids_out) check_hip(hipMemcpy(ids_out, a.ids, sizeof(int) * TK, hipMemcpyDeviceToHost), "d2h");
+        if (w_out) check_hip(hipMemcpy(w_out, a.wts, sizeof(float) * TK, hipMemcpyDeviceToHost), "d2h");
+        if (logits_out)
+            check_hip(hipMemcpy(logits_out, a.logits, sizeof(float) * (size_t)a.T * a.E, hipMemcpyDeviceToHost), "d2h");
+    }
+};
 dsocr_status dsocr_k_moe_ex(int T, int H, int E, int topk, int I, int Is, const float* x, const float* norm_w,
                             float eps, const void* router, const void* Wgu, const void* Wd, const void* sWgu,
                             const void* sWd, int wdtype, int norm_topk, float scaling, float* out, int* ids_out,
@@ -2046,70 +2090,28 @@ dsocr_status dsocr_k_moe_ex(int T, int H, int E, int topk, int I, int Is, const 
         if (T <= 0 || H <= 0 || E <= 0 || topk <= 0 || I <= 0) throw std::runtime_error("EINVAL: bad MoE shape");
         if (E > 256 || topk > 8 || topk > E) throw std::runtime_error("EINVAL: decode MoE takes <= 256 experts, top_k <= min(8, E)");
         if (!x || !router || !Wgu || !Wd || !out) throw std::runtime_error("EINVAL: NULL argument");
-        std::vector<void*> bufs;
-        auto alloc = [&](size_t b) {
-            void* p = nullptr;
-            check_hip(hipMalloc(&p, b ? b : 16), "hipMalloc");
-            bufs.push_back(p);
-            return p;
-        };
-        try {
-            const int TK = T * topk;
-            // the engine's own dispatch (Engine::decode_step -> launch_moe_decode): mix kernels at one
-            // token, slot kernels at two, the grouped (expert-deduplicated) kernels at 3..8, sorted groups above
-            dsocr::MoeDecodeArgs a;
-            a.T = T; a.H = H; a.E = E; a.topk = topk; a.I = I;
-            a.x = x; a.norm_w = norm_w; a.eps = eps; a.out = out;
-            a.router = router; a.router_wdt = wdtype; a.Wgu = Wgu; a.Wd = Wd; a.wdtype = wdtype;
-            a.router_bias = router_bias;
-            if (sWgu && sWd && Is > 0) {
-                a.Is = Is; a.sWgu = sWgu; a.sWd = sWd; a.hs = (float*)alloc(sizeof(float) * (size_t)T * Is);
+        // the engine's own dispatch (Engine::decode_step -> launch_moe_decode): mix kernels at one
+        // token, slot kernels at two, the grouped (expert-deduplicated) kernels at 3..8, sorted groups above
+        MoeHookRun h(T, H, E, topk, I, x, norm_w, eps, router, wdtype, out, softmax_scoring, norm_topk, scaling);
+        dsocr::MoeExperts& w = h.a.w;
+        h.a.router_bias = router_bias;
+        w.gu = Wgu; w.d = Wd;
+        if (sWgu && sWd && Is > 0) { w.Is = Is; w.sgu = sWgu; w.sd = sWd; }
+        if (wdtype == 1 && H % 32 == 0 && I % 32 == 0 && T <= 8) {
+            // fragment-ordered expert copies, as Engine::ensure_mm_weights keeps them
+            auto copy = [&](const void* m, int rows, int cols) {
+                void* o = h.alloc(sizeof(uint16_t) * dsocr::mm_swizzle_elems(rows, cols));
+                dsocr::launch_mm_swizzle(m, rows, cols, o, nullptr);
+                return o;
+            };
+            w.gu_swz = copy(Wgu, E * 2 * I, H);
+            w.d_swz = copy(Wd, E * H, I);
+            if (w.Is > 0 && w.Is % 32 == 0) {
+                w.sgu_swz = copy(sWgu, 2 * w.Is, H);
+                w.sd_swz = copy(sWd, H, w.Is);
             }
-            a.softmax_scoring = softmax_scoring ? 1 : 0; a.norm_topk = norm_topk; a.scaling = scaling;
-            a.xn = (float*)alloc(sizeof(float) * (size_t)T * H);
-            a.xn_router = (float*)alloc(sizeof(float) * (size_t)T * H);
-            a.logits = (float*)alloc(sizeof(float) * (size_t)T * E);
-            a.ids = (int*)alloc(sizeof(int) * TK);
-            a.wts = (float*)alloc(sizeof(float) * TK);
-            a.h = (float*)alloc(sizeof(float) * (size_t)TK * I);
-            a.grp = (int*)alloc(sizeof(int) * dsocr::moe_grp_ints(E, T, topk));
-            a.route_cnt = (int*)alloc(sizeof(int) * 16);
-            check_hip(hipMemset(a.route_cnt, 0, sizeof(int) * 16), "hipMemset");
-            if (wdtype == 1 && H % 32 == 0 && I % 32 == 0 && T <= 8) {
-                // fragment-ordered expert copies, as Engine::ensure_mm_weights keeps them
-                a.Wgu_swz = alloc(sizeof(uint16_t) * dsocr::mm_swizzle_elems(E * 2 * I, H));
-                dsocr::launch_mm_swizzle(Wgu, E * 2 * I, H, const_cast<void*>(a.Wgu_swz), nullptr);
-                a.Wd_swz = alloc(sizeof(uint16_t) * dsocr::mm_swizzle_elems(E * H, I));
-                dsocr::launch_mm_swizzle(Wd, E * H, I, const_cast<void*>(a.Wd_swz), nullptr);
-                if (a.Is > 0 && a.Is % 32 == 0) {
-                    a.sWgu_swz = alloc(sizeof(uint16_t) * dsocr::mm_swizzle_elems(2 * a.Is, H));
-                    dsocr::launch_mm_swizzle(sWgu, 2 * a.Is, H, const_cast<void*>(a.sWgu_swz), nullptr);
-                    a.sWd_swz = alloc(sizeof(uint16_t) * dsocr::mm_swizzle_elems(H, a.Is));
-                    dsocr::launch_mm_swizzle(sWd, H, a.Is, const_cast<void*>(a.sWd_swz), nullptr);
-                }
-            }
-            if (T >= 3 && T <= 8) {
-                a.dn_part = (float*)alloc(sizeof(float) * dsocr::moe_down_mm_part_floats(E, T, topk, I, a.Is, H));
-                a.dn_tick = (int*)alloc(sizeof(int) * (H / 64 + 1));
-                check_hip(hipMemset(a.dn_tick, 0, sizeof(int) * (H / 64 + 1)), "hipMemset");
-            }
-            if (T > 8) {
-                a.eoff = (int*)alloc(sizeof(int) * (E + 1)); a.arow = (int*)alloc(sizeof(int) * TK);
-                a.apos = (int*)alloc(sizeof(int) * TK); a.active = (int*)alloc(sizeof(int) * E);
-                a.aw = (float*)alloc(sizeof(float) * TK); a.n_active = (int*)alloc(sizeof(int));
-            }
-            dsocr::launch_moe_decode(a, nullptr);
-            check_hip(hipGetLastError(), "moe launch");
-            check_hip(hipDeviceSynchronize(), "moe");
-            if (ids_out) check_hip(hipMemcpy(ids_out, a.ids, sizeof(int) * TK, hipMemcpyDeviceToHost), "d2h");
-            if (w_out) check_hip(hipMemcpy(w_out, a.wts, sizeof(float) * TK, hipMemcpyDeviceToHost), "d2h");
-            if (logits_out)
-                check_hip(hipMemcpy(logits_out, a.logits, sizeof(float) * (size_t)T * E, hipMemcpyDeviceToHost), "d2h");
-        } catch (...) {
-            for (void* p : bufs) (void)hipFree(p);
-            throw;
         }
-        for (void* p : bufs) (void)hipFree(p);
+        h.run(nullptr, nullptr, ids_out, w_out, logits_out);
     });
 }
 dsocr_status dsocr_k_moe_prefill_route(int T, int E, int topk, const float* logits, int softmax_scoring, int norm_topk,
@@ -2151,69 +2153,36 @@ static dsocr_status moe_packed_impl(int T, int H, int E, int topk, int I, int Is
         if (!dsocr::dsq_packed_ok(gu_qtype, H) || !dsocr::dsq_packed_ok(d_qtype, I) ||
             (shared && (!dsocr::dsq_packed_ok(sgu_qtype, H) || !dsocr::dsq_packed_ok(sd_qtype, Is))))
             throw std::runtime_error("EINVAL: packed experts take Q4_K (in_dim % 256 == 0) or Q8_0 (in_dim % 32 == 0) records");
-        std::vector<void*> bufs;
-        auto alloc = [&](size_t b) {
-            void* p = nullptr;
-            check_hip(hipMalloc(&p, b ? b : 16), "hipMalloc");
-            bufs.push_back(p);
-            return p;
+        MoeHookRun h(T, H, E, topk, I, x, norm_w, eps, router_f16, dsocr::WDT_F16, out, 1, norm_topk, scaling);
+        dsocr::MoeExperts& w = h.a.w;
+        auto pack = [&](int qt, const void* payload, long rows, long in_dim) {
+            void* buf = h.alloc(dsocr::dsq_packed_bytes(qt, rows, in_dim));
+            dsocr::QMat m = dsocr::dsq_packed_view(qt, buf, rows, in_dim);
+            dsocr::launch_dsq_repack(m, 0, payload, rows, in_dim, nullptr);
+            return m;
         };
-        try {
-            const int TK = T * topk;
-            auto pack = [&](int qt, const void* payload, long rows, long in_dim) {
-                void* buf = alloc(dsocr::dsq_packed_bytes(qt, rows, in_dim));
-                dsocr::QMat m = dsocr::dsq_packed_view(qt, buf, rows, in_dim);
-                dsocr::launch_dsq_repack(m, 0, payload, rows, in_dim, nullptr);
-                return m;
-            };
-            dsocr::MoeDecodeArgs a;
-            a.T = T; a.H = H; a.E = E; a.topk = topk; a.I = I;
-            a.x = x; a.norm_w = norm_w; a.eps = eps; a.out = out;
-            a.router = router_f16; a.router_wdt = dsocr::WDT_F16; a.wdtype = dsocr::WDT_F16;
-            a.qWgu = pack(gu_qtype, Wgu_payload, (long)E * 2 * I, H);
-            a.qWd = pack(d_qtype, Wd_payload, (long)E * H, I);
-            if (shared) {
-                a.Is = Is;
-                a.qsWgu = pack(sgu_qtype, sWgu_payload, 2L * Is, H);
-                a.qsWd = pack(sd_qtype, sWd_payload, H, Is);
-                a.hs = (float*)alloc(sizeof(float) * (size_t)T * Is);
-            }
-            a.softmax_scoring = 1; a.norm_topk = norm_topk; a.scaling = scaling;
-            a.xn = (float*)alloc(sizeof(float) * (size_t)T * H);
-            a.xn_router = (float*)alloc(sizeof(float) * (size_t)T * H);
-            a.logits = (float*)alloc(sizeof(float) * (size_t)T * E);
-            a.ids = (int*)alloc(sizeof(int) * TK);
-            a.wts = (float*)alloc(sizeof(float) * TK);
-            a.h = (float*)alloc(sizeof(float) * (size_t)TK * I);
-            a.grp = (int*)alloc(sizeof(int) * dsocr::moe_grp_ints(E, T, topk));
-            a.route_cnt = (int*)alloc(sizeof(int) * 16);
-            check_hip(hipMemset(a.route_cnt, 0, sizeof(int) * 16), "hipMemset");
-            if (q8) a.q8_ws = alloc(dsocr::moe_qdot_ws_bytes(T, topk, H, I, a.Is));
-            const char* gu = nullptr;
-            dsocr::moe_decode_kernel_names(a, &gu, nullptr);
-            if (std::string(gu) != (q8 ? "moe_gateup_qdot_kernel" : "moe_gateup_q_kernel"))
-                throw std::runtime_error("EINVAL: packed decode MoE outside its range");
-            dsocr::launch_moe_decode(a, nullptr);
-            check_hip(hipGetLastError(), "moe launch");
-            check_hip(hipDeviceSynchronize(), "moe");
-            if (ids_out) check_hip(hipMemcpy(ids_out, a.ids, sizeof(int) * TK, hipMemcpyDeviceToHost), "d2h");
-            if (w_out) check_hip(hipMemcpy(w_out, a.wts, sizeof(float) * TK, hipMemcpyDeviceToHost), "d2h");
-            if (q8) {
-                dsocr::Q8Planes qx, qh, qhs;
-                dsocr::moe_qdot_planes(a.q8_ws, T, topk, H, I, a.Is, &qx, &qh, &qhs);
-                auto copy_out = [&](const dsocr::Q8Planes& p, int qt, long rows, long in_dim, int8_t* codes, float* d) {
-                    if (codes) check_hip(hipMemcpy(codes, p.q, (size_t)rows * in_dim, hipMemcpyDeviceToHost), "d2h");
-                    if (d) check_hip(hipMemcpy(d, p.d, sizeof(float) * rows * (in_dim / (qt == dsocr::DSQ_Q4K ? 256 : 32)), hipMemcpyDeviceToHost), "d2h");
-                };
-                copy_out(qx, gu_qtype, T, H, q8->xn_codes, q8->xn_d);
-                copy_out(qh, d_qtype, TK, I, q8->h_codes, q8->h_d);
-                if (shared) copy_out(qhs, sd_qtype, T, Is, q8->hs_codes, q8->hs_d);
-            }
-        } catch (...) {
-            for (void* p : bufs) (void)hipFree(p);
-            throw;
+        w.q_gu = pack(gu_qtype, Wgu_payload, (long)E * 2 * I, H);
+        w.q_d = pack(d_qtype, Wd_payload, (long)E * H, I);
+        if (shared) {
+            w.Is = Is;
+            w.q_sgu = pack(sgu_qtype, sWgu_payload, 2L * Is, H);
+            w.q_sd = pack(sd_qtype, sWd_payload, H, Is);
         }
-        for (void* p : bufs) (void)hipFree(p);
+        w.int8dot = q8 != nullptr;
+        const dsocr::MoeGateUp want = q8 ? dsocr::MoeGateUp::Qdot : dsocr::MoeGateUp::Q;
+        h.run(&want, "EINVAL: packed decode MoE outside its range", ids_out, w_out, nullptr);
+        if (q8) {
+            const int TK = T * topk;
+            dsocr::Q8Planes qx, qh, qhs;
+            dsocr::moe_qdot_planes(h.a.q8_ws, T, topk, H, I, w.Is, &qx, &qh, &qhs);
+            auto copy_out = [&](const dsocr::Q8Planes& p, int qt, long rows, long in_dim, int8_t* codes, float* d) {
+                if (codes) check_hip(hipMemcpy(codes, p.q, (size_t)rows * in_dim, hipMemcpyDeviceToHost), "d2h");
+                if (d) check_hip(hipMemcpy(d, p.d, sizeof(float) * rows * (in_dim / (qt == dsocr::DSQ_Q4K ? 256 : 32)), hipMemcpyDeviceToHost), "d2h");
+            };
+            copy_out(qx, gu_qtype, T, H, q8->xn_codes, q8->xn_d);
+            copy_out(qh, d_qtype, TK, I, q8->h_codes, q8->h_d);
+            if (shared) copy_out(qhs, sd_qtype, T, Is, q8->hs_codes, q8->hs_d);
+        }
     });
 }
 dsocr_status dsocr_k_moe_packed(int T, int H, int E, int topk, int I, int Is, const float* x, const float* norm_w,
@@ -2297,71 +2266,32 @@ static dsocr_status k_moe_fp8(bool mm, int T, int H, int E, int topk, int I, int
         const bool shared = sWgu_f16 && sWd_f16 && Is > 0;
         if (!dsocr::fp8_rows_ok(H) || !dsocr::fp8_rows_ok(I) || (shared && !dsocr::fp8_rows_ok(Is)))
             throw std::runtime_error("EINVAL: FP8 experts take widths that are multiples of 16");
-        std::vector<void*> bufs;
-        auto alloc = [&](size_t b) {
-            void* p = nullptr;
-            check_hip(hipMalloc(&p, b ? b : 16), "hipMalloc");
-            bufs.push_back(p);
-            return p;
+        MoeHookRun h(T, H, E, topk, I, x, norm_w, eps, router_f16, dsocr::WDT_F16, out, 1, norm_topk, scaling);
+        dsocr::MoeExperts& w = h.a.w;
+        auto quantise = [&](const void* m16, long rows, long cols) {
+            dsocr::F8Mat m;
+            uint8_t* q = (uint8_t*)h.alloc((size_t)rows * cols);
+            int8_t* e = (int8_t*)h.alloc((size_t)rows);
+            dsocr::launch_fp8_quantize_rows(rows, cols, m16, q, e, nullptr);
+            m.q = q; m.e = e;
+            if (mm && dsocr::fp8_tile_ok(cols) && rows % 16 == 0) {
+                uint8_t* t = (uint8_t*)h.alloc(dsocr::fp8_tile_bytes(rows, cols));
+                dsocr::launch_fp8_tile_order(rows, cols, q, t, nullptr);
+                m.t = t;
+            }
+            return m;
         };
-        try {
-            const int TK = T * topk;
-            auto quantise = [&](const void* w, long rows, long cols) {
-                dsocr::F8Mat m;
-                uint8_t* q = (uint8_t*)alloc((size_t)rows * cols);
-                int8_t* e = (int8_t*)alloc((size_t)rows);
-                dsocr::launch_fp8_quantize_rows(rows, cols, w, q, e, nullptr);
-                m.q = q; m.e = e;
-                if (mm && dsocr::fp8_tile_ok(cols) && rows % 16 == 0) {
-                    uint8_t* t = (uint8_t*)alloc(dsocr::fp8_tile_bytes(rows, cols));
-                    dsocr::launch_fp8_tile_order(rows, cols, q, t, nullptr);
-                    m.t = t;
-                }
-                return m;
-            };
-            dsocr::MoeDecodeArgs a;
-            a.T = T; a.H = H; a.E = E; a.topk = topk; a.I = I;
-            a.x = x; a.norm_w = norm_w; a.eps = eps; a.out = out;
-            a.router = router_f16; a.router_wdt = dsocr::WDT_F16; a.wdtype = dsocr::WDT_F16;
-            a.Wgu = Wgu_f16; a.Wd = Wd_f16;
-            a.f8Wgu = quantise(Wgu_f16, (long)E * 2 * I, H);
-            a.f8Wd = quantise(Wd_f16, (long)E * H, I);
-            if (shared) {
-                a.Is = Is; a.sWgu = sWgu_f16; a.sWd = sWd_f16;
-                a.f8sWgu = quantise(sWgu_f16, 2L * Is, H);
-                a.f8sWd = quantise(sWd_f16, H, Is);
-                a.hs = (float*)alloc(sizeof(float) * (size_t)T * Is);
-            }
-            a.softmax_scoring = 1; a.norm_topk = norm_topk; a.scaling = scaling;
-            a.xn = (float*)alloc(sizeof(float) * (size_t)T * H);
-            a.xn_router = (float*)alloc(sizeof(float) * (size_t)T * H);
-            a.logits = (float*)alloc(sizeof(float) * (size_t)T * E);
-            a.ids = (int*)alloc(sizeof(int) * TK);
-            a.wts = (float*)alloc(sizeof(float) * TK);
-            a.h = (float*)alloc(sizeof(float) * (size_t)TK * I);
-            a.grp = (int*)alloc(sizeof(int) * dsocr::moe_grp_ints(E, T, topk));
-            a.route_cnt = (int*)alloc(sizeof(int) * 16);
-            check_hip(hipMemset(a.route_cnt, 0, sizeof(int) * 16), "hipMemset");
-            if (mm) {
-                a.f8mm_any_T = true;
-                a.dn_part = (float*)alloc(sizeof(float) * dsocr::moe_down_mm_part_floats(E, T, topk, I, a.Is, H));
-                a.dn_tick = (int*)alloc(sizeof(int) * ((size_t)H / 64 + 1));
-                check_hip(hipMemset(a.dn_tick, 0, sizeof(int) * ((size_t)H / 64 + 1)), "hipMemset");
-            }
-            const char* gu = nullptr;
-            dsocr::moe_decode_kernel_names(a, &gu, nullptr);
-            if (std::string(gu) != (mm ? "moe_gateup_f8mm_kernel" : "moe_gateup_f8_kernel"))
-                throw std::runtime_error("EINVAL: FP8 decode MoE outside its range");
-            dsocr::launch_moe_decode(a, nullptr);
-            check_hip(hipGetLastError(), "moe launch");
-            check_hip(hipDeviceSynchronize(), "moe");
-            if (ids_out) check_hip(hipMemcpy(ids_out, a.ids, sizeof(int) * TK, hipMemcpyDeviceToHost), "d2h");
-            if (w_out) check_hip(hipMemcpy(w_out, a.wts, sizeof(float) * TK, hipMemcpyDeviceToHost), "d2h");
-        } catch (...) {
-            for (void* p : bufs) (void)hipFree(p);
-            throw;
+        w.gu = Wgu_f16; w.d = Wd_f16;
+        w.f8_gu = quantise(Wgu_f16, (long)E * 2 * I, H);
+        w.f8_d = quantise(Wd_f16, (long)E * H, I);
+        if (shared) {
+            w.Is = Is; w.sgu = sWgu_f16; w.sd = sWd_f16;
+            w.f8_sgu = quantise(sWgu_f16, 2L * Is, H);
+            w.f8_sd = quantise(sWd_f16, H, Is);
         }
-        for (void* p : bufs) (void)hipFree(p);
+        h.a.f8mm_any_T = mm;  // (its down launch meets through the dn_part / dn_tick workspaces at every T)
+        const dsocr::MoeGateUp want = mm ? dsocr::MoeGateUp::F8mm : dsocr::MoeGateUp::F8;
+        h.run(&want, "EINVAL: FP8 decode MoE outside its range", ids_out, w_out, nullptr);
     });
 }
 dsocr_status dsocr_k_moe_fp8(int T, int H, int E, int topk, int I, int Is, const float* x, const float* norm_w, float eps,
@@ -2427,41 +2357,64 @@ dsocr_status dsocr_k_moe_kernels(int T, int H, int E, int topk, int I, int Is, i
                                  const char** down) {
     return guarded([&] {
         dsocr::MoeDecodeArgs a;
-        a.T = T; a.H = H; a.E = E; a.topk = topk; a.I = I; a.Is = Is;
+        dsocr::MoeExperts& w = a.w;
+        a.T = T; a.H = H; a.E = E; a.topk = topk; a.I = I; w.Is = Is;
         int dummy = 0;
         float fd = 0.f;
         a.x = &fd; a.out = &fd; a.norm_w = has_norm ? &fd : nullptr;
-        if (Is > 0) { a.sWgu = &dummy; a.sWd = &dummy; a.hs = &fd; }
+        if (Is > 0) { w.sgu = &dummy; w.sd = &dummy; a.hs = &fd; }
         a.xn = a.xn_router = a.logits = a.wts = a.h = &fd;
         a.ids = a.grp = a.route_cnt = &dummy;
         if (T >= 3 && T <= 8) { a.dn_part = &fd; a.dn_tick = &dummy; }
         // the engine keeps fragment-ordered expert copies (Engine::ensure_mm_weights)
-        a.Wgu_swz = a.Wd_swz = &dummy;
-        if (Is > 0) a.sWgu_swz = a.sWd_swz = &dummy;
+        w.gu_swz = w.d_swz = &dummy;
+        if (Is > 0) w.sgu_swz = w.sd_swz = &dummy;
         if (T > 8) { a.eoff = a.arow = a.apos = a.active = a.n_active = &dummy; a.aw = &fd; }
         dsocr::moe_decode_kernel_names(a, gateup, down);
     });
 }
 dsocr_status dsocr_k_moe_route_kind(int T, int H, int E, int topk, int I, int Is, int has_norm, const char** kind) {
+    if (!kind) return guarded([] { throw std::runtime_error("EINVAL: NULL argument"); });
+    // the arguments dsocr_k_moe_ex builds for f16 weights (which workspaces and fragment-ordered copies exist)
+    return dsocr_k_moe_plan(DSOCR_MOE_FORM_FP16, T, H, E, topk, I, Is, has_norm, kind, nullptr, nullptr);
+}
+dsocr_status dsocr_k_moe_plan(int form, int T, int H, int E, int topk, int I, int Is, int has_norm, const char** route,
+                              const char** gateup, const char** down) {
     return guarded([&] {
-        if (!kind) throw std::runtime_error("EINVAL: NULL argument");
-        // the arguments dsocr_k_moe_ex builds for f16 weights (which workspaces and fragment-ordered copies exist)
+        if (form < DSOCR_MOE_FORM_FP16 || form > DSOCR_MOE_FORM_FP8_MM) throw std::runtime_error("EINVAL: unknown expert form");
         dsocr::MoeDecodeArgs a;
+        dsocr::MoeExperts& w = a.w;
         a.T = T; a.H = H; a.E = E; a.topk = topk; a.I = I;
         int dummy = 0;
         float fd = 0.f;
         a.x = &fd; a.out = &fd; a.norm_w = has_norm ? &fd : nullptr;
-        a.router = a.Wgu = a.Wd = &dummy;
-        if (Is > 0) { a.Is = Is; a.sWgu = &dummy; a.sWd = &dummy; a.hs = &fd; }
+        a.router = w.gu = w.d = &dummy;
+        if (Is > 0) { w.Is = Is; w.sgu = &dummy; w.sd = &dummy; a.hs = &fd; }
         a.xn = a.xn_router = a.logits = a.wts = a.h = &fd;
         a.ids = a.grp = a.route_cnt = &dummy;
-        if (H % 32 == 0 && I % 32 == 0 && T <= 8) {
-            a.Wgu_swz = a.Wd_swz = &dummy;
-            if (Is > 0 && Is % 32 == 0) a.sWgu_swz = a.sWd_swz = &dummy;
+        if (form == DSOCR_MOE_FORM_FP16 && H % 32 == 0 && I % 32 == 0 && T <= 8) {
+            w.gu_swz = w.d_swz = &dummy;
+            if (Is > 0 && Is % 32 == 0) w.sgu_swz = w.sd_swz = &dummy;
+        }
+        // a reduced-byte form sits beside the fp16 tables, without fragment-ordered copies, as in a loaded engine
+        if (form == DSOCR_MOE_FORM_Q4K || form == DSOCR_MOE_FORM_Q8_0 || form == DSOCR_MOE_FORM_PACKED_INT8_DOT) {
+            dsocr::QMat m;
+            m.q = m.d = &dummy; m.qtype = form == DSOCR_MOE_FORM_Q8_0 ? dsocr::DSQ_Q8_0 : dsocr::DSQ_Q4K;
+            w.q_gu = w.q_d = m;
+            if (Is > 0) w.q_sgu = w.q_sd = m;
+            if (form == DSOCR_MOE_FORM_PACKED_INT8_DOT) { w.int8dot = true; a.q8_ws = &dummy; }
+        }
+        if (form == DSOCR_MOE_FORM_FP8 || form == DSOCR_MOE_FORM_FP8_MM) {
+            dsocr::F8Mat m;
+            m.q = (const uint8_t*)&dummy; m.e = (const int8_t*)&dummy;
+            if (form == DSOCR_MOE_FORM_FP8_MM) m.t = m.q;
+            w.f8_gu = w.f8_d = m;
+            if (Is > 0) w.f8_sgu = w.f8_sd = m;
         }
         if (T >= 3 && T <= 8) { a.dn_part = &fd; a.dn_tick = &dummy; }
         if (T > 8) { a.eoff = a.arow = a.apos = a.active = a.n_active = &dummy; a.aw = &fd; }
-        *kind = dsocr::moe_decode_route_kind(a);
+        if (route) *route = dsocr::moe_decode_route_kind(a);
+        dsocr::moe_decode_kernel_names(a, gateup, down);
     });
 }
 dsocr_status dsocr_k_lmhead_screened(int B, int V, int K, const float* x, const float* norm_w, float eps,

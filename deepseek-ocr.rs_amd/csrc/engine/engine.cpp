@@ -12,6 +12,7 @@
 #include <functional>
 #include <sstream>
 
+#include "../../../include/dsocr.h"
 #include "../common/host_util.hpp"
 #include "dsq.hpp"
 #include "host_ops.hpp"
@@ -243,21 +244,26 @@ void* Engine::ws(const std::string& name0, size_t bytes) {
     return p;
 }
 
+Engine::LoadOptions Engine::decode_load_flags(uint32_t f, int dtype, const std::string& snapshot_path) {
+    constexpr uint32_t kPacked = DSOCR_LOAD_PACKED_EXPERTS | DSOCR_LOAD_PACKED_INT8_DOT;
+    constexpr uint32_t kFp8 = DSOCR_LOAD_FP8_EXPERTS | DSOCR_LOAD_FP8_EXPERTS_MM;
+    if (f & ~(kPacked | kFp8 | DSOCR_LOAD_KV_F16)) throw std::runtime_error("EINVAL: unknown load flags");
+    LoadOptions o;
+    o.kv_f16 = (f & DSOCR_LOAD_KV_F16) != 0;
+    // the matrix-core form runs on the FP8 tables, the integer-dot form on the packed ones
+    o.fp8 = (f & DSOCR_LOAD_FP8_EXPERTS_MM) ? 2 : (f & DSOCR_LOAD_FP8_EXPERTS) ? 1 : 0;
+    o.packed = (f & DSOCR_LOAD_PACKED_INT8_DOT) ? 2 : (f & DSOCR_LOAD_PACKED_EXPERTS) ? 1 : 0;
+    if (o.fp8 && o.packed) throw std::runtime_error("EINVAL: FP8 experts cannot be combined with packed snapshot experts");
+    if (o.fp8 && dtype != 1) throw std::runtime_error("EINVAL: FP8 experts quantise the fp16 engine's weights: use dtype f16");
+    if (o.packed && snapshot_path.empty())
+        throw std::runtime_error("EINVAL: packed experts need a .dsq snapshot (snapshot_path)");
+    return o;
+}
+
 Engine::Engine(const std::string& config_path, const std::string& weights_path, int device, int dtype, uint64_t seed,
                const std::string& snapshot_path, uint32_t load_flags)
     : device_(device), dtype_(dtype) {
-    if (load_flags & ~31u) throw std::runtime_error("EINVAL: unknown load flags");
-    kv_f16_ = (load_flags & 16u) != 0;
-    if (load_flags & 8u) load_flags |= 4u;  // the matrix-core form runs on the FP8 tables
-    fp8_mm_ = (load_flags & 8u) != 0;
-    if ((load_flags & 4u) && (load_flags & 3u))
-        throw std::runtime_error("EINVAL: FP8 experts cannot be combined with packed snapshot experts");
-    if ((load_flags & 4u) && dtype != 1) throw std::runtime_error("EINVAL: FP8 experts quantise the fp16 engine's weights: use dtype f16");
-    fp8_experts_ = (load_flags & 4u) != 0;
-    if (load_flags & 2u) load_flags |= 1u;  // the integer-dot form runs on the packed tables
-    packed_mode_ = (load_flags & 2u) ? 2 : (int)(load_flags & 1u);
-    if ((load_flags & 1u) && snapshot_path.empty())
-        throw std::runtime_error("EINVAL: packed experts need a .dsq snapshot (snapshot_path)");
+    opts_ = decode_load_flags(load_flags, dtype, snapshot_path);
     int n = 0;
     HIP_CHECK(hipGetDeviceCount(&n));
     if (device < 0 || device >= n) throw std::runtime_error("EDEVICE: no HIP device with ordinal " + std::to_string(device));
@@ -279,8 +285,8 @@ Engine::Engine(const std::string& config_path, const std::string& weights_path, 
         throw std::runtime_error("EINVAL: .dsq snapshots load as fp16 (dequant-on-load): use dtype f16");
     if (!snapshot_path.empty() && cfg_.variant == VARIANT_OCR2)
         throw std::runtime_error("EINVAL: .dsq snapshots are not supported for DeepSeek-OCR-2 configs (load the checkpoint without snapshot_path)");
-    load_weights(weights_path, seed, snapshot_path, (load_flags & 1u) != 0);
-    if (fp8_experts_ && cfg_.variant == VARIANT_OCR2) {
+    load_weights(weights_path, seed, snapshot_path, opts_.packed != 0);
+    if (opts_.fp8 && cfg_.variant == VARIANT_OCR2) {
         size_t fl = 0;
         fp8_info(&fl, nullptr, nullptr);
         if (!fl) throw std::runtime_error("EINVAL: FP8 experts: no MoE layer of this DeepSeek-OCR-2 decoder fits the FP8 kernels");
@@ -445,7 +451,7 @@ void Engine::packed_info(size_t* packed_layers, size_t* moe_layers, size_t* pack
     for (const DecLayer& d : layers_) {
         if (!d.moe) continue;
         ++ml;
-        if (d.packed) { ++pl; pb += d.packed_bytes; }
+        if (d.ex.packed()) { ++pl; pb += d.packed_bytes; }
     }
     if (packed_layers) *packed_layers = pl;
     if (moe_layers) *moe_layers = ml;
@@ -457,7 +463,7 @@ void Engine::fp8_info(size_t* fp8_layers, size_t* moe_layers, size_t* fp8_bytes)
     for (const DecLayer& d : layers_) {
         if (!d.moe) continue;
         ++ml;
-        if (d.fp8) { ++fl; fb += d.fp8_bytes; }
+        if (d.ex.fp8()) { ++fl; fb += d.fp8_bytes; }
     }
     if (fp8_layers) *fp8_layers = fl;
     if (moe_layers) *moe_layers = ml;
@@ -752,16 +758,18 @@ void Engine::load_weights(const std::string& path, uint64_t seed, const std::str
                 std::copy(w.data.begin(), w.data.end(), dn.data.begin() + (size_t)e * H * I);
                 gu.dt = dn.dt = g.dt;
             }
-            d.e_gu = up16(gu);
-            d.e_d = up16(dn);
-            d.e_wdt = gu.dt;
+            void* e_gu = up16(gu);  // (FP8 experts round these in place, below)
+            void* e_d = up16(dn);
+            MoeExperts& ex = d.ex;
+            ex.gu = e_gu; ex.d = e_d; ex.wdtype = gu.dt;
             if (L.n_shared > 0) {
                 const int Is = I * L.n_shared;
                 d.has_shared = true;
                 d.s_gu = lin_cat({lp + "mlp.shared_experts.gate_proj", lp + "mlp.shared_experts.up_proj"}, {Is, Is}, H);
                 d.s_d = lin(lp + "mlp.shared_experts.down_proj", H, Is, true);
+                ex.sgu = d.s_gu.W; ex.sd = d.s_d.W; ex.Is = Is;
             }
-            if (packed_experts && d.e_wdt == WDT_F16 && dec_route_grp_ok(8, E, H, L.topk)) {
+            if (packed_experts && ex.wdtype == WDT_F16 && dec_route_grp_ok(8, E, H, L.topk)) {
                 // every routed and shared record Q4_K / Q8_0 (one dtype per matrix role): keep the blocks; any
                 // other layer runs the fp16 kernels
                 std::vector<std::string> gu_n, dn_n;
@@ -779,14 +787,13 @@ void Engine::load_weights(const std::string& path, uint64_t seed, const std::str
                 if (ok && d.has_shared)
                     ok = !d.s_gu.b && !d.s_d.b && records_qtype(sgu_n, Is, H) >= 0 && records_qtype(sdn_n, H, Is) >= 0;
                 if (ok) {
-                    pack_records(gu_n, I, H, d.q_gu, d.packed_bytes);
-                    pack_records(dn_n, H, I, d.q_d, d.packed_bytes);
+                    pack_records(gu_n, I, H, ex.q_gu, d.packed_bytes);
+                    pack_records(dn_n, H, I, ex.q_d, d.packed_bytes);
                     if (d.has_shared) {
-                        pack_records(sgu_n, Is, H, d.q_sgu, d.packed_bytes);
-                        pack_records(sdn_n, H, Is, d.q_sd, d.packed_bytes);
+                        pack_records(sgu_n, Is, H, ex.q_sgu, d.packed_bytes);
+                        pack_records(sdn_n, H, Is, ex.q_sd, d.packed_bytes);
                     }
-                    d.packed = true;
-                    d.int8dot = packed_mode_ == 2;
+                    ex.int8dot = opts_.packed == 2;
                 }
             }
             // FP8 experts (DSOCR_LOAD_FP8_EXPERTS): E4M3 codes and a row exponent beside the fp16 tables, for the
@@ -794,7 +801,7 @@ void Engine::load_weights(const std::string& path, uint64_t seed, const std::str
             // runs the fp16 kernels.  The fp16 tables of an FP8 layer then hold W8 (an fp16 tensor), so prefill and
             // batches above 8 run on the weights the FP8 launches stream.
             const int Is8 = d.has_shared ? d.s_d.K : 0;
-            if (fp8_experts_ && d.e_wdt == WDT_F16 && dec_route_grp_ok(8, E, H, L.topk) && H % 16 == 0 && I % 16 == 0 &&
+            if (opts_.fp8 && ex.wdtype == WDT_F16 && dec_route_grp_ok(8, E, H, L.topk) && H % 16 == 0 && I % 16 == 0 &&
                 Is8 % 16 == 0 && (!d.has_shared || (d.s_gu.wdt == WDT_F16 && d.s_d.wdt == WDT_F16 && !d.s_gu.b && !d.s_d.b))) {
                 auto quantise = [&](void* w, long rows, long cols, F8Mat& out) {
                     const size_t codes = ((size_t)rows * cols + 15) & ~(size_t)15, exps = ((size_t)rows + 15) & ~(size_t)15;
@@ -805,30 +812,29 @@ void Engine::load_weights(const std::string& path, uint64_t seed, const std::str
                     launch_fp8_dequant_rows(rows, cols, out, w, stream_);
                     d.fp8_bytes += codes + exps;
                 };
-                quantise(d.e_gu, (long)E * 2 * I, H, d.f8_gu);
-                quantise(d.e_d, (long)E * H, I, d.f8_d);
+                quantise(e_gu, (long)E * 2 * I, H, ex.f8_gu);
+                quantise(e_d, (long)E * H, I, ex.f8_d);
                 if (d.has_shared) {
-                    quantise(d.s_gu.W, 2L * Is8, H, d.f8_sgu);
-                    quantise(d.s_d.W, H, Is8, d.f8_sd);
+                    quantise(d.s_gu.W, 2L * Is8, H, ex.f8_sgu);
+                    quantise(d.s_d.W, H, Is8, ex.f8_sd);
                 }
                 // DSOCR_LOAD_FP8_EXPERTS_MM: the tile-ordered copies the matrix-core form streams at 3..8 tokens
                 // (decode_f8mm.hip), for the layers whose widths are whole 64-code steps
-                if (fp8_mm_ && H % 64 == 0 && I % 64 == 0 && Is8 % 64 == 0 && H <= 1536 && I <= 1024) {
+                if (opts_.fp8 == 2 && H % 64 == 0 && I % 64 == 0 && Is8 % 64 == 0 && H <= 1536 && I <= 1024) {
                     auto tile_order = [&](long rows, long cols, F8Mat& m) {
                         uint8_t* t = (uint8_t*)dev_alloc(fp8_tile_bytes(rows, cols));
                         launch_fp8_tile_order(rows, cols, m.q, t, stream_);
                         m.t = t;
                         d.fp8_bytes += fp8_tile_bytes(rows, cols);
                     };
-                    tile_order((long)E * 2 * I, H, d.f8_gu);
-                    tile_order((long)E * H, I, d.f8_d);
+                    tile_order((long)E * 2 * I, H, ex.f8_gu);
+                    tile_order((long)E * H, I, ex.f8_d);
                     if (d.has_shared) {
-                        tile_order(2L * Is8, H, d.f8_sgu);
-                        tile_order(H, Is8, d.f8_sd);
+                        tile_order(2L * Is8, H, ex.f8_sgu);
+                        tile_order(H, Is8, ex.f8_sd);
                     }
                 }
                 HIP_CHECK(hipStreamSynchronize(stream_));
-                d.fp8 = true;
             }
         }
         layers_.push_back(d);
@@ -1246,10 +1252,10 @@ void Engine::layer_forward_prefill(int l, int T, int B, const int* row_page, con
     // (a session prefills one page into its own slot of the session cache: kv_page0_)
     // (f16 cache: the layer's f32 rows go to a one-layer scratch every layer reuses - the prefill's own attention
     // reads them - and rope_kv stores the rounded rows into the cache beside)
-    if (kv_f16_ && (past || chunk_attn || kv_page0_ || kv_pages_))
+    if (opts_.kv_f16 && (past || chunk_attn || kv_page0_ || kv_pages_))
         throw std::runtime_error("EINTERNAL: the f16 KV cache serves no session, prefix or chunked prefill");
-    float* kc = kv_f16_ ? kv_scratch_k_ : kc_ + (long)l * layer_kv(B) + (long)kv_page0_ * page_stride_;
-    float* vc = kv_f16_ ? kv_scratch_v_ : vc_ + (long)l * layer_kv(B) + (long)kv_page0_ * page_stride_;
+    float* kc = opts_.kv_f16 ? kv_scratch_k_ : kc_ + (long)l * layer_kv(B) + (long)kv_page0_ * page_stride_;
+    float* vc = opts_.kv_f16 ? kv_scratch_v_ : vc_ + (long)l * layer_kv(B) + (long)kv_page0_ * page_stride_;
 
     launch_rmsnorm(X, H, XN, H, T, H, d.in_norm.w, L.rms_eps, st);
     linear(XN, T, H, d.qkv, QKV, QKVN);
@@ -1257,7 +1263,7 @@ void Engine::layer_forward_prefill(int l, int T, int B, const int* row_page, con
     r.qkv = QKV; r.ld = QKVN; r.rows = T; r.row_page = row_page; r.row_pos = row_pos;
     r.heads = L.heads; r.kv_heads = L.kv_heads; r.hd = hd; r.rope_dim = L.rope_dim; r.use_mla = L.use_mla;
     r.cos = rope_cos_; r.sin = rope_sin_; r.kc = kc; r.vc = vc; r.page_stride = page_stride_; r.head_stride = head_stride_;
-    if (kv_f16_) { r.kc16 = kc16_ + (long)l * layer_kv(B); r.vc16 = vc16_ + (long)l * layer_kv(B); }
+    if (opts_.kv_f16) { r.kc16 = kc16_ + (long)l * layer_kv(B); r.vc16 = vc16_ + (long)l * layer_kv(B); }
     launch_rope_kv(r, st);
     if (past) {
         // behind a cached past (a page prefix entry): seq_len counts the new rows, row_pos starts at the past
@@ -1329,14 +1335,14 @@ void Engine::layer_forward_prefill(int l, int T, int B, const int* row_page, con
     float* HH = wsf("d_ehh", (size_t)TK * I);
     float* Y = wsf("d_ey", (size_t)TK * H);
     GemmArgs g1;
-    g1.M = TK; g1.N = 2 * I; g1.K = H; g1.A = XN; g1.lda = H; g1.a_rows = AROW; g1.W = d.e_gu; g1.ldw = H;
-    g1.wdtype = d.e_wdt; g1.w_group_stride = (long)2 * I * H; g1.C = G; g1.ldc = 2 * I;
+    g1.M = TK; g1.N = 2 * I; g1.K = H; g1.A = XN; g1.lda = H; g1.a_rows = AROW; g1.W = d.ex.gu; g1.ldw = H;
+    g1.wdtype = d.ex.wdtype; g1.w_group_stride = (long)2 * I * H; g1.C = G; g1.ldc = 2 * I;
     g1.group_off = EOFF; g1.groups = E; g1.max_group_rows = T;
     launch_gemm(g1, st);
     flops_acc_ += 2.0 * TK * (2.0 * I) * H + 2.0 * TK * (double)H * I;  // routed gate/up + down (next launch)
     launch_silu_mul(G, 2 * I, I, TK, HH, I, st);
     GemmArgs g2;
-    g2.M = TK; g2.N = H; g2.K = I; g2.A = HH; g2.lda = I; g2.W = d.e_d; g2.ldw = I; g2.wdtype = d.e_wdt;
+    g2.M = TK; g2.N = H; g2.K = I; g2.A = HH; g2.lda = I; g2.W = d.ex.d; g2.ldw = I; g2.wdtype = d.ex.wdtype;
     g2.w_group_stride = (long)H * I; g2.C = Y; g2.ldc = H; g2.group_off = EOFF; g2.groups = E; g2.max_group_rows = T;
     launch_gemm(g2, st);
     float* YS = nullptr;
@@ -1369,43 +1375,28 @@ static bool mm_swz_off() {
 MoeDecodeArgs Engine::moe_args(int l, int B, float* X) {
     const LangConfig& L = cfg_.lang;
     DecLayer& d = layers_[l];
-    const int H = L.hidden, E = L.n_routed, K = L.topk, I = L.moe_inter, TK = B * K;
+    const int H = L.hidden, E = L.n_routed, K = L.topk, I = L.moe_inter;
     MoeDecodeArgs a;
     a.T = B; a.H = H; a.E = E; a.topk = K; a.I = I;
     a.x = X; a.norm_w = d.post_norm.w; a.eps = L.rms_eps; a.out = X;
     a.router = d.router.W; a.router_wdt = d.router.wdt; a.router_bias = d.router.b;
-    a.Wgu = d.e_gu; a.Wd = d.e_d; a.wdtype = d.e_wdt;
-    if (d.has_shared) {
-        if (d.s_gu.wdt != d.e_wdt) throw std::runtime_error("EINTERNAL: shared/routed expert dtype mismatch");
-        a.Is = d.s_d.K; a.sWgu = d.s_gu.W; a.sWd = d.s_d.W; a.hs = wsf("s_shh", (size_t)B * a.Is);
-    }
+    if (d.has_shared && d.s_gu.wdt != d.ex.wdtype) throw std::runtime_error("EINTERNAL: shared/routed expert dtype mismatch");
+    a.w = d.ex;
+    if (!router_swz_off()) a.router_swz = d.router_swz;
     a.softmax_scoring = L.scoring == "softmax"; a.norm_topk = L.norm_topk; a.scaling = L.routed_scaling;
-    a.xn = wsf("s_xn", (size_t)B * H);
-    a.xn_router = wsf("s_xn_router", (size_t)B * H);
-    a.logits = wsf("s_log", (size_t)B * E);
-    a.ids = wsi("s_ids", TK); a.wts = wsf("s_wts", TK);
-    a.h = wsf("s_ehh", (size_t)TK * I);
-    a.grp = wsi("s_grp", moe_grp_ints(E, B, K));
-    a.route_cnt = rows_.route_cnt;
-    if (B >= 3 && B <= 8) {  // matrix-core grouped kernels: down partials + tickets
-        a.dn_part = wsf("s_dnpart", moe_down_mm_part_floats(E, B, K, I, a.Is, H));
-        a.dn_tick = rows_.dn_tick;  // one ticket per 64-row tile
-    }
-    if (B <= 8 && d.packed) {  // the packed decode kernels (decode_q.hip)
-        a.qWgu = d.q_gu; a.qWd = d.q_d; a.qsWgu = d.q_sgu; a.qsWd = d.q_sd;
-        if (d.int8dot) a.q8_ws = ws("s_q8", moe_qdot_ws_bytes(B, K, H, I, a.Is));
-    }
-    if (B <= 8 && d.fp8) {  // the FP8 decode kernels (decode_f8.hip)
-        a.f8Wgu = d.f8_gu; a.f8Wd = d.f8_d; a.f8sWgu = d.f8_sgu; a.f8sWd = d.f8_sd;
-    }
-    if (B <= 8 && d.e_gu_swz && (!d.has_shared || d.s_gu_swz)) {  // fragment-ordered experts
-        a.Wgu_swz = d.e_gu_swz; a.Wd_swz = d.e_d_swz; a.sWgu_swz = d.s_gu_swz; a.sWd_swz = d.s_d_swz;
-        if (!router_swz_off()) a.router_swz = d.router_swz;
-    }
-    if (B > 8) {
-        a.eoff = wsi("s_eoff", E + 1); a.arow = wsi("s_arow", TK); a.apos = wsi("s_apos", TK);
-        a.aw = wsf("s_aw", TK); a.active = wsi("s_active", E); a.n_active = wsi("s_nact", 1);
-    }
+    const MoeWorkspaces n = moe_workspaces(B, E, K, H, I, a.w.Is, a.w.packed() && a.w.int8dot);
+    auto f = [&](const char* name, size_t count) { return count ? wsf(name, count) : nullptr; };
+    auto i = [&](const char* name, size_t count) { return count ? wsi(name, count) : nullptr; };
+    a.xn = f("s_xn", n.xn); a.xn_router = f("s_xn_router", n.xn_router); a.logits = f("s_log", n.logits);
+    a.ids = i("s_ids", n.ids); a.wts = f("s_wts", n.wts);
+    a.h = f("s_ehh", n.h); a.hs = f("s_shh", n.hs);
+    a.grp = i("s_grp", n.grp);
+    a.route_cnt = rows_.route_cnt;  // the tickets live with the decode rows (reserve_decode_rows zeroes them)
+    a.dn_part = f("s_dnpart", n.dn_part);
+    if (n.dn_tick) a.dn_tick = rows_.dn_tick;
+    if (n.q8_ws) a.q8_ws = ws("s_q8", n.q8_ws);
+    a.eoff = i("s_eoff", n.eoff); a.arow = i("s_arow", n.arow); a.apos = i("s_apos", n.apos);
+    a.aw = f("s_aw", n.aw); a.active = i("s_active", n.active); a.n_active = i("s_nact", n.n_active);
     return a;
 }
 
@@ -1424,7 +1415,7 @@ DecAttn2Args Engine::attn_args(int l, int B, int Lmax, int copy) {
     da.qkv = rows_.qkv[copy]; da.ld = QKVN; da.kv_pos = rows_.kv_pos; da.B = B;
     da.heads = L.heads; da.kv_heads = L.kv_heads; da.hd = hd; da.rope_dim = L.rope_dim; da.use_mla = L.use_mla;
     da.max_len = Lmax; da.cos = rope_cos_; da.sin = rope_sin_;
-    if (!kv_f16_) { da.kc = kc_ + (long)l * layer_kv; da.vc = vc_ + (long)l * layer_kv; }
+    if (!opts_.kv_f16) { da.kc = kc_ + (long)l * layer_kv; da.vc = vc_ + (long)l * layer_kv; }
     da.page_stride = page_stride_; da.head_stride = head_stride_;
     da.scale = (float)(1.0 / std::sqrt((double)hd));
     da.part = rows_.part[copy];
@@ -1454,10 +1445,10 @@ bool Engine::persist_ok(int B, int Lmax) {
     // opt-in (DSOCR_PERSIST=1, read per generate): measured slower than the per-layer launch chain on MI355X
     // (43.5 vs 33.5 us per layer), kept as the A/B of the persistent-layer design
     const char* e = getenv("DSOCR_PERSIST");
-    if (!e || atoi(e) == 0 || kv_f16_) return false;  // (the persistent launch reads an f32 cache)
+    if (!e || atoi(e) == 0 || opts_.kv_f16) return false;  // (the persistent launch reads an f32 cache)
     const LangConfig& L = cfg_.lang;
     for (const DecLayer& d : layers_)
-        if (d.packed || d.fp8) return false;  // the persistent launch streams the fp16 experts only
+        if (d.ex.reduced()) return false;  // the persistent launch streams the fp16 experts only
     if (B != 1 || L.use_mla || L.rope_dim != L.head_dim || L.v_head_dim != L.head_dim || L.n_shared <= 0 ||
         L.topk_method != "greedy" || L.hidden_act != "silu")
         return false;
@@ -1467,7 +1458,7 @@ bool Engine::persist_ok(int B, int Lmax) {
     for (const DecLayer& d : layers_) {
         if (d.qkv.wdt != WDT_F16 || d.qkv.b || d.o.wdt != WDT_F16 || d.o.b) return false;
         if (d.moe) {
-            if (!d.router.W || d.router.wdt != WDT_F16 || d.e_wdt != WDT_F16 || !d.has_shared || d.s_gu.wdt != WDT_F16 ||
+            if (!d.router.W || d.router.wdt != WDT_F16 || d.ex.wdtype != WDT_F16 || !d.has_shared || d.s_gu.wdt != WDT_F16 ||
                 d.s_d.wdt != WDT_F16 || d.s_gu.b || d.s_d.b)
                 return false;
         } else if (!d.gu.W || d.gu.wdt != WDT_F16 || d.down.wdt != WDT_F16) {
@@ -1496,7 +1487,7 @@ void Engine::ensure_persist() {
             if (!d.e_dT) {
                 d.e_dT = dev_alloc((size_t)E * I * H * 2);
                 for (int e = 0; e < E; ++e)
-                    launch_transpose16((const uint16_t*)d.e_d + (size_t)e * H * I, (uint16_t*)d.e_dT + (size_t)e * I * H, H, I,
+                    launch_transpose16((const uint16_t*)d.ex.d + (size_t)e * H * I, (uint16_t*)d.e_dT + (size_t)e * I * H, H, I,
                                        stream_);
             }
             const int Is = d.s_d.K;
@@ -1506,7 +1497,7 @@ void Engine::ensure_persist() {
             }
             w.router = (const uint16_t*)d.router.W;
             w.router_bias = d.router.b;
-            w.e_gu = (const uint16_t*)d.e_gu;
+            w.e_gu = (const uint16_t*)d.ex.gu;
             w.e_dT = (const uint16_t*)d.e_dT;
             w.s_gu = (const uint16_t*)d.s_gu.W;
             w.s_dT = (const uint16_t*)d.s_dT;
@@ -1609,7 +1600,7 @@ void Engine::decode_step(int B, int Lmax) {
     // and cleans the other copy only behind a launch that handed its refill on
     std::vector<char> defer_l(L.layers, 0);
     // (f16 cache: no fused one-page launch - the projection, then launch_dec_attn_kv16)
-    const bool fused_ok = qkv_attn_fused() && !kv_f16_;
+    const bool fused_ok = qkv_attn_fused() && !opts_.kv_f16;
     if (one_page && fused_ok && att_refill_defer() && !(step_skip_ & SKIP_ATTN))
         for (int l = 0; l < L.layers; ++l) {
             DecGemvArgs g; DecRopeEpi re; DecAttn2Args da;
@@ -1656,7 +1647,7 @@ void Engine::decode_step(int B, int Lmax) {
             launch_dec_gemv(g, st);
         }
         if (!attn_done && !(step_skip_ & SKIP_ATTN))
-            stamped(SPAN_ATTN, l, [&] { kv_f16_ ? launch_dec_attn_kv16(attn_args_kv16(da, l), st) : launch_dec_attn(da, st); }, nullptr, 0);
+            stamped(SPAN_ATTN, l, [&] { opts_.kv_f16 ? launch_dec_attn_kv16(attn_args_kv16(da, l), st) : launch_dec_attn(da, st); }, nullptr, 0);
         // o_proj + residual
         DecGemvArgs go;
         go.M = B; go.N = H; go.K = L.heads * hd; go.x = CTX; go.ldx = H; go.W = d.o.W; go.ldw = go.K;
@@ -1777,17 +1768,18 @@ void Engine::ensure_mm_weights(int B) {
         if (!d.moe) swz(d.gu, d.gu_swz);
     }
     for (DecLayer& d : layers_) {
-        if (!d.moe || d.packed || d.fp8 || d.e_gu_swz || d.e_wdt != WDT_F16 || H % 32 || I % 32) continue;
-        d.e_gu_swz = dev_alloc(mm_swizzle_elems(E * 2 * I, H) * 2);
-        launch_mm_swizzle(d.e_gu, E * 2 * I, H, d.e_gu_swz, stream_);
-        d.e_d_swz = dev_alloc(mm_swizzle_elems(E * H, I) * 2);
-        launch_mm_swizzle(d.e_d, E * H, I, d.e_d_swz, stream_);
+        MoeExperts& ex = d.ex;
+        if (!d.moe || ex.reduced() || ex.gu_swz || ex.wdtype != WDT_F16 || H % 32 || I % 32) continue;
+        auto copy = [&](const void* w, int rows, int cols) {
+            void* out = dev_alloc(mm_swizzle_elems(rows, cols) * 2);
+            launch_mm_swizzle(w, rows, cols, out, stream_);
+            return out;
+        };
+        ex.gu_swz = copy(ex.gu, E * 2 * I, H);
+        ex.d_swz = copy(ex.d, E * H, I);
         if (d.has_shared && d.s_gu.wdt == WDT_F16) {
-            const int Is = d.s_d.K;
-            d.s_gu_swz = dev_alloc(mm_swizzle_elems(2 * Is, H) * 2);
-            launch_mm_swizzle(d.s_gu.W, 2 * Is, H, d.s_gu_swz, stream_);
-            d.s_d_swz = dev_alloc(mm_swizzle_elems(H, Is) * 2);
-            launch_mm_swizzle(d.s_d.W, H, Is, d.s_d_swz, stream_);
+            ex.sgu_swz = copy(ex.sgu, 2 * ex.Is, H);
+            ex.sd_swz = copy(ex.sd, H, ex.Is);
         }
         if (d.router.W && d.router.wdt == WDT_F16 && E % 16 == 0) {
             d.router_swz = dev_alloc(mm_swizzle_elems(E, H) * 2);
@@ -1912,12 +1904,12 @@ void Engine::reserve_decode_rows(const DecodeRowsSpec& spec) {
     head_stride_ = (long)r.Lcap * L.head_dim;
     page_stride_ = (long)L.kv_heads * head_stride_;
     const size_t kv_floats = (size_t)L.layers * S * page_stride_;
-    const size_t kv_eb = kv_f16_ ? 2 : 4;
+    const size_t kv_eb = opts_.kv_f16 ? 2 : 4;
     void* kcv = ws("kv_k", kv_floats * kv_eb);
     void* vcv = ws("kv_v", kv_floats * kv_eb);
-    kc_ = kv_f16_ ? nullptr : (float*)kcv; vc_ = kv_f16_ ? nullptr : (float*)vcv;
-    kc16_ = kv_f16_ ? (uint16_t*)kcv : nullptr; vc16_ = kv_f16_ ? (uint16_t*)vcv : nullptr;
-    if (kv_f16_) {
+    kc_ = opts_.kv_f16 ? nullptr : (float*)kcv; vc_ = opts_.kv_f16 ? nullptr : (float*)vcv;
+    kc16_ = opts_.kv_f16 ? (uint16_t*)kcv : nullptr; vc16_ = opts_.kv_f16 ? (uint16_t*)vcv : nullptr;
+    if (opts_.kv_f16) {
         kv_scratch_k_ = wsf("kv_k_f32", (size_t)S * page_stride_);
         kv_scratch_v_ = wsf("kv_v_f32", (size_t)S * page_stride_);
     }
@@ -1933,8 +1925,10 @@ void Engine::reserve_decode_rows(const DecodeRowsSpec& spec) {
     };
     // the step-wide words: the arrival tickets (every launch leaves them zero) and the fused kernels' give-up flag
     r.attn_cnt = ints("s_attn_cnt", (size_t)S * L.heads, true);
-    r.route_cnt = ints("s_route_cnt", 16, true);
-    r.dn_tick = ints("s_dntick", (size_t)H / 64 + 1, true);
+    // (the MoE tickets: sized by the decode MoE's workspace plan at one token; they do not grow with the token count)
+    const MoeWorkspaces mw = moe_workspaces(1, L.n_routed, L.topk, H, L.moe_inter, 0, false);
+    r.route_cnt = ints("s_route_cnt", mw.route_cnt, true);
+    r.dn_tick = ints("s_dntick", mw.dn_tick, true);
     r.d_tick = ints("s_dtick", dec_mm_splitk_ticks(H), true);
     r.err = ints("s_err", 4, true);
     // the hand-off copies: the attention records of `rows` pages, or of whichever n <= rows needs the most
@@ -3110,7 +3104,7 @@ static RowParams resolve_row_params(const GenParams& p) {
 }
 
 void Engine::session_open(int S, int max_context, const GenParams& p, const SessionFeatures& feat) {
-    if (kv_f16_) throw std::runtime_error(kKvF16NoSession);
+    if (opts_.kv_f16) throw std::runtime_error(kKvF16NoSession);
     if (sess_) throw std::runtime_error("EINVAL: a decode session is already open on this engine");
     if (S < 1 || S > 8) throw std::runtime_error("EINVAL: a session has 1..8 slots");
     if (!p.use_cache || p.trace) throw std::runtime_error("EINVAL: a session decodes with the K/V cache and without a logits trace");
@@ -3835,7 +3829,7 @@ void Engine::time_launches(KernelProfile& kp, int n, const std::function<void(in
 }
 
 void Engine::kv_info(int* elem_bytes, size_t* cache_bytes) const {
-    const size_t eb = kv_f16_ ? 2 : 4;
+    const size_t eb = opts_.kv_f16 ? 2 : 4;
     if (elem_bytes) *elem_bytes = (int)eb;
     if (cache_bytes) *cache_bytes = 2 * (size_t)cfg_.lang.layers * rows_.S * page_stride_ * eb;
 }
@@ -3864,14 +3858,14 @@ Engine::DecodeProfile Engine::profile_decode(int iters) {
     // the replays rewrite the K / V slot of pos - 1 in every layer (the attention replays from the scratch
     // row): keep those slots and put them back after the attention replays and at the end, so the
     // step-graph replays and any later use of the engine state see the cache the generate left
-    const size_t eb = kv_f16_ ? 2 : 4;  // the cache's element size
+    const size_t eb = opts_.kv_f16 ? 2 : 4;  // the cache's element size
     const size_t slot_w = (size_t)hd * eb, n_slots = (size_t)L.layers * B * 2;
     char* kv_saved = (char*)ws("p_kv_saved", n_slots * L.kv_heads * slot_w);
     auto kv_slots = [&](bool restore) {
         for (int l = 0; l < L.layers; ++l)
             for (int b = 0; b < B; ++b)
                 for (int kv = 0; kv < 2; ++kv) {
-                    char* cache = kv_f16_ ? (char*)(kv ? vc16_ : kc16_) : (char*)(kv ? vc_ : kc_);
+                    char* cache = opts_.kv_f16 ? (char*)(kv ? vc16_ : kc16_) : (char*)(kv ? vc_ : kc_);
                     char* base = cache + ((long)l * B * page_stride_ + (long)b * page_stride_ + (long)pm1[b] * hd) * eb;
                     char* keep = kv_saved + (((size_t)l * B + b) * 2 + kv) * L.kv_heads * slot_w;
                     if (restore)
@@ -3900,32 +3894,33 @@ Engine::DecodeProfile Engine::profile_decode(int iters) {
         auto args = [&](int i) { return moe_args(moe_layers[i % moe_layers.size()], B, Xs); };
         const int n = iters * (int)moe_layers.size();
         moe_decode_kernel_names(args(0), &prof.gateup_kernel, &prof.down_kernel);
+        const MoeGateUp kind = moe_decode_gateup_kind(args(0));
         // rotating over the layers (~55 MB each) defeats the 256 MB Infinity Cache
         time_launches(prof.moe_gateup, n, [&](int i) { launch_moe_decode(args(i), st, MOE_GATEUP); });
         time_launches(prof.moe_down, n, [&](int i) { launch_moe_decode(args(i), st, MOE_DOWN); });
-        const DecLayer& d0 = layers_[moe_layers[0]];
-        const double Is = d0.has_shared ? d0.s_d.K : 0;
+        const MoeExperts& w0 = layers_[moe_layers[0]].ex;
+        const double Is = w0.Is;
         const double touched = (double)prof.experts_touched;
         prof.moe_gateup.bytes = (touched * 2.0 * I + 2.0 * Is) * H * 2.0   // fp16 gate+up rows
                                 + (double)B * H * 4 + (double)(TK * I + B * Is) * 4;  // x in, h out
         prof.moe_gateup.flops = 2.0 * (TK * 2.0 * I + B * 2.0 * Is) * H;
         prof.moe_down.bytes = (touched * I + Is) * H * 2.0 + (double)(TK * I + B * Is) * 4 + 2.0 * B * H * 4;
         prof.moe_down.flops = 2.0 * (TK * (double)I + B * Is) * H;
-        if (d0.packed && B <= 8) {
+        if (kind == MoeGateUp::Q || kind == MoeGateUp::Qdot) {
             // packed layers stream the blocks: 144 bytes per 256 weights (Q4_K), 34 per 32 (Q8_0)
             auto bpw = [](const QMat& m) { return m.qtype == DSQ_Q4K ? 144.0 / 256.0 : 34.0 / 32.0; };
-            prof.moe_gateup.bytes = (touched * 2.0 * I * bpw(d0.q_gu) + 2.0 * Is * (Is ? bpw(d0.q_sgu) : 0.0)) * H
+            prof.moe_gateup.bytes = (touched * 2.0 * I * bpw(w0.q_gu) + 2.0 * Is * (Is ? bpw(w0.q_sgu) : 0.0)) * H
                                     + (double)B * H * 4 + (double)(TK * I + B * Is) * 4;
-            prof.moe_down.bytes = (touched * I * bpw(d0.q_d) + Is * (Is ? bpw(d0.q_sd) : 0.0)) * H
+            prof.moe_down.bytes = (touched * I * bpw(w0.q_d) + Is * (Is ? bpw(w0.q_sd) : 0.0)) * H
                                   + (double)(TK * I + B * Is) * 4 + 2.0 * B * H * 4;
-            if (std::string(prof.gateup_kernel) == "moe_gateup_qdot_kernel") {
+            if (kind == MoeGateUp::Qdot) {
                 // the integer-dot form also writes and reads the code planes: 1 byte per activation, d and bs beside
                 auto planes = [](double rows, double in_dim) { return rows * (in_dim + in_dim / 32 * 6); };
                 prof.moe_gateup.bytes += 2.0 * planes(B, H);
                 prof.moe_down.bytes += 2.0 * (planes(TK, I) + planes(B, Is));
             }
         }
-        if (std::string(prof.gateup_kernel) == "moe_gateup_f8_kernel" || std::string(prof.gateup_kernel) == "moe_gateup_f8mm_kernel") {
+        if (kind == MoeGateUp::F8 || kind == MoeGateUp::F8mm) {
             // FP8 layers stream one byte per weight and one exponent byte per row
             prof.moe_gateup.bytes = (touched * 2.0 * I + 2.0 * Is) * (H + 1.0)
                                     + (double)B * H * 4 + (double)(TK * I + B * Is) * 4;
@@ -3937,7 +3932,7 @@ Engine::DecodeProfile Engine::profile_decode(int iters) {
     time_launches(prof.attention, iters * L.layers, [&](int i) {
         DecAttn2Args da = attn_args(i % L.layers, B, Lmax);
         da.qkv = qkv0; da.kv_pos = d_pos; da.o = CTX;  // (the replays rewrite the K / V slot of pos - 1 from qkv0)
-        kv_f16_ ? launch_dec_attn_kv16(attn_args_kv16(da, i % L.layers), st) : launch_dec_attn(da, st);
+        opts_.kv_f16 ? launch_dec_attn_kv16(attn_args_kv16(da, i % L.layers), st) : launch_dec_attn(da, st);
     });
     kv_slots(true);
     // K and V of every attended key (f32 cache) + q/k/v row + context out

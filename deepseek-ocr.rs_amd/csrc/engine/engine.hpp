@@ -68,29 +68,22 @@ struct DecLayer {
     Lin gu, down;                 // dense MLP (layer 0) [2I][H], [H][I]
     Lin router;                   // [E][H]
     float* router_bias = nullptr; // e_score_correction_bias
-    void* e_gu = nullptr;         // [E][2Im][H]
-    void* e_d = nullptr;          // [E][H][Im]
-    int e_wdt = WDT_F16;
+    // the experts in every form the layer keeps: fp16 [E][2Im][H] / [E][H][Im] (shared: the rows of s_gu / s_d below),
+    // the fragment-ordered copies for the 3..8-page matrix-core kernels (Engine::ensure_mm_weights), the snapshot's
+    // packed Q4_K / Q8_0 blocks (DSOCR_LOAD_PACKED_EXPERTS) and the FP8 codes (DSOCR_LOAD_FP8_EXPERTS).  moe_plan
+    // (decode_moe.hip) decides which launches stream which.
+    MoeExperts ex;
     bool has_shared = false;
     Lin s_gu, s_d;                // [2Is][H], [H][Is]
-    // fragment-ordered copies for the 3..8-page matrix-core kernels (Engine::ensure_mm_weights)
-    void* e_gu_swz = nullptr; void* e_d_swz = nullptr; void* s_gu_swz = nullptr; void* s_d_swz = nullptr;
-    void* router_swz = nullptr;  // fragment-ordered router rows (3..8 pages: the routing inside gate/up)
-    void* qkv_swz = nullptr; void* o_swz = nullptr; void* gu_swz = nullptr;  // ... q/k/v, o_proj, dense gate|up
+    // fragment-ordered copies (Engine::ensure_mm_weights): the router rows (3..8 pages: the routing inside gate/up),
+    // q/k/v, o_proj, the dense gate|up
+    void* router_swz = nullptr;
+    void* qkv_swz = nullptr; void* o_swz = nullptr; void* gu_swz = nullptr;
     // the persistent one-page decode (decode_persist.hip): down projections transposed to [inter][H] rows
     void* e_dT = nullptr;         // routed [E][Im][H]
     void* s_dT = nullptr;         // shared [Is][H] (MoE) / dense [I][H]
-    // packed experts (DSOCR_LOAD_PACKED_EXPERTS): the snapshot's Q4_K / Q8_0 blocks kept for the packed decode
-    // kernels (decode_q.hip), beside the fp16 copies above; routed [E][2Im][H], [E][H][Im], shared [2Is][H], [H][Is]
-    bool packed = false;
-    bool int8dot = false;  // DSOCR_LOAD_PACKED_INT8_DOT: the packed launches in their integer-dot form (decode_qdot.hip)
-    QMat q_gu, q_d, q_sgu, q_sd;
-    size_t packed_bytes = 0;
-    // FP8 experts (DSOCR_LOAD_FP8_EXPERTS): E4M3 codes and row exponents for the FP8 decode kernels (decode_f8.hip),
-    // beside the fp16 copies above, in their layouts
-    bool fp8 = false;
-    F8Mat f8_gu, f8_d, f8_sgu, f8_sd;
-    size_t fp8_bytes = 0;
+    size_t packed_bytes = 0;      // device bytes of ex.q_* (packed_info)
+    size_t fp8_bytes = 0;         // device bytes of ex.f8_* (fp8_info)
 };
 
 // DeepSeek-OCR-2: the Qwen2 decoder used as the vision encoder (vision/qwen2.rs)
@@ -325,11 +318,11 @@ class Engine {
     // MoE layers that kept their packed blocks / all MoE layers / device bytes of the packed tables
     void packed_info(size_t* packed_layers, size_t* moe_layers, size_t* packed_bytes) const;
     // 0 dequant-on-load, 1 packed experts (fp16-exact), 2 packed experts with integer block dots
-    int packed_mode() const { return packed_mode_; }
+    int packed_mode() const { return opts_.packed; }
     // MoE layers that run the FP8 decode kernels / all MoE layers / device bytes of the FP8 tables
     void fp8_info(size_t* fp8_layers, size_t* moe_layers, size_t* fp8_bytes) const;
     // 0 fp16 experts, 1 FP8 experts, 2 FP8 experts with the matrix-core form at 3..8 tokens
-    int fp8_mode() const { return fp8_mm_ ? 2 : fp8_experts_ ? 1 : 0; }
+    int fp8_mode() const { return opts_.fp8; }
     // KV cache: bytes per element (4, or 2 under DSOCR_LOAD_KV_F16) and the bytes of K + V of the current decode
     // rows (0 before any generate)
     void kv_info(int* elem_bytes, size_t* cache_bytes) const;
@@ -489,9 +482,14 @@ class Engine {
   private:
     // ---- loading
     void load_weights(const std::string& path, uint64_t seed, const std::string& snapshot_path, bool packed_experts);
-    int packed_mode_ = 0;
-    bool fp8_experts_ = false;
-    bool fp8_mm_ = false;  // DSOCR_LOAD_FP8_EXPERTS_MM
+    // load_flags (DSOCR_LOAD_*) decoded once, in the constructor
+    struct LoadOptions {
+        int packed = 0;       // 0 dequant-on-load, 1 packed experts, 2 packed experts with integer block dots
+        int fp8 = 0;          // 0 fp16 experts, 1 FP8 experts, 2 FP8 experts with the matrix-core form
+        bool kv_f16 = false;  // the K/V cache's element type
+    };
+    static LoadOptions decode_load_flags(uint32_t load_flags, int dtype, const std::string& snapshot_path);
+    LoadOptions opts_;
     // ---- workspace
     void* ws(const std::string& name, size_t bytes);
     float* wsf(const std::string& name, size_t n) { return (float*)ws(name, n * sizeof(float)); }
@@ -673,9 +671,8 @@ class Engine {
     // kv cache
     float* kc_ = nullptr;
     float* vc_ = nullptr;
-    // f16 cache (kv_f16_): kc16_ / vc16_ replace kc_ / vc_ (null then) at the same element strides;
+    // f16 cache (opts_.kv_f16): kc16_ / vc16_ replace kc_ / vc_ (null then) at the same element strides;
     // kv_scratch_k_ / _v_ are the one-layer f32 rows [S][kv_heads][Lcap][hd] the prefill's own attention reads
-    bool kv_f16_ = false;
     uint16_t* kc16_ = nullptr;
     uint16_t* vc16_ = nullptr;
     float* kv_scratch_k_ = nullptr;

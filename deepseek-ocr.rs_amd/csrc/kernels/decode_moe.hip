@@ -827,19 +827,7 @@ enum class Route {
     DecRouteGrp,   // topk_wave64 in the one-launch router (also the packed path)
     DecRouter,     // topk_write in dec_router's last-block epilogue
 };
-enum class GateUp {
-    Mix,         // moe_gateup_mix_kernel (T = 1)
-    Shared,      // moe_gateup_shared_kernel alone: one token through a dense / shared-only MLP (layer 0)
-    Slot,        // moe_gateup_slot_kernel, routed slots and shared blocks in one grid (T <= 2)
-    SlotShared,  // moe_gateup_slot_kernel<1> over the routed slots, then moe_gateup_shared_kernel if shared (T = 3..8)
-    Gateup2,     // moe_gateup2_kernel (sorted groups; also self-routing slots whose K is too long for the slot kernel)
-    Grp,         // moe_gateup_grp_kernel
-    Mm,          // moe_gateup_mm_kernel (decode_mm.hip); routes too under Route::InGateupMm
-    Q,           // moe_gateup_q_kernel (decode_q.hip)
-    Qdot,        // q8_quantize_kernel over xn, then moe_gateup_qdot_kernel (decode_qdot.hip)
-    F8,          // moe_gateup_f8_kernel (decode_f8.hip)
-    F8mm,        // moe_gateup_f8mm_kernel (decode_f8mm.hip)
-};
+using GateUp = MoeGateUp;  // (kernels.hpp: the profile selects its byte formula by it)
 enum class Down {
     Mix,          // moe_down_mix_kernel (T = 1)
     Slot,         // moe_down_slot_kernel (top-k 6 or 3)
@@ -1222,42 +1210,54 @@ static bool route_fused_on() {
     return !(e && atoi(e) == 0);
 }
 
-// The only place that reads the layer's shapes: T = 1 mix, T <= 2 (or no grouped form) self-routing slots, 3..8
-// grouped by expert, more than 8 sorted; packed experts (T <= 8) take the grouped packed kernels, in their
-// integer-dot form when the arguments carry the code-plane workspace; FP8 experts (T <= 8) take the grouped FP8
-// kernels where the router and the shapes fit (at 3..8 tokens their matrix-core form when the tables carry the
-// tile-ordered copies and moe_f8mm_ok holds), else the fp16 forms.
+// The only place that reads the layer's shapes and decides which of the layer's tables (MoeExperts) a launch
+// streams: T = 1 mix, T <= 2 (or no grouped form) self-routing slots, 3..8 grouped by expert (on the fragment-ordered
+// copies at T <= 8 where the layer keeps them), more than 8 sorted; packed experts (T <= 8) take the grouped packed
+// kernels, in their integer-dot form when the layer asks for it and the arguments carry the code-plane workspace;
+// FP8 experts (T <= 8) take the grouped FP8 kernels where the router and the shapes fit (at 3..8 tokens their
+// matrix-core form when the tables carry the tile-ordered copies and moe_f8mm_ok holds), else the fp16 forms.
 MoePlan moe_plan(const MoeDecodeArgs& a) {
+    const MoeExperts& w = a.w;
     const int T = a.T, E = a.E, K = a.topk, TK = T * K;
     if (T <= 0 || TK > 512 || E > 256 || K > 8 || K > E)
         throw std::runtime_error("EINVAL: decode MoE supports batch*top_k <= 512, <= 256 experts, top_k <= min(8, E)");
-    if (a.H % 8 || a.I % 8 || (a.Is && a.Is % 8)) throw std::runtime_error("EINVAL: MoE dims must be multiples of 8");
+    if (a.H % 8 || a.I % 8 || (w.Is && w.Is % 8)) throw std::runtime_error("EINVAL: MoE dims must be multiples of 8");
     MoePlan p;
     const bool fuse_norm = T <= 2;  // T > 2: the rows are normalised once (by the router launch, into xn)
     const float* mx = (fuse_norm || !a.norm_w) ? a.x : a.xn;
     const float* mnorm = fuse_norm ? a.norm_w : nullptr;
+    // the grouped down launches meet through dn_part / dn_tick at 3..8 tokens (the FP8 parity hook: at every T)
+    const bool meet = (T >= 3 && T <= 8) || a.f8mm_any_T;
+    float* dn_part = meet ? a.dn_part : nullptr;
+    int* dn_tick = meet ? a.dn_tick : nullptr;
     MoeDec2Args& m = p.m;
     m.T = T; m.K = a.H; m.Hout = a.H; m.x = mx; m.norm_w = mnorm; m.eps = a.eps; m.out = a.out;
-    m.topk = K; m.E = E; m.I = a.I; m.Wgu = a.Wgu; m.Wd = a.Wd; m.wdtype = a.wdtype; m.h = a.h; m.ids = a.ids;
-    if (a.sWgu && a.sWd && a.Is > 0) { m.Is = a.Is; m.sWgu = a.sWgu; m.sWd = a.sWd; m.hs = a.hs; }
-    m.Wgu_swz = a.Wgu_swz; m.sWgu_swz = a.sWgu_swz; m.Wd_swz = a.Wd_swz; m.sWd_swz = a.sWd_swz;
-    m.dn_part = a.dn_part; m.dn_tick = a.dn_tick; m.span = a.span; m.stamps = a.stamps;
+    m.topk = K; m.E = E; m.I = a.I; m.Wgu = w.gu; m.Wd = w.d; m.wdtype = w.wdtype; m.h = a.h; m.ids = a.ids;
+    if (w.sgu && w.sd && w.Is > 0) { m.Is = w.Is; m.sWgu = w.sgu; m.sWd = w.sd; m.hs = a.hs; }
+    const bool swz = T <= 8 && w.gu_swz;  // the fragment-ordered set (and, with it, the router's copy)
+    if (swz) { m.Wgu_swz = w.gu_swz; m.sWgu_swz = w.sgu_swz; m.Wd_swz = w.d_swz; m.sWd_swz = w.sd_swz; }
+    m.dn_part = dn_part; m.dn_tick = dn_tick; m.span = a.span; m.stamps = a.stamps;
     DecGemvArgs& gr = p.router;
     gr.M = T; gr.N = E; gr.K = a.H; gr.x = mx; gr.ldx = a.H; gr.W = a.router; gr.ldw = a.H; gr.wdtype = a.router_wdt;
     gr.bias = a.router_bias; gr.y = a.logits; gr.ldy = E; gr.norm_w = mnorm; gr.eps = a.eps; gr.span = a.route_span;
-    if (a.f8Wgu.q && T <= 8) {
-        // FP8 experts: dec_route_grp on the unquantised rows (rows -> a.xn), then the grouped FP8 gate/up and down
+    // the reduced-byte forms run behind dec_route_grp on the unquantised rows (norm + router + top-k + expert records,
+    // rows -> a.xn), then their grouped gate/up and down: the part of the arguments both share
+    auto grp_args = [&](auto& g, const auto& gu, const auto& d, const auto& sgu, const auto& sd) {
+        g.T = T; g.topk = K; g.E = E; g.H = a.H; g.I = a.I; g.slots = std::min(E, TK);
+        g.x = a.norm_w ? a.xn : a.x; g.grp = a.grp; g.Wgu = gu; g.Wd = d; g.h = a.h; g.out = a.out;
+        if (sgu.q && sd.q && w.Is > 0) { g.Is = w.Is; g.sWgu = sgu; g.sWd = sd; g.hs = a.hs; }
+        g.span = a.span;
+    };
+    const bool grp_route = T <= 8 && dec_route_grp_ok(T, E, a.H, K) && a.route_cnt && a.grp && a.xn;
+    if (w.fp8() && T <= 8) {
         MoeF8Args& f = p.f8;
-        f.T = T; f.topk = K; f.E = E; f.H = a.H; f.I = a.I; f.slots = std::min(E, TK);
-        f.x = a.norm_w ? a.xn : a.x; f.grp = a.grp; f.Wgu = a.f8Wgu; f.Wd = a.f8Wd; f.h = a.h; f.out = a.out;
-        if (a.f8sWgu.q && a.f8sWd.q && a.Is > 0) { f.Is = a.Is; f.sWgu = a.f8sWgu; f.sWd = a.f8sWd; f.hs = a.hs; }
-        f.span = a.span;
-        if (dec_route_grp_ok(T, E, a.H, K) && a.route_cnt && a.grp && a.xn && (f.Is > 0) == (m.Is > 0) && moe_f8_ok(f)) {
+        grp_args(f, w.f8_gu, w.f8_d, w.f8_sgu, w.f8_sd);
+        if (grp_route && (f.Is > 0) == (m.Is > 0) && moe_f8_ok(f)) {
             p.route = Route::DecRouteGrp;
             p.gu = GateUp::F8;
             p.dn = Down::F8;
             // 3..8 tokens from the tile-ordered copies: the matrix-core form (T = 1, 2 keep the VALU form)
-            f.dn_part = a.dn_part; f.dn_tick = a.dn_tick;
+            f.dn_part = dn_part; f.dn_tick = dn_tick;
             if ((T >= 3 || a.f8mm_any_T) && moe_f8mm_ok(f)) {
                 p.gu = GateUp::F8mm;
                 p.dn = Down::F8mm;
@@ -1265,19 +1265,14 @@ MoePlan moe_plan(const MoeDecodeArgs& a) {
             return p;
         }
     }
-    if (a.qWgu.q && T <= 8) {
-        // packed experts: dec_route_grp (norm + router + top-k + expert records, rows -> a.xn), then the
-        // grouped packed gate/up and down
+    if (w.packed() && T <= 8) {
         MoeQArgs& q = p.q;
-        q.T = T; q.topk = K; q.E = E; q.H = a.H; q.I = a.I; q.slots = std::min(E, TK);
-        q.x = a.norm_w ? a.xn : a.x; q.grp = a.grp; q.Wgu = a.qWgu; q.Wd = a.qWd; q.h = a.h; q.out = a.out;
-        if (a.qsWgu.q && a.qsWd.q && a.Is > 0) { q.Is = a.Is; q.sWgu = a.qsWgu; q.sWd = a.qsWd; q.hs = a.hs; }
-        q.span = a.span;
-        if (dec_route_grp_ok(T, E, a.H, K) && a.route_cnt && a.grp && a.xn && moe_q_ok(q)) {
+        grp_args(q, w.q_gu, w.q_d, w.q_sgu, w.q_sd);
+        if (grp_route && moe_q_ok(q)) {
             p.route = Route::DecRouteGrp;
             p.gu = GateUp::Q;
             p.dn = Down::Q;
-            if (a.q8_ws) {  // the integer-dot form where its shapes allow, else the fp16-exact packed kernels
+            if (w.int8dot && a.q8_ws) {  // the integer-dot form where its shapes allow, else the fp16-exact packed kernels
                 moe_qdot_planes(a.q8_ws, T, K, a.H, a.I, q.Is, &q.qx, &q.qh, &q.qhs);
                 if (moe_qdot_ok(q)) {
                     p.gu = GateUp::Qdot;
@@ -1286,7 +1281,7 @@ MoePlan moe_plan(const MoeDecodeArgs& a) {
             }
             return p;
         }
-        if (!a.Wgu || !a.Wd) throw std::runtime_error("EINVAL: packed decode MoE outside its range (T <= 8, E <= 64, H <= 1536)");
+        if (!w.gu || !w.d) throw std::runtime_error("EINVAL: packed decode MoE outside its range (T <= 8, E <= 64, H <= 1536)");
     }
     bool grouped = false;
     if (T >= 3 && T <= 8 && dec_router_ok(T, E, a.H, K) && a.route_cnt && a.grp) {
@@ -1299,10 +1294,10 @@ MoePlan moe_plan(const MoeDecodeArgs& a) {
         p.route = dec_route_grp_ok(T, E, a.H, K) ? Route::DecRouteGrp : Route::DecRouter;
         p.gu = moe_gateup_mm_ok(m) ? GateUp::Mm : GateUp::Grp;
         p.dn = moe_down_mm_ok(m) ? Down::Mm : Down::Grp;
-        if (p.route == Route::DecRouteGrp && p.gu == GateUp::Mm && a.norm_w && a.router_wdt == a.wdtype && route_fused_on()) {
+        if (p.route == Route::DecRouteGrp && p.gu == GateUp::Mm && a.norm_w && a.router_wdt == w.wdtype && route_fused_on()) {
             MoeDec2Args r = m;
             r.x = a.x; r.norm_w = a.norm_w; r.eps = a.eps;
-            r.router = a.router; r.router_bias = a.router_bias; r.router_swz = a.router_swz;
+            r.router = a.router; r.router_bias = a.router_bias; r.router_swz = swz ? a.router_swz : nullptr;
             r.softmax_scoring = a.softmax_scoring; r.norm_topk = a.norm_topk; r.scaling = a.scaling;
             r.ids_out = a.ids; r.w_out = a.wts; r.logits = a.logits;  // (block 0 also writes the logits)
             if (moe_gateup_mm_route_ok(r)) {
@@ -1346,6 +1341,28 @@ const char* moe_decode_route_kind(const MoeDecodeArgs& a) {
         case Route::DecRouter: return "dec_router";
     }
     return "none";
+}
+
+MoeGateUp moe_decode_gateup_kind(const MoeDecodeArgs& a) { return moe_plan(a).gu; }
+
+MoeWorkspaces moe_workspaces(int T, int E, int topk, int H, int I, int Is, bool int8dot) {
+    const size_t TK = (size_t)T * topk;
+    MoeWorkspaces n;
+    n.xn = n.xn_router = (size_t)T * H;
+    n.logits = (size_t)T * E;
+    n.ids = n.wts = TK;
+    n.h = TK * I;
+    n.hs = (size_t)T * Is;
+    n.grp = moe_grp_ints(E, T, topk);
+    n.route_cnt = 16;
+    if (T <= 8) {
+        n.dn_part = moe_down_mm_part_floats(E, T, topk, I, Is, H);
+        n.dn_tick = (size_t)H / 64 + 1;  // one ticket per 64-row tile
+        if (int8dot) n.q8_ws = moe_qdot_ws_bytes(T, topk, H, I, Is);
+    } else {
+        n.eoff = (size_t)E + 1; n.arow = n.apos = n.aw = TK; n.active = E; n.n_active = 1;
+    }
+    return n;
 }
 
 void moe_decode_kernel_names(const MoeDecodeArgs& a, const char** gateup, const char** down) {

@@ -34,6 +34,30 @@ struct F8Mat {
     const uint8_t* t = nullptr;
 };
 
+// A MoE layer's expert weights in every form the layer keeps (the one owner: DecLayer holds it, MoeDecodeArgs carries
+// it by value, moe_plan in decode_moe.hip alone decides which launches stream which tables).  The form is what is
+// set: q_gu.q the packed blocks, f8_gu.q the FP8 codes (f8_gu.t their tile-ordered copies), gu_swz the
+// fragment-ordered fp16 copies.  Routed [E][2I][H] and [E][H][I], shared [2Is][H] and [H][Is] in every form.
+struct MoeExperts {
+    const void* gu = nullptr; const void* d = nullptr;    // fp16 / bf16 routed tables (may be null beside packed ones)
+    const void* sgu = nullptr; const void* sd = nullptr;  // ... shared (or null)
+    int wdtype = WDT_F16;
+    int Is = 0;                                           // shared intermediate size (0: no shared expert)
+    // fragment-ordered copies (launch_mm_swizzle) for the matrix-core grouped kernels at 3..8 tokens; a set with the
+    // routed copies but not the shared expert's is not streamed by them (moe_gateup_mm_ok / moe_down_mm_ok)
+    const void* gu_swz = nullptr; const void* d_swz = nullptr; const void* sgu_swz = nullptr; const void* sd_swz = nullptr;
+    // packed Q4_K / Q8_0 blocks (decode_q.hip; made by launch_dsq_repack), streamed at T <= 8; int8dot: in their
+    // integer-dot form (decode_qdot.hip) where the arguments carry the code-plane workspace
+    QMat q_gu, q_d, q_sgu, q_sd;
+    bool int8dot = false;
+    // FP8 codes (decode_f8.hip), streamed at T <= 8 where moe_f8_ok holds; with the tile-ordered copies on the
+    // matrix cores at 3..8 tokens (decode_f8mm.hip)
+    F8Mat f8_gu, f8_d, f8_sgu, f8_sd;
+    bool packed() const { return q_gu.q != nullptr; }
+    bool fp8() const { return f8_gu.q != nullptr; }
+    bool reduced() const { return packed() || fp8(); }  // a reduced-byte form beside (or instead of) the fp16 tables
+};
+
 // Profiling hook: while prof_events() holds a (start, stop) pair, the next kernel launched through
 // DSOCR_LAUNCH (the decode_*.hip units, lmhead.hip) records its own dispatch begin / end into the two events
 // (hipExtLaunchKernelGGL: the dispatch-packet timestamps rocprofv3's kernel trace reports) and the
@@ -551,15 +575,11 @@ void launch_moe_down_mm(const MoeDec2Args& a, hipStream_t s);
 // out[T][H] += moe(rmsnorm(x)).  The single dispatch shared by Engine::decode_step and the
 // kernel-level entry dsocr_k_moe.  Workspaces are device buffers sized as commented.
 struct MoeDecodeArgs {
-    int T = 0, H = 0, E = 0, topk = 0, I = 0, Is = 0;
+    int T = 0, H = 0, E = 0, topk = 0, I = 0;
     const float* x = nullptr; const float* norm_w = nullptr; float eps = 0.f;  // x: [T][H] (may equal out)
     const void* router = nullptr; int router_wdt = WDT_F16; const float* router_bias = nullptr;
-    const void* Wgu = nullptr; const void* Wd = nullptr;    // [E][2I][H], [E][H][I]
-    const void* sWgu = nullptr; const void* sWd = nullptr;  // [2Is][H], [H][Is] (or null)
-    const void* Wgu_swz = nullptr; const void* sWgu_swz = nullptr;  // optional fragment-ordered copies
-    const void* Wd_swz = nullptr; const void* sWd_swz = nullptr;
-    const void* router_swz = nullptr;  // optional fragment-ordered router rows (the routing inside gate/up)
-    int wdtype = WDT_F16;
+    MoeExperts w;                      // the layer's experts, whole (w.Is: the shared intermediate size)
+    const void* router_swz = nullptr;  // optional fragment-ordered router rows (the routing inside gate/up; used with w.gu_swz)
     int softmax_scoring = 1, norm_topk = 0; float scaling = 1.f;
     float* out = nullptr;
     // workspaces
@@ -578,21 +598,25 @@ struct MoeDecodeArgs {
     unsigned long long* span = nullptr;  // launch-span slots for the gate/up and down launches (or null)
     unsigned long long* route_span = nullptr;  // launch-span slots for the router launch (or null)
     unsigned long long* stamps = nullptr;      // dev: the grouped gate/up's phase clocks (MoeDec2Args::stamps)
-    // packed experts (decode_q.hip): when qWgu.q is set and T <= 8 the gate/up and down launches decode these
-    // Q4_K / Q8_0 tables instead of streaming the fp16 matrices above (which may then be null); routed
-    // [E][2I][H] and [E][H][I], shared [2Is][H] and [H][Is], made by launch_dsq_repack
-    QMat qWgu, qWd, qsWgu, qsWd;
-    // integer-dot form of the packed launches (decode_qdot.hip): a workspace of moe_qdot_ws_bytes(T, topk, H, I, Is)
+    // integer-dot form of the packed launches (w.int8dot): a workspace of moe_qdot_ws_bytes(T, topk, H, I, Is)
     // bytes for the activation code planes; null = the fp16-exact packed kernels
     void* q8_ws = nullptr;
-    // FP8 experts (decode_f8.hip): when f8Wgu.q is set and T <= 8 the gate/up and down launches stream these E4M3
-    // tables (layouts of Wgu / Wd / sWgu / sWd, one exponent per row) where moe_f8_ok holds; else the fp16 kernels
-    F8Mat f8Wgu, f8Wd, f8sWgu, f8sWd;
-    // matrix-core form of the FP8 launches (decode_f8mm.hip): taken at 3 <= T <= 8 (f8mm_any_T: at every T <= 8, the
-    // parity hook) when the four tables carry their tile-ordered copies and moe_f8mm_ok holds; its down launch meets
-    // through dn_part / dn_tick above when both are set
+    // the FP8 matrix-core form is taken at 3 <= T <= 8; f8mm_any_T: at every T <= 8 (the parity hook).  Its down
+    // launch meets through dn_part / dn_tick above when both are set (handed on at the same T only)
     bool f8mm_any_T = false;
 };
+// Element counts of the workspaces MoeDecodeArgs points at (0: not needed at this T).  The one place that sizes
+// them: Engine::moe_args / Engine::reserve_decode_rows and the parity hooks' harness allocate by it.  route_cnt and
+// dn_tick are the tickets: zero before the first launch (every launch leaves them zero).
+struct MoeWorkspaces {
+    size_t xn = 0, xn_router = 0, logits = 0, ids = 0, wts = 0, h = 0, hs = 0;  // floats (ids: ints)
+    size_t grp = 0;                                                             // ints
+    size_t route_cnt = 0, dn_tick = 0;                                          // ints, zeroed (dn_tick: T <= 8)
+    size_t dn_part = 0;                                                         // floats (T <= 8; moe_plan: who meets there)
+    size_t q8_ws = 0;                                                           // BYTES (int8dot only)
+    size_t eoff = 0, arow = 0, apos = 0, active = 0, n_active = 0, aw = 0;      // T > 8: ints, aw floats
+};
+MoeWorkspaces moe_workspaces(int T, int E, int topk, int H, int I, int Is, bool int8dot);
 // ---- one-page decode step as ONE persistent launch (decode_persist.hip): every decoder layer inside 256 resident
 // workgroups handing their vectors over as {f32, tag} granules (tag = the decode position; the granule buffer is
 // reset to all-ones before a generate's first step and after the dry step)
@@ -645,6 +669,21 @@ enum MoeParts : int { MOE_ROUTE = 1, MOE_GATEUP = 2, MOE_DOWN = 4, MOE_ALL = 7 }
 // false when the routing runs inside the gate/up launch (3..8 tokens, DSOCR_ROUTE_FUSED): MOE_ROUTE launches nothing
 bool moe_decode_route_launch(const MoeDecodeArgs& a);
 void moe_decode_kernel_names(const MoeDecodeArgs& a, const char** gateup, const char** down);
+// the plan's gate/up choice itself, each enumerator named after the kernels that run
+enum class MoeGateUp {
+    Mix,         // moe_gateup_mix_kernel (T = 1)
+    Shared,      // moe_gateup_shared_kernel alone: one token through a dense / shared-only MLP (layer 0)
+    Slot,        // moe_gateup_slot_kernel, routed slots and shared blocks in one grid (T <= 2)
+    SlotShared,  // moe_gateup_slot_kernel<1> over the routed slots, then moe_gateup_shared_kernel if shared (T = 3..8)
+    Gateup2,     // moe_gateup2_kernel (sorted groups; also self-routing slots whose K is too long for the slot kernel)
+    Grp,         // moe_gateup_grp_kernel
+    Mm,          // moe_gateup_mm_kernel (decode_mm.hip); routes too under Route::InGateupMm
+    Q,           // moe_gateup_q_kernel (decode_q.hip)
+    Qdot,        // q8_quantize_kernel over xn, then moe_gateup_qdot_kernel (decode_qdot.hip)
+    F8,          // moe_gateup_f8_kernel (decode_f8.hip)
+    F8mm,        // moe_gateup_f8mm_kernel (decode_f8mm.hip)
+};
+MoeGateUp moe_decode_gateup_kind(const MoeDecodeArgs& a);
 // which of the routing implementations the dispatch picks (static string): "moe_gateup_mix", "moe_gateup_slot",
 // "dec_route_grp", "moe_gateup_mm" (the router inside gate/up), "dec_router", "moe_route"
 const char* moe_decode_route_kind(const MoeDecodeArgs& a);
@@ -950,14 +989,17 @@ void launch_dsq_repack(const QMat& dst, long dst_row0, const void* payload, long
 void launch_dsq_rows_dot(const QMat& m, long rows, long in_dim, int T, const float* x, float* y, hipStream_t s);
 // Packed gate/up (+ SwiGLU, routing weight folded into h) and down (+ combine + residual) for T <= 8 tokens in
 // grouped form: the expert records of the router launch (MOE_GRP_* layout), x = the normalised rows [T][H]
-struct MoeQArgs {
+template <typename Mat>
+struct MoeGrpArgs {  // what the packed (Mat = QMat) and the FP8 (F8Mat) launches share; moe_plan fills it in one place
     int T = 0, topk = 0, E = 0, H = 0, I = 0, Is = 0, slots = 0;
     const float* x = nullptr;
     const int* grp = nullptr;
-    QMat Wgu, Wd, sWgu, sWd;
+    Mat Wgu, Wd, sWgu, sWd;
     float* h = nullptr; float* hs = nullptr;   // [T*topk][I], [T][Is]
     float* out = nullptr;                      // [T][H], += combined
     unsigned long long* span = nullptr;        // launch-span slots (SPAN_SLOTS pairs) or null
+};
+struct MoeQArgs : MoeGrpArgs<QMat> {
     Q8Planes qx, qh, qhs;                      // integer-dot form only: the code planes of x, h and hs
 };
 bool moe_q_ok(const MoeQArgs& a);
@@ -986,14 +1028,7 @@ void launch_fp8_quantize_rows(long rows, long cols, const void* w_f16, uint8_t* 
 // W8 = 2^e e4m3(code) as fp16 (exact), e.g. over the rows the codes were made from
 void launch_fp8_dequant_rows(long rows, long cols, const F8Mat& m, void* w8_f16, hipStream_t s);
 void launch_fp8_rows_dot(const F8Mat& m, long rows, long cols, int T, const float* x, float* y, hipStream_t s);
-struct MoeF8Args {
-    int T = 0, topk = 0, E = 0, H = 0, I = 0, Is = 0, slots = 0;
-    const float* x = nullptr;
-    const int* grp = nullptr;
-    F8Mat Wgu, Wd, sWgu, sWd;
-    float* h = nullptr; float* hs = nullptr;   // [T*topk][I], [T][Is]
-    float* out = nullptr;                      // [T][H], += combined
-    unsigned long long* span = nullptr;        // launch-span slots (SPAN_SLOTS pairs) or null
+struct MoeF8Args : MoeGrpArgs<F8Mat> {
     // matrix-core down (decode_f8mm.hip): group partials [groups][8][H] (at least min(E, T topk) groups) and one
     // ticket per 64-row tile, zero between launches; null = one group per row tile, no workspace
     float* dn_part = nullptr; int* dn_tick = nullptr;

@@ -167,6 +167,8 @@ LOAD_KV_F16 = 16  # DSOCR_LOAD_KV_F16
 # what dsocr_session_open* answers on an engine with the f16 KV cache (the server's start-up check says the same)
 KV_F16_NO_SESSION = ("decode sessions (with page prefixes and chunked admission) need the f32 KV cache: this engine was "
                      "loaded with the f16 KV cache (DSOCR_LOAD_KV_F16)")
+# dsocr_k_moe_plan forms (DSOCR_MOE_FORM_*)
+MOE_FORM_FP16, MOE_FORM_Q4K, MOE_FORM_Q8_0, MOE_FORM_PACKED_INT8_DOT, MOE_FORM_FP8, MOE_FORM_FP8_MM = range(6)
 STREAM_CB = C.CFUNCTYPE(None, C.c_size_t, C.POINTER(C.c_int64), C.c_void_p)
 
 # every symbol include/dsocr.h declares (tests check the library exports all of them)
@@ -214,6 +216,7 @@ EXPORTS = [
     "dsocr_k_guided_mask", "dsocr_k_guided_advance",
     "dsocr_k_gemm_f32a_ex", "dsocr_k_layernorm_ex", "dsocr_k_rmsnorm_ex", "dsocr_k_sam_relbias", "dsocr_k_attention_fused",
     "dsocr_k_vision_op", "dsocr_window_maps",
+    "dsocr_k_moe_plan",
 ]
 
 # model variants behind the deepseek engine (dsocr_engine_variant)
@@ -344,6 +347,7 @@ def lib():
     L.dsocr_k_moe.argtypes = [i32, i32, i32, i32, i32, i32, vp, vp, f32, vp, vp, vp, vp, vp, i32, i32, f32, vp, vp, vp]
     L.dsocr_k_moe_ex.argtypes = L.dsocr_k_moe.argtypes + [i32, vp, vp]
     L.dsocr_k_moe_route_kind.argtypes = [i32, i32, i32, i32, i32, i32, i32, C.POINTER(C.c_char_p)]
+    L.dsocr_k_moe_plan.argtypes = [i32] * 8 + [C.POINTER(C.c_char_p)] * 3
     L.dsocr_k_moe_prefill_route.argtypes = [i32, i32, i32, vp, i32, i32, f32, vp, vp, vp, vp, vp]
     L.dsocr_k_moe_combine.argtypes = [i32, i32, i32, vp, vp, vp, vp, vp, i32]
     L.dsocr_k_sample_greedy.argtypes =[i32, i32, vp, vp, i32, vp, i32, f32, vp]

@@ -1044,6 +1044,21 @@ dsocr_status dsocr_k_moe_fp8_mm(int T, int H, int E, int topk, int I, int Is, co
  * roofline label: "moe_gateup_mix_kernel" at T = 1, "moe_gateup_grp_kernel" at T = 3..8. */
 dsocr_status dsocr_k_moe_kernels(int T, int H, int E, int topk, int I, int Is, int has_norm, const char** gateup,
                                  const char** down);
+/* The whole plan of a decode MoE layer that keeps its experts in `form`: the routing implementation (the strings of
+ * dsocr_k_moe_route_kind) and the gate/up and down kernel names (as dsocr_k_moe_kernels), any of which may be NULL.
+ * Host-only, from the arguments a loaded engine builds: the fp16 tables always, DSOCR_MOE_FORM_FP16 with the
+ * fragment-ordered copies dsocr_k_moe_ex makes, the reduced-byte forms with their tables beside the fp16 ones (Q4_K
+ * or Q8_0 blocks in all four matrices; the integer-dot form on Q4_K blocks; FP8 codes, with DSOCR_MOE_FORM_FP8_MM
+ * their tile-ordered copies).  A shape the form's kernels do not take falls back to the fp16 kernels, as in the
+ * engine.  DSOCR_EINVAL for an unknown form or a shape outside the decode MoE. */
+#define DSOCR_MOE_FORM_FP16 0
+#define DSOCR_MOE_FORM_Q4K 1
+#define DSOCR_MOE_FORM_Q8_0 2
+#define DSOCR_MOE_FORM_PACKED_INT8_DOT 3
+#define DSOCR_MOE_FORM_FP8 4
+#define DSOCR_MOE_FORM_FP8_MM 5
+dsocr_status dsocr_k_moe_plan(int form, int T, int H, int E, int topk, int I, int Is, int has_norm, const char** route,
+                              const char** gateup, const char** down);
 /* Screened greedy selection (the engine's decode head at B <= 2 without repetition penalty): the
  * int8 copy of W (bf16 [V][K], quantised as at engine load) gives every row an interval that holds
  * the exact logit, the surviving rows are rescored with the exact kernel's arithmetic; out_tok[b] =

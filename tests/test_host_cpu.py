@@ -291,6 +291,33 @@ def test_moe_dispatch_route_kinds(monkeypatch):
         assert k.value.decode() == _MOE_ROUTE_RECORDED[(fused, (E, topk), H)][T - 1], (fused, T, Is, E, topk, H)
 
 
+def test_moe_plan_by_expert_form(monkeypatch):
+    """The whole plan (routing implementation, gate/up and down kernels) for every form a layer keeps its experts in
+    (dsocr_k_moe_plan: fp16, packed Q4_K, packed Q8_0, packed + integer-dot, FP8, FP8 + tile copies), as recorded
+    in tests/golden/moe_plan_dispatch.json from the dispatch before the experts had one owner: 1, 2, 3, 8 and 9
+    tokens, with and without a shared expert, both DSOCR_ROUTE_FUSED values; the flagship shape (hidden 1280, 64 x
+    top-6 of 896), one with Q4_K-sized rows (1024), a misfit of the FP8 matrix-core form (880: no multiple of 64), a
+    misfit of Q4_K (hidden 1152: no multiple of 256) and one the grouped router does not take (128 x top-8), where
+    every reduced-byte form falls back to the fp16 kernels."""
+    import ctypes as C
+    from dsocr._lib import check, lib
+    with open(os.path.join(ROOT, "tests", "golden", "moe_plan_dispatch.json")) as f:
+        table = json.load(f)
+    assert table["columns"] == ["form", "T", "H", "E", "topk", "I", "Is", "route_fused", "route", "gateup", "down"]
+    rows = table["rows"]
+    assert {r[0] for r in rows} == set(range(6)) and {r[1] for r in rows} == {1, 2, 3, 8, 9}
+    for form, T, H, E, topk, I, Is, fused, route, gateup, down in rows:
+        monkeypatch.setenv("DSOCR_ROUTE_FUSED", str(fused))
+        r, g, d = C.c_char_p(), C.c_char_p(), C.c_char_p()
+        check(lib().dsocr_k_moe_plan(form, T, H, E, topk, I, Is, 1, C.byref(r), C.byref(g), C.byref(d)))
+        got = (r.value.decode(), g.value.decode(), d.value.decode())
+        assert got == (route, gateup, down), (form, T, H, E, topk, I, Is, fused)
+    # each reduced-byte form reaches its own kernels somewhere on the grid
+    assert {"moe_gateup_q_kernel", "moe_gateup_qdot_kernel", "moe_gateup_f8_kernel", "moe_gateup_f8mm_kernel"} <= {r[9] for r in rows}
+    k = C.c_char_p()
+    assert lib().dsocr_k_moe_plan(6, 1, 1280, 64, 6, 896, 0, 1, C.byref(k), None, None) == 1  # EINVAL: unknown form
+
+
 # (M, N, K, ldw, wdtype, norm, xn_out, swizzle) -> (kind, token rows per launch), worked out by hand from
 # dec_gemv_rb / launch_dec_gemv / mm_dispatch: rows = min(16, (64 KiB - 512 B) / (4 K)); the staged-row template
 # is 1, 2, 4, 8 or 16 by the first chunk's rows; 3..8 rows take dec_mm when K = 1280, N >= 16, ldw % 8 == 0 and no

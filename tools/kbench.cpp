@@ -161,9 +161,9 @@ static void case_moe(int T, hipStream_t s, bool route_only) {
     moe_weights();
     float* x = rand_f32((size_t)T * H);
     MoeDecodeArgs a;
-    a.T = T; a.H = H; a.E = E; a.topk = TOPK; a.I = I; a.Is = IS;
+    a.T = T; a.H = H; a.E = E; a.topk = TOPK; a.I = I; a.w.Is = IS;
     a.x = x; a.eps = 1e-6f; a.out = x;
-    a.router_wdt = WDT_F16; a.wdtype = WDT_F16;
+    a.router_wdt = WDT_F16; a.w.wdtype = WDT_F16;
     a.softmax_scoring = 1; a.norm_topk = 0; a.scaling = 1.f;
     a.xn = (float*)dalloc((size_t)T * H * 4);
     a.xn_router = (float*)dalloc((size_t)T * H * 4);
@@ -180,8 +180,8 @@ static void case_moe(int T, hipStream_t s, bool route_only) {
     }
     auto set = [&](int l) {
         const MoeLayerW& w = g_moe[l % NL];
-        a.norm_w = w.norm; a.router = w.router; a.Wgu = w.gu; a.Wd = w.d; a.sWgu = w.sgu; a.sWd = w.sd;
-        a.Wgu_swz = w.gu_s; a.sWgu_swz = w.sgu_s; a.Wd_swz = w.d_s; a.sWd_swz = w.sd_s; a.router_swz = w.router_s;
+        a.norm_w = w.norm; a.router = w.router; a.w.gu = w.gu; a.w.d = w.d; a.w.sgu = w.sgu; a.w.sd = w.sd;
+        a.w.gu_swz = w.gu_s; a.w.sgu_swz = w.sgu_s; a.w.d_swz = w.d_s; a.w.sd_swz = w.sd_s; a.router_swz = w.router_s;
     };
     const int n = 4 * NL;
     CK(hipDeviceSynchronize());  // the fills ran on the null stream; s does not wait for it
