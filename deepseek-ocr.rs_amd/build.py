@@ -23,7 +23,7 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 CLANG = os.environ.get("DSOCR_CXX", "/opt/rocm/llvm/bin/clang++")
 ARCH = "gfx950"
 
-KERNELS = ["gemm", "gemm_bf16", "moe", "norm", "attention", "misc", "decode_gemv", "decode_attn", "decode_attn16", "decode_route",
+KERNELS = ["gemm", "gemm_bf16", "moe", "norm", "attention", "misc", "decode_gemv", "decode_attn", "decode_attn16", "decode_attn_shared", "decode_route",
            "decode_moe", "decode_sample", "lmhead", "dsq", "preprocess", "sampling", "dots_ops", "attention_bf16",
            "decode_mm", "decode_persist", "decode_q", "decode_qdot", "decode_f8", "decode_f8mm", "attention_prefix", "ocr2_ops", "session",
            "decode_logprob", "attention_past", "decode_bias", "decode_stop", "decode_penalty",

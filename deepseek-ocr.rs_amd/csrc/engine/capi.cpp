@@ -2,6 +2,7 @@
 // prefixed with a status tag ("EINVAL: ...") and mapped to dsocr_status.
 #include "../../../include/dsocr.h"
 
+#include <random>
 #include <fcntl.h>
 #include <signal.h>
 #include <unistd.h>
@@ -652,6 +653,24 @@ dsocr_status dsocr_generate_batch(dsocr_engine* e, size_t n, const dsocr_request
                                   const dsocr_decode_params* params, dsocr_result* results) {
     // (NULL params: to_params' error, after the requests')
     return guarded([&] { generate_pages(e, n, reqs, params, results, GenExtras()); });
+}
+
+dsocr_status dsocr_generate_n(dsocr_engine* e, const dsocr_request* req, const dsocr_decode_params* params, size_t n,
+                              const uint64_t* seeds, dsocr_result* results) {
+    return guarded([&] {
+        if (!e || !req || !results) throw std::runtime_error("EINVAL: NULL argument");
+        if (n < 2 || n > 8) throw std::runtime_error("EINVAL: dsocr_generate_n takes 2..8 samples");
+        const dsocr::GenParams g = to_params(params);
+        uint64_t base = g.seed;
+        if (!seeds && !g.seed_set) {
+            std::random_device rd;
+            base = ((uint64_t)rd() << 32) ^ rd();
+        }
+        std::vector<uint64_t> sd(n);
+        for (size_t i = 0; i < n; ++i) sd[i] = seeds ? seeds[i] : base + i;
+        auto r = e->impl->generate_n(to_request(*req), g, (int)n, sd);
+        for (size_t i = 0; i < n; ++i) write_result(r[i], results[i]);
+    });
 }
 
 dsocr_status dsocr_generate_trace(dsocr_engine* e, size_t n, const dsocr_request* reqs,
@@ -1767,6 +1786,28 @@ dsocr_status dsocr_k_decode_attention_kv16(int B, int heads, int kv_heads, int h
         check_hip(e, "decode attention (f16 cache)");
         for (int v : left)
             if (v) throw std::runtime_error("EINTERNAL: decode attention left an arrival ticket non-zero");
+    });
+}
+dsocr_status dsocr_k_decode_attention_shared(int B, int heads, int kv_heads, int hd, int rope_dim, int max_len, float scale,
+                                             const float* qkv, const float* cos, const float* sin, float* kc, float* vc,
+                                             const int* kv_pos, int shared_len, float* o, int prerot) {
+    return guarded([&] {
+        dsocr::DecAttnSharedArgs a;
+        a.qkv = qkv; a.ld = (long)(heads + 2 * kv_heads) * hd; a.kv_pos = kv_pos; a.B = B; a.heads = heads;
+        a.kv_heads = kv_heads; a.hd = hd; a.rope_dim = rope_dim; a.use_mla = 0; a.max_len = max_len;
+        a.cos = cos; a.sin = sin; a.kc = kc; a.vc = vc; a.head_stride = (long)max_len * hd;
+        a.page_stride = (long)kv_heads * max_len * hd; a.scale = scale; a.o = o;
+        a.o_ld = (long)heads * hd; a.prerot = prerot != 0; a.shared_len = shared_len;
+        if (!dsocr::dec_attn_shared_ok(a)) throw std::runtime_error("EINVAL: bad shared-prompt decode attention shape");
+        std::vector<int> pos(B);
+        check_hip(hipMemcpy(pos.data(), kv_pos, sizeof(int) * B, hipMemcpyDeviceToHost), "hipMemcpy");
+        for (int p : pos)
+            if (p < shared_len || p >= max_len) throw std::runtime_error("EINVAL: kv_pos outside [shared_len, max_len)");
+        check_hip(hipMalloc(&a.part, dsocr::dec_attn_shared_workspace(B, heads, hd, max_len, shared_len)), "hipMalloc");
+        dsocr::launch_dec_attn_shared(a, nullptr);
+        const hipError_t e = hipDeviceSynchronize();
+        (void)hipFree(a.part);
+        check_hip(e, "decode attention (shared prompt)");
     });
 }
 // The one body of the three prefill-attention hooks below: the plan and the views of Engine::forward_rows /

@@ -1433,6 +1433,14 @@ DecAttnKv16Args Engine::attn_args_kv16(const DecAttn2Args& da, int l) {
     return k;
 }
 
+// the shared-prompt form of a layer's arguments (launch_dec_attn_shared; generate_n reserved shared_part_)
+DecAttnSharedArgs Engine::attn_args_shared(const DecAttn2Args& da) {
+    DecAttnSharedArgs k;
+    static_cast<DecAttn2Args&>(k) = da;
+    k.shared_len = shared_len_; k.part = shared_part_;
+    return k;
+}
+
 // DSOCR_NO_GRAPH=1 (read per generate and per profile section): the decode step's kernels launched eagerly
 // instead of replayed from a hipGraph (rocprofv3 kernel tracing of graph replays is unreliable on this stack;
 // kernel durations are unchanged)
@@ -1647,7 +1655,10 @@ void Engine::decode_step(int B, int Lmax) {
             launch_dec_gemv(g, st);
         }
         if (!attn_done && !(step_skip_ & SKIP_ATTN))
-            stamped(SPAN_ATTN, l, [&] { opts_.kv_f16 ? launch_dec_attn_kv16(attn_args_kv16(da, l), st) : launch_dec_attn(da, st); }, nullptr, 0);
+            stamped(SPAN_ATTN, l, [&] {
+                if (shared_len_) launch_dec_attn_shared(attn_args_shared(da), st);
+                else opts_.kv_f16 ? launch_dec_attn_kv16(attn_args_kv16(da, l), st) : launch_dec_attn(da, st);
+            }, nullptr, 0);
         // o_proj + residual
         DecGemvArgs go;
         go.M = B; go.N = H; go.K = L.heads * hd; go.x = CTX; go.ldx = H; go.W = d.o.W; go.ldw = go.K;
@@ -2392,6 +2403,7 @@ struct Engine::GenState {
     std::vector<std::vector<std::pair<int, long>>> img;  // per page: (kind, index) of every <image> slot
     std::vector<std::vector<int>> extra;                 // per page: the tokens a forward without cache appends
     std::vector<int> kvpos, kvlen;                       // first decode position / cache length of every page
+    const std::vector<uint64_t>* row_seeds = nullptr;    // generate_n: the seed of every row (else p.seed for all)
     PinnedBuffer<int> pin;  // poll(): [done | output length | last token] x B
     int streamed = 0;       // tokens the stream callback has seen
     size_t steps = 0;
@@ -2466,6 +2478,70 @@ std::vector<std::vector<int64_t>> Engine::generate(const std::vector<GenRequest>
     }
     if (p.use_cache) decode_cached(g);
     else decode_uncached(g);
+    return collect_outputs(g);
+}
+
+// n samples of one page: generate's phases with vision and prefill on the one request (page 0 of the cache) and the
+// decode rows, their sampling state and the decode loop on n copies of it.  The prefill's logits row is copied to
+// every row, so each row's first token is selected from the same logits by its own RNG row; the decode steps run in
+// shared-prompt mode (decode_step's attention launch), which the guard clears on every exit.  Rows [0, P) of pages
+// 1 .. n - 1 stay allocated and unused.
+std::vector<std::vector<int64_t>> Engine::generate_n(const GenRequest& rq, const GenParams& p, int n,
+                                                     const std::vector<uint64_t>& seeds) {
+    if (sess_) throw std::runtime_error("EINVAL: a decode session is open on this engine (close it before generate)");
+    if (n < 2 || n > 8 || (int)seeds.size() != n) throw std::runtime_error("EINVAL: generate_n takes 2..8 samples and one seed each");
+    if (opts_.kv_f16) throw std::runtime_error("EINVAL: generate_n needs the f32 KV cache (engine loaded with DSOCR_LOAD_KV_F16)");
+    if (!p.use_cache || p.trace || p.lp_k >= 0)
+        throw std::runtime_error("EINVAL: generate_n needs the K/V cache (use_cache = 1), no logits trace and no log-probabilities");
+    const char* pe = getenv("DSOCR_PERSIST");
+    if (pe && atoi(pe) != 0) throw std::runtime_error("EINVAL: generate_n does not combine with the persistent decode step (DSOCR_PERSIST)");
+    if (cfg_.lang.use_mla) throw std::runtime_error("EINVAL: generate_n does not serve MLA configs");
+    if (rq.ctl.active()) throw std::runtime_error("EINVAL: generate_n takes no per-request controls");
+    timings_ = Timings();
+    timings_.pages = 1;
+    last_lp_ = LogprobRows();
+    last_stop_hits_.clear();
+    last_guided_.clear();
+    if (p.max_new == 0) return std::vector<std::vector<int64_t>>(n);
+    ensure_small(64);
+    const std::vector<GenRequest> one(1, rq), rows(n, rq);
+    GenState g1(one, p, nullptr, nullptr), g(rows, p, nullptr, nullptr);
+    ScopedSet idle_chain(chain_active_, false);
+    ScopedSet idle_rec(span_rec_, nullptr);
+    ScopedSet idle_step(span_step_, nullptr);
+    ScopedSet idle_slots(span_slots_, nullptr);
+    ScopedSet idle_trace(trace_, nullptr);
+    hipStream_t st = stream_;
+    HIP_CHECK(hipEventRecord(g.ev[0], st));
+    flops_acc_ = 0;
+    embed_pages(g1);
+    HIP_CHECK(hipEventRecord(g.ev[1], st));
+    timings_.vision_flops = flops_acc_;
+    plan_image_rows(g1);
+    const int P = g1.prompt_len[0];
+    g.prompt_len.assign(n, P);
+    g.max_p = P;
+    g.row_seeds = &seeds;
+    // (the cache holds n pages per layer from the prefill on, though the prefill itself runs one page)
+    ScopedSet pages(kv_pages_, n);
+    reset_decode_state(g);
+    const LangConfig& L = cfg_.lang;
+    DecAttnSharedArgs probe = attn_args_shared(attn_args(0, n, rows_.Lcap));
+    probe.shared_len = P;
+    if (!dec_attn_shared_ok(probe)) throw std::runtime_error("EINVAL: generate_n: no shared-prompt attention kernel for this model shape");
+    // the records of the shared-prompt attention, before any capture
+    shared_part_ = (float*)ws("s_part_shared", dec_attn_shared_workspace(n, L.heads, L.head_dim, rows_.Lcap, P));
+    HIP_CHECK(hipEventRecord(g.ev[2], st));
+    flops_acc_ = 0;
+    forward_rows(g1, g1.prompt_len);
+    for (int b = 1; b < n; ++b)
+        HIP_CHECK(hipMemcpyAsync(rows_.logits + (size_t)b * L.vocab, rows_.logits, sizeof(float) * L.vocab, hipMemcpyDeviceToDevice, st));
+    init_sampling(g);
+    HIP_CHECK(hipEventRecord(g.ev[3], st));
+    timings_.prefill_flops = flops_acc_;
+    g.pin = PinnedBuffer<int>(3 * g.B + 1);
+    ScopedSet shared(shared_len_, P);
+    decode_cached(g);
     return collect_outputs(g);
 }
 
@@ -2772,6 +2848,10 @@ void Engine::init_sampling(GenState& g) {
         const std::vector<uint32_t> rng = rng_state_from_u64(seed);
         std::vector<uint32_t> all((size_t)B * RNG_WORDS);
         for (int b = 0; b < B; ++b) memcpy(&all[(size_t)b * RNG_WORDS], rng.data(), sizeof(uint32_t) * RNG_WORDS);
+        for (int b = 0; g.row_seeds && b < B; ++b) {
+            const std::vector<uint32_t> own = rng_state_from_u64((*g.row_seeds)[b]);
+            memcpy(&all[(size_t)b * RNG_WORDS], own.data(), sizeof(uint32_t) * RNG_WORDS);
+        }
         upload_to(r.rng, "s_rng", all);
     }
     // penalty (applied in place to the logits when != 1) + fused greedy selection

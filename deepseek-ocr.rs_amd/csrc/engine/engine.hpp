@@ -338,6 +338,10 @@ class Engine {
     // batched generate; returns generated ids per page
     std::vector<std::vector<int64_t>> generate(const std::vector<GenRequest>& reqs, const GenParams& p, TokenCb cb,
                                                void* user);
+    // n samples (2..8) of one page: vision and prefill once, n decode rows that share the prompt's
+    // K/V in page 0 (launch_dec_attn_shared); sample i draws from seeds[i]; each stops at its own EOS
+    std::vector<std::vector<int64_t>> generate_n(const GenRequest& rq, const GenParams& p, int n,
+                                                 const std::vector<uint64_t>& seeds);
     Timings last_timings() const { return timings_; }
     // the log-probability entries of the last generate with p.lp_k >= 0: per page n[b] entries (one per emitted id,
     // same index) of rows [b][cap]: lp, and [b][cap][K]: top_id / top_lp
@@ -533,6 +537,7 @@ class Engine {
     MoeDecodeArgs moe_args(int l, int B, float* X);
     DecAttn2Args attn_args(int l, int B, int Lmax, int copy = 0);
     DecAttnKv16Args attn_args_kv16(const DecAttn2Args& da, int l);
+    DecAttnSharedArgs attn_args_shared(const DecAttn2Args& da);
     // the decode rows: reserved under their workspace names and initialised (tickets and flag zeroed, hand-offs
     // sentinel-filled) by the one function that knows their sizes
     DecodeRows rows_;
@@ -724,6 +729,10 @@ class Engine {
         return span_rec_ + ((size_t)kind * cfg_.lang.layers + layer) * span_cap_ * 4;
     }
     long trace_steps_ = 0;
+    // shared-prompt mode (generate_n sets it for its decode steps, a guard clears it): the rows of a step share keys
+    // [0, shared_len_) of page 0 and decode_step's attention launch is launch_dec_attn_shared on shared_part_
+    int shared_len_ = 0;
+    float* shared_part_ = nullptr;
     bool persist_active_ = false;               // this generate's decode steps run dec_persist
     PersistLayerW* persist_lw_ = nullptr;       // device [layers]
     unsigned long long* persist_g_ = nullptr;   // granules [dec_persist_granules(layers)]

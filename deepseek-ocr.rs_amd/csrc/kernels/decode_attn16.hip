@@ -32,18 +32,6 @@ __device__ __forceinline__ uint32_t f16_rne_clamp(float x) {
     return b;
 }
 
-// one step of the transposing butterfly: the n values of v halve, lane bit BIT choosing the half this lane keeps
-// and the DPP row operation CTRL naming the partner (opposite BIT, same higher bits)
-template <int CTRL, int BIT, int N>
-__device__ __forceinline__ void bfly(float* v, int lane) {
-    const bool up = (lane & BIT) != 0;
-#pragma unroll
-    for (int j = 0; j < N / 2; ++j) {
-        const float keep = up ? v[j + N / 2] : v[j], send = up ? v[j] : v[j + N / 2];
-        v[j] = keep + dpp_f<CTRL>(0.f, send);
-    }
-}
-constexpr int DPP_ROW_ROR8 = 0x128;  // lane l of a 16-lane row reads lane l ^ 8
 }  // namespace
 
 template <int HD, bool PREROT>

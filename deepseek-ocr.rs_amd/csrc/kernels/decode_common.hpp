@@ -172,6 +172,19 @@ __device__ __forceinline__ void ld_x8(const float* xs, float* o) {
     o[0] = a.x; o[1] = a.y; o[2] = a.z; o[3] = a.w; o[4] = b.x; o[5] = b.y; o[6] = b.z; o[7] = b.w;
 }
 
+// one step of the transposing butterfly: the n values of v halve, lane bit BIT choosing the half this lane keeps
+// and the DPP row operation CTRL naming the partner (opposite BIT, same higher bits)
+template <int CTRL, int BIT, int N>
+__device__ __forceinline__ void bfly(float* v, int lane) {
+    const bool up = (lane & BIT) != 0;
+#pragma unroll
+    for (int j = 0; j < N / 2; ++j) {
+        const float keep = up ? v[j + N / 2] : v[j], send = up ? v[j] : v[j + N / 2];
+        v[j] = keep + dpp_f<CTRL>(0.f, send);
+    }
+}
+constexpr int DPP_ROW_ROR8 = 0x128;  // lane l of a 16-lane row reads lane l ^ 8
+
 inline size_t stage_bytes(int M, int K) { return sizeof(float) * (XS_RED + (size_t)M * K); }
 constexpr size_t STAGE_LDS_MAX = 64 * 1024;
 

@@ -464,6 +464,19 @@ struct DecAttnKv16Args : DecAttn2Args {
 // dec_attn_workspace, a.counters zero between launches; no sentinel is read or written).  Any B, hd 32 / 64 / 128,
 // heads % kv_heads == 0, prerot or not, max_len <= 512 * 128.
 void launch_dec_attn_kv16(const DecAttnKv16Args& a, hipStream_t s);
+// DecAttn2Args of B rows that share keys [0, shared_len) (a struct of its own, as DecAttnKv16Args)
+struct DecAttnSharedArgs : DecAttn2Args {
+    int shared_len = 0;
+};
+// Decode attention of rows that share a prompt (decode_attn_shared.hip): keys
+// [0, shared_len) of every row are read from page 0 only, keys [shared_len, kv_pos[b]) from page b, the step's own
+// key / value from qkv (appended to page b at kv_pos[b] >= shared_len).  f32 cache, f32 throughout.  A partials
+// launch (shared blocks on the f32 MFMA serving all B rows of a head, one-query own blocks) and a merge launch;
+// a.part sized by dec_attn_shared_workspace, a.counters / a.err unused.  hd 32 / 64 / 128, heads % kv_heads == 0,
+// 1 <= B <= 16, 1 <= shared_len < max_len <= 512 * 128 (dec_attn_shared_ok; the launch throws EINVAL otherwise).
+bool dec_attn_shared_ok(const DecAttnSharedArgs& a);
+size_t dec_attn_shared_workspace(int B, int heads, int hd, int max_len, int shared_len);
+void launch_dec_attn_shared(const DecAttnSharedArgs& a, hipStream_t s);
 // q/k/v projection of one token with RoPE applied in the epilogue (rows < rot_rows rotated at
 // position kv_pos[0]; table layout [pos][hd], rope on the full head dim, rotate_half pairing).
 struct DecRopeEpi {

@@ -187,7 +187,7 @@ EXPORTS = [
     "dsocr_resize_catmull_rom",
     "dsocr_engine_load_flags", "dsocr_engine_packed_info", "dsocr_k_moe_packed", "dsocr_k_dsq_rows_dot",
     "dsocr_engine_fp8_info", "dsocr_k_fp8_quantize_rows", "dsocr_k_fp8_rows_dot", "dsocr_k_moe_fp8",
-    "dsocr_engine_kv_info", "dsocr_k_decode_attention_kv16",
+    "dsocr_engine_kv_info", "dsocr_k_decode_attention_kv16", "dsocr_k_decode_attention_shared", "dsocr_generate_n",
     "dsocr_engine_fp8_mode", "dsocr_k_fp8_tile_order", "dsocr_k_fp8_mm_rows_dot", "dsocr_k_moe_fp8_mm",
     "dsocr_engine_packed_mode", "dsocr_k_q8_quantize", "dsocr_k_dsq_rows_dot_q8", "dsocr_k_moe_packed_q8",
     "dsocr_k_moe_ex", "dsocr_k_moe_route_kind", "dsocr_k_moe_prefill_route", "dsocr_k_moe_combine",
@@ -337,6 +337,8 @@ def lib():
     L.dsocr_engine_fp8_info.argtypes = [vp, C.POINTER(sz), C.POINTER(sz), C.POINTER(sz)]
     L.dsocr_engine_kv_info.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(sz)]
     L.dsocr_k_decode_attention_kv16.argtypes = [i32, i32, i32, i32, i32, i32, f32, vp, vp, vp, vp, vp, vp, vp, i32]
+    L.dsocr_k_decode_attention_shared.argtypes = [i32, i32, i32, i32, i32, i32, f32, vp, vp, vp, vp, vp, vp, i32, vp, i32]
+    L.dsocr_generate_n.argtypes = [vp, C.POINTER(RequestC), C.POINTER(DecodeParamsC), sz, vp, C.POINTER(ResultC)]
     L.dsocr_k_fp8_quantize_rows.argtypes = [sz, sz, vp, vp, vp]
     L.dsocr_k_fp8_rows_dot.argtypes = [sz, sz, vp, vp, i32, vp, vp]
     L.dsocr_k_moe_fp8.argtypes = [i32, i32, i32, i32, i32, i32, vp, vp, f32, vp, vp, vp, vp, vp, i32, f32, vp, vp, vp]

@@ -147,6 +147,9 @@ def build_parser() -> argparse.ArgumentParser:
                    help="the window of --ngram-window-size in tokens (default 100)")
     p.add_argument("--ngram-whitelist", metavar="ID,ID,...",
                    help="token ids --ngram-window-size never bans (at most 32)")
+    p.add_argument("--n", dest="n_samples", type=int, default=1, metavar="N",
+                   help="N samples (2..8) of the request: one vision pass and prefill, the decode rows share the "
+                        "prompt's K/V; sample i draws from --seed + i")
     p.add_argument("--slots", type=int, default=0, metavar="N",
                    help="treat every --image as its own one-page document (the prompt has one <image>) and decode them "
                         "together in a session of N slots (1..8); results print in input order.  0 = off")
@@ -432,6 +435,16 @@ def run_inference(args, out=sys.stdout, err=sys.stderr) -> int:
                 out.flush()
 
         info(f"Starting generation with requested budget {params.max_new_tokens} tokens")
+        if getattr(args, "n_samples", 1) != 1:
+            if constraint or getattr(args, "logprobs", None) is not None:
+                raise DsocrError(1, "--n does not combine with the per-request controls or --logprobs")
+            outcomes = engine.decode_n(tokenizer, prompt, images, vision, params, args.n_samples)
+            for i, o in enumerate(outcomes):
+                if not args.quiet:
+                    out.write(f"==> sample {i} <==\n")
+                out.write(o.text + "\n")
+            out.flush()
+            return 0
         lp_k = getattr(args, "logprobs", None)
         if lp_k is not None and not 0 <= lp_k <= 20:
             raise DsocrError(1, "--logprobs takes 0..20")

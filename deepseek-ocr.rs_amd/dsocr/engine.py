@@ -513,6 +513,18 @@ class DeepseekOcrEngine:
         check(lib().dsocr_generate_batch(self._h, b.n, b.reqs, C.byref(pc), b.res))
         return b.ids()
 
+    def generate_n(self, ids, mask, page: Optional[Page], n: int, params: DecodeParameters = DecodeParameters(),
+                   seeds=None, ignore_eos: bool = False):
+        """``n`` samples (2..8) of one page (dsocr_generate_n): vision and prefill run once and the decode rows share
+        the prompt's K/V.  Sample i draws from ``seeds[i]`` (None: ``params.seed + i``).  Returns the ids per sample."""
+        if seeds is not None and len(seeds) != n:
+            raise DsocrError(1, "EINVAL: generate_n takes one seed per sample")
+        b = _Batch(self, [(ids, mask, page, None)] * max(int(n), 0), params)
+        pc = _params_c(params, self.eos_token_id, ignore_eos)
+        sd = None if seeds is None else (C.c_uint64 * n)(*[int(s) for s in seeds])
+        check(lib().dsocr_generate_n(self._h, b.reqs, C.byref(pc), n, sd, b.res))
+        return b.ids()
+
     def generate_trace(self, requests, params: DecodeParameters = DecodeParameters(), ignore_eos: bool = False):
         """generate_batch + the raw logits of every step (dsocr_generate_trace): returns
         (ids per page, logits [n][max_new][vocab] float32; rows past a page's last token are 0)."""
@@ -818,6 +830,16 @@ class DeepseekOcrEngine:
             except TypeError:
                 text = tokenizer.decode([int(t) for t in gen])
         return DecodeOutcome(normalize_text(text), len(ids), len(gen), gen, token_lp, top)
+
+    def decode_n(self, tokenizer, prompt: str, images: Sequence, vision: VisionSettings, params: DecodeParameters,
+                 n: int, seeds=None) -> list:
+        """``n`` samples (2..8) of one request with at most one image (``generate_n``): one ``DecodeOutcome`` each."""
+        if len(images) > 1:
+            raise DsocrError(1, "EINVAL: n samples take a prompt with at most one image")
+        pages = [Page(im, vision, self) for im in images]
+        ids, mask = build_prompt_tokens(tokenizer, prompt, [p.n_image_tokens for p in pages])
+        gens = self.generate_n(ids, mask, pages[0] if pages else None, n, params, seeds)
+        return [DecodeOutcome(normalize_text(_decode_tokens(tokenizer, g)), len(ids), len(g), g) for g in gens]
 
 
 def _decode_tokens(tokenizer, toks) -> str:

@@ -440,6 +440,32 @@ def generate_blocking(state: ServerState, prompt: str, images: list, params: Dec
     return outcome
 
 
+def parse_n(req: dict, stream: bool, slots: bool) -> int:
+    """OpenAI's `n` (1..8): samples of the one request, decoded together with one prefill (OcrEngine.generate_n)."""
+    n = req.get("n")
+    if n is None:
+        return 1
+    if isinstance(n, bool) or not isinstance(n, int) or not 1 <= n <= 8:
+        raise ApiError.bad_request("`n` must be an integer in 1..8")
+    if n > 1 and stream:
+        raise ApiError.bad_request("`n` > 1 does not stream")
+    if n > 1 and slots:
+        raise ApiError.bad_request("`n` > 1 is not served with --slots (a decode session)")
+    return n
+
+
+def generate_n_blocking(state: ServerState, prompt: str, images: list, params: DecodeParameters, n: int) -> list:
+    """n samples of one request behind the lock (no scheduler: parse_n refused it)."""
+    with state.lock:
+        try:
+            outs = state.engine.decode_n(state.tokenizer, prompt, images, state.vision, params, n)
+        except DsocrError as e:
+            raise (ApiError.bad_request if "EINVAL" in str(e) else ApiError.internal)(f"generation failed: {e}")
+    if all(o.response_tokens == 0 and not o.text.strip() for o in outs):
+        raise ApiError.internal(EMPTY_GENERATION_ERROR)
+    return outs
+
+
 class StreamController:
     """stream.rs:120-374: initial event, per-token deltas through DeltaTracker, final event, [DONE]."""
 
@@ -582,6 +608,15 @@ def _chat_response(model, text, pt, ct):
             "usage": {"prompt_tokens": pt, "completion_tokens": ct, "total_tokens": pt + ct}}
 
 
+def _chat_n_response(model, outs, max_new):
+    """n choices of one request: each with its own finish_reason, the prompt counted once, the completions summed."""
+    pt, ct = outs[0].prompt_tokens, sum(o.response_tokens for o in outs)
+    return {"id": f"chatcmpl-{uuid.uuid4()}", "object": "chat.completion", "created": _now(), "model": model,
+            "choices": [{"index": i, "message": {"role": "assistant", "content": o.text},
+                         "finish_reason": "length" if o.response_tokens >= max_new else "stop"} for i, o in enumerate(outs)],
+            "usage": {"prompt_tokens": pt, "completion_tokens": ct, "total_tokens": pt + ct}}
+
+
 def _responses_response(model, text, pt, ct):
     return {"id": f"resp-{uuid.uuid4()}", "object": "response", "created": _now(), "model": model,
             "output": [{"id": f"msg-{uuid.uuid4()}", "type": "message", "role": "assistant",
@@ -598,9 +633,10 @@ def handle_generation(state: ServerState, req: dict, kind: str):
     if not isinstance(model, str):
         raise ApiError.bad_request("missing field `model`")
     state.validate_model(model)
+    stream = bool(req.get("stream"))
+    n = parse_n(req, stream, state.scheduler is not None) if kind == "chat" else 1
     messages = req.get("input" if kind == "responses" else "messages") or []
     prompt, images = convert_messages(messages)
-    stream = bool(req.get("stream"))
     if "<image>" not in prompt:
         if stream:
             c = StreamController(state.tokenizer, kind, model)
@@ -625,6 +661,11 @@ def handle_generation(state: ServerState, req: dict, kind: str):
     guided = parse_guided(req, state.tokenizer, getattr(state.engine, "vocab", None))
     if guided:  # the same; the response names how the automaton ended
         constraint = dict(constraint or {}, **guided)
+    if n > 1:
+        if logprobs is not None or constraint or stops:
+            raise ApiError.bad_request("`n` > 1 does not combine with logprobs, logit_bias / token lists, stop, penalties, "
+                                       "an n-gram window or guided decoding")
+        return "json", _chat_n_response(model, generate_n_blocking(state, prompt, images, params, n), params.max_new_tokens)
     if stream:
         c = StreamController(state.tokenizer, kind, model)
         if stops:

@@ -230,6 +230,14 @@ dsocr_status dsocr_generate(dsocr_engine* e, const dsocr_request* req, const dso
 /* B pages at once (vision batched, prefill batched, decode batched); each result equals dsocr_generate. */
 dsocr_status dsocr_generate_batch(dsocr_engine* e, size_t n, const dsocr_request* reqs,
                                   const dsocr_decode_params* params, dsocr_result* results);
+/* n samples (2..8) of one page: vision and prefill run once, the n decode rows share the prompt's K/V (page 0 of the
+ * cache) and each owns only its tail; the decode attention reads the prompt rows once per step for all n rows
+ * (DESIGN.md section 4.1.5).  `params` apply to every sample; sample i draws from seeds[i] (NULL: params->seed + i)
+ * and equals dsocr_generate of the page alone with that seed up to the summation order of the attention; each stops
+ * at its own EOS.  results [n].  DSOCR_EINVAL before any device work: n outside 2..8, an engine loaded with
+ * DSOCR_LOAD_KV_F16, use_cache == 0, DSOCR_PERSIST, an MLA config, an open session. */
+dsocr_status dsocr_generate_n(dsocr_engine* e, const dsocr_request* req, const dsocr_decode_params* params, size_t n,
+                              const uint64_t* seeds, dsocr_result* results);
 dsocr_status dsocr_last_timings(const dsocr_engine* e, dsocr_timings* t);
 /* Parity hook: dsocr_generate_batch plus the raw logits (before repetition penalty and n-gram ban) of
  * every step of every page, logits_out [n][max_new_tokens][vocab] host f32, step s = the logits the
@@ -888,6 +896,14 @@ dsocr_status dsocr_k_decode_attention(int B, int heads, int kv_heads, int hd, in
 dsocr_status dsocr_k_decode_attention_kv16(int B, int heads, int kv_heads, int hd, int rope_dim, int max_len, float scale,
                                            const float* qkv, const float* cos, const float* sin, uint16_t* kc,
                                            uint16_t* vc, const int* kv_pos, float* o, int prerot);
+/* The same step for B rows that share a prompt (decode_attn_shared.hip): keys
+ * [0, shared_len) of every row are read from page 0 of the f32 caches only (rows [0, shared_len) of the other pages
+ * are neither read nor written), keys [shared_len, kv_pos[b]) from page b, the row's own k / v appended to page b.
+ * DSOCR_EINVAL unless hd is 32, 64 or 128, 1 <= B <= 16, 1 <= shared_len < max_len <= 65536 and every
+ * kv_pos[b] is in [shared_len, max_len). */
+dsocr_status dsocr_k_decode_attention_shared(int B, int heads, int kv_heads, int hd, int rope_dim, int max_len, float scale,
+                                             const float* qkv, const float* cos, const float* sin, float* kc, float* vc,
+                                             const int* kv_pos, int shared_len, float* o, int prerot);
 /* The decoder prefill between the q|k|v linear and the o linear, as the engine launches it on a ragged batch
  * (block.rs:608-789, rope block.rs:1403-1471): B sequences of lens[b] rows (host array) packed one after another,
  * T = sum lens rows in all.  qkv [T][(heads + 2 kv_heads) * hd]: the q columns are rotated in place at the row's
