@@ -25,12 +25,12 @@ ARCH = "gfx950"
 
 KERNELS = ["gemm", "gemm_bf16", "moe", "norm", "attention", "misc", "decode_gemv", "decode_attn", "decode_attn16", "decode_attn_shared", "decode_route",
            "decode_moe", "decode_sample", "lmhead", "dsq", "preprocess", "sampling", "dots_ops", "attention_bf16",
-           "decode_mm", "decode_persist", "decode_q", "decode_qdot", "decode_f8", "decode_f8mm", "attention_prefix", "ocr2_ops", "session",
+           "decode_mm", "decode_persist", "decode_q", "decode_qdot", "decode_f8", "decode_f8mm", "decode_f4mm", "attention_prefix", "ocr2_ops", "session",
            "decode_logprob", "attention_past", "decode_bias", "decode_stop", "decode_penalty",
            "decode_ngram_window", "decode_guided"]
 HOST = ["engine", "dots", "capi"]
 # units compiled without the packed f32 VALU forms (v_pk_*_f32)
-NO_PACKED_F32 = {"decode_qdot", "decode_f8", "decode_f8mm"}
+NO_PACKED_F32 = {"decode_qdot", "decode_f8", "decode_f8mm", "decode_f4mm"}
 
 
 def sources():

@@ -12,6 +12,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
+#include <functional>
 #include <memory>
 #include <sstream>
 #include <string>
@@ -408,9 +409,18 @@ dsocr_status dsocr_engine_load(const dsocr_load_args* args, dsocr_engine** out) 
     const bool fp8mm = f8m && atoi(f8m) != 0;
     const char* k16 = getenv("DSOCR_KV_F16");
     const bool kv16 = k16 && atoi(k16) != 0;
+    const char* f4 = getenv("DSOCR_EXPERT_MXFP4");
+    const bool fp4 = f4 && atoi(f4) != 0;
     return dsocr_engine_load_flags(args, (packed ? DSOCR_LOAD_PACKED_EXPERTS : 0u) | (int8 ? DSOCR_LOAD_PACKED_INT8_DOT : 0u) |
                                              (fp8 ? DSOCR_LOAD_FP8_EXPERTS : 0u) | (fp8mm ? DSOCR_LOAD_FP8_EXPERTS_MM : 0u) |
-                                             (kv16 ? DSOCR_LOAD_KV_F16 : 0u), out);
+                                             (kv16 ? DSOCR_LOAD_KV_F16 : 0u) | (fp4 ? DSOCR_LOAD_MXFP4_EXPERTS : 0u), out);
+}
+
+dsocr_status dsocr_engine_fp4_info(const dsocr_engine* e, size_t* fp4_layers, size_t* moe_layers, size_t* fp4_bytes) {
+    return guarded([&] {
+        if (!e) throw std::runtime_error("EINVAL: NULL engine");
+        e->impl->fp4_info(fp4_layers, moe_layers, fp4_bytes);
+    });
 }
 
 dsocr_status dsocr_engine_fp8_mode(const dsocr_engine* e, int* mode) {
@@ -2371,6 +2381,82 @@ dsocr_status dsocr_k_fp8_mm_rows_dot(size_t rows, size_t cols, const uint8_t* co
             throw;
         }
         (void)hipFree(t);
+    });
+}
+// ---- MXFP4 experts (decode_f4mm.hip)
+dsocr_status dsocr_k_mxfp4_quantize_rows(size_t rows, size_t cols, const void* w_f16, uint8_t* codes_out, uint8_t* shifts_out,
+                                         int8_t* exps_out) {
+    return guarded([&] {
+        if (!rows || !w_f16 || !codes_out || !shifts_out || !exps_out) throw std::runtime_error("EINVAL: NULL argument");
+        dsocr::launch_mxfp4_quantize_rows((long)rows, (long)cols, w_f16, codes_out, shifts_out, exps_out, nullptr);
+        check_hip(hipGetLastError(), "mxfp4_quantize_rows launch");
+        check_hip(hipDeviceSynchronize(), "mxfp4_quantize_rows");
+    });
+}
+// the tile-ordered form of one table through alloc (a ragged last row tile padded with zero codes; exps is the
+// caller's [rows] array as it is: only the MoE launches read whole tiles of it, and their tables have rows % 16 == 0)
+static dsocr::F4Mat mxfp4_tiles(const std::function<void*(size_t)>& alloc, long rows, long cols, const uint8_t* codes, const uint8_t* shifts, const int8_t* exps) {
+    dsocr::F4Mat m;
+    uint8_t* tq = (uint8_t*)alloc(dsocr::mxfp4_tile_code_bytes(rows, cols));
+    uint8_t* td = (uint8_t*)alloc(dsocr::mxfp4_tile_shift_bytes(rows, cols));
+    dsocr::launch_mxfp4_tile_order(rows, cols, codes, shifts, tq, td, nullptr);
+    m.q = tq; m.d = td; m.e = exps;
+    return m;
+}
+dsocr_status dsocr_k_mxfp4_dequant_rows(size_t rows, size_t cols, const uint8_t* codes, const uint8_t* shifts, const int8_t* exps,
+                                        void* w4_f16_out) {
+    return guarded([&] {
+        if (!rows) throw std::runtime_error("EINVAL: NULL argument");
+        dsocr::launch_mxfp4_dequant_rows((long)rows, (long)cols, codes, shifts, exps, w4_f16_out, nullptr);
+        check_hip(hipGetLastError(), "mxfp4_dequant_rows launch");
+        check_hip(hipDeviceSynchronize(), "mxfp4_dequant_rows");
+    });
+}
+dsocr_status dsocr_k_mxfp4_mm_rows_dot(size_t rows, size_t cols, const uint8_t* codes, const uint8_t* shifts, const int8_t* exps,
+                                       int T, const float* x, float* y) {
+    return guarded([&] {
+        if (!rows || !dsocr::mxfp4_tile_ok((long)cols) || !codes || !shifts || !exps)
+            throw std::runtime_error("EINVAL: mxfp4_mm_rows_dot takes rows of a multiple of 128 codes");
+        std::vector<dsocr::DeviceBuffer> bufs;
+        auto alloc = [&](size_t bytes) {
+            bufs.emplace_back(bytes);
+            return bufs.back().get();
+        };
+        const dsocr::F4Mat m = mxfp4_tiles(alloc, (long)rows, (long)cols, codes, shifts, exps);
+        dsocr::launch_mxfp4_mm_rows_dot(m, (long)rows, (long)cols, T, x, y, nullptr);
+        check_hip(hipGetLastError(), "mxfp4_mm_rows_dot launch");
+        check_hip(hipDeviceSynchronize(), "mxfp4_mm_rows_dot");
+    });
+}
+dsocr_status dsocr_k_moe_mxfp4(int T, int H, int E, int topk, int I, int Is, const float* x, const float* norm_w, float eps,
+                               const void* router_f16, const void* Wgu_f16, const void* Wd_f16, const void* sWgu_f16,
+                               const void* sWd_f16, int norm_topk, float scaling, float* out, int* ids_out, float* w_out) {
+    return guarded([&] {
+        if (T <= 0 || T > 8 || H <= 0 || E <= 0 || topk <= 0 || I <= 0 || Is < 0) throw std::runtime_error("EINVAL: bad MoE shape");
+        if (!x || !router_f16 || !Wgu_f16 || !Wd_f16 || !out) throw std::runtime_error("EINVAL: NULL argument");
+        const bool shared = sWgu_f16 && sWd_f16 && Is > 0;
+        if (!dsocr::moe_f4mm_shape_ok(E, H, I, shared ? Is : 0))
+            throw std::runtime_error("EINVAL: MXFP4 decode MoE outside its range (E <= 64, widths multiples of 128, H <= 1536, I <= 1024)");
+        MoeHookRun h(T, H, E, topk, I, x, norm_w, eps, router_f16, dsocr::WDT_F16, out, 1, norm_topk, scaling);
+        dsocr::MoeExperts& w = h.a.w;
+        auto alloc = [&](size_t bytes) { return h.alloc(bytes); };
+        auto quantise = [&](const void* m16, long rows, long cols) {
+            uint8_t* q = (uint8_t*)h.alloc((size_t)rows * cols / 2);
+            uint8_t* d = (uint8_t*)h.alloc((size_t)rows * cols / 32);
+            int8_t* e = (int8_t*)h.alloc((size_t)rows);
+            dsocr::launch_mxfp4_quantize_rows(rows, cols, m16, q, d, e, nullptr);
+            return mxfp4_tiles(alloc, rows, cols, q, d, e);
+        };
+        w.gu = Wgu_f16; w.d = Wd_f16;
+        w.f4_gu = quantise(Wgu_f16, (long)E * 2 * I, H);
+        w.f4_d = quantise(Wd_f16, (long)E * H, I);
+        if (shared) {
+            w.Is = Is; w.sgu = sWgu_f16; w.sd = sWd_f16;
+            w.f4_sgu = quantise(sWgu_f16, 2L * Is, H);
+            w.f4_sd = quantise(sWd_f16, H, Is);
+        }
+        const dsocr::MoeGateUp want = dsocr::MoeGateUp::F4mm;
+        h.run(&want, "EINVAL: MXFP4 decode MoE outside its range", ids_out, w_out, nullptr);
     });
 }
 dsocr_status dsocr_k_dsq_rows_dot(int qtype, size_t rows, size_t in_dim, const void* payload, int T, const float* x,

@@ -247,8 +247,12 @@ void* Engine::ws(const std::string& name0, size_t bytes) {
 Engine::LoadOptions Engine::decode_load_flags(uint32_t f, int dtype, const std::string& snapshot_path) {
     constexpr uint32_t kPacked = DSOCR_LOAD_PACKED_EXPERTS | DSOCR_LOAD_PACKED_INT8_DOT;
     constexpr uint32_t kFp8 = DSOCR_LOAD_FP8_EXPERTS | DSOCR_LOAD_FP8_EXPERTS_MM;
-    if (f & ~(kPacked | kFp8 | DSOCR_LOAD_KV_F16)) throw std::runtime_error("EINVAL: unknown load flags");
+    if (f & ~(kPacked | kFp8 | DSOCR_LOAD_KV_F16 | DSOCR_LOAD_MXFP4_EXPERTS)) throw std::runtime_error("EINVAL: unknown load flags");
     LoadOptions o;
+    o.fp4 = (f & DSOCR_LOAD_MXFP4_EXPERTS) != 0;
+    if (o.fp4 && (f & (kPacked | kFp8)))
+        throw std::runtime_error("EINVAL: MXFP4 experts cannot be combined with packed snapshot experts or FP8 experts");
+    if (o.fp4 && dtype != 1) throw std::runtime_error("EINVAL: MXFP4 experts quantise the fp16 engine's weights: use dtype f16");
     o.kv_f16 = (f & DSOCR_LOAD_KV_F16) != 0;
     // the matrix-core form runs on the FP8 tables, the integer-dot form on the packed ones
     o.fp8 = (f & DSOCR_LOAD_FP8_EXPERTS_MM) ? 2 : (f & DSOCR_LOAD_FP8_EXPERTS) ? 1 : 0;
@@ -290,6 +294,11 @@ Engine::Engine(const std::string& config_path, const std::string& weights_path, 
         size_t fl = 0;
         fp8_info(&fl, nullptr, nullptr);
         if (!fl) throw std::runtime_error("EINVAL: FP8 experts: no MoE layer of this DeepSeek-OCR-2 decoder fits the FP8 kernels");
+    }
+    if (opts_.fp4) {
+        size_t fl = 0;
+        fp4_info(&fl, nullptr, nullptr);
+        if (!fl) throw std::runtime_error("EINVAL: MXFP4 experts: no MoE layer of this decoder fits the MXFP4 kernels");
     }
     ensure_rope(4096);
     ensure_small(64);
@@ -468,6 +477,18 @@ void Engine::fp8_info(size_t* fp8_layers, size_t* moe_layers, size_t* fp8_bytes)
     if (fp8_layers) *fp8_layers = fl;
     if (moe_layers) *moe_layers = ml;
     if (fp8_bytes) *fp8_bytes = fb;
+}
+
+void Engine::fp4_info(size_t* fp4_layers, size_t* moe_layers, size_t* fp4_bytes) const {
+    size_t fl = 0, ml = 0, fb = 0;
+    for (const DecLayer& d : layers_) {
+        if (!d.moe) continue;
+        ++ml;
+        if (d.ex.fp4()) { ++fl; fb += d.fp4_bytes; }
+    }
+    if (fp4_layers) *fp4_layers = fl;
+    if (moe_layers) *moe_layers = ml;
+    if (fp4_bytes) *fp4_bytes = fb;
 }
 
 void Engine::load_weights(const std::string& path, uint64_t seed, const std::string& snapshot_path, bool packed_experts) {
@@ -835,6 +856,33 @@ void Engine::load_weights(const std::string& path, uint64_t seed, const std::str
                     }
                 }
                 HIP_CHECK(hipStreamSynchronize(stream_));
+            }
+            // MXFP4 experts (DSOCR_LOAD_MXFP4_EXPERTS): tile-ordered E2M1 codes, block shifts and row
+            // exponents beside the fp16 tables, for the layers whose router fits dec_route_grp and whose shapes fit
+            // moe_f4mm_shape_ok; any other layer runs the fp16 kernels.  The row-major codes live only until W4 is
+            // written back over the fp16 tables and the tile-ordered copy is made.
+            if (opts_.fp4 && ex.wdtype == WDT_F16 && dec_route_grp_ok(8, E, H, L.topk) && moe_f4mm_shape_ok(E, H, I, Is8) &&
+                (!d.has_shared || (d.s_gu.wdt == WDT_F16 && d.s_d.wdt == WDT_F16 && !d.s_gu.b && !d.s_d.b))) {
+                auto quantise = [&](void* w, long rows, long cols, F4Mat& out) {
+                    const size_t cb = mxfp4_tile_code_bytes(rows, cols), sb = mxfp4_tile_shift_bytes(rows, cols);
+                    const size_t eb = ((size_t)rows + 15) & ~(size_t)15;
+                    DeviceBuffer q((size_t)rows * cols / 2), sh((size_t)rows * cols / 32);
+                    uint8_t* tq = (uint8_t*)dev_alloc(cb);
+                    uint8_t* td = (uint8_t*)dev_alloc(sb);
+                    int8_t* e = (int8_t*)dev_alloc(eb);
+                    launch_mxfp4_quantize_rows(rows, cols, w, (uint8_t*)q.get(), (uint8_t*)sh.get(), e, stream_);
+                    launch_mxfp4_dequant_rows(rows, cols, (const uint8_t*)q.get(), (const uint8_t*)sh.get(), e, w, stream_);
+                    launch_mxfp4_tile_order(rows, cols, (const uint8_t*)q.get(), (const uint8_t*)sh.get(), tq, td, stream_);
+                    HIP_CHECK(hipStreamSynchronize(stream_));  // (the row-major codes are freed here)
+                    out.q = tq; out.d = td; out.e = e;
+                    d.fp4_bytes += cb + sb + eb;
+                };
+                quantise(e_gu, (long)E * 2 * I, H, ex.f4_gu);
+                quantise(e_d, (long)E * H, I, ex.f4_d);
+                if (d.has_shared) {
+                    quantise(d.s_gu.W, 2L * Is8, H, ex.f4_sgu);
+                    quantise(d.s_d.W, H, Is8, ex.f4_sd);
+                }
             }
         }
         layers_.push_back(d);
@@ -4005,6 +4053,14 @@ Engine::DecodeProfile Engine::profile_decode(int iters) {
             prof.moe_gateup.bytes = (touched * 2.0 * I + 2.0 * Is) * (H + 1.0)
                                     + (double)B * H * 4 + (double)(TK * I + B * Is) * 4;
             prof.moe_down.bytes = touched * H * (I + 1.0) + (Is ? H * (Is + 1.0) : 0.0)
+                                  + (double)(TK * I + B * Is) * 4 + 2.0 * B * H * 4;
+        }
+        if (kind == MoeGateUp::F4mm) {
+            // MXFP4 layers stream half a byte per weight, one shift byte per 32 and one exponent byte per row
+            const double bpw = 0.5 + 1.0 / 32.0;
+            prof.moe_gateup.bytes = (touched * 2.0 * I + 2.0 * Is) * (H * bpw + 1.0)
+                                    + (double)B * H * 4 + (double)(TK * I + B * Is) * 4;
+            prof.moe_down.bytes = touched * H * (I * bpw + 1.0) + (Is ? H * (Is * bpw + 1.0) : 0.0)
                                   + (double)(TK * I + B * Is) * 4 + 2.0 * B * H * 4;
         }
     }

@@ -84,6 +84,7 @@ struct DecLayer {
     void* s_dT = nullptr;         // shared [Is][H] (MoE) / dense [I][H]
     size_t packed_bytes = 0;      // device bytes of ex.q_* (packed_info)
     size_t fp8_bytes = 0;         // device bytes of ex.f8_* (fp8_info)
+    size_t fp4_bytes = 0;         // device bytes of ex.f4_* (fp4_info)
 };
 
 // DeepSeek-OCR-2: the Qwen2 decoder used as the vision encoder (vision/qwen2.rs)
@@ -323,6 +324,8 @@ class Engine {
     void fp8_info(size_t* fp8_layers, size_t* moe_layers, size_t* fp8_bytes) const;
     // 0 fp16 experts, 1 FP8 experts, 2 FP8 experts with the matrix-core form at 3..8 tokens
     int fp8_mode() const { return opts_.fp8; }
+    // MoE layers that run the MXFP4 decode kernels / all MoE layers / device bytes of the MXFP4 tables
+    void fp4_info(size_t* fp4_layers, size_t* moe_layers, size_t* fp4_bytes) const;
     // KV cache: bytes per element (4, or 2 under DSOCR_LOAD_KV_F16) and the bytes of K + V of the current decode
     // rows (0 before any generate)
     void kv_info(int* elem_bytes, size_t* cache_bytes) const;
@@ -490,6 +493,7 @@ class Engine {
     struct LoadOptions {
         int packed = 0;       // 0 dequant-on-load, 1 packed experts, 2 packed experts with integer block dots
         int fp8 = 0;          // 0 fp16 experts, 1 FP8 experts, 2 FP8 experts with the matrix-core form
+        bool fp4 = false;     // MXFP4 experts (DSOCR_LOAD_MXFP4_EXPERTS)
         bool kv_f16 = false;  // the K/V cache's element type
     };
     static LoadOptions decode_load_flags(uint32_t load_flags, int dtype, const std::string& snapshot_path);

@@ -27,7 +27,7 @@
 #include <string>
 
 #include "decode_common.hpp"
-#include "mm_planes.hpp"
+#include "mm_codes.hpp"
 
 namespace dsocr {
 
@@ -36,10 +36,6 @@ namespace {
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 typedef MmT<f16_t>::frag frag;
 
-// 2^e as an f32 (|e| <= 126)
-__device__ __forceinline__ float pow2i(int e) { return __uint_as_float((uint32_t)(127 + e) << 23); }
-// exponent i of four int8 packed in a dword
-__device__ __forceinline__ float pow2b(uint32_t e4, int i) { return pow2i((int)(int8_t)(e4 >> (8 * i))); }
 
 // eight E4M3 codes (two dwords) -> the f16 A fragment: v_cvt_scalef32_pk_f16_fp8, scale 1.0, low / high word
 __device__ __forceinline__ frag f8_frag(uint32_t w0, uint32_t w1) {
@@ -257,7 +253,7 @@ __global__ __launch_bounds__(512, 4) void moe_gateup_f8mm_kernel(MoeF8Args a) {
 }
 
 // ------------------------------------------------------------------ down + combine + residual
-constexpr int DN_RT = 64;  // output rows per block: 16 per wave
+constexpr int DN_RT = MMC_DN_RT;  // output rows per block: 16 per wave
 
 __global__ __launch_bounds__(256) void moe_down_f8mm_kernel(MoeF8Args a, int G) {
     WaveSpan span_(a.span);
@@ -322,60 +318,9 @@ __global__ __launch_bounds__(256) void moe_down_f8mm_kernel(MoeF8Args a, int G) 
         for (int i = 0; i < 4; ++i) tot[i] += (acc[0][i] * sc) * pow2b(e4, i);
         __syncthreads();  // the planes are restaged by the next segment
     }
-    if (G == 1) {  // the block holds the whole sum: the workspace is not touched
-        if (col < a.T) {
-            float4* op = reinterpret_cast<float4*>(a.out + (long)col * a.H + j0 + 4 * g);
-            float4 o = *op;
-            o.x += tot[0]; o.y += tot[1]; o.z += tot[2]; o.w += tot[3];
-            *op = o;
-        }
-        return;
-    }
-    // partial tile -> part[group][t][j], write-through (sc1); the block that completes the row tile's ticket sums the
-    // groups in group order (an empty group stored zeros) and leaves the ticket at zero for the next launch
-    const auto prs = __builtin_amdgcn_make_buffer_rsrc(a.dn_part, (short)0, 0x7fffffff, 0x00020000);
-    if (col < a.T) {
-        u32x4 bits;
-        __builtin_memcpy(&bits, &tot, 16);
-        __builtin_amdgcn_raw_buffer_store_b128(bits, prs, (int)((((long)gi * MM_MT + col) * a.H + j0 + 4 * g) * 4), 0, 16);
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (tid == 0) {
-        int* tk = a.dn_tick + tile;
-        const int old = __hip_atomic_fetch_add(tk, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const int last = old == G - 1;
-        if (last) __hip_atomic_store(tk, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        last_s = last;
-    }
-    __syncthreads();
-    if (!last_s) return;
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");  // no instruction: keeps the sc1 loads below
-    const int t = tid >> 4, j = tile * DN_RT + 4 * (tid & 15);  // thread = (token, 4 rows) for tid < 128
-    if (tid < 128 && t < a.T) {
-        const int base = (int)(((long)t * a.H + j) * 4), gstride = MM_MT * a.H * 4;
-        float4* op = reinterpret_cast<float4*>(a.out + (long)t * a.H + j);
-        const float4 o = *op;
-        f32x4 v = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll 8
-        for (int q = 0; q < G; ++q) {
-            const u32x4 pv = __builtin_amdgcn_raw_buffer_load_b128(prs, base + q * gstride, 0, 16);
-            v[0] += __uint_as_float(pv[0]); v[1] += __uint_as_float(pv[1]);
-            v[2] += __uint_as_float(pv[2]); v[3] += __uint_as_float(pv[3]);
-        }
-        *op = make_float4(o.x + v[0], o.y + v[1], o.z + v[2], o.w + v[3]);
-    }
+    mmc_down_finish(tot, G, gi, tile, j0, a.T, a.H, a.out, a.dn_part, a.dn_tick, &last_s);
 }
 
-int resident_blocks(const void* kernel, int threads, size_t lds) {
-    int per_cu = 0, dev = 0, cus = 0;
-    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, threads, lds);
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    return std::max(1, per_cu) * std::max(1, cus);
-}
-
-size_t plane_bytes(int K) { return sizeof(uint16_t) * 3 * MM_MT * (size_t)mm_pitch(K); }
 
 }  // namespace
 
@@ -402,7 +347,7 @@ void launch_fp8_mm_rows_dot(const uint8_t* tiles, const int8_t* exps, long rows,
         (void)hipFuncSetAttribute((const void*)fp8_mm_rows_dot_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
         attr = true;
     }
-    hipLaunchKernelGGL(fp8_mm_rows_dot_kernel, dim3((unsigned)((rows + 15) / 16)), dim3(256), plane_bytes((int)cols), s, tiles, exps,
+    hipLaunchKernelGGL(fp8_mm_rows_dot_kernel, dim3((unsigned)((rows + 15) / 16)), dim3(256), mmc_plane_bytes((int)cols), s, tiles, exps,
                        rows, (int)cols, T, x, y);
 }
 
@@ -416,14 +361,14 @@ void launch_moe_gateup_f8mm(const MoeF8Args& a, hipStream_t s) {
     if (!moe_f8mm_ok(a)) throw std::runtime_error("EINVAL: FP8 decode MoE (matrix cores) outside its range");
     const int steps = a.H / 64, ks = steps % 4 == 0 ? 4 : steps % 2 == 0 ? 2 : 1;
     const int max_units = a.Is / 16 + a.slots * (a.I / 16);
-    const size_t lds = plane_bytes(a.H) + (ks > 1 ? (size_t)(8 / ks) * (ks - 1) * 2 * 64 * sizeof(f32x4) : 0);
+    const size_t lds = mmc_plane_bytes(a.H) + (ks > 1 ? (size_t)(8 / ks) * (ks - 1) * 2 * 64 * sizeof(f32x4) : 0);
 #define DSOCR_GF(KS)                                                                                                    \
     do {                                                                                                                \
         static int resident = 0;                                                                                        \
         if (!resident) {                                                                                                \
             (void)hipFuncSetAttribute((const void*)moe_gateup_f8mm_kernel<KS>, hipFuncAttributeMaxDynamicSharedMemorySize, \
                                       96 * 1024);                                                                       \
-            resident = resident_blocks((const void*)moe_gateup_f8mm_kernel<KS>, 512, lds);                               \
+            resident = mmc_resident_blocks((const void*)moe_gateup_f8mm_kernel<KS>, 512, lds);                               \
         }                                                                                                               \
         const int nu = 8 / KS, blocks = std::max(1, std::min(resident, (max_units + nu - 1) / nu));                      \
         DSOCR_LAUNCH(moe_gateup_f8mm_kernel<KS>, dim3(blocks), dim3(512), lds, s, a);                                    \
@@ -434,18 +379,12 @@ void launch_moe_gateup_f8mm(const MoeF8Args& a, hipStream_t s) {
 #undef DSOCR_GF
 }
 
-// groups of segments per 64-row tile: enough blocks for three per CU, at most one group per routed slot (the
-// workspace's size: moe_down_mm_part_floats), one when the launch has no workspace
-int moe_down_f8mm_groups(const MoeF8Args& a) {
-    if (!a.dn_part || !a.dn_tick) return 1;
-    const int tiles = a.H / DN_RT;
-    return std::max(1, std::min((768 + tiles - 1) / tiles, a.slots));
-}
+int moe_down_f8mm_groups(const MoeF8Args& a) { return mmc_down_groups(a); }
 
 void launch_moe_down_f8mm(const MoeF8Args& a, hipStream_t s) {
     if (!moe_f8mm_ok(a)) throw std::runtime_error("EINVAL: FP8 decode MoE (matrix cores) outside its range");
     const int G = moe_down_f8mm_groups(a);
-    DSOCR_LAUNCH(moe_down_f8mm_kernel, dim3((unsigned)(G * (a.H / DN_RT))), dim3(256), plane_bytes(a.I), s, a, G);
+    DSOCR_LAUNCH(moe_down_f8mm_kernel, dim3((unsigned)(G * (a.H / DN_RT))), dim3(256), mmc_plane_bytes(a.I), s, a, G);
 }
 
 }  // namespace dsocr

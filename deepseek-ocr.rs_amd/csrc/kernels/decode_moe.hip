@@ -839,6 +839,7 @@ enum class Down {
     Qdot,         // q8_quantize_kernel over h and hs, then moe_down_qdot_kernel (decode_qdot.hip)
     F8,           // moe_down_f8_kernel (decode_f8.hip)
     F8mm,         // moe_down_f8mm_kernel (decode_f8mm.hip)
+    F4mm,         // moe_down_f4mm_kernel (decode_f4mm.hip)
 };
 
 // The forms behind launch_moe_gateup2 / launch_moe_down2, read off the launch's own arguments (the two are entry
@@ -1198,6 +1199,7 @@ struct MoePlan {
     DecGemvArgs router;
     MoeQArgs q;      // GateUp::Q / Down::Q: the packed launches' arguments (decode_q.hip)
     MoeF8Args f8;    // GateUp::F8 / Down::F8: the FP8 launches' arguments (decode_f8.hip)
+    MoeF4Args f4;    // GateUp::F4mm / Down::F4mm: the MXFP4 launches' arguments (decode_f4mm.hip)
     MoeDec2Args mr;  // Route::InGateupMm: the arguments of the gate/up launch that also routes
 };
 
@@ -1215,7 +1217,8 @@ static bool route_fused_on() {
 // copies at T <= 8 where the layer keeps them), more than 8 sorted; packed experts (T <= 8) take the grouped packed
 // kernels, in their integer-dot form when the layer asks for it and the arguments carry the code-plane workspace;
 // FP8 experts (T <= 8) take the grouped FP8 kernels where the router and the shapes fit (at 3..8 tokens their
-// matrix-core form when the tables carry the tile-ordered copies and moe_f8mm_ok holds), else the fp16 forms.
+// matrix-core form when the tables carry the tile-ordered copies and moe_f8mm_ok holds), else the fp16 forms; MXFP4
+// experts (T <= 8) take their matrix-core kernels at every T where moe_f4mm_ok holds, else the fp16 forms.
 MoePlan moe_plan(const MoeDecodeArgs& a) {
     const MoeExperts& w = a.w;
     const int T = a.T, E = a.E, K = a.topk, TK = T * K;
@@ -1262,6 +1265,18 @@ MoePlan moe_plan(const MoeDecodeArgs& a) {
                 p.gu = GateUp::F8mm;
                 p.dn = Down::F8mm;
             }
+            return p;
+        }
+    }
+    if (w.fp4() && T <= 8) {
+        MoeF4Args& f = p.f4;
+        grp_args(f, w.f4_gu, w.f4_d, w.f4_sgu, w.f4_sd);
+        // one family at every T <= 8: the down launch meets through the workspaces whenever the arguments carry them
+        f.dn_part = a.dn_part; f.dn_tick = a.dn_tick;
+        if (grp_route && (f.Is > 0) == (m.Is > 0) && moe_f4mm_ok(f)) {
+            p.route = Route::DecRouteGrp;
+            p.gu = GateUp::F4mm;
+            p.dn = Down::F4mm;
             return p;
         }
     }
@@ -1381,6 +1396,7 @@ void moe_decode_kernel_names(const MoeDecodeArgs& a, const char** gateup, const 
         case GateUp::Qdot: gu = "moe_gateup_qdot_kernel"; break;
         case GateUp::F8: gu = "moe_gateup_f8_kernel"; break;
         case GateUp::F8mm: gu = "moe_gateup_f8mm_kernel"; break;
+        case GateUp::F4mm: gu = "moe_gateup_f4mm_kernel"; break;
     }
     switch (p.dn) {
         case Down::Mix: dn = "moe_down_mix_kernel"; break;
@@ -1393,6 +1409,7 @@ void moe_decode_kernel_names(const MoeDecodeArgs& a, const char** gateup, const 
         case Down::Qdot: dn = "moe_down_qdot_kernel"; break;
         case Down::F8: dn = "moe_down_f8_kernel"; break;
         case Down::F8mm: dn = "moe_down_f8mm_kernel"; break;
+        case Down::F4mm: dn = "moe_down_f4mm_kernel"; break;
     }
     if (gateup) *gateup = gu;
     if (down) *down = dn;
@@ -1437,6 +1454,7 @@ void launch_moe_decode(const MoeDecodeArgs& a, hipStream_t s, int parts) {
             case GateUp::Qdot: launch_moe_gateup_qdot(p.q, s); break;
             case GateUp::F8: launch_moe_gateup_f8(p.f8, s); break;
             case GateUp::F8mm: launch_moe_gateup_f8mm(p.f8, s); break;
+            case GateUp::F4mm: launch_moe_gateup_f4mm(p.f4, s); break;
             case GateUp::Mix: launch_moe_gateup_mix(m, a.xn_router, s); break;
             case GateUp::Mm: launch_moe_gateup_mm(p.route == Route::InGateupMm ? p.mr : m, s); break;
             case GateUp::Grp: launch_moe_gateup_grp(m, s); break;
@@ -1452,6 +1470,7 @@ void launch_moe_decode(const MoeDecodeArgs& a, hipStream_t s, int parts) {
             case Down::Qdot: launch_moe_down_qdot(p.q, s); break;
             case Down::F8: launch_moe_down_f8(p.f8, s); break;
             case Down::F8mm: launch_moe_down_f8mm(p.f8, s); break;
+            case Down::F4mm: launch_moe_down_f4mm(p.f4, s); break;
             case Down::Mm: launch_moe_down_mm(m, s); break;
             case Down::Grp: launch_moe_down_grp(m, s); break;
             case Down::Mix: launch_moe_down_mix(m, s); break;

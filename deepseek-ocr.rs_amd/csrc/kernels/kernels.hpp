@@ -33,6 +33,14 @@ struct F8Mat {
     // [rows / 16][cols / 64][64 lanes][16 B], rows % 16 == 0, cols % 64 == 0
     const uint8_t* t = nullptr;
 };
+// MXFP4 expert rows (decode_f4mm.hip; contract: DESIGN.md section 4.4.5), kept in tile order only: q the E2M1 codes
+// [rows / 16][cols / 128][64 lanes][16 B], d the block down-shifts [rows / 16][cols / 128][16 rows][4 B], e [rows] the
+// row exponents; the weight is 2^(e[r] - d[r][k / 32]) * e2m1(code[r][k]).  rows % 16 == 0, cols % 128 == 0.
+struct F4Mat {
+    const uint8_t* q = nullptr;
+    const uint8_t* d = nullptr;
+    const int8_t* e = nullptr;
+};
 
 // A MoE layer's expert weights in every form the layer keeps (the one owner: DecLayer holds it, MoeDecodeArgs carries
 // it by value, moe_plan in decode_moe.hip alone decides which launches stream which tables).  The form is what is
@@ -53,9 +61,12 @@ struct MoeExperts {
     // FP8 codes (decode_f8.hip), streamed at T <= 8 where moe_f8_ok holds; with the tile-ordered copies on the
     // matrix cores at 3..8 tokens (decode_f8mm.hip)
     F8Mat f8_gu, f8_d, f8_sgu, f8_sd;
+    // MXFP4 codes in tile order (decode_f4mm.hip), streamed on the matrix cores at T <= 8 where moe_f4mm_ok holds
+    F4Mat f4_gu, f4_d, f4_sgu, f4_sd;
     bool packed() const { return q_gu.q != nullptr; }
     bool fp8() const { return f8_gu.q != nullptr; }
-    bool reduced() const { return packed() || fp8(); }  // a reduced-byte form beside (or instead of) the fp16 tables
+    bool fp4() const { return f4_gu.q != nullptr; }
+    bool reduced() const { return packed() || fp8() || fp4(); }  // a reduced-byte form beside (or instead of) the fp16 tables
 };
 
 // Profiling hook: while prof_events() holds a (start, stop) pair, the next kernel launched through
@@ -695,6 +706,7 @@ enum class MoeGateUp {
     Qdot,        // q8_quantize_kernel over xn, then moe_gateup_qdot_kernel (decode_qdot.hip)
     F8,          // moe_gateup_f8_kernel (decode_f8.hip)
     F8mm,        // moe_gateup_f8mm_kernel (decode_f8mm.hip)
+    F4mm,        // moe_gateup_f4mm_kernel (decode_f4mm.hip)
 };
 MoeGateUp moe_decode_gateup_kind(const MoeDecodeArgs& a);
 // which of the routing implementations the dispatch picks (static string): "moe_gateup_mix", "moe_gateup_slot",
@@ -1063,6 +1075,37 @@ bool moe_f8mm_ok(const MoeF8Args& a);
 int moe_down_f8mm_groups(const MoeF8Args& a);
 void launch_moe_gateup_f8mm(const MoeF8Args& a, hipStream_t s);
 void launch_moe_down_f8mm(const MoeF8Args& a, hipStream_t s);
+
+// MXFP4 expert weights on the matrix cores (decode_f4mm.hip; contract: DESIGN.md section 4.4.5).
+// launch_mxfp4_quantize_rows: fp16 rows [rows][cols] -> row-major nibble codes [rows][cols / 2] (low nibble = even k),
+// one down-shift byte per 32-block [rows][cols / 32] and one exponent per row (cols % 32 == 0).
+// launch_mxfp4_dequant_rows: W4 as fp16 (exact) from the same three.  launch_mxfp4_tile_order: the tile-ordered codes
+// (mxfp4_tile_code_bytes) and shift plane (mxfp4_tile_shift_bytes) an F4Mat points at; rows are rounded up to whole
+// 16-row tiles (zero codes), cols % 128 == 0.  launch_mxfp4_mm_rows_dot: y[T][rows] = x[T][cols] . W4^T from the
+// tile-ordered form (parity hook, T <= 8, cols <= 1536).
+bool mxfp4_rows_ok(long cols);
+bool mxfp4_tile_ok(long cols);
+size_t mxfp4_tile_code_bytes(long rows, long cols);
+size_t mxfp4_tile_shift_bytes(long rows, long cols);
+void launch_mxfp4_quantize_rows(long rows, long cols, const void* w_f16, uint8_t* codes, uint8_t* shifts, int8_t* exps,
+                                hipStream_t s);
+void launch_mxfp4_dequant_rows(long rows, long cols, const uint8_t* codes, const uint8_t* shifts, const int8_t* exps, void* w4_f16,
+                               hipStream_t s);
+void launch_mxfp4_tile_order(long rows, long cols, const uint8_t* codes, const uint8_t* shifts, uint8_t* tile_codes,
+                             uint8_t* tile_shifts, hipStream_t s);
+void launch_mxfp4_mm_rows_dot(const F4Mat& m, long rows, long cols, int T, const float* x, float* y, hipStream_t s);
+// The MoE launches behind dec_route_grp, as MoeF8Args': x = the normalised rows, h carries the routing weight.
+// moe_f4mm_shape_ok: E <= 64, H / I / Is multiples of 128, H <= 1536, I <= 1024; moe_f4mm_ok: that, T <= 8, every table.
+struct MoeF4Args : MoeGrpArgs<F4Mat> {
+    // group partials [groups][8][H] (at least min(E, T topk) groups) and one ticket per 64-row tile, zero between
+    // launches; null = one group per row tile, no workspace
+    float* dn_part = nullptr; int* dn_tick = nullptr;
+};
+bool moe_f4mm_shape_ok(int E, int H, int I, int Is);
+bool moe_f4mm_ok(const MoeF4Args& a);
+int moe_down_f4mm_groups(const MoeF4Args& a);
+void launch_moe_gateup_f4mm(const MoeF4Args& a, hipStream_t s);
+void launch_moe_down_f4mm(const MoeF4Args& a, hipStream_t s);
 
 // Page preprocessing on the GPU (preprocess.hip): Pillow 22-bit bicubic (tap tables from the host),
 // then a vertical pass fused with canvas placement / tile cropping and the CHW normalisation

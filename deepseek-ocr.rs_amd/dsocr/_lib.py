@@ -164,6 +164,7 @@ LOAD_PACKED_INT8_DOT = 2  # DSOCR_LOAD_PACKED_INT8_DOT (implies LOAD_PACKED_EXPE
 LOAD_FP8_EXPERTS = 4  # DSOCR_LOAD_FP8_EXPERTS
 LOAD_FP8_EXPERTS_MM = 8  # DSOCR_LOAD_FP8_EXPERTS_MM (implies LOAD_FP8_EXPERTS)
 LOAD_KV_F16 = 16  # DSOCR_LOAD_KV_F16
+LOAD_MXFP4_EXPERTS = 32  # DSOCR_LOAD_MXFP4_EXPERTS
 # what dsocr_session_open* answers on an engine with the f16 KV cache (the server's start-up check says the same)
 KV_F16_NO_SESSION = ("decode sessions (with page prefixes and chunked admission) need the f32 KV cache: this engine was "
                      "loaded with the f16 KV cache (DSOCR_LOAD_KV_F16)")
@@ -217,6 +218,8 @@ EXPORTS = [
     "dsocr_k_gemm_f32a_ex", "dsocr_k_layernorm_ex", "dsocr_k_rmsnorm_ex", "dsocr_k_sam_relbias", "dsocr_k_attention_fused",
     "dsocr_k_vision_op", "dsocr_window_maps",
     "dsocr_k_moe_plan",
+    "dsocr_engine_fp4_info", "dsocr_k_mxfp4_quantize_rows", "dsocr_k_mxfp4_mm_rows_dot", "dsocr_k_moe_mxfp4",
+    "dsocr_k_mxfp4_dequant_rows",
 ]
 
 # model variants behind the deepseek engine (dsocr_engine_variant)
@@ -346,6 +349,11 @@ def lib():
     L.dsocr_k_fp8_tile_order.argtypes = [sz, sz, vp, vp]
     L.dsocr_k_fp8_mm_rows_dot.argtypes = L.dsocr_k_fp8_rows_dot.argtypes
     L.dsocr_k_moe_fp8_mm.argtypes = L.dsocr_k_moe_fp8.argtypes
+    L.dsocr_engine_fp4_info.argtypes = L.dsocr_engine_fp8_info.argtypes
+    L.dsocr_k_mxfp4_quantize_rows.argtypes = [sz, sz, vp, vp, vp, vp]
+    L.dsocr_k_mxfp4_dequant_rows.argtypes = [sz, sz, vp, vp, vp, vp]
+    L.dsocr_k_mxfp4_mm_rows_dot.argtypes = [sz, sz, vp, vp, vp, i32, vp, vp]
+    L.dsocr_k_moe_mxfp4.argtypes = L.dsocr_k_moe_fp8.argtypes
     L.dsocr_k_moe.argtypes = [i32, i32, i32, i32, i32, i32, vp, vp, f32, vp, vp, vp, vp, vp, i32, i32, f32, vp, vp, vp]
     L.dsocr_k_moe_ex.argtypes = L.dsocr_k_moe.argtypes + [i32, vp, vp]
     L.dsocr_k_moe_route_kind.argtypes = [i32, i32, i32, i32, i32, i32, i32, C.POINTER(C.c_char_p)]

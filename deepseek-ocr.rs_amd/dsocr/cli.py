@@ -41,6 +41,11 @@ def expert_fp8_arg(args):
     return "mm" if getattr(args, "expert_fp8_mm", False) else getattr(args, "expert_fp8", None)
 
 
+def expert_fp4_arg(args):
+    """ModelLoadArgs.expert_fp4 from --expert-mxfp4 (not given: the DSOCR_EXPERT_MXFP4 environment switch decides)."""
+    return True if getattr(args, "expert_mxfp4", False) else None
+
+
 def kv_dtype_arg(args):
     """ModelLoadArgs.kv_dtype from --kv-f16 (not given: the DSOCR_KV_F16 environment switch decides)."""
     return "f16" if getattr(args, "kv_f16", False) else None
@@ -77,6 +82,10 @@ def add_model_args(p: argparse.ArgumentParser) -> None:
                         "1..8 tokens (dtype f16; default: the DSOCR_EXPERT_FP8 environment switch decides)")
     g.add_argument("--expert-fp8-mm", action="store_true", default=False,
                    help="as --expert-fp8, with decode steps of 3..8 tokens running the FP8 codes on the matrix cores")
+    g.add_argument("--expert-mxfp4", action="store_true", default=False,
+                   help="keep the MoE experts as MXFP4 (E2M1 codes, a row exponent, a shift per block of 32) and run "
+                        "decode steps of 1..8 tokens on the matrix cores from them (dtype f16; not with --expert-fp8* or "
+                        "--snapshot-packed; default: the DSOCR_EXPERT_MXFP4 environment switch decides)")
     g.add_argument("--kv-f16", action="store_true", default=False,
                    help="keep the decoder's K/V cache in f16 (rounded once at append; half the cache bytes, a decode "
                         "attention kernel of its own; not with a decode session; default: the DSOCR_KV_F16 "
@@ -397,7 +406,8 @@ def run_inference(args, out=sys.stdout, err=sys.stderr) -> int:
     t0 = time.perf_counter()
     engine = load_model(ModelLoadArgs(config_path=config, weights_path=args.weights, snapshot_path=args.snapshot,
                                       snapshot_packed=snapshot_packed_arg(args),
-                                      expert_fp8=expert_fp8_arg(args), kv_dtype=kv_dtype_arg(args),
+                                      expert_fp8=expert_fp8_arg(args), expert_fp4=expert_fp4_arg(args),
+                                      kv_dtype=kv_dtype_arg(args),
                                       device=device, dtype=args.dtype, synthetic_seed=args.synthetic_seed))
     load_ms = (time.perf_counter() - t0) * 1e3
     events.append(_event("model.load", load_ms, model=args.model, kind="Deepseek", device=f"hip:{device}",

@@ -18,7 +18,7 @@ from typing import Any, Callable, Optional, Sequence, Union
 
 import numpy as np
 
-from ._lib import (DTYPES, LOAD_FP8_EXPERTS, LOAD_FP8_EXPERTS_MM, LOAD_KV_F16, LOAD_PACKED_EXPERTS, LOAD_PACKED_INT8_DOT, MAX_TOP_LOGPROBS, DecodeParamsC, DsocrError, LoadArgs, LogitBiasC, LogprobsC,
+from ._lib import (DTYPES, LOAD_FP8_EXPERTS, LOAD_FP8_EXPERTS_MM, LOAD_KV_F16, LOAD_MXFP4_EXPERTS, LOAD_PACKED_EXPERTS, LOAD_PACKED_INT8_DOT, MAX_TOP_LOGPROBS, DecodeParamsC, DsocrError, LoadArgs, LogitBiasC, LogprobsC,
                    GuidedC, GuidedResultC, NgramWindowC, PenaltiesC, SESSION_GUIDED, RequestC, ResultC, STREAM_CB, SESSION_LOGIT_BIAS, SESSION_LOGPROBS,
                    SESSION_NGRAM_WINDOW, SESSION_PENALTIES,
                    SESSION_PER_REQUEST, SESSION_STOP,
@@ -193,6 +193,11 @@ class ModelLoadArgs:
     # environment switch decides (when snapshot_packed is None too), True / False = dsocr_engine_load_flags
     # "mm" = DSOCR_LOAD_FP8_EXPERTS_MM: as True, and decode steps of 3..8 tokens run the codes on the matrix cores
     expert_fp8: Union[None, bool, str] = None
+    # MoE experts kept as MXFP4 (E2M1 codes, a power-of-two exponent per row, a down-shift per block of 32) and run on
+    # the matrix cores at 1..8 decode tokens (DSOCR_LOAD_MXFP4_EXPERTS; dtype f16, no snapshot needed, not with
+    # snapshot_packed or expert_fp8): None = the DSOCR_EXPERT_MXFP4 environment switch decides (when the other load
+    # switches are None too), True / False = dsocr_engine_load_flags
+    expert_fp4: Optional[bool] = None
     # the decoder's K/V cache: "f16" = DSOCR_LOAD_KV_F16 (K / V rounded once at append, half the cache bytes, a decode
     # attention kernel of its own; no decode session on such an engine), "f32" = the f32 cache, None = the DSOCR_KV_F16
     # environment switch decides (when snapshot_packed and expert_fp8 are None too; else f32)
@@ -387,7 +392,7 @@ class DeepseekOcrEngine:
                       args.snapshot_path.encode() if args.snapshot_path else None, args.device, DTYPES[args.dtype],
                       args.synthetic_seed)
         h = C.c_void_p()
-        if args.snapshot_packed is None and args.expert_fp8 is None and args.kv_dtype is None:
+        if args.snapshot_packed is None and args.expert_fp8 is None and args.kv_dtype is None and args.expert_fp4 is None:
             check(lib().dsocr_engine_load(C.byref(la), C.byref(h)))
         else:
             if isinstance(args.snapshot_packed, str) and args.snapshot_packed != "int8":
@@ -400,6 +405,8 @@ class DeepseekOcrEngine:
                 flags |= LOAD_FP8_EXPERTS | LOAD_FP8_EXPERTS_MM if args.expert_fp8 == "mm" else LOAD_FP8_EXPERTS
             if args.kv_dtype == "f16":
                 flags |= LOAD_KV_F16
+            if args.expert_fp4:
+                flags |= LOAD_MXFP4_EXPERTS
             check(lib().dsocr_engine_load_flags(C.byref(la), flags, C.byref(h)))
         self._h = h
         self.args = args
@@ -421,6 +428,12 @@ class DeepseekOcrEngine:
         fl, ml, fb = C.c_size_t(), C.c_size_t(), C.c_size_t()
         check(lib().dsocr_engine_fp8_info(self._h, C.byref(fl), C.byref(ml), C.byref(fb)))
         return {"fp8_layers": fl.value, "moe_layers": ml.value, "fp8_bytes": fb.value}
+
+    def fp4_info(self) -> dict:
+        """MoE layers that run the MXFP4 decode kernels, MoE layers in all, device bytes of the MXFP4 tables."""
+        fl, ml, fb = C.c_size_t(), C.c_size_t(), C.c_size_t()
+        check(lib().dsocr_engine_fp4_info(self._h, C.byref(fl), C.byref(ml), C.byref(fb)))
+        return {"fp4_layers": fl.value, "moe_layers": ml.value, "fp4_bytes": fb.value}
 
     def kv_info(self) -> dict:
         """The K/V cache: {"elem_bytes": 4 or 2 (kv_dtype f16), "cache_bytes": K + V of the current decode rows (0

@@ -836,7 +836,7 @@ def main(argv=None) -> int:
     import argparse
 
     from .cli import (_vocab_of, add_inference_args, add_model_args, decode_params, load_tokenizer, model_config,
-                      parse_device, expert_fp8_arg, kv_dtype_arg, snapshot_packed_arg, vision_settings)
+                      parse_device, expert_fp4_arg, expert_fp8_arg, kv_dtype_arg, snapshot_packed_arg, vision_settings)
     from .engine import ModelLoadArgs, load_model
 
     p = argparse.ArgumentParser(prog="deepseek-ocr-server", description="DeepSeek-OCR API Server (MI355X engine)")
@@ -866,7 +866,8 @@ def main(argv=None) -> int:
     config = model_config(args)  # --model deepseek-ocr | deepseek-ocr-2: the bundled config and vision defaults
     engine = load_model(ModelLoadArgs(config_path=config, weights_path=args.weights, snapshot_path=args.snapshot,
                                       snapshot_packed=snapshot_packed_arg(args),
-                                      expert_fp8=expert_fp8_arg(args), kv_dtype=kv_dtype_arg(args),
+                                      expert_fp8=expert_fp8_arg(args), expert_fp4=expert_fp4_arg(args),
+                                      kv_dtype=kv_dtype_arg(args),
                                       device=parse_device(args.device), dtype=args.dtype,
                                       synthetic_seed=args.synthetic_seed))
     state = ServerState(engine, load_tokenizer(args.tokenizer, _vocab_of(config)), args.model,

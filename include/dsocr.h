@@ -157,6 +157,18 @@ dsocr_status dsocr_engine_load(const dsocr_load_args* args, dsocr_engine** out);
  * the attention); there is no FP8 cache.  dsocr_engine_load adds the flag when the environment has DSOCR_KV_F16 set to
  * a non-zero value. */
 #define DSOCR_LOAD_KV_F16 16u
+/* DSOCR_LOAD_MXFP4_EXPERTS (dtype DSOCR_F16 only; DSOCR_EINVAL with either packed flag or either FP8 flag; combines
+ * with DSOCR_LOAD_KV_F16): at load every MoE layer whose router fits the one-launch grouped router (at most 64
+ * experts) and whose hidden and intermediate sizes are multiples of 128 (hidden at most 1536, routed intermediate at
+ * most 1024) also keeps its routed and shared expert matrices as OCP E2M1 codes with one power-of-two exponent per
+ * output row and one down-shift of 0..12 per block of 32 weights, in tile order, and decode steps of 1..8 tokens run
+ * them on the matrix cores (the codes widened to f16 by v_cvt_scalef32_pk_f16_fp4 into v_mfma_f32_16x16x32_f16 against
+ * the token rows as three f16 planes: DESIGN.md section 4.4.5).  The effective weights W4 = 2^(e_r - d_b) e2m1(code)
+ * are fp16 values and are written back over the layer's fp16 tables, so the result is the fp16 engine's on W4 up to
+ * summation order; activations are never quantised.  Other layers, prefill and larger batches run the fp16 kernels.
+ * DSOCR_EINVAL when no MoE layer fits.  Needs no snapshot.  dsocr_engine_load adds the flag when the environment has
+ * DSOCR_EXPERT_MXFP4 set to a non-zero value.  dsocr_engine_packed_mode / dsocr_engine_fp8_mode keep reporting 0. */
+#define DSOCR_LOAD_MXFP4_EXPERTS 32u
 dsocr_status dsocr_engine_load_flags(const dsocr_load_args* args, uint32_t flags, dsocr_engine** out);
 /* MoE layers that kept packed blocks, MoE layers in all, device bytes of the packed tables (any may be NULL) */
 dsocr_status dsocr_engine_packed_info(const dsocr_engine* e, size_t* packed_layers, size_t* moe_layers,
@@ -170,6 +182,8 @@ dsocr_status dsocr_engine_fp8_info(const dsocr_engine* e, size_t* fp8_layers, si
 dsocr_status dsocr_engine_kv_info(const dsocr_engine* e, int* elem_bytes, size_t* cache_bytes);
 /* How the engine was loaded: 0 fp16 experts, 1 FP8 experts, 2 FP8 experts with the matrix-core form at 3..8 tokens */
 dsocr_status dsocr_engine_fp8_mode(const dsocr_engine* e, int* mode);
+/* MoE layers that run the MXFP4 decode kernels, MoE layers in all, device bytes of the MXFP4 tables (any may be NULL) */
+dsocr_status dsocr_engine_fp4_info(const dsocr_engine* e, size_t* fp4_layers, size_t* moe_layers, size_t* fp4_bytes);
 void dsocr_engine_free(dsocr_engine* e);
 const char* dsocr_last_error(void);
 /* hidden size (image-row width), vocab, eos id, layers */
@@ -1056,6 +1070,25 @@ dsocr_status dsocr_k_moe_fp8_mm(int T, int H, int E, int topk, int I, int Is, co
                                 const void* router_f16, const void* Wgu_f16, const void* Wd_f16, const void* sWgu_f16,
                                 const void* sWd_f16, int norm_topk, float scaling, float* out, int* topk_ids_out,
                                 float* topk_w_out);
+/* Parity hooks of the MXFP4 experts (DSOCR_LOAD_MXFP4_EXPERTS; device pointers).
+ * dsocr_k_mxfp4_quantize_rows: fp16 rows [rows][cols] (cols % 32 == 0) to row-major E2M1 codes [rows][cols / 2] (low
+ * nibble = even k), one down-shift byte per block of 32 [rows][cols / 32] and one exponent per row (the load-time
+ * quantiser).  dsocr_k_mxfp4_mm_rows_dot: y[T][rows] = x[T][cols] . W4^T, W4[r][k] = 2^(exps[r] - shifts[r][k / 32])
+ * e2m1(codes[r][k]), through the tile-ordered copy (made inside; a ragged last row tile padded with zero codes), the
+ * f16 converts, the three-plane staging and the epilogue scales of the MoE launches (T <= 8, cols % 128 == 0, cols <=
+ * 1536).  dsocr_k_moe_mxfp4: dsocr_k_moe_fp8_mm's arguments; one decode MoE layer quantised from the fp16 tables and
+ * run through the MXFP4 launches at every T in 1..8; DSOCR_EINVAL when the shapes do not fit them. */
+dsocr_status dsocr_k_mxfp4_quantize_rows(size_t rows, size_t cols, const void* w_f16, uint8_t* codes_out, uint8_t* shifts_out,
+                                         int8_t* exps_out);
+/* the load-time write-back: W4 as fp16 [rows][cols] (exact) from what dsocr_k_mxfp4_quantize_rows wrote */
+dsocr_status dsocr_k_mxfp4_dequant_rows(size_t rows, size_t cols, const uint8_t* codes, const uint8_t* shifts, const int8_t* exps,
+                                        void* w4_f16_out);
+dsocr_status dsocr_k_mxfp4_mm_rows_dot(size_t rows, size_t cols, const uint8_t* codes, const uint8_t* shifts, const int8_t* exps,
+                                       int T, const float* x, float* y);
+dsocr_status dsocr_k_moe_mxfp4(int T, int H, int E, int topk, int I, int Is, const float* x, const float* norm_w, float eps,
+                               const void* router_f16, const void* Wgu_f16, const void* Wd_f16, const void* sWgu_f16,
+                               const void* sWd_f16, int norm_topk, float scaling, float* out, int* topk_ids_out,
+                               float* topk_w_out);
 /* Kernel names launch_moe_decode picks for a decode MoE of T tokens (static strings), e.g. the bench's
  * roofline label: "moe_gateup_mix_kernel" at T = 1, "moe_gateup_grp_kernel" at T = 3..8. */
 dsocr_status dsocr_k_moe_kernels(int T, int H, int E, int topk, int I, int Is, int has_norm, const char** gateup,
